@@ -8,8 +8,12 @@ A single suffix array does not shard; independent inputs d
 data-path collective, so N GPUs = N buffers (weak scaling) and
 value = total MB sorted / max-over-ranks time.
 
-    python bench.py [--gpus 1] [--steps K] [--warmup W]
+    python bench.py [--gpus 1] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+`--dump-outputs DIR` writes, after the timed steps, the suffix array the last timed step left in HBM as float64 .npy files
+(a fixed sample of positions once it is larger than the budget), so that two builds can be compared output for output:
+the inputs are generated from fixed seeds and are the same in every run with the same arguments.
 
 Prints ONE JSON line (rank 0).  Beside the contract's fields it carries
   roofline      the dominant kernel, measured live: every launch of it inside the timed region is
@@ -45,6 +49,8 @@ SEED_CONFIG1 = 0x5EED0002      # 64 MiB uniform
 SEED_ENWIK = 0xD17A0           # 256 MiB enwik-style text
 SEED_BATCH = 0x5EED0500        # + j, 128 x 16 MiB
 BATCH_COUNT, BATCH_BYTES = 128, 16 << 20
+SEED_DUMP = 0x5EED0D00         # positions of the --dump-outputs sample
+DUMP_VALUES = 1 << 21          # --dump-outputs: values per run, all ranks together (values + positions: 32 MiB of float64)
 
 
 def main() -> int:
@@ -69,11 +75,16 @@ def main() -> int:
                          "restatement with 64-bit indices on the 2 GiB buffer of configs[3] and bit-compare (SURVEY 8(d) Config 4)")
     ap.add_argument("--share-gpu", action="store_true",
                     help="plumbing test on a 1-GPU box: every rank uses cuda:0 (use with --backend gloo)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the suffix array of the last timed step as DIR/*.npy (float64, "
+                         "a fixed sample of positions when larger than %d values)" % DUMP_VALUES)
     args = ap.parse_args()
 
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # started as `python bench.py --gpus N` without a launcher: start the N ranks ourselves, as fresh child
         # processes, before this process has loaded the library or touched the GPU; relay their output (rank 0
@@ -179,6 +190,7 @@ def main() -> int:
     L.dq_profile_enable(0)
     prof = _abi.profile_snapshot()
     info = _abi.last_sort_info()
+    dumped = dump_outputs(args.dump_outputs, sa, rank, world) if args.dump_outputs else None
     prof_all, all_steps = {}, 3
     if not args.no_profile:
         L.dq_profile_reset()
@@ -239,6 +251,8 @@ def main() -> int:
             "roofline": roofline,
             "kernels_untimed_pass": kernels,
         }
+        if dumped is not None:
+            out["outputs_dumped"] = dumped
         if through_abi is not None:
             out["through_abi"] = through_abi
         if configs is not None:
@@ -327,6 +341,23 @@ def managed_reference_probe():
     rec["note"] = ("toolchain and reference checkout present: build bindings/csharp/DeltaQ.SuffixSorting.Hip.Tests against it and "
                    "run its benchmark harness (INTEGRATION.md section 2); not automated in bench.py")
     return rec
+
+
+def dump_outputs(out_dir, sa, rank, world):
+    """--dump-outputs: the suffix array the last timed step handed its caller, as float64 (exact for every index).  Each
+    rank has DUMP_VALUES / world values of the budget; a longer array is sampled at positions drawn from SEED_DUMP (the
+    same in every run with the same arguments), and the positions are written beside the values."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = sa.cpu().numpy()
+    tag = "" if world == 1 else f"_rank{rank}"
+    arrays = {f"suffix_array{tag}": host}
+    if host.size > DUMP_VALUES // world:
+        pos = np.unique(np.random.default_rng(SEED_DUMP).integers(0, host.size, DUMP_VALUES // world, dtype=np.int64))
+        arrays = {f"suffix_array{tag}": host[pos], f"suffix_array_positions{tag}": pos}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64))
+    return {"dir": out_dir, "files": sorted(name + ".npy" for name in arrays), "sampled": len(arrays) > 1}
 
 
 def kernel_table(snapshot, steps):
