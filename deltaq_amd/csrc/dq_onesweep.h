@@ -710,13 +710,26 @@ __device__ __forceinline__ void sample_kgrams(const uint8_t *__restrict__ text, 
     if (t < 8) coll[t] = (unsigned long long)cnt[t];
 }
 
+// Eighths of the text for the XCD-local first pass of the bucketed round 0 (dq_xcd_rank.h): eighth e is the text
+// positions [e E, (e + 1) E) with E = xcd_eighth(n), a whole number of that pass's tiles (so no tile straddles two),
+// a multiple of 16 bytes (so no 16-byte chunk of text_hist_kernel straddles two).  The last eighths of a short text
+// may be empty.
+constexpr int kXcds = 8;
+constexpr int kXcdTileN = 1024 * 12;
+__host__ __device__ inline int64_t xcd_eighth(int64_t n)
+{
+    const int64_t e = (n + kXcds - 1) / kXcds;
+    return (e + kXcdTileN - 1) / kXcdTileN * kXcdTileN;
+}
+
 // copy_out (round 5): the caller's device-resident text is read HERE for the first time -- the histogram pass also writes
 // the library's padded copy of it (16 bytes stored per 16 bytes loaded, behind LDS atomics that bound the kernel anyway)
 // instead of a device-to-device copy in front of the sort: 98 us of the 3.73 ms of a 256 MiB sort.
 static __global__ __launch_bounds__(kBlock) void text_hist_kernel(const uint8_t *__restrict__ text, int64_t n,
                                                            unsigned long long *__restrict__ bytehist /*[256], zeroed*/,
                                                            unsigned long long *__restrict__ kgram_coll = nullptr,
-                                                           uint8_t *__restrict__ copy_out = nullptr /* 16-byte aligned, or none */)
+                                                           uint8_t *__restrict__ copy_out = nullptr /* 16-byte aligned, or none */,
+                                                           unsigned long long *__restrict__ xcd_hist = nullptr /*[8][256], zeroed*/)
 {
     // 4 interleaved sub-histograms (hist[d][lane & 3]) spread equal bytes over 4 banks
     __shared__ uint32_t hist[kRadixSize * 4];
@@ -727,8 +740,20 @@ static __global__ __launch_bounds__(kBlock) void text_hist_kernel(const uint8_t 
     }
     const int tid = threadIdx.x;
     const int sub = tid & 3;
-    const int64_t nblocks = (int64_t)gridDim.x - (kgram_coll ? 1 : 0);          // workgroups that build the histogram
-    const int64_t hblock = (int64_t)blockIdx.x - (kgram_coll ? 1 : 0);
+    int64_t nblocks = (int64_t)gridDim.x - (kgram_coll ? 1 : 0);                // workgroups that build the histogram
+    int64_t hblock = (int64_t)blockIdx.x - (kgram_coll ? 1 : 0);
+    // xcd_hist: the byte histogram of every eighth of the text too (xcd_eighth).  The workgroups are then dealt out
+    // to the eighths (nblocks / 8 each: a multiple of 8 of them), so a workgroup adds into one eighth's counters only.
+    int64_t c0 = 0, c1 = n >> 4;                         // this workgroup's chunks
+    int eighth = 0;
+    if (xcd_hist) {
+        const int64_t per = nblocks / kXcds, ech = xcd_eighth(n) >> 4;
+        eighth = (int)(hblock / per);
+        c0 = std::min(c1, eighth * ech);
+        c1 = std::min(c1, c0 + ech);
+        hblock %= per;
+        nblocks = per;
+    }
     for (int i = tid; i < kRadixSize * 4; i += kBlock) hist[i] = 0;
     __syncthreads();
     const uint4 *t16 = reinterpret_cast<const uint4 *>(text);      // text is 16-byte aligned
@@ -736,7 +761,7 @@ static __global__ __launch_bounds__(kBlock) void text_hist_kernel(const uint8_t 
     bool long_run = false;
     unsigned long long flat_chunks = 0;                  // 16-byte chunks made of one byte value (wave-uniform count)
     uint4 *o16 = reinterpret_cast<uint4 *>(copy_out);
-    for (int64_t i = hblock * kBlock + tid; i < chunks; i += nblocks * kBlock) {
+    for (int64_t i = c0 + hblock * kBlock + tid; i < c1; i += nblocks * kBlock) {
         const uint4 v = t16[i];
         if (copy_out) o16[i] = v;
         const uint32_t wds[4] = {v.x, v.y, v.z, v.w};
@@ -752,26 +777,39 @@ static __global__ __launch_bounds__(kBlock) void text_hist_kernel(const uint8_t 
             for (int b = 0; b < 4; ++b) atomicAdd(&hist[(((wds[j] >> (8 * b)) & 0xff) << 2) | sub], 1u);
         }
     }
-    if (hblock == 0) {
+    if (hblock == 0 && eighth == 0) {
         for (int64_t i = (chunks << 4) + tid; i < n; i += kBlock) {
             const uint8_t b = text[i];
             if (copy_out) copy_out[i] = b;
             atomicAdd(&hist[((uint32_t)b << 2) | sub], 1u);
+            // (the last < 16 bytes lie in the last non-empty eighth, not in this workgroup's: moved there)
+            if (xcd_hist) {
+                atomicAdd(&xcd_hist[(i / xcd_eighth(n)) * kRadixSize + b], 1ull);
+                atomicAdd(&xcd_hist[b], ~0ull);
+            }
         }
     }
     __syncthreads();
     const uint32_t c = hist[tid * 4] + hist[tid * 4 + 1] + hist[tid * 4 + 2] + hist[tid * 4 + 3];
-    if (c) atomicAdd(&bytehist[tid], (unsigned long long)c);
+    if (c) {
+        atomicAdd(&bytehist[tid], (unsigned long long)c);
+        if (xcd_hist) atomicAdd(&xcd_hist[eighth * kRadixSize + tid], (unsigned long long)c);
+    }
     if (kgram_coll && long_run && lane_id() == 0) atomicOr(&kgram_coll[8], 1ull);      // (wave-uniform flag)
     // kgram_coll[9]: how much of the text lies in runs -- dq_runs.h pays where that is a good part of it
     if (kgram_coll && flat_chunks && lane_id() == 0) atomicAdd(&kgram_coll[9], flat_chunks);
 }
 
 // digit_offset[p][d] for p < kb (one workgroup per digit place p)
+// sub_offset (bucketed round 0, dq_xcd_rank.h): the region of digit d of place 0 cut into 8 sub-regions, one per
+// eighth of the text: sub_offset[e][d] = digit_offset[0][d] + the suffixes of eighths < e whose digit 0 is d.
+// (xcd_hist counts the bytes at the POSITIONS of an eighth; its suffixes' digits sit kb - 1 positions further on.)
 static __global__ __launch_bounds__(kBlock) void text_digit_offsets_kernel(const int64_t *__restrict__ bytehist,
                                                                     const uint8_t *__restrict__ text,
                                                                     int64_t n, int kb,
-                                                                    int64_t *__restrict__ digit_offset)
+                                                                    int64_t *__restrict__ digit_offset,
+                                                                    const int64_t *__restrict__ xcd_hist = nullptr /*[8][256]*/,
+                                                                    int64_t *__restrict__ sub_offset = nullptr /*[8][256]*/)
 {
     __shared__ int64_t tmp[kWavesPerBlock];
     const int p = blockIdx.x;
@@ -784,6 +822,21 @@ static __global__ __launch_bounds__(kBlock) void text_digit_offsets_kernel(const
     int64_t total;
     const int64_t excl = block_excl_sum(c, tmp, &total);
     digit_offset[p * kRadixSize + d] = excl;
+    if (sub_offset && p == 0) {
+        const int64_t E = xcd_eighth(n);
+        int64_t run = excl;
+        for (int e = 0; e < kXcds; ++e) {
+            sub_offset[e * kRadixSize + d] = run;
+            const int64_t s0 = (int64_t)e * E;
+            if (s0 >= n) continue;
+            const int64_t s1 = std::min(s0 + E, n);
+            // suffixes [s0, s1) have their digit at positions [s0 + off, s1 + off) (zero past the end)
+            int64_t ce = xcd_hist[e * kRadixSize + d];
+            for (int64_t j = s0; j < std::min(s0 + off, s1); ++j) ce -= (text[j] == d);
+            for (int64_t j = std::max(s0 + off, s1); j < s1 + off; ++j) ce += j < n ? (text[j] == d) : (d == 0);
+            run += ce;
+        }
+    }
 }
 
 }  // namespace dq

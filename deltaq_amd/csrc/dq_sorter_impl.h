@@ -31,6 +31,7 @@
 #include "dq_ties.h"
 #include "dq_isa_pairs.h"
 #include "dq_bucket_sort.h"
+#include "dq_xcd_rank.h"
 #include "dq_pair_chains.h"
 #include "dq_tail.h"
 #include "dq_split_round0.h"
@@ -70,7 +71,8 @@ struct Workspace {
     uint32_t *run_lead, *run_carry;   // per 4096-byte chunk
     uint8_t *run_link;
     int64_t *digit_offset;      // [8][256]
-    int64_t *bytehist;          // [256]
+    int64_t *bytehist;          // [256], then 16 words of k-gram sample and flags, then [8][256]: the bytes of each eighth
+    int64_t *xcd_offset;        // [8][256] sub-region starts of the XCD-local first pass (dq_xcd_rank.h)
     char *ctl_status;           // per digit pass: OnesweepCtl (256 B) + the tiles' status words
     size_t ctl_status_bytes;
     size_t ctl_status_stride;   // bytes per pass (set by prepare_status)
@@ -128,7 +130,9 @@ Workspace<IdxT> carve(char *base, int64_t n, bool with_sa)
         w.run_carry = (uint32_t *)take(nchunks * 4);
         w.run_link = (uint8_t *)take(nchunks);
     }
-    w.bytehist = (int64_t *)take((size_t)(kRadixSize + 16) * 8);       // + the 8 k-gram sample counters + the long-run flag
+    // + the 8 k-gram sample counters + the long-run flag, + the byte histograms of the text's eighths
+    w.bytehist = (int64_t *)take((size_t)(kRadixSize + 16 + kXcds * kRadixSize) * 8);
+    w.xcd_offset = (int64_t *)take((size_t)kXcds * kRadixSize * 8);
     // smallest tile is 8192 keys (2048 for lists of up to kSmallTileMaxM entries, see RankCfg); 8-byte status words
     // once a list reaches 2^30 entries
     w.ctl_status_bytes = (size_t)kMaxPasses * align_up(256 + status_tiles(un) * kRadixSize * (un >= (1ull << 30) ? 8 : 4));
@@ -408,6 +412,8 @@ bool split_round0_wanted(int64_t n, bool packed, int kb, bool coded)
     return n >= (64ll << 20);
 }
 
+constexpr int kXcdHistAt = kRadixSize + 16;          // words of w.bytehist in front of the eighths' histograms
+
 template <typename IdxT>
 int onesweep_sort_text_prepare(Launcher &L, DeviceCtx &c, Workspace<IdxT> &w, int64_t n, int *kb_out,
                                bool *packed_out, bool *coded_out, const uint8_t *text_src = nullptr, bool *hist_deferred = nullptr)
@@ -417,14 +423,19 @@ int onesweep_sort_text_prepare(Launcher &L, DeviceCtx &c, Workspace<IdxT> &w, in
     // 2048 / 4096 workgroups at 256 MiB: 165 / 131 / 139 / 143 us -- more waves hide more latency until the 256 global adds
     // each workgroup ends with pile up.  DQ_TEXT_HIST_BLOCKS tries other grids.)
     const int64_t hist_cap = env("DQ_TEXT_HIST_BLOCKS") ? std::max(1, std::min(8192, atoi(env("DQ_TEXT_HIST_BLOCKS")))) : 1024;
-    const int blocks = (int)std::min<int64_t>(hist_cap, ((n >> 4) + kBlock - 1) / kBlock + 1);
-    HIP_TRY(hipMemsetAsync(w.bytehist, 0, (256 + 10) * 8, L.st));
+    int blocks = (int)std::min<int64_t>(hist_cap, ((n >> 4) + kBlock - 1) / kBlock + 1);
+    // (texts the bucketed round 0 may take: the bytes of every eighth too, for its XCD-local first pass; the
+    // workgroups are then dealt out to the eighths evenly)
+    unsigned long long *xcd_hist = n >= (1 << 16) ? reinterpret_cast<unsigned long long *>(w.bytehist + kXcdHistAt) : nullptr;
+    if (xcd_hist) blocks = (blocks + kXcds - 1) / kXcds * kXcds;
+    HIP_TRY(hipMemsetAsync(w.bytehist, 0, (size_t)(kXcdHistAt + (xcd_hist ? kXcds * kRadixSize : 0)) * 8, L.st));
     // (+1 workgroup: the k-gram sample, whose 8 counters sit right behind the byte histogram: one readback)
     LAUNCH(L, DQ_K_TEXT_HIST, n, n,
            // (text_src: the caller's device buffer, not copied yet -- this pass reads it and fills w.text, see the kernel)
            hipLaunchKernelGGL(text_hist_kernel, dim3(blocks + 1), dim3(kBlock), 0, L.st,
                               text_src ? text_src : (const uint8_t *)w.text, n, reinterpret_cast<unsigned long long *>(w.bytehist),
-                              reinterpret_cast<unsigned long long *>(w.bytehist + 256), text_src ? w.text : (uint8_t *)nullptr));
+                              reinterpret_cast<unsigned long long *>(w.bytehist + 256), text_src ? w.text : (uint8_t *)nullptr,
+                              xcd_hist));
     int kb = 8;
     bool packed = false;
     HIP_TRY(hipMemcpyAsync(c.pinned, w.bytehist, (256 + 10) * 8, hipMemcpyDeviceToHost, L.st));
@@ -903,14 +914,35 @@ struct SuffixSorter {
         TieCounters *ctr = reinterpret_cast<TieCounters *>(w.totals + 6);     // zero since run()
         BucketFlags *flags = reinterpret_cast<BucketFlags *>(&ctr->overflow);
         const uint64_t *text64 = reinterpret_cast<const uint64_t *>(w.text);
+        // The first pass: persistent and XCD-local (dq_xcd_rank.h) -- its regions cut in 8 sub-regions by the byte
+        // histograms of the text's eighths that text_hist_kernel made -- or, with the extra key byte or under
+        // DQ_OLD_FIRST_PASS=1, radix_rank_kernel<kTextPacked(Ext)>.  The regions hold the same words either way.
+        const bool xcd_pass = !ext && !env("DQ_OLD_FIRST_PASS");
         // digit p of the bucket of suffix i is T[i + bbytes - 1 - p]
         hipLaunchKernelGGL(text_digit_offsets_kernel, dim3(bbytes), dim3(kBlock), 0, st,
-                           (const int64_t *)w.bytehist, (const uint8_t *)w.text, n, bbytes, w.digit_offset);
+                           (const int64_t *)w.bytehist, (const uint8_t *)w.text, n, bbytes, w.digit_offset,
+                           xcd_pass ? (const int64_t *)(w.bytehist + kXcdHistAt) : nullptr, xcd_pass ? w.xcd_offset : nullptr);
         HIP_TRY(hipGetLastError());
-        int rc = ext ? rank_pass_ext<IdxT, kTextPackedExt>(L, w, text64, (const uint8_t *)nullptr, K[1], E[1], n, 0, ib, ib + lowbits, keybits)
+        if (c.ncu <= 0) {
+            int v = 0;
+            c.ncu = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, c.dev) == hipSuccess && v > 0 ? v : 256;
+        }
+        int rc = DQ_OK;
+        if (xcd_pass) {
+            if (env("DQ_TRACE")) fprintf(stderr, "[dq] XCD-local first pass (n=%lld, eighths of %lld)\n", (long long)n, (long long)xcd_eighth(n));
+            // (its tickets and cursors: the look-back area of digit pass 0, zeroed by onesweep_sort_text_prepare)
+            if (sizeof(XcdRankCtl) > w.ctl_status_stride) return fail(DQ_ERR_HIP, "status buffer too small");
+            LAUNCH(L, DQ_K_RADIX_RANK, n, n * (1 + 8),                 // persistent: one workgroup per CU
+                   hipLaunchKernelGGL(xcd_text_rank_kernel, dim3((unsigned)std::min<int64_t>(c.ncu, (n + kXcdTileN - 1) / kXcdTileN)),
+                                      dim3(kXcdRankThreads), 0, st, reinterpret_cast<const uint32_t *>(w.text), K[1], n,
+                                      ib + lowbits, keybits, ib, (const int64_t *)w.xcd_offset,
+                                      reinterpret_cast<XcdRankCtl *>(w.ctl_status)));
+        } else {
+            rc = ext ? rank_pass_ext<IdxT, kTextPackedExt>(L, w, text64, (const uint8_t *)nullptr, K[1], E[1], n, 0, ib, ib + lowbits, keybits)
                      : rank_pass<IdxT, kTextPacked>(L, w, text64, (const IdxT *)nullptr, K[1], (IdxT *)nullptr, n, 0, kb, ib,
                                                     nullptr, nullptr, ib + lowbits, keybits);
-        if (rc != DQ_OK) return rc;
+            if (rc != DQ_OK) return rc;
+        }
         for (int p = 1; p < bbytes; ++p) {                   // pass p reads buffer p & 1 and writes the other
             rc = ext ? rank_pass_ext<IdxT, kKeysExt>(L, w, K[p & 1], E[p & 1], K[(p & 1) ^ 1], E[(p & 1) ^ 1], n, p, ib, ib + lowbits + 8 * p, keybits)
                      : rank_pass<IdxT, kKeys>(L, w, K[p & 1], (const IdxT *)nullptr, K[(p & 1) ^ 1], (IdxT *)nullptr, n, p, kb, ib,
@@ -922,10 +954,6 @@ struct SuffixSorter {
         LAUNCH(L, DQ_K_BUCKET_SORT, ntiles, ntiles * 16 * 8,
                hipLaunchKernelGGL(bucket_bounds_kernel, dim3((unsigned)((ntiles + 1 + kBlock - 1) / kBlock)), dim3(kBlock), 0,
                                   st, (const uint64_t *)Ks, n, ib + lowbits, C, X, ntiles, w.bkt_bounds, flags));
-        if (c.ncu <= 0) {
-            int v = 0;
-            c.ncu = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, c.dev) == hipSuccess && v > 0 ? v : 256;
-        }
         if (ext) {
             LAUNCH(L, DQ_K_BUCKET_SORT, n, n * (9 + wb) + n / 8,              // persistent: one workgroup per CU
                    hipLaunchKernelGGL((bucket_sort_kernel<IdxT, true>), dim3((unsigned)std::min<int64_t>(ntiles, c.ncu)),
