@@ -29,7 +29,7 @@ EXPORTS = (
     "dq_bsdiff_search_dev_i32", "dq_bsdiff_search_dev_i64", "dq_bsdiff_search_i32", "dq_bsdiff_search_i64",
     "dq_bsdiff_create", "dq_bsdiff_patch_bound", "dq_bsdiff_scan_i32", "dq_bspatch_apply",
     "dq_bsdiff_index_create", "dq_bsdiff_index_clone", "dq_bsdiff_index_buffers", "dq_bsdiff_index_diff", "dq_bsdiff_index_free",
-    "dq_sufsort_hip_workspace_bytes", "dq_sufsort_hip_release",
+    "dq_sufsort_hip_workspace_bytes", "dq_sufsort_hip_workspace_plan", "dq_sufsort_hip_release",
     "dq_profile_enable", "dq_profile_reset", "dq_profile_get", "dq_profile_kernel_name",
     "dq_profile_category_count",
     "dq_last_sort_info", "dq_last_diff_info", "dq_last_batch_info", "dq_device_numa_node",
@@ -122,6 +122,8 @@ def load() -> ctypes.CDLL:
     L.dq_bspatch_apply.argtypes = [vp, i64, vp, i64, vp, i64, ctypes.POINTER(i64)]
     L.dq_sufsort_hip_workspace_bytes.restype = i64
     L.dq_sufsort_hip_workspace_bytes.argtypes = [i64, i32]
+    L.dq_sufsort_hip_workspace_plan.restype = i64
+    L.dq_sufsort_hip_workspace_plan.argtypes = [i64, i32, i32, i64]
     L.dq_sufsort_hip_release.restype = None
     L.dq_sufsort_hip_release.argtypes = []
     L.dq_profile_enable.restype = i32

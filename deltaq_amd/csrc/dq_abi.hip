@@ -440,6 +440,14 @@ int64_t dq_sufsort_hip_workspace_bytes(int64_t n, int32_t index_bytes)
     return -1;
 }
 
+int64_t dq_sufsort_hip_workspace_plan(int64_t n, int32_t index_bytes, int32_t host_entry, int64_t avail_bytes)
+{
+    if (n < 0 || n > (1ll << 32) || (index_bytes == 4 && n > 0x7fffffffLL)) return -1;
+    if (index_bytes == 4) return sufsort_workspace_plan<int32_t>(n, host_entry != 0, avail_bytes);
+    if (index_bytes == 8) return sufsort_workspace_plan<int64_t>(n, host_entry != 0, avail_bytes);
+    return -1;
+}
+
 void dq_sufsort_hip_release(void)
 {
     int count = 0;

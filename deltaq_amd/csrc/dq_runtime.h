@@ -454,12 +454,15 @@ struct SortHints {
 template <typename IdxT> int sufsort_host(const uint8_t *text, int64_t n, IdxT *sa, int32_t device, SortHints hints = SortHints());
 template <typename IdxT> int sufsort_dev(const void *d_text, int64_t n, void *d_sa, int32_t device, void *stream);
 template <typename IdxT> int64_t sufsort_workspace_bytes(int64_t n);
+template <typename IdxT> int64_t sufsort_workspace_plan(int64_t n, bool host_entry, int64_t avail);
 extern template int sufsort_host<int32_t>(const uint8_t *, int64_t, int32_t *, int32_t, SortHints);
 extern template int sufsort_host<int64_t>(const uint8_t *, int64_t, int64_t *, int32_t, SortHints);
 extern template int sufsort_dev<int32_t>(const void *, int64_t, void *, int32_t, void *);
 extern template int sufsort_dev<int64_t>(const void *, int64_t, void *, int32_t, void *);
 extern template int64_t sufsort_workspace_bytes<int32_t>(int64_t);
 extern template int64_t sufsort_workspace_bytes<int64_t>(int64_t);
+extern template int64_t sufsort_workspace_plan<int32_t>(int64_t, bool, int64_t);
+extern template int64_t sufsort_workspace_plan<int64_t>(int64_t, bool, int64_t);
 
 // match search + BSDIFF40 (dq_diff.hip)
 int match_search_dev_i32(const void *d_old, int64_t n, const void *d_sa, const void *d_new, int64_t m, const int64_t *d_scans,

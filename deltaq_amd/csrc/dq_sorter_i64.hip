@@ -5,4 +5,5 @@ namespace dq {
 template int sufsort_host<int64_t>(const uint8_t *, int64_t, int64_t *, int32_t, SortHints);
 template int sufsort_dev<int64_t>(const void *, int64_t, void *, int32_t, void *);
 template int64_t sufsort_workspace_bytes<int64_t>(int64_t);
+template int64_t sufsort_workspace_plan<int64_t>(int64_t, bool, int64_t);
 }  // namespace dq

@@ -94,8 +94,9 @@ struct Workspace {
 // + 1024 entries per top bucket) must fit a quarter of the suffix array
 constexpr int64_t kSplitMinN = 5ll << 20;
 
+// lists: carve the third list buffer (X, Xs) -- see with_list_buffers()
 template <typename IdxT>
-Workspace<IdxT> carve(char *base, int64_t n, bool with_sa)
+Workspace<IdxT> carve(char *base, int64_t n, bool with_sa, bool lists)
 {
     Workspace<IdxT> w{};
     size_t off = 0;
@@ -111,8 +112,8 @@ Workspace<IdxT> carve(char *base, int64_t n, bool with_sa)
     w.SAbuf = with_sa ? (IdxT *)take(un * sizeof(IdxT)) : nullptr;
     // (n > 2^32 is refused before anything is allocated; texts of more than n/2 tied suffixes after round 0 -- real
     // binaries -- take their first doubling rounds through the LDS class too, whose three output lists then need a
-    // buffer of their own: +12 n / +16 n bytes of a 288 GB device)
-    if (un < (1ull << 32)) {            // (exactly 2^32 bytes: no small-group rounds, uses_small_round())
+    // buffer of their own: +12 n / +16 n bytes.  Without it such lists take the radix rounds, uses_small_round())
+    if (lists) {
         w.X = (uint64_t *)take((un + 2) * 8);
         w.Xs = (IdxT *)take((un + 2) * sizeof(IdxT));
     }
@@ -157,6 +158,21 @@ Workspace<IdxT> carve(char *base, int64_t n, bool with_sa)
     }
     w.bytes = off;
     return w;
+}
+
+// Device memory a sort leaves to the runtime and to whatever else the process allocates meanwhile
+constexpr uint64_t kWsReserve = 1ull << 30;
+
+// The layout of a sort of n bytes, from what fits: the third list buffer (X, Xs) is carved only where the whole
+// workspace, with it, fits the `avail` bytes of device memory the sort may take (the cached workspace included).
+// int64 indices take 59 B per text byte with it, 43 B without (+ 8 B for the host entry point's SAbuf): near 2^32
+// the full layout would not fit a 288 GB device, the reduced one does.  Exactly 2^32 bytes never carve it (its
+// rounds are all radix rounds, see fits32()).  A pure host function: tested on the CPU through
+// dq_sufsort_hip_workspace_plan.
+template <typename IdxT>
+bool with_list_buffers(int64_t n, bool with_sa, uint64_t avail)
+{
+    return n < (1ll << 32) && carve<IdxT>(nullptr, n, with_sa, true).bytes <= avail;
 }
 
 
@@ -771,11 +787,16 @@ struct SuffixSorter {
     //      tied list is (P1, Va) and m its length.
     // (wide: a list of more than n/2 entries -- the output lists of its round do not fit beside each other in the
     // partner buffers, see round_layout(); DQ_NO_WIDE_SMALL=1: such lists take the radix path as before round 5)
+    // (without the third list buffer -- with_list_buffers() -- wide lists take the radix path too)
     bool wide_list(int64_t mm) const { return mm * 2 > n; }
     bool uses_small_round(int64_t mm) const
     {
-        return !env("DQ_NO_SMALL") && n < (1ll << 32) && (!wide_list(mm) || !env("DQ_NO_WIDE_SMALL"));
+        return !env("DQ_NO_SMALL") && fits32() && (!wide_list(mm) || (w.X && !env("DQ_NO_WIDE_SMALL")));
     }
+    // Exactly 2^32 bytes: ranks and suffixes no longer fit 32 bits, and from h = 1 on every doubling round keys on
+    // rank >> 1 (kbits = 33), which only the radix round does.  The LDS-class rounds (whose chains clamp key2 to
+    // 64 - rbits bits), the pair chains and the tail kernel (32-bit ranks and suffixes, dq_tail.h) stay off there.
+    bool fits32() const { return n < (1ll << 32); }
 
     int build_isa_binned(uint64_t *keys, uint64_t *P0, int kb, int kshift0)
     {
@@ -1640,6 +1661,7 @@ struct SuffixSorter {
         TailResult *res = reinterpret_cast<TailResult *>(w.sg_ctr + kSgChain);
         const bool spec_tail = tail_behind_chain;
         if (spec_tail) {
+            if (env("DQ_TRACE")) fprintf(stderr, "[dq] tail kernel launched behind a chain of %d at h=%lld\n", chain_len, (long long)hr);
             LAUNCH(L, DQ_K_SMALL_ROUND, m_in, 0,
                    launch_tail((const uint64_t *)Kr[rcur], (const IdxT *)Vr[rcur], (int)0, hr, res,
                                (const unsigned long long *)&w.sg_ctr[chain_len - 1].tied_moved));
@@ -1880,6 +1902,9 @@ struct SuffixSorter {
         int rc = round0(&dense_built);
         if (rc != DQ_OK) return rc;
         t_info[1] = m;
+        if (env("DQ_TRACE"))
+            fprintf(stderr, "[dq] after round 0: n=%lld, %d index bits, %lld tied suffixes, third list buffer %s\n", (long long)n,
+                    bit_length((uint64_t)(n - 1)), (long long)m, w.X ? "carved" : "left out");
         if (m == 0) return flush_profile(c);
 
         bool sparse = m * 6 <= n || shallow_ties;
@@ -1920,7 +1945,7 @@ struct SuffixSorter {
         // (DQ_TAIL_MAX = 0 ... 4096: the list length from which the rest of the sort is one launch; 0 = never)
         const int64_t tail_max = env("DQ_TAIL_MAX") ? std::max(0, std::min(kTailMax, atoi(env("DQ_TAIL_MAX")))) : kTailMax;
         while (m > 0) {
-            if (m <= tail_max && n < (1ll << 32) && !keys_ready && !list_ungrouped && !first_rank32 && !run_order) {
+            if (m <= tail_max && fits32() && !keys_ready && !list_ungrouped && !first_rank32 && !run_order) {
                 rc = tail_rounds();
                 if (rc != DQ_OK) return rc;
                 break;
@@ -1944,7 +1969,7 @@ struct SuffixSorter {
                                  : m_before > 0 && m >= pair_chain_min && after_abort &&
                                    (pair_tries == 0 || (pair_paid ? stagnant : h >= 16 * pair_h));
             const int max_tries = env("DQ_PAIR_TRIES") ? atoi(env("DQ_PAIR_TRIES")) : kPairChainTries;
-            if (want && pair_tries < max_tries && pair_aborts < 2 * kPairChainTries && !env("DQ_NO_SMALL") && n < (1ll << 32) &&
+            if (want && pair_tries < max_tries && pair_aborts < 2 * kPairChainTries && !env("DQ_NO_SMALL") && fits32() &&
                 m < n && !keys_ready && !list_ungrouped && !first_rank32) {
                 int outcome = 0;
                 m_before = 0;
@@ -1994,7 +2019,7 @@ struct SuffixSorter {
             // (doubled text: a look at the pairs after every round while the list is long)
             if (only_small_groups && uses_small_round(m) && !keys_ready && !list_ungrouped && (twin_half == 0 || m < (1 << 16)) &&
                 !env("DQ_NO_CHAIN")) {
-                tail_behind_chain = tail_max >= kTailMax && m <= 4 * tail_max && n < (1ll << 32);      // (the kernel's own bound is kTailMax)
+                tail_behind_chain = tail_max >= kTailMax && m <= 4 * tail_max && fits32();      // (the kernel's own bound is kTailMax)
                 // (two rounds, then four, then eight per host round trip: a list that hovers just above the tail
                 // kernel's reach -- a long repeat among a few thousand suffixes -- must not pay a round trip every two rounds)
                 chain_len = tail_behind_chain ? std::min(kSgChain, 2 << std::min(spec_misses, 2)) : kSgChain;
@@ -2016,6 +2041,9 @@ struct SuffixSorter {
             const int rshift = (kbits + rbits > 64 || (env("DQ_FORCE_RSHIFT") && !first_rank32)) ? 1 : 0;
             if (rshift && first_rank32) return fail(DQ_ERR_HIP, "rank-shift round on a list with 32-bit ranks");
             if (kbits + rbits - rshift > 64) return fail(DQ_ERR_TOO_LARGE, "composite key exceeds 64 bits");
+            if (rshift && env("DQ_TRACE"))
+                fprintf(stderr, "[dq] rank-shift round at h=%lld on %lld tied suffixes (kbits %d + rbits %d)%s\n", (long long)h,
+                        (long long)m, kbits, rbits, kbits + rbits > 64 ? "" : " (forced)");
             if (rshift && keys_ready) {
                 // the list came keyed from build_isa_binned() (rank << kbits | key2, unshifted): take the group
                 // ranks back out of the keys and let the round gather its own, shifted ones
@@ -2054,6 +2082,25 @@ int sufsort_small(DeviceCtx &c, hipStream_t st, const uint8_t *text, int64_t n, 
            hipLaunchKernelGGL(small_sufsort_kernel<IdxT>, dim3(1), dim3(kSmallThreads), 0, st, text, (int)n, sa));
     HIP_TRY(hipStreamSynchronize(st));
     return flush_profile(c);
+}
+
+// with_list_buffers() on this device: the memory a sort may take is what is free plus the cached workspace, which
+// ensure_ws() gives back before it allocates a larger one.  (A cached workspace that already holds the full layout
+// asks the driver nothing.)  DQ_NO_LIST_BUFFERS=1: the reduced layout at any n (tests).
+template <typename IdxT>
+bool choose_list_buffers(DeviceCtx &c, int64_t n, bool with_sa)
+{
+    bool lists = n < (1ll << 32) && !env("DQ_NO_LIST_BUFFERS");
+    size_t free_b = 0, total_b = 0;
+    if (lists && c.ws_bytes < carve<IdxT>(nullptr, n, with_sa, true).bytes && hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+        // (where the driver cannot say, the allocation decides, as before)
+        const uint64_t avail = (uint64_t)free_b + c.ws_bytes;
+        lists = with_list_buffers<IdxT>(n, with_sa, avail > kWsReserve ? avail - kWsReserve : 0);
+    }
+    if (env("DQ_TRACE") && !lists)
+        fprintf(stderr, "[dq] workspace without the third list buffer (n=%lld; %.1f GB free, %.1f GB cached)\n", (long long)n,
+                free_b / 1e9, c.ws_bytes / 1e9);
+    return lists;
 }
 
 template <typename IdxT>
@@ -2101,10 +2148,11 @@ int sufsort_host(const uint8_t *text, int64_t n, IdxT *sa, int32_t device, SortH
         memcpy(sa, io_sa, (size_t)n * sizeof(IdxT));
         return DQ_OK;
     }
-    Workspace<IdxT> w = carve<IdxT>(nullptr, n, true);
+    const bool lists = choose_list_buffers<IdxT>(c, n, true);
+    Workspace<IdxT> w = carve<IdxT>(nullptr, n, true, lists);
     rc = ensure_ws(c, w.bytes);
     if (rc != DQ_OK) return rc;
-    w = carve<IdxT>(c.ws, n, true);
+    w = carve<IdxT>(c.ws, n, true, lists);
     hipStream_t st = c.stream;
     // The caller's buffers are ordinary pageable memory; the runtime's staged copies already run
     // at PCIe rate here (page-locking them per call with hipHostRegister measured no gain).
@@ -2142,10 +2190,11 @@ int sufsort_dev(const void *d_text, int64_t n, void *d_sa, int32_t device, void 
         if (rc != DQ_OK) drop_pending(c, sst);
         return rc;
     }
-    Workspace<IdxT> w = carve<IdxT>(nullptr, n, false);
+    const bool lists = choose_list_buffers<IdxT>(c, n, false);
+    Workspace<IdxT> w = carve<IdxT>(nullptr, n, false, lists);
     rc = ensure_ws(c, w.bytes);
     if (rc != DQ_OK) return rc;
-    w = carve<IdxT>(c.ws, n, false);
+    w = carve<IdxT>(c.ws, n, false, lists);
     hipStream_t st = stream ? (hipStream_t)stream : c.stream;
     // The library works on a padded, 16-byte aligned copy of the text.  The copy is made by the pass that reads the
     // text first anyway (text_hist_kernel) when the caller's buffer is 16-byte aligned; DQ_TEXT_COPY=1: by a copy in front.
@@ -2158,6 +2207,10 @@ int sufsort_dev(const void *d_text, int64_t n, void *d_sa, int32_t device, void 
     return DQ_OK;
 }
 
-template <typename IdxT> int64_t sufsort_workspace_bytes(int64_t n) { return (int64_t)carve<IdxT>(nullptr, n, false).bytes; }
+template <typename IdxT> int64_t sufsort_workspace_bytes(int64_t n) { return (int64_t)carve<IdxT>(nullptr, n, false, n < (1ll << 32)).bytes; }
+template <typename IdxT> int64_t sufsort_workspace_plan(int64_t n, bool host_entry, int64_t avail)
+{
+    return (int64_t)carve<IdxT>(nullptr, n, host_entry, with_list_buffers<IdxT>(n, host_entry, (uint64_t)std::max<int64_t>(avail, 0))).bytes;
+}
 
 }  // namespace dq

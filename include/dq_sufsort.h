@@ -52,7 +52,11 @@ int32_t dq_sufsort_hip_i32(const uint8_t *text, int64_t n, int32_t *sa, int32_t 
 /* Same contract with 64-bit indices, for inputs beyond ISuffixSort's int limit: 2^31 <= n <= 2^32
  * bytes (any n is accepted up to that).  n > 2^32 returns DQ_ERR_TOO_LARGE before any device work:
  * a doubling round sorts (rank, rank of the suffix h bytes on) as one 64-bit word, 32 + 32 bits at
- * most, and the workspace of ~42 n bytes would not fit 288 GB much beyond that anyway. */
+ * most.  Device workspace per text byte: 59 B with the third list buffer of the doubling rounds, 43 B
+ * without it (int32 indices: 47 B / 35 B); the host entry points add n * index width for their device
+ * copy of sa.  The buffer is left out where the whole workspace would not fit the free device memory
+ * (and always at n = 2^32): any accepted n then fits one 288 GB MI355X (the reduced host-entry layout
+ * is 219 GB at most). */
 int32_t dq_sufsort_hip_i64(const uint8_t *text, int64_t n, int64_t *sa, int32_t device);
 
 /* ---- device-resident variant: text and sa are device pointers on `device` ----------------------
@@ -148,8 +152,13 @@ int32_t dq_bspatch_apply(const uint8_t *old_data, int64_t n, const uint8_t *patc
                          int64_t cap, int64_t *out_len);
 
 /* Device workspace (bytes) a sort of n bytes with index_bytes (4 or 8) wide indices needs,
- * excluding the caller's text and sa buffers. */
+ * excluding the caller's text and sa buffers: the device entry point's full layout (the reduced one at n = 2^32). */
 int64_t dq_sufsort_hip_workspace_bytes(int64_t n, int32_t index_bytes);
+/* The workspace a sort of n bytes carves when avail_bytes of device memory are left to it (free memory plus the
+ * cached workspace, less a reserve of 1 GiB): the full layout if that fits, else the one without the third list
+ * buffer.  host_entry != 0: the host entry points' layout (+ n * index_bytes for the device copy of sa).  The result
+ * may exceed avail_bytes (the allocation then fails with DQ_ERR_OOM).  -1: bad arguments, or n beyond the index width. */
+int64_t dq_sufsort_hip_workspace_plan(int64_t n, int32_t index_bytes, int32_t host_entry, int64_t avail_bytes);
 /* Free every cached device workspace / pinned staging buffer / stream. */
 void dq_sufsort_hip_release(void);
 

@@ -193,12 +193,24 @@ def sufcheck(text, sa) -> int:
     return int(getattr(lib(), f"dq_oracle_sufcheck_{_suf(sa)}")(_ptr(T), T.size, _ptr(sa), sa.size))
 
 
+def default_threads() -> int:
+    """Threads of the threaded checker: OMP_NUM_THREADS where it is set, else at most 16 (os.cpu_count() reports the
+    whole host, which a job that may use a share of it must not size itself by)."""
+    try:
+        v = int(os.environ.get("OMP_NUM_THREADS", ""))
+        if v > 0:
+            return v
+    except ValueError:
+        pass
+    return max(1, min(16, os.cpu_count() or 1))
+
+
 def sufcheck_mt(text, sa, threads: int = 0) -> int:
     """LDSSChecker.Check evaluated by several threads (full-size configurations); same codes."""
     T = _text(text)
     sa = np.ascontiguousarray(sa)
     if threads <= 0:
-        threads = min(64, os.cpu_count() or 1)
+        threads = default_threads()
     return int(getattr(lib(), f"dq_oracle_sufcheck_mt_{_suf(sa)}")(_ptr(T), T.size, _ptr(sa), sa.size, threads))
 
 

@@ -38,6 +38,53 @@ def test_workspace_query(backend_lib):
     assert 52 * n <= b8 < 53 * n + (16 << 20)      # 36 + 16
     assert backend_lib.dq_sufsort_hip_workspace_bytes(n, 3) == -1
     assert backend_lib.dq_sufsort_hip_workspace_bytes(-5, 4) == -1
+    # int64 on both sides of 2^32: 59 B per byte with the third list buffer (X, Xs) just below, 43 B at exactly 2^32,
+    # which never carves it
+    below, at = (1 << 32) - 1, 1 << 32
+    assert 59 * below <= backend_lib.dq_sufsort_hip_workspace_bytes(below, 8) < 59.05 * below
+    assert 43 * at <= backend_lib.dq_sufsort_hip_workspace_bytes(at, 8) < 43.05 * at
+    assert 47 * INT_MAX <= backend_lib.dq_sufsort_hip_workspace_bytes(INT_MAX, 4) < 47.05 * INT_MAX
+
+
+INT_MAX = (1 << 31) - 1
+HBM = 288 * 10**9 - (2 << 30)          # an MI355X (288 GB) less 2 GiB for the runtime and whatever else is resident
+
+
+def test_workspace_plan_fits_every_length(backend_lib):
+    """The layout a sort carves is chosen from what fits (dq_sufsort_hip_workspace_plan, the host function the entry
+    points call with the device's free memory): the full layout where it fits, otherwise the one without the third
+    list buffer.  For every n the 64-bit contract accepts, and every int32 n, the chosen workspace plus the caller's
+    device buffers must fit one MI355X -- through the host entry (workspace + the device copy of sa) and through the
+    device entry (workspace + the caller's text and sa)."""
+    plan = backend_lib.dq_sufsort_hip_workspace_plan
+    lengths = sorted({(1 << 31) + 1, 3 << 30, 4_030_000_000, 4_200_000_000, (1 << 32) - 1, 1 << 32} |
+                     {int(x) for x in np.linspace(1 << 20, 1 << 32, 4097)})
+    for n in lengths:
+        for wb, host in ((8, 1), (8, 0), (4, 1), (4, 0)):
+            if wb == 4 and n > INT_MAX:
+                continue
+            caller = 0 if host else n + wb * n
+            avail = HBM - caller
+            got = plan(n, wb, host, avail)
+            assert 0 < got <= avail, (n, wb, host, got, avail)
+            full = plan(n, wb, host, 1 << 62)
+            reduced = plan(n, wb, host, 0)
+            assert got == (full if full <= avail else reduced), (n, wb, host)
+            # the reduced layout is the full one without X / Xs: (n + 2) list entries of 8 + wb bytes, aligned
+            if n < (1 << 32):
+                assert 0 < full - reduced - (n + 2) * (8 + wb) < 1024, (n, wb, host)
+            else:
+                assert full == reduced
+            assert plan(n, wb, 0, 1 << 62) == backend_lib.dq_sufsort_hip_workspace_bytes(n, wb)
+            assert plan(n, wb, 1, 1 << 62) - plan(n, wb, 0, 1 << 62) >= wb * n        # the host entry's SAbuf
+    # just below 2^32 only the reduced layout fits; it is chosen there, and the full one where it fits
+    n = (1 << 32) - 1
+    assert plan(n, 8, 1, 1 << 62) > HBM >= plan(n, 8, 1, HBM)
+    assert plan(3 << 30, 8, 1, HBM) == plan(3 << 30, 8, 1, 1 << 62)
+    assert plan((1 << 32) + 1, 8, 1, HBM) == -1
+    assert plan(1 << 31, 4, 1, HBM) == -1
+    assert plan(1 << 20, 3, 1, HBM) == -1
+    assert plan(-1, 8, 1, HBM) == -1
 
 
 def test_argument_validation_precedes_device_use(backend_lib):
@@ -49,6 +96,12 @@ def test_argument_validation_precedes_device_use(backend_lib):
     assert backend_lib.dq_sufsort_hip_i32(buf.ctypes.data, 8, None, 0) == _abi.DQ_ERR_BAD_ARGS
     assert backend_lib.dq_sufsort_hip_i32(buf.ctypes.data, 1 << 31, sa.ctypes.data, 0) == _abi.DQ_ERR_TOO_LARGE
     assert b"2^31" in backend_lib.dq_last_error()
+    # the 64-bit entry points take n <= 2^32: one byte more is refused before the device is even looked for
+    sa8 = np.zeros(8, np.int64)
+    for fn in (lambda: backend_lib.dq_sufsort_hip_i64(buf.ctypes.data, (1 << 32) + 1, sa8.ctypes.data, 0),
+               lambda: backend_lib.dq_sufsort_hip_dev_i64(buf.ctypes.data, (1 << 32) + 1, sa8.ctypes.data, 0, None)):
+        assert fn() == _abi.DQ_ERR_TOO_LARGE
+        assert b"2^32" in backend_lib.dq_last_error()
     assert backend_lib.dq_sufsort_hip_batch_i32(-1, None, None, None, 1, None) == _abi.DQ_ERR_BAD_ARGS
     assert backend_lib.dq_sufsort_hip_batch_i32(0, None, None, None, 1, None) == _abi.DQ_OK
 

@@ -584,7 +584,18 @@ def test_every_code_path_is_bit_exact(ldss, oracle_mod, monkeypatch, env):
     monkeypatch.setenv("DQ_SMALL_N", "0")
     for k, v in env.items():
         monkeypatch.setenv(k, v)
-    cases = [
+    cases = forced_path_cases(oracle_mod)
+    for T in cases:
+        T = np.ascontiguousarray(T, dtype=np.uint8)
+        SA = ldss.Sort(T)
+        assert np.array_equal(SA, oracle_mod.divsufsort(T)), (env, T.size)
+    T = oracle_mod.gen_uniform(1_000_003, 7)
+    assert np.array_equal(ldss.Sort(T, index_dtype=np.int64), oracle_mod.divsufsort(T).astype(np.int64))
+
+
+def forced_path_cases(oracle_mod):
+    """The structured inputs every forced path of the sorter is run on."""
+    return [
         load_asset("crash-04dc74e45e66386a3312a5a5825b020bcadc175c"),
         load_asset("fuzz3"),
         oracle_mod.gen_uniform(3_000_000, 0x5EED0002),
@@ -595,12 +606,36 @@ def test_every_code_path_is_bit_exact(ldss, oracle_mod, monkeypatch, env):
         np.zeros(70_001, np.uint8),
         oracle_mod.net_random_bytes(8193),
     ]
-    for T in cases:
+
+
+# the workspace without the third list buffer (X, Xs), which texts just below 2^32 bytes get where the full layout does
+# not fit the device: lists of more than n/2 tied suffixes then take the radix rounds, and round 0 the plain passes
+REDUCED_LAYOUT = [
+    {"DQ_NO_LIST_BUFFERS": "1"},
+    {"DQ_NO_LIST_BUFFERS": "1", "DQ_PACKED": "0", "DQ_KEY_BYTES": "2", "DQ_SPARSE": "0", "DQ_TAIL_MAX": "0"},   # wide lists
+    {"DQ_NO_LIST_BUFFERS": "1", "DQ_PACKED": "0", "DQ_KEY_BYTES": "1", "DQ_SPARSE": "0", "DQ_BINNED_ISA": "1", "DQ_TAIL_MAX": "0"},
+    {"DQ_NO_LIST_BUFFERS": "1", "DQ_SPLIT": "2", "DQ_PACKED": "0"},                  # the sample-sort round 0 needs X: plain passes
+]
+
+
+@pytest.mark.parametrize("index_dtype", [np.int32, np.int64], ids=["i32", "i64"])
+@pytest.mark.parametrize("env", REDUCED_LAYOUT, ids=lambda e: ",".join(f"{k[3:]}={v}" for k, v in e.items()))
+def test_reduced_layout_is_bit_exact(ldss, oracle_mod, monkeypatch, capfd, env, index_dtype):
+    """The structured inputs of test_every_code_path_is_bit_exact on the reduced workspace layout, both index widths,
+    bit for bit against the LibDivSufSort restatement; the trace shows the layout was the reduced one."""
+    monkeypatch.setenv("DQ_SMALL_N", "0")
+    monkeypatch.setenv("DQ_TRACE", "1")
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    for T in forced_path_cases(oracle_mod) + [oracle_mod.gen_uniform(6 << 20, 0x5EED0009)]:
         T = np.ascontiguousarray(T, dtype=np.uint8)
-        SA = ldss.Sort(T)
-        assert np.array_equal(SA, oracle_mod.divsufsort(T)), (env, T.size)
-    T = oracle_mod.gen_uniform(1_000_003, 7)
-    assert np.array_equal(ldss.Sort(T, index_dtype=np.int64), oracle_mod.divsufsort(T).astype(np.int64))
+        capfd.readouterr()
+        SA = ldss.Sort(T, index_dtype=index_dtype)
+        err = capfd.readouterr().err
+        assert SA.dtype == index_dtype
+        assert np.array_equal(SA, oracle_mod.divsufsort(T).astype(index_dtype)), (env, T.size)
+        assert "without the third list buffer" in err, err[-2000:]
+        assert "(wide)" not in err, err[-2000:]            # no LDS-class round over a list of more than n/2 entries
 
 
 @pytest.mark.parametrize("env", [{"DQ_UPD_WINDOW": "1"}, {"DQ_UPD_BIN": "1", "DQ_UPD_BIN_MIN": "1"}, {"DQ_UPD_BIN": "2", "DQ_UPD_BIN_MIN": "1"}],

@@ -196,3 +196,18 @@ def test_prefix_doubling_model_matches_oracle(oracle_mod):
         assert np.array_equal(pd_model.suffix_array(T), oracle_mod.divsufsort(T))
     for T in (np.zeros(65, np.uint8), np.array([5, 0, 0, 5, 0, 7, 5, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 5, 0], np.uint8)):
         assert np.array_equal(pd_model.suffix_array(T), oracle_mod.naive_sa(T))
+
+
+def test_threaded_checker_sizes_itself_by_the_job(oracle_mod, monkeypatch):
+    """sufcheck_mt's default thread count: OMP_NUM_THREADS where the job sets it, otherwise at most 16 -- never the
+    whole host's cpu_count()."""
+    monkeypatch.setenv("OMP_NUM_THREADS", "7")
+    assert oracle_mod.default_threads() == 7
+    monkeypatch.delenv("OMP_NUM_THREADS")
+    assert 1 <= oracle_mod.default_threads() <= 16
+    monkeypatch.setattr(oracle_mod.os, "cpu_count", lambda: 384)
+    assert oracle_mod.default_threads() == 16
+    monkeypatch.setenv("OMP_NUM_THREADS", "x")
+    assert oracle_mod.default_threads() == 16
+    T = oracle_mod.gen_uniform(100_000, 3)
+    assert oracle_mod.sufcheck_mt(T, oracle_mod.divsufsort(T)) == oracle_mod.CHECK_DONE
