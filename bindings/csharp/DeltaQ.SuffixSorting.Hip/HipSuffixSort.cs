@@ -26,6 +26,12 @@ public sealed class HipSuffixSort : ISuffixSort
     private static extern unsafe int dq_sufsort_hip_i32(byte* text, long n, int* sa, int device);
 
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    private static extern unsafe int dq_sufcheck_hip_i32(byte* text, long n, int* sa, long saLen, int* result, int device);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    private static extern unsafe int dq_sufcheck_hip_i64(byte* text, long n, long* sa, long saLen, int* result, int device);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
     private static extern int dq_abi_version();
 
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
@@ -133,5 +139,58 @@ public sealed class HipSuffixSort : ISuffixSort
         throw new InvalidOperationException($"dq_sufsort_hip_i32 failed ({rc}): {msg}");
     }
 
+    /// <summary>
+    /// <c>LDSSChecker.Check(T, SA)</c> (test/DeltaQ.SuffixSorting.LibDivSufSort.Tests/LDSSChecker.cs:23-119) on the
+    /// device: the same verdict for every text and array, lengths that differ and out-of-range entries included.
+    /// A failure of the native call (no device, out of device memory) throws <see cref="InvalidOperationException"/>;
+    /// there is no managed fallback for the check.
+    /// </summary>
+    public unsafe SuffixCheckResult Check(ReadOnlySpan<byte> text, ReadOnlySpan<int> suffixes)
+    {
+        int rc, result = 0;
+        fixed (byte* pText = text)
+        fixed (int* pSa = suffixes)
+        {
+            rc = dq_sufcheck_hip_i32(pText, text.Length, pSa, suffixes.Length, &result, _device);
+        }
+
+        return CheckResult(rc, result, "dq_sufcheck_hip_i32");
+    }
+
+    /// <summary>The same check of a 64-bit suffix array (texts of up to 2^32 bytes).</summary>
+    public unsafe SuffixCheckResult Check(ReadOnlySpan<byte> text, ReadOnlySpan<long> suffixes)
+    {
+        int rc, result = 0;
+        fixed (byte* pText = text)
+        fixed (long* pSa = suffixes)
+        {
+            rc = dq_sufcheck_hip_i64(pText, text.Length, pSa, suffixes.Length, &result, _device);
+        }
+
+        return CheckResult(rc, result, "dq_sufcheck_hip_i64");
+    }
+
+    private static SuffixCheckResult CheckResult(int rc, int result, string entry)
+    {
+        if (rc != 0)
+        {
+            string msg = Marshal.PtrToStringAnsi(dq_last_error()) ?? string.Empty;
+            throw new InvalidOperationException($"{entry} failed ({rc}): {msg}");
+        }
+
+        return (SuffixCheckResult)result;
+    }
+
     private static void ThrowHelper() => throw new ArgumentException("Text and suffix buffers should have the same length");
+}
+
+/// <summary>The verdicts of <see cref="HipSuffixSort.Check(ReadOnlySpan{byte}, ReadOnlySpan{int})"/>: LDSSChecker.ResultCode
+/// (LDSSChecker.cs:11-18), value for value.</summary>
+public enum SuffixCheckResult
+{
+    Done = 0,
+    BadArguments = -1,
+    OutOfRange = -2,
+    WrongOrder = -3,
+    WrongPosition = -4,
 }

@@ -18,6 +18,13 @@ DQ_ERR_HIP = -3
 DQ_ERR_TOO_LARGE = -4
 DQ_ERR_NO_DEVICE = -5
 
+# LDSSChecker.ResultCode: the verdicts of dq_sufcheck_hip_* (written to *result, not returned)
+DQ_SUFCHECK_DONE = 0
+DQ_SUFCHECK_BAD_ARGUMENTS = -1
+DQ_SUFCHECK_OUT_OF_RANGE = -2
+DQ_SUFCHECK_WRONG_ORDER = -3
+DQ_SUFCHECK_WRONG_POSITION = -4
+
 K_RADIX_RANK = 2          # DQ_K_RADIX_RANK: the dominant kernel's profile category
 
 # every symbol include/dq_sufsort.h declares
@@ -26,6 +33,7 @@ EXPORTS = (
     "dq_sufsort_hip_i32", "dq_sufsort_hip_i64",
     "dq_sufsort_hip_dev_i32", "dq_sufsort_hip_dev_i64",
     "dq_sufsort_hip_batch_i32",
+    "dq_sufcheck_hip_i32", "dq_sufcheck_hip_i64", "dq_sufcheck_hip_dev_i32", "dq_sufcheck_hip_dev_i64",
     "dq_bsdiff_search_dev_i32", "dq_bsdiff_search_dev_i64", "dq_bsdiff_search_i32", "dq_bsdiff_search_i64",
     "dq_bsdiff_create", "dq_bsdiff_patch_bound", "dq_bsdiff_scan_i32", "dq_bspatch_apply",
     "dq_bsdiff_index_create", "dq_bsdiff_index_clone", "dq_bsdiff_index_buffers", "dq_bsdiff_index_diff", "dq_bsdiff_index_free",
@@ -93,6 +101,12 @@ def load() -> ctypes.CDLL:
     for name in ("dq_sufsort_hip_dev_i32", "dq_sufsort_hip_dev_i64"):
         getattr(L, name).restype = i32
         getattr(L, name).argtypes = [vp, i64, vp, i32, vp]
+    for name in ("dq_sufcheck_hip_i32", "dq_sufcheck_hip_i64"):
+        getattr(L, name).restype = i32
+        getattr(L, name).argtypes = [vp, i64, vp, i64, ctypes.POINTER(i32), i32]
+    for name in ("dq_sufcheck_hip_dev_i32", "dq_sufcheck_hip_dev_i64"):
+        getattr(L, name).restype = i32
+        getattr(L, name).argtypes = [vp, i64, vp, i64, ctypes.POINTER(i32), i32, vp]
     L.dq_sufsort_hip_batch_i32.restype = i32
     L.dq_sufsort_hip_batch_i32.argtypes = [i32, vp, vp, vp, i32, vp]
     for name in ("dq_bsdiff_search_dev_i32", "dq_bsdiff_search_dev_i64"):

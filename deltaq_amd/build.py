@@ -3,9 +3,10 @@
 The shared library is built IN-TREE (deltaq_amd/libdq_sufsort_hip.so) so that it
 travels with the repository snapshot; it is git-ignored.
 
-Four translation units, compiled side by side and linked into one library:
+Five translation units, compiled side by side and linked into one library:
     dq_sorter_i32.hip / dq_sorter_i64.hip   the suffix sorter and its kernels per index width
     dq_diff.hip                             match search, Diff.Create / Patch.Apply
+    dq_sufcheck.hip                         LDSSChecker.Check of a suffix array on the device
     dq_abi.hip                              the C ABI and the batch pipeline (host code only)
 Objects live in deltaq_amd/csrc/obj/ with the compiler's own dependency files, so an edit
 rebuilds only the units that include what changed.
@@ -22,7 +23,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "obj")
 LIB_NAME = "libdq_sufsort_hip.so"
 LIB_PATH = os.path.join(HERE, LIB_NAME)
-SOURCES = ["dq_sorter_i32.hip", "dq_sorter_i64.hip", "dq_diff.hip", "dq_abi.hip"]
+SOURCES = ["dq_sorter_i32.hip", "dq_sorter_i64.hip", "dq_diff.hip", "dq_sufcheck.hip", "dq_abi.hip"]
 ARCH = "gfx950"
 FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-pthread"]
 

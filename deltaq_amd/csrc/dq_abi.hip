@@ -1,5 +1,5 @@
 // dq_abi.hip -- the C ABI of libdq_sufsort_hip.so (include/dq_sufsort.h) and the batch pipeline behind
-// dq_sufsort_hip_batch_i32.  Host code only: the kernels live in dq_sorter_i32/i64.hip and dq_diff.hip.
+// dq_sufsort_hip_batch_i32.  Host code only: the kernels live in dq_sorter_i32/i64.hip, dq_diff.hip and dq_sufcheck.hip.
 //
 // This library contains no CPU sorting path: if HIP is unusable the entry points fail.
 #include "dq_runtime.h"
@@ -215,6 +215,34 @@ int32_t dq_sufsort_hip_dev_i64(const void *d_text, int64_t n, void *d_sa, int32_
 {
     EnvScope flags;
     return sufsort_dev<int64_t>(d_text, n, d_sa, device, stream);
+}
+
+int32_t dq_sufcheck_hip_i32(const uint8_t *text, int64_t n, const int32_t *sa, int64_t sa_len, int32_t *result,
+                            int32_t device)
+{
+    EnvScope flags;
+    return sufcheck_host<int32_t>(text, n, sa, sa_len, result, device);
+}
+
+int32_t dq_sufcheck_hip_i64(const uint8_t *text, int64_t n, const int64_t *sa, int64_t sa_len, int32_t *result,
+                            int32_t device)
+{
+    EnvScope flags;
+    return sufcheck_host<int64_t>(text, n, sa, sa_len, result, device);
+}
+
+int32_t dq_sufcheck_hip_dev_i32(const void *d_text, int64_t n, const void *d_sa, int64_t sa_len, int32_t *result,
+                                int32_t device, void *stream)
+{
+    EnvScope flags;
+    return sufcheck_dev<int32_t>(d_text, n, d_sa, sa_len, result, device, stream);
+}
+
+int32_t dq_sufcheck_hip_dev_i64(const void *d_text, int64_t n, const void *d_sa, int64_t sa_len, int32_t *result,
+                                int32_t device, void *stream)
+{
+    EnvScope flags;
+    return sufcheck_dev<int64_t>(d_text, n, d_sa, sa_len, result, device, stream);
 }
 
 int32_t dq_sufsort_hip_batch_i32(int32_t count, const uint8_t *const *texts, const int64_t *lens,

@@ -4,6 +4,7 @@
 // every unit the same state.
 //   dq_sorter_i32.hip / dq_sorter_i64.hip   the suffix sorter (dq_sorter_impl.h) for 32- / 64-bit indices
 //   dq_diff.hip                             match search, Diff.Create / Patch.Apply, the many-new-files index
+//   dq_sufcheck.hip                         LDSSChecker.Check of a suffix array on the device (dq_sufcheck.h)
 //   dq_abi.hip                              the C ABI (include/dq_sufsort.h), the batch pipeline, profile getters
 #pragma once
 #include <hip/hip_runtime.h>
@@ -463,6 +464,17 @@ extern template int64_t sufsort_workspace_bytes<int32_t>(int64_t);
 extern template int64_t sufsort_workspace_bytes<int64_t>(int64_t);
 extern template int64_t sufsort_workspace_plan<int32_t>(int64_t, bool, int64_t);
 extern template int64_t sufsort_workspace_plan<int64_t>(int64_t, bool, int64_t);
+
+// LDSSChecker.Check on the device (dq_sufcheck.hip): DQ_OK with the verdict (DQ_SUFCHECK_*) in *result, or an error
+template <typename IdxT>
+int sufcheck_host(const uint8_t *text, int64_t n, const IdxT *sa, int64_t sa_len, int32_t *result, int32_t device);
+template <typename IdxT>
+int sufcheck_dev(const void *d_text, int64_t n, const void *d_sa, int64_t sa_len, int32_t *result, int32_t device,
+                 void *stream);
+extern template int sufcheck_host<int32_t>(const uint8_t *, int64_t, const int32_t *, int64_t, int32_t *, int32_t);
+extern template int sufcheck_host<int64_t>(const uint8_t *, int64_t, const int64_t *, int64_t, int32_t *, int32_t);
+extern template int sufcheck_dev<int32_t>(const void *, int64_t, const void *, int64_t, int32_t *, int32_t, void *);
+extern template int sufcheck_dev<int64_t>(const void *, int64_t, const void *, int64_t, int32_t *, int32_t, void *);
 
 // match search + BSDIFF40 (dq_diff.hip)
 int match_search_dev_i32(const void *d_old, int64_t n, const void *d_sa, const void *d_new, int64_t m, const int64_t *d_scans,

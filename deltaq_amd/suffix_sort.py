@@ -13,12 +13,21 @@ libdq_sufsort_hip.so; this file only marshals buffers.
 """
 from __future__ import annotations
 
+import ctypes
+
 import numpy as np
 
 from . import _abi
 
 LENGTH_MISMATCH_MESSAGE = "Text and suffix buffers should have the same length"  # LibDivSufSort.cs:31
 INT_MAX = 0x7FFFFFFF
+
+# LDSSChecker.ResultCode (test/DeltaQ.SuffixSorting.LibDivSufSort.Tests/LDSSChecker.cs:11-18): what Check returns
+CHECK_DONE = _abi.DQ_SUFCHECK_DONE
+CHECK_BAD_ARGUMENTS = _abi.DQ_SUFCHECK_BAD_ARGUMENTS
+CHECK_OUT_OF_RANGE = _abi.DQ_SUFCHECK_OUT_OF_RANGE
+CHECK_WRONG_ORDER = _abi.DQ_SUFCHECK_WRONG_ORDER
+CHECK_WRONG_POSITION = _abi.DQ_SUFCHECK_WRONG_POSITION
 
 
 def _as_text(text) -> np.ndarray:
@@ -102,15 +111,69 @@ class HipSuffixSort:
                 raise ValueError(LENGTH_MISMATCH_MESSAGE)
         fn = (self._lib.dq_sufsort_hip_dev_i32 if suffixes.dtype == torch.int32
               else self._lib.dq_sufsort_hip_dev_i64)
-        dev = text.device.index if text.device.index is not None else torch.cuda.current_device()
-        cur = torch.cuda.current_stream(text.device)
-        stream = cur.cuda_stream
-        if not stream:
-            # torch's default stream is the legacy null stream: the library then works on its own
-            # (non-blocking) stream, so whatever produced `text` has to be finished first
-            cur.synchronize()
+        dev, stream = _device_and_stream(text)
         _abi.check(fn(text.data_ptr() if n else None, n, suffixes.data_ptr() if n else None, dev, stream))
         return ret
+
+    # -- LDSSChecker.Check(T, SA)   (test/DeltaQ.SuffixSorting.LibDivSufSort.Tests/LDSSChecker.cs:23-119) --------
+    def Check(self, text, suffixes) -> int:
+        """LDSSChecker's verdict on ``suffixes`` as the suffix array of ``text``, decided on the device:
+        ``CHECK_DONE`` (0), ``CHECK_BAD_ARGUMENTS`` (lengths differ), ``CHECK_OUT_OF_RANGE``, ``CHECK_WRONG_ORDER``
+        or ``CHECK_WRONG_POSITION``.  Any entry values are safe to check.
+
+        Host buffers (bytes / bytearray / numpy uint8 text, numpy int32 / int64 suffixes) go through
+        ``dq_sufcheck_hip_i32`` / ``_i64``; torch GPU tensors stay on the device (``dq_sufcheck_hip_dev_*``, on the
+        current stream).
+        """
+        if _is_torch_tensor(text) or _is_torch_tensor(suffixes):
+            return self._check_device(text, suffixes)
+        T = _as_text(text)
+        if not isinstance(suffixes, np.ndarray) or suffixes.dtype not in (np.int32, np.int64) or suffixes.ndim != 1:
+            raise TypeError("suffixes must be a 1-D numpy int32 or int64 array")
+        sa = np.ascontiguousarray(suffixes)
+        fn = self._lib.dq_sufcheck_hip_i32 if sa.dtype == np.int32 else self._lib.dq_sufcheck_hip_i64
+        res = ctypes.c_int32()
+        _abi.check(fn(T.ctypes.data if T.size else None, T.size, sa.ctypes.data if sa.size else None, sa.size,
+                      ctypes.byref(res), self.device))
+        return res.value
+
+    check = Check
+
+    def _check_device(self, text, suffixes) -> int:
+        import torch
+
+        if not (_is_torch_tensor(text) and _is_torch_tensor(suffixes)):
+            raise TypeError("text and suffixes must both be host buffers or both torch GPU tensors")
+        if text.dtype != torch.uint8 or text.dim() != 1 or not text.is_contiguous():
+            raise TypeError("device text must be a contiguous 1-D uint8 tensor")
+        if not text.is_cuda:
+            raise TypeError("torch text tensors must live on the GPU; pass host data as bytes/numpy")
+        if suffixes.dtype not in (torch.int32, torch.int64) or suffixes.dim() != 1 or not suffixes.is_contiguous():
+            raise TypeError("suffixes must be a contiguous 1-D int32 or int64 tensor")
+        if suffixes.device != text.device:
+            raise TypeError("text and suffixes must be on the same device")
+        n, m = text.numel(), suffixes.numel()
+        fn = (self._lib.dq_sufcheck_hip_dev_i32 if suffixes.dtype == torch.int32
+              else self._lib.dq_sufcheck_hip_dev_i64)
+        dev, stream = _device_and_stream(text)
+        res = ctypes.c_int32()
+        _abi.check(fn(text.data_ptr() if n else None, n, suffixes.data_ptr() if m else None, m, ctypes.byref(res),
+                      dev, stream))
+        return res.value
+
+
+def _device_and_stream(t):
+    """(device ordinal, stream handle) for work on tensor t's device, on torch's current stream."""
+    import torch
+
+    dev = t.device.index if t.device.index is not None else torch.cuda.current_device()
+    cur = torch.cuda.current_stream(t.device)
+    stream = cur.cuda_stream
+    if not stream:
+        # torch's default stream is the legacy null stream: the library then works on its own
+        # (non-blocking) stream, so whatever produced the inputs has to be finished first
+        cur.synchronize()
+    return dev, stream
 
 
 def device_count() -> int:

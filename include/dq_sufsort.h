@@ -151,6 +151,37 @@ int32_t dq_bsdiff_scan_i32(const uint8_t *old_data, int64_t n, const uint8_t *ne
 int32_t dq_bspatch_apply(const uint8_t *old_data, int64_t n, const uint8_t *patch, int64_t patch_len, uint8_t *out,
                          int64_t cap, int64_t *out_len);
 
+/* ---- LDSSChecker.Check(T, SA) on the device: is sa the suffix array of text? --------------------------------------
+ * = libdivsufsort's sufcheck as the reference's tests restate it (test/DeltaQ.SuffixSorting.LibDivSufSort.Tests/
+ * LDSSChecker.cs:23-119), the same verdict for every (text, array) pair, decided by two passes over sa instead of the
+ * sequential walk: sa is a permutation (through its inverse), first characters do not decrease, and equal first
+ * characters are followed by suffixes in rank order.  Entries are used as addresses only after their range test:
+ * any int32 / int64 values are safe to check (sa arriving from elsewhere before dq_bsdiff_index_create, say).
+ * The return value is a DQ_* status; the verdict goes to *result (the two sets overlap numerically):
+ *   sa_len != n                                         DQ_OK, *result = DQ_SUFCHECK_BAD_ARGUMENTS (LDSSChecker.cs:29-33)
+ *   null result, negative n, null text with n > 0,
+ *   null sa with sa_len > 0                             DQ_ERR_BAD_ARGS
+ *   i32: n > 2^31-1; i64: n > 2^32                      DQ_ERR_TOO_LARGE (all before any device work)
+ *   n == 0                                              DQ_OK, *result = DQ_SUFCHECK_DONE
+ * Device memory: 4 n bytes (a uint32 inverse array) and a flag word, carved from the cached workspace of the slot the
+ * call leases (a sort's workspace on that slot is larger: a check after a sort allocates nothing); the host entries
+ * add their device copies of sa (n * index width) and text (n).  No CPU fallback: DQ_ERR_OOM when that does not fit.
+ * The _dev_ forms take device pointers on `device`, enqueue on `stream` (NULL = the library's stream) and return after
+ * it has drained. */
+#define DQ_SUFCHECK_DONE             0   /* LDSSChecker.ResultCode values (LDSSChecker.cs:11-18) */
+#define DQ_SUFCHECK_BAD_ARGUMENTS  (-1)
+#define DQ_SUFCHECK_OUT_OF_RANGE   (-2)
+#define DQ_SUFCHECK_WRONG_ORDER    (-3)
+#define DQ_SUFCHECK_WRONG_POSITION (-4)
+int32_t dq_sufcheck_hip_i32(const uint8_t *text, int64_t n, const int32_t *sa, int64_t sa_len, int32_t *result,
+                            int32_t device);
+int32_t dq_sufcheck_hip_i64(const uint8_t *text, int64_t n, const int64_t *sa, int64_t sa_len, int32_t *result,
+                            int32_t device);
+int32_t dq_sufcheck_hip_dev_i32(const void *d_text, int64_t n, const void *d_sa, int64_t sa_len, int32_t *result,
+                                int32_t device, void *stream);
+int32_t dq_sufcheck_hip_dev_i64(const void *d_text, int64_t n, const void *d_sa, int64_t sa_len, int32_t *result,
+                                int32_t device, void *stream);
+
 /* Device workspace (bytes) a sort of n bytes with index_bytes (4 or 8) wide indices needs,
  * excluding the caller's text and sa buffers: the device entry point's full layout (the reduced one at n = 2^32). */
 int64_t dq_sufsort_hip_workspace_bytes(int64_t n, int32_t index_bytes);
