@@ -157,9 +157,9 @@ int batch_on_device(int device, const std::vector<int> &jobs, const uint8_t *con
         // the stages already running are woken through fail_stage and joined
         JoinAll stages;
         try {
-            stages.v.emplace_back(stage_in);
-            stages.v.emplace_back(stage_sort);
-            stages.v.emplace_back(stage_out);
+            stages.v.emplace_back(with_flags(stage_in));
+            stages.v.emplace_back(with_flags(stage_sort));
+            stages.v.emplace_back(with_flags(stage_out));
         } catch (const std::exception &e) {
             fail_stage(0, DQ_ERR_OOM, std::string("batch: cannot start a pipeline thread: ") + e.what());
         }
@@ -195,60 +195,60 @@ const char *dq_last_error(void) { return t_err.c_str(); }
 
 int32_t dq_sufsort_hip_i32(const uint8_t *text, int64_t n, int32_t *sa, int32_t device)
 {
-    EnvScope flags;
+    EnvScope scope;
     return sufsort_host<int32_t>(text, n, sa, device);
 }
 
 int32_t dq_sufsort_hip_i64(const uint8_t *text, int64_t n, int64_t *sa, int32_t device)
 {
-    EnvScope flags;
+    EnvScope scope;
     return sufsort_host<int64_t>(text, n, sa, device);
 }
 
 int32_t dq_sufsort_hip_dev_i32(const void *d_text, int64_t n, void *d_sa, int32_t device, void *stream)
 {
-    EnvScope flags;
+    EnvScope scope;
     return sufsort_dev<int32_t>(d_text, n, d_sa, device, stream);
 }
 
 int32_t dq_sufsort_hip_dev_i64(const void *d_text, int64_t n, void *d_sa, int32_t device, void *stream)
 {
-    EnvScope flags;
+    EnvScope scope;
     return sufsort_dev<int64_t>(d_text, n, d_sa, device, stream);
 }
 
 int32_t dq_sufcheck_hip_i32(const uint8_t *text, int64_t n, const int32_t *sa, int64_t sa_len, int32_t *result,
                             int32_t device)
 {
-    EnvScope flags;
+    EnvScope scope;
     return sufcheck_host<int32_t>(text, n, sa, sa_len, result, device);
 }
 
 int32_t dq_sufcheck_hip_i64(const uint8_t *text, int64_t n, const int64_t *sa, int64_t sa_len, int32_t *result,
                             int32_t device)
 {
-    EnvScope flags;
+    EnvScope scope;
     return sufcheck_host<int64_t>(text, n, sa, sa_len, result, device);
 }
 
 int32_t dq_sufcheck_hip_dev_i32(const void *d_text, int64_t n, const void *d_sa, int64_t sa_len, int32_t *result,
                                 int32_t device, void *stream)
 {
-    EnvScope flags;
+    EnvScope scope;
     return sufcheck_dev<int32_t>(d_text, n, d_sa, sa_len, result, device, stream);
 }
 
 int32_t dq_sufcheck_hip_dev_i64(const void *d_text, int64_t n, const void *d_sa, int64_t sa_len, int32_t *result,
                                 int32_t device, void *stream)
 {
-    EnvScope flags;
+    EnvScope scope;
     return sufcheck_dev<int64_t>(d_text, n, d_sa, sa_len, result, device, stream);
 }
 
 int32_t dq_sufsort_hip_batch_i32(int32_t count, const uint8_t *const *texts, const int64_t *lens,
                                  int32_t *const *sas, int32_t ndev, const int32_t *devs)
 {
-    EnvScope flags;
+    EnvScope scope;
     if (count < 0 || ndev <= 0 || (count > 0 && (!texts || !lens || !sas)))
         return fail(DQ_ERR_BAD_ARGS, "bad batch arguments");
     if (count == 0) return DQ_OK;
@@ -273,7 +273,7 @@ int32_t dq_sufsort_hip_batch_i32(int32_t count, const uint8_t *const *texts, con
     {
         JoinAll threads;
         for (int d = 0; d < ndev; ++d) {
-            threads.v.emplace_back([&, d]() {
+            threads.v.emplace_back(with_flags([&, d]() {
                 const int device = devs ? devs[d] : d;
                 try {
                     rcs[d] = batch_on_device(device, share[d], texts, lens, sas, &errs[d], &stats[d]);
@@ -281,7 +281,7 @@ int32_t dq_sufsort_hip_batch_i32(int32_t count, const uint8_t *const *texts, con
                     rcs[d] = DQ_ERR_OOM;
                     errs[d] = std::string("batch: ") + e.what();
                 }
-            });
+            }));
         }
     }
     for (const ShareStats &s : stats) {
@@ -303,7 +303,7 @@ int32_t dq_bsdiff_search_dev_i32(const void *d_old, int64_t n, const void *d_sa,
                                  const int64_t *d_scans, int64_t scan0, int64_t count, int64_t cap, void *d_pos,
                                  void *d_len, int32_t device, void *stream)
 {
-    EnvScope flags;
+    EnvScope scope;
     return match_search_dev_i32(d_old, n, d_sa, d_new, m, d_scans, scan0, count, cap, d_pos, d_len, device, stream);
 }
 
@@ -311,7 +311,7 @@ int32_t dq_bsdiff_search_dev_i64(const void *d_old, int64_t n, const void *d_sa,
                                  const int64_t *d_scans, int64_t scan0, int64_t count, int64_t cap, void *d_pos,
                                  void *d_len, int32_t device, void *stream)
 {
-    EnvScope flags;
+    EnvScope scope;
     return match_search_dev_i64(d_old, n, d_sa, d_new, m, d_scans, scan0, count, cap, d_pos, d_len, device, stream);
 }
 
@@ -319,7 +319,7 @@ int32_t dq_bsdiff_search_i32(const uint8_t *old_data, int64_t n, const int32_t *
                              const int64_t *scans, int64_t scan0, int64_t count, int64_t cap, int32_t *pos, int32_t *len,
                              int32_t device)
 {
-    EnvScope flags;
+    EnvScope scope;
     return match_search_host_i32(old_data, n, sa, new_data, m, scans, scan0, count, cap, pos, len, device);
 }
 
@@ -327,7 +327,7 @@ int32_t dq_bsdiff_search_i64(const uint8_t *old_data, int64_t n, const int64_t *
                              const int64_t *scans, int64_t scan0, int64_t count, int64_t cap, int64_t *pos, int64_t *len,
                              int32_t device)
 {
-    EnvScope flags;
+    EnvScope scope;
     return match_search_host_i64(old_data, n, sa, new_data, m, scans, scan0, count, cap, pos, len, device);
 }
 
@@ -335,7 +335,7 @@ int32_t dq_bsdiff_scan_i32(const uint8_t *old_data, int64_t n, const uint8_t *ne
                            int64_t ctrl_cap, int64_t *nctrl, uint8_t *diff, int64_t *ndiff, uint8_t *extra, int64_t *nextra,
                            int64_t *stats, int32_t device)
 {
-    EnvScope flags;
+    EnvScope scope;
     try {
         std::vector<int64_t> r_ctrl;
         std::vector<uint8_t> r_diff, r_extra;
@@ -360,7 +360,7 @@ int32_t dq_bsdiff_scan_i32(const uint8_t *old_data, int64_t n, const uint8_t *ne
 int32_t dq_bsdiff_create(const uint8_t *old_data, int64_t n, const uint8_t *new_data, int64_t m, uint8_t *patch,
                          int64_t cap, int64_t *patch_len, int32_t device)
 {
-    EnvScope flags;
+    EnvScope scope;
     try {
         std::vector<uint8_t> v;
         const int rc = bsdiff_create_host(old_data, n, new_data, m, device, v);
@@ -379,7 +379,7 @@ int32_t dq_bsdiff_create(const uint8_t *old_data, int64_t n, const uint8_t *new_
 int32_t dq_bsdiff_index_create(const uint8_t *old_data, int64_t n, const void *d_old, const void *d_sa, int32_t device,
                                void **index_out)
 {
-    EnvScope flags;
+    EnvScope scope;
     if (!index_out) return fail(DQ_ERR_BAD_ARGS, "null index pointer");
     *index_out = nullptr;
     try {
@@ -395,7 +395,7 @@ int32_t dq_bsdiff_index_create(const uint8_t *old_data, int64_t n, const void *d
 
 int32_t dq_bsdiff_index_clone(const void *index, int32_t device, void **index_out)
 {
-    EnvScope flags;
+    EnvScope scope;
     if (!index || !index_out) return fail(DQ_ERR_BAD_ARGS, "null index");
     *index_out = nullptr;
     try {
@@ -416,7 +416,7 @@ int32_t dq_bsdiff_index_buffers(const void *index, const void **d_old, const voi
 int32_t dq_bsdiff_index_diff(const void *index, const uint8_t *new_data, int64_t m, uint8_t *patch, int64_t cap,
                              int64_t *patch_len)
 {
-    EnvScope flags;
+    EnvScope scope;
     if (!index) return fail(DQ_ERR_BAD_ARGS, "null index");
     try {
         std::vector<uint8_t> v;

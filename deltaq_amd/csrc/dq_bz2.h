@@ -28,6 +28,8 @@
 #include <emmintrin.h>
 #include <vector>
 
+#include "dq_flags.h"
+
 namespace dq {
 namespace bz2 {
 
@@ -481,7 +483,7 @@ using DoubledSorter = std::function<int(const uint8_t *text, int64_t n2, int32_t
 inline int compress_block(BitWriter &bw, const std::vector<uint8_t> &blk, uint32_t crc, const DoubledSorter &sorter)
 {
     const int32_t nblock = (int32_t)blk.size();
-    const bool trace = getenv("DQ_TRACE") != nullptr;
+    const bool trace = flags().trace.has_value();
     auto now = [] { return std::chrono::steady_clock::now(); };
     auto t_prev = now();
     double t_ph[5] = {0, 0, 0, 0, 0};                       // sort, last column, MTF, tables, bits

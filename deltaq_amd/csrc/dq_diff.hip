@@ -39,12 +39,13 @@ int match_search_dev(const void *d_old, int64_t n, const void *d_sa, const void 
     const int64_t probes = bit_length((uint64_t)std::max<int64_t>(n, 1));
     // (DQ_SEARCH_WAVE=1: consecutive positions through the one-wave-per-position kernel of the scan-loop driver, so
     // that the tests can compare its answers one by one; position 0 is answered exactly whatever the cap)
-    const bool wave = env("DQ_SEARCH_WAVE") && !d_scans && count <= 4096;
+    const Flags &F = flags();
+    const bool wave = F.search_wave && !d_scans && count <= 4096;
     // (DQ_SEARCH_PTAB = 2 | 3: the search starts from a prefix table of that many bytes, as the scan-loop driver's
     // windows do -- built here for the call, so that the tests can compare the answers of both kernels with it)
     struct TmpTab { void *p = nullptr; ~TmpTab() { if (p) (void)hipFree(p); } } tmp_tab;
-    if (!d_ptab && env("DQ_SEARCH_PTAB") && n > 0) {
-        pk = atoi(env("DQ_SEARCH_PTAB")) >= 3 ? 3 : 2;
+    if (!d_ptab && F.search_ptab && n > 0) {
+        pk = *F.search_ptab >= 3 ? 3 : 2;
         const int64_t total = (1ll << (8 * pk)) + 1;
         HIP_TRY(dq_malloc(&tmp_tab.p, (size_t)total * sizeof(IdxT)));
         hipLaunchKernelGGL(prefix_bounds_kernel<IdxT>, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
@@ -210,7 +211,7 @@ struct SearchWindows {
         // the previous window was used up to its end: the loop is walking byte by byte -> a larger one
         next_size = (w0 >= 0 && scan == w0 + wc) ? std::min(next_size * 2, kMaxWindow) : min_window;
         const int64_t count = std::min(next_size, m - scan);
-        if (count <= kWaveWindow && !env("DQ_NO_WAVE_WINDOWS")) {
+        if (count <= kWaveWindow && !flags().no_wave_windows) {
             // short windows (the loop is hopping from match to match: every launch is a dependent round trip): one WAVE
             // per position, 65-ary search; the position the loop stands on exactly, the ones behind it with the cap
             std::lock_guard<std::mutex> lk(c.mu);
@@ -479,7 +480,7 @@ struct BlockSorter {
             if (words * 64 >= nb && nb >= (1 << 15)) hints.run_period = 5;
         }
         const int r = sufsort_host<int32_t>(t, n2, sa, dev, hints);
-        if (env("DQ_TRACE"))
+        if (flags().trace)
             fprintf(stderr, "[dq] bzip2 block transform: suffix array of %lld bytes in %.3f ms\n", (long long)n2,
                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
         if (r == DQ_OK) return 0;
@@ -490,7 +491,8 @@ struct BlockSorter {
         }
         return -2;
     }
-    bz2::DoubledSorter fn() { return [this](const uint8_t *t, int64_t n2, int32_t *sa) { return sort(t, n2, sa); }; }
+    // (the encoders call it on threads of their own: under the snapshot of the thread that asked for it)
+    bz2::DoubledSorter fn() { return with_flags([this](const uint8_t *t, int64_t n2, int32_t *sa) { return sort(t, n2, sa); }); }
 };
 
 // Large host buffers that are written once from front to back (the diff / extra streams of a large pair, the chain
@@ -533,7 +535,7 @@ struct PatchFramer {
                 enc[k].reset(new bz2::StreamEncoder(sorter.fn()));
             }
             state.store(0);
-            for (int k = 0; k < 2; ++k) th[k] = std::thread([this, k] { follow(k); });
+            for (int k = 0; k < 2; ++k) th[k] = std::thread(with_flags([this, k] { follow(k); }));
         } catch (const std::exception &) {
             abandon();
             return false;
@@ -747,12 +749,13 @@ int scan_on_device(const DiffIndex &ix, DeviceCtx &c, char *d_new, char *scratch
     *retry_on_host = false;
     bsdiff::TripleEmitter em(ix.old, ix.n, nw, m, raw);
     // (short files: two more threads cost more than the framing they would hide)
-    const int64_t follow_min = env("DQ_FRAME_FOLLOW_MIN") ? atoll(env("DQ_FRAME_FOLLOW_MIN")) : (int64_t)256 << 10;
+    const Flags &F = flags();
+    const int64_t follow_min = F.frame_follow_min.value_or((int64_t)256 << 10);
     if (framer && m >= follow_min && framer->start(raw, m)) em.progress = framer->final_len;
     std::lock_guard<std::mutex> lk(c.mu);                 // (the device context's stream and pinned areas)
     int rc = init_ctx(c, ix.dev);
     if (rc != DQ_OK) return rc;
-    const bool trace = env("DQ_TRACE") != nullptr;
+    const bool trace = F.trace.has_value();
     // The grids are persistent and their workgroups wait for each other's answers: all of them must be on the device at
     // once.  What the device holds (occupancy of this kernel x compute units; a partitioned or smaller part holds
     // fewer) bounds them; below 8 workgroups, or for a while after a launch whose workgroups waited in vain (a device
@@ -775,18 +778,18 @@ int scan_on_device(const DiffIndex &ix, DeviceCtx &c, char *d_new, char *scratch
                            kScanChainGroups, ncu);
     }
     int cap = c.scan_groups_cap;
-    if (const char *v = env("DQ_SCAN_GROUPS_CAP")) cap = std::min(cap, std::max(0, atoi(v)));           // (tests: a small device)
-    const int asked = env("DQ_SCAN_GROUPS") ? std::max(8, std::min(kAsMaxGroups, atoi(env("DQ_SCAN_GROUPS")))) : 0;
+    if (F.scan_groups_cap) cap = std::min(cap, *F.scan_groups_cap);           // (tests: a small device)
+    const int asked = F.scan_groups ? std::min(kAsMaxGroups, *F.scan_groups) : 0;
     const int groups_alone = std::min(asked ? asked : kAsGroups, cap);                 // a grid that is alone on the file
     const int groups_chain = std::min(asked ? asked : kScanChainGroups, cap);          // one of several
     // (workgroups of narrow grids the device holds at once: more than of the widest, their LDS is a quarter)
     int cap_chains = groups_chain <= kScanChainGroups ? std::max(cap, c.scan_groups_cap_narrow) : cap;
-    if (const char *v = env("DQ_SCAN_GROUPS_CAP")) cap_chains = std::min(cap_chains, std::max(0, atoi(v)));
-    int chains_max = env("DQ_SCAN_CHAINS") ? std::max(1, std::min(kScanMaxChains, atoi(env("DQ_SCAN_CHAINS")))) : kScanChains;
+    if (F.scan_groups_cap) cap_chains = std::min(cap_chains, *F.scan_groups_cap);
+    int chains_max = F.scan_chains ? std::min(kScanMaxChains, *F.scan_chains) : kScanChains;
     if (groups_chain >= 8) chains_max = std::min(chains_max, cap_chains / groups_chain);
-    const int64_t min_seg = env("DQ_SCAN_MIN_SEG") ? std::max<int64_t>(64, atoll(env("DQ_SCAN_MIN_SEG"))) : kScanMinSegment;
-    const int64_t extra_ends = env("DQ_SCAN_EXTRA") ? std::max<int64_t>(1, atoll(env("DQ_SCAN_EXTRA"))) : kScanExtra;
-    const int64_t lane_budget = env("DQ_SCAN_LANE_BUDGET") ? std::max<int64_t>(1, atoll(env("DQ_SCAN_LANE_BUDGET"))) : kScanLaneBudget;
+    const int64_t min_seg = F.scan_min_seg.value_or(kScanMinSegment);
+    const int64_t extra_ends = F.scan_extra.value_or(kScanExtra);
+    const int64_t lane_budget = F.scan_lane_budget.value_or(kScanLaneBudget);
     t_diff_info[4] = chains_max > 1 && m >= 2 * min_seg ? groups_chain : groups_alone;
     if (groups_alone < 8 || c.scan_skip > 0) {
         if (c.scan_skip > 0) --c.scan_skip;
@@ -923,11 +926,11 @@ int scan_on_device(const DiffIndex &ix, DeviceCtx &c, char *d_new, char *scratch
             AnchorCtl up = x.st;
             up.nrec = 0; up.done = 0; up.windows = 0; up.stops = 0; up.error = 0;
             up.t_search = up.t_wait = up.t_eval = up.t_stop = 0;
-            up.pad = (trace ? 1u : 0u) | ((unsigned)(env("DQ_SCAN_POLL_SLEEP") ? std::max(1, std::min(32, atoi(env("DQ_SCAN_POLL_SLEEP")))) : 16) << 8);
+            up.pad = (trace ? 1u : 0u) | ((unsigned)F.scan_poll_sleep.value_or(16) << 8);
             // (the tests: a spin bound of 2^k polls -- DQ_FAULT=spin: 2 --, and workgroup k - 1 as the straggler of every window)
             if (t_fault.spin) up.pad |= 1u << 16;
-            else if (const char *v = env("DQ_SCAN_SPIN_LOG2")) up.pad |= (unsigned)std::max(1, std::min(24, atoi(v))) << 16;
-            if (const char *v = env("DQ_SCAN_SLOW_GROUP")) up.pad |= (unsigned)std::max(0, std::min(255, atoi(v))) << 24;
+            else if (F.scan_spin_log2) up.pad |= (unsigned)*F.scan_spin_log2 << 16;
+            if (F.scan_slow_group) up.pad |= (unsigned)*F.scan_slow_group << 24;
             *x.h_up = up;
             const int64_t refill = std::min<int64_t>(*x.dirty, kAnchorRecs);
             for (int64_t r = 0; r < refill; ++r) x.ring[r] = kAnchorPending;
@@ -964,7 +967,7 @@ int scan_on_device(const DiffIndex &ix, DeviceCtx &c, char *d_new, char *scratch
     bool serial_next = false;
     int64_t n_joins = 0, n_launches = 0, n_dropped = 0, n_adopted = 0;
     // emitters of the speculative chains on threads of their own (DQ_SCAN_PAR_EMIT=0: everything on this thread)
-    const bool par_emit = env("DQ_SCAN_PAR_EMIT") ? atoi(env("DQ_SCAN_PAR_EMIT")) != 0 : true;
+    const bool par_emit = F.scan_par_emit.value_or(1) != 0;
     bool want_adopt = false;                              // the followed chain has an emitter whose state has not been seen equal to em's yet
     bool adopting = false;                                // ... it has: its output is copied
     // Launch the followed chain (again) from its state -- and, when no other chain is left and enough of the file is,
@@ -1032,7 +1035,7 @@ int scan_on_device(const DiffIndex &ix, DeviceCtx &c, char *d_new, char *scratch
                     const int64_t part = upto - x.start;
                     e.reset(x.start, (size_t)std::min<int64_t>(m - x.start, part + part / 4 + (64 << 10)) + 64);
                     x.mark_at = 0;
-                    e.th = std::thread([&e, &ix, nw, m, ring = x.ring, start = x.start] { e.run(ix.old, ix.n, nw, m, ring, start); });
+                    e.th = std::thread(with_flags([&e, &ix, nw, m, ring = x.ring, start = x.start] { e.run(ix.old, ix.n, nw, m, ring, start); }));
                     x.em = &e;
                 }
             } catch (const std::exception &) {
@@ -1207,7 +1210,7 @@ int scan_on_device(const DiffIndex &ix, DeviceCtx &c, char *d_new, char *scratch
     // caller runs the host loop over windows instead; nothing of this attempt is kept; the next 16 diffs on this device
     // do not try again)
     if (gave_up) {
-        if (!t_fault.spin && !env("DQ_SCAN_SPIN_LOG2")) c.scan_skip = 16;     // (not under the tests' own bound)
+        if (!t_fault.spin && !F.scan_spin_log2) c.scan_skip = 16;     // (not under the tests' own bound)
         if (trace) fprintf(stderr, "[dq] anchor scan: grid barrier timed out\n");
         *retry_on_host = true;
         return DQ_ERR_HIP;                                  // (no fail(): the host loop's DQ_OK must not carry this text)
@@ -1238,7 +1241,8 @@ int diff_index_scan(const DiffIndex &ix, const uint8_t *nw, int64_t m, bsdiff::R
     const int dev = ix.dev;
     HIP_TRY(hipSetDevice(dev));
     DeviceCtx &c = ctx0(dev);
-    const bool trace = env("DQ_TRACE") != nullptr;
+    const Flags &F = flags();
+    const bool trace = F.trace.has_value();
     const auto t_begin = std::chrono::steady_clock::now();
     auto stamp = [&](const char *what) {
         if (trace) fprintf(stderr, "[dq] bsdiff %-14s at %8.3f ms (%.3f ms of the clock)\n", what,
@@ -1265,7 +1269,7 @@ int diff_index_scan(const DiffIndex &ix, const uint8_t *nw, int64_t m, bsdiff::R
     stamp("new on device");
     // the anchor search of the scan loop on the device (default), or the host loop over windows of device answers
     // (its answer words have 31 bits for a length, all ones standing for "not exact": files of 2^31 - 1 bytes take the host loop)
-    const bool device_scan = (env("DQ_SCAN_DEVICE") ? atoi(env("DQ_SCAN_DEVICE")) != 0 : true) && ix.n < 0x7fffffffLL && m < 0x7fffffffLL;
+    const bool device_scan = F.scan_device.value_or(1) != 0 && ix.n < 0x7fffffffLL && m < 0x7fffffffLL;
     if (device_scan) {
         bool retry_on_host = false;
         rc = scan_on_device(ix, c, d_new, d_new + b_new + 256, pinned + kDiffWindowBytes, nw, m, raw, &retry_on_host, framer);
@@ -1286,15 +1290,15 @@ int diff_index_scan(const DiffIndex &ix, const uint8_t *nw, int64_t m, bsdiff::R
     win.pk = ix.pk;
     win.h_pos = reinterpret_cast<int32_t *>(pinned);
     win.h_len = reinterpret_cast<int32_t *>(pinned + b_win);
-    win.h_packed = env("DQ_NO_POLL") ? nullptr : reinterpret_cast<uint64_t *>(pinned + 2 * b_win);
+    win.h_packed = F.no_poll ? nullptr : reinterpret_cast<uint64_t *>(pinned + 2 * b_win);
     win.d_mail = d_new + b_new;
     HIP_TRY(hipMemset(win.d_mail, 0, 16));
-    win.no_second = env("DQ_NO_SECOND_STAGE") != nullptr;
-    if (const char *v = env("DQ_WIN_MIN")) win.min_window = std::min<int64_t>(std::max(16, atoi(v)), SearchWindows::kWaveWindow);
-    if (const char *v = env("DQ_WIN_SECOND")) win.second = std::min<int64_t>(std::max(16, atoi(v)), SearchWindows::kSecond);
+    win.no_second = F.no_second_stage;
+    if (F.win_min) win.min_window = std::min<int64_t>(*F.win_min, SearchWindows::kWaveWindow);
+    if (F.win_second) win.second = std::min<int64_t>(*F.win_second, SearchWindows::kSecond);
     win.next_size = win.min_window;
-    if (const char *v = env("DQ_WALK_ON")) win.walk_on = atoi(v) != 0;
-    win.no_resume = env("DQ_NO_RESUME") != nullptr;
+    if (F.walk_on) win.walk_on = *F.walk_on != 0;
+    win.no_resume = F.no_resume;
     rc = bsdiff::scan_loop(ix.old, ix.n, nw, m, win, raw);
     raw.windows = win.windows;
     raw.exact = win.exact;
@@ -1343,7 +1347,7 @@ int bz2_stream(const std::vector<uint8_t> &src, std::vector<uint8_t> &out, int d
 // their run-length / MTF / Huffman work overlaps, the block sorts take turns on the device.
 int frame_patch(const bsdiff::RawStreams &raw, int64_t m, int dev, std::vector<uint8_t> &patch, PatchFramer *framer = nullptr)
 {
-    const bool trace = env("DQ_TRACE") != nullptr;
+    const bool trace = flags().trace.has_value();
     const auto t_begin = std::chrono::steady_clock::now();
     const bool followed = framer && framer->ready();       // diff and extra were framed while they grew: their last blocks are left
     std::vector<uint8_t> z[3];
@@ -1367,10 +1371,10 @@ int frame_patch(const bsdiff::RawStreams &raw, int64_t m, int dev, std::vector<u
     {
         JoinAll threads;
         // (streams of a few KB are not worth a thread)
-        const bool parallel = raw.ctrl.size() + raw.diff.size() + raw.extra.size() >= (1u << 16) && !env("DQ_BZ2_SERIAL");
+        const bool parallel = raw.ctrl.size() + raw.diff.size() + raw.extra.size() >= (1u << 16);
         for (int k = 1; k < 3; ++k) {
             if (!parallel) { work(k); continue; }
-            try { threads.v.emplace_back(work, k); } catch (const std::exception &) { work(k); }
+            try { threads.v.emplace_back(with_flags(work), k); } catch (const std::exception &) { work(k); }
         }
         work(0);
     }
@@ -1394,7 +1398,7 @@ int bsdiff_create_host(const uint8_t *old, int64_t n, const uint8_t *nw, int64_t
     if (rc != DQ_OK) return rc;
     bsdiff::RawStreams raw;
     PatchFramer framer(dev);                              // (after raw: it reads the streams until it is gone)
-    const bool follow = !env("DQ_FRAME_AFTER");
+    const bool follow = !flags().frame_after;
     rc = bsdiff_raw(old, n, nw, m, device, raw, follow ? &framer : nullptr);
     if (rc != DQ_OK) return rc;
     return frame_patch(raw, m, dev, patch, &framer);
@@ -1480,7 +1484,7 @@ int diff_index_diff(const void *index, const uint8_t *nw, int64_t m, std::vector
     PatchFramer framer(ix->dev);
     {
         std::lock_guard<std::mutex> one_diff(ctx0(ix->dev).diff_mu);      // scan loops take turns on a device
-        const int rc = diff_index_scan(*ix, nw, m, raw, env("DQ_FRAME_AFTER") ? nullptr : &framer);
+        const int rc = diff_index_scan(*ix, nw, m, raw, flags().frame_after ? nullptr : &framer);
         if (rc != DQ_OK) return rc;
     }
     return frame_patch(raw, m, ix->dev, patch, &framer);                            // (framing overlaps the next caller's scan loop)

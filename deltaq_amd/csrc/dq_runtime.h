@@ -1,7 +1,7 @@
-// dq_runtime.h -- host runtime shared by the translation units of libdq_sufsort_hip.so: error reporting, the per-call
-// snapshot of the DQ_* flags, per-kernel hipEvent timers, device contexts (stream + workspace + pinned areas) and their
-// leases, and the entry points one unit calls in another.  Host code only (no kernels): C++17 inline variables give
-// every unit the same state.
+// dq_runtime.h -- host runtime shared by the translation units of libdq_sufsort_hip.so: error reporting, fault injection
+// (the DQ_* flags and their per-call snapshot: dq_flags.h), per-kernel hipEvent timers, device contexts (stream +
+// workspace + pinned areas) and their leases, and the entry points one unit calls in another.  Host code only (no
+// kernels): C++17 inline variables give every unit the same state.
 //   dq_sorter_i32.hip / dq_sorter_i64.hip   the suffix sorter (dq_sorter_impl.h) for 32- / 64-bit indices
 //   dq_diff.hip                             match search, Diff.Create / Patch.Apply, the many-new-files index
 //   dq_sufcheck.hip                         LDSSChecker.Check of a suffix array on the device (dq_sufcheck.h)
@@ -27,6 +27,7 @@
 #include <sched.h>
 
 #include "../../include/dq_sufsort.h"
+#include "dq_flags.h"
 
 namespace dq {
 
@@ -55,21 +56,7 @@ inline int fail(int code, const char *what, hipError_t e = hipSuccess)
     return code;
 }
 
-// ------------------------------------------------------------------ fault injection (tests of the error paths)
-// DQ_FAULT = alloc:K | hip:K | spin, read once per outermost call on this thread (EnvScope) and, like every DQ_* flag but
-// DQ_TRACE, only under DQ_DEBUG_FLAGS=1:
-//   alloc:K   the K-th device / pinned allocation of the call fails as if the device were out of memory   -> DQ_ERR_OOM
-//   hip:K     the K-th checked HIP call of the call (copies, memsets, launches, event work) fails          -> DQ_ERR_HIP
-//   spin      every bounded device spin gives up at its first empty poll: the look-back of radix_rank_kernel /
-//             seg_fused_kernel (-> DQ_ERR_HIP) and the answer exchange of anchor_scan_kernel (-> the host loop)
-// What the tests then check: the error code and message, nothing written to the caller's output, the next call on the
-// same thread correct, dq_sufsort_hip_release leaving no allocation behind (failure detection).
-struct FaultPlan {
-    int alloc_at = 0, hip_at = 0;       // 0: off
-    int alloc_seen = 0, hip_seen = 0;
-    bool spin = false;
-};
-inline thread_local FaultPlan t_fault;
+// ------------------------------------------------------------------ fault injection (dq_flags.h: DQ_FAULT)
 inline bool fault_alloc() { return t_fault.alloc_at > 0 && ++t_fault.alloc_seen == t_fault.alloc_at; }
 inline bool fault_hip() { return t_fault.hip_at > 0 && ++t_fault.hip_seen == t_fault.hip_at; }
 
@@ -88,62 +75,6 @@ inline hipError_t dq_host_malloc(void **p, size_t bytes, unsigned flags)
         if (e_ != hipSuccess)                                                           \
             return fail(e_ == hipErrorOutOfMemory ? DQ_ERR_OOM : DQ_ERR_HIP, #expr, e_); \
     } while (0)
-
-// ------------------------------------------------------------------ DQ_* flags
-// Every entry point reads the DQ_* environment flags through env(): the first lookup of a name inside a call asks
-// the process environment, later ones get the same answer -- a call sees ONE consistent set of flags, each variable
-// is read once per call and thread, and nothing on the per-kernel path touches the environment.  (The tests flip
-// flags between calls, so the answers are not kept beyond the outermost call on this thread.)
-struct EnvCache {
-    struct Entry { const char *name; bool set; std::string val; };
-    static constexpr int kMax = 64;
-    Entry e[kMax];
-    int count = 0, depth = 0;
-    bool debug_flags = false;           // DQ_DEBUG_FLAGS as the outermost call on this thread found it
-};
-inline thread_local EnvCache t_env;
-
-// The adaptive choices are compiled in; the DQ_* overrides (forced paths of the tests, experiment knobs, fault
-// injection) are honoured only in a process that sets DQ_DEBUG_FLAGS=1 -- a stray DQ_PACKED in a production environment
-// changes nothing.  Exempt: DQ_TRACE (prints, decides nothing) and DQ_HIP_DEVICE (which device "-1" means).
-inline bool env_gated(const char *name)
-{
-    return strcmp(name, "DQ_TRACE") != 0 && strcmp(name, "DQ_HIP_DEVICE") != 0 && strcmp(name, "DQ_DEBUG_FLAGS") != 0 &&
-           strcmp(name, "DQ_NUMA_BIND") != 0;
-}
-
-inline const char *env(const char *name)
-{
-    EnvCache &c = t_env;
-    for (int i = 0; i < c.count; ++i)
-        if (c.e[i].name == name || strcmp(c.e[i].name, name) == 0) return c.e[i].set ? c.e[i].val.c_str() : nullptr;
-    const char *v = getenv(name);
-    if (v && env_gated(name)) {
-        const char *g = c.depth > 0 ? (c.debug_flags ? "1" : nullptr) : getenv("DQ_DEBUG_FLAGS");
-        if (!g || atoi(g) == 0) v = nullptr;
-    }
-    if (c.depth == 0 || c.count == EnvCache::kMax) return v;          // outside an entry point: nothing is kept
-    EnvCache::Entry &x = c.e[c.count++];
-    x.name = name; x.set = v != nullptr; x.val = v ? v : "";
-    return x.set ? x.val.c_str() : nullptr;
-}
-
-struct EnvScope {
-    EnvScope()
-    {
-        if (t_env.depth++ != 0) return;
-        t_env.count = 0;
-        const char *g = getenv("DQ_DEBUG_FLAGS");
-        t_env.debug_flags = g && atoi(g) != 0;
-        t_fault = FaultPlan{};
-        if (const char *f = env("DQ_FAULT")) {
-            if (strncmp(f, "alloc:", 6) == 0) t_fault.alloc_at = std::max(1, atoi(f + 6));
-            else if (strncmp(f, "hip:", 4) == 0) t_fault.hip_at = std::max(1, atoi(f + 4));
-            else if (strcmp(f, "spin") == 0) t_fault.spin = true;
-        }
-    }
-    ~EnvScope() { if (--t_env.depth == 0) t_fault = FaultPlan{}; }
-};
 
 // ------------------------------------------------------------------ profiling
 struct KernelStat { int64_t launches = 0; double ms = 0; int64_t elems = 0; int64_t bytes = 0; };
@@ -345,8 +276,8 @@ inline int bit_length(uint64_t x) { return x == 0 ? 1 : 64 - __builtin_clzll(x);
 // device-wide pipeline; the tests use that to keep the pipeline covered on the fixtures).
 inline int64_t small_limit()
 {
-    if (const char *v = env("DQ_SMALL_N")) return std::min<int64_t>(std::max(0, atoi(v)), kSmallMaxN);
-    return kSmallMaxN;
+    const Flags &F = flags();
+    return F.small_n ? std::min<int64_t>(*F.small_n, kSmallMaxN) : kSmallMaxN;
 }
 
 inline int resolve_device(int32_t device, int *out)
@@ -354,10 +285,7 @@ inline int resolve_device(int32_t device, int *out)
     int count = 0;
     hipError_t e = hipGetDeviceCount(&count);
     if (e != hipSuccess || count <= 0) return fail(DQ_ERR_NO_DEVICE, "no HIP device available", e);
-    if (device < 0) {
-        const char *v = env("DQ_HIP_DEVICE");
-        device = v ? atoi(v) : 0;
-    }
+    if (device < 0) device = flags().hip_device.value_or(0);
     if (device < 0 || device >= count || device >= kMaxDevices)
         return fail(DQ_ERR_BAD_ARGS, "device ordinal out of range");
     *out = device;
@@ -425,7 +353,7 @@ inline bool numa_node_cpus(int node, cpu_set_t *set)
 // binds the CALLING thread (one the library started) to the device's NUMA node; true if it did
 inline bool bind_this_thread_to_device(int dev)
 {
-    if (const char *v = env("DQ_NUMA_BIND")) if (atoi(v) == 0) return false;
+    if (flags().numa_bind == 0) return false;
     cpu_set_t want, have;
     if (!numa_node_cpus(device_numa_node(dev), &want)) return false;
     // (never widen what the process was given: a container's cpuset, taskset)

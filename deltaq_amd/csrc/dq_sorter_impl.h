@@ -220,8 +220,7 @@ inline uint32_t spin_bound() { return t_fault.spin ? 0u : kSpinLimit; }
 
 inline int xcd_tile_group()
 {
-    if (const char *v = env("DQ_XCD_GROUP")) return std::max(0, std::min(64, atoi(v)));
-    return 8;
+    return flags().xcd_group.value_or(8);
 }
 
 template <typename IdxT, typename StatusT, int kMode, bool kCoded = false, bool kSmall = false>
@@ -388,7 +387,7 @@ void choose_key_bytes(const int64_t *bytehist, const int64_t *kgram_coll, int64_
         const double twins = (double)n * 2.0 * (double)C / ((double)kKgramSamples * (double)kKgramSamples);
         if (C >= kKgramSamples / 16 && twins > 0.25) { packed = false; kb = 8; }
     }
-    if (const char *v = env("DQ_PACKED")) packed = atoi(v) != 0 && fit >= 2;
+    if (const std::optional<int> v = flags().packed) packed = *v != 0 && fit >= 2;
     if (packed) kb = std::min(kb, fit);
     *kb_out = kb;
     *packed_out = packed;
@@ -422,8 +421,9 @@ template <typename IdxT>
 bool split_round0_wanted(int64_t n, bool packed, int kb, bool coded)
 {
     if (sizeof(IdxT) != 4 || packed || kb != 8 || n < kSplitMinN || n > (int64_t)kSplitBuckets * (kFinCap / 2)) return false;
-    if (const char *v = env("DQ_SPLIT")) return atoi(v) != 0;
-    if (env("DQ_KEY_BYTES") || env("DQ_NO_BUCKET")) return false;     // (forced plain paths of the tests stay what they were)
+    const Flags &F = flags();
+    if (F.split) return *F.split != 0;
+    if (F.key_bytes || F.no_bucket) return false;     // (forced plain paths of the tests stay what they were)
     (void)coded;
     return n >= (64ll << 20);
 }
@@ -437,9 +437,8 @@ int onesweep_sort_text_prepare(Launcher &L, DeviceCtx &c, Workspace<IdxT> &w, in
     *coded_out = false;
     // (256-thread workgroups: the pass is a chain of 16-byte loads and LDS adds, bound by how many are in flight.  512 / 1024 /
     // 2048 / 4096 workgroups at 256 MiB: 165 / 131 / 139 / 143 us -- more waves hide more latency until the 256 global adds
-    // each workgroup ends with pile up.  DQ_TEXT_HIST_BLOCKS tries other grids.)
-    const int64_t hist_cap = env("DQ_TEXT_HIST_BLOCKS") ? std::max(1, std::min(8192, atoi(env("DQ_TEXT_HIST_BLOCKS")))) : 1024;
-    int blocks = (int)std::min<int64_t>(hist_cap, ((n >> 4) + kBlock - 1) / kBlock + 1);
+    // each workgroup ends with pile up.)
+    int blocks = (int)std::min<int64_t>(1024, ((n >> 4) + kBlock - 1) / kBlock + 1);
     // (texts the bucketed round 0 may take: the bytes of every eighth too, for its XCD-local first pass; the
     // workgroups are then dealt out to the eighths evenly)
     unsigned long long *xcd_hist = n >= (1 << 16) ? reinterpret_cast<unsigned long long *>(w.bytehist + kXcdHistAt) : nullptr;
@@ -465,8 +464,9 @@ int onesweep_sort_text_prepare(Launcher &L, DeviceCtx &c, Workspace<IdxT> &w, in
     if (n >= (1 << 16)) HIP_TRY(hipMemsetAsync(w.Vb, 0, (size_t)((n + 63) / 64 + 1) * 8, L.st));
     HIP_TRY(hipEventSynchronize(c.readback));
     choose_key_bytes(c.pinned, n >= kKgramSamples * 8 ? c.pinned + 256 : nullptr, n, &kb, &packed);
-    if (const char *force = env("DQ_KEY_BYTES")) {
-        kb = std::min(8, std::max(1, atoi(force)));
+    const Flags &F = flags();
+    if (F.key_bytes) {
+        kb = *F.key_bytes;
         const int fit = (64 - bit_length((uint64_t)(n - 1))) / 8;
         if (kb > fit || kb < 2) packed = false;
     }
@@ -489,10 +489,10 @@ int onesweep_sort_text_prepare(Launcher &L, DeviceCtx &c, Workspace<IdxT> &w, in
         }
         coded = h0 <= kCodedMaxAvgLen - 0.25 && (sigma <= 128 || n >= 2 * kCodedMinN);
     }
-    if (const char *v = env("DQ_CODED")) coded = atoi(v) != 0 && !packed && kb == 8 && n >= 64;
+    if (F.coded) coded = *F.coded != 0 && !packed && kb == 8 && n >= 64;
     if (coded) {
         AlphaCode code;
-        coded = build_alpha_code(c.pinned, &code) && (code.avg_len <= kCodedMaxAvgLen || env("DQ_CODED"));
+        coded = build_alpha_code(c.pinned, &code) && (code.avg_len <= kCodedMaxAvgLen || F.coded);
         if (coded) {
             uint16_t *stage = reinterpret_cast<uint16_t *>(c.pinned + 512);          // the upload half of the pinned area
             memcpy(stage, code.tab, sizeof(code.tab));
@@ -505,7 +505,7 @@ int onesweep_sort_text_prepare(Launcher &L, DeviceCtx &c, Workspace<IdxT> &w, in
                 const int rc2 = launch_coded_hist<IdxT>(L, w, n);
                 if (rc2 != DQ_OK) return rc2;
             }
-            if (env("DQ_TRACE")) fprintf(stderr, "[dq] coded round 0: %d symbols, %.2f bits per byte\n", code.sigma, code.avg_len);
+            if (F.trace) fprintf(stderr, "[dq] coded round 0: %d symbols, %.2f bits per byte\n", code.sigma, code.avg_len);
             *coded_out = true;
             return DQ_OK;
         }
@@ -608,7 +608,7 @@ int collect_ties(Launcher &L, DeviceCtx &c, Workspace<IdxT> &w, int64_t n, int k
     if (c.pinned[1] != 0) return fail(DQ_ERR_HIP, "radix look-back timed out (device spin bound hit)");
     *count = c.pinned[6];
     *overflow = c.pinned[7] != 0;
-    if (*overflow && env("DQ_TRACE")) fprintf(stderr, "[dq] tie / bucket overflow flags: %lld\n", (long long)c.pinned[7]);
+    if (*overflow && flags().trace) fprintf(stderr, "[dq] tie / bucket overflow flags: %lld\n", (long long)c.pinned[7]);
     *fin_left = c.pinned[3];
     // byte model of the speculative finisher, now that the list length is known: list entry in, one 64-byte
     // sector of text per tied suffix, SA entry out
@@ -699,9 +699,8 @@ struct SuffixSorter {
     // (16 MiB: 4.1 - 4.3 ms against 5.2; 64 KiB: 0.56 against 0.76).
     static int mid_group_cap(int64_t list_len)
     {
-        if (const char *v = env("DQ_MID_GROUPS")) {
-            const int g = atoi(v);
-            return g >= 1024 ? 1024 : g >= 512 ? 512 : g >= 256 ? 256 : 0;
+        if (const std::optional<int> g = flags().mid_groups) {
+            return *g >= 1024 ? 1024 : *g >= 512 ? 512 : *g >= 256 ? 256 : 0;
         }
         return list_len >= kSgShortList ? 512 : 1024;
     }
@@ -744,9 +743,10 @@ struct SuffixSorter {
     int build_isa(const uint64_t *rank, const IdxT *suf, int64_t cnt)
     {
         const int ib = bit_length((uint64_t)(n - 1));
-        const bool pays = env("DQ_BINNED_ISA") ? atoi(env("DQ_BINNED_ISA")) != 0 : n > (32ll << 20);
+        const Flags &F = flags();
+        const bool pays = F.binned_isa ? *F.binned_isa != 0 : n > (32ll << 20);
         const bool fits = (size_t)cnt * 8 <= (size_t)(n + 2) * sizeof(IdxT) && rank == Kr[rcur] && suf == Vr[rcur];
-        if (pays && fits && n >= (1 << 16) && 2 * ib <= 63 && !env("DQ_NO_BINNED_ISA")) {
+        if (pays && fits && n >= (1 << 16) && 2 * ib <= 63 && !F.no_binned_isa) {
             uint64_t *P0 = Kr[rcur ^ 1], *P1 = Kr[rcur];
             uint64_t *stash = reinterpret_cast<uint64_t *>(Vr[rcur ^ 1]);
             if (cnt > 0) HIP_TRY(hipMemcpyAsync(stash, P1, (size_t)cnt * 8, hipMemcpyDeviceToDevice, st));
@@ -791,7 +791,8 @@ struct SuffixSorter {
     bool wide_list(int64_t mm) const { return mm * 2 > n; }
     bool uses_small_round(int64_t mm) const
     {
-        return !env("DQ_NO_SMALL") && fits32() && (!wide_list(mm) || (w.X && !env("DQ_NO_WIDE_SMALL")));
+        const Flags &F = flags();
+        return !F.no_small && fits32() && (!wide_list(mm) || (w.X && !F.no_wide_small));
     }
     // Exactly 2^32 bytes: ranks and suffixes no longer fit 32 bits, and from h = 1 on every doubling round keys on
     // rank >> 1 (kbits = 33), which only the radix round does.  The LDS-class rounds (whose chains clamp key2 to
@@ -810,8 +811,8 @@ struct SuffixSorter {
         // more than 8 go through the radix passes.
         // (32-bit ranks: every 64-bit buffer is busy until the words have been binned.  They go to the run-length buffer
         // when that is idle -- the first round's kernel reads them there -- else to Vb, to be widened into a key buffer)
-        const bool rank32_direct = sizeof(IdxT) == 4 && !runs_wanted && mid_group_cap(n) > 0 && !env("DQ_WIDEN_RANKS");
-        uint32_t *list_rank = (uses_small_round(0) && !env("DQ_NO_FIRST_SMALL"))
+        const bool rank32_direct = sizeof(IdxT) == 4 && !runs_wanted && mid_group_cap(n) > 0;
+        uint32_t *list_rank = (uses_small_round(0) && !flags().no_first_small)
                                   ? (rank32_direct ? w.RL : reinterpret_cast<uint32_t *>(w.Vb)) : nullptr;
         LAUNCH(L, DQ_K_SEG_FUSED, n, n * (8 + wb + 8),
                hipLaunchKernelGGL((seg_fused_kernel<IdxT, true, false, false, true>), dim3((unsigned)ntiles),
@@ -876,8 +877,9 @@ struct SuffixSorter {
         *done = false;
         if (coded) return DQ_OK;                          // (the digit offsets on the device are those of the coded keys)
         const int ib = bit_length((uint64_t)(n - 1));
-        if (env("DQ_NO_BUCKET") || env("DQ_NO_FUSED_TIES") || env("DQ_SPARSE") || env("DQ_KEY_BYTES")) return DQ_OK;
-        const bool forced = env("DQ_BUCKET") != nullptr;
+        const Flags &F = flags();
+        if (F.no_bucket || F.no_fused_ties || F.sparse || F.key_bytes) return DQ_OK;
+        const bool forced = F.bucket.has_value();
         if (ib > 31 || n < (1 << 16)) return DQ_OK;                           // a suffix must fit 31 bits next to the tie flag
         // a run of >= 64 equal bytes somewhere (zero padding of real binaries; text_hist_kernel saw it): more equal
         // keys than a bin takes -- the pass would only raise its flag and be repeated by the plain passes
@@ -890,7 +892,7 @@ struct SuffixSorter {
             if (c.pinned[b] > 0) { const double p = (double)c.pinned[b] / (double)n; h0 -= p * std::log2(p); }
         }
         int keybits = std::min(64 - ib, 36);
-        if (const char *v = env("DQ_BUCKET_KEYBITS")) keybits = std::max(17, std::min(keybits, atoi(v)));      // (tests: few key bits on small inputs)
+        if (F.bucket_keybits) keybits = std::max(17, std::min(keybits, *F.bucket_keybits));      // (tests: few key bits on small inputs)
         if (!packed) {
             // Words were not chosen because too many suffixes would stay tied for the tie-bit path of the plain
             // passes (2 GiB of random bytes: 33 key bits leave 1/4 of them tied).  Those ties are shallow, which the
@@ -906,7 +908,7 @@ struct SuffixSorter {
         double need = est + 6.0 * std::sqrt(est) + 64.0;
         // a tile must not span more than 64 two-byte buckets (its keys, relative to its first bucket, take 26
         // bits + 6 arrival bits): buckets of >= 192 words on average, i.e. texts of >= 12 MiB
-        const bool force3 = forced && atoi(env("DQ_BUCKET")) == 3;          // (tests: 3-byte buckets on mid-size inputs)
+        const bool force3 = forced && *F.bucket == 3;          // (tests: 3-byte buckets on mid-size inputs)
         if (need > 5120 || (!forced && n < (12 << 20)) || force3) {
             if (keybits - 24 >= 8 && (forced || n >= (12 << 20))) {
                 bbytes = 3;
@@ -928,7 +930,7 @@ struct SuffixSorter {
         // DQ_BUCKET_EXT = 0 | 1 overrides (tests: small inputs).
         bool ext = !coded && keybits + 8 <= 56 && lowbits + 8 <= 18 &&
                    (double)n * std::exp2(-(double)keybits * h0 / 8.0) > 0.02 && (size_t)2 * align_up((size_t)n) <= (size_t)(n + 2) * sizeof(IdxT);
-        if (const char *v = env("DQ_BUCKET_EXT")) ext = atoi(v) != 0 && keybits + 8 <= 56 && (size_t)2 * align_up((size_t)n) <= (size_t)(n + 2) * sizeof(IdxT);
+        if (F.bucket_ext) ext = *F.bucket_ext != 0 && keybits + 8 <= 56 && (size_t)2 * align_up((size_t)n) <= (size_t)(n + 2) * sizeof(IdxT);
         uint8_t *E[2] = {reinterpret_cast<uint8_t *>(w.Va), reinterpret_cast<uint8_t *>(w.Va) + align_up((size_t)n)};
         const int64_t ntiles = (n + C - 1) / C;
         uint32_t *ebits = reinterpret_cast<uint32_t *>(w.Vb);                  // zeroed by onesweep_sort_text_prepare
@@ -938,7 +940,7 @@ struct SuffixSorter {
         // The first pass: persistent and XCD-local (dq_xcd_rank.h) -- its regions cut in 8 sub-regions by the byte
         // histograms of the text's eighths that text_hist_kernel made -- or, with the extra key byte or under
         // DQ_OLD_FIRST_PASS=1, radix_rank_kernel<kTextPacked(Ext)>.  The regions hold the same words either way.
-        const bool xcd_pass = !ext && !env("DQ_OLD_FIRST_PASS");
+        const bool xcd_pass = !ext && !F.old_first_pass;
         // digit p of the bucket of suffix i is T[i + bbytes - 1 - p]
         hipLaunchKernelGGL(text_digit_offsets_kernel, dim3(bbytes), dim3(kBlock), 0, st,
                            (const int64_t *)w.bytehist, (const uint8_t *)w.text, n, bbytes, w.digit_offset,
@@ -950,7 +952,7 @@ struct SuffixSorter {
         }
         int rc = DQ_OK;
         if (xcd_pass) {
-            if (env("DQ_TRACE")) fprintf(stderr, "[dq] XCD-local first pass (n=%lld, eighths of %lld)\n", (long long)n, (long long)xcd_eighth(n));
+            if (F.trace) fprintf(stderr, "[dq] XCD-local first pass (n=%lld, eighths of %lld)\n", (long long)n, (long long)xcd_eighth(n));
             // (its tickets and cursors: the look-back area of digit pass 0, zeroed by onesweep_sort_text_prepare)
             if (sizeof(XcdRankCtl) > w.ctl_status_stride) return fail(DQ_ERR_HIP, "status buffer too small");
             LAUNCH(L, DQ_K_RADIX_RANK, n, n * (1 + 8),                 // persistent: one workgroup per CU
@@ -986,7 +988,7 @@ struct SuffixSorter {
                                       dim3(kBktThreads), 0, st, (const uint64_t *)Ks, ib, lowbits,
                                       (const int64_t *)w.bkt_bounds, ntiles, d_sa, ebits, flags, (const uint8_t *)nullptr));
         }
-        if (ext && env("DQ_TRACE")) fprintf(stderr, "[dq] bucketed round 0 with %d + 8 key bits per suffix (n=%lld)\n", keybits, (long long)n);
+        if (ext && F.trace) fprintf(stderr, "[dq] bucketed round 0 with %d + 8 key bits per suffix (n=%lld)\n", keybits, (long long)n);
         bool overflow = false;
         fin_cap = n / 8;
         const int64_t hb = (keybits + (ext ? 8 : 0)) / 8;    // whole bytes the members of a tie group share
@@ -996,7 +998,7 @@ struct SuffixSorter {
         if (overflow) {
             // a bucket or a bin this path does not take (or a run of equal keys too long for the tie walk):
             // back to the plain digit passes, with the state they expect
-            if (env("DQ_TRACE")) fprintf(stderr, "[dq] bucketed round 0 gave up (n=%lld): plain digit passes\n", (long long)n);
+            if (F.trace) fprintf(stderr, "[dq] bucketed round 0 gave up (n=%lld): plain digit passes\n", (long long)n);
             rc = prepare_status<IdxT>(L, w, n, kMaxPasses);
             if (rc != DQ_OK) return rc;
             HIP_TRY(hipMemsetAsync(w.Vb, 0, (size_t)((n + 63) / 64 + 1) * 8, st));
@@ -1044,7 +1046,8 @@ struct SuffixSorter {
             uint64_t *ovf_k[2] = {reinterpret_cast<uint64_t *>(w.ISA), K[0]};
             IdxT *ovf_v[2] = {reinterpret_cast<IdxT *>(w.RL), w.Vb};
             // (DQ_TRACE=2: the stream is drained after every phase and the phase named -- tests/manual/t_split_small.py)
-            const bool dbg = env("DQ_TRACE") && atoi(env("DQ_TRACE")) >= 2;
+            const Flags &F = flags();
+            const bool dbg = F.trace.value_or(0) >= 2;
             auto phase = [&](const char *what) -> int {
                 if (!dbg) return DQ_OK;
                 HIP_TRY(hipStreamSynchronize(st));
@@ -1075,10 +1078,10 @@ struct SuffixSorter {
             const int64_t heavy = c.pinned[0];
             // (heavy keys have buckets of their own and are placed unsorted; but their copies beyond a slot wait in the
             // same arena of n / 2 entries as the oversize buckets: a text that is mostly heavy keys does not fit it)
-            if (env("DQ_TRACE"))
+            if (F.trace)
                 fprintf(stderr, "[dq] sample-sort round 0: %.1f %% of the sampled keys are copies of keys too heavy for a bucket%s\n",
                         100.0 * (double)heavy / (double)kSplitSample, heavy * 5 > 2 * kSplitSample ? " -- the digit passes instead" : "");
-            if (heavy * 5 > 2 * kSplitSample && !(env("DQ_SPLIT") && atoi(env("DQ_SPLIT")) >= 2)) return DQ_OK;      // (DQ_SPLIT=2: the tests go on regardless)
+            if (heavy * 5 > 2 * kSplitSample && F.split.value_or(0) < 2) return DQ_OK;      // (DQ_SPLIT=2: the tests go on regardless)
             HIP_TRY(hipMemsetAsync(w.sp_cursor_b, 0, (size_t)kSplitBuckets * 8, st));
             HIP_TRY(hipMemsetAsync(w.sp_ctl, 0, sizeof(SplitCtl), st));
             // pass A's output: a virtual array of ~1.13 n entries -- the first n_main in (K[1], Va), the rest spilled into the
@@ -1127,7 +1130,7 @@ struct SuffixSorter {
             // two geometries by bucket size (dq_split_round0.h: what a CU gets through is set by how many buckets it holds at
             // once): <= 1024 entries with 16 KB of LDS, eight workgroups per CU; the others with 31 KB, five.  The last launch
             // also moves the oversize buckets to the overflow list.
-            const bool two = cap > kFinSmallCap && !env("DQ_SPLIT_ONE_CLASS");
+            const bool two = cap > kFinSmallCap;
             LAUNCH(L, DQ_K_SPLIT_FINISH, n, n * 2 * (8 + wb),
                    if (two || cap <= kFinSmallCap)
                        hipLaunchKernelGGL((bucket_finish_kernel<IdxT, 256, 4>), dim3(kSplitBuckets), dim3(256), 0, st, (const uint64_t *)Ks[0], (const IdxT *)Vs[0],
@@ -1141,7 +1144,7 @@ struct SuffixSorter {
             HIP_TRY(hipStreamSynchronize(st));
             const int64_t ovf = c.pinned[0], ovf_buckets = c.pinned[1], npure = c.pinned[4];
             const bool abandon = c.pinned[3] != 0 || ovf + npure > ovf_cap;            // (the two lists share one arena, from either end)
-            if (env("DQ_TRACE"))
+            if (flags().trace)
                 fprintf(stderr, "[dq] sample-sort round 0 (%s keys, %d buckets of <= %lld): %lld suffixes in %lld oversize buckets, %lld copies of heavy keys placed unsorted%s\n",
                         coded ? "coded" : "raw", kSplitBuckets, (long long)cap, (long long)ovf, (long long)ovf_buckets, (long long)npure,
                         abandon ? " -- overflow lists full, given up" : "");
@@ -1170,6 +1173,7 @@ struct SuffixSorter {
     //      the rebucket pass already wrote the inverse suffix array.
     int round0(bool *dense_built)
     {
+        const Flags &F = flags();
         uint64_t *K[2] = {w.K0, w.K1};
         IdxT *V[2];
         int cur = 0, kb = 8, rc;
@@ -1189,8 +1193,8 @@ struct SuffixSorter {
         // large groups that stop shrinking are what calls them)
         late_runs_possible = sizeof(IdxT) == 4 && n >= (1 << 16);
         if (period_hint > 0 && sizeof(IdxT) == 4 && n >= (1 << 16)) runs_wanted = true;      // (the caller has seen the stretches)
-        if (const char *v = env("DQ_RUNS")) { runs_wanted = sizeof(IdxT) == 4 && atoi(v) != 0; late_runs_possible = late_runs_possible && atoi(v) != 0; }
-        if (const char *v = env("DQ_MID_GROUPS")) runs_wanted = runs_wanted && atoi(v) >= 256;   // (the LDS class carries the run offsets)
+        if (F.runs) { runs_wanted = sizeof(IdxT) == 4 && *F.runs != 0; late_runs_possible = late_runs_possible && *F.runs != 0; }
+        if (F.mid_groups) runs_wanted = runs_wanted && *F.mid_groups >= 256;   // (the LDS class carries the run offsets)
         V[kb & 1] = d_sa;
         V[(kb & 1) ^ 1] = w.Va;
         // Random-like input (packed words = few ties expected) of a size whose 2-byte buckets fit a workgroup's
@@ -1204,8 +1208,7 @@ struct SuffixSorter {
         // Packed words were chosen because few ties are expected: the last pass then records the tie
         // structure itself (1 bit per suffix + 2 words per tile and digit, in the idle Vb buffer)
         // instead of writing the sorted words for a rebucket pass to read back.
-        const bool fused_ties = packed && kb >= 2 && n >= (1 << 16) && !env("DQ_NO_FUSED_TIES") &&
-                                !env("DQ_SPARSE");
+        const bool fused_ties = packed && kb >= 2 && n >= (1 << 16) && !F.no_fused_ties && !F.sparse;
         if (fused_ties) {
             const int ib = bit_length((uint64_t)(n - 1));
             const int64_t nwords = (n + 63) / 64;
@@ -1242,7 +1245,7 @@ struct SuffixSorter {
             // (a text that has a good part of itself in runs -- runs_wanted: padded images, sparse files -- is a text of heavy
             // keys: the sorted sample would only say so, 0.5 ms later)
             const bool split_wanted = split_round0_wanted<IdxT>(n, packed, kb, coded);
-            if (split_wanted && (!runs_wanted || env("DQ_SPLIT"))) {
+            if (split_wanted && (!runs_wanted || F.split)) {
                 rc = round0_split(K, coded, &split_done);
                 if (rc != DQ_OK) return rc;
             }
@@ -1280,7 +1283,7 @@ struct SuffixSorter {
         bool predict_dense = false;
         // (below 8 MiB the sample's host round trip costs more than a wrong guess: 8-byte pair keys were chosen because the
         // text repeats itself, so "many ties" is the guess, and the inverse suffix array of a short text is cheap either way)
-        if (n >= (1 << 16) && n < (8 << 20) && !packed && kb == 8 && !env("DQ_SAMPLE_TIES")) {
+        if (n >= (1 << 16) && n < (8 << 20) && !packed && kb == 8) {
             predict_dense = true;
         } else if (n >= (1 << 16) && !packed && kb == 8) {
             constexpr int kSamples = 4096;
@@ -1293,12 +1296,12 @@ struct SuffixSorter {
             // a pair ties with probability ~ (tied fraction) * (1 - 1/group size); 1/12 ~ tied fraction 1/6
             predict_dense = c.pinned[0] * 12 > kSamples;
         }
-        if (const char *v = env("DQ_SPARSE")) predict_dense = atoi(v) == 0;
+        if (F.sparse) predict_dense = *F.sparse == 0;
         // (the suffix-binned build pays once the inverse suffix array outgrows the last-level cache: 4n > 128 MiB.  Below
         // that the plain scatter is ahead -- 64 KiB ... 16 MiB of text: 1-6 %.  DQ_BINNED_ISA=1: from 64 KiB on, for the tests)
-        const bool binned_pays = env("DQ_BINNED_ISA") ? atoi(env("DQ_BINNED_ISA")) != 0 : n > (32ll << 20);
+        const bool binned_pays = F.binned_isa ? *F.binned_isa != 0 : n > (32ll << 20);
         const bool binned = predict_dense && n >= (1 << 16) && binned_pays &&
-                            2 * bit_length((uint64_t)(n - 1)) <= 63 && !env("DQ_NO_BINNED_ISA");
+                            2 * bit_length((uint64_t)(n - 1)) <= 63 && !F.no_binned_isa;
         if (binned) {
             rc = build_isa_binned(K[cur], K[cur ^ 1], kb, kshift0);
             if (rc != DQ_OK) return rc;
@@ -1428,7 +1431,7 @@ struct SuffixSorter {
     int upd_ib() const
     {
         const int ib = bit_length((uint64_t)(n - 1));
-        return (2 * ib <= 64 && !env("DQ_NO_UPD_WORDS")) ? ib : 0;
+        return (2 * ib <= 64 && !flags().no_upd_words) ? ib : 0;
     }
 
     // ISA[s] = new rank for the mU entries a round left in U (stored downward from B + top / Bs + top).  A long list of
@@ -1441,8 +1444,9 @@ struct SuffixSorter {
     int apply_rank_updates(uint64_t *A, IdxT *As, uint64_t *u_end, IdxT *u_suf_end, int64_t mU, int u_ib)
     {
         // (the entries lie downward from u_end / u_suf_end: B + top of the round's partner pair, or the third buffer's)
-        int passes = env("DQ_UPD_BIN") ? std::max(0, std::min(2, atoi(env("DQ_UPD_BIN")))) : 1;
-        const int64_t min_len = env("DQ_UPD_BIN_MIN") ? std::max(1, atoi(env("DQ_UPD_BIN_MIN"))) : kUpdBinMin;
+        const Flags &F = flags();
+        int passes = F.upd_bin.value_or(1);
+        const int64_t min_len = F.upd_bin_min ? *F.upd_bin_min : kUpdBinMin;
         // (the second pass writes into the dead suffix buffer of the round's input list, as 64-bit words)
         const bool second_fits = (size_t)(mU + 1) * 8 <= (size_t)(n + 2) * sizeof(IdxT);
         // Dense updates (at least 1/4 of the array moves: the first round of a text-like input or a binary) are binned by
@@ -1450,8 +1454,8 @@ struct SuffixSorter {
         // 75 M updates: 0.4 + 1.45 ms -> 0.7 + 0.55 ms (the sort 29.87 -> 29.44 ms).  The window kernel moves the whole
         // array once whatever the number of updates, and the second pass costs what it costs: at 1/6 of the array
         // (second round of libtorch_cpu.so, 20.7 M of 134 M) the one-pass form is ahead again.  DQ_UPD_WINDOW = 0 | 1 overrides.
-        bool window = u_ib >= 16 && 2 * u_ib <= 63 && second_fits && mU >= min_len && mU * 4 >= n && !env("DQ_UPD_BIN");
-        if (const char *v = env("DQ_UPD_WINDOW")) window = atoi(v) != 0 && u_ib >= 16 && 2 * u_ib <= 63 && second_fits;
+        bool window = u_ib >= 16 && 2 * u_ib <= 63 && second_fits && mU >= min_len && mU * 4 >= n && !F.upd_bin;
+        if (F.upd_window) window = *F.upd_window != 0 && u_ib >= 16 && 2 * u_ib <= 63 && second_fits;
         if (window) passes = 2;
         if (u_ib < 16 || mU < min_len || (passes == 2 && !second_fits)) passes = window ? 2 : 0;
         if (passes == 0) {
@@ -1528,7 +1532,7 @@ struct SuffixSorter {
         const bool use_mid = mid_g > 0;
         // the radix list's composite keys with rank >> log2(mid_g) as the rank field (dq_mid_groups.h): 57 -> 48 bits for
         // 256 MiB of text, 8 -> 6 digit passes per large-group sort.  DQ_NO_L_SHIFT=1: the full rank, as before round 5.
-        const int l_shift = (use_mid && !env("DQ_NO_L_SHIFT")) ? (mid_g >= 1024 ? 10 : mid_g >= 512 ? 9 : 8) : 0;
+        const int l_shift = (use_mid && !flags().no_l_shift) ? (mid_g >= 1024 ? 10 : mid_g >= 512 ? 9 : 8) : 0;
         if (use_mid) {
             int rc = launch_mid_round(mid_g, m, A, As, lay, h, kbits, ctr, nullptr, m * (8 + wb + wb + wb + 8 + wb), l_shift);
             if (rc != DQ_OK) return rc;
@@ -1551,7 +1555,7 @@ struct SuffixSorter {
         HIP_TRY(hipMemcpyAsync(c.pinned, ctr, sizeof(SmallGroupCounters), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         const int64_t m1 = c.pinned[0] & 0xffffffffll, mU = (int64_t)((uint64_t)c.pinned[0] >> 32), mL = c.pinned[1];
-        if (env("DQ_TRACE"))
+        if (flags().trace)
             fprintf(stderr, "[dq] %s round h=%lld m=%lld%s -> tied %lld, to radix %lld, moved %lld\n",
                     use_mid ? "mid-group" : "small", (long long)h,
                     (long long)m, wide_list(m) ? " (wide)" : "", (long long)m1, (long long)mL, (long long)mU);
@@ -1629,7 +1633,7 @@ struct SuffixSorter {
         // ONE rank, behind its run) and not on long lists, whose rounds are bound by the sectors their gathers move.
         // DQ_CHAIN_STEPS = 1 | 3 overrides.
         int steps = (kCap == 0 && sizeof(IdxT) == 4 && m_in < kSgShortList && !runs_on) ? kChainSteps : 1;
-        if (const char *v = env("DQ_CHAIN_STEPS")) steps = (atoi(v) >= kChainSteps && kCap == 0 && sizeof(IdxT) == 4 && !runs_on) ? kChainSteps : 1;
+        if (const std::optional<int> v = flags().chain_steps) steps = (*v >= kChainSteps && kCap == 0 && sizeof(IdxT) == 4 && !runs_on) ? kChainSteps : 1;
         for (int r = 0; r < chain_len; ++r) {
             uint64_t *A = Kr[rcur], *B = Kr[rcur ^ 1];
             IdxT *As = Vr[rcur], *Bs = Vr[rcur ^ 1];
@@ -1661,7 +1665,7 @@ struct SuffixSorter {
         TailResult *res = reinterpret_cast<TailResult *>(w.sg_ctr + kSgChain);
         const bool spec_tail = tail_behind_chain;
         if (spec_tail) {
-            if (env("DQ_TRACE")) fprintf(stderr, "[dq] tail kernel launched behind a chain of %d at h=%lld\n", chain_len, (long long)hr);
+            if (flags().trace) fprintf(stderr, "[dq] tail kernel launched behind a chain of %d at h=%lld\n", chain_len, (long long)hr);
             LAUNCH(L, DQ_K_SMALL_ROUND, m_in, 0,
                    launch_tail((const uint64_t *)Kr[rcur], (const IdxT *)Vr[rcur], (int)0, hr, res,
                                (const unsigned long long *)&w.sg_ctr[chain_len - 1].tied_moved));
@@ -1679,7 +1683,7 @@ struct SuffixSorter {
         if (spec_tail && cur_m > 0) {
             const int64_t rounds = c.pinned[2 * kSgChain], entries = c.pinned[2 * kSgChain + 1], left = c.pinned[2 * kSgChain + 2];
             if (cur_m <= kTailMax) {                       // the kernel took the list
-                if (env("DQ_TRACE"))
+                if (flags().trace)
                     fprintf(stderr, "[dq] tail behind a chain of %d: %lld tied suffixes from h=%lld on, %lld rounds (%lld list entries in all)\n",
                             chain_len, (long long)cur_m, (long long)hr, (long long)rounds, (long long)entries);
                 if (left != 0) return fail(DQ_ERR_HIP, "tail rounds did not finish (round bound hit)");
@@ -1709,12 +1713,7 @@ struct SuffixSorter {
         // up to 3 when the list is longer than n/3: the records (1.5 per entry for groups of 4, at most 1 for
         // pairs and triples) must fit behind `half`.
         int maxg = m >= kSgShortList ? 2 : (m * 3 <= n ? kPcMaxG : (m * 2 <= n ? 3 : 2));
-        // (experiment knob: groups of 3 / 4 as their pairs on long lists too, where the records fit)
-        if (const char *v = env("DQ_PAIR_MAXG_LONG")) {
-            const int g = atoi(v);
-            if (m >= kSgShortList && g >= 3) maxg = (m * 3 <= n && g >= 4) ? kPcMaxG : (m * 2 <= n ? 3 : 2);
-        }
-        if (const char *v = env("DQ_PAIR_MAXG")) maxg = std::min(maxg >= 3 ? maxg : 2, std::max(2, atoi(v)));
+        if (const std::optional<int> v = flags().pair_maxg) maxg = std::min(maxg >= 3 ? maxg : 2, *v);
         // record = d << xbits | x.  Pairs only: x padded to whole digits, so that the digit passes over x see nothing of d
         const int xbits = maxg == 2 ? (ib + 7) / 8 * 8 : ib;
         uint32_t *tile_cnt = w.pc_tiles;
@@ -1736,7 +1735,7 @@ struct SuffixSorter {
         // a small-group round, or from the end of a longer list if they still fit
         const int64_t half = std::max(sg_half(), (m + 1) & ~(int64_t)1);
         if (cnt == 0 || half + cnt > n || (!forced && copied * 5 > m * 3)) {
-            if (env("DQ_TRACE"))
+            if (flags().trace)
                 fprintf(stderr, "[dq] pair chains h=%lld m=%lld: given up, %lld entries in groups > %d\n", (long long)h, (long long)m,
                         (long long)copied, maxg);
             *outcome = 0;
@@ -1792,7 +1791,7 @@ struct SuffixSorter {
         rcur ^= 1;
         m = c.pinned[1];
         if ((m_in - m) * 2 >= m_in) *outcome = 2;         // at least half of the list was finished
-        if (env("DQ_TRACE"))
+        if (flags().trace)
             fprintf(stderr, "[dq] pair chains h=%lld m=%lld (groups <= %d): %lld pair records, %lld entries in larger groups, %lld entries left\n",
                     (long long)h, (long long)m_in, maxg, (long long)cnt, (long long)copied, (long long)m);
         return DQ_OK;
@@ -1801,7 +1800,8 @@ struct SuffixSorter {
     // (the three-step form of the tail kernel where its 32-bit keys hold rank + h and no run lengths are in force)
     void launch_tail(const uint64_t *rank, const IdxT *suf, int mm, int64_t hh, TailResult *res, const unsigned long long *m_dev)
     {
-        const bool three = sizeof(IdxT) == 4 && !runs_on && !(env("DQ_CHAIN_STEPS") && atoi(env("DQ_CHAIN_STEPS")) < kChainSteps);
+        const std::optional<int> forced = flags().chain_steps;
+        const bool three = sizeof(IdxT) == 4 && !runs_on && !(forced && *forced < kChainSteps);
         if constexpr (sizeof(IdxT) == 4) {
             if (three) {
                 hipLaunchKernelGGL((tail_rounds_kernel<IdxT, uint32_t, kChainSteps>), dim3(1), dim3(kTailThreads), 0, st, rank, suf, mm, n, hh,
@@ -1825,7 +1825,7 @@ struct SuffixSorter {
         HIP_TRY(hipMemcpyAsync(c.pinned, res, sizeof(TailResult), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         const int64_t rounds = c.pinned[0], entries = c.pinned[1], left = c.pinned[2];
-        if (env("DQ_TRACE"))
+        if (flags().trace)
             fprintf(stderr, "[dq] tail: %lld tied suffixes from h=%lld on, %lld rounds in one launch (%lld list entries in all)\n",
                     (long long)m, (long long)h, (long long)rounds, (long long)entries);
         if (left != 0) return fail(DQ_ERR_HIP, "tail rounds did not finish (round bound hit)");
@@ -1877,7 +1877,7 @@ struct SuffixSorter {
         HIP_TRY(hipMemcpyAsync(c.pinned, ctr, sizeof(PairCounters), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         const int64_t groups = c.pinned[0], kept = c.pinned[1];
-        if (env("DQ_TRACE"))
+        if (flags().trace)
             fprintf(stderr, "[dq] doubled text at h=%lld: %lld of %lld tied suffixes in pairs (i, i + n/2), %lld other groups\n", (long long)h,
                     (long long)(m - kept), (long long)m, (long long)groups);
         if (kept == 0) { *done = true; return DQ_OK; }
@@ -1896,19 +1896,20 @@ struct SuffixSorter {
 
     int run()
     {
+        const Flags &F = flags();
         t_info[0] = t_info[1] = t_info[2] = 0;
         HIP_TRY(hipMemsetAsync(w.totals, 0, 64, st));
         bool dense_built = false;
         int rc = round0(&dense_built);
         if (rc != DQ_OK) return rc;
         t_info[1] = m;
-        if (env("DQ_TRACE"))
+        if (F.trace)
             fprintf(stderr, "[dq] after round 0: n=%lld, %d index bits, %lld tied suffixes, third list buffer %s\n", (long long)n,
                     bit_length((uint64_t)(n - 1)), (long long)m, w.X ? "carved" : "left out");
         if (m == 0) return flush_profile(c);
 
         bool sparse = m * 6 <= n || shallow_ties;
-        if (const char *v = env("DQ_SPARSE")) sparse = atoi(v) != 0;
+        if (F.sparse) sparse = *F.sparse != 0;
         // the ISA exists and the list is keyed / laid out for a radix round -- or carries its ranks as 32-bit values
         // for the first LDS-class round (first_rank32: nothing else may read Kr[rcur] as ranks before that round)
         if (keys_ready || list_ungrouped || first_rank32) sparse = false;
@@ -1922,7 +1923,7 @@ struct SuffixSorter {
             // (a period other than 1 -- the caller's hint, or DQ_RUN_PERIOD in the tests -- must not exceed the depth the
             // groups are tied to: the rules of dq_runs.h hold for P <= h)
             int period = period_hint > 0 ? period_hint : 1;
-            if (const char *v = env("DQ_RUN_PERIOD")) period = std::max(1, atoi(v));
+            if (F.run_period) period = *F.run_period;
             if (period > h || period > 64) period = 1;
             rc = compute_run_lengths(period);
             if (rc != DQ_OK) return rc;
@@ -1930,7 +1931,7 @@ struct SuffixSorter {
             run_order = period;
             t_info[0] += 1;
             t_info[2] += m;
-            if (env("DQ_TRACE"))
+            if (F.trace)
                 fprintf(stderr, "[dq] run-order round (period %d) at h=%lld on %lld tied suffixes\n", period, (long long)h, (long long)m);
             rc = (uses_small_round(m) && !list_ungrouped) ? doubling_round_small(32) : doubling_round_radix(32, 0);
             run_order = 0;
@@ -1943,7 +1944,7 @@ struct SuffixSorter {
         int64_t pair_h = 0;               // h of the last phase
         int64_t abort_h = 0, abort_m = 0; // h and list length when a phase last gave up after its count
         // (DQ_TAIL_MAX = 0 ... 4096: the list length from which the rest of the sort is one launch; 0 = never)
-        const int64_t tail_max = env("DQ_TAIL_MAX") ? std::max(0, std::min(kTailMax, atoi(env("DQ_TAIL_MAX")))) : kTailMax;
+        const int64_t tail_max = F.tail_max ? std::min(kTailMax, *F.tail_max) : kTailMax;
         while (m > 0) {
             if (m <= tail_max && fits32() && !keys_ready && !list_ungrouped && !first_rank32 && !run_order) {
                 rc = tail_rounds();
@@ -1962,19 +1963,18 @@ struct SuffixSorter {
             // at a time).  A phase gives up after its count pass when most of the list sits in larger groups, and
             // is tried again once the list has halved or h has grown 16-fold.
             const bool stagnant = m_before > 0 && m * 5 > m_before * 3;
-            const char *pc = env("DQ_PAIR_CHAINS");
-            const int64_t pair_chain_min = env("DQ_PAIR_CHAINS_MIN") ? std::max(1, atoi(env("DQ_PAIR_CHAINS_MIN"))) : kPairChainMinM;
+            const std::optional<int> pc = F.pair_chains;
+            const int64_t pair_chain_min = F.pair_chains_min ? *F.pair_chains_min : kPairChainMinM;
             const bool after_abort = abort_h == 0 || m * 2 <= abort_m || h >= 16 * abort_h;
-            const bool want = pc ? atoi(pc) != 0 && (m_before > 0 || atoi(pc) > 1)
+            const bool want = pc ? *pc != 0 && (m_before > 0 || *pc > 1)
                                  : m_before > 0 && m >= pair_chain_min && after_abort &&
                                    (pair_tries == 0 || (pair_paid ? stagnant : h >= 16 * pair_h));
-            const int max_tries = env("DQ_PAIR_TRIES") ? atoi(env("DQ_PAIR_TRIES")) : kPairChainTries;
-            if (want && pair_tries < max_tries && pair_aborts < 2 * kPairChainTries && !env("DQ_NO_SMALL") && fits32() &&
+            if (want && pair_tries < kPairChainTries && pair_aborts < 2 * kPairChainTries && !F.no_small && fits32() &&
                 m < n && !keys_ready && !list_ungrouped && !first_rank32) {
                 int outcome = 0;
                 m_before = 0;
                 const int64_t m_try = m;
-                rc = pair_chain_phase(&outcome, pc != nullptr);
+                rc = pair_chain_phase(&outcome, pc.has_value());
                 if (rc != DQ_OK) return rc;
                 if (outcome == 0) { ++pair_aborts; abort_h = h; abort_m = m_try; }
                 else { ++pair_tries; pair_paid = outcome == 2; pair_h = h; abort_h = 0; }
@@ -1982,31 +1982,29 @@ struct SuffixSorter {
             }
             // runs seen late (see long_run_seen): the large groups have stopped shrinking -- run lengths now, one
             // run-order round at the current depth on the current list, the rank behind the run from then on
-            const int64_t late_min = env("DQ_LATE_RUNS_MIN") ? std::max(1, atoi(env("DQ_LATE_RUNS_MIN"))) : (1 << 15);   // (tests: small inputs)
+            const int64_t late_min = F.late_runs_min.value_or(1 << 15);   // (tests: small inputs)
             // (the run lengths are a sweep over the whole text, what they save is a few passes over the large groups:
             // librocsparse.so, 256 MiB, 0.32 M members of large groups -- 2.2 ms of run lengths for nothing)
-            const int64_t late_share = env("DQ_LATE_RUNS_SHARE") ? std::max(1, atoi(env("DQ_LATE_RUNS_SHARE")))
-                                       : env("DQ_LATE_RUNS_MIN") ? (int64_t)1 << 30 : 64;      // (the tests' knob lifts this bar too)
-            // (stagnation: the large groups kept at least late_ratio / 8 of their members over the last round.  Measured with
+            const int64_t late_share = F.late_runs_min ? (int64_t)1 << 30 : 64;      // (the tests' knob lifts this bar too)
+            // (stagnation: the large groups kept at least 7 / 8 of their members over the last round.  Measured with
             // 5 / 8 and 4 / 8, which call the round one doubling earlier on libtorch_cpu.so: 25.3 / 25.5 ms against 24.8)
-            const int64_t late_ratio = env("DQ_LATE_RUNS_RATIO") ? std::max(1, std::min(8, atoi(env("DQ_LATE_RUNS_RATIO")))) : 7;
             if (late_runs_possible && !runs_on && !runs_late_tried && !run_order && last_large >= late_min && prev_large > 0 &&
-                last_large * late_share >= n && last_large * 8 >= prev_large * late_ratio && h >= 32 && 32 + rbits <= 64 && uses_small_round(m) && !keys_ready &&
-                !list_ungrouped && !first_rank32 && mid_group_cap(m) > 0 && !env("DQ_NO_LATE_RUNS")) {
+                last_large * late_share >= n && last_large * 8 >= prev_large * 7 && h >= 32 && 32 + rbits <= 64 && uses_small_round(m) && !keys_ready &&
+                !list_ungrouped && !first_rank32 && mid_group_cap(m) > 0 && !F.no_late_runs) {
                 runs_late_tried = true;
                 // the rules hold for stretches that repeat with any period P <= h (tests/test_models_cpu.py has the
                 // model): P = 64 (or the largest power of two <= h) takes runs of one byte and tables of 2-, 4-, ...
                 // 64-byte entries alike
                 int period = 1;
                 while (period * 2 <= 64 && period * 2 <= h) period *= 2;
-                if (const char *v = env("DQ_RUN_PERIOD")) period = std::max(1, std::min<int>((int)std::min<int64_t>(h, 1 << 20), atoi(v)));
+                if (F.run_period) period = std::min<int>((int)std::min<int64_t>(h, 1 << 20), *F.run_period);
                 rc = compute_run_lengths(period);
                 if (rc != DQ_OK) return rc;
                 runs_on = true;
                 run_order = period;                        // (the kernels take the period from here)
                 t_info[0] += 1;
                 t_info[2] += m;
-                if (env("DQ_TRACE"))
+                if (F.trace)
                     fprintf(stderr, "[dq] late run-order round (period %d) at h=%lld on %lld tied suffixes (%lld in large groups, %lld the round before)\n",
                             period, (long long)h, (long long)m, (long long)last_large, (long long)prev_large);
                 rc = doubling_round_small(32);
@@ -2018,7 +2016,7 @@ struct SuffixSorter {
             m_before = m;
             // (doubled text: a look at the pairs after every round while the list is long)
             if (only_small_groups && uses_small_round(m) && !keys_ready && !list_ungrouped && (twin_half == 0 || m < (1 << 16)) &&
-                !env("DQ_NO_CHAIN")) {
+                !F.no_chain) {
                 tail_behind_chain = tail_max >= kTailMax && m <= 4 * tail_max && fits32();      // (the kernel's own bound is kTailMax)
                 // (two rounds, then four, then eight per host round trip: a list that hovers just above the tail
                 // kernel's reach -- a long repeat among a few thousand suffixes -- must not pay a round trip every two rounds)
@@ -2038,10 +2036,10 @@ struct SuffixSorter {
             // (a list that still carries its ranks as 32-bit values for the first LDS-class round -- first_rank32 -- has
             // nothing in Kr[rcur] for the radix path to read: the test flag is ignored for that round; kbits + rbits > 64
             // cannot coincide with it, n < 2^32 there)
-            const int rshift = (kbits + rbits > 64 || (env("DQ_FORCE_RSHIFT") && !first_rank32)) ? 1 : 0;
+            const int rshift = (kbits + rbits > 64 || (F.force_rshift && !first_rank32)) ? 1 : 0;
             if (rshift && first_rank32) return fail(DQ_ERR_HIP, "rank-shift round on a list with 32-bit ranks");
             if (kbits + rbits - rshift > 64) return fail(DQ_ERR_TOO_LARGE, "composite key exceeds 64 bits");
-            if (rshift && env("DQ_TRACE"))
+            if (rshift && F.trace)
                 fprintf(stderr, "[dq] rank-shift round at h=%lld on %lld tied suffixes (kbits %d + rbits %d)%s\n", (long long)h,
                         (long long)m, kbits, rbits, kbits + rbits > 64 ? "" : " (forced)");
             if (rshift && keys_ready) {
@@ -2067,8 +2065,9 @@ int sufsort_device(DeviceCtx &c, hipStream_t st, Workspace<IdxT> &w, int64_t n, 
 {
     SuffixSorter<IdxT> sorter(c, st, w, n, d_sa);
     // (DQ_ASSUME_DOUBLED: the tests vouch for their inputs through the public entry points)
-    if ((hints.doubled || env("DQ_ASSUME_DOUBLED")) && n % 2 == 0 && !env("DQ_NO_TWINS")) sorter.twin_half = n / 2;
-    if (hints.run_period > 0 && !env("DQ_NO_PERIOD_HINT")) sorter.period_hint = hints.run_period;
+    const Flags &F = flags();
+    if ((hints.doubled || F.assume_doubled) && n % 2 == 0 && !F.no_twins) sorter.twin_half = n / 2;
+    if (hints.run_period > 0 && !F.no_period_hint) sorter.period_hint = hints.run_period;
     sorter.text_src = text_src;
     return sorter.run();
 }
@@ -2090,14 +2089,15 @@ int sufsort_small(DeviceCtx &c, hipStream_t st, const uint8_t *text, int64_t n, 
 template <typename IdxT>
 bool choose_list_buffers(DeviceCtx &c, int64_t n, bool with_sa)
 {
-    bool lists = n < (1ll << 32) && !env("DQ_NO_LIST_BUFFERS");
+    const Flags &F = flags();
+    bool lists = n < (1ll << 32) && !F.no_list_buffers;
     size_t free_b = 0, total_b = 0;
     if (lists && c.ws_bytes < carve<IdxT>(nullptr, n, with_sa, true).bytes && hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
         // (where the driver cannot say, the allocation decides, as before)
         const uint64_t avail = (uint64_t)free_b + c.ws_bytes;
         lists = with_list_buffers<IdxT>(n, with_sa, avail > kWsReserve ? avail - kWsReserve : 0);
     }
-    if (env("DQ_TRACE") && !lists)
+    if (F.trace && !lists)
         fprintf(stderr, "[dq] workspace without the third list buffer (n=%lld; %.1f GB free, %.1f GB cached)\n", (long long)n,
                 free_b / 1e9, c.ws_bytes / 1e9);
     return lists;
@@ -2198,7 +2198,7 @@ int sufsort_dev(const void *d_text, int64_t n, void *d_sa, int32_t device, void 
     hipStream_t st = stream ? (hipStream_t)stream : c.stream;
     // The library works on a padded, 16-byte aligned copy of the text.  The copy is made by the pass that reads the
     // text first anyway (text_hist_kernel) when the caller's buffer is 16-byte aligned; DQ_TEXT_COPY=1: by a copy in front.
-    const bool fused_copy = (reinterpret_cast<uintptr_t>(d_text) & 15) == 0 && !env("DQ_TEXT_COPY");
+    const bool fused_copy = (reinterpret_cast<uintptr_t>(d_text) & 15) == 0 && !flags().text_copy;
     if (!fused_copy) HIP_TRY(hipMemcpyAsync(w.text, d_text, (size_t)n, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemsetAsync(w.text + n, 0, 64, st));
     rc = sufsort_device<IdxT>(c, st, w, n, (IdxT *)d_sa, SortHints(), fused_copy ? (const uint8_t *)d_text : nullptr);

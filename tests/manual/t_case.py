@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """One named input under several forced settings: device-resident time, per-kernel profile, DQ_TRACE of the rounds;
 every variant's suffix array is compared with the first one's (which is checked by sufcheck + sampled strict pairs).
-usage: t_case.py <uniform256|enwik256|enwik64|textk1024|libtorch128|rocsparse256|rocsparse64> "" "DQ_X=1,DQ_Y=2" ...   (T_TRACE=1: per-round trace)"""
+usage: t_case.py <uniform256|enwik256|enwik64|textk1024|libtorch128|rocsparse256|rocsparse64> "" "DQ_NO_CHAIN=1,DQ_TAIL_MAX=0" ...   (T_TRACE=1: per-round trace)"""
 import glob, os, sys, time
 os.environ.setdefault("DQ_DEBUG_FLAGS", "1")      # the library honours its DQ_* overrides only under this gate
 import numpy as np

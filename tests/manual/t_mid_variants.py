@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Mid-size text-like inputs under forced settings: wall clock per sort (device-resident), launches, rounds.
-usage: t_mid_variants.py "" "DQ_MID_SHORT=1" ..."""
+usage: t_mid_variants.py "" "DQ_MID_GROUPS=0" ..."""
 import os, sys, time
 os.environ.setdefault("DQ_DEBUG_FLAGS", "1")      # the library honours its DQ_* overrides only under this gate
 import numpy as np

@@ -20,7 +20,7 @@ CSRC = os.path.join(ROOT, "deltaq_amd", "csrc")
 def test_hostile_patches_under_asan_ubsan():
     exe = os.path.join(NATIVE, "patch_fuzz")
     src = os.path.join(NATIVE, "patch_fuzz.cpp")
-    deps = [src] + [os.path.join(CSRC, h) for h in ("dq_bspatch.h", "dq_bsdiff.h", "dq_bz2.h")]
+    deps = [src] + [os.path.join(CSRC, h) for h in ("dq_bspatch.h", "dq_bsdiff.h", "dq_bz2.h", "dq_flags.h")]
     if not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(d) for d in deps):
         subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                         "-pthread", src, "-o", exe], check=True)
@@ -37,7 +37,7 @@ def test_host_pieces_from_six_threads_under_tsan():
     threads of their own) and compare the result with the stream framed at once."""
     exe = os.path.join(NATIVE, "host_tsan")
     src = os.path.join(NATIVE, "host_tsan.cpp")
-    deps = [src] + [os.path.join(CSRC, h) for h in ("dq_bspatch.h", "dq_bsdiff.h", "dq_bz2.h", "dq_alpha_code.h")]
+    deps = [src] + [os.path.join(CSRC, h) for h in ("dq_bspatch.h", "dq_bsdiff.h", "dq_bz2.h", "dq_alpha_code.h", "dq_flags.h")]
     if not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(d) for d in deps):
         subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=thread", src, "-o", exe, "-pthread"], check=True)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
