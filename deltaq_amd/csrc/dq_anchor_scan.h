@@ -90,6 +90,9 @@ struct AnchorCtl {
     unsigned long long t_begin, t_end;                    // out: the device's 100 MHz clock when workgroup 0 began and ended (DQ_TRACE)
 };
 constexpr unsigned long long kAsSilent = 1ull << 63;      // list entry of an iteration end that emitted nothing: kAsSilent | cursor << 32
+// a list entry as the host reads it (an emitted one is cursor << 32 | hit_pos)
+struct AnchorEntry { int64_t cursor, hit_pos; bool silent; };
+inline AnchorEntry decode_entry(unsigned long long v) { return {(int64_t)((v & ~kAsSilent) >> 32), (int64_t)(uint32_t)v, (v & kAsSilent) != 0}; }
 static_assert(sizeof(AnchorCtl) <= 248, "a control block and the word behind it fill 256 bytes");
 
 // One launch carries up to kScanMaxChains grids ("chains"): workgroup b belongs to chain b / groups and works on that

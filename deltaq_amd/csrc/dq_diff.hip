@@ -6,6 +6,7 @@
 #include "dq_runtime.h"
 #include "dq_match_search.h"
 #include "dq_anchor_scan.h"
+#include "dq_scan_wait.h"
 #include "dq_bz2.h"
 #include "dq_bsdiff.h"
 #include "dq_bspatch.h"
@@ -648,32 +649,32 @@ struct ChainEmitter {
     bsdiff::TripleEmitter::Anchor first;                  // the state it began with
     std::thread th;
 
-    void run(const uint8_t *old, int64_t n, const uint8_t *nw, int64_t m, const unsigned long long *ring, int64_t start)
+    void run(const uint8_t *old, int64_t n, const uint8_t *nw, int64_t m, const unsigned long long *ring)
     {
         try {
             bsdiff::TripleEmitter em(old, n, nw, m, priv);
             em.prev = first;
-            (void)start;
             for (int64_t i = 0; !stop.load(std::memory_order_relaxed);) {
                 const int64_t over = nent.load(std::memory_order_acquire);
                 if (over >= 0 && i >= over) return;
                 if (i >= kAnchorRecs) return;
                 const unsigned long long v = __atomic_load_n(&ring[i], __ATOMIC_ACQUIRE);
-                if (v == ~0ull) {
+                if (v == kAnchorPending) {
                     for (int q = 0; q < 64; ++q) __builtin_ia32_pause();
                     std::this_thread::yield();
                     continue;
                 }
-                if (!(v & kAsSilent)) {
+                const AnchorEntry e = decode_entry(v);
+                if (!e.silent) {
                     // (a triple adds at most the bytes between the last extension and this anchor to either stream; the
                     // vectors may not move under the thread that reads them: out of room means out of this thread's job)
-                    const size_t span = (size_t)((int64_t)(v >> 32) - em.prev.at) + 16;
+                    const size_t span = (size_t)(e.cursor - em.prev.at) + 16;
                     if (priv.diff.size() + span > priv.diff.capacity() || priv.extra.size() + span > priv.extra.capacity() ||
                         priv.ctrl.size() + 24 > priv.ctrl.capacity() || marks.size() + 1 > marks.capacity()) {
                         failed.store(1, std::memory_order_release);
                         return;
                     }
-                    em.take((int64_t)(v >> 32), (int64_t)(uint32_t)v);
+                    em.take(e.cursor, e.hit_pos);
                     marks.push_back(Mark{i, em.prev, priv.ctrl.size(), priv.diff.size(), priv.extra.size()});
                     n_marks.store((int64_t)marks.size(), std::memory_order_release);
                 }
@@ -741,145 +742,165 @@ struct ScanChain {
     int64_t shift = 0;                                    // shift in force behind the entries read so far
     ChainEmitter *em = nullptr;                           // its own emitter thread (speculative chains of a launch; kept in the device context)
     int64_t mark_at = 0;                                  // marks of it whose entries the following thread has passed
+    // the entry at `taken` if the current launch has written it, else kAnchorPending
+    unsigned long long peek() const { return (running || taken < nent) && taken < kAnchorRecs ? __atomic_load_n(&ring[taken], __ATOMIC_ACQUIRE) : kAnchorPending; }
 };
 
-int scan_on_device(const DiffIndex &ix, DeviceCtx &c, char *d_new, char *scratch, char *pinned_chains, const uint8_t *nw,
-                   int64_t m, bsdiff::RawStreams &raw, bool *retry_on_host, PatchFramer *framer)
+// The grids are persistent and their workgroups wait for each other's answers: all of them must be on the device at once.
+// What the device holds (occupancy of this kernel x compute units; a partitioned or smaller part holds fewer) bounds
+// them, asked once per device.  A device that refuses the widest grid's LDS holds none: the host loop takes its files.
+void probe_scan_capacity(DeviceCtx &c, int dev, bool trace)
 {
-    *retry_on_host = false;
-    bsdiff::TripleEmitter em(ix.old, ix.n, nw, m, raw);
-    // (short files: two more threads cost more than the framing they would hide)
+    // (the widest grid's workgroups ask for a little more than 64 KB of dynamic LDS)
+    const int lds = (int)as_agp_bytes(kAsMaxGroups);
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(&anchor_scan_kernel<int32_t, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void *>(&anchor_scan_kernel<int32_t, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
+        (void)hipGetLastError();                          // (not to be met by the next launch's check)
+        c.scan_groups_cap = c.scan_groups_cap_narrow = 0;
+        return;
+    }
+    int per_cu = 0, per_cu_narrow = 0, ncu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, anchor_scan_kernel<int32_t, 1>, kAsThreads, as_agp_bytes(kAsMaxGroups)) != hipSuccess) per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_narrow, anchor_scan_kernel<int32_t, 2>, kAsThreads, as_agp_bytes(kScanChainGroups)) != hipSuccess)
+        per_cu_narrow = 0;
+    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) ncu = 0;
+    c.scan_groups_cap = per_cu > 0 && ncu > 0 ? per_cu * ncu : kAsGroups;       // (unknown: as before)
+    c.scan_groups_cap_narrow = per_cu_narrow > 0 && ncu > 0 ? per_cu_narrow * ncu : c.scan_groups_cap;
+    if (trace) fprintf(stderr, "[dq] anchor scan: %d workgroups per compute unit (%d of a grid of %d) x %d compute units resident\n", per_cu, per_cu_narrow,
+                       kScanChainGroups, ncu);
+}
+
+// One device scan of one new file: the chains, their launches, and the caller's thread, which follows one chain at a
+// time -- emits its triples or copies them from the chain's own emitter -- and joins the next where they meet.
+struct ChainScan {
+    const DiffIndex &ix;
+    DeviceCtx &c;
+    char *const d_new, *const scratch, *const pinned_chains;
+    const uint8_t *const nw;
+    const int64_t m;
+    bsdiff::RawStreams &raw;
+    PatchFramer *const framer;
     const Flags &F = flags();
-    const int64_t follow_min = F.frame_follow_min.value_or((int64_t)256 << 10);
-    if (framer && m >= follow_min && framer->start(raw, m)) em.progress = framer->final_len;
-    std::lock_guard<std::mutex> lk(c.mu);                 // (the device context's stream and pinned areas)
-    int rc = init_ctx(c, ix.dev);
-    if (rc != DQ_OK) return rc;
     const bool trace = F.trace.has_value();
-    // The grids are persistent and their workgroups wait for each other's answers: all of them must be on the device at
-    // once.  What the device holds (occupancy of this kernel x compute units; a partitioned or smaller part holds
-    // fewer) bounds them; below 8 workgroups, or for a while after a launch whose workgroups waited in vain (a device
-    // kept full by other streams or processes -- every such launch costs its spin bound), the host loop over windows
-    // takes the file instead.
-    if (c.scan_groups_cap < 0) {
-        int per_cu = 0, per_cu_narrow = 0, ncu = 0;
-        // (the widest grid's workgroups ask for a little more than 64 KB of dynamic LDS)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&anchor_scan_kernel<int32_t, 1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)as_agp_bytes(kAsMaxGroups)));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&anchor_scan_kernel<int32_t, 2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)as_agp_bytes(kAsMaxGroups)));
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, anchor_scan_kernel<int32_t, 1>, kAsThreads, as_agp_bytes(kAsMaxGroups)) != hipSuccess) per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_narrow, anchor_scan_kernel<int32_t, 2>, kAsThreads, as_agp_bytes(kScanChainGroups)) != hipSuccess)
-            per_cu_narrow = 0;
-        if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ix.dev) != hipSuccess) ncu = 0;
-        c.scan_groups_cap = per_cu > 0 && ncu > 0 ? per_cu * ncu : kAsGroups;       // (unknown: as before)
-        c.scan_groups_cap_narrow = per_cu_narrow > 0 && ncu > 0 ? per_cu_narrow * ncu : c.scan_groups_cap;
-        if (trace) fprintf(stderr, "[dq] anchor scan: %d workgroups per compute unit (%d of a grid of %d) x %d compute units resident\n", per_cu, per_cu_narrow,
-                           kScanChainGroups, ncu);
-    }
-    int cap = c.scan_groups_cap;
-    if (F.scan_groups_cap) cap = std::min(cap, *F.scan_groups_cap);           // (tests: a small device)
-    const int asked = F.scan_groups ? std::min(kAsMaxGroups, *F.scan_groups) : 0;
-    const int groups_alone = std::min(asked ? asked : kAsGroups, cap);                 // a grid that is alone on the file
-    const int groups_chain = std::min(asked ? asked : kScanChainGroups, cap);          // one of several
-    // (workgroups of narrow grids the device holds at once: more than of the widest, their LDS is a quarter)
-    int cap_chains = groups_chain <= kScanChainGroups ? std::max(cap, c.scan_groups_cap_narrow) : cap;
-    if (F.scan_groups_cap) cap_chains = std::min(cap_chains, *F.scan_groups_cap);
-    int chains_max = F.scan_chains ? std::min(kScanMaxChains, *F.scan_chains) : kScanChains;
-    if (groups_chain >= 8) chains_max = std::min(chains_max, cap_chains / groups_chain);
-    const int64_t min_seg = F.scan_min_seg.value_or(kScanMinSegment);
-    const int64_t extra_ends = F.scan_extra.value_or(kScanExtra);
-    const int64_t lane_budget = F.scan_lane_budget.value_or(kScanLaneBudget);
-    t_diff_info[4] = chains_max > 1 && m >= 2 * min_seg ? groups_chain : groups_alone;
-    if (groups_alone < 8 || c.scan_skip > 0) {
-        if (c.scan_skip > 0) --c.scan_skip;
-        // (not an error: the host loop takes the file and the call succeeds -- dq_last_error() must not be left saying
-        // otherwise behind a DQ_OK, so nothing goes through fail(); dq_last_diff_info counts the file, skipped ones too)
-        if (trace)
-            fprintf(stderr, "[dq] %s\n", groups_alone < 8 ? "anchor scan: the device holds fewer than 8 of its workgroups" : "anchor scan: skipped after a starved launch");
-        *retry_on_host = true;
-        return DQ_ERR_HIP;
-    }
+    bsdiff::TripleEmitter em{ix.old, ix.n, nw, m, raw};
+    int cap = 0, groups_alone = 0, groups_chain = 0, chains_max = 0;
+    int64_t min_seg = 0, extra_ends = 0, lane_budget = 0;
+    // emitters of the speculative chains on threads of their own (DQ_SCAN_PAR_EMIT=0: everything on this thread)
+    const bool par_emit = F.scan_par_emit.value_or(1) != 0;
     ScanChain ch[kScanMaxChains];
-    for (int k = 0; k < kScanMaxChains; ++k) {
-        ScanChain &x = ch[k];
-        char *hp = pinned_chains + kAsSlotAt + (size_t)k * kAsSlotBytes;
-        x.d_ctl = reinterpret_cast<AnchorCtl *>(scratch + (size_t)k * 256);
-        x.h_up = reinterpret_cast<AnchorCtl *>(pinned_chains + (size_t)k * 256);
-        x.ring = reinterpret_cast<unsigned long long *>(hp);
-        x.cum = x.ring + kAnchorRecs;
-        x.h_out = reinterpret_cast<const AnchorCtl *>(x.ring + 2 * kAnchorRecs);
-        x.h_landed = x.ring + 2 * kAnchorRecs + 31;
-        x.dirty = &c.scan_dirty[k];
-    }
-    struct EmitterGuard {                                 // (no emitter thread outlives this call, however it is left)
-        DeviceCtx &c;
-        ~EmitterGuard()
-        {
-            if (!c.scan_pool) return;
-            ScanPool &pool = *static_cast<ScanPool *>(c.scan_pool.get());
-            for (auto &e : pool.em) if (e) e->trim();
-        }
-    } emitter_guard{c};
-    double emit_ms = 0;                                   // (DQ_TRACE: time inside the emitter)
-    double emit_phase_ms[3] = {0, 0, 0};
-    if (trace) em.phase_ms = emit_phase_ms;
-    const auto t_host0 = std::chrono::steady_clock::now();
-    auto host_ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host0).count(); };
-    // Whatever way this function is left while a launch is out -- a failed copy, an exception out of the emitter -- the
-    // kernel must be off the stream before anybody refills the lists or the answer buffers: its chains are told to stop
-    // (the error word every spin looks at), the stream drains, the timing events go back to their pool.
+    int cur = 0;                                          // the chain this thread follows
+    // Search counts along the path this thread followed: the last chain's own count + (count at the entry a chain was
+    // left at - count at the entry its successor was joined at) over the joins; the counts beside the entries are read
+    // once the launch that wrote them has said it is over (mod 2^64: only the sum has to be right).
+    struct Count { int chain; int64_t at; bool minus, read; };
+    std::vector<Count> counts;
+    unsigned long long joined_searches = 0;
     bool launch_out = false;                              // a launch may still be on the stream
-    struct LaunchGuard {
-        DeviceCtx &c; ScanChain *ch; bool &out;
-        ~LaunchGuard()
-        {
-            if (!out) return;
+    bool gave_up = false;
+    int serial_log2 = 0;                                  // iteration ends the next launch that is alone on purpose walks: 2^this
+    bool serial_next = false;
+    bool want_adopt = false;                              // the followed chain has an emitter whose state has not been seen equal to em's yet
+    bool adopting = false;                                // ... it has: its output is copied
+    int64_t n_joins = 0, n_launches = 0, n_dropped = 0, n_adopted = 0;
+    // (DQ_TRACE) device clock of the first chain that came back; time inside the emitter; the scan's start
+    unsigned long long t_first = 0;
+    double emit_ms = 0, emit_phase_ms[3] = {0, 0, 0};
+    std::chrono::steady_clock::time_point t_host0;
+
+    // Whatever way the scan is left while a launch is out -- a failed copy, an exception out of the emitter -- the kernel
+    // must be off the stream before anybody refills the lists or the answer buffers: its chains are told to stop (the
+    // error word every spin looks at), the stream drains, the timing events go back to their pool.  Then the emitter
+    // threads end: none outlives the scan.
+    ~ChainScan()
+    {
+        if (launch_out) {
             hipStream_t side = nullptr;
             if (hipStreamCreateWithFlags(&side, hipStreamNonBlocking) == hipSuccess) {
                 static const unsigned int one = 1;
-                for (int k = 0; k < kScanMaxChains; ++k)
-                    if (ch[k].running) (void)hipMemcpyAsync(&ch[k].d_ctl->error, &one, sizeof(one), hipMemcpyHostToDevice, side);
+                for (ScanChain &x : ch)
+                    if (x.running) (void)hipMemcpyAsync(&x.d_ctl->error, &one, sizeof(one), hipMemcpyHostToDevice, side);
                 (void)hipStreamSynchronize(side);
                 (void)hipStreamDestroy(side);
             }
-            for (int k = 0; k < kScanMaxChains; ++k) if (ch[k].running) *ch[k].dirty = kAnchorRecs;
+            for (ScanChain &x : ch) if (x.running) *x.dirty = kAnchorRecs;
             drop_pending(c, c.stream);                    // (synchronises c.stream first)
         }
-    } guard{c, ch, launch_out};
-
-    // Search counts along the path this thread followed: the last chain's own count + (count at the entry a chain was
-    // left at - count at the entry its successor was joined at) over the joins; the counts beside the entries are read
-    // once the launch that wrote them has said it is over.
-    struct Join { int from, to; int64_t from_at, to_at; bool have_from, have_to; unsigned long long from_v, to_v; };
-    std::vector<Join> joins;
-    auto settle = [&](int k) {
-        for (Join &j : joins) {
-            if (j.from == k && !j.have_from) { j.from_v = ch[k].cum[j.from_at]; j.have_from = true; }
-            if (j.to == k && !j.have_to) { j.to_v = ch[k].cum[j.to_at]; j.have_to = true; }
+        if (c.scan_pool)
+            for (auto &e : static_cast<ScanPool *>(c.scan_pool.get())->em) if (e) e->trim();
+    }
+    int run(bool *retry_on_host)
+    {
+        // (short files: two more threads cost more than the framing they would hide)
+        if (framer && m >= F.frame_follow_min.value_or((int64_t)256 << 10) && framer->start(raw, m)) em.progress = framer->final_len;
+        if (trace) em.phase_ms = emit_phase_ms;
+        for (int k = 0; k < kScanMaxChains; ++k) {
+            ScanChain &x = ch[k];
+            char *hp = pinned_chains + kAsSlotAt + (size_t)k * kAsSlotBytes;
+            x.d_ctl = reinterpret_cast<AnchorCtl *>(scratch + (size_t)k * 256);
+            x.h_up = reinterpret_cast<AnchorCtl *>(pinned_chains + (size_t)k * 256);
+            x.ring = reinterpret_cast<unsigned long long *>(hp);
+            x.cum = x.ring + kAnchorRecs;
+            x.h_out = reinterpret_cast<const AnchorCtl *>(x.ring + 2 * kAnchorRecs);
+            x.h_landed = x.ring + 2 * kAnchorRecs + 31;
+            x.dirty = &c.scan_dirty[k];
         }
-    };
-    bool gave_up = false;
-    unsigned long long t_first = 0;                       // (DQ_TRACE: device clock of the first chain that came back)
-    // is chain k's part of its launch over?  (x.st, x.nent are what it left)  1 yes, 0 not yet, < 0 error
-    auto landed = [&](int k, bool wait) -> int {
+        ch[0].alive = true;                               // (from the loop's initial state: all zero)
+        plan();
+        // Below 8 workgroups, or for a while after a launch whose workgroups waited in vain (a device kept full by other
+        // streams or processes -- every such launch costs its spin bound), the host loop over windows takes the file.
+        if (groups_alone < 8 || c.scan_skip > 0) {
+            if (c.scan_skip > 0) --c.scan_skip;
+            // (not an error: the host loop takes the file and the call succeeds -- dq_last_error() must not be left saying
+            // otherwise behind a DQ_OK, so nothing goes through fail(); dq_last_diff_info counts the file, skipped ones too)
+            if (trace)
+                fprintf(stderr, "[dq] %s\n", groups_alone < 8 ? "anchor scan: the device holds fewer than 8 of its workgroups" : "anchor scan: skipped after a starved launch");
+            *retry_on_host = true;
+            return DQ_ERR_HIP;
+        }
+        const int rc = follow();
+        if (rc != DQ_OK) return rc;
+        // (a workgroup of a persistent grid did not get onto the device in time -- a device kept full by other work: the
+        // caller runs the host loop over windows instead; nothing of this attempt is kept; the next 16 diffs on this device
+        // do not try again)
+        if (gave_up) {
+            if (!t_fault.spin && !F.scan_spin_log2) c.scan_skip = 16;     // (not under the tests' own bound)
+            if (trace) fprintf(stderr, "[dq] anchor scan: grid barrier timed out\n");
+            *retry_on_host = true;
+            return DQ_ERR_HIP;                                  // (no fail(): the host loop's DQ_OK must not carry this text)
+        }
+        return finish();
+    }
+    double host_ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host0).count(); }
+    // workgroups of a grid alone on the file and of one of several, how many grids, and their budgets
+    void plan()
+    {
+        if (c.scan_groups_cap < 0) probe_scan_capacity(c, ix.dev, trace);
+        cap = c.scan_groups_cap;
+        if (F.scan_groups_cap) cap = std::min(cap, *F.scan_groups_cap);           // (tests: a small device)
+        const int asked = F.scan_groups ? std::min(kAsMaxGroups, *F.scan_groups) : 0;
+        groups_alone = std::min(asked ? asked : kAsGroups, cap);                  // a grid that is alone on the file
+        groups_chain = std::min(asked ? asked : kScanChainGroups, cap);           // one of several
+        // (workgroups of narrow grids the device holds at once: more than of the widest, their LDS is a quarter)
+        int cap_chains = groups_chain <= kScanChainGroups ? std::max(cap, c.scan_groups_cap_narrow) : cap;
+        if (F.scan_groups_cap) cap_chains = std::min(cap_chains, *F.scan_groups_cap);
+        chains_max = F.scan_chains ? std::min(kScanMaxChains, *F.scan_chains) : kScanChains;
+        if (groups_chain >= 8) chains_max = std::min(chains_max, cap_chains / groups_chain);
+        min_seg = F.scan_min_seg.value_or(kScanMinSegment);
+        extra_ends = F.scan_extra.value_or(kScanExtra);
+        lane_budget = F.scan_lane_budget.value_or(kScanLaneBudget);
+        t_diff_info[4] = chains_max > 1 && m >= 2 * min_seg ? groups_chain : groups_alone;
+    }
+    void settle(int k)
+    {
+        for (Count &q : counts)
+            if (q.chain == k && !q.read) { joined_searches += q.minus ? 0 - ch[k].cum[q.at] : ch[k].cum[q.at]; q.read = true; }
+    }
+    // Has chain k's part of its launch said it is over?  Then what it left is taken (x.st, x.nent): 1 yes, 0 not yet, < 0 error
+    int landed(int k)
+    {
         ScanChain &x = ch[k];
         if (!x.running) return 1;
-        for (uint32_t spins = 0;;) {
-            if (__atomic_load_n(x.h_landed, __ATOMIC_ACQUIRE) == x.seq) break;
-            if (!wait) return 0;
-            if ((++spins & 4095u) == 0) {                  // (a launch that died leaves no word: ask the stream now and then)
-                const hipError_t q = hipStreamQuery(c.stream);
-                if (q == hipSuccess) {
-                    if (__atomic_load_n(x.h_landed, __ATOMIC_ACQUIRE) == x.seq) break;
-                    return fail(DQ_ERR_HIP, "anchor scan: a launch ended without its result");
-                }
-                if (q != hipErrorNotReady) return fail(DQ_ERR_HIP, "anchor scan: stream query failed", q);
-                std::this_thread::yield();
-            } else {
-                __builtin_ia32_pause();
-            }
-        }
+        if (__atomic_load_n(x.h_landed, __ATOMIC_ACQUIRE) != x.seq) return 0;
         x.running = false;
         AnchorCtl back;
         std::memcpy(&back, x.h_out, sizeof(back));
@@ -901,20 +922,30 @@ int scan_on_device(const DiffIndex &ix, DeviceCtx &c, char *d_new, char *scratch
                     (double)(back.t_begin - t_first) * 1e-5, (double)(back.t_end - t_first) * 1e-5, back.t_search * 1e-5, back.t_wait * 1e-5,
                     back.t_eval * 1e-5, back.t_stop * 1e-5);
         return 1;
-    };
+    }
+    // one poll on the way to chain k's result that found nothing new (dq_scan_wait.h): 0, 1 (landed) or an error
+    int poll(int k, uint32_t &idle)
+    {
+        static_assert(hipErrorNotReady == kStreamNotReady, "dq_scan_wait.h");
+        return wait_poll(idle, [&] { return landed(k); }, [&] { return (int)hipStreamQuery(c.stream); },
+                         [](const char *what, int e) { return fail(DQ_ERR_HIP, what, (hipError_t)e); });
+    }
     // every chain of the launch that is out over, the stream drained (before the buffers of any chain are touched again)
-    auto drain = [&]() -> int {
+    int drain()
+    {
         if (!launch_out) return DQ_OK;
         for (int k = 0; k < kScanMaxChains; ++k) {
-            const int r = landed(k, true);
+            int r = landed(k);
+            for (uint32_t idle = 0; r == 0;) r = poll(k, idle);
             if (r < 0) return r;
         }
         HIP_TRY(hipStreamSynchronize(c.stream));
         launch_out = false;
         return flush_profile(c);
-    };
-    // ---- one launch: the chains in `slots`, each from its x.st ----
-    auto launch = [&](const std::vector<int> &slots, int groups) -> int {
+    }
+    // one launch: the chains in `slots`, each from its x.st
+    int launch(const std::vector<int> &slots, int groups)
+    {
         AnchorLaunch ln{};
         ln.chains = (int)slots.size();
         ln.groups = groups;
@@ -942,38 +973,23 @@ int scan_on_device(const DiffIndex &ix, DeviceCtx &c, char *d_new, char *scratch
         for (int s : slots)                                // (no answer word carries a window's tag yet)
             HIP_TRY(hipMemsetAsync(scratch + kAsAnswersAt + (size_t)s * kAnchorAnswers, 0xff, kAnchorAnswers, c.stream));
         // (all its registers where the launch fits the device with one workgroup per compute unit)
-        if (groups * ln.chains <= cap)
-            LAUNCH(L, DQ_K_MATCH_SEARCH, m, m * 2,
-                   hipLaunchKernelGGL((anchor_scan_kernel<int32_t, 1>), dim3(groups * ln.chains), dim3(kAsThreads), as_agp_bytes(groups), c.stream,
-                                      (const uint8_t *)ix.d_old, ix.n, (const int32_t *)ix.d_sa, (const uint8_t *)d_new, m,
-                                      (const int32_t *)ix.d_tab, ix.pk, scratch, pinned_chains, ln));
-        else
-            LAUNCH(L, DQ_K_MATCH_SEARCH, m, m * 2,
-                   hipLaunchKernelGGL((anchor_scan_kernel<int32_t, 2>), dim3(groups * ln.chains), dim3(kAsThreads), as_agp_bytes(groups), c.stream,
-                                      (const uint8_t *)ix.d_old, ix.n, (const int32_t *)ix.d_sa, (const uint8_t *)d_new, m,
-                                      (const int32_t *)ix.d_tab, ix.pk, scratch, pinned_chains, ln));
+        const auto kernel = groups * ln.chains <= cap ? anchor_scan_kernel<int32_t, 1> : anchor_scan_kernel<int32_t, 2>;
+        LAUNCH(L, DQ_K_MATCH_SEARCH, m, m * 2,
+               hipLaunchKernelGGL(kernel, dim3(groups * ln.chains), dim3(kAsThreads), as_agp_bytes(groups), c.stream,
+                                  (const uint8_t *)ix.d_old, ix.n, (const int32_t *)ix.d_sa, (const uint8_t *)d_new, m,
+                                  (const int32_t *)ix.d_tab, ix.pk, scratch, pinned_chains, ln));
         launch_out = true;
         for (int s : slots) {
             ScanChain &x = ch[s];
             x.running = true; x.seq = ln.seq; x.groups = groups; x.taken = 0; x.nent = 0;
         }
         return DQ_OK;
-    };
-    auto entry_cursor = [](unsigned long long v) -> int64_t { return (int64_t)((v & ~kAsSilent) >> 32); };
-
-    int cur = 0;                                          // the chain this thread follows
-    ch[0].alive = true;                                   // (from the loop's initial state: all zero)
-    int serial_log2 = 0;                                  // iteration ends the next launch that is alone on purpose walks: 2^this
-    bool serial_next = false;
-    int64_t n_joins = 0, n_launches = 0, n_dropped = 0, n_adopted = 0;
-    // emitters of the speculative chains on threads of their own (DQ_SCAN_PAR_EMIT=0: everything on this thread)
-    const bool par_emit = F.scan_par_emit.value_or(1) != 0;
-    bool want_adopt = false;                              // the followed chain has an emitter whose state has not been seen equal to em's yet
-    bool adopting = false;                                // ... it has: its output is copied
+    }
     // Launch the followed chain (again) from its state -- and, when no other chain is left and enough of the file is,
     // new chains over the rest of it.
-    auto relaunch = [&]() -> int {
-        rc = drain();                                     // (one launch at a time: chains that were left behind end by themselves)
+    int relaunch()
+    {
+        int rc = drain();                                 // (one launch at a time: chains that were left behind end by themselves)
         if (rc != DQ_OK || gave_up) return rc;
         ScanChain &t = ch[cur];
         const int64_t pos = t.st.mid ? t.st.i : t.st.cursor + t.st.hit_len;
@@ -1013,222 +1029,203 @@ int scan_on_device(const DiffIndex &ix, DeviceCtx &c, char *d_new, char *scratch
             t.st.lane_budget = lane_budget;
         }
         serial_next = false;
-        for (int sl : slots) {                             // (their lists are about to be refilled: the threads that read them end first)
-            if (ch[sl].em) ch[sl].em->halt();
-            ch[sl].em = nullptr;
-        }
+        halt_emitters(slots);                             // (their lists are about to be refilled: the threads that read them end first)
         adopting = false; want_adopt = false;             // (the followed chain's new entries are computed here)
         rc = launch(slots, slots.size() > 1 ? groups_chain : groups_alone);
         if (rc != DQ_OK) return rc;
         n_launches += (int64_t)slots.size();
-        if (par_emit) {
-            try {
-                if (!c.scan_pool) c.scan_pool = std::make_shared<ScanPool>();
-                ScanPool &pool = *static_cast<ScanPool *>(c.scan_pool.get());
-                for (size_t q = 1; q < slots.size(); ++q) {
-                    ScanChain &x = ch[slots[q]];
-                    if (!pool.em[slots[q]]) pool.em[slots[q]].reset(new ChainEmitter);
-                    ChainEmitter &e = *pool.em[slots[q]];
-                    // (its own part of the file and a quarter more; a chain that walks further -- nothing joined it for a
-                    // long time -- leaves the rest to the thread that follows it)
-                    const int64_t upto = q + 1 < slots.size() ? ch[slots[q + 1]].start : m;
-                    const int64_t part = upto - x.start;
-                    e.reset(x.start, (size_t)std::min<int64_t>(m - x.start, part + part / 4 + (64 << 10)) + 64);
-                    x.mark_at = 0;
-                    e.th = std::thread(with_flags([&e, &ix, nw, m, ring = x.ring, start = x.start] { e.run(ix.old, ix.n, nw, m, ring, start); }));
-                    x.em = &e;
-                }
-            } catch (const std::exception &) {
-                for (int sl : slots) {                     // (no memory or no thread: everything is computed here, as without them)
-                    if (ch[sl].em) ch[sl].em->halt();
-                    ch[sl].em = nullptr;
-                }
-            }
-        }
+        if (par_emit) start_emitters(slots);
         return DQ_OK;
-    };
-    // The followed chain has just ended an iteration at c (silent: without a triple; under shift s): is that where
-    // another chain ended one under the same shift?  (Entries of that chain in front of c are stepped over for good:
-    // the followed chain's ends only grow.)
-    auto try_join = [&](int64_t cpos, bool silent, int64_t s) -> int {
+    }
+    void halt_emitters(const std::vector<int> &slots) { for (int sl : slots) if (ch[sl].em) { ch[sl].em->halt(); ch[sl].em = nullptr; } }
+    // an emitter thread for each speculative chain of the launch (slots[1..])
+    void start_emitters(const std::vector<int> &slots)
+    {
+        try {
+            if (!c.scan_pool) c.scan_pool = std::make_shared<ScanPool>();
+            ScanPool &pool = *static_cast<ScanPool *>(c.scan_pool.get());
+            for (size_t q = 1; q < slots.size(); ++q) {
+                ScanChain &x = ch[slots[q]];
+                if (!pool.em[slots[q]]) pool.em[slots[q]].reset(new ChainEmitter);
+                ChainEmitter &e = *pool.em[slots[q]];
+                // (its own part of the file and a quarter more; a chain that walks further -- nothing joined it for a
+                // long time -- leaves the rest to the thread that follows it)
+                const int64_t upto = q + 1 < slots.size() ? ch[slots[q + 1]].start : m;
+                const int64_t part = upto - x.start;
+                e.reset(x.start, (size_t)std::min<int64_t>(m - x.start, part + part / 4 + (64 << 10)) + 64);
+                x.mark_at = 0;
+                e.th = std::thread(with_flags([&e, &ix = ix, nw = nw, m = m, ring = x.ring] { e.run(ix.old, ix.n, nw, m, ring); }));
+                x.em = &e;
+            }
+        } catch (const std::exception &) {
+            halt_emitters(slots);                         // (no memory or no thread: everything is computed here, as without them)
+        }
+    }
+    // The followed chain has just ended an iteration at `at` (silent: without a triple; under shift s): is that where
+    // another chain ended one under the same shift?  Then that chain is followed from here on: 1.  (Entries of that chain
+    // in front of `at` are stepped over for good: the followed chain's ends only grow.)
+    int try_join(const AnchorEntry &at, int64_t s)
+    {
         for (;;) {
             int best = -1;
             for (int k = 0; k < kScanMaxChains; ++k)
-                if (k != cur && ch[k].alive && ch[k].start <= cpos && (best < 0 || ch[k].start > ch[best].start)) best = k;
+                if (k != cur && ch[k].alive && ch[k].start <= at.cursor && (best < 0 || ch[k].start > ch[best].start)) best = k;
             if (best < 0) return 0;
             ScanChain &x = ch[best];
-            bool again = false;
             for (uint32_t idle = 0;;) {
-                if ((x.running || x.taken < x.nent) && x.taken < kAnchorRecs) {
-                    const unsigned long long v = __atomic_load_n(&x.ring[x.taken], __ATOMIC_ACQUIRE);
-                    if (v != kAnchorPending) {
-                        idle = 0;
-                        const int64_t cj = entry_cursor(v);
-                        const bool sj = (v & kAsSilent) != 0;
-                        if (cj < cpos) {
-                            if (!sj) x.shift = (int64_t)(uint32_t)v - cj;
-                            ++x.taken;
-                            continue;
-                        }
-                        if (cj == cpos && sj == silent && (!silent || x.shift == s)) {
-                            if (!sj) x.shift = (int64_t)(uint32_t)v - cj;
-                            joins.push_back(Join{cur, best, ch[cur].taken - 1, x.taken, false, false, 0, 0});
-                            ++x.taken;
-                            if (!ch[cur].running) settle(cur);
-                            if (!x.running) settle(best);
-                            ch[cur].alive = false;        // (its grid leaves by itself a few iterations on)
-                            if (ch[cur].em) ch[cur].em->stop.store(1, std::memory_order_relaxed);
-                            adopting = false;
-                            want_adopt = x.em != nullptr;
-                            cur = best;
-                            ++n_joins;
-                            serial_log2 = 0;
-                            if (trace)
-                                fprintf(stderr, "[dq] anchor scan: chain %d joined at %lld (its entry %lld), %.3f ms (emitter %.2f ms so far; its own emitter: %s, %lld entries seen, %lld marks)\n",
-                                        best, (long long)cpos, (long long)x.taken - 1, host_ms(), emit_ms, !x.em ? "none" : x.em->failed.load() ? "failed" : "running",
-                                        x.em ? (long long)x.em->seen.load() : 0ll, x.em ? (long long)x.em->n_marks.load() : 0ll);
-                            return 1;
-                        }
-                        break;                            // its next end lies behind c, or at c under another shift
-                    }
+                const unsigned long long v = x.peek();
+                if (v != kAnchorPending) {
+                    idle = 0;
+                    const AnchorEntry e = decode_entry(v);
+                    const bool meet = e.cursor == at.cursor && e.silent == at.silent && (!at.silent || x.shift == s);
+                    if (e.cursor >= at.cursor && !meet) return 0;   // its next end lies behind `at`, or at `at` under another shift
+                    if (!e.silent) x.shift = e.hit_pos - e.cursor;
+                    ++x.taken;
+                    if (!meet) continue;
+                    counts.push_back(Count{cur, ch[cur].taken - 1, false, false});
+                    counts.push_back(Count{best, x.taken - 1, true, false});
+                    if (!ch[cur].running) settle(cur);
+                    if (!x.running) settle(best);
+                    ch[cur].alive = false;                // (its grid leaves by itself a few iterations on)
+                    if (ch[cur].em) ch[cur].em->stop.store(1, std::memory_order_relaxed);
+                    adopting = false;
+                    want_adopt = x.em != nullptr;
+                    cur = best;
+                    ++n_joins;
+                    serial_log2 = 0;
+                    if (trace)
+                        fprintf(stderr, "[dq] anchor scan: chain %d joined at %lld (its entry %lld), %.3f ms (emitter %.2f ms so far; its own emitter: %s, %lld entries seen, %lld marks)\n",
+                                best, (long long)at.cursor, (long long)x.taken - 1, host_ms(), emit_ms, !x.em ? "none" : x.em->failed.load() ? "failed" : "running",
+                                x.em ? (long long)x.em->seen.load() : 0ll, x.em ? (long long)x.em->n_marks.load() : 0ll);
+                    return 1;
                 }
                 if (!x.running) {
-                    if (x.taken >= x.nent) {                   // nothing of it lies behind c
-                        x.alive = false; ++n_dropped; again = true;
-                        if (x.em) x.em->stop.store(1, std::memory_order_relaxed);
-                        break;
-                    }
-                    return fail(DQ_ERR_HIP, "anchor scan: a record slot was left unfilled");
+                    if (x.taken < x.nent) return fail(DQ_ERR_HIP, "anchor scan: a record slot was left unfilled");
+                    x.alive = false; ++n_dropped;         // nothing of it lies behind `at`
+                    if (x.em) x.em->stop.store(1, std::memory_order_relaxed);
+                    break;
                 }
                 // the chain has not got there yet (it started when the followed one did: rare): wait for its entry or its end
-                if ((++idle & 63u) != 0) { __builtin_ia32_pause(); continue; }
-                const int r = landed(best, false);
+                const int r = poll(best, idle);
                 if (r < 0) return r;
                 if (gave_up) return 0;
             }
-            if (!again) return 0;
         }
-    };
-
-    rc = relaunch();
-    if (rc != DQ_OK) return rc;
-    if (trace) fprintf(stderr, "[dq] anchor scan: first launch out at %.3f ms\n", host_ms());
-    for (uint32_t idle = 0; !gave_up;) {
-        ScanChain &t = ch[cur];
-        if ((t.running || t.taken < t.nent) && t.taken < kAnchorRecs) {
-            const unsigned long long v = __atomic_load_n(&t.ring[t.taken], __ATOMIC_ACQUIRE);
+    }
+    // Entry e of the followed chain t: its triple computed here, or copied from the chain's own emitter
+    int take(ScanChain &t, const AnchorEntry &e)
+    {
+        // Has the chain's own emitter been through the entries passed so far, and does it stand where em stands?  Then
+        // what it writes from here on is what em would write.
+        if (want_adopt && !adopting && t.em) {
+            ChainEmitter &x = *t.em;
+            // (an emitter that ran out of room -- its chain walked far beyond its part -- has stopped for good; what it
+            // wrote up to there is as good as any)
+            if (x.seen.load(std::memory_order_acquire) < t.taken) {
+                if (x.failed.load(std::memory_order_acquire)) want_adopt = false;
+            } else {
+                const int64_t nm = x.n_marks.load(std::memory_order_acquire);
+                while (t.mark_at < nm && x.marks[(size_t)t.mark_at].entry < t.taken) ++t.mark_at;
+                const bsdiff::TripleEmitter::Anchor theirs = t.mark_at > 0 ? x.marks[(size_t)t.mark_at - 1].prev : x.first;
+                if (theirs.at == em.prev.at && theirs.in_old == em.prev.in_old) { adopting = true; want_adopt = false; }
+            }
+        }
+        if (e.silent) return DQ_OK;
+        t.shift = e.hit_pos - e.cursor;
+        // the chain's emitter has this entry's triple and bytes, or is about to (its thread fills host memory: no device wait)
+        for (uint32_t idle = 0; adopting && t.em->n_marks.load(std::memory_order_acquire) <= t.mark_at;) {
+            if (t.em->failed.load(std::memory_order_acquire)) adopting = false;       // (computed here from now on)
+            else if ((++idle & 63u) == 0) std::this_thread::yield();
+            else __builtin_ia32_pause();
+        }
+        if (!adopting) {
+            const auto t0 = trace ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point();
+            em.take(e.cursor, e.hit_pos);
+            if (trace) emit_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            return DQ_OK;
+        }
+        const ChainEmitter &x = *t.em;
+        const ChainEmitter::Mark &mk = x.marks[(size_t)t.mark_at];
+        if (mk.entry != t.taken) return fail(DQ_ERR_HIP, "anchor scan: a chain's emitter lost step with its list");
+        const ChainEmitter::Mark before = t.mark_at > 0 ? x.marks[(size_t)t.mark_at - 1] : ChainEmitter::Mark{};
+        raw.ctrl.insert(raw.ctrl.end(), x.priv.ctrl.data() + before.ctrl, x.priv.ctrl.data() + mk.ctrl);
+        raw.diff.insert(raw.diff.end(), x.priv.diff.data() + before.diff, x.priv.diff.data() + mk.diff);
+        raw.extra.insert(raw.extra.end(), x.priv.extra.data() + before.extra, x.priv.extra.data() + mk.extra);
+        em.prev = mk.prev;
+        if (em.progress) {
+            em.progress[0].store(raw.diff.size(), std::memory_order_release);
+            em.progress[1].store(raw.extra.size(), std::memory_order_release);
+        }
+        ++t.mark_at;
+        ++n_adopted;
+        return DQ_OK;
+    }
+    // The followed chain's entries in order, a join tried behind each; a relaunch whenever its launch is over and read to
+    // its end -- up to the end of the file, or until a grid has given up.
+    int follow()
+    {
+        t_host0 = std::chrono::steady_clock::now();
+        int rc = relaunch();
+        if (rc != DQ_OK) return rc;
+        if (trace) fprintf(stderr, "[dq] anchor scan: first launch out at %.3f ms\n", host_ms());
+        for (uint32_t idle = 0; !gave_up;) {
+            ScanChain &t = ch[cur];
+            const unsigned long long v = t.peek();
             if (v != kAnchorPending) {
-                const int64_t cpos = entry_cursor(v);
-                const bool silent = (v & kAsSilent) != 0;
-                // Has the chain's own emitter been through the entries passed so far, and does it stand where em stands?
-                // Then what it writes from here on is what em would write.
-                if (want_adopt && !adopting && t.em) {
-                    ChainEmitter &e = *t.em;
-                    // (an emitter that ran out of room -- its chain walked far beyond its part -- has stopped for good; what it
-                    // wrote up to there is as good as any)
-                    if (e.seen.load(std::memory_order_acquire) < t.taken) {
-                        if (e.failed.load(std::memory_order_acquire)) want_adopt = false;
-                    } else {
-                        const int64_t nm = e.n_marks.load(std::memory_order_acquire);
-                        while (t.mark_at < nm && e.marks[(size_t)t.mark_at].entry < t.taken) ++t.mark_at;
-                        const bsdiff::TripleEmitter::Anchor theirs = t.mark_at > 0 ? e.marks[(size_t)t.mark_at - 1].prev : e.first;
-                        if (theirs.at == em.prev.at && theirs.in_old == em.prev.in_old) { adopting = true; want_adopt = false; }
-                    }
-                }
-                if (!silent && adopting) {
-                    // the chain's emitter has this entry's triple and bytes, or is about to
-                    ChainEmitter &e = *t.em;
-                    if (e.n_marks.load(std::memory_order_acquire) <= t.mark_at) {
-                        if (e.failed.load(std::memory_order_acquire)) { adopting = false; continue; }       // (computed here from now on)
-                        if ((++idle & 63u) == 0) std::this_thread::yield(); else __builtin_ia32_pause();
-                        continue;
-                    }
-                    const ChainEmitter::Mark &mk = e.marks[(size_t)t.mark_at];
-                    if (mk.entry != t.taken) return fail(DQ_ERR_HIP, "anchor scan: a chain's emitter lost step with its list");
-                    const size_t c0 = t.mark_at > 0 ? e.marks[(size_t)t.mark_at - 1].ctrl : 0, d0 = t.mark_at > 0 ? e.marks[(size_t)t.mark_at - 1].diff : 0,
-                                 x0 = t.mark_at > 0 ? e.marks[(size_t)t.mark_at - 1].extra : 0;
-                    raw.ctrl.insert(raw.ctrl.end(), e.priv.ctrl.data() + c0, e.priv.ctrl.data() + mk.ctrl);
-                    raw.diff.insert(raw.diff.end(), e.priv.diff.data() + d0, e.priv.diff.data() + mk.diff);
-                    raw.extra.insert(raw.extra.end(), e.priv.extra.data() + x0, e.priv.extra.data() + mk.extra);
-                    em.prev = mk.prev;
-                    if (em.progress) {
-                        em.progress[0].store(raw.diff.size(), std::memory_order_release);
-                        em.progress[1].store(raw.extra.size(), std::memory_order_release);
-                    }
-                    ++t.mark_at;
-                    ++n_adopted;
-                    t.shift = (int64_t)(uint32_t)v - cpos;
-                } else if (!silent) {
-                    if (trace) {
-                        const auto t0 = std::chrono::steady_clock::now();
-                        em.take(cpos, (int64_t)(uint32_t)v);
-                        emit_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-                    } else {
-                        em.take(cpos, (int64_t)(uint32_t)v);
-                    }
-                    t.shift = (int64_t)(uint32_t)v - cpos;
-                }
+                const AnchorEntry e = decode_entry(v);
+                int r = take(t, e);
+                if (r != DQ_OK) return r;
                 idle = 0;
                 ++t.taken;
-                const int j = try_join(cpos, silent, t.shift);
-                if (j < 0) return j;
+                r = try_join(e, t.shift);
+                if (r < 0) return r;
                 continue;
             }
-        }
-        if (t.running) {
-            if ((++idle & 63u) != 0) { if ((idle & 7u) == 0) __builtin_ia32_pause(); continue; }
-            const int r = landed(cur, false);
-            if (r < 0) return r;
-            // (nothing new for thousands of looks: the kernel is inside a long search -- leave the core to the framing
-            // and encoder threads of this and other callers for a moment)
-            if (r == 0) {
-                if ((idle & 0xffffu) == 0) {               // (a launch that died would never say so: ask the stream now and then)
-                    const hipError_t q = hipStreamQuery(c.stream);
-                    if (q != hipSuccess && q != hipErrorNotReady) return fail(DQ_ERR_HIP, "anchor scan: stream query failed", q);
-                    if (q == hipSuccess && landed(cur, false) == 0) return fail(DQ_ERR_HIP, "anchor scan: a launch ended without its result");
-                }
-                if (idle >= (1u << 14)) std::this_thread::yield();
+            if (t.running) {
+                const int r = poll(cur, idle);
+                if (r < 0) return r;
+                continue;
             }
-            continue;
+            if (t.taken < t.nent) return fail(DQ_ERR_HIP, "anchor scan: a record slot was left unfilled");
+            // the followed chain's launch is over and read to its end
+            if (t.st.done) break;
+            if (t.nent == 0 && !t.st.mid) return fail(DQ_ERR_HIP, "anchor scan: no progress");
+            if (t.st.mid) {                               // it left a long differing stretch: that iteration alone, with all it can get
+                serial_next = true;
+            } else if (t.st.extra > 0 && t.st.stop_at == 0) { // a launch that was alone on purpose has ended its iterations
+                serial_log2 = std::min(serial_log2 + 1, 12);
+            }
+            rc = relaunch();
+            if (rc != DQ_OK) return rc;
         }
-        if (t.taken < t.nent) return fail(DQ_ERR_HIP, "anchor scan: a record slot was left unfilled");
-        // the followed chain's launch is over and read to its end
-        if (t.st.done) break;
-        if (t.nent == 0 && !t.st.mid) return fail(DQ_ERR_HIP, "anchor scan: no progress");
-        if (t.st.mid) {                                   // it left a long differing stretch: that iteration alone, with all it can get
-            serial_next = true;
-        } else if (t.st.extra > 0 && t.st.stop_at == 0) { // a launch that was alone on purpose has ended its iterations
-            serial_log2 = std::min(serial_log2 + 1, 12);
-        }
-        rc = relaunch();
-        if (rc != DQ_OK) return rc;
+        if (trace) fprintf(stderr, "[dq] anchor scan: end of file at %.3f ms\n", host_ms());
+        return drain();                                   // (chains that were left behind end by themselves)
     }
-    if (trace) fprintf(stderr, "[dq] anchor scan: end of file at %.3f ms\n", host_ms());
-    rc = drain();                                         // (chains that were left behind end by themselves)
+    // the Search count along the path followed, dq_last_diff_info's counts of the chains, the streams complete
+    int finish()
+    {
+        for (const Count &q : counts) if (!q.read) return fail(DQ_ERR_HIP, "anchor scan: a join was left unsettled");
+        raw.searches += (int64_t)(ch[cur].st.searches + joined_searches);
+        t_diff_info[5] = n_launches; t_diff_info[6] = n_joins; t_diff_info[7] = n_dropped; t_diff_info[8] = n_adopted;
+        if (em.progress) framer->complete();
+        if (trace)
+            fprintf(stderr, "[dq] anchor scan: %lld chain launches, %lld joins, %lld chains dropped in %.3f ms; emitter (steps 2 and 3 on the host, beside the kernels): %.2f ms "
+                    "on this thread, %lld triples taken from the chains' own emitters\n", (long long)n_launches, (long long)n_joins, (long long)n_dropped, host_ms(), emit_ms,
+                    (long long)n_adopted);
+        if (trace) fprintf(stderr, "[dq] emitter: extensions %.2f ms, diff bytes %.2f ms, extra bytes and triple %.2f ms\n", emit_phase_ms[0], emit_phase_ms[1], emit_phase_ms[2]);
+        return DQ_OK;
+    }
+};
+
+int scan_on_device(const DiffIndex &ix, DeviceCtx &c, char *d_new, char *scratch, char *pinned_chains, const uint8_t *nw,
+                   int64_t m, bsdiff::RawStreams &raw, bool *retry_on_host, PatchFramer *framer)
+{
+    *retry_on_host = false;
+    std::lock_guard<std::mutex> lk(c.mu);                 // (the device context's stream and pinned areas)
+    const int rc = init_ctx(c, ix.dev);
     if (rc != DQ_OK) return rc;
-    // (a workgroup of a persistent grid did not get onto the device in time -- a device kept full by other work: the
-    // caller runs the host loop over windows instead; nothing of this attempt is kept; the next 16 diffs on this device
-    // do not try again)
-    if (gave_up) {
-        if (!t_fault.spin && !F.scan_spin_log2) c.scan_skip = 16;     // (not under the tests' own bound)
-        if (trace) fprintf(stderr, "[dq] anchor scan: grid barrier timed out\n");
-        *retry_on_host = true;
-        return DQ_ERR_HIP;                                  // (no fail(): the host loop's DQ_OK must not carry this text)
-    }
-    unsigned long long searches = ch[cur].st.searches;
-    for (const Join &j : joins) {
-        if (!j.have_from || !j.have_to) return fail(DQ_ERR_HIP, "anchor scan: a join was left unsettled");
-        searches += j.from_v - j.to_v;
-    }
-    raw.searches += (int64_t)searches;
-    t_diff_info[5] = n_launches; t_diff_info[6] = n_joins; t_diff_info[7] = n_dropped; t_diff_info[8] = n_adopted;
-    if (em.progress) framer->complete();
-    if (trace)
-        fprintf(stderr, "[dq] anchor scan: %lld chain launches, %lld joins, %lld chains dropped in %.3f ms; emitter (steps 2 and 3 on the host, beside the kernels): %.2f ms "
-                "on this thread, %lld triples taken from the chains' own emitters\n", (long long)n_launches, (long long)n_joins, (long long)n_dropped, host_ms(), emit_ms,
-                (long long)n_adopted);
-    if (trace) fprintf(stderr, "[dq] emitter: extensions %.2f ms, diff bytes %.2f ms, extra bytes and triple %.2f ms\n", emit_phase_ms[0], emit_phase_ms[1], emit_phase_ms[2]);
-    return DQ_OK;
+    ChainScan scan{ix, c, d_new, scratch, pinned_chains, nw, m, raw, framer};
+    return scan.run(retry_on_host);
 }
 
 // Diff.Create's data path up to the raw streams for one new file: upload it, run the scan loop over windows of answers
