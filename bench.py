@@ -8,16 +8,20 @@ A single suffix array does not shard; independent inputs d
 data-path collective, so N GPUs = N buffers (weak scaling) and
 value = total MB sorted / max-over-ranks time.
 
-    python bench.py [--gpus 1] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus 1] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 `--dump-outputs DIR` writes, after the timed steps, the suffix array the last timed step left in HBM as float64 .npy files
 (a fixed sample of positions once it is larger than the budget), so that two builds can be compared output for output:
 the inputs are generated from fixed seeds and are the same in every run with the same arguments.
 
-Prints ONE JSON line (rank 0).  Beside the contract's fields it carries
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the steps, dumps (if asked) and prints the
+contract's fields with
   roofline      the dominant kernel, measured live: every launch of it inside the timed region is
-                bracketed by hipEvents on its launch stream (library side, dq_profile_*)
+                bracketed by hipEvents on its launch stream (library side, dq_profile_*); one profiled sort
+                before the timed region picks the kernel
+`--full` adds everything that takes runs of its own (about a minute more):
+  kernels_untimed_pass  per-kernel table of three more sorts with every launch bracketed (not timed steps)
   through_abi   the same buffer through the interface the reference exposes (host pointers in and
                 out, dq_sufsort_hip_i32 == ISuffixSort.Sort(text, suffixes)): PCIe-inclusive, never `value`
   configs       one short record per other BASELINE.json configuration (64 MiB uniform, 256 MiB
@@ -60,10 +64,13 @@ def main() -> int:
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--size-mib", type=int, default=256, help="bytes of text per GPU (MiB)")
     ap.add_argument("--workload", choices=["uniform", "enwik"], default="uniform")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also every record that takes runs of its own: kernels_untimed_pass, through_abi, configs, batch, "
+                         "cpu_baseline (a plain run only sets up, warms up, times the steps, dumps and prints)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no cpu_baseline record")
     ap.add_argument("--no-profile", action="store_true", help="skip per-kernel hipEvent timing")
     ap.add_argument("--no-extras", action="store_true",
-                    help="only the timed region (profiling runs): no through_abi / configs / batch records")
+                    help="with --full: no through_abi / configs / batch records")
     ap.add_argument("--no-build", action="store_true",
                     help="never spawn a compiler (runs under rocprofv3, where the GPU is up before main())")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N>1 (nccl == RCCL)")
@@ -71,7 +78,7 @@ def main() -> int:
     ap.add_argument("--batch-mib", type=int, default=BATCH_BYTES >> 20, help="MiB per buffer of the batch record (configs[4]: 16)")
     ap.add_argument("--many-new-per-rank", type=int, default=4, help="new files per rank of the one-old-many-new record")
     ap.add_argument("--config3-cpu", action="store_true",
-                    help="opt-in (minutes of one host core, not in the driver's default run): time the oracle's LibDivSufSort "
+                    help="with --full, opt-in (minutes of one host core): time the oracle's LibDivSufSort "
                          "restatement with 64-bit indices on the 2 GiB buffer of configs[3] and bit-compare (SURVEY 8(d) Config 4)")
     ap.add_argument("--share-gpu", action="store_true",
                     help="plumbing test on a 1-GPU box: every rank uses cuda:0 (use with --backend gloo)")
@@ -85,6 +92,8 @@ def main() -> int:
         raise SystemExit("--gpus must be >= 1")
     if args.steps < 1:
         raise SystemExit("--steps must be >= 1")
+    if args.config3_cpu and not args.full:
+        raise SystemExit("--config3-cpu needs --full: configs[3] is a record of the full run")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # started as `python bench.py --gpus N` without a launcher: start the N ranks ourselves, as fresh child
         # processes, before this process has loaded the library or touched the GPU; relay their output (rank 0
@@ -99,18 +108,20 @@ def main() -> int:
 
     # Native builds first, before anything initialises the GPU runtime (compilers are child processes;
     # under rocprofv3 the GPU is already up, so a stale library there is an error, not a rebuild).
+    # The oracle is only the --full run's baseline / checker.
     from deltaq_amd import build as dq_build
-    import oracle
     from tools import datagen
     if args.no_build:
         if dq_build.is_stale():
             raise SystemExit("libdq_sufsort_hip.so is stale: run __graft_entry__.build() first")
     else:
         dq_build.build()                   # no-op when the in-tree .so is current
-        oracle.build()
         datagen.build()
+        if args.full:
+            import oracle
+            oracle.build()
 
-    managed = managed_reference_probe() if rank == 0 else None      # (child processes: before anything touches the GPU)
+    managed = managed_reference_probe() if rank == 0 and args.full else None      # (child processes: before anything touches the GPU)
 
     import numpy as np
     import torch
@@ -192,7 +203,7 @@ def main() -> int:
     info = _abi.last_sort_info()
     dumped = dump_outputs(args.dump_outputs, sa, rank, world) if args.dump_outputs else None
     prof_all, all_steps = {}, 3
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         L.dq_profile_reset()
         L.dq_profile_enable(1)
         for _ in range(all_steps):
@@ -206,7 +217,7 @@ def main() -> int:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    extras = not args.no_extras
+    extras = args.full and not args.no_extras
     through_abi = configs = None
     if extras and rank == 0:
         through_abi = time_through_abi(sorter, host, sa, reps=3)
@@ -236,7 +247,6 @@ def main() -> int:
                 "avg_launch_us": round(rs["ms"] / rs["launches"] * 1e3, 2),
                 "alg_bytes_per_launch": rs["alg_bytes"] // rs["launches"],
             }
-        kernels = kernel_table(prof_all, all_steps)
         out = {
             "metric": "MB of text suffix-sorted per second (bit-exact SA)",
             "value": round(value, 2), "unit": "MB/s",
@@ -249,8 +259,9 @@ def main() -> int:
             "config": {"workload": wname, "bytes_per_gpu": n, "residency": "text and SA resident in HBM",
                        "rounds_after_initial_sort": info["rounds"], "sharding": f"{world} independent buffers"},
             "roofline": roofline,
-            "kernels_untimed_pass": kernels,
         }
+        if args.full:
+            out["kernels_untimed_pass"] = kernel_table(prof_all, all_steps)
         if dumped is not None:
             out["outputs_dumped"] = dumped
         if through_abi is not None:
@@ -259,7 +270,7 @@ def main() -> int:
             out["configs"] = configs
         if batch is not None:
             out["batch"] = batch
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb = cpu_baseline(host, sa)
             cb["managed_reference"] = managed
             out["cpu_baseline"] = cb

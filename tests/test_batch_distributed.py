@@ -287,7 +287,7 @@ def test_bench_line_of_two_ranks_sharing_the_gpu():
         env.pop(k)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--share-gpu", "--backend", "gloo", "--no-cpu-baseline"]
+           "--share-gpu", "--backend", "gloo", "--full", "--no-cpu-baseline"]
     p = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900, cwd=ROOT)
     assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]
@@ -340,7 +340,7 @@ def test_bench_line_of_four_ranks_sharing_the_gpu():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1",
            "--size-mib", "16", "--batch-count", "32", "--batch-mib", "4", "--many-new-per-rank", "2",
-           "--share-gpu", "--backend", "gloo", "--no-cpu-baseline"]
+           "--share-gpu", "--backend", "gloo", "--full", "--no-cpu-baseline"]
     p = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900, cwd=ROOT)
     assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]
@@ -402,7 +402,7 @@ def test_bench_without_a_launcher_runs_two_ranks():
     import json
     import subprocess
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--share-gpu", "--backend", "gloo", "--no-cpu-baseline"], capture_output=True, text=True,
+                        "--share-gpu", "--backend", "gloo", "--full", "--no-cpu-baseline"], capture_output=True, text=True,
                        env=_bench_env(), timeout=900, cwd=ROOT)
     assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]

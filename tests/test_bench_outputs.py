@@ -56,3 +56,37 @@ def test_bench_dumps_the_suffix_array_of_its_last_step(tmp_path, oracle_mod):
     pos = np.load(out / "suffix_array_positions.npy").astype(np.int64)
     ref = oracle_mod.divsufsort(datagen.gen_uniform(16 << 20, 0x5EED0002))       # bench.py's seed for a non-256 MiB uniform run
     assert vals.dtype == np.float64 and np.array_equal(vals, ref[pos].astype(np.float64))
+
+
+def _plain_env():
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    for k in [k for k in env if k.startswith("DQ_") or k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")]:
+        env.pop(k)
+    return env
+
+
+def test_config3_cpu_needs_full():
+    """configs[3] is a record of the --full run: asking for its CPU figure in a plain run is an error, not a quiet no-op
+    (the check comes before the library is loaded, so no GPU is needed)."""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config3-cpu"], capture_output=True, text=True,
+                       env=_plain_env(), timeout=300, cwd=ROOT)
+    assert p.returncode != 0 and "--config3-cpu needs --full" in p.stderr, (p.returncode, p.stderr[-500:])
+    assert '"metric"' not in p.stdout
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_has_the_headline_and_no_full_records():
+    """Without --full the line carries the contract's fields and the live roofline, and none of the records that take runs
+    of their own."""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--size-mib", "16"], capture_output=True, text=True, env=_plain_env(), timeout=600, cwd=ROOT)
+    assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]
+    assert len(lines) == 1, p.stdout[-2000:]
+    rec = json.loads(lines[0])
+    assert rec["metric"] == "MB of text suffix-sorted per second (bit-exact SA)" and rec["unit"] == "MB/s"
+    assert rec["higher_is_better"] is True and rec["dtype"] == "u8 text / u64 keys / int32 SA"
+    assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["ms_per_step"] > 0 and rec["value"] > 0
+    assert rec["roofline"]["frac_of_6p3"] > rec["roofline"]["frac"] > 0
+    for key in ("kernels_untimed_pass", "through_abi", "configs", "batch", "cpu_baseline", "speedup_vs_cpu_device_resident"):
+        assert key not in rec, key
