@@ -10,6 +10,7 @@
 using CommunityToolkit.HighPerformance.Buffers;
 using System;
 using System.Buffers;
+using System.Collections.Generic;
 using System.Runtime.InteropServices;
 
 namespace DeltaQ.SuffixSorting.Hip;
@@ -24,6 +25,13 @@ public sealed class HipSuffixSort : ISuffixSort
 
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
     private static extern unsafe int dq_sufsort_hip_i32(byte* text, long n, int* sa, int device);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    private static extern unsafe int dq_sufsort_hip_many_i32(byte* texts, long* offsets, int count, int* sas, int device);
+
+    // (declared for hosts that keep their buffers on the device: device pointers, a hipStream_t or zero)
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern int dq_sufsort_hip_many_dev_i32(IntPtr dTexts, IntPtr dOffsets, int count, IntPtr dSas, int device, IntPtr stream);
 
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
     private static extern unsafe int dq_sufcheck_hip_i32(byte* text, long n, int* sa, long saLen, int* result, int device);
@@ -137,6 +145,86 @@ public sealed class HipSuffixSort : ISuffixSort
 
         string msg = Marshal.PtrToStringAnsi(dq_last_error()) ?? string.Empty;
         throw new InvalidOperationException($"dq_sufsort_hip_i32 failed ({rc}): {msg}");
+    }
+
+    /// <summary>
+    /// The suffix arrays of many independent texts in one native call (dq_sufsort_hip_many_i32): texts of up to
+    /// 8192 bytes share kernel launches instead of costing a launch and a round trip each, longer ones are sorted one
+    /// after another.  Entry j of the result is what <see cref="Sort(ReadOnlySpan{byte})"/> returns for texts[j].
+    /// The texts are laid back to back in one managed buffer for the call (their total plus four times as much for the
+    /// suffix arrays), so the total is limited to what one array holds; callers with more split their list.
+    /// </summary>
+    public unsafe int[][] SortMany(IReadOnlyList<ReadOnlyMemory<byte>> texts)
+    {
+        int count = texts.Count;
+        var result = new int[count][];
+        if (_nativeMissing)
+        {
+            for (int j = 0; j < count; j++)
+            {
+                result[j] = new int[texts[j].Length];
+                _fallback!.Sort(texts[j].Span, result[j]);
+            }
+
+            return result;
+        }
+
+        var offsets = new long[count + 1];
+        for (int j = 0; j < count; j++)
+        {
+            offsets[j + 1] = offsets[j] + texts[j].Length;
+        }
+
+        long total = offsets[count];
+        if (count == 0)
+        {
+            return result;
+        }
+
+        if (total > Array.MaxLength)
+        {
+            throw new ArgumentException("the texts of one SortMany call must total less than 2^31 bytes");
+        }
+
+        // (at least one element each: the native side wants non-null pointers whenever there are texts)
+        byte[] flat = new byte[Math.Max(total, 1)];
+        int[] sas = new int[Math.Max(total, 1)];
+        for (int j = 0; j < count; j++)
+        {
+            texts[j].Span.CopyTo(flat.AsSpan((int)offsets[j], texts[j].Length));
+        }
+
+        int rc;
+        fixed (byte* pTexts = flat)
+        fixed (long* pOffsets = offsets)
+        fixed (int* pSas = sas)
+        {
+            rc = dq_sufsort_hip_many_i32(pTexts, pOffsets, count, pSas, _device);
+        }
+
+        if (rc != 0)
+        {
+            if (_fallback is not null && rc != -1)
+            {
+                for (int j = 0; j < count; j++)
+                {
+                    result[j] = new int[texts[j].Length];
+                    _fallback.Sort(texts[j].Span, result[j]);
+                }
+
+                return result;
+            }
+
+            string msg = Marshal.PtrToStringAnsi(dq_last_error()) ?? string.Empty;
+            throw new InvalidOperationException($"dq_sufsort_hip_many_i32 failed ({rc}): {msg}");
+        }
+
+        for (int j = 0; j < count; j++)
+        {
+            result[j] = sas.AsSpan((int)offsets[j], texts[j].Length).ToArray();
+        }
+
+        return result;
     }
 
     /// <summary>

@@ -26,6 +26,8 @@ DQ_SUFCHECK_WRONG_ORDER = -3
 DQ_SUFCHECK_WRONG_POSITION = -4
 
 K_RADIX_RANK = 2          # DQ_K_RADIX_RANK: the dominant kernel's profile category
+K_SMALL_SORT = 14         # DQ_K_SMALL_SORT: one short text, one launch
+K_SMALL_MANY = 23         # DQ_K_SMALL_MANY: many short texts in shared launches
 
 # every symbol include/dq_sufsort.h declares
 EXPORTS = (
@@ -33,6 +35,7 @@ EXPORTS = (
     "dq_sufsort_hip_i32", "dq_sufsort_hip_i64",
     "dq_sufsort_hip_dev_i32", "dq_sufsort_hip_dev_i64",
     "dq_sufsort_hip_batch_i32",
+    "dq_sufsort_hip_many_i32", "dq_sufsort_hip_many_dev_i32",
     "dq_sufcheck_hip_i32", "dq_sufcheck_hip_i64", "dq_sufcheck_hip_dev_i32", "dq_sufcheck_hip_dev_i64",
     "dq_bsdiff_search_dev_i32", "dq_bsdiff_search_dev_i64", "dq_bsdiff_search_i32", "dq_bsdiff_search_i64",
     "dq_bsdiff_create", "dq_bsdiff_patch_bound", "dq_bsdiff_scan_i32", "dq_bspatch_apply",
@@ -109,6 +112,10 @@ def load() -> ctypes.CDLL:
         getattr(L, name).argtypes = [vp, i64, vp, i64, ctypes.POINTER(i32), i32, vp]
     L.dq_sufsort_hip_batch_i32.restype = i32
     L.dq_sufsort_hip_batch_i32.argtypes = [i32, vp, vp, vp, i32, vp]
+    L.dq_sufsort_hip_many_i32.restype = i32
+    L.dq_sufsort_hip_many_i32.argtypes = [vp, vp, i32, vp, i32]
+    L.dq_sufsort_hip_many_dev_i32.restype = i32
+    L.dq_sufsort_hip_many_dev_i32.argtypes = [vp, vp, i32, vp, i32, vp]
     for name in ("dq_bsdiff_search_dev_i32", "dq_bsdiff_search_dev_i64"):
         getattr(L, name).restype = i32
         getattr(L, name).argtypes = [vp, i64, vp, vp, i64, vp, i64, i64, i64, vp, vp, i32, vp]
@@ -211,10 +218,10 @@ def last_diff_info() -> dict:
 def last_batch_info() -> dict:
     """Shape of the last dq_sufsort_hip_batch_i32 on this thread (dq_last_batch_info)."""
     L = load()
-    v = (ctypes.c_int64 * 6)()
-    L.dq_last_batch_info(v, 6)
+    v = (ctypes.c_int64 * 7)()
+    L.dq_last_batch_info(v, 7)
     return {"pipelined": v[0], "copy_in_ms": v[1] / 1e3, "sort_ms": v[2] / 1e3, "copy_out_ms": v[3] / 1e3,
-            "slowest_share_ms": v[4] / 1e3, "shares_bound_to_numa_node": v[5]}
+            "slowest_share_ms": v[4] / 1e3, "shares_bound_to_numa_node": v[5], "shared_launch": v[6]}
 
 
 def bind_process_to_device_numa_node(device: int) -> int | None:

@@ -44,7 +44,12 @@ def plan_shards(lengths: Sequence[int], world_size: int) -> List[List[int]]:
 
 
 def sort_batch_local(texts: Sequence, sorter) -> List[np.ndarray]:
-    """All inputs on one device, through the provider's ISuffixSort surface."""
+    """All inputs on one device, through the provider's ISuffixSort surface.  A provider with ``SortMany``
+    (``HipSuffixSort``) gets its host inputs in one call: the short ones share launches instead of costing one each."""
+    texts = list(texts)
+    many = getattr(sorter, "SortMany", None)
+    if many is not None and len(texts) > 1 and not any(type(t).__module__.startswith("torch") for t in texts):
+        return many(texts)
     return [sorter.Sort(t) for t in texts]
 
 

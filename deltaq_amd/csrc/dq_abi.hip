@@ -12,13 +12,16 @@ namespace {
 //   copy-in   text j -> slot          (pageable host memory: the copy blocks its thread, not the others)
 //   sort      slot's text -> slot's SA (device-resident sorter; one sort at a time per device anyway)
 //   copy-out  slot's SA -> sas[j]
-// so the PCIe transfers of neighbouring inputs overlap the sort.  Inputs that need the
-// short-text path or that are larger than the slot size go through the plain host entry point.
+// so the PCIe transfers of neighbouring inputs overlap the sort.  Inputs larger than the slot
+// size go through the plain host entry point.  The short inputs (the single-workgroup sorter's) are gathered into one
+// host staging buffer, sorted in shared launches (dq_small_many.h) and scattered to their arrays: kBatchManyBytes of
+// text and four times as much of suffix arrays on the host at a time.
 constexpr int kBatchSlots = 3;
+constexpr int64_t kBatchManyBytes = 32ll << 20;
 
 
 // what one device share reports back (dq_last_batch_info): inputs through its pipeline, busy microseconds per stage
-struct ShareStats { int64_t piped = 0, in_us = 0, sort_us = 0, out_us = 0, wall_us = 0, bound = 0; };
+struct ShareStats { int64_t piped = 0, in_us = 0, sort_us = 0, out_us = 0, wall_us = 0, bound = 0, shared = 0; };
 inline int64_t us_since(std::chrono::steady_clock::time_point t0)
 {
     return std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
@@ -38,13 +41,59 @@ int batch_on_device(int device, const std::vector<int> &jobs, const uint8_t *con
         return rc;
     };
     const int64_t direct = std::max<int64_t>(small_limit(), 2);             // these bypass the pipeline
+    // the short inputs of the share, in shared launches (DQ_NO_MANY=1: one by one, as the others that bypass it)
+    auto sort_shorts = [&]() -> int {
+        if (flags().no_many.value_or(0) == 1) {
+            for (int j : jobs)
+                if (lens[j] <= direct) { int rc = plain(j); if (rc != DQ_OK) return rc; }
+            return DQ_OK;
+        }
+        int64_t total = 0, largest = 0;
+        for (int j : jobs)
+            if (lens[j] <= direct) {
+                if (lens[j] < 0 || (lens[j] > 0 && (!texts[j] || !sas[j]))) return plain(j);       // (its error, its message)
+                total += lens[j];
+                largest = std::max(largest, lens[j]);
+            }
+        if (total == 0) return DQ_OK;
+        const int64_t cap = std::min(total, std::max(kBatchManyBytes, largest));
+        std::unique_ptr<uint8_t[]> stage_text(new uint8_t[(size_t)cap]);
+        std::unique_ptr<int32_t[]> stage_sa(new int32_t[(size_t)cap]);
+        std::vector<int> group;
+        std::vector<int64_t> offs;
+        auto flush = [&]() -> int {
+            if (group.empty()) return DQ_OK;
+            offs.assign(1, 0);
+            for (int j : group) {
+                memcpy(stage_text.get() + offs.back(), texts[j], (size_t)lens[j]);
+                offs.push_back(offs.back() + lens[j]);
+            }
+            int64_t shared = 0;
+            const int rc = sufsort_many_host(stage_text.get(), offs.data(), (int32_t)group.size(), stage_sa.get(), device, &shared);
+            if (rc != DQ_OK) { *err = t_err; return rc; }
+            for (size_t k = 0; k < group.size(); ++k)
+                memcpy(sas[group[k]], stage_sa.get() + offs[k], (size_t)lens[group[k]] * sizeof(int32_t));
+            stats->shared += shared;
+            group.clear();
+            return DQ_OK;
+        };
+        int64_t held = 0;
+        for (int j : jobs) {
+            if (lens[j] > direct || lens[j] == 0) continue;
+            if (held + lens[j] > cap) { int rc = flush(); if (rc != DQ_OK) return rc; held = 0; }
+            group.push_back(j);
+            held += lens[j];
+        }
+        return flush();
+    };
     int64_t cap = 0;
     int big = 0;
     for (int j : jobs)
         if (lens[j] > direct) { cap = std::max(cap, lens[j]); ++big; }
     if (big < 3 || cap > (1ll << 30)) {                       // nothing to overlap / slots would be huge
-        for (int j : jobs) { int rc = plain(j); if (rc != DQ_OK) return rc; }
-        return DQ_OK;
+        for (int j : jobs)
+            if (lens[j] > direct) { int rc = plain(j); if (rc != DQ_OK) return rc; }
+        return sort_shorts();
     }
     if (hipSetDevice(device) != hipSuccess) { *err = "hipSetDevice failed"; return DQ_ERR_HIP; }
     // the three device slots and streams live in the device context: allocated once, grown on demand
@@ -169,9 +218,7 @@ int batch_on_device(int device, const std::vector<int> &jobs, const uint8_t *con
         for (const std::string &e : errs) if (!e.empty()) { *err = e; break; }
         return failed.load();
     }
-    for (int j : jobs)
-        if (lens[j] <= direct) { int rc = plain(j); if (rc != DQ_OK) return rc; }
-    return DQ_OK;
+    return sort_shorts();
 }
 
 }  // namespace
@@ -288,6 +335,7 @@ int32_t dq_sufsort_hip_batch_i32(int32_t count, const uint8_t *const *texts, con
         t_batch_info[0] += s.piped; t_batch_info[1] += s.in_us; t_batch_info[2] += s.sort_us; t_batch_info[3] += s.out_us;
         t_batch_info[4] = std::max(t_batch_info[4], s.wall_us);
         t_batch_info[5] += s.bound;
+        t_batch_info[6] += s.shared;
     }
     for (int d = 0; d < ndev; ++d)
         if (rcs[d] != DQ_OK) { t_err = errs[d]; return rcs[d]; }
@@ -296,6 +344,27 @@ int32_t dq_sufsort_hip_batch_i32(int32_t count, const uint8_t *const *texts, con
         return fail(DQ_ERR_OOM, "batch: host allocation failed");
     } catch (const std::exception &e) {            // std::system_error from std::thread, ...
         return fail(DQ_ERR_HIP, e.what());
+    }
+}
+
+int32_t dq_sufsort_hip_many_i32(const uint8_t *texts, const int64_t *offsets, int32_t count, int32_t *sas, int32_t device)
+{
+    EnvScope scope;
+    try {
+        return sufsort_many_host(texts, offsets, count, sas, device);
+    } catch (const std::bad_alloc &) {             // nothing may propagate through the C ABI
+        return fail(DQ_ERR_OOM, "many: host allocation failed");
+    }
+}
+
+int32_t dq_sufsort_hip_many_dev_i32(const void *d_texts, const void *d_offsets, int32_t count, void *d_sas, int32_t device,
+                                    void *stream)
+{
+    EnvScope scope;
+    try {
+        return sufsort_many_dev(d_texts, d_offsets, count, d_sas, device, stream);
+    } catch (const std::bad_alloc &) {
+        return fail(DQ_ERR_OOM, "many: host allocation failed");
     }
 }
 
@@ -568,7 +637,7 @@ int32_t dq_last_sort_info(int64_t *rounds, int64_t *initial_active, int64_t *sum
 int32_t dq_last_batch_info(int64_t *info, int32_t count)
 {
     if (!info || count < 0) return fail(DQ_ERR_BAD_ARGS, "bad arguments");
-    for (int32_t k = 0; k < count; ++k) info[k] = k < 6 ? t_batch_info[k] : 0;
+    for (int32_t k = 0; k < count; ++k) info[k] = k < 7 ? t_batch_info[k] : 0;
     return DQ_OK;
 }
 

@@ -2,7 +2,8 @@
 // (the DQ_* flags and their per-call snapshot: dq_flags.h), per-kernel hipEvent timers, device contexts (stream +
 // workspace + pinned areas) and their leases, and the entry points one unit calls in another.  Host code only (no
 // kernels): C++17 inline variables give every unit the same state.
-//   dq_sorter_i32.hip / dq_sorter_i64.hip   the suffix sorter (dq_sorter_impl.h) for 32- / 64-bit indices
+//   dq_sorter_i32.hip / dq_sorter_i64.hip   the suffix sorter (dq_sorter_impl.h) for 32- / 64-bit indices; the i32 unit
+//                                           also holds the many-short-texts launches (dq_small_many.h)
 //   dq_diff.hip                             match search, Diff.Create / Patch.Apply, the many-new-files index
 //   dq_sufcheck.hip                         LDSSChecker.Check of a suffix array on the device (dq_sufcheck.h)
 //   dq_abi.hip                              the C ABI (include/dq_sufsort.h), the batch pipeline, profile getters
@@ -42,8 +43,9 @@ inline thread_local int64_t t_diff_info[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
 
 // the last dq_sufsort_hip_batch_i32 on this thread (dq_last_batch_info): inputs through the pipelines, microseconds the
 // copy-in / sort / copy-out stages were busy (summed over the device shares), wall microseconds of the slowest share,
-// device shares whose host threads were bound to their device's NUMA node
-inline thread_local int64_t t_batch_info[6] = {0, 0, 0, 0, 0, 0};
+// device shares whose host threads were bound to their device's NUMA node, inputs sorted in shared launches
+// (dq_small_many.h)
+inline thread_local int64_t t_batch_info[7] = {0, 0, 0, 0, 0, 0, 0};
 
 inline int fail(int code, const char *what, hipError_t e = hipSuccess)
 {
@@ -88,7 +90,7 @@ inline const char *const kKernelNames[DQ_K_COUNT] = {
     "isa_update_kernel", "isa_from_pairs_kernel", "key2_from_pairs_kernel", "gather_key2_kernel",
     "gather_text_key_kernel", "isa_from_sa_kernel", "small_sufsort_kernel", "bucket_sort_kernel",
     "match_search_kernel", "pair_chain_kernels", "mid_group_round_kernel", "runlen_kernels",
-    "split_pass_kernel", "bucket_finish_kernel", "split_round0_aux_kernels"};
+    "split_pass_kernel", "bucket_finish_kernel", "split_round0_aux_kernels", "small_many_kernel"};
 
 struct ProfRec { int cat; hipEvent_t a, b; int64_t elems, bytes; };
 
@@ -97,6 +99,7 @@ struct DeviceCtx {
     std::mutex mu;
     int dev = -1;
     int ncu = 0;                        // compute units of the device (grid of the persistent kernels)
+    int many_groups[3] = {0, 0, 0};     // workgroups of small_many_kernel the device holds at once, per length class (0: not asked yet)
     hipStream_t stream = nullptr;
     char *ws = nullptr;
     size_t ws_bytes = 0;
@@ -392,6 +395,12 @@ extern template int64_t sufsort_workspace_bytes<int32_t>(int64_t);
 extern template int64_t sufsort_workspace_bytes<int64_t>(int64_t);
 extern template int64_t sufsort_workspace_plan<int32_t>(int64_t, bool, int64_t);
 extern template int64_t sufsort_workspace_plan<int64_t>(int64_t, bool, int64_t);
+
+// many short texts in shared launches (dq_small_many.h, in dq_sorter_i32.hip): the bodies of dq_sufsort_hip_many_i32 /
+// _many_dev_i32.  shared_out (optional): texts that were sorted in shared launches.
+int sufsort_many_host(const uint8_t *texts, const int64_t *offsets, int32_t count, int32_t *sas, int32_t device,
+                      int64_t *shared_out = nullptr);
+int sufsort_many_dev(const void *d_texts, const void *d_offsets, int32_t count, void *d_sas, int32_t device, void *stream);
 
 // LDSSChecker.Check on the device (dq_sufcheck.hip): DQ_OK with the verdict (DQ_SUFCHECK_*) in *result, or an error
 template <typename IdxT>

@@ -19,24 +19,35 @@ namespace dq {
 
 // (kSmallMaxN = 8192 lives in dq_runtime.h: the host runtime sizes its pinned areas by it)
 constexpr int kSmallThreads = 1024;
-constexpr int kSmallWaves = kSmallThreads / kWave;
-constexpr int kSmallItems = kSmallMaxN / kSmallThreads;       // positions per thread at the largest n
 
-struct SmallLds {
-    uint32_t key[2][kSmallMaxN];          // composite keys, ping-pong                       64 KiB
-    uint16_t val[2][kSmallMaxN];          // suffix indices, ping-pong                       32 KiB
-    uint16_t isa[kSmallMaxN + 8];         // ranks by text position (holds the text first)   16 KiB
-    uint16_t cnt[kSmallWaves][256];       // per-wave digit counts -> scatter bases           8 KiB
-    int32_t wmax[kSmallWaves];
-    int32_t wsum[kSmallWaves];
+// The LDS block of a workgroup of kThreadsT threads that sorts texts of up to kMaxNT bytes (sizes: kMaxNT = 8192,
+// kThreadsT = 1024, the class of small_sufsort_kernel; dq_small_many.h adds smaller classes, several workgroups per
+// CU).  Every array is written for the text at hand before it is read: nothing carries over from one text to the next.
+template <int kMaxNT, int kThreadsT>
+struct SmallLdsT {
+    static constexpr int kMaxN = kMaxNT;
+    static constexpr int kThreads = kThreadsT;
+    static constexpr int kWaves = kThreadsT / kWave;
+    static constexpr int kItems = kMaxNT / kThreadsT;          // positions per thread at the largest n
+    static_assert(kThreadsT % 256 == 0 && kThreadsT <= 1024, "the digit scan takes 256 threads and 4 wave sums");
+    static_assert(kMaxNT % kThreadsT == 0 && kMaxNT <= 65536, "suffix indices are 16 bits wide");
+    uint32_t key[2][kMaxNT];              // composite keys, ping-pong                       64 KiB
+    uint16_t val[2][kMaxNT];              // suffix indices, ping-pong                       32 KiB
+    uint16_t isa[kMaxNT + 8];             // ranks by text position (holds the text first)   16 KiB
+    uint16_t cnt[kWaves][256];            // per-wave digit counts -> scatter bases           8 KiB
+    int32_t wmax[kWaves];
+    int32_t wsum[kWaves];
     uint32_t dsum[4];
 };
+using SmallLds = SmallLdsT<kSmallMaxN, kSmallThreads>;
 
 // One stable 8-bit digit pass src -> dst over positions [0, n).  Wave w owns the contiguous
 // positions [w*64*E, (w+1)*64*E) and walks them 64 at a time, so "earlier position" is
 // (earlier wave, earlier step, lower lane).
-__device__ __forceinline__ void small_digit_pass(SmallLds &L, int src, int n, int E, int shift)
+template <typename Lds>
+__device__ __forceinline__ void small_digit_pass(Lds &L, int src, int n, int E, int shift)
 {
+    constexpr int kSmallItems = Lds::kItems, kSmallWaves = Lds::kWaves;
     const int lane = lane_id();
     const int w = threadIdx.x >> 6;
     const int dst = src ^ 1;
@@ -99,8 +110,10 @@ __device__ __forceinline__ void small_digit_pass(SmallLds &L, int src, int n, in
 
 // Group heads of the sorted list in buffer `cur`, rank = position of the group's head,
 // isa[suffix] = rank.  Returns the number of groups (uniform over the workgroup).
-__device__ __forceinline__ int small_rebucket(SmallLds &L, int cur, int n, int E)
+template <typename Lds>
+__device__ __forceinline__ int small_rebucket(Lds &L, int cur, int n, int E)
 {
+    constexpr int kSmallItems = Lds::kItems, kSmallWaves = Lds::kWaves;
     const int lane = lane_id();
     const int w = threadIdx.x >> 6;
     const int first = threadIdx.x * E;                          // blocked ownership for the scan
@@ -140,11 +153,12 @@ __device__ __forceinline__ int small_rebucket(SmallLds &L, int cur, int n, int E
 
 __device__ __forceinline__ int small_bits(uint32_t x) { return x ? 32 - __builtin_clz(x) : 0; }
 
-template <typename IdxT>
-__global__ __launch_bounds__(kSmallThreads) void small_sufsort_kernel(const uint8_t *__restrict__ text, int n,
-                                                                      IdxT *__restrict__ sa)
+// The whole sort of one text by the workgroup that owns L: text (n <= Lds::kMaxN bytes, any alignment) -> sa (n
+// entries).  Ends with reads of L: a caller that goes on to another text puts a barrier in between.
+template <typename Lds, typename IdxT>
+__device__ __forceinline__ void small_sufsort_body(Lds &L, const uint8_t *__restrict__ text, int n, IdxT *__restrict__ sa)
 {
-    __shared__ SmallLds L;
+    constexpr int kSmallThreads = Lds::kThreads;
     const int t = threadIdx.x;
     const int E = (n + kSmallThreads - 1) / kSmallThreads;
 
@@ -176,6 +190,14 @@ __global__ __launch_bounds__(kSmallThreads) void small_sufsort_kernel(const uint
         groups = small_rebucket(L, cur, n, E);
     }
     for (int p = t; p < n; p += kSmallThreads) sa[p] = (IdxT)L.val[cur][p];
+}
+
+template <typename IdxT>
+__global__ __launch_bounds__(kSmallThreads) void small_sufsort_kernel(const uint8_t *__restrict__ text, int n,
+                                                                      IdxT *__restrict__ sa)
+{
+    __shared__ SmallLds L;
+    small_sufsort_body(L, text, n, sa);
 }
 
 }  // namespace dq

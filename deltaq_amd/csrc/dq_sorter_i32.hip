@@ -1,5 +1,7 @@
-// dq_sorter_i32.hip -- the suffix sorter for 32-bit suffix indices (dq_sorter_impl.h).
+// dq_sorter_i32.hip -- the suffix sorter for 32-bit suffix indices (dq_sorter_impl.h), and many short texts in shared
+// launches (dq_small_many.h: 32-bit indices only).
 #include "dq_sorter_impl.h"
+#include "dq_small_many.h"
 
 namespace dq {
 template int sufsort_host<int32_t>(const uint8_t *, int64_t, int32_t *, int32_t, SortHints);

@@ -115,6 +115,61 @@ class HipSuffixSort:
         _abi.check(fn(text.data_ptr() if n else None, n, suffixes.data_ptr() if n else None, dev, stream))
         return ret
 
+    # -- many short texts in shared launches (no counterpart in ISuffixSort: the reference sorts file by file) -------
+    def SortMany(self, texts):
+        """Suffix arrays of many independent texts, the short ones (up to 8192 bytes) in shared launches.
+
+        ``SortMany([t0, t1, ...])`` -- bytes-like objects / numpy uint8 arrays -- returns a list of int32 arrays, each
+        what ``Sort(t)`` returns (``dq_sufsort_hip_many_i32``).  ``SortMany((texts_tensor, offsets_tensor))`` -- a
+        pair of a uint8 and an int64 torch GPU tensor, texts back to back, ``offsets[j]`` the start of text j,
+        ``offsets[-1]`` the total -- returns ONE int32 device tensor in the same layout, entry ``offsets[j] + i``
+        being the i-th suffix of text j counted from its own start (``dq_sufsort_hip_many_dev_i32``, on the current
+        torch stream).
+        """
+        if isinstance(texts, tuple) and len(texts) == 2 and _is_torch_tensor(texts[0]):
+            return self._sort_many_device(*texts)
+        arrs = [_as_text(t) for t in texts]
+        if any(a.ndim != 1 for a in arrs):
+            raise TypeError("every text must be one-dimensional")
+        if any(a.size > INT_MAX for a in arrs):
+            raise ValueError("SortMany has 32-bit indices: every text must be shorter than 2^31 bytes")
+        count = len(arrs)
+        off = np.zeros(count + 1, dtype=np.int64)
+        if count:
+            np.cumsum([a.size for a in arrs], out=off[1:])
+        total = int(off[-1])
+        flat = np.concatenate(arrs) if total else np.zeros(1, np.uint8)
+        sas = np.empty(max(total, 1), dtype=np.int32)
+        _abi.check(self._lib.dq_sufsort_hip_many_i32(flat.ctypes.data, off.ctypes.data, count, sas.ctypes.data,
+                                                     self.device))
+        return [sas[off[j]:off[j + 1]] for j in range(count)]
+
+    sort_many = SortMany
+
+    def _sort_many_device(self, texts, offsets):
+        import torch
+
+        if not _is_torch_tensor(offsets):
+            raise TypeError("device texts need a device offsets tensor")
+        if texts.dtype != torch.uint8 or texts.dim() != 1 or not texts.is_contiguous():
+            raise TypeError("device texts must be a contiguous 1-D uint8 tensor")
+        if offsets.dtype != torch.int64 or offsets.dim() != 1 or not offsets.is_contiguous() or offsets.numel() < 1:
+            raise TypeError("offsets must be a contiguous 1-D int64 tensor of count + 1 entries")
+        if not texts.is_cuda or offsets.device != texts.device:
+            raise TypeError("texts and offsets must live on the same GPU")
+        count = offsets.numel() - 1
+        total = texts.numel()
+        sas = torch.empty(total, dtype=torch.int32, device=texts.device)
+        if count == 0:
+            return sas
+        dev, stream = _device_and_stream(texts)
+        # (a buffer of no bytes has no address: the library wants non-null pointers whenever there are texts)
+        tp = texts if total else torch.zeros(1, dtype=torch.uint8, device=texts.device)
+        sp = sas if total else torch.zeros(1, dtype=torch.int32, device=texts.device)
+        _abi.check(self._lib.dq_sufsort_hip_many_dev_i32(tp.data_ptr(), offsets.data_ptr(), count, sp.data_ptr(),
+                                                         dev, stream))
+        return sas
+
     # -- LDSSChecker.Check(T, SA)   (test/DeltaQ.SuffixSorting.LibDivSufSort.Tests/LDSSChecker.cs:23-119) --------
     def Check(self, text, suffixes) -> int:
         """LDSSChecker's verdict on ``suffixes`` as the suffix array of ``text``, decided on the device:

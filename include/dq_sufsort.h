@@ -74,6 +74,29 @@ int32_t dq_sufsort_hip_dev_i64(const void *d_text, int64_t n, void *d_sa, int32_
 int32_t dq_sufsort_hip_batch_i32(int32_t count, const uint8_t *const *texts, const int64_t *lens,
                                  int32_t *const *sas, int32_t ndev, const int32_t *devs);
 
+/* ---- many independent SHORT texts in one launch (a directory tree of small files) ----------------------------
+ * A text of up to 8192 bytes is sorted by one workgroup; sorted one by one (the entry points above) such texts cost a
+ * launch and a host round trip each and keep one compute unit busy.  Here they share launches: the workgroups of one
+ * grid take text after text, longest first, until none is left.
+ * Layout: the texts lie back to back in one buffer; offsets[count + 1] (int64, offsets[0] == 0, never decreasing) says
+ * where each begins, text j being bytes offsets[j] .. offsets[j + 1] - 1.  The suffix arrays come back to back in
+ * the same layout: sas[offsets[j] + i] is the i-th suffix of text j COUNTED FROM THE START OF TEXT j -- each segment
+ * is exactly what dq_sufsort_hip_i32 returns for that text alone (n = 0, 1, 2 included).  Nothing outside the
+ * segments is written.  The total may exceed 2^31 bytes; each text is limited to 2^31-1 (32-bit indices only).
+ * The call is total: a text longer than 8192 bytes is sorted by the device sorter, one after another, into its place.
+ * Errors, all before any device use in the host form: count < 0, a NULL pointer with count > 0, offsets[0] != 0,
+ * decreasing offsets -> DQ_ERR_BAD_ARGS; a text of 2^31 bytes or more -> DQ_ERR_TOO_LARGE.  count == 0 is a no-op.
+ *   dq_sufsort_hip_many_i32      host pointers.  Runs of short texts are copied in, sorted and copied out in chunks of
+ *                                whole texts (64 MiB of text at most: 5 bytes of device memory per chunk byte, whatever
+ *                                the total); no host staging: the copies read and write the caller's buffers.
+ *   dq_sufsort_hip_many_dev_i32  device pointers on `device` (d_offsets too: the library fetches it once to plan the
+ *                                launches, and checks it before it launches anything); work on `stream` (NULL = the
+ *                                library's), returns after the stream has drained. */
+int32_t dq_sufsort_hip_many_i32(const uint8_t *texts, const int64_t *offsets, int32_t count, int32_t *sas,
+                                int32_t device);
+int32_t dq_sufsort_hip_many_dev_i32(const void *d_texts, const void *d_offsets, int32_t count, void *d_sas,
+                                    int32_t device, void *stream);
+
 /* ---- Diff.Create's match search on the device-resident suffix array ----------
  * Replaces, for a batch of scan positions, the reference's
  *   Search(I, oldData, newData[scan..], 0, oldData.Length, out pos)          src/DeltaQ.BsDiff/Diff.cs:267-298
@@ -222,7 +245,8 @@ void dq_sufsort_hip_release(void);
 #define DQ_K_SPLIT_PASS          20   /* dq_split_round0.h: split_pass_kernel, round 0 as a sample sort: text -> pairs by top bucket (1+12), pairs -> bucket slots (12+12) */
 #define DQ_K_SPLIT_FINISH        21   /* bucket_finish_kernel: every bucket sorted by its 64-bit keys inside LDS, 12+12           */
 #define DQ_K_SPLIT_AUX           22   /* sample, splitter tables, top-bucket histogram (1 B/text byte), plans, scans, overflow placement */
-#define DQ_K_COUNT               23
+#define DQ_K_SMALL_MANY          23   /* small_many_kernel: many short texts, one workgroup each, in one launch per length class; elements = texts, 5 B/text byte */
+#define DQ_K_COUNT               24
 
 /* 0 off, 1 every kernel, 2 only radix_rank_kernel, 100 + c only category c (cheapest: the timed region) */
 int32_t dq_profile_enable(int32_t on);
@@ -249,11 +273,12 @@ int32_t dq_last_sort_info(int64_t *rounds, int64_t *initial_active, int64_t *sum
  * emitter threads. */
 int32_t dq_last_diff_info(int64_t *info, int32_t count);
 
-/* Shape of the last dq_sufsort_hip_batch_i32 on this thread, `count` entries (6 are defined, further ones read 0):
+/* Shape of the last dq_sufsort_hip_batch_i32 on this thread, `count` entries (7 are defined, further ones read 0):
  * inputs that went through the three-stage pipelines; microseconds the copy-in, the sort and the copy-out stages were
  * busy, each summed over the device shares (a share whose sort stage is busy all the time waits for the GPU, one whose
  * copy stages are waits for host memory / PCIe: what an 8-GPU run needs to tell the two apart); wall microseconds of
- * the slowest share; device shares whose host threads were bound to their device's NUMA node.  New API like the batch
+ * the slowest share; device shares whose host threads were bound to their device's NUMA node; inputs that were sorted
+ * in shared launches (short texts, dq_sufsort_hip_many_i32 below).  New API like the batch
  * entry itself: the reference has no multi-file call ("Who calls it"). */
 int32_t dq_last_batch_info(int64_t *info, int32_t count);
 
