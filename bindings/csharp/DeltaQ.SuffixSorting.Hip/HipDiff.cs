@@ -10,6 +10,7 @@
 // Ships as SOURCE (no dotnet SDK in the build image); the tested surface is the C ABI (tests/test_gpu_bsdiff.py,
 // tests/test_gpu_match_search.py bind the same exports through ctypes).
 using System;
+using System.Collections.Generic;
 using System.IO;
 using System.Runtime.InteropServices;
 
@@ -32,6 +33,13 @@ internal static unsafe class Native
 
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
     internal static extern long dq_bsdiff_patch_bound(long n, long m);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern int dq_bsdiff_create_many(byte* olds, long* oldOffsets, byte* news, long* newOffsets, int count,
+                                                     byte* patches, long* patchOffsets, long* patchLens, int device);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern int dq_last_diff_many_info(long* info, int count);
 
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
     internal static extern int dq_bspatch_apply(byte* oldData, long n, byte* patch, long patchLen, byte* output, long cap,
@@ -104,6 +112,92 @@ public static class HipDiff
         fixed (long* p = info)
         {
             Native.Check(Native.dq_last_diff_info(p, info.Length), nameof(Native.dq_last_diff_info));
+        }
+
+        return info;
+    }
+
+    /// <summary>
+    /// The patches of many independent (old, new) pairs in one native call (dq_bsdiff_create_many): pairs whose files
+    /// both have at most 8192 bytes share kernel launches and block sorts instead of costing four or five device round
+    /// trips each, longer ones are diffed one after another.  Entry j of the result is the patch
+    /// <see cref="Create"/> writes for (olds[j], news[j]).  The files are laid back to back in managed buffers for the
+    /// call and every pair gets a slot of dq_bsdiff_patch_bound bytes, so the totals are limited to what one array holds;
+    /// callers with more split their list.
+    /// </summary>
+    public static unsafe byte[][] CreateMany(IReadOnlyList<ReadOnlyMemory<byte>> olds, IReadOnlyList<ReadOnlyMemory<byte>> news,
+                                             int device = -1)
+    {
+        if (olds.Count != news.Count)
+        {
+            throw new ArgumentException("CreateMany takes as many new files as old files");
+        }
+
+        int count = olds.Count;
+        var result = new byte[count][];
+        if (count == 0)
+        {
+            return result;
+        }
+
+        var oldOffsets = new long[count + 1];
+        var newOffsets = new long[count + 1];
+        var patchOffsets = new long[count + 1];
+        for (int j = 0; j < count; j++)
+        {
+            oldOffsets[j + 1] = oldOffsets[j] + olds[j].Length;
+            newOffsets[j + 1] = newOffsets[j] + news[j].Length;
+            patchOffsets[j + 1] = patchOffsets[j] + Native.dq_bsdiff_patch_bound(olds[j].Length, news[j].Length);
+        }
+
+        if (oldOffsets[count] > Array.MaxLength || newOffsets[count] > Array.MaxLength || patchOffsets[count] > Array.MaxLength)
+        {
+            throw new ArgumentException("the files and patch slots of one CreateMany call must each total less than 2^31 bytes");
+        }
+
+        // (at least one element each: the native side wants non-null pointers whenever there are pairs)
+        byte[] flatOld = new byte[Math.Max(oldOffsets[count], 1)];
+        byte[] flatNew = new byte[Math.Max(newOffsets[count], 1)];
+        byte[] patches = new byte[Math.Max(patchOffsets[count], 1)];
+        var lens = new long[count];
+        for (int j = 0; j < count; j++)
+        {
+            olds[j].Span.CopyTo(flatOld.AsSpan((int)oldOffsets[j], olds[j].Length));
+            news[j].Span.CopyTo(flatNew.AsSpan((int)newOffsets[j], news[j].Length));
+        }
+
+        fixed (byte* pOlds = flatOld)
+        fixed (long* pOldOffsets = oldOffsets)
+        fixed (byte* pNews = flatNew)
+        fixed (long* pNewOffsets = newOffsets)
+        fixed (byte* pPatches = patches)
+        fixed (long* pPatchOffsets = patchOffsets)
+        fixed (long* pLens = lens)
+        {
+            Native.Check(Native.dq_bsdiff_create_many(pOlds, pOldOffsets, pNews, pNewOffsets, count, pPatches, pPatchOffsets,
+                                                      pLens, device),
+                         nameof(Native.dq_bsdiff_create_many));
+        }
+
+        for (int j = 0; j < count; j++)
+        {
+            result[j] = patches.AsSpan((int)patchOffsets[j], (int)lens[j]).ToArray();
+        }
+
+        return result;
+    }
+
+    /// <summary>
+    /// Shape of the last CreateMany on this thread (dq_last_diff_many_info): pairs through the shared launches, pairs
+    /// diffed one by one, launches of the anchor kernel, bzip2 blocks transformed by a shared sort, blocks sorted singly,
+    /// then microseconds per phase (sort of the old files, anchor kernel + copies, host emission, block sorts, framing).
+    /// </summary>
+    public static unsafe long[] LastDiffManyInfo()
+    {
+        var info = new long[10];
+        fixed (long* p = info)
+        {
+            Native.Check(Native.dq_last_diff_many_info(p, info.Length), nameof(Native.dq_last_diff_many_info));
         }
 
         return info;

@@ -39,6 +39,7 @@ EXPORTS = (
     "dq_sufcheck_hip_i32", "dq_sufcheck_hip_i64", "dq_sufcheck_hip_dev_i32", "dq_sufcheck_hip_dev_i64",
     "dq_bsdiff_search_dev_i32", "dq_bsdiff_search_dev_i64", "dq_bsdiff_search_i32", "dq_bsdiff_search_i64",
     "dq_bsdiff_create", "dq_bsdiff_patch_bound", "dq_bsdiff_scan_i32", "dq_bspatch_apply",
+    "dq_bsdiff_create_many", "dq_last_diff_many_info",
     "dq_bsdiff_index_create", "dq_bsdiff_index_clone", "dq_bsdiff_index_buffers", "dq_bsdiff_index_diff", "dq_bsdiff_index_free",
     "dq_sufsort_hip_workspace_bytes", "dq_sufsort_hip_workspace_plan", "dq_sufsort_hip_release",
     "dq_profile_enable", "dq_profile_reset", "dq_profile_get", "dq_profile_kernel_name",
@@ -124,6 +125,10 @@ def load() -> ctypes.CDLL:
         getattr(L, name).argtypes = [vp, i64, vp, vp, i64, vp, i64, i64, i64, vp, vp, i32]
     L.dq_bsdiff_create.restype = i32
     L.dq_bsdiff_create.argtypes = [vp, i64, vp, i64, vp, i64, ctypes.POINTER(i64), i32]
+    L.dq_bsdiff_create_many.restype = i32
+    L.dq_bsdiff_create_many.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, i32]
+    L.dq_last_diff_many_info.restype = i32
+    L.dq_last_diff_many_info.argtypes = [ctypes.POINTER(i64), i32]
     L.dq_bsdiff_patch_bound.restype = i64
     L.dq_bsdiff_patch_bound.argtypes = [i64, i64]
     L.dq_bsdiff_scan_i32.restype = i32
@@ -213,6 +218,16 @@ def last_diff_info() -> dict:
     L.dq_last_diff_info(v, 9)
     return {"searches": v[0], "windows": v[1], "exact": v[2], "host_loop_fallbacks": v[3], "scan_groups": v[4],
             "chains_launched": v[5], "chains_joined": v[6], "chains_dropped": v[7], "triples_from_chain_emitters": v[8]}
+
+
+def last_diff_many_info() -> dict:
+    """Shape of the last dq_bsdiff_create_many on this thread (dq_last_diff_many_info)."""
+    L = load()
+    v = (ctypes.c_int64 * 10)()
+    L.dq_last_diff_many_info(v, 10)
+    return {"shared_pairs": v[0], "single_pairs": v[1], "anchor_launches": v[2], "shared_block_sorts": v[3],
+            "single_block_sorts": v[4], "sort_old_ms": v[5] / 1e3, "anchor_ms": v[6] / 1e3, "emit_ms": v[7] / 1e3,
+            "block_sort_ms": v[8] / 1e3, "frame_ms": v[9] / 1e3}
 
 
 def last_batch_info() -> dict:

@@ -52,6 +52,36 @@ class Diff:
         return buf[:ln.value].tobytes()
 
     @staticmethod
+    def CreateMany(olds, news, device: int = -1) -> list:
+        """``[Diff.CreateBytes(o, n) for o, n in zip(olds, news)]`` in one call (dq_bsdiff_create_many): pairs whose
+        files both have at most 8192 bytes share their device launches, longer ones are diffed one by one.  ``olds`` /
+        ``news``: sequences of bytes-likes or uint8 arrays, of equal length."""
+        L = _abi.load()
+        olds, news = list(olds), list(news)
+        if len(olds) != len(news):
+            raise ValueError(f"CreateMany: {len(olds)} old files against {len(news)} new files")
+        count = len(olds)
+        if count == 0:
+            return []
+        O, N = [_as_text(x) for x in olds], [_as_text(x) for x in news]
+
+        def pack(arrs):
+            off = np.zeros(count + 1, np.int64)
+            np.cumsum([a.size for a in arrs], out=off[1:])
+            flat = np.concatenate(arrs) if int(off[-1]) else np.zeros(1, np.uint8)
+            return np.ascontiguousarray(flat, dtype=np.uint8), off
+
+        o_flat, o_off = pack(O)
+        n_flat, n_off = pack(N)
+        p_off = np.zeros(count + 1, np.int64)
+        np.cumsum([L.dq_bsdiff_patch_bound(o.size, n.size) for o, n in zip(O, N)], out=p_off[1:])
+        buf = np.empty(int(p_off[-1]), dtype=np.uint8)          # (slots of the bound's size: pages no patch reaches stay untouched)
+        lens = np.full(count, -1, np.int64)
+        _abi.check(L.dq_bsdiff_create_many(o_flat.ctypes.data, o_off.ctypes.data, n_flat.ctypes.data, n_off.ctypes.data, count,
+                                           buf.ctypes.data, p_off.ctypes.data, lens.ctypes.data, device))
+        return [buf[int(p_off[j]):int(p_off[j]) + int(lens[j])].tobytes() for j in range(count)]
+
+    @staticmethod
     def Scan(oldData, newData, device: int = -1):
         """The raw streams of the scan loop (before bzip2): (ctrl triples [k, 3] int64, diff bytes, extra bytes,
         {searches, windows, exact})."""

@@ -508,6 +508,19 @@ void dq_bsdiff_index_free(void *index)
     diff_index_delete(index);
 }
 
+int32_t dq_bsdiff_create_many(const uint8_t *olds, const int64_t *old_offsets, const uint8_t *news, const int64_t *new_offsets,
+                              int32_t count, uint8_t *patches, const int64_t *patch_offsets, int64_t *patch_lens, int32_t device)
+{
+    EnvScope scope;
+    try {
+        return bsdiff_create_many_host(olds, old_offsets, news, new_offsets, count, patches, patch_offsets, patch_lens, device);
+    } catch (const std::bad_alloc &) {
+        return fail(DQ_ERR_OOM, "bsdiff: host allocation failed");
+    } catch (const std::exception &e) {            // nothing may propagate through the C ABI
+        return fail(DQ_ERR_HIP, e.what());
+    }
+}
+
 int64_t dq_bsdiff_patch_bound(int64_t n, int64_t m)
 {
     if (n < 0 || m < 0) return -1;
@@ -646,6 +659,13 @@ int32_t dq_device_numa_node(int32_t device)
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) return -1;
     return device_numa_node(device);
+}
+
+int32_t dq_last_diff_many_info(int64_t *info, int32_t count)
+{
+    if (!info || count < 0) return fail(DQ_ERR_BAD_ARGS, "bad arguments");
+    for (int32_t k = 0; k < count; ++k) info[k] = k < 10 ? t_diff_many_info[k] : 0;
+    return DQ_OK;
 }
 
 int32_t dq_last_diff_info(int64_t *info, int32_t count)

@@ -479,23 +479,18 @@ inline void make_code_lengths(uint8_t *len, const int32_t *freq, int alpha, int 
 // sa_of_doubled(text, n2, sa): suffix array (int32, n2 entries) of the n2 = 2 * nblock bytes block+block.
 using DoubledSorter = std::function<int(const uint8_t *text, int64_t n2, int32_t *sa)>;
 
-// One block: `blk` is the run-length coded data (nblock bytes), crc the CRC of the original bytes it stands for.
-inline int compress_block(BitWriter &bw, const std::vector<uint8_t> &blk, uint32_t crc, const DoubledSorter &sorter)
+// One block, behind its transform: `blk` is the run-length coded data (nblock bytes), crc the CRC of the original bytes
+// it stands for, `sa` the finished suffix array (2 * nblock entries) of block+block, whoever sorted it -- the caller's
+// sorter (compress_block below) or a sort shared with the blocks of other streams (dq_bsdiff_create_many).  Last
+// column, MTF, Huffman tables, bits.  sort_ms: what the transform took (DQ_TRACE prints it).
+inline int compress_block_sorted(BitWriter &bw, const std::vector<uint8_t> &blk, uint32_t crc, const int32_t *sa, double sort_ms = 0)
 {
     const int32_t nblock = (int32_t)blk.size();
     const bool trace = flags().trace.has_value();
     auto now = [] { return std::chrono::steady_clock::now(); };
     auto t_prev = now();
-    double t_ph[5] = {0, 0, 0, 0, 0};                       // sort, last column, MTF, tables, bits
+    double t_ph[5] = {sort_ms, 0, 0, 0, 0};                 // sort, last column, MTF, tables, bits
     auto lap = [&](int k) { const auto t = now(); t_ph[k] += std::chrono::duration<double, std::milli>(t - t_prev).count(); t_prev = t; };
-    // ---- Burrows-Wheeler transform through the suffix array of block+block ----
-    std::vector<uint8_t> doubled((size_t)nblock * 2);
-    memcpy(doubled.data(), blk.data(), (size_t)nblock);
-    memcpy(doubled.data() + nblock, blk.data(), (size_t)nblock);
-    std::vector<int32_t> sa((size_t)nblock * 2);
-    const int rc = sorter(doubled.data(), (int64_t)nblock * 2, sa.data());
-    if (rc != 0) return rc;
-    lap(0);
     std::vector<uint8_t> last((size_t)nblock);
     int32_t orig_ptr = -1, row = 0;
     for (int32_t i = 0; i < 2 * nblock; ++i) {
@@ -687,6 +682,28 @@ inline int compress_block(BitWriter &bw, const std::vector<uint8_t> &blk, uint32
     return 0;
 }
 
+// block+block, the text whose suffix array is the block's Burrows-Wheeler transform: 2 * blk.size() bytes at `out`
+inline void double_block(const std::vector<uint8_t> &blk, uint8_t *out)
+{
+    memcpy(out, blk.data(), blk.size());
+    memcpy(out + blk.size(), blk.data(), blk.size());
+}
+
+// One block through the caller's sorter: the transform (block+block to `sorter`), then compress_block_sorted.
+inline int compress_block(BitWriter &bw, const std::vector<uint8_t> &blk, uint32_t crc, const DoubledSorter &sorter)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t nblock = blk.size();
+    std::vector<uint8_t> doubled(nblock * 2);
+    double_block(blk, doubled.data());
+    std::vector<int32_t> sa(nblock * 2);
+    const int rc = sorter(doubled.data(), (int64_t)nblock * 2, sa.data());
+    if (rc != 0) return rc;
+    std::vector<uint8_t>().swap(doubled);
+    return compress_block_sorted(bw, blk, crc, sa.data(),
+                                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+}
+
 // The blocks of a stream -- Burrows-Wheeler transform through the sorter, MTF / Huffman -- are independent and go to up
 // to 4 threads (the extra stream of two unrelated 4 MiB files is five blocks of random bytes: 250 ms of move-to-front
 // on one thread); their bit strings are then appended in order.
@@ -856,6 +873,26 @@ public:
     }
 
     size_t consumed() const { return pos; }
+
+    // The two-part route (hold_blocks() before feed(), so that no block leaves for an encoder thread): the run-length
+    // coded blocks as the pre-pass cut them, for a caller that sorts the blocks of many streams in one shared sort and
+    // hands each block its finished suffix array (2 * block_rle(i).size() entries); finish() then strings them together.
+    size_t block_count() const { return blocks.size(); }
+    const std::vector<uint8_t> &block_rle(size_t i) const { return blocks[i].rle; }
+    void encode_block_sorted(size_t i, const int32_t *sa)
+    {
+        Block &b = blocks[i];
+        b.claimed.store(1);
+        try {
+            BitWriter w(b.bytes);
+            b.rc = compress_block_sorted(w, b.rle, b.crc, sa);
+            b.nbits = w.total;
+            w.flush();
+            std::vector<uint8_t>().swap(b.rle);
+        } catch (...) {
+            b.rc = -3;
+        }
+    }
 
     // (tests: the run-length coded blocks and their CRCs as the pre-pass cut them, before anything is encoded --
     // constructed with hold = true, so that no block leaves for an encoder thread)

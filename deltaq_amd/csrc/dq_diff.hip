@@ -6,6 +6,7 @@
 #include "dq_runtime.h"
 #include "dq_match_search.h"
 #include "dq_anchor_scan.h"
+#include "dq_anchor_many.h"
 #include "dq_scan_wait.h"
 #include "dq_bz2.h"
 #include "dq_bsdiff.h"
@@ -1386,7 +1387,347 @@ int frame_patch(const bsdiff::RawStreams &raw, int64_t m, int dev, std::vector<u
     for (int k = 0; k < 3; ++k) patch.insert(patch.end(), z[k].begin(), z[k].end());
     return DQ_OK;
 }
+
+// ---- many short pairs in shared launches (dq_bsdiff_create_many) ----------------------------------------------------
+// A pair of files of up to kDiffManyMax bytes each costs the one-pair path four or five dependent device round trips
+// (sort of old, anchor scan, up to three block sorts) for a few kilobytes.  Here the pairs of a call travel in chunks
+// of whole pairs -- at most kDiffManyChunkBytes of old + new -- and every chunk goes through five phases, each shared
+// by all its pairs:
+//   1. old and new files and their offsets to the device; sufsort_many_dev on the old files (the suffix arrays stay there)
+//   2. anchor_many_kernel (dq_anchor_many.h): the (cursor, hit_pos) list of every pair; lists to the host
+//   3. host threads: TripleEmitter + scan_from_anchors per pair -> RawStreams; run-length pre-pass and CRC of the three
+//      streams (bz2::StreamEncoder with its blocks held back)
+//   4. all blocks of all streams of the chunk, doubled and laid back to back: ONE sufsort_many_host call (a block whose
+//      doubled length exceeds the short-text limit takes that call's own one-by-one route)
+//   5. host threads: each block finished from its suffix array, header + three streams into the pair's slot.
+// Device memory per chunk: old + new + 4 bytes of suffix array per byte of old + one int32 per byte of new for the
+// anchor lists + 40 bytes per pair (< 6 bytes per byte of text).  Host memory per chunk: the raw streams (< 4 bytes
+// per byte of new), their blocks doubled with 4 bytes of suffix array per doubled byte (10 bytes per stream byte).
+constexpr int64_t kDiffManyChunkBytes = 64ll << 20;
+constexpr int32_t kDiffManyChunkPairs = 1 << 18;
+
+// anchors a pair of `m` new bytes can emit: every triple but the last stands on a match of more than 8 bytes
+// (hit_len > carried + 8, carried >= 0) and the scan goes on behind it, so there are at most m / 9 + 1
+inline int64_t diff_many_anchor_room(int64_t m) { return m / 8 + 2; }
+
+struct DeviceBuf {                      // one allocation of the call, grown when a later chunk needs more
+    char *p = nullptr;
+    size_t bytes = 0;
+    int dev = 0;
+    ~DeviceBuf() { if (p) { (void)hipSetDevice(dev); (void)hipFree(p); } }
+    int need(size_t want)
+    {
+        if (bytes >= want) return DQ_OK;
+        if (p) { (void)hipFree(p); p = nullptr; bytes = 0; }
+        const hipError_t e = dq_malloc((void **)&p, want);
+        if (e != hipSuccess) return fail(DQ_ERR_OOM, "hipMalloc(many pairs)", e);
+        bytes = want;
+        return DQ_OK;
+    }
+};
+
+// fn(i) for i in [0, count) on the caller's thread and as many framing threads as the process-wide budget grants
+template <typename Fn>
+void diff_many_parallel(int64_t count, Fn fn)
+{
+    std::atomic<int64_t> next{0};
+    auto work = with_flags([&] {
+        for (;;) {
+            const int64_t a = next.fetch_add(16);
+            if (a >= count) return;
+            for (int64_t i = a; i < std::min(count, a + 16); ++i) fn(i);
+        }
+    });
+    const int granted = bz2::framing_threads_acquire((int)std::min<int64_t>(15, count / 32));
+    {
+        JoinAll threads;
+        for (int t = 0; t < granted; ++t) {
+            try { threads.v.emplace_back(work); } catch (const std::exception &) { break; }
+        }
+        work();
+    }
+    bz2::framing_threads_release(granted);
+}
+
+inline int64_t us_since(std::chrono::steady_clock::time_point t0)
+{
+    return std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+}
+
+struct ManyPair {
+    bsdiff::RawStreams raw;
+    std::unique_ptr<bz2::StreamEncoder> enc[3];
+    int64_t first_block = 0;            // number of its first block (ctrl's, diff's, extra's, in that order) among the chunk's, in pairs' order
+    std::vector<uint8_t> patch;
+    int rc = DQ_OK;
+    std::string err;
+};
+
+// pairs [first, first + cnt) of the call, all short: their patches into `out`
+int diff_many_chunk(const uint8_t *olds, const int64_t *ooff, const uint8_t *news, const int64_t *noff, int32_t first, int32_t cnt,
+                    int dev, DeviceBuf &buf, std::vector<ManyPair> &out)
+{
+    HIP_TRY(hipSetDevice(dev));                            // (the chunk's allocation below is this device's)
+    const int64_t o_base = ooff[first], n_base = noff[first];
+    const int64_t o_bytes = ooff[first + cnt] - o_base, n_bytes = noff[first + cnt] - n_base;
+    out.clear();
+    out.resize((size_t)cnt);
+    // offsets relative to the chunk; anchor room per pair; the work list, longest new first
+    std::vector<int64_t> off((size_t)(cnt + 1) * 3);
+    int64_t *rel_o = off.data(), *rel_n = rel_o + cnt + 1, *rel_a = rel_n + cnt + 1;
+    rel_a[0] = 0;
+    for (int32_t j = 0; j <= cnt; ++j) {
+        rel_o[j] = ooff[first + j] - o_base;
+        rel_n[j] = noff[first + j] - n_base;
+        if (j > 0) rel_a[j] = rel_a[j - 1] + diff_many_anchor_room(rel_n[j] - rel_n[j - 1]);
+    }
+    const int64_t anchors = rel_a[cnt];
+    std::vector<int32_t> order((size_t)cnt);
+    for (int32_t j = 0; j < cnt; ++j) order[(size_t)j] = j;
+    std::stable_sort(order.begin(), order.end(),
+                     [&](int32_t a, int32_t b) { return rel_n[a + 1] - rel_n[a] > rel_n[b + 1] - rel_n[b]; });
+    // what comes back: anchor lists, then counts and searches per pair
+    std::vector<int32_t> back((size_t)anchors * 2 + (size_t)cnt * 2);
+
+    // ---- 1. + 2. on the device.  (A device context is leased for the copies and again for the kernel, never across the
+    // sort in between, which leases its own: two callers holding one each and waiting for a second would wait for ever.)
+    {
+        const size_t b_old = align_up((size_t)o_bytes + 64), b_new = align_up((size_t)n_bytes + 64),
+                     b_sa = align_up((size_t)o_bytes * sizeof(int32_t) + 64), b_off = align_up(off.size() * sizeof(int64_t)),
+                     b_order = align_up(order.size() * sizeof(int32_t)), b_next = 256, b_back = align_up(back.size() * sizeof(int32_t));
+        int rc = buf.need(b_old + b_new + b_sa + b_off + b_order + b_next + b_back);
+        if (rc != DQ_OK) return rc;
+        char *q = buf.p;
+        uint8_t *d_old = reinterpret_cast<uint8_t *>(q); q += b_old;
+        uint8_t *d_new = reinterpret_cast<uint8_t *>(q); q += b_new;
+        int32_t *d_sa = reinterpret_cast<int32_t *>(q); q += b_sa;
+        int64_t *d_off = reinterpret_cast<int64_t *>(q); q += b_off;
+        int32_t *d_order = reinterpret_cast<int32_t *>(q); q += b_order;
+        uint32_t *d_next = reinterpret_cast<uint32_t *>(q); q += b_next;
+        int32_t *d_back = reinterpret_cast<int32_t *>(q);
+        auto upload = [&](DeviceCtx &c, hipStream_t st) -> int {
+            const auto t0 = std::chrono::steady_clock::now();
+            if (o_bytes > 0) HIP_TRY(hipMemcpyAsync(d_old, olds + o_base, (size_t)o_bytes, hipMemcpyHostToDevice, st));
+            if (n_bytes > 0) HIP_TRY(hipMemcpyAsync(d_new, news + n_base, (size_t)n_bytes, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(d_off, off.data(), off.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(d_order, order.data(), order.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemsetAsync(d_next, 0, b_next, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            t_diff_many_info[6] += us_since(t0);
+            return DQ_OK;
+        };
+        auto sort_olds = [&]() -> int {
+            const auto t0 = std::chrono::steady_clock::now();
+            const int r = sufsort_many_dev(d_old, d_off, cnt, d_sa, dev, nullptr);     // Diff.cs:90 for every pair
+            if (r != DQ_OK) return r;
+            HIP_TRY(hipSetDevice(dev));
+            HIP_TRY(hipDeviceSynchronize());               // (whichever streams its routes used)
+            t_diff_many_info[5] += us_since(t0);
+            return DQ_OK;
+        };
+        auto scan = [&](DeviceCtx &c, hipStream_t st) -> int {
+            const auto t0 = std::chrono::steady_clock::now();
+            if (c.anchor_many_groups <= 0) {
+                // workgroups the device holds at once (a wrong answer costs time only: nobody waits for anybody)
+                int per_cu = 0, ncu = 0;
+                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, anchor_many_kernel, kAmThreads, 0) != hipSuccess || per_cu <= 0)
+                    per_cu = 1;
+                if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
+                c.anchor_many_groups = per_cu * ncu;
+            }
+            Launcher L{c, st, g_prof_on.load()};
+            const int grid = std::min<int>(cnt, c.anchor_many_groups);
+            LAUNCH(L, DQ_K_MATCH_SEARCH, n_bytes, o_bytes * 5 + n_bytes,
+                   hipLaunchKernelGGL(anchor_many_kernel, dim3((unsigned)grid), dim3(kAmThreads), 0, st, d_old, d_off, d_sa, d_new,
+                                      d_off + (cnt + 1), d_off + 2 * (cnt + 1), d_order, cnt, d_next, d_back, d_back + 2 * anchors,
+                                      d_back + 2 * anchors + cnt));
+            t_diff_many_info[2] += 1;
+            const hipError_t e1 = hipMemcpyAsync(back.data(), d_back, back.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+            const hipError_t e2 = hipStreamSynchronize(st);
+            HIP_TRY(e1 != hipSuccess ? e1 : e2);
+            t_diff_many_info[6] += us_since(t0);
+            return flush_profile(c);
+        };
+        auto leased = [&](auto &&step) -> int {
+            SlotLease lease(dev, 0);
+            DeviceCtx &c = *lease.c;
+            int r = init_ctx(c, dev);
+            if (r != DQ_OK) return r;
+            r = step(c, c.stream);
+            if (r != DQ_OK) drop_pending(c, c.stream);
+            return r;
+        };
+        rc = leased(upload);
+        if (rc == DQ_OK) rc = sort_olds();
+        if (rc == DQ_OK) rc = leased(scan);
+        if (rc != DQ_OK) return rc;
+    }
+    const int32_t *counts = back.data() + 2 * anchors, *searches = counts + cnt;
+
+    // ---- 3. the raw streams of every pair, and their blocks up to the transform
+    auto t0 = std::chrono::steady_clock::now();
+    diff_many_parallel(cnt, [&](int64_t j) {
+        ManyPair &w = out[(size_t)j];
+        try {
+            const int64_t n = rel_o[j + 1] - rel_o[j], m = rel_n[j + 1] - rel_n[j];
+            const int32_t k = counts[j];
+            if (k < 0 || k > rel_a[j + 1] - rel_a[j]) { w.rc = DQ_ERR_HIP; w.err = "anchor list of a pair is not complete"; return; }
+            const uint8_t *old = olds + ooff[first + j], *nw = news + noff[first + j];
+            bsdiff::TripleEmitter em(old, n, nw, m, w.raw);
+            const int32_t *a = back.data() + 2 * rel_a[j];
+            for (int32_t t = 0; t < k; ++t) {
+                const int64_t pair[2] = {a[2 * t], a[2 * t + 1]};
+                // (the emitter indexes both files with them: never beyond what the kernel may have written)
+                if (pair[0] < em.prev.at || pair[0] > m || pair[1] < 0 || pair[1] > n || (t == k - 1) != (pair[0] == m)) {
+                    w.rc = DQ_ERR_HIP; w.err = "anchor list of a pair is out of range"; return;
+                }
+                bsdiff::scan_from_anchors(em, pair, 1);
+            }
+            if ((m > 0) != (k > 0)) { w.rc = DQ_ERR_HIP; w.err = "anchor list of a pair is not complete"; return; }
+            w.raw.searches = searches[j];
+            const std::vector<uint8_t> *src[3] = {&w.raw.ctrl, &w.raw.diff, &w.raw.extra};
+            for (int s = 0; s < 3; ++s) {
+                w.enc[s].reset(new bz2::StreamEncoder(bz2::DoubledSorter()));
+                w.enc[s]->hold_blocks();
+                w.enc[s]->feed(src[s]->data(), src[s]->size(), true);
+            }
+        } catch (const std::exception &e) {
+            w.rc = DQ_ERR_OOM; w.err = std::string("bsdiff: ") + e.what();
+        }
+    });
+    for (ManyPair &w : out)
+        if (w.rc != DQ_OK) { t_err = w.err; return w.rc; }
+    t_diff_many_info[7] += us_since(t0);
+
+    // ---- 4. every block of the chunk in one shared sort
+    t0 = std::chrono::steady_clock::now();
+    // (the short blocks first, then the long ones: sufsort_many_host shares launches among neighbours in its list, and a
+    // long block between two short ones would end a chunk of them)
+    std::vector<int64_t> blen;                             // doubled length per block, pairs' order
+    for (ManyPair &w : out) {
+        w.first_block = (int64_t)blen.size();
+        for (int s = 0; s < 3; ++s)
+            for (size_t b = 0; b < w.enc[s]->block_count(); ++b) blen.push_back(2 * (int64_t)w.enc[s]->block_rle(b).size());
+    }
+    const int64_t nblocks = (int64_t)blen.size();
+    if (nblocks > 0x7fffffffLL) return fail(DQ_ERR_TOO_LARGE, "too many bzip2 blocks in one chunk");
+    std::vector<int64_t> bplace((size_t)nblocks), boff((size_t)nblocks + 1, 0);      // block -> place in the list; the list's offsets
+    {
+        int64_t at = 0;
+        for (int pass = 0; pass < 2; ++pass)
+            for (int64_t b = 0; b < nblocks; ++b)
+                if ((blen[(size_t)b] > kSmallMaxN) == (pass == 1)) {
+                    bplace[(size_t)b] = at;
+                    boff[(size_t)at + 1] = boff[(size_t)at] + blen[(size_t)b];
+                    ++at;
+                }
+    }
+    std::vector<uint8_t> btext((size_t)boff.back());
+    std::vector<int32_t> bsa((size_t)boff.back());
+    diff_many_parallel(cnt, [&](int64_t j) {
+        ManyPair &w = out[(size_t)j];
+        int64_t at = w.first_block;
+        for (int s = 0; s < 3; ++s)
+            for (size_t b = 0; b < w.enc[s]->block_count(); ++b)
+                bz2::double_block(w.enc[s]->block_rle(b), btext.data() + boff[(size_t)bplace[(size_t)at++]]);
+    });
+    int64_t shared = 0;
+    const int rc = sufsort_many_host(btext.data(), boff.data(), (int32_t)nblocks, bsa.data(), dev, &shared);
+    if (rc != DQ_OK) return rc;
+    std::vector<uint8_t>().swap(btext);
+    t_diff_many_info[3] += shared;
+    t_diff_many_info[4] += nblocks - shared;
+    t_diff_many_info[8] += us_since(t0);
+
+    // ---- 5. the blocks' bits, the streams, the patches
+    t0 = std::chrono::steady_clock::now();
+    diff_many_parallel(cnt, [&](int64_t j) {
+        ManyPair &w = out[(size_t)j];
+        try {
+            int64_t at = w.first_block;
+            std::vector<uint8_t> z[3];
+            for (int s = 0; s < 3; ++s) {
+                for (size_t b = 0; b < w.enc[s]->block_count(); ++b) w.enc[s]->encode_block_sorted(b, bsa.data() + boff[(size_t)bplace[(size_t)at++]]);
+                if (w.enc[s]->finish(z[s]) != 0) { w.rc = DQ_ERR_HIP; w.err = "bzip2 block transform failed"; return; }
+                w.enc[s].reset();
+            }
+            const int64_t m = rel_n[j + 1] - rel_n[j];
+            w.patch.assign((size_t)bsdiff::kHeaderSize, 0);                             // as frame_patch
+            bsdiff::write_packed_long(&w.patch[0], bsdiff::kSignature);
+            bsdiff::write_packed_long(&w.patch[8], (int64_t)z[0].size());
+            bsdiff::write_packed_long(&w.patch[16], (int64_t)z[1].size());
+            bsdiff::write_packed_long(&w.patch[24], m);
+            w.patch.reserve(w.patch.size() + z[0].size() + z[1].size() + z[2].size());
+            for (int s = 0; s < 3; ++s) w.patch.insert(w.patch.end(), z[s].begin(), z[s].end());
+            w.raw = bsdiff::RawStreams{};
+        } catch (const std::exception &e) {
+            w.rc = DQ_ERR_OOM; w.err = std::string("bsdiff: ") + e.what();
+        }
+    });
+    for (ManyPair &w : out)
+        if (w.rc != DQ_OK) { t_err = w.err; return w.rc; }
+    t_diff_many_info[9] += us_since(t0);
+    return DQ_OK;
+}
 }  // namespace
+
+int bsdiff_create_many_host(const uint8_t *olds, const int64_t *ooff, const uint8_t *news, const int64_t *noff, int32_t count,
+                            uint8_t *patches, const int64_t *poff, int64_t *plens, int32_t device)
+{
+    for (int64_t &x : t_diff_many_info) x = 0;
+    if (count < 0) return fail(DQ_ERR_BAD_ARGS, "negative count");
+    if (count == 0) return DQ_OK;
+    if (!olds || !ooff || !news || !noff || !patches || !poff || !plens) return fail(DQ_ERR_BAD_ARGS, "null buffer");
+    for (const int64_t *off : {ooff, noff, poff})
+        if (off[0] != 0) return fail(DQ_ERR_BAD_ARGS, "offsets[0] must be 0");
+    for (int32_t j = 0; j < count; ++j)
+        if (ooff[j + 1] < ooff[j] || noff[j + 1] < noff[j] || poff[j + 1] < poff[j]) return fail(DQ_ERR_BAD_ARGS, "offsets must not decrease");
+    for (int32_t j = 0; j < count; ++j)
+        if (ooff[j + 1] - ooff[j] > 0x7fffffffLL || noff[j + 1] - noff[j] > 0x7fffffffLL)
+            return fail(DQ_ERR_TOO_LARGE, "the BSDIFF40 path takes files below 2 GiB (int indices, as the reference)");
+    for (int32_t j = 0; j < count; ++j) plens[j] = -1;
+    int dev = 0;
+    int rc = resolve_device(device, &dev);
+    if (rc != DQ_OK) return rc;
+
+    auto deliver = [&](int32_t j, const std::vector<uint8_t> &patch) -> int {
+        if ((int64_t)patch.size() > poff[j + 1] - poff[j]) return fail(DQ_ERR_BAD_ARGS, "output buffer too small (see dq_bsdiff_patch_bound)");
+        if (!patch.empty()) memcpy(patches + poff[j], patch.data(), patch.size());
+        plens[j] = (int64_t)patch.size();
+        return DQ_OK;
+    };
+    const int64_t short_max = kDiffManyMax;
+    const bool one_by_one = flags().no_diff_many.value_or(0) != 0;
+    auto is_short = [&](int32_t j) { return !one_by_one && ooff[j + 1] - ooff[j] <= short_max && noff[j + 1] - noff[j] <= short_max; };
+    DeviceBuf buf;
+    buf.dev = dev;
+    std::vector<ManyPair> done;
+    for (int32_t i = 0; i < count;) {
+        if (!is_short(i)) {
+            // the one-pair path, into the pair's slot (it reports under its own dq_last_diff_info)
+            std::vector<uint8_t> patch;
+            rc = bsdiff_create_host(olds + ooff[i], ooff[i + 1] - ooff[i], news + noff[i], noff[i + 1] - noff[i], dev, patch);
+            if (rc == DQ_OK) rc = deliver(i, patch);
+            if (rc != DQ_OK) return rc;
+            t_diff_many_info[1] += 1;
+            ++i;
+            continue;
+        }
+        int32_t e = i;
+        while (e < count && e - i < kDiffManyChunkPairs && is_short(e) &&
+               (ooff[e + 1] - ooff[i]) + (noff[e + 1] - noff[i]) <= kDiffManyChunkBytes)
+            ++e;
+        rc = diff_many_chunk(olds, ooff, news, noff, i, e - i, dev, buf, done);
+        if (rc != DQ_OK) return rc;
+        t_diff_many_info[0] += e - i;
+        for (int32_t j = i; j < e; ++j) {
+            rc = deliver(j, done[(size_t)(j - i)].patch);
+            if (rc != DQ_OK) return rc;
+        }
+        i = e;
+    }
+    return DQ_OK;
+}
 
 int bsdiff_create_host(const uint8_t *old, int64_t n, const uint8_t *nw, int64_t m, int32_t device, std::vector<uint8_t> &patch)
 {

@@ -40,6 +40,7 @@ inline thread_local int64_t t_info[3] = {0, 0, 0};
 // the last Diff.Create / index diff on this thread (dq_last_diff_info): Search calls of the loop, windows, positions
 // asked again exactly, launches of the device's anchor scan that were given back to the host loop, workgroups of its grid
 inline thread_local int64_t t_diff_info[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+inline thread_local int64_t t_diff_many_info[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};     // dq_last_diff_many_info
 
 // the last dq_sufsort_hip_batch_i32 on this thread (dq_last_batch_info): inputs through the pipelines, microseconds the
 // copy-in / sort / copy-out stages were busy (summed over the device shares), wall microseconds of the slowest share,
@@ -100,6 +101,7 @@ struct DeviceCtx {
     int dev = -1;
     int ncu = 0;                        // compute units of the device (grid of the persistent kernels)
     int many_groups[3] = {0, 0, 0};     // workgroups of small_many_kernel the device holds at once, per length class (0: not asked yet)
+    int anchor_many_groups = 0;         // ... and of anchor_many_kernel (dq_anchor_many.h)
     hipStream_t stream = nullptr;
     char *ws = nullptr;
     size_t ws_bytes = 0;
@@ -425,6 +427,8 @@ int match_search_host_i64(const uint8_t *old, int64_t n, const int64_t *sa, cons
 int bsdiff_scan_raw(const uint8_t *old, int64_t n, const uint8_t *nw, int64_t m, int32_t device, std::vector<int64_t> &ctrl,
                     std::vector<uint8_t> &diff, std::vector<uint8_t> &extra, int64_t stats[3]);
 int bsdiff_create_host(const uint8_t *old, int64_t n, const uint8_t *nw, int64_t m, int32_t device, std::vector<uint8_t> &patch);
+int bsdiff_create_many_host(const uint8_t *olds, const int64_t *old_offsets, const uint8_t *news, const int64_t *new_offsets, int32_t count,
+                            uint8_t *patches, const int64_t *patch_offsets, int64_t *patch_lens, int32_t device);
 int bspatch_apply_host(const uint8_t *old, int64_t n, const uint8_t *patch, int64_t plen, uint8_t *out, int64_t cap, int64_t *out_len);
 int diff_index_new(const uint8_t *old, int64_t n, int32_t device, const void *d_old, const void *d_sa, void **index_out);
 int diff_index_clone(const void *index, int32_t device, void **index_out);

@@ -143,6 +143,31 @@ int32_t dq_bsdiff_create(const uint8_t *old_data, int64_t n, const uint8_t *new_
                          int64_t cap, int64_t *patch_len, int32_t device);
 int64_t dq_bsdiff_patch_bound(int64_t n, int64_t m);
 
+/* ---- many SHORT file pairs in shared launches (two directory trees of small files) ------------------------------
+ * dq_bsdiff_create_many: `count` independent (old, new) pairs in one call.  Layout as dq_sufsort_hip_many_i32: the old
+ * files back to back in `olds`, the new files in `news`, each with an offsets array of count + 1 int64 entries
+ * (offsets[0] == 0, never decreasing); pair j is olds[old_offsets[j] .. old_offsets[j + 1]) against
+ * news[new_offsets[j] .. new_offsets[j + 1]).  patch_offsets[count + 1] gives every pair its slot in `patches`
+ * (capacity patch_offsets[j + 1] - patch_offsets[j]; dq_bsdiff_patch_bound(n_j, m_j) always suffices), patch_lens[j]
+ * receives the length; nothing outside patches[patch_offsets[j] .. + patch_lens[j]) is written.
+ * Patch j is byte for byte what dq_bsdiff_create returns for pair j alone, empty files on either side included.
+ * Pairs whose files both have at most 8192 bytes share their launches: in chunks of whole pairs (at most 64 MiB of
+ * old + new, 262 144 pairs), the old files are sorted by the launches of dq_sufsort_hip_many_dev_i32, one launch of
+ * anchor_many_kernel finds the anchors of every pair (one workgroup per pair, nobody waits for anybody), host threads
+ * turn them into the raw streams, all bzip2 blocks of the chunk are transformed by one dq_sufsort_hip_many_i32-style
+ * sort and host threads frame the patches.  The call is total: a pair with a longer file (below 2 GiB) is diffed by
+ * dq_bsdiff_create's path, one after another, into its slot.
+ * Footprint per chunk -- device: old + new + 4 bytes per byte of old + 1 byte per byte of new + 40 bytes per pair, freed
+ * on return; host: below 4 bytes per byte of new for the raw streams and 10 bytes per byte of stream for the shared sort.
+ * Errors found before any device use: count < 0, a NULL pointer with count > 0, offsets[0] != 0 or decreasing offsets
+ * in any of the three arrays -> DQ_ERR_BAD_ARGS; a file of 2^31 bytes or more -> DQ_ERR_TOO_LARGE.  count == 0 is a
+ * no-op.  A slot too small for its patch -> DQ_ERR_BAD_ARGS ("output buffer too small"), known only once the patch
+ * is.  The first failing pair's code is returned: pairs before it have their patches and lengths, patch_lens of the
+ * others read -1.  New API like the batch entry: the reference diffs one pair per Diff.Create call. */
+int32_t dq_bsdiff_create_many(const uint8_t *olds, const int64_t *old_offsets, const uint8_t *news,
+                              const int64_t *new_offsets, int32_t count, uint8_t *patches, const int64_t *patch_offsets,
+                              int64_t *patch_lens, int32_t device);
+
 /* ---- one old file, many new files (the many-files bsdiff path of the batch mode) --------------------------------
  * Diff.Create sorts oldData on every call (Diff.cs:89-90); the suffix array depends on the old file alone.  An index
  * holds (old, suffix array, the match search's prefix table) on one device; any number of new files are diffed
@@ -272,6 +297,12 @@ int32_t dq_last_sort_info(int64_t *rounds, int64_t *initial_active, int64_t *sum
  * their entries are the loop's from there on), grids dropped unjoined, control triples taken over from the grids' own
  * emitter threads. */
 int32_t dq_last_diff_info(int64_t *info, int32_t count);
+
+/* Shape of the last dq_bsdiff_create_many on this thread, `count` entries (10 are defined, further ones read 0): pairs
+ * that went through the shared launches; pairs diffed one by one; launches of anchor_many_kernel; bzip2 blocks whose
+ * transform went through a shared sort; bzip2 blocks sorted singly (doubled length above 8192); microseconds in each
+ * phase: sort of the old files, anchor kernel + copies, host emission, block sorts, host framing. */
+int32_t dq_last_diff_many_info(int64_t *info, int32_t count);
 
 /* Shape of the last dq_sufsort_hip_batch_i32 on this thread, `count` entries (7 are defined, further ones read 0):
  * inputs that went through the three-stage pipelines; microseconds the copy-in, the sort and the copy-out stages were
