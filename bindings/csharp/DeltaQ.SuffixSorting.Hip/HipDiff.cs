@@ -189,7 +189,8 @@ public static class HipDiff
 
     /// <summary>
     /// Shape of the last CreateMany on this thread (dq_last_diff_many_info): pairs through the shared launches, pairs
-    /// diffed one by one, launches of the anchor kernel, bzip2 blocks transformed by a shared sort, blocks sorted singly,
+    /// diffed one by one, launches of the anchor kernel, bzip2 blocks of doubled length up to 8192 (shared sort), blocks
+    /// above it (in medium launches or sorted singly: HipSuffixSort.LastManyInfo tells which),
     /// then microseconds per phase (sort of the old files, anchor kernel + copies, host emission, block sorts, framing).
     /// </summary>
     public static unsafe long[] LastDiffManyInfo()

@@ -34,6 +34,9 @@ public sealed class HipSuffixSort : ISuffixSort
     internal static extern int dq_sufsort_hip_many_dev_i32(IntPtr dTexts, IntPtr dOffsets, int count, IntPtr dSas, int device, IntPtr stream);
 
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    private static extern unsafe int dq_last_many_info(long* info, int count);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
     private static extern unsafe int dq_sufcheck_hip_i32(byte* text, long n, int* sa, long saLen, int* result, int device);
 
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
@@ -148,9 +151,29 @@ public sealed class HipSuffixSort : ISuffixSort
     }
 
     /// <summary>
+    /// Shape of the shared sorts of the last SortMany / CreateMany on this thread (dq_last_many_info): texts in the
+    /// short classes' launches, texts in medium launches, medium-length texts sorted singly, texts above 65 536 bytes
+    /// sorted singly, launches of the medium kernel, bytes of scratch carved for them.
+    /// </summary>
+    public static unsafe long[] LastManyInfo()
+    {
+        var info = new long[6];
+        fixed (long* p = info)
+        {
+            int rc = dq_last_many_info(p, info.Length);
+            if (rc != 0)
+            {
+                throw new InvalidOperationException($"dq_last_many_info failed ({rc})");
+            }
+        }
+
+        return info;
+    }
+
+    /// <summary>
     /// The suffix arrays of many independent texts in one native call (dq_sufsort_hip_many_i32): texts of up to
-    /// 8192 bytes share kernel launches instead of costing a launch and a round trip each, longer ones are sorted one
-    /// after another.  Entry j of the result is what <see cref="Sort(ReadOnlySpan{byte})"/> returns for texts[j].
+    /// 8192 bytes share kernel launches instead of costing a launch and a round trip each, and so do texts of up to
+    /// 65 536 bytes where the call holds enough of them; the others are sorted one after another.  Entry j of the result is what <see cref="Sort(ReadOnlySpan{byte})"/> returns for texts[j].
     /// The texts are laid back to back in one managed buffer for the call (their total plus four times as much for the
     /// suffix arrays), so the total is limited to what one array holds; callers with more split their list.
     /// </summary>

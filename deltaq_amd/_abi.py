@@ -27,7 +27,9 @@ DQ_SUFCHECK_WRONG_POSITION = -4
 
 K_RADIX_RANK = 2          # DQ_K_RADIX_RANK: the dominant kernel's profile category
 K_SMALL_SORT = 14         # DQ_K_SMALL_SORT: one short text, one launch
-K_SMALL_MANY = 23         # DQ_K_SMALL_MANY: many short texts in shared launches
+K_SMALL_MANY = 23         # DQ_K_SMALL_MANY: many short / medium texts in shared launches
+# kernels that are accounted under another kernel's category (the category count is part of the ABI)
+CATEGORY_ALIASES = {"mid_many_kernel": "small_many_kernel"}
 
 # every symbol include/dq_sufsort.h declares
 EXPORTS = (
@@ -35,7 +37,7 @@ EXPORTS = (
     "dq_sufsort_hip_i32", "dq_sufsort_hip_i64",
     "dq_sufsort_hip_dev_i32", "dq_sufsort_hip_dev_i64",
     "dq_sufsort_hip_batch_i32",
-    "dq_sufsort_hip_many_i32", "dq_sufsort_hip_many_dev_i32",
+    "dq_sufsort_hip_many_i32", "dq_sufsort_hip_many_dev_i32", "dq_last_many_info",
     "dq_sufcheck_hip_i32", "dq_sufcheck_hip_i64", "dq_sufcheck_hip_dev_i32", "dq_sufcheck_hip_dev_i64",
     "dq_bsdiff_search_dev_i32", "dq_bsdiff_search_dev_i64", "dq_bsdiff_search_i32", "dq_bsdiff_search_i64",
     "dq_bsdiff_create", "dq_bsdiff_patch_bound", "dq_bsdiff_scan_i32", "dq_bspatch_apply",
@@ -127,6 +129,8 @@ def load() -> ctypes.CDLL:
     L.dq_bsdiff_create.argtypes = [vp, i64, vp, i64, vp, i64, ctypes.POINTER(i64), i32]
     L.dq_bsdiff_create_many.restype = i32
     L.dq_bsdiff_create_many.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, i32]
+    L.dq_last_many_info.restype = i32
+    L.dq_last_many_info.argtypes = [ctypes.POINTER(i64), i32]
     L.dq_last_diff_many_info.restype = i32
     L.dq_last_diff_many_info.argtypes = [ctypes.POINTER(i64), i32]
     L.dq_bsdiff_patch_bound.restype = i64
@@ -205,6 +209,7 @@ def profile_snapshot() -> dict:
 def category_of(kernel_name: str) -> int:
     """Profile category (DQ_K_*) of a kernel name."""
     L = load()
+    kernel_name = CATEGORY_ALIASES.get(kernel_name, kernel_name)
     for cat in range(L.dq_profile_category_count()):
         if L.dq_profile_kernel_name(cat).decode() == kernel_name:
             return cat
@@ -225,9 +230,20 @@ def last_diff_many_info() -> dict:
     L = load()
     v = (ctypes.c_int64 * 10)()
     L.dq_last_diff_many_info(v, 10)
+    # (shared_block_sorts / single_block_sorts count by length: doubled length up to / above 8192; medium_block_sorts
+    # says how many of the latter shared a medium launch.  The old files' sort has no medium texts: they are <= 8192)
     return {"shared_pairs": v[0], "single_pairs": v[1], "anchor_launches": v[2], "shared_block_sorts": v[3],
             "single_block_sorts": v[4], "sort_old_ms": v[5] / 1e3, "anchor_ms": v[6] / 1e3, "emit_ms": v[7] / 1e3,
-            "block_sort_ms": v[8] / 1e3, "frame_ms": v[9] / 1e3}
+            "block_sort_ms": v[8] / 1e3, "frame_ms": v[9] / 1e3, "medium_block_sorts": last_many_info()["medium_texts"]}
+
+
+def last_many_info() -> dict:
+    """Shape of the shared sorts of the last many-texts / batch / many-pairs call on this thread (dq_last_many_info)."""
+    L = load()
+    v = (ctypes.c_int64 * 6)()
+    check(L.dq_last_many_info(v, 6))
+    return {"short_texts": v[0], "medium_texts": v[1], "medium_single": v[2], "long_single": v[3],
+            "medium_launches": v[4], "scratch_bytes": v[5]}
 
 
 def last_batch_info() -> dict:

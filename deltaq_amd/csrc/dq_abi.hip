@@ -296,6 +296,7 @@ int32_t dq_sufsort_hip_batch_i32(int32_t count, const uint8_t *const *texts, con
                                  int32_t *const *sas, int32_t ndev, const int32_t *devs)
 {
     EnvScope scope;
+    for (int64_t &x : t_many_info) x = 0;
     if (count < 0 || ndev <= 0 || (count > 0 && (!texts || !lens || !sas)))
         return fail(DQ_ERR_BAD_ARGS, "bad batch arguments");
     if (count == 0) return DQ_OK;
@@ -336,6 +337,9 @@ int32_t dq_sufsort_hip_batch_i32(int32_t count, const uint8_t *const *texts, con
         t_batch_info[4] = std::max(t_batch_info[4], s.wall_us);
         t_batch_info[5] += s.bound;
         t_batch_info[6] += s.shared;
+        // (the shares' threads made the shared sorts; only inputs of up to 8192 bytes go there, so the texts of the
+        // short classes are the whole record of a batch call: entries [1] .. [5] stay 0, as the header says)
+        t_many_info[0] += s.shared;
     }
     for (int d = 0; d < ndev; ++d)
         if (rcs[d] != DQ_OK) { t_err = errs[d]; return rcs[d]; }
@@ -350,6 +354,7 @@ int32_t dq_sufsort_hip_batch_i32(int32_t count, const uint8_t *const *texts, con
 int32_t dq_sufsort_hip_many_i32(const uint8_t *texts, const int64_t *offsets, int32_t count, int32_t *sas, int32_t device)
 {
     EnvScope scope;
+    for (int64_t &x : t_many_info) x = 0;
     try {
         return sufsort_many_host(texts, offsets, count, sas, device);
     } catch (const std::bad_alloc &) {             // nothing may propagate through the C ABI
@@ -361,6 +366,7 @@ int32_t dq_sufsort_hip_many_dev_i32(const void *d_texts, const void *d_offsets, 
                                     void *stream)
 {
     EnvScope scope;
+    for (int64_t &x : t_many_info) x = 0;
     try {
         return sufsort_many_dev(d_texts, d_offsets, count, d_sas, device, stream);
     } catch (const std::bad_alloc &) {
@@ -512,6 +518,7 @@ int32_t dq_bsdiff_create_many(const uint8_t *olds, const int64_t *old_offsets, c
                               int32_t count, uint8_t *patches, const int64_t *patch_offsets, int64_t *patch_lens, int32_t device)
 {
     EnvScope scope;
+    for (int64_t &x : t_many_info) x = 0;
     try {
         return bsdiff_create_many_host(olds, old_offsets, news, new_offsets, count, patches, patch_offsets, patch_lens, device);
     } catch (const std::bad_alloc &) {
@@ -665,6 +672,13 @@ int32_t dq_last_diff_many_info(int64_t *info, int32_t count)
 {
     if (!info || count < 0) return fail(DQ_ERR_BAD_ARGS, "bad arguments");
     for (int32_t k = 0; k < count; ++k) info[k] = k < 10 ? t_diff_many_info[k] : 0;
+    return DQ_OK;
+}
+
+int32_t dq_last_many_info(int64_t *info, int32_t count)
+{
+    if (!info || count < 0) return fail(DQ_ERR_BAD_ARGS, "bad arguments");
+    for (int32_t k = 0; k < count; ++k) info[k] = k < 6 ? t_many_info[k] : 0;
     return DQ_OK;
 }
 

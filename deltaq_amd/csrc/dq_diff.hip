@@ -1397,8 +1397,9 @@ int frame_patch(const bsdiff::RawStreams &raw, int64_t m, int dev, std::vector<u
 //   2. anchor_many_kernel (dq_anchor_many.h): the (cursor, hit_pos) list of every pair; lists to the host
 //   3. host threads: TripleEmitter + scan_from_anchors per pair -> RawStreams; run-length pre-pass and CRC of the three
 //      streams (bz2::StreamEncoder with its blocks held back)
-//   4. all blocks of all streams of the chunk, doubled and laid back to back: ONE sufsort_many_host call (a block whose
-//      doubled length exceeds the short-text limit takes that call's own one-by-one route)
+//   4. all blocks of all streams of the chunk, doubled and laid back to back: ONE sufsort_many_host call (blocks whose
+//      doubled length exceeds the short-text limit share its medium launches up to kMidMaxN, where there are enough of
+//      them; the others take that call's own one-by-one route)
 //   5. host threads: each block finished from its suffix array, header + three streams into the pair's slot.
 // Device memory per chunk: old + new + 4 bytes of suffix array per byte of old + one int32 per byte of new for the
 // anchor lists + 40 bytes per pair (< 6 bytes per byte of text).  Host memory per chunk: the raw streams (< 4 bytes
@@ -1601,8 +1602,8 @@ int diff_many_chunk(const uint8_t *olds, const int64_t *ooff, const uint8_t *new
 
     // ---- 4. every block of the chunk in one shared sort
     t0 = std::chrono::steady_clock::now();
-    // (the short blocks first, then the long ones: sufsort_many_host shares launches among neighbours in its list, and a
-    // long block between two short ones would end a chunk of them)
+    // (the short blocks first, then the medium ones, then those above kMidMaxN: sufsort_many_host shares launches among
+    // neighbours in its list, and a block above kMidMaxN between two others would end a chunk of them)
     std::vector<int64_t> blen;                             // doubled length per block, pairs' order
     for (ManyPair &w : out) {
         w.first_block = (int64_t)blen.size();
@@ -1614,9 +1615,9 @@ int diff_many_chunk(const uint8_t *olds, const int64_t *ooff, const uint8_t *new
     std::vector<int64_t> bplace((size_t)nblocks), boff((size_t)nblocks + 1, 0);      // block -> place in the list; the list's offsets
     {
         int64_t at = 0;
-        for (int pass = 0; pass < 2; ++pass)
+        for (int pass = 0; pass < 3; ++pass)
             for (int64_t b = 0; b < nblocks; ++b)
-                if ((blen[(size_t)b] > kSmallMaxN) == (pass == 1)) {
+                if ((blen[(size_t)b] > kSmallMaxN) + (blen[(size_t)b] > kMidMaxN) == pass) {
                     bplace[(size_t)b] = at;
                     boff[(size_t)at + 1] = boff[(size_t)at] + blen[(size_t)b];
                     ++at;

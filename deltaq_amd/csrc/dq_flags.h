@@ -29,7 +29,8 @@ struct Flags {
     // ---- entry, runtime (gated)
     std::optional<std::string> fault;       // DQ_FAULT: alloc:K | hip:K | spin (FaultPlan below)
     std::optional<int> small_n;             // DQ_SMALL_N: largest n of the single-workgroup sorter, >= 0 (<= kSmallMaxN)
-    std::optional<int> no_many;             // DQ_NO_MANY: 1: every short text of a batch its own launch; 2 | 4 | 6: no 2048- / 4096-byte class / neither
+    std::optional<int> no_many;             // DQ_NO_MANY: 1: every text of a batch its own launch; bits 2 | 4: no 2048- / 4096-byte class; bit 8: no medium class
+    std::optional<int> mid_many_min;        // DQ_MID_MANY_MIN: fewest medium texts of a call / chunk that share a launch, >= 1
     std::optional<int> no_diff_many;        // DQ_NO_DIFF_MANY: 1: every pair of dq_bsdiff_create_many through the one-pair path
     bool no_list_buffers = false;           // DQ_NO_LIST_BUFFERS: the workspace without the third list buffer
     bool text_copy = false;                 // DQ_TEXT_COPY: copy the text in front instead of in the first pass
@@ -122,7 +123,8 @@ inline Flags read_flags()
 
     if (const char *v = getenv("DQ_FAULT")) f.fault = v;
     f.small_n = num("DQ_SMALL_N", 0);
-    f.no_many = num("DQ_NO_MANY", 0, 7);
+    f.no_many = num("DQ_NO_MANY", 0, 15);
+    f.mid_many_min = num("DQ_MID_MANY_MIN", 1);
     f.no_diff_many = num("DQ_NO_DIFF_MANY", 0, 1);
     f.no_list_buffers = on("DQ_NO_LIST_BUFFERS");
     f.text_copy = on("DQ_TEXT_COPY");

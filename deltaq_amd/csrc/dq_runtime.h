@@ -33,6 +33,7 @@
 namespace dq {
 
 constexpr int kSmallMaxN = 8192;          // largest text the single-workgroup sorter takes (dq_small.h)
+constexpr int kMidMaxN = 65536;           // largest text of the medium class of the many-texts launches (dq_mid_many.h)
 
 // ------------------------------------------------------------------ errors
 inline thread_local std::string t_err;
@@ -41,6 +42,10 @@ inline thread_local int64_t t_info[3] = {0, 0, 0};
 // asked again exactly, launches of the device's anchor scan that were given back to the host loop, workgroups of its grid
 inline thread_local int64_t t_diff_info[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
 inline thread_local int64_t t_diff_many_info[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};     // dq_last_diff_many_info
+// the shared sorts of the last outermost many-texts / batch / many-pairs call on this thread (dq_last_many_info): texts in
+// the short classes' launches, texts in medium launches, medium-length texts sorted singly, texts above kMidMaxN sorted
+// singly, launches of mid_many_kernel, bytes of per-workgroup scratch carved for them
+inline thread_local int64_t t_many_info[6] = {0, 0, 0, 0, 0, 0};
 
 // the last dq_sufsort_hip_batch_i32 on this thread (dq_last_batch_info): inputs through the pipelines, microseconds the
 // copy-in / sort / copy-out stages were busy (summed over the device shares), wall microseconds of the slowest share,
@@ -100,7 +105,7 @@ struct DeviceCtx {
     std::mutex mu;
     int dev = -1;
     int ncu = 0;                        // compute units of the device (grid of the persistent kernels)
-    int many_groups[3] = {0, 0, 0};     // workgroups of small_many_kernel the device holds at once, per length class (0: not asked yet)
+    int many_groups[5] = {0, 0, 0, 0, 0};   // workgroups of small_many_kernel (3 length classes) and mid_many_kernel (2) the device holds at once (0: not asked yet)
     int anchor_many_groups = 0;         // ... and of anchor_many_kernel (dq_anchor_many.h)
     hipStream_t stream = nullptr;
     char *ws = nullptr;
@@ -399,7 +404,8 @@ extern template int64_t sufsort_workspace_plan<int32_t>(int64_t, bool, int64_t);
 extern template int64_t sufsort_workspace_plan<int64_t>(int64_t, bool, int64_t);
 
 // many short texts in shared launches (dq_small_many.h, in dq_sorter_i32.hip): the bodies of dq_sufsort_hip_many_i32 /
-// _many_dev_i32.  shared_out (optional): texts that were sorted in shared launches.
+// _many_dev_i32.  shared_out (optional): texts of the short classes (by length: up to the short-text limit).  Both add
+// what they did to t_many_info; the entry point that is outermost resets it.
 int sufsort_many_host(const uint8_t *texts, const int64_t *offsets, int32_t count, int32_t *sas, int32_t device,
                       int64_t *shared_out = nullptr);
 int sufsort_many_dev(const void *d_texts, const void *d_offsets, int32_t count, void *d_sas, int32_t device, void *stream);

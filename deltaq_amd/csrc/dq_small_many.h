@@ -11,9 +11,11 @@
 //   * texts are sorted in length classes (LDS block and thread count are template parameters of the body): a text of
 //     2048 bytes needs 30 KiB of LDS and 256 threads, five such workgroups share a CU where the 8192-byte class
 //     (120 KiB, 1024 threads) fits once.  One launch per class, on the same stream.
-// Texts longer than the short-text limit are not this file's: the host drivers below hand them to the device sorter
-// one after another.  32-bit indices only (dq_sorter_i32.hip includes this file).
+// Texts between the short-text limit and kMidMaxN = 65 536 bytes share launches of mid_many_kernel (dq_mid_many.h), where
+// a call or chunk holds at least kMidManyMin of them; the others, and every text above kMidMaxN, are handed to the
+// device sorter one after another by the host drivers below.  32-bit indices only (dq_sorter_i32.hip includes this file).
 #pragma once
+#include "dq_mid_many.h"
 #include "dq_small.h"
 
 namespace dq {
@@ -46,44 +48,91 @@ __global__ __launch_bounds__(kThreads) void small_many_kernel(const uint8_t *__r
 
 namespace {
 
-// the length classes, shortest first: {largest text, threads}.  The last one is small_sufsort_kernel's own.
+// the length classes, shortest first: {largest text, threads}.  The last short one is small_sufsort_kernel's own; the
+// medium classes (mid_many_kernel) follow the short ones.
 struct ManyClass { int max_n, threads; };
 constexpr int kManyClasses = 3;
-constexpr ManyClass kManyClass[kManyClasses] = {{2048, 256}, {4096, 512}, {kSmallMaxN, kSmallThreads}};
+constexpr int kMidClasses = 2;
+constexpr int kAllClasses = kManyClasses + kMidClasses;
+constexpr ManyClass kManyClass[kAllClasses] = {{2048, 256}, {4096, 512}, {kSmallMaxN, kSmallThreads}, {32768, 512}, {kMidMaxN, 1024}};
 
+// Fewest medium texts of a call (device form) or chunk (host form) that are worth a shared launch: one workgroup is
+// slower on one medium text than the whole device is (1.8 / 2.8 / 7.4 ms against 0.5 - 0.6 ms at 16 / 32 / 64 KiB).
+// Measured (profiles/r09/many_medium.json): the forced launch beats the one-by-one route from 8 /
+// 16 / 32 texts of 16 / 32 / 64 KiB on; twice the largest crossing, rounded up to a power of two.
+constexpr int kMidManyMin = 64;
+
+template <int kC> struct ManyKernel {
+    static constexpr int kMaxN = kManyClass[kC].max_n, kThreads = kManyClass[kC].threads;
+    static constexpr bool kMid = kC >= kManyClasses;
+    static constexpr size_t kScratch = kMid ? MidLdsT<kMaxN, kThreads>::kScratchBytes : 0;
+    static const void *fn()
+    {
+        if constexpr (kMid) return (const void *)mid_many_kernel<kMaxN, kThreads>;
+        else return (const void *)small_many_kernel<kMaxN, kThreads>;
+    }
+};
+
+// workgroups of class kC the device holds at once (a wrong answer costs time only: nobody waits for anybody)
 template <int kC>
-int launch_many_class(Launcher &L, DeviceCtx &c, hipStream_t st, const uint8_t *d_texts, const int64_t *d_offsets,
-                      const int32_t *d_order, int count, int64_t text_bytes, uint32_t *d_next, int32_t *d_sas)
+int many_class_groups(DeviceCtx &c)
 {
-    constexpr int kMaxN = kManyClass[kC].max_n, kThreads = kManyClass[kC].threads;
     if (c.many_groups[kC] <= 0) {
-        // workgroups the device holds at once (a wrong answer costs time only: nobody waits for anybody)
         int per_cu = 0, ncu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, small_many_kernel<kMaxN, kThreads>, kThreads, 0) != hipSuccess || per_cu <= 0)
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ManyKernel<kC>::fn(), ManyKernel<kC>::kThreads, 0) != hipSuccess || per_cu <= 0)
             per_cu = 1;
         if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c.dev) != hipSuccess || ncu <= 0) ncu = 256;
         c.many_groups[kC] = per_cu * ncu;
     }
-    const int grid = std::min(count, c.many_groups[kC]);
-    LAUNCH(L, DQ_K_SMALL_MANY, count, text_bytes * 5,
-           hipLaunchKernelGGL((small_many_kernel<kMaxN, kThreads>), dim3((unsigned)grid), dim3(kThreads), 0, st, d_texts,
-                              d_offsets, d_order, count, d_next, d_sas));
+    return c.many_groups[kC];
+}
+
+template <int kC>
+int launch_many_class(Launcher &L, DeviceCtx &c, hipStream_t st, const uint8_t *d_texts, const int64_t *d_offsets,
+                      const int32_t *d_order, int count, int64_t text_bytes, uint32_t *d_next, int32_t *d_sas, char *d_scratch)
+{
+    constexpr int kMaxN = ManyKernel<kC>::kMaxN, kThreads = ManyKernel<kC>::kThreads;
+    const int grid = std::min(count, many_class_groups<kC>(c));
+    if constexpr (ManyKernel<kC>::kMid) {
+        LAUNCH(L, DQ_K_SMALL_MANY, count, text_bytes * 5,
+               hipLaunchKernelGGL((mid_many_kernel<kMaxN, kThreads>), dim3((unsigned)grid), dim3(kThreads), 0, st, d_texts,
+                                  d_offsets, d_order, count, d_next, d_sas, d_scratch));
+        t_many_info[4] += 1;
+    } else {
+        LAUNCH(L, DQ_K_SMALL_MANY, count, text_bytes * 5,
+               hipLaunchKernelGGL((small_many_kernel<kMaxN, kThreads>), dim3((unsigned)grid), dim3(kThreads), 0, st, d_texts,
+                                  d_offsets, d_order, count, d_next, d_sas));
+    }
     return DQ_OK;
 }
 
 // what the host decides about a set of texts from their offsets
 struct ManyPlan {
     std::vector<int32_t> order;                 // the classes' work lists back to back, each longest text first
-    int class_count[kManyClasses] = {0, 0, 0};
-    int64_t class_bytes[kManyClasses] = {0, 0, 0};
-    std::vector<int32_t> longs;                 // texts beyond the short-text limit, in input order
-    int64_t shorts() const { return (int64_t)order.size(); }
+    int class_count[kAllClasses] = {0, 0, 0, 0, 0};
+    int64_t class_bytes[kAllClasses] = {0, 0, 0, 0, 0};
+    std::vector<int32_t> longs;                 // texts sorted singly, in input order: those above kMidMaxN, and the medium ones that share no launch
+    int64_t mid_single = 0, above_mid = 0;      // ... how many of them have medium length / are longer
+    int64_t shorts() const { return class_count[0] + class_count[1] + class_count[2]; }
+    int64_t mids() const { return class_count[3] + class_count[4]; }
+    int64_t listed() const { return (int64_t)order.size(); }
 };
 
 // texts of up to this many bytes share a launch (n <= 2 always: the device-wide sorter is not built for them)
 inline int64_t many_short_max() { return std::max<int64_t>(small_limit(), 2); }
 
-// DQ_NO_MANY: bit 1 drops the 2048-byte class, bit 2 the 4096-byte class (their texts move up a class)
+// The medium class is off under DQ_NO_MANY bit 8 and DQ_NO_MANY=1, and whenever DQ_SMALL_N is set (what that flag means
+// to the tests that set it: everything to the device-wide sorter).
+inline bool mid_many_on()
+{
+    const Flags &F = flags();
+    const int drop = F.no_many.value_or(0);
+    return !F.small_n && drop != 1 && !(drop & 8);
+}
+// texts of up to this many bytes may sit in a chunk of the host form / on a work list
+inline int64_t many_listed_max() { return mid_many_on() ? (int64_t)kMidMaxN : many_short_max(); }
+
+// DQ_NO_MANY: bit 2 drops the 2048-byte class, bit 4 the 4096-byte class (their texts move up a class)
 inline int many_class_of(int64_t n, int drop)
 {
     for (int k = 0; k < kManyClasses - 1; ++k)
@@ -96,16 +145,40 @@ inline ManyPlan plan_many(const int64_t *off, int32_t first, int32_t last)
     ManyPlan p;
     const int64_t short_max = many_short_max();
     const int drop = flags().no_many.value_or(0);
-    std::vector<int32_t> lists[kManyClasses];
+    const bool mid_on = mid_many_on();
+    std::vector<int32_t> lists[kAllClasses];
+    std::vector<int32_t> mids;
     for (int32_t j = first; j < last; ++j) {
         const int64_t n = off[j + 1] - off[j];
         if (n == 0) continue;
-        if (n > short_max) { p.longs.push_back(j); continue; }
+        if (n > short_max) {
+            if (mid_on && n <= kMidMaxN) mids.push_back(j);
+            else p.longs.push_back(j);
+            continue;
+        }
         const int k = many_class_of(n, drop);
         lists[k].push_back(j);
         p.class_bytes[k] += n;
     }
-    for (int k = 0; k < kManyClasses; ++k) {
+    // the medium texts share launches when there are enough of them
+    if ((int64_t)mids.size() >= flags().mid_many_min.value_or(kMidManyMin)) {
+        for (int32_t j : mids) {
+            const int64_t n = off[j + 1] - off[j];
+            const int k = n <= kManyClass[kManyClasses].max_n ? kManyClasses : kManyClasses + 1;
+            lists[k].push_back(j);
+            p.class_bytes[k] += n;
+        }
+    } else if (!mids.empty()) {
+        const size_t at = p.longs.size();
+        p.longs.insert(p.longs.end(), mids.begin(), mids.end());
+        std::inplace_merge(p.longs.begin(), p.longs.begin() + (ptrdiff_t)at, p.longs.end());
+    }
+    for (int32_t j : p.longs) {
+        const int64_t n = off[j + 1] - off[j];
+        if (n > kMidMaxN) ++p.above_mid;
+        else if (n > kSmallMaxN) ++p.mid_single;
+    }
+    for (int k = 0; k < kAllClasses; ++k) {
         std::stable_sort(lists[k].begin(), lists[k].end(),
                          [&](int32_t a, int32_t b) { return off[a + 1] - off[a] > off[b + 1] - off[b]; });
         p.class_count[k] = (int)lists[k].size();
@@ -118,11 +191,24 @@ inline ManyPlan plan_many(const int64_t *off, int32_t first, int32_t last)
 constexpr size_t kManyCounterBytes = 256;
 inline size_t many_ctl_bytes(int64_t texts) { return kManyCounterBytes + align_up((size_t)texts * sizeof(int32_t)); }
 
+// ... and of the medium launches' per-workgroup scratch blocks.  The launches of a plan follow each other on one stream,
+// so they share the area: the larger of the two grids' needs (0 without medium texts).
+inline size_t many_scratch_bytes(DeviceCtx &c, const ManyPlan &plan)
+{
+    size_t need = 0;
+    if (plan.class_count[3] > 0)
+        need = std::max(need, (size_t)std::min(plan.class_count[3], many_class_groups<3>(c)) * ManyKernel<3>::kScratch);
+    if (plan.class_count[4] > 0)
+        need = std::max(need, (size_t)std::min(plan.class_count[4], many_class_groups<4>(c)) * ManyKernel<4>::kScratch);
+    return align_up(need);
+}
+
 // The shared launches of a plan made from the host's copy of d_offsets (plan.order indexes d_offsets; d_offsets gives
-// byte positions in d_texts and entry positions in d_sas).  d_ctl: many_ctl_bytes(plan.shorts()) bytes.  Enqueues only:
-// the caller drains the stream, and keeps the plan until then.
+// byte positions in d_texts and entry positions in d_sas).  d_ctl: many_ctl_bytes(plan.listed()) bytes, 256-byte
+// aligned; d_scratch: many_scratch_bytes(c, plan) bytes.  Enqueues only: the caller drains the stream, and keeps the
+// plan until then.
 inline int launch_many(DeviceCtx &c, hipStream_t st, const ManyPlan &plan, const uint8_t *d_texts, const int64_t *d_offsets,
-                       int32_t *d_sas, char *d_ctl)
+                       int32_t *d_sas, char *d_ctl, char *d_scratch)
 {
     if (plan.order.empty()) return DQ_OK;
     Launcher L{c, st, g_prof_on.load()};
@@ -131,17 +217,31 @@ inline int launch_many(DeviceCtx &c, hipStream_t st, const ManyPlan &plan, const
     HIP_TRY(hipMemsetAsync(d_next, 0, kManyCounterBytes, st));
     HIP_TRY(hipMemcpyAsync(d_order, plan.order.data(), plan.order.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
     int at = 0, rc = DQ_OK;
-    for (int k = 0; k < kManyClasses && rc == DQ_OK; ++k) {
+    for (int k = 0; k < kAllClasses && rc == DQ_OK; ++k) {
         const int cnt = plan.class_count[k];
         if (cnt == 0) continue;
         switch (k) {
-        case 0: rc = launch_many_class<0>(L, c, st, d_texts, d_offsets, d_order + at, cnt, plan.class_bytes[k], d_next + k, d_sas); break;
-        case 1: rc = launch_many_class<1>(L, c, st, d_texts, d_offsets, d_order + at, cnt, plan.class_bytes[k], d_next + k, d_sas); break;
-        default: rc = launch_many_class<2>(L, c, st, d_texts, d_offsets, d_order + at, cnt, plan.class_bytes[k], d_next + k, d_sas); break;
+        case 0: rc = launch_many_class<0>(L, c, st, d_texts, d_offsets, d_order + at, cnt, plan.class_bytes[k], d_next + k, d_sas, d_scratch); break;
+        case 1: rc = launch_many_class<1>(L, c, st, d_texts, d_offsets, d_order + at, cnt, plan.class_bytes[k], d_next + k, d_sas, d_scratch); break;
+        case 2: rc = launch_many_class<2>(L, c, st, d_texts, d_offsets, d_order + at, cnt, plan.class_bytes[k], d_next + k, d_sas, d_scratch); break;
+        case 3: rc = launch_many_class<3>(L, c, st, d_texts, d_offsets, d_order + at, cnt, plan.class_bytes[k], d_next + k, d_sas, d_scratch); break;
+        default: rc = launch_many_class<4>(L, c, st, d_texts, d_offsets, d_order + at, cnt, plan.class_bytes[k], d_next + k, d_sas, d_scratch); break;
         }
         at += cnt;
     }
     return rc;
+}
+
+// what a plan's shared launches and single sorts add to dq_last_many_info (one_by_one: no shared launch was made)
+inline void many_account(const ManyPlan &plan, bool one_by_one, size_t scratch)
+{
+    if (!one_by_one) {
+        t_many_info[0] += plan.shorts();
+        t_many_info[1] += plan.mids();
+        t_many_info[5] += (int64_t)scratch;
+    }
+    t_many_info[2] += plan.mid_single;
+    t_many_info[3] += plan.above_mid;
 }
 
 // one text of the device form outside the shared launches (a long text, or every text under DQ_NO_MANY=1)
@@ -202,15 +302,18 @@ int sufsort_many_dev(const void *d_texts_v, const void *d_offsets_v, int32_t cou
         if (rc != DQ_OK) return rc;
         t_info[0] = t_info[1] = t_info[2] = 0;
         plan = plan_many(off.data(), 0, count);
-        if (!many_one_by_one() && plan.shorts() > 0) {
-            rc = ensure_ws(c, many_ctl_bytes(plan.shorts()));
+        if (!many_one_by_one() && plan.listed() > 0) {
+            const size_t b_ctl = many_ctl_bytes(plan.listed()), b_scratch = many_scratch_bytes(c, plan);
+            rc = ensure_ws(c, b_ctl + b_scratch);
             if (rc != DQ_OK) return rc;
-            rc = launch_many(c, st, plan, d_texts, d_offsets, d_sas, c.ws);
+            rc = launch_many(c, st, plan, d_texts, d_offsets, d_sas, c.ws, c.ws + b_ctl);
             if (rc != DQ_OK) { drop_pending(c, st); return rc; }
             HIP_TRY(hipStreamSynchronize(st));              // (plan.order is read by the copy until here)
             rc = flush_profile(c);
             if (rc != DQ_OK) return rc;
-        }
+            many_account(plan, false, b_scratch);
+        } else
+            many_account(plan, true, 0);
     }   // (the slot is given back: the sorts below lease their own)
     if (many_one_by_one())
         for (int32_t j : plan.order) {
@@ -224,8 +327,9 @@ int sufsort_many_dev(const void *d_texts_v, const void *d_offsets_v, int32_t cou
     return DQ_OK;
 }
 
-// Host buffers in / out.  Runs of short texts travel in chunks of whole texts: at most kManyChunkBytes of text, its
-// suffix arrays (4 bytes per text byte), offsets and work list on the device at a time, whatever the total.
+// Host buffers in / out.  Runs of short and medium texts travel in chunks of whole texts: at most kManyChunkBytes of
+// text, its suffix arrays (4 bytes per text byte), offsets and work list on the device at a time, whatever the total,
+// and the medium launches' scratch blocks beside them.
 constexpr int64_t kManyChunkBytes = 64ll << 20;
 constexpr int32_t kManyChunkTexts = 1 << 20;
 
@@ -241,20 +345,22 @@ int sufsort_many_host(const uint8_t *texts, const int64_t *offsets, int32_t coun
     int dev = 0;
     rc = resolve_device(device, &dev);
     if (rc != DQ_OK) return rc;
-    const int64_t short_max = many_short_max();
+    const int64_t listed_max = many_listed_max();
     const bool one_by_one = many_one_by_one();
     std::vector<int64_t> rel;
     for (int32_t i = 0; i < count;) {
         const int64_t n = offsets[i + 1] - offsets[i];
-        if (n > short_max || one_by_one) {
+        if (n > listed_max || one_by_one) {
             rc = sufsort_host<int32_t>(texts + offsets[i], n, sas + offsets[i], dev);
             if (rc != DQ_OK) return rc;
+            if (n > kMidMaxN) t_many_info[3] += 1;
+            else if (n > kSmallMaxN) t_many_info[2] += 1;
             ++i;
             continue;
         }
-        // the chunk: texts [i, e), all short, back to back in the caller's buffer
+        // the chunk: texts [i, e), none above the limit, back to back in the caller's buffer
         int32_t e = i;
-        while (e < count && e - i < kManyChunkTexts && offsets[e + 1] - offsets[e] <= short_max &&
+        while (e < count && e - i < kManyChunkTexts && offsets[e + 1] - offsets[e] <= listed_max &&
                offsets[e + 1] - offsets[i] <= kManyChunkBytes)
             ++e;
         const int64_t base = offsets[i], bytes = offsets[e] - base;
@@ -263,33 +369,49 @@ int sufsort_many_host(const uint8_t *texts, const int64_t *offsets, int32_t coun
             rel.resize((size_t)cnt + 1);
             for (int32_t j = 0; j <= cnt; ++j) rel[(size_t)j] = offsets[i + j] - base;
             const ManyPlan plan = plan_many(rel.data(), 0, cnt);
-            SlotLease lease(dev, 0);
-            DeviceCtx &c = *lease.c;
-            rc = init_ctx(c, dev);
-            if (rc != DQ_OK) return rc;
-            hipStream_t st = c.stream;
-            const size_t b_text = align_up((size_t)bytes + 64), b_sa = align_up((size_t)bytes * sizeof(int32_t)),
-                         b_off = align_up(rel.size() * sizeof(int64_t));
-            rc = ensure_ws(c, b_text + b_sa + b_off + many_ctl_bytes(plan.shorts()));
-            if (rc != DQ_OK) return rc;
-            uint8_t *d_text = reinterpret_cast<uint8_t *>(c.ws);
-            int32_t *d_sa = reinterpret_cast<int32_t *>(c.ws + b_text);
-            int64_t *d_off = reinterpret_cast<int64_t *>(c.ws + b_text + b_sa);
-            t_info[0] = t_info[1] = t_info[2] = 0;
-            auto run = [&]() -> int {
-                HIP_TRY(hipMemcpyAsync(d_text, texts + base, (size_t)bytes, hipMemcpyHostToDevice, st));
-                HIP_TRY(hipMemcpyAsync(d_off, rel.data(), rel.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
-                const int r = launch_many(c, st, plan, d_text, d_off, d_sa, c.ws + b_text + b_sa + b_off);
-                if (r != DQ_OK) return r;
-                // (one checked step: a failure must not leave a copy into the caller's array in flight behind the return)
-                const hipError_t e1 = hipMemcpyAsync(sas + base, d_sa, (size_t)bytes * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-                const hipError_t e2 = hipStreamSynchronize(st);
-                HIP_TRY(e1 != hipSuccess ? e1 : e2);
-                return flush_profile(c);
-            };
-            rc = run();
-            if (rc != DQ_OK) { drop_pending(c, st); return rc; }
+            if (plan.listed() > 0) {
+                SlotLease lease(dev, 0);
+                DeviceCtx &c = *lease.c;
+                rc = init_ctx(c, dev);
+                if (rc != DQ_OK) return rc;
+                hipStream_t st = c.stream;
+                const size_t b_text = align_up((size_t)bytes + 64), b_sa = align_up((size_t)bytes * sizeof(int32_t)),
+                             b_off = align_up(rel.size() * sizeof(int64_t)), b_ctl = many_ctl_bytes(plan.listed()),
+                             b_scratch = many_scratch_bytes(c, plan);
+                rc = ensure_ws(c, b_text + b_sa + b_off + b_ctl + b_scratch);
+                if (rc != DQ_OK) return rc;
+                uint8_t *d_text = reinterpret_cast<uint8_t *>(c.ws);
+                int32_t *d_sa = reinterpret_cast<int32_t *>(c.ws + b_text);
+                int64_t *d_off = reinterpret_cast<int64_t *>(c.ws + b_text + b_sa);
+                t_info[0] = t_info[1] = t_info[2] = 0;
+                auto run = [&]() -> int {
+                    HIP_TRY(hipMemcpyAsync(d_text, texts + base, (size_t)bytes, hipMemcpyHostToDevice, st));
+                    HIP_TRY(hipMemcpyAsync(d_off, rel.data(), rel.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+                    const int r = launch_many(c, st, plan, d_text, d_off, d_sa, c.ws + b_text + b_sa + b_off,
+                                              c.ws + b_text + b_sa + b_off + b_ctl);
+                    if (r != DQ_OK) return r;
+                    // (one checked step: a failure must not leave a copy into the caller's array in flight behind the return)
+                    const hipError_t e1 = hipMemcpyAsync(sas + base, d_sa, (size_t)bytes * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+                    const hipError_t e2 = hipStreamSynchronize(st);
+                    HIP_TRY(e1 != hipSuccess ? e1 : e2);
+                    return flush_profile(c);
+                };
+                rc = run();
+                if (rc != DQ_OK) { drop_pending(c, st); return rc; }
+                many_account(plan, false, b_scratch);
+            } else
+                many_account(plan, true, 0);
             if (shared_out) *shared_out += plan.shorts();
+            // the chunk's medium texts that were too few for a launch: singly, into their place (the slot is given back).
+            // They travelled with the chunk -- its extent is decided before its plan -- so their bytes were copied in for
+            // nothing and the copy back laid never-written workspace words over their segments; the sorts below
+            // overwrite them.  (A failing call leaves the caller's array undefined, here as in every chunk after the
+            // failing one.)
+            for (int32_t j : plan.longs) {
+                rc = sufsort_host<int32_t>(texts + base + rel[(size_t)j], rel[(size_t)j + 1] - rel[(size_t)j],
+                                           sas + base + rel[(size_t)j], dev);
+                if (rc != DQ_OK) return rc;
+            }
         }
         i = e;
     }

@@ -77,18 +77,23 @@ int32_t dq_sufsort_hip_batch_i32(int32_t count, const uint8_t *const *texts, con
 /* ---- many independent SHORT texts in one launch (a directory tree of small files) ----------------------------
  * A text of up to 8192 bytes is sorted by one workgroup; sorted one by one (the entry points above) such texts cost a
  * launch and a host round trip each and keep one compute unit busy.  Here they share launches: the workgroups of one
- * grid take text after text, longest first, until none is left.
+ * grid take text after text, longest first, until none is left.  Texts of 8193 .. 65 536 bytes ("medium") do the same
+ * in launches of their own (mid_many_kernel: one workgroup per text, its ranks in LDS, its sort buffers in a scratch
+ * block in device memory), where a call -- in the host form: a chunk -- holds enough of them to beat the device sorter.
  * Layout: the texts lie back to back in one buffer; offsets[count + 1] (int64, offsets[0] == 0, never decreasing) says
  * where each begins, text j being bytes offsets[j] .. offsets[j + 1] - 1.  The suffix arrays come back to back in
  * the same layout: sas[offsets[j] + i] is the i-th suffix of text j COUNTED FROM THE START OF TEXT j -- each segment
  * is exactly what dq_sufsort_hip_i32 returns for that text alone (n = 0, 1, 2 included).  Nothing outside the
  * segments is written.  The total may exceed 2^31 bytes; each text is limited to 2^31-1 (32-bit indices only).
- * The call is total: a text longer than 8192 bytes is sorted by the device sorter, one after another, into its place.
+ * The call is total: a text longer than 65 536 bytes, and a medium one that has too few companions, is sorted by the
+ * device sorter, one after another ("singly"), into its place.
  * Errors, all before any device use in the host form: count < 0, a NULL pointer with count > 0, offsets[0] != 0,
  * decreasing offsets -> DQ_ERR_BAD_ARGS; a text of 2^31 bytes or more -> DQ_ERR_TOO_LARGE.  count == 0 is a no-op.
- *   dq_sufsort_hip_many_i32      host pointers.  Runs of short texts are copied in, sorted and copied out in chunks of
- *                                whole texts (64 MiB of text at most: 5 bytes of device memory per chunk byte, whatever
- *                                the total); no host staging: the copies read and write the caller's buffers.
+ *   dq_sufsort_hip_many_i32      host pointers.  Runs of texts of up to 65 536 bytes are copied in, sorted and copied
+ *                                out in chunks of whole texts (64 MiB of text at most: 5 bytes of device memory per
+ *                                chunk byte, whatever the total, and with medium texts up to 320 MiB of scratch blocks:
+ *                                1.25 MiB per resident workgroup); no host staging: the copies read and write the
+ *                                caller's buffers.
  *   dq_sufsort_hip_many_dev_i32  device pointers on `device` (d_offsets too: the library fetches it once to plan the
  *                                launches, and checks it before it launches anything); work on `stream` (NULL = the
  *                                library's), returns after the stream has drained. */
@@ -155,10 +160,12 @@ int64_t dq_bsdiff_patch_bound(int64_t n, int64_t m);
  * old + new, 262 144 pairs), the old files are sorted by the launches of dq_sufsort_hip_many_dev_i32, one launch of
  * anchor_many_kernel finds the anchors of every pair (one workgroup per pair, nobody waits for anybody), host threads
  * turn them into the raw streams, all bzip2 blocks of the chunk are transformed by one dq_sufsort_hip_many_i32-style
- * sort and host threads frame the patches.  The call is total: a pair with a longer file (below 2 GiB) is diffed by
+ * sort (blocks of doubled length 8193 .. 65 536 in its medium launches, where there are enough) and host threads frame
+ * the patches.  The call is total: a pair with a longer file (below 2 GiB) is diffed by
  * dq_bsdiff_create's path, one after another, into its slot.
  * Footprint per chunk -- device: old + new + 4 bytes per byte of old + 1 byte per byte of new + 40 bytes per pair, freed
- * on return; host: below 4 bytes per byte of new for the raw streams and 10 bytes per byte of stream for the shared sort.
+ * on return (the shared sort's own workspace, scratch blocks of medium launches included, stays with the library until
+ * dq_sufsort_hip_release); host: below 4 bytes per byte of new for the raw streams and 10 bytes per byte of stream for the shared sort.
  * Errors found before any device use: count < 0, a NULL pointer with count > 0, offsets[0] != 0 or decreasing offsets
  * in any of the three arrays -> DQ_ERR_BAD_ARGS; a file of 2^31 bytes or more -> DQ_ERR_TOO_LARGE.  count == 0 is a
  * no-op.  A slot too small for its patch -> DQ_ERR_BAD_ARGS ("output buffer too small"), known only once the patch
@@ -270,7 +277,7 @@ void dq_sufsort_hip_release(void);
 #define DQ_K_SPLIT_PASS          20   /* dq_split_round0.h: split_pass_kernel, round 0 as a sample sort: text -> pairs by top bucket (1+12), pairs -> bucket slots (12+12) */
 #define DQ_K_SPLIT_FINISH        21   /* bucket_finish_kernel: every bucket sorted by its 64-bit keys inside LDS, 12+12           */
 #define DQ_K_SPLIT_AUX           22   /* sample, splitter tables, top-bucket histogram (1 B/text byte), plans, scans, overflow placement */
-#define DQ_K_SMALL_MANY          23   /* small_many_kernel: many short texts, one workgroup each, in one launch per length class; elements = texts, 5 B/text byte */
+#define DQ_K_SMALL_MANY          23   /* small_many_kernel / mid_many_kernel: many short / medium texts, one workgroup each, in one launch per length class; elements = texts, 5 B/text byte */
 #define DQ_K_COUNT               24
 
 /* 0 off, 1 every kernel, 2 only radix_rank_kernel, 100 + c only category c (cheapest: the timed region) */
@@ -300,9 +307,19 @@ int32_t dq_last_diff_info(int64_t *info, int32_t count);
 
 /* Shape of the last dq_bsdiff_create_many on this thread, `count` entries (10 are defined, further ones read 0): pairs
  * that went through the shared launches; pairs diffed one by one; launches of anchor_many_kernel; bzip2 blocks whose
- * transform went through a shared sort; bzip2 blocks sorted singly (doubled length above 8192); microseconds in each
- * phase: sort of the old files, anchor kernel + copies, host emission, block sorts, host framing. */
+ * transform went through a shared sort of the short classes (doubled length up to 8192); bzip2 blocks of doubled length
+ * above 8192, whether they shared a medium launch or were sorted singly (dq_last_many_info tells which); microseconds
+ * in each phase: sort of the old files, anchor kernel + copies, host emission, block sorts, host framing. */
 int32_t dq_last_diff_many_info(int64_t *info, int32_t count);
+
+/* Shape of the shared sorts of the last outermost dq_sufsort_hip_many_i32 / _many_dev_i32 / dq_sufsort_hip_batch_i32 /
+ * dq_bsdiff_create_many on this thread, summed over every shared sort that call made and reset when such a call
+ * starts; `count` entries (6 are defined, further ones read 0; a NULL array is DQ_ERR_BAD_ARGS): texts sorted in the
+ * short classes' launches; texts sorted in medium launches; texts of 8193 .. 65 536 bytes sorted singly (fewer than the
+ * threshold in their call or chunk, or the medium class switched off); texts above 65 536 bytes sorted singly; launches
+ * of mid_many_kernel; bytes of per-workgroup scratch carved for them.  After dq_sufsort_hip_batch_i32 only the first
+ * entry is filled, the others read 0: that call shares launches among its inputs of up to 8192 bytes only. */
+int32_t dq_last_many_info(int64_t *info, int32_t count);
 
 /* Shape of the last dq_sufsort_hip_batch_i32 on this thread, `count` entries (7 are defined, further ones read 0):
  * inputs that went through the three-stage pipelines; microseconds the copy-in, the sort and the copy-out stages were

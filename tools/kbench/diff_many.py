@@ -6,7 +6,8 @@ dq_bsdiff_create over the pairs.  The two libraries are timed in processes of th
 state: they cannot share one), alternating parent / new / parent / new; each process warms its shape and times --calls
 calls; the patches of both are digested and compared.  ratio = parent ms / new ms.  Beside it, not the yardstick: this
 build under DQ_NO_DIFF_MANY=1 (every pair through the one-pair path).  The new build also reports the phase times and
-counts of dq_last_diff_many_info for its last timed call.
+counts of dq_last_diff_many_info for its last timed call.  --parent-kind many drives the parent build through
+dq_bsdiff_create_many too (a parent that has it: what a later change to the shared path is measured against).
 
 Sets (tests/diff_pairs.py, seeded): fixed4k = 4096 pairs of 4 KiB; loguniform = 16 384 pairs of 64 B .. 8 KiB.
 Times are host clock around blocking calls (each ends in a device synchronise); profiler off.
@@ -136,6 +137,9 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r08", "diff_many.json"))
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=2, help="parent / new alternations per set")
+    ap.add_argument("--parent-kind", choices=["loop", "many"], default="loop",
+                    help="how the parent build is driven: a loop of dq_bsdiff_create (a build without "
+                         "dq_bsdiff_create_many), or dq_bsdiff_create_many like this build")
     ap.add_argument("--sets", default="fixed4k,loguniform")
     ap.add_argument("--worker", choices=["loop", "many", "many_off"])
     ap.add_argument("--lib")
@@ -158,7 +162,7 @@ def main():
     for set_name in args.sets.split(","):
         runs = {"parent": [], "new": []}
         for _ in range(args.rounds):
-            for who, path, kind in (("parent", args.parent_lib, "loop"), ("new", new_lib, "many")):
+            for who, path, kind in (("parent", args.parent_lib, args.parent_kind), ("new", new_lib, "many")):
                 if path:
                     runs[who].append(run_worker(kind, path, set_name, args.calls, 1100))
                     print(set_name, who, runs[who][-1]["ms_median"], "ms", flush=True)
@@ -176,7 +180,9 @@ def main():
         if runs["parent"]:
             p_ms = statistics.median(r["ms_median"] for r in runs["parent"])
             spread = max(max(r["ms_median"] for r in rs) - min(r["ms_median"] for r in rs) for rs in runs.values())
-            rec.update(parent_ms=[r["ms_median"] for r in runs["parent"]], parent_ms_median=p_ms,
+            if "last_call_info" in runs["parent"][-1]:
+                rec["parent_last_call_info"] = runs["parent"][-1]["last_call_info"]
+            rec.update(parent_kind=args.parent_kind, parent_ms=[r["ms_median"] for r in runs["parent"]], parent_ms_median=p_ms,
                        ratio_parent_over_new=round(p_ms / n_ms, 2), spread_ms=round(spread, 3),
                        faster_by_more_than_the_spread=bool(p_ms - n_ms > spread))
         result["sets"][set_name] = rec
