@@ -119,8 +119,9 @@ public static class HipDiff
 
     /// <summary>
     /// The patches of many independent (old, new) pairs in one native call (dq_bsdiff_create_many): pairs whose files
-    /// both have at most 8192 bytes share kernel launches and block sorts instead of costing four or five device round
-    /// trips each, longer ones are diffed one after another.  Entry j of the result is the patch
+    /// both have at most 65 536 bytes share kernel launches and block sorts instead of costing four or five device round
+    /// trips each (pairs with a file above 8192 bytes where a chunk of the call holds at least 16 of them), longer ones
+    /// are diffed one after another.  Entry j of the result is the patch
     /// <see cref="Create"/> writes for (olds[j], news[j]).  The files are laid back to back in managed buffers for the
     /// call and every pair gets a slot of dq_bsdiff_patch_bound bytes, so the totals are limited to what one array holds;
     /// callers with more split their list.
@@ -191,11 +192,13 @@ public static class HipDiff
     /// Shape of the last CreateMany on this thread (dq_last_diff_many_info): pairs through the shared launches, pairs
     /// diffed one by one, launches of the anchor kernel, bzip2 blocks of doubled length up to 8192 (shared sort), blocks
     /// above it (in medium launches or sorted singly: HipSuffixSort.LastManyInfo tells which),
-    /// then microseconds per phase (sort of the old files, anchor kernel + copies, host emission, block sorts, framing).
+    /// then microseconds per phase (sort of the old files, anchor kernels + copies, host emission, block sorts, framing),
+    /// [10] pairs with a file above 8192 bytes that went through the medium anchor launches (counted in [0] too),
+    /// [11] launches of the medium anchor kernel ([2] counts the short pairs' kernel only).
     /// </summary>
     public static unsafe long[] LastDiffManyInfo()
     {
-        var info = new long[10];
+        var info = new long[12];
         fixed (long* p = info)
         {
             Native.Check(Native.dq_last_diff_many_info(p, info.Length), nameof(Native.dq_last_diff_many_info));

@@ -228,13 +228,15 @@ def last_diff_info() -> dict:
 def last_diff_many_info() -> dict:
     """Shape of the last dq_bsdiff_create_many on this thread (dq_last_diff_many_info)."""
     L = load()
-    v = (ctypes.c_int64 * 10)()
-    L.dq_last_diff_many_info(v, 10)
+    v = (ctypes.c_int64 * 12)()
+    L.dq_last_diff_many_info(v, 12)
     # (shared_block_sorts / single_block_sorts count by length: doubled length up to / above 8192; medium_block_sorts
-    # says how many of the latter shared a medium launch.  The old files' sort has no medium texts: they are <= 8192)
+    # says how many texts of the call shared a medium launch of the sorter: blocks, and old files above 8192 bytes.
+    # medium_pairs are counted in shared_pairs too; anchor_launches counts the short pairs' kernel only)
     return {"shared_pairs": v[0], "single_pairs": v[1], "anchor_launches": v[2], "shared_block_sorts": v[3],
             "single_block_sorts": v[4], "sort_old_ms": v[5] / 1e3, "anchor_ms": v[6] / 1e3, "emit_ms": v[7] / 1e3,
-            "block_sort_ms": v[8] / 1e3, "frame_ms": v[9] / 1e3, "medium_block_sorts": last_many_info()["medium_texts"]}
+            "block_sort_ms": v[8] / 1e3, "frame_ms": v[9] / 1e3, "medium_block_sorts": last_many_info()["medium_texts"],
+            "medium_pairs": v[10], "medium_anchor_launches": v[11]}
 
 
 def last_many_info() -> dict:

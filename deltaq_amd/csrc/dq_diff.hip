@@ -7,6 +7,7 @@
 #include "dq_match_search.h"
 #include "dq_anchor_scan.h"
 #include "dq_anchor_many.h"
+#include "dq_anchor_mid_many.h"
 #include "dq_scan_wait.h"
 #include "dq_bz2.h"
 #include "dq_bsdiff.h"
@@ -1388,13 +1389,16 @@ int frame_patch(const bsdiff::RawStreams &raw, int64_t m, int dev, std::vector<u
     return DQ_OK;
 }
 
-// ---- many short pairs in shared launches (dq_bsdiff_create_many) ----------------------------------------------------
-// A pair of files of up to kDiffManyMax bytes each costs the one-pair path four or five dependent device round trips
+// ---- many short and medium pairs in shared launches (dq_bsdiff_create_many) -----------------------------------------
+// A pair of files of up to kMidMaxN bytes each costs the one-pair path four or five dependent device round trips
 // (sort of old, anchor scan, up to three block sorts) for a few kilobytes.  Here the pairs of a call travel in chunks
 // of whole pairs -- at most kDiffManyChunkBytes of old + new -- and every chunk goes through five phases, each shared
 // by all its pairs:
-//   1. old and new files and their offsets to the device; sufsort_many_dev on the old files (the suffix arrays stay there)
-//   2. anchor_many_kernel (dq_anchor_many.h): the (cursor, hit_pos) list of every pair; lists to the host
+//   1. old and new files and their offsets to the device; sufsort_many_dev on the old files (the suffix arrays stay
+//      there; old files above the short-text limit take its medium launches or, below its own threshold, its one-by-one route)
+//   2. the (cursor, hit_pos) list of every pair: anchor_many_kernel (dq_anchor_many.h) on the short pairs -- both files of
+//      at most kDiffManyMax bytes -- and anchor_mid_many_kernel (dq_anchor_mid_many.h) on the medium ones; the two
+//      launches go back to back on one stream, each with its own work list and counter; lists to the host
 //   3. host threads: TripleEmitter + scan_from_anchors per pair -> RawStreams; run-length pre-pass and CRC of the three
 //      streams (bz2::StreamEncoder with its blocks held back)
 //   4. all blocks of all streams of the chunk, doubled and laid back to back: ONE sufsort_many_host call (blocks whose
@@ -1402,10 +1406,18 @@ int frame_patch(const bsdiff::RawStreams &raw, int64_t m, int dev, std::vector<u
 //      them; the others take that call's own one-by-one route)
 //   5. host threads: each block finished from its suffix array, header + three streams into the pair's slot.
 // Device memory per chunk: old + new + 4 bytes of suffix array per byte of old + one int32 per byte of new for the
-// anchor lists + 40 bytes per pair (< 6 bytes per byte of text).  Host memory per chunk: the raw streams (< 4 bytes
+// anchor lists + 40 bytes per pair (< 6 bytes per byte of text), whatever the pairs' classes: the medium kernel reads
+// the suffix arrays where the sort left them and has no scratch blocks.  Host memory per chunk: the raw streams (< 4 bytes
 // per byte of new), their blocks doubled with 4 bytes of suffix array per doubled byte (10 bytes per stream byte).
 constexpr int64_t kDiffManyChunkBytes = 64ll << 20;
 constexpr int32_t kDiffManyChunkPairs = 1 << 18;
+// Fewest medium pairs (a file above kDiffManyMax, none above kMidMaxN) of a chunk that share its launches.  Below it
+// the chunk is taken as without the medium class: those pairs one by one, the short runs between them as chunks.
+// One workgroup on a 64 KiB pair is slower than the whole device on it; tools/kbench/diff_many_medium.py sweeps where
+// the two meet: from 2 to 8 pairs over 16 / 32 / 64 KiB files, similar and unrelated (profiles/r10/diff_many_medium.json);
+// twice the largest crossing.  (At least 8 whatever a sweep says: a handful of larger files among short ones keeps the
+// path it had.)
+constexpr int32_t kDiffMidManyMin = 16;
 
 // anchors a pair of `m` new bytes can emit: every triple but the last stands on a match of more than 8 bytes
 // (hit_len > carried + 8, carried >= 0) and the scan goes on behind it, so there are at most m / 9 + 1
@@ -1464,7 +1476,7 @@ struct ManyPair {
     std::string err;
 };
 
-// pairs [first, first + cnt) of the call, all short: their patches into `out`
+// pairs [first, first + cnt) of the call, no file above kMidMaxN bytes: their patches into `out`
 int diff_many_chunk(const uint8_t *olds, const int64_t *ooff, const uint8_t *news, const int64_t *noff, int32_t first, int32_t cnt,
                     int dev, DeviceBuf &buf, std::vector<ManyPair> &out)
 {
@@ -1483,10 +1495,16 @@ int diff_many_chunk(const uint8_t *olds, const int64_t *ooff, const uint8_t *new
         if (j > 0) rel_a[j] = rel_a[j - 1] + diff_many_anchor_room(rel_n[j] - rel_n[j - 1]);
     }
     const int64_t anchors = rel_a[cnt];
+    // (two lists in one: the short pairs, then the medium ones)
+    auto klass = [&](int32_t j) { return std::max(rel_o[j + 1] - rel_o[j], rel_n[j + 1] - rel_n[j]) <= kDiffManyMax ? 0 : 1; };
     std::vector<int32_t> order((size_t)cnt);
     for (int32_t j = 0; j < cnt; ++j) order[(size_t)j] = j;
-    std::stable_sort(order.begin(), order.end(),
-                     [&](int32_t a, int32_t b) { return rel_n[a + 1] - rel_n[a] > rel_n[b + 1] - rel_n[b]; });
+    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
+        const int ka = klass(a), kb = klass(b);
+        return ka != kb ? ka < kb : rel_n[a + 1] - rel_n[a] > rel_n[b + 1] - rel_n[b];
+    });
+    int32_t in_class[2] = {0, 0};
+    for (int32_t j = 0; j < cnt; ++j) ++in_class[klass(j)];
     // what comes back: anchor lists, then counts and searches per pair
     std::vector<int32_t> back((size_t)anchors * 2 + (size_t)cnt * 2);
 
@@ -1528,21 +1546,37 @@ int diff_many_chunk(const uint8_t *olds, const int64_t *ooff, const uint8_t *new
         };
         auto scan = [&](DeviceCtx &c, hipStream_t st) -> int {
             const auto t0 = std::chrono::steady_clock::now();
-            if (c.anchor_many_groups <= 0) {
-                // workgroups the device holds at once (a wrong answer costs time only: nobody waits for anybody)
+            // workgroups the device holds at once (a wrong answer costs time only: nobody waits for anybody)
+            auto resident = [&](int *groups, auto kernel, int threads) {
+                if (*groups > 0) return;
                 int per_cu = 0, ncu = 0;
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, anchor_many_kernel, kAmThreads, 0) != hipSuccess || per_cu <= 0)
-                    per_cu = 1;
+                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, 0) != hipSuccess || per_cu <= 0) per_cu = 1;
                 if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
-                c.anchor_many_groups = per_cu * ncu;
-            }
+                *groups = per_cu * ncu;
+            };
             Launcher L{c, st, g_prof_on.load()};
-            const int grid = std::min<int>(cnt, c.anchor_many_groups);
-            LAUNCH(L, DQ_K_MATCH_SEARCH, n_bytes, o_bytes * 5 + n_bytes,
-                   hipLaunchKernelGGL(anchor_many_kernel, dim3((unsigned)grid), dim3(kAmThreads), 0, st, d_old, d_off, d_sa, d_new,
-                                      d_off + (cnt + 1), d_off + 2 * (cnt + 1), d_order, cnt, d_next, d_back, d_back + 2 * anchors,
-                                      d_back + 2 * anchors + cnt));
-            t_diff_many_info[2] += 1;
+            const int64_t *d_noff = d_off + (cnt + 1), *d_aoff = d_off + 2 * (cnt + 1);
+            int32_t *d_counts = d_back + 2 * anchors, *d_searches = d_counts + cnt;
+            // (a class's share of the bytes is not known here: the profile books all of them on the first launch)
+            int64_t prof_units = n_bytes, prof_bytes = o_bytes * 5 + n_bytes;
+            if (in_class[0] > 0) {
+                resident(&c.anchor_many_groups, anchor_many_kernel, kAmThreads);
+                const int grid = std::min<int>(in_class[0], c.anchor_many_groups);
+                LAUNCH(L, DQ_K_MATCH_SEARCH, prof_units, prof_bytes,
+                       hipLaunchKernelGGL(anchor_many_kernel, dim3((unsigned)grid), dim3(kAmThreads), 0, st, d_old, d_off, d_sa, d_new,
+                                          d_noff, d_aoff, d_order, in_class[0], d_next, d_back, d_counts, d_searches));
+                prof_units = prof_bytes = 0;
+                t_diff_many_info[2] += 1;
+            }
+            if (in_class[1] > 0) {
+                resident(&c.anchor_mid_many_groups, anchor_mid_many_kernel, kAmmThreads);
+                const int grid = std::min<int>(in_class[1], c.anchor_mid_many_groups);
+                LAUNCH(L, DQ_K_MATCH_SEARCH, prof_units, prof_bytes,
+                       hipLaunchKernelGGL(anchor_mid_many_kernel, dim3((unsigned)grid), dim3(kAmmThreads), 0, st, d_old, d_off, d_sa, d_new,
+                                          d_noff, d_aoff, d_order + in_class[0], in_class[1], d_next + 16, d_back, d_counts, d_searches));
+                t_diff_many_info[11] += 1;
+            }
+            t_diff_many_info[10] += in_class[1];
             const hipError_t e1 = hipMemcpyAsync(back.data(), d_back, back.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st);
             const hipError_t e2 = hipStreamSynchronize(st);
             HIP_TRY(e1 != hipSuccess ? e1 : e2);
@@ -1697,33 +1731,56 @@ int bsdiff_create_many_host(const uint8_t *olds, const int64_t *ooff, const uint
         plens[j] = (int64_t)patch.size();
         return DQ_OK;
     };
-    const int64_t short_max = kDiffManyMax;
     const bool one_by_one = flags().no_diff_many.value_or(0) != 0;
-    auto is_short = [&](int32_t j) { return !one_by_one && ooff[j + 1] - ooff[j] <= short_max && noff[j + 1] - noff[j] <= short_max; };
+    const int64_t listed_max = flags().no_diff_mid_many.value_or(0) != 0 ? kDiffManyMax : kMidMaxN;
+    const int64_t mid_min = flags().diff_mid_many_min.value_or(kDiffMidManyMin);
+    auto longest = [&](int32_t j) { return std::max(ooff[j + 1] - ooff[j], noff[j + 1] - noff[j]); };
+    auto is_short = [&](int32_t j) { return !one_by_one && longest(j) <= kDiffManyMax; };
+    auto is_listed = [&](int32_t j) { return !one_by_one && longest(j) <= listed_max; };
     DeviceBuf buf;
     buf.dev = dev;
     std::vector<ManyPair> done;
+    auto single = [&](int32_t j) -> int {
+        // the one-pair path, into the pair's slot (it reports under its own dq_last_diff_info)
+        std::vector<uint8_t> patch;
+        int r = bsdiff_create_host(olds + ooff[j], ooff[j + 1] - ooff[j], news + noff[j], noff[j + 1] - noff[j], dev, patch);
+        if (r == DQ_OK) r = deliver(j, patch);
+        if (r == DQ_OK) t_diff_many_info[1] += 1;
+        return r;
+    };
+    auto chunk = [&](int32_t a, int32_t b) -> int {
+        int r = diff_many_chunk(olds, ooff, news, noff, a, b - a, dev, buf, done);
+        if (r != DQ_OK) return r;
+        t_diff_many_info[0] += b - a;
+        for (int32_t j = a; j < b && r == DQ_OK; ++j) r = deliver(j, done[(size_t)(j - a)].patch);
+        return r;
+    };
     for (int32_t i = 0; i < count;) {
-        if (!is_short(i)) {
-            // the one-pair path, into the pair's slot (it reports under its own dq_last_diff_info)
-            std::vector<uint8_t> patch;
-            rc = bsdiff_create_host(olds + ooff[i], ooff[i + 1] - ooff[i], news + noff[i], noff[i + 1] - noff[i], dev, patch);
-            if (rc == DQ_OK) rc = deliver(i, patch);
+        if (!is_listed(i)) {
+            rc = single(i);
             if (rc != DQ_OK) return rc;
-            t_diff_many_info[1] += 1;
             ++i;
             continue;
         }
         int32_t e = i;
-        while (e < count && e - i < kDiffManyChunkPairs && is_short(e) &&
-               (ooff[e + 1] - ooff[i]) + (noff[e + 1] - noff[i]) <= kDiffManyChunkBytes)
+        int64_t mids = 0;
+        while (e < count && e - i < kDiffManyChunkPairs && is_listed(e) &&
+               (ooff[e + 1] - ooff[i]) + (noff[e + 1] - noff[i]) <= kDiffManyChunkBytes) {
+            mids += !is_short(e);
             ++e;
-        rc = diff_many_chunk(olds, ooff, news, noff, i, e - i, dev, buf, done);
-        if (rc != DQ_OK) return rc;
-        t_diff_many_info[0] += e - i;
-        for (int32_t j = i; j < e; ++j) {
-            rc = deliver(j, done[(size_t)(j - i)].patch);
+        }
+        if (mids == 0 || mids >= mid_min) {
+            rc = chunk(i, e);
             if (rc != DQ_OK) return rc;
+        } else {
+            // too few medium pairs for launches of their own: the run as without the class, in input order
+            for (int32_t a = i; a < e;) {
+                int32_t b = a;
+                while (b < e && is_short(b)) ++b;
+                rc = b > a ? chunk(a, b) : single(b++);
+                if (rc != DQ_OK) return rc;
+                a = b;
+            }
         }
         i = e;
     }

@@ -41,7 +41,7 @@ inline thread_local int64_t t_info[3] = {0, 0, 0};
 // the last Diff.Create / index diff on this thread (dq_last_diff_info): Search calls of the loop, windows, positions
 // asked again exactly, launches of the device's anchor scan that were given back to the host loop, workgroups of its grid
 inline thread_local int64_t t_diff_info[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-inline thread_local int64_t t_diff_many_info[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};     // dq_last_diff_many_info
+inline thread_local int64_t t_diff_many_info[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};     // dq_last_diff_many_info
 // the shared sorts of the last outermost many-texts / batch / many-pairs call on this thread (dq_last_many_info): texts in
 // the short classes' launches, texts in medium launches, medium-length texts sorted singly, texts above kMidMaxN sorted
 // singly, launches of mid_many_kernel, bytes of per-workgroup scratch carved for them
@@ -107,6 +107,7 @@ struct DeviceCtx {
     int ncu = 0;                        // compute units of the device (grid of the persistent kernels)
     int many_groups[5] = {0, 0, 0, 0, 0};   // workgroups of small_many_kernel (3 length classes) and mid_many_kernel (2) the device holds at once (0: not asked yet)
     int anchor_many_groups = 0;         // ... and of anchor_many_kernel (dq_anchor_many.h)
+    int anchor_mid_many_groups = 0;     // ... and of anchor_mid_many_kernel (dq_anchor_mid_many.h)
     hipStream_t stream = nullptr;
     char *ws = nullptr;
     size_t ws_bytes = 0;

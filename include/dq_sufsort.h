@@ -148,7 +148,7 @@ int32_t dq_bsdiff_create(const uint8_t *old_data, int64_t n, const uint8_t *new_
                          int64_t cap, int64_t *patch_len, int32_t device);
 int64_t dq_bsdiff_patch_bound(int64_t n, int64_t m);
 
-/* ---- many SHORT file pairs in shared launches (two directory trees of small files) ------------------------------
+/* ---- many SHORT and MEDIUM file pairs in shared launches (two directory trees of small files) -------------------
  * dq_bsdiff_create_many: `count` independent (old, new) pairs in one call.  Layout as dq_sufsort_hip_many_i32: the old
  * files back to back in `olds`, the new files in `news`, each with an offsets array of count + 1 int64 entries
  * (offsets[0] == 0, never decreasing); pair j is olds[old_offsets[j] .. old_offsets[j + 1]) against
@@ -156,14 +156,21 @@ int64_t dq_bsdiff_patch_bound(int64_t n, int64_t m);
  * (capacity patch_offsets[j + 1] - patch_offsets[j]; dq_bsdiff_patch_bound(n_j, m_j) always suffices), patch_lens[j]
  * receives the length; nothing outside patches[patch_offsets[j] .. + patch_lens[j]) is written.
  * Patch j is byte for byte what dq_bsdiff_create returns for pair j alone, empty files on either side included.
- * Pairs whose files both have at most 8192 bytes share their launches: in chunks of whole pairs (at most 64 MiB of
- * old + new, 262 144 pairs), the old files are sorted by the launches of dq_sufsort_hip_many_dev_i32, one launch of
- * anchor_many_kernel finds the anchors of every pair (one workgroup per pair, nobody waits for anybody), host threads
- * turn them into the raw streams, all bzip2 blocks of the chunk are transformed by one dq_sufsort_hip_many_i32-style
- * sort (blocks of doubled length 8193 .. 65 536 in its medium launches, where there are enough) and host threads frame
- * the patches.  The call is total: a pair with a longer file (below 2 GiB) is diffed by
- * dq_bsdiff_create's path, one after another, into its slot.
- * Footprint per chunk -- device: old + new + 4 bytes per byte of old + 1 byte per byte of new + 40 bytes per pair, freed
+ * Pairs whose files both have at most 65 536 bytes share their launches: in chunks of whole pairs (at most 64 MiB of
+ * old + new, 262 144 pairs), the old files are sorted by the launches of dq_sufsort_hip_many_dev_i32, the anchors of
+ * every pair are found by one workgroup per pair (nobody waits for anybody), host threads turn them into the raw
+ * streams, all bzip2 blocks of the chunk are transformed by one dq_sufsort_hip_many_i32-style sort (blocks of doubled
+ * length 8193 .. 65 536 in its medium launches, where there are enough) and host threads frame the patches.
+ * The anchor step has two classes of pairs, one launch each per chunk where the class has pairs: SHORT, both files of
+ * at most 8192 bytes (anchor_many_kernel, everything in LDS), and MEDIUM, a file above 8192 bytes
+ * (anchor_mid_many_kernel: both files in LDS, the suffix array read from device memory).
+ * A chunk with fewer than 16 medium pairs is taken as if there were no medium class: those pairs one after another by
+ * dq_bsdiff_create's path, the short runs between them in chunks of their own -- one workgroup on a medium pair is not
+ * faster than the whole device on it, only many of them side by side are.
+ * The call is total: a pair with a file above 65 536 bytes (below 2 GiB) is diffed by dq_bsdiff_create's path, one
+ * after another, into its slot.  Patches are delivered in input order whichever way a pair went.
+ * Footprint per chunk -- device: old + new + 4 bytes per byte of old + 1 byte per byte of new + 40 bytes per pair, the
+ * same for every class (the medium anchor kernel has no scratch blocks), freed
  * on return (the shared sort's own workspace, scratch blocks of medium launches included, stays with the library until
  * dq_sufsort_hip_release); host: below 4 bytes per byte of new for the raw streams and 10 bytes per byte of stream for the shared sort.
  * Errors found before any device use: count < 0, a NULL pointer with count > 0, offsets[0] != 0 or decreasing offsets
@@ -305,11 +312,13 @@ int32_t dq_last_sort_info(int64_t *rounds, int64_t *initial_active, int64_t *sum
  * emitter threads. */
 int32_t dq_last_diff_info(int64_t *info, int32_t count);
 
-/* Shape of the last dq_bsdiff_create_many on this thread, `count` entries (10 are defined, further ones read 0): pairs
- * that went through the shared launches; pairs diffed one by one; launches of anchor_many_kernel; bzip2 blocks whose
- * transform went through a shared sort of the short classes (doubled length up to 8192); bzip2 blocks of doubled length
- * above 8192, whether they shared a medium launch or were sorted singly (dq_last_many_info tells which); microseconds
- * in each phase: sort of the old files, anchor kernel + copies, host emission, block sorts, host framing. */
+/* Shape of the last dq_bsdiff_create_many on this thread, `count` entries (12 are defined, further ones read 0): pairs
+ * that went through the shared launches, short and medium; pairs diffed one by one; launches of anchor_many_kernel (the
+ * short pairs' kernel only); bzip2 blocks whose transform went through a shared sort of the short classes (doubled
+ * length up to 8192); bzip2 blocks of doubled length above 8192, whether they shared a medium launch or were sorted
+ * singly (dq_last_many_info tells which); microseconds in each phase: sort of the old files, anchor kernels + copies,
+ * host emission, block sorts, host framing; [10] pairs with a file above 8192 bytes that went through the medium anchor
+ * launches (counted in [0] too); [11] launches of anchor_mid_many_kernel. */
 int32_t dq_last_diff_many_info(int64_t *info, int32_t count);
 
 /* Shape of the shared sorts of the last outermost dq_sufsort_hip_many_i32 / _many_dev_i32 / dq_sufsort_hip_batch_i32 /
