@@ -29,7 +29,12 @@ K_RADIX_RANK = 2          # DQ_K_RADIX_RANK: the dominant kernel's profile categ
 K_SMALL_SORT = 14         # DQ_K_SMALL_SORT: one short text, one launch
 K_SMALL_MANY = 23         # DQ_K_SMALL_MANY: many short / medium texts in shared launches
 # kernels that are accounted under another kernel's category (the category count is part of the ABI)
-CATEGORY_ALIASES = {"mid_many_kernel": "small_many_kernel"}
+CATEGORY_ALIASES = {"mid_many_kernel": "small_many_kernel", "large_text_kernel": "small_many_kernel",
+                    "large_doubled_kernel": "small_many_kernel", "large_key0_kernel": "small_many_kernel",
+                    "large_key2_kernel": "small_many_kernel", "large_twin_kernel": "small_many_kernel",
+                    "large_scatter_kernel": "small_many_kernel"}
+MID_MAX_N = 65536         # kMidMaxN: longest text of the medium class of the many-texts launches
+LARGE_MAX_N = 4 << 20     # kLargeMaxN: longest text of their segmented sort (dq_large_many.h)
 
 # every symbol include/dq_sufsort.h declares
 EXPORTS = (
@@ -246,6 +251,16 @@ def last_many_info() -> dict:
     check(L.dq_last_many_info(v, 6))
     return {"short_texts": v[0], "medium_texts": v[1], "medium_single": v[2], "long_single": v[3],
             "medium_launches": v[4], "scratch_bytes": v[5]}
+
+
+def last_many_large_info() -> dict:
+    """The segmented sorts (texts above 65 536 bytes sorted together, dq_large_many.h) of the last many-texts / many-pairs
+    call on this thread: entries [6] .. [8] of dq_last_many_info.  list_entries sums the list lengths over all rounds of
+    all those sorts, round 0 counting the batch's bytes."""
+    L = load()
+    v = (ctypes.c_int64 * 9)()
+    check(L.dq_last_many_info(v, 9))
+    return {"large_texts": v[6], "segmented_sorts": v[7], "list_entries": v[8]}
 
 
 def last_batch_info() -> dict:

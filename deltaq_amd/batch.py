@@ -45,7 +45,8 @@ def plan_shards(lengths: Sequence[int], world_size: int) -> List[List[int]]:
 
 def sort_batch_local(texts: Sequence, sorter) -> List[np.ndarray]:
     """All inputs on one device, through the provider's ISuffixSort surface.  A provider with ``SortMany``
-    (``HipSuffixSort``) gets its host inputs in one call: the short ones share launches instead of costing one each."""
+    (``HipSuffixSort``) gets its host inputs in one call: the short and medium ones share launches instead of costing one
+    each; longer ones are sorted one after another (the segmented sort of large texts is off by default)."""
     texts = list(texts)
     many = getattr(sorter, "SortMany", None)
     if many is not None and len(texts) > 1 and not any(type(t).__module__.startswith("torch") for t in texts):

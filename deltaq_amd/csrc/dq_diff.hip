@@ -1403,7 +1403,8 @@ int frame_patch(const bsdiff::RawStreams &raw, int64_t m, int dev, std::vector<u
 //      streams (bz2::StreamEncoder with its blocks held back)
 //   4. all blocks of all streams of the chunk, doubled and laid back to back: ONE sufsort_many_host call (blocks whose
 //      doubled length exceeds the short-text limit share its medium launches up to kMidMaxN, where there are enough of
-//      them; the others take that call's own one-by-one route)
+//      them; the others, and every block above kMidMaxN, take that call's own one-by-one route: the segmented sort of
+//      large texts, dq_large_many.h, is off here unless the debug flag DQ_LARGE_MANY_MIN asks for it)
 //   5. host threads: each block finished from its suffix array, header + three streams into the pair's slot.
 // Device memory per chunk: old + new + 4 bytes of suffix array per byte of old + one int32 per byte of new for the
 // anchor lists + 40 bytes per pair (< 6 bytes per byte of text), whatever the pairs' classes: the medium kernel reads
@@ -1667,7 +1668,10 @@ int diff_many_chunk(const uint8_t *olds, const int64_t *ooff, const uint8_t *new
                 bz2::double_block(w.enc[s]->block_rle(b), btext.data() + boff[(size_t)bplace[(size_t)at++]]);
     });
     int64_t shared = 0;
-    const int rc = sufsort_many_host(btext.data(), boff.data(), (int32_t)nblocks, bsa.data(), dev, &shared);
+    // Blocks above kMidMaxN doubled bytes reach the planner's large class (dq_large_many.h), but here it stays off unless
+    // DQ_LARGE_MANY_MIN asks for it: the block-sort phase has not been measured faster with it than with the one-by-one
+    // route, whose sorts get no hint either but run the device sorter's LDS group rounds (docs/ROUNDS.md, round 11).
+    const int rc = sufsort_many_host(btext.data(), boff.data(), (int32_t)nblocks, bsa.data(), dev, &shared, /*large_by_default=*/false);
     if (rc != DQ_OK) return rc;
     std::vector<uint8_t>().swap(btext);
     t_diff_many_info[3] += shared;

@@ -31,6 +31,8 @@ struct Flags {
     std::optional<int> small_n;             // DQ_SMALL_N: largest n of the single-workgroup sorter, >= 0 (<= kSmallMaxN)
     std::optional<int> no_many;             // DQ_NO_MANY: 1: every text of a batch its own launch; bits 2 | 4: no 2048- / 4096-byte class; bit 8: no medium class
     std::optional<int> mid_many_min;        // DQ_MID_MANY_MIN: fewest medium texts of a call / chunk that share a launch, >= 1
+    std::optional<int> no_large_many;       // DQ_NO_LARGE_MANY: 1: no segmented sort of the texts above 65 536 bytes (singly, as without the class)
+    std::optional<int> large_many_min;      // DQ_LARGE_MANY_MIN: fewest large texts of a call / chunk that share a segmented sort, >= 1; set at all, it also switches the class on in dq_bsdiff_create_many's block sort
     std::optional<int> no_diff_many;        // DQ_NO_DIFF_MANY: 1: every pair of dq_bsdiff_create_many through the one-pair path
     std::optional<int> no_diff_mid_many;    // DQ_NO_DIFF_MID_MANY: 1: no medium class of its pairs (a file above 8192 bytes: singly)
     std::optional<int> diff_mid_many_min;   // DQ_DIFF_MID_MANY_MIN: fewest medium pairs of a chunk that share its launches, >= 1
@@ -127,6 +129,8 @@ inline Flags read_flags()
     f.small_n = num("DQ_SMALL_N", 0);
     f.no_many = num("DQ_NO_MANY", 0, 15);
     f.mid_many_min = num("DQ_MID_MANY_MIN", 1);
+    f.no_large_many = num("DQ_NO_LARGE_MANY", 0, 1);
+    f.large_many_min = num("DQ_LARGE_MANY_MIN", 1);
     f.no_diff_many = num("DQ_NO_DIFF_MANY", 0, 1);
     f.no_diff_mid_many = num("DQ_NO_DIFF_MID_MANY", 0, 1);
     f.diff_mid_many_min = num("DQ_DIFF_MID_MANY_MIN", 1);

@@ -34,6 +34,7 @@ namespace dq {
 
 constexpr int kSmallMaxN = 8192;          // largest text the single-workgroup sorter takes (dq_small.h)
 constexpr int kMidMaxN = 65536;           // largest text of the medium class of the many-texts launches (dq_mid_many.h)
+constexpr int kLargeMaxN = 4 << 20;       // largest text of their segmented sort (dq_large_many.h; the figures: dq_small_many.h)
 
 // ------------------------------------------------------------------ errors
 inline thread_local std::string t_err;
@@ -44,8 +45,9 @@ inline thread_local int64_t t_diff_info[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
 inline thread_local int64_t t_diff_many_info[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};     // dq_last_diff_many_info
 // the shared sorts of the last outermost many-texts / batch / many-pairs call on this thread (dq_last_many_info): texts in
 // the short classes' launches, texts in medium launches, medium-length texts sorted singly, texts above kMidMaxN sorted
-// singly, launches of mid_many_kernel, bytes of per-workgroup scratch carved for them
-inline thread_local int64_t t_many_info[6] = {0, 0, 0, 0, 0, 0};
+// singly, launches of mid_many_kernel, bytes of per-workgroup scratch carved for them, texts sorted in segmented sorts
+// (dq_large_many.h), segmented sorts run, their list lengths summed over all rounds (round 0 counting the batch's bytes)
+inline thread_local int64_t t_many_info[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
 
 // the last dq_sufsort_hip_batch_i32 on this thread (dq_last_batch_info): inputs through the pipelines, microseconds the
 // copy-in / sort / copy-out stages were busy (summed over the device shares), wall microseconds of the slowest share,
@@ -406,9 +408,10 @@ extern template int64_t sufsort_workspace_plan<int64_t>(int64_t, bool, int64_t);
 
 // many short texts in shared launches (dq_small_many.h, in dq_sorter_i32.hip): the bodies of dq_sufsort_hip_many_i32 /
 // _many_dev_i32.  shared_out (optional): texts of the short classes (by length: up to the short-text limit).  Both add
-// what they did to t_many_info; the entry point that is outermost resets it.
+// what they did to t_many_info; the entry point that is outermost resets it.  large_by_default = false: the large class
+// (dq_large_many.h) only where DQ_LARGE_MANY_MIN is set.
 int sufsort_many_host(const uint8_t *texts, const int64_t *offsets, int32_t count, int32_t *sas, int32_t device,
-                      int64_t *shared_out = nullptr);
+                      int64_t *shared_out = nullptr, bool large_by_default = true);
 int sufsort_many_dev(const void *d_texts, const void *d_offsets, int32_t count, void *d_sas, int32_t device, void *stream);
 
 // LDSSChecker.Check on the device (dq_sufcheck.hip): DQ_OK with the verdict (DQ_SUFCHECK_*) in *result, or an error

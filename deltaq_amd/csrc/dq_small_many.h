@@ -12,9 +12,13 @@
 //     2048 bytes needs 30 KiB of LDS and 256 threads, five such workgroups share a CU where the 8192-byte class
 //     (120 KiB, 1024 threads) fits once.  One launch per class, on the same stream.
 // Texts between the short-text limit and kMidMaxN = 65 536 bytes share launches of mid_many_kernel (dq_mid_many.h), where
-// a call or chunk holds at least kMidManyMin of them; the others, and every text above kMidMaxN, are handed to the
-// device sorter one after another by the host drivers below.  32-bit indices only (dq_sorter_i32.hip includes this file).
+// a call or chunk holds at least kMidManyMin of them.  Texts above kMidMaxN and up to kLargeMaxN bytes share one segmented
+// sort per batch (dq_large_many.h), where that class is on (kLargeManyByDefault below: not by default) and a call or chunk
+// holds at least the threshold of them.  The others, and every
+// text above kLargeMaxN, are handed to the device sorter one after another by the host drivers below.  32-bit indices
+// only (dq_sorter_i32.hip includes this file).
 #pragma once
+#include "dq_large_many.h"
 #include "dq_mid_many.h"
 #include "dq_small.h"
 
@@ -61,6 +65,18 @@ constexpr ManyClass kManyClass[kAllClasses] = {{2048, 256}, {4096, 512}, {kSmall
 // Measured (profiles/r09/many_medium.json): the forced launch beats the one-by-one route from 8 /
 // 16 / 32 texts of 16 / 32 / 64 KiB on; twice the largest crossing, rounded up to a power of two.
 constexpr int kMidManyMin = 64;
+
+// The large class (kMidMaxN + 1 ... kLargeMaxN bytes, dq_runtime.h: one segmented sort per batch, dq_large_many.h) is
+// OFF by default: its texts are sorted singly, as without it, unless the debug flag DQ_LARGE_MANY_MIN names the fewest
+// large texts of a call (device form) or chunk (host form) that share a sort.  It goes on by default with measured
+// constants only.  The rule (tools/kbench/many_large.py, which writes profiles/r11/many_large.json): the sweep of 1 ...
+// 512 texts of 128 KiB ... 4 MiB, forced on against off, gives a crossing per length; kLargeMaxN = the largest swept
+// length with a crossing at or below 64, kLargeManyMin = twice the largest crossing among the lengths kept, rounded up to
+// a power of two, and never below 5 (existing tests put four large texts into a call and expect them sorted singly).
+// No such sweep is recorded, so kLargeManyByDefault is false; kLargeMaxN = 4 MiB is the largest length the sweep covers,
+// and kLargeManyMin = 8 -- the smallest power of two above that 5 -- holds the place of a measured threshold.
+constexpr bool kLargeManyByDefault = false;
+constexpr int kLargeManyMin = 8;
 
 template <int kC> struct ManyKernel {
     static constexpr int kMaxN = kManyClass[kC].max_n, kThreads = kManyClass[kC].threads;
@@ -111,11 +127,13 @@ struct ManyPlan {
     std::vector<int32_t> order;                 // the classes' work lists back to back, each longest text first
     int class_count[kAllClasses] = {0, 0, 0, 0, 0};
     int64_t class_bytes[kAllClasses] = {0, 0, 0, 0, 0};
-    std::vector<int32_t> longs;                 // texts sorted singly, in input order: those above kMidMaxN, and the medium ones that share no launch
+    std::vector<int32_t> larges;                // texts of the segmented sorts (dq_large_many.h), in input order
+    std::vector<int32_t> longs;                 // texts sorted singly, in input order: those above kLargeMaxN, and the medium and large ones that share nothing
     int64_t mid_single = 0, above_mid = 0;      // ... how many of them have medium length / are longer
     int64_t shorts() const { return class_count[0] + class_count[1] + class_count[2]; }
     int64_t mids() const { return class_count[3] + class_count[4]; }
     int64_t listed() const { return (int64_t)order.size(); }
+    bool shared() const { return !order.empty() || !larges.empty(); }      // the plan has launches of its own
 };
 
 // texts of up to this many bytes share a launch (n <= 2 always: the device-wide sorter is not built for them)
@@ -129,8 +147,19 @@ inline bool mid_many_on()
     const int drop = F.no_many.value_or(0);
     return !F.small_n && drop != 1 && !(drop & 8);
 }
+// The large class is off under DQ_NO_LARGE_MANY=1 and DQ_NO_MANY=1 and whenever DQ_SMALL_N is set; and unless
+// DQ_LARGE_MANY_MIN is set, wherever it is not on by default: kLargeManyByDefault, and by_default = false (a caller
+// that takes the class on request only whatever that constant says: sufsort_many_host's parameter).
+inline bool large_many_on(bool by_default)
+{
+    const Flags &F = flags();
+    if (!(by_default && kLargeManyByDefault) && !F.large_many_min) return false;
+    return !F.small_n && F.no_many.value_or(0) != 1 && F.no_large_many.value_or(0) == 0;
+}
+inline int64_t large_many_min() { return flags().large_many_min.value_or(kLargeManyMin); }
+inline bool is_large(int64_t n) { return n > kMidMaxN && n <= kLargeMaxN; }
 // texts of up to this many bytes may sit in a chunk of the host form / on a work list
-inline int64_t many_listed_max() { return mid_many_on() ? (int64_t)kMidMaxN : many_short_max(); }
+inline int64_t many_listed_max(bool large_by_default) { return large_many_on(large_by_default) ? (int64_t)kLargeMaxN : mid_many_on() ? (int64_t)kMidMaxN : many_short_max(); }
 
 // DQ_NO_MANY: bit 2 drops the 2048-byte class, bit 4 the 4096-byte class (their texts move up a class)
 inline int many_class_of(int64_t n, int drop)
@@ -140,12 +169,12 @@ inline int many_class_of(int64_t n, int drop)
     return kManyClasses - 1;
 }
 
-inline ManyPlan plan_many(const int64_t *off, int32_t first, int32_t last)
+inline ManyPlan plan_many(const int64_t *off, int32_t first, int32_t last, bool large_by_default = true)
 {
     ManyPlan p;
     const int64_t short_max = many_short_max();
     const int drop = flags().no_many.value_or(0);
-    const bool mid_on = mid_many_on();
+    const bool mid_on = mid_many_on(), large_on = large_many_on(large_by_default);
     std::vector<int32_t> lists[kAllClasses];
     std::vector<int32_t> mids;
     for (int32_t j = first; j < last; ++j) {
@@ -153,6 +182,7 @@ inline ManyPlan plan_many(const int64_t *off, int32_t first, int32_t last)
         if (n == 0) continue;
         if (n > short_max) {
             if (mid_on && n <= kMidMaxN) mids.push_back(j);
+            else if (large_on && is_large(n)) p.larges.push_back(j);
             else p.longs.push_back(j);
             continue;
         }
@@ -172,6 +202,13 @@ inline ManyPlan plan_many(const int64_t *off, int32_t first, int32_t last)
         const size_t at = p.longs.size();
         p.longs.insert(p.longs.end(), mids.begin(), mids.end());
         std::inplace_merge(p.longs.begin(), p.longs.begin() + (ptrdiff_t)at, p.longs.end());
+    }
+    // ... and so do the large ones
+    if (!p.larges.empty() && (int64_t)p.larges.size() < large_many_min()) {
+        const size_t at = p.longs.size();
+        p.longs.insert(p.longs.end(), p.larges.begin(), p.larges.end());
+        std::inplace_merge(p.longs.begin(), p.longs.begin() + (ptrdiff_t)at, p.longs.end());
+        p.larges.clear();
     }
     for (int32_t j : p.longs) {
         const int64_t n = off[j + 1] - off[j];
@@ -230,6 +267,60 @@ inline int launch_many(DeviceCtx &c, hipStream_t st, const ManyPlan &plan, const
         at += cnt;
     }
     return rc;
+}
+
+// Host buffers travel in chunks of at most this much text (sufsort_many_host), and a segmented sort takes at most this
+// much large text: fewer than kLargeSegMax texts above kMidMaxN.
+constexpr int64_t kManyChunkBytes = 64ll << 20;
+constexpr int32_t kManyChunkTexts = 1 << 20;
+static_assert(kManyChunkBytes / (kMidMaxN + 1) < kLargeSegMax, "a batch's segment ordinals fit 10 bits");
+static_assert(kLargeMaxN > kMidMaxN && kLargeMaxN <= kManyChunkBytes, "a large text fits a batch");
+
+// the batches of a plan's large texts: runs [from, to) of plan.larges with at most kManyChunkBytes of text each
+inline std::vector<std::pair<size_t, size_t>> large_batches(const ManyPlan &plan, const int64_t *off)
+{
+    std::vector<std::pair<size_t, size_t>> b;
+    size_t from = 0;
+    int64_t bytes = 0;
+    for (size_t k = 0; k < plan.larges.size(); ++k) {
+        const int64_t n = off[plan.larges[k] + 1] - off[plan.larges[k]];
+        if (k > from && bytes + n > kManyChunkBytes) { b.emplace_back(from, k); from = k; bytes = 0; }
+        bytes += n;
+    }
+    if (from < plan.larges.size()) b.emplace_back(from, plan.larges.size());
+    return b;
+}
+
+// device memory of a plan's segmented sorts (they follow each other and the shared launches on one stream, so all of
+// them share one area: the largest batch's need; 0 without large texts)
+inline size_t many_large_bytes(const ManyPlan &plan, const int64_t *off)
+{
+    size_t need = 0;
+    for (const auto &b : large_batches(plan, off)) {
+        int64_t bytes = 0;
+        for (size_t k = b.first; k < b.second; ++k) bytes += off[plan.larges[k] + 1] - off[plan.larges[k]];
+        need = std::max(need, large_ws_bytes(bytes, (int)(b.second - b.first)));
+    }
+    return need;
+}
+
+// The segmented sorts of a plan made from `off`, the host's copy of the offsets (byte positions in d_texts, entry positions
+// in d_sas).  d_ws: many_large_bytes(plan, off) bytes, 256-byte aligned, free once what the stream holds has run.
+// Returns with the stream drained.
+inline int launch_large(DeviceCtx &c, hipStream_t st, const ManyPlan &plan, const int64_t *off, const uint8_t *d_texts,
+                        int32_t *d_sas, char *d_ws)
+{
+    for (const auto &b : large_batches(plan, off)) {
+        LargeTables tab;
+        int64_t lists = 0;
+        const int segs = (int)(b.second - b.first);
+        const int rc = large_many_sort(c, st, d_ws, d_texts, off, plan.larges.data() + b.first, segs, d_sas, tab, &lists);
+        if (rc != DQ_OK) { (void)hipStreamSynchronize(st); return rc; }      // (the uploads read `tab` until here)
+        t_many_info[6] += segs;
+        t_many_info[7] += 1;
+        t_many_info[8] += lists;
+    }
+    return DQ_OK;
 }
 
 // what a plan's shared launches and single sorts add to dq_last_many_info (one_by_one: no shared launch was made)
@@ -302,11 +393,13 @@ int sufsort_many_dev(const void *d_texts_v, const void *d_offsets_v, int32_t cou
         if (rc != DQ_OK) return rc;
         t_info[0] = t_info[1] = t_info[2] = 0;
         plan = plan_many(off.data(), 0, count);
-        if (!many_one_by_one() && plan.listed() > 0) {
+        if (!many_one_by_one() && plan.shared()) {
             const size_t b_ctl = many_ctl_bytes(plan.listed()), b_scratch = many_scratch_bytes(c, plan);
-            rc = ensure_ws(c, b_ctl + b_scratch);
+            rc = ensure_ws(c, std::max(b_ctl + b_scratch, many_large_bytes(plan, off.data())));
             if (rc != DQ_OK) return rc;
             rc = launch_many(c, st, plan, d_texts, d_offsets, d_sas, c.ws, c.ws + b_ctl);
+            // (the segmented sorts, batch after batch, take the same area once the launches before them have run)
+            if (rc == DQ_OK) rc = launch_large(c, st, plan, off.data(), d_texts, d_sas, c.ws);
             if (rc != DQ_OK) { drop_pending(c, st); return rc; }
             HIP_TRY(hipStreamSynchronize(st));              // (plan.order is read by the copy until here)
             rc = flush_profile(c);
@@ -327,14 +420,12 @@ int sufsort_many_dev(const void *d_texts_v, const void *d_offsets_v, int32_t cou
     return DQ_OK;
 }
 
-// Host buffers in / out.  Runs of short and medium texts travel in chunks of whole texts: at most kManyChunkBytes of
-// text, its suffix arrays (4 bytes per text byte), offsets and work list on the device at a time, whatever the total,
-// and the medium launches' scratch blocks beside them.
-constexpr int64_t kManyChunkBytes = 64ll << 20;
-constexpr int32_t kManyChunkTexts = 1 << 20;
-
+// Host buffers in / out.  Runs of short and medium texts -- and of large ones, in a call that holds enough of them --
+// travel in chunks of whole texts: at most kManyChunkBytes of text, its suffix arrays (4 bytes per text byte), offsets
+// and work list on the device at a time, whatever the total, and the medium launches' scratch blocks and the
+// segmented sort's workspace beside them.
 int sufsort_many_host(const uint8_t *texts, const int64_t *offsets, int32_t count, int32_t *sas, int32_t device,
-                      int64_t *shared_out)
+                      int64_t *shared_out, bool large_by_default)
 {
     if (shared_out) *shared_out = 0;
     if (count < 0) return fail(DQ_ERR_BAD_ARGS, "negative count");
@@ -345,7 +436,14 @@ int sufsort_many_host(const uint8_t *texts, const int64_t *offsets, int32_t coun
     int dev = 0;
     rc = resolve_device(device, &dev);
     if (rc != DQ_OK) return rc;
-    const int64_t listed_max = many_listed_max();
+    // (large texts sit in chunks only where the call holds enough of them for a segmented sort: a call with fewer is
+    // cut into chunks, and sorted, exactly as it was without the class)
+    int64_t listed_max = many_listed_max(large_by_default);
+    if (listed_max > kMidMaxN) {
+        int64_t larges = 0;
+        for (int32_t i = 0; i < count; ++i) larges += is_large(offsets[i + 1] - offsets[i]) ? 1 : 0;
+        if (larges < large_many_min()) listed_max = mid_many_on() ? (int64_t)kMidMaxN : many_short_max();
+    }
     const bool one_by_one = many_one_by_one();
     std::vector<int64_t> rel;
     for (int32_t i = 0; i < count;) {
@@ -368,8 +466,8 @@ int sufsort_many_host(const uint8_t *texts, const int64_t *offsets, int32_t coun
         if (bytes > 0) {
             rel.resize((size_t)cnt + 1);
             for (int32_t j = 0; j <= cnt; ++j) rel[(size_t)j] = offsets[i + j] - base;
-            const ManyPlan plan = plan_many(rel.data(), 0, cnt);
-            if (plan.listed() > 0) {
+            const ManyPlan plan = plan_many(rel.data(), 0, cnt, large_by_default);
+            if (plan.shared()) {
                 SlotLease lease(dev, 0);
                 DeviceCtx &c = *lease.c;
                 rc = init_ctx(c, dev);
@@ -377,8 +475,8 @@ int sufsort_many_host(const uint8_t *texts, const int64_t *offsets, int32_t coun
                 hipStream_t st = c.stream;
                 const size_t b_text = align_up((size_t)bytes + 64), b_sa = align_up((size_t)bytes * sizeof(int32_t)),
                              b_off = align_up(rel.size() * sizeof(int64_t)), b_ctl = many_ctl_bytes(plan.listed()),
-                             b_scratch = many_scratch_bytes(c, plan);
-                rc = ensure_ws(c, b_text + b_sa + b_off + b_ctl + b_scratch);
+                             b_scratch = many_scratch_bytes(c, plan), b_large = many_large_bytes(plan, rel.data());
+                rc = ensure_ws(c, b_text + b_sa + b_off + b_ctl + b_scratch + b_large);
                 if (rc != DQ_OK) return rc;
                 uint8_t *d_text = reinterpret_cast<uint8_t *>(c.ws);
                 int32_t *d_sa = reinterpret_cast<int32_t *>(c.ws + b_text);
@@ -390,6 +488,8 @@ int sufsort_many_host(const uint8_t *texts, const int64_t *offsets, int32_t coun
                     const int r = launch_many(c, st, plan, d_text, d_off, d_sa, c.ws + b_text + b_sa + b_off,
                                               c.ws + b_text + b_sa + b_off + b_ctl);
                     if (r != DQ_OK) return r;
+                    const int rl = launch_large(c, st, plan, rel.data(), d_text, d_sa, c.ws + b_text + b_sa + b_off + b_ctl + b_scratch);
+                    if (rl != DQ_OK) return rl;
                     // (one checked step: a failure must not leave a copy into the caller's array in flight behind the return)
                     const hipError_t e1 = hipMemcpyAsync(sas + base, d_sa, (size_t)bytes * sizeof(int32_t), hipMemcpyDeviceToHost, st);
                     const hipError_t e2 = hipStreamSynchronize(st);
@@ -402,7 +502,7 @@ int sufsort_many_host(const uint8_t *texts, const int64_t *offsets, int32_t coun
             } else
                 many_account(plan, true, 0);
             if (shared_out) *shared_out += plan.shorts();
-            // the chunk's medium texts that were too few for a launch: singly, into their place (the slot is given back).
+            // the chunk's medium (and large) texts that were too few for a launch: singly, into their place (the slot is given back).
             // They travelled with the chunk -- its extent is decided before its plan -- so their bytes were copied in for
             // nothing and the copy back laid never-written workspace words over their segments; the sorts below
             // overwrite them.  (A failing call leaves the caller's array undefined, here as in every chunk after the

@@ -118,7 +118,9 @@ class HipSuffixSort:
     # -- many short texts in shared launches (no counterpart in ISuffixSort: the reference sorts file by file) -------
     def SortMany(self, texts):
         """Suffix arrays of many independent texts, the short ones (up to 8192 bytes) in shared launches -- and those
-        of up to 65 536 bytes too, where the call holds enough of them (``_abi.last_many_info()`` tells what happened).
+        of up to 65 536 bytes too, where the call holds enough of them; longer texts are sorted one after another (the segmented
+        sort that takes texts of 65 537 to 4 194 304 bytes together, dq_large_many.h, is off by default)
+        (``_abi.last_many_info()`` and ``_abi.last_many_large_info()`` tell what happened).
 
         ``SortMany([t0, t1, ...])`` -- bytes-like objects / numpy uint8 arrays -- returns a list of int32 arrays, each
         what ``Sort(t)`` returns (``dq_sufsort_hip_many_i32``).  ``SortMany((texts_tensor, offsets_tensor))`` -- a

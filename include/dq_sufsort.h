@@ -80,23 +80,35 @@ int32_t dq_sufsort_hip_batch_i32(int32_t count, const uint8_t *const *texts, con
  * grid take text after text, longest first, until none is left.  Texts of 8193 .. 65 536 bytes ("medium") do the same
  * in launches of their own (mid_many_kernel: one workgroup per text, its ranks in LDS, its sort buffers in a scratch
  * block in device memory), where a call -- in the host form: a chunk -- holds enough of them to beat the device sorter.
+ * Texts of 65 537 .. 4 194 304 bytes ("large") can be sorted TOGETHER: laid back to back, in one segmented
+ * prefix-doubling sort per batch of at most 64 MiB of them (dq_large_many.h), whose launches and host round trips follow
+ * the longest repeat of the batch instead of the number of its texts.  That class is OFF BY DEFAULT -- no timing of it is
+ * recorded yet (dq_small_many.h: kLargeManyByDefault) -- and such texts are sorted singly; the debug flag
+ * DQ_LARGE_MANY_MIN = the fewest large texts of a call or chunk that share a sort switches it on.
  * Layout: the texts lie back to back in one buffer; offsets[count + 1] (int64, offsets[0] == 0, never decreasing) says
  * where each begins, text j being bytes offsets[j] .. offsets[j + 1] - 1.  The suffix arrays come back to back in
  * the same layout: sas[offsets[j] + i] is the i-th suffix of text j COUNTED FROM THE START OF TEXT j -- each segment
  * is exactly what dq_sufsort_hip_i32 returns for that text alone (n = 0, 1, 2 included).  Nothing outside the
  * segments is written.  The total may exceed 2^31 bytes; each text is limited to 2^31-1 (32-bit indices only).
- * The call is total: a text longer than 65 536 bytes, and a medium one that has too few companions, is sorted by the
- * device sorter, one after another ("singly"), into its place.
+ * The call is total: a text longer than 65 536 bytes (with the large class on: longer than 4 194 304 bytes, or a large
+ * one with too few companions), and a medium one that has too few companions, is sorted by the device sorter, one after
+ * another ("singly"), into its place.
  * Errors, all before any device use in the host form: count < 0, a NULL pointer with count > 0, offsets[0] != 0,
  * decreasing offsets -> DQ_ERR_BAD_ARGS; a text of 2^31 bytes or more -> DQ_ERR_TOO_LARGE.  count == 0 is a no-op.
- *   dq_sufsort_hip_many_i32      host pointers.  Runs of texts of up to 65 536 bytes are copied in, sorted and copied
+ *   dq_sufsort_hip_many_i32      host pointers.  Runs of texts of up to 65 536 bytes -- with the large class on, up to
+ *                                4 194 304 in a call that holds enough large texts -- are copied in, sorted and copied
  *                                out in chunks of whole texts (64 MiB of text at most: 5 bytes of device memory per
  *                                chunk byte, whatever the total, and with medium texts up to 320 MiB of scratch blocks:
- *                                1.25 MiB per resident workgroup); no host staging: the copies read and write the
+ *                                1.25 MiB per resident workgroup; with the large class on the segmented sort's workspace: 33
+ *                                bytes per byte of the batch's large text -- compact text, two (key, suffix) lists,
+ *                                rank and suffix arrays -- and at most 4 more for the radix passes' status words,
+ *                                2.3 GiB for a full batch); no host staging: the copies read and write the
  *                                caller's buffers.
  *   dq_sufsort_hip_many_dev_i32  device pointers on `device` (d_offsets too: the library fetches it once to plan the
  *                                launches, and checks it before it launches anything); work on `stream` (NULL = the
- *                                library's), returns after the stream has drained. */
+ *                                library's), returns after the stream has drained.  With the large class on, large
+ *                                texts are gathered from where they lie, batch after batch, through the same
+ *                                workspace per byte. */
 int32_t dq_sufsort_hip_many_i32(const uint8_t *texts, const int64_t *offsets, int32_t count, int32_t *sas,
                                 int32_t device);
 int32_t dq_sufsort_hip_many_dev_i32(const void *d_texts, const void *d_offsets, int32_t count, void *d_sas,
@@ -160,7 +172,8 @@ int64_t dq_bsdiff_patch_bound(int64_t n, int64_t m);
  * old + new, 262 144 pairs), the old files are sorted by the launches of dq_sufsort_hip_many_dev_i32, the anchors of
  * every pair are found by one workgroup per pair (nobody waits for anybody), host threads turn them into the raw
  * streams, all bzip2 blocks of the chunk are transformed by one dq_sufsort_hip_many_i32-style sort (blocks of doubled
- * length 8193 .. 65 536 in its medium launches, where there are enough) and host threads frame the patches.
+ * length 8193 .. 65 536 in its medium launches where there are enough; longer blocks one after another: the large
+ * class of the many-texts call is OFF in this call) and host threads frame the patches.
  * The anchor step has two classes of pairs, one launch each per chunk where the class has pairs: SHORT, both files of
  * at most 8192 bytes (anchor_many_kernel, everything in LDS), and MEDIUM, a file above 8192 bytes
  * (anchor_mid_many_kernel: both files in LDS, the suffix array read from device memory).
@@ -284,7 +297,7 @@ void dq_sufsort_hip_release(void);
 #define DQ_K_SPLIT_PASS          20   /* dq_split_round0.h: split_pass_kernel, round 0 as a sample sort: text -> pairs by top bucket (1+12), pairs -> bucket slots (12+12) */
 #define DQ_K_SPLIT_FINISH        21   /* bucket_finish_kernel: every bucket sorted by its 64-bit keys inside LDS, 12+12           */
 #define DQ_K_SPLIT_AUX           22   /* sample, splitter tables, top-bucket histogram (1 B/text byte), plans, scans, overflow placement */
-#define DQ_K_SMALL_MANY          23   /* small_many_kernel / mid_many_kernel: many short / medium texts, one workgroup each, in one launch per length class; elements = texts, 5 B/text byte */
+#define DQ_K_SMALL_MANY          23   /* small_many_kernel / mid_many_kernel: many short / medium texts, one workgroup each, in one launch per length class; elements = texts, 5 B/text byte; and the segmented sort's own kernels (dq_large_many.h) */
 #define DQ_K_COUNT               24
 
 /* 0 off, 1 every kernel, 2 only radix_rank_kernel, 100 + c only category c (cheapest: the timed region) */
@@ -323,10 +336,12 @@ int32_t dq_last_diff_many_info(int64_t *info, int32_t count);
 
 /* Shape of the shared sorts of the last outermost dq_sufsort_hip_many_i32 / _many_dev_i32 / dq_sufsort_hip_batch_i32 /
  * dq_bsdiff_create_many on this thread, summed over every shared sort that call made and reset when such a call
- * starts; `count` entries (6 are defined, further ones read 0; a NULL array is DQ_ERR_BAD_ARGS): texts sorted in the
+ * starts; `count` entries (9 are defined, further ones read 0; a NULL array is DQ_ERR_BAD_ARGS): texts sorted in the
  * short classes' launches; texts sorted in medium launches; texts of 8193 .. 65 536 bytes sorted singly (fewer than the
  * threshold in their call or chunk, or the medium class switched off); texts above 65 536 bytes sorted singly; launches
- * of mid_many_kernel; bytes of per-workgroup scratch carved for them.  After dq_sufsort_hip_batch_i32 only the first
+ * of mid_many_kernel; bytes of per-workgroup scratch carved for them; [6] texts of 65 537 .. 4 194 304 bytes sorted in
+ * segmented sorts (those that were not count in [3]); [7] segmented sorts run; [8] list lengths summed over all their
+ * rounds, round 0 counting the batch's bytes.  After dq_sufsort_hip_batch_i32 only the first
  * entry is filled, the others read 0: that call shares launches among its inputs of up to 8192 bytes only. */
 int32_t dq_last_many_info(int64_t *info, int32_t count);
 
