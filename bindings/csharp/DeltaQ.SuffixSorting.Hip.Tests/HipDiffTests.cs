@@ -88,6 +88,34 @@ public sealed class HipDiffTests
     }
 
     [Fact]
+    public void OneOldManyNewInSharedLaunches()
+    {
+        // dq_bsdiff_index_diff_many: runs of 40 and 61 short new files share a launch of the anchor kernel each (32 files
+        // are the fewest that do), the file above 65 536 bytes between them goes through Create's path; every patch is Create's
+        byte[] oldData = RandomBytes(1 << 20, 3);
+        using var index = new HipDiffIndex(oldData);
+        var news = new List<ReadOnlyMemory<byte>>();
+        for (int k = 0; k < 100; k++)
+        {
+            news.Add(oldData.Skip(10_000 * k).Take(100 + 600 * k).Concat(RandomBytes(k, k)).ToArray());
+        }
+
+        news.Insert(40, oldData.Take(70_000).ToArray());
+        news.Add(Array.Empty<byte>());
+        byte[][] patches = index.CreateMany(news);
+        long[] info = HipDiffIndex.LastIndexManyInfo();
+        Assert.Equal(9, info.Length);
+        Assert.Equal(101, info[0]);
+        Assert.Equal(1, info[1]);
+        Assert.Equal(2, info[2]);                                 // the long file splits the list into two runs
+        for (int j = 0; j < news.Count; j++)
+        {
+            Assert.Equal(index.Create(news[j].Span), patches[j]);
+            Assert.Equal(news[j].ToArray(), ManagedApply(oldData, patches[j]));
+        }
+    }
+
+    [Fact]
     public void ACloneOfAnIndexGivesTheSamePatchesAndOutlivesItsSource()
     {
         // dq_bsdiff_index_clone: text + suffix array + prefix table copied device to device (xGMI between the devices of a

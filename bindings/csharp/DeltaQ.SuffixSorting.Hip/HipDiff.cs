@@ -52,6 +52,13 @@ internal static unsafe class Native
     internal static extern int dq_bsdiff_index_diff(IntPtr index, byte* newData, long m, byte* patch, long cap, long* patchLen);
 
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern int dq_bsdiff_index_diff_many(IntPtr index, byte* news, long* newOffsets, int count, byte* patches,
+                                                         long* patchOffsets, long* patchLens);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern int dq_last_index_many_info(long* info, int count);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
     internal static extern int dq_bsdiff_index_clone(IntPtr index, int device, IntPtr* indexOut);
 
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
@@ -359,6 +366,84 @@ public sealed unsafe class HipDiffIndex : IDisposable
 
         Array.Resize(ref patch, checked((int)len));
         return patch;
+    }
+
+    /// <summary>
+    /// The patches of many new files against this index in one native call (dq_bsdiff_index_diff_many): new files of at
+    /// most 65 536 bytes share one kernel launch per chunk and their block sorts instead of costing a scan launch and up
+    /// to three block sorts each (where at least 32 of them follow one another), longer ones are diffed one after
+    /// another.  Entry j of the result is the patch <see cref="Create"/> returns for news[j].  The files are laid back to
+    /// back in managed buffers for the call and every file gets a slot of dq_bsdiff_patch_bound bytes, so the totals are
+    /// limited to what one array holds; callers with more split their list.
+    /// </summary>
+    public byte[][] CreateMany(IReadOnlyList<ReadOnlyMemory<byte>> news)
+    {
+        if (_index == IntPtr.Zero)
+        {
+            throw new ObjectDisposedException(nameof(HipDiffIndex));
+        }
+
+        int count = news.Count;
+        var result = new byte[count][];
+        if (count == 0)
+        {
+            return result;
+        }
+
+        var newOffsets = new long[count + 1];
+        var patchOffsets = new long[count + 1];
+        for (int j = 0; j < count; j++)
+        {
+            newOffsets[j + 1] = newOffsets[j] + news[j].Length;
+            patchOffsets[j + 1] = patchOffsets[j] + Native.dq_bsdiff_patch_bound(_old.Length, news[j].Length);
+        }
+
+        if (newOffsets[count] > Array.MaxLength || patchOffsets[count] > Array.MaxLength)
+        {
+            throw new ArgumentException("the files and patch slots of one CreateMany call must each total less than 2^31 bytes");
+        }
+
+        // (at least one element each: the native side wants non-null pointers whenever there are files)
+        byte[] flatNew = new byte[Math.Max(newOffsets[count], 1)];
+        byte[] patches = new byte[Math.Max(patchOffsets[count], 1)];
+        var lens = new long[count];
+        for (int j = 0; j < count; j++)
+        {
+            news[j].Span.CopyTo(flatNew.AsSpan((int)newOffsets[j], news[j].Length));
+        }
+
+        fixed (byte* pNews = flatNew)
+        fixed (long* pNewOffsets = newOffsets)
+        fixed (byte* pPatches = patches)
+        fixed (long* pPatchOffsets = patchOffsets)
+        fixed (long* pLens = lens)
+        {
+            Native.Check(Native.dq_bsdiff_index_diff_many(_index, pNews, pNewOffsets, count, pPatches, pPatchOffsets, pLens),
+                         nameof(Native.dq_bsdiff_index_diff_many));
+        }
+
+        for (int j = 0; j < count; j++)
+        {
+            result[j] = patches.AsSpan((int)patchOffsets[j], (int)lens[j]).ToArray();
+        }
+
+        return result;
+    }
+
+    /// <summary>
+    /// Shape of the last CreateMany of an index on this thread (dq_last_index_many_info): new files through shared
+    /// launches, files diffed one by one, launches of the anchor kernel, bzip2 blocks sorted in shared launches, blocks
+    /// sorted singly, then microseconds per phase (copies + anchor kernel, host emission, block sorts, framing).
+    /// </summary>
+    public static long[] LastIndexManyInfo()
+    {
+        var info = new long[9];
+        fixed (long* p = info)
+        {
+            Native.Check(Native.dq_last_index_many_info(p, info.Length), nameof(Native.dq_last_index_many_info));
+        }
+
+        return info;
     }
 
     public void Dispose()

@@ -48,6 +48,7 @@ EXPORTS = (
     "dq_bsdiff_create", "dq_bsdiff_patch_bound", "dq_bsdiff_scan_i32", "dq_bspatch_apply",
     "dq_bsdiff_create_many", "dq_last_diff_many_info",
     "dq_bsdiff_index_create", "dq_bsdiff_index_clone", "dq_bsdiff_index_buffers", "dq_bsdiff_index_diff", "dq_bsdiff_index_free",
+    "dq_bsdiff_index_diff_many", "dq_last_index_many_info",
     "dq_sufsort_hip_workspace_bytes", "dq_sufsort_hip_workspace_plan", "dq_sufsort_hip_release",
     "dq_profile_enable", "dq_profile_reset", "dq_profile_get", "dq_profile_kernel_name",
     "dq_profile_category_count",
@@ -149,6 +150,10 @@ def load() -> ctypes.CDLL:
     L.dq_bsdiff_index_clone.argtypes = [vp, i32, ctypes.POINTER(vp)]
     L.dq_bsdiff_index_buffers.restype = i32
     L.dq_bsdiff_index_buffers.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i64)]
+    L.dq_bsdiff_index_diff_many.restype = i32
+    L.dq_bsdiff_index_diff_many.argtypes = [vp, vp, vp, i32, vp, vp, vp]
+    L.dq_last_index_many_info.restype = i32
+    L.dq_last_index_many_info.argtypes = [ctypes.POINTER(i64), i32]
     L.dq_bsdiff_index_diff.restype = i32
     L.dq_bsdiff_index_diff.argtypes = [vp, vp, i64, vp, i64, ctypes.POINTER(i64)]
     L.dq_bsdiff_index_free.restype = None
@@ -242,6 +247,16 @@ def last_diff_many_info() -> dict:
             "single_block_sorts": v[4], "sort_old_ms": v[5] / 1e3, "anchor_ms": v[6] / 1e3, "emit_ms": v[7] / 1e3,
             "block_sort_ms": v[8] / 1e3, "frame_ms": v[9] / 1e3, "medium_block_sorts": last_many_info()["medium_texts"],
             "medium_pairs": v[10], "medium_anchor_launches": v[11]}
+
+
+def last_index_many_info() -> dict:
+    """Shape of the last dq_bsdiff_index_diff_many on this thread (dq_last_index_many_info)."""
+    L = load()
+    v = (ctypes.c_int64 * 9)()
+    check(L.dq_last_index_many_info(v, 9))
+    return {"shared_files": v[0], "single_files": v[1], "anchor_launches": v[2], "shared_block_sorts": v[3],
+            "single_block_sorts": v[4], "anchor_ms": v[5] / 1e3, "emit_ms": v[6] / 1e3, "block_sort_ms": v[7] / 1e3,
+            "frame_ms": v[8] / 1e3}
 
 
 def last_many_info() -> dict:

@@ -218,7 +218,8 @@ def diff_many_distributed(old, news: Optional[Sequence], *, sorter_factory: Opti
     input order (``patch[j]`` turns ``old`` into ``news[j]``; other ranks return ``None``).
 
     ``sorter_factory()`` -> object with ``Sort(text)`` (default ``HipSuffixSort``);
-    ``index_factory(old_bytes, text_tensor, sa_tensor)`` -> object with ``Create(new) -> bytes`` (default
+    ``index_factory(old_bytes, text_tensor, sa_tensor)`` -> object with ``Create(new) -> bytes`` and, optionally,
+    ``CreateMany(news) -> list[bytes]``, which is then given the rank's whole share in one call (default
     ``DiffIndex`` on the tensors as they arrived: device tensors under ``nccl``, uploaded once under ``gloo``).
     The CPU tests inject both.
     """
@@ -280,7 +281,11 @@ def diff_many_distributed(old, news: Optional[Sequence], *, sorter_factory: Opti
             index = DiffIndex(old_np, device_text=text_t, device_sa=sa_t)
         else:
             index = index_factory(old_np, text_t, sa_t)
-        patches = {j: index.Create(mine[j]) for j in plan[rank]}
+        share = list(plan[rank])
+        if hasattr(index, "CreateMany"):               # short files of the share in shared launches
+            patches = dict(zip(share, index.CreateMany([mine[j] for j in share])))
+        else:
+            patches = {j: index.Create(mine[j]) for j in share}
         if hasattr(index, "close"):
             index.close()
     except Exception as e:                      # noqa: BLE001 -- reported to every rank below

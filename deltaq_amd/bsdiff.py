@@ -153,6 +153,25 @@ class DiffIndex:
                                                   ctypes.byref(ln)))
         return buf[:ln.value].tobytes()
 
+    def CreateMany(self, news) -> list:
+        """``[self.Create(n) for n in news]`` in one call (dq_bsdiff_index_diff_many): new files of at most 65 536 bytes
+        share their device launches, where at least 32 of them follow one another; longer ones are diffed one by
+        one.  ``news``: a sequence of bytes-likes or uint8 arrays."""
+        N = [_as_text(x) for x in news]
+        count = len(N)
+        if count == 0:
+            return []
+        n_off = np.zeros(count + 1, np.int64)
+        np.cumsum([a.size for a in N], out=n_off[1:])
+        n_flat = np.ascontiguousarray(np.concatenate(N) if int(n_off[-1]) else np.zeros(1, np.uint8), dtype=np.uint8)
+        p_off = np.zeros(count + 1, np.int64)
+        np.cumsum([self._lib.dq_bsdiff_patch_bound(self._old.size, a.size) for a in N], out=p_off[1:])
+        buf = np.empty(int(p_off[-1]), dtype=np.uint8)          # (slots of the bound's size: pages no patch reaches stay untouched)
+        lens = np.full(count, -1, np.int64)
+        _abi.check(self._lib.dq_bsdiff_index_diff_many(self._h, n_flat.ctypes.data, n_off.ctypes.data, count, buf.ctypes.data,
+                                                       p_off.ctypes.data, lens.ctypes.data))
+        return [buf[int(p_off[j]):int(p_off[j]) + int(lens[j])].tobytes() for j in range(count)]
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             self._lib.dq_bsdiff_index_free(self._h)

@@ -508,6 +508,20 @@ int32_t dq_bsdiff_index_diff(const void *index, const uint8_t *new_data, int64_t
     }
 }
 
+int32_t dq_bsdiff_index_diff_many(const void *index, const uint8_t *news, const int64_t *new_offsets, int32_t count,
+                                  uint8_t *patches, const int64_t *patch_offsets, int64_t *patch_lens)
+{
+    EnvScope scope;
+    for (int64_t &x : t_many_info) x = 0;
+    try {
+        return diff_index_many(index, news, new_offsets, count, patches, patch_offsets, patch_lens);
+    } catch (const std::bad_alloc &) {
+        return fail(DQ_ERR_OOM, "bsdiff: host allocation failed");
+    } catch (const std::exception &e) {            // nothing may propagate through the C ABI
+        return fail(DQ_ERR_HIP, e.what());
+    }
+}
+
 void dq_bsdiff_index_free(void *index)
 {
     if (!index) return;
@@ -666,6 +680,13 @@ int32_t dq_device_numa_node(int32_t device)
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) return -1;
     return device_numa_node(device);
+}
+
+int32_t dq_last_index_many_info(int64_t *info, int32_t count)
+{
+    if (!info || count < 0) return fail(DQ_ERR_BAD_ARGS, "null info array");
+    for (int32_t k = 0; k < count; ++k) info[k] = k < 9 ? t_index_many_info[k] : 0;
+    return DQ_OK;
 }
 
 int32_t dq_last_diff_many_info(int64_t *info, int32_t count)

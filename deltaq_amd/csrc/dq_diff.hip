@@ -8,6 +8,7 @@
 #include "dq_anchor_scan.h"
 #include "dq_anchor_many.h"
 #include "dq_anchor_mid_many.h"
+#include "dq_anchor_index_many.h"
 #include "dq_scan_wait.h"
 #include "dq_bz2.h"
 #include "dq_bsdiff.h"
@@ -1477,6 +1478,135 @@ struct ManyPair {
     std::string err;
 };
 
+// The files of a chunk as phases 3 - 5 see them: `cnt` new files, each against its own old file (ooff set: pair j is
+// olds[ooff[j] .. ooff[j + 1])) or all against one shared old file of n bytes (ooff null).  Host pointers; the offset
+// arrays are the caller's, already advanced to the chunk's first file.
+struct ManyFiles {
+    const uint8_t *olds;
+    const int64_t *ooff;
+    int64_t n;
+    const uint8_t *news;
+    const int64_t *noff;
+    const uint8_t *old_at(int64_t j) const { return ooff ? olds + ooff[j] : olds; }
+    int64_t old_len(int64_t j) const { return ooff ? ooff[j + 1] - ooff[j] : n; }
+    int64_t new_len(int64_t j) const { return noff[j + 1] - noff[j]; }
+};
+
+// Phases 3 - 5 of a chunk (see above), from the anchor lists the device wrote: list j is anch[2 * rel_a[j] ..) with
+// counts[j] pairs, searches[j] its Search calls.  The patches into `out`; info[0 .. 5) += blocks sorted in shared
+// launches, blocks sorted singly, microseconds of host emission, block sorts, host framing.
+int diff_many_finish(const ManyFiles &f, int32_t cnt, const int32_t *anch, const int64_t *rel_a, const int32_t *counts,
+                     const int32_t *searches, int dev, std::vector<ManyPair> &out, int64_t *info)
+{
+    // ---- 3. the raw streams of every pair, and their blocks up to the transform
+    auto t0 = std::chrono::steady_clock::now();
+    diff_many_parallel(cnt, [&](int64_t j) {
+        ManyPair &w = out[(size_t)j];
+        try {
+            const int64_t n = f.old_len(j), m = f.new_len(j);
+            const int32_t k = counts[j];
+            if (k < 0 || k > rel_a[j + 1] - rel_a[j]) { w.rc = DQ_ERR_HIP; w.err = "anchor list of a pair is not complete"; return; }
+            const uint8_t *old = f.old_at(j), *nw = f.news + f.noff[j];
+            bsdiff::TripleEmitter em(old, n, nw, m, w.raw);
+            const int32_t *a = anch + 2 * rel_a[j];
+            for (int32_t t = 0; t < k; ++t) {
+                const int64_t pair[2] = {a[2 * t], a[2 * t + 1]};
+                // (the emitter indexes both files with them: never beyond what the kernel may have written)
+                if (pair[0] < em.prev.at || pair[0] > m || pair[1] < 0 || pair[1] > n || (t == k - 1) != (pair[0] == m)) {
+                    w.rc = DQ_ERR_HIP; w.err = "anchor list of a pair is out of range"; return;
+                }
+                bsdiff::scan_from_anchors(em, pair, 1);
+            }
+            if ((m > 0) != (k > 0)) { w.rc = DQ_ERR_HIP; w.err = "anchor list of a pair is not complete"; return; }
+            w.raw.searches = searches[j];
+            const std::vector<uint8_t> *src[3] = {&w.raw.ctrl, &w.raw.diff, &w.raw.extra};
+            for (int s = 0; s < 3; ++s) {
+                w.enc[s].reset(new bz2::StreamEncoder(bz2::DoubledSorter()));
+                w.enc[s]->hold_blocks();
+                w.enc[s]->feed(src[s]->data(), src[s]->size(), true);
+            }
+        } catch (const std::exception &e) {
+            w.rc = DQ_ERR_OOM; w.err = std::string("bsdiff: ") + e.what();
+        }
+    });
+    for (ManyPair &w : out)
+        if (w.rc != DQ_OK) { t_err = w.err; return w.rc; }
+    info[2] += us_since(t0);
+
+    // ---- 4. every block of the chunk in one shared sort
+    t0 = std::chrono::steady_clock::now();
+    // (the short blocks first, then the medium ones, then those above kMidMaxN: sufsort_many_host shares launches among
+    // neighbours in its list, and a block above kMidMaxN between two others would end a chunk of them)
+    std::vector<int64_t> blen;                             // doubled length per block, pairs' order
+    for (ManyPair &w : out) {
+        w.first_block = (int64_t)blen.size();
+        for (int s = 0; s < 3; ++s)
+            for (size_t b = 0; b < w.enc[s]->block_count(); ++b) blen.push_back(2 * (int64_t)w.enc[s]->block_rle(b).size());
+    }
+    const int64_t nblocks = (int64_t)blen.size();
+    if (nblocks > 0x7fffffffLL) return fail(DQ_ERR_TOO_LARGE, "too many bzip2 blocks in one chunk");
+    std::vector<int64_t> bplace((size_t)nblocks), boff((size_t)nblocks + 1, 0);      // block -> place in the list; the list's offsets
+    {
+        int64_t at = 0;
+        for (int pass = 0; pass < 3; ++pass)
+            for (int64_t b = 0; b < nblocks; ++b)
+                if ((blen[(size_t)b] > kSmallMaxN) + (blen[(size_t)b] > kMidMaxN) == pass) {
+                    bplace[(size_t)b] = at;
+                    boff[(size_t)at + 1] = boff[(size_t)at] + blen[(size_t)b];
+                    ++at;
+                }
+    }
+    std::vector<uint8_t> btext((size_t)boff.back());
+    std::vector<int32_t> bsa((size_t)boff.back());
+    diff_many_parallel(cnt, [&](int64_t j) {
+        ManyPair &w = out[(size_t)j];
+        int64_t at = w.first_block;
+        for (int s = 0; s < 3; ++s)
+            for (size_t b = 0; b < w.enc[s]->block_count(); ++b)
+                bz2::double_block(w.enc[s]->block_rle(b), btext.data() + boff[(size_t)bplace[(size_t)at++]]);
+    });
+    int64_t shared = 0;
+    // Blocks above kMidMaxN doubled bytes reach the planner's large class (dq_large_many.h), but here it stays off unless
+    // DQ_LARGE_MANY_MIN asks for it: the block-sort phase has not been measured faster with it than with the one-by-one
+    // route, whose sorts get no hint either but run the device sorter's LDS group rounds (docs/ROUNDS.md, round 11).
+    const int rc = sufsort_many_host(btext.data(), boff.data(), (int32_t)nblocks, bsa.data(), dev, &shared, /*large_by_default=*/false);
+    if (rc != DQ_OK) return rc;
+    std::vector<uint8_t>().swap(btext);
+    info[0] += shared;
+    info[1] += nblocks - shared;
+    info[3] += us_since(t0);
+
+    // ---- 5. the blocks' bits, the streams, the patches
+    t0 = std::chrono::steady_clock::now();
+    diff_many_parallel(cnt, [&](int64_t j) {
+        ManyPair &w = out[(size_t)j];
+        try {
+            int64_t at = w.first_block;
+            std::vector<uint8_t> z[3];
+            for (int s = 0; s < 3; ++s) {
+                for (size_t b = 0; b < w.enc[s]->block_count(); ++b) w.enc[s]->encode_block_sorted(b, bsa.data() + boff[(size_t)bplace[(size_t)at++]]);
+                if (w.enc[s]->finish(z[s]) != 0) { w.rc = DQ_ERR_HIP; w.err = "bzip2 block transform failed"; return; }
+                w.enc[s].reset();
+            }
+            const int64_t m = f.new_len(j);
+            w.patch.assign((size_t)bsdiff::kHeaderSize, 0);                             // as frame_patch
+            bsdiff::write_packed_long(&w.patch[0], bsdiff::kSignature);
+            bsdiff::write_packed_long(&w.patch[8], (int64_t)z[0].size());
+            bsdiff::write_packed_long(&w.patch[16], (int64_t)z[1].size());
+            bsdiff::write_packed_long(&w.patch[24], m);
+            w.patch.reserve(w.patch.size() + z[0].size() + z[1].size() + z[2].size());
+            for (int s = 0; s < 3; ++s) w.patch.insert(w.patch.end(), z[s].begin(), z[s].end());
+            w.raw = bsdiff::RawStreams{};
+        } catch (const std::exception &e) {
+            w.rc = DQ_ERR_OOM; w.err = std::string("bsdiff: ") + e.what();
+        }
+    });
+    for (ManyPair &w : out)
+        if (w.rc != DQ_OK) { t_err = w.err; return w.rc; }
+    info[4] += us_since(t0);
+    return DQ_OK;
+}
+
 // pairs [first, first + cnt) of the call, no file above kMidMaxN bytes: their patches into `out`
 int diff_many_chunk(const uint8_t *olds, const int64_t *ooff, const uint8_t *news, const int64_t *noff, int32_t first, int32_t cnt,
                     int dev, DeviceBuf &buf, std::vector<ManyPair> &out)
@@ -1599,114 +1729,16 @@ int diff_many_chunk(const uint8_t *olds, const int64_t *ooff, const uint8_t *new
         if (rc != DQ_OK) return rc;
     }
     const int32_t *counts = back.data() + 2 * anchors, *searches = counts + cnt;
-
-    // ---- 3. the raw streams of every pair, and their blocks up to the transform
-    auto t0 = std::chrono::steady_clock::now();
-    diff_many_parallel(cnt, [&](int64_t j) {
-        ManyPair &w = out[(size_t)j];
-        try {
-            const int64_t n = rel_o[j + 1] - rel_o[j], m = rel_n[j + 1] - rel_n[j];
-            const int32_t k = counts[j];
-            if (k < 0 || k > rel_a[j + 1] - rel_a[j]) { w.rc = DQ_ERR_HIP; w.err = "anchor list of a pair is not complete"; return; }
-            const uint8_t *old = olds + ooff[first + j], *nw = news + noff[first + j];
-            bsdiff::TripleEmitter em(old, n, nw, m, w.raw);
-            const int32_t *a = back.data() + 2 * rel_a[j];
-            for (int32_t t = 0; t < k; ++t) {
-                const int64_t pair[2] = {a[2 * t], a[2 * t + 1]};
-                // (the emitter indexes both files with them: never beyond what the kernel may have written)
-                if (pair[0] < em.prev.at || pair[0] > m || pair[1] < 0 || pair[1] > n || (t == k - 1) != (pair[0] == m)) {
-                    w.rc = DQ_ERR_HIP; w.err = "anchor list of a pair is out of range"; return;
-                }
-                bsdiff::scan_from_anchors(em, pair, 1);
-            }
-            if ((m > 0) != (k > 0)) { w.rc = DQ_ERR_HIP; w.err = "anchor list of a pair is not complete"; return; }
-            w.raw.searches = searches[j];
-            const std::vector<uint8_t> *src[3] = {&w.raw.ctrl, &w.raw.diff, &w.raw.extra};
-            for (int s = 0; s < 3; ++s) {
-                w.enc[s].reset(new bz2::StreamEncoder(bz2::DoubledSorter()));
-                w.enc[s]->hold_blocks();
-                w.enc[s]->feed(src[s]->data(), src[s]->size(), true);
-            }
-        } catch (const std::exception &e) {
-            w.rc = DQ_ERR_OOM; w.err = std::string("bsdiff: ") + e.what();
-        }
-    });
-    for (ManyPair &w : out)
-        if (w.rc != DQ_OK) { t_err = w.err; return w.rc; }
-    t_diff_many_info[7] += us_since(t0);
-
-    // ---- 4. every block of the chunk in one shared sort
-    t0 = std::chrono::steady_clock::now();
-    // (the short blocks first, then the medium ones, then those above kMidMaxN: sufsort_many_host shares launches among
-    // neighbours in its list, and a block above kMidMaxN between two others would end a chunk of them)
-    std::vector<int64_t> blen;                             // doubled length per block, pairs' order
-    for (ManyPair &w : out) {
-        w.first_block = (int64_t)blen.size();
-        for (int s = 0; s < 3; ++s)
-            for (size_t b = 0; b < w.enc[s]->block_count(); ++b) blen.push_back(2 * (int64_t)w.enc[s]->block_rle(b).size());
-    }
-    const int64_t nblocks = (int64_t)blen.size();
-    if (nblocks > 0x7fffffffLL) return fail(DQ_ERR_TOO_LARGE, "too many bzip2 blocks in one chunk");
-    std::vector<int64_t> bplace((size_t)nblocks), boff((size_t)nblocks + 1, 0);      // block -> place in the list; the list's offsets
-    {
-        int64_t at = 0;
-        for (int pass = 0; pass < 3; ++pass)
-            for (int64_t b = 0; b < nblocks; ++b)
-                if ((blen[(size_t)b] > kSmallMaxN) + (blen[(size_t)b] > kMidMaxN) == pass) {
-                    bplace[(size_t)b] = at;
-                    boff[(size_t)at + 1] = boff[(size_t)at] + blen[(size_t)b];
-                    ++at;
-                }
-    }
-    std::vector<uint8_t> btext((size_t)boff.back());
-    std::vector<int32_t> bsa((size_t)boff.back());
-    diff_many_parallel(cnt, [&](int64_t j) {
-        ManyPair &w = out[(size_t)j];
-        int64_t at = w.first_block;
-        for (int s = 0; s < 3; ++s)
-            for (size_t b = 0; b < w.enc[s]->block_count(); ++b)
-                bz2::double_block(w.enc[s]->block_rle(b), btext.data() + boff[(size_t)bplace[(size_t)at++]]);
-    });
-    int64_t shared = 0;
-    // Blocks above kMidMaxN doubled bytes reach the planner's large class (dq_large_many.h), but here it stays off unless
-    // DQ_LARGE_MANY_MIN asks for it: the block-sort phase has not been measured faster with it than with the one-by-one
-    // route, whose sorts get no hint either but run the device sorter's LDS group rounds (docs/ROUNDS.md, round 11).
-    const int rc = sufsort_many_host(btext.data(), boff.data(), (int32_t)nblocks, bsa.data(), dev, &shared, /*large_by_default=*/false);
-    if (rc != DQ_OK) return rc;
-    std::vector<uint8_t>().swap(btext);
-    t_diff_many_info[3] += shared;
-    t_diff_many_info[4] += nblocks - shared;
-    t_diff_many_info[8] += us_since(t0);
-
-    // ---- 5. the blocks' bits, the streams, the patches
-    t0 = std::chrono::steady_clock::now();
-    diff_many_parallel(cnt, [&](int64_t j) {
-        ManyPair &w = out[(size_t)j];
-        try {
-            int64_t at = w.first_block;
-            std::vector<uint8_t> z[3];
-            for (int s = 0; s < 3; ++s) {
-                for (size_t b = 0; b < w.enc[s]->block_count(); ++b) w.enc[s]->encode_block_sorted(b, bsa.data() + boff[(size_t)bplace[(size_t)at++]]);
-                if (w.enc[s]->finish(z[s]) != 0) { w.rc = DQ_ERR_HIP; w.err = "bzip2 block transform failed"; return; }
-                w.enc[s].reset();
-            }
-            const int64_t m = rel_n[j + 1] - rel_n[j];
-            w.patch.assign((size_t)bsdiff::kHeaderSize, 0);                             // as frame_patch
-            bsdiff::write_packed_long(&w.patch[0], bsdiff::kSignature);
-            bsdiff::write_packed_long(&w.patch[8], (int64_t)z[0].size());
-            bsdiff::write_packed_long(&w.patch[16], (int64_t)z[1].size());
-            bsdiff::write_packed_long(&w.patch[24], m);
-            w.patch.reserve(w.patch.size() + z[0].size() + z[1].size() + z[2].size());
-            for (int s = 0; s < 3; ++s) w.patch.insert(w.patch.end(), z[s].begin(), z[s].end());
-            w.raw = bsdiff::RawStreams{};
-        } catch (const std::exception &e) {
-            w.rc = DQ_ERR_OOM; w.err = std::string("bsdiff: ") + e.what();
-        }
-    });
-    for (ManyPair &w : out)
-        if (w.rc != DQ_OK) { t_err = w.err; return w.rc; }
-    t_diff_many_info[9] += us_since(t0);
-    return DQ_OK;
+    // ---- 3. - 5. on the host and in the shared block sort
+    const ManyFiles files{olds, ooff + first, 0, news, noff + first};
+    int64_t info[5] = {0, 0, 0, 0, 0};
+    const int rc = diff_many_finish(files, cnt, back.data(), rel_a, counts, searches, dev, out, info);
+    t_diff_many_info[3] += info[0];
+    t_diff_many_info[4] += info[1];
+    t_diff_many_info[7] += info[2];
+    t_diff_many_info[8] += info[3];
+    t_diff_many_info[9] += info[4];
+    return rc;
 }
 }  // namespace
 
@@ -1888,6 +1920,195 @@ int diff_index_diff(const void *index, const uint8_t *nw, int64_t m, std::vector
         if (rc != DQ_OK) return rc;
     }
     return frame_patch(raw, m, ix->dev, patch, &framer);                            // (framing overlaps the next caller's scan loop)
+}
+
+
+// ---- many new files against one index in shared launches (dq_bsdiff_index_diff_many) --------------------------------
+// A new file of a few KiB costs diff_index_diff a copy, the launch of the persistent anchor scan, its polls and up to
+// three block sorts, all under the device's diff_mu.  Here the new files of a call travel in chunks of whole files -- at
+// most kDiffManyChunkBytes of new bytes, kDiffManyChunkPairs files -- and a chunk goes through dq_bsdiff_create_many's
+// phases without the first: there is nothing to sort, the index has (old, suffix array, prefix table) on the device.
+//   2. new files, offsets, work list and counter to the device; ONE launch of anchor_index_many_kernel
+//      (dq_anchor_index_many.h: a workgroup per new file, new in LDS, old and the suffix array read from device
+//      memory); anchor lists, counts and searches back.  The device's diff_mu is held for this phase only.
+//   3. - 5. diff_many_finish, as for the pairs of dq_bsdiff_create_many, every emitter on the index's host copy of old.
+// Device memory per chunk: new + diff_many_anchor_room(m) = m / 8 + 2 pairs of int32 per file for the anchor lists (a byte
+// per byte of new + 16) + 28 bytes per file (two offsets, order, count, searches), freed on return.
+constexpr int64_t kIndexManyMax = kMidMaxN;                // longest new file of the shared launches
+// Fewest new files of a chunk that share a launch; below it they go one by one through diff_index_diff's path, where the
+// whole device works on one file.  The rule is kDiffMidManyMin's: twice the largest crossing of the sweep of
+// tools/kbench/index_diff_many.py (1 .. 512 files of 4 / 16 / 64 KiB, similar and unrelated, old files of 1 and 16 MiB),
+// rounded up to a power of two, at least 8.  The largest crossing is 16 files (files of 16 and 64 KiB unrelated to old; 2
+// to 8 files in the other rows), and every row has one, so the class keeps its upper length
+// (profiles/r12/index_diff_many.json, docs/ROUNDS.md round 12).
+constexpr int32_t kIndexManyMin = 32;
+// Workgroup size of the launch: 256 threads, two workgroups per CU, measured against 512 threads, one per CU
+// (dq_anchor_index_many.h has the figures; DQ_INDEX_MANY_THREADS chooses the other one for a measurement).
+constexpr int kIndexManyThreads = 256;
+
+namespace {
+// new files [first, first + cnt) of the call, none above kIndexManyMax bytes: their patches into `out`
+int diff_index_many_chunk(const DiffIndex &ix, const uint8_t *news, const int64_t *noff, int32_t first, int32_t cnt, DeviceBuf &buf,
+                          std::vector<ManyPair> &out)
+{
+    const int dev = ix.dev;
+    HIP_TRY(hipSetDevice(dev));
+    const int64_t n_base = noff[first], n_bytes = noff[first + cnt] - n_base;
+    out.clear();
+    out.resize((size_t)cnt);
+    // offsets relative to the chunk; anchor room per file; the work list, longest first
+    std::vector<int64_t> off((size_t)(cnt + 1) * 2);
+    int64_t *rel_n = off.data(), *rel_a = rel_n + cnt + 1;
+    rel_a[0] = 0;
+    for (int32_t j = 0; j <= cnt; ++j) {
+        rel_n[j] = noff[first + j] - n_base;
+        if (j > 0) rel_a[j] = rel_a[j - 1] + diff_many_anchor_room(rel_n[j] - rel_n[j - 1]);
+    }
+    const int64_t anchors = rel_a[cnt];
+    std::vector<int32_t> order((size_t)cnt);
+    for (int32_t j = 0; j < cnt; ++j) order[(size_t)j] = j;
+    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return rel_n[a + 1] - rel_n[a] > rel_n[b + 1] - rel_n[b]; });
+    std::vector<int32_t> back((size_t)anchors * 2 + (size_t)cnt * 2);
+    const int threads = flags().index_many_threads.value_or(kIndexManyThreads);
+    if (threads != 256 && threads != 512) return fail(DQ_ERR_BAD_ARGS, "DQ_INDEX_MANY_THREADS is 256 or 512");
+
+    // ---- 2. on the device, scan loops of other callers taking their turns before and after
+    {
+        const auto t0 = std::chrono::steady_clock::now();
+        const size_t b_new = align_up((size_t)n_bytes + 64), b_off = align_up(off.size() * sizeof(int64_t)),
+                     b_order = align_up(order.size() * sizeof(int32_t)), b_next = 256, b_back = align_up(back.size() * sizeof(int32_t));
+        int rc = buf.need(b_new + b_off + b_order + b_next + b_back);
+        if (rc != DQ_OK) return rc;
+        char *q = buf.p;
+        uint8_t *d_new = reinterpret_cast<uint8_t *>(q); q += b_new;
+        int64_t *d_off = reinterpret_cast<int64_t *>(q); q += b_off;
+        int32_t *d_order = reinterpret_cast<int32_t *>(q); q += b_order;
+        uint32_t *d_next = reinterpret_cast<uint32_t *>(q); q += b_next;
+        int32_t *d_back = reinterpret_cast<int32_t *>(q);
+        std::lock_guard<std::mutex> one_diff(ctx0(dev).diff_mu);
+        SlotLease lease(dev, 0);
+        DeviceCtx &c = *lease.c;
+        rc = init_ctx(c, dev);
+        if (rc != DQ_OK) return rc;
+        hipStream_t st = c.stream;
+        auto run = [&]() -> int {
+            if (n_bytes > 0) HIP_TRY(hipMemcpyAsync(d_new, news + n_base, (size_t)n_bytes, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(d_off, off.data(), off.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(d_order, order.data(), order.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemsetAsync(d_next, 0, b_next, st));
+            // workgroups the device holds at once (a wrong answer costs time only: nobody waits for anybody)
+            int *groups = &c.anchor_index_many_groups[threads == 256 ? 0 : 1];
+            if (*groups <= 0) {
+                int per_cu = 0, ncu = 0;
+                const hipError_t e = threads == 256
+                    ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, anchor_index_many_kernel<256>, 256, 0)
+                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, anchor_index_many_kernel<512>, 512, 0);
+                if (e != hipSuccess || per_cu <= 0) per_cu = 1;
+                if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
+                *groups = per_cu * ncu;
+            }
+            const int grid = std::min<int>(cnt, *groups);
+            Launcher L{c, st, g_prof_on.load()};
+            const uint8_t *d_old = reinterpret_cast<const uint8_t *>(ix.d_old);
+            const int32_t *d_sa = reinterpret_cast<const int32_t *>(ix.d_sa), *d_tab = reinterpret_cast<const int32_t *>(ix.d_tab);
+            const int64_t *d_noff = d_off, *d_aoff = d_off + (cnt + 1);
+            int32_t *d_counts = d_back + 2 * anchors, *d_searches = d_counts + cnt;
+            if (threads == 256) {
+                LAUNCH(L, DQ_K_MATCH_SEARCH, n_bytes, n_bytes,
+                       hipLaunchKernelGGL(anchor_index_many_kernel<256>, dim3((unsigned)grid), dim3(256), 0, st, d_old, ix.n, d_sa, d_tab,
+                                          ix.pk, d_new, d_noff, d_aoff, d_order, cnt, d_next, d_back, d_counts, d_searches));
+            } else {
+                LAUNCH(L, DQ_K_MATCH_SEARCH, n_bytes, n_bytes,
+                       hipLaunchKernelGGL(anchor_index_many_kernel<512>, dim3((unsigned)grid), dim3(512), 0, st, d_old, ix.n, d_sa, d_tab,
+                                          ix.pk, d_new, d_noff, d_aoff, d_order, cnt, d_next, d_back, d_counts, d_searches));
+            }
+            t_index_many_info[2] += 1;
+            const hipError_t e1 = hipMemcpyAsync(back.data(), d_back, back.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+            const hipError_t e2 = hipStreamSynchronize(st);
+            HIP_TRY(e1 != hipSuccess ? e1 : e2);
+            return flush_profile(c);
+        };
+        rc = run();
+        if (rc != DQ_OK) { drop_pending(c, c.stream); return rc; }
+        t_index_many_info[5] += us_since(t0);
+    }
+    // ---- 3. - 5. on the host and in the shared block sort
+    const ManyFiles files{ix.old, nullptr, ix.n, news, noff + first};
+    const int32_t *counts = back.data() + 2 * anchors, *searches = counts + cnt;
+    int64_t info[5] = {0, 0, 0, 0, 0};
+    const int rc = diff_many_finish(files, cnt, back.data(), rel_a, counts, searches, dev, out, info);
+    t_index_many_info[3] += info[0];
+    t_index_many_info[4] += info[1];
+    t_index_many_info[6] += info[2];
+    t_index_many_info[7] += info[3];
+    t_index_many_info[8] += info[4];
+    return rc;
+}
+}  // namespace
+
+int diff_index_many(const void *index, const uint8_t *news, const int64_t *noff, int32_t count, uint8_t *patches, const int64_t *poff,
+                    int64_t *plens)
+{
+    for (int64_t &x : t_index_many_info) x = 0;
+    if (!index) return fail(DQ_ERR_BAD_ARGS, "null index");
+    if (count < 0) return fail(DQ_ERR_BAD_ARGS, "negative count");
+    if (count == 0) return DQ_OK;
+    if (!news || !noff || !patches || !poff || !plens) return fail(DQ_ERR_BAD_ARGS, "null buffer");
+    for (const int64_t *off : {noff, poff})
+        if (off[0] != 0) return fail(DQ_ERR_BAD_ARGS, "offsets[0] must be 0");
+    for (int32_t j = 0; j < count; ++j)
+        if (noff[j + 1] < noff[j] || poff[j + 1] < poff[j]) return fail(DQ_ERR_BAD_ARGS, "offsets must not decrease");
+    for (int32_t j = 0; j < count; ++j)
+        if (noff[j + 1] - noff[j] > 0x7fffffffLL)
+            return fail(DQ_ERR_TOO_LARGE, "the BSDIFF40 path takes files below 2 GiB (int indices, as the reference)");
+    for (int32_t j = 0; j < count; ++j) plens[j] = -1;
+    const DiffIndex *ix = static_cast<const DiffIndex *>(index);
+
+    auto deliver = [&](int32_t j, const std::vector<uint8_t> &patch) -> int {
+        if ((int64_t)patch.size() > poff[j + 1] - poff[j]) return fail(DQ_ERR_BAD_ARGS, "output buffer too small (see dq_bsdiff_patch_bound)");
+        if (!patch.empty()) memcpy(patches + poff[j], patch.data(), patch.size());
+        plens[j] = (int64_t)patch.size();
+        return DQ_OK;
+    };
+    const bool one_by_one = flags().no_index_many.value_or(0) != 0;
+    const int64_t many_min = flags().index_many_min.value_or(kIndexManyMin);
+    auto is_listed = [&](int32_t j) { return !one_by_one && noff[j + 1] - noff[j] <= kIndexManyMax; };
+    DeviceBuf buf;
+    buf.dev = ix->dev;
+    std::vector<ManyPair> done;
+    auto single = [&](int32_t j) -> int {
+        // the one-file path, into the file's slot (it reports under its own dq_last_diff_info)
+        std::vector<uint8_t> patch;
+        int r = diff_index_diff(index, news + noff[j], noff[j + 1] - noff[j], patch);
+        if (r == DQ_OK) r = deliver(j, patch);
+        if (r == DQ_OK) t_index_many_info[1] += 1;
+        return r;
+    };
+    for (int32_t i = 0; i < count;) {
+        if (!is_listed(i)) {
+            const int rc = single(i);
+            if (rc != DQ_OK) return rc;
+            ++i;
+            continue;
+        }
+        int32_t e = i;
+        while (e < count && e - i < kDiffManyChunkPairs && is_listed(e) && noff[e + 1] - noff[i] <= kDiffManyChunkBytes) ++e;
+        if (e - i >= many_min) {
+            int rc = diff_index_many_chunk(*ix, news, noff, i, e - i, buf, done);
+            if (rc != DQ_OK) return rc;
+            t_index_many_info[0] += e - i;
+            for (int32_t j = i; j < e && rc == DQ_OK; ++j) rc = deliver(j, done[(size_t)(j - i)].patch);
+            if (rc != DQ_OK) return rc;
+        } else {
+            // too few files for a launch of their own: one by one, in input order
+            for (int32_t j = i; j < e; ++j) {
+                const int rc = single(j);
+                if (rc != DQ_OK) return rc;
+            }
+        }
+        i = e;
+    }
+    return DQ_OK;
 }
 
 void diff_index_delete(void *index)

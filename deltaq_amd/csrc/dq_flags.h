@@ -36,6 +36,9 @@ struct Flags {
     std::optional<int> no_diff_many;        // DQ_NO_DIFF_MANY: 1: every pair of dq_bsdiff_create_many through the one-pair path
     std::optional<int> no_diff_mid_many;    // DQ_NO_DIFF_MID_MANY: 1: no medium class of its pairs (a file above 8192 bytes: singly)
     std::optional<int> diff_mid_many_min;   // DQ_DIFF_MID_MANY_MIN: fewest medium pairs of a chunk that share its launches, >= 1
+    std::optional<int> no_index_many;       // DQ_NO_INDEX_MANY: 1: every new file of dq_bsdiff_index_diff_many through the one-file path
+    std::optional<int> index_many_min;      // DQ_INDEX_MANY_MIN: fewest new files of a chunk that share its launch, >= 1
+    std::optional<int> index_many_threads;  // DQ_INDEX_MANY_THREADS: 256 | 512, workgroup size of anchor_index_many_kernel
     bool no_list_buffers = false;           // DQ_NO_LIST_BUFFERS: the workspace without the third list buffer
     bool text_copy = false;                 // DQ_TEXT_COPY: copy the text in front instead of in the first pass
     bool assume_doubled = false;            // DQ_ASSUME_DOUBLED: every even-length text is block + block
@@ -134,6 +137,9 @@ inline Flags read_flags()
     f.no_diff_many = num("DQ_NO_DIFF_MANY", 0, 1);
     f.no_diff_mid_many = num("DQ_NO_DIFF_MID_MANY", 0, 1);
     f.diff_mid_many_min = num("DQ_DIFF_MID_MANY_MIN", 1);
+    f.no_index_many = num("DQ_NO_INDEX_MANY", 0, 1);
+    f.index_many_min = num("DQ_INDEX_MANY_MIN", 1);
+    f.index_many_threads = num("DQ_INDEX_MANY_THREADS");
     f.no_list_buffers = on("DQ_NO_LIST_BUFFERS");
     f.text_copy = on("DQ_TEXT_COPY");
     f.assume_doubled = on("DQ_ASSUME_DOUBLED");

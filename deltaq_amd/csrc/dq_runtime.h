@@ -43,6 +43,7 @@ inline thread_local int64_t t_info[3] = {0, 0, 0};
 // asked again exactly, launches of the device's anchor scan that were given back to the host loop, workgroups of its grid
 inline thread_local int64_t t_diff_info[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
 inline thread_local int64_t t_diff_many_info[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};     // dq_last_diff_many_info
+inline thread_local int64_t t_index_many_info[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};              // dq_last_index_many_info
 // the shared sorts of the last outermost many-texts / batch / many-pairs call on this thread (dq_last_many_info): texts in
 // the short classes' launches, texts in medium launches, medium-length texts sorted singly, texts above kMidMaxN sorted
 // singly, launches of mid_many_kernel, bytes of per-workgroup scratch carved for them, texts sorted in segmented sorts
@@ -110,6 +111,7 @@ struct DeviceCtx {
     int many_groups[5] = {0, 0, 0, 0, 0};   // workgroups of small_many_kernel (3 length classes) and mid_many_kernel (2) the device holds at once (0: not asked yet)
     int anchor_many_groups = 0;         // ... and of anchor_many_kernel (dq_anchor_many.h)
     int anchor_mid_many_groups = 0;     // ... and of anchor_mid_many_kernel (dq_anchor_mid_many.h)
+    int anchor_index_many_groups[2] = {0, 0};   // ... and of anchor_index_many_kernel at 256 and 512 threads (dq_anchor_index_many.h)
     hipStream_t stream = nullptr;
     char *ws = nullptr;
     size_t ws_bytes = 0;
@@ -444,6 +446,8 @@ int diff_index_new(const uint8_t *old, int64_t n, int32_t device, const void *d_
 int diff_index_clone(const void *index, int32_t device, void **index_out);
 int diff_index_buffers(const void *index, const void **d_old, const void **d_sa, int64_t *n);
 int diff_index_diff(const void *index, const uint8_t *nw, int64_t m, std::vector<uint8_t> &patch);
+int diff_index_many(const void *index, const uint8_t *news, const int64_t *new_offsets, int32_t count, uint8_t *patches,
+                    const int64_t *patch_offsets, int64_t *patch_lens);
 void diff_index_delete(void *index);
 
 }  // namespace dq

@@ -212,7 +212,8 @@ int32_t dq_bsdiff_create_many(const uint8_t *olds, const int64_t *old_offsets, c
  *   dq_bsdiff_index_buffers  the device pointers (for a broadcast / gather by the caller) and n.
  *   dq_bsdiff_index_diff     = Diff.Create(oldData, newData, ...) without its suffix sort.  Thread-safe: scan loops of
  *                            concurrent callers take turns on the device, their bzip2 framing overlaps.
- *   dq_bsdiff_index_free     releases the index (not the caller's buffers). */
+ *   dq_bsdiff_index_free     releases the index (not the caller's buffers).
+ *   dq_bsdiff_index_diff_many  below: many new files against one index in shared launches. */
 int32_t dq_bsdiff_index_create(const uint8_t *old_data, int64_t n, const void *d_old, const void *d_sa, int32_t device,
                                void **index_out);
 int32_t dq_bsdiff_index_clone(const void *index, int32_t device, void **index_out);
@@ -220,6 +221,41 @@ int32_t dq_bsdiff_index_buffers(const void *index, const void **d_old, const voi
 int32_t dq_bsdiff_index_diff(const void *index, const uint8_t *new_data, int64_t m, uint8_t *patch, int64_t cap,
                              int64_t *patch_len);
 void dq_bsdiff_index_free(void *index);
+
+/* ---- one old file, MANY new files in shared launches (a tree of small files against one base image) ---------------
+ * dq_bsdiff_index_diff_many: `count` new files against one index in one call.  Layout as dq_bsdiff_create_many without
+ * its old files: the new files back to back in `news` with an offsets array of count + 1 int64 entries (offsets[0] == 0,
+ * never decreasing); new file j is news[new_offsets[j] .. new_offsets[j + 1]).  patch_offsets[count + 1] gives every
+ * file its slot in `patches` (capacity patch_offsets[j + 1] - patch_offsets[j]; dq_bsdiff_patch_bound(n, m_j) always
+ * suffices), patch_lens[j] receives the length; nothing outside patches[patch_offsets[j] .. + patch_lens[j]) is written.
+ * Patch j is byte for byte what dq_bsdiff_index_diff(index, new_j) returns, empty files included; the old file is the
+ * index's, of any size below 2 GiB (0 included), the device is the index's.
+ * New files of at most 65 536 bytes share their launches: in chunks of whole files (at most 64 MiB of new bytes,
+ * 262 144 files), the anchors of every file of a chunk are found by ONE launch of anchor_index_many_kernel -- one
+ * workgroup per new file, nobody waits for anybody; the new file in LDS, the old file, its suffix array and the prefix
+ * table read where the index keeps them, in device memory --, host threads turn them into the raw streams, all bzip2
+ * blocks of the chunk are transformed by one dq_sufsort_hip_many_i32-style sort (the large class of the many-texts call
+ * is OFF in this call, as in dq_bsdiff_create_many) and host threads frame the patches.  Scan loops of other callers on
+ * the index's device take turns with the copies and the launch of a chunk only, not with its host phases or block sorts.
+ * A chunk with fewer than 32 such files is taken one file after another by dq_bsdiff_index_diff's path -- one workgroup
+ * on a file is not faster than the whole device on it, only many of them side by side are.  A chunk is a run of
+ * NEIGHBOURING files of the list: a longer file ends it, so short files share a launch only where 32 or more follow one
+ * another (as the pairs of dq_bsdiff_create_many).
+ * The call is total: a new file above 65 536 bytes (below 2 GiB) is diffed by dq_bsdiff_index_diff's path, one after
+ * another, into its slot.  Patches are delivered in input order whichever way a file went.
+ * Footprint per chunk -- device: new + 1 byte per byte of new (anchor lists: m / 8 + 2 pairs of int32 a file) + 44 bytes
+ * per file (offsets, work list, counts, searches, the lists' spare pairs), freed on return (the
+ * shared sort's own workspace stays with the library until dq_sufsort_hip_release); host: as dq_bsdiff_create_many.
+ * Errors found before any device use: a NULL index, count < 0, a NULL pointer with count > 0, offsets[0] != 0 or
+ * decreasing offsets in either array -> DQ_ERR_BAD_ARGS; a new file of 2^31 bytes or more -> DQ_ERR_TOO_LARGE.
+ * count == 0 with an index is a no-op.  A slot too small for its patch -> DQ_ERR_BAD_ARGS ("output buffer too small"),
+ * known only once the patch is.  The first failing file's code is returned: files before it have their patches and
+ * lengths, patch_lens of the others read -1.
+ * The call reports under dq_last_index_many_info; it resets and fills the thread's dq_last_many_info like every
+ * outermost many-texts call (its block sorts), leaves dq_last_diff_many_info alone, and a file that goes one by one
+ * leaves its dq_last_diff_info behind.  New API: the reference diffs one pair per Diff.Create call. */
+int32_t dq_bsdiff_index_diff_many(const void *index, const uint8_t *news, const int64_t *new_offsets, int32_t count,
+                                  uint8_t *patches, const int64_t *patch_offsets, int64_t *patch_lens);
 int32_t dq_bsdiff_scan_i32(const uint8_t *old_data, int64_t n, const uint8_t *new_data, int64_t m, int64_t *ctrl,
                            int64_t ctrl_cap, int64_t *nctrl, uint8_t *diff, int64_t *ndiff, uint8_t *extra, int64_t *nextra,
                            int64_t *stats, int32_t device);
@@ -334,8 +370,14 @@ int32_t dq_last_diff_info(int64_t *info, int32_t count);
  * launches (counted in [0] too); [11] launches of anchor_mid_many_kernel. */
 int32_t dq_last_diff_many_info(int64_t *info, int32_t count);
 
+/* Shape of the last dq_bsdiff_index_diff_many on this thread, reset when such a call starts; `count` entries (9 are
+ * defined, further ones read 0; a NULL array is DQ_ERR_BAD_ARGS): new files that went through shared launches; files
+ * diffed one by one; launches of anchor_index_many_kernel; bzip2 blocks sorted in shared launches; blocks sorted singly;
+ * [5..8] microseconds in each phase: copies + anchor kernel, host emission, block sorts, host framing. */
+int32_t dq_last_index_many_info(int64_t *info, int32_t count);
+
 /* Shape of the shared sorts of the last outermost dq_sufsort_hip_many_i32 / _many_dev_i32 / dq_sufsort_hip_batch_i32 /
- * dq_bsdiff_create_many on this thread, summed over every shared sort that call made and reset when such a call
+ * dq_bsdiff_create_many / dq_bsdiff_index_diff_many on this thread, summed over every shared sort that call made and reset when such a call
  * starts; `count` entries (9 are defined, further ones read 0; a NULL array is DQ_ERR_BAD_ARGS): texts sorted in the
  * short classes' launches; texts sorted in medium launches; texts of 8193 .. 65 536 bytes sorted singly (fewer than the
  * threshold in their call or chunk, or the medium class switched off); texts above 65 536 bytes sorted singly; launches
