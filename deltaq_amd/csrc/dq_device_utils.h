@@ -123,9 +123,10 @@ __device__ __forceinline__ T block_excl_sum(T v, T *tmp, T *total)
     return off + incl - v;
 }
 
-// Exclusive prefix max over the 256 threads of a workgroup; identity is -1 (the
-// values are non-negative indices).  One __syncthreads(); `tmp` as above.
-template <typename T>
+// Exclusive prefix max over the kWaves * 64 threads of a workgroup; identity is -1 (the
+// values are non-negative indices).  One __syncthreads(); `tmp` is kWaves words of LDS,
+// reusable as above.
+template <typename T, int kWaves = kWavesPerBlock>
 __device__ __forceinline__ T block_excl_max(T v, T *tmp)
 {
     const int l = lane_id();
@@ -136,7 +137,7 @@ __device__ __forceinline__ T block_excl_max(T v, T *tmp)
     if (l == 0) excl = (T)-1;
     __syncthreads();
 #pragma unroll
-    for (int i = 0; i < kWavesPerBlock; ++i) {
+    for (int i = 0; i < kWaves; ++i) {
         const T t = tmp[i];
         if (i < w) excl = t > excl ? t : excl;
     }

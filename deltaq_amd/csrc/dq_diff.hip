@@ -7,8 +7,6 @@
 #include "dq_match_search.h"
 #include "dq_anchor_scan.h"
 #include "dq_anchor_many.h"
-#include "dq_anchor_mid_many.h"
-#include "dq_anchor_index_many.h"
 #include "dq_scan_wait.h"
 #include "dq_bz2.h"
 #include "dq_bsdiff.h"
@@ -1397,8 +1395,8 @@ int frame_patch(const bsdiff::RawStreams &raw, int64_t m, int dev, std::vector<u
 // by all its pairs:
 //   1. old and new files and their offsets to the device; sufsort_many_dev on the old files (the suffix arrays stay
 //      there; old files above the short-text limit take its medium launches or, below its own threshold, its one-by-one route)
-//   2. the (cursor, hit_pos) list of every pair: anchor_many_kernel (dq_anchor_many.h) on the short pairs -- both files of
-//      at most kDiffManyMax bytes -- and anchor_mid_many_kernel (dq_anchor_mid_many.h) on the medium ones; the two
+//   2. the (cursor, hit_pos) list of every pair: anchor_many_kernel on the short pairs -- both files of at most kDiffManyMax
+//      bytes -- and anchor_mid_many_kernel on the medium ones (dq_anchor_many.h has both); the two
 //      launches go back to back on one stream, each with its own work list and counter; lists to the host
 //   3. host threads: TripleEmitter + scan_from_anchors per pair -> RawStreams; run-length pre-pass and CRC of the three
 //      streams (bz2::StreamEncoder with its blocks held back)
@@ -1492,12 +1490,33 @@ struct ManyFiles {
     int64_t new_len(int64_t j) const { return noff[j + 1] - noff[j]; }
 };
 
-// Phases 3 - 5 of a chunk (see above), from the anchor lists the device wrote: list j is anch[2 * rel_a[j] ..) with
-// counts[j] pairs, searches[j] its Search calls.  The patches into `out`; info[0 .. 5) += blocks sorted in shared
-// launches, blocks sorted singly, microseconds of host emission, block sorts, host framing.
-int diff_many_finish(const ManyFiles &f, int32_t cnt, const int32_t *anch, const int64_t *rel_a, const int32_t *counts,
-                     const int32_t *searches, int dev, std::vector<ManyPair> &out, int64_t *info)
+// What a chunk prepares for its anchor launches -- pairs [first, first + cnt) of a call (ooff set) or new files against
+// one index (ooff null): offsets relative to the chunk, the anchor room of every file, the work list (two lists in
+// one: the short pairs, then the medium ones, each longest new first; without ooff every file is in the first), what
+// comes back, and the carving of the call's one device allocation.
+struct ManyChunk {
+    int32_t cnt = 0, in_class[2] = {0, 0};
+    int64_t o_base = 0, o_bytes = 0, n_base = 0, n_bytes = 0, anchors = 0;
+    std::vector<int64_t> off;           // [rel_o,] rel_n, rel_a: cnt + 1 entries each
+    const int64_t *rel_a = nullptr;
+    std::vector<int32_t> order, back;   // back: the anchor lists (list j at 2 * rel_a[j]), then counts and searches per file
+    uint8_t *d_old = nullptr, *d_new = nullptr;
+    int32_t *d_sa = nullptr, *d_order = nullptr, *d_back = nullptr, *d_counts = nullptr, *d_searches = nullptr;
+    int64_t *d_off = nullptr;           // `off` as it is: d_noff and d_aoff point into it
+    const int64_t *d_noff = nullptr, *d_aoff = nullptr;
+    uint32_t *d_next = nullptr;         // 256 zeroed bytes: the counters of the work lists
+    std::chrono::steady_clock::time_point t_device;        // when the host's part of the preparation was over
+};
+
+// Phases 3 - 5 of a chunk (see above), from what the device wrote into k.back: list j has counts[j] pairs, searches[j]
+// its Search calls.  The patches into `out`; info[at[0 .. 5)] += blocks sorted in shared launches, blocks sorted singly,
+// microseconds of host emission, block sorts, host framing.
+int diff_many_finish(const ManyFiles &f, const ManyChunk &k, int dev, std::vector<ManyPair> &out, int64_t *info, std::array<int, 5> at)
 {
+    out.clear();
+    out.resize((size_t)k.cnt);
+    const int32_t cnt = k.cnt, *anch = k.back.data(), *counts = anch + 2 * k.anchors, *searches = counts + cnt;
+    const int64_t *rel_a = k.rel_a;
     // ---- 3. the raw streams of every pair, and their blocks up to the transform
     auto t0 = std::chrono::steady_clock::now();
     diff_many_parallel(cnt, [&](int64_t j) {
@@ -1531,7 +1550,7 @@ int diff_many_finish(const ManyFiles &f, int32_t cnt, const int32_t *anch, const
     });
     for (ManyPair &w : out)
         if (w.rc != DQ_OK) { t_err = w.err; return w.rc; }
-    info[2] += us_since(t0);
+    info[at[2]] += us_since(t0);
 
     // ---- 4. every block of the chunk in one shared sort
     t0 = std::chrono::steady_clock::now();
@@ -1572,9 +1591,9 @@ int diff_many_finish(const ManyFiles &f, int32_t cnt, const int32_t *anch, const
     const int rc = sufsort_many_host(btext.data(), boff.data(), (int32_t)nblocks, bsa.data(), dev, &shared, /*large_by_default=*/false);
     if (rc != DQ_OK) return rc;
     std::vector<uint8_t>().swap(btext);
-    info[0] += shared;
-    info[1] += nblocks - shared;
-    info[3] += us_since(t0);
+    info[at[0]] += shared;
+    info[at[1]] += nblocks - shared;
+    info[at[3]] += us_since(t0);
 
     // ---- 5. the blocks' bits, the streams, the patches
     t0 = std::chrono::steady_clock::now();
@@ -1603,7 +1622,81 @@ int diff_many_finish(const ManyFiles &f, int32_t cnt, const int32_t *anch, const
     });
     for (ManyPair &w : out)
         if (w.rc != DQ_OK) { t_err = w.err; return w.rc; }
-    info[4] += us_since(t0);
+    info[at[4]] += us_since(t0);
+    return DQ_OK;
+}
+
+// Workgroups of `kernel` the device holds at once, asked once per context (*cache).  A wrong answer costs time only:
+// nobody waits for anybody.
+template <typename Kernel>
+int resident_groups(int *cache, Kernel kernel, int threads, int dev)
+{
+    if (*cache <= 0) {
+        int per_cu = 0, ncu = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, 0) != hipSuccess || per_cu <= 0) per_cu = 1;
+        if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
+        *cache = per_cu * ncu;
+    }
+    return *cache;
+}
+
+int many_chunk_prepare(ManyChunk &k, const int64_t *ooff, const int64_t *noff, int32_t first, int32_t cnt, DeviceBuf &buf)
+{
+    k.cnt = cnt;
+    k.n_base = noff[first];
+    k.n_bytes = noff[first + cnt] - k.n_base;
+    k.o_base = ooff ? ooff[first] : 0;
+    k.o_bytes = ooff ? ooff[first + cnt] - k.o_base : 0;
+    const size_t each = (size_t)cnt + 1;
+    k.off.resize(each * (ooff ? 3 : 2));
+    int64_t *rel_o = ooff ? k.off.data() : nullptr, *rel_n = k.off.data() + (ooff ? each : 0), *rel_a = rel_n + each;
+    rel_a[0] = 0;
+    for (int32_t j = 0; j <= cnt; ++j) {
+        if (ooff) rel_o[j] = ooff[first + j] - k.o_base;
+        rel_n[j] = noff[first + j] - k.n_base;
+        if (j > 0) rel_a[j] = rel_a[j - 1] + diff_many_anchor_room(rel_n[j] - rel_n[j - 1]);
+    }
+    k.rel_a = rel_a;
+    k.anchors = rel_a[cnt];
+    auto klass = [&](int32_t j) { return !ooff || std::max(rel_o[j + 1] - rel_o[j], rel_n[j + 1] - rel_n[j]) <= kDiffManyMax ? 0 : 1; };
+    k.order.resize((size_t)cnt);
+    for (int32_t j = 0; j < cnt; ++j) k.order[(size_t)j] = j;
+    std::stable_sort(k.order.begin(), k.order.end(), [&](int32_t a, int32_t b) {
+        const int ka = klass(a), kb = klass(b);
+        return ka != kb ? ka < kb : rel_n[a + 1] - rel_n[a] > rel_n[b + 1] - rel_n[b];
+    });
+    for (int32_t j = 0; j < cnt; ++j) ++k.in_class[klass(j)];
+    k.back.resize((size_t)k.anchors * 2 + (size_t)cnt * 2);
+
+    const size_t b_old = ooff ? align_up((size_t)k.o_bytes + 64) : 0, b_new = align_up((size_t)k.n_bytes + 64),
+                 b_sa = ooff ? align_up((size_t)k.o_bytes * sizeof(int32_t) + 64) : 0, b_off = align_up(k.off.size() * sizeof(int64_t)),
+                 b_order = align_up(k.order.size() * sizeof(int32_t)), b_next = 256, b_back = align_up(k.back.size() * sizeof(int32_t));
+    k.t_device = std::chrono::steady_clock::now();
+    const int rc = buf.need(b_old + b_new + b_sa + b_off + b_order + b_next + b_back);
+    if (rc != DQ_OK) return rc;
+    char *q = buf.p;
+    k.d_old = reinterpret_cast<uint8_t *>(q); q += b_old;
+    k.d_new = reinterpret_cast<uint8_t *>(q); q += b_new;
+    k.d_sa = reinterpret_cast<int32_t *>(q); q += b_sa;
+    k.d_off = reinterpret_cast<int64_t *>(q); q += b_off;
+    k.d_order = reinterpret_cast<int32_t *>(q); q += b_order;
+    k.d_next = reinterpret_cast<uint32_t *>(q); q += b_next;
+    k.d_back = reinterpret_cast<int32_t *>(q);
+    k.d_noff = k.d_off + (rel_n - k.off.data());
+    k.d_aoff = k.d_off + (rel_a - k.off.data());
+    k.d_counts = k.d_back + 2 * k.anchors;
+    k.d_searches = k.d_counts + cnt;
+    return DQ_OK;
+}
+
+// the chunk's files (olds null: none), offsets and work list to the device, its counters zeroed; nothing is waited for
+int many_chunk_upload(const ManyChunk &k, const uint8_t *olds, const uint8_t *news, hipStream_t st)
+{
+    if (olds && k.o_bytes > 0) HIP_TRY(hipMemcpyAsync(k.d_old, olds + k.o_base, (size_t)k.o_bytes, hipMemcpyHostToDevice, st));
+    if (k.n_bytes > 0) HIP_TRY(hipMemcpyAsync(k.d_new, news + k.n_base, (size_t)k.n_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(k.d_off, k.off.data(), k.off.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(k.d_order, k.order.data(), k.order.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(k.d_next, 0, 256, st));
     return DQ_OK;
 }
 
@@ -1612,63 +1705,24 @@ int diff_many_chunk(const uint8_t *olds, const int64_t *ooff, const uint8_t *new
                     int dev, DeviceBuf &buf, std::vector<ManyPair> &out)
 {
     HIP_TRY(hipSetDevice(dev));                            // (the chunk's allocation below is this device's)
-    const int64_t o_base = ooff[first], n_base = noff[first];
-    const int64_t o_bytes = ooff[first + cnt] - o_base, n_bytes = noff[first + cnt] - n_base;
-    out.clear();
-    out.resize((size_t)cnt);
-    // offsets relative to the chunk; anchor room per pair; the work list, longest new first
-    std::vector<int64_t> off((size_t)(cnt + 1) * 3);
-    int64_t *rel_o = off.data(), *rel_n = rel_o + cnt + 1, *rel_a = rel_n + cnt + 1;
-    rel_a[0] = 0;
-    for (int32_t j = 0; j <= cnt; ++j) {
-        rel_o[j] = ooff[first + j] - o_base;
-        rel_n[j] = noff[first + j] - n_base;
-        if (j > 0) rel_a[j] = rel_a[j - 1] + diff_many_anchor_room(rel_n[j] - rel_n[j - 1]);
-    }
-    const int64_t anchors = rel_a[cnt];
-    // (two lists in one: the short pairs, then the medium ones)
-    auto klass = [&](int32_t j) { return std::max(rel_o[j + 1] - rel_o[j], rel_n[j + 1] - rel_n[j]) <= kDiffManyMax ? 0 : 1; };
-    std::vector<int32_t> order((size_t)cnt);
-    for (int32_t j = 0; j < cnt; ++j) order[(size_t)j] = j;
-    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
-        const int ka = klass(a), kb = klass(b);
-        return ka != kb ? ka < kb : rel_n[a + 1] - rel_n[a] > rel_n[b + 1] - rel_n[b];
-    });
-    int32_t in_class[2] = {0, 0};
-    for (int32_t j = 0; j < cnt; ++j) ++in_class[klass(j)];
-    // what comes back: anchor lists, then counts and searches per pair
-    std::vector<int32_t> back((size_t)anchors * 2 + (size_t)cnt * 2);
+    ManyChunk k;
+    int rc = many_chunk_prepare(k, ooff, noff, first, cnt, buf);
+    if (rc != DQ_OK) return rc;
 
     // ---- 1. + 2. on the device.  (A device context is leased for the copies and again for the kernel, never across the
     // sort in between, which leases its own: two callers holding one each and waiting for a second would wait for ever.)
     {
-        const size_t b_old = align_up((size_t)o_bytes + 64), b_new = align_up((size_t)n_bytes + 64),
-                     b_sa = align_up((size_t)o_bytes * sizeof(int32_t) + 64), b_off = align_up(off.size() * sizeof(int64_t)),
-                     b_order = align_up(order.size() * sizeof(int32_t)), b_next = 256, b_back = align_up(back.size() * sizeof(int32_t));
-        int rc = buf.need(b_old + b_new + b_sa + b_off + b_order + b_next + b_back);
-        if (rc != DQ_OK) return rc;
-        char *q = buf.p;
-        uint8_t *d_old = reinterpret_cast<uint8_t *>(q); q += b_old;
-        uint8_t *d_new = reinterpret_cast<uint8_t *>(q); q += b_new;
-        int32_t *d_sa = reinterpret_cast<int32_t *>(q); q += b_sa;
-        int64_t *d_off = reinterpret_cast<int64_t *>(q); q += b_off;
-        int32_t *d_order = reinterpret_cast<int32_t *>(q); q += b_order;
-        uint32_t *d_next = reinterpret_cast<uint32_t *>(q); q += b_next;
-        int32_t *d_back = reinterpret_cast<int32_t *>(q);
         auto upload = [&](DeviceCtx &c, hipStream_t st) -> int {
             const auto t0 = std::chrono::steady_clock::now();
-            if (o_bytes > 0) HIP_TRY(hipMemcpyAsync(d_old, olds + o_base, (size_t)o_bytes, hipMemcpyHostToDevice, st));
-            if (n_bytes > 0) HIP_TRY(hipMemcpyAsync(d_new, news + n_base, (size_t)n_bytes, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(d_off, off.data(), off.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(d_order, order.data(), order.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemsetAsync(d_next, 0, b_next, st));
+            const int r = many_chunk_upload(k, olds, news, st);
+            if (r != DQ_OK) return r;
             HIP_TRY(hipStreamSynchronize(st));
             t_diff_many_info[6] += us_since(t0);
             return DQ_OK;
         };
         auto sort_olds = [&]() -> int {
             const auto t0 = std::chrono::steady_clock::now();
-            const int r = sufsort_many_dev(d_old, d_off, cnt, d_sa, dev, nullptr);     // Diff.cs:90 for every pair
+            const int r = sufsort_many_dev(k.d_old, k.d_off, cnt, k.d_sa, dev, nullptr);       // Diff.cs:90 for every pair
             if (r != DQ_OK) return r;
             HIP_TRY(hipSetDevice(dev));
             HIP_TRY(hipDeviceSynchronize());               // (whichever streams its routes used)
@@ -1677,38 +1731,28 @@ int diff_many_chunk(const uint8_t *olds, const int64_t *ooff, const uint8_t *new
         };
         auto scan = [&](DeviceCtx &c, hipStream_t st) -> int {
             const auto t0 = std::chrono::steady_clock::now();
-            // workgroups the device holds at once (a wrong answer costs time only: nobody waits for anybody)
-            auto resident = [&](int *groups, auto kernel, int threads) {
-                if (*groups > 0) return;
-                int per_cu = 0, ncu = 0;
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, 0) != hipSuccess || per_cu <= 0) per_cu = 1;
-                if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
-                *groups = per_cu * ncu;
-            };
             Launcher L{c, st, g_prof_on.load()};
-            const int64_t *d_noff = d_off + (cnt + 1), *d_aoff = d_off + 2 * (cnt + 1);
-            int32_t *d_counts = d_back + 2 * anchors, *d_searches = d_counts + cnt;
             // (a class's share of the bytes is not known here: the profile books all of them on the first launch)
-            int64_t prof_units = n_bytes, prof_bytes = o_bytes * 5 + n_bytes;
-            if (in_class[0] > 0) {
-                resident(&c.anchor_many_groups, anchor_many_kernel, kAmThreads);
-                const int grid = std::min<int>(in_class[0], c.anchor_many_groups);
+            int64_t prof_units = k.n_bytes, prof_bytes = k.o_bytes * 5 + k.n_bytes;
+            if (k.in_class[0] > 0) {
+                const int grid = std::min<int>(k.in_class[0], resident_groups(&c.anchor_many_groups, anchor_many_kernel, kAmThreads, dev));
                 LAUNCH(L, DQ_K_MATCH_SEARCH, prof_units, prof_bytes,
-                       hipLaunchKernelGGL(anchor_many_kernel, dim3((unsigned)grid), dim3(kAmThreads), 0, st, d_old, d_off, d_sa, d_new,
-                                          d_noff, d_aoff, d_order, in_class[0], d_next, d_back, d_counts, d_searches));
+                       hipLaunchKernelGGL(anchor_many_kernel, dim3((unsigned)grid), dim3(kAmThreads), 0, st, k.d_old, k.d_off, k.d_sa, k.d_new,
+                                          k.d_noff, k.d_aoff, k.d_order, k.in_class[0], k.d_next, k.d_back, k.d_counts, k.d_searches));
                 prof_units = prof_bytes = 0;
                 t_diff_many_info[2] += 1;
             }
-            if (in_class[1] > 0) {
-                resident(&c.anchor_mid_many_groups, anchor_mid_many_kernel, kAmmThreads);
-                const int grid = std::min<int>(in_class[1], c.anchor_mid_many_groups);
+            if (k.in_class[1] > 0) {
+                const int grid = std::min<int>(k.in_class[1],
+                                               resident_groups(&c.anchor_mid_many_groups, anchor_mid_many_kernel, kAmMidThreads, dev));
                 LAUNCH(L, DQ_K_MATCH_SEARCH, prof_units, prof_bytes,
-                       hipLaunchKernelGGL(anchor_mid_many_kernel, dim3((unsigned)grid), dim3(kAmmThreads), 0, st, d_old, d_off, d_sa, d_new,
-                                          d_noff, d_aoff, d_order + in_class[0], in_class[1], d_next + 16, d_back, d_counts, d_searches));
+                       hipLaunchKernelGGL(anchor_mid_many_kernel, dim3((unsigned)grid), dim3(kAmMidThreads), 0, st, k.d_old, k.d_off, k.d_sa,
+                                          k.d_new, k.d_noff, k.d_aoff, k.d_order + k.in_class[0], k.in_class[1], k.d_next + 16, k.d_back,
+                                          k.d_counts, k.d_searches));
                 t_diff_many_info[11] += 1;
             }
-            t_diff_many_info[10] += in_class[1];
-            const hipError_t e1 = hipMemcpyAsync(back.data(), d_back, back.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+            t_diff_many_info[10] += k.in_class[1];
+            const hipError_t e1 = hipMemcpyAsync(k.back.data(), k.d_back, k.back.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st);
             const hipError_t e2 = hipStreamSynchronize(st);
             HIP_TRY(e1 != hipSuccess ? e1 : e2);
             t_diff_many_info[6] += us_since(t0);
@@ -1728,17 +1772,33 @@ int diff_many_chunk(const uint8_t *olds, const int64_t *ooff, const uint8_t *new
         if (rc == DQ_OK) rc = leased(scan);
         if (rc != DQ_OK) return rc;
     }
-    const int32_t *counts = back.data() + 2 * anchors, *searches = counts + cnt;
     // ---- 3. - 5. on the host and in the shared block sort
     const ManyFiles files{olds, ooff + first, 0, news, noff + first};
-    int64_t info[5] = {0, 0, 0, 0, 0};
-    const int rc = diff_many_finish(files, cnt, back.data(), rel_a, counts, searches, dev, out, info);
-    t_diff_many_info[3] += info[0];
-    t_diff_many_info[4] += info[1];
-    t_diff_many_info[7] += info[2];
-    t_diff_many_info[8] += info[3];
-    t_diff_many_info[9] += info[4];
-    return rc;
+    return diff_many_finish(files, k, dev, out, t_diff_many_info, {3, 4, 7, 8, 9});
+}
+
+// The checks both many-file calls make on their offset arrays (ooff null: the call has no old files), in this order;
+// then every plens[j] = -1.
+int many_check_offsets(const int64_t *ooff, const int64_t *noff, const int64_t *poff, int32_t count, int64_t *plens)
+{
+    if (!ooff) ooff = noff;                                // (every test of it then repeats new's)
+    if (ooff[0] != 0 || noff[0] != 0 || poff[0] != 0) return fail(DQ_ERR_BAD_ARGS, "offsets[0] must be 0");
+    for (int32_t j = 0; j < count; ++j)
+        if (ooff[j + 1] < ooff[j] || noff[j + 1] < noff[j] || poff[j + 1] < poff[j]) return fail(DQ_ERR_BAD_ARGS, "offsets must not decrease");
+    for (int32_t j = 0; j < count; ++j)
+        if (ooff[j + 1] - ooff[j] > 0x7fffffffLL || noff[j + 1] - noff[j] > 0x7fffffffLL)
+            return fail(DQ_ERR_TOO_LARGE, "the BSDIFF40 path takes files below 2 GiB (int indices, as the reference)");
+    for (int32_t j = 0; j < count; ++j) plens[j] = -1;
+    return DQ_OK;
+}
+
+// patch j of a many-file call into its slot
+int many_deliver(const std::vector<uint8_t> &patch, int32_t j, uint8_t *patches, const int64_t *poff, int64_t *plens)
+{
+    if ((int64_t)patch.size() > poff[j + 1] - poff[j]) return fail(DQ_ERR_BAD_ARGS, "output buffer too small (see dq_bsdiff_patch_bound)");
+    if (!patch.empty()) memcpy(patches + poff[j], patch.data(), patch.size());
+    plens[j] = (int64_t)patch.size();
+    return DQ_OK;
 }
 }  // namespace
 
@@ -1749,24 +1809,13 @@ int bsdiff_create_many_host(const uint8_t *olds, const int64_t *ooff, const uint
     if (count < 0) return fail(DQ_ERR_BAD_ARGS, "negative count");
     if (count == 0) return DQ_OK;
     if (!olds || !ooff || !news || !noff || !patches || !poff || !plens) return fail(DQ_ERR_BAD_ARGS, "null buffer");
-    for (const int64_t *off : {ooff, noff, poff})
-        if (off[0] != 0) return fail(DQ_ERR_BAD_ARGS, "offsets[0] must be 0");
-    for (int32_t j = 0; j < count; ++j)
-        if (ooff[j + 1] < ooff[j] || noff[j + 1] < noff[j] || poff[j + 1] < poff[j]) return fail(DQ_ERR_BAD_ARGS, "offsets must not decrease");
-    for (int32_t j = 0; j < count; ++j)
-        if (ooff[j + 1] - ooff[j] > 0x7fffffffLL || noff[j + 1] - noff[j] > 0x7fffffffLL)
-            return fail(DQ_ERR_TOO_LARGE, "the BSDIFF40 path takes files below 2 GiB (int indices, as the reference)");
-    for (int32_t j = 0; j < count; ++j) plens[j] = -1;
+    int rc = many_check_offsets(ooff, noff, poff, count, plens);
+    if (rc != DQ_OK) return rc;
     int dev = 0;
-    int rc = resolve_device(device, &dev);
+    rc = resolve_device(device, &dev);
     if (rc != DQ_OK) return rc;
 
-    auto deliver = [&](int32_t j, const std::vector<uint8_t> &patch) -> int {
-        if ((int64_t)patch.size() > poff[j + 1] - poff[j]) return fail(DQ_ERR_BAD_ARGS, "output buffer too small (see dq_bsdiff_patch_bound)");
-        if (!patch.empty()) memcpy(patches + poff[j], patch.data(), patch.size());
-        plens[j] = (int64_t)patch.size();
-        return DQ_OK;
-    };
+    auto deliver = [&](int32_t j, const std::vector<uint8_t> &patch) { return many_deliver(patch, j, patches, poff, plens); };
     const bool one_by_one = flags().no_diff_many.value_or(0) != 0;
     const int64_t listed_max = flags().no_diff_mid_many.value_or(0) != 0 ? kDiffManyMax : kMidMaxN;
     const int64_t mid_min = flags().diff_mid_many_min.value_or(kDiffMidManyMin);
@@ -1929,7 +1978,7 @@ int diff_index_diff(const void *index, const uint8_t *nw, int64_t m, std::vector
 // most kDiffManyChunkBytes of new bytes, kDiffManyChunkPairs files -- and a chunk goes through dq_bsdiff_create_many's
 // phases without the first: there is nothing to sort, the index has (old, suffix array, prefix table) on the device.
 //   2. new files, offsets, work list and counter to the device; ONE launch of anchor_index_many_kernel
-//      (dq_anchor_index_many.h: a workgroup per new file, new in LDS, old and the suffix array read from device
+//      (dq_anchor_many.h: a workgroup per new file, new in LDS, old and the suffix array read from device
 //      memory); anchor lists, counts and searches back.  The device's diff_mu is held for this phase only.
 //   3. - 5. diff_many_finish, as for the pairs of dq_bsdiff_create_many, every emitter on the index's host copy of old.
 // Device memory per chunk: new + diff_many_anchor_room(m) = m / 8 + 2 pairs of int32 per file for the anchor lists (a byte
@@ -1943,7 +1992,7 @@ constexpr int64_t kIndexManyMax = kMidMaxN;                // longest new file o
 // (profiles/r12/index_diff_many.json, docs/ROUNDS.md round 12).
 constexpr int32_t kIndexManyMin = 32;
 // Workgroup size of the launch: 256 threads, two workgroups per CU, measured against 512 threads, one per CU
-// (dq_anchor_index_many.h has the figures; DQ_INDEX_MANY_THREADS chooses the other one for a measurement).
+// (docs/ROUNDS.md, round 12, has the figures; DQ_INDEX_MANY_THREADS chooses the other one for a measurement).
 constexpr int kIndexManyThreads = 256;
 
 namespace {
@@ -1953,96 +2002,49 @@ int diff_index_many_chunk(const DiffIndex &ix, const uint8_t *news, const int64_
 {
     const int dev = ix.dev;
     HIP_TRY(hipSetDevice(dev));
-    const int64_t n_base = noff[first], n_bytes = noff[first + cnt] - n_base;
-    out.clear();
-    out.resize((size_t)cnt);
-    // offsets relative to the chunk; anchor room per file; the work list, longest first
-    std::vector<int64_t> off((size_t)(cnt + 1) * 2);
-    int64_t *rel_n = off.data(), *rel_a = rel_n + cnt + 1;
-    rel_a[0] = 0;
-    for (int32_t j = 0; j <= cnt; ++j) {
-        rel_n[j] = noff[first + j] - n_base;
-        if (j > 0) rel_a[j] = rel_a[j - 1] + diff_many_anchor_room(rel_n[j] - rel_n[j - 1]);
-    }
-    const int64_t anchors = rel_a[cnt];
-    std::vector<int32_t> order((size_t)cnt);
-    for (int32_t j = 0; j < cnt; ++j) order[(size_t)j] = j;
-    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return rel_n[a + 1] - rel_n[a] > rel_n[b + 1] - rel_n[b]; });
-    std::vector<int32_t> back((size_t)anchors * 2 + (size_t)cnt * 2);
     const int threads = flags().index_many_threads.value_or(kIndexManyThreads);
     if (threads != 256 && threads != 512) return fail(DQ_ERR_BAD_ARGS, "DQ_INDEX_MANY_THREADS is 256 or 512");
+    ManyChunk k;
+    int rc = many_chunk_prepare(k, nullptr, noff, first, cnt, buf);
+    if (rc != DQ_OK) return rc;
 
     // ---- 2. on the device, scan loops of other callers taking their turns before and after
     {
-        const auto t0 = std::chrono::steady_clock::now();
-        const size_t b_new = align_up((size_t)n_bytes + 64), b_off = align_up(off.size() * sizeof(int64_t)),
-                     b_order = align_up(order.size() * sizeof(int32_t)), b_next = 256, b_back = align_up(back.size() * sizeof(int32_t));
-        int rc = buf.need(b_new + b_off + b_order + b_next + b_back);
-        if (rc != DQ_OK) return rc;
-        char *q = buf.p;
-        uint8_t *d_new = reinterpret_cast<uint8_t *>(q); q += b_new;
-        int64_t *d_off = reinterpret_cast<int64_t *>(q); q += b_off;
-        int32_t *d_order = reinterpret_cast<int32_t *>(q); q += b_order;
-        uint32_t *d_next = reinterpret_cast<uint32_t *>(q); q += b_next;
-        int32_t *d_back = reinterpret_cast<int32_t *>(q);
         std::lock_guard<std::mutex> one_diff(ctx0(dev).diff_mu);
         SlotLease lease(dev, 0);
         DeviceCtx &c = *lease.c;
         rc = init_ctx(c, dev);
         if (rc != DQ_OK) return rc;
         hipStream_t st = c.stream;
+        Launcher L{c, st, g_prof_on.load()};
+        auto launch = [&](auto width) -> int {
+            constexpr int kThreads = decltype(width)::value;
+            const int grid = std::min<int>(cnt, resident_groups(&c.anchor_index_many_groups[kThreads == 256 ? 0 : 1],
+                                                                anchor_index_many_kernel<kThreads>, kThreads, dev));
+            LAUNCH(L, DQ_K_MATCH_SEARCH, k.n_bytes, k.n_bytes,
+                   hipLaunchKernelGGL(anchor_index_many_kernel<kThreads>, dim3((unsigned)grid), dim3(kThreads), 0, st,
+                                      reinterpret_cast<const uint8_t *>(ix.d_old), ix.n, reinterpret_cast<const int32_t *>(ix.d_sa),
+                                      reinterpret_cast<const int32_t *>(ix.d_tab), ix.pk, k.d_new, k.d_noff, k.d_aoff, k.d_order, cnt,
+                                      k.d_next, k.d_back, k.d_counts, k.d_searches));
+            return DQ_OK;
+        };
         auto run = [&]() -> int {
-            if (n_bytes > 0) HIP_TRY(hipMemcpyAsync(d_new, news + n_base, (size_t)n_bytes, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(d_off, off.data(), off.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(d_order, order.data(), order.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemsetAsync(d_next, 0, b_next, st));
-            // workgroups the device holds at once (a wrong answer costs time only: nobody waits for anybody)
-            int *groups = &c.anchor_index_many_groups[threads == 256 ? 0 : 1];
-            if (*groups <= 0) {
-                int per_cu = 0, ncu = 0;
-                const hipError_t e = threads == 256
-                    ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, anchor_index_many_kernel<256>, 256, 0)
-                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, anchor_index_many_kernel<512>, 512, 0);
-                if (e != hipSuccess || per_cu <= 0) per_cu = 1;
-                if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
-                *groups = per_cu * ncu;
-            }
-            const int grid = std::min<int>(cnt, *groups);
-            Launcher L{c, st, g_prof_on.load()};
-            const uint8_t *d_old = reinterpret_cast<const uint8_t *>(ix.d_old);
-            const int32_t *d_sa = reinterpret_cast<const int32_t *>(ix.d_sa), *d_tab = reinterpret_cast<const int32_t *>(ix.d_tab);
-            const int64_t *d_noff = d_off, *d_aoff = d_off + (cnt + 1);
-            int32_t *d_counts = d_back + 2 * anchors, *d_searches = d_counts + cnt;
-            if (threads == 256) {
-                LAUNCH(L, DQ_K_MATCH_SEARCH, n_bytes, n_bytes,
-                       hipLaunchKernelGGL(anchor_index_many_kernel<256>, dim3((unsigned)grid), dim3(256), 0, st, d_old, ix.n, d_sa, d_tab,
-                                          ix.pk, d_new, d_noff, d_aoff, d_order, cnt, d_next, d_back, d_counts, d_searches));
-            } else {
-                LAUNCH(L, DQ_K_MATCH_SEARCH, n_bytes, n_bytes,
-                       hipLaunchKernelGGL(anchor_index_many_kernel<512>, dim3((unsigned)grid), dim3(512), 0, st, d_old, ix.n, d_sa, d_tab,
-                                          ix.pk, d_new, d_noff, d_aoff, d_order, cnt, d_next, d_back, d_counts, d_searches));
-            }
+            int r = many_chunk_upload(k, nullptr, news, st);
+            if (r == DQ_OK) r = threads == 256 ? launch(std::integral_constant<int, 256>{}) : launch(std::integral_constant<int, 512>{});
+            if (r != DQ_OK) return r;
             t_index_many_info[2] += 1;
-            const hipError_t e1 = hipMemcpyAsync(back.data(), d_back, back.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+            const hipError_t e1 = hipMemcpyAsync(k.back.data(), k.d_back, k.back.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st);
             const hipError_t e2 = hipStreamSynchronize(st);
             HIP_TRY(e1 != hipSuccess ? e1 : e2);
             return flush_profile(c);
         };
         rc = run();
         if (rc != DQ_OK) { drop_pending(c, c.stream); return rc; }
-        t_index_many_info[5] += us_since(t0);
+        t_index_many_info[5] += us_since(k.t_device);
     }
     // ---- 3. - 5. on the host and in the shared block sort
     const ManyFiles files{ix.old, nullptr, ix.n, news, noff + first};
-    const int32_t *counts = back.data() + 2 * anchors, *searches = counts + cnt;
-    int64_t info[5] = {0, 0, 0, 0, 0};
-    const int rc = diff_many_finish(files, cnt, back.data(), rel_a, counts, searches, dev, out, info);
-    t_index_many_info[3] += info[0];
-    t_index_many_info[4] += info[1];
-    t_index_many_info[6] += info[2];
-    t_index_many_info[7] += info[3];
-    t_index_many_info[8] += info[4];
-    return rc;
+    return diff_many_finish(files, k, dev, out, t_index_many_info, {3, 4, 6, 7, 8});
 }
 }  // namespace
 
@@ -2054,22 +2056,11 @@ int diff_index_many(const void *index, const uint8_t *news, const int64_t *noff,
     if (count < 0) return fail(DQ_ERR_BAD_ARGS, "negative count");
     if (count == 0) return DQ_OK;
     if (!news || !noff || !patches || !poff || !plens) return fail(DQ_ERR_BAD_ARGS, "null buffer");
-    for (const int64_t *off : {noff, poff})
-        if (off[0] != 0) return fail(DQ_ERR_BAD_ARGS, "offsets[0] must be 0");
-    for (int32_t j = 0; j < count; ++j)
-        if (noff[j + 1] < noff[j] || poff[j + 1] < poff[j]) return fail(DQ_ERR_BAD_ARGS, "offsets must not decrease");
-    for (int32_t j = 0; j < count; ++j)
-        if (noff[j + 1] - noff[j] > 0x7fffffffLL)
-            return fail(DQ_ERR_TOO_LARGE, "the BSDIFF40 path takes files below 2 GiB (int indices, as the reference)");
-    for (int32_t j = 0; j < count; ++j) plens[j] = -1;
+    const int checked = many_check_offsets(nullptr, noff, poff, count, plens);
+    if (checked != DQ_OK) return checked;
     const DiffIndex *ix = static_cast<const DiffIndex *>(index);
 
-    auto deliver = [&](int32_t j, const std::vector<uint8_t> &patch) -> int {
-        if ((int64_t)patch.size() > poff[j + 1] - poff[j]) return fail(DQ_ERR_BAD_ARGS, "output buffer too small (see dq_bsdiff_patch_bound)");
-        if (!patch.empty()) memcpy(patches + poff[j], patch.data(), patch.size());
-        plens[j] = (int64_t)patch.size();
-        return DQ_OK;
-    };
+    auto deliver = [&](int32_t j, const std::vector<uint8_t> &patch) { return many_deliver(patch, j, patches, poff, plens); };
     const bool one_by_one = flags().no_index_many.value_or(0) != 0;
     const int64_t many_min = flags().index_many_min.value_or(kIndexManyMin);
     auto is_listed = [&](int32_t j) { return !one_by_one && noff[j + 1] - noff[j] <= kIndexManyMax; };

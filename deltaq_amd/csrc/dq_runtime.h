@@ -110,8 +110,8 @@ struct DeviceCtx {
     int ncu = 0;                        // compute units of the device (grid of the persistent kernels)
     int many_groups[5] = {0, 0, 0, 0, 0};   // workgroups of small_many_kernel (3 length classes) and mid_many_kernel (2) the device holds at once (0: not asked yet)
     int anchor_many_groups = 0;         // ... and of anchor_many_kernel (dq_anchor_many.h)
-    int anchor_mid_many_groups = 0;     // ... and of anchor_mid_many_kernel (dq_anchor_mid_many.h)
-    int anchor_index_many_groups[2] = {0, 0};   // ... and of anchor_index_many_kernel at 256 and 512 threads (dq_anchor_index_many.h)
+    int anchor_mid_many_groups = 0;     // ... and of anchor_mid_many_kernel
+    int anchor_index_many_groups[2] = {0, 0};   // ... and of anchor_index_many_kernel at 256 and 512 threads (dq_anchor_many.h)
     hipStream_t stream = nullptr;
     char *ws = nullptr;
     size_t ws_bytes = 0;

@@ -1,5 +1,5 @@
 """Seeded (old, new) pairs with a file above 8192 bytes and none above 65 536 -- the medium class of
-dq_bsdiff_create_many (dq_anchor_mid_many.h): what tests/test_diff_many_medium_cpu.py models, tests/test_gpu_diff_many_medium.py
+dq_bsdiff_create_many (anchor_mid_many_kernel): what tests/test_diff_many_medium_cpu.py models, tests/test_gpu_diff_many_medium.py
 diffs and tools/kbench/diff_many_medium.py times.  Built on tests/many_medium_inputs.py (the old files are its texts) and
 tests/many_inputs.py.  Files are numpy uint8 arrays."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""Seeded old files and sets of new files for dq_bsdiff_index_diff_many (dq_anchor_index_many.h): many new files of at most
+"""Seeded old files and sets of new files for dq_bsdiff_index_diff_many (anchor_index_many_kernel, dq_anchor_many.h): many new files of at most
 65 536 bytes against ONE old file of any size.  What tests/test_index_many_cpu.py models, tests/test_gpu_index_many.py
 diffs and tools/kbench/index_diff_many.py times.  Built on tests/many_medium_inputs.py and tests/diff_pairs_medium.py.
 Files are numpy uint8 arrays."""

@@ -174,3 +174,16 @@ def test_window_model_gives_the_reference_anchors_on_the_pair_set(oracle_mod, sc
         searched += searches
         new_bytes += m
     assert 0 < searched <= new_bytes
+
+
+def test_window_model_on_the_window_edges(oracle_mod, scan_harness):
+    """diff_pairs.window_anchors (windows of 256) on new files of 1 .. 515 bytes against an old file of the short class:
+    tests/window_edge_inputs.py has the lengths and the three kinds; tests/test_gpu_window_edges.py runs the same files
+    through the kernels."""
+    import window_edge_inputs as wei
+
+    def anchors_of(old, sa, new):
+        pos, ln = oracle_mod.bsdiff_search(old, sa, new)
+        return diff_pairs.window_anchors(old, new, pos, ln)
+
+    wei.check_model(oracle_mod, scan_harness, wei.old_file(wei.SHORT_OLD), anchors_of)

@@ -1,4 +1,4 @@
-"""The medium class of dq_bsdiff_create_many (pairs with a file of 8193 .. 65 536 bytes, dq_anchor_mid_many.h), without a
+"""The medium class of dq_bsdiff_create_many (pairs with a file of 8193 .. 65 536 bytes, anchor_mid_many_kernel), without a
 GPU: the two new info entries and flags; the compact form of the prefix counts of `agree` (a bit per position and a count
 per 32-bit word) against plain prefix sums; and a numpy model of the kernel's evaluation with windows of 512 positions
 against the reference's loop, anchors through the product's emitter triple for triple, on the corner pairs and 150 pairs
@@ -103,3 +103,15 @@ def test_window_model_gives_the_reference_anchors_on_medium_pairs(oracle_mod, sc
         trip, dif, extra = triples_of(scan_harness, old, new, got)
         assert np.array_equal(trip, wc), (j, old.size, m)
         assert np.array_equal(dif, wd) and np.array_equal(extra, we), (j, old.size, m)
+
+
+def test_window_model_on_the_window_edges(oracle_mod, scan_harness):
+    """dpm.window_anchors (windows of 512, P from the bit mask) on new files of 1 .. 515 bytes against the shortest old
+    file of the medium class: tests/window_edge_inputs.py has the lengths and the three kinds;
+    tests/test_gpu_window_edges.py runs the same files through the kernels."""
+    import window_edge_inputs as wei
+
+    def anchors_of(old, sa, new):
+        return dpm.window_anchors(old, new, lambda c: oracle_mod.bsdiff_search(old, sa, new, scans=c))
+
+    wei.check_model(oracle_mod, scan_harness, wei.old_file(wei.MEDIUM_OLD), anchors_of)

@@ -1,4 +1,4 @@
-"""GPU tests of the medium class of dq_bsdiff_create_many / Diff.CreateMany (dq_anchor_mid_many.h, the driver in
+"""GPU tests of the medium class of dq_bsdiff_create_many / Diff.CreateMany (anchor_mid_many_kernel, the driver in
 dq_diff.hip): pairs with a file of 8193 .. 65 536 bytes give, byte for byte, the patch dq_bsdiff_create makes of the pair
 alone, their streams are the reference loop's triple for triple, and they really went through the medium anchor launches;
 the threshold and its two flags; short, medium and long pairs in one call; nothing leaks from one pair to the next in a

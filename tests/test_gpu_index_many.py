@@ -1,4 +1,4 @@
-"""GPU tests of dq_bsdiff_index_diff_many / DiffIndex.CreateMany (dq_anchor_index_many.h, the driver in dq_diff.hip): every
+"""GPU tests of dq_bsdiff_index_diff_many / DiffIndex.CreateMany (dq_anchor_many.h, the driver in dq_diff.hip): every
 patch byte for byte the one DiffIndex.Create makes of that new file alone, its three streams the reference loop's, triple
 for triple, on both sides of each prefix-table width; that short new files really share one launch; the threshold and
 the switch; that the call is total; that nothing leaks from one file to the next in a workgroup's LDS; the chunk

@@ -1,4 +1,4 @@
-"""Many new files against one index in shared launches (dq_bsdiff_index_diff_many, dq_anchor_index_many.h), without a
+"""Many new files against one index in shared launches (dq_bsdiff_index_diff_many, dq_anchor_many.h), without a
 GPU: the two exports and their declarations in the header, the Python binding and the C# shim; the argument checks that
 come before any device use; the info call; the two flags; and the numpy model of the windowed evaluation
 (diff_pairs_medium.window_anchors) on exact Search answers with old files far longer than the new ones."""
@@ -114,3 +114,15 @@ def test_window_model_gives_the_reference_anchors_when_old_is_far_longer(oracle_
                 trip, dif, extra = triples_of(scan_harness, old, new, got)
                 assert np.array_equal(trip, wc), (j, m, window)
                 assert np.array_equal(dif, wd) and np.array_equal(extra, we), (j, m, window)
+
+
+def test_window_model_on_the_window_edges(oracle_mod, scan_harness):
+    """dpm.window_anchors at the index kernel's two widths, 256 and 512 positions, on new files of 1 .. 515 bytes:
+    tests/window_edge_inputs.py has the lengths and the three kinds; tests/test_gpu_window_edges.py runs the same files
+    through the kernels."""
+    import window_edge_inputs as wei
+    for window in (256, 512):
+        def anchors_of(old, sa, new):
+            return dpm.window_anchors(old, new, lambda c: oracle_mod.bsdiff_search(old, sa, new, scans=c), window)
+
+        wei.check_model(oracle_mod, scan_harness, wei.old_file(wei.MEDIUM_OLD), anchors_of)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Many medium file pairs (a file of 8193 .. 65 536 bytes): what the medium class of dq_bsdiff_create_many
-(anchor_mid_many_kernel, dq_anchor_mid_many.h) buys over the build before it, where such a pair goes through the one-pair
+(anchor_mid_many_kernel, dq_anchor_many.h) buys over the build before it, where such a pair goes through the one-pair
 path.
 
 compare   Both builds are driven through dq_bsdiff_create_many, each in processes of its own (both define the same C++

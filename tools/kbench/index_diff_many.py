@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Many new files against one index: what the shared launches of dq_bsdiff_index_diff_many (anchor_index_many_kernel,
-dq_anchor_index_many.h) buy over a loop of dq_bsdiff_index_diff on the same index.
+dq_anchor_many.h) buy over a loop of dq_bsdiff_index_diff on the same index.
 
 compare   The parent build (--parent-lib: the commit before the call exists) runs a loop of dq_bsdiff_index_diff over one
           index built once; this build makes ONE dq_bsdiff_index_diff_many call on an index built the same way.  Each in
@@ -8,13 +8,15 @@ compare   The parent build (--parent-lib: the commit before the call exists) run
           parent / new; each process warms its shape once and times --calls runs; the patches of both are digested and
           compared.  Acceptance is against the parent: the new build's median must lie below the parent's FASTEST single
           run of the loop.  A set that misses it is reported as such, not dropped.  The new build also reports the phase
-          times and counts of dq_last_index_many_info for its last timed call.
+          times and counts of dq_last_index_many_info for its last timed call.  --parent-kind many drives the parent
+          build through dq_bsdiff_index_diff_many too (a parent that has it: what a later change to the shared path is
+          measured against); its info is then reported beside the new build's, with the spread of the medians.
 sweep     This build only: 1 .. 512 new files of 4 / 16 / 64 KiB, similar files and unrelated ones, against both old
           files, the shared launch forced on (DQ_INDEX_MANY_MIN=1) against off (DQ_NO_INDEX_MANY=1).  The crossing of a
           row is the smallest count from which on the shared launch is faster; kIndexManyMin (dq_diff.hip) = twice the
           largest crossing, rounded up to a power of two, and at least 8.
 threads   This build only: the sets under DQ_INDEX_MANY_THREADS=512 and =256, the anchor phase of
-          dq_last_index_many_info side by side (the workgroup-size choice of dq_anchor_index_many.h).
+          dq_last_index_many_info side by side (the workgroup-size choice of anchor_index_many_kernel).
 
 Old files (tests/index_many_inputs.py, seeded): 1 MiB and 16 MiB, text-like with repeats.  Sets: fixed4k = 4096 files of
 4 KiB; fixed32k = 2048 of 32 KiB; tree = 16 384 of 64 B .. 64 KiB -- edited slices of old, every fifth unrelated --;
@@ -245,6 +247,9 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r12", "index_diff_many.json"))
     ap.add_argument("--calls", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=2, help="parent / new alternations per set")
+    ap.add_argument("--parent-kind", choices=["loop", "many"], default="loop",
+                    help="how the parent build is driven: a loop of dq_bsdiff_index_diff (a build without "
+                         "dq_bsdiff_index_diff_many), or dq_bsdiff_index_diff_many like this build")
     ap.add_argument("--sets", default="fixed4k,fixed32k,tree,unrelated64k", help="comma-separated; empty: none")
     ap.add_argument("--old-mib", default="1,16", help="comma-separated sizes of the old file of the compare step")
     ap.add_argument("--sweep", action="store_true", help="the crossover sweep (this build only)")
@@ -296,7 +301,7 @@ def main():
         for set_name in set_names:
             runs = {"parent": [], "new": []}
             for _ in range(args.rounds):
-                for who, path, kind in (("parent", args.parent_lib, "loop"), ("new", new_lib, "many")):
+                for who, path, kind in (("parent", args.parent_lib, args.parent_kind), ("new", new_lib, "many")):
                     if path:
                         runs[who].append(run_worker(["--worker", "set", "--lib", path, "--kind", kind, "--set", set_name, "--mib",
                                                      str(mib), "--calls", str(args.calls)], 1100))
@@ -311,9 +316,13 @@ def main():
             if runs["parent"]:
                 p_ms = statistics.median(r["ms_median"] for r in runs["parent"])
                 p_fastest = min(r["ms_min"] for r in runs["parent"])
-                rec.update(parent_loop_ms=[r["ms_median"] for r in runs["parent"]], parent_loop_ms_median=p_ms,
-                           parent_fastest_loop_ms=p_fastest, ratio_parent_over_new=round(p_ms / n_ms, 2),
+                rec.update(parent_kind=args.parent_kind, parent_loop_ms=[r["ms_median"] for r in runs["parent"]],
+                           parent_loop_ms_median=p_ms, parent_fastest_loop_ms=p_fastest, ratio_parent_over_new=round(p_ms / n_ms, 2),
                            new_median_below_parents_fastest_loop=bool(n_ms < p_fastest))
+                if args.parent_kind == "many":
+                    rec["parent_last_call_info"] = runs["parent"][-1]["last_call_info"]
+                    rec["spread_ms"] = round(max(max(r["ms_median"] for r in rs) - min(r["ms_median"] for r in rs)
+                                                 for rs in runs.values()), 3)
             result["sets"][f"{set_name}@{mib}MiB"] = rec
             save()
     print(json.dumps(result))
