@@ -7,7 +7,7 @@
 // workgroup, so its whole anchor search runs inside it and the launch takes as many files as the caller has:
 //   * grid and work list as small_many_kernel (dq_small_many.h): as many workgroups as are resident, each claims the
 //     next file of a longest-new-first list with ONE agent-scope relaxed atomic add by thread 0, handed on through LDS
-//     (for_each_claimed_file);
+//     (for_each_claimed, dq_device_utils.h);
 //   * nothing else is shared between workgroups: no flags, no look-back, no spin, no watchdog -- a workgroup never
 //     waits for another one, so a grid of any size is correct and the launch cannot hang.
 // A file outside its class's limits gets counts[j] = -1 and is never copied: nothing is read or written out of the LDS
@@ -281,23 +281,6 @@ __device__ __forceinline__ void copy_in(uint32_t *__restrict__ dst, const uint8_
     }
 }
 
-// per_file(order[k]) for every entry k of the work list this workgroup claims: *next starts at 0, `claimed` is a word of
-// the workgroup's LDS.  per_file is called by the whole workgroup and leaves it converged.
-template <typename Fn>
-__device__ __forceinline__ void for_each_claimed_file(int32_t *claimed, uint32_t *__restrict__ next, const int32_t *__restrict__ order,
-                                            int count, Fn per_file)
-{
-    for (;;) {
-        if (threadIdx.x == 0) *claimed = (int)__hip_atomic_fetch_add(next, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        const int k = *claimed;
-        if (k < 0 || k >= count) return;                       // (uniform: the whole workgroup leaves)
-        per_file(order[k]);
-        // the file's last reads of LDS (and everybody's read of `claimed`) are over before the next file's first write
-        __syncthreads();
-    }
-}
-
 // (the host lists only files that fit their class; one that does not is left alone)
 __device__ __forceinline__ void anchor_refuse_file(int32_t *__restrict__ count_out, int32_t *__restrict__ searches_out)
 {
@@ -315,7 +298,7 @@ __global__ __launch_bounds__(kAmThreads) void anchor_many_kernel(const uint8_t *
                                                                 int32_t *__restrict__ searches)
 {
     __shared__ AnchorShortLds L;
-    for_each_claimed_file(&L.claimed, next, order, count, [&](int j) {
+    for_each_claimed(&L.claimed, next, order, count, [&](int j) {
         const int64_t o_at = old_off[j], n_at = new_off[j], a_at = anch_off[j];
         const int64_t n64 = old_off[j + 1] - o_at, m64 = new_off[j + 1] - n_at;
         const int cap = (int)(anch_off[j + 1] - a_at);
@@ -343,7 +326,7 @@ __global__ __launch_bounds__(kAmMidThreads) void anchor_mid_many_kernel(
     int32_t *__restrict__ counts, int32_t *__restrict__ searches)
 {
     __shared__ AnchorMidLds L;
-    for_each_claimed_file(&L.claimed, next, order, count, [&](int j) {
+    for_each_claimed(&L.claimed, next, order, count, [&](int j) {
         const int64_t o_at = old_off[j], n_at = new_off[j], a_at = anch_off[j];
         const int64_t n64 = old_off[j + 1] - o_at, m64 = new_off[j + 1] - n_at;
         const int cap = (int)(anch_off[j + 1] - a_at);
@@ -370,7 +353,7 @@ __global__ __launch_bounds__(kThreads) void anchor_index_many_kernel(
     int32_t *__restrict__ counts, int32_t *__restrict__ searches)
 {
     __shared__ AnchorIndexLds<kThreads> L;
-    for_each_claimed_file(&L.claimed, next, order, count, [&](int j) {
+    for_each_claimed(&L.claimed, next, order, count, [&](int j) {
         const int64_t n_at = new_off[j], a_at = anch_off[j];
         const int64_t m64 = new_off[j + 1] - n_at;
         const int cap = (int)(anch_off[j + 1] - a_at);

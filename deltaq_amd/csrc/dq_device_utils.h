@@ -144,4 +144,24 @@ __device__ __forceinline__ T block_excl_max(T v, T *tmp)
     return excl;
 }
 
+// The claim loop of the many-texts and many-files kernels (dq_small.h, dq_mid_many.h, dq_anchor_many.h):
+// per_entry(order[k]) for every entry k of the work list this workgroup claims, with ONE agent-scope relaxed atomic add
+// by thread 0 per entry, handed on through `claimed`, a word of the workgroup's LDS.  *next starts at 0.  per_entry is
+// called by the whole workgroup and leaves it converged.  Nothing else is shared between workgroups: nobody ever waits
+// for anybody, so a grid of any size is correct and the launch cannot hang.
+template <typename Fn>
+__device__ __forceinline__ void for_each_claimed(int32_t *claimed, uint32_t *__restrict__ next, const int32_t *__restrict__ order,
+                                                 int count, Fn per_entry)
+{
+    for (;;) {
+        if (threadIdx.x == 0) *claimed = (int)__hip_atomic_fetch_add(next, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __syncthreads();
+        const int k = *claimed;
+        if (k < 0 || k >= count) return;                       // (uniform: the whole workgroup leaves)
+        per_entry(order[k]);
+        // the entry's last reads of LDS (and everybody's read of `claimed`) are over before the next entry's first write
+        __syncthreads();
+    }
+}
+
 }  // namespace dq

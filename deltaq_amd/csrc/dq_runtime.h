@@ -34,6 +34,8 @@ namespace dq {
 
 constexpr int kSmallMaxN = 8192;          // largest text the single-workgroup sorter takes (dq_small.h)
 constexpr int kMidMaxN = 65536;           // largest text of the medium class of the many-texts launches (dq_mid_many.h)
+// length classes of the many-texts launches: up to kSmallMaxN, from there to kMidMaxN (the table: dq_small_many.h)
+constexpr int kManyClasses = 3, kMidClasses = 2, kAllClasses = kManyClasses + kMidClasses;
 constexpr int kLargeMaxN = 4 << 20;       // largest text of their segmented sort (dq_large_many.h; the figures: dq_small_many.h)
 
 // ------------------------------------------------------------------ errors
@@ -108,7 +110,7 @@ struct DeviceCtx {
     std::mutex mu;
     int dev = -1;
     int ncu = 0;                        // compute units of the device (grid of the persistent kernels)
-    int many_groups[5] = {0, 0, 0, 0, 0};   // workgroups of small_many_kernel (3 length classes) and mid_many_kernel (2) the device holds at once (0: not asked yet)
+    int many_groups[kAllClasses] = {};  // workgroups of each length class of small_many_kernel and mid_many_kernel the device holds at once (0: not asked yet)
     int anchor_many_groups = 0;         // ... and of anchor_many_kernel (dq_anchor_many.h)
     int anchor_mid_many_groups = 0;     // ... and of anchor_mid_many_kernel
     int anchor_index_many_groups[2] = {0, 0};   // ... and of anchor_index_many_kernel at 256 and 512 threads (dq_anchor_many.h)

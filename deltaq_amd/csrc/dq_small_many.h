@@ -5,60 +5,75 @@
 // files) pays the launches, not the sorting.  Here the same body runs in a grid of as many workgroups as the device
 // holds at once; each workgroup takes the next text from a work list until the list is empty:
 //   * the host writes the list longest text first, so the workgroups that finish last hold the shortest texts;
-//   * a workgroup claims an entry with one agent-scope atomic add by thread 0, handed on through LDS;
+//   * a workgroup claims an entry with one agent-scope atomic add by thread 0, handed on through LDS
+//     (for_each_claimed, dq_device_utils.h);
 //   * no workgroup ever waits for another -- no look-back, no flags, no spin -- so a grid larger or smaller than what
 //     is resident costs time, never correctness, and the launch cannot hang;
-//   * texts are sorted in length classes (LDS block and thread count are template parameters of the body): a text of
-//     2048 bytes needs 30 KiB of LDS and 256 threads, five such workgroups share a CU where the 8192-byte class
-//     (120 KiB, 1024 threads) fits once.  One launch per class, on the same stream.
+//   * texts are sorted in length classes (LDS block and thread count are template parameters of small_many_kernel,
+//     dq_small.h; kManyClass below is the one list of the classes): a text of 2048 bytes needs 30 KiB of LDS and 256
+//     threads, five such workgroups share a CU where the 8192-byte class (120 KiB, 1024 threads) fits once.  One launch
+//     per class, on the same stream.
 // Texts between the short-text limit and kMidMaxN = 65 536 bytes share launches of mid_many_kernel (dq_mid_many.h), where
 // a call or chunk holds at least kMidManyMin of them.  Texts above kMidMaxN and up to kLargeMaxN bytes share one segmented
 // sort per batch (dq_large_many.h), where that class is on (kLargeManyByDefault below: not by default) and a call or chunk
-// holds at least the threshold of them.  The others, and every
-// text above kLargeMaxN, are handed to the device sorter one after another by the host drivers below.  32-bit indices
-// only (dq_sorter_i32.hip includes this file).
+// holds at least the threshold of them.  The others, and every text above kLargeMaxN, are handed to the device sorter one
+// after another by the host drivers below.  32-bit indices only (dq_sorter_i32.hip includes this file).  This file is
+// the host side; the kernels are in the headers it includes.
 #pragma once
+#include <numeric>
+
 #include "dq_large_many.h"
 #include "dq_mid_many.h"
-#include "dq_small.h"
 
 namespace dq {
 
-template <int kMaxN, int kThreads>
-__global__ __launch_bounds__(kThreads) void small_many_kernel(const uint8_t *__restrict__ texts,
-                                                              const int64_t *__restrict__ offsets,
-                                                              const int32_t *__restrict__ order, int count,
-                                                              uint32_t *__restrict__ next, int32_t *__restrict__ sas)
-{
-    using Lds = SmallLdsT<kMaxN, kThreads>;
-    __shared__ Lds L;
-    __shared__ int claimed;
-    for (;;) {
-        if (threadIdx.x == 0)
-            claimed = (int)__hip_atomic_fetch_add(next, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        const int k = claimed;
-        if (k < 0 || k >= count) return;                       // (uniform: the whole workgroup leaves)
-        const int j = order[k];
-        const int64_t at = offsets[j];
-        const int64_t n = offsets[j + 1] - at;
-        // (the host puts only texts of this class on the list; a length outside it is left alone, never sorted out of
-        // the LDS block's bounds)
-        if (n > 0 && n <= kMaxN) small_sufsort_body(L, texts + at, (int)n, sas + at);
-        // the body's last reads of L (and everybody's read of `claimed`) are over before the next text's first write
-        __syncthreads();
-    }
-}
-
 namespace {
 
-// the length classes, shortest first: {largest text, threads}.  The last short one is small_sufsort_kernel's own; the
-// medium classes (mid_many_kernel) follow the short ones.
-struct ManyClass { int max_n, threads; };
-constexpr int kManyClasses = 3;
-constexpr int kMidClasses = 2;
-constexpr int kAllClasses = kManyClasses + kMidClasses;
-constexpr ManyClass kManyClass[kAllClasses] = {{2048, 256}, {4096, 512}, {kSmallMaxN, kSmallThreads}, {32768, 512}, {kMidMaxN, 1024}};
+// The length classes, shortest first: kManyClasses short ones (small_many_kernel; the last is small_sufsort_kernel's own)
+// and kMidClasses medium ones (mid_many_kernel) behind them -- the counts are dq_runtime.h's, where DeviceCtx keeps a
+// word per class.  Nothing below names a class but by its index in this table.
+struct ManyArgs {                         // what a class's kernel is handed (the short classes take all but scratch)
+    const uint8_t *texts;
+    const int64_t *offsets;
+    const int32_t *order;
+    int count;
+    uint32_t *claim;
+    int32_t *sas;
+    char *scratch;
+};
+struct ManyClass {
+    int max_n, threads;                   // largest text; workgroup
+    const void *(*kernel)();              // for the occupancy query (a kernel's address is no constant expression)
+    void (*launch)(int grid, hipStream_t st, const ManyArgs &a);
+    size_t scratch;                       // bytes of device memory per workgroup (the medium classes' store; 0: none)
+};
+// A row is made from the class's two numbers alone: what the table says and what the kernel is built for cannot differ.
+template <int kMaxN, int kThreads>
+struct ShortClass {
+    static const void *kernel() { return (const void *)small_many_kernel<kMaxN, kThreads>; }
+    static void launch(int grid, hipStream_t st, const ManyArgs &a)
+    {
+        hipLaunchKernelGGL((small_many_kernel<kMaxN, kThreads>), dim3((unsigned)grid), dim3(kThreads), 0, st, a.texts, a.offsets,
+                           a.order, a.count, a.claim, a.sas);
+    }
+    static constexpr ManyClass row() { return {kMaxN, kThreads, kernel, launch, 0}; }
+};
+template <int kMaxN, int kThreads>
+struct MidClass {
+    static const void *kernel() { return (const void *)mid_many_kernel<kMaxN, kThreads>; }
+    static void launch(int grid, hipStream_t st, const ManyArgs &a)
+    {
+        hipLaunchKernelGGL((mid_many_kernel<kMaxN, kThreads>), dim3((unsigned)grid), dim3(kThreads), 0, st, a.texts, a.offsets,
+                           a.order, a.count, a.claim, a.sas, a.scratch);
+    }
+    static constexpr ManyClass row() { return {kMaxN, kThreads, kernel, launch, MidStore<kMaxN>::kScratchBytes}; }
+};
+constexpr ManyClass kManyClass[kAllClasses] = {
+    ShortClass<2048, 256>::row(), ShortClass<4096, 512>::row(), ShortClass<kSmallMaxN, kSmallThreads>::row(),
+    MidClass<32768, 512>::row(),  MidClass<kMidMaxN, 1024>::row(),
+};
+static_assert(kManyClass[kManyClasses - 1].max_n == kSmallMaxN && kManyClass[kAllClasses - 1].max_n == kMidMaxN,
+              "the last short and the last medium class end where the constants of dq_runtime.h say");
 
 // Fewest medium texts of a call (device form) or chunk (host form) that are worth a shared launch: one workgroup is
 // slower on one medium text than the whole device is (1.8 / 2.8 / 7.4 ms against 0.5 - 0.6 ms at 16 / 32 / 64 KiB).
@@ -78,61 +93,30 @@ constexpr int kMidManyMin = 64;
 constexpr bool kLargeManyByDefault = false;
 constexpr int kLargeManyMin = 8;
 
-template <int kC> struct ManyKernel {
-    static constexpr int kMaxN = kManyClass[kC].max_n, kThreads = kManyClass[kC].threads;
-    static constexpr bool kMid = kC >= kManyClasses;
-    static constexpr size_t kScratch = kMid ? MidLdsT<kMaxN, kThreads>::kScratchBytes : 0;
-    static const void *fn()
-    {
-        if constexpr (kMid) return (const void *)mid_many_kernel<kMaxN, kThreads>;
-        else return (const void *)small_many_kernel<kMaxN, kThreads>;
-    }
-};
-
-// workgroups of class kC the device holds at once (a wrong answer costs time only: nobody waits for anybody)
-template <int kC>
-int many_class_groups(DeviceCtx &c)
+// workgroups of class k the device holds at once (a wrong answer costs time only: nobody waits for anybody)
+inline int many_class_groups(DeviceCtx &c, int k)
 {
-    if (c.many_groups[kC] <= 0) {
+    if (c.many_groups[k] <= 0) {
         int per_cu = 0, ncu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ManyKernel<kC>::fn(), ManyKernel<kC>::kThreads, 0) != hipSuccess || per_cu <= 0)
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kManyClass[k].kernel(), kManyClass[k].threads, 0) != hipSuccess || per_cu <= 0)
             per_cu = 1;
         if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c.dev) != hipSuccess || ncu <= 0) ncu = 256;
-        c.many_groups[kC] = per_cu * ncu;
+        c.many_groups[k] = per_cu * ncu;
     }
-    return c.many_groups[kC];
-}
-
-template <int kC>
-int launch_many_class(Launcher &L, DeviceCtx &c, hipStream_t st, const uint8_t *d_texts, const int64_t *d_offsets,
-                      const int32_t *d_order, int count, int64_t text_bytes, uint32_t *d_next, int32_t *d_sas, char *d_scratch)
-{
-    constexpr int kMaxN = ManyKernel<kC>::kMaxN, kThreads = ManyKernel<kC>::kThreads;
-    const int grid = std::min(count, many_class_groups<kC>(c));
-    if constexpr (ManyKernel<kC>::kMid) {
-        LAUNCH(L, DQ_K_SMALL_MANY, count, text_bytes * 5,
-               hipLaunchKernelGGL((mid_many_kernel<kMaxN, kThreads>), dim3((unsigned)grid), dim3(kThreads), 0, st, d_texts,
-                                  d_offsets, d_order, count, d_next, d_sas, d_scratch));
-        t_many_info[4] += 1;
-    } else {
-        LAUNCH(L, DQ_K_SMALL_MANY, count, text_bytes * 5,
-               hipLaunchKernelGGL((small_many_kernel<kMaxN, kThreads>), dim3((unsigned)grid), dim3(kThreads), 0, st, d_texts,
-                                  d_offsets, d_order, count, d_next, d_sas));
-    }
-    return DQ_OK;
+    return c.many_groups[k];
 }
 
 // what the host decides about a set of texts from their offsets
 struct ManyPlan {
     std::vector<int32_t> order;                 // the classes' work lists back to back, each longest text first
-    int class_count[kAllClasses] = {0, 0, 0, 0, 0};
-    int64_t class_bytes[kAllClasses] = {0, 0, 0, 0, 0};
+    int class_count[kAllClasses] = {};
+    int64_t class_bytes[kAllClasses] = {};
     std::vector<int32_t> larges;                // texts of the segmented sorts (dq_large_many.h), in input order
     std::vector<int32_t> longs;                 // texts sorted singly, in input order: those above kLargeMaxN, and the medium and large ones that share nothing
     int64_t mid_single = 0, above_mid = 0;      // ... how many of them have medium length / are longer
-    int64_t shorts() const { return class_count[0] + class_count[1] + class_count[2]; }
-    int64_t mids() const { return class_count[3] + class_count[4]; }
+    int64_t shorts() const { return std::accumulate(class_count, class_count + kManyClasses, (int64_t)0); }
     int64_t listed() const { return (int64_t)order.size(); }
+    int64_t mids() const { return listed() - shorts(); }
     bool shared() const { return !order.empty() || !larges.empty(); }      // the plan has launches of its own
 };
 
@@ -194,7 +178,8 @@ inline ManyPlan plan_many(const int64_t *off, int32_t first, int32_t last, bool 
     if ((int64_t)mids.size() >= flags().mid_many_min.value_or(kMidManyMin)) {
         for (int32_t j : mids) {
             const int64_t n = off[j + 1] - off[j];
-            const int k = n <= kManyClass[kManyClasses].max_n ? kManyClasses : kManyClasses + 1;
+            int k = kManyClasses;
+            while (k < kAllClasses - 1 && n > kManyClass[k].max_n) ++k;
             lists[k].push_back(j);
             p.class_bytes[k] += n;
         }
@@ -233,10 +218,9 @@ inline size_t many_ctl_bytes(int64_t texts) { return kManyCounterBytes + align_u
 inline size_t many_scratch_bytes(DeviceCtx &c, const ManyPlan &plan)
 {
     size_t need = 0;
-    if (plan.class_count[3] > 0)
-        need = std::max(need, (size_t)std::min(plan.class_count[3], many_class_groups<3>(c)) * ManyKernel<3>::kScratch);
-    if (plan.class_count[4] > 0)
-        need = std::max(need, (size_t)std::min(plan.class_count[4], many_class_groups<4>(c)) * ManyKernel<4>::kScratch);
+    for (int k = 0; k < kAllClasses; ++k)
+        if (plan.class_count[k] > 0 && kManyClass[k].scratch > 0)
+            need = std::max(need, (size_t)std::min(plan.class_count[k], many_class_groups(c, k)) * kManyClass[k].scratch);
     return align_up(need);
 }
 
@@ -253,20 +237,16 @@ inline int launch_many(DeviceCtx &c, hipStream_t st, const ManyPlan &plan, const
     int32_t *d_order = reinterpret_cast<int32_t *>(d_ctl + kManyCounterBytes);
     HIP_TRY(hipMemsetAsync(d_next, 0, kManyCounterBytes, st));
     HIP_TRY(hipMemcpyAsync(d_order, plan.order.data(), plan.order.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    int at = 0, rc = DQ_OK;
-    for (int k = 0; k < kAllClasses && rc == DQ_OK; ++k) {
-        const int cnt = plan.class_count[k];
-        if (cnt == 0) continue;
-        switch (k) {
-        case 0: rc = launch_many_class<0>(L, c, st, d_texts, d_offsets, d_order + at, cnt, plan.class_bytes[k], d_next + k, d_sas, d_scratch); break;
-        case 1: rc = launch_many_class<1>(L, c, st, d_texts, d_offsets, d_order + at, cnt, plan.class_bytes[k], d_next + k, d_sas, d_scratch); break;
-        case 2: rc = launch_many_class<2>(L, c, st, d_texts, d_offsets, d_order + at, cnt, plan.class_bytes[k], d_next + k, d_sas, d_scratch); break;
-        case 3: rc = launch_many_class<3>(L, c, st, d_texts, d_offsets, d_order + at, cnt, plan.class_bytes[k], d_next + k, d_sas, d_scratch); break;
-        default: rc = launch_many_class<4>(L, c, st, d_texts, d_offsets, d_order + at, cnt, plan.class_bytes[k], d_next + k, d_sas, d_scratch); break;
-        }
-        at += cnt;
+    for (int k = 0; k < kAllClasses; ++k) {
+        const int count = plan.class_count[k];
+        if (count == 0) continue;
+        const int grid = std::min(count, many_class_groups(c, k));
+        const ManyArgs a{d_texts, d_offsets, d_order, count, d_next + k, d_sas, d_scratch};
+        LAUNCH(L, DQ_K_SMALL_MANY, count, plan.class_bytes[k] * 5, kManyClass[k].launch(grid, st, a));
+        if (k >= kManyClasses) t_many_info[4] += 1;
+        d_order += count;
     }
-    return rc;
+    return DQ_OK;
 }
 
 // Host buffers travel in chunks of at most this much text (sufsort_many_host), and a segmented sort takes at most this

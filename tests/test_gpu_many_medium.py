@@ -66,6 +66,32 @@ def test_parity_with_the_oracle(backend_lib, oracle_mod, ldss, monkeypatch, form
     assert 1 <= got["medium_launches"] <= MEDIUM_CLASSES * (longs + 1 if form == "host" else 1) and got["scratch_bytes"] > 0
 
 
+@pytest.fixture(scope="module")
+def odd_512_texts(oracle_mod):
+    """(texts, their suffix arrays by the oracle), built once for both forms."""
+    rng = np.random.default_rng(20261017)
+    lengths = [k * 512 + d for k in range(17, 64, 2) for d in (-1, 0, 1)]
+    texts = [mm.medium_text(rng, n, i) for i, n in enumerate(lengths)]
+    return texts, [oracle_mod.divsufsort(t) for t in texts]
+
+
+@pytest.mark.parametrize("form", ["host", "device"])
+def test_odd_multiples_of_512_in_the_512_thread_class(backend_lib, ldss, monkeypatch, odd_512_texts, form):
+    """The 512-thread medium class (up to 32 768 bytes) changes its positions per thread, and with them every wave's
+    block of positions, at every multiple of 512; mm.edge_lengths() has the even multiples (those of 1024) only.  Here:
+    k * 512 - 1, k * 512, k * 512 + 1 for odd k from 17 to 63, 72 texts, the kinds in turn, all in shared launches."""
+    texts, want = odd_512_texts
+    assert len(texts) == 72 and all(mm.is_medium(t.size) and t.size <= mm.CLASSES[0][0] for t in texts)
+    monkeypatch.setenv("DQ_MID_MANY_MIN", "1")
+    segs, tail = (many_host if form == "host" else many_dev)(backend_lib, texts)
+    got = info()
+    assert (tail == FILL).all(), form
+    assert len(segs) == len(texts)
+    for j, (s, w) in enumerate(zip(segs, want)):
+        assert np.array_equal(s, w), (form, j, texts[j].size)
+    assert got["medium_texts"] == 72 and got["medium_single"] == 0, got
+
+
 def test_medium_texts_share_launches(backend_lib, oracle_mod, ldss, monkeypatch):
     """1100 medium and 300 short texts under the default threshold (far more medium texts than any plausible one): every
     medium text in a medium launch, at most one launch per class.  Then three medium texts with DQ_MID_MANY_MIN=1."""
