@@ -43,6 +43,16 @@ public sealed class HipSuffixSort : ISuffixSort
     private static extern unsafe int dq_sufcheck_hip_i64(byte* text, long n, long* sa, long saLen, int* result, int device);
 
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    private static extern unsafe int dq_sufcheck_hip_many_i32(byte* texts, long* offsets, int count, int* sas, int* results, int device);
+
+    // (declared for hosts that keep their buffers on the device: device pointers, host results, a hipStream_t or zero)
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern unsafe int dq_sufcheck_hip_many_dev_i32(IntPtr dTexts, IntPtr dOffsets, int count, IntPtr dSas, int* results, int device, IntPtr stream);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    private static extern unsafe int dq_last_check_many_info(long* info, int count);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
     private static extern int dq_abi_version();
 
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
@@ -279,6 +289,95 @@ public sealed class HipSuffixSort : ISuffixSort
         }
 
         return CheckResult(rc, result, "dq_sufcheck_hip_i64");
+    }
+
+    /// <summary>
+    /// The verdicts of <see cref="Check(ReadOnlySpan{byte}, ReadOnlySpan{int})"/> for many (text, array) pairs in one
+    /// native call (dq_sufcheck_hip_many_i32): texts of up to 65 536 bytes are decided in shared launches, one
+    /// workgroup each, and the call waits for the device once per 64 MiB of text instead of once per text.  A pair
+    /// whose lengths differ gets <see cref="SuffixCheckResult.BadArguments"/> in its place without reaching the
+    /// library.  The pairs are laid back to back in managed buffers for the call, so their total is limited to what one
+    /// array holds; callers with more split their list.  No managed fallback, as for the single check.
+    /// </summary>
+    public unsafe SuffixCheckResult[] CheckMany(IReadOnlyList<ReadOnlyMemory<byte>> texts, IReadOnlyList<ReadOnlyMemory<int>> suffixes)
+    {
+        if (texts.Count != suffixes.Count)
+        {
+            throw new ArgumentException("CheckMany takes one suffix array per text");
+        }
+
+        var verdicts = new SuffixCheckResult[texts.Count];
+        var fit = new List<int>();
+        long total = 0;
+        for (int j = 0; j < texts.Count; j++)
+        {
+            if (texts[j].Length != suffixes[j].Length)
+            {
+                verdicts[j] = SuffixCheckResult.BadArguments;        // LDSSChecker.cs:29-33
+                continue;
+            }
+
+            fit.Add(j);
+            total += texts[j].Length;
+        }
+
+        if (fit.Count == 0)
+        {
+            return verdicts;
+        }
+
+        if (total > Array.MaxLength)
+        {
+            throw new ArgumentException("the texts of one CheckMany call must total less than 2^31 bytes");
+        }
+
+        // (at least one element each: the native side wants non-null pointers whenever there are texts)
+        var offsets = new long[fit.Count + 1];
+        byte[] flat = new byte[Math.Max(total, 1)];
+        int[] sas = new int[Math.Max(total, 1)];
+        int[] results = new int[fit.Count];
+        for (int k = 0; k < fit.Count; k++)
+        {
+            int j = fit[k];
+            texts[j].Span.CopyTo(flat.AsSpan((int)offsets[k], texts[j].Length));
+            suffixes[j].Span.CopyTo(sas.AsSpan((int)offsets[k], texts[j].Length));
+            offsets[k + 1] = offsets[k] + texts[j].Length;
+        }
+
+        int rc;
+        fixed (byte* pTexts = flat)
+        fixed (long* pOffsets = offsets)
+        fixed (int* pSas = sas)
+        fixed (int* pResults = results)
+        {
+            rc = dq_sufcheck_hip_many_i32(pTexts, pOffsets, fit.Count, pSas, pResults, _device);
+        }
+
+        for (int k = 0; k < fit.Count; k++)
+        {
+            verdicts[fit[k]] = CheckResult(rc, results[k], "dq_sufcheck_hip_many_i32");
+        }
+
+        return verdicts;
+    }
+
+    /// <summary>
+    /// Shape of the last CheckMany on this thread (dq_last_check_many_info): texts checked in shared launches, texts
+    /// checked by the single-text kernels, launches of the shared kernel, chunks, stream waits.
+    /// </summary>
+    public static unsafe long[] LastCheckManyInfo()
+    {
+        var info = new long[5];
+        fixed (long* p = info)
+        {
+            int rc = dq_last_check_many_info(p, info.Length);
+            if (rc != 0)
+            {
+                throw new InvalidOperationException($"dq_last_check_many_info failed ({rc})");
+            }
+        }
+
+        return info;
     }
 
     private static SuffixCheckResult CheckResult(int rc, int result, string entry)

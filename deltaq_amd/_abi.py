@@ -44,6 +44,7 @@ EXPORTS = (
     "dq_sufsort_hip_batch_i32",
     "dq_sufsort_hip_many_i32", "dq_sufsort_hip_many_dev_i32", "dq_last_many_info",
     "dq_sufcheck_hip_i32", "dq_sufcheck_hip_i64", "dq_sufcheck_hip_dev_i32", "dq_sufcheck_hip_dev_i64",
+    "dq_sufcheck_hip_many_i32", "dq_sufcheck_hip_many_dev_i32", "dq_last_check_many_info",
     "dq_bsdiff_search_dev_i32", "dq_bsdiff_search_dev_i64", "dq_bsdiff_search_i32", "dq_bsdiff_search_i64",
     "dq_bsdiff_create", "dq_bsdiff_patch_bound", "dq_bsdiff_scan_i32", "dq_bspatch_apply",
     "dq_bsdiff_create_many", "dq_last_diff_many_info",
@@ -119,6 +120,12 @@ def load() -> ctypes.CDLL:
     for name in ("dq_sufcheck_hip_dev_i32", "dq_sufcheck_hip_dev_i64"):
         getattr(L, name).restype = i32
         getattr(L, name).argtypes = [vp, i64, vp, i64, ctypes.POINTER(i32), i32, vp]
+    L.dq_sufcheck_hip_many_i32.restype = i32
+    L.dq_sufcheck_hip_many_i32.argtypes = [vp, vp, i32, vp, vp, i32]
+    L.dq_sufcheck_hip_many_dev_i32.restype = i32
+    L.dq_sufcheck_hip_many_dev_i32.argtypes = [vp, vp, i32, vp, vp, i32, vp]
+    L.dq_last_check_many_info.restype = i32
+    L.dq_last_check_many_info.argtypes = [ctypes.POINTER(i64), i32]
     L.dq_sufsort_hip_batch_i32.restype = i32
     L.dq_sufsort_hip_batch_i32.argtypes = [i32, vp, vp, vp, i32, vp]
     L.dq_sufsort_hip_many_i32.restype = i32
@@ -276,6 +283,14 @@ def last_many_large_info() -> dict:
     v = (ctypes.c_int64 * 9)()
     check(L.dq_last_many_info(v, 9))
     return {"large_texts": v[6], "segmented_sorts": v[7], "list_entries": v[8]}
+
+
+def last_check_many_info() -> dict:
+    """Shape of the last dq_sufcheck_hip_many_* on this thread (dq_last_check_many_info)."""
+    L = load()
+    v = (ctypes.c_int64 * 5)()
+    check(L.dq_last_check_many_info(v, 5))
+    return {"shared_texts": v[0], "single_texts": v[1], "launches": v[2], "chunks": v[3], "stream_waits": v[4]}
 
 
 def last_batch_info() -> dict:

@@ -292,6 +292,30 @@ int32_t dq_sufcheck_hip_dev_i64(const void *d_text, int64_t n, const void *d_sa,
     return sufcheck_dev<int64_t>(d_text, n, d_sa, sa_len, result, device, stream);
 }
 
+int32_t dq_sufcheck_hip_many_i32(const uint8_t *texts, const int64_t *offsets, int32_t count, const int32_t *sas,
+                                 int32_t *results, int32_t device)
+{
+    EnvScope scope;
+    for (int64_t &x : t_check_many_info) x = 0;
+    try {
+        return sufcheck_many_host(texts, offsets, count, sas, results, device);
+    } catch (const std::bad_alloc &) {             // nothing may propagate through the C ABI
+        return fail(DQ_ERR_OOM, "check many: host allocation failed");
+    }
+}
+
+int32_t dq_sufcheck_hip_many_dev_i32(const void *d_texts, const void *d_offsets, int32_t count, const void *d_sas,
+                                     int32_t *results, int32_t device, void *stream)
+{
+    EnvScope scope;
+    for (int64_t &x : t_check_many_info) x = 0;
+    try {
+        return sufcheck_many_dev(d_texts, d_offsets, count, d_sas, results, device, stream);
+    } catch (const std::bad_alloc &) {
+        return fail(DQ_ERR_OOM, "check many: host allocation failed");
+    }
+}
+
 int32_t dq_sufsort_hip_batch_i32(int32_t count, const uint8_t *const *texts, const int64_t *lens,
                                  int32_t *const *sas, int32_t ndev, const int32_t *devs)
 {
@@ -700,6 +724,13 @@ int32_t dq_last_many_info(int64_t *info, int32_t count)
 {
     if (!info || count < 0) return fail(DQ_ERR_BAD_ARGS, "bad arguments");
     for (int32_t k = 0; k < count; ++k) info[k] = k < 9 ? t_many_info[k] : 0;
+    return DQ_OK;
+}
+
+int32_t dq_last_check_many_info(int64_t *info, int32_t count)
+{
+    if (!info || count < 0) return fail(DQ_ERR_BAD_ARGS, "null info array");
+    for (int32_t k = 0; k < count; ++k) info[k] = k < 5 ? t_check_many_info[k] : 0;
     return DQ_OK;
 }
 

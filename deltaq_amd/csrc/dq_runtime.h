@@ -37,6 +37,11 @@ constexpr int kMidMaxN = 65536;           // largest text of the medium class of
 // length classes of the many-texts launches: up to kSmallMaxN, from there to kMidMaxN (the table: dq_small_many.h)
 constexpr int kManyClasses = 3, kMidClasses = 2, kAllClasses = kManyClasses + kMidClasses;
 constexpr int kLargeMaxN = 4 << 20;       // largest text of their segmented sort (dq_large_many.h; the figures: dq_small_many.h)
+constexpr int kCheckClasses = 3;          // length classes of the many-texts check (the table: dq_sufcheck.hip)
+// Host buffers of the many-texts calls travel in chunks of whole texts: at most this much text, at most this many texts
+// (sufsort_many_host, sufcheck_many_host); a segmented sort takes at most this much large text.
+constexpr int64_t kManyChunkBytes = 64ll << 20;
+constexpr int32_t kManyChunkTexts = 1 << 20;
 
 // ------------------------------------------------------------------ errors
 inline thread_local std::string t_err;
@@ -51,6 +56,9 @@ inline thread_local int64_t t_index_many_info[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; 
 // singly, launches of mid_many_kernel, bytes of per-workgroup scratch carved for them, texts sorted in segmented sorts
 // (dq_large_many.h), segmented sorts run, their list lengths summed over all rounds (round 0 counting the batch's bytes)
 inline thread_local int64_t t_many_info[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+// the last dq_sufcheck_hip_many_* on this thread (dq_last_check_many_info): texts checked in shared launches, texts checked
+// by the single-text kernels, launches of sufcheck_many_kernel, chunks of the host form, stream waits for verdicts
+inline thread_local int64_t t_check_many_info[5] = {0, 0, 0, 0, 0};
 
 // the last dq_sufsort_hip_batch_i32 on this thread (dq_last_batch_info): inputs through the pipelines, microseconds the
 // copy-in / sort / copy-out stages were busy (summed over the device shares), wall microseconds of the slowest share,
@@ -111,6 +119,7 @@ struct DeviceCtx {
     int dev = -1;
     int ncu = 0;                        // compute units of the device (grid of the persistent kernels)
     int many_groups[kAllClasses] = {};  // workgroups of each length class of small_many_kernel and mid_many_kernel the device holds at once (0: not asked yet)
+    int check_many_groups[kCheckClasses] = {};  // ... and of each length class of sufcheck_many_kernel (dq_sufcheck_many.h)
     int anchor_many_groups = 0;         // ... and of anchor_many_kernel (dq_anchor_many.h)
     int anchor_mid_many_groups = 0;     // ... and of anchor_mid_many_kernel
     int anchor_index_many_groups[2] = {0, 0};   // ... and of anchor_index_many_kernel at 256 and 512 threads (dq_anchor_many.h)
@@ -309,6 +318,18 @@ inline int resolve_device(int32_t device, int *out)
     return DQ_OK;
 }
 
+// offsets[0 .. count] of a many-texts call: starts at 0, never decreases, no text of 2^31 bytes or more
+inline int check_many_offsets(const int64_t *off, int32_t count)
+{
+    if (off[0] != 0) return fail(DQ_ERR_BAD_ARGS, "offsets[0] must be 0");
+    for (int32_t j = 0; j < count; ++j) {
+        if (off[j + 1] < off[j]) return fail(DQ_ERR_BAD_ARGS, "offsets must not decrease");
+        if (off[j + 1] - off[j] > 0x7fffffffLL)
+            return fail(DQ_ERR_TOO_LARGE, "a text exceeds 2^31-1 bytes: the many-texts entry points have 32-bit indices");
+    }
+    return DQ_OK;
+}
+
 // ------------------------------------------------------------------ NUMA placement of a device's host threads
 // The batch pipeline's stage threads copy through pageable host memory: 8 devices x 50+ GB/s of staged copies meet in
 // host memory, and a thread on the far socket pays the inter-socket link both ways.  Each device's threads are
@@ -428,6 +449,12 @@ extern template int sufcheck_host<int32_t>(const uint8_t *, int64_t, const int32
 extern template int sufcheck_host<int64_t>(const uint8_t *, int64_t, const int64_t *, int64_t, int32_t *, int32_t);
 extern template int sufcheck_dev<int32_t>(const void *, int64_t, const void *, int64_t, int32_t *, int32_t, void *);
 extern template int sufcheck_dev<int64_t>(const void *, int64_t, const void *, int64_t, int32_t *, int32_t, void *);
+// ... of many suffix arrays in shared launches (dq_sufcheck_many.h): the bodies of dq_sufcheck_hip_many_i32 / _many_dev_i32;
+// results[j] = the verdict of text j.  Both fill t_check_many_info; the entry point resets it.
+int sufcheck_many_host(const uint8_t *texts, const int64_t *offsets, int32_t count, const int32_t *sas, int32_t *results,
+                       int32_t device);
+int sufcheck_many_dev(const void *d_texts, const void *d_offsets, int32_t count, const void *d_sas, int32_t *results,
+                      int32_t device, void *stream);
 
 // match search + BSDIFF40 (dq_diff.hip)
 int match_search_dev_i32(const void *d_old, int64_t n, const void *d_sa, const void *d_new, int64_t m, const int64_t *d_scans,

@@ -249,10 +249,8 @@ inline int launch_many(DeviceCtx &c, hipStream_t st, const ManyPlan &plan, const
     return DQ_OK;
 }
 
-// Host buffers travel in chunks of at most this much text (sufsort_many_host), and a segmented sort takes at most this
-// much large text: fewer than kLargeSegMax texts above kMidMaxN.
-constexpr int64_t kManyChunkBytes = 64ll << 20;
-constexpr int32_t kManyChunkTexts = 1 << 20;
+// (kManyChunkBytes, kManyChunkTexts: dq_runtime.h) A segmented sort takes at most kManyChunkBytes of large text: fewer than
+// kLargeSegMax texts above kMidMaxN.
 static_assert(kManyChunkBytes / (kMidMaxN + 1) < kLargeSegMax, "a batch's segment ordinals fit 10 bits");
 static_assert(kLargeMaxN > kMidMaxN && kLargeMaxN <= kManyChunkBytes, "a large text fits a batch");
 
@@ -327,18 +325,6 @@ inline int many_single_dev(const uint8_t *d_text, int64_t n, int32_t *d_sa, int 
     rc = sufsort_small<int32_t>(c, st, d_text, n, d_sa);
     if (rc != DQ_OK) drop_pending(c, st);
     return rc;
-}
-
-// offsets[0 .. count]: starts at 0, never decreases, no text of 2^31 bytes or more
-inline int check_many_offsets(const int64_t *off, int32_t count)
-{
-    if (off[0] != 0) return fail(DQ_ERR_BAD_ARGS, "offsets[0] must be 0");
-    for (int32_t j = 0; j < count; ++j) {
-        if (off[j + 1] < off[j]) return fail(DQ_ERR_BAD_ARGS, "offsets must not decrease");
-        if (off[j + 1] - off[j] > 0x7fffffffLL)
-            return fail(DQ_ERR_TOO_LARGE, "a text exceeds 2^31-1 bytes: the many-texts entry points have 32-bit indices");
-    }
-    return DQ_OK;
 }
 
 inline bool many_one_by_one() { return flags().no_many.value_or(0) == 1; }

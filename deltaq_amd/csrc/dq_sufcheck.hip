@@ -2,8 +2,12 @@
 // Same conventions as the sorter's entry points: the arguments are checked before any device work, the call holds a
 // slot of the device (SlotLease) and carves its scratch from that slot's cached workspace, so a check that follows a
 // sort on the same slot allocates nothing.
+// dq_sufcheck_hip_many_*: many suffix arrays in one call, those of texts of up to 65 536 bytes in shared launches
+// (dq_sufcheck_many.h), the longer ones by the two kernels of dq_sufcheck.h on the same stream; one wait for all verdicts.
+#include <numeric>
+
 #include "dq_runtime.h"
-#include "dq_sufcheck.h"
+#include "dq_sufcheck_many.h"
 
 namespace dq {
 namespace {
@@ -26,6 +30,28 @@ int sufcheck_args(const void *text, int64_t n, const void *sa, int64_t sa_len, i
     return DQ_OK;
 }
 
+// LDSSChecker's verdict from the bits the kernels raised, by its priority
+inline int32_t sufcheck_verdict(uint32_t bits)
+{
+    return (bits & kCheckOutOfRange) ? DQ_SUFCHECK_OUT_OF_RANGE
+         : (bits & kCheckOrder)      ? DQ_SUFCHECK_WRONG_ORDER
+         : (bits & kCheckPosition)   ? DQ_SUFCHECK_WRONG_POSITION
+                                     : DQ_SUFCHECK_DONE;
+}
+
+// both passes on st; `flags` is zero when they start (stream order), isa holds n words
+template <typename IdxT>
+int sufcheck_launch(hipStream_t st, const uint8_t *d_text, int64_t n, const IdxT *d_sa, uint32_t *isa, uint32_t *flags)
+{
+    const int64_t blocks = sufcheck_blocks(n);
+    hipLaunchKernelGGL(sufcheck_scatter_kernel<IdxT>, dim3((unsigned)blocks), dim3(kBlock), 0, st, d_sa, n, isa, flags);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(sufcheck_pair_kernel<IdxT>, dim3((unsigned)blocks), dim3(kBlock), 0, st, d_text, d_sa, n,
+                       (const uint32_t *)isa, flags);
+    HIP_TRY(hipGetLastError());
+    return DQ_OK;
+}
+
 // both passes on st, then the flag word back to the host
 template <typename IdxT>
 int sufcheck_run(DeviceCtx &c, hipStream_t st, const uint8_t *d_text, int64_t n, const IdxT *d_sa, char *scratch,
@@ -33,21 +59,13 @@ int sufcheck_run(DeviceCtx &c, hipStream_t st, const uint8_t *d_text, int64_t n,
 {
     uint32_t *flags = reinterpret_cast<uint32_t *>(scratch);
     uint32_t *isa = reinterpret_cast<uint32_t *>(scratch + 256);
-    const int64_t blocks = sufcheck_blocks(n);
     HIP_TRY(hipMemsetAsync(flags, 0, sizeof(uint32_t), st));
-    hipLaunchKernelGGL(sufcheck_scatter_kernel<IdxT>, dim3((unsigned)blocks), dim3(kBlock), 0, st, d_sa, n, isa, flags);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(sufcheck_pair_kernel<IdxT>, dim3((unsigned)blocks), dim3(kBlock), 0, st, d_text, d_sa, n,
-                       (const uint32_t *)isa, flags);
-    HIP_TRY(hipGetLastError());
+    const int rc = sufcheck_launch<IdxT>(st, d_text, n, d_sa, isa, flags);
+    if (rc != DQ_OK) return rc;
     uint32_t *back = reinterpret_cast<uint32_t *>(c.pinned);
     HIP_TRY(hipMemcpyAsync(back, flags, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    const uint32_t bits = *back;
-    *result = (bits & kCheckOutOfRange) ? DQ_SUFCHECK_OUT_OF_RANGE
-            : (bits & kCheckOrder)      ? DQ_SUFCHECK_WRONG_ORDER
-            : (bits & kCheckPosition)   ? DQ_SUFCHECK_WRONG_POSITION
-                                        : DQ_SUFCHECK_DONE;
+    *result = sufcheck_verdict(*back);
     return DQ_OK;
 }
 
@@ -106,6 +124,278 @@ int sufcheck_dev(const void *d_text, int64_t n, const void *d_sa, int64_t sa_len
     rc = sufcheck_run<IdxT>(c, st, (const uint8_t *)d_text, n, (const IdxT *)d_sa, c.ws, result);
     if (rc != DQ_OK) (void)hipStreamSynchronize(st);
     return rc;
+}
+
+// ====================================================================== many suffix arrays in one call
+namespace {
+
+// The length classes of sufcheck_many_kernel, shortest first (kCheckClasses of them: DeviceCtx keeps a word per class).
+// Up to 32 768 bytes text and 16-bit ranks are both in LDS (24 KiB at 256 threads: several workgroups per CU; 96 KiB at
+// 512); up to 65 536 the ranks alone (128 KiB, 1024 threads) and the text is read from device memory, where 64 KiB stay
+// in L2.  A row is made from the class's two numbers alone, as kManyClass's are.
+struct CheckArgs {
+    const uint8_t *texts;
+    const int64_t *offsets;
+    const int32_t *order;
+    int count;
+    uint32_t *claim;
+    const int32_t *sas;
+    uint32_t *results;
+};
+struct CheckClass {
+    int max_n, threads;
+    int min_texts;                        // fewest texts of the class in a call / chunk that share its launch (below)
+    const void *(*kernel)();
+    void (*launch)(int grid, hipStream_t st, const CheckArgs &a);
+};
+template <int kMaxN, int kThreads>
+struct CheckRow {
+    static const void *kernel() { return (const void *)sufcheck_many_kernel<kMaxN, kThreads>; }
+    static void launch(int grid, hipStream_t st, const CheckArgs &a)
+    {
+        hipLaunchKernelGGL((sufcheck_many_kernel<kMaxN, kThreads>), dim3((unsigned)grid), dim3(kThreads), 0, st, a.texts,
+                           a.offsets, a.order, a.count, a.claim, a.sas, a.results);
+    }
+    static constexpr CheckClass row(int min_texts) { return {kMaxN, kThreads, min_texts, kernel, launch}; }
+};
+// min_texts: one workgroup replaces a memset and two launches, but on a long text it is slower than the whole device:
+// where a class loses to the single-text kernels at small counts (tools/kbench/check_many.py, the sweep with
+// DQ_NO_CHECK_MANY=0 against the loop), fewer texts of it than twice the largest crossing, rounded up to a power of two,
+// go to those kernels -- inside the same call, on the same stream, still one wait.
+constexpr CheckClass kCheckClass[kCheckClasses] = {CheckRow<8192, 256>::row(1), CheckRow<32768, 512>::row(1),
+                                                   CheckRow<kMidMaxN, 1024>::row(1)};
+constexpr int64_t kCheckManyMaxN = kCheckClass[kCheckClasses - 1].max_n;
+
+// workgroups of class k the device holds at once (a wrong answer costs time only: nobody waits for anybody)
+inline int check_class_groups(DeviceCtx &c, int k)
+{
+    if (c.check_many_groups[k] <= 0) {
+        int per_cu = 0, ncu = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kCheckClass[k].kernel(), kCheckClass[k].threads, 0) != hipSuccess || per_cu <= 0)
+            per_cu = 1;
+        if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c.dev) != hipSuccess || ncu <= 0) ncu = 256;
+        c.check_many_groups[k] = per_cu * ncu;
+    }
+    return c.check_many_groups[k];
+}
+
+// what the host decides about texts [0, count) from their offsets
+struct CheckPlan {
+    std::vector<int32_t> order;                 // the classes' work lists back to back, each longest text first
+    int class_count[kCheckClasses] = {};
+    std::vector<int32_t> longs;                 // in input order: texts of the single-text kernels -- those above kCheckManyMaxN, and those of a class with too few
+    int64_t longest = 0;                        // ... the longest of them
+};
+
+inline CheckPlan plan_check(const int64_t *off, int32_t count)
+{
+    CheckPlan p;
+    std::vector<int32_t> lists[kCheckClasses];
+    for (int32_t j = 0; j < count; ++j) {
+        const int64_t n = off[j + 1] - off[j];
+        if (n == 0) continue;                   // DONE without device work: its result word stays 0
+        if (n > kCheckManyMaxN) { p.longs.push_back(j); continue; }
+        int k = 0;
+        while (n > kCheckClass[k].max_n) ++k;
+        lists[k].push_back(j);
+    }
+    const bool forced = flags().no_check_many.value_or(1) == 0;
+    for (int k = 0; k < kCheckClasses; ++k) {
+        if (!forced && !lists[k].empty() && (int)lists[k].size() < kCheckClass[k].min_texts) {
+            const size_t at = p.longs.size();
+            p.longs.insert(p.longs.end(), lists[k].begin(), lists[k].end());
+            std::inplace_merge(p.longs.begin(), p.longs.begin() + (ptrdiff_t)at, p.longs.end());
+            lists[k].clear();
+        }
+    }
+    for (int32_t j : p.longs) p.longest = std::max(p.longest, off[j + 1] - off[j]);
+    for (int k = 0; k < kCheckClasses; ++k) {
+        std::stable_sort(lists[k].begin(), lists[k].end(),
+                         [&](int32_t a, int32_t b) { return off[a + 1] - off[a] > off[b + 1] - off[b]; });
+        p.class_count[k] = (int)lists[k].size();
+        p.order.insert(p.order.end(), lists[k].begin(), lists[k].end());
+    }
+    return p;
+}
+
+// Scratch of a plan: one claim word per class (a 256-byte line), one result word per text, the work lists, and the
+// single-text kernels' inverse array -- 4 bytes per byte of the longest long text, shared by all of them (stream order).
+struct CheckScratch {
+    size_t results_at, order_at, isa_at, bytes;
+    CheckScratch(const CheckPlan &p, int32_t count)
+    {
+        results_at = 256;
+        order_at = results_at + align_up((size_t)count * sizeof(uint32_t));
+        isa_at = order_at + align_up(p.order.size() * sizeof(int32_t));
+        bytes = isa_at + align_up((size_t)p.longest * sizeof(uint32_t));
+    }
+};
+
+// Everything a plan needs on st, up to the copy of the result words into results[0 .. count): enqueues only.  `off` is
+// the host's copy of d_offsets; the caller waits for the stream (keeping the plan until then) and maps the words.
+inline int launch_check(DeviceCtx &c, hipStream_t st, const CheckPlan &plan, const int64_t *off, int32_t count,
+                        const uint8_t *d_texts, const int64_t *d_offsets, const int32_t *d_sas, char *scratch, int32_t *results)
+{
+    const CheckScratch at(plan, count);
+    uint32_t *d_next = reinterpret_cast<uint32_t *>(scratch);
+    uint32_t *d_results = reinterpret_cast<uint32_t *>(scratch + at.results_at);
+    int32_t *d_order = reinterpret_cast<int32_t *>(scratch + at.order_at);
+    HIP_TRY(hipMemsetAsync(scratch, 0, at.order_at, st));                       // claim words and result words
+    if (!plan.order.empty())
+        HIP_TRY(hipMemcpyAsync(d_order, plan.order.data(), plan.order.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    for (int k = 0; k < kCheckClasses; ++k) {
+        const int cnt = plan.class_count[k];
+        if (cnt == 0) continue;
+        const CheckArgs a{d_texts, d_offsets, d_order, cnt, d_next + k, d_sas, d_results};
+        kCheckClass[k].launch(std::min(cnt, check_class_groups(c, k)), st, a);
+        HIP_TRY(hipGetLastError());
+        t_check_many_info[2] += 1;
+        d_order += cnt;
+    }
+    for (int32_t j : plan.longs) {
+        const int rc = sufcheck_launch<int32_t>(st, d_texts + off[j], off[j + 1] - off[j], d_sas + off[j],
+                                                reinterpret_cast<uint32_t *>(scratch + at.isa_at), d_results + j);
+        if (rc != DQ_OK) return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(results, d_results, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    return DQ_OK;
+}
+
+inline void check_account(const CheckPlan &plan, int32_t *results, int32_t count)
+{
+    for (int32_t j = 0; j < count; ++j) results[j] = sufcheck_verdict((uint32_t)results[j]);
+    t_check_many_info[0] += (int64_t)plan.order.size();
+    t_check_many_info[1] += (int64_t)plan.longs.size();
+    t_check_many_info[4] += 1;
+}
+
+inline bool check_one_by_one() { return flags().no_check_many.value_or(0) == 1; }
+
+}  // namespace
+
+// device buffers in, the verdicts to the host: one fetch of the offsets, then one wait for the whole call
+int sufcheck_many_dev(const void *d_texts_v, const void *d_offsets_v, int32_t count, const void *d_sas_v, int32_t *results,
+                      int32_t device, void *stream)
+{
+    if (count < 0) return fail(DQ_ERR_BAD_ARGS, "negative count");
+    if (count == 0) return DQ_OK;
+    if (!d_texts_v || !d_offsets_v || !d_sas_v || !results) return fail(DQ_ERR_BAD_ARGS, "null buffer");
+    const uint8_t *d_texts = (const uint8_t *)d_texts_v;
+    const int64_t *d_offsets = (const int64_t *)d_offsets_v;
+    const int32_t *d_sas = (const int32_t *)d_sas_v;
+    int dev = 0;
+    int rc = resolve_device(device, &dev);
+    if (rc != DQ_OK) return rc;
+    std::vector<int64_t> off((size_t)count + 1);
+    {
+        SlotLease lease(dev, 0);
+        DeviceCtx &c = *lease.c;
+        rc = init_ctx(c, dev);
+        if (rc != DQ_OK) return rc;
+        hipStream_t st = stream ? (hipStream_t)stream : c.stream;
+        // the offsets come to the host once, to plan the launches (and to be checked before anything is launched)
+        HIP_TRY(hipMemcpyAsync(off.data(), d_offsets, off.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        rc = check_many_offsets(off.data(), count);
+        if (rc != DQ_OK) return rc;
+    }   // (the slot is given back: the call below leases the one its longest text needs)
+    if (check_one_by_one()) {
+        for (int32_t j = 0; j < count; ++j) {
+            const int64_t n = off[j + 1] - off[j];
+            rc = sufcheck_dev<int32_t>(d_texts + off[j], n, d_sas + off[j], n, results + j, dev, stream);
+            if (rc != DQ_OK) return rc;
+            t_check_many_info[1] += 1;
+            t_check_many_info[4] += n > 0 ? 1 : 0;
+        }
+        return DQ_OK;
+    }
+    const CheckPlan plan = plan_check(off.data(), count);
+    if (plan.order.empty() && plan.longs.empty()) {             // nothing but empty texts
+        std::fill(results, results + count, DQ_SUFCHECK_DONE);
+        return DQ_OK;
+    }
+    SlotLease lease(dev, plan.longest);
+    DeviceCtx &c = *lease.c;
+    rc = init_ctx(c, dev);
+    if (rc != DQ_OK) return rc;
+    rc = ensure_ws(c, CheckScratch(plan, count).bytes);
+    if (rc != DQ_OK) return rc;
+    hipStream_t st = stream ? (hipStream_t)stream : c.stream;
+    rc = launch_check(c, st, plan, off.data(), count, d_texts, d_offsets, d_sas, c.ws, results);
+    // (one checked step: a failure must not leave a copy into the caller's array in flight behind the return)
+    const hipError_t e = hipStreamSynchronize(st);
+    if (rc != DQ_OK) return rc;
+    HIP_TRY(e);
+    check_account(plan, results, count);
+    return DQ_OK;
+}
+
+// Host buffers in.  Runs of whole texts travel in chunks of at most kManyChunkBytes of text (and four times as much of
+// suffix arrays): copies in, the launches, the result words back, one wait per chunk.  A text that is longer than a
+// chunk goes through sufcheck_host's own path.
+int sufcheck_many_host(const uint8_t *texts, const int64_t *offsets, int32_t count, const int32_t *sas, int32_t *results,
+                       int32_t device)
+{
+    if (count < 0) return fail(DQ_ERR_BAD_ARGS, "negative count");
+    if (count == 0) return DQ_OK;
+    if (!texts || !offsets || !sas || !results) return fail(DQ_ERR_BAD_ARGS, "null buffer");
+    int rc = check_many_offsets(offsets, count);
+    if (rc != DQ_OK) return rc;
+    int dev = 0;
+    rc = resolve_device(device, &dev);
+    if (rc != DQ_OK) return rc;
+    const bool one_by_one = check_one_by_one();
+    std::vector<int64_t> rel;
+    for (int32_t i = 0; i < count;) {
+        const int64_t n = offsets[i + 1] - offsets[i];
+        if (n > kManyChunkBytes || one_by_one) {
+            rc = sufcheck_host<int32_t>(texts + offsets[i], n, sas + offsets[i], n, results + i, dev);
+            if (rc != DQ_OK) return rc;
+            t_check_many_info[1] += 1;
+            t_check_many_info[4] += n > 0 ? 1 : 0;
+            ++i;
+            continue;
+        }
+        // the chunk: texts [i, e), back to back in the caller's buffers
+        int32_t e = i;
+        while (e < count && e - i < kManyChunkTexts && offsets[e + 1] - offsets[i] <= kManyChunkBytes) ++e;
+        const int64_t base = offsets[i], bytes = offsets[e] - base;
+        const int32_t cnt = e - i;
+        if (bytes == 0) {
+            std::fill(results + i, results + e, DQ_SUFCHECK_DONE);
+            i = e;
+            continue;
+        }
+        rel.resize((size_t)cnt + 1);
+        for (int32_t j = 0; j <= cnt; ++j) rel[(size_t)j] = offsets[i + j] - base;
+        const CheckPlan plan = plan_check(rel.data(), cnt);
+        SlotLease lease(dev, bytes);
+        DeviceCtx &c = *lease.c;
+        rc = init_ctx(c, dev);
+        if (rc != DQ_OK) return rc;
+        const size_t b_scratch = CheckScratch(plan, cnt).bytes, b_sa = align_up((size_t)bytes * sizeof(int32_t)),
+                     b_text = align_up((size_t)bytes), b_off = align_up(rel.size() * sizeof(int64_t));
+        rc = ensure_ws(c, b_scratch + b_sa + b_text + b_off);
+        if (rc != DQ_OK) return rc;
+        hipStream_t st = c.stream;
+        int32_t *d_sa = reinterpret_cast<int32_t *>(c.ws + b_scratch);
+        uint8_t *d_text = reinterpret_cast<uint8_t *>(c.ws + b_scratch + b_sa);
+        int64_t *d_off = reinterpret_cast<int64_t *>(c.ws + b_scratch + b_sa + b_text);
+        auto run = [&]() -> int {
+            HIP_TRY(hipMemcpyAsync(d_sa, sas + base, (size_t)bytes * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(d_text, texts + base, (size_t)bytes, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(d_off, rel.data(), rel.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+            return launch_check(c, st, plan, rel.data(), cnt, d_text, d_off, d_sa, c.ws, results + i);
+        };
+        rc = run();
+        const hipError_t err = hipStreamSynchronize(st);         // (nothing of the chunk stays in flight behind a failure)
+        if (rc != DQ_OK) return rc;
+        HIP_TRY(err);
+        check_account(plan, results + i, cnt);
+        t_check_many_info[3] += 1;
+        i = e;
+    }
+    return DQ_OK;
 }
 
 template int sufcheck_host<int32_t>(const uint8_t *, int64_t, const int32_t *, int64_t, int32_t *, int32_t);

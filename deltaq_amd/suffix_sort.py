@@ -219,6 +219,75 @@ class HipSuffixSort:
                       dev, stream))
         return res.value
 
+    # -- LDSSChecker.Check of many (text, array) pairs in one call (no counterpart in the reference) -----------------
+    def CheckMany(self, texts, suffixes) -> np.ndarray:
+        """The verdicts of ``Check`` for many pairs, as one int32 array: texts of up to 65 536 bytes are decided in
+        shared launches, one workgroup each, and the call waits for the device once (per 64 MiB of text in the host
+        form) instead of once per text (``_abi.last_check_many_info()`` tells what happened).
+
+        ``CheckMany([t0, t1, ...], [sa0, sa1, ...])`` -- bytes-like objects / numpy uint8 arrays and numpy int32 arrays,
+        two equally long lists -- goes through ``dq_sufcheck_hip_many_i32``; a pair whose lengths differ gets
+        ``CHECK_BAD_ARGUMENTS`` in its place, as from ``Check``.  ``CheckMany((texts_tensor, offsets_tensor),
+        sas_tensor)`` -- torch GPU tensors in ``SortMany``'s device layout -- goes through
+        ``dq_sufcheck_hip_many_dev_i32`` on the current torch stream.
+        """
+        if isinstance(texts, tuple) and len(texts) == 2 and _is_torch_tensor(texts[0]):
+            return self._check_many_device(texts[0], texts[1], suffixes)
+        arrs = [_as_text(t) for t in texts]
+        sas = list(suffixes)
+        if len(sas) != len(arrs):
+            raise ValueError("CheckMany takes one suffix array per text")
+        if any(a.ndim != 1 for a in arrs):
+            raise TypeError("every text must be one-dimensional")
+        if any(not isinstance(s, np.ndarray) or s.dtype != np.int32 or s.ndim != 1 for s in sas):
+            raise TypeError("every suffix array must be a 1-D numpy int32 array")
+        if any(a.size > INT_MAX for a in arrs):
+            raise ValueError("CheckMany has 32-bit indices: every text must be shorter than 2^31 bytes")
+        out = np.full(len(arrs), CHECK_BAD_ARGUMENTS, dtype=np.int32)
+        fit = [j for j in range(len(arrs)) if arrs[j].size == sas[j].size]       # (the others: Check's verdict, LDSSChecker.cs:29-33)
+        if not fit:
+            return out
+        off = np.zeros(len(fit) + 1, dtype=np.int64)
+        np.cumsum([arrs[j].size for j in fit], out=off[1:])
+        total = int(off[-1])
+        # (a buffer of no bytes has no address: the library wants non-null pointers whenever there are texts)
+        flat = np.concatenate([arrs[j] for j in fit]) if total else np.zeros(1, np.uint8)
+        flat_sa = np.concatenate([sas[j] for j in fit]) if total else np.zeros(1, np.int32)
+        res = np.empty(len(fit), dtype=np.int32)
+        _abi.check(self._lib.dq_sufcheck_hip_many_i32(flat.ctypes.data, off.ctypes.data, len(fit), flat_sa.ctypes.data,
+                                                      res.ctypes.data, self.device))
+        out[fit] = res
+        return out
+
+    check_many = CheckMany
+
+    def _check_many_device(self, texts, offsets, sas) -> np.ndarray:
+        import torch
+
+        if not _is_torch_tensor(offsets) or not _is_torch_tensor(sas):
+            raise TypeError("device texts need device offsets and suffix array tensors")
+        if texts.dtype != torch.uint8 or texts.dim() != 1 or not texts.is_contiguous():
+            raise TypeError("device texts must be a contiguous 1-D uint8 tensor")
+        if offsets.dtype != torch.int64 or offsets.dim() != 1 or not offsets.is_contiguous() or offsets.numel() < 1:
+            raise TypeError("offsets must be a contiguous 1-D int64 tensor of count + 1 entries")
+        if sas.dtype != torch.int32 or sas.dim() != 1 or not sas.is_contiguous():
+            raise TypeError("suffixes must be a contiguous 1-D int32 tensor")
+        if not texts.is_cuda or offsets.device != texts.device or sas.device != texts.device:
+            raise TypeError("texts, offsets and suffixes must live on the same GPU")
+        if sas.numel() != texts.numel():
+            raise TypeError("suffixes must have one entry per text byte")
+        count = offsets.numel() - 1
+        res = np.empty(count, dtype=np.int32)
+        if count == 0:
+            return res
+        dev, stream = _device_and_stream(texts)
+        total = texts.numel()
+        tp = texts if total else torch.zeros(1, dtype=torch.uint8, device=texts.device)
+        sp = sas if total else torch.zeros(1, dtype=torch.int32, device=texts.device)
+        _abi.check(self._lib.dq_sufcheck_hip_many_dev_i32(tp.data_ptr(), offsets.data_ptr(), count, sp.data_ptr(),
+                                                          res.ctypes.data, dev, stream))
+        return res
+
 
 def _device_and_stream(t):
     """(device ordinal, stream handle) for work on tensor t's device, on torch's current stream."""

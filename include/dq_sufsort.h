@@ -293,6 +293,46 @@ int32_t dq_sufcheck_hip_dev_i32(const void *d_text, int64_t n, const void *d_sa,
 int32_t dq_sufcheck_hip_dev_i64(const void *d_text, int64_t n, const void *d_sa, int64_t sa_len, int32_t *result,
                                 int32_t device, void *stream);
 
+/* ---- the same check of MANY suffix arrays in one call (what dq_sufsort_hip_many_* returns, or arrays from elsewhere) ---
+ * Checked one by one, the texts of a directory tree cost a memset, two launches, a 4-byte copy and a host round trip
+ * each.  Here a text of up to 65 536 bytes is decided by ONE workgroup (sufcheck_many_kernel, dq_sufcheck_many.h): its
+ * ranks are below 2^16, so its whole inverse array -- 16-bit ranks, 128 KiB at most -- lies in LDS, and the workgroups of
+ * one grid take text after text, longest first, until none is left; nobody waits for anybody.
+ * Layout as dq_sufsort_hip_many_i32: the texts back to back, offsets[count + 1] (int64, offsets[0] == 0, never
+ * decreasing); the int32 suffix arrays back to back in the same layout, sas[offsets[j] + i] counted from the start of
+ * text j.  results[count] is HOST memory in both forms: results[j] is exactly what dq_sufcheck_hip_i32(text_j, n_j,
+ * sa_j, n_j, ...) puts in *result -- DQ_SUFCHECK_DONE / _OUT_OF_RANGE / _WRONG_ORDER / _WRONG_POSITION (DONE for a text
+ * of 0 bytes, without device work).  DQ_SUFCHECK_BAD_ARGUMENTS cannot arise: by the layout every array is as long as
+ * its text.  Any int32 entry values are safe to check; the text and array buffers are only read, and nothing on the
+ * device outside the library's own scratch is written.
+ * Length classes (one launch each, on one stream): up to 8192 bytes -- text and ranks in LDS, 24 KiB, 256 threads,
+ * several workgroups per compute unit; up to 32 768 -- 96 KiB, 512 threads; up to 65 536 -- the ranks in LDS, 128 KiB,
+ * 1024 threads, the text read from device memory.  A text above 65 536 bytes is checked by the two kernels of the
+ * single-text check on the same stream, one text after another, each with a flag word of its own.
+ * Device memory, carved from the cached workspace of the slot the call leases: 4 bytes per text (its result word), 4
+ * per text on a work list, a line of claim words, and 4 bytes per byte of the longest text above 65 536 bytes (the
+ * inverse array the single-text kernels share); the host form adds its copies of a chunk: text, 4 bytes of suffix
+ * array per text byte, the offsets.
+ * Errors, all before any device use in the host form: count < 0, a NULL pointer with count > 0, offsets[0] != 0,
+ * decreasing offsets -> DQ_ERR_BAD_ARGS; a text of 2^31 bytes or more -> DQ_ERR_TOO_LARGE.  count == 0 is a no-op.
+ * An error leaves results undefined.
+ *   dq_sufcheck_hip_many_i32      host pointers.  Runs of whole texts travel in chunks of at most 64 MiB of text; per
+ *                                 chunk the copies in, the launches, one copy of the result words back and ONE stream
+ *                                 wait.  A single text above 64 MiB goes the way of dq_sufcheck_hip_i32.
+ *   dq_sufcheck_hip_many_dev_i32  device pointers on `device` (d_offsets too: the library fetches it once to plan the
+ *                                 launches, and checks it before it launches anything); work on `stream` (NULL = the
+ *                                 library's); one copy of all result words back and ONE stream wait for the whole call.
+ * dq_last_check_many_info: shape of the last of these calls on this thread, reset when one starts; `count` entries (5
+ * are defined, further ones read 0; a NULL array is DQ_ERR_BAD_ARGS): [0] texts checked in shared launches; [1] texts
+ * checked by the single-text kernels; [2] launches of sufcheck_many_kernel; [3] chunks (host form); [4] stream waits
+ * for verdicts (the device form's fetch of d_offsets, before anything is launched, is not among them).  The debug flag
+ * DQ_NO_CHECK_MANY=1 sends every text through dq_sufcheck_hip_i32 / _dev_i32 instead ([0] == 0). */
+int32_t dq_sufcheck_hip_many_i32(const uint8_t *texts, const int64_t *offsets, int32_t count, const int32_t *sas,
+                                 int32_t *results, int32_t device);
+int32_t dq_sufcheck_hip_many_dev_i32(const void *d_texts, const void *d_offsets, int32_t count, const void *d_sas,
+                                     int32_t *results, int32_t device, void *stream);
+int32_t dq_last_check_many_info(int64_t *info, int32_t count);
+
 /* Device workspace (bytes) a sort of n bytes with index_bytes (4 or 8) wide indices needs,
  * excluding the caller's text and sa buffers: the device entry point's full layout (the reduced one at n = 2^32). */
 int64_t dq_sufsort_hip_workspace_bytes(int64_t n, int32_t index_bytes);
