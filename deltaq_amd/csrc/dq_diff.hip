@@ -1494,12 +1494,12 @@ struct ManyFiles {
 // one index (ooff null): offsets relative to the chunk, the anchor room of every file, the work list (two lists in
 // one: the short pairs, then the medium ones, each longest new first; without ooff every file is in the first), what
 // comes back, and the carving of the call's one device allocation.
-struct ManyChunk {
-    int32_t cnt = 0, in_class[2] = {0, 0};
+struct ManyChunk : WorkLists<2> {
+    int32_t cnt = 0;
     int64_t o_base = 0, o_bytes = 0, n_base = 0, n_bytes = 0, anchors = 0;
     std::vector<int64_t> off;           // [rel_o,] rel_n, rel_a: cnt + 1 entries each
     const int64_t *rel_a = nullptr;
-    std::vector<int32_t> order, back;   // back: the anchor lists (list j at 2 * rel_a[j]), then counts and searches per file
+    std::vector<int32_t> back;          // the anchor lists (list j at 2 * rel_a[j]), then counts and searches per file
     uint8_t *d_old = nullptr, *d_new = nullptr;
     int32_t *d_sa = nullptr, *d_order = nullptr, *d_back = nullptr, *d_counts = nullptr, *d_searches = nullptr;
     int64_t *d_off = nullptr;           // `off` as it is: d_noff and d_aoff point into it
@@ -1626,20 +1626,6 @@ int diff_many_finish(const ManyFiles &f, const ManyChunk &k, int dev, std::vecto
     return DQ_OK;
 }
 
-// Workgroups of `kernel` the device holds at once, asked once per context (*cache).  A wrong answer costs time only:
-// nobody waits for anybody.
-template <typename Kernel>
-int resident_groups(int *cache, Kernel kernel, int threads, int dev)
-{
-    if (*cache <= 0) {
-        int per_cu = 0, ncu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, 0) != hipSuccess || per_cu <= 0) per_cu = 1;
-        if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
-        *cache = per_cu * ncu;
-    }
-    return *cache;
-}
-
 int many_chunk_prepare(ManyChunk &k, const int64_t *ooff, const int64_t *noff, int32_t first, int32_t cnt, DeviceBuf &buf)
 {
     k.cnt = cnt;
@@ -1650,22 +1636,14 @@ int many_chunk_prepare(ManyChunk &k, const int64_t *ooff, const int64_t *noff, i
     const size_t each = (size_t)cnt + 1;
     k.off.resize(each * (ooff ? 3 : 2));
     int64_t *rel_o = ooff ? k.off.data() : nullptr, *rel_n = k.off.data() + (ooff ? each : 0), *rel_a = rel_n + each;
+    if (ooff) chunk_offsets(ooff, first, cnt, rel_o);
+    chunk_offsets(noff, first, cnt, rel_n);
     rel_a[0] = 0;
-    for (int32_t j = 0; j <= cnt; ++j) {
-        if (ooff) rel_o[j] = ooff[first + j] - k.o_base;
-        rel_n[j] = noff[first + j] - k.n_base;
-        if (j > 0) rel_a[j] = rel_a[j - 1] + diff_many_anchor_room(rel_n[j] - rel_n[j - 1]);
-    }
+    for (int32_t j = 1; j <= cnt; ++j) rel_a[j] = rel_a[j - 1] + diff_many_anchor_room(rel_n[j] - rel_n[j - 1]);
     k.rel_a = rel_a;
     k.anchors = rel_a[cnt];
     auto klass = [&](int32_t j) { return !ooff || std::max(rel_o[j + 1] - rel_o[j], rel_n[j + 1] - rel_n[j]) <= kDiffManyMax ? 0 : 1; };
-    k.order.resize((size_t)cnt);
-    for (int32_t j = 0; j < cnt; ++j) k.order[(size_t)j] = j;
-    std::stable_sort(k.order.begin(), k.order.end(), [&](int32_t a, int32_t b) {
-        const int ka = klass(a), kb = klass(b);
-        return ka != kb ? ka < kb : rel_n[a + 1] - rel_n[a] > rel_n[b + 1] - rel_n[b];
-    });
-    for (int32_t j = 0; j < cnt; ++j) ++k.in_class[klass(j)];
+    build_work_lists(k, cnt, klass, [&](int32_t j) { return rel_n[j + 1] - rel_n[j]; });
     k.back.resize((size_t)k.anchors * 2 + (size_t)cnt * 2);
 
     const size_t b_old = ooff ? align_up((size_t)k.o_bytes + 64) : 0, b_new = align_up((size_t)k.n_bytes + 64),
@@ -1734,27 +1712,23 @@ int diff_many_chunk(const uint8_t *olds, const int64_t *ooff, const uint8_t *new
             Launcher L{c, st, g_prof_on.load()};
             // (a class's share of the bytes is not known here: the profile books all of them on the first launch)
             int64_t prof_units = k.n_bytes, prof_bytes = k.o_bytes * 5 + k.n_bytes;
-            if (k.in_class[0] > 0) {
-                const int grid = std::min<int>(k.in_class[0], resident_groups(&c.anchor_many_groups, anchor_many_kernel, kAmThreads, dev));
+            // the short pairs' launch claims from word 0 of the counter line, the medium pairs' from word 16
+            int r = for_each_class(k.class_count, k.d_order, k.d_next, 16, [&](int cls, int pairs, const int32_t *order, uint32_t *claim) -> int {
+                const auto kernel = cls == 0 ? anchor_many_kernel : anchor_mid_many_kernel;
+                const int threads = cls == 0 ? kAmThreads : kAmMidThreads;
+                const int grid = std::min(pairs, resident_groups(cls == 0 ? &c.anchor_many_groups : &c.anchor_mid_many_groups,
+                                                                 (const void *)kernel, threads, dev));
                 LAUNCH(L, DQ_K_MATCH_SEARCH, prof_units, prof_bytes,
-                       hipLaunchKernelGGL(anchor_many_kernel, dim3((unsigned)grid), dim3(kAmThreads), 0, st, k.d_old, k.d_off, k.d_sa, k.d_new,
-                                          k.d_noff, k.d_aoff, k.d_order, k.in_class[0], k.d_next, k.d_back, k.d_counts, k.d_searches));
+                       hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3((unsigned)threads), 0, st, k.d_old, k.d_off, k.d_sa, k.d_new,
+                                          k.d_noff, k.d_aoff, order, pairs, claim, k.d_back, k.d_counts, k.d_searches));
                 prof_units = prof_bytes = 0;
-                t_diff_many_info[2] += 1;
-            }
-            if (k.in_class[1] > 0) {
-                const int grid = std::min<int>(k.in_class[1],
-                                               resident_groups(&c.anchor_mid_many_groups, anchor_mid_many_kernel, kAmMidThreads, dev));
-                LAUNCH(L, DQ_K_MATCH_SEARCH, prof_units, prof_bytes,
-                       hipLaunchKernelGGL(anchor_mid_many_kernel, dim3((unsigned)grid), dim3(kAmMidThreads), 0, st, k.d_old, k.d_off, k.d_sa,
-                                          k.d_new, k.d_noff, k.d_aoff, k.d_order + k.in_class[0], k.in_class[1], k.d_next + 16, k.d_back,
-                                          k.d_counts, k.d_searches));
-                t_diff_many_info[11] += 1;
-            }
-            t_diff_many_info[10] += k.in_class[1];
-            const hipError_t e1 = hipMemcpyAsync(k.back.data(), k.d_back, k.back.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-            const hipError_t e2 = hipStreamSynchronize(st);
-            HIP_TRY(e1 != hipSuccess ? e1 : e2);
+                t_diff_many_info[cls == 0 ? 2 : 11] += 1;
+                return DQ_OK;
+            });
+            if (r != DQ_OK) return r;
+            t_diff_many_info[10] += k.class_count[1];
+            r = copy_back_and_wait(k.back.data(), k.d_back, k.back.size() * sizeof(int32_t), st);
+            if (r != DQ_OK) return r;
             t_diff_many_info[6] += us_since(t0);
             return flush_profile(c);
         };
@@ -1840,36 +1814,17 @@ int bsdiff_create_many_host(const uint8_t *olds, const int64_t *ooff, const uint
         for (int32_t j = a; j < b && r == DQ_OK; ++j) r = deliver(j, done[(size_t)(j - a)].patch);
         return r;
     };
-    for (int32_t i = 0; i < count;) {
-        if (!is_listed(i)) {
-            rc = single(i);
-            if (rc != DQ_OK) return rc;
-            ++i;
-            continue;
-        }
-        int32_t e = i;
+    auto run = [&](int32_t i, int32_t e) -> int {
         int64_t mids = 0;
-        while (e < count && e - i < kDiffManyChunkPairs && is_listed(e) &&
-               (ooff[e + 1] - ooff[i]) + (noff[e + 1] - noff[i]) <= kDiffManyChunkBytes) {
-            mids += !is_short(e);
-            ++e;
-        }
-        if (mids == 0 || mids >= mid_min) {
-            rc = chunk(i, e);
-            if (rc != DQ_OK) return rc;
-        } else {
-            // too few medium pairs for launches of their own: the run as without the class, in input order
-            for (int32_t a = i; a < e;) {
-                int32_t b = a;
-                while (b < e && is_short(b)) ++b;
-                rc = b > a ? chunk(a, b) : single(b++);
-                if (rc != DQ_OK) return rc;
-                a = b;
-            }
-        }
-        i = e;
-    }
-    return DQ_OK;
+        for (int32_t j = i; j < e; ++j) mids += !is_short(j);
+        if (mids == 0 || mids >= mid_min) return chunk(i, e);
+        // too few medium pairs for launches of their own: the run as without the class, in input order
+        return walk_runs(e - i, e - i, [&](int32_t j) { return is_short(i + j); }, [](int32_t, int32_t) { return true; },
+                         [&](int32_t j) { return single(i + j); }, [&](int32_t a, int32_t b) { return chunk(i + a, i + b); });
+    };
+    static_assert(2 * kMidMaxN <= kDiffManyChunkBytes, "a listed pair fits a chunk of its own (walk_runs)");
+    return walk_runs(count, kDiffManyChunkPairs, is_listed,
+                     [&](int32_t i, int32_t e) { return (ooff[e + 1] - ooff[i]) + (noff[e + 1] - noff[i]) <= kDiffManyChunkBytes; }, single, run);
 }
 
 int bsdiff_create_host(const uint8_t *old, int64_t n, const uint8_t *nw, int64_t m, int32_t device, std::vector<uint8_t> &patch)
@@ -2020,7 +1975,7 @@ int diff_index_many_chunk(const DiffIndex &ix, const uint8_t *news, const int64_
         auto launch = [&](auto width) -> int {
             constexpr int kThreads = decltype(width)::value;
             const int grid = std::min<int>(cnt, resident_groups(&c.anchor_index_many_groups[kThreads == 256 ? 0 : 1],
-                                                                anchor_index_many_kernel<kThreads>, kThreads, dev));
+                                                                (const void *)anchor_index_many_kernel<kThreads>, kThreads, dev));
             LAUNCH(L, DQ_K_MATCH_SEARCH, k.n_bytes, k.n_bytes,
                    hipLaunchKernelGGL(anchor_index_many_kernel<kThreads>, dim3((unsigned)grid), dim3(kThreads), 0, st,
                                       reinterpret_cast<const uint8_t *>(ix.d_old), ix.n, reinterpret_cast<const int32_t *>(ix.d_sa),
@@ -2033,10 +1988,8 @@ int diff_index_many_chunk(const DiffIndex &ix, const uint8_t *news, const int64_
             if (r == DQ_OK) r = threads == 256 ? launch(std::integral_constant<int, 256>{}) : launch(std::integral_constant<int, 512>{});
             if (r != DQ_OK) return r;
             t_index_many_info[2] += 1;
-            const hipError_t e1 = hipMemcpyAsync(k.back.data(), k.d_back, k.back.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-            const hipError_t e2 = hipStreamSynchronize(st);
-            HIP_TRY(e1 != hipSuccess ? e1 : e2);
-            return flush_profile(c);
+            r = copy_back_and_wait(k.back.data(), k.d_back, k.back.size() * sizeof(int32_t), st);
+            return r != DQ_OK ? r : flush_profile(c);
         };
         rc = run();
         if (rc != DQ_OK) { drop_pending(c, c.stream); return rc; }
@@ -2075,31 +2028,22 @@ int diff_index_many(const void *index, const uint8_t *news, const int64_t *noff,
         if (r == DQ_OK) t_index_many_info[1] += 1;
         return r;
     };
-    for (int32_t i = 0; i < count;) {
-        if (!is_listed(i)) {
-            const int rc = single(i);
-            if (rc != DQ_OK) return rc;
-            ++i;
-            continue;
-        }
-        int32_t e = i;
-        while (e < count && e - i < kDiffManyChunkPairs && is_listed(e) && noff[e + 1] - noff[i] <= kDiffManyChunkBytes) ++e;
-        if (e - i >= many_min) {
-            int rc = diff_index_many_chunk(*ix, news, noff, i, e - i, buf, done);
-            if (rc != DQ_OK) return rc;
-            t_index_many_info[0] += e - i;
-            for (int32_t j = i; j < e && rc == DQ_OK; ++j) rc = deliver(j, done[(size_t)(j - i)].patch);
-            if (rc != DQ_OK) return rc;
-        } else {
+    auto run = [&](int32_t i, int32_t e) -> int {
+        int rc = DQ_OK;
+        if (e - i < many_min) {
             // too few files for a launch of their own: one by one, in input order
-            for (int32_t j = i; j < e; ++j) {
-                const int rc = single(j);
-                if (rc != DQ_OK) return rc;
-            }
+            for (int32_t j = i; j < e && rc == DQ_OK; ++j) rc = single(j);
+            return rc;
         }
-        i = e;
-    }
-    return DQ_OK;
+        rc = diff_index_many_chunk(*ix, news, noff, i, e - i, buf, done);
+        if (rc != DQ_OK) return rc;
+        t_index_many_info[0] += e - i;
+        for (int32_t j = i; j < e && rc == DQ_OK; ++j) rc = deliver(j, done[(size_t)(j - i)].patch);
+        return rc;
+    };
+    static_assert(kIndexManyMax <= kDiffManyChunkBytes, "a listed file fits a chunk of its own (walk_runs)");
+    return walk_runs(count, kDiffManyChunkPairs, is_listed, [&](int32_t i, int32_t e) { return noff[e + 1] - noff[i] <= kDiffManyChunkBytes; },
+                     single, run);
 }
 
 void diff_index_delete(void *index)

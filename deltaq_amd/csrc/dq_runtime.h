@@ -29,6 +29,7 @@
 
 #include "../../include/dq_sufsort.h"
 #include "dq_flags.h"
+#include "dq_work_lists.h"
 
 namespace dq {
 
@@ -327,6 +328,51 @@ inline int check_many_offsets(const int64_t *off, int32_t count)
         if (off[j + 1] - off[j] > 0x7fffffffLL)
             return fail(DQ_ERR_TOO_LARGE, "a text exceeds 2^31-1 bytes: the many-texts entry points have 32-bit indices");
     }
+    return DQ_OK;
+}
+
+// ------------------------------------------------------------------ the many-* calls' launches (the planning: dq_work_lists.h)
+// Workgroups of `kernel` the device holds at once, asked once per context (*cache: a word of DeviceCtx).  A wrong answer
+// costs time only: the kernels that claim their work from a list never wait for each other.
+inline int resident_groups(int *cache, const void *kernel, int threads, int dev)
+{
+    if (*cache <= 0) {
+        int per_cu = 0, ncu = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, 0) != hipSuccess || per_cu <= 0) per_cu = 1;
+        if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
+        *cache = per_cu * ncu;
+    }
+    return *cache;
+}
+
+// A length class of such a kernel, a row of its table: Args is what the kernel is handed.
+template <typename Args>
+struct ClassRow {
+    int max_n, threads;                   // largest text; workgroup
+    const void *(*kernel)();              // for the occupancy query (a kernel's address is no constant expression)
+    void (*launch)(int grid, hipStream_t st, const Args &a);
+    size_t scratch;                       // bytes of device memory per workgroup (the sort's medium classes; 0: none)
+    int min_texts;                        // fewest texts of the class in a call / chunk that share its launch (the check)
+    int grid(int *cache, int count, int dev) const { return std::min(count, resident_groups(cache, kernel(), threads, dev)); }
+};
+
+// The device forms' first step: the offsets come to the host once, to plan the launches, and are checked before
+// anything is launched.
+inline int fetch_many_offsets(const int64_t *d_offsets, int32_t count, hipStream_t st, std::vector<int64_t> &off)
+{
+    off.resize((size_t)count + 1);
+    HIP_TRY(hipMemcpyAsync(off.data(), d_offsets, off.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return check_many_offsets(off.data(), count);
+}
+
+// Copy back, then wait, as one checked step: a failure must not leave a copy into the caller's array in flight behind
+// the return.
+inline int copy_back_and_wait(void *dst, const void *d_src, size_t bytes, hipStream_t st)
+{
+    const hipError_t e1 = hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, st);
+    const hipError_t e2 = hipStreamSynchronize(st);
+    HIP_TRY(e1 != hipSuccess ? e1 : e2);
     return DQ_OK;
 }
 

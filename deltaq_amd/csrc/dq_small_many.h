@@ -41,12 +41,7 @@ struct ManyArgs {                         // what a class's kernel is handed (th
     int32_t *sas;
     char *scratch;
 };
-struct ManyClass {
-    int max_n, threads;                   // largest text; workgroup
-    const void *(*kernel)();              // for the occupancy query (a kernel's address is no constant expression)
-    void (*launch)(int grid, hipStream_t st, const ManyArgs &a);
-    size_t scratch;                       // bytes of device memory per workgroup (the medium classes' store; 0: none)
-};
+using ManyClass = ClassRow<ManyArgs>;      // (dq_runtime.h; scratch: the medium classes' store)
 // A row is made from the class's two numbers alone: what the table says and what the kernel is built for cannot differ.
 template <int kMaxN, int kThreads>
 struct ShortClass {
@@ -56,7 +51,7 @@ struct ShortClass {
         hipLaunchKernelGGL((small_many_kernel<kMaxN, kThreads>), dim3((unsigned)grid), dim3(kThreads), 0, st, a.texts, a.offsets,
                            a.order, a.count, a.claim, a.sas);
     }
-    static constexpr ManyClass row() { return {kMaxN, kThreads, kernel, launch, 0}; }
+    static constexpr ManyClass row() { return {kMaxN, kThreads, kernel, launch, 0, 1}; }
 };
 template <int kMaxN, int kThreads>
 struct MidClass {
@@ -66,7 +61,7 @@ struct MidClass {
         hipLaunchKernelGGL((mid_many_kernel<kMaxN, kThreads>), dim3((unsigned)grid), dim3(kThreads), 0, st, a.texts, a.offsets,
                            a.order, a.count, a.claim, a.sas, a.scratch);
     }
-    static constexpr ManyClass row() { return {kMaxN, kThreads, kernel, launch, MidStore<kMaxN>::kScratchBytes}; }
+    static constexpr ManyClass row() { return {kMaxN, kThreads, kernel, launch, MidStore<kMaxN>::kScratchBytes, 1}; }
 };
 constexpr ManyClass kManyClass[kAllClasses] = {
     ShortClass<2048, 256>::row(), ShortClass<4096, 512>::row(), ShortClass<kSmallMaxN, kSmallThreads>::row(),
@@ -93,23 +88,10 @@ constexpr int kMidManyMin = 64;
 constexpr bool kLargeManyByDefault = false;
 constexpr int kLargeManyMin = 8;
 
-// workgroups of class k the device holds at once (a wrong answer costs time only: nobody waits for anybody)
-inline int many_class_groups(DeviceCtx &c, int k)
-{
-    if (c.many_groups[k] <= 0) {
-        int per_cu = 0, ncu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kManyClass[k].kernel(), kManyClass[k].threads, 0) != hipSuccess || per_cu <= 0)
-            per_cu = 1;
-        if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c.dev) != hipSuccess || ncu <= 0) ncu = 256;
-        c.many_groups[k] = per_cu * ncu;
-    }
-    return c.many_groups[k];
-}
-
-// what the host decides about a set of texts from their offsets
-struct ManyPlan {
-    std::vector<int32_t> order;                 // the classes' work lists back to back, each longest text first
-    int class_count[kAllClasses] = {};
+// What the host decides about a set of texts from their offsets.  The work lists (dq_work_lists.h) of the classes, each
+// longest text first; the list behind them, of the large texts, is empty again once the plan is made.
+constexpr int kLargeList = kAllClasses;
+struct ManyPlan : WorkLists<kAllClasses + 1> {
     int64_t class_bytes[kAllClasses] = {};
     std::vector<int32_t> larges;                // texts of the segmented sorts (dq_large_many.h), in input order
     std::vector<int32_t> longs;                 // texts sorted singly, in input order: those above kLargeMaxN, and the medium and large ones that share nothing
@@ -153,59 +135,39 @@ inline int many_class_of(int64_t n, int drop)
     return kManyClasses - 1;
 }
 
-inline ManyPlan plan_many(const int64_t *off, int32_t first, int32_t last, bool large_by_default = true)
+inline ManyPlan plan_many(const int64_t *off, int32_t count, bool large_by_default = true)
 {
     ManyPlan p;
     const int64_t short_max = many_short_max();
     const int drop = flags().no_many.value_or(0);
     const bool mid_on = mid_many_on(), large_on = large_many_on(large_by_default);
-    std::vector<int32_t> lists[kAllClasses];
-    std::vector<int32_t> mids;
-    for (int32_t j = first; j < last; ++j) {
-        const int64_t n = off[j + 1] - off[j];
-        if (n == 0) continue;
-        if (n > short_max) {
-            if (mid_on && n <= kMidMaxN) mids.push_back(j);
-            else if (large_on && is_large(n)) p.larges.push_back(j);
-            else p.longs.push_back(j);
-            continue;
-        }
-        const int k = many_class_of(n, drop);
-        lists[k].push_back(j);
-        p.class_bytes[k] += n;
-    }
-    // the medium texts share launches when there are enough of them
-    if ((int64_t)mids.size() >= flags().mid_many_min.value_or(kMidManyMin)) {
-        for (int32_t j : mids) {
-            const int64_t n = off[j + 1] - off[j];
-            int k = kManyClasses;
-            while (k < kAllClasses - 1 && n > kManyClass[k].max_n) ++k;
-            lists[k].push_back(j);
-            p.class_bytes[k] += n;
-        }
-    } else if (!mids.empty()) {
-        const size_t at = p.longs.size();
-        p.longs.insert(p.longs.end(), mids.begin(), mids.end());
-        std::inplace_merge(p.longs.begin(), p.longs.begin() + (ptrdiff_t)at, p.longs.end());
-    }
-    // ... and so do the large ones
-    if (!p.larges.empty() && (int64_t)p.larges.size() < large_many_min()) {
-        const size_t at = p.longs.size();
-        p.longs.insert(p.longs.end(), p.larges.begin(), p.larges.end());
-        std::inplace_merge(p.longs.begin(), p.longs.begin() + (ptrdiff_t)at, p.longs.end());
-        p.larges.clear();
-    }
+    auto len = [&](int32_t j) { return off[j + 1] - off[j]; };
+    auto klass = [&](int32_t j) {
+        const int64_t n = len(j);
+        if (n == 0) return -1;
+        if (n <= short_max) return many_class_of(n, drop);
+        if (large_on && is_large(n)) return kLargeList;
+        if (!mid_on || n > kMidMaxN) return -1;
+        int k = kManyClasses;
+        while (k < kAllClasses - 1 && n > kManyClass[k].max_n) ++k;
+        return k;
+    };
+    build_work_lists(p, count, klass, len);
+    for (int32_t j = 0; j < count; ++j)
+        if (len(j) > 0 && klass(j) < 0) p.longs.push_back(j);
+    // the large texts share sorts when there are enough of them (their list goes to `larges`, in input order, if so), and
+    // the medium ones launches
+    p.demote(kLargeList, (int64_t)p.class_count[kLargeList] < large_many_min() ? p.longs : p.larges);
+    if (p.mids() < flags().mid_many_min.value_or(kMidManyMin))
+        for (int k = kManyClasses; k < kAllClasses; ++k) p.demote(k, p.longs);
     for (int32_t j : p.longs) {
-        const int64_t n = off[j + 1] - off[j];
+        const int64_t n = len(j);
         if (n > kMidMaxN) ++p.above_mid;
         else if (n > kSmallMaxN) ++p.mid_single;
     }
-    for (int k = 0; k < kAllClasses; ++k) {
-        std::stable_sort(lists[k].begin(), lists[k].end(),
-                         [&](int32_t a, int32_t b) { return off[a + 1] - off[a] > off[b + 1] - off[b]; });
-        p.class_count[k] = (int)lists[k].size();
-        p.order.insert(p.order.end(), lists[k].begin(), lists[k].end());
-    }
+    const int32_t *at = p.order.data();
+    for (int k = 0; k < kAllClasses; ++k)
+        for (int i = 0; i < p.class_count[k]; ++i) p.class_bytes[k] += len(*at++);
     return p;
 }
 
@@ -220,7 +182,7 @@ inline size_t many_scratch_bytes(DeviceCtx &c, const ManyPlan &plan)
     size_t need = 0;
     for (int k = 0; k < kAllClasses; ++k)
         if (plan.class_count[k] > 0 && kManyClass[k].scratch > 0)
-            need = std::max(need, (size_t)std::min(plan.class_count[k], many_class_groups(c, k)) * kManyClass[k].scratch);
+            need = std::max(need, (size_t)kManyClass[k].grid(&c.many_groups[k], plan.class_count[k], c.dev) * kManyClass[k].scratch);
     return align_up(need);
 }
 
@@ -237,22 +199,19 @@ inline int launch_many(DeviceCtx &c, hipStream_t st, const ManyPlan &plan, const
     int32_t *d_order = reinterpret_cast<int32_t *>(d_ctl + kManyCounterBytes);
     HIP_TRY(hipMemsetAsync(d_next, 0, kManyCounterBytes, st));
     HIP_TRY(hipMemcpyAsync(d_order, plan.order.data(), plan.order.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    for (int k = 0; k < kAllClasses; ++k) {
-        const int count = plan.class_count[k];
-        if (count == 0) continue;
-        const int grid = std::min(count, many_class_groups(c, k));
-        const ManyArgs a{d_texts, d_offsets, d_order, count, d_next + k, d_sas, d_scratch};
-        LAUNCH(L, DQ_K_SMALL_MANY, count, plan.class_bytes[k] * 5, kManyClass[k].launch(grid, st, a));
+    return for_each_class(plan.class_count, d_order, d_next, 1, [&](int k, int count, const int32_t *order, uint32_t *claim) -> int {
+        const ManyArgs a{d_texts, d_offsets, order, count, claim, d_sas, d_scratch};
+        LAUNCH(L, DQ_K_SMALL_MANY, count, plan.class_bytes[k] * 5,
+               kManyClass[k].launch(kManyClass[k].grid(&c.many_groups[k], count, c.dev), st, a));
         if (k >= kManyClasses) t_many_info[4] += 1;
-        d_order += count;
-    }
-    return DQ_OK;
+        return DQ_OK;
+    });
 }
 
 // (kManyChunkBytes, kManyChunkTexts: dq_runtime.h) A segmented sort takes at most kManyChunkBytes of large text: fewer than
 // kLargeSegMax texts above kMidMaxN.
 static_assert(kManyChunkBytes / (kMidMaxN + 1) < kLargeSegMax, "a batch's segment ordinals fit 10 bits");
-static_assert(kLargeMaxN > kMidMaxN && kLargeMaxN <= kManyChunkBytes, "a large text fits a batch");
+static_assert(kLargeMaxN > kMidMaxN && kLargeMaxN <= kManyChunkBytes, "a large text fits a batch, and every listed text a chunk of its own (walk_runs)");
 
 // the batches of a plan's large texts: runs [from, to) of plan.larges with at most kManyChunkBytes of text each
 inline std::vector<std::pair<size_t, size_t>> large_batches(const ManyPlan &plan, const int64_t *off)
@@ -344,7 +303,7 @@ int sufsort_many_dev(const void *d_texts_v, const void *d_offsets_v, int32_t cou
     int dev = 0;
     int rc = resolve_device(device, &dev);
     if (rc != DQ_OK) return rc;
-    std::vector<int64_t> off((size_t)count + 1);
+    std::vector<int64_t> off;
     ManyPlan plan;
     {
         SlotLease lease(dev, 0);
@@ -352,13 +311,10 @@ int sufsort_many_dev(const void *d_texts_v, const void *d_offsets_v, int32_t cou
         rc = init_ctx(c, dev);
         if (rc != DQ_OK) return rc;
         hipStream_t st = stream ? (hipStream_t)stream : c.stream;
-        // the offsets come to the host once, to plan the launches (and to be checked before anything is launched)
-        HIP_TRY(hipMemcpyAsync(off.data(), d_offsets, off.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        rc = check_many_offsets(off.data(), count);
+        rc = fetch_many_offsets(d_offsets, count, st, off);
         if (rc != DQ_OK) return rc;
         t_info[0] = t_info[1] = t_info[2] = 0;
-        plan = plan_many(off.data(), 0, count);
+        plan = plan_many(off.data(), count);
         if (!many_one_by_one() && plan.shared()) {
             const size_t b_ctl = many_ctl_bytes(plan.listed()), b_scratch = many_scratch_bytes(c, plan);
             rc = ensure_ws(c, std::max(b_ctl + b_scratch, many_large_bytes(plan, off.data())));
@@ -412,27 +368,22 @@ int sufsort_many_host(const uint8_t *texts, const int64_t *offsets, int32_t coun
     }
     const bool one_by_one = many_one_by_one();
     std::vector<int64_t> rel;
-    for (int32_t i = 0; i < count;) {
-        const int64_t n = offsets[i + 1] - offsets[i];
-        if (n > listed_max || one_by_one) {
-            rc = sufsort_host<int32_t>(texts + offsets[i], n, sas + offsets[i], dev);
-            if (rc != DQ_OK) return rc;
-            if (n > kMidMaxN) t_many_info[3] += 1;
-            else if (n > kSmallMaxN) t_many_info[2] += 1;
-            ++i;
-            continue;
-        }
-        // the chunk: texts [i, e), none above the limit, back to back in the caller's buffer
-        int32_t e = i;
-        while (e < count && e - i < kManyChunkTexts && offsets[e + 1] - offsets[e] <= listed_max &&
-               offsets[e + 1] - offsets[i] <= kManyChunkBytes)
-            ++e;
+    auto len = [&](int32_t j) { return offsets[j + 1] - offsets[j]; };
+    auto single = [&](int32_t i) -> int {
+        const int r = sufsort_host<int32_t>(texts + offsets[i], len(i), sas + offsets[i], dev);
+        if (r != DQ_OK) return r;
+        if (len(i) > kMidMaxN) t_many_info[3] += 1;
+        else if (len(i) > kSmallMaxN) t_many_info[2] += 1;
+        return DQ_OK;
+    };
+    // the chunk: texts [i, e), none above the limit, back to back in the caller's buffer
+    auto chunk = [&](int32_t i, int32_t e) -> int {
         const int64_t base = offsets[i], bytes = offsets[e] - base;
         const int32_t cnt = e - i;
         if (bytes > 0) {
             rel.resize((size_t)cnt + 1);
-            for (int32_t j = 0; j <= cnt; ++j) rel[(size_t)j] = offsets[i + j] - base;
-            const ManyPlan plan = plan_many(rel.data(), 0, cnt, large_by_default);
+            chunk_offsets(offsets, i, cnt, rel.data());
+            const ManyPlan plan = plan_many(rel.data(), cnt, large_by_default);
             if (plan.shared()) {
                 SlotLease lease(dev, 0);
                 DeviceCtx &c = *lease.c;
@@ -456,11 +407,8 @@ int sufsort_many_host(const uint8_t *texts, const int64_t *offsets, int32_t coun
                     if (r != DQ_OK) return r;
                     const int rl = launch_large(c, st, plan, rel.data(), d_text, d_sa, c.ws + b_text + b_sa + b_off + b_ctl + b_scratch);
                     if (rl != DQ_OK) return rl;
-                    // (one checked step: a failure must not leave a copy into the caller's array in flight behind the return)
-                    const hipError_t e1 = hipMemcpyAsync(sas + base, d_sa, (size_t)bytes * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-                    const hipError_t e2 = hipStreamSynchronize(st);
-                    HIP_TRY(e1 != hipSuccess ? e1 : e2);
-                    return flush_profile(c);
+                    const int rb = copy_back_and_wait(sas + base, d_sa, (size_t)bytes * sizeof(int32_t), st);
+                    return rb != DQ_OK ? rb : flush_profile(c);
                 };
                 rc = run();
                 if (rc != DQ_OK) { drop_pending(c, st); return rc; }
@@ -479,9 +427,10 @@ int sufsort_many_host(const uint8_t *texts, const int64_t *offsets, int32_t coun
                 if (rc != DQ_OK) return rc;
             }
         }
-        i = e;
-    }
-    return DQ_OK;
+        return DQ_OK;
+    };
+    return walk_runs(count, kManyChunkTexts, [&](int32_t j) { return !one_by_one && len(j) <= listed_max; },
+                     [&](int32_t i, int32_t e) { return offsets[e + 1] - offsets[i] <= kManyChunkBytes; }, single, chunk);
 }
 
 }  // namespace dq

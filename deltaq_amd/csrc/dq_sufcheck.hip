@@ -142,12 +142,7 @@ struct CheckArgs {
     const int32_t *sas;
     uint32_t *results;
 };
-struct CheckClass {
-    int max_n, threads;
-    int min_texts;                        // fewest texts of the class in a call / chunk that share its launch (below)
-    const void *(*kernel)();
-    void (*launch)(int grid, hipStream_t st, const CheckArgs &a);
-};
+using CheckClass = ClassRow<CheckArgs>;    // (dq_runtime.h; min_texts: below)
 template <int kMaxN, int kThreads>
 struct CheckRow {
     static const void *kernel() { return (const void *)sufcheck_many_kernel<kMaxN, kThreads>; }
@@ -156,7 +151,7 @@ struct CheckRow {
         hipLaunchKernelGGL((sufcheck_many_kernel<kMaxN, kThreads>), dim3((unsigned)grid), dim3(kThreads), 0, st, a.texts,
                            a.offsets, a.order, a.count, a.claim, a.sas, a.results);
     }
-    static constexpr CheckClass row(int min_texts) { return {kMaxN, kThreads, min_texts, kernel, launch}; }
+    static constexpr CheckClass row(int min_texts) { return {kMaxN, kThreads, kernel, launch, 0, min_texts}; }
 };
 // min_texts: one workgroup replaces a memset and two launches, but on a long text it is slower than the whole device:
 // where a class loses to the single-text kernels at small counts (tools/kbench/check_many.py, the sweep with
@@ -166,23 +161,9 @@ constexpr CheckClass kCheckClass[kCheckClasses] = {CheckRow<8192, 256>::row(1), 
                                                    CheckRow<kMidMaxN, 1024>::row(1)};
 constexpr int64_t kCheckManyMaxN = kCheckClass[kCheckClasses - 1].max_n;
 
-// workgroups of class k the device holds at once (a wrong answer costs time only: nobody waits for anybody)
-inline int check_class_groups(DeviceCtx &c, int k)
-{
-    if (c.check_many_groups[k] <= 0) {
-        int per_cu = 0, ncu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kCheckClass[k].kernel(), kCheckClass[k].threads, 0) != hipSuccess || per_cu <= 0)
-            per_cu = 1;
-        if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c.dev) != hipSuccess || ncu <= 0) ncu = 256;
-        c.check_many_groups[k] = per_cu * ncu;
-    }
-    return c.check_many_groups[k];
-}
-
-// what the host decides about texts [0, count) from their offsets
-struct CheckPlan {
-    std::vector<int32_t> order;                 // the classes' work lists back to back, each longest text first
-    int class_count[kCheckClasses] = {};
+// What the host decides about texts [0, count) from their offsets: the classes' work lists (dq_work_lists.h), each
+// longest text first, and the texts that are on none.
+struct CheckPlan : WorkLists<kCheckClasses> {
     std::vector<int32_t> longs;                 // in input order: texts of the single-text kernels -- those above kCheckManyMaxN, and those of a class with too few
     int64_t longest = 0;                        // ... the longest of them
 };
@@ -190,31 +171,21 @@ struct CheckPlan {
 inline CheckPlan plan_check(const int64_t *off, int32_t count)
 {
     CheckPlan p;
-    std::vector<int32_t> lists[kCheckClasses];
-    for (int32_t j = 0; j < count; ++j) {
-        const int64_t n = off[j + 1] - off[j];
-        if (n == 0) continue;                   // DONE without device work: its result word stays 0
-        if (n > kCheckManyMaxN) { p.longs.push_back(j); continue; }
+    auto len = [&](int32_t j) { return off[j + 1] - off[j]; };
+    auto klass = [&](int32_t j) {
+        const int64_t n = len(j);
+        if (n == 0 || n > kCheckManyMaxN) return -1;    // (an empty text is DONE without device work: its result word stays 0)
         int k = 0;
         while (n > kCheckClass[k].max_n) ++k;
-        lists[k].push_back(j);
-    }
+        return k;
+    };
+    build_work_lists(p, count, klass, len);
+    for (int32_t j = 0; j < count; ++j)
+        if (len(j) > kCheckManyMaxN) p.longs.push_back(j);
     const bool forced = flags().no_check_many.value_or(1) == 0;
-    for (int k = 0; k < kCheckClasses; ++k) {
-        if (!forced && !lists[k].empty() && (int)lists[k].size() < kCheckClass[k].min_texts) {
-            const size_t at = p.longs.size();
-            p.longs.insert(p.longs.end(), lists[k].begin(), lists[k].end());
-            std::inplace_merge(p.longs.begin(), p.longs.begin() + (ptrdiff_t)at, p.longs.end());
-            lists[k].clear();
-        }
-    }
-    for (int32_t j : p.longs) p.longest = std::max(p.longest, off[j + 1] - off[j]);
-    for (int k = 0; k < kCheckClasses; ++k) {
-        std::stable_sort(lists[k].begin(), lists[k].end(),
-                         [&](int32_t a, int32_t b) { return off[a + 1] - off[a] > off[b + 1] - off[b]; });
-        p.class_count[k] = (int)lists[k].size();
-        p.order.insert(p.order.end(), lists[k].begin(), lists[k].end());
-    }
+    for (int k = 0; k < kCheckClasses; ++k)
+        if (!forced && p.class_count[k] < kCheckClass[k].min_texts) p.demote(k, p.longs);
+    for (int32_t j : p.longs) p.longest = std::max(p.longest, len(j));
     return p;
 }
 
@@ -243,15 +214,14 @@ inline int launch_check(DeviceCtx &c, hipStream_t st, const CheckPlan &plan, con
     HIP_TRY(hipMemsetAsync(scratch, 0, at.order_at, st));                       // claim words and result words
     if (!plan.order.empty())
         HIP_TRY(hipMemcpyAsync(d_order, plan.order.data(), plan.order.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    for (int k = 0; k < kCheckClasses; ++k) {
-        const int cnt = plan.class_count[k];
-        if (cnt == 0) continue;
-        const CheckArgs a{d_texts, d_offsets, d_order, cnt, d_next + k, d_sas, d_results};
-        kCheckClass[k].launch(std::min(cnt, check_class_groups(c, k)), st, a);
+    const int launched = for_each_class(plan.class_count, d_order, d_next, 1, [&](int k, int cnt, const int32_t *order, uint32_t *claim) -> int {
+        const CheckArgs a{d_texts, d_offsets, order, cnt, claim, d_sas, d_results};
+        kCheckClass[k].launch(kCheckClass[k].grid(&c.check_many_groups[k], cnt, c.dev), st, a);
         HIP_TRY(hipGetLastError());
         t_check_many_info[2] += 1;
-        d_order += cnt;
-    }
+        return DQ_OK;
+    });
+    if (launched != DQ_OK) return launched;
     for (int32_t j : plan.longs) {
         const int rc = sufcheck_launch<int32_t>(st, d_texts + off[j], off[j + 1] - off[j], d_sas + off[j],
                                                 reinterpret_cast<uint32_t *>(scratch + at.isa_at), d_results + j);
@@ -286,17 +256,13 @@ int sufcheck_many_dev(const void *d_texts_v, const void *d_offsets_v, int32_t co
     int dev = 0;
     int rc = resolve_device(device, &dev);
     if (rc != DQ_OK) return rc;
-    std::vector<int64_t> off((size_t)count + 1);
+    std::vector<int64_t> off;
     {
         SlotLease lease(dev, 0);
         DeviceCtx &c = *lease.c;
         rc = init_ctx(c, dev);
         if (rc != DQ_OK) return rc;
-        hipStream_t st = stream ? (hipStream_t)stream : c.stream;
-        // the offsets come to the host once, to plan the launches (and to be checked before anything is launched)
-        HIP_TRY(hipMemcpyAsync(off.data(), d_offsets, off.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        rc = check_many_offsets(off.data(), count);
+        rc = fetch_many_offsets(d_offsets, count, stream ? (hipStream_t)stream : c.stream, off);
         if (rc != DQ_OK) return rc;
     }   // (the slot is given back: the call below leases the one its longest text needs)
     if (check_one_by_one()) {
@@ -346,28 +312,24 @@ int sufcheck_many_host(const uint8_t *texts, const int64_t *offsets, int32_t cou
     if (rc != DQ_OK) return rc;
     const bool one_by_one = check_one_by_one();
     std::vector<int64_t> rel;
-    for (int32_t i = 0; i < count;) {
+    auto single = [&](int32_t i) -> int {
         const int64_t n = offsets[i + 1] - offsets[i];
-        if (n > kManyChunkBytes || one_by_one) {
-            rc = sufcheck_host<int32_t>(texts + offsets[i], n, sas + offsets[i], n, results + i, dev);
-            if (rc != DQ_OK) return rc;
-            t_check_many_info[1] += 1;
-            t_check_many_info[4] += n > 0 ? 1 : 0;
-            ++i;
-            continue;
-        }
-        // the chunk: texts [i, e), back to back in the caller's buffers
-        int32_t e = i;
-        while (e < count && e - i < kManyChunkTexts && offsets[e + 1] - offsets[i] <= kManyChunkBytes) ++e;
+        const int r = sufcheck_host<int32_t>(texts + offsets[i], n, sas + offsets[i], n, results + i, dev);
+        if (r != DQ_OK) return r;
+        t_check_many_info[1] += 1;
+        t_check_many_info[4] += n > 0 ? 1 : 0;
+        return DQ_OK;
+    };
+    // the chunk: texts [i, e), back to back in the caller's buffers
+    auto chunk = [&](int32_t i, int32_t e) -> int {
         const int64_t base = offsets[i], bytes = offsets[e] - base;
         const int32_t cnt = e - i;
         if (bytes == 0) {
             std::fill(results + i, results + e, DQ_SUFCHECK_DONE);
-            i = e;
-            continue;
+            return DQ_OK;
         }
         rel.resize((size_t)cnt + 1);
-        for (int32_t j = 0; j <= cnt; ++j) rel[(size_t)j] = offsets[i + j] - base;
+        chunk_offsets(offsets, i, cnt, rel.data());
         const CheckPlan plan = plan_check(rel.data(), cnt);
         SlotLease lease(dev, bytes);
         DeviceCtx &c = *lease.c;
@@ -393,9 +355,11 @@ int sufcheck_many_host(const uint8_t *texts, const int64_t *offsets, int32_t cou
         HIP_TRY(err);
         check_account(plan, results + i, cnt);
         t_check_many_info[3] += 1;
-        i = e;
-    }
-    return DQ_OK;
+        return DQ_OK;
+    };
+    // (a text is listed if it fits a chunk alone: the walk needs no more to make progress)
+    auto fits = [&](int32_t i, int32_t e) { return offsets[e + 1] - offsets[i] <= kManyChunkBytes; };
+    return walk_runs(count, kManyChunkTexts, [&](int32_t j) { return !one_by_one && fits(j, j); }, fits, single, chunk);
 }
 
 template int sufcheck_host<int32_t>(const uint8_t *, int64_t, const int32_t *, int64_t, int32_t *, int32_t);
