@@ -4,7 +4,9 @@ The shared library is built IN-TREE (deltaq_amd/libdq_sufsort_hip.so) so that it
 travels with the repository snapshot; it is git-ignored.
 
 Five translation units, compiled side by side and linked into one library:
-    dq_sorter_i32.hip / dq_sorter_i64.hip   the suffix sorter and its kernels per index width
+    dq_sorter_i32.hip / dq_sorter_i64.hip   the suffix sorter and its kernels per index width (dq_sorter_impl.h:
+                                            the doubling rounds and entry points; dq_round0.h: round 0, deciding
+                                            by the host-only dq_round0_plan.h; dq_sort_passes.h: the engine)
     dq_diff.hip                             match search, Diff.Create / Patch.Apply
     dq_sufcheck.hip                         LDSSChecker.Check of a suffix array on the device
     dq_abi.hip                              the C ABI and the batch pipeline (host code only)

@@ -26,10 +26,11 @@
 // no look-back, tiles are independent.
 #pragma once
 #include "dq_onesweep.h"
+#include "dq_round0_plan.h"
 
 namespace dq {
 
-constexpr int kBktCap = 12288;                             // words per tile at most (= threads x items of every geometry)
+// (kBktCap, words per tile at most = threads x items of every geometry: dq_round0_plan.h, which cuts the tiles)
 constexpr int kBktBins = kBktCap;                          // ~1 element per bin
 constexpr int kBktMaxBin = 48;                             // a fuller bin = not the data this path is for
 

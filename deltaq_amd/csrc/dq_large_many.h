@@ -22,7 +22,7 @@
 // No kernel of this file waits for another workgroup; the radix passes and the rebucket pass keep their bounded spins.
 // 32-bit indices only (dq_sorter_i32.hip includes this file through dq_small_many.h).
 #pragma once
-#include "dq_sorter_impl.h"
+#include "dq_sort_passes.h"
 
 namespace dq {
 
@@ -326,12 +326,10 @@ inline int large_many_sort(DeviceCtx &c, hipStream_t st, char *ws, const uint8_t
     LAUNCH(L, DQ_K_SMALL_MANY, segs, (int64_t)M * 13,
            hipLaunchKernelGGL(large_key0_kernel, dim3(large_grid(M, 2)), dim3(kLargeThreads), 0, st, (const uint8_t *)w.text,
                               (const int32_t *)lw.c, segs, M, K[0], V[0]));
-    int rc = onesweep_sort_pairs<int32_t>(L, w, K, V, M, 8 * kLargeKeyBytes + 3 + bit_length((uint64_t)(segs - 1)), cur);
-    if (rc != DQ_OK) return rc;
+    DQ_TRY(onesweep_sort_pairs<int32_t>(L, w, K, V, M, 8 * kLargeKeyBytes + 3 + bit_length((uint64_t)(segs - 1)), cur));
     if (twins) HIP_TRY(hipMemcpyAsync(tab.half.data(), lw.half, tab.half.size() * 4, hipMemcpyDeviceToHost, st));
     int64_t m = 0;
-    rc = rebucket<int32_t, true, true, true>(L, c, w, K[cur], (const int32_t *)V[cur], M, 0, 0, SA, K[cur ^ 1], V[cur ^ 1], &m);
-    if (rc != DQ_OK) return rc;
+    DQ_TRY(rebucket<int32_t, true, true, true>(L, c, w, K[cur], (const int32_t *)V[cur], M, 0, 0, SA, K[cur ^ 1], V[cur ^ 1], &m));
     cur ^= 1;
     bool marked = false;
     for (int32_t hf : tab.half) marked = marked || hf != 0;
@@ -362,11 +360,9 @@ inline int large_many_sort(DeviceCtx &c, hipStream_t st, char *ws, const uint8_t
         LAUNCH(L, DQ_K_SMALL_MANY, m, m * 28,
                hipLaunchKernelGGL(large_key2_kernel, dim3(large_grid(m, 2)), dim3(kLargeThreads), 0, st, K[cur], (const int32_t *)V[cur],
                                   (const int32_t *)w.ISA, (const int32_t *)lw.c, segs, m, (int32_t)h, kbits));
-        rc = onesweep_sort_pairs<int32_t>(L, w, K, V, m, kbits + rbits, cur);
-        if (rc != DQ_OK) return rc;
+        DQ_TRY(onesweep_sort_pairs<int32_t>(L, w, K, V, m, kbits + rbits, cur));
         int64_t m2 = 0;
-        rc = rebucket<int32_t, false, true, true>(L, c, w, K[cur], (const int32_t *)V[cur], m, kbits, 0, SA, K[cur ^ 1], V[cur ^ 1], &m2);
-        if (rc != DQ_OK) return rc;
+        DQ_TRY(rebucket<int32_t, false, true, true>(L, c, w, K[cur], (const int32_t *)V[cur], m, kbits, 0, SA, K[cur ^ 1], V[cur ^ 1], &m2));
         cur ^= 1;
         lists += m;
         m = m2;

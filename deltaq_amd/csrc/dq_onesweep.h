@@ -19,6 +19,7 @@
 #pragma once
 #include "dq_coded_keys.h"
 #include "dq_radix.h"
+#include "dq_round0_plan.h"
 
 namespace dq {
 
@@ -673,7 +674,7 @@ __global__ __launch_bounds__(kThreads, kMinWaves) void radix_rank_kernel(
 // ~1.6 % full table gives ~16 false hits, far below the threshold the host applies).  With C such samples
 // out of S, a suffix expects about n * 2C / S^2 twins under an L-byte key.  kgram_coll[L-1] = C for L.
 // It runs beside the histogram workgroups, so the sample costs no time of its own.
-constexpr int kKgramSamples = 1024;
+// (kKgramSamples: dq_round0_plan.h, whose choose_key_bytes reads the counters)
 constexpr int kKgramBits = 32768;                    // bits per length in the seen-set
 
 __device__ __forceinline__ void sample_kgrams(const uint8_t *__restrict__ text, int64_t n,

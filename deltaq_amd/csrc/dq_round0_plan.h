@@ -1,0 +1,264 @@
+// dq_round0_plan.h -- what round 0 of the suffix sorter decides, as pure host functions: key width, packed words or pairs,
+// coded keys, the bucketed round 0 and its geometry, the sample-sort round 0, fused ties, the dense / sparse guess, the
+// binned inverse suffix array, run lengths up front or late.  Each is a function of the words text_hist_kernel leaves
+// behind (TextStats), n, the index width and the flags; dq_round0.h launches what they say.  Only the C++ standard library
+// and dq_flags.h: tests/native/round0_plan_harness.cpp checks every field of every plan without a device.  The constants
+// the decisions share with the kernels are defined here, once; the kernels' headers include this file.
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
+
+#include "dq_flags.h"
+
+namespace dq {
+
+constexpr int kKgramSamples = 1024;            // suffixes text_hist_kernel samples for repetition (dq_onesweep.h, sample_kgrams)
+constexpr int kBktCap = 12288;                 // words per tile of the bucketed round 0 at most (dq_bucket_sort.h)
+constexpr int kSplitTop = 512;                 // sample-sort round 0 (dq_split_round0.h): top buckets = regions of pass A
+constexpr int kSplitSub = 512;                 // parts of a top bucket = regions of pass B
+constexpr int kSplitBuckets = kSplitTop * kSplitSub;             // 262 144: a 256 MiB text has 1024 suffixes per bucket
+constexpr int kFinCap = 2048;                  // the longest bucket its finish kernel sorts
+// smallest text the sample-sort round 0 can take: its 2 Mi sampled keys are sorted in idle key buffers, and pass A's spill (n / 8
+// + 1024 entries per top bucket) must fit a quarter of the suffix array
+constexpr int64_t kSplitMinN = 5ll << 20;
+// coded round 0 (dq_alpha_code.h): from this size on, and only if a byte costs at most this many bits on average
+constexpr int64_t kCodedMinN = 8ll << 20;
+constexpr double kCodedMaxAvgLen = 5.8;       // >= 11 characters per key (a 205-symbol Python source tree: 6.17, no gain)
+constexpr int kTieSamples = 4096;             // adjacent sorted pairs sample_ties_kernel looks at for the dense guess
+constexpr int64_t kRound0MinN = 1 << 16;      // below this a text takes the plain passes, a general rebucket, no sample
+
+// bits of the largest suffix index, n - 1
+inline int index_bits(int64_t n) { return n <= 1 ? 1 : 64 - __builtin_clzll((uint64_t)(n - 1)); }
+
+// What text_hist_kernel saw, held by value from the one readback on: `words` are the 256 + 10 words it leaves in
+// w.bytehist -- the byte histogram, the eight k-gram counters ([L - 1]: sampled suffixes whose first L bytes an earlier
+// sample had too), the long-run flag (a run of >= 64 equal bytes somewhere), the 16-byte chunks of one value.
+struct TextStats {
+    int64_t n = 0;
+    int ib = 1;                         // index_bits(n)
+    int64_t hist[256] = {};
+    int64_t kgram[8] = {};
+    bool long_run = false;
+    int64_t run_chunks = 0;
+    double h0 = 0;                      // order-0 entropy, bits per byte
+    int sigma = 0;                      // symbols that occur
+    int64_t cmax = 0;                   // the most frequent one's count
+
+    TextStats() = default;
+    TextStats(const int64_t *words, int64_t n_) : n(n_), ib(index_bits(n_)), long_run(words[256 + 8] != 0), run_chunks(words[256 + 9])
+    {
+        std::copy(words, words + 256, hist);
+        std::copy(words + 256, words + 256 + 8, kgram);
+        for (int b = 0; b < 256; ++b) {
+            cmax = std::max(cmax, hist[b]);
+            if (hist[b] > 0) { ++sigma; const double p = (double)hist[b] / (double)n; h0 -= p * std::log2(p); }
+        }
+    }
+};
+
+// Number of leading text bytes worth sorting in round 0: enough bits, under an order-0 model
+// of the text, to make ties among n suffixes rare (~n/1000); text-like inputs get all 8.
+// If (almost) that many key bytes fit into one 64-bit word next to the suffix index
+// (ib = bits of n-1), round 0 sorts PACKED words (key << ib | suffix): 16 B per element per
+// pass instead of 24 and no value array; the few extra ties go to the sparse finishing path.
+struct KeyPlan { int kb = 8; bool packed = false; };
+
+inline KeyPlan choose_key_bytes(const TextStats &s, const Flags &F)
+{
+    const int64_t n = s.n;
+    const double need = std::log2((double)std::max<int64_t>(n, 2)) + 10.0;
+    int kb = 8;
+    if (s.h0 >= 0.25) kb = std::min(8, std::max(3, (int)std::ceil(need / s.h0)));
+    const int fit = (64 - s.ib) / 8;
+    // packed if the bytes that fit still leave at most ~1/8 of the suffixes tied
+    bool packed = fit >= 2 && (kb <= fit || (double)fit * s.h0 >= std::log2((double)std::max<int64_t>(n, 2)) + 3.0);
+    // Veto from the k-gram sample: an order-0 model cannot see repetition.  With S sampled suffixes and C
+    // adjacent sorted pairs agreeing on L bytes, a suffix expects about n * 2C / S^2 twins under an L-byte
+    // key.  Repetitive (text-like) data takes the 8-byte pair path, which is built for many ties.
+    // (It takes 1 sample in 16 with a twin among the samples: a few repeated regions in otherwise random data
+    // are what the packed sort and its sparse finishing are good at.)
+    if (n >= kKgramSamples * 8) {
+        const int L = packed ? std::min(kb, fit) : kb;
+        const int64_t C = s.kgram[std::max(L, 1) - 1];
+        const double twins = (double)n * 2.0 * (double)C / ((double)kKgramSamples * (double)kKgramSamples);
+        if (C >= kKgramSamples / 16 && twins > 0.25) { packed = false; kb = 8; }
+    }
+    if (F.packed) packed = *F.packed != 0 && fit >= 2;
+    if (packed) kb = std::min(kb, fit);
+    if (F.key_bytes) {
+        kb = *F.key_bytes;
+        if (kb > fit || kb < 2) packed = false;
+    }
+    return {kb, packed};
+}
+
+// Text-like input on the 8-byte pair path: the 64 key bits hold the codewords of an alphabetic prefix code instead of 8
+// raw bytes (dq_alpha_code.h) when that makes the key reach at least ~10 characters on average.  Whether the code is
+// worth building: the expected codeword length is at least the order-0 entropy, and texts with more than 128 symbols
+// must be large enough to hide the construction (0.2 ms for 73 symbols, 1-2 ms for 200+, on the host while the device
+// waits).  The code's own average length decides afterwards (kCodedMaxAvgLen; DQ_CODED=1: whatever it is).
+inline bool coded_keys_tried(const TextStats &s, const Flags &F, KeyPlan k)
+{
+    bool coded = !k.packed && k.kb == 8 && s.n >= kCodedMinN;
+    if (coded) coded = s.h0 <= kCodedMaxAvgLen - 0.25 && (s.sigma <= 128 || s.n >= 2 * kCodedMinN);
+    if (F.coded) coded = *F.coded != 0 && !k.packed && k.kb == 8 && s.n >= 64;
+    return coded;
+}
+
+// Round 0 as a sample sort (dq_split_round0.h) instead of eight digit passes: the 8-byte pair path -- coded keys (text-like
+// input) or raw ones (real binaries) --, int32 indices, from 64 MiB on.  Measured, sample sort against digit passes in one
+// process: enwik-style text 64 MiB 7.29 / 7.86 ms, 96 MiB 9.87 / 11.11, 128 MiB 12.42 / 14.12, 256 MiB 24.9 / 29.3 (32 MiB, an
+// earlier build: 5.54 / 4.60 -- its fixed costs, a 2 Mi-key sample sorted and 262 144 workgroups of the finish kernel, want
+// a long text); first 128 MiB of libtorch_cpu.so 19.9 / 21.75 (17 M copies of heavy keys placed unsorted; while they
+// took the sorted overflow route: 22.7).  Up to the size whose mean bucket is half the finish kernel's capacity (256 MiB).
+// DQ_SPLIT = 0 | 1 | 2 overrides (1: from kSplitMinN on; 2: also past what the sample says about heavy keys -- for the tests).
+inline bool split_round0_wanted(int64_t n, KeyPlan k, int idx_bytes, const Flags &F)
+{
+    if (idx_bytes != 4 || k.packed || k.kb != 8 || n < kSplitMinN || n > (int64_t)kSplitBuckets * (kFinCap / 2)) return false;
+    if (F.split) return *F.split != 0;
+    if (F.key_bytes || F.no_bucket) return false;     // (forced plain paths of the tests stay what they were)
+    return n >= (64ll << 20);
+}
+
+// The bucketed round 0 (dq_bucket_sort.h): random-like input (packed words = few ties expected) of a size whose 2-byte
+// (3-byte) buckets fit a workgroup's LDS -- two (three) digit passes on the top key bits, then every bucket is finished
+// in LDS.  Every field is zero where the path does not apply.
+struct BucketPlan {
+    bool applies = false;
+    int keybits = 0, bbytes = 0, lowbits = 0;   // key bits per word, bytes the buckets are cut by, key bits below them
+    int64_t X = 0, C = 0, ntiles = 0;           // room of a tile's longest bucket, words per tile, tiles
+    bool ext = false;                           // one more byte of key beside every word
+    bool xcd_pass = false;                      // the XCD-local first pass (dq_xcd_rank.h)
+    int64_t hb = 0;                             // whole bytes the members of a tie group share
+};
+
+inline BucketPlan plan_bucketed(const TextStats &s, const Flags &F, KeyPlan k, bool coded, int idx_bytes)
+{
+    const int64_t n = s.n;
+    const int ib = s.ib;
+    BucketPlan p;
+    if (coded) return p;                              // (the digit offsets on the device are those of the coded keys)
+    if (F.no_bucket || F.no_fused_ties || F.sparse || F.key_bytes) return p;
+    const bool forced = F.bucket.has_value();
+    if (ib > 31 || n < kRound0MinN) return p;         // a suffix must fit 31 bits next to the tie flag
+    // a run of >= 64 equal bytes somewhere (zero padding of real binaries; text_hist_kernel saw it): more equal
+    // keys than a bin takes -- the pass would only raise its flag and be repeated by the plain passes
+    if (!forced && s.long_run) return p;
+    int keybits = std::min(64 - ib, 36);
+    if (F.bucket_keybits) keybits = std::max(17, std::min(keybits, *F.bucket_keybits));      // (tests: few key bits on small inputs)
+    const double tied = (double)n * std::exp2(-(double)keybits * s.h0 / 8.0);
+    if (!k.packed) {
+        // Words were not chosen because too many suffixes would stay tied for the tie-bit path of the plain
+        // passes (2 GiB of random bytes: 33 key bits leave 1/4 of them tied).  Those ties are shallow, which the
+        // direct-comparison finisher takes; the key must still separate most suffixes, and the k-gram sample
+        // must not have seen repetition (it then set kb = 8).
+        if (!forced && (k.kb >= 8 || tied > 0.3)) return p;
+    }
+    // longest bucket expected when the words are grouped by their first 2 (3) bytes; tiles are cut for it
+    const double pm = (double)s.cmax / (double)n;
+    int bbytes = 2;
+    double est = (double)n * pm * pm;
+    double need = est + 6.0 * std::sqrt(est) + 64.0;
+    // a tile must not span more than 64 two-byte buckets (its keys, relative to its first bucket, take 26
+    // bits + 6 arrival bits): buckets of >= 192 words on average, i.e. texts of >= 12 MiB
+    const bool force3 = forced && *F.bucket == 3;          // (tests: 3-byte buckets on mid-size inputs)
+    if (need > 5120 || (!forced && n < (12 << 20)) || force3) {
+        if (keybits - 24 >= 8 && (forced || n >= (12 << 20))) {
+            bbytes = 3;
+            est *= pm;
+            need = est + 6.0 * std::sqrt(est) + 64.0;
+        }
+        if (need > 5120 || (bbytes == 2 && !forced)) {
+            if (!forced) return p;
+            need = 5120;
+        }
+    }
+    p.applies = true;
+    p.keybits = keybits;
+    p.bbytes = bbytes;
+    p.X = std::min<int64_t>(((int64_t)need + 255) / 256 * 256, 5120);
+    p.C = kBktCap - p.X;
+    p.lowbits = keybits - 8 * bbytes;
+    p.ntiles = (n + p.C - 1) / p.C;
+    // One more byte of key beside every word (kTextPackedExt / kKeysExt passes, bucket_sort_kernel<kExt>) where the
+    // word's own key bits would leave more than a few per cent of the suffixes tied: 2 GiB of random bytes have 33
+    // bits beside the 31-bit suffix -- 22 % tied, 19 ms of direct comparisons behind one 64-byte sector each --
+    // and 41 with the byte (0.1 %).  The bytes live in the idle index buffer Va (two arrays of n, each a multiple of 256).
+    // DQ_BUCKET_EXT = 0 | 1 overrides (tests: small inputs).
+    const bool room = (size_t)2 * (((size_t)n + 255) / 256 * 256) <= (size_t)(n + 2) * (size_t)idx_bytes;
+    p.ext = keybits + 8 <= 56 && p.lowbits + 8 <= 18 && tied > 0.02 && room;
+    if (F.bucket_ext) p.ext = *F.bucket_ext != 0 && keybits + 8 <= 56 && room;
+    // The first pass: persistent and XCD-local (dq_xcd_rank.h) -- its regions cut in 8 sub-regions by the byte
+    // histograms of the text's eighths that text_hist_kernel made -- or, with the extra key byte or under
+    // DQ_OLD_FIRST_PASS=1, radix_rank_kernel<kTextPacked(Ext)>.  The regions hold the same words either way.
+    p.xcd_pass = !p.ext && !F.old_first_pass;
+    p.hb = (keybits + (p.ext ? 8 : 0)) / 8;
+    return p;
+}
+
+// Packed words were chosen because few ties are expected: the last pass then records the tie structure itself (1 bit per
+// suffix + 2 words per tile and digit, in the idle Vb buffer) instead of writing the sorted words for a rebucket pass.
+inline bool fused_ties_wanted(int64_t n, KeyPlan k, const Flags &F)
+{
+    return k.packed && k.kb >= 2 && n >= kRound0MinN && !F.no_fused_ties && !F.sparse;
+}
+
+// Few ties (random-like input): they are finished by direct comparison / key extension from the text, without the n
+// random writes of a full inverse suffix array.  Many ties: the ISA is needed for doubling, and the dense case writes it
+// in the rebucket pass itself.  Inputs whose order-0 entropy already promised few ties -- packed words or a short key --
+// are not asked.  Below 8 MiB the sample's host round trip costs more than a wrong guess: 8-byte pair keys were chosen
+// because the text repeats itself, so "many ties" is the guess, and the ISA of a short text is cheap either way.  From
+// there on kTieSamples adjacent sorted pairs predict which.
+enum class DenseGuess { kNeither, kGuessDense, kTakeSample };
+
+inline DenseGuess dense_guess(int64_t n, KeyPlan k)
+{
+    if (n < kRound0MinN || k.packed || k.kb != 8) return DenseGuess::kNeither;
+    return n < (8 << 20) ? DenseGuess::kGuessDense : DenseGuess::kTakeSample;
+}
+
+// tied_pairs: what the sample counted (kTakeSample only).  A pair ties with probability ~ (tied fraction) * (1 - 1 /
+// group size); 1/12 ~ tied fraction 1/6.  DQ_SPARSE = 0 | 1 overrides whatever was guessed or sampled.
+inline bool predict_dense(DenseGuess g, int64_t tied_pairs, const Flags &F)
+{
+    if (F.sparse) return *F.sparse == 0;
+    return g == DenseGuess::kGuessDense || (g == DenseGuess::kTakeSample && tied_pairs * 12 > kTieSamples);
+}
+
+// The suffix-binned build of the inverse suffix array (dq_isa_pairs.h) pays once the array outgrows the last-level cache:
+// 4n > 128 MiB.  Below that the plain scatter is ahead -- 64 KiB ... 16 MiB of text: 1-6 %.  DQ_BINNED_ISA=1: from 64 KiB
+// on, for the tests.  (Two index fields must fit a word.)
+inline bool binned_isa_pays(int64_t n, const Flags &F)
+{
+    const bool pays = F.binned_isa ? *F.binned_isa != 0 : n > (32ll << 20);
+    return pays && n >= kRound0MinN && 2 * index_bits(n) <= 63 && !F.no_binned_isa;
+}
+
+// Runs of one byte (dq_runs.h; int32 indices, texts of >= 64 KiB).
+struct RunPlan {
+    // run lengths + the run-order round up front.  They cost about one doubling round: worth it where a good part of the
+    // text lies in runs -- padded images, sparse files; measured on the image's shared libraries, whose long tie tails are
+    // code repeated for several targets, not runs: 5-20 % slower with it.  1/16 of the text in 16-byte chunks of one value,
+    // or the caller has seen the stretches (period_hint)
+    bool runs_wanted = false;
+    bool long_run_seen = false;         // text_hist_kernel saw a run of >= 64 equal bytes somewhere
+    // the late rounds also take stretches that repeat with a period > 1, which the histogram pass does not see: large
+    // groups that stop shrinking are what calls them
+    bool late_runs_possible = false;
+};
+
+inline RunPlan plan_runs(const TextStats &s, const Flags &F, int idx_bytes, int period_hint)
+{
+    RunPlan r;
+    const bool can = idx_bytes == 4 && s.n >= kRound0MinN;
+    r.long_run_seen = can && s.long_run;
+    r.runs_wanted = (r.long_run_seen && s.run_chunks * 16 * 16 >= s.n) || (period_hint > 0 && can);
+    r.late_runs_possible = can;
+    if (F.runs) { r.runs_wanted = idx_bytes == 4 && *F.runs != 0; r.late_runs_possible = r.late_runs_possible && *F.runs != 0; }
+    if (F.mid_groups) r.runs_wanted = r.runs_wanted && *F.mid_groups >= 256;   // (the LDS class carries the run offsets)
+    return r;
+}
+
+}  // namespace dq

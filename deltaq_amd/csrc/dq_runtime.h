@@ -2,8 +2,13 @@
 // (the DQ_* flags and their per-call snapshot: dq_flags.h), per-kernel hipEvent timers, device contexts (stream +
 // workspace + pinned areas) and their leases, and the entry points one unit calls in another.  Host code only (no
 // kernels): C++17 inline variables give every unit the same state.
-//   dq_sorter_i32.hip / dq_sorter_i64.hip   the suffix sorter (dq_sorter_impl.h) for 32- / 64-bit indices; the i32 unit
-//                                           also holds the many-short-texts launches (dq_small_many.h)
+//   dq_sorter_i32.hip / dq_sorter_i64.hip   the suffix sorter for 32- / 64-bit indices; the i32 unit also holds the
+//                                           many-short-texts launches (dq_small_many.h)
+//       dq_round0_plan.h                    what round 0 decides: host-only, standard library + dq_flags.h
+//       dq_sort_passes.h                    workspace, digit passes, pair sort, rebucket, binned ISA: the engine the
+//                                           sorter shares with the segmented sort of dq_large_many.h
+//       dq_round0.h                         round 0: histogram, key width, the sorted keys, the first tie list
+//       dq_sorter_impl.h                    sparse finish, doubling rounds, entry points, workspace exports
 //   dq_diff.hip                             match search, Diff.Create / Patch.Apply, the many-new-files index
 //   dq_sufcheck.hip                         LDSSChecker.Check of a suffix array on the device (dq_sufcheck.h)
 //   dq_abi.hip                              the C ABI (include/dq_sufsort.h), the batch pipeline, profile getters
@@ -96,6 +101,13 @@ inline hipError_t dq_host_malloc(void **p, size_t bytes, unsigned flags)
         hipError_t e_ = (expr);                                                         \
         if (e_ != hipSuccess)                                                           \
             return fail(e_ == hipErrorOutOfMemory ? DQ_ERR_OOM : DQ_ERR_HIP, #expr, e_); \
+    } while (0)
+
+// a step that returns one of the library's codes: anything but DQ_OK ends the calling function with it
+#define DQ_TRY(...)                           \
+    do {                                      \
+        const int rc_ = (__VA_ARGS__);        \
+        if (rc_ != DQ_OK) return rc_;         \
     } while (0)
 
 // ------------------------------------------------------------------ profiling

@@ -45,12 +45,11 @@
 // SsSort.cs:934-1269, is what dominates the reference on text); the suffix array is unchanged by any of this.
 #pragma once
 #include "dq_onesweep.h"
+#include "dq_round0_plan.h"
 
 namespace dq {
 
-constexpr int kSplitTop = 512;                                   // top buckets = regions of pass A
-constexpr int kSplitSub = 512;                                   // parts of a top bucket = regions of pass B
-constexpr int kSplitBuckets = kSplitTop * kSplitSub;             // 262 144: a 256 MiB text has 1024 suffixes per bucket
+// (kSplitTop, kSplitSub, kSplitBuckets and kFinCap: dq_round0_plan.h, which decides by them whether the path is taken)
 // sampled keys per bucket: 8 -> bucket sizes spread like Gamma(8) around the mean (sigma 35 %): one bucket in ~250 grows past
 // twice the mean, its slot, and takes the overflow route -- cheaper than sorting a sample twice as long (16: 0.25 ms more)
 constexpr int kSplitOversample = 8;
@@ -59,7 +58,6 @@ constexpr int kSplitThreads = 512;
 constexpr int kSplitItemsA = 20, kSplitItemsB = 16;              // keys per thread: pass A (text -> pairs), pass B (pairs -> slots: 16 keep it inside 128 registers)
 constexpr int kSplitTileA = kSplitThreads * kSplitItemsA;        // 10 240 keys per tile
 constexpr int kSplitTileB = kSplitThreads * kSplitItemsB;        // 8 192
-constexpr int kFinCap = 2048;                                    // the longest bucket the finish kernel sorts
 constexpr int kFinSmallCap = 1024;                               // ... and what its small geometry takes
 
 struct SplitCtl {
