@@ -59,6 +59,9 @@ internal static unsafe class Native
     internal static extern int dq_last_index_many_info(long* info, int count);
 
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern int dq_last_index_large_info(long* info, int count);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
     internal static extern int dq_bsdiff_index_clone(IntPtr index, int device, IntPtr* indexOut);
 
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
@@ -441,6 +444,23 @@ public sealed unsafe class HipDiffIndex : IDisposable
         fixed (long* p = info)
         {
             Native.Check(Native.dq_last_index_many_info(p, info.Length), nameof(Native.dq_last_index_many_info));
+        }
+
+        return info;
+    }
+
+    /// <summary>
+    /// The large class of the last CreateMany of an index on this thread (dq_last_index_large_info): new files of
+    /// 65 537 to 524 288 bytes through shared launches, those launches, files of the class diffed one by one because
+    /// too few followed one another, positions of the agreement counts built on the device, microseconds in copies
+    /// and the kernel.
+    /// </summary>
+    public static long[] LastIndexLargeInfo()
+    {
+        var info = new long[5];
+        fixed (long* p = info)
+        {
+            Native.Check(Native.dq_last_index_large_info(p, info.Length), nameof(Native.dq_last_index_large_info));
         }
 
         return info;

@@ -155,8 +155,11 @@ class DiffIndex:
 
     def CreateMany(self, news) -> list:
         """``[self.Create(n) for n in news]`` in one call (dq_bsdiff_index_diff_many): new files of at most 65 536 bytes
-        share their device launches, where at least 32 of them follow one another; longer ones are diffed one by
-        one.  ``news``: a sequence of bytes-likes or uint8 arrays."""
+        share their device launches, where at least 32 of them follow one another; so do new files of 65 537 to
+        524 288 bytes, in launches of their own kernel, where at least 64 of them follow one another
+        (``_abi.last_index_large_info()`` reports that class); longer ones, and files in shorter runs, are diffed one
+        by one.  Patches come back in input order and are ``self.Create``'s byte for byte whichever way a file went.
+        ``news``: a sequence of bytes-likes or uint8 arrays."""
         N = [_as_text(x) for x in news]
         count = len(N)
         if count == 0:

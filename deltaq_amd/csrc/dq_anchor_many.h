@@ -1,10 +1,12 @@
 // dq_anchor_many.h -- step 1 of the scan loop (Diff.cs:100-125) for MANY files in one launch, one file per workgroup:
 // anchor_many_kernel and anchor_mid_many_kernel for the pairs of dq_bsdiff_create_many, anchor_index_many_kernel for the
-// new files of dq_bsdiff_index_diff_many.  One loop body, anchor_scan_file, instantiated three times.
+// new files of dq_bsdiff_index_diff_many up to kMidMaxN bytes and anchor_index_large_kernel for its longer ones.  One
+// loop body, anchor_scan_file, instantiated four times.
 //
 // Launch shape.  dq_anchor_scan.h spreads ONE long new file over a persistent multi-grid and pays for it with flags,
 // bounded spins and a host fallback.  A new file of up to kMidMaxN bytes needs none of that: it fits the LDS of one
-// workgroup, so its whole anchor search runs inside it and the launch takes as many files as the caller has:
+// workgroup (of a longer one, in the fourth class, P does), so its whole anchor search runs inside it and the launch
+// takes as many files as the caller has:
 //   * grid and work list as small_many_kernel (dq_small_many.h): as many workgroups as are resident, each claims the
 //     next file of a longest-new-first list with ONE agent-scope relaxed atomic add by thread 0, handed on through LDS
 //     (for_each_claimed, dq_device_utils.h);
@@ -13,7 +15,7 @@
 // A file outside its class's limits gets counts[j] = -1 and is never copied: nothing is read or written out of the LDS
 // block's bounds.  What a file leaves behind in LDS is harmless to the next one: old and new are only read below n and
 // m (ms_load8's whole dwords beyond them are masked out by the lengths), P is rebuilt for all of [0, m] before its
-// first read.
+// first read (the fourth class: built for every stretch before that stretch's first read).
 //
 // Search is ms_search_one (dq_match_search.h): the reference's answer for every position (ties and the zero sentinel
 // slot I[n] = 0 as documented there), found by a lower bound that skips the prefix both interval ends share with the
@@ -31,7 +33,7 @@
 // answers nobody reads.  Only when the head does not break do the lanes take the next positions, one each.  The
 // anchors and the Search count do not depend on the window's width.
 //
-// The three classes (threads = window; LDS bytes; workgroups per CU; the body needs about 190 VGPRs):
+// The four classes (threads = window; LDS bytes; workgroups per CU; the body needs about 190 VGPRs):
 //   * short, anchor_many_kernel: both files of at most kDiffManyMax = 8192 bytes.  256 threads.  LDS holds old, its
 //     suffix array narrowed to 16 bits, new, and P as one uint16 per position (AgreeCounts): 49 240 bytes, three
 //     workgroups per CU.
@@ -54,7 +56,20 @@
 //     dwords around them that ms_load8 touches when 12 bytes exist behind its position.  Both widths are compiled; the
 //     driver launches 256 threads, two workgroups per CU (kIndexManyThreads, dq_diff.hip; DQ_INDEX_MANY_THREADS takes
 //     the other): docs/ROUNDS.md, round 12, has the measurement.
+//   * indexed large, anchor_index_large_kernel<524 288, 512>: new of kMidMaxN + 1 .. 524 288 bytes against a DiffIndex.
+//     The new file STAYS in device memory, where the chunk's copy put it (the loop body takes a plain pointer;
+//     ms_search_one and ms_load8 read it there as they read old).  LDS holds P alone, as AgreeMaskLazy: a 64-bit mask
+//     word and a 32-bit count per 64 positions, 98 336 bytes, 98 432 with the rest of the block -- one workgroup per CU.
+//     Rebuilding that P for all of [0, m] at every control triple, as the other classes do, would make the work
+//     m x triples bytes read one by one from device memory (a 512 KiB file with an edit every 150 bytes: 3500 triples,
+//     1.8 GB in one workgroup).  So it is built ON DEMAND: reset() at a new alignment forgets it, ensure(upto) builds the
+//     64-position steps up to the one `upto` lies in before P is read there, rounded up to a stretch of
+//     kLazyStepsPerWave steps per wave, and the counts are relative to where the built range begins -- the loop only
+//     ever takes differences of P.  The work per file then follows the bytes its matches cover.  The anchors and the
+//     Search count do not depend on the stretch.  (docs/ROUNDS.md, round 18.)
 #pragma once
+#include <type_traits>
+
 #include "dq_match_search.h"
 
 namespace dq {
@@ -77,6 +92,7 @@ struct AnchorMidFiles {
 struct AnchorIndexFiles {
     uint32_t new_w[kMidMaxN / 4 + 4];
 };
+struct AnchorNoFiles {};                          // (the large indexed class: both files stay in device memory)
 
 // ---- P[i] = number of k < i with agree(k), for i = 0 .. m, under the alignment `shift`:
 // agree(k) = k < m, 0 <= k + shift < n, old[k + shift] == new[k].  (k + shift < 0: positions in front of the anchor the
@@ -84,7 +100,10 @@ struct AnchorIndexFiles {
 
 // one count per position: m <= kDiffManyMax
 struct AgreeCounts {
+    static constexpr bool kLazy = false;
     uint16_t p[kDiffManyMax + 2];
+    template <int kWaves, typename LenT>
+    __device__ __forceinline__ void ensure(const uint8_t *, LenT, const uint8_t *, int, LenT, int, int32_t *) {}    // (P is whole)
     __device__ __forceinline__ int prefix(int i) const { return (int)p[i]; }
 
     template <int kWaves, typename LenT>
@@ -119,6 +138,7 @@ struct AgreeMask {
     static constexpr int kShift = kBits == 64 ? 6 : 5;         // i >> kShift: the word of position i
     static constexpr int kPerStep = 64 / kBits;                // words of a step
     static constexpr int kWords = (kMidMaxN / 64 + 1) * kPerStep;
+    static constexpr bool kLazy = false;
     WordT mask[kWords];                           // bit (i % bits) of mask[i / bits]: agree(i), i = 0 .. m (agree(m) = 0)
     uint32_t cnt[kWords];                         // agreeing positions in front of the word
 
@@ -128,6 +148,8 @@ struct AgreeMask {
         if constexpr (kBits == 64) return (int)(cnt[i >> kShift] + (uint32_t)__builtin_popcountll(below));
         else return (int)(cnt[i >> kShift] + (uint32_t)__builtin_popcount(below));
     }
+    template <int kWaves, typename LenT>
+    __device__ __forceinline__ void ensure(const uint8_t *, LenT, const uint8_t *, int, LenT, int, int32_t *) {}    // (P is whole)
 
     template <int kWaves, typename LenT>
     __device__ __forceinline__ void rebuild(const uint8_t *old, LenT n, const uint8_t *nw, int m, LenT shift, int32_t *tmp)
@@ -170,6 +192,82 @@ struct AgreeMask {
     }
 };
 
+// The same, built on demand: m <= kMaxM, new and old both in device memory.  One 64-bit mask word and one count per
+// step of 64 positions; built are the steps of the positions [lo, hi), lo and hi multiples of 64, and cnt[] counts from
+// lo: prefix(i) is valid for lo <= i < hi and only differences of it mean anything.  (Once the step of position m is
+// built, hi = 64 * (m / 64 + 1) > m: nothing is asked beyond it.)
+constexpr int kLazyStepsPerWave = 4;              // steps a wave builds at least, once something has to be built
+template <int kMaxM>
+struct AgreeMaskLazy {
+    static_assert(kMaxM % 64 == 0, "the mask is built 64 positions a step");
+    static constexpr bool kLazy = true;
+    static constexpr int kSteps = kMaxM / 64 + 1;
+    uint64_t mask[kSteps];                        // bit (i % 64) of mask[i / 64]: agree(i), for the built steps
+    uint32_t cnt[kSteps];                         // agreeing positions in [lo, 64 * step)
+    int32_t lo, hi;
+    uint32_t total;                               // agreeing positions in [lo, hi)
+    int32_t built;                                // steps built since the kernel set it to 0: what it reports per file
+
+    __device__ __forceinline__ int prefix(int i) const
+    {
+        const uint64_t below = mask[i >> 6] & (((uint64_t)1 << (i & 63)) - (uint64_t)1);
+        return (int)(cnt[i >> 6] + (uint32_t)__builtin_popcountll(below));
+    }
+
+    // A new alignment: nothing is built, the next step to build is the one `from` (the cursor) lies in.  Called by the
+    // whole workgroup; begins and ends with a barrier.
+    __device__ __forceinline__ void reset(int from)
+    {
+        __syncthreads();                                       // (everybody has read hi and total)
+        if (threadIdx.x == 0) { lo = hi = from & ~63; total = 0; }
+        __syncthreads();
+    }
+
+    // P is readable up to `upto` (<= m) afterwards.  Called by the whole workgroup with the same `upto` in every thread.
+    // Where steps are missing, they are built up to the end of a stretch of kLazyStepsPerWave * kWaves steps (or the
+    // step of m), split evenly among the waves: one ballot per step, the waves' totals added as AgreeMask::rebuild
+    // adds them, the counts going on from `total`.  tmp: kWaves words, free when the call is made except for reads
+    // of it that a barrier has not yet closed (the first barrier below closes them).
+    template <int kWaves, typename LenT>
+    __device__ __forceinline__ void ensure(const uint8_t *old, LenT n, const uint8_t *nw, int m, LenT shift, int upto, int32_t *tmp)
+    {
+        const int have = hi;
+        if (upto < have) return;                               // (uniform)
+        constexpr int kStretch = kLazyStepsPerWave * kWaves;
+        const int lane = lane_id();
+        const int w = (int)threadIdx.x >> 6;
+        const int steps = (m >> 6) + 1;                        // position m is inside the last one
+        const int s_have = have >> 6;
+        const int need = (upto >> 6) + 1 - s_have;
+        const int s_end = min(steps, s_have + (need + kStretch - 1) / kStretch * kStretch);
+        const int per = (s_end - s_have + kWaves - 1) / kWaves;
+        const int s0 = min(s_have + w * per, s_end), s1 = min(s0 + per, s_end);
+        const uint32_t before = total;
+        __syncthreads();                                       // (tmp, hi and total are read)
+        uint32_t run = 0;                                      // (wave-uniform)
+        for (int s = s0; s < s1; ++s) {
+            const int i = 64 * s + lane;
+            const LenT k = (LenT)i + shift;
+            const bool ok = i < m && k >= 0 && k < n && old[k] == nw[i];
+            const uint64_t bal = __ballot(ok);
+            if (lane == 0) { mask[s] = bal; cnt[s] = run; }
+            run += (uint32_t)__builtin_popcountll(bal);
+        }
+        if (lane == 0) tmp[w] = (int32_t)run;
+        __syncthreads();
+        uint32_t front = before, all = before;
+#pragma unroll
+        for (int i = 0; i < kWaves; ++i) {
+            const uint32_t t = (uint32_t)tmp[i];
+            if (i < w) front += t;
+            all += t;
+        }
+        for (int x = s0 + lane; x < s1; x += kWave) cnt[x] += front;        // (the wave's own words)
+        if (threadIdx.x == 0) { hi = 64 * s_end; total = all; built += s_end - s_have; }
+        __syncthreads();
+    }
+};
+
 // ---- the LDS block of a workgroup of kWaves waves
 template <typename Files, typename Agree, int kWaves>
 struct AnchorLds {
@@ -184,11 +282,15 @@ using AnchorShortLds = AnchorLds<AnchorShortFiles, AgreeCounts, kWavesPerBlock>;
 using AnchorMidLds = AnchorLds<AnchorMidFiles, AgreeMask<uint32_t>, kAmMidThreads / kWave>;
 template <int kThreads>
 using AnchorIndexLds = AnchorLds<AnchorIndexFiles, AgreeMask<uint64_t>, kThreads / kWave>;
+template <int kMaxM, int kThreads>
+using AnchorIndexLargeLds = AnchorLds<AnchorNoFiles, AgreeMaskLazy<kMaxM>, kThreads / kWave>;
 
-// The anchors of one new file (m bytes at nw, in LDS) against old (n bytes) with its suffix array sa and, where there is
+// The anchors of one new file (m bytes at nw, in LDS or in device memory) against old (n bytes) with its suffix array sa and, where there is
 // one, the prefix table (ptab, pk) -- in LDS or in device memory, as the class has them: (cursor, hit_pos) per control
 // triple, the last one with cursor == m, at most `cap` of them written (*count_out = -1 if there were more: the host
-// then takes the file by itself); *searches_out = the Search calls of the reference's loop.
+// then takes the file by itself); *searches_out = the Search calls of the reference's loop.  P is made for a new
+// alignment by realign -- rebuilt whole, or (a lazy P) forgotten -- and L.P.ensure comes before every read of it: nothing
+// for a P that is whole.
 template <int kWaves, typename LenT, typename IdxT, typename Lds>
 __device__ __forceinline__ void anchor_scan_file(Lds &L, const uint8_t *__restrict__ old, LenT n, const IdxT *__restrict__ sa,
                                                  const IdxT *__restrict__ ptab, int pk, const uint8_t *nw, int m,
@@ -200,7 +302,12 @@ __device__ __forceinline__ void anchor_scan_file(Lds &L, const uint8_t *__restri
     // the loop's state, the same in every thread
     int cursor = 0, hit_pos = 0, hit_len = 0, searches = 0, emitted = 0;
     LenT shift = 0;
-    if (m > 0) L.P.template rebuild<kWaves>(old, n, nw, m, shift, L.tmp);
+    constexpr bool kLazy = std::remove_reference_t<decltype(L.P)>::kLazy;
+    auto realign = [&]() {
+        if constexpr (kLazy) L.P.reset(cursor);
+        else L.P.template rebuild<kWaves>(old, n, nw, m, shift, L.tmp);
+    };
+    if (m > 0) realign();
     while (cursor < m) {
         cursor += hit_len;
         int counted = cursor, carried = 0;
@@ -217,6 +324,7 @@ __device__ __forceinline__ void anchor_scan_file(Lds &L, const uint8_t *__restri
             hit_len = L.hit[1];
             ++searches;
             counted = max(counted, cursor + hit_len);
+            L.P.template ensure<kWaves>(old, n, nw, m, shift, counted, L.tmp);
             carried = L.P.prefix(counted) - L.P.prefix(cursor);
             __syncthreads();                                   // (L.hit is read: the next window may write it)
             if ((hit_len == carried && hit_len != 0) || hit_len > carried + 8) { broke = true; break; }
@@ -232,6 +340,13 @@ __device__ __forceinline__ void anchor_scan_file(Lds &L, const uint8_t *__restri
             const int end = live ? c + len : -1;
             int upto = block_excl_max<int, kWaves>(end, L.tmp);  // (one barrier)
             upto = max(max(upto, end), counted);
+            if constexpr (kLazy) {
+                // the largest `upto` of the window: `counted` and every wave's maximum, which the scan left in L.tmp
+                int all = counted;
+#pragma unroll
+                for (int i = 0; i < kWaves; ++i) all = max(all, L.tmp[i]);
+                L.P.template ensure<kWaves>(old, n, nw, m, shift, all, L.tmp);
+            }
             const int car = live ? L.P.prefix(upto) - L.P.prefix(c) : 0;
             const bool brk = live && ((len == car && len != 0) || len > car + 8);
             const uint64_t bal = __ballot(brk);
@@ -257,7 +372,7 @@ __device__ __forceinline__ void anchor_scan_file(Lds &L, const uint8_t *__restri
         if (tid == 0 && emitted < cap) { anch[2 * emitted] = cursor; anch[2 * emitted + 1] = hit_pos; }
         ++emitted;
         shift = (LenT)hit_pos - cursor;
-        if (cursor < m) L.P.template rebuild<kWaves>(old, n, nw, m, shift, L.tmp);
+        if (cursor < m) realign();
     }
     if (tid == 0) {
         *count_out = emitted <= cap ? emitted : -1;
@@ -363,6 +478,34 @@ __global__ __launch_bounds__(kThreads) void anchor_index_many_kernel(
         __syncthreads();
         anchor_scan_file<kThreads / kWave, int64_t, int32_t>(L, old, n, sa, ptab, pk, reinterpret_cast<const uint8_t *>(L.f.new_w), m,
                                                              anchors + 2 * a_at, cap, counts + j, searches + j);
+    });
+}
+
+// The longer new files of an index call: file j of kMidMaxN + 1 .. kMaxM bytes is read where it lies, at
+// news + new_off[j] in device memory -- nothing of it is copied to LDS, which holds P (AgreeMaskLazy) and the loop's few
+// words.  Arguments as anchor_index_many_kernel's, and built[j] = the 64-position steps of P that file j had built.
+// ms_load8 touches whole dwords: up to 3 bytes in front of a file and up to 3 behind the 12 it is promised; `news` begins
+// dword-aligned and has 8 readable bytes behind its last file, so every such byte is a neighbour's or spare, read and
+// masked out, never written.  Launch shape as the other three: resident grid, one workgroup per claimed file, nobody
+// waits for anybody.
+template <int kMaxM, int kThreads>
+__global__ __launch_bounds__(kThreads) void anchor_index_large_kernel(
+    const uint8_t *__restrict__ old, int64_t n, const int32_t *__restrict__ sa, const int32_t *__restrict__ ptab, int pk,
+    const uint8_t *__restrict__ news, const int64_t *__restrict__ new_off, const int64_t *__restrict__ anch_off,
+    const int32_t *__restrict__ order, int count, uint32_t *__restrict__ next, int32_t *__restrict__ anchors,
+    int32_t *__restrict__ counts, int32_t *__restrict__ searches, int32_t *__restrict__ built)
+{
+    static_assert(kMaxM > kMidMaxN, "the class begins where anchor_index_many_kernel's ends");
+    __shared__ AnchorIndexLargeLds<kMaxM, kThreads> L;
+    for_each_claimed(&L.claimed, next, order, count, [&](int j) {
+        const int64_t n_at = new_off[j], a_at = anch_off[j];
+        const int64_t m64 = new_off[j + 1] - n_at;
+        const int cap = (int)(anch_off[j + 1] - a_at);
+        if (threadIdx.x == 0) { L.P.built = 0; built[j] = 0; }
+        if (m64 <= kMidMaxN || m64 > kMaxM) return anchor_refuse_file(counts + j, searches + j);
+        anchor_scan_file<kThreads / kWave, int64_t, int32_t>(L, old, n, sa, ptab, pk, news + n_at, (int)m64, anchors + 2 * a_at, cap,
+                                                             counts + j, searches + j);
+        if (threadIdx.x == 0) built[j] = L.P.built;            // (thread 0 wrote it last, behind ensure's barriers)
     });
 }
 

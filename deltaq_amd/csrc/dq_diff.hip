@@ -1499,7 +1499,7 @@ struct ManyChunk : WorkLists<2> {
     int64_t o_base = 0, o_bytes = 0, n_base = 0, n_bytes = 0, anchors = 0;
     std::vector<int64_t> off;           // [rel_o,] rel_n, rel_a: cnt + 1 entries each
     const int64_t *rel_a = nullptr;
-    std::vector<int32_t> back;          // the anchor lists (list j at 2 * rel_a[j]), then counts and searches per file
+    std::vector<int32_t> back;          // the anchor lists (list j at 2 * rel_a[j]), then counts and searches per file, then `more` further words per file
     uint8_t *d_old = nullptr, *d_new = nullptr;
     int32_t *d_sa = nullptr, *d_order = nullptr, *d_back = nullptr, *d_counts = nullptr, *d_searches = nullptr;
     int64_t *d_off = nullptr;           // `off` as it is: d_noff and d_aoff point into it
@@ -1626,7 +1626,8 @@ int diff_many_finish(const ManyFiles &f, const ManyChunk &k, int dev, std::vecto
     return DQ_OK;
 }
 
-int many_chunk_prepare(ManyChunk &k, const int64_t *ooff, const int64_t *noff, int32_t first, int32_t cnt, DeviceBuf &buf)
+// (more: further int32 words per file that a kernel reports behind `searches`; the large indexed class has one)
+int many_chunk_prepare(ManyChunk &k, const int64_t *ooff, const int64_t *noff, int32_t first, int32_t cnt, DeviceBuf &buf, int more = 0)
 {
     k.cnt = cnt;
     k.n_base = noff[first];
@@ -1644,7 +1645,7 @@ int many_chunk_prepare(ManyChunk &k, const int64_t *ooff, const int64_t *noff, i
     k.anchors = rel_a[cnt];
     auto klass = [&](int32_t j) { return !ooff || std::max(rel_o[j + 1] - rel_o[j], rel_n[j + 1] - rel_n[j]) <= kDiffManyMax ? 0 : 1; };
     build_work_lists(k, cnt, klass, [&](int32_t j) { return rel_n[j + 1] - rel_n[j]; });
-    k.back.resize((size_t)k.anchors * 2 + (size_t)cnt * 2);
+    k.back.resize((size_t)k.anchors * 2 + (size_t)cnt * (2 + (size_t)more));
 
     const size_t b_old = ooff ? align_up((size_t)k.o_bytes + 64) : 0, b_new = align_up((size_t)k.n_bytes + 64),
                  b_sa = ooff ? align_up((size_t)k.o_bytes * sizeof(int32_t) + 64) : 0, b_off = align_up(k.off.size() * sizeof(int64_t)),
@@ -1936,6 +1937,7 @@ int diff_index_diff(const void *index, const uint8_t *nw, int64_t m, std::vector
 //      (dq_anchor_many.h: a workgroup per new file, new in LDS, old and the suffix array read from device
 //      memory); anchor lists, counts and searches back.  The device's diff_mu is held for this phase only.
 //   3. - 5. diff_many_finish, as for the pairs of dq_bsdiff_create_many, every emitter on the index's host copy of old.
+// New files above kIndexManyMax bytes are a class of their own, further down.
 // Device memory per chunk: new + diff_many_anchor_room(m) = m / 8 + 2 pairs of int32 per file for the anchor lists (a byte
 // per byte of new + 16) + 28 bytes per file (two offsets, order, count, searches), freed on return.
 constexpr int64_t kIndexManyMax = kMidMaxN;                // longest new file of the shared launches
@@ -1950,17 +1952,35 @@ constexpr int32_t kIndexManyMin = 32;
 // (docs/ROUNDS.md, round 12, has the figures; DQ_INDEX_MANY_THREADS chooses the other one for a measurement).
 constexpr int kIndexManyThreads = 256;
 
+// ---- the large class: new files of kIndexManyMax + 1 .. kIndexLargeMax bytes, anchor_index_large_kernel (dq_anchor_many.h:
+// the new file stays in device memory, P is built on demand).  Runs are of ONE class: a file of the other class ends a
+// run as an unlisted one does, so every chunk has one launch of one kernel.  A chunk of this class takes up to
+// kIndexLargeChunkBytes of new bytes, so that one chunk can hold as many longest files as the device has CUs (256 x 512
+// KiB); its device memory is twice that plus 48 bytes per file (256 MiB + change at the cap), the host's copy of what
+// comes back the same 128 MiB, and the host phases' memory as for any chunk of that many bytes.
+constexpr int64_t kIndexLargeMax = 512 << 10;
+constexpr int kIndexLargeThreads = 512;
+constexpr int64_t kIndexLargeChunkBytes = 128ll << 20;
+// Fewest neighbouring files of the class that share a launch; a shorter run goes one by one, in input order.  The rule is
+// kIndexManyMin's, on the sweep of tools/kbench/index_diff_large.py (1 .. 512 files of 128 / 256 / 512 KiB, similar and
+// unrelated, old files of 1 and 16 MiB): the largest crossing is 32 files (8 to 32 in every row), twice that is 64.  Every
+// row of every length has its crossing at or below 256 files, so the class reaches up to the longest length swept and is
+// taken by default (kIndexLargeOn; were it false, only DQ_INDEX_LARGE_MIN would switch the class on):
+// profiles/r18/index_diff_large.json, docs/ROUNDS.md round 18.
+constexpr int32_t kIndexLargeMin = 64;
+constexpr bool kIndexLargeOn = true;
+
 namespace {
-// new files [first, first + cnt) of the call, none above kIndexManyMax bytes: their patches into `out`
-int diff_index_many_chunk(const DiffIndex &ix, const uint8_t *news, const int64_t *noff, int32_t first, int32_t cnt, DeviceBuf &buf,
-                          std::vector<ManyPair> &out)
+// New files [first, first + cnt) of the call, all of one class: their patches into `out`.  The chunk's copies, the one
+// launch the class makes -- launch(c, st, L), the only part in which the classes differ -- and the copy back run
+// under the device's diff_mu; *device_us += what that took.  k: the chunk, for what the caller reads from k.back.
+template <typename Launch>
+int diff_index_chunk(const DiffIndex &ix, const uint8_t *news, const int64_t *noff, int32_t first, int32_t cnt, DeviceBuf &buf,
+                     std::vector<ManyPair> &out, ManyChunk &k, int more, int64_t *device_us, Launch launch)
 {
     const int dev = ix.dev;
     HIP_TRY(hipSetDevice(dev));
-    const int threads = flags().index_many_threads.value_or(kIndexManyThreads);
-    if (threads != 256 && threads != 512) return fail(DQ_ERR_BAD_ARGS, "DQ_INDEX_MANY_THREADS is 256 or 512");
-    ManyChunk k;
-    int rc = many_chunk_prepare(k, nullptr, noff, first, cnt, buf);
+    int rc = many_chunk_prepare(k, nullptr, noff, first, cnt, buf, more);
     if (rc != DQ_OK) return rc;
 
     // ---- 2. on the device, scan loops of other callers taking their turns before and after
@@ -1972,10 +1992,35 @@ int diff_index_many_chunk(const DiffIndex &ix, const uint8_t *news, const int64_
         if (rc != DQ_OK) return rc;
         hipStream_t st = c.stream;
         Launcher L{c, st, g_prof_on.load()};
+        auto run = [&]() -> int {
+            int r = many_chunk_upload(k, nullptr, news, st);
+            if (r == DQ_OK) r = launch(c, st, L);
+            if (r != DQ_OK) return r;
+            r = copy_back_and_wait(k.back.data(), k.d_back, k.back.size() * sizeof(int32_t), st);
+            return r != DQ_OK ? r : flush_profile(c);
+        };
+        rc = run();
+        if (rc != DQ_OK) { drop_pending(c, c.stream); return rc; }
+        *device_us += us_since(k.t_device);
+    }
+    // ---- 3. - 5. on the host and in the shared block sort
+    const ManyFiles files{ix.old, nullptr, ix.n, news, noff + first};
+    return diff_many_finish(files, k, dev, out, t_index_many_info, {3, 4, 6, 7, 8});
+}
+
+// ... none above kIndexManyMax bytes: one launch of anchor_index_many_kernel
+int diff_index_many_chunk(const DiffIndex &ix, const uint8_t *news, const int64_t *noff, int32_t first, int32_t cnt, DeviceBuf &buf,
+                          std::vector<ManyPair> &out)
+{
+    const int threads = flags().index_many_threads.value_or(kIndexManyThreads);
+    if (threads != 256 && threads != 512) return fail(DQ_ERR_BAD_ARGS, "DQ_INDEX_MANY_THREADS is 256 or 512");
+    ManyChunk k;
+    return diff_index_chunk(ix, news, noff, first, cnt, buf, out, k, 0, &t_index_many_info[5],
+                            [&](DeviceCtx &c, hipStream_t st, Launcher &L) -> int {
         auto launch = [&](auto width) -> int {
             constexpr int kThreads = decltype(width)::value;
             const int grid = std::min<int>(cnt, resident_groups(&c.anchor_index_many_groups[kThreads == 256 ? 0 : 1],
-                                                                (const void *)anchor_index_many_kernel<kThreads>, kThreads, dev));
+                                                                (const void *)anchor_index_many_kernel<kThreads>, kThreads, ix.dev));
             LAUNCH(L, DQ_K_MATCH_SEARCH, k.n_bytes, k.n_bytes,
                    hipLaunchKernelGGL(anchor_index_many_kernel<kThreads>, dim3((unsigned)grid), dim3(kThreads), 0, st,
                                       reinterpret_cast<const uint8_t *>(ix.d_old), ix.n, reinterpret_cast<const int32_t *>(ix.d_sa),
@@ -1983,21 +2028,36 @@ int diff_index_many_chunk(const DiffIndex &ix, const uint8_t *news, const int64_
                                       k.d_next, k.d_back, k.d_counts, k.d_searches));
             return DQ_OK;
         };
-        auto run = [&]() -> int {
-            int r = many_chunk_upload(k, nullptr, news, st);
-            if (r == DQ_OK) r = threads == 256 ? launch(std::integral_constant<int, 256>{}) : launch(std::integral_constant<int, 512>{});
-            if (r != DQ_OK) return r;
-            t_index_many_info[2] += 1;
-            r = copy_back_and_wait(k.back.data(), k.d_back, k.back.size() * sizeof(int32_t), st);
-            return r != DQ_OK ? r : flush_profile(c);
-        };
-        rc = run();
-        if (rc != DQ_OK) { drop_pending(c, c.stream); return rc; }
-        t_index_many_info[5] += us_since(k.t_device);
-    }
-    // ---- 3. - 5. on the host and in the shared block sort
-    const ManyFiles files{ix.old, nullptr, ix.n, news, noff + first};
-    return diff_many_finish(files, k, dev, out, t_index_many_info, {3, 4, 6, 7, 8});
+        const int r = threads == 256 ? launch(std::integral_constant<int, 256>{}) : launch(std::integral_constant<int, 512>{});
+        if (r == DQ_OK) t_index_many_info[2] += 1;
+        return r;
+    });
+}
+
+// ... all of kIndexManyMax + 1 .. kIndexLargeMax bytes: one launch of anchor_index_large_kernel
+int diff_index_large_chunk(const DiffIndex &ix, const uint8_t *news, const int64_t *noff, int32_t first, int32_t cnt, DeviceBuf &buf,
+                           std::vector<ManyPair> &out)
+{
+    ManyChunk k;
+    int64_t us = 0;
+    const int rc = diff_index_chunk(ix, news, noff, first, cnt, buf, out, k, 1, &us,
+                                    [&](DeviceCtx &c, hipStream_t st, Launcher &L) -> int {
+        const auto kernel = anchor_index_large_kernel<(int)kIndexLargeMax, kIndexLargeThreads>;
+        const int grid = std::min<int>(cnt, resident_groups(&c.anchor_index_large_groups, (const void *)kernel, kIndexLargeThreads, ix.dev));
+        LAUNCH(L, DQ_K_MATCH_SEARCH, k.n_bytes, k.n_bytes,
+               hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(kIndexLargeThreads), 0, st,
+                                  reinterpret_cast<const uint8_t *>(ix.d_old), ix.n, reinterpret_cast<const int32_t *>(ix.d_sa),
+                                  reinterpret_cast<const int32_t *>(ix.d_tab), ix.pk, k.d_new, k.d_noff, k.d_aoff, k.d_order, cnt,
+                                  k.d_next, k.d_back, k.d_counts, k.d_searches, k.d_searches + cnt));
+        t_index_large_info[1] += 1;
+        return DQ_OK;
+    });
+    t_index_many_info[5] += us;                            // (the call's device phase, whichever kernel)
+    t_index_large_info[4] += us;
+    if (rc != DQ_OK) return rc;
+    const int32_t *built = k.back.data() + 2 * k.anchors + 2 * (size_t)cnt;
+    for (int32_t j = 0; j < cnt; ++j) t_index_large_info[3] += 64 * (int64_t)built[j];
+    return DQ_OK;
 }
 }  // namespace
 
@@ -2005,6 +2065,7 @@ int diff_index_many(const void *index, const uint8_t *news, const int64_t *noff,
                     int64_t *plens)
 {
     for (int64_t &x : t_index_many_info) x = 0;
+    for (int64_t &x : t_index_large_info) x = 0;
     if (!index) return fail(DQ_ERR_BAD_ARGS, "null index");
     if (count < 0) return fail(DQ_ERR_BAD_ARGS, "negative count");
     if (count == 0) return DQ_OK;
@@ -2016,7 +2077,13 @@ int diff_index_many(const void *index, const uint8_t *news, const int64_t *noff,
     auto deliver = [&](int32_t j, const std::vector<uint8_t> &patch) { return many_deliver(patch, j, patches, poff, plens); };
     const bool one_by_one = flags().no_index_many.value_or(0) != 0;
     const int64_t many_min = flags().index_many_min.value_or(kIndexManyMin);
-    auto is_listed = [&](int32_t j) { return !one_by_one && noff[j + 1] - noff[j] <= kIndexManyMax; };
+    const bool large_on = !one_by_one && flags().no_index_large.value_or(0) == 0 && (kIndexLargeOn || flags().index_large_min.has_value());
+    const int64_t large_min = flags().index_large_min.value_or(kIndexLargeMin);
+    // the class of a file: 0 short / medium, 1 large, -1 unlisted
+    auto klass = [&](int32_t j) {
+        const int64_t m = noff[j + 1] - noff[j];
+        return one_by_one ? -1 : m <= kIndexManyMax ? 0 : large_on && m <= kIndexLargeMax ? 1 : -1;
+    };
     DeviceBuf buf;
     buf.dev = ix->dev;
     std::vector<ManyPair> done;
@@ -2030,19 +2097,27 @@ int diff_index_many(const void *index, const uint8_t *news, const int64_t *noff,
     };
     auto run = [&](int32_t i, int32_t e) -> int {
         int rc = DQ_OK;
-        if (e - i < many_min) {
+        const bool large = klass(i) == 1;
+        if (e - i < (large ? large_min : many_min)) {
             // too few files for a launch of their own: one by one, in input order
             for (int32_t j = i; j < e && rc == DQ_OK; ++j) rc = single(j);
+            if (large && rc == DQ_OK) t_index_large_info[2] += e - i;
             return rc;
         }
-        rc = diff_index_many_chunk(*ix, news, noff, i, e - i, buf, done);
+        rc = large ? diff_index_large_chunk(*ix, news, noff, i, e - i, buf, done) : diff_index_many_chunk(*ix, news, noff, i, e - i, buf, done);
         if (rc != DQ_OK) return rc;
         t_index_many_info[0] += e - i;
+        if (large) t_index_large_info[0] += e - i;
         for (int32_t j = i; j < e && rc == DQ_OK; ++j) rc = deliver(j, done[(size_t)(j - i)].patch);
         return rc;
     };
-    static_assert(kIndexManyMax <= kDiffManyChunkBytes, "a listed file fits a chunk of its own (walk_runs)");
-    return walk_runs(count, kDiffManyChunkPairs, is_listed, [&](int32_t i, int32_t e) { return noff[e + 1] - noff[i] <= kDiffManyChunkBytes; },
+    static_assert(kIndexManyMax <= kDiffManyChunkBytes && kIndexLargeMax <= kIndexLargeChunkBytes,
+                  "a listed file fits a chunk of its own (walk_runs)");
+    return walk_runs(count, kDiffManyChunkPairs, [&](int32_t j) { return klass(j) >= 0; },
+                     [&](int32_t i, int32_t e) {
+                         const int c = klass(i);
+                         return klass(e) == c && noff[e + 1] - noff[i] <= (c == 1 ? kIndexLargeChunkBytes : kDiffManyChunkBytes);
+                     },
                      single, run);
 }
 

@@ -39,6 +39,8 @@ struct Flags {
     std::optional<int> no_index_many;       // DQ_NO_INDEX_MANY: 1: every new file of dq_bsdiff_index_diff_many through the one-file path
     std::optional<int> index_many_min;      // DQ_INDEX_MANY_MIN: fewest new files of a chunk that share its launch, >= 1
     std::optional<int> index_many_threads;  // DQ_INDEX_MANY_THREADS: 256 | 512, workgroup size of anchor_index_many_kernel
+    std::optional<int> no_index_large;      // DQ_NO_INDEX_LARGE: 1: no large class of its new files (a file above 65 536 bytes: singly, as without the class)
+    std::optional<int> index_large_min;     // DQ_INDEX_LARGE_MIN: fewest neighbouring new files of 65 537 .. 524 288 bytes that share a launch, >= 1; set at all, it also switches the class on where it ships off
     std::optional<int> no_check_many;       // DQ_NO_CHECK_MANY: 1: every text of dq_sufcheck_hip_many_* through the single-text check; 0: every class shares launches however few its texts
     bool no_list_buffers = false;           // DQ_NO_LIST_BUFFERS: the workspace without the third list buffer
     bool text_copy = false;                 // DQ_TEXT_COPY: copy the text in front instead of in the first pass
@@ -141,6 +143,8 @@ inline Flags read_flags()
     f.no_index_many = num("DQ_NO_INDEX_MANY", 0, 1);
     f.index_many_min = num("DQ_INDEX_MANY_MIN", 1);
     f.index_many_threads = num("DQ_INDEX_MANY_THREADS");
+    f.no_index_large = num("DQ_NO_INDEX_LARGE", 0, 1);
+    f.index_large_min = num("DQ_INDEX_LARGE_MIN", 1);
     f.no_check_many = num("DQ_NO_CHECK_MANY", 0, 1);
     f.no_list_buffers = on("DQ_NO_LIST_BUFFERS");
     f.text_copy = on("DQ_TEXT_COPY");

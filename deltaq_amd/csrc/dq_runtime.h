@@ -57,6 +57,9 @@ inline thread_local int64_t t_info[3] = {0, 0, 0};
 inline thread_local int64_t t_diff_info[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
 inline thread_local int64_t t_diff_many_info[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};     // dq_last_diff_many_info
 inline thread_local int64_t t_index_many_info[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};              // dq_last_index_many_info
+// ... and its large class (dq_last_index_large_info): files through large launches, launches of anchor_index_large_kernel,
+// large-class files that went one by one, positions of P built, microseconds in copies + the kernel
+inline thread_local int64_t t_index_large_info[5] = {0, 0, 0, 0, 0};
 // the shared sorts of the last outermost many-texts / batch / many-pairs call on this thread (dq_last_many_info): texts in
 // the short classes' launches, texts in medium launches, medium-length texts sorted singly, texts above kMidMaxN sorted
 // singly, launches of mid_many_kernel, bytes of per-workgroup scratch carved for them, texts sorted in segmented sorts
@@ -136,6 +139,7 @@ struct DeviceCtx {
     int anchor_many_groups = 0;         // ... and of anchor_many_kernel (dq_anchor_many.h)
     int anchor_mid_many_groups = 0;     // ... and of anchor_mid_many_kernel
     int anchor_index_many_groups[2] = {0, 0};   // ... and of anchor_index_many_kernel at 256 and 512 threads (dq_anchor_many.h)
+    int anchor_index_large_groups = 0;  // ... and of anchor_index_large_kernel
     hipStream_t stream = nullptr;
     char *ws = nullptr;
     size_t ws_bytes = 0;

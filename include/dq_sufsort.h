@@ -241,10 +241,18 @@ void dq_bsdiff_index_free(void *index);
  * on a file is not faster than the whole device on it, only many of them side by side are.  A chunk is a run of
  * NEIGHBOURING files of the list: a longer file ends it, so short files share a launch only where 32 or more follow one
  * another (as the pairs of dq_bsdiff_create_many).
- * The call is total: a new file above 65 536 bytes (below 2 GiB) is diffed by dq_bsdiff_index_diff's path, one after
+ * New files of 65 537 .. 524 288 bytes are a class of their own, with launches of their own: a run of NEIGHBOURING files
+ * of this class -- a file of the other class or a longer one ends it -- travels in chunks of at most 128 MiB of new bytes,
+ * and ONE launch of anchor_index_large_kernel finds the anchors of a chunk's files: one workgroup per file again, the new
+ * file left in device memory beside the index, and the per-alignment agreement counts, which the shorter class rebuilds
+ * whole at every control triple, built on demand for the stretch the loop asks about, so that a file's work follows the
+ * bytes its matches cover.  The other phases are the shorter class's.  A run with fewer than 64 such files is taken one
+ * file after another by dq_bsdiff_index_diff's path.  dq_last_index_large_info reports the class.
+ * The call is total: a new file above 524 288 bytes (below 2 GiB) is diffed by dq_bsdiff_index_diff's path, one after
  * another, into its slot.  Patches are delivered in input order whichever way a file went.
  * Footprint per chunk -- device: new + 1 byte per byte of new (anchor lists: m / 8 + 2 pairs of int32 a file) + 44 bytes
- * per file (offsets, work list, counts, searches, the lists' spare pairs), freed on return (the
+ * per file (offsets, work list, counts, searches, the lists' spare pairs; 48 in the large class), freed on return: at
+ * most 128 MiB and a little for a chunk of the shorter class, 256 MiB and a little for one of the large class (the
  * shared sort's own workspace stays with the library until dq_sufsort_hip_release); host: as dq_bsdiff_create_many.
  * Errors found before any device use: a NULL index, count < 0, a NULL pointer with count > 0, offsets[0] != 0 or
  * decreasing offsets in either array -> DQ_ERR_BAD_ARGS; a new file of 2^31 bytes or more -> DQ_ERR_TOO_LARGE.
@@ -415,6 +423,14 @@ int32_t dq_last_diff_many_info(int64_t *info, int32_t count);
  * diffed one by one; launches of anchor_index_many_kernel; bzip2 blocks sorted in shared launches; blocks sorted singly;
  * [5..8] microseconds in each phase: copies + anchor kernel, host emission, block sorts, host framing. */
 int32_t dq_last_index_many_info(int64_t *info, int32_t count);
+
+/* The large class (new files of 65 537 .. 524 288 bytes) of the last dq_bsdiff_index_diff_many on this thread, reset when
+ * such a call starts; `count` entries (5 are defined, further ones read 0; a NULL array is DQ_ERR_BAD_ARGS): [0] files
+ * that went through launches of anchor_index_large_kernel (counted in dq_last_index_many_info's [0] too); [1] those
+ * launches; [2] files of the class diffed one by one because fewer than the threshold followed one another (counted
+ * in its [1] too); [3] positions of P -- the per-alignment agreement counts, built on demand -- that the kernel built,
+ * summed over the files; [4] microseconds in copies + the kernel (part of its [5]). */
+int32_t dq_last_index_large_info(int64_t *info, int32_t count);
 
 /* Shape of the shared sorts of the last outermost dq_sufsort_hip_many_i32 / _many_dev_i32 / dq_sufsort_hip_batch_i32 /
  * dq_bsdiff_create_many / dq_bsdiff_index_diff_many on this thread, summed over every shared sort that call made and reset when such a call
