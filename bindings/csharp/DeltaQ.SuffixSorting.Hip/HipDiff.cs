@@ -42,6 +42,9 @@ internal static unsafe class Native
     internal static extern int dq_last_diff_many_info(long* info, int count);
 
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern int dq_last_diff_large_info(long* info, int count);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
     internal static extern int dq_bspatch_apply(byte* oldData, long n, byte* patch, long patchLen, byte* output, long cap,
                                                 long* outLen);
 
@@ -212,6 +215,23 @@ public static class HipDiff
         fixed (long* p = info)
         {
             Native.Check(Native.dq_last_diff_many_info(p, info.Length), nameof(Native.dq_last_diff_many_info));
+        }
+
+        return info;
+    }
+
+    /// <summary>
+    /// The large class of the last CreateMany on this thread (dq_last_diff_large_info): pairs whose longer file has
+    /// 65 537 to 524 288 bytes through shared launches, those launches, pairs of the class diffed one by one because
+    /// too few followed one another, positions of the agreement counts built on the device, microseconds in copies
+    /// and the kernel, microseconds sorting the old files of large chunks.
+    /// </summary>
+    public static unsafe long[] LastDiffLargeInfo()
+    {
+        var info = new long[6];
+        fixed (long* p = info)
+        {
+            Native.Check(Native.dq_last_diff_large_info(p, info.Length), nameof(Native.dq_last_diff_large_info));
         }
 
         return info;

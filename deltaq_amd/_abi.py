@@ -47,7 +47,7 @@ EXPORTS = (
     "dq_sufcheck_hip_many_i32", "dq_sufcheck_hip_many_dev_i32", "dq_last_check_many_info",
     "dq_bsdiff_search_dev_i32", "dq_bsdiff_search_dev_i64", "dq_bsdiff_search_i32", "dq_bsdiff_search_i64",
     "dq_bsdiff_create", "dq_bsdiff_patch_bound", "dq_bsdiff_scan_i32", "dq_bspatch_apply",
-    "dq_bsdiff_create_many", "dq_last_diff_many_info",
+    "dq_bsdiff_create_many", "dq_last_diff_many_info", "dq_last_diff_large_info",
     "dq_bsdiff_index_create", "dq_bsdiff_index_clone", "dq_bsdiff_index_buffers", "dq_bsdiff_index_diff", "dq_bsdiff_index_free",
     "dq_bsdiff_index_diff_many", "dq_last_index_many_info", "dq_last_index_large_info",
     "dq_sufsort_hip_workspace_bytes", "dq_sufsort_hip_workspace_plan", "dq_sufsort_hip_release",
@@ -161,6 +161,8 @@ def load() -> ctypes.CDLL:
     L.dq_bsdiff_index_diff_many.argtypes = [vp, vp, vp, i32, vp, vp, vp]
     L.dq_last_index_many_info.restype = i32
     L.dq_last_index_many_info.argtypes = [ctypes.POINTER(i64), i32]
+    L.dq_last_diff_large_info.restype = i32
+    L.dq_last_diff_large_info.argtypes = [ctypes.POINTER(i64), i32]
     L.dq_last_index_large_info.restype = i32
     L.dq_last_index_large_info.argtypes = [ctypes.POINTER(i64), i32]
     L.dq_bsdiff_index_diff.restype = i32
@@ -266,6 +268,18 @@ def last_index_many_info() -> dict:
     return {"shared_files": v[0], "single_files": v[1], "anchor_launches": v[2], "shared_block_sorts": v[3],
             "single_block_sorts": v[4], "anchor_ms": v[5] / 1e3, "emit_ms": v[6] / 1e3, "block_sort_ms": v[7] / 1e3,
             "frame_ms": v[8] / 1e3}
+
+
+def last_diff_large_info() -> dict:
+    """The large class (pairs whose longer file has 65 537 .. 524 288 bytes, anchor_pair_large_kernel) of the last
+    dq_bsdiff_create_many on this thread (dq_last_diff_large_info).  large_pairs are counted in
+    last_diff_many_info()["shared_pairs"] too, large_single in its "single_pairs"; anchor_ms and sort_old_ms are parts of
+    its "anchor_ms" and "sort_old_ms"."""
+    L = load()
+    v = (ctypes.c_int64 * 6)()
+    check(L.dq_last_diff_large_info(v, 6))
+    return {"large_pairs": v[0], "large_launches": v[1], "large_single": v[2], "positions_built": v[3], "anchor_ms": v[4] / 1e3,
+            "sort_old_ms": v[5] / 1e3}
 
 
 def last_index_large_info() -> dict:

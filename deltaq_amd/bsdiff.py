@@ -55,7 +55,10 @@ class Diff:
     def CreateMany(olds, news, device: int = -1) -> list:
         """``[Diff.CreateBytes(o, n) for o, n in zip(olds, news)]`` in one call (dq_bsdiff_create_many): pairs whose
         files both have at most 65 536 bytes share their device launches (those with a file above 8192 bytes where a chunk
-        of the call holds at least 16 of them), longer ones are diffed one by one.  The bzip2 blocks of a chunk are
+        of the call holds at least 16 of them); so do pairs whose longer file has 65 537 to 524 288 bytes, in launches of
+        their own kernel, where at least 64 of them follow one another (``_abi.last_diff_large_info()`` reports that
+        class); longer ones, and pairs in shorter runs, are diffed one by one.  Patches come back in input order and are
+        ``Diff.CreateBytes``'s byte for byte whichever way a pair went.  The bzip2 blocks of a chunk are
         sorted together; those of more than 65 536 doubled bytes one after another (the segmented sort of ``SortMany`` is
         off in this call).  ``olds`` /
         ``news``: sequences of bytes-likes or uint8 arrays, of equal length."""

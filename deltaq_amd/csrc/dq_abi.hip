@@ -727,6 +727,13 @@ int32_t dq_last_diff_many_info(int64_t *info, int32_t count)
     return DQ_OK;
 }
 
+int32_t dq_last_diff_large_info(int64_t *info, int32_t count)
+{
+    if (!info || count < 0) return fail(DQ_ERR_BAD_ARGS, "null info array");
+    for (int32_t k = 0; k < count; ++k) info[k] = k < 6 ? t_diff_large_info[k] : 0;
+    return DQ_OK;
+}
+
 int32_t dq_last_many_info(int64_t *info, int32_t count)
 {
     if (!info || count < 0) return fail(DQ_ERR_BAD_ARGS, "bad arguments");

@@ -1,11 +1,12 @@
 // dq_anchor_many.h -- step 1 of the scan loop (Diff.cs:100-125) for MANY files in one launch, one file per workgroup:
 // anchor_many_kernel and anchor_mid_many_kernel for the pairs of dq_bsdiff_create_many, anchor_index_many_kernel for the
-// new files of dq_bsdiff_index_diff_many up to kMidMaxN bytes and anchor_index_large_kernel for its longer ones.  One
-// loop body, anchor_scan_file, instantiated four times.
+// new files of dq_bsdiff_index_diff_many up to kMidMaxN bytes and anchor_index_large_kernel for its longer ones, and
+// anchor_pair_large_kernel for the pairs of dq_bsdiff_create_many with a file above kMidMaxN bytes.  One loop body,
+// anchor_scan_file, instantiated five times.
 //
 // Launch shape.  dq_anchor_scan.h spreads ONE long new file over a persistent multi-grid and pays for it with flags,
 // bounded spins and a host fallback.  A new file of up to kMidMaxN bytes needs none of that: it fits the LDS of one
-// workgroup (of a longer one, in the fourth class, P does), so its whole anchor search runs inside it and the launch
+// workgroup (of a longer one, in the fourth and fifth class, P does), so its whole anchor search runs inside it and the launch
 // takes as many files as the caller has:
 //   * grid and work list as small_many_kernel (dq_small_many.h): as many workgroups as are resident, each claims the
 //     next file of a longest-new-first list with ONE agent-scope relaxed atomic add by thread 0, handed on through LDS
@@ -15,7 +16,8 @@
 // A file outside its class's limits gets counts[j] = -1 and is never copied: nothing is read or written out of the LDS
 // block's bounds.  What a file leaves behind in LDS is harmless to the next one: old and new are only read below n and
 // m (ms_load8's whole dwords beyond them are masked out by the lengths), P is rebuilt for all of [0, m] before its
-// first read (the fourth class: built for every stretch before that stretch's first read).
+// first read (the fourth and fifth class: built for every stretch before that stretch's first read; the fifth's one-byte
+// table is written, behind a barrier, before the pair's first search).
 //
 // Search is ms_search_one (dq_match_search.h): the reference's answer for every position (ties and the zero sentinel
 // slot I[n] = 0 as documented there), found by a lower bound that skips the prefix both interval ends share with the
@@ -33,7 +35,7 @@
 // answers nobody reads.  Only when the head does not break do the lanes take the next positions, one each.  The
 // anchors and the Search count do not depend on the window's width.
 //
-// The four classes (threads = window; LDS bytes; workgroups per CU; the body needs about 190 VGPRs):
+// The five classes (threads = window; LDS bytes; workgroups per CU; the body needs about 190 VGPRs):
 //   * short, anchor_many_kernel: both files of at most kDiffManyMax = 8192 bytes.  256 threads.  LDS holds old, its
 //     suffix array narrowed to 16 bits, new, and P as one uint16 per position (AgreeCounts): 49 240 bytes, three
 //     workgroups per CU.
@@ -67,6 +69,11 @@
 //     kLazyStepsPerWave steps per wave, and the counts are relative to where the built range begins -- the loop only
 //     ever takes differences of P.  The work per file then follows the bytes its matches cover.  The anchors and the
 //     Search count do not depend on the stretch.  (docs/ROUNDS.md, round 18.)
+//   * large pairs, anchor_pair_large_kernel<524 288, 512, table>: a pair of dq_bsdiff_create_many whose longer file has
+//     kMidMaxN + 1 .. 524 288 bytes.  Old, its suffix array and new all stay in device memory; LDS holds P as
+//     AgreeMaskLazy and a one-byte prefix table of the pair's old file, built by the workgroup when it claims the pair
+//     (the comment at the kernel): 99 456 bytes, one workgroup per CU.  n, m and the alignment fit an int.
+//     (docs/ROUNDS.md, round 19.)
 #pragma once
 #include <type_traits>
 
@@ -486,7 +493,7 @@ __global__ __launch_bounds__(kThreads) void anchor_index_many_kernel(
 // words.  Arguments as anchor_index_many_kernel's, and built[j] = the 64-position steps of P that file j had built.
 // ms_load8 touches whole dwords: up to 3 bytes in front of a file and up to 3 behind the 12 it is promised; `news` begins
 // dword-aligned and has 8 readable bytes behind its last file, so every such byte is a neighbour's or spare, read and
-// masked out, never written.  Launch shape as the other three: resident grid, one workgroup per claimed file, nobody
+// masked out, never written.  Launch shape as the first three: resident grid, one workgroup per claimed file, nobody
 // waits for anybody.
 template <int kMaxM, int kThreads>
 __global__ __launch_bounds__(kThreads) void anchor_index_large_kernel(
@@ -505,6 +512,65 @@ __global__ __launch_bounds__(kThreads) void anchor_index_large_kernel(
         if (m64 <= kMidMaxN || m64 > kMaxM) return anchor_refuse_file(counts + j, searches + j);
         anchor_scan_file<kThreads / kWave, int64_t, int32_t>(L, old, n, sa, ptab, pk, news + n_at, (int)m64, anchors + 2 * a_at, cap,
                                                              counts + j, searches + j);
+        if (threadIdx.x == 0) built[j] = L.P.built;            // (thread 0 wrote it last, behind ensure's barriers)
+    });
+}
+
+// The large pairs of dq_bsdiff_create_many: pair j with max(n, m) in kMidMaxN + 1 .. kMaxM, either file as short as 0
+// bytes.  Arguments as anchor_mid_many_kernel's, and built[j] as anchor_index_large_kernel reports it.  BOTH files and
+// the suffix array (sas + old_off[j], where the sort left it) stay in device memory; LDS holds P (AgreeMaskLazy), the
+// loop's few words and, with kTable, the pair's one-byte prefix table.  olds and news begin dword-aligned and have 8
+// readable bytes behind their last file: every byte ms_load8 touches outside a file is a neighbour's or spare, read and
+// masked out, never written.  n and the alignment fit an int (LenT).  Launch shape as the other four: resident grid, one
+// workgroup per claimed pair, nobody waits for anybody.
+//
+// The table.  The index classes start every search from the index's prefix table; a pair has none, and from the whole
+// suffix array a search makes about log2(n) dependent probes.  With kTable a workgroup that claims a pair whose old file
+// has at least kPairTableMinN bytes has its first 257 threads build ptab[v] = number of suffixes of old below the byte v,
+// v = 0 .. 256 (ptab[256] = n), each by the lower bound of prefix_bounds_kernel at pk = 1 (prefix_lower_bound,
+// dq_match_search.h), and the searches start from [ptab[v], ptab[v + 1]) with pk = 1.  The answers are the same by
+// construction: every suffix in that range begins with v (a suffix has at least one byte: ms_trim_short_suffixes removes
+// nothing at pk = 1), and the query's lower bound lies inside the range.  1028 bytes of LDS.
+constexpr int kPairTableMinN = 256;               // (below it a search has at most 8 probes to save)
+struct AnchorByteTable {
+    int32_t ptab[257];
+};
+template <int kMaxM, int kThreads, bool kTable>
+using AnchorPairLargeLds = AnchorLds<std::conditional_t<kTable, AnchorByteTable, AnchorNoFiles>, AgreeMaskLazy<kMaxM>, kThreads / kWave>;
+
+template <int kMaxM, int kThreads, bool kTable>
+__global__ __launch_bounds__(kThreads) void anchor_pair_large_kernel(
+    const uint8_t *__restrict__ olds, const int64_t *__restrict__ old_off, const int32_t *__restrict__ sas,
+    const uint8_t *__restrict__ news, const int64_t *__restrict__ new_off, const int64_t *__restrict__ anch_off,
+    const int32_t *__restrict__ order, int count, uint32_t *__restrict__ next, int32_t *__restrict__ anchors,
+    int32_t *__restrict__ counts, int32_t *__restrict__ searches, int32_t *__restrict__ built)
+{
+    static_assert(kMaxM > kMidMaxN, "the class begins where anchor_mid_many_kernel's ends");
+    static_assert(kThreads >= 257, "one thread per entry of the one-byte table");
+    __shared__ AnchorPairLargeLds<kMaxM, kThreads, kTable> L;
+    for_each_claimed(&L.claimed, next, order, count, [&](int j) {
+        const int64_t o_at = old_off[j], n_at = new_off[j], a_at = anch_off[j];
+        const int64_t n64 = old_off[j + 1] - o_at, m64 = new_off[j + 1] - n_at;
+        const int cap = (int)(anch_off[j + 1] - a_at);
+        if (threadIdx.x == 0) { L.P.built = 0; built[j] = 0; }
+        const int64_t longest = n64 > m64 ? n64 : m64;
+        if (n64 < 0 || m64 < 0 || longest <= kMidMaxN || longest > kMaxM) return anchor_refuse_file(counts + j, searches + j);
+        const int n = (int)n64, m = (int)m64;
+        const uint8_t *old = olds + o_at;
+        const int32_t *sa = sas + o_at;
+        const int32_t *ptab = nullptr;
+        int pk = 0;
+        if constexpr (kTable) {
+            if (n >= kPairTableMinN) {                         // (uniform)
+                const int v = (int)threadIdx.x;
+                if (v <= 256) L.f.ptab[v] = v == 256 ? n : (int32_t)prefix_lower_bound<int32_t>(old, n, sa, 1, v, 0, n);
+                __syncthreads();
+                ptab = L.f.ptab;
+                pk = 1;
+            }
+        }
+        anchor_scan_file<kThreads / kWave, int, int32_t>(L, old, n, sa, ptab, pk, news + n_at, m, anchors + 2 * a_at, cap, counts + j,
+                                                         searches + j);
         if (threadIdx.x == 0) built[j] = L.P.built;            // (thread 0 wrote it last, behind ensure's barriers)
     });
 }

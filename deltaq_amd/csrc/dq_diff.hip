@@ -1397,7 +1397,8 @@ int frame_patch(const bsdiff::RawStreams &raw, int64_t m, int dev, std::vector<u
 //      there; old files above the short-text limit take its medium launches or, below its own threshold, its one-by-one route)
 //   2. the (cursor, hit_pos) list of every pair: anchor_many_kernel on the short pairs -- both files of at most kDiffManyMax
 //      bytes -- and anchor_mid_many_kernel on the medium ones (dq_anchor_many.h has both); the two
-//      launches go back to back on one stream, each with its own work list and counter; lists to the host
+//      launches go back to back on one stream, each with its own work list and counter; lists to the host.  (A chunk of
+//      the large class, further down, has ONE launch of anchor_pair_large_kernel here instead.)
 //   3. host threads: TripleEmitter + scan_from_anchors per pair -> RawStreams; run-length pre-pass and CRC of the three
 //      streams (bz2::StreamEncoder with its blocks held back)
 //   4. all blocks of all streams of the chunk, doubled and laid back to back: ONE sufsort_many_host call (blocks whose
@@ -1418,6 +1419,30 @@ constexpr int32_t kDiffManyChunkPairs = 1 << 18;
 // twice the largest crossing.  (At least 8 whatever a sweep says: a handful of larger files among short ones keeps the
 // path it had.)
 constexpr int32_t kDiffMidManyMin = 16;
+
+// ---- the large class: pairs whose longer file has kMidMaxN + 1 .. kDiffLargeMax bytes, anchor_pair_large_kernel
+// (dq_anchor_many.h: both files and the suffix array stay in device memory, P is built on demand, the searches start from
+// a one-byte table the workgroup builds).  Runs are of ONE class, as in dq_bsdiff_index_diff_many: a pair of the other
+// class ends a run as an unlisted one does, so a chunk of this class has the one launch of that kernel.  It takes up to
+// kDiffLargeChunkBytes of old + new bytes, so that one chunk can hold as many pairs of two longest files as the device
+// has CUs (256 x 2 x 512 KiB); device memory per byte as for the other chunks (< 6 bytes per byte of text: 1.5 GiB at
+// the cap), and 4 bytes more per pair.
+constexpr int64_t kDiffLargeMax = 512 << 10;
+constexpr int kDiffLargeThreads = 512;
+constexpr int64_t kDiffLargeChunkBytes = 256ll << 20;
+// Fewest neighbouring pairs of the class that share a launch; a shorter run goes one by one, in input order.  The rule
+// is kIndexLargeMin's, on the sweep of tools/kbench/diff_many_large.py (1 .. 512 pairs of 128 / 256 / 512 KiB per file,
+// similar and unrelated): the largest crossing is 32 pairs (8 to 32 in every row), twice that is 64.  Every row of every
+// length has its crossing at or below 256 pairs, so the class reaches up to the longest length swept; and on every set
+// of the tool's `compare` this build's median lies below the parent's fastest run (3.1x .. 5.4x), so the class is
+// taken by default (kDiffLargeOn; were it false, only DQ_DIFF_LARGE_MIN would switch the class on):
+// profiles/r19/diff_many_large.json, docs/ROUNDS.md round 19.
+constexpr int32_t kDiffLargeMin = 64;
+constexpr bool kDiffLargeOn = true;
+// anchor_pair_large_kernel with its one-byte table per pair (DQ_DIFF_LARGE_TABLE=0 takes the instantiation without it
+// for a measurement): copies + kernel summed over the 60 cells of that sweep, 1.21 s with the table, 1.42 s without --
+// unrelated files, where every position is searched, gain a fifth to a quarter, similar ones nothing.
+constexpr bool kDiffLargeTable = true;
 
 // anchors a pair of `m` new bytes can emit: every triple but the last stands on a match of more than 8 bytes
 // (hit_len > carried + 8, carried >= 0) and the scan goes on behind it, so there are at most m / 9 + 1
@@ -1679,13 +1704,17 @@ int many_chunk_upload(const ManyChunk &k, const uint8_t *olds, const uint8_t *ne
     return DQ_OK;
 }
 
-// pairs [first, first + cnt) of the call, no file above kMidMaxN bytes: their patches into `out`
-int diff_many_chunk(const uint8_t *olds, const int64_t *ooff, const uint8_t *news, const int64_t *noff, int32_t first, int32_t cnt,
-                    int dev, DeviceBuf &buf, std::vector<ManyPair> &out)
+// Pairs [first, first + cnt) of the call, all on the work lists of ONE kind of chunk: their patches into `out`.  Phases 1 - 5
+// as listed above; launch(c, st, L) makes phase 2's launches, the only part in which the kinds of chunk differ.
+// *sort_us += what sorting the old files took, *device_us += the copies and the launches.  k: the chunk, for what the
+// caller reads from k.back; more: as many_chunk_prepare's.
+template <typename Launch>
+int diff_pairs_chunk(const uint8_t *olds, const int64_t *ooff, const uint8_t *news, const int64_t *noff, int32_t first, int32_t cnt,
+                     int dev, DeviceBuf &buf, std::vector<ManyPair> &out, ManyChunk &k, int more, int64_t *sort_us, int64_t *device_us,
+                     Launch launch)
 {
     HIP_TRY(hipSetDevice(dev));                            // (the chunk's allocation below is this device's)
-    ManyChunk k;
-    int rc = many_chunk_prepare(k, ooff, noff, first, cnt, buf);
+    int rc = many_chunk_prepare(k, ooff, noff, first, cnt, buf, more);
     if (rc != DQ_OK) return rc;
 
     // ---- 1. + 2. on the device.  (A device context is leased for the copies and again for the kernel, never across the
@@ -1696,7 +1725,7 @@ int diff_many_chunk(const uint8_t *olds, const int64_t *ooff, const uint8_t *new
             const int r = many_chunk_upload(k, olds, news, st);
             if (r != DQ_OK) return r;
             HIP_TRY(hipStreamSynchronize(st));
-            t_diff_many_info[6] += us_since(t0);
+            *device_us += us_since(t0);
             return DQ_OK;
         };
         auto sort_olds = [&]() -> int {
@@ -1705,32 +1734,17 @@ int diff_many_chunk(const uint8_t *olds, const int64_t *ooff, const uint8_t *new
             if (r != DQ_OK) return r;
             HIP_TRY(hipSetDevice(dev));
             HIP_TRY(hipDeviceSynchronize());               // (whichever streams its routes used)
-            t_diff_many_info[5] += us_since(t0);
+            *sort_us += us_since(t0);
             return DQ_OK;
         };
         auto scan = [&](DeviceCtx &c, hipStream_t st) -> int {
             const auto t0 = std::chrono::steady_clock::now();
             Launcher L{c, st, g_prof_on.load()};
-            // (a class's share of the bytes is not known here: the profile books all of them on the first launch)
-            int64_t prof_units = k.n_bytes, prof_bytes = k.o_bytes * 5 + k.n_bytes;
-            // the short pairs' launch claims from word 0 of the counter line, the medium pairs' from word 16
-            int r = for_each_class(k.class_count, k.d_order, k.d_next, 16, [&](int cls, int pairs, const int32_t *order, uint32_t *claim) -> int {
-                const auto kernel = cls == 0 ? anchor_many_kernel : anchor_mid_many_kernel;
-                const int threads = cls == 0 ? kAmThreads : kAmMidThreads;
-                const int grid = std::min(pairs, resident_groups(cls == 0 ? &c.anchor_many_groups : &c.anchor_mid_many_groups,
-                                                                 (const void *)kernel, threads, dev));
-                LAUNCH(L, DQ_K_MATCH_SEARCH, prof_units, prof_bytes,
-                       hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3((unsigned)threads), 0, st, k.d_old, k.d_off, k.d_sa, k.d_new,
-                                          k.d_noff, k.d_aoff, order, pairs, claim, k.d_back, k.d_counts, k.d_searches));
-                prof_units = prof_bytes = 0;
-                t_diff_many_info[cls == 0 ? 2 : 11] += 1;
-                return DQ_OK;
-            });
+            int r = launch(c, st, L);
             if (r != DQ_OK) return r;
-            t_diff_many_info[10] += k.class_count[1];
             r = copy_back_and_wait(k.back.data(), k.d_back, k.back.size() * sizeof(int32_t), st);
             if (r != DQ_OK) return r;
-            t_diff_many_info[6] += us_since(t0);
+            *device_us += us_since(t0);
             return flush_profile(c);
         };
         auto leased = [&](auto &&step) -> int {
@@ -1750,6 +1764,69 @@ int diff_many_chunk(const uint8_t *olds, const int64_t *ooff, const uint8_t *new
     // ---- 3. - 5. on the host and in the shared block sort
     const ManyFiles files{olds, ooff + first, 0, news, noff + first};
     return diff_many_finish(files, k, dev, out, t_diff_many_info, {3, 4, 7, 8, 9});
+}
+
+// ... no file above kMidMaxN bytes: one launch of anchor_many_kernel and one of anchor_mid_many_kernel, as the chunk has pairs for them
+int diff_many_chunk(const uint8_t *olds, const int64_t *ooff, const uint8_t *news, const int64_t *noff, int32_t first, int32_t cnt,
+                    int dev, DeviceBuf &buf, std::vector<ManyPair> &out)
+{
+    ManyChunk k;
+    return diff_pairs_chunk(olds, ooff, news, noff, first, cnt, dev, buf, out, k, 0, &t_diff_many_info[5], &t_diff_many_info[6],
+                            [&](DeviceCtx &c, hipStream_t st, Launcher &L) -> int {
+        // (a class's share of the bytes is not known here: the profile books all of them on the first launch)
+        int64_t prof_units = k.n_bytes, prof_bytes = k.o_bytes * 5 + k.n_bytes;
+        // the short pairs' launch claims from word 0 of the counter line, the medium pairs' from word 16
+        const int r = for_each_class(k.class_count, k.d_order, k.d_next, 16, [&](int cls, int pairs, const int32_t *order, uint32_t *claim) -> int {
+            const auto kernel = cls == 0 ? anchor_many_kernel : anchor_mid_many_kernel;
+            const int threads = cls == 0 ? kAmThreads : kAmMidThreads;
+            const int grid = std::min(pairs, resident_groups(cls == 0 ? &c.anchor_many_groups : &c.anchor_mid_many_groups,
+                                                             (const void *)kernel, threads, dev));
+            LAUNCH(L, DQ_K_MATCH_SEARCH, prof_units, prof_bytes,
+                   hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3((unsigned)threads), 0, st, k.d_old, k.d_off, k.d_sa, k.d_new,
+                                      k.d_noff, k.d_aoff, order, pairs, claim, k.d_back, k.d_counts, k.d_searches));
+            prof_units = prof_bytes = 0;
+            t_diff_many_info[cls == 0 ? 2 : 11] += 1;
+            return DQ_OK;
+        });
+        if (r == DQ_OK) t_diff_many_info[10] += k.class_count[1];
+        return r;
+    });
+}
+
+// ... every pair's longer file of kMidMaxN + 1 .. kDiffLargeMax bytes: one launch of anchor_pair_large_kernel (every pair
+// is on the chunk's second work list: many_chunk_prepare knows two kinds of pair, and none of these is short)
+int diff_large_chunk(const uint8_t *olds, const int64_t *ooff, const uint8_t *news, const int64_t *noff, int32_t first, int32_t cnt,
+                     int dev, DeviceBuf &buf, std::vector<ManyPair> &out)
+{
+    const bool table = flags().diff_large_table.value_or(kDiffLargeTable ? 1 : 0) != 0;
+    ManyChunk k;
+    int64_t sort_us = 0, device_us = 0;
+    const int rc = diff_pairs_chunk(olds, ooff, news, noff, first, cnt, dev, buf, out, k, 1, &sort_us, &device_us,
+                                    [&](DeviceCtx &c, hipStream_t st, Launcher &L) -> int {
+        if (k.class_count[0] != 0 || k.class_count[1] != cnt) return fail(DQ_ERR_HIP, "a large chunk holds a short pair");
+        auto launch = [&](auto with_table) -> int {
+            constexpr bool kTable = decltype(with_table)::value;
+            const auto kernel = anchor_pair_large_kernel<(int)kDiffLargeMax, kDiffLargeThreads, kTable>;
+            const int grid = std::min<int>(cnt, resident_groups(&c.anchor_pair_large_groups[kTable ? 1 : 0], (const void *)kernel,
+                                                                kDiffLargeThreads, dev));
+            LAUNCH(L, DQ_K_MATCH_SEARCH, k.n_bytes, k.o_bytes * 5 + k.n_bytes,
+                   hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(kDiffLargeThreads), 0, st, k.d_old, k.d_off, k.d_sa, k.d_new,
+                                      k.d_noff, k.d_aoff, k.d_order, cnt, k.d_next, k.d_back, k.d_counts, k.d_searches,
+                                      k.d_searches + cnt));
+            return DQ_OK;
+        };
+        const int r = table ? launch(std::true_type{}) : launch(std::false_type{});
+        if (r == DQ_OK) t_diff_large_info[1] += 1;
+        return r;
+    });
+    t_diff_many_info[5] += sort_us;                        // (the call's phases, whichever kernel)
+    t_diff_many_info[6] += device_us;
+    t_diff_large_info[4] += device_us;
+    t_diff_large_info[5] += sort_us;
+    if (rc != DQ_OK) return rc;
+    const int32_t *built = k.back.data() + 2 * k.anchors + 2 * (size_t)cnt;
+    for (int32_t j = 0; j < cnt; ++j) t_diff_large_info[3] += 64 * (int64_t)built[j];
+    return DQ_OK;
 }
 
 // The checks both many-file calls make on their offset arrays (ooff null: the call has no old files), in this order;
@@ -1781,6 +1858,7 @@ int bsdiff_create_many_host(const uint8_t *olds, const int64_t *ooff, const uint
                             uint8_t *patches, const int64_t *poff, int64_t *plens, int32_t device)
 {
     for (int64_t &x : t_diff_many_info) x = 0;
+    for (int64_t &x : t_diff_large_info) x = 0;
     if (count < 0) return fail(DQ_ERR_BAD_ARGS, "negative count");
     if (count == 0) return DQ_OK;
     if (!olds || !ooff || !news || !noff || !patches || !poff || !plens) return fail(DQ_ERR_BAD_ARGS, "null buffer");
@@ -1794,9 +1872,15 @@ int bsdiff_create_many_host(const uint8_t *olds, const int64_t *ooff, const uint
     const bool one_by_one = flags().no_diff_many.value_or(0) != 0;
     const int64_t listed_max = flags().no_diff_mid_many.value_or(0) != 0 ? kDiffManyMax : kMidMaxN;
     const int64_t mid_min = flags().diff_mid_many_min.value_or(kDiffMidManyMin);
+    const bool large_on = !one_by_one && flags().no_diff_large.value_or(0) == 0 && (kDiffLargeOn || flags().diff_large_min.has_value());
+    const int64_t large_min = flags().diff_large_min.value_or(kDiffLargeMin);
     auto longest = [&](int32_t j) { return std::max(ooff[j + 1] - ooff[j], noff[j + 1] - noff[j]); };
     auto is_short = [&](int32_t j) { return !one_by_one && longest(j) <= kDiffManyMax; };
-    auto is_listed = [&](int32_t j) { return !one_by_one && longest(j) <= listed_max; };
+    // the class of a pair: 0 both files at most kMidMaxN bytes (where the medium class is off: kDiffManyMax), 1 large, -1 unlisted
+    auto klass = [&](int32_t j) {
+        const int64_t len = longest(j);
+        return one_by_one ? -1 : len <= listed_max ? 0 : large_on && len > kMidMaxN && len <= kDiffLargeMax ? 1 : -1;
+    };
     DeviceBuf buf;
     buf.dev = dev;
     std::vector<ManyPair> done;
@@ -1808,24 +1892,40 @@ int bsdiff_create_many_host(const uint8_t *olds, const int64_t *ooff, const uint
         if (r == DQ_OK) t_diff_many_info[1] += 1;
         return r;
     };
-    auto chunk = [&](int32_t a, int32_t b) -> int {
-        int r = diff_many_chunk(olds, ooff, news, noff, a, b - a, dev, buf, done);
+    auto chunk = [&](int32_t a, int32_t b, bool large) -> int {
+        int r = large ? diff_large_chunk(olds, ooff, news, noff, a, b - a, dev, buf, done)
+                      : diff_many_chunk(olds, ooff, news, noff, a, b - a, dev, buf, done);
         if (r != DQ_OK) return r;
         t_diff_many_info[0] += b - a;
+        if (large) t_diff_large_info[0] += b - a;
         for (int32_t j = a; j < b && r == DQ_OK; ++j) r = deliver(j, done[(size_t)(j - a)].patch);
         return r;
     };
     auto run = [&](int32_t i, int32_t e) -> int {
+        if (klass(i) == 1) {
+            if (e - i >= large_min) return chunk(i, e, true);
+            // too few pairs for a launch of their own: one by one, in input order
+            int rc = DQ_OK;
+            for (int32_t j = i; j < e && rc == DQ_OK; ++j) rc = single(j);
+            if (rc == DQ_OK) t_diff_large_info[2] += e - i;
+            return rc;
+        }
         int64_t mids = 0;
         for (int32_t j = i; j < e; ++j) mids += !is_short(j);
-        if (mids == 0 || mids >= mid_min) return chunk(i, e);
+        if (mids == 0 || mids >= mid_min) return chunk(i, e, false);
         // too few medium pairs for launches of their own: the run as without the class, in input order
         return walk_runs(e - i, e - i, [&](int32_t j) { return is_short(i + j); }, [](int32_t, int32_t) { return true; },
-                         [&](int32_t j) { return single(i + j); }, [&](int32_t a, int32_t b) { return chunk(i + a, i + b); });
+                         [&](int32_t j) { return single(i + j); }, [&](int32_t a, int32_t b) { return chunk(i + a, i + b, false); });
     };
-    static_assert(2 * kMidMaxN <= kDiffManyChunkBytes, "a listed pair fits a chunk of its own (walk_runs)");
-    return walk_runs(count, kDiffManyChunkPairs, is_listed,
-                     [&](int32_t i, int32_t e) { return (ooff[e + 1] - ooff[i]) + (noff[e + 1] - noff[i]) <= kDiffManyChunkBytes; }, single, run);
+    static_assert(2 * kMidMaxN <= kDiffManyChunkBytes && 2 * kDiffLargeMax <= kDiffLargeChunkBytes,
+                  "a listed pair fits a chunk of its own (walk_runs)");
+    return walk_runs(count, kDiffManyChunkPairs, [&](int32_t j) { return klass(j) >= 0; },
+                     [&](int32_t i, int32_t e) {
+                         const int c = klass(i);
+                         return klass(e) == c &&
+                                (ooff[e + 1] - ooff[i]) + (noff[e + 1] - noff[i]) <= (c == 1 ? kDiffLargeChunkBytes : kDiffManyChunkBytes);
+                     },
+                     single, run);
 }
 
 int bsdiff_create_host(const uint8_t *old, int64_t n, const uint8_t *nw, int64_t m, int32_t device, std::vector<uint8_t> &patch)

@@ -36,6 +36,9 @@ struct Flags {
     std::optional<int> no_diff_many;        // DQ_NO_DIFF_MANY: 1: every pair of dq_bsdiff_create_many through the one-pair path
     std::optional<int> no_diff_mid_many;    // DQ_NO_DIFF_MID_MANY: 1: no medium class of its pairs (a file above 8192 bytes: singly)
     std::optional<int> diff_mid_many_min;   // DQ_DIFF_MID_MANY_MIN: fewest medium pairs of a chunk that share its launches, >= 1
+    std::optional<int> no_diff_large;       // DQ_NO_DIFF_LARGE: 1: no large class of its pairs (a file above 65 536 bytes: singly, as without the class)
+    std::optional<int> diff_large_min;      // DQ_DIFF_LARGE_MIN: fewest neighbouring pairs with a longer file of 65 537 .. 524 288 bytes that share a launch, >= 1; set at all, it also switches the class on where it ships off
+    std::optional<int> diff_large_table;    // DQ_DIFF_LARGE_TABLE: 0 | 1, anchor_pair_large_kernel without or with the one-byte prefix table per pair
     std::optional<int> no_index_many;       // DQ_NO_INDEX_MANY: 1: every new file of dq_bsdiff_index_diff_many through the one-file path
     std::optional<int> index_many_min;      // DQ_INDEX_MANY_MIN: fewest new files of a chunk that share its launch, >= 1
     std::optional<int> index_many_threads;  // DQ_INDEX_MANY_THREADS: 256 | 512, workgroup size of anchor_index_many_kernel
@@ -140,6 +143,9 @@ inline Flags read_flags()
     f.no_diff_many = num("DQ_NO_DIFF_MANY", 0, 1);
     f.no_diff_mid_many = num("DQ_NO_DIFF_MID_MANY", 0, 1);
     f.diff_mid_many_min = num("DQ_DIFF_MID_MANY_MIN", 1);
+    f.no_diff_large = num("DQ_NO_DIFF_LARGE", 0, 1);
+    f.diff_large_min = num("DQ_DIFF_LARGE_MIN", 1);
+    f.diff_large_table = num("DQ_DIFF_LARGE_TABLE", 0, 1);
     f.no_index_many = num("DQ_NO_INDEX_MANY", 0, 1);
     f.index_many_min = num("DQ_INDEX_MANY_MIN", 1);
     f.index_many_threads = num("DQ_INDEX_MANY_THREADS");

@@ -139,6 +139,25 @@ __device__ __forceinline__ void ms_trim_short_suffixes(const IdxT *__restrict__ 
 // coarse: the table of pk - 1 bytes, if it has been built: the bound of v lies inside [coarse[v >> 8], coarse[(v >> 8) + 1]]
 // (the suffixes below the shorter pattern are below every pattern it begins, those below v are below the next shorter
 // pattern) -- 8 probes instead of log2(n): the 3-byte table of a 16 MiB file 0.84 -> 0.3 ms, a twelfth of a Diff.Create.
+// (prefix_lower_bound is one entry of the table: the kernel below and the one-byte table a workgroup of
+// anchor_pair_large_kernel builds in LDS, dq_anchor_many.h, share it)
+template <typename IdxT>
+__device__ __forceinline__ int64_t prefix_lower_bound(const uint8_t *__restrict__ old, int64_t n, const IdxT *__restrict__ sa, int pk,
+                                                      int64_t v, int64_t L, int64_t R)
+{
+    while (L < R) {
+        const int64_t mid = L + ((R - L) >> 1);
+        const int64_t p = (int64_t)sa[mid], la = n - p;
+        bool less = la < pk;                               // all compared bytes equal: the shorter (a proper prefix) first
+        for (int j = 0; j < pk && j < la; ++j) {
+            const int a = old[p + j], b = (int)((v >> (8 * (pk - 1 - j))) & 0xff);
+            if (a != b) { less = a < b; break; }
+        }
+        if (less) L = mid + 1; else R = mid;
+    }
+    return L;
+}
+
 template <typename IdxT>
 __global__ __launch_bounds__(kBlock) void prefix_bounds_kernel(const uint8_t *__restrict__ old, int64_t n,
                                                                const IdxT *__restrict__ sa, int pk, IdxT *__restrict__ ptab,
@@ -150,17 +169,7 @@ __global__ __launch_bounds__(kBlock) void prefix_bounds_kernel(const uint8_t *__
     if (v == total) { ptab[v] = (IdxT)n; return; }
     int64_t L = 0, R = n;
     if (coarse) { L = (int64_t)coarse[v >> 8]; R = (int64_t)coarse[(v >> 8) + 1]; }
-    while (L < R) {
-        const int64_t mid = L + ((R - L) >> 1);
-        const int64_t p = (int64_t)sa[mid], la = n - p;
-        bool less = la < pk;                               // all compared bytes equal: the shorter (a proper prefix) first
-        for (int j = 0; j < pk && j < la; ++j) {
-            const int a = old[p + j], b = (int)((v >> (8 * (pk - 1 - j))) & 0xff);
-            if (a != b) { less = a < b; break; }
-        }
-        if (less) L = mid + 1; else R = mid;
-    }
-    ptab[v] = (IdxT)L;
+    ptab[v] = (IdxT)prefix_lower_bound<IdxT>(old, n, sa, pk, v, L, R);
 }
 
 // One query per lane: Search(I, old, nw[scan..], 0, n).  Called by whole waves (the wave-wide comparison needs

@@ -56,6 +56,10 @@ inline thread_local int64_t t_info[3] = {0, 0, 0};
 // asked again exactly, launches of the device's anchor scan that were given back to the host loop, workgroups of its grid
 inline thread_local int64_t t_diff_info[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
 inline thread_local int64_t t_diff_many_info[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};     // dq_last_diff_many_info
+// ... and its large class (dq_last_diff_large_info): pairs through large launches, launches of anchor_pair_large_kernel,
+// large-class pairs that went one by one, positions of P built, microseconds in copies + the kernel, microseconds sorting
+// the old files of large chunks
+inline thread_local int64_t t_diff_large_info[6] = {0, 0, 0, 0, 0, 0};
 inline thread_local int64_t t_index_many_info[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};              // dq_last_index_many_info
 // ... and its large class (dq_last_index_large_info): files through large launches, launches of anchor_index_large_kernel,
 // large-class files that went one by one, positions of P built, microseconds in copies + the kernel
@@ -140,6 +144,7 @@ struct DeviceCtx {
     int anchor_mid_many_groups = 0;     // ... and of anchor_mid_many_kernel
     int anchor_index_many_groups[2] = {0, 0};   // ... and of anchor_index_many_kernel at 256 and 512 threads (dq_anchor_many.h)
     int anchor_index_large_groups = 0;  // ... and of anchor_index_large_kernel
+    int anchor_pair_large_groups[2] = {0, 0};   // ... and of anchor_pair_large_kernel without and with its one-byte table
     hipStream_t stream = nullptr;
     char *ws = nullptr;
     size_t ws_bytes = 0;

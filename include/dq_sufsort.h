@@ -160,7 +160,7 @@ int32_t dq_bsdiff_create(const uint8_t *old_data, int64_t n, const uint8_t *new_
                          int64_t cap, int64_t *patch_len, int32_t device);
 int64_t dq_bsdiff_patch_bound(int64_t n, int64_t m);
 
-/* ---- many SHORT and MEDIUM file pairs in shared launches (two directory trees of small files) -------------------
+/* ---- many SHORT, MEDIUM and LARGE file pairs in shared launches (two directory trees of files up to 512 KiB) -------
  * dq_bsdiff_create_many: `count` independent (old, new) pairs in one call.  Layout as dq_sufsort_hip_many_i32: the old
  * files back to back in `olds`, the new files in `news`, each with an offsets array of count + 1 int64 entries
  * (offsets[0] == 0, never decreasing); pair j is olds[old_offsets[j] .. old_offsets[j + 1]) against
@@ -180,9 +180,19 @@ int64_t dq_bsdiff_patch_bound(int64_t n, int64_t m);
  * A chunk with fewer than 16 medium pairs is taken as if there were no medium class: those pairs one after another by
  * dq_bsdiff_create's path, the short runs between them in chunks of their own -- one workgroup on a medium pair is not
  * faster than the whole device on it, only many of them side by side are.
- * The call is total: a pair with a file above 65 536 bytes (below 2 GiB) is diffed by dq_bsdiff_create's path, one
+ * Pairs whose longer file has 65 537 .. 524 288 bytes (the other file of any length down to 0) are a class of their own,
+ * LARGE, with launches of their own: a run of NEIGHBOURING pairs of this class -- a pair of the other classes or a
+ * longer one ends it -- travels in chunks of at most 256 MiB of old + new, and ONE launch of anchor_pair_large_kernel
+ * finds the anchors of a chunk's pairs: one workgroup per pair again, both files and the suffix array left in device
+ * memory, the per-alignment agreement counts built on demand as in dq_bsdiff_index_diff_many's large class, and every
+ * search started from a one-byte prefix table of the pair's old file that the workgroup builds in LDS.  The other phases
+ * are the shorter classes'; the old files of such a chunk are still sorted one after another.  A run with
+ * fewer than 64 such pairs is taken one pair after another by dq_bsdiff_create's path.  dq_last_diff_large_info reports
+ * the class.
+ * The call is total: a pair with a file above 524 288 bytes (below 2 GiB) is diffed by dq_bsdiff_create's path, one
  * after another, into its slot.  Patches are delivered in input order whichever way a pair went.
- * Footprint per chunk -- device: old + new + 4 bytes per byte of old + 1 byte per byte of new + 40 bytes per pair, the
+ * Footprint per chunk -- device: old + new + 4 bytes per byte of old + 1 byte per byte of new + 40 bytes per pair (44 in
+ * the large class: below 1.5 GiB + change for its longest chunk), the
  * same for every class (the medium anchor kernel has no scratch blocks), freed
  * on return (the shared sort's own workspace, scratch blocks of medium launches included, stays with the library until
  * dq_sufsort_hip_release); host: below 4 bytes per byte of new for the raw streams and 10 bytes per byte of stream for the shared sort.
@@ -417,6 +427,15 @@ int32_t dq_last_diff_info(int64_t *info, int32_t count);
  * host emission, block sorts, host framing; [10] pairs with a file above 8192 bytes that went through the medium anchor
  * launches (counted in [0] too); [11] launches of anchor_mid_many_kernel. */
 int32_t dq_last_diff_many_info(int64_t *info, int32_t count);
+
+/* The large class (pairs whose longer file has 65 537 .. 524 288 bytes) of the last dq_bsdiff_create_many on this thread,
+ * reset when such a call starts; `count` entries (6 are defined, further ones read 0; a NULL array is DQ_ERR_BAD_ARGS):
+ * [0] pairs that went through launches of anchor_pair_large_kernel (counted in dq_last_diff_many_info's [0] too); [1]
+ * those launches; [2] pairs of the class diffed one by one because fewer than the threshold followed one another
+ * (counted in its [1] too); [3] positions of P -- the per-alignment agreement counts, built on demand -- that the kernel
+ * built, summed over the pairs; [4] microseconds in copies + the kernel (part of its [6]); [5] microseconds sorting the
+ * old files of large chunks (part of its [5]). */
+int32_t dq_last_diff_large_info(int64_t *info, int32_t count);
 
 /* Shape of the last dq_bsdiff_index_diff_many on this thread, reset when such a call starts; `count` entries (9 are
  * defined, further ones read 0; a NULL array is DQ_ERR_BAD_ARGS): new files that went through shared launches; files
