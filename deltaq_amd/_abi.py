@@ -57,6 +57,36 @@ EXPORTS = (
 )
 
 
+def _n(*keys) -> tuple:
+    return tuple((key, 1) for key in keys)
+
+
+def _ms(*keys) -> tuple:
+    return tuple((key, 1e-3) for key in keys)
+
+
+# The dq_last_*_info records: export -> the (key, scale) of every ABI entry, in ABI order.  The keys are the field names of
+# deltaq_amd/csrc/dq_call_info.h, which has their meanings; scale 1e-3 (_ms): the field there holds microseconds and is
+# named ..._us, the key here reports milliseconds and is named ..._ms (tests/test_abi_cpu.py compares the two files).
+RECORDS = {
+    "dq_last_sort_info": _n("rounds", "initial_active", "sum_active"),
+    "dq_last_diff_info": _n("searches", "windows", "exact", "host_loop_fallbacks", "scan_groups", "chains_launched",
+                            "chains_joined", "chains_dropped", "triples_from_chain_emitters"),
+    "dq_last_diff_many_info": _n("shared_pairs", "single_pairs", "anchor_launches", "shared_block_sorts", "single_block_sorts")
+    + _ms("sort_old_ms", "anchor_ms", "emit_ms", "block_sort_ms", "frame_ms") + _n("medium_pairs", "medium_anchor_launches"),
+    "dq_last_diff_large_info": _n("large_pairs", "large_launches", "large_single", "positions_built")
+    + _ms("anchor_ms", "sort_old_ms"),
+    "dq_last_index_many_info": _n("shared_files", "single_files", "anchor_launches", "shared_block_sorts", "single_block_sorts")
+    + _ms("anchor_ms", "emit_ms", "block_sort_ms", "frame_ms"),
+    "dq_last_index_large_info": _n("large_files", "large_launches", "large_single", "positions_built") + _ms("anchor_ms"),
+    "dq_last_many_info": _n("short_texts", "medium_texts", "medium_single", "long_single", "medium_launches", "scratch_bytes",
+                            "large_texts", "segmented_sorts", "list_entries"),
+    "dq_last_check_many_info": _n("shared_texts", "single_texts", "launches", "chunks", "stream_waits"),
+    "dq_last_batch_info": _n("pipelined") + _ms("copy_in_ms", "sort_ms", "copy_out_ms", "slowest_share_ms")
+    + _n("shares_bound_to_numa_node", "shared_launch"),
+}
+
+
 class BackendMissingError(RuntimeError):
     """libdq_sufsort_hip.so is absent or unloadable -- the product cannot run."""
 
@@ -124,8 +154,6 @@ def load() -> ctypes.CDLL:
     L.dq_sufcheck_hip_many_i32.argtypes = [vp, vp, i32, vp, vp, i32]
     L.dq_sufcheck_hip_many_dev_i32.restype = i32
     L.dq_sufcheck_hip_many_dev_i32.argtypes = [vp, vp, i32, vp, vp, i32, vp]
-    L.dq_last_check_many_info.restype = i32
-    L.dq_last_check_many_info.argtypes = [ctypes.POINTER(i64), i32]
     L.dq_sufsort_hip_batch_i32.restype = i32
     L.dq_sufsort_hip_batch_i32.argtypes = [i32, vp, vp, vp, i32, vp]
     L.dq_sufsort_hip_many_i32.restype = i32
@@ -142,10 +170,6 @@ def load() -> ctypes.CDLL:
     L.dq_bsdiff_create.argtypes = [vp, i64, vp, i64, vp, i64, ctypes.POINTER(i64), i32]
     L.dq_bsdiff_create_many.restype = i32
     L.dq_bsdiff_create_many.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, i32]
-    L.dq_last_many_info.restype = i32
-    L.dq_last_many_info.argtypes = [ctypes.POINTER(i64), i32]
-    L.dq_last_diff_many_info.restype = i32
-    L.dq_last_diff_many_info.argtypes = [ctypes.POINTER(i64), i32]
     L.dq_bsdiff_patch_bound.restype = i64
     L.dq_bsdiff_patch_bound.argtypes = [i64, i64]
     L.dq_bsdiff_scan_i32.restype = i32
@@ -159,12 +183,6 @@ def load() -> ctypes.CDLL:
     L.dq_bsdiff_index_buffers.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i64)]
     L.dq_bsdiff_index_diff_many.restype = i32
     L.dq_bsdiff_index_diff_many.argtypes = [vp, vp, vp, i32, vp, vp, vp]
-    L.dq_last_index_many_info.restype = i32
-    L.dq_last_index_many_info.argtypes = [ctypes.POINTER(i64), i32]
-    L.dq_last_diff_large_info.restype = i32
-    L.dq_last_diff_large_info.argtypes = [ctypes.POINTER(i64), i32]
-    L.dq_last_index_large_info.restype = i32
-    L.dq_last_index_large_info.argtypes = [ctypes.POINTER(i64), i32]
     L.dq_bsdiff_index_diff.restype = i32
     L.dq_bsdiff_index_diff.argtypes = [vp, vp, i64, vp, i64, ctypes.POINTER(i64)]
     L.dq_bsdiff_index_free.restype = None
@@ -188,12 +206,9 @@ def load() -> ctypes.CDLL:
     L.dq_profile_kernel_name.argtypes = [i32]
     L.dq_profile_category_count.restype = i32
     L.dq_profile_category_count.argtypes = []
-    L.dq_last_sort_info.restype = i32
-    L.dq_last_sort_info.argtypes = [ctypes.POINTER(i64)] * 3
-    L.dq_last_diff_info.restype = i32
-    L.dq_last_diff_info.argtypes = [ctypes.POINTER(i64), i32]
-    L.dq_last_batch_info.restype = i32
-    L.dq_last_batch_info.argtypes = [ctypes.POINTER(i64), i32]
+    for name, fields in RECORDS.items():            # (dq_last_sort_info: a pointer per entry; the others: array, count)
+        getattr(L, name).restype = i32
+        getattr(L, name).argtypes = [ctypes.POINTER(i64)] * len(fields) if name == "dq_last_sort_info" else [ctypes.POINTER(i64), i32]
     L.dq_device_numa_node.restype = i32
     L.dq_device_numa_node.argtypes = [i32]
     _lib = L
@@ -237,37 +252,35 @@ def category_of(kernel_name: str) -> int:
     raise KeyError(kernel_name)
 
 
+def _read(export: str) -> dict:
+    """The record behind one of the array getters, on this thread: {key: entry x scale} by RECORDS."""
+    fields = RECORDS[export]
+    v = (ctypes.c_int64 * len(fields))()
+    check(getattr(load(), export)(v, len(fields)))
+    return {key: v[i] * scale for i, (key, scale) in enumerate(fields)}
+
+
 def last_diff_info() -> dict:
     """Shape of the last Diff.Create / index diff on this thread (dq_last_diff_info)."""
-    L = load()
-    v = (ctypes.c_int64 * 9)()
-    L.dq_last_diff_info(v, 9)
-    return {"searches": v[0], "windows": v[1], "exact": v[2], "host_loop_fallbacks": v[3], "scan_groups": v[4],
-            "chains_launched": v[5], "chains_joined": v[6], "chains_dropped": v[7], "triples_from_chain_emitters": v[8]}
+    return _read("dq_last_diff_info")
 
 
 def last_diff_many_info() -> dict:
-    """Shape of the last dq_bsdiff_create_many on this thread (dq_last_diff_many_info)."""
-    L = load()
-    v = (ctypes.c_int64 * 12)()
-    L.dq_last_diff_many_info(v, 12)
-    # (shared_block_sorts / single_block_sorts count by length: doubled length up to / above 8192; medium_block_sorts
-    # says how many texts of the call shared a medium launch of the sorter: blocks, and old files above 8192 bytes.
-    # medium_pairs are counted in shared_pairs too; anchor_launches counts the short pairs' kernel only)
-    return {"shared_pairs": v[0], "single_pairs": v[1], "anchor_launches": v[2], "shared_block_sorts": v[3],
-            "single_block_sorts": v[4], "sort_old_ms": v[5] / 1e3, "anchor_ms": v[6] / 1e3, "emit_ms": v[7] / 1e3,
-            "block_sort_ms": v[8] / 1e3, "frame_ms": v[9] / 1e3, "medium_block_sorts": last_many_info()["medium_texts"],
-            "medium_pairs": v[10], "medium_anchor_launches": v[11]}
+    """Shape of the last dq_bsdiff_create_many on this thread (dq_last_diff_many_info).
+    (shared_block_sorts / single_block_sorts count by length: doubled length up to / above 8192; medium_block_sorts
+    says how many texts of the call shared a medium launch of the sorter: blocks, and old files above 8192 bytes.
+    medium_pairs are counted in shared_pairs too; anchor_launches counts the short pairs' kernel only)"""
+    out = {}
+    for key, value in _read("dq_last_diff_many_info").items():
+        out[key] = value
+        if key == "frame_ms":
+            out["medium_block_sorts"] = last_many_info()["medium_texts"]
+    return out
 
 
 def last_index_many_info() -> dict:
     """Shape of the last dq_bsdiff_index_diff_many on this thread (dq_last_index_many_info)."""
-    L = load()
-    v = (ctypes.c_int64 * 9)()
-    check(L.dq_last_index_many_info(v, 9))
-    return {"shared_files": v[0], "single_files": v[1], "anchor_launches": v[2], "shared_block_sorts": v[3],
-            "single_block_sorts": v[4], "anchor_ms": v[5] / 1e3, "emit_ms": v[6] / 1e3, "block_sort_ms": v[7] / 1e3,
-            "frame_ms": v[8] / 1e3}
+    return _read("dq_last_index_many_info")
 
 
 def last_diff_large_info() -> dict:
@@ -275,57 +288,37 @@ def last_diff_large_info() -> dict:
     dq_bsdiff_create_many on this thread (dq_last_diff_large_info).  large_pairs are counted in
     last_diff_many_info()["shared_pairs"] too, large_single in its "single_pairs"; anchor_ms and sort_old_ms are parts of
     its "anchor_ms" and "sort_old_ms"."""
-    L = load()
-    v = (ctypes.c_int64 * 6)()
-    check(L.dq_last_diff_large_info(v, 6))
-    return {"large_pairs": v[0], "large_launches": v[1], "large_single": v[2], "positions_built": v[3], "anchor_ms": v[4] / 1e3,
-            "sort_old_ms": v[5] / 1e3}
+    return _read("dq_last_diff_large_info")
 
 
 def last_index_large_info() -> dict:
     """The large class (new files of 65 537 .. 524 288 bytes, anchor_index_large_kernel) of the last
     dq_bsdiff_index_diff_many on this thread (dq_last_index_large_info).  large_files are counted in
     last_index_many_info()["shared_files"] too, large_single in its "single_files"."""
-    L = load()
-    v = (ctypes.c_int64 * 5)()
-    check(L.dq_last_index_large_info(v, 5))
-    return {"large_files": v[0], "large_launches": v[1], "large_single": v[2], "positions_built": v[3], "anchor_ms": v[4] / 1e3}
+    return _read("dq_last_index_large_info")
 
 
 def last_many_info() -> dict:
-    """Shape of the shared sorts of the last many-texts / batch / many-pairs call on this thread (dq_last_many_info)."""
-    L = load()
-    v = (ctypes.c_int64 * 6)()
-    check(L.dq_last_many_info(v, 6))
-    return {"short_texts": v[0], "medium_texts": v[1], "medium_single": v[2], "long_single": v[3],
-            "medium_launches": v[4], "scratch_bytes": v[5]}
+    """Shape of the shared sorts of the last many-texts / batch / many-pairs call on this thread (dq_last_many_info):
+    its first six entries (the others: last_many_large_info)."""
+    return dict(list(_read("dq_last_many_info").items())[:6])
 
 
 def last_many_large_info() -> dict:
     """The segmented sorts (texts above 65 536 bytes sorted together, dq_large_many.h) of the last many-texts / many-pairs
     call on this thread: entries [6] .. [8] of dq_last_many_info.  list_entries sums the list lengths over all rounds of
     all those sorts, round 0 counting the batch's bytes."""
-    L = load()
-    v = (ctypes.c_int64 * 9)()
-    check(L.dq_last_many_info(v, 9))
-    return {"large_texts": v[6], "segmented_sorts": v[7], "list_entries": v[8]}
+    return dict(list(_read("dq_last_many_info").items())[6:])
 
 
 def last_check_many_info() -> dict:
     """Shape of the last dq_sufcheck_hip_many_* on this thread (dq_last_check_many_info)."""
-    L = load()
-    v = (ctypes.c_int64 * 5)()
-    check(L.dq_last_check_many_info(v, 5))
-    return {"shared_texts": v[0], "single_texts": v[1], "launches": v[2], "chunks": v[3], "stream_waits": v[4]}
+    return _read("dq_last_check_many_info")
 
 
 def last_batch_info() -> dict:
     """Shape of the last dq_sufsort_hip_batch_i32 on this thread (dq_last_batch_info)."""
-    L = load()
-    v = (ctypes.c_int64 * 7)()
-    L.dq_last_batch_info(v, 7)
-    return {"pipelined": v[0], "copy_in_ms": v[1] / 1e3, "sort_ms": v[2] / 1e3, "copy_out_ms": v[3] / 1e3,
-            "slowest_share_ms": v[4] / 1e3, "shares_bound_to_numa_node": v[5], "shared_launch": v[6]}
+    return _read("dq_last_batch_info")
 
 
 def bind_process_to_device_numa_node(device: int) -> int | None:
@@ -356,7 +349,7 @@ def bind_process_to_device_numa_node(device: int) -> int | None:
 
 
 def last_sort_info() -> dict:
-    L = load()
-    a, b, c = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
-    L.dq_last_sort_info(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c))
-    return {"rounds": a.value, "initial_active": b.value, "sum_active": c.value}
+    fields = RECORDS["dq_last_sort_info"]
+    v = [ctypes.c_int64() for _ in fields]
+    load().dq_last_sort_info(*map(ctypes.byref, v))
+    return {key: x.value for (key, _), x in zip(fields, v)}

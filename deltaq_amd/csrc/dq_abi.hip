@@ -221,6 +221,15 @@ int batch_on_device(int device, const std::vector<int> &jobs, const uint8_t *con
     return sort_shorts();
 }
 
+// a dq_last_*_info getter: the record's entries into info[0 .. count) (dq_call_info.h), `what` where there is no such array
+template <typename Record>
+int last_info(const Record &record, int64_t *info, int32_t count, const char *what)
+{
+    if (!info || count < 0) return fail(DQ_ERR_BAD_ARGS, what);
+    copy_info(record, info, count);
+    return DQ_OK;
+}
+
 }  // namespace
 }  // namespace dq
 
@@ -296,7 +305,7 @@ int32_t dq_sufcheck_hip_many_i32(const uint8_t *texts, const int64_t *offsets, i
                                  int32_t *results, int32_t device)
 {
     EnvScope scope;
-    for (int64_t &x : t_check_many_info) x = 0;
+    t_check_many_info = {};
     try {
         return sufcheck_many_host(texts, offsets, count, sas, results, device);
     } catch (const std::bad_alloc &) {             // nothing may propagate through the C ABI
@@ -308,7 +317,7 @@ int32_t dq_sufcheck_hip_many_dev_i32(const void *d_texts, const void *d_offsets,
                                      int32_t *results, int32_t device, void *stream)
 {
     EnvScope scope;
-    for (int64_t &x : t_check_many_info) x = 0;
+    t_check_many_info = {};
     try {
         return sufcheck_many_dev(d_texts, d_offsets, count, d_sas, results, device, stream);
     } catch (const std::bad_alloc &) {
@@ -320,7 +329,7 @@ int32_t dq_sufsort_hip_batch_i32(int32_t count, const uint8_t *const *texts, con
                                  int32_t *const *sas, int32_t ndev, const int32_t *devs)
 {
     EnvScope scope;
-    for (int64_t &x : t_many_info) x = 0;
+    t_many_info = {};
     if (count < 0 || ndev <= 0 || (count > 0 && (!texts || !lens || !sas)))
         return fail(DQ_ERR_BAD_ARGS, "bad batch arguments");
     if (count == 0) return DQ_OK;
@@ -341,7 +350,7 @@ int32_t dq_sufsort_hip_batch_i32(int32_t count, const uint8_t *const *texts, con
     std::vector<int> rcs(ndev, DQ_OK);
     std::vector<std::string> errs(ndev);
     std::vector<ShareStats> stats(ndev);
-    for (int64_t &x : t_batch_info) x = 0;
+    t_batch_info = {};
     {
         JoinAll threads;
         for (int d = 0; d < ndev; ++d) {
@@ -357,13 +366,14 @@ int32_t dq_sufsort_hip_batch_i32(int32_t count, const uint8_t *const *texts, con
         }
     }
     for (const ShareStats &s : stats) {
-        t_batch_info[0] += s.piped; t_batch_info[1] += s.in_us; t_batch_info[2] += s.sort_us; t_batch_info[3] += s.out_us;
-        t_batch_info[4] = std::max(t_batch_info[4], s.wall_us);
-        t_batch_info[5] += s.bound;
-        t_batch_info[6] += s.shared;
+        t_batch_info.pipelined += s.piped; t_batch_info.copy_in_us += s.in_us; t_batch_info.sort_us += s.sort_us;
+        t_batch_info.copy_out_us += s.out_us;
+        t_batch_info.slowest_share_us = std::max(t_batch_info.slowest_share_us, s.wall_us);
+        t_batch_info.shares_bound_to_numa_node += s.bound;
+        t_batch_info.shared_launch += s.shared;
         // (the shares' threads made the shared sorts; only inputs of up to 8192 bytes go there, so the texts of the
-        // short classes are the whole record of a batch call: entries [1] .. [5] stay 0, as the header says)
-        t_many_info[0] += s.shared;
+        // short classes are the whole record of a batch call: the other entries stay 0, as the header says)
+        t_many_info.short_texts += s.shared;
     }
     for (int d = 0; d < ndev; ++d)
         if (rcs[d] != DQ_OK) { t_err = errs[d]; return rcs[d]; }
@@ -378,7 +388,7 @@ int32_t dq_sufsort_hip_batch_i32(int32_t count, const uint8_t *const *texts, con
 int32_t dq_sufsort_hip_many_i32(const uint8_t *texts, const int64_t *offsets, int32_t count, int32_t *sas, int32_t device)
 {
     EnvScope scope;
-    for (int64_t &x : t_many_info) x = 0;
+    t_many_info = {};
     try {
         return sufsort_many_host(texts, offsets, count, sas, device);
     } catch (const std::bad_alloc &) {             // nothing may propagate through the C ABI
@@ -390,7 +400,7 @@ int32_t dq_sufsort_hip_many_dev_i32(const void *d_texts, const void *d_offsets, 
                                     void *stream)
 {
     EnvScope scope;
-    for (int64_t &x : t_many_info) x = 0;
+    t_many_info = {};
     try {
         return sufsort_many_dev(d_texts, d_offsets, count, d_sas, device, stream);
     } catch (const std::bad_alloc &) {
@@ -536,7 +546,7 @@ int32_t dq_bsdiff_index_diff_many(const void *index, const uint8_t *news, const 
                                   uint8_t *patches, const int64_t *patch_offsets, int64_t *patch_lens)
 {
     EnvScope scope;
-    for (int64_t &x : t_many_info) x = 0;
+    t_many_info = {};
     try {
         return diff_index_many(index, news, new_offsets, count, patches, patch_offsets, patch_lens);
     } catch (const std::bad_alloc &) {
@@ -556,7 +566,7 @@ int32_t dq_bsdiff_create_many(const uint8_t *olds, const int64_t *old_offsets, c
                               int32_t count, uint8_t *patches, const int64_t *patch_offsets, int64_t *patch_lens, int32_t device)
 {
     EnvScope scope;
-    for (int64_t &x : t_many_info) x = 0;
+    t_many_info = {};
     try {
         return bsdiff_create_many_host(olds, old_offsets, news, new_offsets, count, patches, patch_offsets, patch_lens, device);
     } catch (const std::bad_alloc &) {
@@ -686,18 +696,13 @@ const char *dq_profile_kernel_name(int32_t category)
 
 int32_t dq_last_sort_info(int64_t *rounds, int64_t *initial_active, int64_t *sum_active)
 {
-    if (rounds) *rounds = t_info[0];
-    if (initial_active) *initial_active = t_info[1];
-    if (sum_active) *sum_active = t_info[2];
+    if (rounds) *rounds = t_sort_info.rounds;
+    if (initial_active) *initial_active = t_sort_info.initial_active;
+    if (sum_active) *sum_active = t_sort_info.sum_active;
     return DQ_OK;
 }
 
-int32_t dq_last_batch_info(int64_t *info, int32_t count)
-{
-    if (!info || count < 0) return fail(DQ_ERR_BAD_ARGS, "bad arguments");
-    for (int32_t k = 0; k < count; ++k) info[k] = k < 7 ? t_batch_info[k] : 0;
-    return DQ_OK;
-}
+int32_t dq_last_batch_info(int64_t *info, int32_t count) { return last_info(t_batch_info, info, count, "bad arguments"); }
 
 int32_t dq_device_numa_node(int32_t device)
 {
@@ -706,53 +711,18 @@ int32_t dq_device_numa_node(int32_t device)
     return device_numa_node(device);
 }
 
-int32_t dq_last_index_many_info(int64_t *info, int32_t count)
-{
-    if (!info || count < 0) return fail(DQ_ERR_BAD_ARGS, "null info array");
-    for (int32_t k = 0; k < count; ++k) info[k] = k < 9 ? t_index_many_info[k] : 0;
-    return DQ_OK;
-}
+int32_t dq_last_index_many_info(int64_t *info, int32_t count) { return last_info(t_index_many_info, info, count, "null info array"); }
 
-int32_t dq_last_index_large_info(int64_t *info, int32_t count)
-{
-    if (!info || count < 0) return fail(DQ_ERR_BAD_ARGS, "null info array");
-    for (int32_t k = 0; k < count; ++k) info[k] = k < 5 ? t_index_large_info[k] : 0;
-    return DQ_OK;
-}
+int32_t dq_last_index_large_info(int64_t *info, int32_t count) { return last_info(t_index_large_info, info, count, "null info array"); }
 
-int32_t dq_last_diff_many_info(int64_t *info, int32_t count)
-{
-    if (!info || count < 0) return fail(DQ_ERR_BAD_ARGS, "bad arguments");
-    for (int32_t k = 0; k < count; ++k) info[k] = k < 12 ? t_diff_many_info[k] : 0;
-    return DQ_OK;
-}
+int32_t dq_last_diff_many_info(int64_t *info, int32_t count) { return last_info(t_diff_many_info, info, count, "bad arguments"); }
 
-int32_t dq_last_diff_large_info(int64_t *info, int32_t count)
-{
-    if (!info || count < 0) return fail(DQ_ERR_BAD_ARGS, "null info array");
-    for (int32_t k = 0; k < count; ++k) info[k] = k < 6 ? t_diff_large_info[k] : 0;
-    return DQ_OK;
-}
+int32_t dq_last_diff_large_info(int64_t *info, int32_t count) { return last_info(t_diff_large_info, info, count, "null info array"); }
 
-int32_t dq_last_many_info(int64_t *info, int32_t count)
-{
-    if (!info || count < 0) return fail(DQ_ERR_BAD_ARGS, "bad arguments");
-    for (int32_t k = 0; k < count; ++k) info[k] = k < 9 ? t_many_info[k] : 0;
-    return DQ_OK;
-}
+int32_t dq_last_many_info(int64_t *info, int32_t count) { return last_info(t_many_info, info, count, "bad arguments"); }
 
-int32_t dq_last_check_many_info(int64_t *info, int32_t count)
-{
-    if (!info || count < 0) return fail(DQ_ERR_BAD_ARGS, "null info array");
-    for (int32_t k = 0; k < count; ++k) info[k] = k < 5 ? t_check_many_info[k] : 0;
-    return DQ_OK;
-}
+int32_t dq_last_check_many_info(int64_t *info, int32_t count) { return last_info(t_check_many_info, info, count, "null info array"); }
 
-int32_t dq_last_diff_info(int64_t *info, int32_t count)
-{
-    if (!info || count < 0) return fail(DQ_ERR_BAD_ARGS, "bad arguments");
-    for (int32_t k = 0; k < count; ++k) info[k] = k < 9 ? t_diff_info[k] : 0;
-    return DQ_OK;
-}
+int32_t dq_last_diff_info(int64_t *info, int32_t count) { return last_info(t_diff_info, info, count, "bad arguments"); }
 
 }  // extern "C"

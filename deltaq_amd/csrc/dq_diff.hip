@@ -889,7 +889,7 @@ struct ChainScan {
         min_seg = F.scan_min_seg.value_or(kScanMinSegment);
         extra_ends = F.scan_extra.value_or(kScanExtra);
         lane_budget = F.scan_lane_budget.value_or(kScanLaneBudget);
-        t_diff_info[4] = chains_max > 1 && m >= 2 * min_seg ? groups_chain : groups_alone;
+        t_diff_info.scan_groups = chains_max > 1 && m >= 2 * min_seg ? groups_chain : groups_alone;
     }
     void settle(int k)
     {
@@ -1207,7 +1207,8 @@ struct ChainScan {
     {
         for (const Count &q : counts) if (!q.read) return fail(DQ_ERR_HIP, "anchor scan: a join was left unsettled");
         raw.searches += (int64_t)(ch[cur].st.searches + joined_searches);
-        t_diff_info[5] = n_launches; t_diff_info[6] = n_joins; t_diff_info[7] = n_dropped; t_diff_info[8] = n_adopted;
+        t_diff_info.chains_launched = n_launches; t_diff_info.chains_joined = n_joins; t_diff_info.chains_dropped = n_dropped;
+        t_diff_info.triples_from_chain_emitters = n_adopted;
         if (em.progress) framer->complete();
         if (trace)
             fprintf(stderr, "[dq] anchor scan: %lld chain launches, %lld joins, %lld chains dropped in %.3f ms; emitter (steps 2 and 3 on the host, beside the kernels): %.2f ms "
@@ -1234,7 +1235,7 @@ int diff_index_scan(const DiffIndex &ix, const uint8_t *nw, int64_t m, bsdiff::R
 {
     if (m < 0 || (m > 0 && !nw)) return fail(DQ_ERR_BAD_ARGS, "bad arguments");
     if (m > 0x7fffffffLL) return fail(DQ_ERR_TOO_LARGE, "the BSDIFF40 path takes files below 2 GiB (int indices, as the reference)");
-    for (int64_t &x : t_diff_info) x = 0;
+    t_diff_info = {};
     if (m == 0) return DQ_OK;
     const int dev = ix.dev;
     HIP_TRY(hipSetDevice(dev));
@@ -1276,10 +1277,10 @@ int diff_index_scan(const DiffIndex &ix, const uint8_t *nw, int64_t m, bsdiff::R
             fprintf(stderr, "[dq] device scan: %lld searches, %lld windows, %lld stop points, %zu triples%s\n", (long long)raw.searches,
                     (long long)raw.windows, (long long)raw.exact, raw.ctrl.size() / 24, retry_on_host ? " -- given up, host loop instead" : "");
         if (!retry_on_host) {
-            t_diff_info[0] = raw.searches; t_diff_info[1] = raw.windows; t_diff_info[2] = raw.exact;
+            t_diff_info.searches = raw.searches; t_diff_info.windows = raw.windows; t_diff_info.exact = raw.exact;
             return rc;
         }
-        t_diff_info[3] += 1;                               // (not silently: dq_last_diff_info says the host loop took this file)
+        t_diff_info.host_loop_fallbacks += 1;            // (not silently: dq_last_diff_info says the host loop took this file)
         if (framer) framer->abandon();                     // (before the streams it reads go away)
         raw = bsdiff::RawStreams{};
     }
@@ -1307,7 +1308,7 @@ int diff_index_scan(const DiffIndex &ix, const uint8_t *nw, int64_t m, bsdiff::R
     // (the loop polled the kernels' own completion counts: drain the stream before the buffers are reused)
     const hipError_t drained = hipStreamSynchronize(c.stream);
     if (rc == DQ_OK && drained != hipSuccess) return fail(DQ_ERR_HIP, "scan loop: stream did not drain", drained);
-    t_diff_info[0] = raw.searches; t_diff_info[1] = raw.windows; t_diff_info[2] = raw.exact;
+    t_diff_info.searches = raw.searches; t_diff_info.windows = raw.windows; t_diff_info.exact = raw.exact;
     return rc;
 }
 
@@ -1534,9 +1535,12 @@ struct ManyChunk : WorkLists<2> {
 };
 
 // Phases 3 - 5 of a chunk (see above), from what the device wrote into k.back: list j has counts[j] pairs, searches[j]
-// its Search calls.  The patches into `out`; info[at[0 .. 5)] += blocks sorted in shared launches, blocks sorted singly,
-// microseconds of host emission, block sorts, host framing.
-int diff_many_finish(const ManyFiles &f, const ManyChunk &k, int dev, std::vector<ManyPair> &out, int64_t *info, std::array<int, 5> at)
+// its Search calls.  The patches into `out`; what the phases did into `fin`, as far as they came.
+struct FinishStats {
+    int64_t shared_block_sorts = 0, single_block_sorts = 0;    // blocks sorted in shared launches, blocks sorted singly
+    int64_t emit_us = 0, block_sort_us = 0, frame_us = 0;      // microseconds of host emission, block sorts, host framing
+};
+int diff_many_finish(const ManyFiles &f, const ManyChunk &k, int dev, std::vector<ManyPair> &out, FinishStats &fin)
 {
     out.clear();
     out.resize((size_t)k.cnt);
@@ -1575,7 +1579,7 @@ int diff_many_finish(const ManyFiles &f, const ManyChunk &k, int dev, std::vecto
     });
     for (ManyPair &w : out)
         if (w.rc != DQ_OK) { t_err = w.err; return w.rc; }
-    info[at[2]] += us_since(t0);
+    fin.emit_us = us_since(t0);
 
     // ---- 4. every block of the chunk in one shared sort
     t0 = std::chrono::steady_clock::now();
@@ -1616,9 +1620,9 @@ int diff_many_finish(const ManyFiles &f, const ManyChunk &k, int dev, std::vecto
     const int rc = sufsort_many_host(btext.data(), boff.data(), (int32_t)nblocks, bsa.data(), dev, &shared, /*large_by_default=*/false);
     if (rc != DQ_OK) return rc;
     std::vector<uint8_t>().swap(btext);
-    info[at[0]] += shared;
-    info[at[1]] += nblocks - shared;
-    info[at[3]] += us_since(t0);
+    fin.shared_block_sorts = shared;
+    fin.single_block_sorts = nblocks - shared;
+    fin.block_sort_us = us_since(t0);
 
     // ---- 5. the blocks' bits, the streams, the patches
     t0 = std::chrono::steady_clock::now();
@@ -1647,8 +1651,28 @@ int diff_many_finish(const ManyFiles &f, const ManyChunk &k, int dev, std::vecto
     });
     for (ManyPair &w : out)
         if (w.rc != DQ_OK) { t_err = w.err; return w.rc; }
-    info[at[4]] += us_since(t0);
+    fin.frame_us = us_since(t0);
     return DQ_OK;
+}
+
+// ... added to the record of the call (dq_last_diff_many_info or dq_last_index_many_info: the fields have one name in both)
+template <typename Record>
+void book_finish(Record &info, const FinishStats &fin)
+{
+    info.shared_block_sorts += fin.shared_block_sorts;
+    info.single_block_sorts += fin.single_block_sorts;
+    info.emit_us += fin.emit_us;
+    info.block_sort_us += fin.block_sort_us;
+    info.frame_us += fin.frame_us;
+}
+
+// positions of P that a large launch built, summed over its files: the kernel reports steps of 64 per file behind `searches`
+int64_t positions_built(const ManyChunk &k)
+{
+    const int32_t *built = k.back.data() + 2 * k.anchors + 2 * (size_t)k.cnt;
+    int64_t sum = 0;
+    for (int32_t j = 0; j < k.cnt; ++j) sum += 64 * (int64_t)built[j];
+    return sum;
 }
 
 // (more: further int32 words per file that a kernel reports behind `searches`; the large indexed class has one)
@@ -1763,7 +1787,10 @@ int diff_pairs_chunk(const uint8_t *olds, const int64_t *ooff, const uint8_t *ne
     }
     // ---- 3. - 5. on the host and in the shared block sort
     const ManyFiles files{olds, ooff + first, 0, news, noff + first};
-    return diff_many_finish(files, k, dev, out, t_diff_many_info, {3, 4, 7, 8, 9});
+    FinishStats fin;
+    const int done = diff_many_finish(files, k, dev, out, fin);
+    book_finish(t_diff_many_info, fin);
+    return done;
 }
 
 // ... no file above kMidMaxN bytes: one launch of anchor_many_kernel and one of anchor_mid_many_kernel, as the chunk has pairs for them
@@ -1771,7 +1798,7 @@ int diff_many_chunk(const uint8_t *olds, const int64_t *ooff, const uint8_t *new
                     int dev, DeviceBuf &buf, std::vector<ManyPair> &out)
 {
     ManyChunk k;
-    return diff_pairs_chunk(olds, ooff, news, noff, first, cnt, dev, buf, out, k, 0, &t_diff_many_info[5], &t_diff_many_info[6],
+    return diff_pairs_chunk(olds, ooff, news, noff, first, cnt, dev, buf, out, k, 0, &t_diff_many_info.sort_old_us, &t_diff_many_info.anchor_us,
                             [&](DeviceCtx &c, hipStream_t st, Launcher &L) -> int {
         // (a class's share of the bytes is not known here: the profile books all of them on the first launch)
         int64_t prof_units = k.n_bytes, prof_bytes = k.o_bytes * 5 + k.n_bytes;
@@ -1785,10 +1812,10 @@ int diff_many_chunk(const uint8_t *olds, const int64_t *ooff, const uint8_t *new
                    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3((unsigned)threads), 0, st, k.d_old, k.d_off, k.d_sa, k.d_new,
                                       k.d_noff, k.d_aoff, order, pairs, claim, k.d_back, k.d_counts, k.d_searches));
             prof_units = prof_bytes = 0;
-            t_diff_many_info[cls == 0 ? 2 : 11] += 1;
+            (cls == 0 ? t_diff_many_info.anchor_launches : t_diff_many_info.medium_anchor_launches) += 1;
             return DQ_OK;
         });
-        if (r == DQ_OK) t_diff_many_info[10] += k.class_count[1];
+        if (r == DQ_OK) t_diff_many_info.medium_pairs += k.class_count[1];
         return r;
     });
 }
@@ -1816,16 +1843,15 @@ int diff_large_chunk(const uint8_t *olds, const int64_t *ooff, const uint8_t *ne
             return DQ_OK;
         };
         const int r = table ? launch(std::true_type{}) : launch(std::false_type{});
-        if (r == DQ_OK) t_diff_large_info[1] += 1;
+        if (r == DQ_OK) t_diff_large_info.large_launches += 1;
         return r;
     });
-    t_diff_many_info[5] += sort_us;                        // (the call's phases, whichever kernel)
-    t_diff_many_info[6] += device_us;
-    t_diff_large_info[4] += device_us;
-    t_diff_large_info[5] += sort_us;
+    t_diff_many_info.sort_old_us += sort_us;           // (the call's phases, whichever kernel)
+    t_diff_many_info.anchor_us += device_us;
+    t_diff_large_info.anchor_us += device_us;
+    t_diff_large_info.sort_old_us += sort_us;
     if (rc != DQ_OK) return rc;
-    const int32_t *built = k.back.data() + 2 * k.anchors + 2 * (size_t)cnt;
-    for (int32_t j = 0; j < cnt; ++j) t_diff_large_info[3] += 64 * (int64_t)built[j];
+    t_diff_large_info.positions_built += positions_built(k);
     return DQ_OK;
 }
 
@@ -1857,8 +1883,8 @@ int many_deliver(const std::vector<uint8_t> &patch, int32_t j, uint8_t *patches,
 int bsdiff_create_many_host(const uint8_t *olds, const int64_t *ooff, const uint8_t *news, const int64_t *noff, int32_t count,
                             uint8_t *patches, const int64_t *poff, int64_t *plens, int32_t device)
 {
-    for (int64_t &x : t_diff_many_info) x = 0;
-    for (int64_t &x : t_diff_large_info) x = 0;
+    t_diff_many_info = {};
+    t_diff_large_info = {};
     if (count < 0) return fail(DQ_ERR_BAD_ARGS, "negative count");
     if (count == 0) return DQ_OK;
     if (!olds || !ooff || !news || !noff || !patches || !poff || !plens) return fail(DQ_ERR_BAD_ARGS, "null buffer");
@@ -1889,15 +1915,15 @@ int bsdiff_create_many_host(const uint8_t *olds, const int64_t *ooff, const uint
         std::vector<uint8_t> patch;
         int r = bsdiff_create_host(olds + ooff[j], ooff[j + 1] - ooff[j], news + noff[j], noff[j + 1] - noff[j], dev, patch);
         if (r == DQ_OK) r = deliver(j, patch);
-        if (r == DQ_OK) t_diff_many_info[1] += 1;
+        if (r == DQ_OK) t_diff_many_info.single_pairs += 1;
         return r;
     };
     auto chunk = [&](int32_t a, int32_t b, bool large) -> int {
         int r = large ? diff_large_chunk(olds, ooff, news, noff, a, b - a, dev, buf, done)
                       : diff_many_chunk(olds, ooff, news, noff, a, b - a, dev, buf, done);
         if (r != DQ_OK) return r;
-        t_diff_many_info[0] += b - a;
-        if (large) t_diff_large_info[0] += b - a;
+        t_diff_many_info.shared_pairs += b - a;
+        if (large) t_diff_large_info.large_pairs += b - a;
         for (int32_t j = a; j < b && r == DQ_OK; ++j) r = deliver(j, done[(size_t)(j - a)].patch);
         return r;
     };
@@ -1907,7 +1933,7 @@ int bsdiff_create_many_host(const uint8_t *olds, const int64_t *ooff, const uint
             // too few pairs for a launch of their own: one by one, in input order
             int rc = DQ_OK;
             for (int32_t j = i; j < e && rc == DQ_OK; ++j) rc = single(j);
-            if (rc == DQ_OK) t_diff_large_info[2] += e - i;
+            if (rc == DQ_OK) t_diff_large_info.large_single += e - i;
             return rc;
         }
         int64_t mids = 0;
@@ -2105,7 +2131,10 @@ int diff_index_chunk(const DiffIndex &ix, const uint8_t *news, const int64_t *no
     }
     // ---- 3. - 5. on the host and in the shared block sort
     const ManyFiles files{ix.old, nullptr, ix.n, news, noff + first};
-    return diff_many_finish(files, k, dev, out, t_index_many_info, {3, 4, 6, 7, 8});
+    FinishStats fin;
+    const int done = diff_many_finish(files, k, dev, out, fin);
+    book_finish(t_index_many_info, fin);
+    return done;
 }
 
 // ... none above kIndexManyMax bytes: one launch of anchor_index_many_kernel
@@ -2115,7 +2144,7 @@ int diff_index_many_chunk(const DiffIndex &ix, const uint8_t *news, const int64_
     const int threads = flags().index_many_threads.value_or(kIndexManyThreads);
     if (threads != 256 && threads != 512) return fail(DQ_ERR_BAD_ARGS, "DQ_INDEX_MANY_THREADS is 256 or 512");
     ManyChunk k;
-    return diff_index_chunk(ix, news, noff, first, cnt, buf, out, k, 0, &t_index_many_info[5],
+    return diff_index_chunk(ix, news, noff, first, cnt, buf, out, k, 0, &t_index_many_info.anchor_us,
                             [&](DeviceCtx &c, hipStream_t st, Launcher &L) -> int {
         auto launch = [&](auto width) -> int {
             constexpr int kThreads = decltype(width)::value;
@@ -2129,7 +2158,7 @@ int diff_index_many_chunk(const DiffIndex &ix, const uint8_t *news, const int64_
             return DQ_OK;
         };
         const int r = threads == 256 ? launch(std::integral_constant<int, 256>{}) : launch(std::integral_constant<int, 512>{});
-        if (r == DQ_OK) t_index_many_info[2] += 1;
+        if (r == DQ_OK) t_index_many_info.anchor_launches += 1;
         return r;
     });
 }
@@ -2149,14 +2178,13 @@ int diff_index_large_chunk(const DiffIndex &ix, const uint8_t *news, const int64
                                   reinterpret_cast<const uint8_t *>(ix.d_old), ix.n, reinterpret_cast<const int32_t *>(ix.d_sa),
                                   reinterpret_cast<const int32_t *>(ix.d_tab), ix.pk, k.d_new, k.d_noff, k.d_aoff, k.d_order, cnt,
                                   k.d_next, k.d_back, k.d_counts, k.d_searches, k.d_searches + cnt));
-        t_index_large_info[1] += 1;
+        t_index_large_info.large_launches += 1;
         return DQ_OK;
     });
-    t_index_many_info[5] += us;                            // (the call's device phase, whichever kernel)
-    t_index_large_info[4] += us;
+    t_index_many_info.anchor_us += us;                 // (the call's device phase, whichever kernel)
+    t_index_large_info.anchor_us += us;
     if (rc != DQ_OK) return rc;
-    const int32_t *built = k.back.data() + 2 * k.anchors + 2 * (size_t)cnt;
-    for (int32_t j = 0; j < cnt; ++j) t_index_large_info[3] += 64 * (int64_t)built[j];
+    t_index_large_info.positions_built += positions_built(k);
     return DQ_OK;
 }
 }  // namespace
@@ -2164,8 +2192,8 @@ int diff_index_large_chunk(const DiffIndex &ix, const uint8_t *news, const int64
 int diff_index_many(const void *index, const uint8_t *news, const int64_t *noff, int32_t count, uint8_t *patches, const int64_t *poff,
                     int64_t *plens)
 {
-    for (int64_t &x : t_index_many_info) x = 0;
-    for (int64_t &x : t_index_large_info) x = 0;
+    t_index_many_info = {};
+    t_index_large_info = {};
     if (!index) return fail(DQ_ERR_BAD_ARGS, "null index");
     if (count < 0) return fail(DQ_ERR_BAD_ARGS, "negative count");
     if (count == 0) return DQ_OK;
@@ -2192,7 +2220,7 @@ int diff_index_many(const void *index, const uint8_t *news, const int64_t *noff,
         std::vector<uint8_t> patch;
         int r = diff_index_diff(index, news + noff[j], noff[j + 1] - noff[j], patch);
         if (r == DQ_OK) r = deliver(j, patch);
-        if (r == DQ_OK) t_index_many_info[1] += 1;
+        if (r == DQ_OK) t_index_many_info.single_files += 1;
         return r;
     };
     auto run = [&](int32_t i, int32_t e) -> int {
@@ -2201,13 +2229,13 @@ int diff_index_many(const void *index, const uint8_t *news, const int64_t *noff,
         if (e - i < (large ? large_min : many_min)) {
             // too few files for a launch of their own: one by one, in input order
             for (int32_t j = i; j < e && rc == DQ_OK; ++j) rc = single(j);
-            if (large && rc == DQ_OK) t_index_large_info[2] += e - i;
+            if (large && rc == DQ_OK) t_index_large_info.large_single += e - i;
             return rc;
         }
         rc = large ? diff_index_large_chunk(*ix, news, noff, i, e - i, buf, done) : diff_index_many_chunk(*ix, news, noff, i, e - i, buf, done);
         if (rc != DQ_OK) return rc;
-        t_index_many_info[0] += e - i;
-        if (large) t_index_large_info[0] += e - i;
+        t_index_many_info.shared_files += e - i;
+        if (large) t_index_large_info.large_files += e - i;
         for (int32_t j = i; j < e && rc == DQ_OK; ++j) rc = deliver(j, done[(size_t)(j - i)].patch);
         return rc;
     };

@@ -33,6 +33,7 @@
 #include <sched.h>
 
 #include "../../include/dq_sufsort.h"
+#include "dq_call_info.h"
 #include "dq_flags.h"
 #include "dq_work_lists.h"
 
@@ -51,33 +52,6 @@ constexpr int32_t kManyChunkTexts = 1 << 20;
 
 // ------------------------------------------------------------------ errors
 inline thread_local std::string t_err;
-inline thread_local int64_t t_info[3] = {0, 0, 0};
-// the last Diff.Create / index diff on this thread (dq_last_diff_info): Search calls of the loop, windows, positions
-// asked again exactly, launches of the device's anchor scan that were given back to the host loop, workgroups of its grid
-inline thread_local int64_t t_diff_info[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-inline thread_local int64_t t_diff_many_info[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};     // dq_last_diff_many_info
-// ... and its large class (dq_last_diff_large_info): pairs through large launches, launches of anchor_pair_large_kernel,
-// large-class pairs that went one by one, positions of P built, microseconds in copies + the kernel, microseconds sorting
-// the old files of large chunks
-inline thread_local int64_t t_diff_large_info[6] = {0, 0, 0, 0, 0, 0};
-inline thread_local int64_t t_index_many_info[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};              // dq_last_index_many_info
-// ... and its large class (dq_last_index_large_info): files through large launches, launches of anchor_index_large_kernel,
-// large-class files that went one by one, positions of P built, microseconds in copies + the kernel
-inline thread_local int64_t t_index_large_info[5] = {0, 0, 0, 0, 0};
-// the shared sorts of the last outermost many-texts / batch / many-pairs call on this thread (dq_last_many_info): texts in
-// the short classes' launches, texts in medium launches, medium-length texts sorted singly, texts above kMidMaxN sorted
-// singly, launches of mid_many_kernel, bytes of per-workgroup scratch carved for them, texts sorted in segmented sorts
-// (dq_large_many.h), segmented sorts run, their list lengths summed over all rounds (round 0 counting the batch's bytes)
-inline thread_local int64_t t_many_info[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-// the last dq_sufcheck_hip_many_* on this thread (dq_last_check_many_info): texts checked in shared launches, texts checked
-// by the single-text kernels, launches of sufcheck_many_kernel, chunks of the host form, stream waits for verdicts
-inline thread_local int64_t t_check_many_info[5] = {0, 0, 0, 0, 0};
-
-// the last dq_sufsort_hip_batch_i32 on this thread (dq_last_batch_info): inputs through the pipelines, microseconds the
-// copy-in / sort / copy-out stages were busy (summed over the device shares), wall microseconds of the slowest share,
-// device shares whose host threads were bound to their device's NUMA node, inputs sorted in shared launches
-// (dq_small_many.h)
-inline thread_local int64_t t_batch_info[7] = {0, 0, 0, 0, 0, 0, 0};
 
 inline int fail(int code, const char *what, hipError_t e = hipSuccess)
 {

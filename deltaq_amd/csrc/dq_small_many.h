@@ -203,7 +203,7 @@ inline int launch_many(DeviceCtx &c, hipStream_t st, const ManyPlan &plan, const
         const ManyArgs a{d_texts, d_offsets, order, count, claim, d_sas, d_scratch};
         LAUNCH(L, DQ_K_SMALL_MANY, count, plan.class_bytes[k] * 5,
                kManyClass[k].launch(kManyClass[k].grid(&c.many_groups[k], count, c.dev), st, a));
-        if (k >= kManyClasses) t_many_info[4] += 1;
+        if (k >= kManyClasses) t_many_info.medium_launches += 1;
         return DQ_OK;
     });
 }
@@ -253,9 +253,9 @@ inline int launch_large(DeviceCtx &c, hipStream_t st, const ManyPlan &plan, cons
         const int segs = (int)(b.second - b.first);
         const int rc = large_many_sort(c, st, d_ws, d_texts, off, plan.larges.data() + b.first, segs, d_sas, tab, &lists);
         if (rc != DQ_OK) { (void)hipStreamSynchronize(st); return rc; }      // (the uploads read `tab` until here)
-        t_many_info[6] += segs;
-        t_many_info[7] += 1;
-        t_many_info[8] += lists;
+        t_many_info.large_texts += segs;
+        t_many_info.segmented_sorts += 1;
+        t_many_info.list_entries += lists;
     }
     return DQ_OK;
 }
@@ -264,12 +264,12 @@ inline int launch_large(DeviceCtx &c, hipStream_t st, const ManyPlan &plan, cons
 inline void many_account(const ManyPlan &plan, bool one_by_one, size_t scratch)
 {
     if (!one_by_one) {
-        t_many_info[0] += plan.shorts();
-        t_many_info[1] += plan.mids();
-        t_many_info[5] += (int64_t)scratch;
+        t_many_info.short_texts += plan.shorts();
+        t_many_info.medium_texts += plan.mids();
+        t_many_info.scratch_bytes += (int64_t)scratch;
     }
-    t_many_info[2] += plan.mid_single;
-    t_many_info[3] += plan.above_mid;
+    t_many_info.medium_single += plan.mid_single;
+    t_many_info.long_single += plan.above_mid;
 }
 
 // one text of the device form outside the shared launches (a long text, or every text under DQ_NO_MANY=1)
@@ -313,7 +313,7 @@ int sufsort_many_dev(const void *d_texts_v, const void *d_offsets_v, int32_t cou
         hipStream_t st = stream ? (hipStream_t)stream : c.stream;
         rc = fetch_many_offsets(d_offsets, count, st, off);
         if (rc != DQ_OK) return rc;
-        t_info[0] = t_info[1] = t_info[2] = 0;
+        t_sort_info = {};
         plan = plan_many(off.data(), count);
         if (!many_one_by_one() && plan.shared()) {
             const size_t b_ctl = many_ctl_bytes(plan.listed()), b_scratch = many_scratch_bytes(c, plan);
@@ -372,8 +372,8 @@ int sufsort_many_host(const uint8_t *texts, const int64_t *offsets, int32_t coun
     auto single = [&](int32_t i) -> int {
         const int r = sufsort_host<int32_t>(texts + offsets[i], len(i), sas + offsets[i], dev);
         if (r != DQ_OK) return r;
-        if (len(i) > kMidMaxN) t_many_info[3] += 1;
-        else if (len(i) > kSmallMaxN) t_many_info[2] += 1;
+        if (len(i) > kMidMaxN) t_many_info.long_single += 1;
+        else if (len(i) > kSmallMaxN) t_many_info.medium_single += 1;
         return DQ_OK;
     };
     // the chunk: texts [i, e), none above the limit, back to back in the caller's buffer
@@ -398,7 +398,7 @@ int sufsort_many_host(const uint8_t *texts, const int64_t *offsets, int32_t coun
                 uint8_t *d_text = reinterpret_cast<uint8_t *>(c.ws);
                 int32_t *d_sa = reinterpret_cast<int32_t *>(c.ws + b_text);
                 int64_t *d_off = reinterpret_cast<int64_t *>(c.ws + b_text + b_sa);
-                t_info[0] = t_info[1] = t_info[2] = 0;
+                t_sort_info = {};
                 auto run = [&]() -> int {
                     HIP_TRY(hipMemcpyAsync(d_text, texts + base, (size_t)bytes, hipMemcpyHostToDevice, st));
                     HIP_TRY(hipMemcpyAsync(d_off, rel.data(), rel.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));

@@ -147,8 +147,7 @@ struct SuffixSorter {
     int finish_sparse()
     {
         // tiny groups with a short remaining common prefix; the leftovers come back as a new list
-        t_info[0] += 1;
-        t_info[2] += m;
+        count_rounds(m);
         int64_t m2 = fin_left;
         if (!fin_done) {
             unsigned long long *left_over = reinterpret_cast<unsigned long long *>(w.totals + 3);
@@ -168,8 +167,7 @@ struct SuffixSorter {
         const int ebytes = std::max(1, std::min(4, (64 - rbits - 3) / 8));
         const int kbits = 8 * ebytes + 3;
         for (int r = 0; r < 3 && m > 0; ++r) {
-            t_info[0] += 1;
-            t_info[2] += m;
+            count_rounds(m);
             LAUNCH(L, DQ_K_GATHER_TEXT_KEY, m, m * (8 + wb + ebytes + 8),
                    hipLaunchKernelGGL(gather_text_key_kernel<IdxT>, dim3(grid_for(m)), dim3(kBlock), 0, st, Kr[rcur],
                                       (const IdxT *)Vr[rcur], (const uint8_t *)w.text, m, n, h, ebytes));
@@ -484,7 +482,7 @@ struct SuffixSorter {
         int64_t cur_m = m_in;
         for (int r = 0; r < chain_len; ++r) {
             if (c.pinned[2 * r + 1] != 0) return fail(DQ_ERR_HIP, "chained small-group round met a large group");
-            if (cur_m > 0) { t_info[0] += 1; t_info[2] += cur_m; }
+            if (cur_m > 0) count_rounds(cur_m);
             cur_m = c.pinned[2 * r] & 0xffffffffll;
         }
         m = cur_m;
@@ -496,8 +494,7 @@ struct SuffixSorter {
                     fprintf(stderr, "[dq] tail behind a chain of %d: %lld tied suffixes from h=%lld on, %lld rounds (%lld list entries in all)\n",
                             chain_len, (long long)cur_m, (long long)hr, (long long)rounds, (long long)entries);
                 if (left != 0) return fail(DQ_ERR_HIP, "tail rounds did not finish (round bound hit)");
-                t_info[0] += rounds;
-                t_info[2] += entries;
+                count_rounds(entries, rounds);
                 m = 0;
             }
         }
@@ -550,8 +547,7 @@ struct SuffixSorter {
             *outcome = 0;
             return DQ_OK;
         }
-        t_info[0] += 1;
-        t_info[2] += m_in;
+        count_rounds(m_in);
         LAUNCH(L, DQ_K_PAIR_CHAINS, m, m * (8 + wb) + cnt * (8 + wb) + copied * (8 + wb),
                hipLaunchKernelGGL((pair_split_kernel<IdxT, true>), dim3((unsigned)ntiles), dim3(kPcThreads), 0, st,
                                   (const uint64_t *)A, (const IdxT *)As, m, xbits, maxg, tile_cnt, B + half, Bs + half, B, Bs));
@@ -638,8 +634,7 @@ struct SuffixSorter {
             fprintf(stderr, "[dq] tail: %lld tied suffixes from h=%lld on, %lld rounds in one launch (%lld list entries in all)\n",
                     (long long)m, (long long)h, (long long)rounds, (long long)entries);
         if (left != 0) return fail(DQ_ERR_HIP, "tail rounds did not finish (round bound hit)");
-        t_info[0] += rounds;
-        t_info[2] += entries;
+        count_rounds(entries, rounds);
         m = 0;
         return DQ_OK;
     }
@@ -718,13 +713,13 @@ struct SuffixSorter {
     int run()
     {
         const Flags &F = flags();
-        t_info[0] = t_info[1] = t_info[2] = 0;
+        t_sort_info = {};
         HIP_TRY(hipMemsetAsync(w.totals, 0, 64, st));
         Round0Out<IdxT> r0;
         int rc = Round0<IdxT>{c, st, w, n, d_sa, L, text_src, period_hint, r0}.run();
         if (rc != DQ_OK) return rc;
         adopt(r0);
-        t_info[1] = m;
+        t_sort_info.initial_active = m;
         if (F.trace)
             fprintf(stderr, "[dq] after round 0: n=%lld, %d index bits, %lld tied suffixes, third list buffer %s\n", (long long)n,
                     bit_length((uint64_t)(n - 1)), (long long)m, w.X ? "carved" : "left out");
@@ -751,8 +746,7 @@ struct SuffixSorter {
             if (rc != DQ_OK) return rc;
             runs_on = true;
             run_order = period;
-            t_info[0] += 1;
-            t_info[2] += m;
+            count_rounds(m);
             if (F.trace)
                 fprintf(stderr, "[dq] run-order round (period %d) at h=%lld on %lld tied suffixes\n", period, (long long)h, (long long)m);
             rc = (uses_small_round(m) && !list_ungrouped) ? doubling_round_small(32) : doubling_round_radix(32, 0);
@@ -824,8 +818,7 @@ struct SuffixSorter {
                 if (rc != DQ_OK) return rc;
                 runs_on = true;
                 run_order = period;                        // (the kernels take the period from here)
-                t_info[0] += 1;
-                t_info[2] += m;
+                count_rounds(m);
                 if (F.trace)
                     fprintf(stderr, "[dq] late run-order round (period %d) at h=%lld on %lld tied suffixes (%lld in large groups, %lld the round before)\n",
                             period, (long long)h, (long long)m, (long long)last_large, (long long)prev_large);
@@ -848,8 +841,7 @@ struct SuffixSorter {
                 if (rc != DQ_OK) return rc;
                 continue;
             }
-            t_info[0] += 1;
-            t_info[2] += m;
+            count_rounds(m);
             const int kbits = bit_length((uint64_t)(n - 1) + (uint64_t)h);
             // (rank << kbits | key2) must fit 64 bits.  For 2^31 < n <= 2^32 a repeat longer than 2^32 - n bytes
             // needs 33 + 32: the key then carries rank >> 1 (unique per group: tied groups have >= 2 members)
@@ -898,7 +890,7 @@ template <typename IdxT>
 int sufsort_small(DeviceCtx &c, hipStream_t st, const uint8_t *text, int64_t n, IdxT *sa)
 {
     Launcher L{c, st, g_prof_on.load()};
-    t_info[0] = t_info[1] = t_info[2] = 0;
+    t_sort_info = {};
     LAUNCH(L, DQ_K_SMALL_SORT, n, n * (1 + (int64_t)sizeof(IdxT)),
            hipLaunchKernelGGL(small_sufsort_kernel<IdxT>, dim3(1), dim3(kSmallThreads), 0, st, text, (int)n, sa));
     HIP_TRY(hipStreamSynchronize(st));

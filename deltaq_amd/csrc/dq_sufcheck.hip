@@ -218,7 +218,7 @@ inline int launch_check(DeviceCtx &c, hipStream_t st, const CheckPlan &plan, con
         const CheckArgs a{d_texts, d_offsets, order, cnt, claim, d_sas, d_results};
         kCheckClass[k].launch(kCheckClass[k].grid(&c.check_many_groups[k], cnt, c.dev), st, a);
         HIP_TRY(hipGetLastError());
-        t_check_many_info[2] += 1;
+        t_check_many_info.launches += 1;
         return DQ_OK;
     });
     if (launched != DQ_OK) return launched;
@@ -234,9 +234,9 @@ inline int launch_check(DeviceCtx &c, hipStream_t st, const CheckPlan &plan, con
 inline void check_account(const CheckPlan &plan, int32_t *results, int32_t count)
 {
     for (int32_t j = 0; j < count; ++j) results[j] = sufcheck_verdict((uint32_t)results[j]);
-    t_check_many_info[0] += (int64_t)plan.order.size();
-    t_check_many_info[1] += (int64_t)plan.longs.size();
-    t_check_many_info[4] += 1;
+    t_check_many_info.shared_texts += (int64_t)plan.order.size();
+    t_check_many_info.single_texts += (int64_t)plan.longs.size();
+    t_check_many_info.stream_waits += 1;
 }
 
 inline bool check_one_by_one() { return flags().no_check_many.value_or(0) == 1; }
@@ -270,8 +270,8 @@ int sufcheck_many_dev(const void *d_texts_v, const void *d_offsets_v, int32_t co
             const int64_t n = off[j + 1] - off[j];
             rc = sufcheck_dev<int32_t>(d_texts + off[j], n, d_sas + off[j], n, results + j, dev, stream);
             if (rc != DQ_OK) return rc;
-            t_check_many_info[1] += 1;
-            t_check_many_info[4] += n > 0 ? 1 : 0;
+            t_check_many_info.single_texts += 1;
+            t_check_many_info.stream_waits += n > 0 ? 1 : 0;
         }
         return DQ_OK;
     }
@@ -316,8 +316,8 @@ int sufcheck_many_host(const uint8_t *texts, const int64_t *offsets, int32_t cou
         const int64_t n = offsets[i + 1] - offsets[i];
         const int r = sufcheck_host<int32_t>(texts + offsets[i], n, sas + offsets[i], n, results + i, dev);
         if (r != DQ_OK) return r;
-        t_check_many_info[1] += 1;
-        t_check_many_info[4] += n > 0 ? 1 : 0;
+        t_check_many_info.single_texts += 1;
+        t_check_many_info.stream_waits += n > 0 ? 1 : 0;
         return DQ_OK;
     };
     // the chunk: texts [i, e), back to back in the caller's buffers
@@ -354,7 +354,7 @@ int sufcheck_many_host(const uint8_t *texts, const int64_t *offsets, int32_t cou
         if (rc != DQ_OK) return rc;
         HIP_TRY(err);
         check_account(plan, results + i, cnt);
-        t_check_many_info[3] += 1;
+        t_check_many_info.chunks += 1;
         return DQ_OK;
     };
     // (a text is listed if it fits a chunk alone: the walk needs no more to make progress)

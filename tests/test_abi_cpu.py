@@ -212,3 +212,69 @@ def test_csharp_dllimports_match_the_header():
             assert cret == ret, f"{f}: {name} returns {cret}, header says {ret}"
             assert len(cparams) == len(params), f"{f}: {name} takes {len(cparams)} arguments, header says {len(params)}"
             assert cparams == params, f"{f}: {name} argument kinds {cparams} differ from the header's {params}"
+
+
+# ---- the dq_last_*_info records: dq_call_info.h's structs against _abi.py's table, and the getters' edges
+def header_records():
+    """{export name: [field names, in order]} parsed out of deltaq_amd/csrc/dq_call_info.h: struct <Name>Info is the record
+    behind dq_last_<name>_info."""
+    text = open(os.path.join(ROOT, "deltaq_amd", "csrc", "dq_call_info.h")).read()
+    text = re.sub(r"//[^\n]*", "", text)
+    records = {}
+    for name, body in re.findall(r"\bstruct\s+(\w+Info)\s*\{(.*?)\};", text, flags=re.S):
+        fields = []
+        for decl in body.split(";"):
+            if decl.strip():
+                m = re.fullmatch(r"\s*int64_t\s+([\w\s,]+)", decl)
+                assert m, f"{name}: a member that is no int64_t field: {decl.strip()!r}"
+                fields += [f.strip() for f in m.group(1).split(",")]
+        records["dq_last_" + re.sub(r"(?<!^)(?=[A-Z])", "_", name).lower()] = fields
+        assert re.search(rf"static_assert\(sizeof\({name}\) == {len(fields)} \* sizeof\(int64_t\)\)", text), name
+    return records
+
+
+def test_python_record_table_matches_the_header_structs():
+    """One name per counter: _abi.RECORDS has the records of dq_call_info.h, each with as many fields in the same order,
+    and every Python key is the field's name -- ..._ms for ..._us exactly where the scale is 1e-3."""
+    from deltaq_amd import _abi
+    hdr = header_records()
+    assert len(hdr) == 9 and set(hdr) == set(_abi.RECORDS)
+    assert set(hdr) <= set(header_symbols())
+    for export, fields in hdr.items():
+        table = _abi.RECORDS[export]
+        assert len(table) == len(fields) == len(set(fields)), export
+        for field, (key, scale) in zip(fields, table):
+            assert scale in (1, 1e-3), (export, key)
+            if scale == 1e-3:
+                assert field.endswith("_us") and key == field[:-3] + "_ms", (export, field, key)
+            else:
+                assert key == field and not field.endswith("_us"), (export, field, key)
+
+
+def test_info_getters_zero_fill_and_reject_bad_arguments(backend_lib):
+    """The eight array getters on a fresh thread (no GPU use: its records are all zero): count = fields + 3 fills every
+    slot, the extra ones with zeros; count = 0 succeeds and writes nothing; a NULL array and a negative count are
+    DQ_ERR_BAD_ARGS."""
+    import threading
+    from deltaq_amd import _abi
+    getters = [name for name in _abi.RECORDS if name != "dq_last_sort_info"]
+    assert len(getters) == 8
+    failures = []
+
+    def work():
+        try:
+            for name in getters:
+                fn, n = getattr(backend_lib, name), len(_abi.RECORDS[name])
+                v = (ctypes.c_int64 * (n + 3))(*([-7] * (n + 3)))
+                assert fn(v, n + 3) == _abi.DQ_OK and list(v) == [0] * (n + 3), (name, list(v))
+                v = (ctypes.c_int64 * 1)(-7)
+                assert fn(v, 0) == _abi.DQ_OK and v[0] == -7, name
+                assert fn(None, n) == _abi.DQ_ERR_BAD_ARGS and backend_lib.dq_last_error(), name
+                assert fn(v, -1) == _abi.DQ_ERR_BAD_ARGS and v[0] == -7, name
+        except Exception as e:                                          # noqa: BLE001 -- reported below
+            failures.append(e)
+
+    t = threading.Thread(target=work)
+    t.start()
+    t.join()
+    assert not failures, failures
