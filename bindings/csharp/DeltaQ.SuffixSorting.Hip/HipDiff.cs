@@ -6,6 +6,7 @@
 //   HipDiff.Apply         Patch.Apply(input, diff, output)                    src/DeltaQ.BsDiff/Patch.cs:34-43,52-168
 //   HipMatchSearch.Search Search(I, oldData, newData[scan..], 0, n, out pos)  src/DeltaQ.BsDiff/Diff.cs:267-298
 //   HipDiffIndex          Diff.cs:89-90 paid once per old file
+//   HipDiff.Scan / ScanMany, HipDiffIndex.Scan / ScanMany    the same calls up to the raw streams, before Diff.cs:15-18's bzip2
 //
 // Ships as SOURCE (no dotnet SDK in the build image); the tested surface is the C ABI (tests/test_gpu_bsdiff.py,
 // tests/test_gpu_match_search.py bind the same exports through ctypes).
@@ -73,6 +74,28 @@ internal static unsafe class Native
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
     internal static extern int dq_last_diff_info(long* info, int count);
 
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern int dq_bsdiff_scan_i32(byte* oldData, long n, byte* newData, long m, long* ctrl, long ctrlCap,
+                                                  long* nctrl, byte* diff, long* ndiff, byte* extra, long* nextra, long* stats,
+                                                  int device);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern long dq_bsdiff_ctrl_bound(long m);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern int dq_bsdiff_scan_many(byte* olds, long* oldOffsets, byte* news, long* newOffsets, int count,
+                                                   long* ctrl, long* ctrlOffsets, long* nctrl, byte* bytes, long* ndiff,
+                                                   long* searches, int device);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern int dq_bsdiff_index_scan(IntPtr index, byte* newData, long m, long* ctrl, long ctrlCap, long* nctrl,
+                                                    byte* bytes, long* ndiff, long* stats);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern int dq_bsdiff_index_scan_many(IntPtr index, byte* news, long* newOffsets, int count, long* ctrl,
+                                                         long* ctrlOffsets, long* nctrl, byte* bytes, long* ndiff,
+                                                         long* searches);
+
     internal static string LastError() => Marshal.PtrToStringAnsi(dq_last_error()) ?? string.Empty;
 
     internal static void Check(int rc, string what)
@@ -81,6 +104,72 @@ internal static unsafe class Native
         {
             throw new InvalidOperationException($"{what} failed ({rc}): {LastError()}");
         }
+    }
+}
+
+/// <summary>
+/// The output of the reference's scan loop for one new file, before bzip2 (Diff.cs:91-232): control triples as plain
+/// (add, copy, seek) longs, three per triple; diff bytes (new - old); extra bytes; and the loop's Search calls.
+/// </summary>
+public sealed class RawDiff
+{
+    public long[] Ctrl = Array.Empty<long>();
+    public byte[] Diff = Array.Empty<byte>();
+    public byte[] Extra = Array.Empty<byte>();
+    public long Searches;
+}
+
+/// <summary>The output buffers of a many-file scan call and their cutting into <see cref="RawDiff"/>s.</summary>
+internal sealed class RawSlots
+{
+    internal readonly long[] NewOffsets;
+    internal readonly long[] CtrlOffsets;
+    internal readonly long[] Ctrl;
+    internal readonly byte[] Bytes;
+    internal readonly long[] NCtrl;
+    internal readonly long[] NDiff;
+    internal readonly long[] Searches;
+
+    /// <summary>Control slots of dq_bsdiff_ctrl_bound(m) triples per file; <c>Bytes</c> in the layout of the new files.</summary>
+    internal RawSlots(long[] newOffsets)
+    {
+        int count = newOffsets.Length - 1;
+        NewOffsets = newOffsets;
+        CtrlOffsets = new long[count + 1];
+        for (int j = 0; j < count; j++)
+        {
+            CtrlOffsets[j + 1] = CtrlOffsets[j] + Native.dq_bsdiff_ctrl_bound(newOffsets[j + 1] - newOffsets[j]);
+        }
+
+        if (newOffsets[count] > Array.MaxLength || 3 * CtrlOffsets[count] > Array.MaxLength)
+        {
+            throw new ArgumentException("the new files of one ScanMany call must total less than 2^31 bytes");
+        }
+
+        // (at least one element each: the native side wants non-null pointers whenever there are files)
+        Ctrl = new long[Math.Max(3 * CtrlOffsets[count], 1)];
+        Bytes = new byte[Math.Max(newOffsets[count], 1)];
+        NCtrl = new long[count];
+        NDiff = new long[count];
+        Searches = new long[count];
+    }
+
+    internal RawDiff[] Unpack()
+    {
+        var result = new RawDiff[NCtrl.Length];
+        for (int j = 0; j < result.Length; j++)
+        {
+            int at = (int)NewOffsets[j], m = (int)(NewOffsets[j + 1] - NewOffsets[j]), ndiff = (int)NDiff[j];
+            result[j] = new RawDiff
+            {
+                Ctrl = Ctrl.AsSpan((int)(3 * CtrlOffsets[j]), (int)(3 * NCtrl[j])).ToArray(),
+                Diff = Bytes.AsSpan(at, ndiff).ToArray(),
+                Extra = Bytes.AsSpan(at + ndiff, m - ndiff).ToArray(),
+                Searches = Searches[j],
+            };
+        }
+
+        return result;
     }
 }
 
@@ -235,6 +324,100 @@ public static class HipDiff
         }
 
         return info;
+    }
+
+    /// <summary>
+    /// The raw streams of <see cref="Create"/> for one pair (dq_bsdiff_scan_i32): what the reference's loop emits before
+    /// its encoding streams (Diff.cs:15-18) compress it.
+    /// </summary>
+    public static unsafe RawDiff Scan(ReadOnlySpan<byte> oldData, ReadOnlySpan<byte> newData, int device = -1)
+    {
+        long m = newData.Length, cap = Native.dq_bsdiff_ctrl_bound(m);
+        var ctrl = new long[3 * cap];
+        var diff = new byte[Math.Max(m, 1)];
+        var extra = new byte[Math.Max(m, 1)];
+        long nctrl = 0, ndiff = 0, nextra = 0;
+        long* stats = stackalloc long[3];
+        fixed (byte* pOld = oldData)
+        fixed (byte* pNew = newData)
+        fixed (long* pCtrl = ctrl)
+        fixed (byte* pDiff = diff)
+        fixed (byte* pExtra = extra)
+        {
+            Native.Check(Native.dq_bsdiff_scan_i32(pOld, oldData.Length, pNew, m, pCtrl, cap, &nctrl, pDiff, &ndiff, pExtra, &nextra,
+                                                   stats, device),
+                         nameof(Native.dq_bsdiff_scan_i32));
+        }
+
+        return new RawDiff
+        {
+            Ctrl = ctrl.AsSpan(0, checked((int)(3 * nctrl))).ToArray(),
+            Diff = diff.AsSpan(0, checked((int)ndiff)).ToArray(),
+            Extra = extra.AsSpan(0, checked((int)nextra)).ToArray(),
+            Searches = stats[0],
+        };
+    }
+
+    /// <summary>
+    /// The raw streams of many independent (old, new) pairs in one native call (dq_bsdiff_scan_many): every pair goes the
+    /// way it goes in <see cref="CreateMany"/> -- the same shared launches, the same thresholds -- and the call stops
+    /// before bzip2.  Entry j of the result is what <see cref="Scan"/> returns for (olds[j], news[j]).  For another
+    /// container or compressor, or for choosing the best of several bases by delta size.  <see cref="LastDiffManyInfo"/>
+    /// and <see cref="LastDiffLargeInfo"/> report the call, the block-sort and framing entries reading 0.
+    /// </summary>
+    public static unsafe RawDiff[] ScanMany(IReadOnlyList<ReadOnlyMemory<byte>> olds, IReadOnlyList<ReadOnlyMemory<byte>> news,
+                                            int device = -1)
+    {
+        if (olds.Count != news.Count)
+        {
+            throw new ArgumentException("ScanMany takes as many new files as old files");
+        }
+
+        int count = olds.Count;
+        if (count == 0)
+        {
+            return Array.Empty<RawDiff>();
+        }
+
+        var oldOffsets = new long[count + 1];
+        var newOffsets = new long[count + 1];
+        for (int j = 0; j < count; j++)
+        {
+            oldOffsets[j + 1] = oldOffsets[j] + olds[j].Length;
+            newOffsets[j + 1] = newOffsets[j] + news[j].Length;
+        }
+
+        if (oldOffsets[count] > Array.MaxLength)
+        {
+            throw new ArgumentException("the old files of one ScanMany call must total less than 2^31 bytes");
+        }
+
+        var slots = new RawSlots(newOffsets);
+        byte[] flatOld = new byte[Math.Max(oldOffsets[count], 1)];
+        byte[] flatNew = new byte[Math.Max(newOffsets[count], 1)];
+        for (int j = 0; j < count; j++)
+        {
+            olds[j].Span.CopyTo(flatOld.AsSpan((int)oldOffsets[j], olds[j].Length));
+            news[j].Span.CopyTo(flatNew.AsSpan((int)newOffsets[j], news[j].Length));
+        }
+
+        fixed (byte* pOlds = flatOld)
+        fixed (long* pOldOffsets = oldOffsets)
+        fixed (byte* pNews = flatNew)
+        fixed (long* pNewOffsets = newOffsets)
+        fixed (long* pCtrl = slots.Ctrl)
+        fixed (long* pCtrlOffsets = slots.CtrlOffsets)
+        fixed (long* pNCtrl = slots.NCtrl)
+        fixed (byte* pBytes = slots.Bytes)
+        fixed (long* pNDiff = slots.NDiff)
+        fixed (long* pSearches = slots.Searches)
+        {
+            Native.Check(Native.dq_bsdiff_scan_many(pOlds, pOldOffsets, pNews, pNewOffsets, count, pCtrl, pCtrlOffsets, pNCtrl,
+                                                    pBytes, pNDiff, pSearches, device),
+                         nameof(Native.dq_bsdiff_scan_many));
+        }
+
+        return slots.Unpack();
     }
 
     public static unsafe byte[] CreateBytes(ReadOnlySpan<byte> oldData, ReadOnlySpan<byte> newData, int device, out long length)
@@ -451,6 +634,85 @@ public sealed unsafe class HipDiffIndex : IDisposable
         }
 
         return result;
+    }
+
+    /// <summary>The raw streams of <see cref="Create"/> (dq_bsdiff_index_scan): the scan loop's output before bzip2.</summary>
+    public RawDiff Scan(ReadOnlySpan<byte> newData)
+    {
+        if (_index == IntPtr.Zero)
+        {
+            throw new ObjectDisposedException(nameof(HipDiffIndex));
+        }
+
+        long m = newData.Length, cap = Native.dq_bsdiff_ctrl_bound(m);
+        var ctrl = new long[3 * cap];
+        var both = new byte[Math.Max(m, 1)];
+        long nctrl = 0, ndiff = 0;
+        long* stats = stackalloc long[3];
+        fixed (byte* pNew = newData)
+        fixed (long* pCtrl = ctrl)
+        fixed (byte* pBoth = both)
+        {
+            Native.Check(Native.dq_bsdiff_index_scan(_index, pNew, m, pCtrl, cap, &nctrl, pBoth, &ndiff, stats),
+                         nameof(Native.dq_bsdiff_index_scan));
+        }
+
+        return new RawDiff
+        {
+            Ctrl = ctrl.AsSpan(0, checked((int)(3 * nctrl))).ToArray(),
+            Diff = both.AsSpan(0, checked((int)ndiff)).ToArray(),
+            Extra = both.AsSpan(checked((int)ndiff), checked((int)(m - ndiff))).ToArray(),
+            Searches = stats[0],
+        };
+    }
+
+    /// <summary>
+    /// The raw streams of many new files against this index in one native call (dq_bsdiff_index_scan_many): every file
+    /// goes the way it goes in <see cref="CreateMany"/> and the call stops before bzip2.  Entry j of the result is what
+    /// <see cref="Scan"/> returns for news[j].  <see cref="LastIndexManyInfo"/> and <see cref="LastIndexLargeInfo"/>
+    /// report the call, the block-sort and framing entries reading 0.
+    /// </summary>
+    public RawDiff[] ScanMany(IReadOnlyList<ReadOnlyMemory<byte>> news)
+    {
+        if (_index == IntPtr.Zero)
+        {
+            throw new ObjectDisposedException(nameof(HipDiffIndex));
+        }
+
+        int count = news.Count;
+        if (count == 0)
+        {
+            return Array.Empty<RawDiff>();
+        }
+
+        var newOffsets = new long[count + 1];
+        for (int j = 0; j < count; j++)
+        {
+            newOffsets[j + 1] = newOffsets[j] + news[j].Length;
+        }
+
+        var slots = new RawSlots(newOffsets);
+        byte[] flatNew = new byte[Math.Max(newOffsets[count], 1)];
+        for (int j = 0; j < count; j++)
+        {
+            news[j].Span.CopyTo(flatNew.AsSpan((int)newOffsets[j], news[j].Length));
+        }
+
+        fixed (byte* pNews = flatNew)
+        fixed (long* pNewOffsets = newOffsets)
+        fixed (long* pCtrl = slots.Ctrl)
+        fixed (long* pCtrlOffsets = slots.CtrlOffsets)
+        fixed (long* pNCtrl = slots.NCtrl)
+        fixed (byte* pBytes = slots.Bytes)
+        fixed (long* pNDiff = slots.NDiff)
+        fixed (long* pSearches = slots.Searches)
+        {
+            Native.Check(Native.dq_bsdiff_index_scan_many(_index, pNews, pNewOffsets, count, pCtrl, pCtrlOffsets, pNCtrl, pBytes,
+                                                          pNDiff, pSearches),
+                         nameof(Native.dq_bsdiff_index_scan_many));
+        }
+
+        return slots.Unpack();
     }
 
     /// <summary>

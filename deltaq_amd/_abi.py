@@ -50,6 +50,7 @@ EXPORTS = (
     "dq_bsdiff_create_many", "dq_last_diff_many_info", "dq_last_diff_large_info",
     "dq_bsdiff_index_create", "dq_bsdiff_index_clone", "dq_bsdiff_index_buffers", "dq_bsdiff_index_diff", "dq_bsdiff_index_free",
     "dq_bsdiff_index_diff_many", "dq_last_index_many_info", "dq_last_index_large_info",
+    "dq_bsdiff_ctrl_bound", "dq_bsdiff_scan_many", "dq_bsdiff_index_scan", "dq_bsdiff_index_scan_many",
     "dq_sufsort_hip_workspace_bytes", "dq_sufsort_hip_workspace_plan", "dq_sufsort_hip_release",
     "dq_profile_enable", "dq_profile_reset", "dq_profile_get", "dq_profile_kernel_name",
     "dq_profile_category_count",
@@ -185,6 +186,14 @@ def load() -> ctypes.CDLL:
     L.dq_bsdiff_index_diff_many.argtypes = [vp, vp, vp, i32, vp, vp, vp]
     L.dq_bsdiff_index_diff.restype = i32
     L.dq_bsdiff_index_diff.argtypes = [vp, vp, i64, vp, i64, ctypes.POINTER(i64)]
+    L.dq_bsdiff_ctrl_bound.restype = i64
+    L.dq_bsdiff_ctrl_bound.argtypes = [i64]
+    L.dq_bsdiff_scan_many.restype = i32
+    L.dq_bsdiff_scan_many.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32]
+    L.dq_bsdiff_index_scan.restype = i32
+    L.dq_bsdiff_index_scan.argtypes = [vp, vp, i64, vp, i64, ctypes.POINTER(i64), vp, ctypes.POINTER(i64), vp]
+    L.dq_bsdiff_index_scan_many.restype = i32
+    L.dq_bsdiff_index_scan_many.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
     L.dq_bsdiff_index_free.restype = None
     L.dq_bsdiff_index_free.argtypes = [vp]
     L.dq_bspatch_apply.restype = i32

@@ -27,6 +27,43 @@ def _bytes_of(x) -> np.ndarray:
     return _as_text(x)
 
 
+def _pack(arrs):
+    """Files back to back and their count + 1 offsets, as the many-file calls take them."""
+    off = np.zeros(len(arrs) + 1, np.int64)
+    np.cumsum([a.size for a in arrs], out=off[1:])
+    flat = np.concatenate(arrs) if int(off[-1]) else np.zeros(1, np.uint8)
+    return np.ascontiguousarray(flat, dtype=np.uint8), off
+
+
+class _RawSlots:
+    """The output buffers of a many-file scan call (dq_bsdiff_scan_many, dq_bsdiff_index_scan_many): control slots of
+    dq_bsdiff_ctrl_bound(m) triples each, and `bytes` in the layout of the new files."""
+
+    def __init__(self, L, n_off):
+        self.count = n_off.size - 1
+        self.n_off = n_off
+        self.c_off = np.zeros(self.count + 1, np.int64)
+        np.cumsum([L.dq_bsdiff_ctrl_bound(int(m)) for m in np.diff(n_off)], out=self.c_off[1:])
+        self.ctrl = np.empty(max(3 * int(self.c_off[-1]), 1), np.int64)
+        self.bytes = np.empty(max(int(n_off[-1]), 1), np.uint8)
+        self.nctrl = np.full(self.count, -1, np.int64)
+        self.ndiff = np.zeros(self.count, np.int64)
+        self.searches = np.zeros(self.count, np.int64)
+
+    def pointers(self):
+        return (self.ctrl.ctypes.data, self.c_off.ctypes.data, self.nctrl.ctypes.data, self.bytes.ctypes.data,
+                self.ndiff.ctypes.data, self.searches.ctypes.data)
+
+    def unpack(self) -> list:
+        """Per file (ctrl [k, 3] int64, diff, extra, searches): views of the two flat buffers, nothing is copied."""
+        out = []
+        for j in range(self.count):
+            c0, k = 3 * int(self.c_off[j]), int(self.nctrl[j])
+            a, b, d = int(self.n_off[j]), int(self.n_off[j + 1]), int(self.ndiff[j])
+            out.append((self.ctrl[c0:c0 + 3 * k].reshape(-1, 3), self.bytes[a:a + d], self.bytes[a + d:b], int(self.searches[j])))
+        return out
+
+
 class Diff:
     @staticmethod
     def Create(oldData, newData, output, suffixSort=None) -> None:
@@ -107,6 +144,27 @@ class Diff:
                  "host_loop_fallbacks": _abi.last_diff_info()["host_loop_fallbacks"]})
 
 
+    @staticmethod
+    def ScanMany(olds, news, device: int = -1) -> list:
+        """The raw streams of ``Diff.CreateMany(olds, news)`` in one call (dq_bsdiff_scan_many): every pair goes the way
+        it goes there -- the same shared launches, the same thresholds -- and the call stops before bzip2.  Per pair
+        ``(ctrl triples [k, 3] int64, diff bytes, extra bytes, searches)``, in input order: the first three are what
+        ``Diff.Scan(old, new)`` returns, ``searches`` its Search count.  The arrays are views of two buffers shared by
+        all pairs of the call."""
+        L = _abi.load()
+        olds, news = list(olds), list(news)
+        if len(olds) != len(news):
+            raise ValueError(f"ScanMany: {len(olds)} old files against {len(news)} new files")
+        if not olds:
+            return []
+        o_flat, o_off = _pack([_as_text(x) for x in olds])
+        n_flat, n_off = _pack([_as_text(x) for x in news])
+        slots = _RawSlots(L, n_off)
+        _abi.check(L.dq_bsdiff_scan_many(o_flat.ctypes.data, o_off.ctypes.data, n_flat.ctypes.data, n_off.ctypes.data, slots.count,
+                                         *slots.pointers(), device))
+        return slots.unpack()
+
+
 class DiffIndex:
     """One old file on one device, ready to be diffed against many new files: what ``Diff.Create`` computes from
     ``oldData`` alone (the suffix array, Diff.cs:89-90) is computed once.  ``Create`` returns the patch
@@ -177,6 +235,33 @@ class DiffIndex:
         _abi.check(self._lib.dq_bsdiff_index_diff_many(self._h, n_flat.ctypes.data, n_off.ctypes.data, count, buf.ctypes.data,
                                                        p_off.ctypes.data, lens.ctypes.data))
         return [buf[int(p_off[j]):int(p_off[j]) + int(lens[j])].tobytes() for j in range(count)]
+
+    def Scan(self, newData):
+        """The raw streams of ``self.Create(newData)`` (dq_bsdiff_index_scan): ``(ctrl triples [k, 3] int64, diff bytes,
+        extra bytes, searches)``, the first three as ``Diff.Scan(oldData, newData)`` returns them."""
+        N = _as_text(newData)
+        m = N.size
+        cap = self._lib.dq_bsdiff_ctrl_bound(m)
+        ctrl = np.empty(3 * cap, np.int64)
+        both = np.empty(max(m, 1), np.uint8)
+        nc, nd = ctypes.c_int64(), ctypes.c_int64()
+        stats = (ctypes.c_int64 * 3)()
+        _abi.check(self._lib.dq_bsdiff_index_scan(self._h, N.ctypes.data if m else None, m, ctrl.ctypes.data, cap, ctypes.byref(nc),
+                                                  both.ctypes.data, ctypes.byref(nd), stats))
+        return ctrl[:3 * nc.value].reshape(-1, 3), both[:nd.value], both[nd.value:m], int(stats[0])
+
+    def ScanMany(self, news) -> list:
+        """The raw streams of ``self.CreateMany(news)`` in one call (dq_bsdiff_index_scan_many): every file goes the way
+        it goes there and the call stops before bzip2.  Per file ``(ctrl triples [k, 3] int64, diff bytes, extra bytes,
+        searches)``, in input order, as ``self.Scan`` returns them; the arrays are views of two buffers shared by all
+        files of the call."""
+        N = [_as_text(x) for x in news]
+        if not N:
+            return []
+        n_flat, n_off = _pack(N)
+        slots = _RawSlots(self._lib, n_off)
+        _abi.check(self._lib.dq_bsdiff_index_scan_many(self._h, n_flat.ctypes.data, n_off.ctypes.data, slots.count, *slots.pointers()))
+        return slots.unpack()
 
     def close(self) -> None:
         if getattr(self, "_h", None):

@@ -576,6 +576,51 @@ int32_t dq_bsdiff_create_many(const uint8_t *olds, const int64_t *old_offsets, c
     }
 }
 
+int64_t dq_bsdiff_ctrl_bound(int64_t m) { return bsdiff_ctrl_bound(m); }
+
+int32_t dq_bsdiff_scan_many(const uint8_t *olds, const int64_t *old_offsets, const uint8_t *news, const int64_t *new_offsets,
+                            int32_t count, int64_t *ctrl, const int64_t *ctrl_offsets, int64_t *nctrl,
+                            uint8_t *bytes, int64_t *ndiff, int64_t *searches, int32_t device)
+{
+    EnvScope scope;
+    t_many_info = {};
+    try {
+        return bsdiff_scan_many_host(olds, old_offsets, news, new_offsets, count, ctrl, ctrl_offsets, nctrl, bytes, ndiff, searches, device);
+    } catch (const std::bad_alloc &) {
+        return fail(DQ_ERR_OOM, "bsdiff: host allocation failed");
+    } catch (const std::exception &e) {            // nothing may propagate through the C ABI
+        return fail(DQ_ERR_HIP, e.what());
+    }
+}
+
+int32_t dq_bsdiff_index_scan(const void *index, const uint8_t *new_data, int64_t m, int64_t *ctrl, int64_t ctrl_cap,
+                             int64_t *nctrl, uint8_t *bytes, int64_t *ndiff, int64_t *stats)
+{
+    EnvScope scope;
+    try {
+        return diff_index_scan_one(index, new_data, m, ctrl, ctrl_cap, nctrl, bytes, ndiff, stats);
+    } catch (const std::bad_alloc &) {
+        return fail(DQ_ERR_OOM, "bsdiff: host allocation failed");
+    } catch (const std::exception &e) {
+        return fail(DQ_ERR_HIP, e.what());
+    }
+}
+
+int32_t dq_bsdiff_index_scan_many(const void *index, const uint8_t *news, const int64_t *new_offsets, int32_t count,
+                                  int64_t *ctrl, const int64_t *ctrl_offsets, int64_t *nctrl,
+                                  uint8_t *bytes, int64_t *ndiff, int64_t *searches)
+{
+    EnvScope scope;
+    t_many_info = {};
+    try {
+        return diff_index_scan_many(index, news, new_offsets, count, ctrl, ctrl_offsets, nctrl, bytes, ndiff, searches);
+    } catch (const std::bad_alloc &) {
+        return fail(DQ_ERR_OOM, "bsdiff: host allocation failed");
+    } catch (const std::exception &e) {            // nothing may propagate through the C ABI
+        return fail(DQ_ERR_HIP, e.what());
+    }
+}
+
 int64_t dq_bsdiff_patch_bound(int64_t n, int64_t m)
 {
     if (n < 0 || m < 0) return -1;

@@ -1411,6 +1411,9 @@ int frame_patch(const bsdiff::RawStreams &raw, int64_t m, int dev, std::vector<u
 // anchor lists + 40 bytes per pair (< 6 bytes per byte of text), whatever the pairs' classes: the medium kernel reads
 // the suffix arrays where the sort left them and has no scratch blocks.  Host memory per chunk: the raw streams (< 4 bytes
 // per byte of new), their blocks doubled with 4 bytes of suffix array per doubled byte (10 bytes per stream byte).
+// The scan calls (dq_bsdiff_scan_many, dq_bsdiff_index_scan_many) run phases 1 - 3 of the same chunks and deliver the raw
+// streams: host memory per chunk is those streams alone, held until they are delivered -- at most the chunk's new bytes
+// plus 24 bytes per triple.
 constexpr int64_t kDiffManyChunkBytes = 64ll << 20;
 constexpr int32_t kDiffManyChunkPairs = 1 << 18;
 // Fewest medium pairs (a file above kDiffManyMax, none above kMidMaxN) of a chunk that share its launches.  Below it
@@ -1535,18 +1538,21 @@ struct ManyChunk : WorkLists<2> {
 };
 
 // Phases 3 - 5 of a chunk (see above), from what the device wrote into k.back: list j has counts[j] pairs, searches[j]
-// its Search calls.  The patches into `out`; what the phases did into `fin`, as far as they came.
+// its Search calls.  What the phases did goes into `fin`, as far as they came.
 struct FinishStats {
     int64_t shared_block_sorts = 0, single_block_sorts = 0;    // blocks sorted in shared launches, blocks sorted singly
     int64_t emit_us = 0, block_sort_us = 0, frame_us = 0;      // microseconds of host emission, block sorts, host framing
 };
-int diff_many_finish(const ManyFiles &f, const ManyChunk &k, int dev, std::vector<ManyPair> &out, FinishStats &fin)
+
+// ---- 3. the raw streams of every pair into out[j].raw and, where the chunk is framed (dq_bsdiff_create_many,
+// dq_bsdiff_index_diff_many), their blocks up to the transform in the same loop.  The scan calls (dq_bsdiff_scan_many,
+// dq_bsdiff_index_scan_many) stop behind this phase: no encoder is made for them.
+int diff_many_emit(const ManyFiles &f, const ManyChunk &k, bool framing, std::vector<ManyPair> &out, FinishStats &fin)
 {
     out.clear();
     out.resize((size_t)k.cnt);
     const int32_t cnt = k.cnt, *anch = k.back.data(), *counts = anch + 2 * k.anchors, *searches = counts + cnt;
     const int64_t *rel_a = k.rel_a;
-    // ---- 3. the raw streams of every pair, and their blocks up to the transform
     auto t0 = std::chrono::steady_clock::now();
     diff_many_parallel(cnt, [&](int64_t j) {
         ManyPair &w = out[(size_t)j];
@@ -1567,6 +1573,7 @@ int diff_many_finish(const ManyFiles &f, const ManyChunk &k, int dev, std::vecto
             }
             if ((m > 0) != (k > 0)) { w.rc = DQ_ERR_HIP; w.err = "anchor list of a pair is not complete"; return; }
             w.raw.searches = searches[j];
+            if (!framing) return;
             const std::vector<uint8_t> *src[3] = {&w.raw.ctrl, &w.raw.diff, &w.raw.extra};
             for (int s = 0; s < 3; ++s) {
                 w.enc[s].reset(new bz2::StreamEncoder(bz2::DoubledSorter()));
@@ -1580,9 +1587,15 @@ int diff_many_finish(const ManyFiles &f, const ManyChunk &k, int dev, std::vecto
     for (ManyPair &w : out)
         if (w.rc != DQ_OK) { t_err = w.err; return w.rc; }
     fin.emit_us = us_since(t0);
+    return DQ_OK;
+}
 
+// ---- 4. + 5. of a framed chunk: from the encoders diff_many_emit left in `out` to the patches in out[j].patch
+int diff_many_frame(const ManyFiles &f, const ManyChunk &k, int dev, std::vector<ManyPair> &out, FinishStats &fin)
+{
+    const int32_t cnt = k.cnt;
     // ---- 4. every block of the chunk in one shared sort
-    t0 = std::chrono::steady_clock::now();
+    auto t0 = std::chrono::steady_clock::now();
     // (the short blocks first, then the medium ones, then those above kMidMaxN: sufsort_many_host shares launches among
     // neighbours in its list, and a block above kMidMaxN between two others would end a chunk of them)
     std::vector<int64_t> blen;                             // doubled length per block, pairs' order
@@ -1653,6 +1666,13 @@ int diff_many_finish(const ManyFiles &f, const ManyChunk &k, int dev, std::vecto
         if (w.rc != DQ_OK) { t_err = w.err; return w.rc; }
     fin.frame_us = us_since(t0);
     return DQ_OK;
+}
+
+// phases 3 - 5 of a framed chunk, phase 3 alone of a chunk whose raw streams are what the call returns
+int diff_many_finish(const ManyFiles &f, const ManyChunk &k, int dev, bool framing, std::vector<ManyPair> &out, FinishStats &fin)
+{
+    const int rc = diff_many_emit(f, k, framing, out, fin);
+    return rc != DQ_OK || !framing ? rc : diff_many_frame(f, k, dev, out, fin);
 }
 
 // ... added to the record of the call (dq_last_diff_many_info or dq_last_index_many_info: the fields have one name in both)
@@ -1728,14 +1748,15 @@ int many_chunk_upload(const ManyChunk &k, const uint8_t *olds, const uint8_t *ne
     return DQ_OK;
 }
 
-// Pairs [first, first + cnt) of the call, all on the work lists of ONE kind of chunk: their patches into `out`.  Phases 1 - 5
+// Pairs [first, first + cnt) of the call, all on the work lists of ONE kind of chunk: their patches into `out` (framing)
+// or their raw streams alone (not framing: phases 1 - 3).  Phases 1 - 5
 // as listed above; launch(c, st, L) makes phase 2's launches, the only part in which the kinds of chunk differ.
 // *sort_us += what sorting the old files took, *device_us += the copies and the launches.  k: the chunk, for what the
 // caller reads from k.back; more: as many_chunk_prepare's.
 template <typename Launch>
 int diff_pairs_chunk(const uint8_t *olds, const int64_t *ooff, const uint8_t *news, const int64_t *noff, int32_t first, int32_t cnt,
-                     int dev, DeviceBuf &buf, std::vector<ManyPair> &out, ManyChunk &k, int more, int64_t *sort_us, int64_t *device_us,
-                     Launch launch)
+                     int dev, bool framing, DeviceBuf &buf, std::vector<ManyPair> &out, ManyChunk &k, int more, int64_t *sort_us,
+                     int64_t *device_us, Launch launch)
 {
     HIP_TRY(hipSetDevice(dev));                            // (the chunk's allocation below is this device's)
     int rc = many_chunk_prepare(k, ooff, noff, first, cnt, buf, more);
@@ -1788,17 +1809,17 @@ int diff_pairs_chunk(const uint8_t *olds, const int64_t *ooff, const uint8_t *ne
     // ---- 3. - 5. on the host and in the shared block sort
     const ManyFiles files{olds, ooff + first, 0, news, noff + first};
     FinishStats fin;
-    const int done = diff_many_finish(files, k, dev, out, fin);
+    const int done = diff_many_finish(files, k, dev, framing, out, fin);
     book_finish(t_diff_many_info, fin);
     return done;
 }
 
 // ... no file above kMidMaxN bytes: one launch of anchor_many_kernel and one of anchor_mid_many_kernel, as the chunk has pairs for them
 int diff_many_chunk(const uint8_t *olds, const int64_t *ooff, const uint8_t *news, const int64_t *noff, int32_t first, int32_t cnt,
-                    int dev, DeviceBuf &buf, std::vector<ManyPair> &out)
+                    int dev, bool framing, DeviceBuf &buf, std::vector<ManyPair> &out)
 {
     ManyChunk k;
-    return diff_pairs_chunk(olds, ooff, news, noff, first, cnt, dev, buf, out, k, 0, &t_diff_many_info.sort_old_us, &t_diff_many_info.anchor_us,
+    return diff_pairs_chunk(olds, ooff, news, noff, first, cnt, dev, framing, buf, out, k, 0, &t_diff_many_info.sort_old_us, &t_diff_many_info.anchor_us,
                             [&](DeviceCtx &c, hipStream_t st, Launcher &L) -> int {
         // (a class's share of the bytes is not known here: the profile books all of them on the first launch)
         int64_t prof_units = k.n_bytes, prof_bytes = k.o_bytes * 5 + k.n_bytes;
@@ -1823,12 +1844,12 @@ int diff_many_chunk(const uint8_t *olds, const int64_t *ooff, const uint8_t *new
 // ... every pair's longer file of kMidMaxN + 1 .. kDiffLargeMax bytes: one launch of anchor_pair_large_kernel (every pair
 // is on the chunk's second work list: many_chunk_prepare knows two kinds of pair, and none of these is short)
 int diff_large_chunk(const uint8_t *olds, const int64_t *ooff, const uint8_t *news, const int64_t *noff, int32_t first, int32_t cnt,
-                     int dev, DeviceBuf &buf, std::vector<ManyPair> &out)
+                     int dev, bool framing, DeviceBuf &buf, std::vector<ManyPair> &out)
 {
     const bool table = flags().diff_large_table.value_or(kDiffLargeTable ? 1 : 0) != 0;
     ManyChunk k;
     int64_t sort_us = 0, device_us = 0;
-    const int rc = diff_pairs_chunk(olds, ooff, news, noff, first, cnt, dev, buf, out, k, 1, &sort_us, &device_us,
+    const int rc = diff_pairs_chunk(olds, ooff, news, noff, first, cnt, dev, framing, buf, out, k, 1, &sort_us, &device_us,
                                     [&](DeviceCtx &c, hipStream_t st, Launcher &L) -> int {
         if (k.class_count[0] != 0 || k.class_count[1] != cnt) return fail(DQ_ERR_HIP, "a large chunk holds a short pair");
         auto launch = [&](auto with_table) -> int {
@@ -1870,31 +1891,63 @@ int many_check_offsets(const int64_t *ooff, const int64_t *noff, const int64_t *
     return DQ_OK;
 }
 
-// patch j of a many-file call into its slot
-int many_deliver(const std::vector<uint8_t> &patch, int32_t j, uint8_t *patches, const int64_t *poff, int64_t *plens)
-{
-    if ((int64_t)patch.size() > poff[j + 1] - poff[j]) return fail(DQ_ERR_BAD_ARGS, "output buffer too small (see dq_bsdiff_patch_bound)");
-    if (!patch.empty()) memcpy(patches + poff[j], patch.data(), patch.size());
-    plens[j] = (int64_t)patch.size();
-    return DQ_OK;
-}
-}  // namespace
+// What a many-file call does with a finished file.  The two drivers below are written once over a sink: kFraming says
+// whether a file is taken as far as its patch (the chunks run phases 4 - 5, a single file goes through frame_patch) or
+// as far as its raw streams; deliver() puts file j of the call into the caller's slot.
+// ... the framing calls: patch j into its slot
+struct PatchSink {
+    static constexpr bool kFraming = true;
+    uint8_t *patches;
+    const int64_t *poff;
+    int64_t *plens;
+    int deliver(int32_t j, const std::vector<uint8_t> &patch) const
+    {
+        if ((int64_t)patch.size() > poff[j + 1] - poff[j]) return fail(DQ_ERR_BAD_ARGS, "output buffer too small (see dq_bsdiff_patch_bound)");
+        if (!patch.empty()) memcpy(patches + poff[j], patch.data(), patch.size());
+        plens[j] = (int64_t)patch.size();
+        return DQ_OK;
+    }
+    int deliver(int32_t j, const ManyPair &w) const { return deliver(j, w.patch); }
+};
+// ... the scan calls: the triples of file j as plain int64 into its control slot (coff counts triples), its diff bytes
+// and behind them its extra bytes into the file's own place in `bytes`, which has the layout of `news`
+struct RawSink {
+    static constexpr bool kFraming = false;
+    const int64_t *noff;
+    int64_t *ctrl;
+    const int64_t *coff;
+    int64_t *nctrl;
+    uint8_t *bytes;
+    int64_t *ndiff, *searches;
+    int deliver(int32_t j, const bsdiff::RawStreams &raw) const
+    {
+        const int64_t triples = (int64_t)(raw.ctrl.size() / 24), m = noff[j + 1] - noff[j];
+        // (every byte of new is in exactly one of the two streams: the file's place in `bytes` needs no capacity of its own)
+        if (raw.ctrl.size() % 24 != 0 || (int64_t)raw.diff.size() + (int64_t)raw.extra.size() != m)
+            return fail(DQ_ERR_HIP, "internal: diff and extra bytes of a file do not add up to its length");
+        if (triples > coff[j + 1] - coff[j]) return fail(DQ_ERR_BAD_ARGS, "output buffer too small (see dq_bsdiff_ctrl_bound)");
+        int64_t *c = ctrl + 3 * coff[j];
+        for (int64_t i = 0; i < 3 * triples; ++i) c[i] = bsdiff::read_packed_long(&raw.ctrl[(size_t)i * 8]);
+        if (!raw.diff.empty()) memcpy(bytes + noff[j], raw.diff.data(), raw.diff.size());
+        if (!raw.extra.empty()) memcpy(bytes + noff[j] + raw.diff.size(), raw.extra.data(), raw.extra.size());
+        ndiff[j] = (int64_t)raw.diff.size();
+        if (searches) searches[j] = raw.searches;
+        nctrl[j] = triples;
+        return DQ_OK;
+    }
+    int deliver(int32_t j, const ManyPair &w) const { return deliver(j, w.raw); }
+};
 
-int bsdiff_create_many_host(const uint8_t *olds, const int64_t *ooff, const uint8_t *news, const int64_t *noff, int32_t count,
-                            uint8_t *patches, const int64_t *poff, int64_t *plens, int32_t device)
+// The body of dq_bsdiff_create_many and of dq_bsdiff_scan_many, behind their argument checks: one planner, whatever the
+// sink -- a pair goes the same way in both calls.
+template <typename Sink>
+int diff_pairs_many(const uint8_t *olds, const int64_t *ooff, const uint8_t *news, const int64_t *noff, int32_t count, int32_t device,
+                    const Sink &sink)
 {
-    t_diff_many_info = {};
-    t_diff_large_info = {};
-    if (count < 0) return fail(DQ_ERR_BAD_ARGS, "negative count");
-    if (count == 0) return DQ_OK;
-    if (!olds || !ooff || !news || !noff || !patches || !poff || !plens) return fail(DQ_ERR_BAD_ARGS, "null buffer");
-    int rc = many_check_offsets(ooff, noff, poff, count, plens);
-    if (rc != DQ_OK) return rc;
     int dev = 0;
-    rc = resolve_device(device, &dev);
+    int rc = resolve_device(device, &dev);
     if (rc != DQ_OK) return rc;
 
-    auto deliver = [&](int32_t j, const std::vector<uint8_t> &patch) { return many_deliver(patch, j, patches, poff, plens); };
     const bool one_by_one = flags().no_diff_many.value_or(0) != 0;
     const int64_t listed_max = flags().no_diff_mid_many.value_or(0) != 0 ? kDiffManyMax : kMidMaxN;
     const int64_t mid_min = flags().diff_mid_many_min.value_or(kDiffMidManyMin);
@@ -1912,19 +1965,28 @@ int bsdiff_create_many_host(const uint8_t *olds, const int64_t *ooff, const uint
     std::vector<ManyPair> done;
     auto single = [&](int32_t j) -> int {
         // the one-pair path, into the pair's slot (it reports under its own dq_last_diff_info)
-        std::vector<uint8_t> patch;
-        int r = bsdiff_create_host(olds + ooff[j], ooff[j + 1] - ooff[j], news + noff[j], noff[j + 1] - noff[j], dev, patch);
-        if (r == DQ_OK) r = deliver(j, patch);
+        const uint8_t *old = olds + ooff[j], *nw = news + noff[j];
+        const int64_t n = ooff[j + 1] - ooff[j], m = noff[j + 1] - noff[j];
+        int r;
+        if constexpr (Sink::kFraming) {
+            std::vector<uint8_t> patch;
+            r = bsdiff_create_host(old, n, nw, m, dev, patch);
+            if (r == DQ_OK) r = sink.deliver(j, patch);
+        } else {
+            bsdiff::RawStreams raw;
+            r = bsdiff_raw(old, n, nw, m, dev, raw);
+            if (r == DQ_OK) r = sink.deliver(j, raw);
+        }
         if (r == DQ_OK) t_diff_many_info.single_pairs += 1;
         return r;
     };
     auto chunk = [&](int32_t a, int32_t b, bool large) -> int {
-        int r = large ? diff_large_chunk(olds, ooff, news, noff, a, b - a, dev, buf, done)
-                      : diff_many_chunk(olds, ooff, news, noff, a, b - a, dev, buf, done);
+        int r = large ? diff_large_chunk(olds, ooff, news, noff, a, b - a, dev, Sink::kFraming, buf, done)
+                      : diff_many_chunk(olds, ooff, news, noff, a, b - a, dev, Sink::kFraming, buf, done);
         if (r != DQ_OK) return r;
         t_diff_many_info.shared_pairs += b - a;
         if (large) t_diff_large_info.large_pairs += b - a;
-        for (int32_t j = a; j < b && r == DQ_OK; ++j) r = deliver(j, done[(size_t)(j - a)].patch);
+        for (int32_t j = a; j < b && r == DQ_OK; ++j) r = sink.deliver(j, done[(size_t)(j - a)]);
         return r;
     };
     auto run = [&](int32_t i, int32_t e) -> int {
@@ -1952,6 +2014,34 @@ int bsdiff_create_many_host(const uint8_t *olds, const int64_t *ooff, const uint
                                 (ooff[e + 1] - ooff[i]) + (noff[e + 1] - noff[i]) <= (c == 1 ? kDiffLargeChunkBytes : kDiffManyChunkBytes);
                      },
                      single, run);
+}
+}  // namespace
+
+int bsdiff_create_many_host(const uint8_t *olds, const int64_t *ooff, const uint8_t *news, const int64_t *noff, int32_t count,
+                            uint8_t *patches, const int64_t *poff, int64_t *plens, int32_t device)
+{
+    t_diff_many_info = {};
+    t_diff_large_info = {};
+    if (count < 0) return fail(DQ_ERR_BAD_ARGS, "negative count");
+    if (count == 0) return DQ_OK;
+    if (!olds || !ooff || !news || !noff || !patches || !poff || !plens) return fail(DQ_ERR_BAD_ARGS, "null buffer");
+    const int rc = many_check_offsets(ooff, noff, poff, count, plens);
+    if (rc != DQ_OK) return rc;
+    return diff_pairs_many(olds, ooff, news, noff, count, device, PatchSink{patches, poff, plens});
+}
+
+// dq_bsdiff_scan_many: dq_bsdiff_create_many as far as the raw streams (the records are that call's)
+int bsdiff_scan_many_host(const uint8_t *olds, const int64_t *ooff, const uint8_t *news, const int64_t *noff, int32_t count, int64_t *ctrl,
+                          const int64_t *coff, int64_t *nctrl, uint8_t *bytes, int64_t *ndiff, int64_t *searches, int32_t device)
+{
+    t_diff_many_info = {};
+    t_diff_large_info = {};
+    if (count < 0) return fail(DQ_ERR_BAD_ARGS, "negative count");
+    if (count == 0) return DQ_OK;
+    if (!olds || !ooff || !news || !noff || !ctrl || !coff || !nctrl || !bytes || !ndiff) return fail(DQ_ERR_BAD_ARGS, "null buffer");
+    const int rc = many_check_offsets(ooff, noff, coff, count, nctrl);
+    if (rc != DQ_OK) return rc;
+    return diff_pairs_many(olds, ooff, news, noff, count, device, RawSink{noff, ctrl, coff, nctrl, bytes, ndiff, searches});
 }
 
 int bsdiff_create_host(const uint8_t *old, int64_t n, const uint8_t *nw, int64_t m, int32_t device, std::vector<uint8_t> &patch)
@@ -2053,6 +2143,32 @@ int diff_index_diff(const void *index, const uint8_t *nw, int64_t m, std::vector
     return frame_patch(raw, m, ix->dev, patch, &framer);                            // (framing overlaps the next caller's scan loop)
 }
 
+// dq_bsdiff_index_scan: diff_index_diff without frame_patch
+int diff_index_raw(const void *index, const uint8_t *nw, int64_t m, bsdiff::RawStreams &raw)
+{
+    const DiffIndex *ix = static_cast<const DiffIndex *>(index);
+    std::lock_guard<std::mutex> one_diff(ctx0(ix->dev).diff_mu);          // scan loops take turns on a device
+    return diff_index_scan(*ix, nw, m, raw);
+}
+
+int diff_index_scan_one(const void *index, const uint8_t *nw, int64_t m, int64_t *ctrl, int64_t ctrl_cap, int64_t *nctrl, uint8_t *bytes,
+                        int64_t *ndiff, int64_t *stats)
+{
+    if (!index) return fail(DQ_ERR_BAD_ARGS, "null index");
+    if (m < 0 || ctrl_cap < 0) return fail(DQ_ERR_BAD_ARGS, "negative length");
+    if (!nctrl || !ndiff || (m > 0 && (!nw || !bytes || !ctrl))) return fail(DQ_ERR_BAD_ARGS, "null buffer");
+    if (m > 0x7fffffffLL) return fail(DQ_ERR_TOO_LARGE, "the BSDIFF40 path takes files below 2 GiB (int indices, as the reference)");
+    *nctrl = -1;
+    bsdiff::RawStreams raw;
+    const int rc = diff_index_raw(index, nw, m, raw);
+    if (rc != DQ_OK) return rc;
+    const int64_t one_off[2] = {0, m}, one_slot[2] = {0, ctrl_cap};
+    int64_t searches = 0;
+    const int put = RawSink{one_off, ctrl, one_slot, nctrl, bytes, ndiff, &searches}.deliver(0, raw);
+    if (put == DQ_OK && stats) { stats[0] = raw.searches; stats[1] = raw.windows; stats[2] = raw.exact; }
+    return put;
+}
+
 
 // ---- many new files against one index in shared launches (dq_bsdiff_index_diff_many) --------------------------------
 // A new file of a few KiB costs diff_index_diff a copy, the launch of the persistent anchor scan, its polls and up to
@@ -2097,12 +2213,12 @@ constexpr int32_t kIndexLargeMin = 64;
 constexpr bool kIndexLargeOn = true;
 
 namespace {
-// New files [first, first + cnt) of the call, all of one class: their patches into `out`.  The chunk's copies, the one
+// New files [first, first + cnt) of the call, all of one class: their patches into `out` (framing) or their raw streams alone.  The chunk's copies, the one
 // launch the class makes -- launch(c, st, L), the only part in which the classes differ -- and the copy back run
 // under the device's diff_mu; *device_us += what that took.  k: the chunk, for what the caller reads from k.back.
 template <typename Launch>
-int diff_index_chunk(const DiffIndex &ix, const uint8_t *news, const int64_t *noff, int32_t first, int32_t cnt, DeviceBuf &buf,
-                     std::vector<ManyPair> &out, ManyChunk &k, int more, int64_t *device_us, Launch launch)
+int diff_index_chunk(const DiffIndex &ix, const uint8_t *news, const int64_t *noff, int32_t first, int32_t cnt, bool framing,
+                     DeviceBuf &buf, std::vector<ManyPair> &out, ManyChunk &k, int more, int64_t *device_us, Launch launch)
 {
     const int dev = ix.dev;
     HIP_TRY(hipSetDevice(dev));
@@ -2132,19 +2248,19 @@ int diff_index_chunk(const DiffIndex &ix, const uint8_t *news, const int64_t *no
     // ---- 3. - 5. on the host and in the shared block sort
     const ManyFiles files{ix.old, nullptr, ix.n, news, noff + first};
     FinishStats fin;
-    const int done = diff_many_finish(files, k, dev, out, fin);
+    const int done = diff_many_finish(files, k, dev, framing, out, fin);
     book_finish(t_index_many_info, fin);
     return done;
 }
 
 // ... none above kIndexManyMax bytes: one launch of anchor_index_many_kernel
-int diff_index_many_chunk(const DiffIndex &ix, const uint8_t *news, const int64_t *noff, int32_t first, int32_t cnt, DeviceBuf &buf,
-                          std::vector<ManyPair> &out)
+int diff_index_many_chunk(const DiffIndex &ix, const uint8_t *news, const int64_t *noff, int32_t first, int32_t cnt, bool framing,
+                          DeviceBuf &buf, std::vector<ManyPair> &out)
 {
     const int threads = flags().index_many_threads.value_or(kIndexManyThreads);
     if (threads != 256 && threads != 512) return fail(DQ_ERR_BAD_ARGS, "DQ_INDEX_MANY_THREADS is 256 or 512");
     ManyChunk k;
-    return diff_index_chunk(ix, news, noff, first, cnt, buf, out, k, 0, &t_index_many_info.anchor_us,
+    return diff_index_chunk(ix, news, noff, first, cnt, framing, buf, out, k, 0, &t_index_many_info.anchor_us,
                             [&](DeviceCtx &c, hipStream_t st, Launcher &L) -> int {
         auto launch = [&](auto width) -> int {
             constexpr int kThreads = decltype(width)::value;
@@ -2164,12 +2280,12 @@ int diff_index_many_chunk(const DiffIndex &ix, const uint8_t *news, const int64_
 }
 
 // ... all of kIndexManyMax + 1 .. kIndexLargeMax bytes: one launch of anchor_index_large_kernel
-int diff_index_large_chunk(const DiffIndex &ix, const uint8_t *news, const int64_t *noff, int32_t first, int32_t cnt, DeviceBuf &buf,
-                           std::vector<ManyPair> &out)
+int diff_index_large_chunk(const DiffIndex &ix, const uint8_t *news, const int64_t *noff, int32_t first, int32_t cnt, bool framing,
+                           DeviceBuf &buf, std::vector<ManyPair> &out)
 {
     ManyChunk k;
     int64_t us = 0;
-    const int rc = diff_index_chunk(ix, news, noff, first, cnt, buf, out, k, 1, &us,
+    const int rc = diff_index_chunk(ix, news, noff, first, cnt, framing, buf, out, k, 1, &us,
                                     [&](DeviceCtx &c, hipStream_t st, Launcher &L) -> int {
         const auto kernel = anchor_index_large_kernel<(int)kIndexLargeMax, kIndexLargeThreads>;
         const int grid = std::min<int>(cnt, resident_groups(&c.anchor_index_large_groups, (const void *)kernel, kIndexLargeThreads, ix.dev));
@@ -2187,22 +2303,14 @@ int diff_index_large_chunk(const DiffIndex &ix, const uint8_t *news, const int64
     t_index_large_info.positions_built += positions_built(k);
     return DQ_OK;
 }
-}  // namespace
 
-int diff_index_many(const void *index, const uint8_t *news, const int64_t *noff, int32_t count, uint8_t *patches, const int64_t *poff,
-                    int64_t *plens)
+// The body of dq_bsdiff_index_diff_many and of dq_bsdiff_index_scan_many, behind their argument checks: one planner,
+// whatever the sink (PatchSink / RawSink above).
+template <typename Sink>
+int diff_index_files(const void *index, const uint8_t *news, const int64_t *noff, int32_t count, const Sink &sink)
 {
-    t_index_many_info = {};
-    t_index_large_info = {};
-    if (!index) return fail(DQ_ERR_BAD_ARGS, "null index");
-    if (count < 0) return fail(DQ_ERR_BAD_ARGS, "negative count");
-    if (count == 0) return DQ_OK;
-    if (!news || !noff || !patches || !poff || !plens) return fail(DQ_ERR_BAD_ARGS, "null buffer");
-    const int checked = many_check_offsets(nullptr, noff, poff, count, plens);
-    if (checked != DQ_OK) return checked;
     const DiffIndex *ix = static_cast<const DiffIndex *>(index);
 
-    auto deliver = [&](int32_t j, const std::vector<uint8_t> &patch) { return many_deliver(patch, j, patches, poff, plens); };
     const bool one_by_one = flags().no_index_many.value_or(0) != 0;
     const int64_t many_min = flags().index_many_min.value_or(kIndexManyMin);
     const bool large_on = !one_by_one && flags().no_index_large.value_or(0) == 0 && (kIndexLargeOn || flags().index_large_min.has_value());
@@ -2217,9 +2325,16 @@ int diff_index_many(const void *index, const uint8_t *news, const int64_t *noff,
     std::vector<ManyPair> done;
     auto single = [&](int32_t j) -> int {
         // the one-file path, into the file's slot (it reports under its own dq_last_diff_info)
-        std::vector<uint8_t> patch;
-        int r = diff_index_diff(index, news + noff[j], noff[j + 1] - noff[j], patch);
-        if (r == DQ_OK) r = deliver(j, patch);
+        int r;
+        if constexpr (Sink::kFraming) {
+            std::vector<uint8_t> patch;
+            r = diff_index_diff(index, news + noff[j], noff[j + 1] - noff[j], patch);
+            if (r == DQ_OK) r = sink.deliver(j, patch);
+        } else {
+            bsdiff::RawStreams raw;
+            r = diff_index_raw(index, news + noff[j], noff[j + 1] - noff[j], raw);
+            if (r == DQ_OK) r = sink.deliver(j, raw);
+        }
         if (r == DQ_OK) t_index_many_info.single_files += 1;
         return r;
     };
@@ -2232,11 +2347,12 @@ int diff_index_many(const void *index, const uint8_t *news, const int64_t *noff,
             if (large && rc == DQ_OK) t_index_large_info.large_single += e - i;
             return rc;
         }
-        rc = large ? diff_index_large_chunk(*ix, news, noff, i, e - i, buf, done) : diff_index_many_chunk(*ix, news, noff, i, e - i, buf, done);
+        rc = large ? diff_index_large_chunk(*ix, news, noff, i, e - i, Sink::kFraming, buf, done)
+                   : diff_index_many_chunk(*ix, news, noff, i, e - i, Sink::kFraming, buf, done);
         if (rc != DQ_OK) return rc;
         t_index_many_info.shared_files += e - i;
         if (large) t_index_large_info.large_files += e - i;
-        for (int32_t j = i; j < e && rc == DQ_OK; ++j) rc = deliver(j, done[(size_t)(j - i)].patch);
+        for (int32_t j = i; j < e && rc == DQ_OK; ++j) rc = sink.deliver(j, done[(size_t)(j - i)]);
         return rc;
     };
     static_assert(kIndexManyMax <= kDiffManyChunkBytes && kIndexLargeMax <= kIndexLargeChunkBytes,
@@ -2248,6 +2364,38 @@ int diff_index_many(const void *index, const uint8_t *news, const int64_t *noff,
                      },
                      single, run);
 }
+}  // namespace
+
+int diff_index_many(const void *index, const uint8_t *news, const int64_t *noff, int32_t count, uint8_t *patches, const int64_t *poff,
+                    int64_t *plens)
+{
+    t_index_many_info = {};
+    t_index_large_info = {};
+    if (!index) return fail(DQ_ERR_BAD_ARGS, "null index");
+    if (count < 0) return fail(DQ_ERR_BAD_ARGS, "negative count");
+    if (count == 0) return DQ_OK;
+    if (!news || !noff || !patches || !poff || !plens) return fail(DQ_ERR_BAD_ARGS, "null buffer");
+    const int checked = many_check_offsets(nullptr, noff, poff, count, plens);
+    if (checked != DQ_OK) return checked;
+    return diff_index_files(index, news, noff, count, PatchSink{patches, poff, plens});
+}
+
+// dq_bsdiff_index_scan_many: dq_bsdiff_index_diff_many as far as the raw streams (the records are that call's)
+int diff_index_scan_many(const void *index, const uint8_t *news, const int64_t *noff, int32_t count, int64_t *ctrl, const int64_t *coff,
+                         int64_t *nctrl, uint8_t *bytes, int64_t *ndiff, int64_t *searches)
+{
+    t_index_many_info = {};
+    t_index_large_info = {};
+    if (!index) return fail(DQ_ERR_BAD_ARGS, "null index");
+    if (count < 0) return fail(DQ_ERR_BAD_ARGS, "negative count");
+    if (count == 0) return DQ_OK;
+    if (!news || !noff || !ctrl || !coff || !nctrl || !bytes || !ndiff) return fail(DQ_ERR_BAD_ARGS, "null buffer");
+    const int checked = many_check_offsets(nullptr, noff, coff, count, nctrl);
+    if (checked != DQ_OK) return checked;
+    return diff_index_files(index, news, noff, count, RawSink{noff, ctrl, coff, nctrl, bytes, ndiff, searches});
+}
+
+int64_t bsdiff_ctrl_bound(int64_t m) { return m < 0 ? -1 : diff_many_anchor_room(m); }
 
 void diff_index_delete(void *index)
 {

@@ -511,6 +511,10 @@ int bsdiff_scan_raw(const uint8_t *old, int64_t n, const uint8_t *nw, int64_t m,
 int bsdiff_create_host(const uint8_t *old, int64_t n, const uint8_t *nw, int64_t m, int32_t device, std::vector<uint8_t> &patch);
 int bsdiff_create_many_host(const uint8_t *olds, const int64_t *old_offsets, const uint8_t *news, const int64_t *new_offsets, int32_t count,
                             uint8_t *patches, const int64_t *patch_offsets, int64_t *patch_lens, int32_t device);
+int bsdiff_scan_many_host(const uint8_t *olds, const int64_t *old_offsets, const uint8_t *news, const int64_t *new_offsets, int32_t count,
+                          int64_t *ctrl, const int64_t *ctrl_offsets, int64_t *nctrl, uint8_t *bytes, int64_t *ndiff, int64_t *searches,
+                          int32_t device);
+int64_t bsdiff_ctrl_bound(int64_t m);
 int bspatch_apply_host(const uint8_t *old, int64_t n, const uint8_t *patch, int64_t plen, uint8_t *out, int64_t cap, int64_t *out_len);
 int diff_index_new(const uint8_t *old, int64_t n, int32_t device, const void *d_old, const void *d_sa, void **index_out);
 int diff_index_clone(const void *index, int32_t device, void **index_out);
@@ -518,6 +522,10 @@ int diff_index_buffers(const void *index, const void **d_old, const void **d_sa,
 int diff_index_diff(const void *index, const uint8_t *nw, int64_t m, std::vector<uint8_t> &patch);
 int diff_index_many(const void *index, const uint8_t *news, const int64_t *new_offsets, int32_t count, uint8_t *patches,
                     const int64_t *patch_offsets, int64_t *patch_lens);
+int diff_index_scan_one(const void *index, const uint8_t *nw, int64_t m, int64_t *ctrl, int64_t ctrl_cap, int64_t *nctrl, uint8_t *bytes,
+                        int64_t *ndiff, int64_t *stats);
+int diff_index_scan_many(const void *index, const uint8_t *news, const int64_t *new_offsets, int32_t count, int64_t *ctrl,
+                         const int64_t *ctrl_offsets, int64_t *nctrl, uint8_t *bytes, int64_t *ndiff, int64_t *searches);
 void diff_index_delete(void *index);
 
 }  // namespace dq

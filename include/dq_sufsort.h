@@ -277,6 +277,57 @@ int32_t dq_bsdiff_index_diff_many(const void *index, const uint8_t *news, const 
 int32_t dq_bsdiff_scan_i32(const uint8_t *old_data, int64_t n, const uint8_t *new_data, int64_t m, int64_t *ctrl,
                            int64_t ctrl_cap, int64_t *nctrl, uint8_t *diff, int64_t *ndiff, uint8_t *extra, int64_t *nextra,
                            int64_t *stats, int32_t device);
+
+/* ---- the RAW streams of many diffs in shared launches (the delta before bzip2, for another container or compressor, or
+ * for choosing the best base by delta size) ---------------------------------------------------------------------------
+ * bzip2 is the reference's choice in one place (Diff.cs:15-18, GetEncodingStream); everything before it is the output of
+ * its scan loop: control triples (add, copy, seek), diff bytes, extra bytes.  dq_bsdiff_scan_i32 above returns them for
+ * one pair; these calls are dq_bsdiff_create_many, dq_bsdiff_index_diff and dq_bsdiff_index_diff_many as far as those
+ * streams.  There is no planner of their own: a file goes EXACTLY the way it goes in the framing call of the same
+ * arguments -- the same classes, chunks and thresholds (16 medium pairs in a chunk, 64 neighbouring large pairs; 32 and 64
+ * neighbouring new files against an index), the same five anchor kernels, the same debug flags -- and the call stops behind
+ * the host threads that turn anchors into streams: no bzip2 block is made, sorted or framed.
+ * Inputs are laid out as in dq_bsdiff_create_many / dq_bsdiff_index_diff_many.  Outputs:
+ *   ctrl, ctrl_offsets, nctrl   ctrl_offsets[count + 1] counts in TRIPLES (ctrl_offsets[0] == 0, never decreasing): file j
+ *                               owns ctrl[3 * ctrl_offsets[j] .. 3 * ctrl_offsets[j + 1]); nctrl[j] receives its number of
+ *                               triples, stored as plain int64 (add, copy, seek) as dq_bsdiff_scan_i32 stores them.
+ *                               dq_bsdiff_ctrl_bound(m_j) = m_j / 8 + 2 triples always suffice (-1 for m < 0): every triple
+ *                               but the last stands on a match of more than 8 bytes and the scan moves on behind it.  It
+ *                               is the room the anchor kernels themselves are given per file.
+ *   bytes, ndiff                `bytes` has the layout of `news` -- the same offsets, the same total: file j's diff bytes
+ *                               are bytes[new_offsets[j] .. + ndiff[j]), its extra bytes lie right behind them up to
+ *                               new_offsets[j + 1].  No capacity is asked for: every byte of a new file is in exactly one of
+ *                               the two streams, ndiff[j] + nextra[j] == m_j (a file for which that did not hold would be
+ *                               an internal error, DQ_ERR_HIP, and is not written).
+ *   searches                    may be NULL; otherwise searches[j] = Search calls of the reference's loop (Diff.cs:106).
+ * Nothing outside a file's own slots is written.  For pairs the result of file j is exactly what dq_bsdiff_scan_i32(old_j,
+ * new_j) returns, for the index forms what dq_bsdiff_scan_i32(the index's old file, new_j) returns, whichever way the
+ * file went; files of 0 bytes on either side are allowed (0 triples, 0 bytes).
+ *   dq_bsdiff_index_scan        the one-file index form: dq_bsdiff_index_diff without its framing, thread-safe like it
+ *                               (scan loops of concurrent callers take turns on the device).  ctrl takes ctrl_cap triples,
+ *                               bytes m bytes; stats (optional) 3 entries as dq_bsdiff_scan_i32's.
+ * Errors, all before any device use: a NULL index, count < 0, a NULL pointer with count > 0 (searches excepted),
+ * offsets[0] != 0 or decreasing offsets in any array -> DQ_ERR_BAD_ARGS; a file of 2^31 bytes or more -> DQ_ERR_TOO_LARGE.
+ * count == 0 is a no-op.  Behind those checks every nctrl[j] is set to -1.  A control slot too small for its triples ->
+ * DQ_ERR_BAD_ARGS ("output buffer too small"), known only once the triples are.  The first failing file's code is
+ * returned: files before it are delivered, nctrl of the others reads -1.
+ * Records: none of their own.  A scan call resets and fills the records of its framing twin -- dq_last_diff_many_info and
+ * dq_last_diff_large_info for pairs, dq_last_index_many_info and dq_last_index_large_info for the index forms -- with the
+ * block-sort counts and the microseconds of block sorts and framing left 0.  dq_bsdiff_scan_many resets and fills
+ * dq_last_many_info through its sort of the old files; dq_bsdiff_index_scan_many resets it and leaves it zero.  A file
+ * that goes one by one leaves its dq_last_diff_info behind.
+ * Footprint per chunk -- device: as the framing twin's; host: the raw streams of one chunk, held until they are delivered
+ * -- at most the chunk's new bytes plus 24 bytes per triple -- and nothing of the twin's blocks and suffix arrays.
+ * New API: the reference has no call that stops before its encoding streams. */
+int64_t dq_bsdiff_ctrl_bound(int64_t m);
+int32_t dq_bsdiff_scan_many(const uint8_t *olds, const int64_t *old_offsets, const uint8_t *news, const int64_t *new_offsets,
+                            int32_t count, int64_t *ctrl, const int64_t *ctrl_offsets, int64_t *nctrl,
+                            uint8_t *bytes, int64_t *ndiff, int64_t *searches, int32_t device);
+int32_t dq_bsdiff_index_scan(const void *index, const uint8_t *new_data, int64_t m, int64_t *ctrl, int64_t ctrl_cap,
+                             int64_t *nctrl, uint8_t *bytes, int64_t *ndiff, int64_t *stats);
+int32_t dq_bsdiff_index_scan_many(const void *index, const uint8_t *news, const int64_t *new_offsets, int32_t count,
+                                  int64_t *ctrl, const int64_t *ctrl_offsets, int64_t *nctrl,
+                                  uint8_t *bytes, int64_t *ndiff, int64_t *searches);
 int32_t dq_bspatch_apply(const uint8_t *old_data, int64_t n, const uint8_t *patch, int64_t patch_len, uint8_t *out,
                          int64_t cap, int64_t *out_len);
 
@@ -419,7 +470,8 @@ int32_t dq_last_sort_info(int64_t *rounds, int64_t *initial_active, int64_t *sum
  * emitter threads. */
 int32_t dq_last_diff_info(int64_t *info, int32_t count);
 
-/* Shape of the last dq_bsdiff_create_many on this thread, `count` entries (12 are defined, further ones read 0): pairs
+/* Shape of the last dq_bsdiff_create_many (or dq_bsdiff_scan_many, which leaves the block-sort and framing entries 0) on
+ * this thread, `count` entries (12 are defined, further ones read 0): pairs
  * that went through the shared launches, short and medium; pairs diffed one by one; launches of anchor_many_kernel (the
  * short pairs' kernel only); bzip2 blocks whose transform went through a shared sort of the short classes (doubled
  * length up to 8192); bzip2 blocks of doubled length above 8192, whether they shared a medium launch or were sorted
@@ -428,7 +480,7 @@ int32_t dq_last_diff_info(int64_t *info, int32_t count);
  * launches (counted in [0] too); [11] launches of anchor_mid_many_kernel. */
 int32_t dq_last_diff_many_info(int64_t *info, int32_t count);
 
-/* The large class (pairs whose longer file has 65 537 .. 524 288 bytes) of the last dq_bsdiff_create_many on this thread,
+/* The large class (pairs whose longer file has 65 537 .. 524 288 bytes) of the last dq_bsdiff_create_many / dq_bsdiff_scan_many on this thread,
  * reset when such a call starts; `count` entries (6 are defined, further ones read 0; a NULL array is DQ_ERR_BAD_ARGS):
  * [0] pairs that went through launches of anchor_pair_large_kernel (counted in dq_last_diff_many_info's [0] too); [1]
  * those launches; [2] pairs of the class diffed one by one because fewer than the threshold followed one another
@@ -437,13 +489,14 @@ int32_t dq_last_diff_many_info(int64_t *info, int32_t count);
  * old files of large chunks (part of its [5]). */
 int32_t dq_last_diff_large_info(int64_t *info, int32_t count);
 
-/* Shape of the last dq_bsdiff_index_diff_many on this thread, reset when such a call starts; `count` entries (9 are
+/* Shape of the last dq_bsdiff_index_diff_many (or dq_bsdiff_index_scan_many, which leaves the block-sort and framing
+ * entries 0) on this thread, reset when such a call starts; `count` entries (9 are
  * defined, further ones read 0; a NULL array is DQ_ERR_BAD_ARGS): new files that went through shared launches; files
  * diffed one by one; launches of anchor_index_many_kernel; bzip2 blocks sorted in shared launches; blocks sorted singly;
  * [5..8] microseconds in each phase: copies + anchor kernel, host emission, block sorts, host framing. */
 int32_t dq_last_index_many_info(int64_t *info, int32_t count);
 
-/* The large class (new files of 65 537 .. 524 288 bytes) of the last dq_bsdiff_index_diff_many on this thread, reset when
+/* The large class (new files of 65 537 .. 524 288 bytes) of the last dq_bsdiff_index_diff_many / dq_bsdiff_index_scan_many on this thread, reset when
  * such a call starts; `count` entries (5 are defined, further ones read 0; a NULL array is DQ_ERR_BAD_ARGS): [0] files
  * that went through launches of anchor_index_large_kernel (counted in dq_last_index_many_info's [0] too); [1] those
  * launches; [2] files of the class diffed one by one because fewer than the threshold followed one another (counted
@@ -452,7 +505,7 @@ int32_t dq_last_index_many_info(int64_t *info, int32_t count);
 int32_t dq_last_index_large_info(int64_t *info, int32_t count);
 
 /* Shape of the shared sorts of the last outermost dq_sufsort_hip_many_i32 / _many_dev_i32 / dq_sufsort_hip_batch_i32 /
- * dq_bsdiff_create_many / dq_bsdiff_index_diff_many on this thread, summed over every shared sort that call made and reset when such a call
+ * dq_bsdiff_create_many / dq_bsdiff_index_diff_many / dq_bsdiff_scan_many / dq_bsdiff_index_scan_many on this thread, summed over every shared sort that call made and reset when such a call
  * starts; `count` entries (9 are defined, further ones read 0; a NULL array is DQ_ERR_BAD_ARGS): texts sorted in the
  * short classes' launches; texts sorted in medium launches; texts of 8193 .. 65 536 bytes sorted singly (fewer than the
  * threshold in their call or chunk, or the medium class switched off); texts above 65 536 bytes sorted singly; launches
