@@ -341,16 +341,37 @@ struct Round0 {
         }
         uint64_t *Ks = K[b.bbytes & 1], *Kfree = K[(b.bbytes & 1) ^ 1];       // sorted words / the other buffer
         const uint8_t *Es = b.ext ? E[b.bbytes & 1] : nullptr;
-        LAUNCH(L, DQ_K_BUCKET_SORT, b.ntiles, b.ntiles * 16 * 8,
-               hipLaunchKernelGGL(bucket_bounds_kernel, dim3((unsigned)((b.ntiles + 1 + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                                  st, (const uint64_t *)Ks, n, ib + lowbits, b.C, b.X, b.ntiles, w.bkt_bounds, bflags));
-        DQ_TRY(with_bool(b.ext, [&](auto kExt) -> int {
-            LAUNCH(L, DQ_K_BUCKET_SORT, n, n * ((b.ext ? 9 : 8) + wb) + n / 8,              // persistent: one workgroup per CU
-                   hipLaunchKernelGGL((bucket_sort_kernel<IdxT, decltype(kExt)::value>), dim3((unsigned)std::min<int64_t>(b.ntiles, c.ncu)),
-                                      dim3(kBktThreads), 0, st, (const uint64_t *)Ks, ib, lowbits,
-                                      (const int64_t *)w.bkt_bounds, b.ntiles, d_sa, ebits, bflags, Es));
+        // the finish kernel's tiles and geometry (plan_finish_tiles): cut every Cf words at a bucket boundary, or every g buckets
+        const FinishTiles ft = plan_finish_tiles(b, n, F);
+        if (F.trace)
+            fprintf(stderr, "[dq] bucket finish: %s geometry, %lld tiles of up to %lld words cut every %lld %s (n=%lld)\n", ft.fine ? "fine" : "coarse",
+                    (long long)ft.ntiles, (long long)ft.cap, (long long)(ft.by_id ? ft.g : ft.Cf), ft.by_id ? "buckets" : "words", (long long)n);
+        if ((size_t)ft.ntiles + 1 > finish_bounds_entries(n)) return fail(DQ_ERR_HIP, "tile bounds buffer too small");
+        if (ft.by_id) {
+            const int64_t nbuckets = (int64_t)1 << (8 * b.bbytes);
+            LAUNCH(L, DQ_K_BUCKET_SORT, ft.ntiles, ft.ntiles * 16 * 8,
+                   hipLaunchKernelGGL(bucket_bounds_by_id_kernel, dim3((unsigned)((nbuckets + 1 + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+                                      st, (const uint64_t *)Ks, n, ib + lowbits, ft.g, b.X, nbuckets, ft.ntiles, w.bkt_bounds, bflags));
+        } else {
+            LAUNCH(L, DQ_K_BUCKET_SORT, ft.ntiles, ft.ntiles * 16 * 8,
+                   hipLaunchKernelGGL(bucket_bounds_kernel, dim3((unsigned)((ft.ntiles + 1 + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+                                      st, (const uint64_t *)Ks, n, ib + lowbits, ft.Cf, b.X, ft.ntiles, w.bkt_bounds, bflags));
+        }
+        auto finish = [&](auto kExt, auto geometry) -> int {
+            using G = decltype(geometry);
+            auto kernel = bucket_sort_kernel<IdxT, decltype(kExt)::value, G>;
+            // persistent: as many workgroups as the device holds at once (coarse: one per CU, fine: two)
+            const int groups = resident_groups(&c.bkt_groups[ft.fine][b.ext][sizeof(IdxT) == 8], (const void *)kernel, G::threads, c.dev);
+            LAUNCH(L, DQ_K_BUCKET_SORT, n, n * ((b.ext ? 9 : 8) + wb) + n / 8,
+                   hipLaunchKernelGGL(kernel, dim3((unsigned)std::min<int64_t>(ft.ntiles, groups)), dim3(G::threads), 0, st,
+                                      (const uint64_t *)Ks, ib, lowbits, (const int64_t *)w.bkt_bounds, ft.ntiles, d_sa, ebits, bflags, Es));
             return DQ_OK;
-        }));
+        };
+        if (ft.fine) {                                       // (plan_finish_tiles: never with the extra key byte)
+            DQ_TRY(finish(std::false_type{}, BktFine{}));
+        } else {
+            DQ_TRY(with_bool(b.ext, [&](auto kExt) -> int { return finish(kExt, BktCoarse{}); }));
+        }
         if (b.ext && F.trace) fprintf(stderr, "[dq] bucketed round 0 with %d + 8 key bits per suffix (n=%lld)\n", keybits, (long long)n);
         bool overflow = false;
         DQ_TRY(collect_ties(ebits, nullptr, Kfree, &overflow, Ks, /*seams=*/false, b.hb));

@@ -16,6 +16,7 @@ namespace dq {
 
 constexpr int kKgramSamples = 1024;            // suffixes text_hist_kernel samples for repetition (dq_onesweep.h, sample_kgrams)
 constexpr int kBktCap = 12288;                 // words per tile of the bucketed round 0 at most (dq_bucket_sort.h)
+constexpr int kBktCapFine = 6144;              // ... of its fine geometry: two workgroups per CU, half the tile each
 constexpr int kSplitTop = 512;                 // sample-sort round 0 (dq_split_round0.h): top buckets = regions of pass A
 constexpr int kSplitSub = 512;                 // parts of a top bucket = regions of pass B
 constexpr int kSplitBuckets = kSplitTop * kSplitSub;             // 262 144: a 256 MiB text has 1024 suffixes per bucket
@@ -196,6 +197,57 @@ inline BucketPlan plan_bucketed(const TextStats &s, const Flags &F, KeyPlan k, b
     p.xcd_pass = !p.ext && !F.old_first_pass;
     p.hb = (keybits + (p.ext ? 8 : 0)) / 8;
     return p;
+}
+
+// The tiles of the finish kernel (bucket_sort_kernel).  BucketPlan's X, C and ntiles describe the coarse geometry -- one
+// 1024-thread workgroup per CU on tiles of up to kBktCap words; the fine geometry runs two 512-thread workgroups per CU on
+// tiles of up to kBktCapFine words.  With Cf = cap - X words of a tile's room left beside its longest bucket:
+//   Cf >= X   tile t starts at the first bucket boundary at or after t * Cf (bucket_bounds_kernel).  Every window of Cf
+//             words holds a boundary while no bucket exceeds X, so no tile is empty.
+//   Cf <  X   that cut would leave most tiles empty (X = 4608, cap = 6144: 62 % of them), so tile j holds the g = cap / X
+//             buckets [j * g, (j + 1) * g) instead (bucket_bounds_by_id_kernel).  g <= 64: a tile's keys take 26 bits.
+//             (Cf < X means cap < 2 X, so g == 1 is the only value that occurs with these capacities, and fine tiles
+//             have 2-byte buckets, so there are 65 536 of them; g and the bucket count are kept general for another capacity.)
+// Fine: 2-byte buckets without the extra key byte (whose fetch has no register room at two workgroups per CU), where the
+// path runs unforced, from kBktFineMinN on -- see there.  DQ_BUCKET_TILE = 0 | 1 overrides, forced small inputs included.
+constexpr int64_t kBktFineMinN = 12ll << 20;
+struct FinishTiles {
+    bool fine = false;
+    bool by_id = false;                         // the cut: false = every Cf words, true = every g buckets
+    int64_t cap = 0;                            // words per tile at most
+    int64_t Cf = 0, g = 0;                      // words per tile nominally / buckets per tile (the other is 0)
+    int64_t ntiles = 0;
+};
+
+inline FinishTiles plan_finish_tiles(const BucketPlan &b, int64_t n, const Flags &F)
+{
+    FinishTiles t;
+    if (!b.applies) return t;
+    const bool can = b.bbytes == 2 && !b.ext;
+    t.fine = can && (F.bucket_tile ? *F.bucket_tile != 0 : !F.bucket.has_value() && n >= kBktFineMinN);
+    t.cap = t.fine ? kBktCapFine : kBktCap;
+    const int64_t Cf = t.cap - b.X;
+    if (Cf >= b.X) {
+        t.Cf = Cf;
+        t.ntiles = (n + Cf - 1) / Cf;
+    } else {
+        t.by_id = true;
+        t.g = std::min<int64_t>(t.cap / b.X, 64);
+        const int64_t nbuckets = (int64_t)1 << (8 * b.bbytes);
+        t.ntiles = (nbuckets + t.g - 1) / t.g;
+    }
+    return t;
+}
+
+// entries of the workspace's tile bounds (ntiles + 1 of them are used): the tiles of either geometry under either cut --
+// X <= 5120, so the coarse Cf >= 7168; a fine tile cut by words has Cf >= 3072; one cut by bucket id is a 2-byte bucket at least.
+// The cost: every workspace of a text of kRound0MinN bytes or more carries at least 512 KiB of bounds, whichever cut its
+// sort takes.  Shorter texts get no room for the bucket-id cut and need none: plan_bucketed refuses n < kRound0MinN (a
+// by-id request that did arrive there would be answered with an error by the driver, not written out of bounds).
+inline size_t finish_bounds_entries(int64_t n)
+{
+    const size_t by_words = (size_t)n / (kBktCapFine / 2) + 4;
+    return n < kRound0MinN ? by_words : std::max<size_t>(by_words, 65536 + 4);
 }
 
 // Packed words were chosen because few ties are expected: the last pass then records the tie structure itself (1 bit per

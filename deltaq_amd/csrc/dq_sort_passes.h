@@ -95,7 +95,7 @@ Workspace<IdxT> carve(char *base, int64_t n, bool with_sa, bool lists)
         w.X = (uint64_t *)take((un + 2) * 8);
         w.Xs = (IdxT *)take((un + 2) * sizeof(IdxT));
     }
-    w.bkt_bounds = (int64_t *)take((un / 4096 + 4) * 8);
+    w.bkt_bounds = (int64_t *)take(finish_bounds_entries(n) * 8);
     w.totals = (int64_t *)take(64);
     w.sg_ctr = (SmallGroupCounters *)take((kSgChain + 2) * sizeof(SmallGroupCounters));     // (+ the tail kernel's result, dq_tail.h)
     w.hist_partial = (uint32_t *)take((size_t)kHistBlocks * kMaxPasses * kRadixSize * 4);

@@ -1,9 +1,10 @@
 // bsort.hip -- developer micro-benchmark for bucket_sort_kernel (not part of the product).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/kbench/bsort.hip -o tools/kbench/bsort
-//   tools/kbench/bsort [log2_n=26] [X=1536]
+//   tools/kbench/bsort [log2_n=28] [X=4608] [repetitions=7]
 // Input: n words (key36 << ib | suffix) with uniformly random keys, already grouped by their top 16 key bits
-// (what the two digit passes of the bucketed round 0 leave).  Prints the kernel time and, with phase stamps
-// compiled in, the average time a workgroup spends in each phase.
+// (what the two digit passes of the bucketed round 0 leave).  Runs the shipped geometry and the candidates in one
+// process, alternating: prints the fastest and the slowest repetition of each and, from one more launch with the phase
+// stamps switched on, the average time a workgroup spends in each phase.  The tiles are cut as plan_finish_tiles cuts them.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdio>
@@ -29,45 +30,105 @@ __global__ void gen_kernel(uint64_t *w, int64_t n, int ib)
     }
 }
 
+__global__ void check_kernel(const uint64_t *w, const int32_t *sa, int64_t n, int ib, unsigned long long *bad)
+{
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x + 1; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const uint32_t a = (uint32_t)sa[i - 1], b = (uint32_t)sa[i];
+        if (a >= (uint64_t)n || b >= (uint64_t)n || (w[a] >> ib) > (w[b] >> ib)) atomicAdd(bad, 1ull);   // suffix index == word position here
+    }
+}
+
+struct Bench {
+    int64_t n, X; int ib, lowbits, ncu;
+    uint64_t *W; int32_t *SA; uint32_t *ebits; int64_t *bounds; BucketFlags *flags; long long *ts; unsigned long long *bad;
+};
+constexpr int64_t kMaxTiles = 1 << 17;
+
+template <typename G>
+struct Runner {
+    const char *name;
+    int64_t ntiles = 0, grid = 0;
+    float lo = 1e9f, hi = 0.f;
+    void bounds(const Bench &B) const
+    {
+        const int64_t Cf = G::cap - B.X;
+        if (Cf >= B.X)
+            hipLaunchKernelGGL(bucket_bounds_kernel, dim3((unsigned)((ntiles + 256) / 256)), dim3(256), 0, 0, (const uint64_t *)B.W, B.n, B.ib + B.lowbits, Cf, B.X, ntiles, B.bounds, B.flags);
+        else
+            hipLaunchKernelGGL(bucket_bounds_by_id_kernel, dim3((65536 + 256) / 256), dim3(256), 0, 0, (const uint64_t *)B.W, B.n, B.ib + B.lowbits, (int64_t)(G::cap / B.X), B.X, (int64_t)65536, ntiles, B.bounds, B.flags);
+    }
+    void init(const Bench &B)
+    {
+        const int64_t Cf = G::cap - B.X;
+        ntiles = Cf >= B.X ? (B.n + Cf - 1) / Cf : (65536 + G::cap / B.X - 1) / (G::cap / B.X);
+        if (ntiles > kMaxTiles) { printf("too many tiles\n"); exit(1); }
+        int per_cu = 0;
+        CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)bucket_sort_kernel<int32_t, false, G>, G::threads, 0));
+        grid = std::min<int64_t>(ntiles, (int64_t)per_cu * B.ncu);
+        hipFuncAttributes fa; CK(hipFuncGetAttributes(&fa, (const void *)bucket_sort_kernel<int32_t, false, G>));
+        printf("%-22s %4d threads x %2d words, cap %5d: %d workgroups per CU, %d VGPRs, scratch %zu B, LDS %zu B, %lld tiles, grid %lld\n", name, G::threads, G::items, G::cap,
+               per_cu, fa.numRegs, (size_t)fa.localSizeBytes, (size_t)fa.sharedSizeBytes, (long long)ntiles, (long long)grid);
+    }
+    void launch(const Bench &B) const
+    {
+        hipLaunchKernelGGL((bucket_sort_kernel<int32_t, false, G>), dim3((unsigned)grid), dim3(G::threads), 0, 0, (const uint64_t *)B.W, B.ib, B.lowbits,
+                           (const int64_t *)B.bounds, ntiles, B.SA, B.ebits, B.flags);
+    }
+    // one timed launch (the bounds kernel is not timed; the geometries share the bounds array)
+    void rep(const Bench &B, hipEvent_t a, hipEvent_t b)
+    {
+        bounds(B);
+        CK(hipEventRecord(a)); launch(B); CK(hipEventRecord(b)); CK(hipEventSynchronize(b));
+        float ms; CK(hipEventElapsedTime(&ms, a, b));
+        lo = std::min(lo, ms); hi = std::max(hi, ms);
+    }
+    void report(const Bench &B)
+    {
+        // correctness, then one launch with the phase stamps on
+        CK(hipMemset(B.SA, 0xff, B.n * 4)); CK(hipMemset(B.bad, 0, 8));
+        bounds(B); launch(B);
+        hipLaunchKernelGGL(check_kernel, dim3(2048), dim3(256), 0, 0, (const uint64_t *)B.W, (const int32_t *)B.SA, B.n, B.ib, B.bad);
+        unsigned long long bad, ov; CK(hipMemcpy(&bad, B.bad, 8, hipMemcpyDeviceToHost)); CK(hipMemcpy(&ov, B.flags, 8, hipMemcpyDeviceToHost));
+        printf("%-22s min %8.1f us  max %8.1f us  spread %5.1f us  (%.1f G elements/s)  order violations %llu%s\n", name, lo * 1e3, hi * 1e3, (hi - lo) * 1e3,
+               B.n / (lo * 1e-3) / 1e9, bad, ov ? "  OVERFLOW" : "");
+        CK(hipMemset(B.ts, 0, kMaxTiles * 16 * 8));
+        CK(hipMemcpyToSymbol(HIP_SYMBOL(g_bkt_ts), &B.ts, sizeof B.ts));
+        launch(B);
+        CK(hipDeviceSynchronize());
+        long long *null = nullptr; CK(hipMemcpyToSymbol(HIP_SYMBOL(g_bkt_ts), &null, sizeof null));
+        std::vector<long long> h(ntiles * 16); CK(hipMemcpy(h.data(), B.ts, ntiles * 16 * 8, hipMemcpyDeviceToHost));
+        double acc[16] = {0}; long long cnt = 0;
+        for (int64_t t = 0; t < ntiles; ++t) { if (!h[t * 16]) continue; ++cnt; for (int i = 1; i < 16; ++i) if (h[t * 16 + i]) acc[i] += (double)(h[t * 16 + i] - h[t * 16 + i - 1]); }
+        const char *nm[16] = {"", "edges + zero bins (words land)", "keys, next fetch, count atomics", "scan", "scatter", "bin walk", "suffix exchange", "store"};
+        for (int i = 1; i < 8; ++i) printf("    phase %-32s avg %9.0f ticks\n", nm[i], cnt ? acc[i] / cnt : 0.0);
+    }
+};
+
 int main(int argc, char **argv)
 {
-    const int lg = argc > 1 ? atoi(argv[1]) : 26;
-    const int64_t X = argc > 2 ? atoll(argv[2]) : 1536;
-    const int64_t grid = argc > 3 ? atoll(argv[3]) : 256;
-    const int64_t n = 1ll << lg;
-    const int ib = lg, lowbits = 20;
-    const int64_t C = kBktCap - X, ntiles = (n + C - 1) / C;
-    uint64_t *W; int32_t *SA; uint32_t *ebits; int64_t *bounds; BucketFlags *flags; long long *ts;
-    CK(hipMalloc(&W, n * 8)); CK(hipMalloc(&SA, n * 4)); CK(hipMalloc(&ebits, n / 8 + 64)); CK(hipMalloc(&bounds, (ntiles + 2) * 8));
-    CK(hipMalloc(&flags, 64)); CK(hipMemset(flags, 0, 64)); CK(hipMemset(ebits, 0, n / 8 + 64));
-    CK(hipMalloc(&ts, ntiles * 16 * 8)); CK(hipMemset(ts, 0, ntiles * 16 * 8));
-    CK(hipMemcpyToSymbol(HIP_SYMBOL(g_bkt_ts), &ts, sizeof ts));
-    hipLaunchKernelGGL(gen_kernel, dim3(2048), dim3(256), 0, 0, W, n, ib);
-    hipLaunchKernelGGL(bucket_bounds_kernel, dim3((unsigned)((ntiles + 256) / 256)), dim3(256), 0, 0, (const uint64_t *)W, n, ib + lowbits, C, X, ntiles, bounds, flags);
+    const int lg = argc > 1 ? atoi(argv[1]) : 28;
+    Bench B;
+    B.X = argc > 2 ? atoll(argv[2]) : 4608;
+    const int reps = argc > 3 ? atoi(argv[3]) : 7;
+    B.n = 1ll << lg; B.ib = lg; B.lowbits = 20;
+    const int64_t n = B.n;
+    CK(hipDeviceGetAttribute(&B.ncu, hipDeviceAttributeMultiprocessorCount, 0));
+    CK(hipMalloc(&B.W, n * 8)); CK(hipMalloc(&B.SA, n * 4)); CK(hipMalloc(&B.ebits, n / 8 + 64)); CK(hipMalloc(&B.bounds, (kMaxTiles + 2) * 8));
+    CK(hipMalloc(&B.flags, 64)); CK(hipMemset(B.flags, 0, 64)); CK(hipMemset(B.ebits, 0, n / 8 + 64)); CK(hipMalloc(&B.bad, 8));
+    CK(hipMalloc(&B.ts, kMaxTiles * 16 * 8));
+    hipLaunchKernelGGL(gen_kernel, dim3(2048), dim3(256), 0, 0, B.W, n, B.ib);
     CK(hipDeviceSynchronize());
-    hipEvent_t a, b; CK(hipEventCreate(&a)); CK(hipEventCreate(&b));
-    float best = 1e9f;
-    for (int r = 0; r < 6; ++r) {
-        CK(hipEventRecord(a));
-        hipLaunchKernelGGL(bucket_sort_kernel<int32_t>, dim3((unsigned)std::min<int64_t>(ntiles, grid)), dim3(kBktThreads), 0, 0, (const uint64_t *)W, ib, lowbits,
-                           (const int64_t *)bounds, ntiles, SA, ebits, flags);
-        CK(hipEventRecord(b)); CK(hipEventSynchronize(b));
-        float ms; CK(hipEventElapsedTime(&ms, a, b)); best = std::min(best, ms);
+    printf("n=2^%d X=%lld, %d CUs, %d repetitions of each, alternating\n", lg, (long long)B.X, B.ncu, reps);
+    Runner<BktCoarse> shipped{"shipped 1024x12"};
+    Runner<BktFine> a{"(a) 512x12"};
+    Runner<BktGeometry<1024, 6, 8>> b{"(b) 1024x6"};
+    shipped.init(B); a.init(B); b.init(B);
+    hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+    for (int r = -1; r < reps; ++r) {                       // (r = -1: a warm-up round, forgotten)
+        shipped.rep(B, e0, e1); a.rep(B, e0, e1); b.rep(B, e0, e1);
+        if (r < 0) { shipped.lo = a.lo = b.lo = 1e9f; shipped.hi = a.hi = b.hi = 0.f; }
     }
     CK(hipGetLastError());
-    unsigned long long ov; CK(hipMemcpy(&ov, flags, 8, hipMemcpyDeviceToHost));
-    printf("n=2^%d X=%lld C=%lld tiles=%lld : %.1f us  (%.1f G elements/s)%s\n", lg, (long long)X, (long long)C, (long long)ntiles, best * 1e3,
-           n / (best * 1e-3) / 1e9, ov ? "  OVERFLOW" : "");
-    std::vector<long long> h(ntiles * 16); CK(hipMemcpy(h.data(), ts, ntiles * 16 * 8, hipMemcpyDeviceToHost));
-    double acc[16] = {0}; long long cnt = 0;
-    for (int64_t t = 0; t < ntiles; ++t) { if (!h[t * 16]) continue; ++cnt; for (int i = 1; i < 16; ++i) if (h[t * 16 + i]) acc[i] += (double)(h[t * 16 + i] - h[t * 16 + i - 1]); }
-    const char *nm[16] = {"", "edges + zero bins (words land)", "keys, next fetch, count atomics", "scan", "scatter", "bin walk", "suffix exchange", "store"};
-    for (int i = 1; i < 8; ++i) printf("  phase %-32s avg %9.0f ticks\n", nm[i], cnt ? acc[i] / cnt : 0.0);
-    // check order on a sample
-    std::vector<uint64_t> hw(n); std::vector<int32_t> hs(n);
-    CK(hipMemcpy(hw.data(), W, n * 8, hipMemcpyDeviceToHost)); CK(hipMemcpy(hs.data(), SA, n * 4, hipMemcpyDeviceToHost));
-    long long bad = 0;
-    for (int64_t i = 1; i < n; ++i) if ((hw[hs[i - 1]] >> ib) > (hw[hs[i]] >> ib)) ++bad;      // suffix index == word position here
-    printf("  order violations: %lld\n", bad);
+    shipped.report(B); a.report(B); b.report(B);
     return 0;
 }
