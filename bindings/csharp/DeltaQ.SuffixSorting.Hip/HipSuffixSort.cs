@@ -34,6 +34,13 @@ public sealed class HipSuffixSort : ISuffixSort
     internal static extern int dq_sufsort_hip_many_dev_i32(IntPtr dTexts, IntPtr dOffsets, int count, IntPtr dSas, int device, IntPtr stream);
 
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    private static extern unsafe int dq_bwt_hip_many(byte* blocks, long* offsets, int count, byte* last, int* origins, int device);
+
+    // (declared for hosts that keep their buffers on the device: device pointers, a hipStream_t or zero)
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern int dq_bwt_hip_many_dev(IntPtr dBlocks, IntPtr dOffsets, int count, IntPtr dLast, IntPtr dOrigins, int device, IntPtr stream);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
     private static extern unsafe int dq_last_many_info(long* info, int count);
 
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
@@ -255,6 +262,71 @@ public sealed class HipSuffixSort : ISuffixSort
         for (int j = 0; j < count; j++)
         {
             result[j] = sas.AsSpan((int)offsets[j], texts[j].Length).ToArray();
+        }
+
+        return result;
+    }
+
+    /// <summary>
+    /// bzip2's block transform of many independent blocks in one native call (dq_bwt_hip_many): doubling, sort and the
+    /// walk over the suffix arrays all stay on the device.  Entry j of the result is the last column of the sorted
+    /// rotations of blocks[j] and the row of the block itself among them (-1 for an empty block) -- what walking the
+    /// suffix array of block + block and keeping the entries below the block's length gives.  Every block must be
+    /// shorter than 2^30 bytes.  The native library has no fallback for this call and neither has this method.
+    /// </summary>
+    public unsafe (byte[] Last, int Origin)[] BwtMany(IReadOnlyList<ReadOnlyMemory<byte>> blocks)
+    {
+        int count = blocks.Count;
+        var result = new (byte[] Last, int Origin)[count];
+        if (count == 0)
+        {
+            return result;
+        }
+
+        var offsets = new long[count + 1];
+        for (int j = 0; j < count; j++)
+        {
+            if (blocks[j].Length >= 1 << 30)
+            {
+                throw new ArgumentException("every block of a BwtMany call must be shorter than 2^30 bytes");
+            }
+
+            offsets[j + 1] = offsets[j] + blocks[j].Length;
+        }
+
+        long total = offsets[count];
+        if (total > Array.MaxLength)
+        {
+            throw new ArgumentException("the blocks of one BwtMany call must total less than 2^31 bytes");
+        }
+
+        // (at least one element each: the native side wants non-null pointers whenever there are blocks)
+        byte[] flat = new byte[Math.Max(total, 1)];
+        byte[] last = new byte[Math.Max(total, 1)];
+        int[] origins = new int[count];
+        for (int j = 0; j < count; j++)
+        {
+            blocks[j].Span.CopyTo(flat.AsSpan((int)offsets[j], blocks[j].Length));
+        }
+
+        int rc;
+        fixed (byte* pBlocks = flat)
+        fixed (long* pOffsets = offsets)
+        fixed (byte* pLast = last)
+        fixed (int* pOrigins = origins)
+        {
+            rc = dq_bwt_hip_many(pBlocks, pOffsets, count, pLast, pOrigins, _device);
+        }
+
+        if (rc != 0)
+        {
+            string msg = Marshal.PtrToStringAnsi(dq_last_error()) ?? string.Empty;
+            throw new InvalidOperationException($"dq_bwt_hip_many failed ({rc}): {msg}");
+        }
+
+        for (int j = 0; j < count; j++)
+        {
+            result[j] = (last.AsSpan((int)offsets[j], blocks[j].Length).ToArray(), origins[j]);
         }
 
         return result;

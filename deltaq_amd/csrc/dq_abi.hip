@@ -408,6 +408,30 @@ int32_t dq_sufsort_hip_many_dev_i32(const void *d_texts, const void *d_offsets, 
     }
 }
 
+int32_t dq_bwt_hip_many(const uint8_t *blocks, const int64_t *offsets, int32_t count, uint8_t *last, int32_t *origins,
+                        int32_t device)
+{
+    EnvScope scope;
+    t_many_info = {};
+    try {
+        return bwt_many_host(blocks, offsets, count, last, origins, device);
+    } catch (const std::bad_alloc &) {
+        return fail(DQ_ERR_OOM, "many: host allocation failed");
+    }
+}
+
+int32_t dq_bwt_hip_many_dev(const void *d_blocks, const void *d_offsets, int32_t count, void *d_last, void *d_origins,
+                            int32_t device, void *stream)
+{
+    EnvScope scope;
+    t_many_info = {};
+    try {
+        return bwt_many_dev(d_blocks, d_offsets, count, d_last, d_origins, device, stream);
+    } catch (const std::bad_alloc &) {
+        return fail(DQ_ERR_OOM, "many: host allocation failed");
+    }
+}
+
 int32_t dq_bsdiff_search_dev_i32(const void *d_old, int64_t n, const void *d_sa, const void *d_new, int64_t m,
                                  const int64_t *d_scans, int64_t scan0, int64_t count, int64_t cap, void *d_pos,
                                  void *d_len, int32_t device, void *stream)
@@ -668,7 +692,7 @@ void dq_sufsort_hip_release(void)
         std::lock_guard<std::mutex> bl(c0.batch_mu);
         std::lock_guard<std::mutex> dl(c0.diff_mu);
         bool any = c0.diff_dev || c0.diff_idx || c0.diff_pinned || c0.bslot_cap;
-        for (int k = 0; k < kCtxSlots; ++k) {
+        for (int k = 0; k <= kBwtSlot; ++k) {
             std::lock_guard<std::mutex> lk(g_dev[d].slot[k].mu);       // (a first use of the slot may be publishing dev right now)
             any = any || g_dev[d].slot[k].dev >= 0;
         }
@@ -687,7 +711,7 @@ void dq_sufsort_hip_release(void)
         if (c0.diff_pinned) (void)hipHostFree(c0.diff_pinned);
         c0.diff_dev = nullptr; c0.diff_idx = nullptr; c0.diff_pinned = nullptr;
         c0.diff_dev_bytes = 0; c0.diff_idx_bytes = 0;
-        for (int k = 0; k < kCtxSlots; ++k) {
+        for (int k = 0; k <= kBwtSlot; ++k) {
             DeviceCtx &c = g_dev[d].slot[k];
             std::lock_guard<std::mutex> lk(c.mu);
             if (c.ws) (void)hipFree(c.ws);

@@ -480,27 +480,21 @@ inline void make_code_lengths(uint8_t *len, const int32_t *freq, int alpha, int 
 using DoubledSorter = std::function<int(const uint8_t *text, int64_t n2, int32_t *sa)>;
 
 // One block, behind its transform: `blk` is the run-length coded data (nblock bytes), crc the CRC of the original bytes
-// it stands for, `sa` the finished suffix array (2 * nblock entries) of block+block, whoever sorted it -- the caller's
-// sorter (compress_block below) or a sort shared with the blocks of other streams (dq_bsdiff_create_many).  Last
-// column, MTF, Huffman tables, bits.  sort_ms: what the transform took (DQ_TRACE prints it).
-inline int compress_block_sorted(BitWriter &bw, const std::vector<uint8_t> &blk, uint32_t crc, const int32_t *sa, double sort_ms = 0)
+// it stands for, `last` the last column of its sorted rotations (nblock bytes) and `origin` the row of the block itself
+// among them (bzip2's origPtr) -- from the host's walk below, or straight from the device (dq_bwt_hip_many:
+// dq_bsdiff_create_many's blocks).  MTF, Huffman tables, bits.  sort_ms / last_ms: what the transform and the walk took
+// (DQ_TRACE prints them).
+inline int compress_block_bwt(BitWriter &bw, const std::vector<uint8_t> &blk, uint32_t crc, const uint8_t *last, int32_t origin,
+                              double sort_ms = 0, double last_ms = 0)
 {
     const int32_t nblock = (int32_t)blk.size();
+    if (origin < 0 || origin >= nblock) return -3;
+    const int32_t orig_ptr = origin;
     const bool trace = flags().trace.has_value();
     auto now = [] { return std::chrono::steady_clock::now(); };
     auto t_prev = now();
-    double t_ph[5] = {sort_ms, 0, 0, 0, 0};                 // sort, last column, MTF, tables, bits
+    double t_ph[5] = {sort_ms, last_ms, 0, 0, 0};           // sort, last column, MTF, tables, bits
     auto lap = [&](int k) { const auto t = now(); t_ph[k] += std::chrono::duration<double, std::milli>(t - t_prev).count(); t_prev = t; };
-    std::vector<uint8_t> last((size_t)nblock);
-    int32_t orig_ptr = -1, row = 0;
-    for (int32_t i = 0; i < 2 * nblock; ++i) {
-        const int32_t s = sa[(size_t)i];
-        if (s >= nblock) continue;
-        if (s == 0) orig_ptr = row;
-        last[(size_t)row++] = blk[(size_t)(s == 0 ? nblock - 1 : s - 1)];
-    }
-    if (row != nblock || orig_ptr < 0) return -3;
-    lap(1);
     // ---- symbols in use, MTF, RUNA / RUNB ----
     bool in_use[256] = {false};
     for (int32_t i = 0; i < nblock; ++i) in_use[blk[(size_t)i]] = true;
@@ -680,6 +674,26 @@ inline int compress_block_sorted(BitWriter &bw, const std::vector<uint8_t> &blk,
                 "done at %.3f ms of the clock\n", nblock, n_mtf, t_ph[0], t_ph[1], t_ph[2], t_ph[3], t_ph[4],
                 std::chrono::duration<double, std::milli>(now().time_since_epoch()).count() - 1e3 * (double)(long long)(std::chrono::duration<double>(now().time_since_epoch()).count() / 100.0) * 100.0);
     return 0;
+}
+
+// ... from the finished suffix array `sa` (2 * nblock entries) of block+block, whoever sorted it -- the caller's sorter
+// (compress_block below) or a sort shared with the blocks of other streams: the last column and the origin row are read
+// off the entries below nblock, then compress_block_bwt.  sort_ms: what the transform took.
+inline int compress_block_sorted(BitWriter &bw, const std::vector<uint8_t> &blk, uint32_t crc, const int32_t *sa, double sort_ms = 0)
+{
+    const int32_t nblock = (int32_t)blk.size();
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<uint8_t> last((size_t)nblock);
+    int32_t orig_ptr = -1, row = 0;
+    for (int32_t i = 0; i < 2 * nblock; ++i) {
+        const int32_t s = sa[(size_t)i];
+        if (s >= nblock) continue;
+        if (s == 0) orig_ptr = row;
+        last[(size_t)row++] = blk[(size_t)(s == 0 ? nblock - 1 : s - 1)];
+    }
+    if (row != nblock || orig_ptr < 0) return -3;
+    return compress_block_bwt(bw, blk, crc, last.data(), orig_ptr, sort_ms,
+                              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
 }
 
 // block+block, the text whose suffix array is the block's Burrows-Wheeler transform: 2 * blk.size() bytes at `out`
@@ -886,6 +900,22 @@ public:
         try {
             BitWriter w(b.bytes);
             b.rc = compress_block_sorted(w, b.rle, b.crc, sa);
+            b.nbits = w.total;
+            w.flush();
+            std::vector<uint8_t>().swap(b.rle);
+        } catch (...) {
+            b.rc = -3;
+        }
+    }
+
+    // ... or its transform itself: the last column (block_rle(i).size() bytes) and the origin row
+    void encode_block_bwt(size_t i, const uint8_t *last, int32_t origin)
+    {
+        Block &b = blocks[i];
+        b.claimed.store(1);
+        try {
+            BitWriter w(b.bytes);
+            b.rc = compress_block_bwt(w, b.rle, b.crc, last, origin);
             b.nbits = w.total;
             w.flush();
             std::vector<uint8_t>().swap(b.rle);

@@ -1405,12 +1405,17 @@ int frame_patch(const bsdiff::RawStreams &raw, int64_t m, int dev, std::vector<u
 //   4. all blocks of all streams of the chunk, doubled and laid back to back: ONE sufsort_many_host call (blocks whose
 //      doubled length exceeds the short-text limit share its medium launches up to kMidMaxN, where there are enough of
 //      them; the others, and every block above kMidMaxN, take that call's own one-by-one route: the segmented sort of
-//      large texts, dq_large_many.h, is off here unless the debug flag DQ_LARGE_MANY_MIN asks for it)
-//   5. host threads: each block finished from its suffix array, header + three streams into the pair's slot.
+//      large texts, dq_large_many.h, is off here unless the debug flag DQ_LARGE_MANY_MIN asks for it).  With the device
+//      transform on (kBwtManyOn, dq_runtime.h: off by default; DQ_NO_BWT_MANY=0) the blocks go up undoubled instead and
+//      ONE bwt_many_host call (dq_bwt_many.h) doubles, sorts -- through the same walker, plan and launches -- and
+//      transforms them on the device.
+//   5. host threads: each block finished from its suffix array (with the device transform: from its last column and
+//      origin row), header + three streams into the pair's slot.
 // Device memory per chunk: old + new + 4 bytes of suffix array per byte of old + one int32 per byte of new for the
 // anchor lists + 40 bytes per pair (< 6 bytes per byte of text), whatever the pairs' classes: the medium kernel reads
 // the suffix arrays where the sort left them and has no scratch blocks.  Host memory per chunk: the raw streams (< 4 bytes
-// per byte of new), their blocks doubled with 4 bytes of suffix array per doubled byte (10 bytes per stream byte).
+// per byte of new), their blocks doubled with 4 bytes of suffix array per doubled byte (10 bytes per stream byte; with
+// the device transform the blocks and their last columns: 2 bytes per stream byte, and 4 per block).
 // The scan calls (dq_bsdiff_scan_many, dq_bsdiff_index_scan_many) run phases 1 - 3 of the same chunks and deliver the raw
 // streams: host memory per chunk is those streams alone, held until they are delivered -- at most the chunk's new bytes
 // plus 24 bytes per triple.
@@ -1617,20 +1622,38 @@ int diff_many_frame(const ManyFiles &f, const ManyChunk &k, int dev, std::vector
                     ++at;
                 }
     }
-    std::vector<uint8_t> btext((size_t)boff.back());
-    std::vector<int32_t> bsa((size_t)boff.back());
+    // With the device transform the blocks go up as they are and come back transformed (dq_bwt_hip_many's body: doubling,
+    // sort and the walk over the suffix arrays stay on the device); otherwise they are doubled here, sorted through
+    // dq_sufsort_hip_many_i32's body and walked by the framing threads.  Either way the same walker cuts the same doubled
+    // lengths into the same chunks and launches.
+    const bool on_device = flags().no_bwt_many ? *flags().no_bwt_many == 0 : kBwtManyOn;
+    const int64_t per = on_device ? 2 : 1;                 // boff counts doubled bytes: a block's place in btext is boff / per
+    std::vector<uint8_t> btext((size_t)(boff.back() / per));
+    std::vector<int32_t> bsa(on_device ? 0 : (size_t)boff.back());
+    std::vector<uint8_t> blast(on_device ? btext.size() : 0);
+    std::vector<int32_t> borigin(on_device ? (size_t)nblocks : 0);
     diff_many_parallel(cnt, [&](int64_t j) {
         ManyPair &w = out[(size_t)j];
         int64_t at = w.first_block;
         for (int s = 0; s < 3; ++s)
-            for (size_t b = 0; b < w.enc[s]->block_count(); ++b)
-                bz2::double_block(w.enc[s]->block_rle(b), btext.data() + boff[(size_t)bplace[(size_t)at++]]);
+            for (size_t b = 0; b < w.enc[s]->block_count(); ++b) {
+                const std::vector<uint8_t> &rle = w.enc[s]->block_rle(b);
+                uint8_t *to = btext.data() + boff[(size_t)bplace[(size_t)at++]] / per;
+                if (!on_device) bz2::double_block(rle, to);
+                else if (!rle.empty()) memcpy(to, rle.data(), rle.size());
+            }
     });
     int64_t shared = 0;
     // Blocks above kMidMaxN doubled bytes reach the planner's large class (dq_large_many.h), but here it stays off unless
     // DQ_LARGE_MANY_MIN asks for it: the block-sort phase has not been measured faster with it than with the one-by-one
     // route, whose sorts get no hint either but run the device sorter's LDS group rounds (docs/ROUNDS.md, round 11).
-    const int rc = sufsort_many_host(btext.data(), boff.data(), (int32_t)nblocks, bsa.data(), dev, &shared, /*large_by_default=*/false);
+    int rc;
+    if (on_device) {
+        std::vector<int64_t> half((size_t)nblocks + 1);
+        for (int64_t b = 0; b <= nblocks; ++b) half[(size_t)b] = boff[(size_t)b] / 2;
+        rc = bwt_many_host(btext.data(), half.data(), (int32_t)nblocks, blast.data(), borigin.data(), dev, &shared, /*large_by_default=*/false);
+    } else
+        rc = sufsort_many_host(btext.data(), boff.data(), (int32_t)nblocks, bsa.data(), dev, &shared, /*large_by_default=*/false);
     if (rc != DQ_OK) return rc;
     std::vector<uint8_t>().swap(btext);
     fin.shared_block_sorts = shared;
@@ -1645,7 +1668,11 @@ int diff_many_frame(const ManyFiles &f, const ManyChunk &k, int dev, std::vector
             int64_t at = w.first_block;
             std::vector<uint8_t> z[3];
             for (int s = 0; s < 3; ++s) {
-                for (size_t b = 0; b < w.enc[s]->block_count(); ++b) w.enc[s]->encode_block_sorted(b, bsa.data() + boff[(size_t)bplace[(size_t)at++]]);
+                for (size_t b = 0; b < w.enc[s]->block_count(); ++b, ++at) {
+                    const int64_t place = bplace[(size_t)at];
+                    if (on_device) w.enc[s]->encode_block_bwt(b, blast.data() + boff[(size_t)place] / 2, borigin[(size_t)place]);
+                    else w.enc[s]->encode_block_sorted(b, bsa.data() + boff[(size_t)place]);
+                }
                 if (w.enc[s]->finish(z[s]) != 0) { w.rc = DQ_ERR_HIP; w.err = "bzip2 block transform failed"; return; }
                 w.enc[s].reset();
             }

@@ -115,6 +115,7 @@ struct DeviceCtx {
     int bkt_groups[2][2][2] = {};       // workgroups of bucket_sort_kernel the device holds at once, [fine][extra key byte][64-bit indices] (0: not asked yet)
     int many_groups[kAllClasses] = {};  // workgroups of each length class of small_many_kernel and mid_many_kernel the device holds at once (0: not asked yet)
     int check_many_groups[kCheckClasses] = {};  // ... and of each length class of sufcheck_many_kernel (dq_sufcheck_many.h)
+    int bwt_many_groups = 0;            // ... and of bwt_many_kernel (dq_bwt_many.h)
     int anchor_many_groups = 0;         // ... and of anchor_many_kernel (dq_anchor_many.h)
     int anchor_mid_many_groups = 0;     // ... and of anchor_mid_many_kernel
     int anchor_index_many_groups[2] = {0, 0};   // ... and of anchor_index_many_kernel at 256 and 512 threads (dq_anchor_many.h)
@@ -165,8 +166,12 @@ constexpr int kCtxSlots = 4;
 constexpr int64_t kSlotSmallN = 4ll << 20;
 constexpr size_t kSmallTextArea = kSmallMaxN + 64;
 constexpr size_t kSmallIoBytes = kSmallTextArea + (size_t)kSmallMaxN * 8;
+// One more context behind the slots belongs to the block transforms of dq_bwt_hip_many* (dq_bwt_many.h): such a call
+// keeps its chunk in that context's workspace while the sorts inside it lease slots of their own, so it is never leased
+// (SlotLease) -- one transform call at a time per device holds its mutex, and takes it before any slot's.
+constexpr int kBwtSlot = kCtxSlots;
 struct DeviceState {
-    DeviceCtx slot[kCtxSlots];
+    DeviceCtx slot[kCtxSlots + 1];
     std::atomic<unsigned> next{0};
 };
 inline DeviceState g_dev[kMaxDevices];
@@ -480,6 +485,22 @@ extern template int64_t sufsort_workspace_plan<int64_t>(int64_t, bool, int64_t);
 int sufsort_many_host(const uint8_t *texts, const int64_t *offsets, int32_t count, int32_t *sas, int32_t device,
                       int64_t *shared_out = nullptr, bool large_by_default = true);
 int sufsort_many_dev(const void *d_texts, const void *d_offsets, int32_t count, void *d_sas, int32_t device, void *stream);
+
+// The Burrows-Wheeler transform of many blocks (dq_bwt_many.h, in dq_sorter_i32.hip): the bodies of dq_bwt_hip_many /
+// _many_dev.  They sort the doubled blocks through the launches above, so they add to t_many_info as those do (the
+// lengths there are the doubled ones); shared_out and large_by_default as sufsort_many_host's.
+int bwt_many_host(const uint8_t *blocks, const int64_t *offsets, int32_t count, uint8_t *last, int32_t *origins, int32_t device,
+                  int64_t *shared_out = nullptr, bool large_by_default = true);
+int bwt_many_dev(const void *d_blocks, const void *d_offsets, int32_t count, void *d_last, void *d_origins, int32_t device,
+                 void *stream);
+// kBwtManyOn true: the framed many-file diffs transform their blocks there (dq_diff.hip: diff_many_frame).
+// DQ_NO_BWT_MANY=1 sends them down the route they had before -- doubled on the host, sufsort_many_host, the host's walk --, =0 down the new one,
+// whatever this says.  The rule (tools/kbench/bwt_many.py, which writes profiles/r23/bwt_many.json): true only if on
+// every framed set this build's median call lies below the parent build's fastest run.  On the ten sets measured the
+// block-sort phase is faster on every one and seven pass (1.05x .. 1.26x), but short/fixed4k, short/loguniform and
+// index/fixed4k@1 -- calls of 40 .. 120 ms of which the new route saves 1 .. 11 ms, less than their run-to-run spread --
+// have their median above the parent's fastest run: false by the rule (docs/ROUNDS.md, round 23).
+constexpr bool kBwtManyOn = false;
 
 // LDSSChecker.Check on the device (dq_sufcheck.hip): DQ_OK with the verdict (DQ_SUFCHECK_*) in *result, or an error
 template <typename IdxT>

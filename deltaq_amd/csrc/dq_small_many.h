@@ -342,6 +342,37 @@ int sufsort_many_dev(const void *d_texts_v, const void *d_offsets_v, int32_t cou
     return DQ_OK;
 }
 
+// The host forms' cut of a caller's texts [0, count) (dq_sufsort_hip_many_i32, dq_bwt_hip_many on its doubled blocks):
+// single(i) for a text that travels alone -- one above what may sit on a work list, every text under DQ_NO_MANY=1 --,
+// chunk(i, e, rel, plan) for a run of whole texts [i, e) of at most kManyChunkBytes and kManyChunkTexts with its offsets
+// relative to text i and its plan.  A run without a byte is passed over.  One walker, so that both callers send every
+// text the same way.
+template <typename Single, typename Chunk>
+int walk_many_host(const int64_t *offsets, int32_t count, bool large_by_default, Single single, Chunk chunk)
+{
+    // (large texts sit in chunks only where the call holds enough of them for a segmented sort: a call with fewer is
+    // cut into chunks, and sorted, exactly as it was without the class)
+    int64_t listed_max = many_listed_max(large_by_default);
+    if (listed_max > kMidMaxN) {
+        int64_t larges = 0;
+        for (int32_t i = 0; i < count; ++i) larges += is_large(offsets[i + 1] - offsets[i]) ? 1 : 0;
+        if (larges < large_many_min()) listed_max = mid_many_on() ? (int64_t)kMidMaxN : many_short_max();
+    }
+    const bool one_by_one = many_one_by_one();
+    std::vector<int64_t> rel;
+    auto len = [&](int32_t j) { return offsets[j + 1] - offsets[j]; };
+    // the chunk: texts [i, e), none above the limit, back to back in the caller's buffer
+    auto planned = [&](int32_t i, int32_t e) -> int {
+        if (offsets[e] == offsets[i]) return DQ_OK;
+        const int32_t cnt = e - i;
+        rel.resize((size_t)cnt + 1);
+        chunk_offsets(offsets, i, cnt, rel.data());
+        return chunk(i, e, rel, plan_many(rel.data(), cnt, large_by_default));
+    };
+    return walk_runs(count, kManyChunkTexts, [&](int32_t j) { return !one_by_one && len(j) <= listed_max; },
+                     [&](int32_t i, int32_t e) { return offsets[e + 1] - offsets[i] <= kManyChunkBytes; }, single, planned);
+}
+
 // Host buffers in / out.  Runs of short and medium texts -- and of large ones, in a call that holds enough of them --
 // travel in chunks of whole texts: at most kManyChunkBytes of text, its suffix arrays (4 bytes per text byte), offsets
 // and work list on the device at a time, whatever the total, and the medium launches' scratch blocks and the
@@ -358,16 +389,6 @@ int sufsort_many_host(const uint8_t *texts, const int64_t *offsets, int32_t coun
     int dev = 0;
     rc = resolve_device(device, &dev);
     if (rc != DQ_OK) return rc;
-    // (large texts sit in chunks only where the call holds enough of them for a segmented sort: a call with fewer is
-    // cut into chunks, and sorted, exactly as it was without the class)
-    int64_t listed_max = many_listed_max(large_by_default);
-    if (listed_max > kMidMaxN) {
-        int64_t larges = 0;
-        for (int32_t i = 0; i < count; ++i) larges += is_large(offsets[i + 1] - offsets[i]) ? 1 : 0;
-        if (larges < large_many_min()) listed_max = mid_many_on() ? (int64_t)kMidMaxN : many_short_max();
-    }
-    const bool one_by_one = many_one_by_one();
-    std::vector<int64_t> rel;
     auto len = [&](int32_t j) { return offsets[j + 1] - offsets[j]; };
     auto single = [&](int32_t i) -> int {
         const int r = sufsort_host<int32_t>(texts + offsets[i], len(i), sas + offsets[i], dev);
@@ -376,61 +397,55 @@ int sufsort_many_host(const uint8_t *texts, const int64_t *offsets, int32_t coun
         else if (len(i) > kSmallMaxN) t_many_info.medium_single += 1;
         return DQ_OK;
     };
-    // the chunk: texts [i, e), none above the limit, back to back in the caller's buffer
-    auto chunk = [&](int32_t i, int32_t e) -> int {
+    auto chunk = [&](int32_t i, int32_t e, const std::vector<int64_t> &rel, const ManyPlan &plan) -> int {
         const int64_t base = offsets[i], bytes = offsets[e] - base;
-        const int32_t cnt = e - i;
-        if (bytes > 0) {
-            rel.resize((size_t)cnt + 1);
-            chunk_offsets(offsets, i, cnt, rel.data());
-            const ManyPlan plan = plan_many(rel.data(), cnt, large_by_default);
-            if (plan.shared()) {
-                SlotLease lease(dev, 0);
-                DeviceCtx &c = *lease.c;
-                rc = init_ctx(c, dev);
-                if (rc != DQ_OK) return rc;
-                hipStream_t st = c.stream;
-                const size_t b_text = align_up((size_t)bytes + 64), b_sa = align_up((size_t)bytes * sizeof(int32_t)),
-                             b_off = align_up(rel.size() * sizeof(int64_t)), b_ctl = many_ctl_bytes(plan.listed()),
-                             b_scratch = many_scratch_bytes(c, plan), b_large = many_large_bytes(plan, rel.data());
-                rc = ensure_ws(c, b_text + b_sa + b_off + b_ctl + b_scratch + b_large);
-                if (rc != DQ_OK) return rc;
-                uint8_t *d_text = reinterpret_cast<uint8_t *>(c.ws);
-                int32_t *d_sa = reinterpret_cast<int32_t *>(c.ws + b_text);
-                int64_t *d_off = reinterpret_cast<int64_t *>(c.ws + b_text + b_sa);
-                t_sort_info = {};
-                auto run = [&]() -> int {
-                    HIP_TRY(hipMemcpyAsync(d_text, texts + base, (size_t)bytes, hipMemcpyHostToDevice, st));
-                    HIP_TRY(hipMemcpyAsync(d_off, rel.data(), rel.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
-                    const int r = launch_many(c, st, plan, d_text, d_off, d_sa, c.ws + b_text + b_sa + b_off,
-                                              c.ws + b_text + b_sa + b_off + b_ctl);
-                    if (r != DQ_OK) return r;
-                    const int rl = launch_large(c, st, plan, rel.data(), d_text, d_sa, c.ws + b_text + b_sa + b_off + b_ctl + b_scratch);
-                    if (rl != DQ_OK) return rl;
-                    const int rb = copy_back_and_wait(sas + base, d_sa, (size_t)bytes * sizeof(int32_t), st);
-                    return rb != DQ_OK ? rb : flush_profile(c);
-                };
-                rc = run();
-                if (rc != DQ_OK) { drop_pending(c, st); return rc; }
-                many_account(plan, false, b_scratch);
-            } else
-                many_account(plan, true, 0);
-            if (shared_out) *shared_out += plan.shorts();
-            // the chunk's medium (and large) texts that were too few for a launch: singly, into their place (the slot is given back).
-            // They travelled with the chunk -- its extent is decided before its plan -- so their bytes were copied in for
-            // nothing and the copy back laid never-written workspace words over their segments; the sorts below
-            // overwrite them.  (A failing call leaves the caller's array undefined, here as in every chunk after the
-            // failing one.)
-            for (int32_t j : plan.longs) {
-                rc = sufsort_host<int32_t>(texts + base + rel[(size_t)j], rel[(size_t)j + 1] - rel[(size_t)j],
-                                           sas + base + rel[(size_t)j], dev);
-                if (rc != DQ_OK) return rc;
-            }
+        if (plan.shared()) {
+            SlotLease lease(dev, 0);
+            DeviceCtx &c = *lease.c;
+            rc = init_ctx(c, dev);
+            if (rc != DQ_OK) return rc;
+            hipStream_t st = c.stream;
+            const size_t b_text = align_up((size_t)bytes + 64), b_sa = align_up((size_t)bytes * sizeof(int32_t)),
+                         b_off = align_up(rel.size() * sizeof(int64_t)), b_ctl = many_ctl_bytes(plan.listed()),
+                         b_scratch = many_scratch_bytes(c, plan), b_large = many_large_bytes(plan, rel.data());
+            rc = ensure_ws(c, b_text + b_sa + b_off + b_ctl + b_scratch + b_large);
+            if (rc != DQ_OK) return rc;
+            uint8_t *d_text = reinterpret_cast<uint8_t *>(c.ws);
+            int32_t *d_sa = reinterpret_cast<int32_t *>(c.ws + b_text);
+            int64_t *d_off = reinterpret_cast<int64_t *>(c.ws + b_text + b_sa);
+            t_sort_info = {};
+            auto run = [&]() -> int {
+                HIP_TRY(hipMemcpyAsync(d_text, texts + base, (size_t)bytes, hipMemcpyHostToDevice, st));
+                HIP_TRY(hipMemcpyAsync(d_off, rel.data(), rel.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+                const int r = launch_many(c, st, plan, d_text, d_off, d_sa, c.ws + b_text + b_sa + b_off,
+                                          c.ws + b_text + b_sa + b_off + b_ctl);
+                if (r != DQ_OK) return r;
+                const int rl = launch_large(c, st, plan, rel.data(), d_text, d_sa, c.ws + b_text + b_sa + b_off + b_ctl + b_scratch);
+                if (rl != DQ_OK) return rl;
+                const int rb = copy_back_and_wait(sas + base, d_sa, (size_t)bytes * sizeof(int32_t), st);
+                return rb != DQ_OK ? rb : flush_profile(c);
+            };
+            rc = run();
+            if (rc != DQ_OK) { drop_pending(c, st); return rc; }
+            many_account(plan, false, b_scratch);
+        } else
+            many_account(plan, true, 0);
+        if (shared_out) *shared_out += plan.shorts();
+        // the chunk's medium (and large) texts that were too few for a launch: singly, into their place (the slot is given back).
+        // They travelled with the chunk -- its extent is decided before its plan -- so their bytes were copied in for
+        // nothing and the copy back laid never-written workspace words over their segments; the sorts below
+        // overwrite them.  (A failing call leaves the caller's array undefined, here as in every chunk after the
+        // failing one.)
+        for (int32_t j : plan.longs) {
+            rc = sufsort_host<int32_t>(texts + base + rel[(size_t)j], rel[(size_t)j + 1] - rel[(size_t)j],
+                                       sas + base + rel[(size_t)j], dev);
+            if (rc != DQ_OK) return rc;
         }
         return DQ_OK;
     };
-    return walk_runs(count, kManyChunkTexts, [&](int32_t j) { return !one_by_one && len(j) <= listed_max; },
-                     [&](int32_t i, int32_t e) { return offsets[e + 1] - offsets[i] <= kManyChunkBytes; }, single, chunk);
+    return walk_many_host(offsets, count, large_by_default, single, chunk);
 }
 
 }  // namespace dq
+
+#include "dq_bwt_many.h"

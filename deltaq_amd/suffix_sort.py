@@ -38,6 +38,14 @@ def _as_text(text) -> np.ndarray:
     return np.frombuffer(memoryview(text).cast("B"), dtype=np.uint8)
 
 
+BWT_MAX_N = 1 << 30         # kBwtMaxN: a block of this many bytes has a doubling beyond 32-bit indices
+
+
+def unpack_bwt_many(last: np.ndarray, origins: np.ndarray, off: np.ndarray) -> list:
+    """dq_bwt_hip_many's flat results as BwtMany returns them: [(last column of block j: a view, origin row: int)]."""
+    return [(last[off[j]:off[j + 1]], int(origins[j])) for j in range(len(off) - 1)]
+
+
 def _is_torch_tensor(x) -> bool:
     return type(x).__module__.startswith("torch") and hasattr(x, "data_ptr")
 
@@ -172,6 +180,65 @@ class HipSuffixSort:
         _abi.check(self._lib.dq_sufsort_hip_many_dev_i32(tp.data_ptr(), offsets.data_ptr(), count, sp.data_ptr(),
                                                          dev, stream))
         return sas
+
+    # -- the Burrows-Wheeler transform of many blocks (no counterpart in the reference: a compressor's block stage) ----
+    def BwtMany(self, blocks):
+        """bzip2's block transform of many independent blocks, doubling, sort and last column all on the device: per
+        block the last column of its sorted rotations and the row of the block itself among them -- what walking
+        ``Sort(block + block)`` and keeping the entries below ``len(block)`` gives.  The blocks are sorted by
+        ``SortMany``'s launches on their doubled lengths (``_abi.last_many_info()`` tells what happened).
+
+        ``BwtMany([b0, b1, ...])`` -- bytes-like objects / numpy uint8 arrays, each shorter than 2^30 bytes -- returns a
+        list of ``(last, origin)``: a uint8 array view of ``len(block)`` bytes and an int, -1 for an empty block
+        (``dq_bwt_hip_many``).  ``BwtMany((blocks_tensor, offsets_tensor))`` -- a uint8 and an int64 torch GPU tensor in
+        ``SortMany``'s device layout -- returns ``(last_tensor, origins_tensor)``, uint8 in the same layout and one int32
+        per block (``dq_bwt_hip_many_dev``, on the current torch stream).
+        """
+        if isinstance(blocks, tuple) and len(blocks) == 2 and _is_torch_tensor(blocks[0]):
+            return self._bwt_many_device(*blocks)
+        arrs = [_as_text(b) for b in blocks]
+        if any(a.ndim != 1 for a in arrs):
+            raise TypeError("every block must be one-dimensional")
+        if any(a.size >= BWT_MAX_N for a in arrs):
+            raise ValueError("BwtMany has 32-bit indices: every block must be shorter than 2^30 bytes")
+        count = len(arrs)
+        off = np.zeros(count + 1, dtype=np.int64)
+        if count:
+            np.cumsum([a.size for a in arrs], out=off[1:])
+        total = int(off[-1])
+        # (a buffer of no bytes has no address: the library wants non-null pointers whenever there are blocks)
+        flat = np.concatenate(arrs) if total else np.zeros(1, np.uint8)
+        last = np.empty(max(total, 1), dtype=np.uint8)
+        origins = np.empty(max(count, 1), dtype=np.int32)
+        _abi.check(self._lib.dq_bwt_hip_many(flat.ctypes.data, off.ctypes.data, count, last.ctypes.data,
+                                             origins.ctypes.data, self.device))
+        return unpack_bwt_many(last, origins, off)
+
+    bwt_many = BwtMany
+
+    def _bwt_many_device(self, blocks, offsets):
+        import torch
+
+        if not _is_torch_tensor(offsets):
+            raise TypeError("device blocks need a device offsets tensor")
+        if blocks.dtype != torch.uint8 or blocks.dim() != 1 or not blocks.is_contiguous():
+            raise TypeError("device blocks must be a contiguous 1-D uint8 tensor")
+        if offsets.dtype != torch.int64 or offsets.dim() != 1 or not offsets.is_contiguous() or offsets.numel() < 1:
+            raise TypeError("offsets must be a contiguous 1-D int64 tensor of count + 1 entries")
+        if not blocks.is_cuda or offsets.device != blocks.device:
+            raise TypeError("blocks and offsets must live on the same GPU")
+        count = offsets.numel() - 1
+        total = blocks.numel()
+        last = torch.empty(total, dtype=torch.uint8, device=blocks.device)
+        origins = torch.empty(count, dtype=torch.int32, device=blocks.device)
+        if count == 0:
+            return last, origins
+        dev, stream = _device_and_stream(blocks)
+        bp = blocks if total else torch.zeros(1, dtype=torch.uint8, device=blocks.device)
+        lp = last if total else torch.zeros(1, dtype=torch.uint8, device=blocks.device)
+        _abi.check(self._lib.dq_bwt_hip_many_dev(bp.data_ptr(), offsets.data_ptr(), count, lp.data_ptr(),
+                                                 origins.data_ptr(), dev, stream))
+        return last, origins
 
     # -- LDSSChecker.Check(T, SA)   (test/DeltaQ.SuffixSorting.LibDivSufSort.Tests/LDSSChecker.cs:23-119) --------
     def Check(self, text, suffixes) -> int:

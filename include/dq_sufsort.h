@@ -114,6 +114,40 @@ int32_t dq_sufsort_hip_many_i32(const uint8_t *texts, const int64_t *offsets, in
 int32_t dq_sufsort_hip_many_dev_i32(const void *d_texts, const void *d_offsets, int32_t count, void *d_sas,
                                     int32_t device, void *stream);
 
+/* ---- the Burrows-Wheeler transform of many independent blocks in shared launches (a compressor's block stage) -------
+ * What a bzip2-style coder needs from a block is its last column (1 byte per block byte) and one integer; taken from
+ * dq_sufsort_hip_many_i32 that costs a doubling on the host, 2 bytes up and 8 bytes down per block byte and a walk over
+ * 2 n entries per block.  Here the doubling (double_blocks_kernel), the sort of the doubled texts -- by the launches of
+ * dq_sufsort_hip_many_i32, chosen exactly as that call chooses them for the same blocks doubled -- and the walk
+ * (bwt_many_kernel: one workgroup per block, claimed from one work list; nobody waits for anybody) stay on the device.
+ * Layout as dq_sufsort_hip_many_i32: blocks back to back, offsets[count + 1] int64, offsets[0] == 0, never decreasing;
+ * `last` has the layout of `blocks`, `origins` has `count` int32 entries.
+ * Definition (bzip2's): for block j of n bytes walk the suffix array of block+block (2 n entries, what
+ * dq_sufsort_hip_i32 returns for it) in order and keep the entries s < n, in that order; the r-th kept entry gives
+ * last[offsets[j] + r] = doubled[s + n - 1], and origins[j] is the r at which s == 0.  Rotations that are equal as
+ * strings keep the order this walk gives them, so the result is unique; the inverse transform returns the block.
+ * n == 0: nothing is written to `last` and origins[j] = -1.  Nothing outside a block's own slots is written.
+ * Errors, all before any device use in the host form: count < 0, a NULL pointer with count > 0, offsets[0] != 0,
+ * decreasing offsets -> DQ_ERR_BAD_ARGS; a block of 2^30 bytes or more -> DQ_ERR_TOO_LARGE (its doubling does not fit
+ * 32-bit indices).  count == 0 is a no-op.  A suffix array that does not give every block n rows and one origin (a
+ * device fault) -> DQ_ERR_HIP.  There is no CPU fallback.
+ *   dq_bwt_hip_many      host pointers.  The blocks travel in the chunks of dq_sufsort_hip_many_i32 on their DOUBLED
+ *                        lengths (64 MiB of doubled text at most): per chunk of b block bytes b + 2 b + 8 b bytes of
+ *                        device memory -- blocks (overwritten by `last`), doubled text, suffix arrays --, offsets,
+ *                        origins, a work list and a flag word: 352 MiB for a full chunk, and beside them what the sort's
+ *                        launches take there (scratch blocks of medium launches).  A block above a chunk goes alone with
+ *                        the same 11 bytes per byte and the device sorter's workspace.  1 byte up and 1 byte down per
+ *                        block byte; one wait per chunk for the copies back.
+ *   dq_bwt_hip_many_dev  device pointers on `device` (d_offsets too: the library fetches it once and checks it before it
+ *                        launches anything); work on `stream` (NULL = the library's), returns after the stream has
+ *                        drained.  Device memory as above without the first b.
+ * Both are outermost many-texts calls: they reset dq_last_many_info and fill it through their sorts (the lengths it
+ * counts by are the doubled ones).  Their kernels are profiled under small_many_kernel's category. */
+int32_t dq_bwt_hip_many(const uint8_t *blocks, const int64_t *offsets, int32_t count, uint8_t *last, int32_t *origins,
+                        int32_t device);
+int32_t dq_bwt_hip_many_dev(const void *d_blocks, const void *d_offsets, int32_t count, void *d_last, void *d_origins,
+                            int32_t device, void *stream);
+
 /* ---- Diff.Create's match search on the device-resident suffix array ----------
  * Replaces, for a batch of scan positions, the reference's
  *   Search(I, oldData, newData[scan..], 0, oldData.Length, out pos)          src/DeltaQ.BsDiff/Diff.cs:267-298
@@ -195,7 +229,8 @@ int64_t dq_bsdiff_patch_bound(int64_t n, int64_t m);
  * the large class: below 1.5 GiB + change for its longest chunk), the
  * same for every class (the medium anchor kernel has no scratch blocks), freed
  * on return (the shared sort's own workspace, scratch blocks of medium launches included, stays with the library until
- * dq_sufsort_hip_release); host: below 4 bytes per byte of new for the raw streams and 10 bytes per byte of stream for the shared sort.
+ * dq_sufsort_hip_release); host: below 4 bytes per byte of new for the raw streams and 10 bytes per byte of stream for the shared sort
+ * (2 bytes per byte of stream under the debug flag DQ_NO_BWT_MANY=0, which has the blocks transformed by dq_bwt_hip_many's body).
  * Errors found before any device use: count < 0, a NULL pointer with count > 0, offsets[0] != 0 or decreasing offsets
  * in any of the three arrays -> DQ_ERR_BAD_ARGS; a file of 2^31 bytes or more -> DQ_ERR_TOO_LARGE.  count == 0 is a
  * no-op.  A slot too small for its patch -> DQ_ERR_BAD_ARGS ("output buffer too small"), known only once the patch
@@ -504,7 +539,7 @@ int32_t dq_last_index_many_info(int64_t *info, int32_t count);
  * summed over the files; [4] microseconds in copies + the kernel (part of its [5]). */
 int32_t dq_last_index_large_info(int64_t *info, int32_t count);
 
-/* Shape of the shared sorts of the last outermost dq_sufsort_hip_many_i32 / _many_dev_i32 / dq_sufsort_hip_batch_i32 /
+/* Shape of the shared sorts of the last outermost dq_sufsort_hip_many_i32 / _many_dev_i32 / dq_bwt_hip_many / _many_dev / dq_sufsort_hip_batch_i32 /
  * dq_bsdiff_create_many / dq_bsdiff_index_diff_many / dq_bsdiff_scan_many / dq_bsdiff_index_scan_many on this thread, summed over every shared sort that call made and reset when such a call
  * starts; `count` entries (9 are defined, further ones read 0; a NULL array is DQ_ERR_BAD_ARGS): texts sorted in the
  * short classes' launches; texts sorted in medium launches; texts of 8193 .. 65 536 bytes sorted singly (fewer than the
