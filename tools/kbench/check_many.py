@@ -25,16 +25,14 @@ import ctypes
 import json
 import os
 import statistics
-import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import harness
 
 SETS = ("fixed4k", "fixed32k", "fixed64k", "tree")
 SWEEP_COUNTS = (1, 2, 4, 8, 16, 32, 64, 128, 256, 512)
 SWEEP_SIZES = (4096, 16384, 65536)
+CHECK_MANY = "dq_last_check_many_info"
+INFO = {CHECK_MANY: harness.INFO_KEYS[CHECK_MANY]}
 
 
 def make_set(name):
@@ -84,17 +82,7 @@ class Shape:
                 raise RuntimeError(f"check failed ({rc}, verdict {self.one.value}): {self.L.dq_last_error()}")
 
     def info(self):
-        from deltaq_amd import _abi
-        return _abi.last_check_many_info()
-
-
-def timed(fn, calls):
-    ms = []
-    for _ in range(calls):
-        t0 = time.perf_counter()
-        fn()
-        ms.append((time.perf_counter() - t0) * 1e3)
-    return ms
+        return harness.last_info(self.L, CHECK_MANY, INFO[CHECK_MANY])
 
 
 def forced(fn):
@@ -116,8 +104,8 @@ def measure(shape, calls, rounds, with_forced=False):
     shape.many()
     loop, many, shared = [], [], []
     for _ in range(rounds):
-        loop += timed(shape.loop, calls)
-        many += timed(shape.many, calls)
+        loop += harness.timed(shape.loop, calls, 0, digits=None)
+        many += harness.timed(shape.many, calls, 0, digits=None)
     info = shape.info()
     rec = {"texts": shape.count, "bytes": shape.bytes, "runs_each": calls * rounds,
            "loop_ms_median": round(statistics.median(loop), 4), "loop_ms_min": round(min(loop), 4),
@@ -127,27 +115,15 @@ def measure(shape, calls, rounds, with_forced=False):
     if with_forced:
         forced(shape.many)()
         for _ in range(rounds):
-            shared += timed(forced(shape.many), calls)
+            shared += harness.timed(forced(shape.many), calls, 0, digits=None)
         rec["shared_ms_median"] = round(statistics.median(shared), 4)
         rec["shared_texts_when_forced"] = shape.info()["shared_texts"]
     return rec
 
 
-def crossing_of(row, key):
-    """The smallest count from which on row's `key` is never above the loop's median; None: not even at the end."""
-    crossing = None
-    for count in reversed(SWEEP_COUNTS):
-        c = row["counts"][str(count)]
-        if c[key] <= c["loop_ms_median"]:
-            crossing = count
-        else:
-            break
-    return crossing
-
-
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r13", "check_many.json"))
+    ap.add_argument("--out", default=os.path.join(harness.ROOT, "profiles", "r13", "check_many.json"))
     ap.add_argument("--calls", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=2, help="loop / one call alternations per shape")
     ap.add_argument("--sets", default=",".join(SETS), help="comma-separated; empty: none")
@@ -156,20 +132,10 @@ def main():
     env_flags = sorted(k for k in os.environ if k.startswith("DQ_") and k not in ("DQ_SUFSORT_LIB",))
     if env_flags:
         raise SystemExit(f"unset {env_flags}: this tool measures the library as it ships")
-    from deltaq_amd import HipSuffixSort, build as dq_build
-    if dq_build.is_stale():
-        raise SystemExit("build the library first (python -m deltaq_amd.build): this tool measures, it does not compile")
-    hip = HipSuffixSort(0)
-    result = {"tool": "tools/kbench/check_many.py", "library_source_digest": dq_build._source_digest(),
-              "baseline": "loop of dq_sufcheck_hip_dev_i32 over the same device-resident texts, same process",
-              "sets": {}, "sweep": []}
-
-    def save():
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:                       # (after every step: a later failure loses nothing)
-            json.dump(result, f, indent=1)
-            f.write("\n")
-
+    from deltaq_amd import HipSuffixSort
+    result = harness.Result(args.out, "tools/kbench/check_many.py", sets={}, sweep=[],
+                            baseline="loop of dq_sufcheck_hip_dev_i32 over the same device-resident texts, same process")
+    hip, save = HipSuffixSort(0), result.save
     for name in [s for s in args.sets.split(",") if s]:
         rec = measure(Shape(hip, make_set(name)), args.calls, args.rounds)
         rec["many_median_below_loops_fastest"] = bool(rec["many_ms_median"] < rec["loop_ms_min"])
@@ -186,9 +152,9 @@ def main():
                                                                   "shared_ms_median", "shared_texts_when_forced")}
                 row["counts"][str(count)]["shared_texts"] = rec["last_call_info"]["shared_texts"]
                 print(size, count, row["counts"][str(count)], flush=True)
-            row["crossing"] = crossing_of(row, "many_ms_median")
+            row["crossing"] = harness.crossing(row, "many_ms_median", "loop_ms_median", strict=False)
             row["never_slower_from_one_text_on"] = row["crossing"] == 1
-            row["crossing_when_forced"] = crossing_of(row, "shared_ms_median")
+            row["crossing_when_forced"] = harness.crossing(row, "shared_ms_median", "loop_ms_median", strict=False)
             if row["crossing_when_forced"] not in (None, 1):
                 row["min_texts_from_this_row"] = 1 << (2 * row["crossing_when_forced"] - 1).bit_length()
             result["sweep"].append(row)

@@ -25,226 +25,99 @@ unrelated64k = 512 unrelated files of 64 KiB.  Times are host clock around block
     python tools/kbench/index_diff_many.py --parent-lib /path/to/parent/libdq_sufsort_hip.so --out profiles/r12/index_diff_many.json
 """
 import argparse
-import ctypes
-import hashlib
 import json
 import os
-import statistics
-import subprocess
-import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import harness
 
 SETS = {"fixed4k": 0x04AA, "fixed32k": 0x32AB, "tree": 0x7EE6, "unrelated64k": 0x64AB}
 OLD_MIB = (1, 16)
 SWEEP_COUNTS = (1, 2, 4, 8, 16, 32, 64, 128, 256, 512)
 SWEEP_SIZES = (4096, 16384, 65536)
-INFO_KEYS = ("shared_files", "single_files", "anchor_launches", "shared_block_sorts", "single_block_sorts",
-             "anchor_and_copies_us", "emit_us", "block_sort_us", "frame_us")
+INDEX_MANY = "dq_last_index_many_info"
+INFO = {INDEX_MANY: harness.INFO_KEYS[INDEX_MANY]}
+STRICT = True                                                # accepted: new median < the parent's fastest run of the loop
+NAMES = {"runs": "parent_loop_ms", "median": "parent_loop_ms_median", "fastest": "parent_fastest_loop_ms",
+         "ratio": "ratio_parent_over_new", "accepted": "new_median_below_parents_fastest_loop"}
 
 
-def load_library(path, many):
-    """ctypes only (no deltaq_amd._abi.load(): another build need not export what this tree's binding declares)."""
-    from deltaq_amd import _abi
-    _abi._preload_torch_hip_runtime()
-    L = ctypes.CDLL(path)
-    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-    L.dq_bsdiff_patch_bound.restype = i64
-    L.dq_bsdiff_patch_bound.argtypes = [i64, i64]
-    L.dq_last_error.restype = ctypes.c_char_p
-    L.dq_bsdiff_index_create.restype = i32
-    L.dq_bsdiff_index_create.argtypes = [vp, i64, vp, vp, i32, ctypes.POINTER(vp)]
-    L.dq_bsdiff_index_diff.restype = i32
-    L.dq_bsdiff_index_diff.argtypes = [vp, vp, i64, vp, i64, ctypes.POINTER(i64)]
-    L.dq_bsdiff_index_free.restype = None
-    L.dq_bsdiff_index_free.argtypes = [vp]
-    if many:
-        L.dq_bsdiff_index_diff_many.restype = i32
-        L.dq_bsdiff_index_diff_many.argtypes = [vp, vp, vp, i32, vp, vp, vp]
-        L.dq_last_index_many_info.restype = i32
-        L.dq_last_index_many_info.argtypes = [ctypes.POINTER(i64), i32]
-    return L
-
-
-class Index:
-    def __init__(self, L, old):
-        self.L, self.old = L, old
-        self.h = ctypes.c_void_p()
-        rc = L.dq_bsdiff_index_create(old.ctypes.data, old.size, None, None, 0, ctypes.byref(self.h))
-        if rc != 0:
-            raise RuntimeError(f"index_create failed ({rc}): {L.dq_last_error()}")
-
-    def close(self):
-        self.L.dq_bsdiff_index_free(self.h)
-
-
-class Call:
-    """One set of new files against one index: packed, the slots sized, repeatable either way."""
-
-    def __init__(self, index, news, kind):
-        import numpy as np
-        import many_inputs
-        self.L, self.h, self.cnt, self.kind = index.L, index.h, len(news), kind
-        self.n_flat, self.n_off = many_inputs.pack(news)
-        self.p_off = np.zeros(self.cnt + 1, np.int64)
-        np.cumsum([self.L.dq_bsdiff_patch_bound(index.old.size, x.size) for x in news], out=self.p_off[1:])
-        self.buf = np.empty(int(self.p_off[-1]), np.uint8)
-        self.lens = np.full(self.cnt, -1, np.int64)
-
-    def __call__(self):
-        if self.kind == "many":
-            rc = self.L.dq_bsdiff_index_diff_many(self.h, self.n_flat.ctypes.data, self.n_off.ctypes.data, self.cnt,
-                                                  self.buf.ctypes.data, self.p_off.ctypes.data, self.lens.ctypes.data)
-            if rc != 0:
-                raise RuntimeError(f"index_diff_many failed ({rc}): {self.L.dq_last_error()}")
-            return
-        base, nb, ln = self.buf.ctypes.data, self.n_flat.ctypes.data, ctypes.c_int64()
-        for j in range(self.cnt):
-            a, b = int(self.n_off[j]), int(self.n_off[j + 1])
-            p0, p1 = int(self.p_off[j]), int(self.p_off[j + 1])
-            rc = self.L.dq_bsdiff_index_diff(self.h, nb + a, b - a, base + p0, p1 - p0, ctypes.byref(ln))
-            if rc != 0:
-                raise RuntimeError(f"index_diff failed ({rc}): {self.L.dq_last_error()}")
-            self.lens[j] = ln.value
-
-    def digest(self):
-        h = hashlib.sha256()
-        for j in range(self.cnt):
-            h.update(int(self.lens[j]).to_bytes(8, "little"))
-            h.update(self.buf[int(self.p_off[j]):int(self.p_off[j]) + int(self.lens[j])].tobytes())
-        return h.hexdigest()
-
-    def info(self):
-        v = (ctypes.c_int64 * 9)()
-        self.L.dq_last_index_many_info(v, 9)
-        return dict(zip(INFO_KEYS, list(v)))
-
-
-def timed(fn, calls, warmup=1):
-    for _ in range(warmup):
-        fn()
-    ms = []
-    for _ in range(calls):
-        t0 = time.perf_counter()
-        fn()
-        ms.append((time.perf_counter() - t0) * 1e3)
-    return {"ms_median": round(statistics.median(ms), 3), "ms_min": round(min(ms), 3), "ms_max": round(max(ms), 3),
-            "calls": calls}
+def info(L):
+    return harness.last_info(L, INDEX_MANY, INFO[INDEX_MANY])
 
 
 def worker_set(lib_path, kind, set_name, mib, calls):
     import index_many_inputs as imi
     old = imi.bench_old(mib)
-    index = Index(load_library(lib_path, kind == "many"), old)
-    call = Call(index, imi.bench_news(set_name, old, SETS[set_name] + mib), kind)
-    rec = timed(call, calls)
+    index = harness.Index(harness.load_library(lib_path), old)
+    call = harness.IndexCall(index, imi.bench_news(set_name, old, SETS[set_name] + mib), kind)
+    rec = harness.timed(call, calls, 1)
     rec.update(files=call.cnt, old_bytes=int(old.size), new_bytes=int(call.n_off[-1]), patch_bytes=int(call.lens.sum()),
                patches_sha256=call.digest())
     if kind == "many":
-        rec["last_call_info"] = call.info()
+        rec["last_call_info"] = info(index.L)
     index.close()
-    print("RESULT " + json.dumps(rec), flush=True)
+    harness.emit(rec)
 
 
 def worker_threads(lib_path, set_names, calls):
     import index_many_inputs as imi
     os.environ["DQ_DEBUG_FLAGS"] = "1"
-    L = load_library(lib_path, True)
+    L = harness.load_library(lib_path)
     rows = []
     for mib in OLD_MIB:
         old = imi.bench_old(mib)
-        index = Index(L, old)
+        index = harness.Index(L, old)
         for set_name in set_names:
-            call = Call(index, imi.bench_news(set_name, old, SETS[set_name] + mib), "many")
+            call = harness.IndexCall(index, imi.bench_news(set_name, old, SETS[set_name] + mib))
             row = {"old_mib": mib, "set": set_name}
             for threads in ("512", "256", "512", "256"):
                 os.environ["DQ_INDEX_MANY_THREADS"] = threads
-                t = timed(call, calls)
+                t = harness.timed(call, calls, 1)
                 del os.environ["DQ_INDEX_MANY_THREADS"]
                 row.setdefault("call_ms_" + threads, []).append(t["ms_median"])
-                row.setdefault("anchor_ms_" + threads, []).append(round(call.info()["anchor_and_copies_us"] / 1e3, 3))
+                row.setdefault("anchor_ms_" + threads, []).append(round(info(L)["anchor_and_copies_us"] / 1e3, 3))
                 row.setdefault("sha", set()).add(call.digest())
             row["identical"] = len(row.pop("sha")) == 1
             rows.append(row)
             print(row, flush=True)
         index.close()
-    print("RESULT " + json.dumps({"rows": rows}), flush=True)
+    harness.emit({"rows": rows})
 
 
 def worker_sweep(lib_path, calls):
     import index_many_inputs as imi
     os.environ["DQ_DEBUG_FLAGS"] = "1"
-    L = load_library(lib_path, True)
+    L = harness.load_library(lib_path)
     rows = []
     for mib in OLD_MIB:
         old = imi.bench_old(mib)
-        index = Index(L, old)
+        index = harness.Index(L, old)
         for size in SWEEP_SIZES:
             for similar in (True, False):
                 row = {"old_mib": mib, "bytes_per_file": size, "files": "similar" if similar else "unrelated", "counts": {}}
                 for count in SWEEP_COUNTS:
-                    call = Call(index, imi.sweep_news(old, size, count, 0x5EE9 + count, similar), "many")
+                    call = harness.IndexCall(index, imi.sweep_news(old, size, count, 0x5EE9 + count, similar))
                     got = {}
                     for name, env in (("on", ("DQ_INDEX_MANY_MIN", "1")), ("off", ("DQ_NO_INDEX_MANY", "1"))):
                         os.environ[env[0]] = env[1]
-                        got[name] = timed(call, calls)
+                        got[name] = harness.timed(call, calls, 1)
                         got[name + "_sha"] = call.digest()
-                        got[name + "_shared"] = call.info()["shared_files"]
+                        got[name + "_shared"] = info(L)["shared_files"]
                         del os.environ[env[0]]
                     row["counts"][str(count)] = {"on_ms": got["on"]["ms_median"], "off_ms": got["off"]["ms_median"],
                                                  "identical": got["on_sha"] == got["off_sha"],
                                                  "on_shared_files": got["on_shared"], "off_shared_files": got["off_shared"]}
                     print(mib, size, row["files"], count, row["counts"][str(count)], flush=True)
-                # the smallest count from which on every larger one is faster shared
-                crossing = None
-                for count in reversed(SWEEP_COUNTS):
-                    c = row["counts"][str(count)]
-                    if c["on_ms"] < c["off_ms"]:
-                        crossing = count
-                    else:
-                        break
-                row["crossing"] = crossing
+                row["crossing"] = harness.crossing(row)
                 rows.append(row)
         index.close()
-    print("RESULT " + json.dumps({"rows": rows}), flush=True)
-
-
-def chosen_threshold(rows):
-    """Twice the largest crossing, rounded up to a power of two; at least 8.  None: a row never crosses."""
-    if any(r["crossing"] is None for r in rows):
-        return None
-    want = max(8, 2 * max(r["crossing"] for r in rows))
-    return 1 << (want - 1).bit_length()
-
-
-def run_worker(args_list, timeout):
-    """One fresh process per measurement; its exit status is checked, nothing is tried twice."""
-    cmd = [sys.executable, os.path.abspath(__file__)] + args_list
-    env = {k: v for k, v in os.environ.items() if not k.startswith("DQ_")}
-    p = subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    deadline, result, tail = time.monotonic() + timeout, None, []
-    for line in p.stdout:                                    # (progress lines pass through as they come)
-        if line.startswith("RESULT "):
-            result = json.loads(line[7:])
-        else:
-            tail = (tail + [line])[-40:]
-            print("  " + line.rstrip(), flush=True)
-        if time.monotonic() > deadline:
-            p.kill()
-    if p.wait() != 0:
-        raise SystemExit(f"worker {args_list} ended with {p.returncode}:\n{''.join(tail)}")
-    if result is None:
-        raise SystemExit(f"worker {args_list} printed no result")
-    return result
+    harness.emit({"rows": rows})
 
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--parent-lib", help="libdq_sufsort_hip.so of the build to compare with")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r12", "index_diff_many.json"))
+    ap.add_argument("--out", default=os.path.join(harness.ROOT, "profiles", "r12", "index_diff_many.json"))
     ap.add_argument("--calls", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=2, help="parent / new alternations per set")
     ap.add_argument("--parent-kind", choices=["loop", "many"], default="loop",
@@ -267,64 +140,40 @@ def main():
         return worker_threads(args.lib, args.set.split(","), args.calls)
     if args.worker:
         return worker_set(args.lib, args.kind, args.set, args.mib, args.calls)
-    from deltaq_amd import build as dq_build
-    new_lib = dq_build.LIB_PATH
-    if dq_build.is_stale():
-        raise SystemExit("build the library first (python -m deltaq_amd.build): this tool measures, it does not compile")
-    result = {"tool": "tools/kbench/index_diff_many.py", "calls_per_median": args.calls,
-              "library_source_digest": dq_build._source_digest(), "sets": {}}
-    if os.path.exists(args.out):                             # (the steps may be measured in separate visits)
-        with open(args.out) as f:
-            old = json.load(f)
-        if old.get("library_source_digest") == result["library_source_digest"]:
-            result.update({k: old[k] for k in ("sets", "sweep", "kIndexManyMin_from_this_sweep", "threads") if k in old})
-
-    def save():
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:                       # (after every step: a later failure loses nothing)
-            json.dump(result, f, indent=1)
-            f.write("\n")
-
+    result = harness.Result(args.out, "tools/kbench/index_diff_many.py", calls=args.calls, same_digest=True, sets={},
+                            kept=("sets", "sweep", "kIndexManyMin_from_this_sweep", "threads"))
     set_names = [s for s in args.sets.split(",") if s]
     if args.threads:
-        result["threads"] = run_worker(["--worker", "threads", "--lib", new_lib, "--set", ",".join(set_names), "--calls",
-                                        str(args.sweep_calls)], 1100)["rows"]
-        save()
+        result["threads"] = harness.run_worker(__file__, ["--worker", "threads", "--lib", result.lib, "--set", ",".join(set_names),
+                                                          "--calls", str(args.sweep_calls)], 1100)["rows"]
+        result.save()
         set_names = []
     if args.sweep:
-        rows = run_worker(["--worker", "sweep", "--lib", new_lib, "--calls", str(args.sweep_calls)], 1100)["rows"]
+        rows = harness.run_worker(__file__, ["--worker", "sweep", "--lib", result.lib, "--calls", str(args.sweep_calls)], 1100)["rows"]
         result["sweep"] = rows
-        result["kIndexManyMin_from_this_sweep"] = chosen_threshold(rows)
+        result["kIndexManyMin_from_this_sweep"] = harness.threshold_from(rows)
         print("sweep crossings", [r["crossing"] for r in rows], "->", result["kIndexManyMin_from_this_sweep"], flush=True)
-        save()
-    for mib in [int(x) for x in args.old_mib.split(",") if x]:
-        for set_name in set_names:
-            runs = {"parent": [], "new": []}
-            for _ in range(args.rounds):
-                for who, path, kind in (("parent", args.parent_lib, args.parent_kind), ("new", new_lib, "many")):
-                    if path:
-                        runs[who].append(run_worker(["--worker", "set", "--lib", path, "--kind", kind, "--set", set_name, "--mib",
-                                                     str(mib), "--calls", str(args.calls)], 1100))
-                        print(mib, set_name, who, runs[who][-1]["ms_median"], "ms", flush=True)
-            n_ms = statistics.median(r["ms_median"] for r in runs["new"])
-            first = runs["new"][0]
-            rec = {"files": first["files"], "old_bytes": first["old_bytes"], "new_bytes": first["new_bytes"],
-                   "patch_bytes": first["patch_bytes"], "new_ms": [r["ms_median"] for r in runs["new"]], "new_ms_median": n_ms,
-                   "new_files_per_s": round(first["files"] / (n_ms / 1e3)), "new_last_call_info": runs["new"][-1]["last_call_info"]}
-            digests = {r["patches_sha256"] for rs in runs.values() for r in rs}
-            rec["patches_identical"] = len(digests) == 1
-            if runs["parent"]:
-                p_ms = statistics.median(r["ms_median"] for r in runs["parent"])
-                p_fastest = min(r["ms_min"] for r in runs["parent"])
-                rec.update(parent_kind=args.parent_kind, parent_loop_ms=[r["ms_median"] for r in runs["parent"]],
-                           parent_loop_ms_median=p_ms, parent_fastest_loop_ms=p_fastest, ratio_parent_over_new=round(p_ms / n_ms, 2),
-                           new_median_below_parents_fastest_loop=bool(n_ms < p_fastest))
-                if args.parent_kind == "many":
-                    rec["parent_last_call_info"] = runs["parent"][-1]["last_call_info"]
-                    rec["spread_ms"] = round(max(max(r["ms_median"] for r in rs) - min(r["ms_median"] for r in rs)
-                                                 for rs in runs.values()), 3)
-            result["sets"][f"{set_name}@{mib}MiB"] = rec
-            save()
+        result.save()
+
+    def run_one(s, who, path, kind):
+        return harness.run_worker(__file__, ["--worker", "set", "--lib", path, "--kind", kind, "--set", s[1], "--mib", str(s[0]),
+                                             "--calls", str(args.calls)], 1100)
+
+    sides = [("parent", args.parent_lib, args.parent_kind), ("new", result.lib, "many")]
+    sets = [(int(x), set_name) for x in args.old_mib.split(",") if x for set_name in set_names]
+    for (mib, set_name), runs in harness.compare(sets, sides, run_one, args.rounds):
+        first, judged = runs["new"][0], harness.judge(runs, STRICT, NAMES)
+        rec = {"files": first["files"], "old_bytes": first["old_bytes"], "new_bytes": first["new_bytes"],
+               "patch_bytes": first["patch_bytes"], "new_ms": judged.pop("new_ms"), "new_ms_median": judged.pop("new_ms_median"),
+               "new_last_call_info": runs["new"][-1]["last_call_info"], "patches_identical": harness.same_digests(runs, "patches_sha256")}
+        rec["new_files_per_s"] = round(first["files"] / (rec["new_ms_median"] / 1e3))
+        if runs["parent"]:
+            rec.update(parent_kind=args.parent_kind, **judged)
+            if args.parent_kind == "many":
+                rec["parent_last_call_info"] = runs["parent"][-1]["last_call_info"]
+                rec["spread_ms"] = round(harness.spread_of(runs), 3)
+        result["sets"][f"{set_name}@{mib}MiB"] = rec
+        result.save()
     print(json.dumps(result))
 
 

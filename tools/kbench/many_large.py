@@ -35,18 +35,11 @@ Times are host clock around a blocking call that ends in a device synchronise; p
     python tools/kbench/many_large.py --parent-lib /path/to/parent/libdq_sufsort_hip.so --diff-out profiles/r11/diff_many_large.json
 """
 import argparse
-import ctypes
-import hashlib
 import json
 import os
 import statistics
-import subprocess
-import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import harness
 
 SETS = {"fixed256k": 0x256C, "tree_large": 0x7EE6, "doubled_large": 0xD0B2}
 SWEEP_BYTES = (128 << 10, 256 << 10, 512 << 10, 1 << 20, 2 << 20, 4 << 20)
@@ -56,42 +49,11 @@ SWEEP_LIMIT = 64 << 20                 # of text per point
 SWEEP_SEED = 0x5EEA
 FLOOR = 5                              # existing tests: four large texts in a call go singly
 TREE_TEXTS = 4096
-
-
-def load_library(path):
-    """ctypes only (no deltaq_amd._abi.load(): another build need not export what this tree's binding declares)."""
-    from deltaq_amd import _abi
-    _abi._preload_torch_hip_runtime()
-    L = ctypes.CDLL(path)
-    vp, i32 = ctypes.c_void_p, ctypes.c_int32
-    L.dq_sufsort_hip_many_i32.restype = i32
-    L.dq_sufsort_hip_many_i32.argtypes = [vp, vp, i32, vp, i32]
-    L.dq_sufsort_hip_many_dev_i32.restype = i32
-    L.dq_sufsort_hip_many_dev_i32.argtypes = [vp, vp, i32, vp, i32, vp]
-    L.dq_last_error.restype = ctypes.c_char_p
-    return L
-
-
-def timed(fn, calls, warmup=2):
-    for _ in range(warmup):
-        fn()
-    ms = []
-    for _ in range(calls):
-        t0 = time.perf_counter()
-        fn()
-        ms.append((time.perf_counter() - t0) * 1e3)
-    return {"ms_median": round(statistics.median(ms), 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4),
-            "calls": calls}
-
-
-def last_many_info(L):
-    if not hasattr(L, "dq_last_many_info"):
-        return None
-    v = (ctypes.c_int64 * 9)()
-    L.dq_last_many_info.argtypes = [ctypes.POINTER(ctypes.c_int64), ctypes.c_int32]
-    L.dq_last_many_info(v, 9)
-    return dict(zip(("short_texts", "medium_texts", "medium_single", "long_single", "medium_launches", "scratch_bytes",
-                     "large_texts", "segmented_sorts", "list_entries"), v))
+MANY, DIFF_MANY = "dq_last_many_info", "dq_last_diff_many_info"
+INFO = {MANY: harness.INFO_KEYS[MANY], DIFF_MANY: harness.INFO_KEYS[DIFF_MANY]}
+STRICT = True                                                # accepted: new median < the parent's fastest call
+NAMES = {"runs": "parent_ms", "median": "parent_ms_median", "fastest": "parent_fastest_call_ms", "ratio": "ratio_parent_over_new",
+         "accepted": "new_median_below_parent_fastest_call"}
 
 
 def bench_texts(set_name):
@@ -103,7 +65,7 @@ def bench_texts(set_name):
 def worker_host(lib_path, set_name, calls):
     import numpy as np
     import many_inputs
-    L = load_library(lib_path)
+    L = harness.load_library(lib_path)
     texts = bench_texts(set_name)
     flat, off = many_inputs.pack(texts)
     sas = np.full(flat.size, -1, np.int32)
@@ -113,10 +75,10 @@ def worker_host(lib_path, set_name, calls):
         if rc != 0:
             raise RuntimeError(f"many failed ({rc}): {L.dq_last_error()}")
 
-    rec = timed(call, calls, warmup=1)
+    rec = harness.timed(call, calls, 1, digits=4)
     rec.update(texts=len(texts), text_bytes=int(flat.size), large=sum(t.size > 65536 for t in texts),
-               outputs_sha256=hashlib.sha256(sas.astype("<i4").tobytes()).hexdigest(), last_many_info=last_many_info(L))
-    print("RESULT " + json.dumps(rec), flush=True)
+               outputs_sha256=harness.digest_arrays([sas]), last_many_info=harness.last_info(L, MANY, INFO[MANY]))
+    harness.emit(rec)
 
 
 def device_call(L, texts):
@@ -150,27 +112,27 @@ def with_flags(flags, fn):
 
 def worker_device(lib_path, set_name, calls):
     os.environ["DQ_DEBUG_FLAGS"] = "1"                     # (the variants are debug overrides, read per call)
-    L = load_library(lib_path)
+    L = harness.load_library(lib_path)
     texts = bench_texts(set_name)
     call, d_sas = device_call(L, texts)
     out, digests = {}, set()
     ask = class_request()
     for name, flags in (("large_class_on", {"DQ_LARGE_MANY_MIN": str(ask)} if ask else {}), ("large_class_off", {"DQ_NO_LARGE_MANY": "1"})):
         d_sas.fill_(-1)
-        rec = with_flags(flags, lambda: timed(call, calls, warmup=1))
+        rec = with_flags(flags, lambda: harness.timed(call, calls, 1, digits=4))
         rec["flags"] = flags
-        digests.add(hashlib.sha256(d_sas.cpu().numpy().astype("<i4").tobytes()).hexdigest())
+        digests.add(harness.digest_arrays([d_sas.cpu().numpy()]))
         out[name] = rec
-    print("RESULT " + json.dumps({"texts": len(texts), "variants": out,
-                                  "ratio_off_over_on": round(out["large_class_off"]["ms_median"] / out["large_class_on"]["ms_median"], 2),
-                                  "outputs_identical_across_variants": len(digests) == 1}), flush=True)
+    harness.emit({"texts": len(texts), "variants": out,
+                  "ratio_off_over_on": round(out["large_class_off"]["ms_median"] / out["large_class_on"]["ms_median"], 2),
+                  "outputs_identical_across_variants": len(digests) == 1})
 
 
 def worker_sweep(lib_path, calls, lengths):
     """One process per length (main() saves after each: a slow or failing length loses only itself)."""
     import many_large_inputs
     os.environ["DQ_DEBUG_FLAGS"] = "1"
-    L = load_library(lib_path)
+    L = harness.load_library(lib_path)
     out = {}
     for n in lengths:
         by_kind = {}
@@ -181,48 +143,43 @@ def worker_sweep(lib_path, calls, lengths):
                     break
                 texts = many_large_inputs.sweep_set(n, count, SWEEP_SEED + count, kind)
                 call, d_sas = device_call(L, texts)
-                on = with_flags({"DQ_LARGE_MANY_MIN": "1"}, lambda: timed(call, calls))
-                a = hashlib.sha256(d_sas.cpu().numpy().tobytes()).hexdigest()
+                on = with_flags({"DQ_LARGE_MANY_MIN": "1"}, lambda: harness.timed(call, calls, 2, digits=4))
+                a = harness.digest_arrays([d_sas.cpu().numpy()])
                 d_sas.fill_(-1)
-                off = with_flags({"DQ_NO_LARGE_MANY": "1"}, lambda: timed(call, calls))
-                b = hashlib.sha256(d_sas.cpu().numpy().tobytes()).hexdigest()
+                off = with_flags({"DQ_NO_LARGE_MANY": "1"}, lambda: harness.timed(call, calls, 2, digits=4))
+                b = harness.digest_arrays([d_sas.cpu().numpy()])
                 rows.append({"texts": count, "forced_on_ms": on["ms_median"], "off_ms": off["ms_median"],
                              "forced_on_ms_min_max": [on["ms_min"], on["ms_max"]], "off_ms_min_max": [off["ms_min"], off["ms_max"]],
                              "outputs_identical": a == b})
                 del call, d_sas
-            # the crossing: the smallest count from which on the segmented sort is faster at every larger count too
-            crossing = None
-            for k in range(len(rows) - 1, -1, -1):
-                if rows[k]["forced_on_ms"] < rows[k]["off_ms"]:
-                    crossing = rows[k]["texts"]
-                else:
-                    break
+            crossing = harness.crossing({"counts": {r["texts"]: r for r in rows}}, on="forced_on_ms")
             by_kind[kind] = {"rows": rows, "crossing": crossing}
-            print("sweep", n, kind, "crossing", crossing, [(r["texts"], r["forced_on_ms"], r["off_ms"]) for r in rows],
-                  file=sys.stderr, flush=True)
+            print("sweep", n, kind, "crossing", crossing, [(r["texts"], r["forced_on_ms"], r["off_ms"]) for r in rows], flush=True)
         cs = [by_kind[k]["crossing"] for k in SWEEP_KINDS]
         out[str(n)] = {"by_kind": by_kind, "crossing": None if any(c is None for c in cs) else max(cs)}
-    print("RESULT " + json.dumps(out), flush=True)
+    harness.emit(out)
 
 
 def worker_diff(lib_path, calls):
     """diff_many_medium.py's tree set on one library (--large-min asks for the large class in the shared block sort)."""
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-    import diff_many_medium
-    diff_many_medium.worker_set(lib_path, "tree", calls)          # (prints the RESULT line)
+    import diff_pairs_medium as dpm
+    from diff_many_medium import SETS as MEDIUM_SETS
+    L = harness.load_library(lib_path)
+    call = harness.PairsCall(L, dpm.bench_pairs("tree", MEDIUM_SETS["tree"]))
+    rec = harness.timed(call, calls, 1)
+    rec.update(patches_sha256=call.digest(), last_call_info=harness.last_info(L, DIFF_MANY, INFO[DIFF_MANY]))
+    harness.emit(rec)
 
 
 def diff_figure(args, new_lib):
-    arms = ([("parent", args.parent_lib, 0)] if args.parent_lib else []) + [("class_off", new_lib, 0), ("class_on", new_lib, args.diff_large_min)]
-    runs = {name: [] for name, _, _ in arms}
+    arms = [("parent", args.parent_lib, 0), ("class_off", new_lib, 0), ("class_on", new_lib, args.diff_large_min)]
     result = {"tool": "tools/kbench/many_large.py --diff-out", "set": "tree (tools/kbench/diff_many_medium.py)",
               "calls_per_median": args.calls, "large_many_min_of_class_on": args.diff_large_min, "arms": {}}
-    for _ in range(args.rounds):
-        for name, path, large_min in arms:
-            runs[name].append(run_worker("diff", path, None, args.calls, 900, large_min=large_min))
-            r = runs[name][-1]
-            print("diff tree", name, r["ms_median"], "ms, block sorts", r["last_call_info"]["block_sort_us"], "us", flush=True)
+    _, runs = next(harness.compare(["diff tree"], arms, lambda s, who, path, large_min:
+                                   run_one(args, "diff", path, None, 900, large_min=large_min), args.rounds))
     for name, rs in runs.items():
+        if not rs:
+            continue
         total, phase = [r["ms_median"] for r in rs], [r["last_call_info"]["block_sort_us"] / 1e3 for r in rs]
         result["arms"][name] = {"call_ms": total, "call_ms_median": statistics.median(total), "call_ms_fastest": min(r["ms_min"] for r in rs),
                                 "block_sort_ms_of_last_call": phase, "block_sort_ms_median": statistics.median(phase),
@@ -230,12 +187,9 @@ def diff_figure(args, new_lib):
                                 "last_call_info": rs[-1]["last_call_info"]}
     on, off = result["arms"]["class_on"], result["arms"]["class_off"]
     spread = max(on["spread_block_sort_ms"], off["spread_block_sort_ms"])
-    result["patches_identical"] = len({r["patches_sha256"] for rs in runs.values() for r in rs}) == 1
+    result["patches_identical"] = harness.same_digests(runs, "patches_sha256")
     result["block_sorts_faster_with_the_class_by_more_than_the_spread"] = bool(off["block_sort_ms_median"] - on["block_sort_ms_median"] > spread)
-    os.makedirs(os.path.dirname(os.path.abspath(args.diff_out)), exist_ok=True)
-    with open(args.diff_out, "w") as f:
-        json.dump(result, f, indent=1)
-        f.write("\n")
+    harness.write_json(args.diff_out, result)
     print(json.dumps(result))
 
 
@@ -246,39 +200,28 @@ def class_request():
     return 0 if many_large_inputs.LARGE_BY_DEFAULT else many_large_inputs.LARGE_MANY_MIN
 
 
-def run_worker(kind, lib_path, set_name, calls, timeout, sweep_bytes=0, large_min=0):
-    """One fresh process per measurement; its exit status is checked, nothing is tried twice."""
-    cmd = [sys.executable, os.path.abspath(__file__), "--worker", kind, "--lib", lib_path, "--set", set_name or "-",
-           "--calls", str(calls), "--tree-texts", str(TREE_TEXTS), "--sweep-bytes", str(sweep_bytes), "--large-min", str(large_min)]
-    env = {k: v for k, v in os.environ.items() if not k.startswith("DQ_")}
-    p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, text=True, timeout=timeout)      # (stderr: progress, passed on)
-    if p.returncode != 0:
-        raise SystemExit(f"worker {kind} {set_name} on {lib_path} ended with {p.returncode}:\n{p.stdout[-2000:]}")
-    for line in p.stdout.splitlines():
-        if line.startswith("RESULT "):
-            return json.loads(line[7:])
-    raise SystemExit(f"worker {kind} {set_name} printed no result:\n{p.stdout[-2000:]}")
+def run_one(args, kind, lib_path, set_name, timeout, sweep_bytes=0, large_min=0):
+    return harness.run_worker(__file__, ["--worker", kind, "--lib", lib_path, "--set", set_name or "-", "--calls", str(args.calls),
+                                         "--tree-texts", str(TREE_TEXTS), "--sweep-bytes", str(sweep_bytes), "--large-min",
+                                         str(large_min)], timeout)
 
 
-def chosen_constants(crossings):
-    """(kLargeMaxN, kLargeManyMin) by the rule above from {text bytes: crossing or None}; (None, None) where no length has a
-    crossing at or below 64: the class is then not ready to be on by default."""
+def max_length_and_min_texts(crossings):
+    """(kLargeMaxN, kLargeManyMin) by this tool's own rule from {text bytes: crossing or None}: lengths with a crossing at or
+    below 64, a floor of FLOOR; (None, None) where no length has such a crossing: the class is then not ready to be on by
+    default."""
     kept = [n for n in SWEEP_BYTES if crossings[n] is not None and crossings[n] <= 64]
     if not kept:
         return None, None
-    max_n = max(kept)
-    among = [crossings[n] for n in SWEEP_BYTES if n <= max_n and crossings[n] is not None]
-    want, p = 2 * max(among), 1
-    while p < want:
-        p *= 2
-    return max_n, max(p, FLOOR)
+    among = [{"crossing": crossings[n]} for n in SWEEP_BYTES if n <= max(kept) and crossings[n] is not None]
+    return max(kept), max(harness.threshold_from(among, floor=1), FLOOR)
 
 
 def main():
     global TREE_TEXTS
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--parent-lib", help="libdq_sufsort_hip.so of the build to compare with (figure 1 needs it)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r11", "many_large.json"))
+    ap.add_argument("--out", default=os.path.join(harness.ROOT, "profiles", "r11", "many_large.json"))
     ap.add_argument("--calls", type=int, default=5)
     ap.add_argument("--tree-texts", type=int, default=TREE_TEXTS, help="texts of the tree_large set (its first so many)")
     ap.add_argument("--rounds", type=int, default=2, help="parent / new alternations per set")
@@ -297,64 +240,40 @@ def main():
         os.environ["DQ_DEBUG_FLAGS"] = "1"                   # (debug overrides are read only under it)
         os.environ["DQ_LARGE_MANY_MIN"] = str(args.large_min)
     if args.worker == "sweep":
-        worker_sweep(args.lib, args.calls, [args.sweep_bytes] if args.sweep_bytes else SWEEP_BYTES)
-        return
+        return worker_sweep(args.lib, args.calls, [args.sweep_bytes] if args.sweep_bytes else SWEEP_BYTES)
     if args.worker == "diff":
-        worker_diff(args.lib, args.calls)
-        return
+        return worker_diff(args.lib, args.calls)
     if args.worker:
-        (worker_host if args.worker == "host" else worker_device)(args.lib, args.set, args.calls)
-        return
-    from deltaq_amd import build as dq_build
-    new_lib = dq_build.LIB_PATH
-    if dq_build.is_stale():
-        raise SystemExit("build the library first (python -m deltaq_amd.build): this tool measures, it does not compile")
+        return (worker_host if args.worker == "host" else worker_device)(args.lib, args.set, args.calls)
+    result = harness.Result(args.out, "tools/kbench/many_large.py", calls=args.calls, tree_large_texts=args.tree_texts,
+                            DQ_LARGE_MANY_MIN_of_the_class_arms=class_request() or None, host_vs_parent={}, device_resident={})
     if args.diff_out:
-        diff_figure(args, new_lib)
-        return
-    result = {"tool": "tools/kbench/many_large.py", "calls_per_median": args.calls, "DQ_LARGE_MANY_MIN_of_the_class_arms": class_request() or None, "tree_large_texts": args.tree_texts,
-              "library_source_digest": dq_build._source_digest(), "host_vs_parent": {}, "device_resident": {}}
-
-    def save():
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:                       # (after every figure: a later failure loses nothing)
-            json.dump(result, f, indent=1)
-            f.write("\n")
-
+        return diff_figure(args, result.lib)
     if not args.no_sweep:
         sweep = {}
         result["sweep"] = {"text_bytes": list(SWEEP_BYTES), "by_text_bytes": sweep}
         for n in SWEEP_BYTES:
-            sweep.update(run_worker("sweep", new_lib, None, args.calls, 400, n))
-            save()
+            sweep.update(run_one(args, "sweep", result.lib, None, 400, n))
+            result.save()
         crossings = {n: sweep[str(n)]["crossing"] for n in SWEEP_BYTES}
-        max_n, min_texts = chosen_constants(crossings)
+        max_n, min_texts = max_length_and_min_texts(crossings)
         result["sweep"].update({"crossings": [crossings[n] for n in SWEEP_BYTES],
                                 "kLargeMaxN_from_this_sweep": max_n, "kLargeManyMin_from_this_sweep": min_texts})
         print("sweep crossings", crossings, "->", max_n, min_texts, flush=True)
-        save()
-    for set_name in [s for s in args.sets.split(",") if s]:
+        result.save()
+    sides = [("parent", args.parent_lib, 0), ("new", result.lib if args.parent_lib else None, class_request())]
+    sets = [s for s in args.sets.split(",") if s]
+    for set_name, runs in harness.compare(sets, sides, lambda s, who, path, ask: run_one(args, "host", path, s, 900, large_min=ask),
+                                          args.rounds):
         if args.parent_lib:
-            runs = {"parent": [], "new": []}
-            for _ in range(args.rounds):
-                for who, path, ask in (("parent", args.parent_lib, 0), ("new", new_lib, class_request())):
-                    runs[who].append(run_worker("host", path, set_name, args.calls, 900, large_min=ask))
-                    print(set_name, who, runs[who][-1]["ms_median"], "ms", flush=True)
-            digests = {r["outputs_sha256"] for rs in runs.values() for r in rs}
-            p_ms = statistics.median(r["ms_median"] for r in runs["parent"])
-            n_ms = statistics.median(r["ms_median"] for r in runs["new"])
-            spread = max(max(r["ms_median"] for r in rs) - min(r["ms_median"] for r in rs) for rs in runs.values())
+            first, last = runs["new"][0], runs["new"][-1]
             result["host_vs_parent"][set_name] = {
-                "texts": runs["new"][0]["texts"], "text_bytes": runs["new"][0]["text_bytes"], "large_texts": runs["new"][0]["large"],
-                "parent_ms": [r["ms_median"] for r in runs["parent"]], "new_ms": [r["ms_median"] for r in runs["new"]],
-                "parent_ms_median": p_ms, "new_ms_median": n_ms, "ratio_parent_over_new": round(p_ms / n_ms, 2),
-                "spread_ms": round(spread, 3), "faster_by_more_than_the_spread": bool(p_ms - n_ms > spread),
-                "parent_fastest_call_ms": min(r["ms_min"] for r in runs["parent"]),
-                "new_median_below_parent_fastest_call": bool(n_ms < min(r["ms_min"] for r in runs["parent"])),
-                "new_last_many_info": runs["new"][-1]["last_many_info"], "outputs_identical": len(digests) == 1}
-        result["device_resident"][set_name] = run_worker("device", new_lib, set_name, args.calls, 900)
+                "texts": first["texts"], "text_bytes": first["text_bytes"], "large_texts": first["large"],
+                **harness.judge(runs, STRICT, NAMES, spread=True),
+                "new_last_many_info": last["last_many_info"], "outputs_identical": harness.same_digests(runs, "outputs_sha256")}
+        result["device_resident"][set_name] = run_one(args, "device", result.lib, set_name, 900)
         print(set_name, "device", json.dumps(result["device_resident"][set_name]["variants"]), flush=True)
-        save()
+        result.save()
     print(json.dumps(result))
 
 
