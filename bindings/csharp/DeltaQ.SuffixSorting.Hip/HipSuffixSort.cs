@@ -41,6 +41,13 @@ public sealed class HipSuffixSort : ISuffixSort
     internal static extern int dq_bwt_hip_many_dev(IntPtr dBlocks, IntPtr dOffsets, int count, IntPtr dLast, IntPtr dOrigins, int device, IntPtr stream);
 
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    private static extern unsafe int dq_mtf_hip_many(byte* last, long* offsets, int count, ushort* syms, int* nsyms, uint* inUse, int device);
+
+    // (declared for hosts that keep their buffers on the device: device pointers, a hipStream_t or zero)
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern int dq_mtf_hip_many_dev(IntPtr dLast, IntPtr dOffsets, int count, IntPtr dSyms, IntPtr dNsyms, IntPtr dInUse, int device, IntPtr stream);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
     private static extern unsafe int dq_last_many_info(long* info, int count);
 
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
@@ -327,6 +334,81 @@ public sealed class HipSuffixSort : ISuffixSort
         for (int j = 0; j < count; j++)
         {
             result[j] = (last.AsSpan((int)offsets[j], blocks[j].Length).ToArray(), origins[j]);
+        }
+
+        return result;
+    }
+
+    /// <summary>
+    /// bzip2's symbol stream of many independent blocks in one native call (dq_mtf_hip_many): every byte replaced by its
+    /// place in the move-to-front list of the bytes in use, runs of place 0 as RUNA (0) / RUNB (1) digits, a place
+    /// p &gt;= 1 as symbol p + 1, and EOB = (bytes in use) + 1 at the end.  A block is what <see cref="BwtMany"/> returns
+    /// as Last, but any bytes are valid.  Entry j of the result holds the symbols written for blocks[j], EOB included
+    /// (none for an empty block), and 256 flags saying which bytes occur in it.  Every block must be shorter than 2^30
+    /// bytes.  The native library has no fallback for this call and neither has this method.
+    /// </summary>
+    public unsafe (ushort[] Symbols, bool[] InUse)[] MtfMany(IReadOnlyList<ReadOnlyMemory<byte>> blocks)
+    {
+        int count = blocks.Count;
+        var result = new (ushort[] Symbols, bool[] InUse)[count];
+        if (count == 0)
+        {
+            return result;
+        }
+
+        var offsets = new long[count + 1];
+        for (int j = 0; j < count; j++)
+        {
+            if (blocks[j].Length >= 1 << 30)
+            {
+                throw new ArgumentException("every block of a MtfMany call must be shorter than 2^30 bytes");
+            }
+
+            offsets[j + 1] = offsets[j] + blocks[j].Length;
+        }
+
+        long total = offsets[count];
+        if (total + count > Array.MaxLength)
+        {
+            throw new ArgumentException("the blocks of one MtfMany call must total less than 2^31 bytes");
+        }
+
+        // (at least one element each: the native side wants non-null pointers whenever there are blocks)
+        byte[] flat = new byte[Math.Max(total, 1)];
+        ushort[] syms = new ushort[total + count];
+        int[] nsyms = new int[count];
+        uint[] inUse = new uint[8 * count];
+        for (int j = 0; j < count; j++)
+        {
+            blocks[j].Span.CopyTo(flat.AsSpan((int)offsets[j], blocks[j].Length));
+        }
+
+        int rc;
+        fixed (byte* pLast = flat)
+        fixed (long* pOffsets = offsets)
+        fixed (ushort* pSyms = syms)
+        fixed (int* pNsyms = nsyms)
+        fixed (uint* pInUse = inUse)
+        {
+            rc = dq_mtf_hip_many(pLast, pOffsets, count, pSyms, pNsyms, pInUse, _device);
+        }
+
+        if (rc != 0)
+        {
+            string msg = Marshal.PtrToStringAnsi(dq_last_error()) ?? string.Empty;
+            throw new InvalidOperationException($"dq_mtf_hip_many failed ({rc}): {msg}");
+        }
+
+        for (int j = 0; j < count; j++)
+        {
+            var flags = new bool[256];
+            for (int c = 0; c < 256; c++)
+            {
+                flags[c] = ((inUse[8 * j + c / 32] >> (c % 32)) & 1u) != 0;
+            }
+
+            // block j owns the slots from offsets[j] + j on
+            result[j] = (syms.AsSpan((int)(offsets[j] + j), nsyms[j]).ToArray(), flags);
         }
 
         return result;

@@ -432,6 +432,28 @@ int32_t dq_bwt_hip_many_dev(const void *d_blocks, const void *d_offsets, int32_t
     }
 }
 
+int32_t dq_mtf_hip_many(const uint8_t *last, const int64_t *offsets, int32_t count, uint16_t *syms, int32_t *nsyms,
+                        uint32_t *in_use, int32_t device)
+{
+    EnvScope scope;
+    try {
+        return mtf_many_host(last, offsets, count, syms, nsyms, in_use, device);
+    } catch (const std::bad_alloc &) {
+        return fail(DQ_ERR_OOM, "many: host allocation failed");
+    }
+}
+
+int32_t dq_mtf_hip_many_dev(const void *d_last, const void *d_offsets, int32_t count, void *d_syms, void *d_nsyms,
+                            void *d_in_use, int32_t device, void *stream)
+{
+    EnvScope scope;
+    try {
+        return mtf_many_dev(d_last, d_offsets, count, d_syms, d_nsyms, d_in_use, device, stream);
+    } catch (const std::bad_alloc &) {
+        return fail(DQ_ERR_OOM, "many: host allocation failed");
+    }
+}
+
 int32_t dq_bsdiff_search_dev_i32(const void *d_old, int64_t n, const void *d_sa, const void *d_new, int64_t m,
                                  const int64_t *d_scans, int64_t scan0, int64_t count, int64_t cap, void *d_pos,
                                  void *d_len, int32_t device, void *stream)

@@ -32,7 +32,14 @@
 // dq_sufsort_hip_many_i32 (the medium classes' scratch blocks; the segmented sort's workspace where that class is on).  One
 // block above a chunk goes alone with the same 11 bytes per byte, and the device sorter's workspace for 2 b.
 // 32-bit indices: a block has fewer than 2^30 bytes.  dq_small_many.h includes this file at its end.
+// On request (BwtIo::syms, the host form's: phase 4 of the framed many-file diffs under kMtfManyOn / DQ_NO_MTF_MANY=0)
+// mtf_many_kernel (dq_mtf_many.h) follows bwt_many_kernel on the same stream: its symbols, counts and in-use maps go into
+// the suffix-array region, which is dead by then, and travel back instead of `last`; the origins, the flag word and the
+// single wait stay as they are.  Its two classes take their work from bwt_many_kernel's own list, which is longest first:
+// the long class its head, the short class the rest.
 #pragma once
+
+#include "dq_mtf_many.h"
 
 namespace dq {
 
@@ -153,6 +160,9 @@ struct BwtIo {
     const uint8_t *blocks;
     uint8_t *last;
     int32_t *origins;
+    uint16_t *syms = nullptr;           // set (host form only): the symbol streams come back instead of `last`, dq_mtf_hip_many's layout
+    int32_t *nsyms = nullptr;
+    uint32_t *in_use = nullptr;
 };
 
 // One group: blocks [0, cnt) at io's pointers, drel their DOUBLED offsets relative to the first, plan the sort's plan of
@@ -168,10 +178,13 @@ inline int bwt_group(DeviceCtx &c, hipStream_t st, int dev, const BwtIo &io, con
     build_work_lists(work, cnt, [&](int32_t j) { return rel[(size_t)j + 1] > rel[(size_t)j] ? 0 : -1; },
                      [&](int32_t j) { return rel[(size_t)j + 1] - rel[(size_t)j]; });
     const int listed = work.class_count[0];
-    const bool shared = plan.shared();
+    const bool shared = plan.shared(), mtf = io.host && io.syms != nullptr;
+    // the symbols' areas inside the suffix-array region (8 bytes per block byte: only a group of nearly empty blocks needs more)
+    const size_t m_syms = align_up(2 * ((size_t)bytes + (size_t)cnt)), m_nsyms = align_up((size_t)cnt * sizeof(int32_t)),
+                 m_in_use = align_up((size_t)cnt * 8 * sizeof(uint32_t));
     const size_t b_blk = io.host ? align_up((size_t)bytes + 64) : 0, b_org = io.host ? align_up((size_t)cnt * sizeof(int32_t)) : 0,
                  b_off = align_up(rel.size() * sizeof(int64_t)), b_dbl = align_up(2 * (size_t)bytes + 64),
-                 b_sa = align_up(2 * (size_t)bytes * sizeof(int32_t)), b_work = many_ctl_bytes(listed),
+                 b_sa = std::max(align_up(2 * (size_t)bytes * sizeof(int32_t)), mtf ? m_syms + m_nsyms + m_in_use : 0), b_work = many_ctl_bytes(listed),
                  b_ctl = shared ? many_ctl_bytes(plan.listed()) : 0, b_scratch = shared ? many_scratch_bytes(c, plan) : 0,
                  b_large = shared ? many_large_bytes(plan, drel.data()) : 0;
     DQ_TRY(ensure_ws(c, b_blk + b_org + 2 * b_off + b_dbl + b_sa + b_work + b_ctl + b_scratch + b_large));
@@ -189,6 +202,11 @@ inline int bwt_group(DeviceCtx &c, hipStream_t st, int dev, const BwtIo &io, con
     const uint8_t *d_in = io.host ? d_blk : io.blocks;
     uint8_t *d_last = io.host ? d_blk : io.last;               // (the host form's copy of the blocks is dead once it is doubled)
     int32_t *d_origins = io.host ? d_org : io.origins;
+    uint16_t *d_syms = reinterpret_cast<uint16_t *>(d_sa);
+    int32_t *d_nsyms = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(d_sa) + m_syms);
+    uint32_t *d_in_use = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(d_sa) + m_syms + m_nsyms);
+    int n_long = 0;                                             // (the list is longest first: the long class is its head)
+    while (mtf && n_long < listed && rel[(size_t)work.order[(size_t)n_long] + 1] - rel[(size_t)work.order[(size_t)n_long]] > mtf_short_max()) ++n_long;
     uint32_t bad = 0;
     t_sort_info = {};
     auto run = [&]() -> int {
@@ -213,10 +231,20 @@ inline int bwt_group(DeviceCtx &c, hipStream_t st, int dev, const BwtIo &io, con
         LAUNCH(L, DQ_K_SMALL_MANY, listed, bytes * 11,
                hipLaunchKernelGGL(bwt_many_kernel, dim3((unsigned)grid), dim3(kBwtThreads), 0, st, d_dbl, d_doff, d_order, listed,
                                   d_next, d_sa, d_off, d_last, d_origins, d_flag));
+        if (mtf) {                                                  // (behind bwt_many_kernel: the suffix arrays are dead)
+            HIP_TRY(hipMemsetAsync(d_nsyms, 0, m_nsyms + m_in_use, st));             // what an empty block keeps
+            DQ_TRY(launch_mtf(c, st, dev, d_last, d_off, d_order + n_long, listed - n_long, d_order, n_long, d_next + 32, bytes,
+                              d_syms, d_nsyms, d_in_use));
+        }
         // (one checked step: a failure must not leave a copy into the caller's arrays in flight behind the return)
         hipError_t e = hipSuccess;
         auto keep = [&](hipError_t x) { if (e == hipSuccess) e = x; };
-        if (io.host) {
+        if (mtf) {
+            keep(hipMemcpyAsync(io.syms, d_syms, 2 * ((size_t)bytes + (size_t)cnt), hipMemcpyDeviceToHost, st));
+            keep(hipMemcpyAsync(io.nsyms, d_nsyms, (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            keep(hipMemcpyAsync(io.in_use, d_in_use, (size_t)cnt * 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            keep(hipMemcpyAsync(io.origins, d_org, (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        } else if (io.host) {
             keep(hipMemcpyAsync(io.last, d_blk, (size_t)bytes, hipMemcpyDeviceToHost, st));
             keep(hipMemcpyAsync(io.origins, d_org, (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         }
@@ -244,7 +272,11 @@ inline int bwt_many_walk(int dev, void *stream, const BwtIo &io, const int64_t *
     DQ_TRY(init_ctx(c, dev));
     if (c.ncu <= 0 && hipDeviceGetAttribute(&c.ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) c.ncu = 0;
     hipStream_t st = stream ? (hipStream_t)stream : c.stream;
-    auto group_io = [&](int32_t i) { return BwtIo{io.host, io.blocks + off[i], io.last + off[i], io.origins + i}; };
+    auto group_io = [&](int32_t i) {
+        BwtIo g{io.host, io.blocks + off[i], io.last ? io.last + off[i] : nullptr, io.origins + i};
+        if (io.syms) { g.syms = io.syms + off[i] + i; g.nsyms = io.nsyms + i; g.in_use = io.in_use + 8 * (size_t)i; }
+        return g;
+    };
     auto single = [&](int32_t i) -> int {
         const int64_t n2 = doff[(size_t)i + 1] - doff[(size_t)i];
         if (n2 == 0) return DQ_OK;
@@ -276,17 +308,24 @@ inline int check_bwt_offsets(const int64_t *off, int32_t count)
 
 // host buffers in / out
 int bwt_many_host(const uint8_t *blocks, const int64_t *offsets, int32_t count, uint8_t *last, int32_t *origins, int32_t device,
-                  int64_t *shared_out, bool large_by_default)
+                  int64_t *shared_out, bool large_by_default, const MtfOut *mtf)
 {
     if (shared_out) *shared_out = 0;
     if (count < 0) return fail(DQ_ERR_BAD_ARGS, "negative count");
     if (count == 0) return DQ_OK;
-    if (!blocks || !offsets || !last || !origins) return fail(DQ_ERR_BAD_ARGS, "null buffer");
+    if (!blocks || !offsets || !origins || (mtf ? !mtf->syms || !mtf->nsyms || !mtf->in_use : !last)) return fail(DQ_ERR_BAD_ARGS, "null buffer");
     DQ_TRY(check_bwt_offsets(offsets, count));
     int dev = 0;
     DQ_TRY(resolve_device(device, &dev));
     std::fill(origins, origins + count, -1);                    // (what an empty block keeps)
-    return bwt_many_walk(dev, nullptr, BwtIo{true, blocks, last, origins}, offsets, count, shared_out, large_by_default);
+    BwtIo io{true, blocks, last, origins};
+    if (mtf) {
+        io.last = nullptr;
+        io.syms = mtf->syms; io.nsyms = mtf->nsyms; io.in_use = mtf->in_use;
+        std::fill(mtf->nsyms, mtf->nsyms + count, 0);           // (what a block keeps that no group holds: an empty one)
+        std::fill(mtf->in_use, mtf->in_use + 8 * (size_t)count, 0u);
+    }
+    return bwt_many_walk(dev, nullptr, io, offsets, count, shared_out, large_by_default);
 }
 
 // device buffers in / out

@@ -479,32 +479,20 @@ inline void make_code_lengths(uint8_t *len, const int32_t *freq, int alpha, int 
 // sa_of_doubled(text, n2, sa): suffix array (int32, n2 entries) of the n2 = 2 * nblock bytes block+block.
 using DoubledSorter = std::function<int(const uint8_t *text, int64_t n2, int32_t *sa)>;
 
-// One block, behind its transform: `blk` is the run-length coded data (nblock bytes), crc the CRC of the original bytes
-// it stands for, `last` the last column of its sorted rotations (nblock bytes) and `origin` the row of the block itself
-// among them (bzip2's origPtr) -- from the host's walk below, or straight from the device (dq_bwt_hip_many:
-// dq_bsdiff_create_many's blocks).  MTF, Huffman tables, bits.  sort_ms / last_ms: what the transform and the walk took
-// (DQ_TRACE prints them).
-inline int compress_block_bwt(BitWriter &bw, const std::vector<uint8_t> &blk, uint32_t crc, const uint8_t *last, int32_t origin,
-                              double sort_ms = 0, double last_ms = 0)
+// The symbol stream of one block behind its transform -- bzip2's move-to-front with zero runs in bijective base 2 (RUNA = 0,
+// RUNB = 1), a place p >= 1 as symbol p + 1, EOB = (bytes in use) + 1 at the end -- from `last`, the block's last column
+// (nblock bytes; any bytes: the stage asks nothing of them): in_use[c] says whether byte c occurs, mtfv receives the
+// symbols, EOB included.  What dq_mtf_hip_many computes on the device (dq_mtf_many.h) is this, symbol for symbol.
+inline void mtf_block_host(const uint8_t *last, int32_t nblock, bool in_use[256], std::vector<uint16_t> &mtfv)
 {
-    const int32_t nblock = (int32_t)blk.size();
-    if (origin < 0 || origin >= nblock) return -3;
-    const int32_t orig_ptr = origin;
-    const bool trace = flags().trace.has_value();
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto t_prev = now();
-    double t_ph[5] = {sort_ms, last_ms, 0, 0, 0};           // sort, last column, MTF, tables, bits
-    auto lap = [&](int k) { const auto t = now(); t_ph[k] += std::chrono::duration<double, std::milli>(t - t_prev).count(); t_prev = t; };
-    // ---- symbols in use, MTF, RUNA / RUNB ----
-    bool in_use[256] = {false};
-    for (int32_t i = 0; i < nblock; ++i) in_use[blk[(size_t)i]] = true;
+    for (int i = 0; i < 256; ++i) in_use[i] = false;
+    for (int32_t i = 0; i < nblock; ++i) in_use[last[(size_t)i]] = true;
     uint8_t unseq_to_seq[256];
     int n_in_use = 0;
     for (int i = 0; i < 256; ++i) if (in_use[i]) unseq_to_seq[i] = (uint8_t)n_in_use++;
-    const int eob = n_in_use + 1, alpha = n_in_use + 2;
-    std::vector<uint16_t> mtfv;
+    const int eob = n_in_use + 1;
+    mtfv.clear();
     mtfv.reserve((size_t)nblock + 1);
-    int32_t mtf_freq[kMaxAlpha] = {0};
     {
         // Move-to-front without the list: a symbol's place in it is the number of symbols used more recently, so every
         // symbol keeps the time of its last use (16 bits, renumbered before they run out) and a place is one sweep of
@@ -523,7 +511,6 @@ inline int compress_block_bwt(BitWriter &bw, const std::vector<uint8_t> &blk, ui
             for (;;) {                                          // bijective base 2: RUNA = 1, RUNB = 2
                 const uint16_t s = (uint16_t)(zrun & 1);
                 mtfv.push_back(s);
-                mtf_freq[s]++;
                 if (zrun < 2) break;
                 zrun = (zrun - 2) / 2;
             }
@@ -555,14 +542,41 @@ inline int compress_block_bwt(BitWriter &bw, const std::vector<uint8_t> &blk, ui
             }
             used[c] = (int16_t)++now;
             mtfv.push_back((uint16_t)(j + 1));
-            mtf_freq[j + 1]++;
         }
         flush_zeros();
         mtfv.push_back((uint16_t)eob);
-        mtf_freq[eob]++;
     }
-    const int32_t n_mtf = (int32_t)mtfv.size();
-    lap(2);
+}
+
+// what DQ_TRACE prints about the stages in front of compress_block_mtf (nothing else reads it)
+struct BlockTrace {
+    int32_t nblock = 0;
+    double sort_ms = 0, last_ms = 0, mtf_ms = 0;
+};
+
+// One block from its symbol stream: `mtfv` is n_mtf symbols as mtf_block_host writes them (from the host, or straight from
+// the device: dq_mtf_hip_many's), in_use the bytes of the block, crc the CRC of the original bytes the block stands for
+// and `origin` the row of the block itself among its sorted rotations (bzip2's origPtr; its range is the caller's to
+// check).  Huffman tables, bits.  A stream that does not end in EOB or names a symbol outside the alphabet is refused (-3)
+// before anything is written.
+inline int compress_block_mtf(BitWriter &bw, uint32_t crc, int32_t origin, const bool in_use[256], const uint16_t *mtfv, int32_t n_mtf,
+                              const BlockTrace &tr = BlockTrace())
+{
+    const int32_t orig_ptr = origin;
+    const bool trace = flags().trace.has_value();
+    auto now = [] { return std::chrono::steady_clock::now(); };
+    auto t_prev = now();
+    double t_ph[3] = {0, 0, 0};                             // (unused), tables, bits
+    auto lap = [&](int k) { const auto t1 = now(); t_ph[k] += std::chrono::duration<double, std::milli>(t1 - t_prev).count(); t_prev = t1; };
+    int n_in_use = 0;
+    for (int i = 0; i < 256; ++i) n_in_use += in_use[i] ? 1 : 0;
+    const int eob = n_in_use + 1, alpha = n_in_use + 2;
+    if (n_mtf < 1 || mtfv[(size_t)n_mtf - 1] != eob) return -3;
+    int32_t mtf_freq[kMaxAlpha] = {0};
+    for (int32_t i = 0; i < n_mtf; ++i) {
+        if (mtfv[(size_t)i] >= alpha) return -3;
+        mtf_freq[mtfv[(size_t)i]]++;
+    }
     // ---- coding tables: initial split by frequency, 4 refinement rounds over groups of 50 symbols ----
     const int n_groups = n_mtf < 200 ? 2 : n_mtf < 600 ? 3 : n_mtf < 1200 ? 4 : n_mtf < 2400 ? 5 : 6;
     uint8_t len[kMaxGroups][kMaxAlpha];
@@ -619,7 +633,7 @@ inline int compress_block_bwt(BitWriter &bw, const std::vector<uint8_t> &blk, ui
             c <<= 1;
         }
     }
-    lap(3);
+    lap(1);
     // ---- the block ----
     bw.bits(24, (uint32_t)(kBlockMagic >> 24));
     bw.bits(24, (uint32_t)(kBlockMagic & 0xffffff));
@@ -668,12 +682,32 @@ inline int compress_block_bwt(BitWriter &bw, const std::vector<uint8_t> &blk, ui
         const int32_t a = g * kGroupSize, b = std::min<int32_t>(a + kGroupSize, n_mtf);
         for (int32_t i = a; i < b; ++i) bw.bits(len[t][mtfv[(size_t)i]], code[t][mtfv[(size_t)i]]);
     }
-    lap(4);
+    lap(2);
     if (trace)
         fprintf(stderr, "[dq] bzip2 block of %d bytes (%d symbols): transform %.2f ms, last column %.2f, move to front %.2f, tables %.2f, bits %.2f; "
-                "done at %.3f ms of the clock\n", nblock, n_mtf, t_ph[0], t_ph[1], t_ph[2], t_ph[3], t_ph[4],
+                "done at %.3f ms of the clock\n", tr.nblock, n_mtf, tr.sort_ms, tr.last_ms, tr.mtf_ms, t_ph[1], t_ph[2],
                 std::chrono::duration<double, std::milli>(now().time_since_epoch()).count() - 1e3 * (double)(long long)(std::chrono::duration<double>(now().time_since_epoch()).count() / 100.0) * 100.0);
     return 0;
+}
+
+// One block, behind its transform: `blk` is the run-length coded data (nblock bytes), crc the CRC of the original bytes
+// it stands for, `last` the last column of its sorted rotations (nblock bytes) and `origin` the row of the block itself
+// among them (bzip2's origPtr) -- from the host's walk below, or straight from the device (dq_bwt_hip_many:
+// dq_bsdiff_create_many's blocks).  mtf_block_host, then compress_block_mtf.  sort_ms / last_ms: what the transform and
+// the walk took (DQ_TRACE prints them).
+inline int compress_block_bwt(BitWriter &bw, const std::vector<uint8_t> &blk, uint32_t crc, const uint8_t *last, int32_t origin,
+                              double sort_ms = 0, double last_ms = 0)
+{
+    const int32_t nblock = (int32_t)blk.size();
+    if (origin < 0 || origin >= nblock) return -3;
+    const auto t0 = std::chrono::steady_clock::now();
+    bool in_use[256];
+    std::vector<uint16_t> mtfv;
+    mtf_block_host(last, nblock, in_use, mtfv);
+    BlockTrace t;
+    t.nblock = nblock; t.sort_ms = sort_ms; t.last_ms = last_ms;
+    t.mtf_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return compress_block_mtf(bw, crc, origin, in_use, mtfv.data(), (int32_t)mtfv.size(), t);
 }
 
 // ... from the finished suffix array `sa` (2 * nblock entries) of block+block, whoever sorted it -- the caller's sorter
@@ -916,6 +950,25 @@ public:
         try {
             BitWriter w(b.bytes);
             b.rc = compress_block_bwt(w, b.rle, b.crc, last, origin);
+            b.nbits = w.total;
+            w.flush();
+            std::vector<uint8_t>().swap(b.rle);
+        } catch (...) {
+            b.rc = -3;
+        }
+    }
+
+    // ... or its symbol stream (dq_mtf_hip_many's layout: n_mtf symbols, EOB included, and the eight in-use words)
+    void encode_block_mtf(size_t i, int32_t origin, const uint32_t *in_use_words, const uint16_t *mtfv, int32_t n_mtf)
+    {
+        Block &b = blocks[i];
+        b.claimed.store(1);
+        try {
+            BitWriter w(b.bytes);
+            bool in_use[256];
+            for (int c = 0; c < 256; ++c) in_use[c] = (in_use_words[c / 32] >> (c % 32)) & 1u;
+            const bool fits = origin >= 0 && (size_t)origin < b.rle.size() && n_mtf >= 1 && (size_t)n_mtf <= b.rle.size() + 1;
+            b.rc = fits ? compress_block_mtf(w, b.crc, origin, in_use, mtfv, n_mtf) : -3;
             b.nbits = w.total;
             w.flush();
             std::vector<uint8_t>().swap(b.rle);

@@ -1408,7 +1408,8 @@ int frame_patch(const bsdiff::RawStreams &raw, int64_t m, int dev, std::vector<u
 //      large texts, dq_large_many.h, is off here unless the debug flag DQ_LARGE_MANY_MIN asks for it).  With the device
 //      transform on (kBwtManyOn, dq_runtime.h: off by default; DQ_NO_BWT_MANY=0) the blocks go up undoubled instead and
 //      ONE bwt_many_host call (dq_bwt_many.h) doubles, sorts -- through the same walker, plan and launches -- and
-//      transforms them on the device.
+//      transforms them on the device; with kMtfManyOn / DQ_NO_MTF_MANY=0 (off by default too) move-to-front and run coding
+//      follow there (dq_mtf_many.h) and phase 5 starts from the symbol streams (StreamEncoder::encode_block_mtf).
 //   5. host threads: each block finished from its suffix array (with the device transform: from its last column and
 //      origin row), header + three streams into the pair's slot.
 // Device memory per chunk: old + new + 4 bytes of suffix array per byte of old + one int32 per byte of new for the
@@ -1627,10 +1628,17 @@ int diff_many_frame(const ManyFiles &f, const ManyChunk &k, int dev, std::vector
     // dq_sufsort_hip_many_i32's body and walked by the framing threads.  Either way the same walker cuts the same doubled
     // lengths into the same chunks and launches.
     const bool on_device = flags().no_bwt_many ? *flags().no_bwt_many == 0 : kBwtManyOn;
+    // ... and with move-to-front on the device too (kMtfManyOn, dq_runtime.h: off by default; DQ_NO_MTF_MANY=0) the
+    // symbol streams come back instead of the last columns (mtf_many_kernel behind bwt_many_kernel, dq_mtf_many.h): block
+    // `place` has its symbols at bsyms[boff[place] / 2 + place ...), bnsyms[place] of them, and binuse[8 place ...).
+    const bool mtf_on_device = on_device && (flags().no_mtf_many ? *flags().no_mtf_many == 0 : kMtfManyOn);
     const int64_t per = on_device ? 2 : 1;                 // boff counts doubled bytes: a block's place in btext is boff / per
     std::vector<uint8_t> btext((size_t)(boff.back() / per));
     std::vector<int32_t> bsa(on_device ? 0 : (size_t)boff.back());
-    std::vector<uint8_t> blast(on_device ? btext.size() : 0);
+    std::vector<uint8_t> blast(on_device && !mtf_on_device ? btext.size() : 0);
+    std::vector<uint16_t> bsyms(mtf_on_device ? btext.size() + (size_t)nblocks : 0);
+    std::vector<int32_t> bnsyms(mtf_on_device ? (size_t)nblocks : 0);
+    std::vector<uint32_t> binuse(mtf_on_device ? 8 * (size_t)nblocks : 0);
     std::vector<int32_t> borigin(on_device ? (size_t)nblocks : 0);
     diff_many_parallel(cnt, [&](int64_t j) {
         ManyPair &w = out[(size_t)j];
@@ -1651,7 +1659,9 @@ int diff_many_frame(const ManyFiles &f, const ManyChunk &k, int dev, std::vector
     if (on_device) {
         std::vector<int64_t> half((size_t)nblocks + 1);
         for (int64_t b = 0; b <= nblocks; ++b) half[(size_t)b] = boff[(size_t)b] / 2;
-        rc = bwt_many_host(btext.data(), half.data(), (int32_t)nblocks, blast.data(), borigin.data(), dev, &shared, /*large_by_default=*/false);
+        const MtfOut mtf{bsyms.data(), bnsyms.data(), binuse.data()};
+        rc = bwt_many_host(btext.data(), half.data(), (int32_t)nblocks, blast.data(), borigin.data(), dev, &shared, /*large_by_default=*/false,
+                           mtf_on_device ? &mtf : nullptr);
     } else
         rc = sufsort_many_host(btext.data(), boff.data(), (int32_t)nblocks, bsa.data(), dev, &shared, /*large_by_default=*/false);
     if (rc != DQ_OK) return rc;
@@ -1670,7 +1680,10 @@ int diff_many_frame(const ManyFiles &f, const ManyChunk &k, int dev, std::vector
             for (int s = 0; s < 3; ++s) {
                 for (size_t b = 0; b < w.enc[s]->block_count(); ++b, ++at) {
                     const int64_t place = bplace[(size_t)at];
-                    if (on_device) w.enc[s]->encode_block_bwt(b, blast.data() + boff[(size_t)place] / 2, borigin[(size_t)place]);
+                    if (mtf_on_device)
+                        w.enc[s]->encode_block_mtf(b, borigin[(size_t)place], binuse.data() + 8 * (size_t)place,
+                                                   bsyms.data() + boff[(size_t)place] / 2 + place, bnsyms[(size_t)place]);
+                    else if (on_device) w.enc[s]->encode_block_bwt(b, blast.data() + boff[(size_t)place] / 2, borigin[(size_t)place]);
                     else w.enc[s]->encode_block_sorted(b, bsa.data() + boff[(size_t)place]);
                 }
                 if (w.enc[s]->finish(z[s]) != 0) { w.rc = DQ_ERR_HIP; w.err = "bzip2 block transform failed"; return; }

@@ -116,6 +116,7 @@ struct DeviceCtx {
     int many_groups[kAllClasses] = {};  // workgroups of each length class of small_many_kernel and mid_many_kernel the device holds at once (0: not asked yet)
     int check_many_groups[kCheckClasses] = {};  // ... and of each length class of sufcheck_many_kernel (dq_sufcheck_many.h)
     int bwt_many_groups = 0;            // ... and of bwt_many_kernel (dq_bwt_many.h)
+    int mtf_many_groups[2] = {0, 0};    // ... and of mtf_many_kernel's short and long class (dq_mtf_many.h)
     int anchor_many_groups = 0;         // ... and of anchor_many_kernel (dq_anchor_many.h)
     int anchor_mid_many_groups = 0;     // ... and of anchor_mid_many_kernel
     int anchor_index_many_groups[2] = {0, 0};   // ... and of anchor_index_many_kernel at 256 and 512 threads (dq_anchor_many.h)
@@ -489,8 +490,14 @@ int sufsort_many_dev(const void *d_texts, const void *d_offsets, int32_t count, 
 // The Burrows-Wheeler transform of many blocks (dq_bwt_many.h, in dq_sorter_i32.hip): the bodies of dq_bwt_hip_many /
 // _many_dev.  They sort the doubled blocks through the launches above, so they add to t_many_info as those do (the
 // lengths there are the doubled ones); shared_out and large_by_default as sufsort_many_host's.
+// mtf (optional, the host form's): the blocks' symbol streams come back instead of `last` (which may then be null).
+struct MtfOut {                         // dq_mtf_hip_many's three arrays in its layout; slots behind a block's written symbols are undefined here
+    uint16_t *syms;
+    int32_t *nsyms;
+    uint32_t *in_use;
+};
 int bwt_many_host(const uint8_t *blocks, const int64_t *offsets, int32_t count, uint8_t *last, int32_t *origins, int32_t device,
-                  int64_t *shared_out = nullptr, bool large_by_default = true);
+                  int64_t *shared_out = nullptr, bool large_by_default = true, const MtfOut *mtf = nullptr);
 int bwt_many_dev(const void *d_blocks, const void *d_offsets, int32_t count, void *d_last, void *d_origins, int32_t device,
                  void *stream);
 // kBwtManyOn true: the framed many-file diffs transform their blocks there (dq_diff.hip: diff_many_frame).
@@ -501,6 +508,19 @@ int bwt_many_dev(const void *d_blocks, const void *d_offsets, int32_t count, voi
 // index/fixed4k@1 -- calls of 40 .. 120 ms of which the new route saves 1 .. 11 ms, less than their run-to-run spread --
 // have their median above the parent's fastest run: false by the rule (docs/ROUNDS.md, round 23).
 constexpr bool kBwtManyOn = false;
+
+// Move-to-front and zero-run coding of many blocks (dq_mtf_many.h, in dq_sorter_i32.hip): the bodies of dq_mtf_hip_many /
+// _many_dev.  No record, no profile category of their own.
+int mtf_many_host(const uint8_t *last, const int64_t *offsets, int32_t count, uint16_t *syms, int32_t *nsyms, uint32_t *in_use,
+                  int32_t device);
+int mtf_many_dev(const void *d_last, const void *d_offsets, int32_t count, void *d_syms, void *d_nsyms, void *d_in_use, int32_t device,
+                 void *stream);
+// kMtfManyOn true: where the framed many-file diffs transform their blocks on the device (kBwtManyOn / DQ_NO_BWT_MANY=0),
+// mtf_many_kernel runs behind bwt_many_kernel and the symbol streams come back instead of the last columns (dq_diff.hip:
+// diff_many_frame).  DQ_NO_MTF_MANY=0 switches that on and =1 off, whatever this says.  The rule is kBwtManyOn's, on the
+// framed sets of tools/kbench/mtf_many.py (profiles/r25/mtf_many.json); false until all of them are measured (docs/ROUNDS.md,
+// round 25).
+constexpr bool kMtfManyOn = false;
 
 // LDSSChecker.Check on the device (dq_sufcheck.hip): DQ_OK with the verdict (DQ_SUFCHECK_*) in *result, or an error
 template <typename IdxT>

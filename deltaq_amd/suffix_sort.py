@@ -46,6 +46,14 @@ def unpack_bwt_many(last: np.ndarray, origins: np.ndarray, off: np.ndarray) -> l
     return [(last[off[j]:off[j + 1]], int(origins[j])) for j in range(len(off) - 1)]
 
 
+def unpack_mtf_many(syms: np.ndarray, nsyms: np.ndarray, in_use: np.ndarray, off: np.ndarray) -> list:
+    """dq_mtf_hip_many's flat results as MtfMany returns them: [(the nsyms[j] symbols of block j: a uint16 view, its 256
+    in-use flags: a bool array)].  Block j's slots begin at off[j] + j; in_use has eight words per block, bit c % 32 of word
+    c / 32 for byte c."""
+    bits = np.unpackbits(np.ascontiguousarray(in_use, dtype="<u4").view(np.uint8), bitorder="little").astype(bool)
+    return [(syms[off[j] + j:off[j] + j + int(nsyms[j])], bits[256 * j:256 * (j + 1)]) for j in range(len(off) - 1)]
+
+
 def _is_torch_tensor(x) -> bool:
     return type(x).__module__.startswith("torch") and hasattr(x, "data_ptr")
 
@@ -239,6 +247,67 @@ class HipSuffixSort:
         _abi.check(self._lib.dq_bwt_hip_many_dev(bp.data_ptr(), offsets.data_ptr(), count, lp.data_ptr(),
                                                  origins.data_ptr(), dev, stream))
         return last, origins
+
+    # -- move-to-front and zero-run coding of many blocks (the stage behind BwtMany) ------------------------------------
+    def MtfMany(self, blocks):
+        """bzip2's symbol stream of many independent blocks, on the device: per block, every byte replaced by its place in
+        the move-to-front list of the bytes in use, runs of place 0 as RUNA (0) / RUNB (1) digits, a place p >= 1 as
+        symbol p + 1, and EOB = (bytes in use) + 1 at the end.  A block is what ``BwtMany`` returns as ``last``, but any
+        bytes are valid.
+
+        ``MtfMany([b0, b1, ...])`` -- bytes-like objects / numpy uint8 arrays, each shorter than 2^30 bytes -- returns a
+        list of ``(symbols, in_use)``: a uint16 array view of the symbols written, EOB included (none for an empty
+        block), and a 256-entry bool array (``dq_mtf_hip_many``).  ``MtfMany((last_tensor, offsets_tensor))`` -- a uint8
+        and an int64 torch GPU tensor in ``SortMany``'s device layout -- returns ``(syms, nsyms, in_use)`` tensors: int16
+        holding the uint16 symbols, block j's from slot ``offsets[j] + j`` on and ``nsyms[j]`` (int32) of them, and eight
+        int32 in-use words per block (``dq_mtf_hip_many_dev``, on the current torch stream).
+        """
+        if isinstance(blocks, tuple) and len(blocks) == 2 and _is_torch_tensor(blocks[0]):
+            return self._mtf_many_device(*blocks)
+        arrs = [_as_text(b) for b in blocks]
+        if any(a.ndim != 1 for a in arrs):
+            raise TypeError("every block must be one-dimensional")
+        if any(a.size >= BWT_MAX_N for a in arrs):
+            raise ValueError("MtfMany takes the blocks BwtMany takes: every block must be shorter than 2^30 bytes")
+        count = len(arrs)
+        off = np.zeros(count + 1, dtype=np.int64)
+        if count:
+            np.cumsum([a.size for a in arrs], out=off[1:])
+        total = int(off[-1])
+        # (a buffer of no bytes has no address: the library wants non-null pointers whenever there are blocks)
+        flat = np.concatenate(arrs) if total else np.zeros(1, np.uint8)
+        syms = np.empty(total + count + 1, dtype=np.uint16)
+        nsyms = np.empty(max(count, 1), dtype=np.int32)
+        in_use = np.empty(8 * max(count, 1), dtype=np.uint32)
+        _abi.check(self._lib.dq_mtf_hip_many(flat.ctypes.data, off.ctypes.data, count, syms.ctypes.data, nsyms.ctypes.data,
+                                             in_use.ctypes.data, self.device))
+        return unpack_mtf_many(syms, nsyms, in_use, off)
+
+    mtf_many = MtfMany
+
+    def _mtf_many_device(self, last, offsets):
+        import torch
+
+        if not _is_torch_tensor(offsets):
+            raise TypeError("device blocks need a device offsets tensor")
+        if last.dtype != torch.uint8 or last.dim() != 1 or not last.is_contiguous():
+            raise TypeError("device blocks must be a contiguous 1-D uint8 tensor")
+        if offsets.dtype != torch.int64 or offsets.dim() != 1 or not offsets.is_contiguous() or offsets.numel() < 1:
+            raise TypeError("offsets must be a contiguous 1-D int64 tensor of count + 1 entries")
+        if not last.is_cuda or offsets.device != last.device:
+            raise TypeError("blocks and offsets must live on the same GPU")
+        count = offsets.numel() - 1
+        total = last.numel()
+        syms = torch.empty(total + count + 1, dtype=torch.int16, device=last.device)
+        nsyms = torch.zeros(count, dtype=torch.int32, device=last.device)
+        in_use = torch.zeros(8 * count, dtype=torch.int32, device=last.device)
+        if count == 0:
+            return syms, nsyms, in_use
+        dev, stream = _device_and_stream(last)
+        lp = last if total else torch.zeros(1, dtype=torch.uint8, device=last.device)
+        _abi.check(self._lib.dq_mtf_hip_many_dev(lp.data_ptr(), offsets.data_ptr(), count, syms.data_ptr(), nsyms.data_ptr(),
+                                                 in_use.data_ptr(), dev, stream))
+        return syms, nsyms, in_use
 
     # -- LDSSChecker.Check(T, SA)   (test/DeltaQ.SuffixSorting.LibDivSufSort.Tests/LDSSChecker.cs:23-119) --------
     def Check(self, text, suffixes) -> int:

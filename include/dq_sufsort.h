@@ -148,6 +148,45 @@ int32_t dq_bwt_hip_many(const uint8_t *blocks, const int64_t *offsets, int32_t c
 int32_t dq_bwt_hip_many_dev(const void *d_blocks, const void *d_offsets, int32_t count, void *d_last, void *d_origins,
                             int32_t device, void *stream);
 
+/* ---- move-to-front and zero-run coding of many independent blocks in shared launches (the stage behind the transform) --
+ * `last` is not what an entropy coder reads: the symbol stream behind move-to-front and zero-run coding is.  Every block
+ * is independent, and inside a block a byte's place in the list is the number of bytes used more recently, which last-use
+ * times decide: mtf_many_kernel keeps them in registers, four per lane, and codes 64 bytes a step per wave; a block of up
+ * to 8192 bytes is one wave's, a longer one goes to eight waves in segments of 2048 bytes whose entering states come
+ * from one table exchange per 16 384 bytes.  Blocks are claimed from work lists; nobody waits for anybody.
+ * Input layout as dq_bwt_hip_many: blocks back to back, offsets[count + 1] int64, offsets[0] == 0, never decreasing.  A
+ * block is what dq_bwt_hip_many wrote to `last`, but any bytes are valid input.
+ * Definition, bzip2's: for block j of n > 0 bytes
+ *   in_use[8 j + c / 32] has bit c % 32 set iff byte c occurs in the block; the bytes in use, ascending, are numbered
+ *     0 .. k - 1, and EOB is k + 1;
+ *   the list starts as 0, 1, .., k - 1; every block byte is replaced by its place p in the list and moved to the front;
+ *   a maximal run of r places equal to 0 becomes the digits of r in bijective base 2, least significant first, RUNA = symbol
+ *     0 and RUNB = symbol 1: r = 1 -> 0; 2 -> 1; 3 -> 0 0; 4 -> 1 0;
+ *   a place p >= 1 becomes symbol p + 1; EOB is appended at the end.
+ * Output layout: block j owns the n_j + 1 slots syms[offsets[j] + j .. offsets[j + 1] + j + 1] exclusive of the last -- a
+ * block never yields more than n + 1 symbols, a run of r zeros having at most r digits; nsyms[j] receives the number of
+ * symbols written, EOB included.  Slots behind the written symbols are not written, nor anything outside a block's own
+ * slots.  n == 0: nsyms[j] = 0, its eight in_use words are 0 and no symbol is written.  The 258 symbol frequencies of a
+ * block are not returned: 1 KiB per block would outweigh the symbols of a short one, and a coder's one pass over `syms`
+ * gives them.
+ * Errors, all before any device use in the host form: count < 0, a NULL pointer with count > 0, offsets[0] != 0,
+ * decreasing offsets -> DQ_ERR_BAD_ARGS; a block of 2^30 bytes or more -> DQ_ERR_TOO_LARGE: the blocks dq_bwt_hip_many
+ * accepts, no more.  count == 0 is a no-op.  There is no CPU fallback.
+ *   dq_mtf_hip_many      host pointers.  The blocks travel in chunks of whole blocks: at most 64 MiB of block bytes and
+ *                        2^20 blocks, a block above that alone; one wait per chunk.  Device memory per chunk of b bytes
+ *                        in c blocks, l of them non-empty: b + 64 blocks, 2 [b + c] symbols, 4 c counts, 32 c in-use
+ *                        words, 8 [c + 1] offsets, 4 l + 256 of work list -- each rounded up to 256 bytes; 192 MiB for a
+ *                        full chunk of 4 KiB blocks.  1 byte up per block byte, 2 [b + c] + 36 c bytes down; the written
+ *                        symbols are handed on from a host copy of the chunk's.
+ *   dq_mtf_hip_many_dev  device pointers on `device`, d_offsets too: the library fetches it once and checks it before it
+ *                        launches anything; work on `stream`, NULL = the library's; returns after the stream has
+ *                        drained.  Device memory: the work list alone, 4 l + 256 bytes.
+ * Neither has a record of its own, and their kernels are profiled under small_many_kernel's category. */
+int32_t dq_mtf_hip_many(const uint8_t *last, const int64_t *offsets, int32_t count, uint16_t *syms, int32_t *nsyms,
+                        uint32_t *in_use, int32_t device);
+int32_t dq_mtf_hip_many_dev(const void *d_last, const void *d_offsets, int32_t count, void *d_syms, void *d_nsyms,
+                            void *d_in_use, int32_t device, void *stream);
+
 /* ---- Diff.Create's match search on the device-resident suffix array ----------
  * Replaces, for a batch of scan positions, the reference's
  *   Search(I, oldData, newData[scan..], 0, oldData.Length, out pos)          src/DeltaQ.BsDiff/Diff.cs:267-298
