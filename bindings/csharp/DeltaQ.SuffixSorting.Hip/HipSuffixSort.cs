@@ -48,6 +48,16 @@ public sealed class HipSuffixSort : ISuffixSort
     internal static extern int dq_mtf_hip_many_dev(IntPtr dLast, IntPtr dOffsets, int count, IntPtr dSyms, IntPtr dNsyms, IntPtr dInUse, int device, IntPtr stream);
 
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern long dq_huff_hip_bound(long n);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    private static extern unsafe int dq_huff_hip_many(ushort* syms, int* nsyms, uint* inUse, long* offsets, int count, uint* crcs, int* origins, long* outOffsets, byte* output, int* nbits, int device);
+
+    // (declared for hosts that keep their buffers on the device: device pointers, a hipStream_t or zero)
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern int dq_huff_hip_many_dev(IntPtr dSyms, IntPtr dNsyms, IntPtr dInUse, IntPtr dOffsets, int count, IntPtr dCrcs, IntPtr dOrigins, IntPtr dOutOffsets, IntPtr dOut, IntPtr dNbits, int device, IntPtr stream);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
     private static extern unsafe int dq_last_many_info(long* info, int count);
 
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
@@ -413,6 +423,114 @@ public sealed class HipSuffixSort : ISuffixSort
 
         return result;
     }
+
+    /// <summary>
+    /// The bits of many bzip2 blocks from their symbol streams in one native call (dq_huff_hip_many): per block what a
+    /// bzip2 compressor writes from the 48-bit block magic to the last code -- coding tables, selectors and codes by
+    /// libbz2's rules, bit for bit.  streams[j] is what <see cref="MtfMany"/> returned for block j, lengths[j] the
+    /// block's length in bytes (at most 900 000), crcs[j] the CRC its header carries and origins[j] its origin row from
+    /// <see cref="BwtMany"/>.  Entry j of the result holds the bytes (most significant bit first, the last byte
+    /// zero-padded) and the bit count; an empty block gives no bytes and 0, a refused one (a stream that does not end in
+    /// EOB or names a symbol outside its alphabet, an origin outside the block) no bytes and -1.  The native library has
+    /// no fallback for this call and neither has this method.
+    /// </summary>
+    public unsafe (byte[] Bits, int BitCount)[] HuffMany(IReadOnlyList<(ushort[] Symbols, bool[] InUse)> streams, IReadOnlyList<int> lengths,
+                                                        IReadOnlyList<uint> crcs, IReadOnlyList<int> origins)
+    {
+        int count = streams.Count;
+        if (lengths.Count != count || crcs.Count != count || origins.Count != count)
+        {
+            throw new ArgumentException("one length, one CRC and one origin per block");
+        }
+
+        var result = new (byte[] Bits, int BitCount)[count];
+        if (count == 0)
+        {
+            return result;
+        }
+
+        var offsets = new long[count + 1];
+        var outOffsets = new long[count + 1];
+        for (int j = 0; j < count; j++)
+        {
+            long bound = lengths[j] < 0 ? -1 : dq_huff_hip_bound(lengths[j]);
+            if (bound < 0)
+            {
+                throw new ArgumentException("every block of a HuffMany call must have 0 to 900 000 bytes");
+            }
+
+            if (streams[j].InUse.Length != 256)
+            {
+                throw new ArgumentException("every block needs 256 in-use flags");
+            }
+
+            offsets[j + 1] = offsets[j] + lengths[j];
+            outOffsets[j + 1] = outOffsets[j] + bound;
+        }
+
+        long total = offsets[count];
+        if (total + count > Array.MaxLength || outOffsets[count] > Array.MaxLength)
+        {
+            throw new ArgumentException("the blocks of one HuffMany call must total less than 2^31 bytes of symbols and of bits");
+        }
+
+        // (at least one element each: the native side wants non-null pointers whenever there are blocks)
+        ushort[] syms = new ushort[total + count];
+        int[] nsyms = new int[count];
+        uint[] inUse = new uint[8 * count];
+        uint[] crcWords = new uint[count];
+        int[] originWords = new int[count];
+        byte[] output = new byte[Math.Max(outOffsets[count], 1)];
+        int[] nbits = new int[count];
+        for (int j = 0; j < count; j++)
+        {
+            ushort[] s = streams[j].Symbols;
+            // block j owns the lengths[j] + 1 slots from offsets[j] + j on; a longer stream is refused by its count
+            s.AsSpan(0, (int)Math.Min(s.Length, (long)lengths[j] + 1)).CopyTo(syms.AsSpan((int)(offsets[j] + j)));
+            nsyms[j] = s.Length;
+            for (int c = 0; c < 256; c++)
+            {
+                if (streams[j].InUse[c])
+                {
+                    inUse[8 * j + c / 32] |= 1u << (c % 32);
+                }
+            }
+
+            crcWords[j] = crcs[j];
+            originWords[j] = origins[j];
+        }
+
+        int rc;
+        fixed (ushort* pSyms = syms)
+        fixed (int* pNsyms = nsyms)
+        fixed (uint* pInUse = inUse)
+        fixed (long* pOffsets = offsets)
+        fixed (uint* pCrcs = crcWords)
+        fixed (int* pOrigins = originWords)
+        fixed (long* pOutOffsets = outOffsets)
+        fixed (byte* pOut = output)
+        fixed (int* pNbits = nbits)
+        {
+            rc = dq_huff_hip_many(pSyms, pNsyms, pInUse, pOffsets, count, pCrcs, pOrigins, pOutOffsets, pOut, pNbits, _device);
+        }
+
+        if (rc != 0)
+        {
+            string msg = Marshal.PtrToStringAnsi(dq_last_error()) ?? string.Empty;
+            throw new InvalidOperationException($"dq_huff_hip_many failed ({rc}): {msg}");
+        }
+
+        for (int j = 0; j < count; j++)
+        {
+            int bytes = nbits[j] > 0 ? (nbits[j] + 7) / 8 : 0;
+            result[j] = (output.AsSpan((int)outOffsets[j], bytes).ToArray(), nbits[j]);
+        }
+
+        return result;
+    }
+
+    /// <summary>dq_huff_hip_bound: bytes that always suffice for the bits of a block of n bytes; -1 outside 0 .. 900 000.</summary>
+    public static long HuffBound(long n) => dq_huff_hip_bound(n);
 
     /// <summary>
     /// <c>LDSSChecker.Check(T, SA)</c> (test/DeltaQ.SuffixSorting.LibDivSufSort.Tests/LDSSChecker.cs:23-119) on the

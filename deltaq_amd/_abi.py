@@ -33,7 +33,8 @@ CATEGORY_ALIASES = {"mid_many_kernel": "small_many_kernel", "large_text_kernel":
                     "large_doubled_kernel": "small_many_kernel", "large_key0_kernel": "small_many_kernel",
                     "large_key2_kernel": "small_many_kernel", "large_twin_kernel": "small_many_kernel",
                     "large_scatter_kernel": "small_many_kernel", "double_blocks_kernel": "small_many_kernel",
-                    "bwt_many_kernel": "small_many_kernel", "mtf_many_kernel": "small_many_kernel"}
+                    "bwt_many_kernel": "small_many_kernel", "mtf_many_kernel": "small_many_kernel",
+                    "huff_many_kernel": "small_many_kernel"}
 MID_MAX_N = 65536         # kMidMaxN: longest text of the medium class of the many-texts launches
 LARGE_MAX_N = 4 << 20     # kLargeMaxN: longest text of their segmented sort (dq_large_many.h)
 
@@ -45,6 +46,7 @@ EXPORTS = (
     "dq_sufsort_hip_batch_i32",
     "dq_sufsort_hip_many_i32", "dq_sufsort_hip_many_dev_i32", "dq_last_many_info",
     "dq_bwt_hip_many", "dq_bwt_hip_many_dev", "dq_mtf_hip_many", "dq_mtf_hip_many_dev",
+    "dq_huff_hip_bound", "dq_huff_hip_many", "dq_huff_hip_many_dev",
     "dq_sufcheck_hip_i32", "dq_sufcheck_hip_i64", "dq_sufcheck_hip_dev_i32", "dq_sufcheck_hip_dev_i64",
     "dq_sufcheck_hip_many_i32", "dq_sufcheck_hip_many_dev_i32", "dq_last_check_many_info",
     "dq_bsdiff_search_dev_i32", "dq_bsdiff_search_dev_i64", "dq_bsdiff_search_i32", "dq_bsdiff_search_i64",
@@ -171,6 +173,12 @@ def load() -> ctypes.CDLL:
     L.dq_mtf_hip_many.argtypes = [vp, vp, i32, vp, vp, vp, i32]
     L.dq_mtf_hip_many_dev.restype = i32
     L.dq_mtf_hip_many_dev.argtypes = [vp, vp, i32, vp, vp, vp, i32, vp]
+    L.dq_huff_hip_bound.restype = i64
+    L.dq_huff_hip_bound.argtypes = [i64]
+    L.dq_huff_hip_many.restype = i32
+    L.dq_huff_hip_many.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32]
+    L.dq_huff_hip_many_dev.restype = i32
+    L.dq_huff_hip_many_dev.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, vp]
     for name in ("dq_bsdiff_search_dev_i32", "dq_bsdiff_search_dev_i64"):
         getattr(L, name).restype = i32
         getattr(L, name).argtypes = [vp, i64, vp, vp, i64, vp, i64, i64, i64, vp, vp, i32, vp]

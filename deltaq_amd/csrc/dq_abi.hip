@@ -454,6 +454,32 @@ int32_t dq_mtf_hip_many_dev(const void *d_last, const void *d_offsets, int32_t c
     }
 }
 
+int64_t dq_huff_hip_bound(int64_t n) { return huff_many_bound(n); }
+
+int32_t dq_huff_hip_many(const uint16_t *syms, const int32_t *nsyms, const uint32_t *in_use, const int64_t *offsets, int32_t count,
+                         const uint32_t *crcs, const int32_t *origins, const int64_t *out_offsets, uint8_t *out, int32_t *nbits,
+                         int32_t device)
+{
+    EnvScope scope;
+    try {
+        return huff_many_host(syms, nsyms, in_use, offsets, count, crcs, origins, out_offsets, out, nbits, device);
+    } catch (const std::bad_alloc &) {
+        return fail(DQ_ERR_OOM, "many: host allocation failed");
+    }
+}
+
+int32_t dq_huff_hip_many_dev(const void *d_syms, const void *d_nsyms, const void *d_in_use, const void *d_offsets, int32_t count,
+                             const void *d_crcs, const void *d_origins, const void *d_out_offsets, void *d_out, void *d_nbits,
+                             int32_t device, void *stream)
+{
+    EnvScope scope;
+    try {
+        return huff_many_dev(d_syms, d_nsyms, d_in_use, d_offsets, count, d_crcs, d_origins, d_out_offsets, d_out, d_nbits, device, stream);
+    } catch (const std::bad_alloc &) {
+        return fail(DQ_ERR_OOM, "many: host allocation failed");
+    }
+}
+
 int32_t dq_bsdiff_search_dev_i32(const void *d_old, int64_t n, const void *d_sa, const void *d_new, int64_t m,
                                  const int64_t *d_scans, int64_t scan0, int64_t count, int64_t cap, void *d_pos,
                                  void *d_len, int32_t device, void *stream)

@@ -37,9 +37,13 @@
 // the suffix-array region, which is dead by then, and travel back instead of `last`; the origins, the flag word and the
 // single wait stay as they are.  Its two classes take their work from bwt_many_kernel's own list, which is longest first:
 // the long class its head, the short class the rest.
+// On a further request (BwtIo::bits, the host form's: kHuffManyOn / DQ_NO_HUFF_MANY=0) huff_many_kernel (dq_huff_many.h)
+// follows mtf_many_kernel on the same stream, on the same list: the blocks' CRCs go up, 4 bytes per block, and the
+// blocks' bits and bit counts travel back instead of the symbols, which never leave the device.
 #pragma once
 
 #include "dq_mtf_many.h"
+#include "dq_huff_many.h"
 
 namespace dq {
 
@@ -163,6 +167,10 @@ struct BwtIo {
     uint16_t *syms = nullptr;           // set (host form only): the symbol streams come back instead of `last`, dq_mtf_hip_many's layout
     int32_t *nsyms = nullptr;
     uint32_t *in_use = nullptr;
+    const uint32_t *crcs = nullptr;     // set (host form only): the blocks' BITS come back instead (dq_huff_hip_many's layout), no symbols
+    const int64_t *slots = nullptr;     // the group's cnt + 1 slot offsets as the caller counts them; bits: the group's first slot
+    uint8_t *bits = nullptr;
+    int32_t *nbits = nullptr;
 };
 
 // One group: blocks [0, cnt) at io's pointers, drel their DOUBLED offsets relative to the first, plan the sort's plan of
@@ -178,7 +186,13 @@ inline int bwt_group(DeviceCtx &c, hipStream_t st, int dev, const BwtIo &io, con
     build_work_lists(work, cnt, [&](int32_t j) { return rel[(size_t)j + 1] > rel[(size_t)j] ? 0 : -1; },
                      [&](int32_t j) { return rel[(size_t)j + 1] - rel[(size_t)j]; });
     const int listed = work.class_count[0];
-    const bool shared = plan.shared(), mtf = io.host && io.syms != nullptr;
+    const bool shared = plan.shared(), huff = io.host && io.bits != nullptr, mtf = huff || (io.host && io.syms != nullptr);
+    std::vector<int64_t> slot_rel(huff ? (size_t)cnt + 1 : 0);
+    for (size_t j = 0; j < slot_rel.size(); ++j) slot_rel[j] = io.slots[j] - io.slots[0];
+    const size_t h_bits = huff ? (size_t)slot_rel[(size_t)cnt] : 0;
+    // the bits' areas: CRCs, slot offsets, slots, bit counts, selectors
+    const size_t b_hword = huff ? align_up((size_t)cnt * sizeof(int32_t)) : 0, b_hoff = huff ? align_up(slot_rel.size() * sizeof(int64_t)) : 0,
+                 b_hbits = huff ? align_up(h_bits + 8) : 0, b_hsel = huff ? huff_sel_bytes(bytes, cnt) : 0;
     // the symbols' areas inside the suffix-array region (8 bytes per block byte: only a group of nearly empty blocks needs more)
     const size_t m_syms = align_up(2 * ((size_t)bytes + (size_t)cnt)), m_nsyms = align_up((size_t)cnt * sizeof(int32_t)),
                  m_in_use = align_up((size_t)cnt * 8 * sizeof(uint32_t));
@@ -187,7 +201,7 @@ inline int bwt_group(DeviceCtx &c, hipStream_t st, int dev, const BwtIo &io, con
                  b_sa = std::max(align_up(2 * (size_t)bytes * sizeof(int32_t)), mtf ? m_syms + m_nsyms + m_in_use : 0), b_work = many_ctl_bytes(listed),
                  b_ctl = shared ? many_ctl_bytes(plan.listed()) : 0, b_scratch = shared ? many_scratch_bytes(c, plan) : 0,
                  b_large = shared ? many_large_bytes(plan, drel.data()) : 0;
-    DQ_TRY(ensure_ws(c, b_blk + b_org + 2 * b_off + b_dbl + b_sa + b_work + b_ctl + b_scratch + b_large));
+    DQ_TRY(ensure_ws(c, b_blk + b_org + 2 * b_off + b_dbl + b_sa + b_work + b_ctl + b_scratch + b_large + 2 * b_hword + b_hoff + b_hbits + b_hsel));
     char *at = c.ws;
     auto carve = [&](size_t b) { char *p = at; at += b; return p; };
     uint8_t *d_blk = reinterpret_cast<uint8_t *>(carve(b_blk));
@@ -197,6 +211,11 @@ inline int bwt_group(DeviceCtx &c, hipStream_t st, int dev, const BwtIo &io, con
     uint8_t *d_dbl = reinterpret_cast<uint8_t *>(carve(b_dbl));
     int32_t *d_sa = reinterpret_cast<int32_t *>(carve(b_sa));
     char *d_work = carve(b_work), *d_ctl = carve(b_ctl), *d_scratch = carve(b_scratch), *d_large = carve(b_large);
+    uint32_t *d_crcs = reinterpret_cast<uint32_t *>(carve(b_hword));
+    int32_t *d_nbits = reinterpret_cast<int32_t *>(carve(b_hword));
+    int64_t *d_slots = reinterpret_cast<int64_t *>(carve(b_hoff));
+    uint8_t *d_bits = reinterpret_cast<uint8_t *>(carve(b_hbits));
+    uint8_t *d_sel = reinterpret_cast<uint8_t *>(carve(b_hsel));
     uint32_t *d_next = reinterpret_cast<uint32_t *>(d_work), *d_flag = d_next + 16;
     int32_t *d_order = reinterpret_cast<int32_t *>(d_work + kManyCounterBytes);
     const uint8_t *d_in = io.host ? d_blk : io.blocks;
@@ -236,10 +255,21 @@ inline int bwt_group(DeviceCtx &c, hipStream_t st, int dev, const BwtIo &io, con
             DQ_TRY(launch_mtf(c, st, dev, d_last, d_off, d_order + n_long, listed - n_long, d_order, n_long, d_next + 32, bytes,
                               d_syms, d_nsyms, d_in_use));
         }
+        if (huff) {                                                 // (behind mtf_many_kernel, on bwt_many_kernel's list)
+            HIP_TRY(hipMemcpyAsync(d_crcs, io.crcs, (size_t)cnt * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(d_slots, slot_rel.data(), slot_rel.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemsetAsync(d_nbits, 0, (size_t)cnt * sizeof(int32_t), st));          // what an empty block keeps
+            DQ_TRY(launch_huff(c, st, dev, d_syms, d_nsyms, d_in_use, d_off, d_order, listed, d_next + 24, d_crcs, d_origins, d_slots,
+                               d_bits, d_nbits, d_sel, bytes));
+        }
         // (one checked step: a failure must not leave a copy into the caller's arrays in flight behind the return)
         hipError_t e = hipSuccess;
         auto keep = [&](hipError_t x) { if (e == hipSuccess) e = x; };
-        if (mtf) {
+        if (huff) {
+            if (h_bits) keep(hipMemcpyAsync(io.bits, d_bits, h_bits, hipMemcpyDeviceToHost, st));
+            keep(hipMemcpyAsync(io.nbits, d_nbits, (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            keep(hipMemcpyAsync(io.origins, d_org, (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        } else if (mtf) {
             keep(hipMemcpyAsync(io.syms, d_syms, 2 * ((size_t)bytes + (size_t)cnt), hipMemcpyDeviceToHost, st));
             keep(hipMemcpyAsync(io.nsyms, d_nsyms, (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
             keep(hipMemcpyAsync(io.in_use, d_in_use, (size_t)cnt * 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -275,6 +305,7 @@ inline int bwt_many_walk(int dev, void *stream, const BwtIo &io, const int64_t *
     auto group_io = [&](int32_t i) {
         BwtIo g{io.host, io.blocks + off[i], io.last ? io.last + off[i] : nullptr, io.origins + i};
         if (io.syms) { g.syms = io.syms + off[i] + i; g.nsyms = io.nsyms + i; g.in_use = io.in_use + 8 * (size_t)i; }
+        if (io.bits) { g.crcs = io.crcs + i; g.slots = io.slots + i; g.bits = io.bits + io.slots[i]; g.nbits = io.nbits + i; }
         return g;
     };
     auto single = [&](int32_t i) -> int {
@@ -308,18 +339,25 @@ inline int check_bwt_offsets(const int64_t *off, int32_t count)
 
 // host buffers in / out
 int bwt_many_host(const uint8_t *blocks, const int64_t *offsets, int32_t count, uint8_t *last, int32_t *origins, int32_t device,
-                  int64_t *shared_out, bool large_by_default, const MtfOut *mtf)
+                  int64_t *shared_out, bool large_by_default, const MtfOut *mtf, const HuffOut *huff)
 {
     if (shared_out) *shared_out = 0;
     if (count < 0) return fail(DQ_ERR_BAD_ARGS, "negative count");
     if (count == 0) return DQ_OK;
-    if (!blocks || !offsets || !origins || (mtf ? !mtf->syms || !mtf->nsyms || !mtf->in_use : !last)) return fail(DQ_ERR_BAD_ARGS, "null buffer");
+    if (!blocks || !offsets || !origins || (huff ? !huff->crcs || !huff->slots || !huff->bits || !huff->nbits
+                                                 : mtf ? !mtf->syms || !mtf->nsyms || !mtf->in_use : !last))
+        return fail(DQ_ERR_BAD_ARGS, "null buffer");
     DQ_TRY(check_bwt_offsets(offsets, count));
+    if (huff) DQ_TRY(check_huff_offsets(offsets, huff->slots, count));
     int dev = 0;
     DQ_TRY(resolve_device(device, &dev));
     std::fill(origins, origins + count, -1);                    // (what an empty block keeps)
     BwtIo io{true, blocks, last, origins};
-    if (mtf) {
+    if (huff) {
+        io.last = nullptr;
+        io.crcs = huff->crcs; io.slots = huff->slots; io.bits = huff->bits; io.nbits = huff->nbits;
+        std::fill(huff->nbits, huff->nbits + count, 0);         // (what a block keeps that no group holds: an empty one)
+    } else if (mtf) {
         io.last = nullptr;
         io.syms = mtf->syms; io.nsyms = mtf->nsyms; io.in_use = mtf->in_use;
         std::fill(mtf->nsyms, mtf->nsyms + count, 0);           // (what a block keeps that no group holds: an empty one)

@@ -977,6 +977,25 @@ public:
         }
     }
 
+    // ... or its finished bits (dq_huff_hip_many's: `nbits` bits from the block magic to the last code, most significant
+    // first; block_crc(i) is the CRC they must carry).  A refused block (nbits < 0) is compress_block_mtf's -3.
+    uint32_t block_crc(size_t i) const { return blocks[i].crc; }
+    void encode_block_bits(size_t i, const uint8_t *bits, int32_t nbits)
+    {
+        Block &b = blocks[i];
+        b.claimed.store(1);
+        try {
+            BitWriter w(b.bytes);
+            if (nbits > 0) w.append(bits, (uint64_t)nbits);
+            b.rc = nbits > 0 ? 0 : -3;
+            b.nbits = w.total;
+            w.flush();
+            std::vector<uint8_t>().swap(b.rle);
+        } catch (...) {
+            b.rc = -3;
+        }
+    }
+
     // (tests: the run-length coded blocks and their CRCs as the pre-pass cut them, before anything is encoded --
     // constructed with hold = true, so that no block leaves for an encoder thread)
     void hold_blocks() { hold = true; }

@@ -1409,7 +1409,9 @@ int frame_patch(const bsdiff::RawStreams &raw, int64_t m, int dev, std::vector<u
 //      transform on (kBwtManyOn, dq_runtime.h: off by default; DQ_NO_BWT_MANY=0) the blocks go up undoubled instead and
 //      ONE bwt_many_host call (dq_bwt_many.h) doubles, sorts -- through the same walker, plan and launches -- and
 //      transforms them on the device; with kMtfManyOn / DQ_NO_MTF_MANY=0 (off by default too) move-to-front and run coding
-//      follow there (dq_mtf_many.h) and phase 5 starts from the symbol streams (StreamEncoder::encode_block_mtf).
+//      follow there (dq_mtf_many.h) and phase 5 starts from the symbol streams (StreamEncoder::encode_block_mtf); with
+//      kHuffManyOn / DQ_NO_HUFF_MANY=0 on top (off as well) coding tables and bits follow too (dq_huff_many.h) and phase 5
+//      only strings the blocks' bits together (StreamEncoder::encode_block_bits).
 //   5. host threads: each block finished from its suffix array (with the device transform: from its last column and
 //      origin row), header + three streams into the pair's slot.
 // Device memory per chunk: old + new + 4 bytes of suffix array per byte of old + one int32 per byte of new for the
@@ -1632,13 +1634,34 @@ int diff_many_frame(const ManyFiles &f, const ManyChunk &k, int dev, std::vector
     // symbol streams come back instead of the last columns (mtf_many_kernel behind bwt_many_kernel, dq_mtf_many.h): block
     // `place` has its symbols at bsyms[boff[place] / 2 + place ...), bnsyms[place] of them, and binuse[8 place ...).
     const bool mtf_on_device = on_device && (flags().no_mtf_many ? *flags().no_mtf_many == 0 : kMtfManyOn);
+    // ... and with the coding tables on the device as well (kHuffManyOn, dq_runtime.h: off; DQ_NO_HUFF_MANY=0) the blocks'
+    // bits come back instead of the symbols (huff_many_kernel behind mtf_many_kernel, dq_huff_many.h): block `place` has
+    // bnbits[place] bits from bbits[bslot[place]] on, its CRC went up in bcrc[place].
+    const bool huff_on_device = mtf_on_device && (flags().no_huff_many ? *flags().no_huff_many == 0 : kHuffManyOn);
     const int64_t per = on_device ? 2 : 1;                 // boff counts doubled bytes: a block's place in btext is boff / per
     std::vector<uint8_t> btext((size_t)(boff.back() / per));
     std::vector<int32_t> bsa(on_device ? 0 : (size_t)boff.back());
     std::vector<uint8_t> blast(on_device && !mtf_on_device ? btext.size() : 0);
-    std::vector<uint16_t> bsyms(mtf_on_device ? btext.size() + (size_t)nblocks : 0);
-    std::vector<int32_t> bnsyms(mtf_on_device ? (size_t)nblocks : 0);
-    std::vector<uint32_t> binuse(mtf_on_device ? 8 * (size_t)nblocks : 0);
+    const bool syms_back = mtf_on_device && !huff_on_device;
+    std::vector<uint16_t> bsyms(syms_back ? btext.size() + (size_t)nblocks : 0);
+    std::vector<int32_t> bnsyms(syms_back ? (size_t)nblocks : 0);
+    std::vector<uint32_t> binuse(syms_back ? 8 * (size_t)nblocks : 0);
+    std::vector<int64_t> bslot(huff_on_device ? (size_t)nblocks + 1 : 0);
+    std::vector<uint32_t> bcrc(huff_on_device ? (size_t)nblocks : 0);
+    std::vector<int32_t> bnbits(huff_on_device ? (size_t)nblocks : 0);
+    if (huff_on_device) {
+        for (int64_t b = 0; b < nblocks; ++b) {
+            const int64_t need = huff_many_bound((boff[(size_t)b + 1] - boff[(size_t)b]) / 2);
+            if (need < 0) return fail(DQ_ERR_TOO_LARGE, "a bzip2 block exceeds 900 000 bytes");
+            bslot[(size_t)b + 1] = bslot[(size_t)b] + need;
+        }
+        for (ManyPair &w : out) {
+            int64_t at = w.first_block;
+            for (int s = 0; s < 3; ++s)
+                for (size_t b = 0; b < w.enc[s]->block_count(); ++b) bcrc[(size_t)bplace[(size_t)at++]] = w.enc[s]->block_crc(b);
+        }
+    }
+    std::vector<uint8_t> bbits(huff_on_device ? (size_t)bslot.back() + 8 : 0);
     std::vector<int32_t> borigin(on_device ? (size_t)nblocks : 0);
     diff_many_parallel(cnt, [&](int64_t j) {
         ManyPair &w = out[(size_t)j];
@@ -1660,8 +1683,9 @@ int diff_many_frame(const ManyFiles &f, const ManyChunk &k, int dev, std::vector
         std::vector<int64_t> half((size_t)nblocks + 1);
         for (int64_t b = 0; b <= nblocks; ++b) half[(size_t)b] = boff[(size_t)b] / 2;
         const MtfOut mtf{bsyms.data(), bnsyms.data(), binuse.data()};
+        const HuffOut huff{bcrc.data(), bslot.data(), bbits.data(), bnbits.data()};
         rc = bwt_many_host(btext.data(), half.data(), (int32_t)nblocks, blast.data(), borigin.data(), dev, &shared, /*large_by_default=*/false,
-                           mtf_on_device ? &mtf : nullptr);
+                           mtf_on_device ? &mtf : nullptr, huff_on_device ? &huff : nullptr);
     } else
         rc = sufsort_many_host(btext.data(), boff.data(), (int32_t)nblocks, bsa.data(), dev, &shared, /*large_by_default=*/false);
     if (rc != DQ_OK) return rc;
@@ -1680,7 +1704,8 @@ int diff_many_frame(const ManyFiles &f, const ManyChunk &k, int dev, std::vector
             for (int s = 0; s < 3; ++s) {
                 for (size_t b = 0; b < w.enc[s]->block_count(); ++b, ++at) {
                     const int64_t place = bplace[(size_t)at];
-                    if (mtf_on_device)
+                    if (huff_on_device) w.enc[s]->encode_block_bits(b, bbits.data() + bslot[(size_t)place], bnbits[(size_t)place]);
+                    else if (mtf_on_device)
                         w.enc[s]->encode_block_mtf(b, borigin[(size_t)place], binuse.data() + 8 * (size_t)place,
                                                    bsyms.data() + boff[(size_t)place] / 2 + place, bnsyms[(size_t)place]);
                     else if (on_device) w.enc[s]->encode_block_bwt(b, blast.data() + boff[(size_t)place] / 2, borigin[(size_t)place]);

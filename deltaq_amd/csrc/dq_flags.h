@@ -47,6 +47,7 @@ struct Flags {
     std::optional<int> no_check_many;       // DQ_NO_CHECK_MANY: 1: every text of dq_sufcheck_hip_many_* through the single-text check; 0: every class shares launches however few its texts
     std::optional<int> no_bwt_many;         // DQ_NO_BWT_MANY: 1: the blocks of the framed many-file diffs doubled on the host and sorted through dq_sufsort_hip_many_i32's body; 0: transformed on the device (dq_bwt_many.h); unset: what kBwtManyOn says (dq_runtime.h)
     std::optional<int> no_mtf_many;         // DQ_NO_MTF_MANY: 0: where those blocks are transformed on the device, move-to-front and run coding follow there too (dq_mtf_many.h) and the symbol streams come back; 1: the last columns come back; unset: what kMtfManyOn says (dq_runtime.h)
+    std::optional<int> no_huff_many;        // DQ_NO_HUFF_MANY: 0: where those blocks' move-to-front runs on the device, coding tables and bits follow there too (dq_huff_many.h) and the blocks' bits come back; 1: the symbol streams come back; unset: what kHuffManyOn says (dq_runtime.h)
     std::optional<int> mtf_short_max;       // DQ_MTF_SHORT_MAX: longest block of mtf_many_kernel's short class (one wave per workgroup), >= 0; unset: kMtfShortMax
     bool no_list_buffers = false;           // DQ_NO_LIST_BUFFERS: the workspace without the third list buffer
     bool text_copy = false;                 // DQ_TEXT_COPY: copy the text in front instead of in the first pass
@@ -158,6 +159,7 @@ inline Flags read_flags()
     f.no_check_many = num("DQ_NO_CHECK_MANY", 0, 1);
     f.no_bwt_many = num("DQ_NO_BWT_MANY", 0, 1);
     f.no_mtf_many = num("DQ_NO_MTF_MANY", 0, 1);
+    f.no_huff_many = num("DQ_NO_HUFF_MANY", 0, 1);
     f.mtf_short_max = num("DQ_MTF_SHORT_MAX", 0);
     f.no_list_buffers = on("DQ_NO_LIST_BUFFERS");
     f.text_copy = on("DQ_TEXT_COPY");

@@ -117,6 +117,7 @@ struct DeviceCtx {
     int check_many_groups[kCheckClasses] = {};  // ... and of each length class of sufcheck_many_kernel (dq_sufcheck_many.h)
     int bwt_many_groups = 0;            // ... and of bwt_many_kernel (dq_bwt_many.h)
     int mtf_many_groups[2] = {0, 0};    // ... and of mtf_many_kernel's short and long class (dq_mtf_many.h)
+    int huff_many_groups = 0;           // ... and of huff_many_kernel (dq_huff_many.h)
     int anchor_many_groups = 0;         // ... and of anchor_many_kernel (dq_anchor_many.h)
     int anchor_mid_many_groups = 0;     // ... and of anchor_mid_many_kernel
     int anchor_index_many_groups[2] = {0, 0};   // ... and of anchor_index_many_kernel at 256 and 512 threads (dq_anchor_many.h)
@@ -496,8 +497,15 @@ struct MtfOut {                         // dq_mtf_hip_many's three arrays in its
     int32_t *nsyms;
     uint32_t *in_use;
 };
+// huff (optional, the host form's; it overrides mtf): the blocks' bits come back instead, in dq_huff_hip_many's layout.
+struct HuffOut {
+    const uint32_t *crcs;               // the CRC every block's header carries
+    const int64_t *slots;               // count + 1 slot offsets: 0 first, multiples of 8, every slot >= dq_huff_hip_bound of its block
+    uint8_t *bits;
+    int32_t *nbits;                     // -1: a refused block
+};
 int bwt_many_host(const uint8_t *blocks, const int64_t *offsets, int32_t count, uint8_t *last, int32_t *origins, int32_t device,
-                  int64_t *shared_out = nullptr, bool large_by_default = true, const MtfOut *mtf = nullptr);
+                  int64_t *shared_out = nullptr, bool large_by_default = true, const MtfOut *mtf = nullptr, const HuffOut *huff = nullptr);
 int bwt_many_dev(const void *d_blocks, const void *d_offsets, int32_t count, void *d_last, void *d_origins, int32_t device,
                  void *stream);
 // kBwtManyOn true: the framed many-file diffs transform their blocks there (dq_diff.hip: diff_many_frame).
@@ -521,6 +529,20 @@ int mtf_many_dev(const void *d_last, const void *d_offsets, int32_t count, void 
 // framed sets of tools/kbench/mtf_many.py (profiles/r25/mtf_many.json); false until all of them are measured (docs/ROUNDS.md,
 // round 25).
 constexpr bool kMtfManyOn = false;
+
+// Coding tables, selectors and bits of many blocks (dq_huff_many.h, in dq_sorter_i32.hip): the bodies of dq_huff_hip_bound,
+// dq_huff_hip_many / _many_dev.  No record, no profile category of their own.
+int64_t huff_many_bound(int64_t n);
+int huff_many_host(const uint16_t *syms, const int32_t *nsyms, const uint32_t *in_use, const int64_t *offsets, int32_t count,
+                   const uint32_t *crcs, const int32_t *origins, const int64_t *out_offsets, uint8_t *out, int32_t *nbits, int32_t device);
+int huff_many_dev(const void *d_syms, const void *d_nsyms, const void *d_in_use, const void *d_offsets, int32_t count, const void *d_crcs,
+                  const void *d_origins, const void *d_out_offsets, void *d_out, void *d_nbits, int32_t device, void *stream);
+// kHuffManyOn true: where the framed many-file diffs take move-to-front on the device (kMtfManyOn / DQ_NO_MTF_MANY=0 on top
+// of the device transform), huff_many_kernel runs behind mtf_many_kernel and the blocks' BITS come back instead of their
+// symbols (dq_diff.hip: diff_many_frame; StreamEncoder::encode_block_bits).  DQ_NO_HUFF_MANY=0 switches that on and =1
+// off, whatever this says.  The rule is kBwtManyOn's, on the framed sets of tools/kbench/huff_many.py
+// (profiles/r26/huff_many.json); false for round 26 whatever is measured (docs/ROUNDS.md, round 26).
+constexpr bool kHuffManyOn = false;
 
 // LDSSChecker.Check on the device (dq_sufcheck.hip): DQ_OK with the verdict (DQ_SUFCHECK_*) in *result, or an error
 template <typename IdxT>

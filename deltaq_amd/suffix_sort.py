@@ -54,6 +54,34 @@ def unpack_mtf_many(syms: np.ndarray, nsyms: np.ndarray, in_use: np.ndarray, off
     return [(syms[off[j] + j:off[j] + j + int(nsyms[j])], bits[256 * j:256 * (j + 1)]) for j in range(len(off) - 1)]
 
 
+HUFF_MAX_N = 900000         # kHuffMaxN: bzip2's largest block (15-bit selector count, 24-bit origin row)
+
+
+def unpack_huff_many(out: np.ndarray, nbits: np.ndarray, out_off: np.ndarray) -> list:
+    """dq_huff_hip_many's flat results as HuffMany returns them: [(the ceil(nbits[j] / 8) bytes of block j, nbits[j])];
+    block j's slot begins at out_off[j].  An empty block gives (b"", 0), a refused one (b"", -1)."""
+    return [(out[out_off[j]:out_off[j] + (max(int(nbits[j]), 0) + 7) // 8].tobytes(), int(nbits[j])) for j in range(len(out_off) - 1)]
+
+
+def huff_bound(n: int) -> int:
+    """dq_huff_hip_bound: bytes that always suffice for the bits of a block of n bytes (a multiple of 8; -1 outside
+    0 .. 900 000)."""
+    return int(_abi.load().dq_huff_hip_bound(int(n)))
+
+
+def huff_block_length(symbols: np.ndarray) -> int:
+    """The bytes of the block a symbol stream of MtfMany stands for: a run's digits d at position p count (d + 1) << p,
+    every other symbol but EOB counts 1."""
+    s = np.asarray(symbols, dtype=np.int64)[:-1]
+    if s.size == 0:
+        return 0
+    idx = np.arange(s.size)
+    digit = s < 2
+    head = digit & ~np.concatenate([[False], digit[:-1]])
+    pos = np.minimum(idx - np.maximum.accumulate(np.where(head, idx, 0)), 40)
+    return int(np.where(digit, (s + 1) << np.where(digit, pos, 0), 1).sum())
+
+
 def _is_torch_tensor(x) -> bool:
     return type(x).__module__.startswith("torch") and hasattr(x, "data_ptr")
 
@@ -308,6 +336,85 @@ class HipSuffixSort:
         _abi.check(self._lib.dq_mtf_hip_many_dev(lp.data_ptr(), offsets.data_ptr(), count, syms.data_ptr(), nsyms.data_ptr(),
                                                  in_use.data_ptr(), dev, stream))
         return syms, nsyms, in_use
+
+    # -- coding tables, selectors and bits of many blocks (the stage behind MtfMany) ------------------------------------
+    def HuffMany(self, *args, lengths=None):
+        """The bits of many bzip2 blocks from their symbol streams, on the device: per block what a bzip2 compressor
+        writes from the 48-bit block magic to the last code (coding tables by libbz2's rules, bit for bit).
+
+        ``HuffMany(streams, crcs, origins)`` -- ``streams`` what ``MtfMany`` returns, ``crcs[j]`` the CRC the block's
+        header carries, ``origins[j]`` its origin row from ``BwtMany`` -- returns a list of ``(bytes, nbits)``: the bits
+        most significant first, the last byte zero-padded (``dq_huff_hip_many``).  A refused block (a stream that does
+        not end in EOB or names a symbol outside its alphabet, an origin outside the block) gives ``(b"", -1)``, an
+        empty one ``(b"", 0)``.  ``lengths[j]`` is block j's length in bytes; left out, it is read off the stream
+        (its runs decoded).  ``HuffMany(syms, nsyms, in_use, offsets, crcs, origins, out_offsets, out)`` -- eight torch GPU
+        tensors: ``MtfMany``'s three and its block offsets (int64), int32 CRCs and origins, the int64 slot offsets
+        (``out_offsets[0] == 0``, multiples of 8, every slot at least ``huff_bound(n_j)`` bytes) and the uint8 output --
+        writes the bits into ``out`` and returns the int32 ``nbits`` tensor (``dq_huff_hip_many_dev``, on the current torch
+        stream).
+        """
+        if len(args) == 8 and _is_torch_tensor(args[0]):
+            return self._huff_many_device(*args)
+        if len(args) != 3:
+            raise TypeError("HuffMany takes (streams, crcs, origins) or eight GPU tensors")
+        streams, crcs, origins = args
+        count = len(streams)
+        if len(crcs) != count or len(origins) != count:
+            raise ValueError("one CRC and one origin per block")
+        syms_of = [np.ascontiguousarray(s, dtype=np.uint16) for s, _ in streams]
+        ns = [huff_block_length(s) for s in syms_of] if lengths is None else [int(x) for x in lengths]
+        if len(ns) != count:
+            raise ValueError("one length per block")
+        if any(n < 0 or n > HUFF_MAX_N for n in ns):
+            raise ValueError("HuffMany takes bzip2's blocks: at most 900 000 bytes each")
+        off = np.zeros(count + 1, dtype=np.int64)
+        out_off = np.zeros(count + 1, dtype=np.int64)
+        if count:
+            np.cumsum(ns, out=off[1:])
+            np.cumsum([huff_bound(n) for n in ns], out=out_off[1:])
+        syms = np.zeros(int(off[-1]) + count + 1, dtype=np.uint16)
+        nsyms = np.zeros(max(count, 1), dtype=np.int32)
+        in_use = np.zeros(8 * max(count, 1), dtype=np.uint32)
+        for j, (s, (_, iu)) in enumerate(zip(syms_of, streams)):
+            room = ns[j] + 1
+            syms[off[j] + j:off[j] + j + min(s.size, room)] = s[:room]
+            nsyms[j] = s.size
+            in_use[8 * j:8 * j + 8] = np.packbits(np.asarray(iu, dtype=bool), bitorder="little").view("<u4")
+        crc_words = np.ascontiguousarray(np.asarray(list(crcs) + [0], dtype=np.uint64).astype(np.uint32))
+        origin_words = np.ascontiguousarray(np.asarray(list(origins) + [0], dtype=np.int64).astype(np.int32))
+        out = np.zeros(int(out_off[-1]) + 8, dtype=np.uint8)
+        nbits = np.zeros(max(count, 1), dtype=np.int32)
+        _abi.check(self._lib.dq_huff_hip_many(syms.ctypes.data, nsyms.ctypes.data, in_use.ctypes.data, off.ctypes.data, count,
+                                              crc_words.ctypes.data, origin_words.ctypes.data, out_off.ctypes.data, out.ctypes.data,
+                                              nbits.ctypes.data, self.device))
+        return unpack_huff_many(out, nbits, out_off)
+
+    huff_many = HuffMany
+
+    def _huff_many_device(self, syms, nsyms, in_use, offsets, crcs, origins, out_offsets, out):
+        import torch
+
+        tensors = (syms, nsyms, in_use, offsets, crcs, origins, out_offsets, out)
+        kinds = (torch.int16, torch.int32, torch.int32, torch.int64, torch.int32, torch.int32, torch.int64, torch.uint8)
+        for t, kind in zip(tensors, kinds):
+            if not _is_torch_tensor(t) or t.dtype != kind or t.dim() != 1 or not t.is_contiguous():
+                raise TypeError("HuffMany's device form takes contiguous 1-D tensors: int16 syms, int32 nsyms, int32 in_use, "
+                                "int64 offsets, int32 crcs, int32 origins, int64 out_offsets, uint8 out")
+            if not t.is_cuda or t.device != syms.device:
+                raise TypeError("all eight tensors must live on the same GPU")
+        count = offsets.numel() - 1
+        if count < 0 or out_offsets.numel() != count + 1 or nsyms.numel() < count or in_use.numel() < 8 * count or \
+                crcs.numel() < count or origins.numel() < count:
+            raise ValueError("offsets and out_offsets hold count + 1 entries, the per-block tensors count (in_use: 8 count)")
+        nbits = torch.zeros(count, dtype=torch.int32, device=syms.device)
+        if count == 0:
+            return nbits
+        dev, stream = _device_and_stream(syms)
+        op = out if out.numel() else torch.zeros(8, dtype=torch.uint8, device=syms.device)
+        _abi.check(self._lib.dq_huff_hip_many_dev(syms.data_ptr(), nsyms.data_ptr(), in_use.data_ptr(), offsets.data_ptr(), count,
+                                                  crcs.data_ptr(), origins.data_ptr(), out_offsets.data_ptr(), op.data_ptr(),
+                                                  nbits.data_ptr(), dev, stream))
+        return nbits
 
     # -- LDSSChecker.Check(T, SA)   (test/DeltaQ.SuffixSorting.LibDivSufSort.Tests/LDSSChecker.cs:23-119) --------
     def Check(self, text, suffixes) -> int:

@@ -187,6 +187,72 @@ int32_t dq_mtf_hip_many(const uint8_t *last, const int64_t *offsets, int32_t cou
 int32_t dq_mtf_hip_many_dev(const void *d_last, const void *d_offsets, int32_t count, void *d_syms, void *d_nsyms,
                             void *d_in_use, int32_t device, void *stream);
 
+/* ---- coding tables, selectors and the bit stream of many independent blocks in shared launches (bzip2's third stage) ----
+ * Behind dq_bwt_hip_many and dq_mtf_hip_many a block is a symbol stream; this call turns it into the BITS of a bzip2
+ * block, so that a block goes in as bytes and nothing but a few bits per byte comes back.  One workgroup per block,
+ * claimed from a work list, longest first; nobody waits for anybody (huff_many_kernel, dq_huff_many.h).
+ * Input: exactly what dq_mtf_hip_many writes.  offsets[count + 1] are the BLOCK offsets (int64, offsets[0] == 0, never
+ * decreasing); block j of n_j = offsets[j + 1] - offsets[j] bytes has its symbols at syms[offsets[j] + j ...), nsyms[j]
+ * of them, and its in-use map in in_use[8 j .. 8 j + 8) (bit c % 32 of word c / 32: byte c).  Any symbol stream that
+ * satisfies the definition is valid input, whoever wrote it.  crcs[j] is the CRC the block's header carries, origins[j]
+ * bzip2's origPtr.
+ * Definition: block j's output is, bit for bit, what bz2::compress_block_mtf (deltaq_amd/csrc/dq_bz2.h) appends to an
+ * empty BitWriter for those arguments, from the 48-bit block magic to the last code.  In words, with k the bytes in use,
+ * alpha = k + 2, EOB = k + 1 and m = nsyms[j]:
+ *   n_groups = 2, 3, 4, 5, 6 for m < 200, < 600, < 1200, < 2400, otherwise; n_sel = ceil(m / 50);
+ *   the initial split: for part = n_groups .. 1, symbols from where the last part ended are taken while their summed
+ *     frequency is below (symbols left) / part; where more than one was taken, part is neither the first nor the last and
+ *     n_groups - part is odd, the last one is given back; table part - 1 gets length 0 inside its range and 15 outside;
+ *   four refinement rounds: every group of 50 symbols chooses the table under which its code lengths sum to the least,
+ *     the LOWEST table on a tie; every table then gets new lengths from the frequencies of the groups that chose it;
+ *   the lengths are libbz2's: a binary heap of the symbols by weight (frequency << 8, a frequency of 0 counting as 1; the
+ *     low 8 bits hold the depth), the two least merged into a node of weight (sum of the frequencies) | (1 + deeper depth),
+ *     until one is left; a length is a leaf's distance from the root; while a length exceeds 17 every frequency f becomes
+ *     1 + f / 2 and the tree is rebuilt.  Ties fall as that heap's shape makes them fall: another Huffman construction
+ *     gives valid but different bits, which this call does not;
+ *   canonical codes: by length, then by symbol;
+ *   the bits: magic 0x314159265359 (48), crcs[j] (32), 0 (1), origins[j] (24), the 16 row flags and one 16-bit map per row
+ *     in use, n_groups (3), n_sel (15), the selectors move-to-front coded in unary (place p: p ones and a zero), per
+ *     table its first length in 5 bits and per symbol the steps from the previous length ("10" up, "11" down) and a "0",
+ *     then every symbol's code under its group's table.
+ * Output: block j owns out[out_offsets[j] .. out_offsets[j + 1]); bits most significant first, the last byte zero-padded;
+ * nbits[j] is the bit count.  Bytes of a slot behind ceil(nbits[j] / 8) are unspecified; nothing outside a block's own
+ * slot is written.  n == 0: nbits[j] = 0 and nothing is written.
+ * A refused block -- nsyms[j] outside [2, n_j + 1], a symbol >= alpha, a last symbol that is not EOB, origins[j] outside
+ * [0, n_j): compress_block_mtf's -3, decided per block -- gets nbits[j] = -1 and no bits; the call still returns DQ_OK.
+ * So does a block whose in-use map names more bytes than the block has AND whose bits do not fit its slot: the bound
+ * below assumes k <= n.
+ * dq_huff_hip_bound(n): bytes that always suffice for a block of n bytes, a multiple of 8; 0 for n == 0, -1 for n < 0 or
+ * n > 900 000.  With m = n + 1 symbols at most, a = min(n, 256) + 2 and G the n_groups of m:
+ *   bits <= 395 + G ceil(m / 50) + G (5 + a + 32 (a - 1)) + 17 m
+ * -- 48 + 32 + 1 + 24 + 16 + 256 + 3 + 15 = 395 for header, maps and counts; a selector is at most G bits (G - 1 ones
+ * and a zero); a table is 5 bits, a stop bit per symbol and at most 16 two-bit steps between neighbours (lengths lie in
+ * 1 .. 17; the first symbol takes none); a code is at most 17 bits.
+ * Errors, all before any device use in the host form: count < 0, a NULL pointer with count > 0, offsets[0] != 0,
+ * decreasing offsets, out_offsets[0] != 0, an out_offsets[j] that is no multiple of 8, a slot shorter than
+ * dq_huff_hip_bound(n_j) -> DQ_ERR_BAD_ARGS; a block above 900 000 bytes -> DQ_ERR_TOO_LARGE: the format's 15-bit
+ * selector count and 24-bit origPtr end there.  count == 0 is a no-op.  There is no CPU fallback.
+ *   dq_huff_hip_many      host pointers.  The blocks travel in chunks of whole blocks: at most 64 MiB of block bytes and
+ *                         2^20 blocks; one wait per chunk.  Device memory per chunk of b bytes in c blocks, l of them
+ *                         non-empty: 2 [b + c] symbols, 4 x 4 c words (counts, CRCs, origins, bit counts), 32 c in-use
+ *                         words, 2 x 8 [c + 1] offsets, the slots at dq_huff_hip_bound(n_j) each (about 2.2 b), b / 50 + c
+ *                         selectors, 4 l + 256 of work list -- each rounded up to 256 bytes; about 280 MiB for a full
+ *                         chunk.  2 [b + c] + 44 c bytes up, the slots and 4 c bytes down; the written bytes are handed on
+ *                         from a host copy of the chunk's slots.
+ *   dq_huff_hip_many_dev  device pointers on `device`, d_offsets and d_out_offsets too: the library fetches both once
+ *                         and checks them before it launches anything; work on `stream`, NULL = the library's; returns
+ *                         after the stream has drained.  Device memory: the selectors and the work list,
+ *                         total / 50 + count + 4 l + 512 bytes.  Four-byte stores where `out` + out_offsets[j] is 4-byte
+ *                         aligned, single bytes elsewhere.
+ * Neither has a record of its own, and the kernel is profiled under small_many_kernel's category. */
+int64_t dq_huff_hip_bound(int64_t n);
+int32_t dq_huff_hip_many(const uint16_t *syms, const int32_t *nsyms, const uint32_t *in_use, const int64_t *offsets, int32_t count,
+                         const uint32_t *crcs, const int32_t *origins, const int64_t *out_offsets, uint8_t *out, int32_t *nbits,
+                         int32_t device);
+int32_t dq_huff_hip_many_dev(const void *d_syms, const void *d_nsyms, const void *d_in_use, const void *d_offsets, int32_t count,
+                             const void *d_crcs, const void *d_origins, const void *d_out_offsets, void *d_out, void *d_nbits,
+                             int32_t device, void *stream);
+
 /* ---- Diff.Create's match search on the device-resident suffix array ----------
  * Replaces, for a batch of scan positions, the reference's
  *   Search(I, oldData, newData[scan..], 0, oldData.Length, out pos)          src/DeltaQ.BsDiff/Diff.cs:267-298

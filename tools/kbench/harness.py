@@ -33,6 +33,7 @@ PROTOTYPES = {                                               # export -> (restyp
     "dq_sufsort_hip_many_dev_i32": (_i32, [_vp, _vp, _i32, _vp, _i32, _vp]),
     "dq_bwt_hip_many": (_i32, [_vp, _vp, _i32, _vp, _vp, _i32]),
     "dq_mtf_hip_many": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _i32]),
+    "dq_huff_hip_many": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32]),
     "dq_bsdiff_patch_bound": (_i64, [_i64, _i64]),
     "dq_bsdiff_create": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _p64, _i32]),
     "dq_bsdiff_create_many": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32]),
