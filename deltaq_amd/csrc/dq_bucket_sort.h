@@ -126,12 +126,17 @@ __device__ long long *g_bkt_ts = nullptr;            // [ntiles][16]
 // passes carried it along): it is appended to the word's low key bits, so the tile sorts by 8 more bits and the tie bits
 // mean "equal in all of them".  The bytes of a tile are fetched when the tile starts (not a tile ahead like the words:
 // the register file has no room for them), behind the zeroing of the bin table.
-template <typename IdxT, bool kExt = false, typename G = BktCoarse>
+// kSlots (dq_slot_rank.h): tile j is bucket j, its words lie unordered in a slot of their own -- slot_count[j] of them from
+// W + slot_base[j] -- and its suffixes and tie bits go to slot_out[j]; `bounds` is not read.  The three values are
+// wave-uniform like the bounds they stand for, and requested as far ahead.
+template <typename IdxT, bool kExt = false, typename G = BktCoarse, bool kSlots = false>
 __global__ __launch_bounds__(G::threads, G::waves) void bucket_sort_kernel(
     const uint64_t *__restrict__ W, int ib, int lowbits, const int64_t *__restrict__ bounds, int64_t ntiles,
     IdxT *__restrict__ SA, uint32_t *__restrict__ ebits, BucketFlags *__restrict__ flags,
-    const uint8_t *__restrict__ E = nullptr)
+    const uint8_t *__restrict__ E = nullptr, const uint32_t *__restrict__ slot_base = nullptr,
+    const uint32_t *__restrict__ slot_count = nullptr, const uint32_t *__restrict__ slot_out = nullptr)
 {
+    static_assert(!(kSlots && kExt), "the slot route has no extra key byte");
     constexpr int kCap = G::cap, kThreads = G::threads, kNB = G::nb, kItems = G::items;
     constexpr int kBinsPerThread = kNB / kThreads;         // 2 x items: 24 sixteen-bit counters = 12 LDS words at both geometries
     constexpr int kWords = kBinsPerThread / 2;
@@ -152,13 +157,26 @@ __global__ __launch_bounds__(G::threads, G::waves) void bucket_sort_kernel(
     int64_t tile = blockIdx.x;
     if (tile >= ntiles) return;
     // (lo, M) of the tile whose words are being fetched; M > capacity has been flagged by the bounds kernel
-    int64_t lo_n = bounds[tile];
-    uint32_t M_n = (uint32_t)(bounds[tile + 1] - lo_n);
+    // (lo, hi, where the output goes) of tile t_; without slots the output goes where the words came from
+#define DQ_BKT_BOUNDS(t_, lo_, hi_, out_)                                         \
+    do {                                                                          \
+        if constexpr (kSlots) {                                                   \
+            lo_ = (int64_t)slot_base[t_];                                         \
+            hi_ = lo_ + (int64_t)slot_count[t_];                                  \
+            out_ = (int64_t)slot_out[t_];                                         \
+        } else {                                                                  \
+            lo_ = bounds[t_];                                                     \
+            hi_ = bounds[(t_) + 1];                                               \
+        }                                                                         \
+    } while (0)
+    int64_t lo_n, hi_n, out_n = 0;
+    DQ_BKT_BOUNDS(tile, lo_n, hi_n, out_n);
+    uint32_t M_n = (uint32_t)(hi_n - lo_n);
     if (M_n > (uint32_t)kCap) M_n = 0;
     // ... and the bounds of the one after that: a dependent load in front of the fetch, so it is requested a
     // whole tile ahead of its use
-    int64_t lo_nn = 0, hi_nn = 0;
-    if (tile + gridDim.x < ntiles) { lo_nn = bounds[tile + gridDim.x]; hi_nn = bounds[tile + gridDim.x + 1]; }
+    int64_t lo_nn = 0, hi_nn = 0, out_nn = 0;
+    if (tile + gridDim.x < ntiles) DQ_BKT_BOUNDS(tile + gridDim.x, lo_nn, hi_nn, out_nn);
     uint64_t wd[kItems];
     // Clamped, not predicated: the loads stay in flight together.  (And every array element is always assigned
     // unconditionally: a conditional element write turns the register array into one wide phi that the
@@ -176,15 +194,17 @@ __global__ __launch_bounds__(G::threads, G::waves) void bucket_sort_kernel(
 #define DQ_BKT_REQUEST_NEXT()                                                     \
     do {                                                                          \
         lo_n = lo_nn;                                                             \
+        if constexpr (kSlots) out_n = out_nn;                                     \
         M_n = (uint32_t)(hi_nn - lo_nn);                                          \
         if (M_n > (uint32_t)kCap) M_n = 0;                                     \
         DQ_BKT_FETCH();                                                           \
-        if (tn + gridDim.x < ntiles) { lo_nn = bounds[tn + gridDim.x]; hi_nn = bounds[tn + gridDim.x + 1]; } \
+        if (tn + gridDim.x < ntiles) DQ_BKT_BOUNDS(tn + gridDim.x, lo_nn, hi_nn, out_nn); \
     } while (0)
     DQ_BKT_FETCH();
 
     for (;;) {
         const int64_t lo = lo_n;
+        const int64_t olo = kSlots ? out_n : lo_n;          // where the tile's suffixes and tie bits go
         const uint32_t M = M_n;
         const int64_t tn = tile + gridDim.x;
         if (M == 0) {                                       // (uniform) an empty tile: no barrier, no bin zeroing
@@ -335,7 +355,7 @@ __global__ __launch_bounds__(G::threads, G::waves) void bucket_sort_kernel(
                 __syncthreads();
                 DQ_BKT_PHASE(6);
                 // ---- sorted suffixes out, coalesced; the few tie bits by atomic OR ----
-                IdxT *out = SA + lo;
+                IdxT *out = SA + olo;
                 uint32_t v[kItems];
 #pragma unroll
                 for (int k = 0; k < kItems; ++k) {
@@ -352,7 +372,7 @@ __global__ __launch_bounds__(G::threads, G::waves) void bucket_sort_kernel(
                 while (ties) {
                     const int k = __builtin_ctz(ties);
                     ties &= ties - 1;
-                    const uint64_t o = (uint64_t)(lo + k * kThreads + tid);
+                    const uint64_t o = (uint64_t)(olo + k * kThreads + tid);
                     atomicOr(&ebits[o >> 5], 1u << ((uint32_t)o & 31u));
                 }
                 DQ_BKT_PHASE(7);
@@ -362,6 +382,7 @@ __global__ __launch_bounds__(G::threads, G::waves) void bucket_sort_kernel(
         tile = tn;
         __syncthreads();                                    // buf, bins and s_edge are reused
     }
+#undef DQ_BKT_BOUNDS
 #undef DQ_BKT_REQUEST_NEXT
 #undef DQ_BKT_FETCH
 }

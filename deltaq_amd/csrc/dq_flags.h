@@ -65,6 +65,7 @@ struct Flags {
     std::optional<int> bucket_keybits;      // DQ_BUCKET_KEYBITS: key bits of the bucketed round 0 (>= 17, <= its own)
     std::optional<int> bucket_ext;          // DQ_BUCKET_EXT: 0 | 1, the extra key byte beside every word
     std::optional<int> bucket_tile;         // DQ_BUCKET_TILE: 0 | 1, finish kernel's geometry: one workgroup per CU on 12 288-word tiles | two on 6144-word tiles
+    std::optional<int> bucket_slots;        // DQ_BUCKET_SLOTS: 0 | 1, second digit pass: the stable look-back pass | into fixed bucket slots (1: forced where the slots fit)
     bool old_first_pass = false;            // DQ_OLD_FIRST_PASS: radix_rank_kernel instead of the XCD-local first pass
     bool no_fused_ties = false;             // DQ_NO_FUSED_TIES: the tie structure by a rebucket pass
     std::optional<int> sparse;              // DQ_SPARSE: 0 | 1, dense or sparse finish; set: no fused ties / bucketing
@@ -177,6 +178,7 @@ inline Flags read_flags()
     f.bucket_keybits = num("DQ_BUCKET_KEYBITS");
     f.bucket_ext = num("DQ_BUCKET_EXT");
     f.bucket_tile = num("DQ_BUCKET_TILE", 0, 1);
+    f.bucket_slots = num("DQ_BUCKET_SLOTS", 0, 1);
     f.old_first_pass = on("DQ_OLD_FIRST_PASS");
     f.no_fused_ties = on("DQ_NO_FUSED_TIES");
     f.sparse = num("DQ_SPARSE");

@@ -10,6 +10,7 @@
 #include "dq_ties.h"
 #include "dq_bucket_sort.h"
 #include "dq_xcd_rank.h"
+#include "dq_slot_rank.h"
 
 namespace dq {
 namespace {
@@ -307,6 +308,18 @@ struct Round0 {
         const BucketPlan b = plan_bucketed(s, F, k, coded, (int)wb);
         if (!b.applies) return DQ_OK;
         const int kb = k.kb, keybits = b.keybits, lowbits = b.lowbits;
+        // the finish kernel's tiles and geometry (plan_finish_tiles): cut every Cf words at a bucket boundary, or every g buckets;
+        // and whether the second pass goes into fixed bucket slots (dq_slot_rank.h): the first pass then writes K[0], so that
+        // the second can write the span that starts at K[1].  Slot bases and output places share the tile bounds' memory,
+        // tickets and cursors take the idle histogram scratch.
+        const SlotPlan sp = bucket_slots_fit(s, b, (int)wb);
+        const FinishTiles ft = plan_finish_tiles(b, n, F, sp.fits);
+        static_assert(sizeof(SlotRankCtl) <= (size_t)kHistBlocks * kMaxPasses * kRadixSize * 4, "the cursors live in the histogram scratch");
+        const bool slots = bucket_slots_wanted(sp, ft, F) && (uint64_t)sp.words <= slot_span_words_of(w) &&
+                           (size_t)(2 * kSlotBuckets + 5) * 4 <= finish_bounds_entries(n) * 8;
+        uint32_t *slot_base = reinterpret_cast<uint32_t *>(w.bkt_bounds), *slot_out = slot_base + kSlotBuckets + 4;     // (16-byte aligned)
+        SlotRankCtl *sctl = reinterpret_cast<SlotRankCtl *>(w.hist_partial);
+        const int first = slots ? 0 : 1;                     // the buffer the first pass writes
         uint8_t *E[2] = {reinterpret_cast<uint8_t *>(w.Va), reinterpret_cast<uint8_t *>(w.Va) + align_up((size_t)n)};
         uint32_t *ebits = reinterpret_cast<uint32_t *>(w.Vb);                  // zeroed by prepare()
         TieCounters *ctr = reinterpret_cast<TieCounters *>(w.totals + 6);     // zero since run()
@@ -316,6 +329,14 @@ struct Round0 {
                            (const int64_t *)w.bytehist, (const uint8_t *)w.text, n, b.bbytes, w.digit_offset,
                            b.xcd_pass ? (const int64_t *)(w.bytehist + kXcdHistAt) : nullptr, b.xcd_pass ? w.xcd_offset : nullptr);
         HIP_TRY(hipGetLastError());
+        if (slots) {
+            if (F.trace)
+                fprintf(stderr, "[dq] second pass into bucket slots: %d x %d slots of %lld words (n=%lld)\n", sp.first, sp.second,
+                        (long long)b.X, (long long)n);
+            HIP_TRY(hipMemsetAsync(sctl, 0, sizeof(SlotRankCtl), st));
+            hipLaunchKernelGGL(slot_plan_kernel, dim3(kRadixSize + 1), dim3(kBlock), 0, st, (const int64_t *)w.bytehist, b.X, slot_base);
+            HIP_TRY(hipGetLastError());
+        }
         if (c.ncu <= 0) {
             int v = 0;
             c.ncu = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, c.dev) == hipSuccess && v > 0 ? v : 256;
@@ -326,28 +347,44 @@ struct Round0 {
             if (sizeof(XcdRankCtl) > w.ctl_status_stride) return fail(DQ_ERR_HIP, "status buffer too small");
             LAUNCH(L, DQ_K_RADIX_RANK, n, n * (1 + 8),                 // persistent: one workgroup per CU
                    hipLaunchKernelGGL(xcd_text_rank_kernel, dim3((unsigned)std::min<int64_t>(c.ncu, (n + kXcdTileN - 1) / kXcdTileN)),
-                                      dim3(kXcdRankThreads), 0, st, reinterpret_cast<const uint32_t *>(w.text), K[1], n,
+                                      dim3(kXcdRankThreads), 0, st, reinterpret_cast<const uint32_t *>(w.text), K[first], n,
                                       ib + lowbits, keybits, ib, (const int64_t *)w.xcd_offset,
                                       reinterpret_cast<XcdRankCtl *>(w.ctl_status)));
         } else {
             DQ_TRY(b.ext ? rank_pass_ext<IdxT, kTextPackedExt>(L, w, text64(), (const uint8_t *)nullptr, K[1], E[1], n, 0, ib, ib + lowbits, keybits)
-                       : rank_pass<IdxT, kTextPacked>(L, w, text64(), (const IdxT *)nullptr, K[1], (IdxT *)nullptr, n, 0, kb, ib,
+                       : rank_pass<IdxT, kTextPacked>(L, w, text64(), (const IdxT *)nullptr, K[first], (IdxT *)nullptr, n, 0, kb, ib,
                                                       nullptr, nullptr, ib + lowbits, keybits));
         }
-        for (int p = 1; p < b.bbytes; ++p) {                 // pass p reads buffer p & 1 and writes the other
+        if (slots) {
+            // persistent; the profile category and the byte count stay the second digit pass's
+            const int groups = resident_groups(&c.slot_rank_groups, (const void *)slot_rank_kernel, kSlotRankThreads, c.dev);
+            LAUNCH(L, DQ_K_RADIX_RANK, n, n * 16,
+                   hipLaunchKernelGGL(slot_rank_kernel, dim3((unsigned)std::min<int64_t>(groups, (n + kSlotTileN - 1) / kSlotTileN)),
+                                      dim3(kSlotRankThreads), 0, st, (const uint64_t *)K[0], K[1], n, ib + lowbits + 8, ib + lowbits,
+                                      (const int64_t *)w.digit_offset, (const uint32_t *)slot_base, sctl, bflags));
+        }
+        for (int p = 1; p < b.bbytes && !slots; ++p) {       // pass p reads buffer p & 1 and writes the other
             DQ_TRY(b.ext ? rank_pass_ext<IdxT, kKeysExt>(L, w, K[p & 1], E[p & 1], K[(p & 1) ^ 1], E[(p & 1) ^ 1], n, p, ib, ib + lowbits + 8 * p, keybits)
                        : rank_pass<IdxT, kKeys>(L, w, K[p & 1], (const IdxT *)nullptr, K[(p & 1) ^ 1], (IdxT *)nullptr, n, p, kb, ib,
                                                 nullptr, nullptr, ib + lowbits + 8 * p, keybits));
         }
-        uint64_t *Ks = K[b.bbytes & 1], *Kfree = K[(b.bbytes & 1) ^ 1];       // sorted words / the other buffer
+        // sorted words / the other buffer (slots: the words in their slots, from K[1] on into Va)
+        uint64_t *Ks = slots ? K[1] : K[b.bbytes & 1], *Kfree = slots ? K[0] : K[(b.bbytes & 1) ^ 1];
         const uint8_t *Es = b.ext ? E[b.bbytes & 1] : nullptr;
-        // the finish kernel's tiles and geometry (plan_finish_tiles): cut every Cf words at a bucket boundary, or every g buckets
-        const FinishTiles ft = plan_finish_tiles(b, n, F);
         if (F.trace)
             fprintf(stderr, "[dq] bucket finish: %s geometry, %lld tiles of up to %lld words cut every %lld %s (n=%lld)\n", ft.fine ? "fine" : "coarse",
                     (long long)ft.ntiles, (long long)ft.cap, (long long)(ft.by_id ? ft.g : ft.Cf), ft.by_id ? "buckets" : "words", (long long)n);
         if ((size_t)ft.ntiles + 1 > finish_bounds_entries(n)) return fail(DQ_ERR_HIP, "tile bounds buffer too small");
-        if (ft.by_id) {
+        if (slots) {
+            LAUNCH(L, DQ_K_BUCKET_SORT, ft.ntiles, ft.ntiles * 16,
+                   hipLaunchKernelGGL(slot_out_kernel, dim3(1), dim3(kSlotOutThreads), 0, st, sctl->cursor, (uint32_t)b.X, slot_out, bflags));
+            auto kernel = bucket_sort_kernel<IdxT, false, BktFine, true>;
+            const int groups = resident_groups(&c.bkt_slot_groups[sizeof(IdxT) == 8], (const void *)kernel, BktFine::threads, c.dev);
+            LAUNCH(L, DQ_K_BUCKET_SORT, n, n * (8 + wb) + n / 8,
+                   hipLaunchKernelGGL(kernel, dim3((unsigned)std::min<int64_t>(ft.ntiles, groups)), dim3(BktFine::threads), 0, st,
+                                      (const uint64_t *)Ks, ib, lowbits, (const int64_t *)nullptr, ft.ntiles, d_sa, ebits, bflags,
+                                      (const uint8_t *)nullptr, (const uint32_t *)slot_base, (const uint32_t *)sctl->cursor, (const uint32_t *)slot_out));
+        } else if (ft.by_id) {
             const int64_t nbuckets = (int64_t)1 << (8 * b.bbytes);
             LAUNCH(L, DQ_K_BUCKET_SORT, ft.ntiles, ft.ntiles * 16 * 8,
                    hipLaunchKernelGGL(bucket_bounds_by_id_kernel, dim3((unsigned)((nbuckets + 1 + kBlock - 1) / kBlock)), dim3(kBlock), 0,
@@ -364,10 +401,12 @@ struct Round0 {
             const int groups = resident_groups(&c.bkt_groups[ft.fine][b.ext][sizeof(IdxT) == 8], (const void *)kernel, G::threads, c.dev);
             LAUNCH(L, DQ_K_BUCKET_SORT, n, n * ((b.ext ? 9 : 8) + wb) + n / 8,
                    hipLaunchKernelGGL(kernel, dim3((unsigned)std::min<int64_t>(ft.ntiles, groups)), dim3(G::threads), 0, st,
-                                      (const uint64_t *)Ks, ib, lowbits, (const int64_t *)w.bkt_bounds, ft.ntiles, d_sa, ebits, bflags, Es));
+                                      (const uint64_t *)Ks, ib, lowbits, (const int64_t *)w.bkt_bounds, ft.ntiles, d_sa, ebits, bflags, Es,
+                                      (const uint32_t *)nullptr, (const uint32_t *)nullptr, (const uint32_t *)nullptr));
             return DQ_OK;
         };
-        if (ft.fine) {                                       // (plan_finish_tiles: never with the extra key byte)
+        if (slots) {                                         // (its finish kernel has been launched above)
+        } else if (ft.fine) {                                // (plan_finish_tiles: never with the extra key byte)
             DQ_TRY(finish(std::false_type{}, BktFine{}));
         } else {
             DQ_TRY(with_bool(b.ext, [&](auto kExt) -> int { return finish(kExt, BktCoarse{}); }));

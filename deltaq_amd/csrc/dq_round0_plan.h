@@ -219,7 +219,9 @@ struct FinishTiles {
     int64_t ntiles = 0;
 };
 
-inline FinishTiles plan_finish_tiles(const BucketPlan &b, int64_t n, const Flags &F)
+// slots_fit (bucket_slots_fit below): under DQ_BUCKET_SLOTS=1 the fine tiles are then cut one bucket each even where
+// Cf >= X, which is the cut the slot route needs.  With the flag unset or 0 the argument changes nothing.
+inline FinishTiles plan_finish_tiles(const BucketPlan &b, int64_t n, const Flags &F, bool slots_fit = false)
 {
     FinishTiles t;
     if (!b.applies) return t;
@@ -227,7 +229,12 @@ inline FinishTiles plan_finish_tiles(const BucketPlan &b, int64_t n, const Flags
     t.fine = can && (F.bucket_tile ? *F.bucket_tile != 0 : !F.bucket.has_value() && n >= kBktFineMinN);
     t.cap = t.fine ? kBktCapFine : kBktCap;
     const int64_t Cf = t.cap - b.X;
-    if (Cf >= b.X) {
+    const bool force_by_id = t.fine && slots_fit && F.bucket_slots && *F.bucket_slots == 1;
+    if (force_by_id) {
+        t.by_id = true;
+        t.g = 1;
+        t.ntiles = (int64_t)1 << (8 * b.bbytes);
+    } else if (Cf >= b.X) {
         t.Cf = Cf;
         t.ntiles = (n + Cf - 1) / Cf;
     } else {
@@ -237,6 +244,55 @@ inline FinishTiles plan_finish_tiles(const BucketPlan &b, int64_t n, const Flags
         t.ntiles = (nbuckets + t.g - 1) / t.g;
     }
     return t;
+}
+
+// The second digit pass into fixed bucket slots (dq_slot_rank.h).  With one 2-byte bucket per finish tile a bucket need
+// not lie dense against its neighbours: every bucket (A, B) whose bytes both occur gets a slot of X words -- the longest
+// bucket the path accepts -- in bucket order, absent buckets get none, and the pass places a word wherever its
+// reservation on the bucket's cursor lands.  No look-back, no status words, no bounds search afterwards.
+// The slots lie in the span the key buffer K1 and the index buffer Va make together: (n + 2) * (8 + index bytes) bytes.
+// Byte 0 counts as a second byte whether the text has it or not: the last suffix reads the zero pad.
+inline int64_t slot_span_words(int64_t n, int idx_bytes) { return (n + 2) * (int64_t)(8 + idx_bytes) / 8; }
+
+struct SlotPlan {
+    bool fits = false;                          // the slots of this text fit the span (and their bases 32 bits)
+    int first = 0, second = 0;                  // byte values that occur as a bucket's first / second byte
+    int64_t words = 0;                          // first * second * X
+};
+
+inline SlotPlan bucket_slots_fit(const TextStats &s, const BucketPlan &b, int idx_bytes)
+{
+    SlotPlan p;
+    if (!b.applies || b.bbytes != 2 || b.ext) return p;
+    p.first = s.sigma;
+    p.second = s.sigma + (s.hist[0] == 0 ? 1 : 0);
+    p.words = (int64_t)p.first * p.second * b.X;
+    p.fits = p.words <= slot_span_words(s.n, idx_bytes) && p.words < ((int64_t)1 << 32);
+    return p;
+}
+
+// base[A * 256 + B] for the 65 536 buckets and the end, as slot_plan_kernel (dq_slot_rank.h) writes them: X words times the
+// buckets in front whose bytes both occur -- in closed form, from the ranks of A and B among the bytes that occur.
+inline void slot_bases(const int64_t *hist /*[256]*/, int64_t X, uint32_t *base /*[65537]*/)
+{
+    int ra[257], rb[257];
+    ra[0] = rb[0] = 0;
+    for (int d = 0; d < 256; ++d) {
+        ra[d + 1] = ra[d] + (hist[d] > 0 ? 1 : 0);
+        rb[d + 1] = rb[d] + (hist[d] > 0 || d == 0 ? 1 : 0);
+    }
+    for (int A = 0; A < 256; ++A)
+        for (int B = 0; B < 256; ++B)
+            base[A * 256 + B] = (uint32_t)(X * ((int64_t)ra[A] * rb[256] + (hist[A] > 0 ? rb[B] : 0)));
+    base[65536] = (uint32_t)(X * ra[256] * rb[256]);
+}
+
+// The route is taken where the slots fit and the finish tiles are the fine geometry's, one bucket each (the index fits
+// 31 bits wherever plan_bucketed applies).  DQ_BUCKET_SLOTS = 0: never; 1: plan_finish_tiles has forced that cut.
+inline bool bucket_slots_wanted(const SlotPlan &p, const FinishTiles &t, const Flags &F)
+{
+    if (F.bucket_slots && *F.bucket_slots == 0) return false;
+    return p.fits && t.fine && t.by_id && t.g == 1;
 }
 
 // entries of the workspace's tile bounds (ntiles + 1 of them are used): the tiles of either geometry under either cut --

@@ -69,8 +69,13 @@ struct Workspace {
     uint32_t *sp_tile_first;
     ScanPart *sp_part;
     SplitCtl *sp_ctl;
+    size_t slot_span_words;     // 64-bit words from K1 to the end of Va, which follows it (0: not adjacent)
     size_t bytes;
 };
+
+// the span the second pass of the slot route may write, from w.K1 on: its length in words
+template <typename IdxT>
+inline uint64_t slot_span_words_of(const Workspace<IdxT> &w) { return (uint64_t)w.slot_span_words; }
 
 // lists: carve the third list buffer (X, Xs) -- see with_list_buffers()
 template <typename IdxT>
@@ -83,8 +88,12 @@ Workspace<IdxT> carve(char *base, int64_t n, bool with_sa, bool lists)
     w.text = (uint8_t *)take(un + 64);
     // (+2: the lists of a small-group round start their L region on an even entry, see sg_half())
     w.K0 = (uint64_t *)take((un + 2) * 8);
+    const size_t k1_at = off;
     w.K1 = (uint64_t *)take((un + 2) * 8);
+    // (K1 and Va are adjacent: together they are the span the slot route's second pass writes, dq_slot_rank.h)
+    const bool adjacent = off == k1_at + align_up((un + 2) * 8);
     w.Va = (IdxT *)take((un + 2) * sizeof(IdxT));
+    w.slot_span_words = adjacent ? (off - k1_at) / 8 : 0;
     w.Vb = (IdxT *)take((un + 2) * sizeof(IdxT));
     w.ISA = (IdxT *)take(un * sizeof(IdxT));
     w.SAbuf = with_sa ? (IdxT *)take(un * sizeof(IdxT)) : nullptr;
