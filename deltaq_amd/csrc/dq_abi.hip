@@ -414,7 +414,7 @@ int32_t dq_bwt_hip_many(const uint8_t *blocks, const int64_t *offsets, int32_t c
     EnvScope scope;
     t_many_info = {};
     try {
-        return bwt_many_host(blocks, offsets, count, last, origins, device);
+        return bwt_many_host(blocks, offsets, count, BwtOut(last), origins, device);
     } catch (const std::bad_alloc &) {
         return fail(DQ_ERR_OOM, "many: host allocation failed");
     }

@@ -32,14 +32,19 @@
 // dq_sufsort_hip_many_i32 (the medium classes' scratch blocks; the segmented sort's workspace where that class is on).  One
 // block above a chunk goes alone with the same 11 bytes per byte, and the device sorter's workspace for 2 b.
 // 32-bit indices: a block has fewer than 2^30 bytes.  dq_small_many.h includes this file at its end.
-// On request (BwtIo::syms, the host form's: phase 4 of the framed many-file diffs under kMtfManyOn / DQ_NO_MTF_MANY=0)
-// mtf_many_kernel (dq_mtf_many.h) follows bwt_many_kernel on the same stream: its symbols, counts and in-use maps go into
-// the suffix-array region, which is dead by then, and travel back instead of `last`; the origins, the flag word and the
-// single wait stay as they are.  Its two classes take their work from bwt_many_kernel's own list, which is longest first:
-// the long class its head, the short class the rest.
-// On a further request (BwtIo::bits, the host form's: kHuffManyOn / DQ_NO_HUFF_MANY=0) huff_many_kernel (dq_huff_many.h)
-// follows mtf_many_kernel on the same stream, on the same list: the blocks' CRCs go up, 4 bytes per block, and the
-// blocks' bits and bit counts travel back instead of the symbols, which never leave the device.
+// How far a group goes is the caller's BlockStage (dq_block_groups.h; the host form's BwtOut, dq_runtime.h), and bwt_group
+// is the shared group frame (run_group, dq_runtime.h) around three parts that enqueue in turn:
+//   Last  the transform above; `last` and the origins come back
+//   Syms  (phase 4 of the framed many-file diffs under kMtfManyOn / DQ_NO_MTF_MANY=0) mtf_many_kernel (dq_mtf_many.h) follows
+//         bwt_many_kernel on the same stream: its symbols, counts and in-use maps go into the suffix-array region, which is
+//         dead by then (BwtGroupAreas: an overlay that is checked to fit), and travel back instead of `last`.  Its two
+//         classes take their work from bwt_many_kernel's own list, which is longest first: the long class its head, the
+//         short class the rest
+//   Bits  (kHuffManyOn / DQ_NO_HUFF_MANY=0) huff_many_kernel (dq_huff_many.h) follows mtf_many_kernel on the same stream, on
+//         the same list: the blocks' CRCs go up, 4 bytes per block, and the blocks' bits and bit counts travel back instead
+//         of the symbols, which never leave the device.
+// The origins, the flag word and the single wait are the same at every stage; each kernel claims from a word of its own of
+// the group's one counter block (CounterWord, dq_block_groups.h).
 #pragma once
 
 #include "dq_mtf_many.h"
@@ -53,7 +58,7 @@ constexpr int kBwtPer = kBwtTile / kBwtThreads;
 constexpr int kBwtWaves = kBwtThreads / kWave;
 static_assert(kBwtPer * kBwtThreads == kBwtTile && kBwtWaves * kWave == kBwtThreads, "whole stripes of whole waves");
 constexpr int kDoubleThreads = 1024;
-constexpr int64_t kBwtMaxN = 1ll << 30;   // a block of this many bytes has a doubling beyond 32-bit indices
+constexpr int64_t kBwtMaxN = kBlockMaxN;  // a block of this many bytes (2^30) has a doubling beyond 32-bit indices
 
 // off[count + 1]: where the blocks begin in `blocks`; doff[count + 1] comes out as twice that, where their doublings
 // begin in `doubled`.
@@ -158,27 +163,17 @@ __global__ __launch_bounds__(kBwtThreads) void bwt_many_kernel(const uint8_t *__
 
 namespace {
 
-// what a group's pointers are: host buffers (copied in and out) or device buffers (used where they lie)
-struct BwtIo {
-    bool host;
-    const uint8_t *blocks;
-    uint8_t *last;
-    int32_t *origins;
-    uint16_t *syms = nullptr;           // set (host form only): the symbol streams come back instead of `last`, dq_mtf_hip_many's layout
-    int32_t *nsyms = nullptr;
-    uint32_t *in_use = nullptr;
-    const uint32_t *crcs = nullptr;     // set (host form only): the blocks' BITS come back instead (dq_huff_hip_many's layout), no symbols
-    const int64_t *slots = nullptr;     // the group's cnt + 1 slot offsets as the caller counts them; bits: the group's first slot
-    uint8_t *bits = nullptr;
-    int32_t *nbits = nullptr;
-};
-
-// One group: blocks [0, cnt) at io's pointers, drel their DOUBLED offsets relative to the first, plan the sort's plan of
-// those (for a block that travels alone: itself on `longs`).  c is the transforms' own context (kBwtSlot), held by the
-// caller; the single sorts lease slots of their own and run on st like everything else.  Returns with st drained.
-inline int bwt_group(DeviceCtx &c, hipStream_t st, int dev, const BwtIo &io, const std::vector<int64_t> &drel, int32_t cnt,
-                     const ManyPlan &plan)
+// One group: blocks [0, cnt) at `blocks`, their origins and `out` (the stage and its arrays from the group's first block on;
+// bits.slots: the group's cnt + 1 slot offsets as the caller counts them) -- host buffers (copied in and out) or device
+// buffers (used where they lie: BlockStage::Last only) --, drel their DOUBLED offsets relative to the first, plan the sort's
+// plan of those (for a block that travels alone: itself on `longs`).  c is the transforms' own context (kBwtSlot), held by
+// the caller; the single sorts lease slots of their own and run on st like everything else.  The frame is run_group
+// (dq_runtime.h), the areas BwtGroupAreas (dq_block_groups.h); the three parts below enqueue in turn, as far as out.stage
+// asks, and the last of them reads back.  Returns with st drained.
+inline int bwt_group(DeviceCtx &c, hipStream_t st, int dev, bool host, const uint8_t *blocks, int32_t *origins, const BwtOut &out,
+                     const std::vector<int64_t> &drel, int32_t cnt, const ManyPlan &plan)
 {
+    const BlockStage stage = out.stage;
     const int64_t bytes = drel[(size_t)cnt] / 2;
     std::vector<int64_t> rel((size_t)cnt + 1);
     for (int32_t j = 0; j <= cnt; ++j) rel[(size_t)j] = drel[(size_t)j] / 2;
@@ -186,105 +181,89 @@ inline int bwt_group(DeviceCtx &c, hipStream_t st, int dev, const BwtIo &io, con
     build_work_lists(work, cnt, [&](int32_t j) { return rel[(size_t)j + 1] > rel[(size_t)j] ? 0 : -1; },
                      [&](int32_t j) { return rel[(size_t)j + 1] - rel[(size_t)j]; });
     const int listed = work.class_count[0];
-    const bool shared = plan.shared(), huff = io.host && io.bits != nullptr, mtf = huff || (io.host && io.syms != nullptr);
-    std::vector<int64_t> slot_rel(huff ? (size_t)cnt + 1 : 0);
-    for (size_t j = 0; j < slot_rel.size(); ++j) slot_rel[j] = io.slots[j] - io.slots[0];
-    const size_t h_bits = huff ? (size_t)slot_rel[(size_t)cnt] : 0;
-    // the bits' areas: CRCs, slot offsets, slots, bit counts, selectors
-    const size_t b_hword = huff ? align_up((size_t)cnt * sizeof(int32_t)) : 0, b_hoff = huff ? align_up(slot_rel.size() * sizeof(int64_t)) : 0,
-                 b_hbits = huff ? align_up(h_bits + 8) : 0, b_hsel = huff ? huff_sel_bytes(bytes, cnt) : 0;
-    // the symbols' areas inside the suffix-array region (8 bytes per block byte: only a group of nearly empty blocks needs more)
-    const size_t m_syms = align_up(2 * ((size_t)bytes + (size_t)cnt)), m_nsyms = align_up((size_t)cnt * sizeof(int32_t)),
-                 m_in_use = align_up((size_t)cnt * 8 * sizeof(uint32_t));
-    const size_t b_blk = io.host ? align_up((size_t)bytes + 64) : 0, b_org = io.host ? align_up((size_t)cnt * sizeof(int32_t)) : 0,
-                 b_off = align_up(rel.size() * sizeof(int64_t)), b_dbl = align_up(2 * (size_t)bytes + 64),
-                 b_sa = std::max(align_up(2 * (size_t)bytes * sizeof(int32_t)), mtf ? m_syms + m_nsyms + m_in_use : 0), b_work = many_ctl_bytes(listed),
-                 b_ctl = shared ? many_ctl_bytes(plan.listed()) : 0, b_scratch = shared ? many_scratch_bytes(c, plan) : 0,
+    const bool shared = plan.shared();
+    std::vector<int64_t> slot_rel(stage == BlockStage::Bits ? (size_t)cnt + 1 : 0);         // the bits' slots, relative to the group's first
+    for (size_t j = 0; j < slot_rel.size(); ++j) slot_rel[j] = out.bits.slots[j] - out.bits.slots[0];
+    const size_t out_bytes = slot_rel.empty() ? 0 : (size_t)slot_rel.back();
+    const size_t b_ctl = shared ? many_ctl_bytes(plan.listed()) : 0, b_scratch = shared ? many_scratch_bytes(c, plan) : 0,
                  b_large = shared ? many_large_bytes(plan, drel.data()) : 0;
-    DQ_TRY(ensure_ws(c, b_blk + b_org + 2 * b_off + b_dbl + b_sa + b_work + b_ctl + b_scratch + b_large + 2 * b_hword + b_hoff + b_hbits + b_hsel));
-    char *at = c.ws;
-    auto carve = [&](size_t b) { char *p = at; at += b; return p; };
-    uint8_t *d_blk = reinterpret_cast<uint8_t *>(carve(b_blk));
-    int32_t *d_org = reinterpret_cast<int32_t *>(carve(b_org));
-    int64_t *d_off = reinterpret_cast<int64_t *>(carve(b_off));
-    int64_t *d_doff = reinterpret_cast<int64_t *>(carve(b_off));
-    uint8_t *d_dbl = reinterpret_cast<uint8_t *>(carve(b_dbl));
-    int32_t *d_sa = reinterpret_cast<int32_t *>(carve(b_sa));
-    char *d_work = carve(b_work), *d_ctl = carve(b_ctl), *d_scratch = carve(b_scratch), *d_large = carve(b_large);
-    uint32_t *d_crcs = reinterpret_cast<uint32_t *>(carve(b_hword));
-    int32_t *d_nbits = reinterpret_cast<int32_t *>(carve(b_hword));
-    int64_t *d_slots = reinterpret_cast<int64_t *>(carve(b_hoff));
-    uint8_t *d_bits = reinterpret_cast<uint8_t *>(carve(b_hbits));
-    uint8_t *d_sel = reinterpret_cast<uint8_t *>(carve(b_hsel));
-    uint32_t *d_next = reinterpret_cast<uint32_t *>(d_work), *d_flag = d_next + 16;
-    int32_t *d_order = reinterpret_cast<int32_t *>(d_work + kManyCounterBytes);
-    const uint8_t *d_in = io.host ? d_blk : io.blocks;
-    uint8_t *d_last = io.host ? d_blk : io.last;               // (the host form's copy of the blocks is dead once it is doubled)
-    int32_t *d_origins = io.host ? d_org : io.origins;
-    uint16_t *d_syms = reinterpret_cast<uint16_t *>(d_sa);
-    int32_t *d_nsyms = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(d_sa) + m_syms);
-    uint32_t *d_in_use = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(d_sa) + m_syms + m_nsyms);
-    int n_long = 0;                                             // (the list is longest first: the long class is its head)
-    while (mtf && n_long < listed && rel[(size_t)work.order[(size_t)n_long] + 1] - rel[(size_t)work.order[(size_t)n_long]] > mtf_short_max()) ++n_long;
+    BwtGroupAreas a;
+    DQ_TRY(carve_ws(c, [&](Carver &cv) { a = BwtGroupAreas(cv, host, stage, bytes, cnt, listed, b_ctl, b_scratch, b_large, out_bytes); }));
+    if (!a.overlay_fits) return fail(DQ_ERR_HIP, "the symbol areas outgrew the suffix arrays' area");
+    const int32_t *d_order = work_order(a.work);
+    const uint8_t *d_in = host ? a.blk : blocks;
+    uint8_t *d_last = host ? a.blk : out.last;      // (the host form's copy of the blocks is dead once it is doubled)
+    int32_t *d_origins = host ? a.org : origins;
     uint32_t bad = 0;
     t_sort_info = {};
-    auto run = [&]() -> int {
+
+    // ---- the transform: the doublings, their sorts, the walk over the suffix arrays
+    auto transform = [&]() -> int {
         Launcher L{c, st, g_prof_on.load()};
-        HIP_TRY(hipMemsetAsync(d_work, 0, kManyCounterBytes, st));                   // the claim word and the flag word
-        if (io.host) {
-            HIP_TRY(hipMemcpyAsync(d_blk, io.blocks, (size_t)bytes, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemsetAsync(d_org, 0xff, (size_t)cnt * sizeof(int32_t), st)); // an empty block's origin stays -1
+        if (host) {
+            HIP_TRY(hipMemcpyAsync(a.blk, blocks, (size_t)bytes, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemsetAsync(a.org, 0xff, word_area_bytes(cnt), st));                  // an empty block's origin stays -1
         }
-        HIP_TRY(hipMemcpyAsync(d_off, rel.data(), rel.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_order, work.order.data(), (size_t)listed * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(a.off, rel.data(), offset_area_bytes(cnt), hipMemcpyHostToDevice, st));
         LAUNCH(L, DQ_K_SMALL_MANY, cnt, bytes * 3,
                hipLaunchKernelGGL(double_blocks_kernel, dim3((unsigned)std::min<int32_t>(cnt, 4 * std::max(c.ncu, 64))),
-                                  dim3(kDoubleThreads), 0, st, d_in, d_off, cnt, d_dbl, d_doff));
+                                  dim3(kDoubleThreads), 0, st, d_in, a.off, cnt, a.dbl, a.doff));
         if (shared) {
-            DQ_TRY(launch_many(c, st, plan, d_dbl, d_doff, d_sa, d_ctl, d_scratch));
-            DQ_TRY(launch_large(c, st, plan, drel.data(), d_dbl, d_sa, d_large));
+            DQ_TRY(launch_many(c, st, plan, a.dbl, a.doff, a.sa, a.ctl, a.scratch));
+            DQ_TRY(launch_large(c, st, plan, drel.data(), a.dbl, a.sa, a.large));
         }
         for (int32_t j : plan.longs)
-            DQ_TRY(many_single_dev(d_dbl + drel[(size_t)j], drel[(size_t)j + 1] - drel[(size_t)j], d_sa + drel[(size_t)j], dev, (void *)st));
+            DQ_TRY(many_single_dev(a.dbl + drel[(size_t)j], drel[(size_t)j + 1] - drel[(size_t)j], a.sa + drel[(size_t)j], dev, (void *)st));
         const int grid = std::min(listed, resident_groups(&c.bwt_many_groups, (const void *)bwt_many_kernel, kBwtThreads, dev));
         LAUNCH(L, DQ_K_SMALL_MANY, listed, bytes * 11,
-               hipLaunchKernelGGL(bwt_many_kernel, dim3((unsigned)grid), dim3(kBwtThreads), 0, st, d_dbl, d_doff, d_order, listed,
-                                  d_next, d_sa, d_off, d_last, d_origins, d_flag));
-        if (mtf) {                                                  // (behind bwt_many_kernel: the suffix arrays are dead)
-            HIP_TRY(hipMemsetAsync(d_nsyms, 0, m_nsyms + m_in_use, st));             // what an empty block keeps
-            DQ_TRY(launch_mtf(c, st, dev, d_last, d_off, d_order + n_long, listed - n_long, d_order, n_long, d_next + 32, bytes,
-                              d_syms, d_nsyms, d_in_use));
-        }
-        if (huff) {                                                 // (behind mtf_many_kernel, on bwt_many_kernel's list)
-            HIP_TRY(hipMemcpyAsync(d_crcs, io.crcs, (size_t)cnt * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(d_slots, slot_rel.data(), slot_rel.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemsetAsync(d_nbits, 0, (size_t)cnt * sizeof(int32_t), st));          // what an empty block keeps
-            DQ_TRY(launch_huff(c, st, dev, d_syms, d_nsyms, d_in_use, d_off, d_order, listed, d_next + 24, d_crcs, d_origins, d_slots,
-                               d_bits, d_nbits, d_sel, bytes));
-        }
-        // (one checked step: a failure must not leave a copy into the caller's arrays in flight behind the return)
-        hipError_t e = hipSuccess;
-        auto keep = [&](hipError_t x) { if (e == hipSuccess) e = x; };
-        if (huff) {
-            if (h_bits) keep(hipMemcpyAsync(io.bits, d_bits, h_bits, hipMemcpyDeviceToHost, st));
-            keep(hipMemcpyAsync(io.nbits, d_nbits, (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-            keep(hipMemcpyAsync(io.origins, d_org, (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        } else if (mtf) {
-            keep(hipMemcpyAsync(io.syms, d_syms, 2 * ((size_t)bytes + (size_t)cnt), hipMemcpyDeviceToHost, st));
-            keep(hipMemcpyAsync(io.nsyms, d_nsyms, (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-            keep(hipMemcpyAsync(io.in_use, d_in_use, (size_t)cnt * 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-            keep(hipMemcpyAsync(io.origins, d_org, (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        } else if (io.host) {
-            keep(hipMemcpyAsync(io.last, d_blk, (size_t)bytes, hipMemcpyDeviceToHost, st));
-            keep(hipMemcpyAsync(io.origins, d_org, (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        }
-        keep(hipMemcpyAsync(&bad, d_flag, sizeof bad, hipMemcpyDeviceToHost, st));
-        keep(hipStreamSynchronize(st));
-        HIP_TRY(e);
-        return flush_profile(c);
+               hipLaunchKernelGGL(bwt_many_kernel, dim3((unsigned)grid), dim3(kBwtThreads), 0, st, a.dbl, a.doff, d_order, listed,
+                                  counter_word(a.work, kBwtClaimWord), a.sa, a.off, d_last, d_origins, counter_word(a.work, kBwtFlagWord)));
+        return DQ_OK;
     };
-    const int rc = run();
-    if (rc != DQ_OK) { drop_pending(c, st); return rc; }
+    auto last_back = [&](FirstError &keep) {
+        if (host) keep(hipMemcpyAsync(out.last, a.blk, (size_t)bytes, hipMemcpyDeviceToHost, st));
+    };
+
+    // ---- move-to-front behind it, the symbols into the suffix arrays' area, which is dead by then.  Its two classes take
+    // their work from the transform's own list, which is longest first: the long class its head, the short class the rest.
+    int n_long = 0;
+    while (stage != BlockStage::Last && n_long < listed &&
+           rel[(size_t)work.order[(size_t)n_long] + 1] - rel[(size_t)work.order[(size_t)n_long]] > mtf_short_max())
+        ++n_long;
+    auto mtf = [&]() -> int {
+        // what an empty block keeps (ONE memset: the in-use maps are carved directly behind the counts' area)
+        HIP_TRY(hipMemsetAsync(a.sy.nsyms, 0, align_up(word_area_bytes(cnt)) + in_use_area_bytes(cnt), st));
+        return launch_mtf(c, st, dev, d_last, a.off, d_order + n_long, listed - n_long, d_order, n_long, a.work, bytes, a.sy);
+    };
+    auto syms_back = [&](FirstError &keep) {
+        keep(hipMemcpyAsync(out.syms.syms, a.sy.syms, sym_area_bytes(bytes, cnt), hipMemcpyDeviceToHost, st));
+        keep(hipMemcpyAsync(out.syms.nsyms, a.sy.nsyms, word_area_bytes(cnt), hipMemcpyDeviceToHost, st));
+        keep(hipMemcpyAsync(out.syms.in_use, a.sy.in_use, in_use_area_bytes(cnt), hipMemcpyDeviceToHost, st));
+    };
+
+    // ---- the coding tables and bits behind that, on the transform's list: the CRCs go up, the symbols never come down
+    auto huff = [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(a.bi.crcs, out.bits.crcs, word_area_bytes(cnt), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(a.bi.slots, slot_rel.data(), offset_area_bytes(cnt), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(a.bi.nbits, 0, word_area_bytes(cnt), st));                    // what an empty block keeps
+        return launch_huff(c, st, dev, a.sy.syms, a.sy.nsyms, a.sy.in_use, a.off, d_order, listed, a.work, a.bi.crcs, d_origins, a.bi.slots,
+                           a.bi.bits, a.bi.nbits, a.bi.sel, bytes);
+    };
+    auto bits_back = [&](FirstError &keep) {
+        if (out_bytes) keep(hipMemcpyAsync(out.bits.bits, a.bi.bits, out_bytes, hipMemcpyDeviceToHost, st));
+        keep(hipMemcpyAsync(out.bits.nbits, a.bi.nbits, word_area_bytes(cnt), hipMemcpyDeviceToHost, st));
+    };
+
+    auto enqueue = [&]() -> int {
+        DQ_TRY(transform());
+        if (stage != BlockStage::Last) DQ_TRY(mtf());
+        return stage == BlockStage::Bits ? huff() : DQ_OK;
+    };
+    DQ_TRY(run_group(c, st, a.work, work.order, enqueue, [&](FirstError &keep) {
+        (stage == BlockStage::Bits ? bits_back(keep) : stage == BlockStage::Syms ? syms_back(keep) : last_back(keep));
+        if (host) keep(hipMemcpyAsync(origins, a.org, word_area_bytes(cnt), hipMemcpyDeviceToHost, st));
+        keep(hipMemcpyAsync(&bad, counter_word(a.work, kBwtFlagWord), sizeof bad, hipMemcpyDeviceToHost, st));
+    }));
     if (bad) return fail(DQ_ERR_HIP, "bzip2 block transform failed");
     many_account(plan, !shared, shared ? b_scratch : 0);
     return DQ_OK;
@@ -292,8 +271,8 @@ inline int bwt_group(DeviceCtx &c, hipStream_t st, int dev, const BwtIo &io, con
 
 // Both forms behind their argument checks: `off` is the host's copy of the offsets.  The walk is dq_sufsort_hip_many_i32's,
 // on the doubled lengths.
-inline int bwt_many_walk(int dev, void *stream, const BwtIo &io, const int64_t *off, int32_t count, int64_t *shared_out,
-                         bool large_by_default)
+inline int bwt_many_walk(int dev, void *stream, bool host, const uint8_t *blocks, int32_t *origins, const BwtOut &out, const int64_t *off,
+                         int32_t count, int64_t *shared_out, bool large_by_default)
 {
     std::vector<int64_t> doff((size_t)count + 1);
     for (int32_t j = 0; j <= count; ++j) doff[(size_t)j] = 2 * off[j];
@@ -302,12 +281,6 @@ inline int bwt_many_walk(int dev, void *stream, const BwtIo &io, const int64_t *
     DQ_TRY(init_ctx(c, dev));
     if (c.ncu <= 0 && hipDeviceGetAttribute(&c.ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) c.ncu = 0;
     hipStream_t st = stream ? (hipStream_t)stream : c.stream;
-    auto group_io = [&](int32_t i) {
-        BwtIo g{io.host, io.blocks + off[i], io.last ? io.last + off[i] : nullptr, io.origins + i};
-        if (io.syms) { g.syms = io.syms + off[i] + i; g.nsyms = io.nsyms + i; g.in_use = io.in_use + 8 * (size_t)i; }
-        if (io.bits) { g.crcs = io.crcs + i; g.slots = io.slots + i; g.bits = io.bits + io.slots[i]; g.nbits = io.nbits + i; }
-        return g;
-    };
     auto single = [&](int32_t i) -> int {
         const int64_t n2 = doff[(size_t)i + 1] - doff[(size_t)i];
         if (n2 == 0) return DQ_OK;
@@ -315,55 +288,37 @@ inline int bwt_many_walk(int dev, void *stream, const BwtIo &io, const int64_t *
         plan.longs.push_back(0);
         if (n2 > kMidMaxN) plan.above_mid = 1;
         else if (n2 > kSmallMaxN) plan.mid_single = 1;
-        return bwt_group(c, st, dev, group_io(i), {0, n2}, 1, plan);
+        return bwt_group(c, st, dev, host, blocks + off[i], origins + i, out.from(off[i], i), {0, n2}, 1, plan);
     };
     auto chunk = [&](int32_t i, int32_t e, const std::vector<int64_t> &drel, const ManyPlan &plan) -> int {
-        DQ_TRY(bwt_group(c, st, dev, group_io(i), drel, e - i, plan));
+        DQ_TRY(bwt_group(c, st, dev, host, blocks + off[i], origins + i, out.from(off[i], i), drel, e - i, plan));
         if (shared_out) *shared_out += plan.shorts();
         return DQ_OK;
     };
     return walk_many_host(doff.data(), count, large_by_default, single, chunk);
 }
 
-// offsets as check_many_offsets wants them, and no block whose doubling leaves 32-bit indices
-inline int check_bwt_offsets(const int64_t *off, int32_t count)
-{
-    DQ_TRY(check_many_offsets(off, count));
-    for (int32_t j = 0; j < count; ++j)
-        if (off[j + 1] - off[j] >= kBwtMaxN)
-            return fail(DQ_ERR_TOO_LARGE, "a block has 2^30 bytes or more: its doubling exceeds 32-bit indices");
-    return DQ_OK;
-}
+// check_block_lengths' message here: no block whose doubling leaves 32-bit indices
+constexpr const char *kBwtTooLong = "a block has 2^30 bytes or more: its doubling exceeds 32-bit indices";
 
 }  // namespace
 
 // host buffers in / out
-int bwt_many_host(const uint8_t *blocks, const int64_t *offsets, int32_t count, uint8_t *last, int32_t *origins, int32_t device,
-                  int64_t *shared_out, bool large_by_default, const MtfOut *mtf, const HuffOut *huff)
+int bwt_many_host(const uint8_t *blocks, const int64_t *offsets, int32_t count, const BwtOut &out, int32_t *origins, int32_t device,
+                  int64_t *shared_out, bool large_by_default)
 {
     if (shared_out) *shared_out = 0;
     if (count < 0) return fail(DQ_ERR_BAD_ARGS, "negative count");
     if (count == 0) return DQ_OK;
-    if (!blocks || !offsets || !origins || (huff ? !huff->crcs || !huff->slots || !huff->bits || !huff->nbits
-                                                 : mtf ? !mtf->syms || !mtf->nsyms || !mtf->in_use : !last))
-        return fail(DQ_ERR_BAD_ARGS, "null buffer");
-    DQ_TRY(check_bwt_offsets(offsets, count));
-    if (huff) DQ_TRY(check_huff_offsets(offsets, huff->slots, count));
+    if (!blocks || !offsets || !origins || !out.complete()) return fail(DQ_ERR_BAD_ARGS, "null buffer");
+    DQ_TRY(check_many_offsets(offsets, count));
+    DQ_TRY(check_block_lengths(offsets, count, kBwtTooLong));
+    if (out.stage == BlockStage::Bits) DQ_TRY(check_huff_offsets(offsets, out.bits.slots, count));
     int dev = 0;
     DQ_TRY(resolve_device(device, &dev));
     std::fill(origins, origins + count, -1);                    // (what an empty block keeps)
-    BwtIo io{true, blocks, last, origins};
-    if (huff) {
-        io.last = nullptr;
-        io.crcs = huff->crcs; io.slots = huff->slots; io.bits = huff->bits; io.nbits = huff->nbits;
-        std::fill(huff->nbits, huff->nbits + count, 0);         // (what a block keeps that no group holds: an empty one)
-    } else if (mtf) {
-        io.last = nullptr;
-        io.syms = mtf->syms; io.nsyms = mtf->nsyms; io.in_use = mtf->in_use;
-        std::fill(mtf->nsyms, mtf->nsyms + count, 0);           // (what a block keeps that no group holds: an empty one)
-        std::fill(mtf->in_use, mtf->in_use + 8 * (size_t)count, 0u);
-    }
-    return bwt_many_walk(dev, nullptr, io, offsets, count, shared_out, large_by_default);
+    out.clear(count);
+    return bwt_many_walk(dev, nullptr, true, blocks, origins, out, offsets, count, shared_out, large_by_default);
 }
 
 // device buffers in / out
@@ -382,14 +337,12 @@ int bwt_many_dev(const void *d_blocks, const void *d_offsets, int32_t count, voi
         DQ_TRY(init_ctx(c, dev));
         hipStream_t st = stream ? (hipStream_t)stream : c.stream;
         DQ_TRY(fetch_many_offsets((const int64_t *)d_offsets, count, st, off));
-        for (int32_t j = 0; j < count; ++j)
-            if (off[(size_t)j + 1] - off[(size_t)j] >= kBwtMaxN)
-                return fail(DQ_ERR_TOO_LARGE, "a block has 2^30 bytes or more: its doubling exceeds 32-bit indices");
+        DQ_TRY(check_block_lengths(off.data(), count, kBwtTooLong));
         HIP_TRY(hipMemsetAsync(d_origins, 0xff, (size_t)count * sizeof(int32_t), st));      // an empty block's origin stays -1
         HIP_TRY(hipStreamSynchronize(st));
     }
-    return bwt_many_walk(dev, stream, BwtIo{false, (const uint8_t *)d_blocks, (uint8_t *)d_last, (int32_t *)d_origins}, off.data(),
-                         count, nullptr, /*large_by_default=*/true);
+    return bwt_many_walk(dev, stream, false, (const uint8_t *)d_blocks, (int32_t *)d_origins, BwtOut((uint8_t *)d_last), off.data(), count,
+                         nullptr, /*large_by_default=*/true);
 }
 
 }  // namespace dq

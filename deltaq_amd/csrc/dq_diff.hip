@@ -1598,6 +1598,34 @@ int diff_many_emit(const ManyFiles &f, const ManyChunk &k, bool framing, std::ve
     return DQ_OK;
 }
 
+// What phase 4 of a framed chunk holds for phase 5, by the route it takes (block_route, dq_block_groups.h): `doubled` bytes
+// of doubled blocks in `nblocks` blocks.  Block `place` of the list has
+//   none      (the host's sort) its doubling in `text` and that doubling's suffix array in `sa`, both from boff[place] on
+//   Last      its bytes in `text` and its last column in `last` from boff[place] / 2 on, its origin row in origin[place]
+//   Syms      (mtf_many_kernel behind bwt_many_kernel, dq_mtf_many.h) its symbols at syms[boff[place] / 2 + place ...),
+//             nsyms[place] of them, and inuse[8 place ...)
+//   Bits      (huff_many_kernel behind that, dq_huff_many.h) nbits[place] bits from bits[slot[place]] on; its CRC went up
+//             in crc[place].  `slot` is filled and `bits` sized by the caller, from the blocks' bounds.
+struct BlockBuffers {
+    std::vector<uint8_t> text, last, bits;
+    std::vector<int32_t> sa, origin, nsyms, nbits;
+    std::vector<uint16_t> syms;
+    std::vector<uint32_t> inuse, crc;
+    std::vector<int64_t> slot;
+    BlockBuffers(std::optional<BlockStage> route, int64_t doubled, int64_t nblocks)
+    {
+        const size_t n = (size_t)nblocks, half = (size_t)(doubled / 2);
+        text.resize(!route ? (size_t)doubled : half);
+        if (!route) { sa.resize((size_t)doubled); return; }
+        origin.resize(n);
+        switch (*route) {
+        case BlockStage::Last: last.resize(half); break;
+        case BlockStage::Syms: syms.resize(half + n); nsyms.resize(n); inuse.resize(8 * n); break;
+        case BlockStage::Bits: slot.assign(n + 1, 0); crc.resize(n); nbits.resize(n); break;
+        }
+    }
+};
+
 // ---- 4. + 5. of a framed chunk: from the encoders diff_many_emit left in `out` to the patches in out[j].patch
 int diff_many_frame(const ManyFiles &f, const ManyChunk &k, int dev, std::vector<ManyPair> &out, FinishStats &fin)
 {
@@ -1628,49 +1656,37 @@ int diff_many_frame(const ManyFiles &f, const ManyChunk &k, int dev, std::vector
     // With the device transform the blocks go up as they are and come back transformed (dq_bwt_hip_many's body: doubling,
     // sort and the walk over the suffix arrays stay on the device); otherwise they are doubled here, sorted through
     // dq_sufsort_hip_many_i32's body and walked by the framing threads.  Either way the same walker cuts the same doubled
-    // lengths into the same chunks and launches.
-    const bool on_device = flags().no_bwt_many ? *flags().no_bwt_many == 0 : kBwtManyOn;
-    // ... and with move-to-front on the device too (kMtfManyOn, dq_runtime.h: off by default; DQ_NO_MTF_MANY=0) the
-    // symbol streams come back instead of the last columns (mtf_many_kernel behind bwt_many_kernel, dq_mtf_many.h): block
-    // `place` has its symbols at bsyms[boff[place] / 2 + place ...), bnsyms[place] of them, and binuse[8 place ...).
-    const bool mtf_on_device = on_device && (flags().no_mtf_many ? *flags().no_mtf_many == 0 : kMtfManyOn);
-    // ... and with the coding tables on the device as well (kHuffManyOn, dq_runtime.h: off; DQ_NO_HUFF_MANY=0) the blocks'
-    // bits come back instead of the symbols (huff_many_kernel behind mtf_many_kernel, dq_huff_many.h): block `place` has
-    // bnbits[place] bits from bbits[bslot[place]] on, its CRC went up in bcrc[place].
-    const bool huff_on_device = mtf_on_device && (flags().no_huff_many ? *flags().no_huff_many == 0 : kHuffManyOn);
-    const int64_t per = on_device ? 2 : 1;                 // boff counts doubled bytes: a block's place in btext is boff / per
-    std::vector<uint8_t> btext((size_t)(boff.back() / per));
-    std::vector<int32_t> bsa(on_device ? 0 : (size_t)boff.back());
-    std::vector<uint8_t> blast(on_device && !mtf_on_device ? btext.size() : 0);
-    const bool syms_back = mtf_on_device && !huff_on_device;
-    std::vector<uint16_t> bsyms(syms_back ? btext.size() + (size_t)nblocks : 0);
-    std::vector<int32_t> bnsyms(syms_back ? (size_t)nblocks : 0);
-    std::vector<uint32_t> binuse(syms_back ? 8 * (size_t)nblocks : 0);
-    std::vector<int64_t> bslot(huff_on_device ? (size_t)nblocks + 1 : 0);
-    std::vector<uint32_t> bcrc(huff_on_device ? (size_t)nblocks : 0);
-    std::vector<int32_t> bnbits(huff_on_device ? (size_t)nblocks : 0);
-    if (huff_on_device) {
+    // lengths into the same chunks and launches.  Which way, and how far on the device: the three debug flags beside the
+    // constants they override (dq_runtime.h: all off by default), by block_route (dq_block_groups.h), which is
+    //   on_device      = flags().no_bwt_many ? *flags().no_bwt_many == 0 : kBwtManyOn
+    //   mtf_on_device  = on_device && (flags().no_mtf_many ? *flags().no_mtf_many == 0 : kMtfManyOn)
+    //   huff_on_device = mtf_on_device && (flags().no_huff_many ? *flags().no_huff_many == 0 : kHuffManyOn)
+    // and the furthest stage that is on, or none.
+    const std::optional<BlockStage> route =
+        block_route(flags().no_bwt_many, flags().no_mtf_many, flags().no_huff_many, kBwtManyOn, kMtfManyOn, kHuffManyOn);
+    const int64_t per = !route ? 1 : 2;    // boff counts doubled bytes: a block's place in `text` is boff / per
+    BlockBuffers B(route, boff.back(), nblocks);
+    if (route == BlockStage::Bits) {
         for (int64_t b = 0; b < nblocks; ++b) {
             const int64_t need = huff_many_bound((boff[(size_t)b + 1] - boff[(size_t)b]) / 2);
             if (need < 0) return fail(DQ_ERR_TOO_LARGE, "a bzip2 block exceeds 900 000 bytes");
-            bslot[(size_t)b + 1] = bslot[(size_t)b] + need;
+            B.slot[(size_t)b + 1] = B.slot[(size_t)b] + need;
         }
         for (ManyPair &w : out) {
             int64_t at = w.first_block;
             for (int s = 0; s < 3; ++s)
-                for (size_t b = 0; b < w.enc[s]->block_count(); ++b) bcrc[(size_t)bplace[(size_t)at++]] = w.enc[s]->block_crc(b);
+                for (size_t b = 0; b < w.enc[s]->block_count(); ++b) B.crc[(size_t)bplace[(size_t)at++]] = w.enc[s]->block_crc(b);
         }
+        B.bits.resize((size_t)B.slot.back() + 8);
     }
-    std::vector<uint8_t> bbits(huff_on_device ? (size_t)bslot.back() + 8 : 0);
-    std::vector<int32_t> borigin(on_device ? (size_t)nblocks : 0);
     diff_many_parallel(cnt, [&](int64_t j) {
         ManyPair &w = out[(size_t)j];
         int64_t at = w.first_block;
         for (int s = 0; s < 3; ++s)
             for (size_t b = 0; b < w.enc[s]->block_count(); ++b) {
                 const std::vector<uint8_t> &rle = w.enc[s]->block_rle(b);
-                uint8_t *to = btext.data() + boff[(size_t)bplace[(size_t)at++]] / per;
-                if (!on_device) bz2::double_block(rle, to);
+                uint8_t *to = B.text.data() + boff[(size_t)bplace[(size_t)at++]] / per;
+                if (!route) bz2::double_block(rle, to);
                 else if (!rle.empty()) memcpy(to, rle.data(), rle.size());
             }
     });
@@ -1679,17 +1695,18 @@ int diff_many_frame(const ManyFiles &f, const ManyChunk &k, int dev, std::vector
     // DQ_LARGE_MANY_MIN asks for it: the block-sort phase has not been measured faster with it than with the one-by-one
     // route, whose sorts get no hint either but run the device sorter's LDS group rounds (docs/ROUNDS.md, round 11).
     int rc;
-    if (on_device) {
+    if (!route)
+        rc = sufsort_many_host(B.text.data(), boff.data(), (int32_t)nblocks, B.sa.data(), dev, &shared, /*large_by_default=*/false);
+    else {
         std::vector<int64_t> half((size_t)nblocks + 1);
         for (int64_t b = 0; b <= nblocks; ++b) half[(size_t)b] = boff[(size_t)b] / 2;
-        const MtfOut mtf{bsyms.data(), bnsyms.data(), binuse.data()};
-        const HuffOut huff{bcrc.data(), bslot.data(), bbits.data(), bnbits.data()};
-        rc = bwt_many_host(btext.data(), half.data(), (int32_t)nblocks, blast.data(), borigin.data(), dev, &shared, /*large_by_default=*/false,
-                           mtf_on_device ? &mtf : nullptr, huff_on_device ? &huff : nullptr);
-    } else
-        rc = sufsort_many_host(btext.data(), boff.data(), (int32_t)nblocks, bsa.data(), dev, &shared, /*large_by_default=*/false);
+        const BwtOut to = route == BlockStage::Bits   ? BwtOut(BwtBits{B.crc.data(), B.slot.data(), B.bits.data(), B.nbits.data()})
+                          : route == BlockStage::Syms ? BwtOut(SymAreas(B.syms.data(), B.nsyms.data(), B.inuse.data()))
+                                                      : BwtOut(B.last.data());
+        rc = bwt_many_host(B.text.data(), half.data(), (int32_t)nblocks, to, B.origin.data(), dev, &shared, /*large_by_default=*/false);
+    }
     if (rc != DQ_OK) return rc;
-    std::vector<uint8_t>().swap(btext);
+    std::vector<uint8_t>().swap(B.text);
     fin.shared_block_sorts = shared;
     fin.single_block_sorts = nblocks - shared;
     fin.block_sort_us = us_since(t0);
@@ -1704,12 +1721,15 @@ int diff_many_frame(const ManyFiles &f, const ManyChunk &k, int dev, std::vector
             for (int s = 0; s < 3; ++s) {
                 for (size_t b = 0; b < w.enc[s]->block_count(); ++b, ++at) {
                     const int64_t place = bplace[(size_t)at];
-                    if (huff_on_device) w.enc[s]->encode_block_bits(b, bbits.data() + bslot[(size_t)place], bnbits[(size_t)place]);
-                    else if (mtf_on_device)
-                        w.enc[s]->encode_block_mtf(b, borigin[(size_t)place], binuse.data() + 8 * (size_t)place,
-                                                   bsyms.data() + boff[(size_t)place] / 2 + place, bnsyms[(size_t)place]);
-                    else if (on_device) w.enc[s]->encode_block_bwt(b, blast.data() + boff[(size_t)place] / 2, borigin[(size_t)place]);
-                    else w.enc[s]->encode_block_sorted(b, bsa.data() + boff[(size_t)place]);
+                    if (!route) { w.enc[s]->encode_block_sorted(b, B.sa.data() + boff[(size_t)place]); continue; }
+                    switch (*route) {
+                    case BlockStage::Bits: w.enc[s]->encode_block_bits(b, B.bits.data() + B.slot[(size_t)place], B.nbits[(size_t)place]); break;
+                    case BlockStage::Syms:
+                        w.enc[s]->encode_block_mtf(b, B.origin[(size_t)place], B.inuse.data() + 8 * (size_t)place,
+                                                   B.syms.data() + boff[(size_t)place] / 2 + place, B.nsyms[(size_t)place]);
+                        break;
+                    case BlockStage::Last: w.enc[s]->encode_block_bwt(b, B.last.data() + boff[(size_t)place] / 2, B.origin[(size_t)place]); break;
+                    }
                 }
                 if (w.enc[s]->finish(z[s]) != 0) { w.rc = DQ_ERR_HIP; w.err = "bzip2 block transform failed"; return; }
                 w.enc[s].reset();

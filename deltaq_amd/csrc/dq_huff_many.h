@@ -39,6 +39,8 @@
 // bytes than the block has: dq_huff_hip_bound assumes it does not) is refused like the others, nbits = -1.
 // Every kHuff* geometry constant is an UNMEASURED starting value (docs/ROUNDS.md, round 26).  dq_bwt_many.h includes this
 // file beside dq_mtf_many.h.
+// The host side: huff_group is the shared group frame (run_group, dq_runtime.h) around its areas (SymAreas, BitAreas: dq_block_groups.h), its
+// uploads and launch_huff, and the host form's validation and copy-out; bwt_group (dq_bwt_many.h) calls launch_huff too.
 #pragma once
 
 namespace dq {
@@ -49,7 +51,7 @@ constexpr int kHuffPer = 4;               // UNMEASURED: pieces (symbols' codes)
 constexpr int kHuffTile = kHuffThreads * kHuffPer;   // symbols coded per step
 constexpr int kHuffAlpha = 258;           // bzip2: 256 bytes' places, RUNA / RUNB folded in, EOB
 constexpr int kHuffGroups = 6;            // coding tables at most
-constexpr int kHuffGroupSize = 50;        // symbols per selector
+//            kHuffGroupSize = 50            symbols per selector (dq_block_groups.h, beside the rule that sizes the selectors' workspace)
 constexpr int kHuffMaxLen = 17;           // longest code the encoder allows itself (bz2::kEncCodeLen)
 constexpr int kHuffPieceBits = 33;        // longest piece: a length's 16 two-bit steps and its stop bit
 constexpr int64_t kHuffMaxN = 900000;     // bzip2's largest block: 15-bit selector count, 24-bit origPtr
@@ -428,12 +430,10 @@ inline int64_t huff_bound(int64_t n)
     return (bits + 63) / 64 * 8;
 }
 
-// bytes of the selectors' workspace for blocks of `bytes` bytes in `cnt` blocks (huff_many_kernel: sel)
-inline size_t huff_sel_bytes(int64_t bytes, int32_t cnt) { return align_up((size_t)(bytes / kHuffGroupSize) + (size_t)cnt + 1); }
-
-// The launch for the `listed` blocks of d_order (non-empty, longest first); d_claim a zeroed word.  Enqueues only.
+// The launch for the `listed` blocks of d_order (non-empty, longest first); d_work the group's zeroed counter block.
+// Enqueues only.
 inline int launch_huff(DeviceCtx &c, hipStream_t st, int dev, const uint16_t *d_syms, const int32_t *d_nsyms, const uint32_t *d_in_use,
-                       const int64_t *d_off, const int32_t *d_order, int listed, uint32_t *d_claim, const uint32_t *d_crcs,
+                       const int64_t *d_off, const int32_t *d_order, int listed, char *d_work, const uint32_t *d_crcs,
                        const int32_t *d_origins, const int64_t *d_out_off, uint8_t *d_out, int32_t *d_nbits, uint8_t *d_sel, int64_t bytes)
 {
     if (listed <= 0) return DQ_OK;
@@ -441,7 +441,7 @@ inline int launch_huff(DeviceCtx &c, hipStream_t st, int dev, const uint16_t *d_
     const int grid = std::min(listed, resident_groups(&c.huff_many_groups, (const void *)huff_many_kernel, kHuffThreads, dev));
     LAUNCH(L, DQ_K_SMALL_MANY, listed, bytes * 12,
            hipLaunchKernelGGL(huff_many_kernel, dim3((unsigned)grid), dim3(kHuffThreads), 0, st, d_syms, d_nsyms, d_in_use, d_off, d_order,
-                              listed, d_claim, d_crcs, d_origins, d_out_off, d_out, d_nbits, d_sel));
+                              listed, counter_word(d_work, kHuffClaimWord), d_crcs, d_origins, d_out_off, d_out, d_nbits, d_sel));
     return DQ_OK;
 }
 
@@ -459,7 +459,8 @@ struct HuffIo {
 
 // One group: blocks [0, cnt) at io's pointers, rel their block offsets relative to the first, out_rel the slots' (host
 // form: the caller's, where the bits are handed on to; the device works on slots of dq_huff_hip_bound bytes back to back.
-// Device form: d_off / d_out_off, the caller's own, are used where they lie).  Returns with st drained.
+// Device form: d_off / d_out_off, the caller's own, are used where they lie; the selectors and the work list are carved).
+// The frame is run_group (dq_runtime.h).  Returns with st drained.
 inline int huff_group(DeviceCtx &c, hipStream_t st, int dev, const HuffIo &io, const int64_t *rel, const int64_t *out_rel,
                       const int64_t *d_off_in, const int64_t *d_out_off_in, int32_t cnt)
 {
@@ -467,74 +468,42 @@ inline int huff_group(DeviceCtx &c, hipStream_t st, int dev, const HuffIo &io, c
     WorkLists<1> work;                                          // every non-empty block, longest first
     build_work_lists(work, cnt, [&](int32_t j) { return rel[j + 1] > rel[j] ? 0 : -1; }, [&](int32_t j) { return rel[j + 1] - rel[j]; });
     const int listed = work.class_count[0];
-    std::vector<int64_t> slots;                                 // host form: the device copy's slots
-    if (io.host) {
-        slots.resize((size_t)cnt + 1);
-        slots[0] = 0;
-        for (int32_t j = 0; j < cnt; ++j) slots[(size_t)j + 1] = slots[(size_t)j] + huff_bound(rel[j + 1] - rel[j]);
-    }
-    const size_t out_bytes = io.host ? (size_t)slots[(size_t)cnt] : 0;
-    const size_t b_syms = io.host ? align_up(2 * ((size_t)bytes + (size_t)cnt)) : 0, b_word = io.host ? align_up((size_t)cnt * sizeof(int32_t)) : 0,
-                 b_in_use = io.host ? align_up((size_t)cnt * 8 * sizeof(uint32_t)) : 0,
-                 b_off = io.host ? align_up(((size_t)cnt + 1) * sizeof(int64_t)) : 0, b_out = io.host ? align_up(out_bytes + 8) : 0,
-                 b_sel = huff_sel_bytes(bytes, cnt), b_work = many_ctl_bytes(listed);
-    DQ_TRY(ensure_ws(c, b_syms + 4 * b_word + b_in_use + 2 * b_off + b_out + b_sel + b_work));
-    char *at = c.ws;
-    auto carve = [&](size_t b) { char *p = at; at += b; return p; };
-    uint16_t *d_sy = reinterpret_cast<uint16_t *>(carve(b_syms));
-    int32_t *d_ns = reinterpret_cast<int32_t *>(carve(b_word));
-    uint32_t *d_crc = reinterpret_cast<uint32_t *>(carve(b_word));
-    int32_t *d_org = reinterpret_cast<int32_t *>(carve(b_word));
-    int32_t *d_nb = reinterpret_cast<int32_t *>(carve(b_word));
-    uint32_t *d_iu = reinterpret_cast<uint32_t *>(carve(b_in_use));
-    int64_t *d_off = reinterpret_cast<int64_t *>(carve(b_off));
-    int64_t *d_slots = reinterpret_cast<int64_t *>(carve(b_off));
-    uint8_t *d_bits = reinterpret_cast<uint8_t *>(carve(b_out));
-    uint8_t *d_sel = reinterpret_cast<uint8_t *>(carve(b_sel));
-    char *d_work = carve(b_work);
-    uint32_t *d_claim = reinterpret_cast<uint32_t *>(d_work);
-    int32_t *d_order = reinterpret_cast<int32_t *>(d_work + kManyCounterBytes);
-    int32_t *d_nbits = io.host ? d_nb : io.nbits;
+    std::vector<int64_t> slots(io.host ? (size_t)cnt + 1 : 0, 0);                           // host form: the device copy's slots
+    for (size_t j = 0; j + 1 < slots.size(); ++j) slots[j + 1] = slots[j] + huff_bound(rel[j + 1] - rel[j]);
+    const size_t out_bytes = io.host ? (size_t)slots.back() : 0;
+    struct { SymAreas sy; int32_t *origins; int64_t *off; BitAreas bi; char *work; } a;
+    DQ_TRY(carve_ws(c, [&](Carver &cv) {
+        a = {SymAreas(cv, io.host, bytes, cnt), cv.take<int32_t>(io.host ? word_area_bytes(cnt) : 0),
+             cv.take<int64_t>(io.host ? offset_area_bytes(cnt) : 0), BitAreas(cv, io.host, bytes, cnt, out_bytes), cv.take<char>(many_ctl_bytes(listed))};
+    }));
+    int32_t *d_nbits = io.host ? a.bi.nbits : io.nbits;
     std::vector<uint8_t> back(out_bytes);
-    auto run = [&]() -> int {
-        HIP_TRY(hipMemsetAsync(d_work, 0, kManyCounterBytes, st));
-        HIP_TRY(hipMemsetAsync(d_nbits, 0, (size_t)cnt * sizeof(int32_t), st));              // what an empty block keeps
-        if (io.host) {
-            HIP_TRY(hipMemcpyAsync(d_sy, io.syms, 2 * ((size_t)bytes + (size_t)cnt), hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(d_ns, io.nsyms, (size_t)cnt * sizeof(int32_t), hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(d_crc, io.crcs, (size_t)cnt * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(d_org, io.origins, (size_t)cnt * sizeof(int32_t), hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(d_iu, io.in_use, (size_t)cnt * 8 * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(d_off, rel, ((size_t)cnt + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(d_slots, slots.data(), ((size_t)cnt + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-        }
-        if (listed > 0) {
-            HIP_TRY(hipMemcpyAsync(d_order, work.order.data(), (size_t)listed * sizeof(int32_t), hipMemcpyHostToDevice, st));
-            if (io.host)
-                DQ_TRY(launch_huff(c, st, dev, d_sy, d_ns, d_iu, d_off, d_order, listed, d_claim, d_crc, d_org, d_slots, d_bits, d_nb, d_sel, bytes));
-            else
-                DQ_TRY(launch_huff(c, st, dev, io.syms, io.nsyms, io.in_use, d_off_in, d_order, listed, d_claim, io.crcs, io.origins,
-                                   d_out_off_in, io.out, io.nbits, d_sel, bytes));
-        }
-        // (one checked step: a failure must not leave a copy into the caller's arrays in flight behind the return)
-        hipError_t e = hipSuccess;
-        auto keep = [&](hipError_t x) { if (e == hipSuccess) e = x; };
-        if (io.host) {
-            if (out_bytes) keep(hipMemcpyAsync(back.data(), d_bits, out_bytes, hipMemcpyDeviceToHost, st));
-            keep(hipMemcpyAsync(io.nbits, d_nb, (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        }
-        keep(hipStreamSynchronize(st));
-        HIP_TRY(e);
-        return flush_profile(c);
+    auto enqueue = [&]() -> int {
+        HIP_TRY(hipMemsetAsync(d_nbits, 0, word_area_bytes(cnt), st));                       // what an empty block keeps
+        if (!io.host)
+            return launch_huff(c, st, dev, io.syms, io.nsyms, io.in_use, d_off_in, work_order(a.work), listed, a.work, io.crcs, io.origins,
+                               d_out_off_in, io.out, io.nbits, a.bi.sel, bytes);
+        HIP_TRY(hipMemcpyAsync(a.sy.syms, io.syms, sym_area_bytes(bytes, cnt), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(a.sy.nsyms, io.nsyms, word_area_bytes(cnt), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(a.sy.in_use, io.in_use, in_use_area_bytes(cnt), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(a.bi.crcs, io.crcs, word_area_bytes(cnt), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(a.origins, io.origins, word_area_bytes(cnt), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(a.off, rel, offset_area_bytes(cnt), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(a.bi.slots, slots.data(), offset_area_bytes(cnt), hipMemcpyHostToDevice, st));
+        return launch_huff(c, st, dev, a.sy.syms, a.sy.nsyms, a.sy.in_use, a.off, work_order(a.work), listed, a.work, a.bi.crcs, a.origins,
+                           a.bi.slots, a.bi.bits, a.bi.nbits, a.bi.sel, bytes);
     };
-    const int rc = run();
-    if (rc != DQ_OK) { drop_pending(c, st); return rc; }
-    if (io.host)
-        for (int32_t j = 0; j < cnt; ++j) {
-            const int64_t nb = io.nbits[j], have = slots[(size_t)j + 1] - slots[(size_t)j];
-            if (nb < -1 || (nb + 7) / 8 > have) return fail(DQ_ERR_HIP, "coding of a block failed");
-            if (nb > 0) memcpy(io.out + out_rel[j], back.data() + slots[(size_t)j], (size_t)((nb + 7) / 8));
-        }
+    auto read_back = [&](FirstError &keep) {
+        if (!io.host) return;
+        if (out_bytes) keep(hipMemcpyAsync(back.data(), a.bi.bits, out_bytes, hipMemcpyDeviceToHost, st));
+        keep(hipMemcpyAsync(io.nbits, a.bi.nbits, word_area_bytes(cnt), hipMemcpyDeviceToHost, st));
+    };
+    DQ_TRY(run_group(c, st, a.work, work.order, enqueue, read_back));
+    for (int32_t j = 0; io.host && j < cnt; ++j) {
+        const int64_t nb = io.nbits[j], have = slots[(size_t)j + 1] - slots[(size_t)j];
+        if (nb < -1 || (nb + 7) / 8 > have) return fail(DQ_ERR_HIP, "coding of a block failed");
+        if (nb > 0) memcpy(io.out + out_rel[j], back.data() + slots[(size_t)j], (size_t)((nb + 7) / 8));
+    }
     return DQ_OK;
 }
 
@@ -584,9 +553,7 @@ int huff_many_host(const uint16_t *syms, const int32_t *nsyms, const uint32_t *i
                           HuffIo{true, syms + offsets[i] + i, nsyms + i, in_use + 8 * (size_t)i, crcs + i, origins + i, out + out_offsets[i], nbits + i},
                           rel.data(), out_rel.data(), nullptr, nullptr, cnt);
     };
-    return walk_runs(count, kManyChunkTexts, [&](int32_t j) { return offsets[j + 1] - offsets[j] <= kManyChunkBytes; },
-                     [&](int32_t i, int32_t e) { return offsets[e + 1] - offsets[i] <= kManyChunkBytes; },
-                     [&](int32_t i) { return group(i, i + 1); }, group);
+    return walk_block_chunks(offsets, count, group);
 }
 
 // Device buffers in / out: one group, whatever its size (a work list and the selectors' workspace are carved).
@@ -603,9 +570,9 @@ int huff_many_dev(const void *d_syms, const void *d_nsyms, const void *d_in_use,
     DeviceCtx &c = *lease.c;
     DQ_TRY(init_ctx(c, dev));
     hipStream_t st = stream ? (hipStream_t)stream : c.stream;
-    std::vector<int64_t> off((size_t)count + 1), out_off((size_t)count + 1);
-    HIP_TRY(hipMemcpyAsync(off.data(), d_offsets, off.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(out_off.data(), d_out_offsets, out_off.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    std::vector<int64_t> off, out_off;
+    DQ_TRY(copy_many_offsets(d_offsets, count, st, off));
+    DQ_TRY(copy_many_offsets(d_out_offsets, count, st, out_off));
     HIP_TRY(hipStreamSynchronize(st));
     DQ_TRY(check_huff_offsets(off.data(), out_off.data(), count));
     return huff_group(c, st, dev,

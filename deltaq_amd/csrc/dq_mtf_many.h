@@ -36,6 +36,8 @@
 // every block forced into one class and then the other; the long class is faster from 16 KiB on, for text-like last columns
 // and for random bytes alike, and slower at 8 KiB and below: the longest swept length below the crossing).  kMtfSegment and
 // kMtfWaves are UNMEASURED starting values (docs/ROUNDS.md, round 25).  dq_bwt_many.h includes this file at its top.
+// The host side: mtf_group is the shared group frame (run_group, dq_runtime.h) around its areas (SymAreas: dq_block_groups.h), its
+// uploads and launch_mtf, and the host form's validation and copy-out; bwt_group (dq_bwt_many.h) calls launch_mtf too.
 #pragma once
 
 namespace dq {
@@ -44,7 +46,7 @@ constexpr int kMtfShortMax = 8192;        // longest block of the short class (o
 constexpr int kMtfSegment = 2048;         // bytes of a block a wave codes per super-tile
 constexpr int kMtfWaves = 8;              // waves of a workgroup of the long class (the short class: 1)
 constexpr int kMtfStage = kMtfSegment + 32;   // symbols a segment can yield: its bytes, and the <= 30 digits of a run that entered it
-constexpr int64_t kMtfMaxN = 1ll << 30;   // (kBwtMaxN: the blocks dq_bwt_hip_many accepts, no more)
+constexpr int64_t kMtfMaxN = kBlockMaxN;  // (kBwtMaxN: the blocks dq_bwt_hip_many accepts, no more)
 static_assert(kMtfSegment % kWave == 0 && kMtfSegment >= kWave, "whole tiles of a wave");
 static_assert(kMtfWaves >= 2 && kMtfWaves * kWave <= 1024, "a workgroup");
 
@@ -229,119 +231,74 @@ namespace {
 inline int64_t mtf_short_max() { return flags().mtf_short_max.value_or(kMtfShortMax); }
 
 // The launches of a set of blocks, one per class that has any: `d_short` / `d_long` are the classes' work lists on the
-// device (non-empty blocks, longest first), d_claim two zeroed words 16 apart.  Enqueues only.
+// device (non-empty blocks, longest first), d_work the group's zeroed counter block: each class has its own claim word
+// there.  Enqueues only.
 inline int launch_mtf(DeviceCtx &c, hipStream_t st, int dev, const uint8_t *d_last, const int64_t *d_off, const int32_t *d_short,
-                      int n_short, const int32_t *d_long, int n_long, uint32_t *d_claim, int64_t bytes, uint16_t *d_syms,
-                      int32_t *d_nsyms, uint32_t *d_in_use)
+                      int n_short, const int32_t *d_long, int n_long, char *d_work, int64_t bytes, const SymAreas &out)
 {
     Launcher L{c, st, g_prof_on.load()};
     if (n_long > 0) {
         const int grid = std::min(n_long, resident_groups(&c.mtf_many_groups[1], (const void *)mtf_many_kernel<kMtfWaves>, kMtfWaves * kWave, dev));
         LAUNCH(L, DQ_K_SMALL_MANY, n_long, bytes * 3,
                hipLaunchKernelGGL((mtf_many_kernel<kMtfWaves>), dim3((unsigned)grid), dim3(kMtfWaves * kWave), 0, st, d_last, d_off,
-                                  d_long, n_long, d_claim + 16, d_syms, d_nsyms, d_in_use));
+                                  d_long, n_long, counter_word(d_work, kMtfLongClaimWord), out.syms, out.nsyms, out.in_use));
     }
     if (n_short > 0) {
         const int grid = std::min(n_short, resident_groups(&c.mtf_many_groups[0], (const void *)mtf_many_kernel<1>, kWave, dev));
         LAUNCH(L, DQ_K_SMALL_MANY, n_short, bytes * 3,
                hipLaunchKernelGGL((mtf_many_kernel<1>), dim3((unsigned)grid), dim3(kWave), 0, st, d_last, d_off, d_short, n_short,
-                                  d_claim, d_syms, d_nsyms, d_in_use));
+                                  counter_word(d_work, kMtfShortClaimWord), out.syms, out.nsyms, out.in_use));
     }
     return DQ_OK;
 }
 
-// what a group's pointers are: host buffers (copied in and out) or device buffers (used where they lie)
-struct MtfIo {
-    bool host;
-    const uint8_t *last;
-    uint16_t *syms;
-    int32_t *nsyms;
-    uint32_t *in_use;
-};
-
-// device memory of a group of `bytes` block bytes in `cnt` blocks, `listed` of them non-empty (each area rounded up to 256)
-struct MtfAreas {
-    size_t last, syms, nsyms, in_use, off, work;
-    MtfAreas(bool host, int64_t bytes, int32_t cnt, int listed)
-        : last(host ? align_up((size_t)bytes + 64) : 0), syms(host ? align_up(2 * ((size_t)bytes + (size_t)cnt)) : 0),
-          nsyms(host ? align_up((size_t)cnt * sizeof(int32_t)) : 0), in_use(host ? align_up((size_t)cnt * 8 * sizeof(uint32_t)) : 0),
-          off(host ? align_up(((size_t)cnt + 1) * sizeof(int64_t)) : 0), work(many_ctl_bytes(listed)) {}
-    size_t total() const { return last + syms + nsyms + in_use + off + work; }
-};
-
-// One group: blocks [0, cnt) at io's pointers, rel their offsets relative to the first (the device form: d_off, the
-// caller's own, is used where it lies).  Returns with st drained.
-inline int mtf_group(DeviceCtx &c, hipStream_t st, int dev, const MtfIo &io, const int64_t *rel, const int64_t *d_off_in, int32_t cnt)
+// One group: blocks [0, cnt) at `last` with their results to `out` -- host buffers (copied in and out) or device buffers
+// (used where they lie, d_off_in the caller's offsets; nothing but the work list is carved) --, rel their offsets relative
+// to the first.  The frame is run_group (dq_runtime.h).  Returns with st drained.
+inline int mtf_group(DeviceCtx &c, hipStream_t st, int dev, bool host, const uint8_t *last, const SymAreas &out, const int64_t *rel,
+                     const int64_t *d_off_in, int32_t cnt)
 {
     const int64_t bytes = rel[cnt], short_max = mtf_short_max();
     WorkLists<2> work;                                          // the short class, the long class: each longest first
     build_work_lists(work, cnt, [&](int32_t j) { return rel[j + 1] == rel[j] ? -1 : rel[j + 1] - rel[j] <= short_max ? 0 : 1; },
                      [&](int32_t j) { return rel[j + 1] - rel[j]; });
-    const int listed = work.class_count[0] + work.class_count[1];
-    const MtfAreas a(io.host, bytes, cnt, listed);
-    DQ_TRY(ensure_ws(c, a.total()));
-    char *at = c.ws;
-    auto carve = [&](size_t b) { char *p = at; at += b; return p; };
-    uint8_t *d_blk = reinterpret_cast<uint8_t *>(carve(a.last));
-    uint16_t *d_sy = reinterpret_cast<uint16_t *>(carve(a.syms));
-    int32_t *d_ns = reinterpret_cast<int32_t *>(carve(a.nsyms));
-    uint32_t *d_iu = reinterpret_cast<uint32_t *>(carve(a.in_use));
-    int64_t *d_off = reinterpret_cast<int64_t *>(carve(a.off));
-    char *d_work = carve(a.work);
-    uint32_t *d_claim = reinterpret_cast<uint32_t *>(d_work);
-    int32_t *d_order = reinterpret_cast<int32_t *>(d_work + kManyCounterBytes);
-    const uint8_t *d_last = io.host ? d_blk : io.last;
-    uint16_t *d_syms = io.host ? d_sy : io.syms;
-    int32_t *d_nsyms = io.host ? d_ns : io.nsyms;
-    uint32_t *d_in_use = io.host ? d_iu : io.in_use;
-    const int64_t *d_offsets = io.host ? d_off : d_off_in;
+    struct { uint8_t *last; SymAreas sy; int64_t *off; char *work; } a;
+    DQ_TRY(carve_ws(c, [&](Carver &cv) {
+        a = {cv.take<uint8_t>(host ? (size_t)bytes + 64 : 0), SymAreas(cv, host, bytes, cnt), cv.take<int64_t>(host ? offset_area_bytes(cnt) : 0),
+             cv.take<char>(many_ctl_bytes((int64_t)work.order.size()))};
+    }));
+    const SymAreas &d = host ? a.sy : out;
     // (the host form's symbols come back whole and are handed on block by block: slots behind a block's written symbols
     // in the caller's array are not written)
-    std::vector<uint16_t> back(io.host ? (size_t)bytes + (size_t)cnt : 0);
-    auto run = [&]() -> int {
-        HIP_TRY(hipMemsetAsync(d_work, 0, kManyCounterBytes, st));
-        HIP_TRY(hipMemsetAsync(d_nsyms, 0, (size_t)cnt * sizeof(int32_t), st));              // what an empty block keeps
-        HIP_TRY(hipMemsetAsync(d_in_use, 0, (size_t)cnt * 8 * sizeof(uint32_t), st));
-        if (io.host) {
-            HIP_TRY(hipMemcpyAsync(d_blk, io.last, (size_t)bytes, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(d_off, rel, ((size_t)cnt + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    std::vector<uint16_t> back(host ? sym_area_bytes(bytes, cnt) / sizeof(uint16_t) : 0);
+    auto enqueue = [&]() -> int {
+        HIP_TRY(hipMemsetAsync(d.nsyms, 0, word_area_bytes(cnt), st));                       // what an empty block keeps
+        HIP_TRY(hipMemsetAsync(d.in_use, 0, in_use_area_bytes(cnt), st));
+        if (host) {
+            HIP_TRY(hipMemcpyAsync(a.last, last, (size_t)bytes, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(a.off, rel, offset_area_bytes(cnt), hipMemcpyHostToDevice, st));
         }
-        if (listed > 0) {
-            HIP_TRY(hipMemcpyAsync(d_order, work.order.data(), (size_t)listed * sizeof(int32_t), hipMemcpyHostToDevice, st));
-            DQ_TRY(launch_mtf(c, st, dev, d_last, d_offsets, d_order, work.class_count[0], d_order + work.class_count[0],
-                              work.class_count[1], d_claim, bytes, d_syms, d_nsyms, d_in_use));
-        }
-        // (one checked step: a failure must not leave a copy into the caller's arrays in flight behind the return)
-        hipError_t e = hipSuccess;
-        auto keep = [&](hipError_t x) { if (e == hipSuccess) e = x; };
-        if (io.host) {
-            keep(hipMemcpyAsync(back.data(), d_sy, back.size() * sizeof(uint16_t), hipMemcpyDeviceToHost, st));
-            keep(hipMemcpyAsync(io.nsyms, d_ns, (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-            keep(hipMemcpyAsync(io.in_use, d_iu, (size_t)cnt * 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        }
-        keep(hipStreamSynchronize(st));
-        HIP_TRY(e);
-        return flush_profile(c);
+        const int32_t *d_order = work_order(a.work);
+        return launch_mtf(c, st, dev, host ? a.last : last, host ? a.off : d_off_in, d_order, work.class_count[0],
+                          d_order + work.class_count[0], work.class_count[1], a.work, bytes, d);
     };
-    const int rc = run();
-    if (rc != DQ_OK) { drop_pending(c, st); return rc; }
-    if (io.host)
-        for (int32_t j = 0; j < cnt; ++j) {
-            const int64_t n = rel[j + 1] - rel[j], m = io.nsyms[j];
-            if (m < (n > 0 ? 1 : 0) || m > (n > 0 ? n + 1 : 0)) return fail(DQ_ERR_HIP, "move-to-front of a block failed");
-            if (m > 0) memcpy(io.syms + rel[j] + j, back.data() + rel[j] + j, (size_t)m * sizeof(uint16_t));
-        }
+    auto read_back = [&](FirstError &keep) {
+        if (!host) return;
+        keep(hipMemcpyAsync(back.data(), d.syms, sym_area_bytes(bytes, cnt), hipMemcpyDeviceToHost, st));
+        keep(hipMemcpyAsync(out.nsyms, d.nsyms, word_area_bytes(cnt), hipMemcpyDeviceToHost, st));
+        keep(hipMemcpyAsync(out.in_use, d.in_use, in_use_area_bytes(cnt), hipMemcpyDeviceToHost, st));
+    };
+    DQ_TRY(run_group(c, st, a.work, work.order, enqueue, read_back));
+    for (int32_t j = 0; host && j < cnt; ++j) {
+        const int64_t n = rel[j + 1] - rel[j], m = out.nsyms[j];
+        if (m < (n > 0 ? 1 : 0) || m > (n > 0 ? n + 1 : 0)) return fail(DQ_ERR_HIP, "move-to-front of a block failed");
+        if (m > 0) memcpy(out.syms + rel[j] + j, back.data() + rel[j] + j, (size_t)m * sizeof(uint16_t));
+    }
     return DQ_OK;
 }
 
-// no block beyond what dq_bwt_hip_many accepts
-inline int check_mtf_lengths(const int64_t *off, int32_t count)
-{
-    for (int32_t j = 0; j < count; ++j)
-        if (off[j + 1] - off[j] >= kMtfMaxN)
-            return fail(DQ_ERR_TOO_LARGE, "a block has 2^30 bytes or more: more than dq_bwt_hip_many transforms");
-    return DQ_OK;
-}
+// check_block_lengths' message here: no block beyond what dq_bwt_hip_many accepts
+constexpr const char *kMtfTooLong = "a block has 2^30 bytes or more: more than dq_bwt_hip_many transforms";
 
 }  // namespace
 
@@ -354,7 +311,7 @@ int mtf_many_host(const uint8_t *last, const int64_t *offsets, int32_t count, ui
     if (count == 0) return DQ_OK;
     if (!last || !offsets || !syms || !nsyms || !in_use) return fail(DQ_ERR_BAD_ARGS, "null buffer");
     DQ_TRY(check_many_offsets(offsets, count));
-    DQ_TRY(check_mtf_lengths(offsets, count));
+    DQ_TRY(check_block_lengths(offsets, count, kMtfTooLong));
     int dev = 0;
     DQ_TRY(resolve_device(device, &dev));
     std::fill(nsyms, nsyms + count, 0);                         // (what an empty block keeps)
@@ -368,12 +325,10 @@ int mtf_many_host(const uint8_t *last, const int64_t *offsets, int32_t count, ui
         SlotLease lease(dev, 0);
         DeviceCtx &c = *lease.c;
         DQ_TRY(init_ctx(c, dev));
-        return mtf_group(c, c.stream, dev, MtfIo{true, last + offsets[i], syms + offsets[i] + i, nsyms + i, in_use + 8 * (size_t)i},
-                         rel.data(), nullptr, cnt);
+        return mtf_group(c, c.stream, dev, true, last + offsets[i], SymAreas{syms + offsets[i] + i, nsyms + i, in_use + 8 * (size_t)i}, rel.data(),
+                         nullptr, cnt);
     };
-    return walk_runs(count, kManyChunkTexts, [&](int32_t j) { return offsets[j + 1] - offsets[j] <= kManyChunkBytes; },
-                     [&](int32_t i, int32_t e) { return offsets[e + 1] - offsets[i] <= kManyChunkBytes; },
-                     [&](int32_t i) { return group(i, i + 1); }, group);
+    return walk_block_chunks(offsets, count, group);
 }
 
 // Device buffers in / out: one group, whatever its size (nothing but a work list is carved).
@@ -391,9 +346,9 @@ int mtf_many_dev(const void *d_last, const void *d_offsets, int32_t count, void 
     hipStream_t st = stream ? (hipStream_t)stream : c.stream;
     std::vector<int64_t> off;
     DQ_TRY(fetch_many_offsets((const int64_t *)d_offsets, count, st, off));
-    DQ_TRY(check_mtf_lengths(off.data(), count));
-    return mtf_group(c, st, dev, MtfIo{false, (const uint8_t *)d_last, (uint16_t *)d_syms, (int32_t *)d_nsyms, (uint32_t *)d_in_use},
-                     off.data(), (const int64_t *)d_offsets, count);
+    DQ_TRY(check_block_lengths(off.data(), count, kMtfTooLong));
+    return mtf_group(c, st, dev, false, (const uint8_t *)d_last, SymAreas{(uint16_t *)d_syms, (int32_t *)d_nsyms, (uint32_t *)d_in_use}, off.data(),
+                     (const int64_t *)d_offsets, count);
 }
 
 }  // namespace dq

@@ -36,6 +36,7 @@
 #include "dq_call_info.h"
 #include "dq_flags.h"
 #include "dq_work_lists.h"
+#include "dq_block_groups.h"
 
 namespace dq {
 
@@ -298,8 +299,19 @@ inline int flush_profile(DeviceCtx &c)
     } while (0)
 
 
-// ------------------------------------------------------------------ workspace carving
-inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
+// ------------------------------------------------------------------ workspace carving (align_up: dq_work_lists.h)
+// The two passes of a Carver (dq_block_groups.h) over the context's workspace: plan(cv) carves the caller's areas from cv,
+// first without a base -- its total is what the workspace is sized by --, then from the workspace itself.
+template <typename Plan>
+int carve_ws(DeviceCtx &c, Plan plan)
+{
+    Carver size;
+    plan(size);
+    DQ_TRY(ensure_ws(c, size.used()));
+    Carver cv(c.ws);
+    plan(cv);
+    return DQ_OK;
+}
 
 inline int bit_length(uint64_t x) { return x == 0 ? 1 : 64 - __builtin_clzll(x); }
 
@@ -336,6 +348,16 @@ inline int check_many_offsets(const int64_t *off, int32_t count)
     return DQ_OK;
 }
 
+// The host forms' walk of dq_mtf_hip_many and dq_huff_hip_many over blocks [0, count): chunks of whole blocks -- at most
+// kManyChunkBytes of block bytes and kManyChunkTexts blocks, group(i, e) each --, a block above a chunk alone.
+template <typename Group>
+int walk_block_chunks(const int64_t *offsets, int32_t count, Group group)
+{
+    return walk_runs(count, kManyChunkTexts, [&](int32_t j) { return offsets[j + 1] - offsets[j] <= kManyChunkBytes; },
+                     [&](int32_t i, int32_t e) { return offsets[e + 1] - offsets[i] <= kManyChunkBytes; },
+                     [&](int32_t i) { return group(i, i + 1); }, group);
+}
+
 // ------------------------------------------------------------------ the many-* calls' launches (the planning: dq_work_lists.h)
 // Workgroups of `kernel` the device holds at once, asked once per context (*cache: a word of DeviceCtx).  A wrong answer
 // costs time only: the kernels that claim their work from a list never wait for each other.
@@ -362,13 +384,28 @@ struct ClassRow {
 };
 
 // The device forms' first step: the offsets come to the host once, to plan the launches, and are checked before
-// anything is launched.
-inline int fetch_many_offsets(const int64_t *d_offsets, int32_t count, hipStream_t st, std::vector<int64_t> &off)
+// anything is launched.  copy_many_offsets: the copy alone, enqueued; a caller with two arrays waits once for both.
+inline int copy_many_offsets(const void *d_offsets, int32_t count, hipStream_t st, std::vector<int64_t> &off)
 {
     off.resize((size_t)count + 1);
     HIP_TRY(hipMemcpyAsync(off.data(), d_offsets, off.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    return DQ_OK;
+}
+inline int fetch_many_offsets(const int64_t *d_offsets, int32_t count, hipStream_t st, std::vector<int64_t> &off)
+{
+    DQ_TRY(copy_many_offsets(d_offsets, count, st, off));
     HIP_TRY(hipStreamSynchronize(st));
     return check_many_offsets(off.data(), count);
+}
+
+// No block of kBlockMaxN bytes or more: its doubling would leave 32-bit indices, so dq_bwt_hip_many takes none, and the
+// stages behind it take what it takes.  `what`: the caller's own words for it.
+constexpr int64_t kBlockMaxN = 1ll << 30;
+inline int check_block_lengths(const int64_t *off, int32_t count, const char *what)
+{
+    for (int32_t j = 0; j < count; ++j)
+        if (off[j + 1] - off[j] >= kBlockMaxN) return fail(DQ_ERR_TOO_LARGE, what);
+    return DQ_OK;
 }
 
 // Copy back, then wait, as one checked step: a failure must not leave a copy into the caller's array in flight behind
@@ -379,6 +416,38 @@ inline int copy_back_and_wait(void *dst, const void *d_src, size_t bytes, hipStr
     const hipError_t e2 = hipStreamSynchronize(st);
     HIP_TRY(e1 != hipSuccess ? e1 : e2);
     return DQ_OK;
+}
+
+// ... and the same rule for a step of several copies: the first error is kept, every call is still made.
+struct FirstError {
+    hipError_t e = hipSuccess;
+    void operator()(hipError_t x) { if (e == hipSuccess) e = x; }
+};
+
+// One group of a many-blocks call (dq_bwt_many.h, dq_mtf_many.h, dq_huff_many.h) on its stream.  d_work: the group's
+// many_ctl_bytes(order.size()) bytes, the counter block (dq_block_groups.h: CounterWord) and the work list behind it.
+//   1. the counter block is zeroed            2. `order` goes up behind it
+//   3. enqueue(): the group's own uploads and launches; it returns the library's codes and waits for nothing
+//   4. read_back(keep): the copies into the caller's arrays, each through keep(...); then the wait -- one checked step,
+//      the wait is made whatever failed, so no copy into a caller's array is in flight behind the return
+//   5. the launches' times are booked         6. on any failure the stream is drained and the pending events dropped.
+// Returns with st drained.
+template <typename Enqueue, typename ReadBack>
+int run_group(DeviceCtx &c, hipStream_t st, char *d_work, const std::vector<int32_t> &order, Enqueue enqueue, ReadBack read_back)
+{
+    const int rc = [&]() -> int {
+        HIP_TRY(hipMemsetAsync(d_work, 0, kManyCounterBytes, st));
+        if (!order.empty())
+            HIP_TRY(hipMemcpyAsync(work_order(d_work), order.data(), order.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        DQ_TRY(enqueue());
+        FirstError keep;
+        read_back(keep);
+        keep(hipStreamSynchronize(st));
+        HIP_TRY(keep.e);
+        return flush_profile(c);
+    }();
+    if (rc != DQ_OK) drop_pending(c, st);
+    return rc;
 }
 
 // ------------------------------------------------------------------ NUMA placement of a device's host threads
@@ -493,21 +562,42 @@ int sufsort_many_dev(const void *d_texts, const void *d_offsets, int32_t count, 
 // The Burrows-Wheeler transform of many blocks (dq_bwt_many.h, in dq_sorter_i32.hip): the bodies of dq_bwt_hip_many /
 // _many_dev.  They sort the doubled blocks through the launches above, so they add to t_many_info as those do (the
 // lengths there are the doubled ones); shared_out and large_by_default as sufsort_many_host's.
-// mtf (optional, the host form's): the blocks' symbol streams come back instead of `last` (which may then be null).
-struct MtfOut {                         // dq_mtf_hip_many's three arrays in its layout; slots behind a block's written symbols are undefined here
-    uint16_t *syms;
-    int32_t *nsyms;
-    uint32_t *in_use;
-};
-// huff (optional, the host form's; it overrides mtf): the blocks' bits come back instead, in dq_huff_hip_many's layout.
-struct HuffOut {
+// out: how far the blocks are taken on the device (dq_block_groups.h: BlockStage) and that stage's arrays, the host's.
+struct BwtBits {                        // BlockStage::Bits: dq_huff_hip_many's layout
     const uint32_t *crcs;               // the CRC every block's header carries
     const int64_t *slots;               // count + 1 slot offsets: 0 first, multiples of 8, every slot >= dq_huff_hip_bound of its block
     uint8_t *bits;
     int32_t *nbits;                     // -1: a refused block
 };
-int bwt_many_host(const uint8_t *blocks, const int64_t *offsets, int32_t count, uint8_t *last, int32_t *origins, int32_t device,
-                  int64_t *shared_out = nullptr, bool large_by_default = true, const MtfOut *mtf = nullptr, const HuffOut *huff = nullptr);
+struct BwtOut {
+    BlockStage stage;
+    uint8_t *last = nullptr;            // BlockStage::Last: dq_bwt_hip_many's own result
+    SymAreas syms;                      // BlockStage::Syms: dq_mtf_hip_many's three arrays in its layout; slots behind a block's written symbols are undefined here
+    BwtBits bits{};
+    BwtOut(uint8_t *o) : stage(BlockStage::Last), last(o) {}
+    BwtOut(SymAreas o) : stage(BlockStage::Syms), syms(o) {}
+    BwtOut(BwtBits o) : stage(BlockStage::Bits), bits(o) {}
+    bool complete() const               // no null among the stage's arrays
+    {
+        return stage == BlockStage::Bits ? bits.crcs && bits.slots && bits.bits && bits.nbits
+               : stage == BlockStage::Syms ? syms.syms && syms.nsyms && syms.in_use : last != nullptr;
+    }
+    BwtOut from(int64_t off, int32_t i) const      // the same arrays from block i on, which begins at byte `off`
+    {
+        if (stage == BlockStage::Last) return BwtOut(last + off);
+        if (stage == BlockStage::Syms) return BwtOut(SymAreas(syms.syms + off + i, syms.nsyms + i, syms.in_use + 8 * (size_t)i));
+        return BwtOut(BwtBits{bits.crcs + i, bits.slots + i, bits.bits + bits.slots[i], bits.nbits + i});
+    }
+    void clear(int32_t count) const     // what a block keeps that no group holds, an empty one: no symbols, nothing in use, no bits
+    {
+        if (stage == BlockStage::Bits) std::fill(bits.nbits, bits.nbits + count, 0);
+        if (stage != BlockStage::Syms) return;
+        std::fill(syms.nsyms, syms.nsyms + count, 0);
+        std::fill(syms.in_use, syms.in_use + 8 * (size_t)count, 0u);
+    }
+};
+int bwt_many_host(const uint8_t *blocks, const int64_t *offsets, int32_t count, const BwtOut &out, int32_t *origins, int32_t device,
+                  int64_t *shared_out = nullptr, bool large_by_default = true);
 int bwt_many_dev(const void *d_blocks, const void *d_offsets, int32_t count, void *d_last, void *d_origins, int32_t device,
                  void *stream);
 // kBwtManyOn true: the framed many-file diffs transform their blocks there (dq_diff.hip: diff_many_frame).

@@ -171,11 +171,8 @@ inline ManyPlan plan_many(const int64_t *off, int32_t count, bool large_by_defau
     return p;
 }
 
-// device memory of a plan's work lists and claim counters (carved from the leased slot's workspace)
-constexpr size_t kManyCounterBytes = 256;
-inline size_t many_ctl_bytes(int64_t texts) { return kManyCounterBytes + align_up((size_t)texts * sizeof(int32_t)); }
-
-// ... and of the medium launches' per-workgroup scratch blocks.  The launches of a plan follow each other on one stream,
+// device memory of a plan's work lists and claim counters (carved from the leased slot's workspace): many_ctl_bytes,
+// dq_block_groups.h; and of the medium launches' per-workgroup scratch blocks.  The launches of a plan follow each other on one stream,
 // so they share the area: the larger of the two grids' needs (0 without medium texts).
 inline size_t many_scratch_bytes(DeviceCtx &c, const ManyPlan &plan)
 {

@@ -11,6 +11,12 @@
 
 namespace dq {
 
+// Device areas are rounded up to kAreaAlign.  A work list lies on the device behind kManyCounterBytes of claim counters,
+// zeroed before every use: many_ctl_bytes(listed) for both.
+constexpr size_t kAreaAlign = 256, kManyCounterBytes = 256;
+inline size_t align_up(size_t x, size_t a = kAreaAlign) { return (x + a - 1) / a * a; }
+inline size_t many_ctl_bytes(int64_t listed) { return kManyCounterBytes + align_up((size_t)listed * sizeof(int32_t)); }
+
 // The work lists of K classes back to back, class_count[k] entries each: what the classes' launches claim from.
 template <int K>
 struct WorkLists {

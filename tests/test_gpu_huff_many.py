@@ -308,6 +308,32 @@ def test_framed_diffs_are_the_same_either_way(backend_lib, ldss, name):
             assert on_n > off_n > no_mtf_n > default_n and alone_n == default_n, [n for _, n in ways]
 
 
+def test_one_group_carries_all_three_stages_and_both_mtf_classes(backend_lib, ldss):
+    """Diff.CreateMany on the smallest of the framed sets with DQ_MTF_SHORT_MAX=64: its blocks are ONE group of bwt_group
+    (one chunk of blocks, none sorted singly) whose blocks fall into both move-to-front classes, so the one frame carries
+    the transform, both mtf launches and the coding launch.  The patches are the same byte for byte with the bits coming
+    from the device and with the symbols coming back (the last flag at 1), and they are Diff.CreateBytes' patches; the
+    three-stage way makes one launch more than the two-stage way, which makes two more than the last columns alone.
+    (A block of these sets is never empty -- a stream without bytes has no block -- so the empty blocks of a group are
+    test_gpu_bwt_many.py's and test_gpu_mtf_many.py's to cover.)"""
+    from deltaq_amd import Diff
+    sets = {name: make() for name, (_, make) in bwt_tests.FRAMED_SETS.items()}
+    name = min(sets, key=lambda k: sum(o.size + n.size for o, n in sets[k]))
+    env, pairs = {**bwt_tests.FRAMED_SETS[name][0], "DQ_MTF_SHORT_MAX": "64", "DQ_NO_BWT_MANY": "0"}, sets[name]
+    olds, news = [o for o, _ in pairs], [n for _, n in pairs]
+    ways = []
+    for way in ({"DQ_NO_MTF_MANY": "0", "DQ_NO_HUFF_MANY": "0"}, {"DQ_NO_MTF_MANY": "0", "DQ_NO_HUFF_MANY": "1"}, {"DQ_NO_MTF_MANY": "1"}):
+        with flags({**env, **way}), profiled(backend_lib) as prof:
+            patches = Diff.CreateMany(olds, news)
+        ways.append((patches, prof.count))
+    (three, three_n), (two, two_n), (one, one_n) = ways
+    assert three == two == one
+    for j, (old, new) in enumerate(pairs):
+        assert three[j] == Diff.CreateBytes(old, new), (name, j, old.size, new.size)
+    assert three_n > two_n, (three_n, two_n)
+    assert (three_n - two_n, two_n - one_n) == (1, 2), (name, three_n, two_n, one_n)     # one group; the long class and the short class
+
+
 def test_two_threads_through_the_framed_route(backend_lib, ldss, main_blocks):
     """HuffMany on one thread while Diff.CreateMany -- its phase 4 through the same kernel -- runs on another"""
     from deltaq_amd import Diff
