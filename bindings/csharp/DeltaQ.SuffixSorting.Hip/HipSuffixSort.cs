@@ -58,6 +58,16 @@ public sealed class HipSuffixSort : ISuffixSort
     internal static extern int dq_huff_hip_many_dev(IntPtr dSyms, IntPtr dNsyms, IntPtr dInUse, IntPtr dOffsets, int count, IntPtr dCrcs, IntPtr dOrigins, IntPtr dOutOffsets, IntPtr dOut, IntPtr dNbits, int device, IntPtr stream);
 
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern long dq_bz2_hip_bound(long n, int level, long span);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    private static extern unsafe int dq_bz2_hip_many(byte* src, long* offsets, int count, int level, long span, long* outOffsets, byte* output, long* outLen, int device);
+
+    // (declared for hosts that keep their buffers on the device: device pointers, a hipStream_t or zero)
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern int dq_bz2_hip_many_dev(IntPtr dSrc, IntPtr dOffsets, int count, int level, long span, IntPtr dOutOffsets, IntPtr dOut, IntPtr dOutLen, int device, IntPtr stream);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
     private static extern unsafe int dq_last_many_info(long* info, int count);
 
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
@@ -531,6 +541,82 @@ public sealed class HipSuffixSort : ISuffixSort
 
     /// <summary>dq_huff_hip_bound: bytes that always suffice for the bits of a block of n bytes; -1 outside 0 .. 900 000.</summary>
     public static long HuffBound(long n) => dq_huff_hip_bound(n);
+
+    /// <summary>
+    /// Complete bzip2 streams of many independent buffers in one native call (dq_bz2_hip_many): per buffer the .bz2
+    /// stream a bzip2 compressor of that level writes, with blocks that also end once they cover <paramref name="span"/>
+    /// input bytes (0: the library's 4 MiB, long.MaxValue: libbz2's cut by coded size alone).  The run-length stage, the
+    /// cut into blocks, the CRCs, the block coding and the stringing of the blocks all run on the device.  An empty
+    /// buffer gives the 14-byte empty stream.  The native library has no fallback for this call and neither has this
+    /// method.
+    /// </summary>
+    public unsafe byte[][] Bz2Many(IReadOnlyList<byte[]> buffers, int level = 9, long span = 0)
+    {
+        if (level < 1 || level > 9)
+        {
+            throw new ArgumentOutOfRangeException(nameof(level), "level must be 1 .. 9");
+        }
+
+        if (span < 0)
+        {
+            throw new ArgumentOutOfRangeException(nameof(span), "span must not be negative");
+        }
+
+        int count = buffers.Count;
+        var result = new byte[count][];
+        if (count == 0)
+        {
+            return result;
+        }
+
+        var offsets = new long[count + 1];
+        var outOffsets = new long[count + 1];
+        for (int j = 0; j < count; j++)
+        {
+            offsets[j + 1] = offsets[j] + buffers[j].Length;
+            outOffsets[j + 1] = outOffsets[j] + dq_bz2_hip_bound(buffers[j].Length, level, span);
+        }
+
+        if (offsets[count] > Array.MaxLength || outOffsets[count] > Array.MaxLength)
+        {
+            throw new ArgumentException("the buffers of one Bz2Many call must total less than 2^31 bytes of input and of slots");
+        }
+
+        // (at least one element each: the native side wants non-null pointers whenever there are buffers)
+        byte[] src = new byte[Math.Max(offsets[count], 1)];
+        for (int j = 0; j < count; j++)
+        {
+            buffers[j].CopyTo(src.AsSpan((int)offsets[j]));
+        }
+
+        byte[] output = new byte[outOffsets[count]];
+        long[] outLen = new long[count];
+        int rc;
+        fixed (byte* pSrc = src)
+        fixed (long* pOffsets = offsets)
+        fixed (long* pOutOffsets = outOffsets)
+        fixed (byte* pOut = output)
+        fixed (long* pOutLen = outLen)
+        {
+            rc = dq_bz2_hip_many(pSrc, pOffsets, count, level, span, pOutOffsets, pOut, pOutLen, _device);
+        }
+
+        if (rc != 0)
+        {
+            string msg = Marshal.PtrToStringAnsi(dq_last_error()) ?? string.Empty;
+            throw new InvalidOperationException($"dq_bz2_hip_many failed ({rc}): {msg}");
+        }
+
+        for (int j = 0; j < count; j++)
+        {
+            result[j] = output.AsSpan((int)outOffsets[j], (int)outLen[j]).ToArray();
+        }
+
+        return result;
+    }
+
+    /// <summary>dq_bz2_hip_bound: bytes that always suffice for the stream of a buffer of n bytes; -1 for bad arguments.</summary>
+    public static long Bz2Bound(long n, int level = 9, long span = 0) => dq_bz2_hip_bound(n, level, span);
 
     /// <summary>
     /// <c>LDSSChecker.Check(T, SA)</c> (test/DeltaQ.SuffixSorting.LibDivSufSort.Tests/LDSSChecker.cs:23-119) on the

@@ -480,6 +480,30 @@ int32_t dq_huff_hip_many_dev(const void *d_syms, const void *d_nsyms, const void
     }
 }
 
+int64_t dq_bz2_hip_bound(int64_t n, int32_t level, int64_t span) { return bz2_many_bound(n, level, span); }
+
+int32_t dq_bz2_hip_many(const uint8_t *src, const int64_t *offsets, int32_t count, int32_t level, int64_t span,
+                        const int64_t *out_offsets, uint8_t *out, int64_t *out_len, int32_t device)
+{
+    EnvScope scope;
+    try {
+        return bz2_many_host(src, offsets, count, level, span, out_offsets, out, out_len, device);
+    } catch (const std::bad_alloc &) {
+        return fail(DQ_ERR_OOM, "many: host allocation failed");
+    }
+}
+
+int32_t dq_bz2_hip_many_dev(const void *d_src, const void *d_offsets, int32_t count, int32_t level, int64_t span,
+                            const void *d_out_offsets, void *d_out, void *d_out_len, int32_t device, void *stream)
+{
+    EnvScope scope;
+    try {
+        return bz2_many_dev(d_src, d_offsets, count, level, span, d_out_offsets, d_out, d_out_len, device, stream);
+    } catch (const std::bad_alloc &) {
+        return fail(DQ_ERR_OOM, "many: host allocation failed");
+    }
+}
+
 int32_t dq_bsdiff_search_dev_i32(const void *d_old, int64_t n, const void *d_sa, const void *d_new, int64_t m,
                                  const int64_t *d_scans, int64_t scan0, int64_t count, int64_t cap, void *d_pos,
                                  void *d_len, int32_t device, void *stream)
@@ -740,7 +764,7 @@ void dq_sufsort_hip_release(void)
         std::lock_guard<std::mutex> bl(c0.batch_mu);
         std::lock_guard<std::mutex> dl(c0.diff_mu);
         bool any = c0.diff_dev || c0.diff_idx || c0.diff_pinned || c0.bslot_cap;
-        for (int k = 0; k <= kBwtSlot; ++k) {
+        for (int k = 0; k <= kBz2Slot; ++k) {
             std::lock_guard<std::mutex> lk(g_dev[d].slot[k].mu);       // (a first use of the slot may be publishing dev right now)
             any = any || g_dev[d].slot[k].dev >= 0;
         }
@@ -759,7 +783,7 @@ void dq_sufsort_hip_release(void)
         if (c0.diff_pinned) (void)hipHostFree(c0.diff_pinned);
         c0.diff_dev = nullptr; c0.diff_idx = nullptr; c0.diff_pinned = nullptr;
         c0.diff_dev_bytes = 0; c0.diff_idx_bytes = 0;
-        for (int k = 0; k <= kBwtSlot; ++k) {
+        for (int k = 0; k <= kBz2Slot; ++k) {
             DeviceCtx &c = g_dev[d].slot[k];
             std::lock_guard<std::mutex> lk(c.mu);
             if (c.ws) (void)hipFree(c.ws);

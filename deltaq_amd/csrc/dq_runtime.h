@@ -175,8 +175,11 @@ constexpr size_t kSmallIoBytes = kSmallTextArea + (size_t)kSmallMaxN * 8;
 // keeps its chunk in that context's workspace while the sorts inside it lease slots of their own, so it is never leased
 // (SlotLease) -- one transform call at a time per device holds its mutex, and takes it before any slot's.
 constexpr int kBwtSlot = kCtxSlots;
+// ... and one behind that to the stream calls of dq_bz2_hip_many* (dq_bz2_many.h), which keep their chunk there while the
+// block stages inside them take the transforms' context and slots of their own: its mutex is taken before any of those.
+constexpr int kBz2Slot = kCtxSlots + 1;
 struct DeviceState {
-    DeviceCtx slot[kCtxSlots + 1];
+    DeviceCtx slot[kCtxSlots + 2];
     std::atomic<unsigned> next{0};
 };
 inline DeviceState g_dev[kMaxDevices];
@@ -635,6 +638,14 @@ int huff_many_dev(const void *d_syms, const void *d_nsyms, const void *d_in_use,
 // off, whatever this says.  The rule is kBwtManyOn's, on the framed sets of tools/kbench/huff_many.py
 // (profiles/r26/huff_many.json); false for round 26 whatever is measured (docs/ROUNDS.md, round 26).
 constexpr bool kHuffManyOn = false;
+
+// Many buffers to complete bzip2 streams (dq_bz2_many.h, in dq_sorter_i32.hip): the bodies of dq_bz2_hip_bound,
+// dq_bz2_hip_many / _many_dev.  No record, no profile category of their own.
+int64_t bz2_many_bound(int64_t n, int32_t level, int64_t span);
+int bz2_many_host(const uint8_t *src, const int64_t *offsets, int32_t count, int32_t level, int64_t span, const int64_t *out_offsets,
+                  uint8_t *out, int64_t *out_len, int32_t device);
+int bz2_many_dev(const void *d_src, const void *d_offsets, int32_t count, int32_t level, int64_t span, const void *d_out_offsets, void *d_out,
+                 void *d_out_len, int32_t device, void *stream);
 
 // LDSSChecker.Check on the device (dq_sufcheck.hip): DQ_OK with the verdict (DQ_SUFCHECK_*) in *result, or an error
 template <typename IdxT>

@@ -69,6 +69,18 @@ def huff_bound(n: int) -> int:
     return int(_abi.load().dq_huff_hip_bound(int(n)))
 
 
+def bz2_bound(n: int, level: int = 9, span=None) -> int:
+    """dq_bz2_hip_bound: bytes that always suffice for the bzip2 stream of a buffer of n bytes (a multiple of 8; -1 for
+    n < 0, n >= 2^31, a level outside 1 .. 9 or a negative span).  span=None is the library's block span."""
+    return int(_abi.load().dq_bz2_hip_bound(int(n), int(level), 0 if span is None else int(span)))
+
+
+def unpack_bz2_many(out: np.ndarray, out_len: np.ndarray, out_off: np.ndarray) -> list:
+    """dq_bz2_hip_many's flat results as Bz2Many returns them: [the out_len[j] bytes of stream j]; stream j's slot begins
+    at out_off[j]."""
+    return [out[out_off[j]:out_off[j] + int(out_len[j])].tobytes() for j in range(len(out_off) - 1)]
+
+
 def huff_block_length(symbols: np.ndarray) -> int:
     """The bytes of the block a symbol stream of MtfMany stands for: a run's digits d at position p count (d + 1) << p,
     every other symbol but EOB counts 1."""
@@ -415,6 +427,76 @@ class HipSuffixSort:
                                                   crcs.data_ptr(), origins.data_ptr(), out_offsets.data_ptr(), op.data_ptr(),
                                                   nbits.data_ptr(), dev, stream))
         return nbits
+
+    # -- whole bzip2 streams of many buffers (the block stages above with everything around them) ------------------------
+    def Bz2Many(self, buffers, level: int = 9, span=None):
+        """Complete bzip2 streams of many independent buffers, each byte for byte what the library's host encoder writes
+        for that buffer: run-length pre-pass, cut into blocks, block CRCs, the three block stages and the bit-level
+        stringing of the blocks all on the device.  ``span`` is the number of input bytes a block covers at most
+        (``None``: the library's 4 MiB; ``2**63 - 1``: libbz2's cut by coded size alone).
+
+        ``Bz2Many([b0, b1, ...])`` -- bytes-like objects / numpy uint8 arrays, each shorter than 2^31 bytes -- returns a
+        list of ``bytes`` (``dq_bz2_hip_many``).  ``Bz2Many((src_tensor, offsets_tensor))`` -- a uint8 and an int64 torch
+        GPU tensor in ``SortMany``'s device layout -- returns ``(out_tensor, out_offsets_tensor, out_len_tensor)``: stream
+        j is ``out[out_offsets[j] : out_offsets[j] + out_len[j]]`` (``dq_bz2_hip_many_dev``, on the current torch stream).
+        """
+        if not 1 <= int(level) <= 9:
+            raise ValueError("level must be 1 .. 9")
+        sp = 0 if span is None else int(span)
+        if sp < 0:
+            raise ValueError("span must not be negative")
+        if isinstance(buffers, tuple) and len(buffers) == 2 and _is_torch_tensor(buffers[0]):
+            return self._bz2_many_device(buffers[0], buffers[1], int(level), sp)
+        arrs = [_as_text(b) for b in buffers]
+        if any(a.ndim != 1 for a in arrs):
+            raise TypeError("every buffer must be one-dimensional")
+        if any(a.size > INT_MAX for a in arrs):
+            raise ValueError("Bz2Many has 32-bit indices: every buffer must be shorter than 2^31 bytes")
+        count = len(arrs)
+        if count == 0:
+            return []
+        off = np.zeros(count + 1, dtype=np.int64)
+        np.cumsum([a.size for a in arrs], out=off[1:])
+        out_off = np.zeros(count + 1, dtype=np.int64)
+        np.cumsum([self._lib.dq_bz2_hip_bound(int(a.size), int(level), sp) for a in arrs], out=out_off[1:])
+        flat = np.concatenate(arrs) if int(off[-1]) else np.zeros(1, np.uint8)
+        out = np.empty(int(out_off[-1]), dtype=np.uint8)
+        out_len = np.empty(count, dtype=np.int64)
+        _abi.check(self._lib.dq_bz2_hip_many(flat.ctypes.data, off.ctypes.data, count, int(level), sp, out_off.ctypes.data,
+                                             out.ctypes.data, out_len.ctypes.data, self.device))
+        return unpack_bz2_many(out, out_len, out_off)
+
+    bz2_many = Bz2Many
+
+    def _bz2_many_device(self, src, offsets, level, span):
+        import torch
+
+        if not _is_torch_tensor(offsets):
+            raise TypeError("device buffers need a device offsets tensor")
+        if src.dtype != torch.uint8 or src.dim() != 1 or not src.is_contiguous():
+            raise TypeError("device buffers must be a contiguous 1-D uint8 tensor")
+        if offsets.dtype != torch.int64 or offsets.dim() != 1 or not offsets.is_contiguous() or offsets.numel() < 1:
+            raise TypeError("offsets must be a contiguous 1-D int64 tensor of count + 1 entries")
+        if not src.is_cuda or offsets.device != src.device:
+            raise TypeError("buffers and offsets must live on the same GPU")
+        count = offsets.numel() - 1
+        host_off = offsets.cpu().numpy()
+        bounds = [self._lib.dq_bz2_hip_bound(int(host_off[j + 1] - host_off[j]), level, span) for j in range(count)]
+        if any(b < 0 for b in bounds):
+            raise ValueError("offsets must not decrease, and every buffer must be shorter than 2^31 bytes")
+        host_out_off = np.zeros(count + 1, dtype=np.int64)
+        if count:
+            np.cumsum(bounds, out=host_out_off[1:])
+        out = torch.empty(max(int(host_out_off[-1]), 1), dtype=torch.uint8, device=src.device)
+        out_off = torch.from_numpy(host_out_off).to(src.device)
+        out_len = torch.zeros(count, dtype=torch.int64, device=src.device)
+        if count == 0:
+            return out, out_off, out_len
+        dev, stream = _device_and_stream(src)
+        sp = src if src.numel() else torch.zeros(1, dtype=torch.uint8, device=src.device)
+        _abi.check(self._lib.dq_bz2_hip_many_dev(sp.data_ptr(), offsets.data_ptr(), count, level, span, out_off.data_ptr(),
+                                                 out.data_ptr(), out_len.data_ptr(), dev, stream))
+        return out, out_off, out_len
 
     # -- LDSSChecker.Check(T, SA)   (test/DeltaQ.SuffixSorting.LibDivSufSort.Tests/LDSSChecker.cs:23-119) --------
     def Check(self, text, suffixes) -> int:

@@ -253,6 +253,64 @@ int32_t dq_huff_hip_many_dev(const void *d_syms, const void *d_nsyms, const void
                              const void *d_crcs, const void *d_origins, const void *d_out_offsets, void *d_out, void *d_nbits,
                              int32_t device, void *stream);
 
+/* ---- Many buffers to complete bzip2 streams on the device ---------------------------------------------------
+ * The three calls above take a block from bytes to bits; this one takes a BUFFER to a .bz2 STREAM: the first
+ * run-length stage, the cut into blocks, the block CRCs and the stringing together of blocks that end at arbitrary bit
+ * positions run on the device around them, and the blocks never leave it.
+ * Layout: as the other many-calls, buffers back to back, offsets[count + 1], offsets[0] == 0, never decreasing.  Stream j
+ * owns out[out_offsets[j] .. out_offsets[j + 1]); out_len[j] is its length in bytes.  Bytes of a slot behind out_len[j]
+ * are unspecified; nothing outside a stream's own slot is written.  level is 1 .. 9.  span is the number of input bytes
+ * a block covers at most: 0 means the library's bz2::kBlockSpan (4 MiB), any value >= 1 is taken as given, INT64_MAX is
+ * libbz2's cut by coded size alone.  An empty buffer yields the 14-byte empty stream ("BZh" + level, end magic, CRC 0).
+ * Definition: stream j is byte for byte bz2::bz2_compress (deltaq_amd/csrc/dq_bz2.h) of buffer j with that level and
+ * span.  In words, with block_max = level * 100000 - 19:
+ *   1. units: every maximal run of equal bytes is split greedily from its start into units of at most 255 bytes -- this
+ *      does not depend on where blocks end: a block always ends between two units.  A unit of length L < 4 is coded as
+ *      its L bytes, a unit of L >= 4 as 4 bytes and the byte L - 4.  Runs never continue across two buffers;
+ *   2. blocks: with E(i) the coded bytes of all units before the unit that starts at input position i, a block that
+ *      begins at unit start p takes units while E(i) - E(p) <= block_max - 5 and i - p < span; the first unit start that
+ *      fails either test begins the next block.  A block is never empty, never has more than block_max coded bytes, and
+ *      covers fewer than span + 255 input bytes;
+ *   3. block CRC: bzip2's CRC (polynomial 0x04c11db7, most significant bit first, initial value and final complement
+ *      0xffffffff) over the INPUT bytes the block covers; the combined CRC is rotl(combined, 1) ^ crc, in block order;
+ *   4. block bits: each block's coded bytes go through the definitions of dq_bwt_hip_many, dq_mtf_hip_many and
+ *      dq_huff_hip_many unchanged;
+ *   5. the stream: the 32 bits 'B' 'Z' 'h' '0' + level, every block's nbits bits in order with no padding in between,
+ *      the 48-bit end magic 0x177245385090, the 32-bit combined CRC, zero padding to a whole byte.
+ * dq_bz2_hip_bound(n, level, span): bytes that always suffice for a buffer of n bytes; a multiple of 8, never decreasing
+ * in n; -1 for n < 0, a bad level, span < 0 or n >= 2^31.  It is 16 for n == 0 and otherwise
+ *   16 + B * dq_huff_hip_bound(c),
+ *   B = ceil(n / min(span, ceil(4 (block_max - 4) / 5))),  c = min(block_max, floor(5 n / 4), floor(5 (span + 254) / 4)).
+ * Proof: x input bytes in whole units code to at most floor(5 x / 4) bytes (the worst unit is 4 bytes coded as 5).  A
+ * block that is not the last ended by span, so it covers at least span bytes, or because its coded bytes reached
+ * block_max - 4, so it covers at least ceil(4 (block_max - 4) / 5); the last block is not empty: at most B blocks.  No
+ * block has more coded bytes than block_max, than the whole buffer codes to, or than the fewer than span + 255 bytes it
+ * covers code to: at most c, and dq_huff_hip_bound never decreases, so each block's bits fit dq_huff_hip_bound(c) bytes.
+ * The stream is 32 + 80 bits around the blocks' bits: ceil(bits / 8) <= 14 + B * dq_huff_hip_bound(c).
+ * Errors, all before any device use in the host form: count < 0, a NULL pointer with count > 0, bad offsets, level
+ * outside 1 .. 9, span < 0, out_offsets[0] != 0, an out_offsets[j] that is no multiple of 8, a slot shorter than the
+ * bound -> DQ_ERR_BAD_ARGS; a buffer of 2^31 bytes or more -> DQ_ERR_TOO_LARGE.  count == 0 is a no-op.  There is no CPU
+ * fallback.  DQ_ERR_HIP ("bzip2 stream failed") after the wait for a block that comes back refused or empty from the
+ * coding stage, or a device-side consistency flag: the kernels range-test every index before it is an address.
+ *   dq_bz2_hip_many       host pointers.  The buffers travel in chunks of whole buffers, at most 64 MiB of input; a
+ *                         buffer above that travels alone.  Device memory per chunk of b bytes whose slots at the bound
+ *                         sum to S: b + S staged, 5 b / 4 coded bytes, 5 b / 2 of symbols, S of block slots, 0.13 b of
+ *                         tile and cell words, 112 bytes per possible block -- about 4.9 b + 2 S, 900 MiB for a full
+ *                         chunk at level 9 -- beside what dq_bwt_hip_many_dev takes for the coded bytes.  Waits per chunk:
+ *                         one for the block table, one at the end, and the block stages' own (two each, one more per
+ *                         64 MiB of doubled blocks in the transform).  The written bytes are handed on from a host copy
+ *                         of the chunk's slots.
+ *   dq_bz2_hip_many_dev   device pointers on `device`, d_offsets and d_out_offsets too (d_out_len: int64): the library
+ *                         fetches both once and checks them before it launches anything; work on `stream`, NULL = the
+ *                         library's; returns after the stream has drained.  Workspace: as the host form's per chunk
+ *                         without the staged b + S.  Four-byte stores where the word's address is 4-byte aligned.
+ * Neither has a record of its own, and the kernels are profiled under small_many_kernel's category. */
+int64_t dq_bz2_hip_bound(int64_t n, int32_t level, int64_t span);
+int32_t dq_bz2_hip_many(const uint8_t *src, const int64_t *offsets, int32_t count, int32_t level, int64_t span,
+                        const int64_t *out_offsets, uint8_t *out, int64_t *out_len, int32_t device);
+int32_t dq_bz2_hip_many_dev(const void *d_src, const void *d_offsets, int32_t count, int32_t level, int64_t span,
+                            const void *d_out_offsets, void *d_out, void *d_out_len, int32_t device, void *stream);
+
 /* ---- Diff.Create's match search on the device-resident suffix array ----------
  * Replaces, for a batch of scan positions, the reference's
  *   Search(I, oldData, newData[scan..], 0, oldData.Length, out pos)          src/DeltaQ.BsDiff/Diff.cs:267-298
