@@ -68,6 +68,13 @@ public sealed class HipSuffixSort : ISuffixSort
     internal static extern int dq_bz2_hip_many_dev(IntPtr dSrc, IntPtr dOffsets, int count, int level, long span, IntPtr dOutOffsets, IntPtr dOut, IntPtr dOutLen, int device, IntPtr stream);
 
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    private static extern unsafe int dq_unbz2_hip_many(byte* src, long* offsets, int count, long* outOffsets, byte* output, long* outLen, int* status, int device);
+
+    // (declared for hosts that keep their buffers on the device: device pointers, a hipStream_t or zero)
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern int dq_unbz2_hip_many_dev(IntPtr dSrc, IntPtr dOffsets, int count, IntPtr dOutOffsets, IntPtr dOut, IntPtr dOutLen, IntPtr dStatus, int device, IntPtr stream);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
     private static extern unsafe int dq_last_many_info(long* info, int count);
 
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
@@ -617,6 +624,80 @@ public sealed class HipSuffixSort : ISuffixSort
 
     /// <summary>dq_bz2_hip_bound: bytes that always suffice for the stream of a buffer of n bytes; -1 for bad arguments.</summary>
     public static long Bz2Bound(long n, int level = 9, long span = 0) => dq_bz2_hip_bound(n, level, span);
+
+    /// <summary>
+    /// Many bzip2 streams decoded in one native call (dq_unbz2_hip_many): per stream the verdict of a bzip2 reader
+    /// that may produce at most <paramref name="caps"/>[j] bytes -- 0 ok, -1 corrupt, -2 truncated, -3 too long -- in
+    /// <paramref name="status"/>, and the decoded bytes where the verdict is 0 (null otherwise).  A stream is untrusted
+    /// input: a malformed one is its own verdict, never an exception.  The native library has no fallback for this call
+    /// and neither has this method.
+    /// </summary>
+    public unsafe byte[]?[] Unbz2Many(IReadOnlyList<byte[]> streams, IReadOnlyList<int> caps, out int[] status)
+    {
+        int count = streams.Count;
+        if (caps.Count != count)
+        {
+            throw new ArgumentException("one capacity per stream", nameof(caps));
+        }
+
+        var result = new byte[]?[count];
+        status = new int[count];
+        if (count == 0)
+        {
+            return result;
+        }
+
+        var offsets = new long[count + 1];
+        var outOffsets = new long[count + 1];
+        for (int j = 0; j < count; j++)
+        {
+            if (caps[j] < 0)
+            {
+                throw new ArgumentOutOfRangeException(nameof(caps), "a capacity must not be negative");
+            }
+
+            offsets[j + 1] = offsets[j] + streams[j].Length;
+            outOffsets[j + 1] = outOffsets[j] + caps[j];
+        }
+
+        if (offsets[count] > Array.MaxLength || outOffsets[count] > Array.MaxLength)
+        {
+            throw new ArgumentException("the streams of one Unbz2Many call must total less than 2^31 bytes of input and of capacity");
+        }
+
+        // (at least one element each: the native side wants non-null pointers whenever there are streams)
+        byte[] src = new byte[Math.Max(offsets[count], 1)];
+        for (int j = 0; j < count; j++)
+        {
+            streams[j].CopyTo(src.AsSpan((int)offsets[j]));
+        }
+
+        byte[] output = new byte[Math.Max(outOffsets[count], 1)];
+        long[] outLen = new long[count];
+        int rc;
+        fixed (byte* pSrc = src)
+        fixed (long* pOffsets = offsets)
+        fixed (long* pOutOffsets = outOffsets)
+        fixed (byte* pOut = output)
+        fixed (long* pOutLen = outLen)
+        fixed (int* pStatus = status)
+        {
+            rc = dq_unbz2_hip_many(pSrc, pOffsets, count, pOutOffsets, pOut, pOutLen, pStatus, _device);
+        }
+
+        if (rc != 0)
+        {
+            string msg = Marshal.PtrToStringAnsi(dq_last_error()) ?? string.Empty;
+            throw new InvalidOperationException($"dq_unbz2_hip_many failed ({rc}): {msg}");
+        }
+
+        for (int j = 0; j < count; j++)
+        {
+            result[j] = status[j] == 0 ? output.AsSpan((int)outOffsets[j], (int)outLen[j]).ToArray() : null;
+        }
+
+        return result;
+    }
 
     /// <summary>
     /// <c>LDSSChecker.Check(T, SA)</c> (test/DeltaQ.SuffixSorting.LibDivSufSort.Tests/LDSSChecker.cs:23-119) on the

@@ -38,7 +38,11 @@ CATEGORY_ALIASES = {"mid_many_kernel": "small_many_kernel", "large_text_kernel":
                     "bz2_scan_max_kernel": "small_many_kernel", "bz2_sizes_kernel": "small_many_kernel",
                     "bz2_scan_sum_kernel": "small_many_kernel", "bz2_cut_kernel": "small_many_kernel",
                     "bz2_emit_kernel": "small_many_kernel", "bz2_crc_kernel": "small_many_kernel",
-                    "bz2_stream_scan_kernel": "small_many_kernel", "bz2_stitch_kernel": "small_many_kernel"}
+                    "bz2_stream_scan_kernel": "small_many_kernel", "bz2_stitch_kernel": "small_many_kernel",
+                    "unbz2_parse_kernel": "small_many_kernel", "unbz2_rank_kernel": "small_many_kernel",
+                    "unbz2_walk_kernel": "small_many_kernel", "unbz2_write_kernel": "small_many_kernel",
+                    "unbz2_unrle_kernel": "small_many_kernel", "unbz2_place_kernel": "small_many_kernel",
+                    "unbz2_verdict_kernel": "small_many_kernel"}
 MID_MAX_N = 65536         # kMidMaxN: longest text of the medium class of the many-texts launches
 LARGE_MAX_N = 4 << 20     # kLargeMaxN: longest text of their segmented sort (dq_large_many.h)
 
@@ -51,7 +55,7 @@ EXPORTS = (
     "dq_sufsort_hip_many_i32", "dq_sufsort_hip_many_dev_i32", "dq_last_many_info",
     "dq_bwt_hip_many", "dq_bwt_hip_many_dev", "dq_mtf_hip_many", "dq_mtf_hip_many_dev",
     "dq_huff_hip_bound", "dq_huff_hip_many", "dq_huff_hip_many_dev",
-    "dq_bz2_hip_bound", "dq_bz2_hip_many", "dq_bz2_hip_many_dev",
+    "dq_bz2_hip_bound", "dq_bz2_hip_many", "dq_bz2_hip_many_dev", "dq_unbz2_hip_many", "dq_unbz2_hip_many_dev",
     "dq_sufcheck_hip_i32", "dq_sufcheck_hip_i64", "dq_sufcheck_hip_dev_i32", "dq_sufcheck_hip_dev_i64",
     "dq_sufcheck_hip_many_i32", "dq_sufcheck_hip_many_dev_i32", "dq_last_check_many_info",
     "dq_bsdiff_search_dev_i32", "dq_bsdiff_search_dev_i64", "dq_bsdiff_search_i32", "dq_bsdiff_search_i64",
@@ -190,6 +194,10 @@ def load() -> ctypes.CDLL:
     L.dq_bz2_hip_many.argtypes = [vp, vp, i32, i32, i64, vp, vp, vp, i32]
     L.dq_bz2_hip_many_dev.restype = i32
     L.dq_bz2_hip_many_dev.argtypes = [vp, vp, i32, i32, i64, vp, vp, vp, i32, vp]
+    L.dq_unbz2_hip_many.restype = i32
+    L.dq_unbz2_hip_many.argtypes = [vp, vp, i32, vp, vp, vp, vp, i32]
+    L.dq_unbz2_hip_many_dev.restype = i32
+    L.dq_unbz2_hip_many_dev.argtypes = [vp, vp, i32, vp, vp, vp, vp, i32, vp]
     for name in ("dq_bsdiff_search_dev_i32", "dq_bsdiff_search_dev_i64"):
         getattr(L, name).restype = i32
         getattr(L, name).argtypes = [vp, i64, vp, vp, i64, vp, i64, i64, i64, vp, vp, i32, vp]

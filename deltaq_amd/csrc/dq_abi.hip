@@ -504,6 +504,28 @@ int32_t dq_bz2_hip_many_dev(const void *d_src, const void *d_offsets, int32_t co
     }
 }
 
+int32_t dq_unbz2_hip_many(const uint8_t *src, const int64_t *offsets, int32_t count, const int64_t *out_offsets,
+                          uint8_t *out, int64_t *out_len, int32_t *status, int32_t device)
+{
+    EnvScope scope;
+    try {
+        return unbz2_many_host(src, offsets, count, out_offsets, out, out_len, status, device);
+    } catch (const std::bad_alloc &) {
+        return fail(DQ_ERR_OOM, "many: host allocation failed");
+    }
+}
+
+int32_t dq_unbz2_hip_many_dev(const void *d_src, const void *d_offsets, int32_t count, const void *d_out_offsets,
+                              void *d_out, void *d_out_len, void *d_status, int32_t device, void *stream)
+{
+    EnvScope scope;
+    try {
+        return unbz2_many_dev(d_src, d_offsets, count, d_out_offsets, d_out, d_out_len, d_status, device, stream);
+    } catch (const std::bad_alloc &) {
+        return fail(DQ_ERR_OOM, "many: host allocation failed");
+    }
+}
+
 int32_t dq_bsdiff_search_dev_i32(const void *d_old, int64_t n, const void *d_sa, const void *d_new, int64_t m,
                                  const int64_t *d_scans, int64_t scan0, int64_t count, int64_t cap, void *d_pos,
                                  void *d_len, int32_t device, void *stream)
@@ -764,7 +786,7 @@ void dq_sufsort_hip_release(void)
         std::lock_guard<std::mutex> bl(c0.batch_mu);
         std::lock_guard<std::mutex> dl(c0.diff_mu);
         bool any = c0.diff_dev || c0.diff_idx || c0.diff_pinned || c0.bslot_cap;
-        for (int k = 0; k <= kBz2Slot; ++k) {
+        for (int k = 0; k <= kUnbz2Slot; ++k) {
             std::lock_guard<std::mutex> lk(g_dev[d].slot[k].mu);       // (a first use of the slot may be publishing dev right now)
             any = any || g_dev[d].slot[k].dev >= 0;
         }
@@ -783,7 +805,7 @@ void dq_sufsort_hip_release(void)
         if (c0.diff_pinned) (void)hipHostFree(c0.diff_pinned);
         c0.diff_dev = nullptr; c0.diff_idx = nullptr; c0.diff_pinned = nullptr;
         c0.diff_dev_bytes = 0; c0.diff_idx_bytes = 0;
-        for (int k = 0; k <= kBz2Slot; ++k) {
+        for (int k = 0; k <= kUnbz2Slot; ++k) {
             DeviceCtx &c = g_dev[d].slot[k];
             std::lock_guard<std::mutex> lk(c.mu);
             if (c.ws) (void)hipFree(c.ws);

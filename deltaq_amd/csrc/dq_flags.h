@@ -49,6 +49,7 @@ struct Flags {
     std::optional<int> no_mtf_many;         // DQ_NO_MTF_MANY: 0: where those blocks are transformed on the device, move-to-front and run coding follow there too (dq_mtf_many.h) and the symbol streams come back; 1: the last columns come back; unset: what kMtfManyOn says (dq_runtime.h)
     std::optional<int> no_huff_many;        // DQ_NO_HUFF_MANY: 0: where those blocks' move-to-front runs on the device, coding tables and bits follow there too (dq_huff_many.h) and the blocks' bits come back; 1: the symbol streams come back; unset: what kHuffManyOn says (dq_runtime.h)
     std::optional<int> mtf_short_max;       // DQ_MTF_SHORT_MAX: longest block of mtf_many_kernel's short class (one wave per workgroup), >= 0; unset: kMtfShortMax
+    std::optional<int> unbz2_one_start;     // DQ_UNBZ2_ONE_START: 1: the inverse transform of dq_unbz2_hip_many* starts its chase at row 0 and at the origin's row only, no further marks (dq_unbz2_many.h; what tools/kbench/unbz2_many.py compares the marks against)
     bool no_list_buffers = false;           // DQ_NO_LIST_BUFFERS: the workspace without the third list buffer
     bool text_copy = false;                 // DQ_TEXT_COPY: copy the text in front instead of in the first pass
     bool assume_doubled = false;            // DQ_ASSUME_DOUBLED: every even-length text is block + block
@@ -162,6 +163,7 @@ inline Flags read_flags()
     f.no_mtf_many = num("DQ_NO_MTF_MANY", 0, 1);
     f.no_huff_many = num("DQ_NO_HUFF_MANY", 0, 1);
     f.mtf_short_max = num("DQ_MTF_SHORT_MAX", 0);
+    f.unbz2_one_start = num("DQ_UNBZ2_ONE_START", 0, 1);
     f.no_list_buffers = on("DQ_NO_LIST_BUFFERS");
     f.text_copy = on("DQ_TEXT_COPY");
     f.assume_doubled = on("DQ_ASSUME_DOUBLED");

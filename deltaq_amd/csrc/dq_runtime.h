@@ -178,8 +178,10 @@ constexpr int kBwtSlot = kCtxSlots;
 // ... and one behind that to the stream calls of dq_bz2_hip_many* (dq_bz2_many.h), which keep their chunk there while the
 // block stages inside them take the transforms' context and slots of their own: its mutex is taken before any of those.
 constexpr int kBz2Slot = kCtxSlots + 1;
+// ... and one more to the decoder, dq_unbz2_hip_many* (dq_unbz2_many.h), which calls nothing that takes another context.
+constexpr int kUnbz2Slot = kCtxSlots + 2;
 struct DeviceState {
-    DeviceCtx slot[kCtxSlots + 2];
+    DeviceCtx slot[kCtxSlots + 3];
     std::atomic<unsigned> next{0};
 };
 inline DeviceState g_dev[kMaxDevices];
@@ -646,6 +648,13 @@ int bz2_many_host(const uint8_t *src, const int64_t *offsets, int32_t count, int
                   uint8_t *out, int64_t *out_len, int32_t device);
 int bz2_many_dev(const void *d_src, const void *d_offsets, int32_t count, int32_t level, int64_t span, const void *d_out_offsets, void *d_out,
                  void *d_out_len, int32_t device, void *stream);
+
+// Many bzip2 streams decoded (dq_unbz2_many.h, in dq_sorter_i32.hip): the bodies of dq_unbz2_hip_many / _many_dev.  No
+// record, no profile category of their own.
+int unbz2_many_host(const uint8_t *src, const int64_t *offsets, int32_t count, const int64_t *out_offsets, uint8_t *out, int64_t *out_len,
+                    int32_t *status, int32_t device);
+int unbz2_many_dev(const void *d_src, const void *d_offsets, int32_t count, const void *d_out_offsets, void *d_out, void *d_out_len,
+                   void *d_status, int32_t device, void *stream);
 
 // LDSSChecker.Check on the device (dq_sufcheck.hip): DQ_OK with the verdict (DQ_SUFCHECK_*) in *result, or an error
 template <typename IdxT>

@@ -498,6 +498,79 @@ class HipSuffixSort:
                                                  out.data_ptr(), out_len.data_ptr(), dev, stream))
         return out, out_off, out_len
 
+    # -- the way back: many bzip2 streams decoded on the device ------------------------------------------------------------
+    def Unbz2Many(self, streams, caps=None):
+        """Many bzip2 streams decoded in shared launches, each with the verdict and the bytes of the library's host
+        decoder for that stream and capacity: 0 ok, -1 corrupt, -2 truncated, -3 longer than its capacity.  A stream is
+        untrusted input; a malformed one is its own verdict, never a failed call.
+
+        ``Unbz2Many([s0, s1, ...], caps)`` -- bytes-like objects / numpy uint8 arrays, ``caps`` one int for all or one
+        per stream -- returns ``(list of bytes or None, int32 status array)`` (``dq_unbz2_hip_many``).
+        ``Unbz2Many(((src_tensor, offsets_tensor), out_offsets_tensor))`` -- uint8 / int64 / int64 torch GPU
+        tensors, stream j's slot being ``out[out_offsets[j] : out_offsets[j + 1]]`` -- returns ``(out, out_len, status)``
+        tensors on the device (``dq_unbz2_hip_many_dev``, on the current torch stream).
+        """
+        if isinstance(streams, tuple) and len(streams) == 2 and isinstance(streams[0], tuple):
+            if caps is not None:
+                raise ValueError("the tensor form takes its capacities from out_offsets: caps must be None")
+            return self._unbz2_many_device(streams[0][0], streams[0][1], streams[1])
+        if caps is None:
+            raise ValueError("caps: one int for all streams, or one per stream")
+        arrs = [_as_text(s) for s in streams]
+        if any(a.ndim != 1 for a in arrs):
+            raise TypeError("every stream must be one-dimensional")
+        count = len(arrs)
+        cap_list = [int(caps)] * count if isinstance(caps, (int, np.integer)) else [int(c) for c in caps]
+        if len(cap_list) != count:
+            raise ValueError("caps must be one int, or one per stream")
+        if any(c < 0 or c > INT_MAX for c in cap_list) or any(a.size > INT_MAX for a in arrs):
+            raise ValueError("Unbz2Many has 32-bit indices: every stream and capacity must be in 0 .. 2^31 - 1")
+        if count == 0:
+            return [], np.zeros(0, dtype=np.int32)
+        off = np.zeros(count + 1, dtype=np.int64)
+        np.cumsum([a.size for a in arrs], out=off[1:])
+        out_off = np.zeros(count + 1, dtype=np.int64)
+        np.cumsum(cap_list, out=out_off[1:])
+        flat = np.concatenate(arrs) if int(off[-1]) else np.zeros(1, np.uint8)
+        out = np.empty(max(int(out_off[-1]), 1), dtype=np.uint8)
+        out_len = np.empty(count, dtype=np.int64)
+        status = np.empty(count, dtype=np.int32)
+        _abi.check(self._lib.dq_unbz2_hip_many(flat.ctypes.data, off.ctypes.data, count, out_off.ctypes.data, out.ctypes.data,
+                                               out_len.ctypes.data, status.ctypes.data, self.device))
+        return [out[out_off[j]:out_off[j] + int(out_len[j])].tobytes() if status[j] == 0 else None for j in range(count)], status
+
+    unbz2_many = Unbz2Many
+
+    def _unbz2_many_device(self, src, offsets, out_offsets):
+        import torch
+
+        for t in (src, offsets, out_offsets):
+            if not _is_torch_tensor(t):
+                raise TypeError("the tensor form needs three torch tensors: ((src, offsets), out_offsets)")
+        if src.dtype != torch.uint8 or src.dim() != 1 or not src.is_contiguous():
+            raise TypeError("device streams must be a contiguous 1-D uint8 tensor")
+        for t in (offsets, out_offsets):
+            if t.dtype != torch.int64 or t.dim() != 1 or not t.is_contiguous() or t.numel() < 1:
+                raise TypeError("offsets and out_offsets must be contiguous 1-D int64 tensors of count + 1 entries")
+        if not src.is_cuda or offsets.device != src.device or out_offsets.device != src.device:
+            raise TypeError("streams, offsets and out_offsets must live on the same GPU")
+        if offsets.numel() != out_offsets.numel():
+            raise ValueError("offsets and out_offsets must have the same number of entries")
+        count = offsets.numel() - 1
+        total = int(out_offsets[-1].item())
+        if total < 0:
+            raise ValueError("out_offsets must not decrease")
+        out = torch.empty(max(total, 1), dtype=torch.uint8, device=src.device)
+        out_len = torch.zeros(count, dtype=torch.int64, device=src.device)
+        status = torch.zeros(count, dtype=torch.int32, device=src.device)
+        if count == 0:
+            return out, out_len, status
+        dev, stream = _device_and_stream(src)
+        sp = src if src.numel() else torch.zeros(1, dtype=torch.uint8, device=src.device)
+        _abi.check(self._lib.dq_unbz2_hip_many_dev(sp.data_ptr(), offsets.data_ptr(), count, out_offsets.data_ptr(), out.data_ptr(),
+                                                   out_len.data_ptr(), status.data_ptr(), dev, stream))
+        return out, out_len, status
+
     # -- LDSSChecker.Check(T, SA)   (test/DeltaQ.SuffixSorting.LibDivSufSort.Tests/LDSSChecker.cs:23-119) --------
     def Check(self, text, suffixes) -> int:
         """LDSSChecker's verdict on ``suffixes`` as the suffix array of ``text``, decided on the device:

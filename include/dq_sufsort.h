@@ -311,6 +311,54 @@ int32_t dq_bz2_hip_many(const uint8_t *src, const int64_t *offsets, int32_t coun
 int32_t dq_bz2_hip_many_dev(const void *d_src, const void *d_offsets, int32_t count, int32_t level, int64_t span,
                             const void *d_out_offsets, void *d_out, void *d_out_len, int32_t device, void *stream);
 
+/* ---- Many bzip2 streams decoded on the device -------------------------------------------------------------------
+ * The way back from dq_bz2_hip_many, and from any bzip2 writer: every stream is untrusted input.
+ * Layout: as the other many-calls, streams back to back, offsets[count + 1], offsets[0] == 0, never decreasing.  Stream j
+ * owns out[out_offsets[j] .. out_offsets[j + 1]); the slot's size is its capacity cap_j (out_offsets[0] == 0, never
+ * decreasing, no alignment asked).  Only byte stores go into a slot (a four-byte store would go only where the word is
+ * aligned and wholly inside the slot).
+ * Definition: with rc = bz2::bz2_decompress(stream j, n_j, v, max_out = cap_j) (deltaq_amd/csrc/dq_bz2.h),
+ *   status[j] == rc: 0 ok, -1 corrupt, -2 truncated, -3 too long;
+ *   rc == 0: out_len[j] == v.size() and the slot's first out_len[j] bytes are v;
+ *   rc != 0: out_len[j] == 0 and the slot's contents are unspecified (the host's cut-off prefix on "too long" is not
+ *            reproduced: a caller who needs it uses the host path);
+ *   nothing outside a stream's own slot is ever written.
+ * Concatenated streams are read as the host reads them -- after a complete stream another "BZh" + level begins the next,
+ * anything else, or fewer than 8 bits, ends the input with what was decoded -- and so are trailing bytes behind a complete
+ * first stream.  Bits behind the input's end read as 0 and make the next test of the reader's state "truncated"; the tests
+ * come where the host makes them: behind a magic, behind the end magic's CRC, behind the code lengths, behind every symbol.
+ * The order of verdicts is the host's: the first block, in stream order, with an event decides, and within a block
+ *   1. an error of the header or the symbols (corrupt or truncated: a set randomised bit, no byte in use, fewer than 2 or
+ *      more than 6 tables, no selector, a selector's unary run that reaches the number of tables, a code length outside
+ *      1 .. 20, a code of more than 20 bits or outside the table, more groups of 50 symbols than selectors, a run digit
+ *      of weight above 2^21, more than level * 100000 bytes, origin >= nblock),
+ *   2. "decoded bytes so far + this block's > cap": too long,
+ *   3. the block CRC: corrupt;
+ * the combined CRC comes after the last block of its stream, a bad level digit or magic where it stands.
+ * Errors, all before any device use in the host form: count < 0, a NULL pointer with count > 0, bad offsets,
+ * out_offsets[0] != 0, a decreasing out_offsets -> DQ_ERR_BAD_ARGS; a stream or a slot of 2^31 bytes or more ->
+ * DQ_ERR_TOO_LARGE.  count == 0 is a no-op.  There is no CPU fallback.  The return value is DQ_OK whenever the call ran: a
+ * malformed stream is a per-stream verdict, never a failed call.  DQ_ERR_HIP ("bzip2 decode failed") is only for a
+ * device-side consistency flag: the kernels range-test every index before it is an address, every loop is bounded by the
+ * stream's bits, by block_max = level * 100000 or by nblock, and no input makes a kernel run on or write outside its areas.
+ *   dq_unbz2_hip_many      host pointers.  The streams travel in chunks of whole streams whose caps and whose stream
+ *                          bytes each sum to at most 64 MiB (and at most 2^20 streams); a stream above that travels
+ *                          alone.  Device memory per chunk of n stream bytes whose caps sum to C, with A = the sum of
+ *                          floor(5 cap / 4) and R = the sum of min(floor(8 n_j / 174), floor(5 cap_j / 4)) possible
+ *                          blocks: n + C staged, A of last columns, A of coded bytes, 4 A of inverse-transform pointers,
+ *                          8 (A / 256 + 2 R + 2) of chase marks, 60 R of block rows -- about 8.5 C beside the rows, 550
+ *                          MiB for a full chunk.  Waits per chunk: ONE, at the end.  The ok streams' bytes are handed on
+ *                          from a host copy of the chunk's slots.
+ *   dq_unbz2_hip_many_dev  device pointers on `device`, d_offsets and d_out_offsets too (d_out_len: int64, d_status:
+ *                          int32): the library fetches both once and checks them before it launches anything; work on
+ *                          `stream`, NULL = the library's; returns after the stream has drained (one wait per chunk, same
+ *                          chunks).  Workspace: as the host form's per chunk without the staged n + C.
+ * Neither has a record of its own, and the kernels are profiled under small_many_kernel's category. */
+int32_t dq_unbz2_hip_many(const uint8_t *src, const int64_t *offsets, int32_t count, const int64_t *out_offsets,
+                          uint8_t *out, int64_t *out_len, int32_t *status, int32_t device);
+int32_t dq_unbz2_hip_many_dev(const void *d_src, const void *d_offsets, int32_t count, const void *d_out_offsets,
+                              void *d_out, void *d_out_len, void *d_status, int32_t device, void *stream);
+
 /* ---- Diff.Create's match search on the device-resident suffix array ----------
  * Replaces, for a batch of scan positions, the reference's
  *   Search(I, oldData, newData[scan..], 0, oldData.Length, out pos)          src/DeltaQ.BsDiff/Diff.cs:267-298
