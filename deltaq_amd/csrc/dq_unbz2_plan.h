@@ -28,6 +28,8 @@ constexpr int kUnbz2MaxMarks = (int)((kUnbz2BlockMax - 1) / kUnbz2Spacing) + 2;
 // that needs more than floor(5 cap / 4) is too long at the block where the area ends, or earlier.
 DQ_UNBZ2_HD inline int64_t unbz2_area(int64_t cap) { return 5 * cap / 4; }
 // ... and the blocks it can hold: each is at least kUnbz2MinBlockBits bits of the stream and one coded byte of the area.
+// (A lower bound with room: under lengths 1, 1, 1 no bits reach EOB, so the densest block that decodes has 176 bits --
+// two tables of lengths 2, 2, 2 and two codes of two bits.  tests/unbz2_model.py, densest(), writes 200 of them.)
 DQ_UNBZ2_HD inline int64_t unbz2_max_rows(int64_t n, int64_t cap)
 {
     const int64_t by_bits = 8 * n / kUnbz2MinBlockBits, by_area = unbz2_area(cap);

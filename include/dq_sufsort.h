@@ -335,6 +335,8 @@ int32_t dq_bz2_hip_many_dev(const void *d_src, const void *d_offsets, int32_t co
  *   2. "decoded bytes so far + this block's > cap": too long,
  *   3. the block CRC: corrupt;
  * the combined CRC comes after the last block of its stream, a bad level digit or magic where it stands.
+ * A block whose coded bytes end directly behind four equal bytes, the count byte missing, decodes (the four bytes are its
+ * end): libbzip2 refuses such a block, this decoder, like the host's, does not.
  * Errors, all before any device use in the host form: count < 0, a NULL pointer with count > 0, bad offsets,
  * out_offsets[0] != 0, a decreasing out_offsets -> DQ_ERR_BAD_ARGS; a stream or a slot of 2^31 bytes or more ->
  * DQ_ERR_TOO_LARGE.  count == 0 is a no-op.  There is no CPU fallback.  The return value is DQ_OK whenever the call ran: a

@@ -3,8 +3,9 @@ every decoded byte is compared with tests/unbz2_model.py, which tests/test_unbz2
 bz2::bz2_decompress, on the host form and on the device form (on a stream that is not the default one), both with guard
 bytes around `out`, `out_len` and `status`: a mixed set of well-formed streams with the families of the stretch rule, periodic
 blocks around the chase's start spacing, blocks with one start only, the round trip through Bz2Many, two long streams, the
-host form's chunk seam, the whole malformed set in one call among good streams, capacities, two threads and the Python
-faces."""
+host form's chunk seam, the whole malformed set in one call among good streams, the streams that no encoder writes
+(U.crafted_families: hostile last columns and run bytes, free tables, the densest blocks, the area met to the byte, two
+events in a stream, bit flips), capacities, two threads and the Python faces."""
 import bz2
 import threading
 
@@ -234,6 +235,62 @@ def test_a_verdict_does_not_depend_on_the_neighbours(backend_lib, ldss, hostile_
     for j in range(0, len(streams), 17):
         assert_decoded(unbz2_host(backend_lib, [streams[j]], [caps[j]]), [want[j]], j)
     assert_decoded(unbz2_host(backend_lib, streams[::-1], caps[::-1]), want[::-1], "reversed")
+
+
+# ---- 7b. streams that no encoder writes (U.crafted_families), in one call among good streams -----------------------------
+@pytest.fixture(scope="module")
+def crafted_set():
+    """[(family, name, stream, cap, model's (status, bytes))]: every crafted family, a good stream behind each crafted one"""
+    good = [("good", name, s, len(b) + 3, (0, b)) for name, s, b in U.well_formed()]
+    rows = []
+    for family, cases in U.crafted_families().items():
+        for name, s, cap in cases:
+            st, b = U.decode(s, cap)
+            rows += [(family, name, s, cap, (st, b if st == 0 else None)), good[len(rows) // 2 % len(good)]]
+    verdicts = [want[0] for family, _, _, _, want in rows if family != "good"]
+    assert verdicts.count(U.OK) >= 400 and verdicts.count(U.CORRUPT) >= 420 and verdicts.count(U.TRUNCATED) >= 13 and verdicts.count(U.TOO_LONG) >= 77
+    return rows
+
+
+def run_rows(form, lib, rows, what):
+    assert_decoded(FORMS[form](lib, [r[2] for r in rows], [r[3] for r in rows]), [r[4] for r in rows], what)
+
+
+@pytest.mark.parametrize("form", ["host", "device"])
+def test_crafted_set_in_one_call(backend_lib, ldss, crafted_set, form):
+    """hostile columns, hostile run bytes, free tables and moving selectors, the densest blocks, the area met to the byte,
+    two events in a stream, bit flips with and without re-stamped CRCs: verdicts and bytes are the model's, and the call
+    returns 0, so no kernel met a state it holds impossible"""
+    run_rows(form, backend_lib, crafted_set, form)
+
+
+def test_an_uncounted_run_of_four_decodes(backend_lib, ldss, crafted_set):
+    """libbzip2 refuses a block whose coded bytes end behind four equal bytes with no count; the contract does not"""
+    rows = [r for r in crafted_set if r[1] == "runs/block ends after 4 equal bytes, an uncounted run of four/cap exact"]
+    assert len(rows) == 1 and rows[0][4] == (0, b"ab" + b"\xee" * 4)
+    with pytest.raises(OSError):
+        bz2.decompress(rows[0][2])
+    for form in FORMS:
+        run_rows(form, backend_lib, rows, form)
+
+
+def test_the_first_event_decides_wherever_the_stream_stands(backend_lib, ldss, crafted_set):
+    events = [r for r in crafted_set if r[0] == "f"]
+    assert len(events) == 55 and all(r[4][0] != 0 for r in events)
+    run_rows("host", backend_lib, events[::-1], "reversed")
+    run_rows("device", backend_lib, events[::-1], "reversed, device form")
+    for j in range(0, len(events), 5):
+        run_rows("host", backend_lib, events[j:j + 1], events[j][1])
+
+
+def test_crafted_blocks_with_one_chase_start(backend_lib, ldss, crafted_set, monkeypatch):
+    """the 20000-row column, the 120 runs of count 255 (600 coded bytes, 31 KiB decoded) and the densest blocks again with
+    the chase started at the origin's row alone (DQ_UNBZ2_ONE_START, read per call as the other overrides are)"""
+    rows = [r for r in crafted_set if "20000 rows" in r[1] or "120 runs of count 255" in r[1] or r[0] == "d"]
+    assert len(rows) == 2 + 3 + 8 and max(len(r[4][1] or b"") for r in rows) > 31000
+    monkeypatch.setenv("DQ_UNBZ2_ONE_START", "1")
+    for form in FORMS:
+        run_rows(form, backend_lib, rows, form + ", one start")
 
 
 # ---- 8. two host threads at once -----------------------------------------------------------------------------------------

@@ -2,8 +2,9 @@
 tests compare against (tests/unbz2_model.py), held verdict for verdict and byte for byte against bz2::bz2_decompress itself
 (tests/native/unbz2_harness.cpp, a stand-alone program under sanitizers, which also checks the std-only host logic of
 dq_unbz2_plan.h: the chase from many marks, the ordering of its segments with the periodic case, the stretch rule) and against
-CPython's bz2; the ABI surface, the argument checks that need no device, and the Python face's refusals."""
+CPython's bz2, on edits of good streams and on the streams no encoder writes (U.crafted_families); the ABI surface, the argument checks that need no device, and the Python face's refusals."""
 import bz2
+import hashlib
 import os
 import re
 import struct
@@ -13,6 +14,7 @@ import sys
 import numpy as np
 import pytest
 
+import bz2_stream_model as M
 import unbz2_model as U
 from conftest import ROOT
 from test_abi_cpu import csharp_signatures, header_signatures
@@ -28,6 +30,8 @@ def all_cases():
     out = [(name, s, ROOMY, want) for name, s, want in U.well_formed()]
     out += [(name, s, ROOMY, None) for name, s in U.malformed()]
     out += [(name, s, cap, None) for name, s, cap in U.cap_cases()]
+    out += [(name, s, cap, None) for cases in U.crafted_families().values() for name, s, cap in cases]
+    assert len({name for name, _, _, _ in out}) == len(out)
     return out
 
 
@@ -65,7 +69,8 @@ def test_the_model_is_the_hosts_decoder(harness_out, all_cases, model_out):
         else:
             assert got == b""
         seen[rc] = seen.get(rc, 0) + 1
-    assert seen[U.OK] >= 30 and seen[U.CORRUPT] >= 20 and seen[U.TRUNCATED] >= 15 and seen[U.TOO_LONG] >= 6, seen
+    print("verdicts:", seen)
+    assert seen[U.OK] >= 437 and seen[U.CORRUPT] >= 494 and seen[U.TRUNCATED] >= 35 and seen[U.TOO_LONG] >= 85, seen
 
 
 def test_well_formed_streams_decode_as_cpython_says(all_cases, model_out):
@@ -102,6 +107,107 @@ def test_caps(all_cases, model_out):
     assert got["fits the first exactly"] == U.TOO_LONG
     assert got["a count that runs over"] == U.TOO_LONG and got["a count that just fits"] == U.OK and got["a count, one short"] == U.TOO_LONG
     assert got["empty stream, zero"] == U.OK and got["random"] == U.TOO_LONG
+
+
+# ---- the streams no encoder writes (U.crafted_families)
+FOUR_OPEN = "runs/block ends after 4 equal bytes, an uncounted run of four/cap exact"
+
+
+def test_the_writer_writes_what_craft_stream_wrote():
+    """craft_block is a wrapper of write_block: the streams it made before that, by their SHA-256"""
+    was = {"fewer selectors than groups of symbols": "0d361f90465f85d6", "a run past block_max": "597778ff718a601b",
+           "a run digit of weight above 2^21": "d26ede03c5d38b42", "a symbol outside the table": "ee95606899531da1",
+           "no EOB before the selectors end": "6acd0ecd723b9674", "a code of 21 bits": "40572881e331372f"}
+    now = {name: s for name, s in U.malformed()}
+    now["crafted"] = {name: s for name, s, _ in U.well_formed()}["crafted"]
+    was["crafted"] = "cae9a2a619a3f7e7"
+    for name, digest in was.items():
+        assert hashlib.sha256(now[name]).hexdigest()[:16] == digest, name
+    # ... and a column's own symbols under flat tables are what craft_stream makes of the same block
+    data = bytes(np.random.default_rng(5).integers(97, 101, 120, dtype=np.uint8))
+    alpha = len(set(data)) + 2
+    coded = b"".join(c for c, _, _ in M.prepass(data, 9, M.SPAN_NONE))
+    assert U.write_stream([U.of_coded(coded, tables=[[9] * alpha] * 2)]) == U.craft_stream([(data, None)])
+    assert U.canonical([1, 2, 3, 3]) == {0: (0, 1), 1: (2, 2), 2: (6, 3), 3: (7, 3)}
+    assert U.canonical([2, 2, 2, 2, 2]) == {k: (k, 2) for k in range(4)} and U.canonical([1, 3, 3]) == {0: (0, 1), 1: (4, 3), 2: (5, 3)}
+    with pytest.raises(AssertionError, match="no code fits"):
+        U.write_stream([dict(last=b"abcabc", origin=0, tables=[[1] * 5] * 2)])
+
+
+def test_every_crafted_family_has_its_verdict(all_cases, model_out):
+    got = {name: rc for (name, _, _, _), (rc, _) in zip(all_cases, model_out)}
+    stream = {name: s for name, s, _, _ in all_cases}
+    fam = U.crafted_families()
+    counts = {k: len(v) for k, v in fam.items()}
+    assert counts == {"a": 212, "b": 156, "c": 15, "d": 8, "e": 8, "f": 55, "g": 460}, counts
+    assert max(len(s) for cases in fam.values() for _, s, _ in cases) <= 40 << 10
+    # a. every column decodes; the shapes of the chain are asserted where they are built
+    assert all(got[name] == U.OK for name, _, _ in fam["a"])
+    assert sum("20000 rows" in name for name, _, _ in fam["a"]) == 2
+    # b. exact and roomy caps decode, one byte less is too long
+    for name, _, _ in fam["b"]:
+        assert got[name] == (U.TOO_LONG if name.endswith("cap - 1") else U.OK), name
+    assert got[FOUR_OPEN] == U.OK                                # libbzip2 refuses this block; the contract does not
+    with pytest.raises(OSError):
+        bz2.decompress(stream[FOUR_OPEN])
+    # c.
+    for name, _, _ in fam["c"]:
+        assert got[name] == (U.CORRUPT if "unassigned" in name else U.OK), name
+    for name in ("2 tables, the selectors move", "3 tables, the selectors move", "6 tables, the selectors move", "tables never selected",
+                 "lengths with gaps", "incomplete code", "incomplete code, an unassigned code read", "skewed complete code", "length 20 in use",
+                 "258 symbols at lengths 8 and 9", "over-subscribed table, the reachable codes used", "n_sel 32767, one selector needed",
+                 "n_sel exactly 1, 50 symbols", "n_sel exactly 2, 100 symbols", "n_sel exactly 3, 150 symbols"):
+        assert "tables/" + name in got, name
+    # d. 200 blocks, and a block table sized from kUnbz2MinBlockBits = 174 that holds them
+    for name, s, cap in fam["d"]:
+        assert 8 * len(s) // 174 >= 200 and got[name] == (U.OK if cap == 200 else U.TOO_LONG), name
+    assert len(stream["densest/176 bits/level 9/cap 200"]) == (32 + 200 * U.DENSEST_BITS + 80 + 7) // 8
+    # e. the coded size is the area, to the byte
+    for buf in U.area_buffers():
+        for span in (M.SPAN_NONE, 400):
+            assert sum(len(c) for c, _, _ in M.prepass(buf, 9, span)) == 5 * len(buf) // 4
+    for name, _, cap in fam["e"]:
+        assert got[name] == (U.OK if name.endswith("cap exact") else U.TOO_LONG), name
+    # f. the first event decides: a pair's verdict is that of its first event alone, at the same cap
+    pairs = [name for name, _, _ in fam["f"] if name.startswith("two events/")]
+    assert len(pairs) == 31
+    for name in pairs:
+        first, cap = re.fullmatch(r"two events/(\w+@\d)\+.*/(cap \d+)", name).groups()
+        assert got[name] == got[f"one event/{first}/{cap}"] != U.OK, name
+        assert got[name] == (U.TOO_LONG if first[:4] in ("slot", "area") else U.CORRUPT), name
+    assert got["same block/too long and a wrong CRC"] == U.TOO_LONG
+    assert got["same block/the area cannot hold it, a symbol error behind that point"] == U.CORRUPT
+    assert got["same block/origin >= nblock, cap 0"] == U.CORRUPT and got["same block/a cut in the symbols, cap 0"] == U.TRUNCATED
+    assert got["second stream/BZh0"] == U.CORRUPT and got["second stream/BZh9 and nothing"] == U.TRUNCATED
+    assert got["second stream/its first block overflows the cap"] == U.TOO_LONG and got["second stream/wrong block CRC"] == U.CORRUPT
+    # g. of 400 flips, those that reach the inverse transform with a column that is not the encoder's
+    flips, by_crc = U.bit_flips()
+    assert sum(name.startswith("flip/") for name, _, _ in flips) == 400 and len(by_crc) >= 100, len(by_crc)
+    restamped = [name for name, _, _ in flips if name.startswith("flip restamped/")]
+    assert len(restamped) == 60 and all(got[name] == U.OK for name in restamped)
+    print("flips decided by a block CRC alone:", len(by_crc), "of 400")
+
+
+def test_crafted_streams_decode_as_cpython_says(all_cases, model_out):
+    """Every crafted stream the model decodes, CPython's bz2 decodes to the same bytes.  Two kinds may be refused instead:
+    a block whose coded bytes end in an uncounted run of four (libbzip2 refuses those) and n_sel above 18002 (libbzip2
+    before 1.0.8 does)."""
+    crafted = {name for cases in U.crafted_families().values() for name, _, _ in cases}
+    agreed, refused = 0, {"open_run": 0, "n_sel": 0}
+    for (name, s, cap, _), (rc, got) in zip(all_cases, model_out):
+        if name not in crafted or rc != U.OK:
+            continue
+        f = []
+        U.decode(s, cap, fields=f)
+        exempt = [kind for kind in refused if any(n == kind and (kind == "open_run" or U.read_bits(s, pos, 15) > 18002) for n, pos, _ in f)]
+        try:
+            assert bz2.decompress(s) == got, name
+            agreed += 1
+        except OSError:
+            assert exempt, name
+            refused[exempt[0]] += 1
+    assert agreed >= 370 and refused["open_run"] >= 20, (agreed, refused)
+    assert any(name.endswith("n_sel 32767, one selector needed") for name in crafted)
 
 
 # ---- the std-only host logic
