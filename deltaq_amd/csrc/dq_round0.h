@@ -154,6 +154,10 @@ struct Round0 {
             }
         }
         if (hist_deferred) return DQ_OK;
+        // (the bucketed round 0 launches the offsets of its own digits, and digit_tables() again should it give up: the
+        // offsets of the kb plain digits would be overwritten unread.  The coded keys' histogram is not text_digit_offsets_kernel
+        // and stays where it was.)
+        if (!coded && plan_bucketed(s, F, k, coded, (int)wb).applies) return DQ_OK;
         return digit_tables(k.kb, coded);
     }
 
@@ -191,9 +195,33 @@ struct Round0 {
     // After a packed sort whose last pass ran in kKeysLastTies mode: decide the cross-tile pairs, then
     // turn the tie bits into the list of tied suffixes (act_rank, Va)[0, o.m).  *overflow: a run of equal keys too long for
     // the per-thread walk was met and the caller must take the general rebucket pass instead.
+    // settle (tie_settle_kernel, dq_ties.h): one kernel orders the groups of <= 8 straight from the tie bits and lists only
+    // what it could not settle, in (act_rank, Va)[0, o.fin_left); o.m is still the number of tied suffixes it saw.
     int collect_ties(uint32_t *ebits, const uint64_t *seam_tab, uint64_t *act_rank, bool *overflow, uint64_t *fin_rank,
-                     bool seams = true, int64_t h_fin = -1)
+                     bool seams = true, int64_t h_fin = -1, bool settle = false)
     {
+        if (settle) {
+            TieCounters *tctr = reinterpret_cast<TieCounters *>(w.totals + 6);                       // zero since run(), or the producer's flags
+            unsigned long long *listed = reinterpret_cast<unsigned long long *>(w.totals + 3);     // zero since run()
+            const int64_t tile = (int64_t)kSettleThreads * kSettleWords;
+            // grid-stride: as many workgroups as stay resident (six waves per SIMD, its launch bounds), and no more than there are tiles
+            const int64_t groups = std::min<int64_t>((tie_words() + tile - 1) / tile, (int64_t)std::max(c.ncu, 1) * 6);
+            o.fin_cap = n;                                   // what the list may take: every member of every group fits
+            LAUNCH(L, DQ_K_TIE_COLLECT, n, n / 8,
+                   hipLaunchKernelGGL(tie_settle_kernel<IdxT>, dim3((unsigned)groups), dim3(kSettleThreads), 0, L.st,
+                                      reinterpret_cast<const uint64_t *>(ebits), tie_words(), n, d_sa, (const uint8_t *)w.text,
+                                      h_fin >= 0 ? h_fin : (int64_t)k.kb, act_rank, w.Va, o.fin_cap, tctr, listed));
+            // [1] sticky flag, [3] list length, [6..7] counters
+            DQ_TRY(read_totals<IdxT>(L, c, w, 64, "radix look-back timed out (device spin bound hit)"));
+            o.m = c.pinned[6];
+            o.fin_left = c.pinned[3];
+            *overflow = c.pinned[7] != 0 || o.fin_left > o.fin_cap;
+            if (flags().trace)
+                fprintf(stderr, "[dq] ties settled from their bits: %lld tied suffixes, %lld of them listed (n=%lld)\n", (long long)o.m,
+                        (long long)o.fin_left, (long long)n);
+            if (*overflow && flags().trace) fprintf(stderr, "[dq] tie / bucket overflow flags: %lld\n", (long long)c.pinned[7]);
+            return DQ_OK;
+        }
         using Cfg = RankCfg<IdxT, kKeysLastTies>;
         using CfgS = RankCfg<IdxT, kKeysLastTies, true>;
         const int64_t tile_keys = small_tiles(n) ? CfgS::kThreads * CfgS::kItems : Cfg::kThreads * Cfg::kItems;
@@ -377,7 +405,8 @@ struct Round0 {
         if ((size_t)ft.ntiles + 1 > finish_bounds_entries(n)) return fail(DQ_ERR_HIP, "tile bounds buffer too small");
         if (slots) {
             LAUNCH(L, DQ_K_BUCKET_SORT, ft.ntiles, ft.ntiles * 16,
-                   hipLaunchKernelGGL(slot_out_kernel, dim3(1), dim3(kSlotOutThreads), 0, st, sctl->cursor, (uint32_t)b.X, slot_out, bflags));
+                   hipLaunchKernelGGL(slot_out_kernel, dim3(kRadixSize), dim3(kSlotOutThreads), 0, st, sctl->cursor, (uint32_t)b.X,
+                                      (const int64_t *)(w.digit_offset + kRadixSize) /* place 1: the first byte */, n, slot_out, bflags));
             auto kernel = bucket_sort_kernel<IdxT, false, BktFine, true>;
             const int groups = resident_groups(&c.bkt_slot_groups[sizeof(IdxT) == 8], (const void *)kernel, BktFine::threads, c.dev);
             LAUNCH(L, DQ_K_BUCKET_SORT, n, n * (8 + wb) + n / 8,
@@ -413,7 +442,10 @@ struct Round0 {
         }
         if (b.ext && F.trace) fprintf(stderr, "[dq] bucketed round 0 with %d + 8 key bits per suffix (n=%lld)\n", keybits, (long long)n);
         bool overflow = false;
-        DQ_TRY(collect_ties(ebits, nullptr, Kfree, &overflow, Ks, /*seams=*/false, b.hb));
+        // the ties settled straight from their bits (DQ_TIE_SETTLE: unset = where the slots route runs, 0 = never, 1 = on
+        // every bucketed route): the bits lie in Vb, so what stays tied is listed in (Kfree, Va)
+        const bool settle = F.tie_settle.value_or(slots ? 1 : 0) != 0;
+        DQ_TRY(collect_ties(ebits, nullptr, Kfree, &overflow, Ks, /*seams=*/false, b.hb, settle));
         if (overflow) {
             // a bucket or a bin this path does not take (or a run of equal keys too long for the tie walk):
             // back to the plain digit passes, with the state they expect
@@ -424,8 +456,13 @@ struct Round0 {
             o.m = 0; o.fin_cap = 0; o.fin_left = 0;
             return digit_tables(kb, false);
         }
-        o.fin_done = o.m <= o.fin_cap;
+        o.fin_done = settle || o.m <= o.fin_cap;
         o.Kr[0] = Kfree; o.Kr[1] = Ks;
+        if (settle) {
+            // finish_sparse() steps from buffer 0 to buffer 1 for the leftovers: there they are
+            o.Kr[0] = Ks; o.Kr[1] = Kfree;
+            o.Vr[0] = w.Vb; o.Vr[1] = w.Va;
+        }
         o.h = b.hb;
         o.shallow_ties = true;                           // ties of random-like text: the finisher, not the ISA
         *done = true;

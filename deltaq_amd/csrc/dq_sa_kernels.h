@@ -7,7 +7,56 @@
 // Order contract (reference: LibDivSufSortTests.cs:43-59 -- unsigned bytes,
 // a proper prefix sorts first): suffixes that run off the end of the text are
 // resolved by gather_key2's "past the end" rule, never by the zero padding.
+//
+// suffix_window_compare is plain C++ and comes first, so that the CPU tests compile the very same function
+// (tests/native/tie_order_harness.cpp); a compiler other than hipcc sees nothing else of this file.
 #pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define DQ_HD __host__ __device__
+#else
+#define DQ_HD
+#endif
+
+namespace dq {
+
+// Order of the suffixes a and b of text[0, n) from offset h on, looking at no more than kMaxLen bytes of each:
+// -1: a < b, +1: a > b, 0: undecided within kMaxLen bytes.  The kMaxLen bytes of both suffixes are fetched as 8-byte
+// words, all in flight together (the text is followed by 64 zero bytes, so the words of a suffix that ends inside the
+// window exist; what lies behind an end never decides: `lim` stops the comparison there, and the suffix that ends
+// first sorts first).  a + h <= n and b + h <= n.
+// (Byte-at-a-time, a pair that shares the whole window cost 2 x kMaxLen dependent loads: a 256 MiB slice of a
+// shared library with 38 M deep ties spent 12.7 ms in small_group_finish_kernel.)
+template <int kMaxLen>
+DQ_HD inline int suffix_window_compare(const uint8_t *text, int64_t n, int64_t h, int64_t a, int64_t b)
+{
+    static_assert(kMaxLen % 8 == 0, "whole words");
+    typedef uint64_t u64_any __attribute__((aligned(1), may_alias));
+    const int64_t pa = a + h, pb = b + h;
+    uint64_t wa[kMaxLen / 8], wbv[kMaxLen / 8];
+#pragma unroll
+    for (int k = 0; k < kMaxLen / 8; ++k) {
+        wa[k] = *reinterpret_cast<const u64_any *>(text + pa + 8 * k);
+        wbv[k] = *reinterpret_cast<const u64_any *>(text + pb + 8 * k);
+    }
+    int d = kMaxLen;                                   // first differing byte
+    bool a_less = false;
+#pragma unroll
+    for (int k = kMaxLen / 8 - 1; k >= 0; --k) {
+        const uint64_t x = __builtin_bswap64(wa[k]), y = __builtin_bswap64(wbv[k]);
+        if (x != y) { d = 8 * k + (__builtin_clzll(x ^ y) >> 3); a_less = x < y; }
+    }
+    const int64_t la = n - pa, lb = n - pb;            // bytes each suffix still has (>= 0)
+    const int64_t lim = la < lb ? (la < kMaxLen ? la : kMaxLen) : (lb < kMaxLen ? lb : kMaxLen);
+    if (d < lim) return a_less ? -1 : 1;
+    if (lim < kMaxLen) return la < lb ? -1 : 1;        // one of them ends inside the window: the shorter first
+    return 0;
+}
+
+}  // namespace dq
+
+#if defined(__HIPCC__)
 #include "dq_runs.h"
 #include "dq_device_utils.h"
 
@@ -139,34 +188,8 @@ __global__ __launch_bounds__(kFinishThreads) void small_group_finish_kernel(
     if (head) {
 #pragma unroll
         for (int i = 0; i < kMaxG; ++i) s[i] = i < g ? (int64_t)suf[j + i] : 0;
-        // -1: a < b, +1: a > b, 0: undecided within kMaxLen bytes.  The kMaxLen bytes of both suffixes are fetched
-        // as 8-byte words, all in flight together (the text is followed by 64 zero bytes, so the words of a suffix
-        // that ends inside the window exist; what lies behind an end never decides: `lim` stops the comparison there).
-        // (Byte-at-a-time, a pair that shares the whole window cost 2 x kMaxLen dependent loads: a 256 MiB slice of a
-        // shared library with 38 M deep ties spent 12.7 ms here.)
-        static_assert(kMaxLen % 8 == 0, "whole words");
-        typedef uint64_t u64_any __attribute__((aligned(1)));
-        auto cmp = [&](int64_t a, int64_t b) -> int {
-            const int64_t pa = a + h, pb = b + h;
-            uint64_t wa[kMaxLen / 8], wbv[kMaxLen / 8];
-#pragma unroll
-            for (int k = 0; k < kMaxLen / 8; ++k) {
-                wa[k] = *reinterpret_cast<const u64_any *>(text + pa + 8 * k);
-                wbv[k] = *reinterpret_cast<const u64_any *>(text + pb + 8 * k);
-            }
-            int d = kMaxLen;                                   // first differing byte
-            bool a_less = false;
-#pragma unroll
-            for (int k = kMaxLen / 8 - 1; k >= 0; --k) {
-                const uint64_t x = __builtin_bswap64(wa[k]), y = __builtin_bswap64(wbv[k]);
-                if (x != y) { d = 8 * k + (__builtin_clzll(x ^ y) >> 3); a_less = x < y; }
-            }
-            const int64_t la = n - pa, lb = n - pb;            // bytes each suffix still has (>= 0)
-            const int64_t lim = la < lb ? (la < kMaxLen ? la : kMaxLen) : (lb < kMaxLen ? lb : kMaxLen);
-            if (d < lim) return a_less ? -1 : 1;
-            if (lim < kMaxLen) return la < lb ? -1 : 1;        // one of them ends inside the window: the shorter first
-            return 0;
-        };
+        // -1: a < b, +1: a > b, 0: undecided within kMaxLen bytes (suffix_window_compare, above)
+        auto cmp = [&](int64_t a, int64_t b) -> int { return suffix_window_compare<kMaxLen>(text, n, h, a, b); };
         // bubble passes with static indices keep s[] in registers.  Nearly every group on random-like
         // data is a pair: it gets its own single comparison instead of walking the 28-site network.
         bool decided = true;
@@ -265,3 +288,4 @@ __global__ __launch_bounds__(kBlock) void isa_scatter_kernel(const uint64_t *__r
 }
 
 }  // namespace dq
+#endif  // __HIPCC__

@@ -18,8 +18,9 @@
 //                      in one L2.  The next tile's words are in flight while the current tile is ranked.  No workgroup
 //                      waits for another anywhere.  A word whose place is beyond its slot is not written; it raises
 //                      BucketFlags reason 2 and the host falls back to the plain digit passes.
-//   slot_out_kernel    exclusive scan of the 65 536 counts: where bucket b's suffixes go in the suffix array.  A count
-//                      above X raises reason 2 (and is clamped: the finish kernel never reads beyond a slot).
+//   slot_out_kernel    where bucket b's suffixes go in the suffix array: per first byte, its exact digit offset plus a
+//                      scan of its 256 counts.  A count above X raises reason 2 (and is clamped: the finish kernel
+//                      never reads beyond a slot).
 // bucket_sort_kernel<.., kSlots> then fetches cursor[b] words from slot_base[b] and writes at out[b].
 #pragma once
 #include "dq_bucket_sort.h"
@@ -58,50 +59,38 @@ static __global__ __launch_bounds__(kBlock) void slot_plan_kernel(const int64_t 
     slot_base[A * kRadixSize + d] = (uint32_t)(X * ((int64_t)s_rank * nb + (s_present ? rb : 0)));
 }
 
-// out[b] for b = 0 .. 65 536: exclusive scan of the buckets' counts.  One workgroup; a thread's 64 consecutive counts come
-// in as 16 vector loads that are all in flight together (the first version walked them one by one: 90 us), and its 64
-// places leave the same way.  A count above X raises reason 2 and is clamped, so the finish kernel never reads beyond a
-// slot (a bucket without a slot has count 0: slot_rank_kernel does not reserve there).
-constexpr int kSlotOutThreads = 1024;
+// out[b] for b = 0 .. 65 536: where bucket b = (A, B)'s suffixes go in the suffix array.  One workgroup per first byte A:
+// the suffixes whose first byte is below A are known exactly (first_offset[A], the digit offsets of the first byte), so
+// the place is first_offset[A] + the counts of (A, B' < B) -- 256 scans of 256 counts side by side instead of one scan of
+// 65 536 by one workgroup (22 us of a single CU at the headline size).  It equals the global scan whenever no flag is up:
+// every row then sums to its byte's count.  A count above X raises reason 2 and is clamped, so the finish kernel never
+// reads beyond a slot (a bucket without a slot has count 0: slot_rank_kernel does not reserve there); a row that would
+// run past its byte's range raises it too and is cut there, so place + count stays inside the array whatever the counts.
+constexpr int kSlotOutThreads = kRadixSize;
 static __global__ __launch_bounds__(kSlotOutThreads) void slot_out_kernel(uint32_t *__restrict__ count /*[65536]*/, uint32_t X,
-                                                                   uint32_t *__restrict__ out /*[65537], 16-byte aligned*/,
+                                                                   const int64_t *__restrict__ first_offset /*[256]*/, int64_t n,
+                                                                   uint32_t *__restrict__ out /*[65537]*/,
                                                                    BucketFlags *__restrict__ flags)
 {
-    constexpr int kPer = kSlotBuckets / kSlotOutThreads, kVec = kPer / 4;
-    __shared__ uint32_t wtot[kSlotOutThreads / kWave];
-    const int tid = threadIdx.x, lane = lane_id(), wv = tid >> 6;
-    uint4 *cv = reinterpret_cast<uint4 *>(count) + tid * kVec;
-    uint4 c[kVec];
-#pragma unroll
-    for (int i = 0; i < kVec; ++i) c[i] = cv[i];
-    uint32_t sum = 0, mx = 0;
-#pragma unroll
-    for (int i = 0; i < kVec; ++i) {
-        mx = max(max(max(c[i].x, c[i].y), max(c[i].z, c[i].w)), mx);
-        c[i].x = min(c[i].x, X); c[i].y = min(c[i].y, X); c[i].z = min(c[i].z, X); c[i].w = min(c[i].w, X);
-        sum += c[i].x + c[i].y + c[i].z + c[i].w;
-    }
-    if (mx > X) {                                           // (the path falls back; the clamped counts keep the finish kernel in bounds)
+    static_assert(kSlotOutThreads == kBlock, "block_excl_sum scans kBlock values");
+    __shared__ uint32_t tmp[kWavesPerBlock];
+    const int A = blockIdx.x, B = threadIdx.x;
+    int64_t lo = first_offset[A], hi = A + 1 < kRadixSize ? first_offset[A + 1] : n;
+    lo = lo < 0 ? 0 : (lo > n ? n : lo);
+    hi = hi < lo ? lo : (hi > n ? n : hi);
+    const uint32_t room = (uint32_t)(hi - lo);              // (n < 2^31 on the bucketed path)
+    const uint32_t raw = count[A * kRadixSize + B];
+    const uint32_t c = min(raw, X);
+    uint32_t total;
+    const uint32_t excl = block_excl_sum(c, tmp, &total);
+    const uint32_t place = min(excl, room);
+    const uint32_t kept = min(c, room - place);
+    if (kept != raw) {                                      // (the path falls back; the clamped count keeps the finish kernel in bounds)
         atomicOr(&flags->overflow, 2ull);
-#pragma unroll
-        for (int i = 0; i < kVec; ++i) cv[i] = c[i];
+        count[A * kRadixSize + B] = kept;
     }
-    const uint32_t incl = wave_incl_sum(sum);
-    if (lane == kWave - 1) wtot[wv] = incl;
-    __syncthreads();
-    uint32_t run = incl - sum;
-    for (int i = 0; i < wv; ++i) run += wtot[i];
-    uint4 *ov = reinterpret_cast<uint4 *>(out) + tid * kVec;
-#pragma unroll
-    for (int i = 0; i < kVec; ++i) {
-        uint4 o;
-        o.x = run; run += c[i].x;
-        o.y = run; run += c[i].y;
-        o.z = run; run += c[i].z;
-        o.w = run; run += c[i].w;
-        ov[i] = o;
-    }
-    if (tid == kSlotOutThreads - 1) out[kSlotBuckets] = run;
+    out[A * kRadixSize + B] = (uint32_t)lo + place;
+    if (A == kRadixSize - 1 && B == kRadixSize - 1) out[kSlotBuckets] = (uint32_t)n;
 }
 
 // developer instrumentation (tools/kbench/slotrank.hip): per-tile phase timestamps from thread 0

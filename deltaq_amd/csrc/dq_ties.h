@@ -14,12 +14,15 @@
 //                       A group is emitted by the thread that owns its first member, so members stay
 //                       adjacent; lists are appended with one atomic per workgroup (order across
 //                       workgroups is arbitrary, as in dq_small_groups.h).
+//   tie_settle_kernel   (bucketed round 0 into slots, DQ_TIE_SETTLE) reads the same bits, orders the groups of <= 8 by
+//                       direct text comparison on the spot and lists only what that leaves tied; see the kernel.
 //
 // This replaces a full pass over the sorted words (8 B per suffix) by 1 bit per suffix.  Runs of more
 // than kTieMaxRun equal keys (long repeats in an otherwise random text) set *overflow and the host
 // falls back to the general rebucket pass.
 #pragma once
 #include "dq_onesweep.h"
+#include "dq_sa_kernels.h"
 
 namespace dq {
 
@@ -168,4 +171,203 @@ __global__ __launch_bounds__(kTieThreads) void tie_collect_kernel(const uint64_t
     (void)n;
 }
 
+// ---------------------------------------------------------------------------------
+// tie_settle_kernel: tie_collect_kernel and small_group_finish_kernel<8, 32> in one pass, for round 0s that leave few and
+// shallow ties (the bucketed round 0 of random-like text: at 36 key bits nearly every group is a pair).  A group's size is
+// the run of its bits and its rank the position of its first member, so the group's suffixes are loaded from SA, ordered
+// with suffix_window_compare -- the finisher's comparison -- and written back to SA[head + i]: no list is written and
+// read back, and nobody looks for a group's bounds among neighbouring ranks.  What cannot be settled -- groups of more
+// than kSettleMaxG, groups with an undecided comparison -- goes to the list (list_rank, list_suf) as (rank = head,
+// suffix), members adjacent: the form tie_collect_kernel writes and the finisher leaves, for the key-extension rounds.
+// SA is written for settled groups only, each by the one lane that took the group, after that lane's own loads of it;
+// ctr->overflow non-zero on entry (the producer gave up) stops the kernel before any write.
+//
+// Shape.  The work is a chain of three dependent loads (tie word -> SA entries -> text), the last at random places of
+// the text, and most tie words of a shallowly tied text hold no group at all (one pair per eight words at the
+// headline): a lane that walks its own words keeps seven of eight lanes idle in every step.  (First version: two
+// words per lane, the loads of a round issued together, four trips: 85 us at the headline against the 114 us of the
+// two kernels it replaces; this one 72 us.  What is left does not follow the number of dependent steps any more: see
+// docs/ROUNDS.md, round 32.)  Here a wave reads kSettleWords x 64 words, all loads in
+// flight together, and its lanes push the groups they find -- word, first bit, members inside the word, "goes on" --
+// into a queue of the wave's own in LDS; then lane q takes group q: the SA loads of 64 groups, then the text loads of
+// their first comparisons, are issued together by full waves.  A queue holds kSettleQueue groups; a wave with more (a
+// densely tied text) fills and drains it as often as needed: every pass reads the words again and pushes the groups
+// whose number falls into it, so that nothing but the pass's number lives through the draining (80 registers, six
+// waves per SIMD).  Groups of 3 ... 8 go on from their first comparison in rolled loops (rare at the headline).
+// 256-thread workgroups on tiles of 2048 words (grid-stride beyond what stays resident), no workgroup barrier in the loop:
+// the list is appended with one atomic per wave and queue pass that has leftovers -- a workgroup-wide append would put
+// barriers into every pass for a list that stays empty on the texts this is for --, the tied suffixes are counted in
+// registers and added once per workgroup.
+// ---------------------------------------------------------------------------------
+constexpr int kSettleThreads = 256;
+constexpr int kSettleWords = 8;
+constexpr int kSettleQueue = 256;
+constexpr int kSettleMaxG = 8, kSettleLen = 32;
+
+// the group SA[head, head + g), 3 <= g <= kSettleMaxG, ordered in place; false: a comparison stayed undecided (nothing
+// written) or an entry is no suffix of the text (*bad)
+template <typename IdxT>
+__device__ __forceinline__ bool settle_group(IdxT *SA, const uint8_t *__restrict__ text, int64_t n, int64_t h, int64_t head, int g, bool *bad)
+{
+    // Place of a member = how many members sort before it: every pair is compared once, in rolled loops that read the
+    // members from SA as they go (they are cached), so that this rare path costs the kernel one comparison's registers.
+    // (small_group_finish_kernel's unrolled 28-site network takes 152 registers a lane.)  Decided comparisons of
+    // distinct suffixes are a total order, so the places are a permutation.
+    uint32_t place = 0;                                             // 4 bits per member
+    bool decided = true;
+#pragma unroll 1
+    for (int i = 0; i + 1 < g && decided; ++i) {
+        const int64_t si = (int64_t)SA[head + i];
+#pragma unroll 1
+        for (int j = i + 1; j < g && decided; ++j) {
+            const int64_t sj = (int64_t)SA[head + j];
+            if (!((uint64_t)si < (uint64_t)n && (uint64_t)sj < (uint64_t)n)) { *bad = true; return false; }
+            const int c = suffix_window_compare<kSettleLen>(text, n, h, si, sj);
+            if (c == 0) decided = false;
+            place += c > 0 ? 1u << (4 * i) : 1u << (4 * j);         // the later one of the two moves up a place
+        }
+    }
+    if (!decided) return false;
+    IdxT s[kSettleMaxG];
+#pragma unroll
+    for (int i = 0; i < kSettleMaxG; ++i) s[i] = i < g ? SA[head + i] : (IdxT)0;
+#pragma unroll
+    for (int i = 0; i < kSettleMaxG; ++i)
+        if (i < g) SA[head + (int64_t)((place >> (4 * i)) & 15u)] = s[i];
+    return true;
+}
+
+template <typename IdxT>
+__global__ __launch_bounds__(kSettleThreads, 6) void tie_settle_kernel(
+    const uint64_t *__restrict__ ebits, int64_t nwords, int64_t n, IdxT *SA, const uint8_t *__restrict__ text, int64_t h,
+    uint64_t *__restrict__ list_rank, IdxT *__restrict__ list_suf, int64_t list_cap /* entries the list may take */,
+    TieCounters *__restrict__ ctr /* count: tied suffixes seen */, unsigned long long *__restrict__ list_count /* zero on entry */)
+{
+    constexpr int kW = kSettleWords, kWaves = kSettleThreads / kWave;
+    constexpr int64_t kWaveWords = (int64_t)kWave * kW, kTile = kWaveWords * kWaves;
+    static_assert(kWaveWords <= 1024 && kSettleQueue % kWave == 0, "a queue entry has 10 bits for the word");
+    if (ctr->overflow != 0 || n < 2) return;                        // (uniform) the producer gave up: BucketFlags
+    __shared__ unsigned long long s_seen;
+    __shared__ uint32_t s_queue[kWaves][kSettleQueue];
+    if (threadIdx.x == 0) s_seen = 0;
+    __syncthreads();
+    const int lane = lane_id(), wv = threadIdx.x >> 6;
+    uint32_t *queue = s_queue[wv];
+    unsigned long long seen = 0;
+    bool over = false;                                              // a run too long for the walk, or an index out of range
+    // (the trip count is uniform per workgroup)
+    for (int64_t t0 = (int64_t)blockIdx.x * kTile; t0 < nwords; t0 += (int64_t)gridDim.x * kTile) {
+        const int64_t w0 = t0 + (int64_t)wv * kWaveWords;           // the wave's words: w0 + k * 64 + lane
+        // Groups P ... P + kSettleQueue - 1 of the wave's words per pass.  Every pass loads the words (again: only a
+        // densely tied text has a second pass, and nothing but P has to live through the queue's draining), counts the
+        // groups in front of this lane and pushes those of its groups that fall into the pass.
+        uint32_t P = 0, total = 0;
+        do {                                                        // (uniform per wave)
+            // E bit b: position 64 * i + b ties with its predecessor.  A first member has its own bit clear and its
+            // successor's set (positions that continue an earlier word's group have their own bit set: not taken here).
+            uint64_t E[kW];
+            uint32_t first = 0;                                     // bit k: word k starts with a set bit
+#pragma unroll
+            for (int k = 0; k < kW; ++k) {
+                const int64_t i = w0 + k * kWave + lane;
+                E[k] = i < nwords ? ebits[i] : 0ull;
+            }
+            const int64_t behind = w0 + kWaveWords;                 // the word behind the wave's
+            const uint32_t last = behind < nwords ? (uint32_t)(ebits[behind] & 1ull) : 0u;
+#pragma unroll
+            for (int k = 0; k < kW; ++k) first |= (uint32_t)(E[k] & 1ull) << k;
+            // bit k: word k's successor starts with a set bit.  The successor is the next lane's word k; behind lane 63
+            // it is lane 0's word k + 1, or the word behind the wave's.
+            const uint32_t lane0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)first);
+            const uint32_t up = (uint32_t)__shfl_down((int)first, 1, kWave);
+            const uint32_t goes = lane == kWave - 1 ? ((lane0 >> 1) | (last << (kW - 1))) : up;
+            uint32_t mine = 0;
+#pragma unroll
+            for (int k = 0; k < kW; ++k) mine += (uint32_t)__popcll(((E[k] >> 1) | ((uint64_t)((goes >> k) & 1u) << 63)) & ~E[k]);
+            const uint32_t incl = wave_incl_sum(mine);
+            total = (uint32_t)__shfl((int)incl, kWave - 1, kWave);
+            if (total == 0) break;
+            uint32_t idx = incl - mine;                             // number of this lane's next group among the wave's
+#pragma unroll
+            for (int k = 0; k < kW; ++k) {
+                uint64_t heads = ((E[k] >> 1) | ((uint64_t)((goes >> k) & 1u) << 63)) & ~E[k];
+                while (heads != 0) {                                // (at most 32 trips)
+                    const int b = __builtin_ctzll(heads);
+                    heads &= heads - 1;
+                    if (idx - P < (uint32_t)kSettleQueue) {         // (unsigned: P <= idx < P + kSettleQueue)
+                        // the members above b inside the word: the run of set bits from b + 1 on (zeros come in from the top)
+                        const int run = b < 63 ? __builtin_ctzll(~(E[k] >> (b + 1))) : 0;
+                        const uint32_t on = (b + run == 63) ? ((goes >> k) & 1u) : 0u;
+                        queue[idx - P] = (uint32_t)(k * kWave + lane) | ((uint32_t)b << 10) | ((uint32_t)(run + 1) << 16) | (on << 23);
+                    }
+                    ++idx;
+                }
+            }
+            __builtin_amdgcn_wave_barrier();
+            const uint32_t cnt = min(total - P, (uint32_t)kSettleQueue);
+            for (uint32_t q0 = 0; q0 < cnt; q0 += kWave) {          // (uniform per wave) lane q takes group q
+                const uint32_t q = q0 + (uint32_t)lane;
+                const uint32_t e = q < cnt ? queue[q] : 0u;
+                uint32_t g = (e >> 16) & 127u;                      // 0: no group
+                const int64_t i = w0 + (int64_t)(e & 1023u);
+                const int64_t head = i * 64 + (int64_t)((e >> 10) & 63u);
+                bool bad = false;
+                if ((e >> 23) & 1u) {
+                    // the group runs on into the following words
+                    uint32_t tail = 0;
+                    for (int64_t j = i + 1;; ++j) {                 // (at most kTieMaxRun / 64 + 2 trips)
+                        const uint64_t F = j < nwords ? ebits[j] : 0ull;
+                        const int c = F == ~0ull ? 64 : __builtin_ctzll(~F);
+                        tail += (uint32_t)c;
+                        if (c < 64) break;
+                        if (tail > (uint32_t)kTieMaxRun) { bad = true; break; }
+                    }
+                    g += tail;
+                }
+                if (g != 0 && (bad || head + (int64_t)g > n)) { over = true; g = 0; }
+                // the first two members of every group, then their comparison: the loads of 64 groups issued together
+                // (lanes without a group read entry 0)
+                const int64_t p = g != 0 ? head : 0;
+                const int64_t s0 = (int64_t)SA[p], s1 = (int64_t)SA[p + 1];
+                if (g != 0 && !((uint64_t)s0 < (uint64_t)n && (uint64_t)s1 < (uint64_t)n)) { over = true; g = 0; }
+                seen += g;
+                const bool small = g != 0 && g <= (uint32_t)kSettleMaxG;
+                const int c = suffix_window_compare<kSettleLen>(text, n, h, small ? s0 : 0, small ? s1 : 0);
+                bool left = g > (uint32_t)kSettleMaxG || (small && c == 0);
+                if (g == 2u) {
+                    if (c > 0) { SA[head] = (IdxT)s1; SA[head + 1] = (IdxT)s0; }
+                } else if (small && c != 0) {
+                    bool bad_entry = false;
+                    if (!settle_group<IdxT>(SA, text, n, h, head, (int)g, &bad_entry)) left = true;
+                    if (bad_entry) { over = true; left = false; }
+                }
+                const uint32_t emit = left ? g : 0u;
+                if (__any(emit != 0)) {                             // (uniform per wave)
+                    const uint32_t upto = wave_incl_sum(emit);
+                    const uint32_t tot = (uint32_t)__shfl((int)upto, kWave - 1, kWave);
+                    unsigned long long base = 0;
+                    if (lane == kWave - 1) base = atomicAdd(list_count, (unsigned long long)tot);
+                    base = (unsigned long long)__shfl((long long)base, kWave - 1, kWave);
+                    // a list that does not fit is not written: the host sees its length and redoes the step
+                    if (emit != 0 && base + tot <= (unsigned long long)list_cap) {
+                        int64_t o = (int64_t)base + (upto - emit);
+                        for (uint32_t j = 0; j < g; ++j, ++o) {     // (an unsettled group's SA entries are as they were)
+                            list_rank[o] = (uint64_t)head;
+                            list_suf[o] = SA[head + j];
+                        }
+                    }
+                }
+            }
+            __builtin_amdgcn_wave_barrier();
+            P += (uint32_t)kSettleQueue;
+        } while (P < total);
+    }
+    if (over) atomicOr(&ctr->overflow, 1ull);
+    seen = wave_sum(seen);
+    if (lane == 0 && seen) atomicAdd(&s_seen, seen);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_seen) atomicAdd(&ctr->count, s_seen);
+}
+
 }  // namespace dq
+
