@@ -6,6 +6,7 @@
 //   HipDiff.Apply         Patch.Apply(input, diff, output)                    src/DeltaQ.BsDiff/Patch.cs:34-43,52-168
 //   HipMatchSearch.Search Search(I, oldData, newData[scan..], 0, n, out pos)  src/DeltaQ.BsDiff/Diff.cs:267-298
 //   HipDiffIndex          Diff.cs:89-90 paid once per old file
+//   HipDiff.ApplyMany, HipDiffIndex.ApplyMany                Patch.Apply for many patches in one call, decoded and applied on the device
 //   HipDiff.Scan / ScanMany, HipDiffIndex.Scan / ScanMany    the same calls up to the raw streams, before Diff.cs:15-18's bzip2
 //
 // Ships as SOURCE (no dotnet SDK in the build image); the tested surface is the C ABI (tests/test_gpu_bsdiff.py,
@@ -48,6 +49,18 @@ internal static unsafe class Native
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
     internal static extern int dq_bspatch_apply(byte* oldData, long n, byte* patch, long patchLen, byte* output, long cap,
                                                 long* outLen);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern int dq_bspatch_new_size_many(byte* patches, long* patchOffsets, int count, long* newSize);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern int dq_bspatch_apply_many(byte* olds, long* oldOffsets, byte* patches, long* patchOffsets, int count,
+                                                     byte* output, long* outOffsets, long* outLen, int* status, int* route,
+                                                     int device);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern int dq_bspatch_index_apply_many(IntPtr index, byte* patches, long* patchOffsets, int count,
+                                                           byte* output, long* outOffsets, long* outLen, int* status, int* route);
 
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
     internal static extern int dq_bsdiff_index_create(byte* oldData, long n, void* dOld, void* dSa, int device, IntPtr* index);
@@ -469,6 +482,128 @@ public static class HipDiff
             output.Write(result, 0, result.Length);
         }
     }
+
+    /// <summary>
+    /// <c>Patch.Apply</c> for many (old file, patch) pairs in one native call (dq_bspatch_apply_many): the three bzip2
+    /// streams of every patch are decoded on the device, the control triples are checked and scanned there and the new
+    /// files come out of one streaming kernel; a patch the device cannot vouch for is applied by the host path, so entry j
+    /// is what <see cref="Apply"/> writes for (olds[j], patches[j]).  The first patch the reference rejects raises
+    /// <see cref="InvalidOperationException"/>("Corrupt patch (patch j)").
+    /// </summary>
+    public static unsafe byte[][] ApplyMany(IReadOnlyList<ReadOnlyMemory<byte>> olds, IReadOnlyList<ReadOnlyMemory<byte>> patches,
+                                            int device = -1)
+    {
+        if (olds.Count != patches.Count)
+        {
+            throw new ArgumentException("ApplyMany takes as many patches as old files");
+        }
+
+        var oldOffsets = PatchSlots.Offsets(olds);
+        byte[] flatOld = PatchSlots.Flatten(olds, oldOffsets);
+        return PatchSlots.Run(patches, (pPatches, pPatchOffsets, count, pOut, pOutOffsets, pOutLen, pStatus, pRoute) =>
+        {
+            fixed (byte* pOlds = flatOld)
+            fixed (long* pOldOffsets = oldOffsets)
+            {
+                return Native.dq_bspatch_apply_many(pOlds, pOldOffsets, pPatches, pPatchOffsets, count, pOut, pOutOffsets, pOutLen,
+                                                    pStatus, pRoute, device);
+            }
+        }, nameof(Native.dq_bspatch_apply_many), out _);
+    }
+}
+
+/// <summary>The buffers of an ApplyMany call: slots of the headers' new sizes (dq_bspatch_new_size_many, host code).</summary>
+internal static unsafe class PatchSlots
+{
+    internal delegate int Call(byte* patches, long* patchOffsets, int count, byte* output, long* outOffsets, long* outLen,
+                               int* status, int* route);
+
+    internal static long[] Offsets(IReadOnlyList<ReadOnlyMemory<byte>> files)
+    {
+        var offsets = new long[files.Count + 1];
+        for (int j = 0; j < files.Count; j++)
+        {
+            offsets[j + 1] = offsets[j] + files[j].Length;
+        }
+
+        if (offsets[files.Count] > Array.MaxLength)
+        {
+            throw new ArgumentException("the files of one ApplyMany call must total less than 2^31 bytes");
+        }
+
+        return offsets;
+    }
+
+    internal static byte[] Flatten(IReadOnlyList<ReadOnlyMemory<byte>> files, long[] offsets)
+    {
+        byte[] flat = new byte[Math.Max(offsets[files.Count], 1)];
+        for (int j = 0; j < files.Count; j++)
+        {
+            files[j].Span.CopyTo(flat.AsSpan((int)offsets[j], files[j].Length));
+        }
+
+        return flat;
+    }
+
+    internal static byte[][] Run(IReadOnlyList<ReadOnlyMemory<byte>> patches, Call call, string what, out int[] routes)
+    {
+        int count = patches.Count;
+        routes = new int[count];
+        if (count == 0)
+        {
+            return Array.Empty<byte[]>();
+        }
+
+        var patchOffsets = Offsets(patches);
+        byte[] flat = Flatten(patches, patchOffsets);
+        var sizes = new long[count];
+        var outOffsets = new long[count + 1];
+        var outLen = new long[count];
+        var status = new int[count];
+        fixed (byte* pPatches = flat)
+        fixed (long* pPatchOffsets = patchOffsets)
+        fixed (long* pSizes = sizes)
+        {
+            Native.Check(Native.dq_bspatch_new_size_many(pPatches, pPatchOffsets, count, pSizes), nameof(Native.dq_bspatch_new_size_many));
+            for (int j = 0; j < count; j++)
+            {
+                if (sizes[j] < 0)
+                {
+                    throw new InvalidOperationException($"Corrupt patch (patch {j})");
+                }
+
+                outOffsets[j + 1] = outOffsets[j] + sizes[j];
+            }
+
+            if (outOffsets[count] > Array.MaxLength)
+            {
+                throw new ArgumentException("the new files of one ApplyMany call must total less than 2^31 bytes");
+            }
+
+            byte[] output = new byte[Math.Max(outOffsets[count], 1)];
+            fixed (byte* pOut = output)
+            fixed (long* pOutOffsets = outOffsets)
+            fixed (long* pOutLen = outLen)
+            fixed (int* pStatus = status)
+            fixed (int* pRoute = routes)
+            {
+                Native.Check(call(pPatches, pPatchOffsets, count, pOut, pOutOffsets, pOutLen, pStatus, pRoute), what);
+            }
+
+            var files = new byte[count][];
+            for (int j = 0; j < count; j++)
+            {
+                if (status[j] != 0)
+                {
+                    throw new InvalidOperationException($"Corrupt patch (patch {j})");
+                }
+
+                files[j] = output.AsSpan((int)outOffsets[j], (int)outLen[j]).ToArray();
+            }
+
+            return files;
+        }
+    }
 }
 
 /// <summary>Batched <c>Search</c> (Diff.cs:267-298) for many scan positions of newData at once.</summary>
@@ -550,6 +685,24 @@ public sealed unsafe class HipDiffIndex : IDisposable
         IntPtr ix;
         Native.Check(Native.dq_bsdiff_index_clone(_index, device, &ix), nameof(Native.dq_bsdiff_index_clone));
         return new HipDiffIndex(_old, ix);
+    }
+
+    /// <summary>
+    /// <see cref="HipDiff.ApplyMany"/> with every patch against this index's old file (dq_bspatch_index_apply_many): the
+    /// old file's device copy is read where it lies.  <paramref name="routes"/>[j] is 1 where the device kernels produced
+    /// file j and 0 where the host path decided.
+    /// </summary>
+    public byte[][] ApplyMany(IReadOnlyList<ReadOnlyMemory<byte>> patches, out int[] routes)
+    {
+        if (_index == IntPtr.Zero)
+        {
+            throw new ObjectDisposedException(nameof(HipDiffIndex));
+        }
+
+        IntPtr index = _index;
+        return PatchSlots.Run(patches, (pPatches, pPatchOffsets, count, pOut, pOutOffsets, pOutLen, pStatus, pRoute) =>
+            Native.dq_bspatch_index_apply_many(index, pPatches, pPatchOffsets, count, pOut, pOutOffsets, pOutLen, pStatus, pRoute),
+            nameof(Native.dq_bspatch_index_apply_many), out routes);
     }
 
     /// <summary>The patch <c>Diff.Create(oldData, newData, ...)</c> writes.</summary>

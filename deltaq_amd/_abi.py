@@ -42,7 +42,8 @@ CATEGORY_ALIASES = {"mid_many_kernel": "small_many_kernel", "large_text_kernel":
                     "unbz2_parse_kernel": "small_many_kernel", "unbz2_rank_kernel": "small_many_kernel",
                     "unbz2_walk_kernel": "small_many_kernel", "unbz2_write_kernel": "small_many_kernel",
                     "unbz2_unrle_kernel": "small_many_kernel", "unbz2_place_kernel": "small_many_kernel",
-                    "unbz2_verdict_kernel": "small_many_kernel"}
+                    "unbz2_verdict_kernel": "small_many_kernel", "bspatch_ctrl_kernel": "small_many_kernel",
+                    "bspatch_apply_kernel": "small_many_kernel"}
 MID_MAX_N = 65536         # kMidMaxN: longest text of the medium class of the many-texts launches
 LARGE_MAX_N = 4 << 20     # kLargeMaxN: longest text of their segmented sort (dq_large_many.h)
 
@@ -60,6 +61,7 @@ EXPORTS = (
     "dq_sufcheck_hip_many_i32", "dq_sufcheck_hip_many_dev_i32", "dq_last_check_many_info",
     "dq_bsdiff_search_dev_i32", "dq_bsdiff_search_dev_i64", "dq_bsdiff_search_i32", "dq_bsdiff_search_i64",
     "dq_bsdiff_create", "dq_bsdiff_patch_bound", "dq_bsdiff_scan_i32", "dq_bspatch_apply",
+    "dq_bspatch_new_size_many", "dq_bspatch_apply_many", "dq_bspatch_index_apply_many",
     "dq_bsdiff_create_many", "dq_last_diff_many_info", "dq_last_diff_large_info",
     "dq_bsdiff_index_create", "dq_bsdiff_index_clone", "dq_bsdiff_index_buffers", "dq_bsdiff_index_diff", "dq_bsdiff_index_free",
     "dq_bsdiff_index_diff_many", "dq_last_index_many_info", "dq_last_index_large_info",
@@ -235,6 +237,12 @@ def load() -> ctypes.CDLL:
     L.dq_bsdiff_index_free.argtypes = [vp]
     L.dq_bspatch_apply.restype = i32
     L.dq_bspatch_apply.argtypes = [vp, i64, vp, i64, vp, i64, ctypes.POINTER(i64)]
+    L.dq_bspatch_new_size_many.restype = i32
+    L.dq_bspatch_new_size_many.argtypes = [vp, vp, i32, vp]
+    L.dq_bspatch_apply_many.restype = i32
+    L.dq_bspatch_apply_many.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32]
+    L.dq_bspatch_index_apply_many.restype = i32
+    L.dq_bspatch_index_apply_many.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp]
     L.dq_sufsort_hip_workspace_bytes.restype = i64
     L.dq_sufsort_hip_workspace_bytes.argtypes = [i64, i32]
     L.dq_sufsort_hip_workspace_plan.restype = i64

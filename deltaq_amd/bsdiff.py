@@ -35,6 +35,35 @@ def _pack(arrs):
     return np.ascontiguousarray(flat, dtype=np.uint8), off
 
 
+def _apply_many(L, patches, run, verdicts: bool):
+    """The common part of ``Patch.ApplyMany`` and ``DiffIndex.ApplyMany``: slots of the headers' new sizes
+    (dq_bspatch_new_size_many, host code), then ``run`` -- the call itself, handed the patches, the count and the output
+    arrays."""
+    P = [_bytes_of(x) for x in patches]
+    count = len(P)
+    if count == 0:
+        return ([], np.zeros(0, np.int32), np.zeros(0, np.int32)) if verdicts else []
+    p_flat, p_off = _pack(P)
+    sizes = np.zeros(count, np.int64)
+    _abi.check(L.dq_bspatch_new_size_many(p_flat.ctypes.data, p_off.ctypes.data, count, sizes.ctypes.data))
+    if not verdicts and (sizes < 0).any():
+        raise ValueError(f"Corrupt patch (patch {int(np.flatnonzero(sizes < 0)[0])})")     # before any device use
+    o_off = np.zeros(count + 1, np.int64)
+    np.cumsum(np.maximum(sizes, 0), out=o_off[1:])
+    out = np.empty(max(int(o_off[-1]), 1), np.uint8)
+    out_len = np.zeros(count, np.int64)
+    status = np.zeros(count, np.int32)
+    route = np.zeros(count, np.int32)
+    _abi.check(run(p_flat.ctypes.data, p_off.ctypes.data, count, out.ctypes.data, o_off.ctypes.data, out_len.ctypes.data,
+                   status.ctypes.data, route.ctypes.data))
+    files = [out[int(o_off[j]):int(o_off[j]) + int(out_len[j])].tobytes() if status[j] == 0 else None for j in range(count)]
+    if verdicts:
+        return files, status, route
+    if (status != 0).any():
+        raise ValueError(f"Corrupt patch (patch {int(np.flatnonzero(status != 0)[0])})")    # InvalidOperationException("Corrupt patch")
+    return files
+
+
 class _RawSlots:
     """The output buffers of a many-file scan call (dq_bsdiff_scan_many, dq_bsdiff_index_scan_many): control slots of
     dq_bsdiff_ctrl_bound(m) triples each, and `bytes` in the layout of the new files."""
@@ -263,6 +292,12 @@ class DiffIndex:
         _abi.check(self._lib.dq_bsdiff_index_scan_many(self._h, n_flat.ctypes.data, n_off.ctypes.data, slots.count, *slots.pointers()))
         return slots.unpack()
 
+    def ApplyMany(self, patches, verdicts: bool = False):
+        """``[Patch.Apply(oldData, p) for p in patches]`` in one call (dq_bspatch_index_apply_many): every patch is applied
+        to this index's old file, whose device copy is read where it lies.  Results, errors and ``verdicts`` as
+        ``Patch.ApplyMany``'s."""
+        return _apply_many(self._lib, patches, lambda *a: self._lib.dq_bspatch_index_apply_many(self._h, *a), verdicts)
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             self._lib.dq_bsdiff_index_free(self._h)
@@ -302,3 +337,19 @@ class Patch:
             return out.tobytes()
         output.write(out.tobytes())
         return None
+
+    @staticmethod
+    def ApplyMany(olds, patches, device: int = -1, verdicts: bool = False):
+        """``[Patch.Apply(o, p) for o, p in zip(olds, patches)]`` in one call (dq_bspatch_apply_many): the three bzip2
+        streams of every patch are decoded on the device, the control triples are checked and scanned there and the new
+        files are produced by one streaming kernel; a patch the device cannot vouch for is applied by the host path, so
+        every result is ``Patch.Apply``'s.  Returns the new files as a list of ``bytes``, in input order; the first patch
+        the reference rejects raises ``ValueError("Corrupt patch (patch j)")``.  ``verdicts=True`` raises nothing and
+        returns ``(files, statuses, routes)`` instead: ``files[j]`` is None where ``statuses[j]`` is not 0 (-1: corrupt),
+        ``routes[j]`` is 1 where the device kernels produced the file and 0 where the host path decided."""
+        L = _abi.load()
+        olds, patches = list(olds), list(patches)
+        if len(olds) != len(patches):
+            raise ValueError(f"ApplyMany: {len(olds)} old files against {len(patches)} patches")
+        o_flat, o_off = _pack([_bytes_of(x) for x in olds]) if olds else (None, None)
+        return _apply_many(L, patches, lambda *a: L.dq_bspatch_apply_many(o_flat.ctypes.data, o_off.ctypes.data, *a, device), verdicts)

@@ -760,6 +760,40 @@ int32_t dq_bspatch_apply(const uint8_t *old_data, int64_t n, const uint8_t *patc
     }
 }
 
+int32_t dq_bspatch_new_size_many(const uint8_t *patches, const int64_t *patch_offsets, int32_t count, int64_t *new_size)
+{
+    return bspatch_new_size_many(patches, patch_offsets, count, new_size);
+}
+
+int32_t dq_bspatch_apply_many(const uint8_t *olds, const int64_t *old_offsets, const uint8_t *patches, const int64_t *patch_offsets,
+                              int32_t count, uint8_t *out, const int64_t *out_offsets, int64_t *out_len, int32_t *status,
+                              int32_t *route, int32_t device)
+{
+    EnvScope scope;
+    try {
+        if (count > 0 && (!olds || !old_offsets)) return fail(DQ_ERR_BAD_ARGS, "null buffer");
+        return bspatch_apply_many(nullptr, olds, old_offsets, patches, patch_offsets, count, out, out_offsets, out_len, status, route, device);
+    } catch (const std::bad_alloc &) {
+        return fail(DQ_ERR_OOM, "bspatch: host allocation failed");
+    } catch (const std::exception &e) {            // nothing may propagate through the C ABI
+        return fail(DQ_ERR_HIP, e.what());
+    }
+}
+
+int32_t dq_bspatch_index_apply_many(const void *index, const uint8_t *patches, const int64_t *patch_offsets, int32_t count,
+                                    uint8_t *out, const int64_t *out_offsets, int64_t *out_len, int32_t *status, int32_t *route)
+{
+    EnvScope scope;
+    try {
+        if (count > 0 && !index) return fail(DQ_ERR_BAD_ARGS, "null index");
+        return bspatch_apply_many(index, nullptr, nullptr, patches, patch_offsets, count, out, out_offsets, out_len, status, route, -1);
+    } catch (const std::bad_alloc &) {
+        return fail(DQ_ERR_OOM, "bspatch: host allocation failed");
+    } catch (const std::exception &e) {            // nothing may propagate through the C ABI
+        return fail(DQ_ERR_HIP, e.what());
+    }
+}
+
 int64_t dq_sufsort_hip_workspace_bytes(int64_t n, int32_t index_bytes)
 {
     if (n < 0) return -1;
@@ -786,7 +820,7 @@ void dq_sufsort_hip_release(void)
         std::lock_guard<std::mutex> bl(c0.batch_mu);
         std::lock_guard<std::mutex> dl(c0.diff_mu);
         bool any = c0.diff_dev || c0.diff_idx || c0.diff_pinned || c0.bslot_cap;
-        for (int k = 0; k <= kUnbz2Slot; ++k) {
+        for (int k = 0; k <= kLastSlot; ++k) {
             std::lock_guard<std::mutex> lk(g_dev[d].slot[k].mu);       // (a first use of the slot may be publishing dev right now)
             any = any || g_dev[d].slot[k].dev >= 0;
         }
@@ -805,7 +839,7 @@ void dq_sufsort_hip_release(void)
         if (c0.diff_pinned) (void)hipHostFree(c0.diff_pinned);
         c0.diff_dev = nullptr; c0.diff_idx = nullptr; c0.diff_pinned = nullptr;
         c0.diff_dev_bytes = 0; c0.diff_idx_bytes = 0;
-        for (int k = 0; k <= kUnbz2Slot; ++k) {
+        for (int k = 0; k <= kLastSlot; ++k) {
             DeviceCtx &c = g_dev[d].slot[k];
             std::lock_guard<std::mutex> lk(c.mu);
             if (c.ws) (void)hipFree(c.ws);

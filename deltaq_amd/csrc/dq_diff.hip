@@ -2215,6 +2215,16 @@ int diff_index_buffers(const void *index, const void **d_old, const void **d_sa,
     return DQ_OK;
 }
 
+int diff_index_old(const void *index, const uint8_t **old, const uint8_t **d_old, int64_t *n, int *dev)
+{
+    const DiffIndex *ix = static_cast<const DiffIndex *>(index);
+    *old = ix->old;
+    *d_old = reinterpret_cast<const uint8_t *>(ix->d_old);
+    *n = ix->n;
+    *dev = ix->dev;
+    return DQ_OK;
+}
+
 int diff_index_diff(const void *index, const uint8_t *nw, int64_t m, std::vector<uint8_t> &patch)
 {
     const DiffIndex *ix = static_cast<const DiffIndex *>(index);

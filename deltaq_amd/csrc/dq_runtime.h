@@ -126,6 +126,7 @@ struct DeviceCtx {
     int anchor_index_many_groups[2] = {0, 0};   // ... and of anchor_index_many_kernel at 256 and 512 threads (dq_anchor_many.h)
     int anchor_index_large_groups = 0;  // ... and of anchor_index_large_kernel
     int anchor_pair_large_groups[2] = {0, 0};   // ... and of anchor_pair_large_kernel without and with its one-byte table
+    int patch_apply_groups = 0;         // ... and of bspatch_apply_kernel (dq_bspatch_many.h)
     hipStream_t stream = nullptr;
     char *ws = nullptr;
     size_t ws_bytes = 0;
@@ -180,8 +181,12 @@ constexpr int kBwtSlot = kCtxSlots;
 constexpr int kBz2Slot = kCtxSlots + 1;
 // ... and one more to the decoder, dq_unbz2_hip_many* (dq_unbz2_many.h), which calls nothing that takes another context.
 constexpr int kUnbz2Slot = kCtxSlots + 2;
+// ... and the last one to dq_bspatch_apply_many* (dq_bspatch_many.h), which keeps its chunk there while the decoder inside it
+// works in its own context: its mutex is taken before the decoder's.
+constexpr int kBspatchSlot = kCtxSlots + 3;
+constexpr int kLastSlot = kBspatchSlot;
 struct DeviceState {
-    DeviceCtx slot[kCtxSlots + 3];
+    DeviceCtx slot[kLastSlot + 1];
     std::atomic<unsigned> next{0};
 };
 inline DeviceState g_dev[kMaxDevices];
@@ -692,9 +697,16 @@ int bsdiff_scan_many_host(const uint8_t *olds, const int64_t *old_offsets, const
                           int32_t device);
 int64_t bsdiff_ctrl_bound(int64_t m);
 int bspatch_apply_host(const uint8_t *old, int64_t n, const uint8_t *patch, int64_t plen, uint8_t *out, int64_t cap, int64_t *out_len);
+// Many patches applied on the device (dq_bspatch_many.h, in dq_sorter_i32.hip): the bodies of dq_bspatch_new_size_many,
+// dq_bspatch_apply_many (index null) and dq_bspatch_index_apply_many (olds, old_offsets and device unused).  No record, no
+// profile category of their own.
+int bspatch_new_size_many(const uint8_t *patches, const int64_t *patch_offsets, int32_t count, int64_t *new_size);
+int bspatch_apply_many(const void *index, const uint8_t *olds, const int64_t *old_offsets, const uint8_t *patches, const int64_t *patch_offsets,
+                       int32_t count, uint8_t *out, const int64_t *out_offsets, int64_t *out_len, int32_t *status, int32_t *route, int32_t device);
 int diff_index_new(const uint8_t *old, int64_t n, int32_t device, const void *d_old, const void *d_sa, void **index_out);
 int diff_index_clone(const void *index, int32_t device, void **index_out);
 int diff_index_buffers(const void *index, const void **d_old, const void **d_sa, int64_t *n);
+int diff_index_old(const void *index, const uint8_t **old, const uint8_t **d_old, int64_t *n, int *dev);     // the old file: host copy, device copy, device
 int diff_index_diff(const void *index, const uint8_t *nw, int64_t m, std::vector<uint8_t> &patch);
 int diff_index_many(const void *index, const uint8_t *news, const int64_t *new_offsets, int32_t count, uint8_t *patches,
                     const int64_t *patch_offsets, int64_t *patch_lens);

@@ -448,3 +448,4 @@ int sufsort_many_host(const uint8_t *texts, const int64_t *offsets, int32_t coun
 #include "dq_bwt_many.h"
 #include "dq_bz2_many.h"
 #include "dq_unbz2_many.h"
+#include "dq_bspatch_many.h"

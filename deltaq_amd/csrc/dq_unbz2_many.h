@@ -46,6 +46,8 @@
 // with A = 5 C / 4 about 7.6 C beside the rows -- in the context of kUnbz2Slot.
 #pragma once
 
+#include <functional>
+
 #include "dq_unbz2_plan.h"
 
 namespace dq {
@@ -705,10 +707,12 @@ struct Unbz2Areas {
 
 // One group: streams [0, cnt) at `src`, rel / out_rel their offsets and their slots' relative to the first; out, out_len
 // and status from the group's first slot / stream on -- host buffers (copied in and out) or device buffers (used where they
-// lie).  spacing: rows between two chase starts (kUnbz2Spacing; a measurement may ask for one start per block).  Returns
-// with st drained.
+// lie).  spacing: rows between two chase starts (kUnbz2Spacing; a measurement may ask for one start per block).  tail (a
+// caller inside the library that works on the decoded bytes where they lie, dq_bspatch_many.h): what it enqueues on st
+// behind the verdicts and in front of the one wait.  Returns with st drained.
 inline int unbz2_group(DeviceCtx &c, hipStream_t st, bool host, const uint8_t *src, const std::vector<int64_t> &rel,
-                       const std::vector<int64_t> &out_rel, int32_t cnt, int spacing, uint8_t *out, int64_t *out_len, int32_t *status)
+                       const std::vector<int64_t> &out_rel, int32_t cnt, int spacing, uint8_t *out, int64_t *out_len, int32_t *status,
+                       const std::function<int()> &tail = nullptr)
 {
     const int64_t bytes = rel[(size_t)cnt], out_bytes = out_rel[(size_t)cnt];
     if (out_bytes > kUnbz2MaxN) return fail(DQ_ERR_TOO_LARGE, "the slots of a group exceed 2^31-1 bytes");
@@ -768,6 +772,7 @@ inline int unbz2_group(DeviceCtx &c, hipStream_t st, bool host, const uint8_t *s
         }
         LAUNCH(L, DQ_K_SMALL_MANY, cnt, rows * 40,
                hipLaunchKernelGGL(unbz2_verdict_kernel, dim3((unsigned)stream_grid), dim3(kUnbz2Threads), 0, st, ba, oa));
+        if (tail) DQ_TRY(tail());
         // ---- the one wait
         FirstError last;
         if (host) {

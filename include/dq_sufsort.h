@@ -579,6 +579,54 @@ int32_t dq_bsdiff_index_scan_many(const void *index, const uint8_t *news, const 
 int32_t dq_bspatch_apply(const uint8_t *old_data, int64_t n, const uint8_t *patch, int64_t patch_len, uint8_t *out,
                          int64_t cap, int64_t *out_len);
 
+/* ---- Many BSDIFF40 patches applied on the device ------------------------------------------------------------------
+ * dq_bspatch_apply for `count` (old file, patch) pairs in one call: the three bzip2 streams of every patch are decoded by
+ * the device decoder (dq_unbz2_hip_many's kernels), the control triples are validated and scanned on the device, and the
+ * add / copy step runs as one streaming kernel.  New API, as dq_bsdiff_create_many is: the reference applies one patch
+ * per Patch.Apply call; dq_bspatch_apply is unchanged.
+ * Layout, as the other many-calls: files back to back with offsets[count + 1], offsets[0] == 0, never decreasing; patch j
+ * owns out[out_offsets[j] .. out_offsets[j + 1]), its slot, whose size is its capacity cap_j.  Host pointers only.
+ * Definition: with rc = bsdiff::apply_patch(old_j, n_j, patch_j, plen_j, slot_j, cap_j, &len) (deltaq_amd/csrc/dq_bspatch.h),
+ *   status[j] == rc: 0 ok, -1 corrupt ("Corrupt patch"), -2 buffer too small;
+ *   out_len[j] == len, the header's new size, for rc 0 and -2 (a caller can re-size); 0 for -1;
+ *   rc == 0: the slot's first len bytes are the host's, byte for byte; otherwise the slot's contents are unspecified;
+ *   nothing outside a patch's own slot is ever written, and the caller's inputs are never written.
+ * The return value is DQ_OK whenever the call ran: a patch is untrusted input, and a malformed patch is its own verdict,
+ * never a failed call.  DQ_ERR_HIP ("bspatch apply failed", "bzip2 decode failed") is only for a device-side consistency
+ * flag.  Errors, all before any device use: count < 0, a NULL pointer with count > 0 (route excepted), bad offsets in any
+ * array -> DQ_ERR_BAD_ARGS; an old file, patch or slot of 2^31 bytes or more -> DQ_ERR_TOO_LARGE.  count == 0 is a no-op.
+ * Who decides: the device only ever says "ok".  The host reads every header first (the header's own checks and the 2^21
+ * expansion bound: -1; new size above the slot: -2; neither costs device work).  Every other patch is a candidate: its
+ * streams are decoded with capacities 24 * dq_bsdiff_ctrl_bound(new_size) for the control stream -- tighter than the
+ * host's 24 * (2 * new_size + 4096), and enough for every patch this library or the reference's loop writes -- and
+ * new_size for the diff and extra streams.  A candidate is delivered by the device only if all three decode verdicts are 0
+ * and the control pass accepts it (every check of apply_streams up to and including the triple that completes the new
+ * file, triples behind it never judged).  Anything else -- a stream that is corrupt, truncated or "too long" (the host
+ * accepts such a stream and cuts it), a control violation, a seek beyond 2^40 in either direction, an old-file position
+ * above 2^62, capacities that together reach 2^31 bytes -- defers the patch: it runs apply_patch on the host, into its
+ * slot, after its chunk's device work.  Serial host work is the rare path.
+ * route (may be NULL): route[j] == 1 if the new file was produced by the device kernels, 0 if the host path decided the
+ * patch.  The only observability: there is no record, and the kernels are profiled under small_many_kernel's category.
+ *   dq_bspatch_new_size_many     host code only, no device: new_size[j] is what dq_bspatch_apply(out = NULL) reports for
+ *                                patch j, -1 where that call answers "Corrupt patch" (a bad header, the expansion bound).
+ *   dq_bspatch_apply_many        patches travel in chunks of whole patches, the decoder's rule on the candidates: decode
+ *                                capacities and stream bytes each sum to at most 64 MiB, at most 2^20 streams, and the
+ *                                chunk's old bytes to at most 64 MiB too; a patch above a limit travels alone.  Device
+ *                                memory per chunk with capacities C (about 5 bytes per new byte), S stream bytes, M new
+ *                                bytes and O old bytes: the decoder's about 8.5 C, and S + C staged, O, M of new files, 32
+ *                                bytes per possible triple (about 4 M / 3), 8 bytes per 4096 new bytes -- about 50 bytes
+ *                                per new byte in all, 650 MiB for a full chunk.  Waits per chunk: ONE, the decoder's own,
+ *                                with the control pass, the apply step and the copies back enqueued in front of it.
+ *   dq_bspatch_index_apply_many  every patch is against the index's old file: its device copy is read where it lies, its
+ *                                host copy serves the deferred patches; the device is the index's.  Same chunks without
+ *                                the old bytes; same footprint without O; same one wait. */
+int32_t dq_bspatch_new_size_many(const uint8_t *patches, const int64_t *patch_offsets, int32_t count, int64_t *new_size);
+int32_t dq_bspatch_apply_many(const uint8_t *olds, const int64_t *old_offsets, const uint8_t *patches,
+                              const int64_t *patch_offsets, int32_t count, uint8_t *out, const int64_t *out_offsets,
+                              int64_t *out_len, int32_t *status, int32_t *route, int32_t device);
+int32_t dq_bspatch_index_apply_many(const void *index, const uint8_t *patches, const int64_t *patch_offsets, int32_t count,
+                                    uint8_t *out, const int64_t *out_offsets, int64_t *out_len, int32_t *status, int32_t *route);
+
 /* ---- LDSSChecker.Check(T, SA) on the device: is sa the suffix array of text? --------------------------------------
  * = libdivsufsort's sufcheck as the reference's tests restate it (test/DeltaQ.SuffixSorting.LibDivSufSort.Tests/
  * LDSSChecker.cs:23-119), the same verdict for every (text, array) pair, decided by two passes over sa instead of the

@@ -43,6 +43,10 @@ PROTOTYPES = {                                               # export -> (restyp
     "dq_bz2_hip_many_dev": (_i32, [_vp, _vp, _i32, _i32, _i64, _vp, _vp, _vp, _i32, _vp]),
     "dq_unbz2_hip_many": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32]),
     "dq_unbz2_hip_many_dev": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "dq_bspatch_apply": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _p64]),
+    "dq_bspatch_new_size_many": (_i32, [_vp, _vp, _i32, _vp]),
+    "dq_bspatch_apply_many": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32]),
+    "dq_bspatch_index_apply_many": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "dq_bsdiff_patch_bound": (_i64, [_i64, _i64]),
     "dq_bsdiff_create": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _p64, _i32]),
     "dq_bsdiff_create_many": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32]),
