@@ -711,27 +711,21 @@ __device__ __forceinline__ void sample_kgrams(const uint8_t *__restrict__ text, 
     if (t < 8) coll[t] = (unsigned long long)cnt[t];
 }
 
-// Eighths of the text for the XCD-local first pass of the bucketed round 0 (dq_xcd_rank.h): eighth e is the text
-// positions [e E, (e + 1) E) with E = xcd_eighth(n), a whole number of that pass's tiles (so no tile straddles two),
-// a multiple of 16 bytes (so no 16-byte chunk of text_hist_kernel straddles two).  The last eighths of a short text
-// may be empty.
-constexpr int kXcds = 8;
-constexpr int kXcdTileN = 1024 * 12;
-__host__ __device__ inline int64_t xcd_eighth(int64_t n)
-{
-    const int64_t e = (n + kXcds - 1) / kXcds;
-    return (e + kXcdTileN - 1) / kXcdTileN * kXcdTileN;
-}
-
 // copy_out (round 5): the caller's device-resident text is read HERE for the first time -- the histogram pass also writes
 // the library's padded copy of it (16 bytes stored per 16 bytes loaded, behind LDS atomics that bound the kernel anyway)
 // instead of a device-to-device copy in front of the sort: 98 us of the 3.73 ms of a 256 MiB sort.
+// kLoads (round 34): every thread issues that many 16-byte loads -- trips t .. t + kLoads - 1 of hist_chunk(),
+// dq_round0_plan.h -- before it counts and stores any of them; one load per thread leaves 16 KiB in flight per CU.  A wave
+// takes a block of kLoads trips only while its last lane's last trip is in range, so on every trip the lanes of a wave
+// that are active are those of the one-load loop: the long-run ballot sees the same lanes either way.
+template <int kLoads>
 static __global__ __launch_bounds__(kBlock) void text_hist_kernel(const uint8_t *__restrict__ text, int64_t n,
                                                            unsigned long long *__restrict__ bytehist /*[256], zeroed*/,
                                                            unsigned long long *__restrict__ kgram_coll = nullptr,
                                                            uint8_t *__restrict__ copy_out = nullptr /* 16-byte aligned, or none */,
                                                            unsigned long long *__restrict__ xcd_hist = nullptr /*[8][256], zeroed*/)
 {
+    static_assert(kBlock == kHistGroupThreads, "hist_chunk() counts in workgroups of kBlock threads");
     // 4 interleaved sub-histograms (hist[d][lane & 3]) spread equal bytes over 4 banks
     __shared__ uint32_t hist[kRadixSize * 4];
     if (kgram_coll && blockIdx.x == 0) {
@@ -741,20 +735,10 @@ static __global__ __launch_bounds__(kBlock) void text_hist_kernel(const uint8_t 
     }
     const int tid = threadIdx.x;
     const int sub = tid & 3;
-    int64_t nblocks = (int64_t)gridDim.x - (kgram_coll ? 1 : 0);                // workgroups that build the histogram
-    int64_t hblock = (int64_t)blockIdx.x - (kgram_coll ? 1 : 0);
     // xcd_hist: the byte histogram of every eighth of the text too (xcd_eighth).  The workgroups are then dealt out
-    // to the eighths (nblocks / 8 each: a multiple of 8 of them), so a workgroup adds into one eighth's counters only.
-    int64_t c0 = 0, c1 = n >> 4;                         // this workgroup's chunks
-    int eighth = 0;
-    if (xcd_hist) {
-        const int64_t per = nblocks / kXcds, ech = xcd_eighth(n) >> 4;
-        eighth = (int)(hblock / per);
-        c0 = std::min(c1, eighth * ech);
-        c1 = std::min(c1, c0 + ech);
-        hblock %= per;
-        nblocks = per;
-    }
+    // to the eighths (a multiple of 8 of them), so a workgroup adds into one eighth's counters only.
+    const HistSpan sp = hist_span(n, (int64_t)blockIdx.x - (kgram_coll ? 1 : 0), (int64_t)gridDim.x - (kgram_coll ? 1 : 0),
+                                  xcd_hist != nullptr);
     for (int i = tid; i < kRadixSize * 4; i += kBlock) hist[i] = 0;
     __syncthreads();
     const uint4 *t16 = reinterpret_cast<const uint4 *>(text);      // text is 16-byte aligned
@@ -762,9 +746,7 @@ static __global__ __launch_bounds__(kBlock) void text_hist_kernel(const uint8_t 
     bool long_run = false;
     unsigned long long flat_chunks = 0;                  // 16-byte chunks made of one byte value (wave-uniform count)
     uint4 *o16 = reinterpret_cast<uint4 *>(copy_out);
-    for (int64_t i = c0 + hblock * kBlock + tid; i < c1; i += nblocks * kBlock) {
-        const uint4 v = t16[i];
-        if (copy_out) o16[i] = v;
+    auto count = [&](const uint4 &v) {
         const uint32_t wds[4] = {v.x, v.y, v.z, v.w};
         // a run of >= 64 equal bytes shows as 4 consecutive lanes whose 16 bytes are all one value (the lanes of a
         // wave hold consecutive chunks): more equal round-0 keys than one bin of the bucket pass takes
@@ -777,8 +759,28 @@ static __global__ __launch_bounds__(kBlock) void text_hist_kernel(const uint8_t 
 #pragma unroll
             for (int b = 0; b < 4; ++b) atomicAdd(&hist[(((wds[j] >> (8 * b)) & 0xff) << 2) | sub], 1u);
         }
+    };
+    const int64_t stride = hist_stride(sp);
+    int64_t trip = 0;
+    if constexpr (kLoads > 1) {
+        const int64_t wave_last = hist_chunk(sp, tid | (kWave - 1), 0);
+        for (; wave_last + (trip + kLoads - 1) * stride < sp.c1; trip += kLoads) {
+            uint4 v[kLoads];
+#pragma unroll
+            for (int q = 0; q < kLoads; ++q) v[q] = t16[hist_chunk(sp, tid, trip + q)];
+#pragma unroll
+            for (int q = 0; q < kLoads; ++q) {
+                if (copy_out) o16[hist_chunk(sp, tid, trip + q)] = v[q];
+                count(v[q]);
+            }
+        }
     }
-    if (hblock == 0 && eighth == 0) {
+    for (int64_t i = hist_chunk(sp, tid, trip); i < sp.c1; i += stride) {
+        const uint4 v = t16[i];
+        if (copy_out) o16[i] = v;
+        count(v);
+    }
+    if (sp.member == 0 && sp.eighth == 0) {
         for (int64_t i = (chunks << 4) + tid; i < n; i += kBlock) {
             const uint8_t b = text[i];
             if (copy_out) copy_out[i] = b;
@@ -794,7 +796,7 @@ static __global__ __launch_bounds__(kBlock) void text_hist_kernel(const uint8_t 
     const uint32_t c = hist[tid * 4] + hist[tid * 4 + 1] + hist[tid * 4 + 2] + hist[tid * 4 + 3];
     if (c) {
         atomicAdd(&bytehist[tid], (unsigned long long)c);
-        if (xcd_hist) atomicAdd(&xcd_hist[eighth * kRadixSize + tid], (unsigned long long)c);
+        if (xcd_hist) atomicAdd(&xcd_hist[sp.eighth * kRadixSize + tid], (unsigned long long)c);
     }
     if (kgram_coll && long_run && lane_id() == 0) atomicOr(&kgram_coll[8], 1ull);      // (wave-uniform flag)
     // kgram_coll[9]: how much of the text lies in runs -- dq_runs.h pays where that is a good part of it
@@ -805,15 +807,12 @@ static __global__ __launch_bounds__(kBlock) void text_hist_kernel(const uint8_t 
 // sub_offset (bucketed round 0, dq_xcd_rank.h): the region of digit d of place 0 cut into 8 sub-regions, one per
 // eighth of the text: sub_offset[e][d] = digit_offset[0][d] + the suffixes of eighths < e whose digit 0 is d.
 // (xcd_hist counts the bytes at the POSITIONS of an eighth; its suffixes' digits sit kb - 1 positions further on.)
-static __global__ __launch_bounds__(kBlock) void text_digit_offsets_kernel(const int64_t *__restrict__ bytehist,
-                                                                    const uint8_t *__restrict__ text,
-                                                                    int64_t n, int kb,
-                                                                    int64_t *__restrict__ digit_offset,
-                                                                    const int64_t *__restrict__ xcd_hist = nullptr /*[8][256]*/,
-                                                                    int64_t *__restrict__ sub_offset = nullptr /*[8][256]*/)
+// (the body of workgroup p: text_digit_offsets_kernel, and slot_setup_kernel of dq_slot_rank.h, which runs it beside the slot bases)
+__device__ __forceinline__ void text_digit_offsets_body(int p, const int64_t *__restrict__ bytehist, const uint8_t *__restrict__ text,
+                                                        int64_t n, int kb, int64_t *__restrict__ digit_offset,
+                                                        const int64_t *__restrict__ xcd_hist, int64_t *__restrict__ sub_offset)
 {
     __shared__ int64_t tmp[kWavesPerBlock];
-    const int p = blockIdx.x;
     const int d = threadIdx.x;
     const int64_t off = kb - 1 - p;                       // digit p of suffix i is T[i + off]
     const int64_t lead = off < n ? off : n;               // text positions < off are never a digit p
@@ -837,6 +836,41 @@ static __global__ __launch_bounds__(kBlock) void text_digit_offsets_kernel(const
             for (int64_t j = std::max(s0 + off, s1); j < s1 + off; ++j) ce += j < n ? (text[j] == d) : (d == 0);
             run += ce;
         }
+    }
+}
+
+static __global__ __launch_bounds__(kBlock) void text_digit_offsets_kernel(const int64_t *__restrict__ bytehist,
+                                                                    const uint8_t *__restrict__ text,
+                                                                    int64_t n, int kb,
+                                                                    int64_t *__restrict__ digit_offset,
+                                                                    const int64_t *__restrict__ xcd_hist = nullptr /*[8][256]*/,
+                                                                    int64_t *__restrict__ sub_offset = nullptr /*[8][256]*/)
+{
+    text_digit_offsets_body(blockIdx.x, bytehist, text, n, kb, digit_offset, xcd_hist, sub_offset);
+}
+
+// Up to three ranges zeroed by one launch (round 0's preamble: the tie bits, the first pass's tickets and cursors, the
+// slots route's): units of 16 bytes from 16-byte aligned starts, grid-stride; count 0 = no range.
+struct ZeroRanges {
+    uint4 *at[3] = {nullptr, nullptr, nullptr};
+    int64_t units[3] = {0, 0, 0};
+    // bytes, rounded up to whole units: false if the start is not 16-byte aligned
+    bool set(int r, void *p, size_t bytes)
+    {
+        at[r] = reinterpret_cast<uint4 *>(p);
+        units[r] = (int64_t)((bytes + 15) / 16);
+        return (reinterpret_cast<uintptr_t>(p) & 15) == 0;
+    }
+    int64_t total() const { return units[0] + units[1] + units[2]; }
+};
+static __global__ __launch_bounds__(kBlock) void zero_ranges_kernel(ZeroRanges r)
+{
+    const uint4 zero = {0u, 0u, 0u, 0u};
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        uint4 *const p = r.at[k];
+        for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < r.units[k]; i += stride) p[i] = zero;
     }
 }
 

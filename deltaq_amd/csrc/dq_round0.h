@@ -76,6 +76,7 @@ struct Round0 {
     static constexpr int64_t wb = (int64_t)sizeof(IdxT);
     TextStats s;                        // what text_hist_kernel saw: from prepare() on
     KeyPlan k;
+    Round0Route route;                  // the bucketed round 0 and its second pass, or none: from prepare() on
     int ib = 0;                         // bits of n - 1
     bool coded = false;
     uint64_t *K[2] = {w.K0, w.K1};      // the two key buffers; V: their suffix buffers, once kb is known (run())
@@ -121,24 +122,37 @@ struct Round0 {
         // (+1 workgroup: the k-gram sample, whose 8 counters sit right behind the byte histogram: one readback)
         LAUNCH(L, DQ_K_TEXT_HIST, n, n,
                // (text_src: the caller's device buffer, not copied yet -- this pass reads it and fills w.text, see the kernel)
-               hipLaunchKernelGGL(text_hist_kernel, dim3(blocks + 1), dim3(kBlock), 0, L.st,
+               // (DQ_HIST_LOADS=1: one 16-byte load in flight per thread, as before round 34)
+               hipLaunchKernelGGL(flags().hist_loads.value_or(kHistLoads) < kHistLoads ? text_hist_kernel<1> : text_hist_kernel<kHistLoads>,
+                                  dim3(blocks + 1), dim3(kBlock), 0, L.st,
                                   text_src ? text_src : (const uint8_t *)w.text, n, reinterpret_cast<unsigned long long *>(w.bytehist),
                                   reinterpret_cast<unsigned long long *>(w.bytehist + 256), text_src ? w.text : (uint8_t *)nullptr,
                                   xcd_hist));
         HIP_TRY(hipMemcpyAsync(c.pinned, w.bytehist, (256 + 10) * 8, hipMemcpyDeviceToHost, L.st));
         HIP_TRY(hipEventRecord(c.readback, L.st));
-        // While the host waits for the histogram and picks the key width, the device zeroes what the passes
-        // need whatever that choice is: the look-back state of the first 3 passes (all the bucketed round 0 runs;
-        // 33 MB per pass at 256 MiB) and the tie bits; the other passes' state once kb is known.
-        constexpr int kEarlyPasses = 3;
-        DQ_TRY(prepare_status<IdxT>(L, w, n, kEarlyPasses));
-        if (n >= kRound0MinN) HIP_TRY(hipMemsetAsync(w.Vb, 0, (size_t)(tie_words() + 1) * 8, L.st));
-        HIP_TRY(hipEventSynchronize(c.readback));
+        // While the host waits for the histogram and picks the key width, the device zeroes what the passes need whatever
+        // that choice is.  Short texts: the look-back state of the first 3 passes (all the bucketed round 0 runs) -- the
+        // fills hide behind the wait; the other passes' state once kb is known.  Long texts (early_status_passes: 33 MB per
+        // pass at 256 MiB, and the slots route they take reads 8 KB of it): none of it before the route is known.
+        // Then, in one launch: the tie bits, the first pass's tickets and cursors where the fill above has not zeroed them,
+        // and the slots route's (in the histogram scratch, idle until then; its other users zero what they read).
         const Flags &F = flags();
+        const int early = early_status_passes(n, F);
+        DQ_TRY(prepare_status<IdxT>(L, w, n, early));
+        if (n >= kRound0MinN) {
+            ZeroRanges z;
+            bool aligned = z.set(0, w.Vb, (size_t)(tie_words() + 1) * 8);
+            if (early == 0) aligned = z.set(1, w.ctl_status, sizeof(XcdRankCtl)) && aligned;
+            aligned = z.set(2, w.hist_partial, sizeof(SlotRankCtl)) && aligned;
+            if (!aligned || sizeof(XcdRankCtl) > w.ctl_status_bytes) return fail(DQ_ERR_HIP, "preamble ranges misplaced");
+            hipLaunchKernelGGL(zero_ranges_kernel, dim3((unsigned)std::min<int64_t>((z.total() + kBlock - 1) / kBlock, 2048)), dim3(kBlock),
+                               0, L.st, z);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipEventSynchronize(c.readback));
         s = TextStats(c.pinned, n);                     // (every later readback reuses the pinned area)
         ib = s.ib;
         k = choose_key_bytes(s, F);
-        DQ_TRY(prepare_status<IdxT>(L, w, n, k.kb, kEarlyPasses));
         bool hist_deferred = false;
         if (coded_keys_tried(s, F, k)) {
             AlphaCode code;
@@ -153,11 +167,18 @@ struct Round0 {
                 if (F.trace) fprintf(stderr, "[dq] coded round 0: %d symbols, %.2f bits per byte\n", code.sigma, code.avg_len);
             }
         }
+        // The route through the bucketed round 0, decided once (bucketed() launches it), and the look-back state it reads:
+        // zeroed early, the passes beyond the first three; deferred, nothing on the slots route behind the XCD-local first
+        // pass (whose 8 KB the launch above has zeroed), the first pass's where the plain first pass runs in front of the
+        // slots, and on every other route what an early fill would have zeroed by now -- its bbytes <= 3 passes among them.
+        route = plan_round0_route(s, F, k, coded, (int)wb, slot_span_words_of(w));
+        if (early > 0) DQ_TRY(prepare_status<IdxT>(L, w, n, k.kb, early));
+        else DQ_TRY(prepare_status<IdxT>(L, w, n, route.slots ? (route.b.xcd_pass ? 0 : 1) : std::max(k.kb, kEarlyPasses)));
         if (hist_deferred) return DQ_OK;
         // (the bucketed round 0 launches the offsets of its own digits, and digit_tables() again should it give up: the
         // offsets of the kb plain digits would be overwritten unread.  The coded keys' histogram is not text_digit_offsets_kernel
         // and stays where it was.)
-        if (!coded && plan_bucketed(s, F, k, coded, (int)wb).applies) return DQ_OK;
+        if (route.b.applies) return DQ_OK;
         return digit_tables(k.kb, coded);
     }
 
@@ -333,18 +354,17 @@ struct Round0 {
     {
         *done = false;
         const Flags &F = flags();
-        const BucketPlan b = plan_bucketed(s, F, k, coded, (int)wb);
+        const BucketPlan &b = route.b;
         if (!b.applies) return DQ_OK;
         const int kb = k.kb, keybits = b.keybits, lowbits = b.lowbits;
         // the finish kernel's tiles and geometry (plan_finish_tiles): cut every Cf words at a bucket boundary, or every g buckets;
         // and whether the second pass goes into fixed bucket slots (dq_slot_rank.h): the first pass then writes K[0], so that
         // the second can write the span that starts at K[1].  Slot bases and output places share the tile bounds' memory,
-        // tickets and cursors take the idle histogram scratch.
-        const SlotPlan sp = bucket_slots_fit(s, b, (int)wb);
-        const FinishTiles ft = plan_finish_tiles(b, n, F, sp.fits);
+        // tickets and cursors take the idle histogram scratch.  (plan_round0_route, asked by prepare())
+        const SlotPlan &sp = route.sp;
+        const FinishTiles &ft = route.ft;
         static_assert(sizeof(SlotRankCtl) <= (size_t)kHistBlocks * kMaxPasses * kRadixSize * 4, "the cursors live in the histogram scratch");
-        const bool slots = bucket_slots_wanted(sp, ft, F) && (uint64_t)sp.words <= slot_span_words_of(w) &&
-                           (size_t)(2 * kSlotBuckets + 5) * 4 <= finish_bounds_entries(n) * 8;
+        const bool slots = route.slots;
         uint32_t *slot_base = reinterpret_cast<uint32_t *>(w.bkt_bounds), *slot_out = slot_base + kSlotBuckets + 4;     // (16-byte aligned)
         SlotRankCtl *sctl = reinterpret_cast<SlotRankCtl *>(w.hist_partial);
         const int first = slots ? 0 : 1;                     // the buffer the first pass writes
@@ -352,19 +372,21 @@ struct Round0 {
         uint32_t *ebits = reinterpret_cast<uint32_t *>(w.Vb);                  // zeroed by prepare()
         TieCounters *ctr = reinterpret_cast<TieCounters *>(w.totals + 6);     // zero since run()
         BucketFlags *bflags = reinterpret_cast<BucketFlags *>(&ctr->overflow);
-        // digit p of the bucket of suffix i is T[i + bbytes - 1 - p]
-        hipLaunchKernelGGL(text_digit_offsets_kernel, dim3(b.bbytes), dim3(kBlock), 0, st,
-                           (const int64_t *)w.bytehist, (const uint8_t *)w.text, n, b.bbytes, w.digit_offset,
-                           b.xcd_pass ? (const int64_t *)(w.bytehist + kXcdHistAt) : nullptr, b.xcd_pass ? w.xcd_offset : nullptr);
-        HIP_TRY(hipGetLastError());
+        // digit p of the bucket of suffix i is T[i + bbytes - 1 - p]; the slots route: the slot bases in the same launch
+        // (its tickets and cursors were zeroed by prepare())
+        const int64_t *xcd_hist = b.xcd_pass ? (const int64_t *)(w.bytehist + kXcdHistAt) : nullptr;
+        int64_t *sub_offset = b.xcd_pass ? w.xcd_offset : nullptr;
         if (slots) {
             if (F.trace)
                 fprintf(stderr, "[dq] second pass into bucket slots: %d x %d slots of %lld words (n=%lld)\n", sp.first, sp.second,
                         (long long)b.X, (long long)n);
-            HIP_TRY(hipMemsetAsync(sctl, 0, sizeof(SlotRankCtl), st));
-            hipLaunchKernelGGL(slot_plan_kernel, dim3(kRadixSize + 1), dim3(kBlock), 0, st, (const int64_t *)w.bytehist, b.X, slot_base);
-            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(slot_setup_kernel, dim3(b.bbytes + kRadixSize + 1), dim3(kBlock), 0, st, (const int64_t *)w.bytehist,
+                               (const uint8_t *)w.text, n, b.bbytes, w.digit_offset, xcd_hist, sub_offset, b.X, slot_base);
+        } else {
+            hipLaunchKernelGGL(text_digit_offsets_kernel, dim3(b.bbytes), dim3(kBlock), 0, st, (const int64_t *)w.bytehist,
+                               (const uint8_t *)w.text, n, b.bbytes, w.digit_offset, xcd_hist, sub_offset);
         }
+        HIP_TRY(hipGetLastError());
         if (c.ncu <= 0) {
             int v = 0;
             c.ncu = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, c.dev) == hipSuccess && v > 0 ? v : 256;

@@ -12,6 +12,13 @@
 
 #include "dq_flags.h"
 
+// the few functions here that a kernel calls too (the chunks of text_hist_kernel): plain functions to the host compiler
+#if defined(__HIPCC__)
+#define DQ_HD __host__ __device__
+#else
+#define DQ_HD
+#endif
+
 namespace dq {
 
 constexpr int kKgramSamples = 1024;            // suffixes text_hist_kernel samples for repetition (dq_onesweep.h, sample_kgrams)
@@ -29,6 +36,55 @@ constexpr int64_t kCodedMinN = 8ll << 20;
 constexpr double kCodedMaxAvgLen = 5.8;       // >= 11 characters per key (a 205-symbol Python source tree: 6.17, no gain)
 constexpr int kTieSamples = 4096;             // adjacent sorted pairs sample_ties_kernel looks at for the dense guess
 constexpr int64_t kRound0MinN = 1 << 16;      // below this a text takes the plain passes, a general rebucket, no sample
+constexpr int kSlotBuckets = 1 << 16;         // 2-byte buckets of the slots route (dq_slot_rank.h)
+constexpr int kEarlyPasses = 3;               // digit passes whose look-back state is zeroed before the key width is known
+
+// Eighths of the text for the XCD-local first pass of the bucketed round 0 (dq_xcd_rank.h): eighth e is the text
+// positions [e E, (e + 1) E) with E = xcd_eighth(n), a whole number of that pass's tiles (so no tile straddles two),
+// a multiple of 16 bytes (so no 16-byte chunk of text_hist_kernel straddles two).  The last eighths of a short text
+// may be empty.
+constexpr int kXcds = 8;
+constexpr int kXcdTileN = 1024 * 12;
+DQ_HD inline int64_t xcd_eighth(int64_t n)
+{
+    const int64_t e = (n + kXcds - 1) / kXcds;
+    return (e + kXcdTileN - 1) / kXcdTileN * kXcdTileN;
+}
+
+// The 16-byte chunks of the text a workgroup of text_hist_kernel (dq_onesweep.h) reads.  Without eighths the `groups`
+// workgroups stride over all n / 16 chunks; with them (groups a multiple of 8) groups / 8 workgroups stride over the
+// chunks [c0, c1) of each eighth.  Thread tid's trip t is chunk hist_chunk(): consecutive threads hold consecutive
+// chunks on every trip, a trip is in range while its chunk is below c1, and nothing else is read by the chunk loops
+// (the last n % 16 bytes belong to workgroup 0).  tests/native/round0_preamble_harness.cpp proves the cover exact.
+constexpr int kHistGroupThreads = 256;
+constexpr int kHistLoads = 4;                  // 16-byte loads a thread keeps in flight
+struct HistSpan {
+    int64_t c0 = 0, c1 = 0;                     // the chunks of this workgroup's eighth (of the text)
+    int eighth = 0;
+    int64_t member = 0, members = 0;            // this workgroup among those that share [c0, c1)
+};
+DQ_HD inline HistSpan hist_span(int64_t n, int64_t group, int64_t groups, bool eighths)
+{
+    HistSpan h;
+    h.c1 = n >> 4;
+    h.member = group;
+    h.members = groups;
+    if (eighths) {
+        const int64_t per = groups / kXcds, ech = xcd_eighth(n) >> 4;
+        h.eighth = (int)(group / per);
+        const int64_t lo = h.eighth * ech;
+        h.c0 = lo < h.c1 ? lo : h.c1;
+        h.c1 = h.c0 + ech < h.c1 ? h.c0 + ech : h.c1;
+        h.member = group % per;
+        h.members = per;
+    }
+    return h;
+}
+DQ_HD inline int64_t hist_stride(const HistSpan &h) { return h.members * kHistGroupThreads; }
+DQ_HD inline int64_t hist_chunk(const HistSpan &h, int tid, int64_t trip)
+{
+    return h.c0 + (h.member + trip * h.members) * kHistGroupThreads + tid;
+}
 
 // bits of the largest suffix index, n - 1
 inline int index_bits(int64_t n) { return n <= 1 ? 1 : 64 - __builtin_clzll((uint64_t)(n - 1)); }
@@ -304,6 +360,81 @@ inline size_t finish_bounds_entries(int64_t n)
 {
     const size_t by_words = (size_t)n / (kBktCapFine / 2) + 4;
     return n < kRound0MinN ? by_words : std::max<size_t>(by_words, 65536 + 4);
+}
+
+// The route round 0 takes through the bucketed path, decided once: prepare() asks right after the key width and the
+// coded keys are known, bucketed() launches what the same answer says.  span_words: the words from K1 to the end of Va
+// (Workspace::slot_span_words).  slots: the second pass goes into fixed bucket slots -- the plan wants it, the slots fit
+// the span, and their bases and output places fit the tile bounds' memory.
+struct Round0Route {
+    BucketPlan b;
+    SlotPlan sp;
+    FinishTiles ft;
+    bool slots = false;
+};
+
+inline Round0Route plan_round0_route(const TextStats &s, const Flags &F, KeyPlan k, bool coded, int idx_bytes, uint64_t span_words)
+{
+    Round0Route r;
+    r.b = plan_bucketed(s, F, k, coded, idx_bytes);
+    if (!r.b.applies) return r;
+    r.sp = bucket_slots_fit(s, r.b, idx_bytes);
+    r.ft = plan_finish_tiles(r.b, s.n, F, r.sp.fits);
+    r.slots = bucket_slots_wanted(r.sp, r.ft, F) && (uint64_t)r.sp.words <= span_words &&
+              (size_t)(2 * kSlotBuckets + 5) * 4 <= finish_bounds_entries(s.n) * 8;
+    return r;
+}
+
+// Whether a text of n uniform bytes (int32 indices, no flags) gets one 2-byte bucket per fine finish tile: the cut the
+// slots route needs, taken where the room X of the longest bucket expected leaves less than X beside it in a fine tile.
+inline bool uniform_text_cut_by_bucket(int64_t n)
+{
+    int64_t words[256 + 10] = {};
+    for (int d = 0; d < 256; ++d) words[d] = n / 256 + (d < n % 256 ? 1 : 0);
+    const TextStats s(words, n);
+    const Flags none;
+    const KeyPlan k = choose_key_bytes(s, none);
+    const BucketPlan b = plan_bucketed(s, none, k, false, 4);
+    const FinishTiles t = plan_finish_tiles(b, n, none);
+    return b.applies && t.fine && t.by_id && t.g == 1;
+}
+
+// The smallest n at which uniform_text_cut_by_bucket holds, found once.  Over the multiples of 256 -- every byte value
+// n / 256 times, the longest bucket expected n / 65 536 -- the answer grows with n up to there: doubling from the smallest
+// text of the fine geometry, then halving the last step.  Between two multiples the most frequent byte occurs once more
+// than n / 256 times, which raises the estimate by what one or two more multiples of 256 would (est = cmax^2 / n lies
+// between (m + 1) / 256 and (m + 2) / 256 for 256 m < n < 256 (m + 1)): the first n of all lies at most three multiples
+// below, and is found by walking there.  0: nowhere below 2^31.
+inline int64_t slots_cut_min_n()
+{
+    static const int64_t at = [] {
+        static_assert(kBktFineMinN % 256 == 0, "the search steps in multiples of 256");
+        int64_t lo = kBktFineMinN / 256, hi = lo;
+        while (!uniform_text_cut_by_bucket(hi * 256)) {
+            lo = hi;
+            hi *= 2;
+            if (hi * 256 >= (1ll << 31)) return (int64_t)0;
+        }
+        while (hi - lo > 1) {                    // (lo: does not hold, hi: holds)
+            const int64_t mid = lo + (hi - lo) / 2;
+            if (uniform_text_cut_by_bucket(mid * 256)) hi = mid; else lo = mid;
+        }
+        for (int64_t n = std::max<int64_t>((hi - 3) * 256, kBktFineMinN); n < hi * 256; ++n)
+            if (uniform_text_cut_by_bucket(n)) return n;
+        return hi * 256;
+    }();
+    return at;
+}
+
+// Digit passes whose look-back state (33 MB per pass at 256 MiB) is zeroed while the host still waits for the histogram.
+// Short texts: kEarlyPasses -- the fills hide behind that wait.  From slots_cut_min_n() on the slots route is what a
+// random-like text takes, and it reads none of that state but the 8 KB of XcdRankCtl: nothing is zeroed early, and the
+// route, once known, zeroes what it reads (Round0::prepare).  DQ_STATUS_ZERO = 0: early at any n; 1: deferred at any n.
+inline int early_status_passes(int64_t n, const Flags &F)
+{
+    if (F.status_zero) return *F.status_zero != 0 ? 0 : kEarlyPasses;
+    const int64_t at = slots_cut_min_n();
+    return at > 0 && n >= at ? 0 : kEarlyPasses;
 }
 
 // Packed words were chosen because few ties are expected: the last pass then records the tie structure itself (1 bit per

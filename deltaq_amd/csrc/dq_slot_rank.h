@@ -28,8 +28,6 @@
 
 namespace dq {
 
-constexpr int kSlotBuckets = 1 << 16;
-
 // tickets and cursors of the pass (zeroed by the driver before every sort)
 struct SlotRankCtl {
     uint32_t ticket[kXcds];                 // next tile of the regions of each XCD
@@ -39,12 +37,11 @@ struct SlotRankCtl {
 
 // slot_base[A * 256 + B] = X * (buckets before it whose bytes both occur); byte 0 always counts as a second byte (the
 // last suffix reads the zero pad).  257 workgroups: one per first byte, the last for the end.
-static __global__ __launch_bounds__(kBlock) void slot_plan_kernel(const int64_t *__restrict__ bytehist, int64_t X,
-                                                           uint32_t *__restrict__ slot_base /*[65537]*/)
+__device__ __forceinline__ void slot_plan_body(int A, const int64_t *__restrict__ bytehist, int64_t X, uint32_t *__restrict__ slot_base /*[65537]*/)
 {
     __shared__ int tmp[kWavesPerBlock];
     __shared__ int s_rank, s_present;
-    const int d = threadIdx.x, A = blockIdx.x;
+    const int d = threadIdx.x;
     const int pa = bytehist[d] > 0 ? 1 : 0, pb = (pa || d == 0) ? 1 : 0;
     int na, nb;
     const int ra = block_excl_sum(pa, tmp, &na);
@@ -57,6 +54,24 @@ static __global__ __launch_bounds__(kBlock) void slot_plan_kernel(const int64_t 
     if (d == A) { s_rank = ra; s_present = pa; }
     __syncthreads();
     slot_base[A * kRadixSize + d] = (uint32_t)(X * ((int64_t)s_rank * nb + (s_present ? rb : 0)));
+}
+
+static __global__ __launch_bounds__(kBlock) void slot_plan_kernel(const int64_t *__restrict__ bytehist, int64_t X,
+                                                           uint32_t *__restrict__ slot_base /*[65537]*/)
+{
+    slot_plan_body(blockIdx.x, bytehist, X, slot_base);
+}
+
+// The slots route's setup in one launch: the first `places` workgroups are text_digit_offsets_kernel's (dq_onesweep.h), the
+// 257 behind them slot_plan_kernel's.  Both read only the byte histograms (and the text's first bytes).
+static __global__ __launch_bounds__(kBlock) void slot_setup_kernel(const int64_t *__restrict__ bytehist, const uint8_t *__restrict__ text,
+                                                            int64_t n, int places, int64_t *__restrict__ digit_offset,
+                                                            const int64_t *__restrict__ xcd_hist, int64_t *__restrict__ sub_offset,
+                                                            int64_t X, uint32_t *__restrict__ slot_base /*[65537]*/)
+{
+    const int g = blockIdx.x;                   // (uniform)
+    if (g < places) text_digit_offsets_body(g, bytehist, text, n, places, digit_offset, xcd_hist, sub_offset);
+    else slot_plan_body(g - places, bytehist, X, slot_base);
 }
 
 // out[b] for b = 0 .. 65 536: where bucket b = (A, B)'s suffixes go in the suffix array.  One workgroup per first byte A:

@@ -186,15 +186,25 @@ template <typename IdxT, int kMode, bool kSmall = false> struct RankCfg {
     static constexpr bool kAtomicBase = (kMode == kTextPacked || kMode == kText || kMode == kTextPackedExt);
 };
 
-// Zero the look-back state (ticket + status words) of ALL digit passes of one sort with a single
-// memset, so the passes run back to back.
+// Bytes of look-back state per digit pass of a sort of m entries (w.ctl_status_stride): every route sets it, whether or
+// not it zeroes any of that state.
 template <typename IdxT>
-int prepare_status(Launcher &L, Workspace<IdxT> &w, int64_t m, int passes, int from = 0)
+int set_status_stride(Workspace<IdxT> &w, int64_t m, int passes)
 {
     const size_t word = m < (1ll << 30) ? 4 : 8;
     const size_t stride = align_up(256 + status_tiles((size_t)m) * kRadixSize * word);
     if ((size_t)passes * stride > w.ctl_status_bytes) return fail(DQ_ERR_HIP, "status buffer too small");
     w.ctl_status_stride = stride;
+    return DQ_OK;
+}
+
+// Zero the look-back state (ticket + status words) of ALL digit passes of one sort with a single
+// memset, so the passes run back to back.
+template <typename IdxT>
+int prepare_status(Launcher &L, Workspace<IdxT> &w, int64_t m, int passes, int from = 0)
+{
+    DQ_TRY(set_status_stride<IdxT>(w, m, passes));
+    const size_t stride = w.ctl_status_stride;
     if (passes > from) HIP_TRY(hipMemsetAsync(w.ctl_status + (size_t)from * stride, 0, (size_t)(passes - from) * stride, L.st));
     return DQ_OK;
 }

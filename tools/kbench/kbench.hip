@@ -105,7 +105,7 @@ int main(int argc, char **argv)
     {
         float t_th = time_it([&]() {
             CK(hipMemsetAsync(B.bytehist, 0, 256 * 8));
-            hipLaunchKernelGGL(text_hist_kernel, dim3(kHistBlocks), dim3(kBlock), 0, 0, (const uint8_t *)B.text, m, (unsigned long long *)B.bytehist);
+            hipLaunchKernelGGL(text_hist_kernel<kHistLoads>, dim3(kHistBlocks), dim3(kBlock), 0, 0, (const uint8_t *)B.text, m, (unsigned long long *)B.bytehist);
             hipLaunchKernelGGL(text_digit_offsets_kernel, dim3(8), dim3(kBlock), 0, 0, (const int64_t *)B.bytehist, (const uint8_t *)B.text, m, 8, B.digit_offset_text); });
         printf("text hist + reduce + offsets %8.1f us\n", t_th * 1e3);
     }
