@@ -94,6 +94,28 @@ public sealed class HipSuffixSort : ISuffixSort
     private static extern unsafe int dq_last_check_many_info(long* info, int count);
 
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    private static extern unsafe int dq_lcp_hip_i32(byte* text, long n, int* sa, int* lcp, int device);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    private static extern unsafe int dq_lcp_hip_i64(byte* text, long n, long* sa, long* lcp, int device);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    private static extern unsafe int dq_lcp_hip_many_i32(byte* texts, long* offsets, int count, int* sas, int* lcps, int device);
+
+    // (declared for hosts that keep their buffers on the device: device pointers, a hipStream_t or zero)
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern int dq_lcp_hip_dev_i32(IntPtr dText, long n, IntPtr dSa, IntPtr dLcp, int device, IntPtr stream);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern int dq_lcp_hip_dev_i64(IntPtr dText, long n, IntPtr dSa, IntPtr dLcp, int device, IntPtr stream);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern int dq_lcp_hip_many_dev_i32(IntPtr dTexts, IntPtr dOffsets, int count, IntPtr dSas, IntPtr dLcps, int device, IntPtr stream);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    private static extern unsafe int dq_lcp_last_info(long* info, int count);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
     private static extern int dq_abi_version();
 
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
@@ -817,6 +839,141 @@ public sealed class HipSuffixSort : ISuffixSort
         }
 
         return info;
+    }
+
+    /// <summary>
+    /// The longest-common-prefix array of <paramref name="text"/> and its suffix array (what <c>Sort</c> returns),
+    /// computed on the device (dq_lcp_hip_i32): <c>lcp[0] = 0</c>, <c>lcp[i]</c> = the number of leading bytes the
+    /// suffixes <c>suffixes[i-1]</c> and <c>suffixes[i]</c> share.  An entry outside the text, or any other failure of
+    /// the native call, throws <see cref="InvalidOperationException"/>; there is no managed fallback.
+    /// </summary>
+    public unsafe int[] Lcp(ReadOnlySpan<byte> text, ReadOnlySpan<int> suffixes)
+    {
+        if (text.Length != suffixes.Length)
+        {
+            ThrowHelper();
+        }
+
+        var lcp = new int[text.Length];
+        int rc;
+        fixed (byte* pText = text)
+        fixed (int* pSa = suffixes)
+        fixed (int* pLcp = lcp)
+        {
+            rc = dq_lcp_hip_i32(pText, text.Length, pSa, pLcp, _device);
+        }
+
+        LcpResult(rc, "dq_lcp_hip_i32");
+        return lcp;
+    }
+
+    /// <summary>The same array for a 64-bit suffix array (texts of up to 2^32 bytes).</summary>
+    public unsafe long[] Lcp(ReadOnlySpan<byte> text, ReadOnlySpan<long> suffixes)
+    {
+        if (text.Length != suffixes.Length)
+        {
+            ThrowHelper();
+        }
+
+        var lcp = new long[text.Length];
+        int rc;
+        fixed (byte* pText = text)
+        fixed (long* pSa = suffixes)
+        fixed (long* pLcp = lcp)
+        {
+            rc = dq_lcp_hip_i64(pText, text.Length, pSa, pLcp, _device);
+        }
+
+        LcpResult(rc, "dq_lcp_hip_i64");
+        return lcp;
+    }
+
+    /// <summary>
+    /// The arrays of <see cref="Lcp(ReadOnlySpan{byte}, ReadOnlySpan{int})"/> for many (text, array) pairs in one native
+    /// call (dq_lcp_hip_many_i32): all pairs go through the same launches and the call waits for the device once.  A
+    /// pair whose lengths differ throws <see cref="ArgumentException"/> naming the pair.  The pairs are laid back to
+    /// back in managed buffers for the call, so their total is limited to what one array holds.
+    /// </summary>
+    public unsafe int[][] LcpMany(IReadOnlyList<ReadOnlyMemory<byte>> texts, IReadOnlyList<ReadOnlyMemory<int>> suffixes)
+    {
+        if (texts.Count != suffixes.Count)
+        {
+            throw new ArgumentException("LcpMany takes one suffix array per text");
+        }
+
+        long total = 0;
+        for (int j = 0; j < texts.Count; j++)
+        {
+            if (texts[j].Length != suffixes[j].Length)
+            {
+                throw new ArgumentException($"pair {j}: the text has {texts[j].Length} bytes, its suffix array {suffixes[j].Length} entries");
+            }
+
+            total += texts[j].Length;
+        }
+
+        if (total > Array.MaxLength)
+        {
+            throw new ArgumentException("the texts of one LcpMany call must total less than 2^31 bytes");
+        }
+
+        // (at least one element each: the native side wants non-null pointers whenever there are texts)
+        var offsets = new long[texts.Count + 1];
+        byte[] flat = new byte[Math.Max(total, 1)];
+        int[] sas = new int[Math.Max(total, 1)];
+        int[] lcps = new int[Math.Max(total, 1)];
+        for (int j = 0; j < texts.Count; j++)
+        {
+            texts[j].Span.CopyTo(flat.AsSpan((int)offsets[j], texts[j].Length));
+            suffixes[j].Span.CopyTo(sas.AsSpan((int)offsets[j], texts[j].Length));
+            offsets[j + 1] = offsets[j] + texts[j].Length;
+        }
+
+        int rc;
+        fixed (byte* pTexts = flat)
+        fixed (long* pOffsets = offsets)
+        fixed (int* pSas = sas)
+        fixed (int* pLcps = lcps)
+        {
+            rc = dq_lcp_hip_many_i32(pTexts, pOffsets, texts.Count, pSas, pLcps, _device);
+        }
+
+        LcpResult(rc, "dq_lcp_hip_many_i32");
+        var result = new int[texts.Count][];
+        for (int j = 0; j < texts.Count; j++)
+        {
+            result[j] = lcps.AsSpan((int)offsets[j], texts[j].Length).ToArray();
+        }
+
+        return result;
+    }
+
+    /// <summary>
+    /// Shape of the last Lcp / LcpMany on this thread (dq_lcp_last_info): irreducible positions, comparisons handed to
+    /// the wave kernel, the longest comparison's result in bytes, kernel launches, stream waits.
+    /// </summary>
+    public static unsafe long[] LastLcpInfo()
+    {
+        var info = new long[5];
+        fixed (long* p = info)
+        {
+            int rc = dq_lcp_last_info(p, info.Length);
+            if (rc != 0)
+            {
+                throw new InvalidOperationException($"dq_lcp_last_info failed ({rc})");
+            }
+        }
+
+        return info;
+    }
+
+    private static void LcpResult(int rc, string entry)
+    {
+        if (rc != 0)
+        {
+            string msg = Marshal.PtrToStringAnsi(dq_last_error()) ?? string.Empty;
+            throw new InvalidOperationException($"{entry} failed ({rc}): {msg}");
+        }
     }
 
     private static SuffixCheckResult CheckResult(int rc, int result, string entry)

@@ -59,6 +59,8 @@ EXPORTS = (
     "dq_bz2_hip_bound", "dq_bz2_hip_many", "dq_bz2_hip_many_dev", "dq_unbz2_hip_many", "dq_unbz2_hip_many_dev",
     "dq_sufcheck_hip_i32", "dq_sufcheck_hip_i64", "dq_sufcheck_hip_dev_i32", "dq_sufcheck_hip_dev_i64",
     "dq_sufcheck_hip_many_i32", "dq_sufcheck_hip_many_dev_i32", "dq_last_check_many_info",
+    "dq_lcp_hip_i32", "dq_lcp_hip_i64", "dq_lcp_hip_dev_i32", "dq_lcp_hip_dev_i64",
+    "dq_lcp_hip_many_i32", "dq_lcp_hip_many_dev_i32", "dq_lcp_last_info",
     "dq_bsdiff_search_dev_i32", "dq_bsdiff_search_dev_i64", "dq_bsdiff_search_i32", "dq_bsdiff_search_i64",
     "dq_bsdiff_create", "dq_bsdiff_patch_bound", "dq_bsdiff_scan_i32", "dq_bspatch_apply",
     "dq_bspatch_new_size_many", "dq_bspatch_apply_many", "dq_bspatch_index_apply_many",
@@ -101,6 +103,11 @@ RECORDS = {
     "dq_last_batch_info": _n("pipelined") + _ms("copy_in_ms", "sort_ms", "copy_out_ms", "slowest_share_ms")
     + _n("shares_bound_to_numa_node", "shared_launch"),
 }
+
+# ... and the record of dq_lcp_last_info, struct LcpInfo of deltaq_amd/csrc/dq_lcp_info.h, in the same form.  It stands
+# beside RECORDS, as its struct stands beside dq_call_info.h: tests/test_abi_cpu.py counts the entries of both, and
+# tests/test_lcp_cpu.py checks this pair the way that file checks those.
+LCP_RECORD = _n("irreducible", "wave_comparisons", "longest", "launches", "stream_waits")
 
 
 class BackendMissingError(RuntimeError):
@@ -170,6 +177,18 @@ def load() -> ctypes.CDLL:
     L.dq_sufcheck_hip_many_i32.argtypes = [vp, vp, i32, vp, vp, i32]
     L.dq_sufcheck_hip_many_dev_i32.restype = i32
     L.dq_sufcheck_hip_many_dev_i32.argtypes = [vp, vp, i32, vp, vp, i32, vp]
+    for name in ("dq_lcp_hip_i32", "dq_lcp_hip_i64"):
+        getattr(L, name).restype = i32
+        getattr(L, name).argtypes = [vp, i64, vp, vp, i32]
+    for name in ("dq_lcp_hip_dev_i32", "dq_lcp_hip_dev_i64"):
+        getattr(L, name).restype = i32
+        getattr(L, name).argtypes = [vp, i64, vp, vp, i32, vp]
+    L.dq_lcp_hip_many_i32.restype = i32
+    L.dq_lcp_hip_many_i32.argtypes = [vp, vp, i32, vp, vp, i32]
+    L.dq_lcp_hip_many_dev_i32.restype = i32
+    L.dq_lcp_hip_many_dev_i32.argtypes = [vp, vp, i32, vp, vp, i32, vp]
+    L.dq_lcp_last_info.restype = i32
+    L.dq_lcp_last_info.argtypes = [ctypes.POINTER(i64), i32]
     L.dq_sufsort_hip_batch_i32.restype = i32
     L.dq_sufsort_hip_batch_i32.argtypes = [i32, vp, vp, vp, i32, vp]
     L.dq_sufsort_hip_many_i32.restype = i32
@@ -368,6 +387,14 @@ def last_many_large_info() -> dict:
 def last_check_many_info() -> dict:
     """Shape of the last dq_sufcheck_hip_many_* on this thread (dq_last_check_many_info)."""
     return _read("dq_last_check_many_info")
+
+
+def last_lcp_info() -> dict:
+    """Shape of the last dq_lcp_hip_* on this thread (dq_lcp_last_info): irreducible positions, comparisons handed to the
+    wave kernel, the longest comparison's result in bytes, kernel launches, stream waits."""
+    v = (ctypes.c_int64 * len(LCP_RECORD))()
+    check(load().dq_lcp_last_info(v, len(LCP_RECORD)))
+    return {key: v[i] * scale for i, (key, scale) in enumerate(LCP_RECORD)}
 
 
 def last_batch_info() -> dict:

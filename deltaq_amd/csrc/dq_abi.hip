@@ -325,6 +325,56 @@ int32_t dq_sufcheck_hip_many_dev_i32(const void *d_texts, const void *d_offsets,
     }
 }
 
+int32_t dq_lcp_hip_i32(const uint8_t *text, int64_t n, const int32_t *sa, int32_t *lcp, int32_t device)
+{
+    EnvScope scope;
+    t_lcp_info = {};
+    return lcp_host<int32_t>(text, n, sa, lcp, device);
+}
+
+int32_t dq_lcp_hip_i64(const uint8_t *text, int64_t n, const int64_t *sa, int64_t *lcp, int32_t device)
+{
+    EnvScope scope;
+    t_lcp_info = {};
+    return lcp_host<int64_t>(text, n, sa, lcp, device);
+}
+
+int32_t dq_lcp_hip_dev_i32(const void *d_text, int64_t n, const void *d_sa, void *d_lcp, int32_t device, void *stream)
+{
+    EnvScope scope;
+    t_lcp_info = {};
+    return lcp_dev<int32_t>(d_text, n, d_sa, d_lcp, device, stream);
+}
+
+int32_t dq_lcp_hip_dev_i64(const void *d_text, int64_t n, const void *d_sa, void *d_lcp, int32_t device, void *stream)
+{
+    EnvScope scope;
+    t_lcp_info = {};
+    return lcp_dev<int64_t>(d_text, n, d_sa, d_lcp, device, stream);
+}
+
+int32_t dq_lcp_hip_many_i32(const uint8_t *texts, const int64_t *offsets, int32_t count, const int32_t *sas,
+                            int32_t *lcps, int32_t device)
+{
+    EnvScope scope;
+    t_lcp_info = {};
+    return lcp_many_host(texts, offsets, count, sas, lcps, device);
+}
+
+int32_t dq_lcp_hip_many_dev_i32(const void *d_texts, const void *d_offsets, int32_t count, const void *d_sas,
+                                void *d_lcps, int32_t device, void *stream)
+{
+    EnvScope scope;
+    t_lcp_info = {};
+    try {
+        return lcp_many_dev(d_texts, d_offsets, count, d_sas, d_lcps, device, stream);
+    } catch (const std::bad_alloc &) {             // (the host's copy of the offsets) nothing may propagate through the C ABI
+        return fail(DQ_ERR_OOM, "lcp many: host allocation failed");
+    }
+}
+
+int32_t dq_lcp_last_info(int64_t *info, int32_t count) { return last_info(t_lcp_info, info, count, "null info array"); }
+
 int32_t dq_sufsort_hip_batch_i32(int32_t count, const uint8_t *const *texts, const int64_t *lens,
                                  int32_t *const *sas, int32_t ndev, const int32_t *devs)
 {

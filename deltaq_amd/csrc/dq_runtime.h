@@ -11,6 +11,7 @@
 //       dq_sorter_impl.h                    sparse finish, doubling rounds, entry points, workspace exports
 //   dq_diff.hip                             match search, Diff.Create / Patch.Apply, the many-new-files index
 //   dq_sufcheck.hip                         LDSSChecker.Check of a suffix array on the device (dq_sufcheck.h)
+//                                           and its LCP array (dq_lcp.h, dq_lcp_host.h)
 //   dq_abi.hip                              the C ABI (include/dq_sufsort.h), the batch pipeline, profile getters
 #pragma once
 #include <hip/hip_runtime.h>
@@ -34,6 +35,7 @@
 
 #include "../../include/dq_sufsort.h"
 #include "dq_call_info.h"
+#include "dq_lcp_info.h"
 #include "dq_flags.h"
 #include "dq_work_lists.h"
 #include "dq_block_groups.h"
@@ -127,6 +129,7 @@ struct DeviceCtx {
     int anchor_index_large_groups = 0;  // ... and of anchor_index_large_kernel
     int anchor_pair_large_groups[2] = {0, 0};   // ... and of anchor_pair_large_kernel without and with its one-byte table
     int patch_apply_groups = 0;         // ... and of bspatch_apply_kernel (dq_bspatch_many.h)
+    int lcp_long_groups[2] = {0, 0};    // ... and of lcp_long_kernel with 32- and 64-bit indices (dq_lcp.h)
     hipStream_t stream = nullptr;
     char *ws = nullptr;
     size_t ws_bytes = 0;
@@ -677,6 +680,20 @@ int sufcheck_many_host(const uint8_t *texts, const int64_t *offsets, int32_t cou
                        int32_t device);
 int sufcheck_many_dev(const void *d_texts, const void *d_offsets, int32_t count, const void *d_sas, int32_t *results,
                       int32_t device, void *stream);
+
+// The LCP array of a text and its suffix array (dq_lcp_host.h, in dq_sufcheck.hip): the bodies of dq_lcp_hip_* and dq_lcp_hip_many_*.  All of
+// them fill t_lcp_info (dq_lcp_info.h); the entry point resets it.
+template <typename IdxT>
+int lcp_host(const uint8_t *text, int64_t n, const IdxT *sa, IdxT *lcp, int32_t device);
+template <typename IdxT>
+int lcp_dev(const void *d_text, int64_t n, const void *d_sa, void *d_lcp, int32_t device, void *stream);
+extern template int lcp_host<int32_t>(const uint8_t *, int64_t, const int32_t *, int32_t *, int32_t);
+extern template int lcp_host<int64_t>(const uint8_t *, int64_t, const int64_t *, int64_t *, int32_t);
+extern template int lcp_dev<int32_t>(const void *, int64_t, const void *, void *, int32_t, void *);
+extern template int lcp_dev<int64_t>(const void *, int64_t, const void *, void *, int32_t, void *);
+int lcp_many_host(const uint8_t *texts, const int64_t *offsets, int32_t count, const int32_t *sas, int32_t *lcps, int32_t device);
+int lcp_many_dev(const void *d_texts, const void *d_offsets, int32_t count, const void *d_sas, void *d_lcps, int32_t device,
+                 void *stream);
 
 // match search + BSDIFF40 (dq_diff.hip)
 int match_search_dev_i32(const void *d_old, int64_t n, const void *d_sa, const void *d_new, int64_t m, const int64_t *d_scans,

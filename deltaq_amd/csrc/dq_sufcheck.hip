@@ -8,6 +8,7 @@
 
 #include "dq_runtime.h"
 #include "dq_sufcheck_many.h"
+#include "dq_lcp_host.h"        // dq_lcp_hip_*: the LCP array, kernels (dq_lcp.h) and driver, compiled in this unit
 
 namespace dq {
 namespace {

@@ -686,6 +686,136 @@ class HipSuffixSort:
                                                           res.ctypes.data, dev, stream))
         return res
 
+    # -- the LCP array of a text and its suffix array (no counterpart in the reference) ------------------------------
+    def Lcp(self, text, suffixes, lcp=None):
+        """The longest-common-prefix array of ``text`` and its suffix array ``suffixes`` (what ``Sort`` returns), computed
+        on the device: ``lcp[0] = 0``, ``lcp[i]`` = the number of leading bytes the suffixes ``suffixes[i-1]`` and
+        ``suffixes[i]`` share.  ``_abi.last_lcp_info()`` tells what happened.
+
+        Host buffers (bytes-like / numpy uint8 text, numpy int32 / int64 suffixes) go through ``dq_lcp_hip_i32`` /
+        ``_i64`` and return a numpy array of the suffixes' dtype; torch GPU tensors stay on the device
+        (``dq_lcp_hip_dev_*``, on the current torch stream) and return a tensor.  ``lcp`` is an array to fill instead of
+        a new one (it is returned).  An entry of ``suffixes`` outside the text raises ``SuffixSortError``
+        (``DQ_ERR_BAD_ARGS``); in-range entries that are not the suffix array give unspecified values.
+        """
+        if _is_torch_tensor(text) or _is_torch_tensor(suffixes) or _is_torch_tensor(lcp):
+            return self._lcp_device(text, suffixes, lcp)
+        T = _as_text(text)
+        if not isinstance(suffixes, np.ndarray) or suffixes.dtype not in (np.int32, np.int64) or suffixes.ndim != 1:
+            raise TypeError("suffixes must be a 1-D numpy int32 or int64 array")
+        if suffixes.size != T.size:
+            raise ValueError(LENGTH_MISMATCH_MESSAGE)
+        sa = np.ascontiguousarray(suffixes)
+        if lcp is None:
+            lcp = np.empty(sa.size, dtype=sa.dtype)
+        elif not isinstance(lcp, np.ndarray) or lcp.dtype != sa.dtype or lcp.ndim != 1 or not lcp.flags.c_contiguous:
+            raise TypeError("lcp must be a contiguous 1-D numpy array of the suffixes' dtype")
+        elif lcp.size != sa.size:
+            raise ValueError(LENGTH_MISMATCH_MESSAGE)
+        fn = self._lib.dq_lcp_hip_i32 if sa.dtype == np.int32 else self._lib.dq_lcp_hip_i64
+        n = T.size
+        _abi.check(fn(T.ctypes.data if n else None, n, sa.ctypes.data if n else None, lcp.ctypes.data if n else None,
+                      self.device))
+        return lcp
+
+    lcp = Lcp
+
+    def _lcp_device(self, text, suffixes, lcp):
+        import torch
+
+        if not (_is_torch_tensor(text) and _is_torch_tensor(suffixes) and (lcp is None or _is_torch_tensor(lcp))):
+            raise TypeError("text, suffixes and lcp must all be host buffers or all torch GPU tensors")
+        if text.dtype != torch.uint8 or text.dim() != 1 or not text.is_contiguous():
+            raise TypeError("device text must be a contiguous 1-D uint8 tensor")
+        if not text.is_cuda:
+            raise TypeError("torch text tensors must live on the GPU; pass host data as bytes/numpy")
+        if suffixes.dtype not in (torch.int32, torch.int64) or suffixes.dim() != 1 or not suffixes.is_contiguous():
+            raise TypeError("suffixes must be a contiguous 1-D int32 or int64 tensor")
+        if suffixes.device != text.device:
+            raise TypeError("text and suffixes must be on the same device")
+        n = text.numel()
+        if suffixes.numel() != n:
+            raise ValueError(LENGTH_MISMATCH_MESSAGE)
+        if lcp is None:
+            lcp = torch.empty(n, dtype=suffixes.dtype, device=text.device)
+        elif lcp.dtype != suffixes.dtype or lcp.dim() != 1 or not lcp.is_contiguous() or lcp.device != text.device:
+            raise TypeError("lcp must be a contiguous 1-D tensor of the suffixes' dtype on the text's device")
+        elif lcp.numel() != n:
+            raise ValueError(LENGTH_MISMATCH_MESSAGE)
+        fn = self._lib.dq_lcp_hip_dev_i32 if suffixes.dtype == torch.int32 else self._lib.dq_lcp_hip_dev_i64
+        dev, stream = _device_and_stream(text)
+        _abi.check(fn(text.data_ptr() if n else None, n, suffixes.data_ptr() if n else None, lcp.data_ptr() if n else None,
+                      dev, stream))
+        return lcp
+
+    # -- the LCP arrays of many (text, array) pairs in one call: the same launches for all of them -------------------
+    def LcpMany(self, texts, suffixes):
+        """The arrays of ``Lcp`` for many pairs, all through the same launches and one wait.
+
+        ``LcpMany([t0, t1, ...], [sa0, sa1, ...])`` -- bytes-like objects / numpy uint8 arrays and numpy int32 arrays, two
+        equally long lists -- returns a list of int32 arrays, each what ``Lcp(t, sa)`` returns
+        (``dq_lcp_hip_many_i32``).  ``LcpMany((texts_tensor, offsets_tensor), sas_tensor)`` -- torch GPU tensors in
+        ``SortMany``'s device layout -- returns ONE int32 device tensor in the same layout
+        (``dq_lcp_hip_many_dev_i32``, on the current torch stream).
+        """
+        if isinstance(texts, tuple) and len(texts) == 2 and _is_torch_tensor(texts[0]):
+            return self._lcp_many_device(texts[0], texts[1], suffixes)
+        arrs = [_as_text(t) for t in texts]
+        sas = list(suffixes)
+        if len(sas) != len(arrs):
+            raise ValueError("LcpMany takes one suffix array per text")
+        if any(a.ndim != 1 for a in arrs):
+            raise TypeError("every text must be one-dimensional")
+        if any(not isinstance(s, np.ndarray) or s.dtype != np.int32 or s.ndim != 1 for s in sas):
+            raise TypeError("every suffix array must be a 1-D numpy int32 array")
+        for j, (a, s) in enumerate(zip(arrs, sas)):
+            if a.size != s.size:
+                raise ValueError(f"pair {j}: the text has {a.size} bytes, its suffix array {s.size} entries")
+        if any(a.size > INT_MAX for a in arrs):
+            raise ValueError("LcpMany has 32-bit indices: every text must be shorter than 2^31 bytes")
+        count = len(arrs)
+        off = np.zeros(count + 1, dtype=np.int64)
+        if count:
+            np.cumsum([a.size for a in arrs], out=off[1:])
+        total = int(off[-1])
+        # (a buffer of no bytes has no address: the library wants non-null pointers whenever there are texts)
+        flat = np.concatenate(arrs) if total else np.zeros(1, np.uint8)
+        flat_sa = np.concatenate(sas) if total else np.zeros(1, np.int32)
+        lcps = np.empty(max(total, 1), dtype=np.int32)
+        _abi.check(self._lib.dq_lcp_hip_many_i32(flat.ctypes.data, off.ctypes.data, count, flat_sa.ctypes.data,
+                                                 lcps.ctypes.data, self.device))
+        return [lcps[off[j]:off[j + 1]] for j in range(count)]
+
+    lcp_many = LcpMany
+
+    def _lcp_many_device(self, texts, offsets, sas):
+        import torch
+
+        if not _is_torch_tensor(offsets) or not _is_torch_tensor(sas):
+            raise TypeError("device texts need device offsets and suffix array tensors")
+        if texts.dtype != torch.uint8 or texts.dim() != 1 or not texts.is_contiguous():
+            raise TypeError("device texts must be a contiguous 1-D uint8 tensor")
+        if offsets.dtype != torch.int64 or offsets.dim() != 1 or not offsets.is_contiguous() or offsets.numel() < 1:
+            raise TypeError("offsets must be a contiguous 1-D int64 tensor of count + 1 entries")
+        if sas.dtype != torch.int32 or sas.dim() != 1 or not sas.is_contiguous():
+            raise TypeError("suffixes must be a contiguous 1-D int32 tensor")
+        if not texts.is_cuda or offsets.device != texts.device or sas.device != texts.device:
+            raise TypeError("texts, offsets and suffixes must live on the same GPU")
+        if sas.numel() != texts.numel():
+            raise ValueError("suffixes must have one entry per text byte")
+        count = offsets.numel() - 1
+        total = texts.numel()
+        lcps = torch.empty(total, dtype=torch.int32, device=texts.device)
+        if count == 0:
+            return lcps
+        dev, stream = _device_and_stream(texts)
+        tp = texts if total else torch.zeros(1, dtype=torch.uint8, device=texts.device)
+        sp = sas if total else torch.zeros(1, dtype=torch.int32, device=texts.device)
+        lp = lcps if total else torch.zeros(1, dtype=torch.int32, device=texts.device)
+        _abi.check(self._lib.dq_lcp_hip_many_dev_i32(tp.data_ptr(), offsets.data_ptr(), count, sp.data_ptr(), lp.data_ptr(),
+                                                     dev, stream))
+        return lcps
+
 
 def _device_and_stream(t):
     """(device ordinal, stream handle) for work on tensor t's device, on torch's current stream."""

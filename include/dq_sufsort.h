@@ -698,6 +698,48 @@ int32_t dq_sufcheck_hip_many_dev_i32(const void *d_texts, const void *d_offsets,
                                      int32_t *results, int32_t device, void *stream);
 int32_t dq_last_check_many_info(int64_t *info, int32_t count);
 
+/* ---- the LCP array of a text and its suffix array, on the device ----------------------------------------------------
+ * For a text T of n bytes and its suffix array sa (what dq_sufsort_hip_* returns): lcp[0] = 0, and for 1 <= i < n lcp[i]
+ * is the number of leading bytes the suffixes at sa[i-1] and sa[i] have in common.  A suffix ends at the end of its
+ * text; no sentinel takes part in the comparison.  n == 0 is a no-op, n == 1 gives {0}.  lcp has the index type of sa;
+ * every value is at most n - 1.  The call only reads text and sa; it writes the n entries of lcp and nothing else.
+ * Computed through the permuted LCP array (Kaerkkaeinen, Manzini, Puglisi 2009; deltaq_amd/csrc/dq_lcp.h): Phi[sa[i]] =
+ * sa[i-1] is scattered with a flag for the IRREDUCIBLE positions -- s of rank 0, s == 0, Phi[s] == 0 or
+ * T[s-1] != T[Phi[s]-1] --, only those compare bytes, every other position is PLCP[s-1] - 1, and lcp[i] = PLCP[sa[i]].
+ *   NULL buffer with n > 0, negative n                  DQ_ERR_BAD_ARGS
+ *   i32: n > 2^31-1; any form: n > 2^32                 DQ_ERR_TOO_LARGE (all before any device work)
+ * Untrusted arrays: an entry becomes an address only after its range test, so any entry values are safe.  An entry
+ * outside [0, n) -- [0, n_j) in the many form -- makes the call return DQ_ERR_BAD_ARGS (dq_last_error says so) and
+ * leaves lcp undefined.  An in-range array that is not the suffix array gives DQ_OK and unspecified values in [0, n],
+ * and no access outside the call's buffers.
+ * Device memory, carved from the cached workspace of the slot the call leases: 16 bytes per byte of text with 32-bit
+ * indices (Phi 4, PLCP 4, the list of long comparisons 8), 17 with 64-bit indices, 8 bytes per 1024 bytes of text and a
+ * line of counters; the host forms add their device copies of text, sa and lcp.  No CPU fallback: DQ_ERR_OOM when that
+ * does not fit.  The _dev_ forms take device pointers on `device`, enqueue on `stream` (NULL = the library's stream)
+ * and return after it has drained.  One stream wait per call.
+ * The many forms take dq_sufsort_hip_many_i32's layout: the texts back to back, offsets[count + 1] (int64, offsets[0] ==
+ * 0, never decreasing), sas and lcps in the same layout with entries counted from the start of their own text.  Segment
+ * j of lcps is exactly what dq_lcp_hip_i32 writes for text j alone; nothing outside the segments is written.  All
+ * texts of a call go through the same launches (one text is the many form with one segment).  The total may exceed
+ * 2^31 bytes, each text stays below 2^31.  Errors as dq_sufcheck_hip_many_*: count < 0, a NULL pointer with count > 0,
+ * offsets[0] != 0, decreasing offsets -> DQ_ERR_BAD_ARGS; a text of 2^31 bytes or more -> DQ_ERR_TOO_LARGE; count == 0
+ * is a no-op.  The host form sends the whole call to the device at once; the device form fetches d_offsets once to
+ * check it before it launches anything (that fetch is not among the waits counted below).
+ * No text above 2^31 bytes has been run: the tests stop at 2^20 + 1 bytes.
+ * dq_lcp_last_info: shape of the last of these calls on this thread, reset when one starts; `count` entries (5 are
+ * defined, further ones read 0; a NULL array is DQ_ERR_BAD_ARGS): [0] irreducible positions; [1] comparisons still
+ * undecided after a lane's own bytes, handed to the wave kernel; [2] the longest comparison's result in bytes;
+ * [3] kernel launches; [4] stream waits. */
+int32_t dq_lcp_hip_i32(const uint8_t *text, int64_t n, const int32_t *sa, int32_t *lcp, int32_t device);
+int32_t dq_lcp_hip_i64(const uint8_t *text, int64_t n, const int64_t *sa, int64_t *lcp, int32_t device);
+int32_t dq_lcp_hip_dev_i32(const void *d_text, int64_t n, const void *d_sa, void *d_lcp, int32_t device, void *stream);
+int32_t dq_lcp_hip_dev_i64(const void *d_text, int64_t n, const void *d_sa, void *d_lcp, int32_t device, void *stream);
+int32_t dq_lcp_hip_many_i32(const uint8_t *texts, const int64_t *offsets, int32_t count, const int32_t *sas,
+                            int32_t *lcps, int32_t device);
+int32_t dq_lcp_hip_many_dev_i32(const void *d_texts, const void *d_offsets, int32_t count, const void *d_sas,
+                                void *d_lcps, int32_t device, void *stream);
+int32_t dq_lcp_last_info(int64_t *info, int32_t count);
+
 /* Device workspace (bytes) a sort of n bytes with index_bytes (4 or 8) wide indices needs,
  * excluding the caller's text and sa buffers: the device entry point's full layout (the reduced one at n = 2^32). */
 int64_t dq_sufsort_hip_workspace_bytes(int64_t n, int32_t index_bytes);

@@ -62,6 +62,10 @@ PROTOTYPES = {                                               # export -> (restyp
     "dq_profile_get": (_i32, [_i32, _vp, _vp, _vp, _vp]),
     "dq_last_many_info": _INFO, "dq_last_diff_many_info": _INFO, "dq_last_diff_large_info": _INFO,
     "dq_last_index_many_info": _INFO, "dq_last_index_large_info": _INFO, "dq_last_check_many_info": _INFO,
+    "dq_sufsort_hip_dev_i32": (_i32, [_vp, _i64, _vp, _i32, _vp]),
+    "dq_lcp_hip_dev_i32": (_i32, [_vp, _i64, _vp, _vp, _i32, _vp]),
+    "dq_lcp_hip_many_dev_i32": (_i32, [_vp, _vp, _i32, _vp, _vp, _i32, _vp]),
+    "dq_lcp_last_info": _INFO,
 }
 
 
