@@ -116,6 +116,22 @@ public sealed class HipSuffixSort : ISuffixSort
     private static extern unsafe int dq_lcp_last_info(long* info, int count);
 
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    private static extern unsafe int dq_lpf_hip_i32(int* sa, int* lcp, long n, int* lpf, int* src, int device);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    private static extern unsafe int dq_lz77_hip_i32(byte* text, long n, int* sa, int* lcp, int* phrases, long cap, long* count, int device);
+
+    // (declared for hosts that keep their buffers on the device: device pointers, a hipStream_t or zero; count is host memory)
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern int dq_lpf_hip_dev_i32(IntPtr dSa, IntPtr dLcp, long n, IntPtr dLpf, IntPtr dSrc, int device, IntPtr stream);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern unsafe int dq_lz77_hip_dev_i32(IntPtr dText, long n, IntPtr dSa, IntPtr dLcp, IntPtr dPhrases, long cap, long* count, int device, IntPtr stream);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    private static extern unsafe int dq_lz77_last_info(long* info, int count);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
     private static extern int dq_abi_version();
 
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
@@ -961,6 +977,131 @@ public sealed class HipSuffixSort : ISuffixSort
             if (rc != 0)
             {
                 throw new InvalidOperationException($"dq_lcp_last_info failed ({rc})");
+            }
+        }
+
+        return info;
+    }
+
+    /// <summary>
+    /// The longest-previous-factor array of a text from its suffix array and LCP array (what <c>Sort</c> and <c>Lcp</c>
+    /// return), computed on the device (dq_lpf_hip_i32): <c>Lpf[i]</c> is the length of the longest match of position i
+    /// with an earlier position, <c>Src[i]</c> where that match starts (-1 where the length is 0; on a tie the
+    /// lexicographically smaller neighbour).  A match may overlap its own copy.  There is no managed fallback.
+    /// </summary>
+    public unsafe (int[] Lpf, int[] Src) Lpf(ReadOnlySpan<int> suffixes, ReadOnlySpan<int> lcp)
+    {
+        if (suffixes.Length != lcp.Length)
+        {
+            ThrowHelper();
+        }
+
+        var lpf = new int[suffixes.Length];
+        var src = new int[suffixes.Length];
+        int rc;
+        fixed (int* pSa = suffixes)
+        fixed (int* pLcp = lcp)
+        fixed (int* pLpf = lpf)
+        fixed (int* pSrc = src)
+        {
+            rc = dq_lpf_hip_i32(pSa, pLcp, suffixes.Length, pLpf, pSrc, _device);
+        }
+
+        LcpResult(rc, "dq_lpf_hip_i32");
+        return (lpf, src);
+    }
+
+    /// <summary>
+    /// The greedy LZ77 factorization of <paramref name="text"/> (dq_lz77_hip_i32), three ints a phrase:
+    /// (start, len, src) for a copy of len bytes from position src -- it may overlap its own output --, (start, 0, byte)
+    /// for a literal.  <see cref="Lz77Decode"/> turns the phrases back into the text.  The output is sized by a first
+    /// native call with no room.
+    /// </summary>
+    public unsafe int[] Lz77(ReadOnlySpan<byte> text, ReadOnlySpan<int> suffixes, ReadOnlySpan<int> lcp)
+    {
+        if (text.Length != suffixes.Length || text.Length != lcp.Length)
+        {
+            ThrowHelper();
+        }
+
+        long count = 0;
+        int rc;
+        fixed (byte* pText = text)
+        fixed (int* pSa = suffixes)
+        fixed (int* pLcp = lcp)
+        {
+            rc = dq_lz77_hip_i32(pText, text.Length, pSa, pLcp, null, 0, &count, _device);
+            LcpResult(rc, "dq_lz77_hip_i32");
+            var phrases = new int[checked(3 * count)];
+            fixed (int* pPhrases = phrases)
+            {
+                rc = dq_lz77_hip_i32(pText, text.Length, pSa, pLcp, count > 0 ? pPhrases : null, count, &count, _device);
+            }
+
+            LcpResult(rc, "dq_lz77_hip_i32");
+            return phrases;
+        }
+    }
+
+    /// <summary>The factorization of a text alone: <c>Sort</c>, <c>Lcp</c> and <c>Lz77</c>.</summary>
+    public int[] Lz77(ReadOnlySpan<byte> text)
+    {
+        var suffixes = new int[text.Length];
+        Sort(text, suffixes);
+        return Lz77(text, suffixes, Lcp(text, suffixes));
+    }
+
+    /// <summary>The text of a factorization, copied byte by byte where a copy overlaps what it writes.</summary>
+    public static byte[] Lz77Decode(ReadOnlySpan<int> phrases)
+    {
+        if (phrases.Length % 3 != 0)
+        {
+            throw new ArgumentException("phrases are three ints each");
+        }
+
+        var text = new List<byte>();
+        for (int k = 0; k < phrases.Length; k += 3)
+        {
+            int start = phrases[k], len = phrases[k + 1], third = phrases[k + 2];
+            if (start != text.Count)
+            {
+                throw new ArgumentException($"phrase at {start} does not start where the one before it ends ({text.Count})");
+            }
+
+            if (len == 0)
+            {
+                text.Add((byte)third);
+                continue;
+            }
+
+            if (third < 0 || third >= start)
+            {
+                throw new ArgumentException($"phrase at {start} copies from {third}");
+            }
+
+            for (int j = 0; j < len; j++)
+            {
+                text.Add(text[third + j]);
+            }
+        }
+
+        return text.ToArray();
+    }
+
+    /// <summary>
+    /// Shape of the last Lpf / Lz77 on this thread (dq_lz77_last_info): phrases, literal phrases (both 0 after Lpf), the
+    /// longest lpf value (Lpf) or phrase (Lz77), ranks handed to the wave kernel, serial hops of the tile walker, kernel
+    /// launches, stream waits.
+    /// </summary>
+    public static unsafe long[] LastLz77Info()
+    {
+        var info = new long[7];
+        fixed (long* p = info)
+        {
+            int rc = dq_lz77_last_info(p, info.Length);
+            if (rc != 0)
+            {
+                throw new InvalidOperationException($"dq_lz77_last_info failed ({rc})");
             }
         }
 

@@ -61,6 +61,7 @@ EXPORTS = (
     "dq_sufcheck_hip_many_i32", "dq_sufcheck_hip_many_dev_i32", "dq_last_check_many_info",
     "dq_lcp_hip_i32", "dq_lcp_hip_i64", "dq_lcp_hip_dev_i32", "dq_lcp_hip_dev_i64",
     "dq_lcp_hip_many_i32", "dq_lcp_hip_many_dev_i32", "dq_lcp_last_info",
+    "dq_lpf_hip_i32", "dq_lpf_hip_dev_i32", "dq_lz77_hip_i32", "dq_lz77_hip_dev_i32", "dq_lz77_last_info",
     "dq_bsdiff_search_dev_i32", "dq_bsdiff_search_dev_i64", "dq_bsdiff_search_i32", "dq_bsdiff_search_i64",
     "dq_bsdiff_create", "dq_bsdiff_patch_bound", "dq_bsdiff_scan_i32", "dq_bspatch_apply",
     "dq_bspatch_new_size_many", "dq_bspatch_apply_many", "dq_bspatch_index_apply_many",
@@ -108,6 +109,10 @@ RECORDS = {
 # beside RECORDS, as its struct stands beside dq_call_info.h: tests/test_abi_cpu.py counts the entries of both, and
 # tests/test_lcp_cpu.py checks this pair the way that file checks those.
 LCP_RECORD = _n("irreducible", "wave_comparisons", "longest", "launches", "stream_waits")
+
+# ... and the record of dq_lz77_last_info, struct Lz77Info of deltaq_amd/csrc/dq_lz77_info.h, likewise beside RECORDS;
+# tests/test_lz77_cpu.py checks this pair.
+LZ77_RECORD = _n("phrases", "literals", "longest", "wave_ranks", "walker_hops", "launches", "stream_waits")
 
 
 class BackendMissingError(RuntimeError):
@@ -189,6 +194,16 @@ def load() -> ctypes.CDLL:
     L.dq_lcp_hip_many_dev_i32.argtypes = [vp, vp, i32, vp, vp, i32, vp]
     L.dq_lcp_last_info.restype = i32
     L.dq_lcp_last_info.argtypes = [ctypes.POINTER(i64), i32]
+    L.dq_lpf_hip_i32.restype = i32
+    L.dq_lpf_hip_i32.argtypes = [vp, vp, i64, vp, vp, i32]
+    L.dq_lpf_hip_dev_i32.restype = i32
+    L.dq_lpf_hip_dev_i32.argtypes = [vp, vp, i64, vp, vp, i32, vp]
+    L.dq_lz77_hip_i32.restype = i32
+    L.dq_lz77_hip_i32.argtypes = [vp, i64, vp, vp, vp, i64, ctypes.POINTER(i64), i32]
+    L.dq_lz77_hip_dev_i32.restype = i32
+    L.dq_lz77_hip_dev_i32.argtypes = [vp, i64, vp, vp, vp, i64, ctypes.POINTER(i64), i32, vp]
+    L.dq_lz77_last_info.restype = i32
+    L.dq_lz77_last_info.argtypes = [ctypes.POINTER(i64), i32]
     L.dq_sufsort_hip_batch_i32.restype = i32
     L.dq_sufsort_hip_batch_i32.argtypes = [i32, vp, vp, vp, i32, vp]
     L.dq_sufsort_hip_many_i32.restype = i32
@@ -395,6 +410,15 @@ def last_lcp_info() -> dict:
     v = (ctypes.c_int64 * len(LCP_RECORD))()
     check(load().dq_lcp_last_info(v, len(LCP_RECORD)))
     return {key: v[i] * scale for i, (key, scale) in enumerate(LCP_RECORD)}
+
+
+def last_lz77_info() -> dict:
+    """Shape of the last dq_lpf_hip_* / dq_lz77_hip_* on this thread (dq_lz77_last_info): phrases and literal phrases (0 in
+    LPF calls), the longest lpf value (LPF calls) or phrase (LZ77 calls), ranks handed to the wave kernel, serial hops of
+    the tile walker, kernel launches, stream waits."""
+    v = (ctypes.c_int64 * len(LZ77_RECORD))()
+    check(load().dq_lz77_last_info(v, len(LZ77_RECORD)))
+    return {key: v[i] * scale for i, (key, scale) in enumerate(LZ77_RECORD)}
 
 
 def last_batch_info() -> dict:

@@ -375,6 +375,38 @@ int32_t dq_lcp_hip_many_dev_i32(const void *d_texts, const void *d_offsets, int3
 
 int32_t dq_lcp_last_info(int64_t *info, int32_t count) { return last_info(t_lcp_info, info, count, "null info array"); }
 
+int32_t dq_lpf_hip_i32(const int32_t *sa, const int32_t *lcp, int64_t n, int32_t *lpf, int32_t *src, int32_t device)
+{
+    EnvScope scope;
+    t_lz77_info = {};
+    return lpf_host(sa, lcp, n, lpf, src, device);
+}
+
+int32_t dq_lpf_hip_dev_i32(const void *d_sa, const void *d_lcp, int64_t n, void *d_lpf, void *d_src, int32_t device, void *stream)
+{
+    EnvScope scope;
+    t_lz77_info = {};
+    return lpf_dev(d_sa, d_lcp, n, d_lpf, d_src, device, stream);
+}
+
+int32_t dq_lz77_hip_i32(const uint8_t *text, int64_t n, const int32_t *sa, const int32_t *lcp, int32_t *phrases, int64_t cap,
+                        int64_t *count, int32_t device)
+{
+    EnvScope scope;
+    t_lz77_info = {};
+    return lz77_host(text, n, sa, lcp, phrases, cap, count, device);
+}
+
+int32_t dq_lz77_hip_dev_i32(const void *d_text, int64_t n, const void *d_sa, const void *d_lcp, void *d_phrases, int64_t cap,
+                            int64_t *count, int32_t device, void *stream)
+{
+    EnvScope scope;
+    t_lz77_info = {};
+    return lz77_dev(d_text, n, d_sa, d_lcp, d_phrases, cap, count, device, stream);
+}
+
+int32_t dq_lz77_last_info(int64_t *info, int32_t count) { return last_info(t_lz77_info, info, count, "null info array"); }
+
 int32_t dq_sufsort_hip_batch_i32(int32_t count, const uint8_t *const *texts, const int64_t *lens,
                                  int32_t *const *sas, int32_t ndev, const int32_t *devs)
 {

@@ -1,0 +1,621 @@
+// dq_lz77.h -- the longest-previous-factor array (with a source) and the greedy LZ77 factorization of a text from its
+// suffix array and LCP array, on the device (after Shun & Zhao, "Practical parallel Lempel-Ziv factorization", DCC 2013:
+// nearest smaller values on SA, range minima of LCP, then the phrases).
+//
+// For the rank r of position i = SA[r]: p = SA[r'] for the nearest r' < r with SA[r'] < i, common(i, p) = min
+// LCP[r'+1 .. r]; q = SA[r''] for the nearest r'' > r with SA[r''] < i, common(i, q) = min LCP[r+1 .. r''];
+// lpf[i] = the larger, src[i] = p on a tie, -1 where lpf[i] == 0 (include/dq_sufsort.h has the contract).
+//
+// Every phase is a launch of its own on one stream; the kernel boundary is all that carries data between workgroups:
+//   lpf_levels_kernel     level k holds, per group of 64^k ranks, the minimum of SA and the minimum of LCP; one launch
+//                         per level, until at most 64 groups remain.  The fan-out is the wave width: one ballot finds
+//                         the nearest group that qualifies.  Level 1 range-tests SA.
+//   lpf_tile_scan_kernel  one workgroup: per tile of kLpfTile ranks the minimum of SA over all tiles before it and over
+//                         all tiles behind it (from level 1)
+//   lpf_tile_kernel       a tile of ranks in LDS as (SA, LCP) pairs, one rank per lane: each lane walks left and right
+//                         with the running minimum of LCP, four pairs in flight, until an entry below its own.  A side
+//                         decided in the tile is final; one that reaches the edge is "none" if the prefix (suffix)
+//                         minimum says nothing smaller lies beyond -- the SA of a run of one byte is decreasing, no rank
+//                         has a left neighbour, and without this test all of them would queue --, otherwise the rank
+//                         goes on the list with what is known: into the tile's own stretch of it, [r0, r0 + tile_cnt),
+//                         so no counter is shared between workgroups
+//   lpf_long_kernel       persistent grid, one wave per listed rank (a wave claims 16 tiles' stretches at a time):
+//                         climbs the levels while the groups' minimum of SA does not undercut the value, folding their
+//                         minima of LCP, then descends by ballots
+//   (both of them scatter lpf[SA[r]], src[SA[r]] where both sides are known)
+//   lz_exit_kernel        per tile of kLzTile positions: next[i] = i + clamp(lpf[i], 1, n - i) in LDS, pointer jumping
+//                         until every position holds its first hop out of the tile
+//   lz_walk_kernel        one lane: follows the exits from position 0, writes each visited tile's entry position (the
+//                         others keep -1, "skipped"): n / kLzTile dependent loads, the serial part
+//   lz_mark_kernel        per tile: one lane walks next[] in LDS from the entry and sets a bit per phrase start
+//   lz_scan_kernel        one workgroup: the tiles' counts -> offsets, and z
+//   lz_emit_kernel        per tile: the triples of the marked positions at their offsets, below cap only
+//
+// Untrusted arrays.  An entry of SA is range-tested wherever it is read and one outside [0, n) takes part as "never
+// smaller" (kLpfNone) and is never an address; level 1 raises kLzOutOfRange for the host.  LCP values are clamped to
+// [0, n] where they are read.  The parse clamps every step to [1, n - i], so next[] strictly increases: the pointer
+// jumping, the walker (which besides forces every hop out of its tile) and the marking walk are bounded whatever lpf
+// holds.  List entries and tile entries are positions these kernels computed; they are tested all the same.
+//
+// Scratch per byte of text: the list 4 + 16 (rank; both sides' neighbour and minimum), the levels 8/63, 12 bytes per
+// tile of ranks: 20.2 bytes for an LPF call.  An LZ77 call adds lpf 4 + src 4 + one bit per position + 8 bytes per tile
+// of positions (the exits reuse the list): 28.3 bytes.  And one 256-byte line of counters.
+#pragma once
+#include "dq_device_utils.h"
+#include "dq_lz77_info.h"
+
+namespace dq {
+
+// UNMEASURED starting values (tools/kbench/lz77.py measures the calls; none of these has been swept):
+constexpr int kLpfFan = kWave;                   // groups per group of the next level: one ballot decides a level
+constexpr int kLpfTile = kBlock;                 // ranks per tile of lpf_tile_kernel: one rank per lane
+constexpr int kLzTile = 8192;                    // positions per tile of the parse: next[] takes 32 KiB of LDS
+// (the grid of lpf_long_kernel, UNMEASURED too: as many workgroups as the occupancy query says the device holds at once)
+constexpr int kLzPer = kLzTile / kBlock;         // positions per thread: 32, one word of the phrase bitmap
+constexpr int kLzJumpRounds = 14;                // 2^13 hops cross a tile; one more round sees that nothing changes
+constexpr int kLpfMaxLevels = 6;                 // 64^6 > 2^31
+constexpr int kLpfPer = 4;                       // tiles per thread and step of the one-workgroup scans
+constexpr int kLpfClaim = 16;                    // tiles of ranks a wave of lpf_long_kernel claims at a time
+constexpr int kLpfPad = 4;                       // pairs a lane of lpf_tile_kernel has in flight, and stoppers on each side of the tile
+static_assert(kLpfFan == 64 && kLpfTile % kLpfFan == 0 && kLzPer == 32 && (1 << (kLzJumpRounds - 1)) >= kLzTile);
+
+constexpr int32_t kLpfNone = 0x7fffffff;         // "no entry": above every position (n <= 2^31 - 1)
+constexpr int32_t kLpfPending = -2;              // a side of a listed rank that the wave kernel has to find
+constexpr uint32_t kLzOutOfRange = 1u;
+
+// the call's line of device counters, zeroed before the first launch and read back behind the one wait
+struct LzCounters {
+    unsigned long long list_len;                 // ranks on the list, summed by the waves of lpf_long_kernel
+    unsigned long long claimed;                  // tiles of ranks claimed by them
+    unsigned long long hops;                     // hops of lz_walk_kernel
+    uint32_t phrases, literals;
+    uint32_t longest_lpf, longest_phrase;
+    uint32_t flags;                              // kLzOutOfRange
+};
+static_assert(sizeof(LzCounters) <= 256);
+
+// the minima hierarchy: [0] is the caller's SA / LCP (untrusted: read through lpf_sa_at / lpf_lcp_at), [k] the minima
+// of level k, cnt[k] = ceil(n / 64^k) entries; `top` is the last level, of at most 64 entries
+struct LpfLevels {
+    const int32_t *sa[kLpfMaxLevels + 1];
+    const int32_t *lcp[kLpfMaxLevels + 1];
+    int64_t cnt[kLpfMaxLevels + 1];
+    int top;
+};
+
+inline int64_t lpf_tiles(int64_t n) { return (n + kLpfTile - 1) / kLpfTile; }
+inline int64_t lz_tiles(int64_t n) { return (n + kLzTile - 1) / kLzTile; }
+
+__device__ __forceinline__ int32_t lpf_sa_value(int32_t x, int64_t n) { return x >= 0 && (int64_t)x < n ? x : kLpfNone; }
+__device__ __forceinline__ int32_t lpf_lcp_value(int32_t x, int64_t n) { return x < 0 ? 0 : ((int64_t)x > n ? (int32_t)n : x); }
+__device__ __forceinline__ int32_t lpf_sa_at(const LpfLevels &L, int k, int64_t idx, int64_t n)
+{
+    const int32_t x = L.sa[k][idx];
+    return k == 0 ? lpf_sa_value(x, n) : x;
+}
+__device__ __forceinline__ int32_t lpf_lcp_at(const LpfLevels &L, int k, int64_t idx, int64_t n)
+{
+    const int32_t x = L.lcp[k][idx];
+    return k == 0 ? lpf_lcp_value(x, n) : x;
+}
+
+__device__ __forceinline__ int32_t lpf_wave_min(int32_t v)
+{
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) {
+        const int32_t t = __shfl_xor(v, o, kWave);
+        v = t < v ? t : v;
+    }
+    return v;
+}
+
+__device__ __forceinline__ uint64_t lz_readlane64(uint64_t v, int lane)
+{
+    return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), lane) << 32) |
+           (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, lane);
+}
+
+// a maximum among the counters: the atomic only where the value read says it would raise it (the word only grows, so a
+// stale read costs an atomic and never loses a maximum)
+__device__ __forceinline__ void lz_raise(uint32_t *word, uint32_t v)
+{
+    if (v > __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+        __hip_atomic_fetch_max(word, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// the tie rule: the lexicographically smaller neighbour p wins a tie; a missing neighbour has nothing in common
+__device__ __forceinline__ void lpf_combine(int32_t pl, int32_t cl, int32_t pr, int32_t cr, int32_t *lpf, int32_t *src)
+{
+    if (pl < 0) cl = 0;
+    if (pr < 0) cr = 0;
+    const bool left = cl >= cr;
+    *lpf = left ? cl : cr;
+    *src = *lpf == 0 ? -1 : (left ? pl : pr);
+}
+
+// ---------------------------------------------------------------------------------------------- the minima hierarchy
+// One wave per entry of the level written: the minima of its 64 entries of the level below (raw: the caller's arrays).
+__global__ __launch_bounds__(kBlock) void lpf_levels_kernel(const int32_t *__restrict__ in_sa, const int32_t *__restrict__ in_lcp,
+                                                            int64_t in_cnt, int raw, int64_t n, int32_t *__restrict__ out_sa,
+                                                            int32_t *__restrict__ out_lcp, LzCounters *ctr)
+{
+    const int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x;      // (a wave's 64 entries are one group)
+    int32_t a = kLpfNone, b = kLpfNone;
+    bool outside = false;
+    if (idx < in_cnt) {
+        a = in_sa[idx];
+        b = in_lcp[idx];
+        if (raw) {
+            outside = a < 0 || (int64_t)a >= n;
+            a = lpf_sa_value(a, n);
+            b = lpf_lcp_value(b, n);
+        }
+    }
+    a = lpf_wave_min(a);
+    b = lpf_wave_min(b);
+    if (lane_id() == 0 && idx < in_cnt) {
+        out_sa[idx / kLpfFan] = a;
+        out_lcp[idx / kLpfFan] = b;
+    }
+    if (__ballot(outside) && lane_id() == 0) __hip_atomic_fetch_or(&ctr->flags, kLzOutOfRange, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// pre[t] = the minimum of SA over the tiles before t, suf[t] = over the tiles behind t (kLpfNone: none), from level 1
+// (kLpfTile / 64 entries a tile).  One workgroup walks the tiles forwards, then backwards, kLpfPer * kBlock at a step,
+// carrying the minimum: plain scans, nothing waits for another workgroup.
+__global__ __launch_bounds__(kBlock) void lpf_tile_scan_kernel(const int32_t *__restrict__ l1_sa, int64_t cnt1, int64_t tiles,
+                                                               int32_t *__restrict__ pre, int32_t *__restrict__ suf)
+{
+    __shared__ int32_t s_tmp[kWavesPerBlock];
+    __shared__ int32_t s_carry;
+    constexpr int kPerTile = kLpfTile / kLpfFan;
+    for (int dir = 0; dir < 2; ++dir) {
+        int32_t *out = dir ? suf : pre;
+        __syncthreads();
+        if (threadIdx.x == 0) s_carry = -1;                                  // (block_excl_max's form: kLpfNone - value)
+        __syncthreads();
+        for (int64_t t0 = 0; t0 < tiles; t0 += (int64_t)kBlock * kLpfPer) {
+            const int64_t at = t0 + (int64_t)threadIdx.x * kLpfPer;
+            int32_t v[kLpfPer], own = -1;
+#pragma unroll
+            for (int k = 0; k < kLpfPer; ++k) {
+                const int64_t t = dir ? tiles - 1 - (at + k) : at + k;      // the k-th tile of this thread in scan order
+                int32_t m = kLpfNone;
+                if (at + k < tiles) {
+#pragma unroll
+                    for (int u = 0; u < kPerTile; ++u) {
+                        const int64_t e = t * kPerTile + u;
+                        const int32_t x = e < cnt1 ? l1_sa[e] : kLpfNone;
+                        m = x < m ? x : m;
+                    }
+                }
+                v[k] = kLpfNone - m;                                         // larger = smaller minimum; none: 0
+                own = at + k < tiles && v[k] > own ? v[k] : own;
+            }
+            const int32_t carry = s_carry;
+            int32_t run = block_excl_max(own, s_tmp);                        // (its barrier: everybody has read s_carry)
+            run = carry > run ? carry : run;
+#pragma unroll
+            for (int k = 0; k < kLpfPer; ++k) {
+                const int64_t t = dir ? tiles - 1 - (at + k) : at + k;
+                if (at + k < tiles) {
+                    out[t] = run < 0 ? kLpfNone : kLpfNone - run;
+                    run = v[k] > run ? v[k] : run;
+                }
+            }
+            if (threadIdx.x == kBlock - 1) s_carry = run;
+            __syncthreads();                                                 // s_tmp and s_carry before the next step
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- the tile pass
+__global__ __launch_bounds__(kBlock) void lpf_tile_kernel(const int32_t *__restrict__ SA, const int32_t *__restrict__ LCP, int64_t n,
+                                                          const int32_t *__restrict__ pre, const int32_t *__restrict__ suf,
+                                                          int32_t *__restrict__ lpf, int32_t *__restrict__ src,
+                                                          int32_t *__restrict__ list_r, int4 *__restrict__ list_q,
+                                                          int32_t *__restrict__ tile_cnt, LzCounters *ctr)
+{
+    __shared__ int s_cnt[kWavesPerBlock];
+    // (SA, LCP) pairs of the tile's ranks between kLpfPad stoppers on each side -- and in place of the ranks beyond the
+    // text --: an entry below every position ends any walk, its LCP is neutral for the minimum; no index is clamped
+    __shared__ int2 s_pair[kLpfTile + 2 * kLpfPad];
+    const int t = (int)threadIdx.x;
+    const int64_t r0 = (int64_t)blockIdx.x * kLpfTile, r = r0 + t;
+    int32_t v = -1, l = kLpfNone;
+    if (r < n) {
+        v = lpf_sa_value(SA[r], n);
+        l = lpf_lcp_value(LCP[r], n);
+    }
+    s_pair[kLpfPad + t] = make_int2(v, l);
+    if (t < kLpfPad) {
+        s_pair[t] = make_int2(-1, kLpfNone);
+        s_pair[kLpfPad + kLpfTile + t] = make_int2(-1, kLpfNone);
+    }
+    __syncthreads();
+    const int cnt = (int)(n - r0 < kLpfTile ? n - r0 : kLpfTile);
+    const bool valid = r < n && v != kLpfNone;
+    int32_t pl = -1, cl = 0, pr = -1, cr = 0;
+    bool pending = false;
+    if (valid) {
+        // to the left: ranks (at, r] are folded into m; four pairs in flight
+        int32_t m = l;
+        int j = kLpfPad + t - 1, at = -1;
+        while (at < 0) {
+            int2 e[kLpfPad];
+#pragma unroll
+            for (int u = 0; u < kLpfPad; ++u) e[u] = s_pair[j - u];            // (j - u >= 0: a stopper ends the walk before)
+#pragma unroll
+            for (int u = 0; u < kLpfPad; ++u) {
+                if (at < 0) {
+                    if (e[u].x < v) at = j - u;
+                    else m = e[u].y < m ? e[u].y : m;
+                }
+            }
+            j -= kLpfPad;
+        }
+        if (at >= kLpfPad) { pl = s_pair[at].x; cl = m; }
+        else if (pre[blockIdx.x] < v) { pl = kLpfPending; cl = m; pending = true; }
+        // to the right: ranks (r, at] are folded, the one that ends the walk included
+        m = kLpfNone;
+        j = kLpfPad + t + 1;
+        at = -1;
+        while (at < 0) {
+            int2 e[kLpfPad];
+#pragma unroll
+            for (int u = 0; u < kLpfPad; ++u) e[u] = s_pair[j + u];            // (j + u < kLpfTile + 2 kLpfPad, likewise)
+#pragma unroll
+            for (int u = 0; u < kLpfPad; ++u) {
+                if (at < 0) {
+                    m = e[u].y < m ? e[u].y : m;
+                    if (e[u].x < v) at = j + u;
+                }
+            }
+            j += kLpfPad;
+        }
+        if (at < kLpfPad + cnt) { pr = s_pair[at].x; cr = m; }
+        else if (r0 + kLpfTile < n && suf[blockIdx.x] < v) { pr = kLpfPending; cr = m; pending = true; }
+    }
+    uint32_t longest = 0;
+    if (valid && !pending) {
+        int32_t f, s;
+        lpf_combine(pl, cl, pr, cr, &f, &s);
+        lpf[v] = f;
+        src[v] = s;
+        longest = (uint32_t)f;
+    }
+    // The tile's listed ranks go to the front of the tile's own stretch of the list, [r0, r0 + tile_cnt): no counter is
+    // shared between workgroups (an atomic per wave on one address was what the whole grid waited for).
+    const uint64_t mask = __ballot(pending);
+    if (lane_id() == 0) s_cnt[t >> 6] = __builtin_popcountll(mask);
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int i = 0; i < kWavesPerBlock; ++i) {
+        const int c = s_cnt[i];
+        before += i < (t >> 6) ? c : 0;
+        total += c;
+    }
+    if (pending) {                                                           // (listed ranks are ranks of the text: at < r0 + cnt <= n)
+        const int64_t at = r0 + before + mask_rank_lt(mask);
+        list_r[at] = (int32_t)r;
+        list_q[at] = make_int4(pl, cl, pr, cr);
+    }
+    if (t == 0) tile_cnt[blockIdx.x] = total;
+    longest = wave_max(longest);
+    if (lane_id() == 0) lz_raise(&ctr->longest_lpf, longest);
+}
+
+// ---------------------------------------------------------------------------------------------- the wave kernel
+// The nearest rank below tile start c (a multiple of kLpfTile; ranks [c, r] are folded into *m) whose entry is below v.
+// Called by the whole wave with wave-uniform arguments.  Level k is looked at from entry ck = c / 64^k leftwards to the
+// start of ck's group of the next level (the top level: to 0); nothing there: fold, go up.  Returns the entry (-1: none).
+__device__ __forceinline__ int32_t lpf_wave_left(const LpfLevels &L, int64_t n, int64_t c, int32_t v, int32_t *m_io)
+{
+    const int lane = lane_id();
+    int32_t m = *m_io;
+    int k = 1;
+    int64_t ck = c / kLpfFan, g = -1;
+    for (; k <= L.top; ++k) {
+        const int64_t base = k == L.top ? 0 : (ck / kLpfFan) * kLpfFan;
+        const int64_t idx = base + lane;
+        const bool in = idx < ck && idx < L.cnt[k];
+        const int32_t a = in ? L.sa[k][idx] : kLpfNone, b = in ? L.lcp[k][idx] : kLpfNone;
+        const uint64_t hit = __ballot(in && a < v);
+        if (hit) {
+            const int hi = 63 - __builtin_clzll(hit);
+            m = min(m, lpf_wave_min(lane > hi ? b : kLpfNone));
+            g = base + hi;
+            break;
+        }
+        m = min(m, lpf_wave_min(b));
+        if (base == 0) return -1;
+        ck = base / kLpfFan;
+    }
+    if (g < 0) return -1;
+    int32_t found = -1;
+    while (k > 0) {                                                          // into group g of level k: its 64 entries of level k - 1
+        --k;
+        const int64_t idx = g * kLpfFan + lane;
+        const bool in = idx < L.cnt[k];
+        const int32_t a = in ? lpf_sa_at(L, k, idx, n) : kLpfNone, b = in ? lpf_lcp_at(L, k, idx, n) : kLpfNone;
+        const uint64_t hit = __ballot(in && a < v);
+        if (!hit) return -1;                                                 // (the level above said there is one)
+        const int hi = 63 - __builtin_clzll(hit);
+        m = min(m, lpf_wave_min(lane > hi ? b : kLpfNone));
+        g = g * kLpfFan + hi;
+        found = __builtin_amdgcn_readlane(a, hi);
+    }
+    *m_io = m;
+    return found;
+}
+
+// ... and the nearest rank at or behind tile end c (ranks (r, c) are folded) whose entry is below v; its own LCP value
+// belongs to the minimum.
+__device__ __forceinline__ int32_t lpf_wave_right(const LpfLevels &L, int64_t n, int64_t c, int32_t v, int32_t *m_io)
+{
+    const int lane = lane_id();
+    int32_t m = *m_io;
+    if (c >= n) return -1;
+    int k = 1;
+    int64_t ck = c / kLpfFan, g = -1;
+    for (; k <= L.top; ++k) {
+        const int64_t cntk = L.cnt[k];
+        const int64_t up = (ck + kLpfFan - 1) / kLpfFan * kLpfFan;
+        const int64_t end = k == L.top || up > cntk ? cntk : up;
+        const int64_t idx = ck + lane;
+        const bool in = idx < end;
+        const int32_t a = in ? L.sa[k][idx] : kLpfNone, b = in ? L.lcp[k][idx] : kLpfNone;
+        const uint64_t hit = __ballot(in && a < v);
+        if (hit) {
+            const int lo = __builtin_ctzll(hit);
+            m = min(m, lpf_wave_min(lane < lo ? b : kLpfNone));
+            g = ck + lo;
+            break;
+        }
+        m = min(m, lpf_wave_min(b));
+        if (end >= cntk) return -1;
+        ck = end / kLpfFan;
+    }
+    if (g < 0) return -1;
+    int32_t found = -1;
+    while (k > 0) {
+        --k;
+        const int64_t idx = g * kLpfFan + lane;
+        const bool in = idx < L.cnt[k];
+        const int32_t a = in ? lpf_sa_at(L, k, idx, n) : kLpfNone, b = in ? lpf_lcp_at(L, k, idx, n) : kLpfNone;
+        const uint64_t hit = __ballot(in && a < v);
+        if (!hit) return -1;
+        const int lo = __builtin_ctzll(hit);
+        m = min(m, lpf_wave_min(lane < lo || (k == 0 && lane == lo) ? b : kLpfNone));
+        g = g * kLpfFan + lo;
+        found = __builtin_amdgcn_readlane(a, lo);
+    }
+    *m_io = m;
+    return found;
+}
+
+// A fixed grid; each wave takes kLpfClaim tiles' stretches of the list through ctr->claimed until none is left.  Nobody
+// waits for anybody: a grid of any size is correct.
+__global__ __launch_bounds__(kBlock) void lpf_long_kernel(LpfLevels L, int64_t n, const int32_t *__restrict__ list_r,
+                                                          const int4 *__restrict__ list_q, const int32_t *__restrict__ tile_cnt,
+                                                          int32_t *__restrict__ lpf, int32_t *__restrict__ src, LzCounters *ctr)
+{
+    const unsigned long long tiles = (unsigned long long)((n + kLpfTile - 1) / kLpfTile);
+    const int lane = lane_id();
+    uint32_t longest = 0;
+    unsigned long long listed = 0;
+    for (;;) {
+        unsigned long long first = 0;
+        if (lane == 0) first = __hip_atomic_fetch_add(&ctr->claimed, (unsigned long long)kLpfClaim, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        first = lz_readlane64(first, 0);
+        if (first >= tiles) break;                                           // (uniform: the whole wave leaves)
+        const int have = (int)(tiles - first < (unsigned long long)kLpfClaim ? tiles - first : (unsigned long long)kLpfClaim);
+        const int32_t my_cnt = lane < have ? tile_cnt[first + lane] : 0;
+        for (int k = 0; k < have; ++k) {
+            const int64_t r0 = (int64_t)(first + k) * kLpfTile;
+            int c = __builtin_amdgcn_readlane(my_cnt, k);
+            const int room = (int)(n - r0 < kLpfTile ? n - r0 : kLpfTile);
+            c = c < 0 ? 0 : (c > room ? room : c);                           // (what lpf_tile_kernel wrote; tested all the same)
+            listed += (unsigned long long)c;
+            // 64 entries at a time: every lane loads one of them and its rank's SA entry, the wave takes them in turn
+            for (int b = 0; b < c; b += kWave) {
+                const int held = c - b < kWave ? c - b : kWave;
+                int32_t my_r = -1, my_v = kLpfNone;
+                int4 my_q = make_int4(-1, 0, -1, 0);
+                if (lane < held) {
+                    my_r = list_r[r0 + b + lane];
+                    my_q = list_q[r0 + b + lane];
+                    if (my_r >= 0 && (int64_t)my_r < n) my_v = lpf_sa_value(L.sa[0][my_r], n);
+                }
+                for (int e = 0; e < held; ++e) {
+                    const int32_t v = __builtin_amdgcn_readlane(my_v, e);
+                    if (v == kLpfNone) continue;                             // (a rank outside, or an entry outside: neither is listed)
+                    const int64_t r = __builtin_amdgcn_readlane(my_r, e);
+                    int32_t pl = __builtin_amdgcn_readlane(my_q.x, e), cl = __builtin_amdgcn_readlane(my_q.y, e);
+                    int32_t pr = __builtin_amdgcn_readlane(my_q.z, e), cr = __builtin_amdgcn_readlane(my_q.w, e);
+                    const int64_t c0 = r / kLpfTile * kLpfTile;
+                    if (pl == kLpfPending) pl = lpf_wave_left(L, n, c0, v, &cl);
+                    if (pr == kLpfPending) pr = lpf_wave_right(L, n, c0 + kLpfTile, v, &cr);
+                    int32_t f, s;
+                    lpf_combine(pl, cl, pr, cr, &f, &s);
+                    if (lane == 0) {
+                        lpf[v] = f;
+                        src[v] = s;
+                    }
+                    longest = (uint32_t)f > longest ? (uint32_t)f : longest;
+                }
+            }
+        }
+    }
+    if (lane == 0) {
+        if (listed) __hip_atomic_fetch_add(&ctr->list_len, listed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        lz_raise(&ctr->longest_lpf, longest);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- the parse
+// next[] of tile t0 .. into LDS: i + clamp(lpf[i], 1, n - i) for the positions of the text, n for the rest of the tile
+__device__ __forceinline__ void lz_load_next(const int32_t *__restrict__ lpf, int64_t n, int64_t t0, int32_t *s_next)
+{
+#pragma unroll 4
+    for (int k = 0; k < kLzPer; ++k) {
+        const int at = k * kBlock + (int)threadIdx.x;
+        const int64_t i = t0 + at;
+        int64_t nx = n;
+        if (i < n) {
+            const int64_t f = lpf[i];
+            nx = i + (f < 1 ? 1 : (f > n - i ? n - i : f));
+        }
+        s_next[at] = (int32_t)nx;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void lz_exit_kernel(const int32_t *__restrict__ lpf, int64_t n, int32_t *__restrict__ exits)
+{
+    __shared__ int32_t s_next[kLzTile];
+    const int64_t t0 = (int64_t)blockIdx.x * kLzTile;
+    const int64_t e64 = t0 + kLzTile < n ? t0 + kLzTile : n;
+    const int32_t e = (int32_t)e64, b0 = (int32_t)t0;
+    lz_load_next(lpf, n, t0, s_next);
+    __syncthreads();
+    // synchronous pointer jumping: after round k an entry is 2^k hops ahead or out of the tile; reads, barrier, writes
+    for (int round = 0; round < kLzJumpRounds; ++round) {
+        int32_t nv[kLzPer];
+        bool moved = false;
+#pragma unroll
+        for (int k = 0; k < kLzPer; ++k) {
+            const int32_t j = s_next[k * kBlock + (int)threadIdx.x];
+            const bool inside = j < e;                                       // (then b0 < j: next[] increases)
+            nv[k] = inside ? s_next[j - b0] : j;
+            moved = moved || inside;
+        }
+        if (!__syncthreads_or(moved)) break;                                 // (uniform; and every read is over)
+#pragma unroll
+        for (int k = 0; k < kLzPer; ++k) s_next[k * kBlock + (int)threadIdx.x] = nv[k];
+        __syncthreads();
+    }
+#pragma unroll 4
+    for (int k = 0; k < kLzPer; ++k) {
+        const int at = k * kBlock + (int)threadIdx.x;
+        if (t0 + at < n) exits[t0 + at] = s_next[at];
+    }
+}
+
+// One lane.  entry[] was filled with -1.  Every hop leaves its tile (forced, whatever exits[] holds), so there are at
+// most lz_tiles(n) hops.
+__global__ __launch_bounds__(kWave) void lz_walk_kernel(const int32_t *__restrict__ exits, int64_t n, int32_t *__restrict__ entry,
+                                                        LzCounters *ctr)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    int64_t pos = 0;
+    unsigned long long hops = 0;
+    while (pos < n) {
+        const int64_t t = pos / kLzTile;
+        entry[t] = (int32_t)pos;
+        const int64_t edge = (t + 1) * kLzTile;
+        int64_t nx = exits[pos];
+        nx = nx < edge ? edge : nx;
+        pos = nx > n ? n : nx;
+        ++hops;
+    }
+    ctr->hops = hops;
+}
+
+__global__ __launch_bounds__(kBlock) void lz_mark_kernel(const int32_t *__restrict__ lpf, int64_t n, const int32_t *__restrict__ entry,
+                                                         uint32_t *__restrict__ bits, uint32_t *__restrict__ tile_count)
+{
+    __shared__ int32_t s_next[kLzTile];
+    __shared__ uint32_t s_bits[kBlock];
+    const int64_t t0 = (int64_t)blockIdx.x * kLzTile;
+    const int64_t e = t0 + kLzTile < n ? t0 + kLzTile : n;
+    const int64_t first = entry[blockIdx.x];
+    s_bits[threadIdx.x] = 0;
+    const bool visited = first >= t0 && first < e;                           // (uniform) -1: the phrases jump over this tile
+    if (visited) lz_load_next(lpf, n, t0, s_next);
+    __syncthreads();
+    if (visited && threadIdx.x == 0) {
+        uint32_t count = 0;
+        int64_t pos = first;
+        while (pos < e) {                                                    // next[] increases: at most kLzTile steps
+            const int at = (int)(pos - t0);
+            s_bits[at >> 5] |= 1u << (at & 31);
+            pos = s_next[at];
+            ++count;
+        }
+        tile_count[blockIdx.x] = count;
+    }
+    if (!visited && threadIdx.x == 0) tile_count[blockIdx.x] = 0;
+    __syncthreads();
+    bits[(int64_t)blockIdx.x * kBlock + threadIdx.x] = s_bits[threadIdx.x];
+}
+
+// tile_count[t] -> the number of phrases that start before tile t, in place; the total is z.  One workgroup.
+__global__ __launch_bounds__(kBlock) void lz_scan_kernel(uint32_t *__restrict__ tile_count, int64_t tiles, LzCounters *ctr)
+{
+    __shared__ uint32_t s_tmp[kWavesPerBlock];
+    __shared__ uint32_t s_carry;
+    if (threadIdx.x == 0) s_carry = 0;
+    __syncthreads();
+    for (int64_t t0 = 0; t0 < tiles; t0 += (int64_t)kBlock * kLpfPer) {
+        const int64_t at = t0 + (int64_t)threadIdx.x * kLpfPer;
+        uint32_t v[kLpfPer], own = 0;
+#pragma unroll
+        for (int k = 0; k < kLpfPer; ++k) {
+            v[k] = at + k < tiles ? tile_count[at + k] : 0;
+            own += v[k];
+        }
+        const uint32_t carry = s_carry;
+        uint32_t total;
+        uint32_t run = carry + block_excl_sum(own, s_tmp, &total);           // (its barrier: everybody has read s_carry)
+#pragma unroll
+        for (int k = 0; k < kLpfPer; ++k) {
+            if (at + k < tiles) tile_count[at + k] = run;
+            run += v[k];
+        }
+        __syncthreads();                                                     // s_tmp is read; s_carry may change
+        if (threadIdx.x == 0) s_carry = carry + total;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) ctr->phrases = s_carry;
+}
+
+// A thread owns the 32 positions of one bitmap word.  A copy is (i, len, src[i]), a literal (i, 0, T[i]); only the
+// triples below cap are written, all of them are counted.
+__global__ __launch_bounds__(kBlock) void lz_emit_kernel(const uint8_t *__restrict__ T, const int32_t *__restrict__ lpf,
+                                                         const int32_t *__restrict__ src, int64_t n, const uint32_t *__restrict__ bits,
+                                                         const uint32_t *__restrict__ tile_off, int32_t *__restrict__ phrases,
+                                                         int64_t cap, LzCounters *ctr)
+{
+    __shared__ uint32_t s_tmp[kWavesPerBlock];
+    uint32_t word = bits[(int64_t)blockIdx.x * kBlock + threadIdx.x];
+    const int64_t i0 = (int64_t)blockIdx.x * kLzTile + (int64_t)threadIdx.x * kLzPer;
+    uint32_t total;
+    int64_t at = (int64_t)tile_off[blockIdx.x] + block_excl_sum((uint32_t)__builtin_popcount(word), s_tmp, &total);
+    uint32_t literals = 0, longest = 0;
+    while (word) {
+        const int64_t i = i0 + __builtin_ctz(word);
+        word &= word - 1;
+        if (i < n) {                                                         // (a set bit is a position of the text)
+            const int64_t f = lpf[i];
+            const int32_t len = (int32_t)(f < 0 ? 0 : (f > n - i ? n - i : f));
+            const int32_t third = len ? src[i] : (int32_t)T[i];
+            literals += len == 0;
+            longest = (uint32_t)(len ? len : 1) > longest ? (uint32_t)(len ? len : 1) : longest;
+            if (at < cap) {
+                phrases[3 * at] = (int32_t)i;
+                phrases[3 * at + 1] = len;
+                phrases[3 * at + 2] = third;
+            }
+        }
+        ++at;
+    }
+    literals = wave_sum(literals);
+    longest = wave_max(longest);
+    if (lane_id() == 0) {
+        if (literals) __hip_atomic_fetch_add(&ctr->literals, literals, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        lz_raise(&ctr->longest_phrase, longest);
+    }
+}
+
+}  // namespace dq

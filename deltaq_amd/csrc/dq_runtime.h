@@ -11,7 +11,8 @@
 //       dq_sorter_impl.h                    sparse finish, doubling rounds, entry points, workspace exports
 //   dq_diff.hip                             match search, Diff.Create / Patch.Apply, the many-new-files index
 //   dq_sufcheck.hip                         LDSSChecker.Check of a suffix array on the device (dq_sufcheck.h)
-//                                           and its LCP array (dq_lcp.h, dq_lcp_host.h)
+//                                           and its LCP array (dq_lcp.h, dq_lcp_host.h), and what the two arrays
+//                                           give together: LPF and the LZ77 factorization (dq_lz77.h, dq_lz77_host.h)
 //   dq_abi.hip                              the C ABI (include/dq_sufsort.h), the batch pipeline, profile getters
 #pragma once
 #include <hip/hip_runtime.h>
@@ -36,6 +37,7 @@
 #include "../../include/dq_sufsort.h"
 #include "dq_call_info.h"
 #include "dq_lcp_info.h"
+#include "dq_lz77_info.h"
 #include "dq_flags.h"
 #include "dq_work_lists.h"
 #include "dq_block_groups.h"
@@ -130,6 +132,7 @@ struct DeviceCtx {
     int anchor_pair_large_groups[2] = {0, 0};   // ... and of anchor_pair_large_kernel without and with its one-byte table
     int patch_apply_groups = 0;         // ... and of bspatch_apply_kernel (dq_bspatch_many.h)
     int lcp_long_groups[2] = {0, 0};    // ... and of lcp_long_kernel with 32- and 64-bit indices (dq_lcp.h)
+    int lpf_long_groups = 0;            // ... and of lpf_long_kernel (dq_lz77.h)
     hipStream_t stream = nullptr;
     char *ws = nullptr;
     size_t ws_bytes = 0;
@@ -694,6 +697,15 @@ extern template int lcp_dev<int64_t>(const void *, int64_t, const void *, void *
 int lcp_many_host(const uint8_t *texts, const int64_t *offsets, int32_t count, const int32_t *sas, int32_t *lcps, int32_t device);
 int lcp_many_dev(const void *d_texts, const void *d_offsets, int32_t count, const void *d_sas, void *d_lcps, int32_t device,
                  void *stream);
+
+// The LPF array and the LZ77 factorization from SA and LCP (dq_lz77_host.h, in dq_sufcheck.hip): the bodies of
+// dq_lpf_hip_* and dq_lz77_hip_*.  All of them fill t_lz77_info (dq_lz77_info.h); the entry point resets it.
+int lpf_host(const int32_t *sa, const int32_t *lcp, int64_t n, int32_t *lpf, int32_t *src, int32_t device);
+int lpf_dev(const void *d_sa, const void *d_lcp, int64_t n, void *d_lpf, void *d_src, int32_t device, void *stream);
+int lz77_host(const uint8_t *text, int64_t n, const int32_t *sa, const int32_t *lcp, int32_t *phrases, int64_t cap, int64_t *count,
+              int32_t device);
+int lz77_dev(const void *d_text, int64_t n, const void *d_sa, const void *d_lcp, void *d_phrases, int64_t cap, int64_t *count,
+             int32_t device, void *stream);
 
 // match search + BSDIFF40 (dq_diff.hip)
 int match_search_dev_i32(const void *d_old, int64_t n, const void *d_sa, const void *d_new, int64_t m, const int64_t *d_scans,

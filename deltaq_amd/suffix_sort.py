@@ -816,6 +816,148 @@ class HipSuffixSort:
                                                      dev, stream))
         return lcps
 
+    # -- the LPF array and the LZ77 factorization from SA and LCP (no counterpart in the reference) ------------------
+    def Lpf(self, suffixes, lcp):
+        """``(lpf, src)``: for every position of the text the length of its longest previous factor and where that one
+        starts (-1 where the length is 0), from the text's suffix array and LCP array (what ``Sort`` and ``Lcp`` return;
+        int32).  On a tie the lexicographically smaller neighbour is the source; a match may overlap its own copy.
+        ``_abi.last_lz77_info()`` tells what happened.
+
+        Numpy arrays go through ``dq_lpf_hip_i32`` and return numpy arrays; torch GPU tensors stay on the device
+        (``dq_lpf_hip_dev_i32``, on the current torch stream) and return tensors.  An entry of ``suffixes`` outside the
+        text raises ``SuffixSortError`` (``DQ_ERR_BAD_ARGS``); in-range arrays that are not the text's give unspecified
+        values.
+        """
+        if _is_torch_tensor(suffixes) or _is_torch_tensor(lcp):
+            import torch
+
+            sa, lc = self._lz_device_arrays(suffixes, lcp, None)
+            n = sa.numel()
+            lpf, src = torch.empty_like(sa), torch.empty_like(sa)
+            dev, stream = _device_and_stream(sa)
+            _abi.check(self._lib.dq_lpf_hip_dev_i32(sa.data_ptr() if n else None, lc.data_ptr() if n else None, n,
+                                                    lpf.data_ptr() if n else None, src.data_ptr() if n else None, dev, stream))
+            return lpf, src
+        sa, lc = self._lz_host_arrays(suffixes, lcp, None)
+        n = sa.size
+        lpf, src = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
+        _abi.check(self._lib.dq_lpf_hip_i32(sa.ctypes.data if n else None, lc.ctypes.data if n else None, n,
+                                            lpf.ctypes.data if n else None, src.ctypes.data if n else None, self.device))
+        return lpf, src
+
+    lpf = Lpf
+
+    def Lz77(self, text, suffixes=None, lcp=None, phrases=None):
+        """The greedy LZ77 factorization of ``text`` as an ``(z, 3)`` int32 array of phrases ``(start, len, src)``: a copy
+        of ``len`` bytes from position ``src`` (it may overlap its own output), or a literal ``(start, 0, byte)``.
+        ``lz77_decode`` turns the phrases back into the text.
+
+        ``suffixes`` and ``lcp`` are the text's int32 suffix array and LCP array; where either is left out, ``Sort`` and
+        ``Lcp`` run first.  Host buffers go through ``dq_lz77_hip_i32``; a torch GPU tensor text goes through
+        ``dq_lz77_hip_dev_i32`` on the current torch stream and everything stays on the device.  The output is sized by
+        a first call with no room (``cap = 0``), or ``phrases`` -- an ``(cap, 3)`` int32 array or tensor -- is filled
+        and its filled part returned (``_abi.last_lz77_info()["phrases"]`` holds the true count).
+        """
+        count = ctypes.c_int64(0)
+        if _is_torch_tensor(text) or _is_torch_tensor(suffixes) or _is_torch_tensor(lcp) or _is_torch_tensor(phrases):
+            import torch
+
+            if not _is_torch_tensor(text):
+                raise TypeError("text, suffixes, lcp and phrases must all be host buffers or all torch GPU tensors")
+            if text.dtype != torch.uint8 or text.dim() != 1 or not text.is_contiguous():
+                raise TypeError("device text must be a contiguous 1-D uint8 tensor")
+            if not text.is_cuda:
+                raise TypeError("torch text tensors must live on the GPU; pass host data as bytes/numpy")
+            if text.numel() > INT_MAX:
+                raise ValueError("Lz77 has 32-bit indices: the text must be shorter than 2^31 bytes")
+            if suffixes is None or lcp is None:
+                suffixes = self.Sort(text, index_dtype=np.int32)
+                lcp = self.Lcp(text, suffixes)
+            sa, lc = self._lz_device_arrays(suffixes, lcp, text)
+            n = text.numel()
+            dev, stream = _device_and_stream(text)
+            fn = self._lib.dq_lz77_hip_dev_i32
+            ptrs = (text.data_ptr() if n else None, n, sa.data_ptr() if n else None, lc.data_ptr() if n else None)
+            if phrases is None:
+                _abi.check(fn(*ptrs, None, 0, ctypes.byref(count), dev, stream))
+                phrases = torch.empty((count.value, 3), dtype=torch.int32, device=text.device)
+            elif (not _is_torch_tensor(phrases) or phrases.dtype != torch.int32 or phrases.dim() != 2 or phrases.shape[1] != 3
+                  or not phrases.is_contiguous() or phrases.device != text.device):
+                raise TypeError("phrases must be a contiguous (cap, 3) int32 tensor on the text's device")
+            cap = phrases.shape[0]
+            _abi.check(fn(*ptrs, phrases.data_ptr() if cap else None, cap, ctypes.byref(count), dev, stream))
+            return phrases[:min(count.value, cap)]
+        T = _as_text(text)
+        n = T.size
+        if n > INT_MAX:
+            raise ValueError("Lz77 has 32-bit indices: the text must be shorter than 2^31 bytes")
+        if suffixes is None or lcp is None:
+            suffixes = self.Sort(T, index_dtype=np.int32)
+            lcp = self.Lcp(T, suffixes)
+        sa, lc = self._lz_host_arrays(suffixes, lcp, n)
+        fn = self._lib.dq_lz77_hip_i32
+        ptrs = (T.ctypes.data if n else None, n, sa.ctypes.data if n else None, lc.ctypes.data if n else None)
+        if phrases is None:
+            _abi.check(fn(*ptrs, None, 0, ctypes.byref(count), self.device))
+            phrases = np.empty((count.value, 3), dtype=np.int32)
+        elif (not isinstance(phrases, np.ndarray) or phrases.dtype != np.int32 or phrases.ndim != 2 or phrases.shape[1] != 3
+              or not phrases.flags.c_contiguous):
+            raise TypeError("phrases must be a contiguous (cap, 3) numpy int32 array")
+        cap = phrases.shape[0]
+        _abi.check(fn(*ptrs, phrases.ctypes.data if cap else None, cap, ctypes.byref(count), self.device))
+        return phrases[:min(count.value, cap)]
+
+    lz77 = Lz77
+
+    @staticmethod
+    def _lz_host_arrays(suffixes, lcp, n):
+        for name, a in (("suffixes", suffixes), ("lcp", lcp)):
+            if _is_torch_tensor(a):
+                raise TypeError("text, suffixes, lcp and phrases must all be host buffers or all torch GPU tensors")
+            if not isinstance(a, np.ndarray) or a.dtype != np.int32 or a.ndim != 1:
+                raise TypeError(f"{name} must be a 1-D numpy int32 array")
+        if suffixes.size != lcp.size or (n is not None and suffixes.size != n):
+            raise ValueError(LENGTH_MISMATCH_MESSAGE)
+        return np.ascontiguousarray(suffixes), np.ascontiguousarray(lcp)
+
+    @staticmethod
+    def _lz_device_arrays(suffixes, lcp, text):
+        import torch
+
+        for name, a in (("suffixes", suffixes), ("lcp", lcp)):
+            if not _is_torch_tensor(a):
+                raise TypeError("text, suffixes, lcp and phrases must all be host buffers or all torch GPU tensors")
+            if a.dtype != torch.int32 or a.dim() != 1 or not a.is_contiguous():
+                raise TypeError(f"{name} must be a contiguous 1-D int32 tensor")
+            if not a.is_cuda:
+                raise TypeError("torch tensors must live on the GPU; pass host data as numpy")
+        if lcp.device != suffixes.device or (text is not None and text.device != suffixes.device):
+            raise TypeError("text, suffixes and lcp must be on the same device")
+        if suffixes.numel() != lcp.numel() or (text is not None and suffixes.numel() != text.numel()):
+            raise ValueError(LENGTH_MISMATCH_MESSAGE)
+        return suffixes, lcp
+
+
+def lz77_decode(phrases) -> bytes:
+    """The text of a factorization ``HipSuffixSort.Lz77`` returned: literals ``(start, 0, byte)`` are appended, a copy
+    ``(start, len, src)`` is taken from the output itself, byte by byte where it overlaps what it writes."""
+    if _is_torch_tensor(phrases):
+        phrases = phrases.cpu().numpy()
+    out = bytearray()
+    for start, length, third in np.asarray(phrases).reshape(-1, 3).tolist():
+        if start != len(out):
+            raise ValueError(f"phrase at {start} does not start where the one before it ends ({len(out)})")
+        if length == 0:
+            out.append(third)
+        elif not 0 <= third < start:
+            raise ValueError(f"phrase at {start} copies from {third}")
+        elif third + length <= start:
+            out += out[third:third + length]
+        else:
+            for k in range(length):
+                out.append(out[third + k])
+    return bytes(out)
+
 
 def _device_and_stream(t):
     """(device ordinal, stream handle) for work on tensor t's device, on torch's current stream."""

@@ -740,6 +740,52 @@ int32_t dq_lcp_hip_many_dev_i32(const void *d_texts, const void *d_offsets, int3
                                 void *d_lcps, int32_t device, void *stream);
 int32_t dq_lcp_last_info(int64_t *info, int32_t count);
 
+/* ---- the longest-previous-factor array and the greedy LZ77 factorization, on the device --------------------------------
+ * For a text T of n bytes, its suffix array sa and its LCP array lcp (dq_lcp_hip_*'s: lcp[0] = 0, no sentinel; a suffix
+ * ends at the end of the text).  For a position i look at the suffixes that start before i: p the lexicographically
+ * greatest of them below suffix i, q the least of them above it; either may be missing, and a missing one has nothing in
+ * common.  lpf[i] = max(common(i, p), common(i, q)); src[i] = p if common(i, p) >= common(i, q), else q; src[i] = -1 where
+ * lpf[i] == 0.  A match may overlap its own copy: src[i] + lpf[i] > i is normal.  With r the rank of i: p = sa[r'] for the
+ * nearest r' < r with sa[r'] < i and common(i, p) = min lcp[r'+1 .. r]; q = sa[r''] for the nearest r'' > r with
+ * sa[r''] < i and common(i, q) = min lcp[r+1 .. r''].  lpf and src have n entries in text order; the LPF forms do not
+ * need the text.
+ * The factorization: phrases start at position 0, the phrase at i has max(1, lpf[i]) bytes and the next one starts right
+ * behind it.  A phrase is three int32: a copy (i, lpf[i], src[i]), a literal (lpf[i] == 0) (i, 0, T[i]) -- the byte
+ * itself, so the triples alone decode to the text, copying byte by byte because copies overlap.  "abababb" gives
+ * (0,0,'a') (1,0,'b') (2,4,0) (6,1,1).  phrases holds cap triples; *count (a host pointer in both forms) always receives
+ * the true number of phrases z <= n; the first min(z, cap) triples are written and nothing beyond them.  cap == 0 with
+ * phrases == NULL is the sizing call and returns DQ_OK.  n == 0 is a no-op with *count = 0.
+ *   negative n, negative cap, a NULL buffer that is needed     DQ_ERR_BAD_ARGS
+ *   n > 2^31-1                                                  DQ_ERR_TOO_LARGE (all before any device work)
+ * Untrusted arrays, as for dq_lcp_hip_*: an entry of sa becomes an address only after its range test, and one outside
+ * [0, n) makes the call return DQ_ERR_BAD_ARGS (outputs undefined); lcp values are clamped to [0, n]; the parse clamps
+ * every step to [1, n - i].  In-range arrays that are not the SA and LCP of the text give DQ_OK and unspecified contents
+ * (count in [1, n]); the call makes no access outside its buffers and every walk is bounded.
+ * Computed after Shun & Zhao, "Practical parallel Lempel-Ziv factorization" (DCC 2013; deltaq_amd/csrc/dq_lz77.h): minima
+ * of sa and lcp per group of 64^k ranks, a tile pass that decides the neighbours inside 256 ranks, one wave per rank whose
+ * neighbour lies outside its tile; the parse finds every position's first hop out of its tile of 8192 positions, ONE
+ * lane follows those hops from position 0 (the serial part: n / 8192 dependent loads), then the tiles mark, count and
+ * write their phrases.
+ * Device memory, carved from the cached workspace of the slot the call leases: 20.2 bytes per byte of text for an LPF
+ * call (the list of ranks for the wave kernel 4 + 16, the minima 8/63, 12 bytes per 256 ranks), 28.3 for an LZ77 call
+ * (lpf 4, src 4, one bit per position, 8 bytes per 8192 positions; the exits reuse the list), and a line of counters; the
+ * host forms add their device copies of the arrays, the text and min(cap, n) triples.  No CPU fallback: DQ_ERR_OOM when
+ * that does not fit.  The _dev_ forms take device pointers on `device`, enqueue on `stream` (NULL = the library's stream)
+ * and return after it has drained.  One stream wait per call.
+ * Out of scope: int64 forms, a many-texts form, and computing sa or lcp inside these calls (dq_sufsort_hip_*, dq_lcp_hip_*
+ * do that).  No text above 2^20 + 1 bytes has been compared with a model.
+ * dq_lz77_last_info: shape of the last of these calls on this thread, reset when one starts; `count` entries (7 are
+ * defined, further ones read 0; a NULL array is DQ_ERR_BAD_ARGS): [0] phrases z, [1] literal phrases (both 0 in LPF
+ * calls); [2] the longest lpf value (LPF calls) or the longest phrase (LZ77 calls); [3] ranks handed to the wave kernel;
+ * [4] serial hops of the tile walker (0 in LPF calls); [5] kernel launches; [6] stream waits. */
+int32_t dq_lpf_hip_i32(const int32_t *sa, const int32_t *lcp, int64_t n, int32_t *lpf, int32_t *src, int32_t device);
+int32_t dq_lpf_hip_dev_i32(const void *d_sa, const void *d_lcp, int64_t n, void *d_lpf, void *d_src, int32_t device, void *stream);
+int32_t dq_lz77_hip_i32(const uint8_t *text, int64_t n, const int32_t *sa, const int32_t *lcp,
+                        int32_t *phrases, int64_t cap, int64_t *count, int32_t device);
+int32_t dq_lz77_hip_dev_i32(const void *d_text, int64_t n, const void *d_sa, const void *d_lcp,
+                            void *d_phrases, int64_t cap, int64_t *count, int32_t device, void *stream);
+int32_t dq_lz77_last_info(int64_t *info, int32_t count);
+
 /* Device workspace (bytes) a sort of n bytes with index_bytes (4 or 8) wide indices needs,
  * excluding the caller's text and sa buffers: the device entry point's full layout (the reduced one at n = 2^32). */
 int64_t dq_sufsort_hip_workspace_bytes(int64_t n, int32_t index_bytes);
