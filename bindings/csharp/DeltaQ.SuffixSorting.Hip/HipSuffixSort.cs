@@ -132,6 +132,29 @@ public sealed class HipSuffixSort : ISuffixSort
     private static extern unsafe int dq_lz77_last_info(long* info, int count);
 
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    private static extern unsafe int dq_mstat_hip_i32(int* sa, int* lcp, long m, long n, int* len, int* src, int device);
+
+    // (the managed Rlz keeps len / src between MatchStats and LzParse; this one-call form is declared for hosts that want it)
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern unsafe int dq_rlz_hip_i32(byte* newData, long m, long n, int* sa, int* lcp, int* phrases, long cap, long* count, int device);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    private static extern unsafe int dq_lzparse_hip_i32(byte* text, long n, int* len, int* src, int* phrases, long cap, long* count, int device);
+
+    // (declared for hosts that keep their buffers on the device: device pointers, a hipStream_t or zero; count is host memory)
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern int dq_mstat_hip_dev_i32(IntPtr dSa, IntPtr dLcp, long m, long n, IntPtr dLen, IntPtr dSrc, int device, IntPtr stream);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern unsafe int dq_rlz_hip_dev_i32(IntPtr dNew, long m, long n, IntPtr dSa, IntPtr dLcp, IntPtr dPhrases, long cap, long* count, int device, IntPtr stream);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern unsafe int dq_lzparse_hip_dev_i32(IntPtr dText, long n, IntPtr dLen, IntPtr dSrc, IntPtr dPhrases, long cap, long* count, int device, IntPtr stream);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    private static extern unsafe int dq_rlz_last_info(long* info, int count);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
     private static extern int dq_abi_version();
 
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
@@ -1102,6 +1125,156 @@ public sealed class HipSuffixSort : ISuffixSort
             if (rc != 0)
             {
                 throw new InvalidOperationException($"dq_lz77_last_info failed ({rc})");
+            }
+        }
+
+        return info;
+    }
+
+    /// <summary>
+    /// The matching statistics of <paramref name="newData"/> against <paramref name="old"/> (dq_mstat_hip_i32):
+    /// <c>Len[j]</c> is the length of the longest prefix of new[j..] that occurs anywhere in old, <c>Src[j]</c> one
+    /// position in old where it occurs (-1 where the length is 0).  <paramref name="suffixes"/> and
+    /// <paramref name="lcp"/> are the suffix array and LCP array of new FOLLOWED BY old.  There is no managed fallback.
+    /// </summary>
+    public unsafe (int[] Len, int[] Src) MatchStats(int oldLength, int newLength, ReadOnlySpan<int> suffixes, ReadOnlySpan<int> lcp)
+    {
+        if (oldLength < 0 || newLength < 0 || suffixes.Length != lcp.Length || suffixes.Length != (long)oldLength + newLength)
+        {
+            ThrowHelper();
+        }
+
+        var len = new int[newLength];
+        var src = new int[newLength];
+        int rc;
+        fixed (int* pSa = suffixes)
+        fixed (int* pLcp = lcp)
+        fixed (int* pLen = len)
+        fixed (int* pSrc = src)
+        {
+            rc = dq_mstat_hip_i32(pSa, pLcp, newLength, oldLength, pLen, pSrc, _device);
+        }
+
+        LcpResult(rc, "dq_mstat_hip_i32");
+        return (len, src);
+    }
+
+    /// <summary>The matching statistics of a pair alone: <c>Sort</c> and <c>Lcp</c> of new + old, then the call above.</summary>
+    public (int[] Len, int[] Src) MatchStats(ReadOnlySpan<byte> old, ReadOnlySpan<byte> newData)
+    {
+        if (newData.Length == 0)
+        {
+            return (Array.Empty<int>(), Array.Empty<int>());
+        }
+
+        var cat = new byte[checked(newData.Length + old.Length)];
+        newData.CopyTo(cat);
+        old.CopyTo(cat.AsSpan(newData.Length));
+        var suffixes = new int[cat.Length];
+        Sort(cat, suffixes);
+        return MatchStats(old.Length, newData.Length, suffixes, Lcp(cat, suffixes));
+    }
+
+    /// <summary>
+    /// The greedy parse of <paramref name="text"/> from a finished (len, src) pair in text order (dq_lzparse_hip_i32),
+    /// three ints a phrase: what <c>Lpf</c> returns gives <c>Lz77</c>'s phrases, what <c>MatchStats</c> returns with
+    /// text = new gives <c>Rlz</c>'s.  The output is sized by a first native call with no room.
+    /// </summary>
+    public unsafe int[] LzParse(ReadOnlySpan<byte> text, ReadOnlySpan<int> len, ReadOnlySpan<int> src)
+    {
+        if (text.Length != len.Length || text.Length != src.Length)
+        {
+            ThrowHelper();
+        }
+
+        long count = 0;
+        int rc;
+        fixed (byte* pText = text)
+        fixed (int* pLen = len)
+        fixed (int* pSrc = src)
+        {
+            rc = dq_lzparse_hip_i32(pText, text.Length, pLen, pSrc, null, 0, &count, _device);
+            LcpResult(rc, "dq_lzparse_hip_i32");
+            var phrases = new int[checked(3 * count)];
+            fixed (int* pPhrases = phrases)
+            {
+                rc = dq_lzparse_hip_i32(pText, text.Length, pLen, pSrc, count > 0 ? pPhrases : null, count, &count, _device);
+            }
+
+            LcpResult(rc, "dq_lzparse_hip_i32");
+            return phrases;
+        }
+    }
+
+    /// <summary>
+    /// The relative Lempel-Ziv factorization of <paramref name="newData"/> against <paramref name="old"/>, three ints a
+    /// phrase: (start, len, src) for a copy of len bytes from position src IN OLD, (start, 0, byte) for a literal.
+    /// <see cref="RlzDecode"/> gives new back.  The matching statistics are computed once, then parsed.
+    /// </summary>
+    public int[] Rlz(ReadOnlySpan<byte> old, ReadOnlySpan<byte> newData)
+    {
+        var (len, src) = MatchStats(old, newData);
+        return LzParse(newData, len, src);
+    }
+
+    /// <summary>... with the suffix array and LCP array of new + old at hand.</summary>
+    public int[] Rlz(ReadOnlySpan<byte> old, ReadOnlySpan<byte> newData, ReadOnlySpan<int> suffixes, ReadOnlySpan<int> lcp)
+    {
+        var (len, src) = MatchStats(old.Length, newData.Length, suffixes, lcp);
+        return LzParse(newData, len, src);
+    }
+
+    /// <summary>
+    /// The new file of a relative factorization.  A phrase that does not start where the one before it ends, or that
+    /// copies from outside old, is refused.
+    /// </summary>
+    public static byte[] RlzDecode(ReadOnlySpan<byte> old, ReadOnlySpan<int> phrases)
+    {
+        if (phrases.Length % 3 != 0)
+        {
+            throw new ArgumentException("phrases are three ints each");
+        }
+
+        var text = new List<byte>();
+        for (int k = 0; k < phrases.Length; k += 3)
+        {
+            int start = phrases[k], len = phrases[k + 1], third = phrases[k + 2];
+            if (start != text.Count)
+            {
+                throw new ArgumentException($"phrase at {start} does not start where the one before it ends ({text.Count})");
+            }
+
+            if (len == 0)
+            {
+                text.Add((byte)third);
+                continue;
+            }
+
+            if (len < 0 || third < 0 || third > old.Length - len)
+            {
+                throw new ArgumentException($"phrase at {start} copies {len} bytes from {third}: outside old ({old.Length} bytes)");
+            }
+
+            text.AddRange(old.Slice(third, len).ToArray());
+        }
+
+        return text.ToArray();
+    }
+
+    /// <summary>
+    /// Shape of the last MatchStats / Rlz / LzParse on this thread (dq_rlz_last_info): phrases, literal phrases (both 0
+    /// after MatchStats), the longest len (MatchStats) or phrase, positions of new with a match (0 after LzParse),
+    /// serial hops of the tile walker, kernel launches, stream waits.
+    /// </summary>
+    public static unsafe long[] LastRlzInfo()
+    {
+        var info = new long[7];
+        fixed (long* p = info)
+        {
+            int rc = dq_rlz_last_info(p, info.Length);
+            if (rc != 0)
+            {
+                throw new InvalidOperationException($"dq_rlz_last_info failed ({rc})");
             }
         }
 

@@ -10,7 +10,7 @@ provider does, and raises if it has not been built.  There is no CPU fallback.
 """
 from ._abi import BackendMissingError, SuffixSortError  # noqa: F401
 from .suffix_sort import HipSuffixSort, device_count, LENGTH_MISMATCH_MESSAGE  # noqa: F401
-from .suffix_sort import lz77_decode  # noqa: F401
+from .suffix_sort import lz77_decode, rlz_decode  # noqa: F401
 from .suffix_sort import (CHECK_DONE, CHECK_BAD_ARGUMENTS, CHECK_OUT_OF_RANGE, CHECK_WRONG_ORDER,  # noqa: F401
                           CHECK_WRONG_POSITION)
 from .match_search import HipMatchSearch  # noqa: F401

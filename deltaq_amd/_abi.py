@@ -62,6 +62,8 @@ EXPORTS = (
     "dq_lcp_hip_i32", "dq_lcp_hip_i64", "dq_lcp_hip_dev_i32", "dq_lcp_hip_dev_i64",
     "dq_lcp_hip_many_i32", "dq_lcp_hip_many_dev_i32", "dq_lcp_last_info",
     "dq_lpf_hip_i32", "dq_lpf_hip_dev_i32", "dq_lz77_hip_i32", "dq_lz77_hip_dev_i32", "dq_lz77_last_info",
+    "dq_mstat_hip_i32", "dq_mstat_hip_dev_i32", "dq_rlz_hip_i32", "dq_rlz_hip_dev_i32",
+    "dq_lzparse_hip_i32", "dq_lzparse_hip_dev_i32", "dq_rlz_last_info",
     "dq_bsdiff_search_dev_i32", "dq_bsdiff_search_dev_i64", "dq_bsdiff_search_i32", "dq_bsdiff_search_i64",
     "dq_bsdiff_create", "dq_bsdiff_patch_bound", "dq_bsdiff_scan_i32", "dq_bspatch_apply",
     "dq_bspatch_new_size_many", "dq_bspatch_apply_many", "dq_bspatch_index_apply_many",
@@ -113,6 +115,9 @@ LCP_RECORD = _n("irreducible", "wave_comparisons", "longest", "launches", "strea
 # ... and the record of dq_lz77_last_info, struct Lz77Info of deltaq_amd/csrc/dq_lz77_info.h, likewise beside RECORDS;
 # tests/test_lz77_cpu.py checks this pair.
 LZ77_RECORD = _n("phrases", "literals", "longest", "wave_ranks", "walker_hops", "launches", "stream_waits")
+
+# ... and the record of dq_rlz_last_info, struct RlzInfo of deltaq_amd/csrc/dq_rlz_info.h; tests/test_rlz_cpu.py checks it.
+RLZ_RECORD = _n("phrases", "literals", "longest", "matched", "walker_hops", "launches", "stream_waits")
 
 
 class BackendMissingError(RuntimeError):
@@ -204,6 +209,20 @@ def load() -> ctypes.CDLL:
     L.dq_lz77_hip_dev_i32.argtypes = [vp, i64, vp, vp, vp, i64, ctypes.POINTER(i64), i32, vp]
     L.dq_lz77_last_info.restype = i32
     L.dq_lz77_last_info.argtypes = [ctypes.POINTER(i64), i32]
+    L.dq_mstat_hip_i32.restype = i32
+    L.dq_mstat_hip_i32.argtypes = [vp, vp, i64, i64, vp, vp, i32]
+    L.dq_mstat_hip_dev_i32.restype = i32
+    L.dq_mstat_hip_dev_i32.argtypes = [vp, vp, i64, i64, vp, vp, i32, vp]
+    L.dq_rlz_hip_i32.restype = i32
+    L.dq_rlz_hip_i32.argtypes = [vp, i64, i64, vp, vp, vp, i64, ctypes.POINTER(i64), i32]
+    L.dq_rlz_hip_dev_i32.restype = i32
+    L.dq_rlz_hip_dev_i32.argtypes = [vp, i64, i64, vp, vp, vp, i64, ctypes.POINTER(i64), i32, vp]
+    L.dq_lzparse_hip_i32.restype = i32
+    L.dq_lzparse_hip_i32.argtypes = [vp, i64, vp, vp, vp, i64, ctypes.POINTER(i64), i32]
+    L.dq_lzparse_hip_dev_i32.restype = i32
+    L.dq_lzparse_hip_dev_i32.argtypes = [vp, i64, vp, vp, vp, i64, ctypes.POINTER(i64), i32, vp]
+    L.dq_rlz_last_info.restype = i32
+    L.dq_rlz_last_info.argtypes = [ctypes.POINTER(i64), i32]
     L.dq_sufsort_hip_batch_i32.restype = i32
     L.dq_sufsort_hip_batch_i32.argtypes = [i32, vp, vp, vp, i32, vp]
     L.dq_sufsort_hip_many_i32.restype = i32
@@ -419,6 +438,15 @@ def last_lz77_info() -> dict:
     v = (ctypes.c_int64 * len(LZ77_RECORD))()
     check(load().dq_lz77_last_info(v, len(LZ77_RECORD)))
     return {key: v[i] * scale for i, (key, scale) in enumerate(LZ77_RECORD)}
+
+
+def last_rlz_info() -> dict:
+    """Shape of the last dq_mstat_hip_* / dq_rlz_hip_* / dq_lzparse_hip_* on this thread (dq_rlz_last_info): phrases and
+    literal phrases (0 in mstat calls), the longest len value (mstat calls) or phrase (parse and rlz calls), positions of
+    new with a match (0 in parse calls), serial hops of the tile walker, kernel launches, stream waits."""
+    v = (ctypes.c_int64 * len(RLZ_RECORD))()
+    check(load().dq_rlz_last_info(v, len(RLZ_RECORD)))
+    return {key: v[i] * scale for i, (key, scale) in enumerate(RLZ_RECORD)}
 
 
 def last_batch_info() -> dict:

@@ -10,7 +10,8 @@ Five translation units, compiled side by side and linked into one library:
     dq_diff.hip                             match search, Diff.Create / Patch.Apply
     dq_sufcheck.hip                         LDSSChecker.Check of a suffix array on the device, and its LCP array
                                             (dq_lcp.h, dq_lcp_host.h), LPF and the LZ77 factorization
-                                            (dq_lz77.h, dq_lz77_host.h)
+                                            (dq_lz77.h, dq_lz77_host.h), matching statistics and the relative
+                                            LZ factorization (dq_rlz.h, dq_rlz_host.h)
     dq_abi.hip                              the C ABI and the batch pipeline (host code only)
 Objects live in deltaq_amd/csrc/obj/ with the compiler's own dependency files, so an edit
 rebuilds only the units that include what changed.

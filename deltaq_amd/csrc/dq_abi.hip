@@ -407,6 +407,55 @@ int32_t dq_lz77_hip_dev_i32(const void *d_text, int64_t n, const void *d_sa, con
 
 int32_t dq_lz77_last_info(int64_t *info, int32_t count) { return last_info(t_lz77_info, info, count, "null info array"); }
 
+int32_t dq_mstat_hip_i32(const int32_t *sa, const int32_t *lcp, int64_t m, int64_t n, int32_t *len, int32_t *src, int32_t device)
+{
+    EnvScope scope;
+    t_rlz_info = {};
+    return mstat_host(sa, lcp, m, n, len, src, device);
+}
+
+int32_t dq_mstat_hip_dev_i32(const void *d_sa, const void *d_lcp, int64_t m, int64_t n, void *d_len, void *d_src, int32_t device,
+                             void *stream)
+{
+    EnvScope scope;
+    t_rlz_info = {};
+    return mstat_dev(d_sa, d_lcp, m, n, d_len, d_src, device, stream);
+}
+
+int32_t dq_rlz_hip_i32(const uint8_t *new_data, int64_t m, int64_t n, const int32_t *sa, const int32_t *lcp, int32_t *phrases,
+                       int64_t cap, int64_t *count, int32_t device)
+{
+    EnvScope scope;
+    t_rlz_info = {};
+    return rlz_host(new_data, m, n, sa, lcp, phrases, cap, count, device);
+}
+
+int32_t dq_rlz_hip_dev_i32(const void *d_new, int64_t m, int64_t n, const void *d_sa, const void *d_lcp, void *d_phrases, int64_t cap,
+                           int64_t *count, int32_t device, void *stream)
+{
+    EnvScope scope;
+    t_rlz_info = {};
+    return rlz_dev(d_new, m, n, d_sa, d_lcp, d_phrases, cap, count, device, stream);
+}
+
+int32_t dq_lzparse_hip_i32(const uint8_t *text, int64_t n, const int32_t *len, const int32_t *src, int32_t *phrases, int64_t cap,
+                           int64_t *count, int32_t device)
+{
+    EnvScope scope;
+    t_rlz_info = {};
+    return lzparse_host(text, n, len, src, phrases, cap, count, device);
+}
+
+int32_t dq_lzparse_hip_dev_i32(const void *d_text, int64_t n, const void *d_len, const void *d_src, void *d_phrases, int64_t cap,
+                               int64_t *count, int32_t device, void *stream)
+{
+    EnvScope scope;
+    t_rlz_info = {};
+    return lzparse_dev(d_text, n, d_len, d_src, d_phrases, cap, count, device, stream);
+}
+
+int32_t dq_rlz_last_info(int64_t *info, int32_t count) { return last_info(t_rlz_info, info, count, "null info array"); }
+
 int32_t dq_sufsort_hip_batch_i32(int32_t count, const uint8_t *const *texts, const int64_t *lens,
                                  int32_t *const *sas, int32_t ndev, const int32_t *devs)
 {

@@ -71,6 +71,7 @@ struct LzCounters {
     uint32_t phrases, literals;
     uint32_t longest_lpf, longest_phrase;
     uint32_t flags;                              // kLzOutOfRange
+    uint32_t unmatched;                          // positions of new with len == 0 (dq_rlz.h; its longest len is longest_lpf)
 };
 static_assert(sizeof(LzCounters) <= 256);
 

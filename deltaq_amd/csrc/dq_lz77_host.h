@@ -101,17 +101,14 @@ int lpf_enqueue(DeviceCtx &c, hipStream_t st, const LzScratch &at, int64_t n, co
     return DQ_OK;
 }
 
-// ... and the parse behind it.  d_phrases may be null with cap == 0.
-int lz_enqueue(DeviceCtx &c, hipStream_t st, const LzScratch &at, int64_t n, const uint8_t *d_text, const int32_t *d_sa,
-               const int32_t *d_lcp, int32_t *d_phrases, int64_t cap, char *scratch)
+// The parse of a text of n > 0 bytes from any finished (lpf, src) pair in text order: one fill and five launches, enqueues
+// only (the caller counts the launches).  exits: n words; entry, count: a word per tile of positions; bits: kBlock words
+// per tile.  ctr's line is zeroed before; d_phrases may be null with cap == 0.  Shared by dq_lz77_hip_*, dq_rlz_hip_*
+// and dq_lzparse_hip_* (dq_rlz_host.h).
+constexpr int kLzParseLaunches = 5;
+int lz_parse_enqueue(hipStream_t st, int64_t n, const uint8_t *d_text, const int32_t *lpf, const int32_t *src, int32_t *exits,
+                     int32_t *entry, uint32_t *count, uint32_t *bits, int32_t *d_phrases, int64_t cap, LzCounters *ctr)
 {
-    LzCounters *ctr = reinterpret_cast<LzCounters *>(scratch);
-    int32_t *lpf = reinterpret_cast<int32_t *>(scratch + at.lpf_at), *src = reinterpret_cast<int32_t *>(scratch + at.src_at);
-    // (where SA is no permutation some entries of lpf stay unwritten: any value is safe, the parse clamps every step)
-    DQ_TRY(lpf_enqueue(c, st, at, n, d_sa, d_lcp, lpf, src, scratch));
-    int32_t *exits = reinterpret_cast<int32_t *>(scratch + at.list_q_at);    // the list is read: its area takes the exits
-    int32_t *entry = reinterpret_cast<int32_t *>(scratch + at.entry_at);
-    uint32_t *count = reinterpret_cast<uint32_t *>(scratch + at.count_at), *bits = reinterpret_cast<uint32_t *>(scratch + at.bits_at);
     const int64_t tiles = lz_tiles(n);
     const dim3 grid((unsigned)tiles), block(kBlock);
     HIP_TRY(hipMemsetAsync(entry, 0xff, (size_t)tiles * sizeof(int32_t), st));
@@ -126,7 +123,22 @@ int lz_enqueue(DeviceCtx &c, hipStream_t st, const LzScratch &at, int64_t n, con
     hipLaunchKernelGGL(lz_emit_kernel, grid, block, 0, st, d_text, (const int32_t *)lpf, (const int32_t *)src, n, (const uint32_t *)bits,
                        (const uint32_t *)count, d_phrases, cap, ctr);
     HIP_TRY(hipGetLastError());
-    t_lz77_info.launches += 5;
+    return DQ_OK;
+}
+
+// ... and the parse behind the LPF array.
+int lz_enqueue(DeviceCtx &c, hipStream_t st, const LzScratch &at, int64_t n, const uint8_t *d_text, const int32_t *d_sa,
+               const int32_t *d_lcp, int32_t *d_phrases, int64_t cap, char *scratch)
+{
+    LzCounters *ctr = reinterpret_cast<LzCounters *>(scratch);
+    int32_t *lpf = reinterpret_cast<int32_t *>(scratch + at.lpf_at), *src = reinterpret_cast<int32_t *>(scratch + at.src_at);
+    // (where SA is no permutation some entries of lpf stay unwritten: any value is safe, the parse clamps every step)
+    DQ_TRY(lpf_enqueue(c, st, at, n, d_sa, d_lcp, lpf, src, scratch));
+    int32_t *exits = reinterpret_cast<int32_t *>(scratch + at.list_q_at);    // the list is read: its area takes the exits
+    int32_t *entry = reinterpret_cast<int32_t *>(scratch + at.entry_at);
+    uint32_t *count = reinterpret_cast<uint32_t *>(scratch + at.count_at), *bits = reinterpret_cast<uint32_t *>(scratch + at.bits_at);
+    DQ_TRY(lz_parse_enqueue(st, n, d_text, lpf, src, exits, entry, count, bits, d_phrases, cap, ctr));
+    t_lz77_info.launches += kLzParseLaunches;
     return DQ_OK;
 }
 

@@ -12,7 +12,9 @@
 //   dq_diff.hip                             match search, Diff.Create / Patch.Apply, the many-new-files index
 //   dq_sufcheck.hip                         LDSSChecker.Check of a suffix array on the device (dq_sufcheck.h)
 //                                           and its LCP array (dq_lcp.h, dq_lcp_host.h), and what the two arrays
-//                                           give together: LPF and the LZ77 factorization (dq_lz77.h, dq_lz77_host.h)
+//                                           give together: LPF and the LZ77 factorization (dq_lz77.h, dq_lz77_host.h),
+//                                           matching statistics of a new file against an old one and the relative
+//                                           LZ factorization (dq_rlz.h, dq_rlz_host.h)
 //   dq_abi.hip                              the C ABI (include/dq_sufsort.h), the batch pipeline, profile getters
 #pragma once
 #include <hip/hip_runtime.h>
@@ -38,6 +40,7 @@
 #include "dq_call_info.h"
 #include "dq_lcp_info.h"
 #include "dq_lz77_info.h"
+#include "dq_rlz_info.h"
 #include "dq_flags.h"
 #include "dq_work_lists.h"
 #include "dq_block_groups.h"
@@ -706,6 +709,20 @@ int lz77_host(const uint8_t *text, int64_t n, const int32_t *sa, const int32_t *
               int32_t device);
 int lz77_dev(const void *d_text, int64_t n, const void *d_sa, const void *d_lcp, void *d_phrases, int64_t cap, int64_t *count,
              int32_t device, void *stream);
+
+// Matching statistics of new against old from the SA and LCP of new + old, the relative LZ factorization and the parse
+// alone (dq_rlz_host.h, in dq_sufcheck.hip): the bodies of dq_mstat_hip_*, dq_rlz_hip_* and dq_lzparse_hip_*.  All of
+// them fill t_rlz_info (dq_rlz_info.h); the entry point resets it.
+int mstat_host(const int32_t *sa, const int32_t *lcp, int64_t m, int64_t n, int32_t *len, int32_t *src, int32_t device);
+int mstat_dev(const void *d_sa, const void *d_lcp, int64_t m, int64_t n, void *d_len, void *d_src, int32_t device, void *stream);
+int rlz_host(const uint8_t *new_data, int64_t m, int64_t n, const int32_t *sa, const int32_t *lcp, int32_t *phrases, int64_t cap,
+             int64_t *count, int32_t device);
+int rlz_dev(const void *d_new, int64_t m, int64_t n, const void *d_sa, const void *d_lcp, void *d_phrases, int64_t cap, int64_t *count,
+            int32_t device, void *stream);
+int lzparse_host(const uint8_t *text, int64_t n, const int32_t *len, const int32_t *src, int32_t *phrases, int64_t cap, int64_t *count,
+                 int32_t device);
+int lzparse_dev(const void *d_text, int64_t n, const void *d_len, const void *d_src, void *d_phrases, int64_t cap, int64_t *count,
+                int32_t device, void *stream);
 
 // match search + BSDIFF40 (dq_diff.hip)
 int match_search_dev_i32(const void *d_old, int64_t n, const void *d_sa, const void *d_new, int64_t m, const int64_t *d_scans,

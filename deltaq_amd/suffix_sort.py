@@ -909,9 +909,131 @@ class HipSuffixSort:
 
     lz77 = Lz77
 
+    # -- a new file against an old one: matching statistics and the relative LZ factorization (no counterpart) --------
+    def MatchStats(self, old, new, suffixes=None, lcp=None):
+        """``(len, src)``: for every position j of ``new`` the length of the longest prefix of ``new[j:]`` that occurs
+        anywhere in ``old`` and one position in ``old`` where it occurs (-1 where the length is 0): the matching
+        statistics of new against old.
+
+        ``suffixes`` and ``lcp`` are the int32 suffix array and LCP array of ``new + old`` (new FIRST); where either is
+        left out, ``Sort`` and ``Lcp`` of that concatenation run first.  Host buffers go through ``dq_mstat_hip_i32`` and
+        return numpy arrays; torch GPU tensors stay on the device (``dq_mstat_hip_dev_i32``, on the current torch
+        stream) and return tensors.  ``_abi.last_rlz_info()`` tells what happened.
+        """
+        if any(_is_torch_tensor(a) for a in (old, new, suffixes, lcp)):
+            import torch
+
+            for name, t in (("old", old), ("new", new)):
+                if not _is_torch_tensor(t):
+                    raise TypeError("text, suffixes, lcp and phrases must all be host buffers or all torch GPU tensors")
+                if t.dtype != torch.uint8 or t.dim() != 1 or not t.is_contiguous():
+                    raise TypeError(f"device {name} must be a contiguous 1-D uint8 tensor")
+                if not t.is_cuda:
+                    raise TypeError("torch text tensors must live on the GPU; pass host data as bytes/numpy")
+            if old.device != new.device:
+                raise TypeError("old and new must be on the same device")
+            m, n = new.numel(), old.numel()
+            if m + n > INT_MAX:
+                raise ValueError("MatchStats has 32-bit indices: old and new together must be shorter than 2^31 bytes")
+            length = torch.empty(m, dtype=torch.int32, device=new.device)
+            src = torch.empty(m, dtype=torch.int32, device=new.device)
+            if m == 0:
+                return length, src
+            if suffixes is None or lcp is None:
+                cat = torch.cat([new, old])
+                suffixes = self.Sort(cat, index_dtype=np.int32)
+                lcp = self.Lcp(cat, suffixes)
+            sa, lc = self._lz_device_arrays(suffixes, lcp, None)
+            if sa.numel() != m + n or sa.device != new.device:
+                raise ValueError(LENGTH_MISMATCH_MESSAGE)
+            dev, stream = _device_and_stream(new)
+            _abi.check(self._lib.dq_mstat_hip_dev_i32(sa.data_ptr(), lc.data_ptr(), m, n, length.data_ptr(), src.data_ptr(), dev, stream))
+            return length, src
+        O, N = _as_text(old), _as_text(new)
+        m, n = N.size, O.size
+        if m + n > INT_MAX:
+            raise ValueError("MatchStats has 32-bit indices: old and new together must be shorter than 2^31 bytes")
+        length, src = np.empty(m, dtype=np.int32), np.empty(m, dtype=np.int32)
+        if suffixes is None or lcp is None:
+            if m == 0:
+                return length, src
+            cat = np.concatenate([N, O])
+            suffixes = self.Sort(cat, index_dtype=np.int32)
+            lcp = self.Lcp(cat, suffixes)
+        sa, lc = self._lz_host_arrays(suffixes, lcp, m + n)
+        _abi.check(self._lib.dq_mstat_hip_i32(sa.ctypes.data if m + n else None, lc.ctypes.data if m + n else None, m, n,
+                                              length.ctypes.data if m else None, src.ctypes.data if m else None, self.device))
+        return length, src
+
+    matchstats = MatchStats
+
+    def Rlz(self, old, new, suffixes=None, lcp=None, phrases=None):
+        """The relative Lempel-Ziv factorization of ``new`` against ``old`` as an ``(z, 3)`` int32 array of phrases: a
+        copy ``(start, len, src)`` of ``len`` bytes from position ``src`` IN OLD, or a literal ``(start, 0, byte)``.
+        ``rlz_decode(old, phrases)`` gives ``new`` back.  The matching statistics are computed once (``MatchStats``),
+        then parsed (``LzParse``: its sizing call, then the triples); arguments as ``MatchStats``, ``phrases`` as ``Lz77``.
+        """
+        length, src = self.MatchStats(old, new, suffixes, lcp)
+        return self.LzParse(new, length, src, phrases)
+
+    rlz = Rlz
+
+    def LzParse(self, text, length, src, phrases=None):
+        """The greedy parse of ``text`` from a finished ``(length, src)`` pair in text order as an ``(z, 3)`` int32 array:
+        ``Lpf``'s output gives ``Lz77``'s phrases, ``MatchStats``'s output with ``text = new`` gives ``Rlz``'s.  The phrase
+        at i has ``max(1, length[i])`` bytes; ``src[i]`` goes into a copy's triple as it is.  Host buffers go through
+        ``dq_lzparse_hip_i32``, torch GPU tensors through ``dq_lzparse_hip_dev_i32`` on the current torch stream.  The
+        output is sized by a first call with no room, or ``phrases`` -- ``(cap, 3)`` int32 -- is filled and its filled
+        part returned (``_abi.last_rlz_info()["phrases"]`` holds the true count).
+        """
+        count = ctypes.c_int64(0)
+        if any(_is_torch_tensor(a) for a in (text, length, src, phrases)):
+            import torch
+
+            if not _is_torch_tensor(text):
+                raise TypeError("text, suffixes, lcp and phrases must all be host buffers or all torch GPU tensors")
+            if text.dtype != torch.uint8 or text.dim() != 1 or not text.is_contiguous():
+                raise TypeError("device text must be a contiguous 1-D uint8 tensor")
+            if not text.is_cuda:
+                raise TypeError("torch text tensors must live on the GPU; pass host data as bytes/numpy")
+            if text.numel() > INT_MAX:
+                raise ValueError("LzParse has 32-bit indices: the text must be shorter than 2^31 bytes")
+            ln, sr = self._lz_device_arrays(length, src, text, ("length", "src"))
+            n = text.numel()
+            dev, stream = _device_and_stream(text)
+            fn = self._lib.dq_lzparse_hip_dev_i32
+            ptrs = (text.data_ptr() if n else None, n, ln.data_ptr() if n else None, sr.data_ptr() if n else None)
+            if phrases is None:
+                _abi.check(fn(*ptrs, None, 0, ctypes.byref(count), dev, stream))
+                phrases = torch.empty((count.value, 3), dtype=torch.int32, device=text.device)
+            elif (not _is_torch_tensor(phrases) or phrases.dtype != torch.int32 or phrases.dim() != 2 or phrases.shape[1] != 3
+                  or not phrases.is_contiguous() or phrases.device != text.device):
+                raise TypeError("phrases must be a contiguous (cap, 3) int32 tensor on the text's device")
+            cap = phrases.shape[0]
+            _abi.check(fn(*ptrs, phrases.data_ptr() if cap else None, cap, ctypes.byref(count), dev, stream))
+            return phrases[:min(count.value, cap)]
+        T = _as_text(text)
+        n = T.size
+        if n > INT_MAX:
+            raise ValueError("LzParse has 32-bit indices: the text must be shorter than 2^31 bytes")
+        ln, sr = self._lz_host_arrays(length, src, n, ("length", "src"))
+        fn = self._lib.dq_lzparse_hip_i32
+        ptrs = (T.ctypes.data if n else None, n, ln.ctypes.data if n else None, sr.ctypes.data if n else None)
+        if phrases is None:
+            _abi.check(fn(*ptrs, None, 0, ctypes.byref(count), self.device))
+            phrases = np.empty((count.value, 3), dtype=np.int32)
+        elif (not isinstance(phrases, np.ndarray) or phrases.dtype != np.int32 or phrases.ndim != 2 or phrases.shape[1] != 3
+              or not phrases.flags.c_contiguous):
+            raise TypeError("phrases must be a contiguous (cap, 3) numpy int32 array")
+        cap = phrases.shape[0]
+        _abi.check(fn(*ptrs, phrases.ctypes.data if cap else None, cap, ctypes.byref(count), self.device))
+        return phrases[:min(count.value, cap)]
+
+    lzparse = LzParse
+
     @staticmethod
-    def _lz_host_arrays(suffixes, lcp, n):
-        for name, a in (("suffixes", suffixes), ("lcp", lcp)):
+    def _lz_host_arrays(suffixes, lcp, n, names=("suffixes", "lcp")):
+        for name, a in zip(names, (suffixes, lcp)):
             if _is_torch_tensor(a):
                 raise TypeError("text, suffixes, lcp and phrases must all be host buffers or all torch GPU tensors")
             if not isinstance(a, np.ndarray) or a.dtype != np.int32 or a.ndim != 1:
@@ -921,10 +1043,10 @@ class HipSuffixSort:
         return np.ascontiguousarray(suffixes), np.ascontiguousarray(lcp)
 
     @staticmethod
-    def _lz_device_arrays(suffixes, lcp, text):
+    def _lz_device_arrays(suffixes, lcp, text, names=("suffixes", "lcp")):
         import torch
 
-        for name, a in (("suffixes", suffixes), ("lcp", lcp)):
+        for name, a in zip(names, (suffixes, lcp)):
             if not _is_torch_tensor(a):
                 raise TypeError("text, suffixes, lcp and phrases must all be host buffers or all torch GPU tensors")
             if a.dtype != torch.int32 or a.dim() != 1 or not a.is_contiguous():
@@ -956,6 +1078,28 @@ def lz77_decode(phrases) -> bytes:
         else:
             for k in range(length):
                 out.append(out[third + k])
+    return bytes(out)
+
+
+def rlz_decode(old, phrases) -> bytes:
+    """The new file of a relative factorization ``HipSuffixSort.Rlz`` returned: literals ``(start, 0, byte)`` are appended,
+    a copy ``(start, len, src)`` is ``old[src:src + len]``.  A phrase that does not start where the one before it ends, or
+    that copies from outside old, is refused."""
+    if _is_torch_tensor(phrases):
+        phrases = phrases.cpu().numpy()
+    if _is_torch_tensor(old):
+        old = old.cpu().numpy()
+    base = _as_text(old).tobytes()
+    out = bytearray()
+    for start, length, third in np.asarray(phrases).reshape(-1, 3).tolist():
+        if start != len(out):
+            raise ValueError(f"phrase at {start} does not start where the one before it ends ({len(out)})")
+        if length == 0:
+            out.append(third)
+        elif length < 0 or not 0 <= third <= len(base) - length:
+            raise ValueError(f"phrase at {start} copies {length} bytes from {third}: outside old ({len(base)} bytes)")
+        else:
+            out += base[third:third + length]
     return bytes(out)
 
 

@@ -786,6 +786,70 @@ int32_t dq_lz77_hip_dev_i32(const void *d_text, int64_t n, const void *d_sa, con
                             void *d_phrases, int64_t cap, int64_t *count, int32_t device, void *stream);
 int32_t dq_lz77_last_info(int64_t *info, int32_t count);
 
+/* ---- matching statistics of a new file against an old one, and the relative Lempel-Ziv factorization, on the device ----
+ * new has m bytes, old has n bytes, m + n <= 2^31 - 1.  cat is NEW FOLLOWED BY OLD: new at [0, m), old at [m, m + n).  sa
+ * and lcp are cat's suffix array and LCP array as dq_sufsort_hip_* and dq_lcp_hip_* return them (lcp[0] = 0, no sentinel, a
+ * suffix ends at the end of the text), m + n entries each.  The order matters: old's suffixes end where cat ends, so their
+ * order in cat is old's own order and no comparison among them runs into foreign bytes; a suffix of new may run on into
+ * old, and the clamp below cuts exactly that.  (With old first the clamp would depend on the source.)
+ * For a position j < m with rank r: r' the nearest rank below r with sa[r'] >= m, r'' the nearest such rank above r;
+ *   p = sa[r'] - m,   cl = min(min lcp[r'+1 .. r],  m - j)
+ *   q = sa[r''] - m,  cr = min(min lcp[r+1 .. r''], m - j)        (a missing neighbour has nothing in common)
+ *   len[j] = max(cl, cr);  src[j] = p if cl >= cr, else q;  src[j] = -1 where len[j] == 0.
+ * lcp[r] belongs to the pair (r - 1, r): the old suffix at r'' brings its own lcp[r''] into cr, the one at r' brings
+ * nothing into cl.  len[j] is the length of the longest prefix of new[j..] that occurs anywhere in old, and
+ * old[src[j] .. src[j] + len[j]) is one occurrence of it: the matching statistics of new against old.  len and src have m
+ * entries in the text order of new; the mstat forms do not need the bytes.
+ * The relative factorization: phrases start at 0, the phrase at j has max(1, len[j]) bytes, the next one starts right
+ * behind it.  A phrase is three int32: a copy (j, len[j], src[j]) with src a position IN OLD, or a literal (j, 0, new[j]).
+ * Copies never overlap their output: old and the triples decode to new.  old "abab", new "babbc": len 3 2 1 1 0, src
+ * 1 0 1 1 -1, phrases (0,3,1) (3,1,1) (4,0,'c').  old "aaa", new "aaaaa": (0,3,0) (3,2,0).  old empty: literals only.
+ * dq_rlz_hip_* compute the statistics and parse them in one call; new_data is read only for the literals' bytes.
+ * dq_lzparse_hip_* are the parse alone, of a text of n bytes from any finished (len, src) pair in text order -- lpf / src of
+ * dq_lpf_hip_* (then the triples are dq_lz77_hip_*'s) or len / src of dq_mstat_hip_* with text = new; src[i] goes into
+ * the triple as it is.  phrases holds cap triples; *count (a host pointer in both forms) always receives the true number
+ * of phrases z; the first min(z, cap) triples are written and nothing beyond them.  cap == 0 with phrases == NULL is the
+ * sizing call.  m == 0 (n == 0 for the parse) returns DQ_OK before a device is looked for, with *count = 0; old may be
+ * empty (n == 0): every position is a literal.
+ *   negative sizes, negative cap, NULL count, a NULL buffer that is needed     DQ_ERR_BAD_ARGS
+ *   m + n > 2^31-1                                                              DQ_ERR_TOO_LARGE (all before any device work)
+ * Untrusted arrays, as for dq_lpf_hip_*: every sa entry is range-tested where it is read, one outside [0, m + n) is never
+ * an address and makes the call return DQ_ERR_BAD_ARGS (outputs undefined); lcp values are clamped to [0, m + n].  Every
+ * written len[j] lies in [0, min(m - j, n - src[j])], and src[j] lies in [-1, n), with len[j] == 0 exactly where
+ * src[j] == -1: with true arrays the second bound never binds, with nonsense it keeps a decoder inside old -- also where
+ * two ranks name one position of new, since every pair is settled by one thread behind the scatter -- and the triples of
+ * dq_rlz_hip_* inherit it.  A position of new that no rank names reads len 0, src -1.  The parse clamps every step to
+ * [1, m - j].  In-range arrays that are not cat's give DQ_OK and unspecified contents within these bounds, with no access
+ * outside the buffers; the work per rank does not depend on what the arrays hold.
+ * Computed as two prefix scans over rank order of one associative operator (deltaq_amd/csrc/dq_rlz.h): the nearest old
+ * suffix met and the minimum of lcp behind it; per tile of 1024 ranks a summary in each direction, ONE workgroup carries
+ * them over the tiles, then every tile scans again seeded with its carries and scatters len and src; a pass over new settles each pair.  Four launches, no
+ * walks: the cost does not depend on match lengths.  The parse is dq_lz77_hip_*'s five launches.
+ * Device memory, carved from the cached workspace of the slot the call leases: 32 bytes per 1024 ranks (a summary and a
+ * carry of 8 bytes in each direction) and a line of counters for an mstat call; a parse adds exits 4 bytes per byte of
+ * text, one bit per position and 8 bytes per 8192 positions; an rlz call adds both and len 4 + src 4 per byte of new:
+ * 12.2 m + 0.03 (m + n) bytes.  The host forms add their device copies of the arrays, the bytes and min(cap, m) triples.
+ * No CPU fallback: DQ_ERR_OOM when that does not fit.  The _dev_ forms take device pointers on `device`, enqueue on
+ * `stream` (NULL = the library's stream) and return after it has drained.  One stream wait per call.
+ * Out of scope: int64 forms, a many-pairs form, matching against a standing index without sorting cat again, sources in
+ * earlier parts of new (that is dq_lz77_hip_* of old + new), and computing sa or lcp inside these calls.
+ * dq_rlz_last_info: shape of the last of these six calls on this thread, reset when one starts; `count` entries (7 are
+ * defined, further ones read 0; a NULL array is DQ_ERR_BAD_ARGS): [0] phrases z, [1] literal phrases (both 0 in mstat
+ * calls); [2] the longest len (mstat calls) or the longest phrase (parse and rlz calls); [3] positions of new with
+ * len > 0 (0 in parse calls); [4] serial hops of the tile walker (0 in mstat calls); [5] kernel launches; [6] stream waits. */
+int32_t dq_mstat_hip_i32(const int32_t *sa, const int32_t *lcp, int64_t m, int64_t n, int32_t *len, int32_t *src, int32_t device);
+int32_t dq_mstat_hip_dev_i32(const void *d_sa, const void *d_lcp, int64_t m, int64_t n, void *d_len, void *d_src, int32_t device,
+                             void *stream);
+int32_t dq_rlz_hip_i32(const uint8_t *new_data, int64_t m, int64_t n, const int32_t *sa, const int32_t *lcp,
+                       int32_t *phrases, int64_t cap, int64_t *count, int32_t device);
+int32_t dq_rlz_hip_dev_i32(const void *d_new, int64_t m, int64_t n, const void *d_sa, const void *d_lcp,
+                           void *d_phrases, int64_t cap, int64_t *count, int32_t device, void *stream);
+int32_t dq_lzparse_hip_i32(const uint8_t *text, int64_t n, const int32_t *len, const int32_t *src,
+                           int32_t *phrases, int64_t cap, int64_t *count, int32_t device);
+int32_t dq_lzparse_hip_dev_i32(const void *d_text, int64_t n, const void *d_len, const void *d_src,
+                               void *d_phrases, int64_t cap, int64_t *count, int32_t device, void *stream);
+int32_t dq_rlz_last_info(int64_t *info, int32_t count);
+
 /* Device workspace (bytes) a sort of n bytes with index_bytes (4 or 8) wide indices needs,
  * excluding the caller's text and sa buffers: the device entry point's full layout (the reduced one at n = 2^32). */
 int64_t dq_sufsort_hip_workspace_bytes(int64_t n, int32_t index_bytes);
