@@ -11,6 +11,7 @@ using CommunityToolkit.HighPerformance.Buffers;
 using System;
 using System.Buffers;
 using System.Collections.Generic;
+using System.Linq;
 using System.Runtime.InteropServices;
 
 namespace DeltaQ.SuffixSorting.Hip;
@@ -150,6 +151,25 @@ public sealed class HipSuffixSort : ISuffixSort
 
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
     internal static extern unsafe int dq_lzparse_hip_dev_i32(IntPtr dText, long n, IntPtr dLen, IntPtr dSrc, IntPtr dPhrases, long cap, long* count, int device, IntPtr stream);
+
+    // many pairs in one call: cats (new FOLLOWED BY old) back to back, offsets / newOffsets of count + 1 entries, phraseOffsets is host memory
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    private static extern unsafe int dq_mstat_hip_many_i32(long* offsets, long* newOffsets, int count, int* sas, int* lcps, int* len, int* src, int device);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    private static extern unsafe int dq_rlz_hip_many_i32(byte* cats, long* offsets, long* newOffsets, int count, int* sas, int* lcps, int* phrases, long cap, long* phraseOffsets, int device);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    private static extern unsafe int dq_lzparse_hip_many_i32(byte* texts, long* offsets, int count, int* len, int* src, int* phrases, long cap, long* phraseOffsets, int device);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern int dq_mstat_hip_many_dev_i32(IntPtr dOffsets, IntPtr dNewOffsets, int count, IntPtr dSas, IntPtr dLcps, IntPtr dLen, IntPtr dSrc, int device, IntPtr stream);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern unsafe int dq_rlz_hip_many_dev_i32(IntPtr dCats, IntPtr dOffsets, IntPtr dNewOffsets, int count, IntPtr dSas, IntPtr dLcps, IntPtr dPhrases, long cap, long* phraseOffsets, int device, IntPtr stream);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern unsafe int dq_lzparse_hip_many_dev_i32(IntPtr dTexts, IntPtr dOffsets, int count, IntPtr dLen, IntPtr dSrc, IntPtr dPhrases, long cap, long* phraseOffsets, int device, IntPtr stream);
 
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
     private static extern unsafe int dq_rlz_last_info(long* info, int count);
@@ -1222,6 +1242,188 @@ public sealed class HipSuffixSort : ISuffixSort
     {
         var (len, src) = MatchStats(old.Length, newData.Length, suffixes, lcp);
         return LzParse(newData, len, src);
+    }
+
+    // The cats (new FOLLOWED BY old) of many pairs back to back with both offset arrays, and their suffix arrays and LCP
+    // arrays flat: SortMany and LcpMany of the cats.  At least one element each: the native side wants non-null pointers.
+    private (byte[] Cats, long[] Offsets, long[] NewOffsets, int[] Sas, int[] Lcps) ManyPairs(
+        IReadOnlyList<ReadOnlyMemory<byte>> olds, IReadOnlyList<ReadOnlyMemory<byte>> news)
+    {
+        if (olds.Count != news.Count)
+        {
+            throw new ArgumentException("one new file per old file");
+        }
+
+        int count = olds.Count;
+        var offsets = new long[count + 1];
+        var newOffsets = new long[count + 1];
+        for (int t = 0; t < count; t++)
+        {
+            offsets[t + 1] = offsets[t] + news[t].Length + olds[t].Length;
+            newOffsets[t + 1] = newOffsets[t] + news[t].Length;
+        }
+
+        if (offsets[count] > Array.MaxLength)
+        {
+            throw new ArgumentException("the pairs of one call must total less than 2^31 bytes");
+        }
+
+        var cats = new byte[Math.Max(offsets[count], 1)];
+        var texts = new ReadOnlyMemory<byte>[count];
+        for (int t = 0; t < count; t++)
+        {
+            news[t].Span.CopyTo(cats.AsSpan((int)offsets[t]));
+            olds[t].Span.CopyTo(cats.AsSpan((int)offsets[t] + news[t].Length));
+            texts[t] = cats.AsMemory((int)offsets[t], (int)(offsets[t + 1] - offsets[t]));
+        }
+
+        var sas = new int[cats.Length];
+        var lcps = new int[cats.Length];
+        if (newOffsets[count] > 0)
+        {
+            int[][] sorted = SortMany(texts);
+            int[][] common = LcpMany(texts, sorted.Select(s => (ReadOnlyMemory<int>)s).ToArray());
+            for (int t = 0; t < count; t++)
+            {
+                sorted[t].CopyTo(sas.AsSpan((int)offsets[t]));
+                common[t].CopyTo(lcps.AsSpan((int)offsets[t]));
+            }
+        }
+
+        return (cats, offsets, newOffsets, sas, lcps);
+    }
+
+    /// <summary>
+    /// <see cref="MatchStats(ReadOnlySpan{byte}, ReadOnlySpan{byte})"/> of many pairs in one native call
+    /// (dq_mstat_hip_many_i32) behind <c>SortMany</c> and <c>LcpMany</c> of new + old: a fixed number of launches and
+    /// one wait, whatever the number of pairs.  Entry t is what the single call gives for pair t alone.
+    /// </summary>
+    public unsafe (int[] Len, int[] Src)[] MatchStatsMany(IReadOnlyList<ReadOnlyMemory<byte>> olds, IReadOnlyList<ReadOnlyMemory<byte>> news)
+    {
+        var (_, offsets, newOffsets, sas, lcps) = ManyPairs(olds, news);
+        int count = olds.Count;
+        var len = new int[Math.Max(newOffsets[count], 1)];
+        var src = new int[len.Length];
+        int rc;
+        fixed (long* pOffsets = offsets)
+        fixed (long* pNewOffsets = newOffsets)
+        fixed (int* pSas = sas)
+        fixed (int* pLcps = lcps)
+        fixed (int* pLen = len)
+        fixed (int* pSrc = src)
+        {
+            rc = dq_mstat_hip_many_i32(pOffsets, pNewOffsets, count, pSas, pLcps, pLen, pSrc, _device);
+        }
+
+        LcpResult(rc, "dq_mstat_hip_many_i32");
+        var result = new (int[] Len, int[] Src)[count];
+        for (int t = 0; t < count; t++)
+        {
+            result[t] = (len.AsSpan((int)newOffsets[t], news[t].Length).ToArray(), src.AsSpan((int)newOffsets[t], news[t].Length).ToArray());
+        }
+
+        return result;
+    }
+
+    /// <summary>
+    /// <see cref="Rlz(ReadOnlySpan{byte}, ReadOnlySpan{byte})"/> of many pairs in one native call (dq_rlz_hip_many_i32):
+    /// entry t holds pair t's phrases, three ints each with starts counted from the start of its own new file, and
+    /// <see cref="RlzDecode"/> of it with olds[t] gives news[t].  The statistics are computed once: the call has room for
+    /// a phrase per byte of the new files.
+    /// </summary>
+    public unsafe int[][] RlzMany(IReadOnlyList<ReadOnlyMemory<byte>> olds, IReadOnlyList<ReadOnlyMemory<byte>> news)
+    {
+        var (cats, offsets, newOffsets, sas, lcps) = ManyPairs(olds, news);
+        int count = olds.Count;
+        long cap = newOffsets[count];
+        var phrases = new int[Math.Max(checked(3 * cap), 1)];
+        var phraseOffsets = new long[count + 1];
+        int rc;
+        fixed (byte* pCats = cats)
+        fixed (long* pOffsets = offsets)
+        fixed (long* pNewOffsets = newOffsets)
+        fixed (int* pSas = sas)
+        fixed (int* pLcps = lcps)
+        fixed (int* pPhrases = phrases)
+        fixed (long* pPhraseOffsets = phraseOffsets)
+        {
+            rc = dq_rlz_hip_many_i32(pCats, pOffsets, pNewOffsets, count, pSas, pLcps, pPhrases, cap, pPhraseOffsets, _device);
+        }
+
+        LcpResult(rc, "dq_rlz_hip_many_i32");
+        return SplitPhrases(phrases, phraseOffsets);
+    }
+
+    /// <summary>
+    /// <see cref="LzParse"/> of many texts in one native call (dq_lzparse_hip_many_i32): texts, len and src arrays of
+    /// equal lengths pair by pair.  The output is sized by a first native call with no room.
+    /// </summary>
+    public unsafe int[][] LzParseMany(IReadOnlyList<ReadOnlyMemory<byte>> texts, IReadOnlyList<ReadOnlyMemory<int>> lens,
+                                      IReadOnlyList<ReadOnlyMemory<int>> srcs)
+    {
+        int count = texts.Count;
+        if (lens.Count != count || srcs.Count != count)
+        {
+            throw new ArgumentException("LzParseMany takes one len array and one src array per text");
+        }
+
+        var offsets = new long[count + 1];
+        for (int t = 0; t < count; t++)
+        {
+            if (lens[t].Length != texts[t].Length || srcs[t].Length != texts[t].Length)
+            {
+                ThrowHelper();
+            }
+
+            offsets[t + 1] = offsets[t] + texts[t].Length;
+        }
+
+        if (offsets[count] > Array.MaxLength)
+        {
+            throw new ArgumentException("the texts of one LzParseMany call must total less than 2^31 bytes");
+        }
+
+        var flat = new byte[Math.Max(offsets[count], 1)];
+        var len = new int[flat.Length];
+        var src = new int[flat.Length];
+        for (int t = 0; t < count; t++)
+        {
+            texts[t].Span.CopyTo(flat.AsSpan((int)offsets[t]));
+            lens[t].Span.CopyTo(len.AsSpan((int)offsets[t]));
+            srcs[t].Span.CopyTo(src.AsSpan((int)offsets[t]));
+        }
+
+        var phraseOffsets = new long[count + 1];
+        int rc;
+        fixed (byte* pTexts = flat)
+        fixed (long* pOffsets = offsets)
+        fixed (int* pLen = len)
+        fixed (int* pSrc = src)
+        fixed (long* pPhraseOffsets = phraseOffsets)
+        {
+            rc = dq_lzparse_hip_many_i32(pTexts, pOffsets, count, pLen, pSrc, null, 0, pPhraseOffsets, _device);
+            LcpResult(rc, "dq_lzparse_hip_many_i32");
+            long z = phraseOffsets[count];
+            var phrases = new int[Math.Max(checked(3 * z), 1)];
+            fixed (int* pPhrases = phrases)
+            {
+                rc = dq_lzparse_hip_many_i32(pTexts, pOffsets, count, pLen, pSrc, pPhrases, z, pPhraseOffsets, _device);
+            }
+
+            LcpResult(rc, "dq_lzparse_hip_many_i32");
+            return SplitPhrases(phrases, phraseOffsets);
+        }
+    }
+
+    private static int[][] SplitPhrases(int[] phrases, long[] phraseOffsets)
+    {
+        var result = new int[phraseOffsets.Length - 1][];
+        for (int t = 0; t < result.Length; t++)
+        {
+            result[t] = phrases.AsSpan(checked((int)(3 * phraseOffsets[t])), checked((int)(3 * (phraseOffsets[t + 1] - phraseOffsets[t])))).ToArray();
+        }
+
+        return result;
     }
 
     /// <summary>

@@ -64,6 +64,8 @@ EXPORTS = (
     "dq_lpf_hip_i32", "dq_lpf_hip_dev_i32", "dq_lz77_hip_i32", "dq_lz77_hip_dev_i32", "dq_lz77_last_info",
     "dq_mstat_hip_i32", "dq_mstat_hip_dev_i32", "dq_rlz_hip_i32", "dq_rlz_hip_dev_i32",
     "dq_lzparse_hip_i32", "dq_lzparse_hip_dev_i32", "dq_rlz_last_info",
+    "dq_mstat_hip_many_i32", "dq_mstat_hip_many_dev_i32", "dq_rlz_hip_many_i32", "dq_rlz_hip_many_dev_i32",
+    "dq_lzparse_hip_many_i32", "dq_lzparse_hip_many_dev_i32",
     "dq_bsdiff_search_dev_i32", "dq_bsdiff_search_dev_i64", "dq_bsdiff_search_i32", "dq_bsdiff_search_i64",
     "dq_bsdiff_create", "dq_bsdiff_patch_bound", "dq_bsdiff_scan_i32", "dq_bspatch_apply",
     "dq_bspatch_new_size_many", "dq_bspatch_apply_many", "dq_bspatch_index_apply_many",
@@ -221,6 +223,18 @@ def load() -> ctypes.CDLL:
     L.dq_lzparse_hip_i32.argtypes = [vp, i64, vp, vp, vp, i64, ctypes.POINTER(i64), i32]
     L.dq_lzparse_hip_dev_i32.restype = i32
     L.dq_lzparse_hip_dev_i32.argtypes = [vp, i64, vp, vp, vp, i64, ctypes.POINTER(i64), i32, vp]
+    L.dq_mstat_hip_many_i32.restype = i32
+    L.dq_mstat_hip_many_i32.argtypes = [vp, vp, i32, vp, vp, vp, vp, i32]
+    L.dq_mstat_hip_many_dev_i32.restype = i32
+    L.dq_mstat_hip_many_dev_i32.argtypes = [vp, vp, i32, vp, vp, vp, vp, i32, vp]
+    L.dq_rlz_hip_many_i32.restype = i32
+    L.dq_rlz_hip_many_i32.argtypes = [vp, vp, vp, i32, vp, vp, vp, i64, vp, i32]
+    L.dq_rlz_hip_many_dev_i32.restype = i32
+    L.dq_rlz_hip_many_dev_i32.argtypes = [vp, vp, vp, i32, vp, vp, vp, i64, vp, i32, vp]
+    L.dq_lzparse_hip_many_i32.restype = i32
+    L.dq_lzparse_hip_many_i32.argtypes = [vp, vp, i32, vp, vp, vp, i64, vp, i32]
+    L.dq_lzparse_hip_many_dev_i32.restype = i32
+    L.dq_lzparse_hip_many_dev_i32.argtypes = [vp, vp, i32, vp, vp, vp, i64, vp, i32, vp]
     L.dq_rlz_last_info.restype = i32
     L.dq_rlz_last_info.argtypes = [ctypes.POINTER(i64), i32]
     L.dq_sufsort_hip_batch_i32.restype = i32

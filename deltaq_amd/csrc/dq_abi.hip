@@ -454,6 +454,57 @@ int32_t dq_lzparse_hip_dev_i32(const void *d_text, int64_t n, const void *d_len,
     return lzparse_dev(d_text, n, d_len, d_src, d_phrases, cap, count, device, stream);
 }
 
+int32_t dq_mstat_hip_many_i32(const int64_t *offsets, const int64_t *new_offsets, int32_t count, const int32_t *sas,
+                              const int32_t *lcps, int32_t *len, int32_t *src, int32_t device)
+{
+    EnvScope scope;
+    t_rlz_info = {};
+    return mstat_many_host(offsets, new_offsets, count, sas, lcps, len, src, device);
+}
+
+int32_t dq_mstat_hip_many_dev_i32(const void *d_offsets, const void *d_new_offsets, int32_t count, const void *d_sas,
+                                  const void *d_lcps, void *d_len, void *d_src, int32_t device, void *stream)
+{
+    EnvScope scope;
+    t_rlz_info = {};
+    return mstat_many_dev(d_offsets, d_new_offsets, count, d_sas, d_lcps, d_len, d_src, device, stream);
+}
+
+int32_t dq_rlz_hip_many_i32(const uint8_t *cats, const int64_t *offsets, const int64_t *new_offsets, int32_t count,
+                            const int32_t *sas, const int32_t *lcps, int32_t *phrases, int64_t cap, int64_t *phrase_offsets,
+                            int32_t device)
+{
+    EnvScope scope;
+    t_rlz_info = {};
+    return rlz_many_host(cats, offsets, new_offsets, count, sas, lcps, phrases, cap, phrase_offsets, device);
+}
+
+int32_t dq_rlz_hip_many_dev_i32(const void *d_cats, const void *d_offsets, const void *d_new_offsets, int32_t count,
+                                const void *d_sas, const void *d_lcps, void *d_phrases, int64_t cap, int64_t *phrase_offsets,
+                                int32_t device, void *stream)
+{
+    EnvScope scope;
+    t_rlz_info = {};
+    return rlz_many_dev(d_cats, d_offsets, d_new_offsets, count, d_sas, d_lcps, d_phrases, cap, phrase_offsets, device, stream);
+}
+
+int32_t dq_lzparse_hip_many_i32(const uint8_t *texts, const int64_t *offsets, int32_t count, const int32_t *len,
+                                const int32_t *src, int32_t *phrases, int64_t cap, int64_t *phrase_offsets, int32_t device)
+{
+    EnvScope scope;
+    t_rlz_info = {};
+    return lzparse_many_host(texts, offsets, count, len, src, phrases, cap, phrase_offsets, device);
+}
+
+int32_t dq_lzparse_hip_many_dev_i32(const void *d_texts, const void *d_offsets, int32_t count, const void *d_len,
+                                    const void *d_src, void *d_phrases, int64_t cap, int64_t *phrase_offsets, int32_t device,
+                                    void *stream)
+{
+    EnvScope scope;
+    t_rlz_info = {};
+    return lzparse_many_dev(d_texts, d_offsets, count, d_len, d_src, d_phrases, cap, phrase_offsets, device, stream);
+}
+
 int32_t dq_rlz_last_info(int64_t *info, int32_t count) { return last_info(t_rlz_info, info, count, "null info array"); }
 
 int32_t dq_sufsort_hip_batch_i32(int32_t count, const uint8_t *const *texts, const int64_t *lens,

@@ -619,4 +619,199 @@ __global__ __launch_bounds__(kBlock) void lz_emit_kernel(const uint8_t *__restri
     }
 }
 
+// ---------------------------------------------------------------------------------------------- the parse of many texts
+// Texts back to back, text t at positions [off[t], off[t + 1]) of lpf / src (dq_lzparse_hip_many_*; the new files of
+// dq_rlz_hip_many_*).  Every step is clamped to its own text's end, so every text start is a phrase start and next[]
+// over the concatenation is one increasing chain through all of them: the tile kernels are the one-text kernels with the
+// text's end in the clamp and its start taken off the triple.  The walk is one lane per text from its own start to its
+// own end (lz_walk_many_kernel); a tile's entry is the minimum over what the lanes report -- the chain from there passes
+// every later text start of the tile.  lz_offsets_kernel turns the scanned tile counts and the bitmap into the phrases
+// before each text.
+struct LzTexts {
+    const int64_t *off;                          // count + 1: the layout of lpf / src, the triples' starts count from off[t]
+    const int64_t *bytes;                        // count + 1: text t's bytes begin at T[bytes[t]] (off itself, or the cats' offsets)
+    int32_t count;
+};
+
+// the text that holds position i, among texts lo .. hi (off[lo] <= i < off[hi + 1]): the last t with off[t] <= i
+__device__ __forceinline__ int32_t lz_text_of(const int64_t *__restrict__ off, int32_t lo, int32_t hi, int64_t i)
+{
+    ++hi;
+    while (hi - lo > 1) {
+        const int32_t mid = (int32_t)(((int64_t)lo + hi) >> 1);
+        if (off[mid] <= i) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// next[] of tile t0 .. into LDS: i + clamp(lpf[i], 1, end of i's text - i); n for the rest of the tile
+__device__ __forceinline__ void lz_load_next_many(const int32_t *__restrict__ lpf, const LzTexts &tx, int64_t n, int64_t t0, int32_t *s_next)
+{
+    const int64_t last = t0 + kLzTile < n ? t0 + kLzTile - 1 : n - 1;       // (t0 < n: the tile holds a position)
+    const int32_t lo = lz_text_of(tx.off, 0, tx.count - 1, t0), hi = lz_text_of(tx.off, lo, tx.count - 1, last);
+#pragma unroll 4
+    for (int k = 0; k < kLzPer; ++k) {
+        const int at = k * kBlock + (int)threadIdx.x;
+        const int64_t i = t0 + at;
+        int64_t nx = n;
+        if (i < n) {
+            int64_t end = tx.off[lz_text_of(tx.off, lo, hi, i) + 1];
+            end = end > n ? n : (end <= i ? i + 1 : end);                    // (the host checked the layout)
+            const int64_t f = lpf[i];
+            nx = i + (f < 1 ? 1 : (f > end - i ? end - i : f));
+        }
+        s_next[at] = (int32_t)nx;
+    }
+}
+
+// lz_exit_kernel over the concatenation
+__global__ __launch_bounds__(kBlock) void lz_exit_many_kernel(const int32_t *__restrict__ lpf, LzTexts tx, int64_t n,
+                                                              int32_t *__restrict__ exits)
+{
+    __shared__ int32_t s_next[kLzTile];
+    const int64_t t0 = (int64_t)blockIdx.x * kLzTile;
+    const int64_t e64 = t0 + kLzTile < n ? t0 + kLzTile : n;
+    const int32_t e = (int32_t)e64, b0 = (int32_t)t0;
+    lz_load_next_many(lpf, tx, n, t0, s_next);
+    __syncthreads();
+    for (int round = 0; round < kLzJumpRounds; ++round) {
+        int32_t nv[kLzPer];
+        bool moved = false;
+#pragma unroll
+        for (int k = 0; k < kLzPer; ++k) {
+            const int32_t j = s_next[k * kBlock + (int)threadIdx.x];
+            const bool inside = j < e;                                       // (then b0 < j: next[] increases)
+            nv[k] = inside ? s_next[j - b0] : j;
+            moved = moved || inside;
+        }
+        if (!__syncthreads_or(moved)) break;                                 // (uniform; and every read is over)
+#pragma unroll
+        for (int k = 0; k < kLzPer; ++k) s_next[k * kBlock + (int)threadIdx.x] = nv[k];
+        __syncthreads();
+    }
+#pragma unroll 4
+    for (int k = 0; k < kLzPer; ++k) {
+        const int at = k * kBlock + (int)threadIdx.x;
+        if (t0 + at < n) exits[t0 + at] = s_next[at];
+    }
+}
+
+// One lane per text.  entry[] was filled with -1, which as an unsigned word is above every position: a tile's entry is
+// the least position a lane enters it at.  Every hop leaves its tile (forced) and no lane leaves its text, so a lane makes
+// at most one hop per tile its text touches; the hops of all lanes are summed.
+__global__ __launch_bounds__(kBlock) void lz_walk_many_kernel(const int32_t *__restrict__ exits, LzTexts tx, int64_t n,
+                                                              int32_t *__restrict__ entry, LzCounters *ctr)
+{
+    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    unsigned long long hops = 0;
+    if (t < tx.count) {
+        int64_t pos = tx.off[t], end = tx.off[t + 1];
+        end = end > n ? n : end;
+        while (pos >= 0 && pos < end) {
+            const int64_t tile = pos / kLzTile;
+            __hip_atomic_fetch_min(reinterpret_cast<uint32_t *>(entry) + tile, (uint32_t)pos, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const int64_t edge = (tile + 1) * kLzTile;
+            const int64_t nx = exits[pos];
+            pos = nx < edge ? edge : nx;
+            ++hops;
+        }
+    }
+    hops = wave_sum(hops);
+    if (lane_id() == 0 && hops) __hip_atomic_fetch_add(&ctr->hops, hops, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// lz_mark_kernel over the concatenation
+__global__ __launch_bounds__(kBlock) void lz_mark_many_kernel(const int32_t *__restrict__ lpf, LzTexts tx, int64_t n,
+                                                              const int32_t *__restrict__ entry, uint32_t *__restrict__ bits,
+                                                              uint32_t *__restrict__ tile_count)
+{
+    __shared__ int32_t s_next[kLzTile];
+    __shared__ uint32_t s_bits[kBlock];
+    const int64_t t0 = (int64_t)blockIdx.x * kLzTile;
+    const int64_t e = t0 + kLzTile < n ? t0 + kLzTile : n;
+    const int64_t first = entry[blockIdx.x];
+    s_bits[threadIdx.x] = 0;
+    const bool visited = first >= t0 && first < e;                           // (uniform) -1: the phrases jump over this tile
+    if (visited) lz_load_next_many(lpf, tx, n, t0, s_next);
+    __syncthreads();
+    if (visited && threadIdx.x == 0) {
+        uint32_t count = 0;
+        int64_t pos = first;
+        while (pos < e) {                                                    // next[] increases: at most kLzTile steps
+            const int at = (int)(pos - t0);
+            s_bits[at >> 5] |= 1u << (at & 31);
+            pos = s_next[at];
+            ++count;
+        }
+        tile_count[blockIdx.x] = count;
+    }
+    if (!visited && threadIdx.x == 0) tile_count[blockIdx.x] = 0;
+    __syncthreads();
+    bits[(int64_t)blockIdx.x * kBlock + threadIdx.x] = s_bits[threadIdx.x];
+}
+
+// lz_emit_kernel over the concatenation: a copy is (i - start of its text, len, src[i]), a literal (.., 0, its byte)
+__global__ __launch_bounds__(kBlock) void lz_emit_many_kernel(const uint8_t *__restrict__ T, const int32_t *__restrict__ lpf,
+                                                              const int32_t *__restrict__ src, LzTexts tx, int64_t n,
+                                                              const uint32_t *__restrict__ bits, const uint32_t *__restrict__ tile_off,
+                                                              int32_t *__restrict__ phrases, int64_t cap, LzCounters *ctr)
+{
+    __shared__ uint32_t s_tmp[kWavesPerBlock];
+    uint32_t word = bits[(int64_t)blockIdx.x * kBlock + threadIdx.x];
+    const int64_t i0 = (int64_t)blockIdx.x * kLzTile + (int64_t)threadIdx.x * kLzPer;
+    uint32_t total;
+    int64_t at = (int64_t)tile_off[blockIdx.x] + block_excl_sum((uint32_t)__builtin_popcount(word), s_tmp, &total);
+    uint32_t literals = 0, longest = 0;
+    int32_t t = -1;
+    int64_t base = 0, end = 0;                                               // the text of the bit before: [base, end)
+    while (word) {
+        const int64_t i = i0 + __builtin_ctz(word);
+        word &= word - 1;
+        if (i < n) {                                                         // (a set bit is a position of a text)
+            if (i >= end) {
+                t = lz_text_of(tx.off, t < 0 ? 0 : t, tx.count - 1, i);
+                base = tx.off[t];
+                end = tx.off[t + 1];
+                end = end > n ? n : (end <= i ? i + 1 : end);
+            }
+            const int64_t f = lpf[i];
+            const int32_t len = (int32_t)(f < 0 ? 0 : (f > end - i ? end - i : f));
+            const int32_t third = len ? src[i] : (int32_t)T[tx.bytes[t] + (i - base)];
+            literals += len == 0;
+            longest = (uint32_t)(len ? len : 1) > longest ? (uint32_t)(len ? len : 1) : longest;
+            if (at < cap) {
+                phrases[3 * at] = (int32_t)(i - base);
+                phrases[3 * at + 1] = len;
+                phrases[3 * at + 2] = third;
+            }
+        }
+        ++at;
+    }
+    literals = wave_sum(literals);
+    longest = wave_max(longest);
+    if (lane_id() == 0) {
+        if (literals) __hip_atomic_fetch_add(&ctr->literals, literals, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        lz_raise(&ctr->longest_phrase, longest);
+    }
+}
+
+// One thread per entry of phrase_offsets[0 .. count]: the phrases that start before text t's first position -- the
+// scanned count of its tile and the bits of the tile below it; behind the last position: all of them (lz_scan_kernel's z).
+__global__ __launch_bounds__(kBlock) void lz_offsets_kernel(LzTexts tx, int64_t n, const uint32_t *__restrict__ bits,
+                                                            const uint32_t *__restrict__ tile_off, const LzCounters *__restrict__ ctr,
+                                                            int64_t *__restrict__ phrase_offsets)
+{
+    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (t > tx.count) return;
+    const int64_t p = tx.off[t];
+    if (p < 0 || p >= n) { phrase_offsets[t] = p < 0 ? 0 : (int64_t)ctr->phrases; return; }
+    const int64_t tile = p / kLzTile;
+    const int in = (int)(p - tile * kLzTile);
+    const uint32_t *w = bits + tile * kBlock;
+    uint32_t before = 0;
+    for (int k = 0; k < (in >> 5); ++k) before += (uint32_t)__builtin_popcount(w[k]);
+    if (in & 31) before += (uint32_t)__builtin_popcount(w[in >> 5] & ((1u << (in & 31)) - 1u));
+    phrase_offsets[t] = (int64_t)tile_off[tile] + before;
+}
+
 }  // namespace dq

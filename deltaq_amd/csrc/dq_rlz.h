@@ -59,10 +59,15 @@ struct MsState {
 };
 static_assert(sizeof(MsState) == 8);
 
-__device__ __forceinline__ MsState ms_none() { return MsState{-1, kLpfNone}; }
+// A second "none" of pos, the cut between two pairs of a many call (below): no old suffix met, and nothing from beyond
+// passes.  Whatever is not kMsNonePos blocks, so the state stays 8 bytes and every scan keeps its shape; a one-pair call
+// never forms it.
+constexpr int32_t kMsNonePos = -1, kMsCutPos = -2;
+__device__ __forceinline__ MsState ms_none() { return MsState{kMsNonePos, kLpfNone}; }
+__device__ __forceinline__ MsState ms_cut() { return MsState{kMsCutPos, kLpfNone}; }
 __device__ __forceinline__ MsState ms_join(MsState far, MsState near)
 {
-    if (near.pos >= 0) return near;
+    if (near.pos != kMsNonePos) return near;
     return MsState{far.pos, near.mn < far.mn ? near.mn : far.mn};
 }
 
@@ -289,6 +294,207 @@ __global__ __launch_bounds__(kBlock) void ms_settle_kernel(int32_t *__restrict__
     const int32_t t = g > 0 ? s : -1;
     if ((int32_t)g != f) len[j] = (int32_t)g;
     if (t != s) src[j] = t;
+}
+
+// ---------------------------------------------------------------------------------------------- many pairs in one call
+// Flat ranks over the whole call: rank g belongs to the text t whose [offsets[t], offsets[t + 1]) holds it (found as
+// lcp_segment of dq_lcp.h finds it; an empty text has no rank).  cat_t = new_t followed by old_t, m_t from new_offsets,
+// n_t the rest; the entries of SA and LCP count from the start of their own text.  The first rank of a text folds in a
+// cut instead of its LCP value, which therefore is never read for anything: upwards (an old suffix: itself, it blocks
+// anyway; a new one: ms_cut()), downwards ms_cut() for both -- a first rank's own entry serves only ranks below it, and
+// those are another pair's.  So no state passes a pair's first rank upwards or its last rank downwards, and summary,
+// carry (ms_carry_kernel itself) and apply are the one-pair scheme.  A thread's four ranks may lie in four pairs.
+struct MsSegs {
+    const int64_t *offsets;                      // count + 1: the cats
+    const int64_t *new_offsets;                  // count + 1: the new files, and the layout of len / src
+    int32_t count;
+};
+
+// the text that holds index g of a layout `off` (off[lo] <= g < off[hi]): the last t with off[t] <= g
+__device__ __forceinline__ int32_t ms_text_of(const int64_t *__restrict__ off, int32_t lo, int32_t hi, int64_t g)
+{
+    while (hi - lo > 1) {
+        const int32_t mid = (int32_t)(((int64_t)lo + hi) >> 1);
+        if (off[mid] <= g) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// A thread's four ranks of a many call.  v: the SA entry (-1: outside its own text, or no rank of the call), l: the LCP
+// value clamped to its text (kLpfNone: no rank), m / n: its pair's sizes, out: where its pair's len / src begin, first:
+// the first rank of its text.  Returns whether an entry lay outside its own text.
+struct MsRanks {
+    int32_t v[kMsPer], l[kMsPer], m[kMsPer], n[kMsPer];
+    int64_t out[kMsPer];
+    bool first[kMsPer];
+};
+__device__ __forceinline__ bool ms_load_ranks_many(const int32_t *__restrict__ SA, const int32_t *__restrict__ LCP, const MsSegs &sg,
+                                                   int64_t r, int64_t total, MsRanks *q)
+{
+    const bool vec = ((reinterpret_cast<uintptr_t>(SA) | reinterpret_cast<uintptr_t>(LCP)) & 15u) == 0;
+    ms_load4(SA, r, total, vec, -1, q->v);
+    ms_load4(LCP, r, total, vec, 0, q->l);
+    bool outside = false;
+    int32_t t = -1;
+    int64_t base = 0, end = 0;                                               // the text of the rank before: [base, end)
+#pragma unroll
+    for (int k = 0; k < kMsPer; ++k) {
+        const int64_t g = r + k;
+        q->m[k] = 0; q->n[k] = 0; q->out[k] = 0; q->first[k] = false;
+        if (g < total) {
+            if (g >= end) {
+                t = ms_text_of(sg.offsets, t < 0 ? 0 : t, sg.count, g);
+                base = sg.offsets[t];
+                end = sg.offsets[t + 1];
+            }
+            const int64_t size = end - base, out = sg.new_offsets[t];
+            int64_t m = sg.new_offsets[t + 1] - out;
+            m = m < 0 ? 0 : (m > size ? size : m);                           // (the host checked it)
+            const bool in = q->v[k] >= 0 && (int64_t)q->v[k] < size;
+            outside = outside || !in;
+            q->v[k] = in ? q->v[k] : -1;
+            q->l[k] = lpf_lcp_value(q->l[k], size);
+            q->m[k] = (int32_t)m;
+            q->n[k] = (int32_t)(size - m);
+            q->out[k] = out;
+            q->first[k] = g == base;
+        } else {
+            q->v[k] = -1;
+            q->l[k] = kLpfNone;
+        }
+    }
+    return outside;
+}
+
+// what rank k folds in, scanning upwards and downwards (a rank beyond the call: nothing)
+__device__ __forceinline__ MsState ms_elem_up(const MsRanks &q, int k)
+{
+    const bool old = q.v[k] >= q.m[k] && q.v[k] >= 0;
+    if (old) return MsState{q.v[k] - q.m[k], kLpfNone};
+    return q.first[k] ? ms_cut() : MsState{kMsNonePos, q.l[k]};
+}
+__device__ __forceinline__ MsState ms_elem_down(const MsRanks &q, int k)
+{
+    if (q.first[k]) return ms_cut();
+    const bool old = q.v[k] >= q.m[k] && q.v[k] >= 0;
+    return MsState{old ? q.v[k] - q.m[k] : kMsNonePos, q.l[k]};
+}
+
+__device__ __forceinline__ void ms_fold_many(const MsRanks &q, MsState *up, MsState *down)
+{
+    MsState a = ms_none(), b = ms_none();
+#pragma unroll
+    for (int k = 0; k < kMsPer; ++k) {
+        a = ms_join(a, ms_elem_up(q, k));
+        b = ms_join(b, ms_elem_down(q, kMsPer - 1 - k));
+    }
+    *up = a;
+    *down = b;
+}
+
+__global__ __launch_bounds__(kBlock) void ms_many_summary_kernel(const int32_t *__restrict__ SA, const int32_t *__restrict__ LCP,
+                                                                 MsSegs sg, int64_t total, MsState *__restrict__ sum_up,
+                                                                 MsState *__restrict__ sum_down, LzCounters *ctr)
+{
+    __shared__ MsState s_up[kWavesPerBlock], s_down[kWavesPerBlock];
+    const int64_t r = (int64_t)blockIdx.x * kMsTile + (int64_t)threadIdx.x * kMsPer;
+    MsRanks q;
+    const bool outside = ms_load_ranks_many(SA, LCP, sg, r, total, &q);
+    MsState up, down, tot_up, tot_down;
+    ms_fold_many(q, &up, &down);
+    ms_block_excl<false>(up, ms_none(), s_up, &tot_up);
+    ms_block_excl<true>(down, ms_none(), s_down, &tot_down);
+    if (threadIdx.x == 0) {
+        sum_up[blockIdx.x] = tot_up;
+        sum_down[blockIdx.x] = tot_down;
+    }
+    if (__ballot(outside) && lane_id() == 0) __hip_atomic_fetch_or(&ctr->flags, kLzOutOfRange, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// ms_apply_kernel with each rank's own pair: scatters len[new_offsets[t] + SA[r]], src[...]
+__global__ __launch_bounds__(kBlock) void ms_many_apply_kernel(const int32_t *__restrict__ SA, const int32_t *__restrict__ LCP, MsSegs sg,
+                                                               int64_t total, const MsState *__restrict__ car_up,
+                                                               const MsState *__restrict__ car_down, int32_t *__restrict__ len,
+                                                               int32_t *__restrict__ src, LzCounters *ctr)
+{
+    __shared__ MsState s_up[kWavesPerBlock], s_down[kWavesPerBlock];
+    __shared__ uint32_t s_longest[kWavesPerBlock], s_unmatched[kWavesPerBlock];
+    const int64_t r = (int64_t)blockIdx.x * kMsTile + (int64_t)threadIdx.x * kMsPer;
+    MsRanks q;
+    ms_load_ranks_many(SA, LCP, sg, r, total, &q);
+    MsState up, down, all;
+    ms_fold_many(q, &up, &down);
+    up = ms_block_excl<false>(up, car_up[blockIdx.x], s_up, &all);           // everything before this thread's ranks
+    down = ms_block_excl<true>(down, car_down[blockIdx.x], s_down, &all);    // everything behind them
+    int32_t pl[kMsPer], cl[kMsPer];
+#pragma unroll
+    for (int k = 0; k < kMsPer; ++k) {
+        up = ms_join(up, ms_elem_up(q, k));
+        pl[k] = up.pos;
+        cl[k] = up.mn;
+    }
+    uint32_t longest = 0, unmatched = 0;
+#pragma unroll
+    for (int k = kMsPer - 1; k >= 0; --k) {
+        const int32_t j = q.v[k];
+        const int64_t m = q.m[k], n = q.n[k];
+        if (j >= 0 && (int64_t)j < m) {                                      // a suffix of its pair's new file
+            const int64_t room = m - j;
+            int64_t a = pl[k] < 0 ? 0 : cl[k], b = down.pos < 0 ? 0 : down.mn;
+            a = a > room ? room : a;
+            b = b > room ? room : b;
+            const bool left = a >= b;
+            int64_t f = left ? a : b;
+            int32_t s = -1;
+            if (f > 0) {
+                s = left ? pl[k] : down.pos;                                 // of this pair: nothing passes a cut; tested all the same
+                if ((int64_t)s >= n) { s = -1; f = 0; }
+                else f = f > n - s ? n - s : f;
+            }
+            len[q.out[k] + j] = (int32_t)f;
+            src[q.out[k] + j] = s;
+            longest = (uint32_t)f > longest ? (uint32_t)f : longest;
+            unmatched += f == 0;
+        }
+        down = ms_join(down, ms_elem_down(q, k));
+    }
+    longest = wave_max(longest);
+    unmatched = wave_sum(unmatched);
+    if (lane_id() == 0) {
+        s_longest[threadIdx.x >> 6] = longest;
+        s_unmatched[threadIdx.x >> 6] = unmatched;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int i = 1; i < kWavesPerBlock; ++i) {
+            longest = s_longest[i] > longest ? s_longest[i] : longest;
+            unmatched += s_unmatched[i];
+        }
+        lz_raise(&ctr->longest_lpf, longest);
+        if (unmatched) __hip_atomic_fetch_add(&ctr->unmatched, unmatched, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// ms_settle_kernel per position of the new layout, with its pair's m_t and n_t
+__global__ __launch_bounds__(kBlock) void ms_many_settle_kernel(int32_t *__restrict__ len, int32_t *__restrict__ src, MsSegs sg,
+                                                                int64_t positions)
+{
+    const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (p >= positions) return;
+    const int32_t t = ms_text_of(sg.new_offsets, 0, sg.count, p);
+    const int64_t j = p - sg.new_offsets[t], m = sg.new_offsets[t + 1] - sg.new_offsets[t];
+    const int64_t n = sg.offsets[t + 1] - sg.offsets[t] - m;
+    const int32_t f = len[p], s = src[p];
+    int64_t g = 0;
+    if (s >= 0 && (int64_t)s < n && f > 0) {
+        g = f;
+        g = g > m - j ? m - j : g;
+        g = g > n - s ? n - s : g;
+    }
+    const int32_t w = g > 0 ? s : -1;
+    if ((int32_t)g != f) len[p] = (int32_t)g;
+    if (w != s) src[p] = w;
 }
 
 }  // namespace dq

@@ -723,6 +723,19 @@ int lzparse_host(const uint8_t *text, int64_t n, const int32_t *len, const int32
                  int32_t device);
 int lzparse_dev(const void *d_text, int64_t n, const void *d_len, const void *d_src, void *d_phrases, int64_t cap, int64_t *count,
                 int32_t device, void *stream);
+// ... and of many pairs in one call: the bodies of dq_mstat_hip_many_*, dq_rlz_hip_many_* and dq_lzparse_hip_many_*
+int mstat_many_host(const int64_t *offsets, const int64_t *new_offsets, int32_t count, const int32_t *sas, const int32_t *lcps,
+                    int32_t *len, int32_t *src, int32_t device);
+int mstat_many_dev(const void *d_offsets, const void *d_new_offsets, int32_t count, const void *d_sas, const void *d_lcps, void *d_len,
+                   void *d_src, int32_t device, void *stream);
+int rlz_many_host(const uint8_t *cats, const int64_t *offsets, const int64_t *new_offsets, int32_t count, const int32_t *sas,
+                  const int32_t *lcps, int32_t *phrases, int64_t cap, int64_t *phrase_offsets, int32_t device);
+int rlz_many_dev(const void *d_cats, const void *d_offsets, const void *d_new_offsets, int32_t count, const void *d_sas,
+                 const void *d_lcps, void *d_phrases, int64_t cap, int64_t *phrase_offsets, int32_t device, void *stream);
+int lzparse_many_host(const uint8_t *texts, const int64_t *offsets, int32_t count, const int32_t *len, const int32_t *src,
+                      int32_t *phrases, int64_t cap, int64_t *phrase_offsets, int32_t device);
+int lzparse_many_dev(const void *d_texts, const void *d_offsets, int32_t count, const void *d_len, const void *d_src, void *d_phrases,
+                     int64_t cap, int64_t *phrase_offsets, int32_t device, void *stream);
 
 // match search + BSDIFF40 (dq_diff.hip)
 int match_search_dev_i32(const void *d_old, int64_t n, const void *d_sa, const void *d_new, int64_t m, const int64_t *d_scans,

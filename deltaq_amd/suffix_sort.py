@@ -1031,6 +1031,220 @@ class HipSuffixSort:
 
     lzparse = LzParse
 
+    # -- many (old, new) pairs in one call: a fixed number of launches and one wait (no counterpart) ------------------
+    MIXED_MANY_MESSAGE = "text, suffixes, lcp and phrases must all be host buffers or all torch GPU tensors"
+
+    def MatchStatsMany(self, olds, news=None, suffixes=None, lcps=None):
+        """``MatchStats`` of many pairs through the same launches and one wait: a list of ``(len, src)``, one per pair,
+        each what ``MatchStats(olds[t], news[t])`` returns (``dq_mstat_hip_many_i32``).
+
+        ``suffixes`` and ``lcps`` are lists of the int32 suffix arrays and LCP arrays of ``news[t] + olds[t]`` (new
+        FIRST); where either is left out, ``SortMany`` and ``LcpMany`` of these concatenations run first.  The device
+        form ``MatchStatsMany((cats_tensor, offsets_tensor, new_offsets_tensor), suffixes=sas_tensor, lcps=lcps_tensor)``
+        -- ``SortMany``'s device layout of the concatenations, and an int64 tensor of the new files' starts; without
+        the two arrays ``SortMany`` and ``LcpMany`` of that layout run first -- stays on
+        the device on the current torch stream (``dq_mstat_hip_many_dev_i32``) and returns two int32 tensors in the new
+        files' layout: pair t's entries start at ``new_offsets[t]``.  ``_abi.last_rlz_info()`` tells what happened.
+        """
+        if self._is_many_device(olds, news, suffixes, lcps):
+            cats, off, noff, sa, lc = self._many_device_arrays(olds, suffixes, lcps)
+            import torch
+
+            count = off.numel() - 1
+            positions = int(noff[-1].item()) if count > 0 else 0
+            length = torch.empty(positions, dtype=torch.int32, device=cats.device)
+            src = torch.empty(positions, dtype=torch.int32, device=cats.device)
+            if positions == 0:
+                return length, src
+            dev, stream = _device_and_stream(cats)
+            _abi.check(self._lib.dq_mstat_hip_many_dev_i32(off.data_ptr(), noff.data_ptr(), count, sa.data_ptr(), lc.data_ptr(),
+                                                           length.data_ptr(), src.data_ptr(), dev, stream))
+            return length, src
+        cats, off, noff, flat, flat_sa, flat_lcp = self._many_host_arrays(olds, news, suffixes, lcps)
+        count, positions = len(cats), int(noff[-1])
+        length, src = np.empty(max(positions, 1), dtype=np.int32), np.empty(max(positions, 1), dtype=np.int32)
+        _abi.check(self._lib.dq_mstat_hip_many_i32(off.ctypes.data, noff.ctypes.data, count, flat_sa.ctypes.data,
+                                                   flat_lcp.ctypes.data, length.ctypes.data, src.ctypes.data, self.device))
+        return [(length[noff[t]:noff[t + 1]], src[noff[t]:noff[t + 1]]) for t in range(count)]
+
+    matchstats_many = MatchStatsMany
+
+    def RlzMany(self, olds, news=None, suffixes=None, lcps=None):
+        """``Rlz`` of many pairs through the same launches and one wait: a list of ``(z_t, 3)`` int32 arrays, each what
+        ``Rlz(olds[t], news[t])`` returns and ``rlz_decode(olds[t], .)`` turns back into ``news[t]``
+        (``dq_rlz_hip_many_i32``).  Arguments as ``MatchStatsMany``.  The statistics are computed once: the one call
+        has room for a phrase per byte of the new files, which no factorization exceeds.  The device form returns
+        ``(phrases_tensor, phrase_offsets)``: the triples of all pairs back to back (starts counted from each new
+        file's own start) and a host int64 array, pair t's triples at ``[phrase_offsets[t], phrase_offsets[t + 1])``.
+        """
+        if self._is_many_device(olds, news, suffixes, lcps):
+            cats, off, noff, sa, lc = self._many_device_arrays(olds, suffixes, lcps)
+            import torch
+
+            count = off.numel() - 1
+            positions = int(noff[-1].item()) if count > 0 else 0
+            poff = np.zeros(count + 1, dtype=np.int64)
+            phrases = torch.empty((positions, 3), dtype=torch.int32, device=cats.device)
+            if positions == 0:
+                return phrases, poff
+            dev, stream = _device_and_stream(cats)
+            _abi.check(self._lib.dq_rlz_hip_many_dev_i32(cats.data_ptr(), off.data_ptr(), noff.data_ptr(), count, sa.data_ptr(),
+                                                         lc.data_ptr(), phrases.data_ptr(), positions, poff.ctypes.data, dev,
+                                                         stream))
+            return phrases[:int(poff[-1])], poff
+        cats, off, noff, flat, flat_sa, flat_lcp = self._many_host_arrays(olds, news, suffixes, lcps)
+        count, positions = len(cats), int(noff[-1])
+        poff = np.zeros(count + 1, dtype=np.int64)
+        phrases = np.empty((max(positions, 1), 3), dtype=np.int32)
+        _abi.check(self._lib.dq_rlz_hip_many_i32(flat.ctypes.data, off.ctypes.data, noff.ctypes.data, count, flat_sa.ctypes.data,
+                                                 flat_lcp.ctypes.data, phrases.ctypes.data, positions, poff.ctypes.data,
+                                                 self.device))
+        return [phrases[poff[t]:poff[t + 1]] for t in range(count)]
+
+    rlz_many = RlzMany
+
+    def LzParseMany(self, texts, lengths, srcs):
+        """``LzParse`` of many texts through the same launches and one wait: a list of ``(z_t, 3)`` int32 arrays from
+        lists of texts and of their finished ``(length, src)`` arrays (``dq_lzparse_hip_many_i32``).  The device form
+        ``LzParseMany((texts_tensor, offsets_tensor), lengths_tensor, srcs_tensor)`` -- texts back to back, the arrays
+        in the same layout -- returns ``(phrases_tensor, phrase_offsets)`` as ``RlzMany`` does
+        (``dq_lzparse_hip_many_dev_i32``: a sizing call, then the triples).
+        """
+        if isinstance(texts, tuple) or any(_is_torch_tensor(a) for a in (texts, lengths, srcs)):
+            import torch
+
+            if (not isinstance(texts, tuple) or len(texts) != 2 or not all(_is_torch_tensor(a) for a in (*texts, lengths, srcs))):
+                raise TypeError(self.MIXED_MANY_MESSAGE)
+            flat, off = texts
+            self._check_many_device_layout(flat, off)
+            for name, a in (("lengths", lengths), ("srcs", srcs)):
+                if a.dtype != torch.int32 or a.dim() != 1 or not a.is_contiguous() or a.device != flat.device:
+                    raise TypeError(f"{name} must be a contiguous 1-D int32 tensor on the texts' device")
+                if a.numel() != flat.numel():
+                    raise ValueError(LENGTH_MISMATCH_MESSAGE)
+            count = off.numel() - 1
+            poff = np.zeros(count + 1, dtype=np.int64)
+            if flat.numel() == 0 or count == 0:
+                return torch.empty((0, 3), dtype=torch.int32, device=flat.device), poff
+            dev, stream = _device_and_stream(flat)
+            fn = self._lib.dq_lzparse_hip_many_dev_i32
+            ptrs = (flat.data_ptr(), off.data_ptr(), count, lengths.data_ptr(), srcs.data_ptr())
+            _abi.check(fn(*ptrs, None, 0, poff.ctypes.data, dev, stream))
+            phrases = torch.empty((int(poff[-1]), 3), dtype=torch.int32, device=flat.device)
+            _abi.check(fn(*ptrs, phrases.data_ptr() if poff[-1] else None, int(poff[-1]), poff.ctypes.data, dev, stream))
+            return phrases, poff
+        arrs = [_as_text(t) for t in texts]
+        lens, srs = list(lengths), list(srcs)
+        if len(lens) != len(arrs) or len(srs) != len(arrs):
+            raise ValueError("LzParseMany takes one length array and one src array per text")
+        if any(a.ndim != 1 for a in arrs):
+            raise TypeError("every text must be one-dimensional")
+        for name, group in (("length", lens), ("src", srs)):
+            if any(_is_torch_tensor(a) for a in group):
+                raise TypeError(self.MIXED_MANY_MESSAGE)
+            if any(not isinstance(a, np.ndarray) or a.dtype != np.int32 or a.ndim != 1 for a in group):
+                raise TypeError(f"every {name} array must be a 1-D numpy int32 array")
+            if any(a.size != t.size for a, t in zip(group, arrs)):
+                raise ValueError(LENGTH_MISMATCH_MESSAGE)
+        count = len(arrs)
+        off = np.zeros(count + 1, dtype=np.int64)
+        if count:
+            np.cumsum([a.size for a in arrs], out=off[1:])
+        total = int(off[-1])
+        if total > INT_MAX:
+            raise ValueError("LzParseMany has 32-bit positions: the texts together must be shorter than 2^31 bytes")
+        poff = np.zeros(count + 1, dtype=np.int64)
+        flat = np.concatenate(arrs) if total else np.zeros(1, np.uint8)
+        flat_len = np.concatenate(lens) if total else np.zeros(1, np.int32)
+        flat_src = np.concatenate(srs) if total else np.zeros(1, np.int32)
+        fn = self._lib.dq_lzparse_hip_many_i32
+        ptrs = (flat.ctypes.data, off.ctypes.data, count, flat_len.ctypes.data, flat_src.ctypes.data)
+        _abi.check(fn(*ptrs, None, 0, poff.ctypes.data, self.device))
+        phrases = np.empty((max(int(poff[-1]), 1), 3), dtype=np.int32)
+        _abi.check(fn(*ptrs, phrases.ctypes.data, int(poff[-1]), poff.ctypes.data, self.device))
+        return [phrases[poff[t]:poff[t + 1]] for t in range(count)]
+
+    lzparse_many = LzParseMany
+
+    def _is_many_device(self, olds, news, suffixes, lcps):
+        """Whether a many-pairs call is the device form; mixing the two raises."""
+        tensors = [_is_torch_tensor(a) for a in (news, suffixes, lcps)]
+        if isinstance(olds, tuple) and len(olds) == 3 and all(_is_torch_tensor(a) for a in olds):
+            if news is not None or any(a is not None and not _is_torch_tensor(a) for a in (suffixes, lcps)):
+                raise TypeError(self.MIXED_MANY_MESSAGE)
+            return True
+        if any(tensors) or _is_torch_tensor(olds) or (isinstance(olds, tuple) and any(_is_torch_tensor(a) for a in olds)):
+            raise TypeError(self.MIXED_MANY_MESSAGE)
+        for group in (olds, news, suffixes, lcps):
+            if group is not None and any(_is_torch_tensor(a) for a in group):
+                raise TypeError(self.MIXED_MANY_MESSAGE)
+        return False
+
+    @staticmethod
+    def _check_many_device_layout(flat, off):
+        import torch
+
+        if flat.dtype != torch.uint8 or flat.dim() != 1 or not flat.is_contiguous():
+            raise TypeError("device texts must be a contiguous 1-D uint8 tensor")
+        if not flat.is_cuda:
+            raise TypeError("torch text tensors must live on the GPU; pass host data as bytes/numpy")
+        if off.dtype != torch.int64 or off.dim() != 1 or not off.is_contiguous() or off.numel() < 1 or off.device != flat.device:
+            raise TypeError("offsets must be a contiguous 1-D int64 tensor of count + 1 entries on the texts' device")
+
+    def _many_device_arrays(self, layout, sas, lcps):
+        import torch
+
+        cats, off, noff = layout
+        self._check_many_device_layout(cats, off)
+        if sas is None or lcps is None:
+            sas = self.SortMany((cats, off))
+            lcps = self.LcpMany((cats, off), sas)
+        if noff.dtype != torch.int64 or noff.dim() != 1 or not noff.is_contiguous() or noff.device != cats.device:
+            raise TypeError("new_offsets must be a contiguous 1-D int64 tensor on the texts' device")
+        if noff.numel() != off.numel():
+            raise ValueError("offsets and new_offsets must have the same length")
+        for name, a in (("suffixes", sas), ("lcps", lcps)):
+            if a.dtype != torch.int32 or a.dim() != 1 or not a.is_contiguous() or a.device != cats.device:
+                raise TypeError(f"{name} must be a contiguous 1-D int32 tensor on the texts' device")
+            if a.numel() != cats.numel():
+                raise ValueError(LENGTH_MISMATCH_MESSAGE)
+        return cats, off, noff, sas, lcps
+
+    def _many_host_arrays(self, olds, news, suffixes, lcps):
+        """The cats, both offset arrays and the flat bytes / suffix arrays / LCP arrays of a host many-pairs call (a
+        buffer of no bytes has no address: one entry stands in)."""
+        if news is None:
+            raise TypeError("the host form takes a list of old files and a list of new files")
+        O, N = [_as_text(t) for t in olds], [_as_text(t) for t in news]
+        if len(O) != len(N):
+            raise ValueError("one new file per old file")
+        if any(a.ndim != 1 for a in O + N):
+            raise TypeError("every file must be one-dimensional")
+        if any(o.size + w.size > INT_MAX for o, w in zip(O, N)):
+            raise ValueError("32-bit indices: an old and a new file together must be shorter than 2^31 bytes")
+        cats = [np.concatenate([w, o]) for o, w in zip(O, N)]
+        count = len(cats)
+        off, noff = np.zeros(count + 1, dtype=np.int64), np.zeros(count + 1, dtype=np.int64)
+        if count:
+            np.cumsum([c.size for c in cats], out=off[1:])
+            np.cumsum([w.size for w in N], out=noff[1:])
+        if suffixes is None or lcps is None:
+            suffixes = self.SortMany(cats) if noff[-1] else [np.zeros(c.size, np.int32) for c in cats]
+            lcps = self.LcpMany(cats, suffixes) if noff[-1] else suffixes
+        suffixes, lcps = list(suffixes), list(lcps)
+        for name, group in (("suffix", suffixes), ("LCP", lcps)):
+            if len(group) != count:
+                raise ValueError(f"one {name} array per pair")
+            if any(not isinstance(a, np.ndarray) or a.dtype != np.int32 or a.ndim != 1 for a in group):
+                raise TypeError(f"every {name} array must be a 1-D numpy int32 array")
+            if any(a.size != c.size for a, c in zip(group, cats)):
+                raise ValueError(LENGTH_MISMATCH_MESSAGE)
+        total = int(off[-1])
+        flat = np.concatenate(cats) if total else np.zeros(1, np.uint8)
+        flat_sa = np.concatenate(suffixes) if total else np.zeros(1, np.int32)
+        flat_lcp = np.concatenate(lcps) if total else np.zeros(1, np.int32)
+        return cats, off, noff, flat, flat_sa, flat_lcp
+
     @staticmethod
     def _lz_host_arrays(suffixes, lcp, n, names=("suffixes", "lcp")):
         for name, a in zip(names, (suffixes, lcp)):

@@ -831,8 +831,8 @@ int32_t dq_lz77_last_info(int64_t *info, int32_t count);
  * 12.2 m + 0.03 (m + n) bytes.  The host forms add their device copies of the arrays, the bytes and min(cap, m) triples.
  * No CPU fallback: DQ_ERR_OOM when that does not fit.  The _dev_ forms take device pointers on `device`, enqueue on
  * `stream` (NULL = the library's stream) and return after it has drained.  One stream wait per call.
- * Out of scope: int64 forms, a many-pairs form, matching against a standing index without sorting cat again, sources in
- * earlier parts of new (that is dq_lz77_hip_* of old + new), and computing sa or lcp inside these calls.
+ * Out of scope: int64 forms, matching against a standing index without sorting cat again, sources in earlier parts of
+ * new (that is dq_lz77_hip_* of old + new), and computing sa or lcp inside these calls.
  * dq_rlz_last_info: shape of the last of these six calls on this thread, reset when one starts; `count` entries (7 are
  * defined, further ones read 0; a NULL array is DQ_ERR_BAD_ARGS): [0] phrases z, [1] literal phrases (both 0 in mstat
  * calls); [2] the longest len (mstat calls) or the longest phrase (parse and rlz calls); [3] positions of new with
@@ -849,6 +849,69 @@ int32_t dq_lzparse_hip_i32(const uint8_t *text, int64_t n, const int32_t *len, c
 int32_t dq_lzparse_hip_dev_i32(const void *d_text, int64_t n, const void *d_len, const void *d_src,
                                void *d_phrases, int64_t cap, int64_t *count, int32_t device, void *stream);
 int32_t dq_rlz_last_info(int64_t *info, int32_t count);
+
+/* ---- ... of many pairs in one call: a fixed number of launches and one wait, whatever `count` is ---------------------
+ * Segment t of every output is exactly what dq_mstat_hip_i32, dq_rlz_hip_i32 or dq_lzparse_hip_i32 gives for pair t
+ * alone, and nothing outside the segments is written.
+ * cat layout: cats, offsets[count + 1], sas and lcps are in dq_sufsort_hip_many_i32's layout; text t is cat_t = new_t
+ *   FOLLOWED BY old_t as above.  Entries of sas and lcps count from the start of their own text: they are what
+ *   dq_sufsort_hip_many_* and dq_lcp_hip_many_* return for the cats.
+ * new_offsets[count + 1]: int64, starts at 0, never decreases; m_t = new_offsets[t+1] - new_offsets[t] is the length of
+ *   new_t, n_t = (offsets[t+1] - offsets[t]) - m_t the length of old_t and must be >= 0.
+ * new layout: len and src have new_offsets[count] entries, pair t's m_t entries start at new_offsets[t]; src is a
+ *   position in old_t, or -1.
+ * dq_lzparse_hip_many_*: texts back to back with one offsets[count + 1], len / src in that same layout; the parse alone.
+ * dq_rlz_hip_many_*: cats, both offset arrays, sas and lcps; a literal's byte is cats[offsets[t] + j], no separate array
+ *   of the new files is needed.
+ * Phrases are (start, len, third) int32 triples with start counted from the start of new_t (of text t), packed pair after
+ *   pair in one buffer of cap triples.  phrase_offsets[count + 1] is int64 and a HOST pointer in both forms, as *count is
+ *   above: it always receives the true prefix sums of the per-pair phrase counts, whatever cap is (Z = its last entry);
+ *   the first min(Z, cap) triples are written and nothing beyond them.  cap == 0 with phrases == NULL is the sizing call.
+ * A pair may have m_t == 0 (no positions, no phrases), n_t == 0 (all literals), or both.  The lcps entry at a text's first
+ * rank is never used: whatever it holds, no state crosses from one pair into the next in either scan direction.
+ * count == 0 returns DQ_OK before a device is looked for, and so does a host-form call whose new files (texts) are all
+ * empty; the _dev_ forms learn that from the offsets they fetch.  phrase_offsets is all zero then.
+ *   count < 0, a NULL pointer (phrases may be NULL with cap == 0), negative cap, offsets[0] != 0 or new_offsets[0] != 0,
+ *   a decreasing array, m_t greater than its text                               DQ_ERR_BAD_ARGS
+ *   a cat (a text) above 2^31-1 bytes; in the parse and rlz forms the parsed texts (the new files) together above
+ *   2^31-1                                                                      DQ_ERR_TOO_LARGE (all before any device work;
+ *                                                                               a refusal leaves phrase_offsets untouched)
+ * The total of the cats may exceed 2^31 in the mstat form, as in dq_lcp_hip_many_*; no call of 2^31 ranks or more has been
+ * run: the tests compare calls of up to 1.05 million ranks with a model, tools/kbench/rlz_many.py ran 310 million.
+ * Untrusted arrays, as above per pair: an sas entry outside [0, size of its OWN text) -- also one that lies inside the
+ * call's total -- makes the call return DQ_ERR_BAD_ARGS; lcps values are clamped to their text; every written pair obeys
+ * len in [0, min(m_t - j, n_t - src)], src in [-1, n_t), len == 0 exactly where src == -1; parse steps are clamped to
+ * [1, m_t - j]; no access goes outside the call's buffers and every walk is bounded.
+ * Computed over flat ranks of the whole call (deltaq_amd/csrc/dq_rlz.h): a rank finds its text by bisection of offsets,
+ * the first rank of a text folds a cut into both scans, the scatter goes to len[new_offsets[t] + sa[r]], the settle pass
+ * runs per position with its pair's m_t and n_t: 4 launches (kMsManyLaunches).  The parse clamps every step to its own
+ * text's end, so every text start is a phrase start and the tile kernels run over the concatenation; one lane PER TEXT
+ * walks the tiles from its text's start to its end, a tile's first phrase start is the minimum over what the lanes
+ * report, and a last launch of one thread per pair turns tile counts and bitmap into phrase_offsets: 6 launches
+ * (kLzParseManyLaunches); an rlz call makes 10 (deltaq_amd/csrc/dq_rlz_host.h names the three constants).
+ * Device memory, with R = offsets[count] ranks and M = new_offsets[count] positions: 256 + 32 ceil(R / 1024) bytes for an
+ * mstat call; a parse over M positions adds 4 M + 8 ceil(M / 8192) + 1024 ceil(M / 8192) + 8 (count + 1); an rlz call has
+ * both and len 4 + src 4 per position.  The host forms add their device copies of every array they are given and
+ * min(cap, M) triples.  No CPU fallback: DQ_ERR_OOM when that does not fit.  The _dev_ forms take device pointers on
+ * `device`, enqueue on `stream`, and fetch the offset arrays once to check them before launching (that fetch is not
+ * counted among the waits).  One stream wait per call.
+ * dq_rlz_last_info after a many call: [0] phrases and [1] literals, totals over the call; [2] the longest, the maximum
+ * over all pairs; [3] matched, the total; [4] walker hops, summed over all walking lanes; [5] launches; [6] waits: 1. */
+int32_t dq_mstat_hip_many_i32(const int64_t *offsets, const int64_t *new_offsets, int32_t count, const int32_t *sas,
+                              const int32_t *lcps, int32_t *len, int32_t *src, int32_t device);
+int32_t dq_mstat_hip_many_dev_i32(const void *d_offsets, const void *d_new_offsets, int32_t count, const void *d_sas,
+                                  const void *d_lcps, void *d_len, void *d_src, int32_t device, void *stream);
+int32_t dq_rlz_hip_many_i32(const uint8_t *cats, const int64_t *offsets, const int64_t *new_offsets, int32_t count,
+                            const int32_t *sas, const int32_t *lcps, int32_t *phrases, int64_t cap, int64_t *phrase_offsets,
+                            int32_t device);
+int32_t dq_rlz_hip_many_dev_i32(const void *d_cats, const void *d_offsets, const void *d_new_offsets, int32_t count,
+                                const void *d_sas, const void *d_lcps, void *d_phrases, int64_t cap, int64_t *phrase_offsets,
+                                int32_t device, void *stream);
+int32_t dq_lzparse_hip_many_i32(const uint8_t *texts, const int64_t *offsets, int32_t count, const int32_t *len,
+                                const int32_t *src, int32_t *phrases, int64_t cap, int64_t *phrase_offsets, int32_t device);
+int32_t dq_lzparse_hip_many_dev_i32(const void *d_texts, const void *d_offsets, int32_t count, const void *d_len,
+                                    const void *d_src, void *d_phrases, int64_t cap, int64_t *phrase_offsets, int32_t device,
+                                    void *stream);
 
 /* Device workspace (bytes) a sort of n bytes with index_bytes (4 or 8) wide indices needs,
  * excluding the caller's text and sa buffers: the device entry point's full layout (the reduced one at n = 2^32). */
