@@ -32,7 +32,7 @@ namespace dq {
 
 // (kBktCap, words per tile at most = threads x items of every geometry: dq_round0_plan.h, which cuts the tiles)
 constexpr int kBktBins = kBktCap;                          // ~1 element per bin
-constexpr int kBktMaxBin = 48;                             // a fuller bin = not the data this path is for
+// (kBktMaxBin, a fuller bin = not the data this path is for, and kBktArrBits: dq_round0_plan.h, shared with dq_slot_finish_plan.h)
 
 struct BucketFlags {
     // non-zero = the path gave up: 2 a bucket longer than X, 4 a tile spanning too many buckets, 8 a bin too
@@ -110,8 +110,7 @@ struct BktGeometry {
 using BktCoarse = BktGeometry<1024, kBktCap / 1024, 4>;
 using BktFine = BktGeometry<512, kBktCapFine / 512, 4>;
 static_assert(BktCoarse::cap == kBktCap && BktFine::cap == kBktCapFine, "the tiles are cut for these capacities");
-constexpr int kBktArrBits = 6;                             // arrival numbers < 64 (kBktMaxBin = 48)
-constexpr int kBktWalk = 4;                                // bin members inspected without a branch
+constexpr int kBktWalk = 4;                               // bin members inspected without a branch
 static_assert(kBktMaxBin < (1 << kBktArrBits), "arrival numbers must fit");
 
 // developer instrumentation (tools/kbench/bsort.hip): per-tile phase timestamps from thread 0

@@ -67,6 +67,7 @@ struct Flags {
     std::optional<int> bucket_ext;          // DQ_BUCKET_EXT: 0 | 1, the extra key byte beside every word
     std::optional<int> bucket_tile;         // DQ_BUCKET_TILE: 0 | 1, finish kernel's geometry: one workgroup per CU on 12 288-word tiles | two on 6144-word tiles
     std::optional<int> bucket_slots;        // DQ_BUCKET_SLOTS: 0 | 1, second digit pass: the stable look-back pass | into fixed bucket slots (1: forced where the slots fit)
+    std::optional<int> slot_finish;         // DQ_SLOT_FINISH: 0 | 1, finish kernel of the slots route: bucket_sort_kernel's slot mode | slot_finish_kernel (dq_slot_finish.h; unset: 1)
     std::optional<int> tie_settle;          // DQ_TIE_SETTLE: 0 | 1, ties of the bucketed round 0: listed, then finished | settled from their bits in one kernel (unset: with the slots; 1: on every bucketed route)
     std::optional<int> status_zero;         // DQ_STATUS_ZERO: 0 | 1, look-back state of the first digit passes: zeroed before the key width is known | once the route is known, and only what it reads (unset: early_status_passes, dq_round0_plan.h)
     std::optional<int> hist_loads;          // DQ_HIST_LOADS: 1 | 4, 16-byte loads a thread of text_hist_kernel keeps in flight (unset: 4)
@@ -184,6 +185,7 @@ inline Flags read_flags()
     f.bucket_ext = num("DQ_BUCKET_EXT");
     f.bucket_tile = num("DQ_BUCKET_TILE", 0, 1);
     f.bucket_slots = num("DQ_BUCKET_SLOTS", 0, 1);
+    f.slot_finish = num("DQ_SLOT_FINISH", 0, 1);
     f.tie_settle = num("DQ_TIE_SETTLE", 0, 1);
     f.status_zero = num("DQ_STATUS_ZERO", 0, 1);
     f.hist_loads = num("DQ_HIST_LOADS", 1, 4);

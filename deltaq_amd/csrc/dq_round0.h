@@ -11,6 +11,7 @@
 #include "dq_bucket_sort.h"
 #include "dq_xcd_rank.h"
 #include "dq_slot_rank.h"
+#include "dq_slot_finish.h"
 
 namespace dq {
 namespace {
@@ -429,12 +430,26 @@ struct Round0 {
             LAUNCH(L, DQ_K_BUCKET_SORT, ft.ntiles, ft.ntiles * 16,
                    hipLaunchKernelGGL(slot_out_kernel, dim3(kRadixSize), dim3(kSlotOutThreads), 0, st, sctl->cursor, (uint32_t)b.X,
                                       (const int64_t *)(w.digit_offset + kRadixSize) /* place 1: the first byte */, n, slot_out, bflags));
-            auto kernel = bucket_sort_kernel<IdxT, false, BktFine, true>;
-            const int groups = resident_groups(&c.bkt_slot_groups[sizeof(IdxT) == 8], (const void *)kernel, BktFine::threads, c.dev);
-            LAUNCH(L, DQ_K_BUCKET_SORT, n, n * (8 + wb) + n / 8,
-                   hipLaunchKernelGGL(kernel, dim3((unsigned)std::min<int64_t>(ft.ntiles, groups)), dim3(BktFine::threads), 0, st,
-                                      (const uint64_t *)Ks, ib, lowbits, (const int64_t *)nullptr, ft.ntiles, d_sa, ebits, bflags,
-                                      (const uint8_t *)nullptr, (const uint32_t *)slot_base, (const uint32_t *)sctl->cursor, (const uint32_t *)slot_out));
+            // slot_finish_kernel (dq_slot_finish.h): a slot holds at most X <= its capacity words of at most kSfMaxLowbits low key
+            // bits (two-byte buckets of at most 36 key bits).  DQ_SLOT_FINISH=0: bucket_sort_kernel's slot mode, as before.
+            const bool one_exchange = F.slot_finish.value_or(1) != 0 && lowbits <= kSfMaxLowbits && b.X <= kSfCap;
+            if (F.trace)
+                fprintf(stderr, "[dq] slot finish: %s (n=%lld)\n", one_exchange ? "slot_finish_kernel, one LDS exchange" : "bucket_sort_kernel, two LDS exchanges", (long long)n);
+            if (one_exchange) {
+                auto kernel = slot_finish_kernel<IdxT>;
+                const int groups = resident_groups(&c.slot_finish_groups[sizeof(IdxT) == 8], (const void *)kernel, kSfThreads, c.dev);
+                LAUNCH(L, DQ_K_BUCKET_SORT, n, n * (8 + wb) + n / 8,
+                       hipLaunchKernelGGL(kernel, dim3((unsigned)std::min<int64_t>(ft.ntiles, groups)), dim3(kSfThreads), 0, st,
+                                          (const uint64_t *)Ks, ib, lowbits, ft.ntiles, d_sa, ebits, bflags,
+                                          (const uint32_t *)slot_base, (const uint32_t *)sctl->cursor, (const uint32_t *)slot_out));
+            } else {
+                auto kernel = bucket_sort_kernel<IdxT, false, BktFine, true>;
+                const int groups = resident_groups(&c.bkt_slot_groups[sizeof(IdxT) == 8], (const void *)kernel, BktFine::threads, c.dev);
+                LAUNCH(L, DQ_K_BUCKET_SORT, n, n * (8 + wb) + n / 8,
+                       hipLaunchKernelGGL(kernel, dim3((unsigned)std::min<int64_t>(ft.ntiles, groups)), dim3(BktFine::threads), 0, st,
+                                          (const uint64_t *)Ks, ib, lowbits, (const int64_t *)nullptr, ft.ntiles, d_sa, ebits, bflags,
+                                          (const uint8_t *)nullptr, (const uint32_t *)slot_base, (const uint32_t *)sctl->cursor, (const uint32_t *)slot_out));
+            }
         } else if (ft.by_id) {
             const int64_t nbuckets = (int64_t)1 << (8 * b.bbytes);
             LAUNCH(L, DQ_K_BUCKET_SORT, ft.ntiles, ft.ntiles * 16 * 8,

@@ -24,6 +24,9 @@ namespace dq {
 constexpr int kKgramSamples = 1024;            // suffixes text_hist_kernel samples for repetition (dq_onesweep.h, sample_kgrams)
 constexpr int kBktCap = 12288;                 // words per tile of the bucketed round 0 at most (dq_bucket_sort.h)
 constexpr int kBktCapFine = 6144;              // ... of its fine geometry: two workgroups per CU, half the tile each
+constexpr int64_t kBktMaxX = 5120;             // room of the longest bucket the bucketed round 0 accepts at most (plan_bucketed)
+constexpr int kBktMaxBin = 48;                 // a fuller bin of a finish kernel = not the data this path is for
+constexpr int kBktArrBits = 6;                 // arrival numbers in a bin < 64 (kBktMaxBin = 48)
 constexpr int kSplitTop = 512;                 // sample-sort round 0 (dq_split_round0.h): top buckets = regions of pass A
 constexpr int kSplitSub = 512;                 // parts of a top bucket = regions of pass B
 constexpr int kSplitBuckets = kSplitTop * kSplitSub;             // 262 144: a 256 MiB text has 1024 suffixes per bucket
@@ -221,21 +224,21 @@ inline BucketPlan plan_bucketed(const TextStats &s, const Flags &F, KeyPlan k, b
     // a tile must not span more than 64 two-byte buckets (its keys, relative to its first bucket, take 26
     // bits + 6 arrival bits): buckets of >= 192 words on average, i.e. texts of >= 12 MiB
     const bool force3 = forced && *F.bucket == 3;          // (tests: 3-byte buckets on mid-size inputs)
-    if (need > 5120 || (!forced && n < (12 << 20)) || force3) {
+    if (need > kBktMaxX || (!forced && n < (12 << 20)) || force3) {
         if (keybits - 24 >= 8 && (forced || n >= (12 << 20))) {
             bbytes = 3;
             est *= pm;
             need = est + 6.0 * std::sqrt(est) + 64.0;
         }
-        if (need > 5120 || (bbytes == 2 && !forced)) {
+        if (need > kBktMaxX || (bbytes == 2 && !forced)) {
             if (!forced) return p;
-            need = 5120;
+            need = kBktMaxX;
         }
     }
     p.applies = true;
     p.keybits = keybits;
     p.bbytes = bbytes;
-    p.X = std::min<int64_t>(((int64_t)need + 255) / 256 * 256, 5120);
+    p.X = std::min<int64_t>(((int64_t)need + 255) / 256 * 256, kBktMaxX);
     p.C = kBktCap - p.X;
     p.lowbits = keybits - 8 * bbytes;
     p.ntiles = (n + p.C - 1) / p.C;

@@ -122,6 +122,7 @@ struct DeviceCtx {
     int ncu = 0;                        // compute units of the device (grid of the persistent kernels)
     int slot_rank_groups = 0;           // ... of slot_rank_kernel, and of bucket_sort_kernel's slot mode [64-bit indices] (dq_slot_rank.h)
     int bkt_slot_groups[2] = {};
+    int slot_finish_groups[2] = {};     // ... and of slot_finish_kernel [64-bit indices] (dq_slot_finish.h)
     int bkt_groups[2][2][2] = {};       // workgroups of bucket_sort_kernel the device holds at once, [fine][extra key byte][64-bit indices] (0: not asked yet)
     int many_groups[kAllClasses] = {};  // workgroups of each length class of small_many_kernel and mid_many_kernel the device holds at once (0: not asked yet)
     int check_many_groups[kCheckClasses] = {};  // ... and of each length class of sufcheck_many_kernel (dq_sufcheck_many.h)
