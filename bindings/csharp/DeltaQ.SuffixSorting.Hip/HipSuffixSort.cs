@@ -129,6 +129,19 @@ public sealed class HipSuffixSort : ISuffixSort
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
     internal static extern unsafe int dq_lz77_hip_dev_i32(IntPtr dText, long n, IntPtr dSa, IntPtr dLcp, IntPtr dPhrases, long cap, long* count, int device, IntPtr stream);
 
+    // many texts in one call: SortMany's layout, offsets of count + 1 entries, phraseOffsets is host memory
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    private static extern unsafe int dq_lpf_hip_many_i32(long* offsets, int count, int* sas, int* lcps, int* lpf, int* src, int device);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    private static extern unsafe int dq_lz77_hip_many_i32(byte* texts, long* offsets, int count, int* sas, int* lcps, int* phrases, long cap, long* phraseOffsets, int device);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern int dq_lpf_hip_many_dev_i32(IntPtr dOffsets, int count, IntPtr dSas, IntPtr dLcps, IntPtr dLpf, IntPtr dSrc, int device, IntPtr stream);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern unsafe int dq_lz77_hip_many_dev_i32(IntPtr dTexts, IntPtr dOffsets, int count, IntPtr dSas, IntPtr dLcps, IntPtr dPhrases, long cap, long* phraseOffsets, int device, IntPtr stream);
+
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
     private static extern unsafe int dq_lz77_last_info(long* info, int count);
 
@@ -1413,6 +1426,115 @@ public sealed class HipSuffixSort : ISuffixSort
             LcpResult(rc, "dq_lzparse_hip_many_i32");
             return SplitPhrases(phrases, phraseOffsets);
         }
+    }
+
+    /// <summary>The offsets of arrays back to back and the arrays themselves in one buffer (one entry stands in for none).</summary>
+    private static (long[] Offsets, T[] Flat) Flatten<T>(IReadOnlyList<ReadOnlyMemory<T>> arrays, string what)
+    {
+        var offsets = new long[arrays.Count + 1];
+        for (int t = 0; t < arrays.Count; t++)
+        {
+            offsets[t + 1] = offsets[t] + arrays[t].Length;
+        }
+
+        if (offsets[arrays.Count] > Array.MaxLength)
+        {
+            throw new ArgumentException($"the texts of one {what} call must total less than 2^31 bytes");
+        }
+
+        var flat = new T[Math.Max(offsets[arrays.Count], 1)];
+        for (int t = 0; t < arrays.Count; t++)
+        {
+            arrays[t].Span.CopyTo(flat.AsSpan((int)offsets[t]));
+        }
+
+        return (offsets, flat);
+    }
+
+    /// <summary>
+    /// <see cref="Lpf"/> of many texts in one native call (dq_lpf_hip_many_i32) from their suffix arrays and LCP arrays
+    /// (what <c>SortMany</c> and <c>LcpMany</c> return): launches that depend on the total size alone and one wait.
+    /// Entry t is what the single call gives for text t alone; Src counts from the text's own start.
+    /// </summary>
+    public unsafe (int[] Lpf, int[] Src)[] LpfMany(IReadOnlyList<ReadOnlyMemory<int>> suffixes, IReadOnlyList<ReadOnlyMemory<int>> lcps)
+    {
+        int count = suffixes.Count;
+        if (lcps.Count != count)
+        {
+            throw new ArgumentException("LpfMany takes one LCP array per suffix array");
+        }
+
+        for (int t = 0; t < count; t++)
+        {
+            if (lcps[t].Length != suffixes[t].Length)
+            {
+                ThrowHelper();
+            }
+        }
+
+        var (offsets, sas) = Flatten(suffixes, "LpfMany");
+        var (_, common) = Flatten(lcps, "LpfMany");
+        var lpf = new int[sas.Length];
+        var src = new int[sas.Length];
+        int rc;
+        fixed (long* pOffsets = offsets)
+        fixed (int* pSas = sas)
+        fixed (int* pLcps = common)
+        fixed (int* pLpf = lpf)
+        fixed (int* pSrc = src)
+        {
+            rc = dq_lpf_hip_many_i32(pOffsets, count, pSas, pLcps, pLpf, pSrc, _device);
+        }
+
+        LcpResult(rc, "dq_lpf_hip_many_i32");
+        var result = new (int[] Lpf, int[] Src)[count];
+        for (int t = 0; t < count; t++)
+        {
+            result[t] = (lpf.AsSpan((int)offsets[t], suffixes[t].Length).ToArray(), src.AsSpan((int)offsets[t], suffixes[t].Length).ToArray());
+        }
+
+        return result;
+    }
+
+    /// <summary>
+    /// <see cref="Lz77(ReadOnlySpan{byte})"/> of many texts in ONE native call (dq_lz77_hip_many_i32) behind
+    /// <c>SortMany</c> and <c>LcpMany</c>: entry t holds text t's phrases, three ints each with starts and sources
+    /// counted from the start of its own text, and <see cref="Lz77Decode"/> of it gives texts[t].  The call has room for
+    /// a phrase per byte.
+    /// </summary>
+    public unsafe int[][] Lz77Many(IReadOnlyList<ReadOnlyMemory<byte>> texts)
+    {
+        int count = texts.Count;
+        var (offsets, flat) = Flatten(texts, "Lz77Many");
+        var sas = new int[flat.Length];
+        var lcps = new int[flat.Length];
+        if (offsets[count] > 0)
+        {
+            int[][] sorted = SortMany(texts);
+            int[][] common = LcpMany(texts, sorted.Select(s => (ReadOnlyMemory<int>)s).ToArray());
+            for (int t = 0; t < count; t++)
+            {
+                sorted[t].CopyTo(sas.AsSpan((int)offsets[t]));
+                common[t].CopyTo(lcps.AsSpan((int)offsets[t]));
+            }
+        }
+
+        long cap = offsets[count];
+        var phrases = new int[Math.Max(checked(3 * cap), 1)];
+        var phraseOffsets = new long[count + 1];
+        int rc;
+        fixed (byte* pTexts = flat)
+        fixed (long* pOffsets = offsets)
+        fixed (int* pSas = sas)
+        fixed (int* pLcps = lcps)
+        fixed (int* pPhrases = phrases)
+        fixed (long* pPhraseOffsets = phraseOffsets)
+        {
+            rc = dq_lz77_hip_many_i32(pTexts, pOffsets, count, pSas, pLcps, pPhrases, cap, pPhraseOffsets, _device);
+        }
+
+        LcpResult(rc, "dq_lz77_hip_many_i32");
+        return SplitPhrases(phrases, phraseOffsets);
     }
 
     private static int[][] SplitPhrases(int[] phrases, long[] phraseOffsets)

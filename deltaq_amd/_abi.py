@@ -62,6 +62,7 @@ EXPORTS = (
     "dq_lcp_hip_i32", "dq_lcp_hip_i64", "dq_lcp_hip_dev_i32", "dq_lcp_hip_dev_i64",
     "dq_lcp_hip_many_i32", "dq_lcp_hip_many_dev_i32", "dq_lcp_last_info",
     "dq_lpf_hip_i32", "dq_lpf_hip_dev_i32", "dq_lz77_hip_i32", "dq_lz77_hip_dev_i32", "dq_lz77_last_info",
+    "dq_lpf_hip_many_i32", "dq_lpf_hip_many_dev_i32", "dq_lz77_hip_many_i32", "dq_lz77_hip_many_dev_i32",
     "dq_mstat_hip_i32", "dq_mstat_hip_dev_i32", "dq_rlz_hip_i32", "dq_rlz_hip_dev_i32",
     "dq_lzparse_hip_i32", "dq_lzparse_hip_dev_i32", "dq_rlz_last_info",
     "dq_mstat_hip_many_i32", "dq_mstat_hip_many_dev_i32", "dq_rlz_hip_many_i32", "dq_rlz_hip_many_dev_i32",
@@ -209,6 +210,14 @@ def load() -> ctypes.CDLL:
     L.dq_lz77_hip_i32.argtypes = [vp, i64, vp, vp, vp, i64, ctypes.POINTER(i64), i32]
     L.dq_lz77_hip_dev_i32.restype = i32
     L.dq_lz77_hip_dev_i32.argtypes = [vp, i64, vp, vp, vp, i64, ctypes.POINTER(i64), i32, vp]
+    L.dq_lpf_hip_many_i32.restype = i32
+    L.dq_lpf_hip_many_i32.argtypes = [vp, i32, vp, vp, vp, vp, i32]
+    L.dq_lpf_hip_many_dev_i32.restype = i32
+    L.dq_lpf_hip_many_dev_i32.argtypes = [vp, i32, vp, vp, vp, vp, i32, vp]
+    L.dq_lz77_hip_many_i32.restype = i32
+    L.dq_lz77_hip_many_i32.argtypes = [vp, vp, i32, vp, vp, vp, i64, vp, i32]
+    L.dq_lz77_hip_many_dev_i32.restype = i32
+    L.dq_lz77_hip_many_dev_i32.argtypes = [vp, vp, i32, vp, vp, vp, i64, vp, i32, vp]
     L.dq_lz77_last_info.restype = i32
     L.dq_lz77_last_info.argtypes = [ctypes.POINTER(i64), i32]
     L.dq_mstat_hip_i32.restype = i32

@@ -405,6 +405,53 @@ int32_t dq_lz77_hip_dev_i32(const void *d_text, int64_t n, const void *d_sa, con
     return lz77_dev(d_text, n, d_sa, d_lcp, d_phrases, cap, count, device, stream);
 }
 
+// (the many forms hold the offsets, and the host forms phrase_offsets' staging, in vectors: nothing may propagate
+// through the C ABI)
+int32_t dq_lpf_hip_many_i32(const int64_t *offsets, int32_t count, const int32_t *sas, const int32_t *lcps, int32_t *lpf,
+                            int32_t *src, int32_t device)
+{
+    EnvScope scope;
+    t_lz77_info = {};
+    return lpf_many_host(offsets, count, sas, lcps, lpf, src, device);
+}
+
+int32_t dq_lpf_hip_many_dev_i32(const void *d_offsets, int32_t count, const void *d_sas, const void *d_lcps, void *d_lpf,
+                                void *d_src, int32_t device, void *stream)
+{
+    EnvScope scope;
+    t_lz77_info = {};
+    try {
+        return lpf_many_dev(d_offsets, count, d_sas, d_lcps, d_lpf, d_src, device, stream);
+    } catch (const std::bad_alloc &) {
+        return fail(DQ_ERR_OOM, "lpf many: host allocation failed");
+    }
+}
+
+int32_t dq_lz77_hip_many_i32(const uint8_t *texts, const int64_t *offsets, int32_t count, const int32_t *sas,
+                             const int32_t *lcps, int32_t *phrases, int64_t cap, int64_t *phrase_offsets, int32_t device)
+{
+    EnvScope scope;
+    t_lz77_info = {};
+    try {
+        return lz77_many_host(texts, offsets, count, sas, lcps, phrases, cap, phrase_offsets, device);
+    } catch (const std::bad_alloc &) {
+        return fail(DQ_ERR_OOM, "lz77 many: host allocation failed");
+    }
+}
+
+int32_t dq_lz77_hip_many_dev_i32(const void *d_texts, const void *d_offsets, int32_t count, const void *d_sas,
+                                 const void *d_lcps, void *d_phrases, int64_t cap, int64_t *phrase_offsets,
+                                 int32_t device, void *stream)
+{
+    EnvScope scope;
+    t_lz77_info = {};
+    try {
+        return lz77_many_dev(d_texts, d_offsets, count, d_sas, d_lcps, d_phrases, cap, phrase_offsets, device, stream);
+    } catch (const std::bad_alloc &) {
+        return fail(DQ_ERR_OOM, "lz77 many: host allocation failed");
+    }
+}
+
 int32_t dq_lz77_last_info(int64_t *info, int32_t count) { return last_info(t_lz77_info, info, count, "null info array"); }
 
 int32_t dq_mstat_hip_i32(const int32_t *sa, const int32_t *lcp, int64_t m, int64_t n, int32_t *len, int32_t *src, int32_t device)

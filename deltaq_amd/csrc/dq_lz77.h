@@ -40,6 +40,17 @@
 // Scratch per byte of text: the list 4 + 16 (rank; both sides' neighbour and minimum), the levels 8/63, 12 bytes per
 // tile of ranks: 20.2 bytes for an LPF call.  An LZ77 call adds lpf 4 + src 4 + one bit per position + 8 bytes per tile
 // of positions (the exits reuse the list): 28.3 bytes.  And one 256-byte line of counters.
+//
+// Many texts in one call (dq_lpf_hip_many_*, dq_lz77_hip_many_*): the same phases over the flat ranks of all texts --
+//   lpf_level1_many_kernel     level 1 with the range test against the rank's OWN text, 0 in place of LCP at every text's
+//                              first rank, the call's own level 0 (sa0 / lcp0) and the tiles' summaries for the scan
+//   lpf_tile_scan_many_kernel  the one-workgroup scan with a cut at text starts in its operator
+//   lpf_tile_many_kernel, lpf_long_many_kernel   lpf_tile_body<true>, lpf_long_body<true>: the one-text bodies, templated
+//                              on kMany rather than copied (the tile walks, the list, the claim loop, the climbs and the
+//                              descents are the same code; what differs is a handful of conditions and the scatter address)
+//   lz_*_many_kernel           the parse over the concatenation, one walking lane per text (below)
+// -- see "... of many texts" below for why the text boundary is an exact barrier.  They add 12 bytes per rank (sa0, lcp0,
+// the listed ranks' scatter addresses) and 16 bytes per tile of ranks.
 #pragma once
 #include "dq_device_utils.h"
 #include "dq_lz77_info.h"
@@ -134,6 +145,35 @@ __device__ __forceinline__ void lpf_combine(int32_t pl, int32_t cl, int32_t pr, 
     *src = *lpf == 0 ? -1 : (left ? pl : pr);
 }
 
+// Many texts back to back (the layout of dq_sufsort_hip_many_*): text t at ranks and positions [off[t], off[t + 1]).
+struct LzTexts {
+    const int64_t *off;                          // count + 1: the layout of lpf / src, the triples' starts count from off[t]
+    const int64_t *bytes;                        // count + 1: text t's bytes begin at T[bytes[t]] (off itself, or the cats' offsets)
+    int32_t count;
+};
+
+// the text that holds position i, among texts lo .. hi (off[lo] <= i < off[hi + 1]): the last t with off[t] <= i
+__device__ __forceinline__ int32_t lz_text_of(const int64_t *__restrict__ off, int32_t lo, int32_t hi, int64_t i)
+{
+    ++hi;
+    while (hi - lo > 1) {
+        const int32_t mid = (int32_t)(((int64_t)lo + hi) >> 1);
+        if (off[mid] <= i) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// The text of rank r of the tile of kLpfTile ranks from r0 (r0 <= r < n): the tile's two ends by bisection over all
+// texts -- 2 log2(count) dependent loads, the same for every thread of the workgroup --, then the thread's own between
+// them: log2(1 + texts that begin in the tile) more, none where one text covers the tile.  *first: the text of r0.
+__device__ __forceinline__ int32_t lpf_tile_text(const LzTexts &tx, int64_t r0, int64_t n, int64_t r, int32_t *first)
+{
+    const int64_t last = r0 + kLpfTile < n ? r0 + kLpfTile - 1 : n - 1;
+    const int32_t lo = lz_text_of(tx.off, 0, tx.count - 1, r0), hi = lz_text_of(tx.off, lo, tx.count - 1, last);
+    *first = lo;
+    return lz_text_of(tx.off, lo, hi, r);
+}
+
 // ---------------------------------------------------------------------------------------------- the minima hierarchy
 // One wave per entry of the level written: the minima of its 64 entries of the level below (raw: the caller's arrays).
 __global__ __launch_bounds__(kBlock) void lpf_levels_kernel(const int32_t *__restrict__ in_sa, const int32_t *__restrict__ in_lcp,
@@ -210,12 +250,155 @@ __global__ __launch_bounds__(kBlock) void lpf_tile_scan_kernel(const int32_t *__
     }
 }
 
+// ---------------------------------------------------------------------------------------------- ... of many texts
+// The flat ranks [0, n) of all texts of tx.  SA values count from the start of their own text, and the LCP entry at a
+// text's first rank takes part as 0, whatever it holds: a neighbour that a walk or a climb finds in a foreign text then
+// has 0 in common, which lpf_combine treats exactly like no neighbour, so the text boundary is an exact barrier and the
+// levels above the first, the climbs and the descents are the one-text ones over the flat ranks.
+//
+// Level 1 of a many call; one workgroup per tile of kLpfTile ranks (= kBlock).  It range-tests SA against the rank's own
+// text and clamps LCP to that text's size, writes both as the call's own level 0 (sa0 / lcp0: kLpfNone for an entry
+// outside, 0 at first ranks) -- what the tile pass and the descents read, so nothing behind this kernel looks at the
+// caller's arrays --, the level-1 minima, and the tile's two summaries for lpf_tile_scan_many_kernel:
+//   sum_fwd = (a text begins in the tile, the minimum of SA from the last such rank on -- without one: of the tile)
+//   sum_bwd = (likewise, the minimum of SA before the first such rank)
+__global__ __launch_bounds__(kBlock) void lpf_level1_many_kernel(const int32_t *__restrict__ SA, const int32_t *__restrict__ LCP,
+                                                                 LzTexts tx, int64_t n, int32_t *__restrict__ sa0,
+                                                                 int32_t *__restrict__ lcp0, int32_t *__restrict__ out_sa,
+                                                                 int32_t *__restrict__ out_lcp, int2 *__restrict__ sum_fwd,
+                                                                 int2 *__restrict__ sum_bwd, LzCounters *ctr)
+{
+    static_assert(kLpfTile == kBlock);
+    __shared__ uint64_t s_start[kWavesPerBlock];
+    __shared__ int32_t s_f[kWavesPerBlock], s_b[kWavesPerBlock];
+    const int t = (int)threadIdx.x, w = t >> 6;
+    const int64_t r0 = (int64_t)blockIdx.x * kLpfTile, r = r0 + t;
+    int32_t a = kLpfNone, b = kLpfNone;
+    bool outside = false, start = false;
+    if (r < n) {
+        int32_t first;
+        const int32_t tt = lpf_tile_text(tx, r0, n, r, &first);
+        const int64_t base = tx.off[tt];
+        int64_t size = tx.off[tt + 1] - base;
+        size = size < 0 ? 0 : (size > n ? n : size);                         // (the host checked the layout)
+        a = SA[r];
+        b = LCP[r];
+        outside = a < 0 || (int64_t)a >= size;
+        a = lpf_sa_value(a, size);
+        start = r == base;
+        b = start ? 0 : lpf_lcp_value(b, size);
+        sa0[r] = a;
+        lcp0[r] = b;
+    }
+    const int32_t wa = lpf_wave_min(a), wb = lpf_wave_min(b);
+    if (lane_id() == 0 && r < n) {                                           // (lane 0 is the wave's first rank)
+        out_sa[r / kLpfFan] = wa;
+        out_lcp[r / kLpfFan] = wb;
+    }
+    const uint64_t sm = __ballot(start);
+    if (lane_id() == 0) s_start[w] = sm;
+    __syncthreads();
+    int ls = -1, fs = kLpfTile;                                              // the tile's last and first rank that begins a text
+#pragma unroll
+    for (int i = 0; i < kWavesPerBlock; ++i) {
+        const uint64_t m = s_start[i];
+        if (m) {
+            ls = i * kWave + 63 - __builtin_clzll(m);
+            if (fs == kLpfTile) fs = i * kWave + __builtin_ctzll(m);
+        }
+    }
+    const int32_t f = lpf_wave_min(t >= ls ? a : kLpfNone), g = lpf_wave_min(t < fs ? a : kLpfNone);
+    if (lane_id() == 0) {
+        s_f[w] = f;
+        s_b[w] = g;
+    }
+    __syncthreads();
+    if (t == 0) {
+        int32_t mf = kLpfNone, mb = kLpfNone;
+#pragma unroll
+        for (int i = 0; i < kWavesPerBlock; ++i) {
+            mf = s_f[i] < mf ? s_f[i] : mf;
+            mb = s_b[i] < mb ? s_b[i] : mb;
+        }
+        sum_fwd[blockIdx.x] = make_int2(ls >= 0, mf);
+        sum_bwd[blockIdx.x] = make_int2(fs < kLpfTile, mb);
+    }
+    if (__ballot(outside) && lane_id() == 0) __hip_atomic_fetch_or(&ctr->flags, kLzOutOfRange, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The scan's operator: a summary with a cut (x != 0) lets nothing from beyond it pass.  Associative, like ms_join's
+// barrier (dq_rlz.h).
+__device__ __forceinline__ int2 lpf_cut_join(int2 far, int2 near)
+{
+    return near.x ? near : make_int2(far.x, near.y < far.y ? near.y : far.y);
+}
+
+// lpf_tile_scan_kernel with the cut: pre[t] = the minimum of SA over the ranks before tile t that belong to the text of
+// the tile's first rank, suf[t] = over the ranks behind it that belong to the text of its last rank (kLpfNone: none).
+// Without the cut the small entries of foreign texts would send every rank of a run of one byte to the wave kernel.
+// (Where the tile's first rank begins a text, pre[t] is the tail of the text before: lpf_tile_body does not look at it.)
+__global__ __launch_bounds__(kBlock) void lpf_tile_scan_many_kernel(const int2 *__restrict__ sum_fwd, const int2 *__restrict__ sum_bwd,
+                                                                    int64_t tiles, int32_t *__restrict__ pre, int32_t *__restrict__ suf)
+{
+    __shared__ int2 s_tmp[kWavesPerBlock];
+    __shared__ int2 s_carry;
+    const int l = lane_id(), w = (int)threadIdx.x >> 6;
+    for (int dir = 0; dir < 2; ++dir) {
+        const int2 *in = dir ? sum_bwd : sum_fwd;
+        int32_t *out = dir ? suf : pre;
+        __syncthreads();
+        if (threadIdx.x == 0) s_carry = make_int2(0, kLpfNone);
+        __syncthreads();
+        for (int64_t t0 = 0; t0 < tiles; t0 += (int64_t)kBlock * kLpfPer) {
+            const int64_t at = t0 + (int64_t)threadIdx.x * kLpfPer;
+            int2 v[kLpfPer], inc = make_int2(0, kLpfNone);
+#pragma unroll
+            for (int k = 0; k < kLpfPer; ++k) {
+                const int64_t t = dir ? tiles - 1 - (at + k) : at + k;      // the k-th tile of this thread in scan order
+                v[k] = at + k < tiles ? in[t] : make_int2(0, kLpfNone);
+                inc = lpf_cut_join(inc, v[k]);
+            }
+#pragma unroll
+            for (int o = 1; o < kWave; o <<= 1) {
+                const int2 far = make_int2(__shfl_up(inc.x, o, kWave), __shfl_up(inc.y, o, kWave));
+                if (l >= o) inc = lpf_cut_join(far, inc);
+            }
+            if (l == kWave - 1) s_tmp[w] = inc;
+            int2 ex = make_int2(__shfl_up(inc.x, 1, kWave), __shfl_up(inc.y, 1, kWave));
+            if (l == 0) ex = make_int2(0, kLpfNone);
+            int2 run = s_carry;
+            __syncthreads();                                                 // (everybody has read s_carry)
+#pragma unroll
+            for (int i = 0; i < kWavesPerBlock; ++i)
+                if (i < w) run = lpf_cut_join(run, s_tmp[i]);
+            run = lpf_cut_join(run, ex);
+#pragma unroll
+            for (int k = 0; k < kLpfPer; ++k) {
+                const int64_t t = dir ? tiles - 1 - (at + k) : at + k;
+                if (at + k < tiles) out[t] = run.y;
+                run = lpf_cut_join(run, v[k]);
+            }
+            if (threadIdx.x == kBlock - 1) s_carry = run;
+            __syncthreads();                                                 // s_tmp and s_carry before the next step
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------- the tile pass
-__global__ __launch_bounds__(kBlock) void lpf_tile_kernel(const int32_t *__restrict__ SA, const int32_t *__restrict__ LCP, int64_t n,
-                                                          const int32_t *__restrict__ pre, const int32_t *__restrict__ suf,
-                                                          int32_t *__restrict__ lpf, int32_t *__restrict__ src,
-                                                          int32_t *__restrict__ list_r, int4 *__restrict__ list_q,
-                                                          int32_t *__restrict__ tile_cnt, LzCounters *ctr)
+// One body for one text and for many (kMany: SA / LCP are lpf_level1_many_kernel's sa0 / lcp0 over the flat ranks, so a
+// first rank holds 0 in LDS too).  What differs in a many call:
+//   - a side that reaches the tile's edge with a folded minimum of 0 is final: it has crossed its text's first rank, or
+//     the next text's, (or met a 0 of its own text,) and whatever lies beyond has nothing in common with it.  Otherwise
+//     the rank's text reaches beyond that edge, so it is the text pre[] (suf[]) of this tile speaks of;
+//   - pre[] is not looked at where the tile's first rank begins a text (it speaks of the text before);
+//   - the scatter goes to off[text] + v, and the listed rank takes that address along (list_d): the wave kernel has no
+//     text to look up.
+template <bool kMany>
+__device__ __forceinline__ void lpf_tile_body(const int32_t *__restrict__ SA, const int32_t *__restrict__ LCP, const LzTexts &tx, int64_t n,
+                                              const int32_t *__restrict__ pre, const int32_t *__restrict__ suf,
+                                              int32_t *__restrict__ lpf, int32_t *__restrict__ src,
+                                              int32_t *__restrict__ list_r, int4 *__restrict__ list_q, int32_t *__restrict__ list_d,
+                                              int32_t *__restrict__ tile_cnt, LzCounters *ctr)
 {
     __shared__ int s_cnt[kWavesPerBlock];
     // (SA, LCP) pairs of the tile's ranks between kLpfPad stoppers on each side -- and in place of the ranks beyond the
@@ -224,9 +407,16 @@ __global__ __launch_bounds__(kBlock) void lpf_tile_kernel(const int32_t *__restr
     const int t = (int)threadIdx.x;
     const int64_t r0 = (int64_t)blockIdx.x * kLpfTile, r = r0 + t;
     int32_t v = -1, l = kLpfNone;
+    int64_t base = 0;                                                        // kMany: where the rank's text begins
+    bool pre_speaks = true;
     if (r < n) {
         v = lpf_sa_value(SA[r], n);
         l = lpf_lcp_value(LCP[r], n);
+        if constexpr (kMany) {
+            int32_t first;
+            base = tx.off[lpf_tile_text(tx, r0, n, r, &first)];
+            pre_speaks = tx.off[first] != r0;
+        }
     }
     s_pair[kLpfPad + t] = make_int2(v, l);
     if (t < kLpfPad) {
@@ -256,7 +446,7 @@ __global__ __launch_bounds__(kBlock) void lpf_tile_kernel(const int32_t *__restr
             j -= kLpfPad;
         }
         if (at >= kLpfPad) { pl = s_pair[at].x; cl = m; }
-        else if (pre[blockIdx.x] < v) { pl = kLpfPending; cl = m; pending = true; }
+        else if ((!kMany || (m != 0 && pre_speaks)) && pre[blockIdx.x] < v) { pl = kLpfPending; cl = m; pending = true; }
         // to the right: ranks (r, at] are folded, the one that ends the walk included
         m = kLpfNone;
         j = kLpfPad + t + 1;
@@ -275,14 +465,17 @@ __global__ __launch_bounds__(kBlock) void lpf_tile_kernel(const int32_t *__restr
             j += kLpfPad;
         }
         if (at < kLpfPad + cnt) { pr = s_pair[at].x; cr = m; }
-        else if (r0 + kLpfTile < n && suf[blockIdx.x] < v) { pr = kLpfPending; cr = m; pending = true; }
+        else if (r0 + kLpfTile < n && (!kMany || m != 0) && suf[blockIdx.x] < v) { pr = kLpfPending; cr = m; pending = true; }
     }
     uint32_t longest = 0;
     if (valid && !pending) {
         int32_t f, s;
         lpf_combine(pl, cl, pr, cr, &f, &s);
-        lpf[v] = f;
-        src[v] = s;
+        const int64_t dst = kMany ? base + v : (int64_t)v;
+        if (!kMany || (dst >= 0 && dst < n)) {                               // (base + v < off[text + 1] <= n: tested all the same)
+            lpf[dst] = f;
+            src[dst] = s;
+        }
         longest = (uint32_t)f;
     }
     // The tile's listed ranks go to the front of the tile's own stretch of the list, [r0, r0 + tile_cnt): no counter is
@@ -301,16 +494,38 @@ __global__ __launch_bounds__(kBlock) void lpf_tile_kernel(const int32_t *__restr
         const int64_t at = r0 + before + mask_rank_lt(mask);
         list_r[at] = (int32_t)r;
         list_q[at] = make_int4(pl, cl, pr, cr);
+        if constexpr (kMany) list_d[at] = (int32_t)(base + v);
     }
     if (t == 0) tile_cnt[blockIdx.x] = total;
     longest = wave_max(longest);
     if (lane_id() == 0) lz_raise(&ctr->longest_lpf, longest);
 }
 
+__global__ __launch_bounds__(kBlock) void lpf_tile_kernel(const int32_t *__restrict__ SA, const int32_t *__restrict__ LCP, int64_t n,
+                                                          const int32_t *__restrict__ pre, const int32_t *__restrict__ suf,
+                                                          int32_t *__restrict__ lpf, int32_t *__restrict__ src,
+                                                          int32_t *__restrict__ list_r, int4 *__restrict__ list_q,
+                                                          int32_t *__restrict__ tile_cnt, LzCounters *ctr)
+{
+    lpf_tile_body<false>(SA, LCP, LzTexts{}, n, pre, suf, lpf, src, list_r, list_q, nullptr, tile_cnt, ctr);
+}
+
+__global__ __launch_bounds__(kBlock) void lpf_tile_many_kernel(const int32_t *__restrict__ sa0, const int32_t *__restrict__ lcp0, LzTexts tx,
+                                                               int64_t n, const int32_t *__restrict__ pre, const int32_t *__restrict__ suf,
+                                                               int32_t *__restrict__ lpf, int32_t *__restrict__ src,
+                                                               int32_t *__restrict__ list_r, int4 *__restrict__ list_q,
+                                                               int32_t *__restrict__ list_d, int32_t *__restrict__ tile_cnt, LzCounters *ctr)
+{
+    lpf_tile_body<true>(sa0, lcp0, tx, n, pre, suf, lpf, src, list_r, list_q, list_d, tile_cnt, ctr);
+}
+
 // ---------------------------------------------------------------------------------------------- the wave kernel
 // The nearest rank below tile start c (a multiple of kLpfTile; ranks [c, r] are folded into *m) whose entry is below v.
 // Called by the whole wave with wave-uniform arguments.  Level k is looked at from entry ck = c / 64^k leftwards to the
 // start of ck's group of the next level (the top level: to 0); nothing there: fold, go up.  Returns the entry (-1: none).
+// kStop (the many-texts form): a climb whose folded minimum has reached 0 ends as "none" -- lpf_combine treats a neighbour
+// with nothing in common exactly like a missing one, and a climb that has crossed a text's first rank has folded its 0.
+template <bool kStop = false>
 __device__ __forceinline__ int32_t lpf_wave_left(const LpfLevels &L, int64_t n, int64_t c, int32_t v, int32_t *m_io)
 {
     const int lane = lane_id();
@@ -318,6 +533,7 @@ __device__ __forceinline__ int32_t lpf_wave_left(const LpfLevels &L, int64_t n, 
     int k = 1;
     int64_t ck = c / kLpfFan, g = -1;
     for (; k <= L.top; ++k) {
+        if (kStop && m == 0) return -1;                                      // (uniform)
         const int64_t base = k == L.top ? 0 : (ck / kLpfFan) * kLpfFan;
         const int64_t idx = base + lane;
         const bool in = idx < ck && idx < L.cnt[k];
@@ -353,6 +569,7 @@ __device__ __forceinline__ int32_t lpf_wave_left(const LpfLevels &L, int64_t n, 
 
 // ... and the nearest rank at or behind tile end c (ranks (r, c) are folded) whose entry is below v; its own LCP value
 // belongs to the minimum.
+template <bool kStop = false>
 __device__ __forceinline__ int32_t lpf_wave_right(const LpfLevels &L, int64_t n, int64_t c, int32_t v, int32_t *m_io)
 {
     const int lane = lane_id();
@@ -361,6 +578,7 @@ __device__ __forceinline__ int32_t lpf_wave_right(const LpfLevels &L, int64_t n,
     int k = 1;
     int64_t ck = c / kLpfFan, g = -1;
     for (; k <= L.top; ++k) {
+        if (kStop && m == 0) return -1;
         const int64_t cntk = L.cnt[k];
         const int64_t up = (ck + kLpfFan - 1) / kLpfFan * kLpfFan;
         const int64_t end = k == L.top || up > cntk ? cntk : up;
@@ -398,9 +616,13 @@ __device__ __forceinline__ int32_t lpf_wave_right(const LpfLevels &L, int64_t n,
 
 // A fixed grid; each wave takes kLpfClaim tiles' stretches of the list through ctr->claimed until none is left.  Nobody
 // waits for anybody: a grid of any size is correct.
-__global__ __launch_bounds__(kBlock) void lpf_long_kernel(LpfLevels L, int64_t n, const int32_t *__restrict__ list_r,
-                                                          const int4 *__restrict__ list_q, const int32_t *__restrict__ tile_cnt,
-                                                          int32_t *__restrict__ lpf, int32_t *__restrict__ src, LzCounters *ctr)
+// kMany: L is the flat hierarchy of a many call (level 0: sa0 / lcp0), the climbs stop at a folded 0, and the scatter goes
+// to the address the tile pass listed (list_d).
+template <bool kMany>
+__device__ __forceinline__ void lpf_long_body(const LpfLevels &L, int64_t n, const int32_t *__restrict__ list_r,
+                                              const int4 *__restrict__ list_q, const int32_t *__restrict__ list_d,
+                                              const int32_t *__restrict__ tile_cnt, int32_t *__restrict__ lpf,
+                                              int32_t *__restrict__ src, LzCounters *ctr)
 {
     const unsigned long long tiles = (unsigned long long)((n + kLpfTile - 1) / kLpfTile);
     const int lane = lane_id();
@@ -422,12 +644,16 @@ __global__ __launch_bounds__(kBlock) void lpf_long_kernel(LpfLevels L, int64_t n
             // 64 entries at a time: every lane loads one of them and its rank's SA entry, the wave takes them in turn
             for (int b = 0; b < c; b += kWave) {
                 const int held = c - b < kWave ? c - b : kWave;
-                int32_t my_r = -1, my_v = kLpfNone;
+                int32_t my_r = -1, my_v = kLpfNone, my_d = -1;
                 int4 my_q = make_int4(-1, 0, -1, 0);
                 if (lane < held) {
                     my_r = list_r[r0 + b + lane];
                     my_q = list_q[r0 + b + lane];
                     if (my_r >= 0 && (int64_t)my_r < n) my_v = lpf_sa_value(L.sa[0][my_r], n);
+                    if constexpr (kMany) {
+                        my_d = list_d[r0 + b + lane];
+                        if (my_d < 0 || (int64_t)my_d >= n) my_v = kLpfNone;     // (what lpf_tile_body wrote; tested all the same)
+                    }
                 }
                 for (int e = 0; e < held; ++e) {
                     const int32_t v = __builtin_amdgcn_readlane(my_v, e);
@@ -436,13 +662,14 @@ __global__ __launch_bounds__(kBlock) void lpf_long_kernel(LpfLevels L, int64_t n
                     int32_t pl = __builtin_amdgcn_readlane(my_q.x, e), cl = __builtin_amdgcn_readlane(my_q.y, e);
                     int32_t pr = __builtin_amdgcn_readlane(my_q.z, e), cr = __builtin_amdgcn_readlane(my_q.w, e);
                     const int64_t c0 = r / kLpfTile * kLpfTile;
-                    if (pl == kLpfPending) pl = lpf_wave_left(L, n, c0, v, &cl);
-                    if (pr == kLpfPending) pr = lpf_wave_right(L, n, c0 + kLpfTile, v, &cr);
+                    if (pl == kLpfPending) pl = lpf_wave_left<kMany>(L, n, c0, v, &cl);
+                    if (pr == kLpfPending) pr = lpf_wave_right<kMany>(L, n, c0 + kLpfTile, v, &cr);
                     int32_t f, s;
                     lpf_combine(pl, cl, pr, cr, &f, &s);
+                    const int32_t dst = kMany ? __builtin_amdgcn_readlane(my_d, e) : v;
                     if (lane == 0) {
-                        lpf[v] = f;
-                        src[v] = s;
+                        lpf[dst] = f;
+                        src[dst] = s;
                     }
                     longest = (uint32_t)f > longest ? (uint32_t)f : longest;
                 }
@@ -453,6 +680,21 @@ __global__ __launch_bounds__(kBlock) void lpf_long_kernel(LpfLevels L, int64_t n
         if (listed) __hip_atomic_fetch_add(&ctr->list_len, listed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         lz_raise(&ctr->longest_lpf, longest);
     }
+}
+
+__global__ __launch_bounds__(kBlock) void lpf_long_kernel(LpfLevels L, int64_t n, const int32_t *__restrict__ list_r,
+                                                          const int4 *__restrict__ list_q, const int32_t *__restrict__ tile_cnt,
+                                                          int32_t *__restrict__ lpf, int32_t *__restrict__ src, LzCounters *ctr)
+{
+    lpf_long_body<false>(L, n, list_r, list_q, nullptr, tile_cnt, lpf, src, ctr);
+}
+
+__global__ __launch_bounds__(kBlock) void lpf_long_many_kernel(LpfLevels L, int64_t n, const int32_t *__restrict__ list_r,
+                                                               const int4 *__restrict__ list_q, const int32_t *__restrict__ list_d,
+                                                               const int32_t *__restrict__ tile_cnt, int32_t *__restrict__ lpf,
+                                                               int32_t *__restrict__ src, LzCounters *ctr)
+{
+    lpf_long_body<true>(L, n, list_r, list_q, list_d, tile_cnt, lpf, src, ctr);
 }
 
 // ---------------------------------------------------------------------------------------------- the parse
@@ -627,22 +869,7 @@ __global__ __launch_bounds__(kBlock) void lz_emit_kernel(const uint8_t *__restri
 // own end (lz_walk_many_kernel); a tile's entry is the minimum over what the lanes report -- the chain from there passes
 // every later text start of the tile.  lz_offsets_kernel turns the scanned tile counts and the bitmap into the phrases
 // before each text.
-struct LzTexts {
-    const int64_t *off;                          // count + 1: the layout of lpf / src, the triples' starts count from off[t]
-    const int64_t *bytes;                        // count + 1: text t's bytes begin at T[bytes[t]] (off itself, or the cats' offsets)
-    int32_t count;
-};
-
-// the text that holds position i, among texts lo .. hi (off[lo] <= i < off[hi + 1]): the last t with off[t] <= i
-__device__ __forceinline__ int32_t lz_text_of(const int64_t *__restrict__ off, int32_t lo, int32_t hi, int64_t i)
-{
-    ++hi;
-    while (hi - lo > 1) {
-        const int32_t mid = (int32_t)(((int64_t)lo + hi) >> 1);
-        if (off[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
+// (LzTexts and lz_text_of: above, with the LPF array of many texts)
 
 // next[] of tile t0 .. into LDS: i + clamp(lpf[i], 1, end of i's text - i); n for the rest of the tile
 __device__ __forceinline__ void lz_load_next_many(const int32_t *__restrict__ lpf, const LzTexts &tx, int64_t n, int64_t t0, int32_t *s_next)

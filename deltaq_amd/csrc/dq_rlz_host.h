@@ -312,6 +312,7 @@ int lzparse_dev(const void *d_text, int64_t n, const void *d_len, const void *d_
 constexpr int kMsManyLaunches = 4;               // summary, carry, apply, settle
 constexpr int kLzParseManyLaunches = 6;          // exit, walk, mark, scan, emit, offsets
 constexpr int kRlzManyLaunches = kMsManyLaunches + kLzParseManyLaunches;
+static_assert(kLzParseManyLaunches == kLzManyParseKernels);                  // (lz_parse_many_enqueue, dq_lz77_host.h)
 
 namespace {
 
@@ -335,21 +336,6 @@ inline int check_text_offsets(const int64_t *off, int32_t count)
     DQ_TRY(check_many_offsets(off, count));
     if (off[count] > 0x7fffffffLL)
         return fail(DQ_ERR_TOO_LARGE, "the texts together exceed 2^31-1 bytes: the parse has 32-bit positions");
-    return DQ_OK;
-}
-
-// The device forms' first step: the offset arrays (b may be null) come to the host once, behind one wait that is not
-// counted among the call's; on a slot that is given back before the call leases the one its size needs.
-inline int fetch_offsets(int dev, void *stream, const void *d_a, const void *d_b, int32_t count, std::vector<int64_t> &a,
-                         std::vector<int64_t> &b)
-{
-    SlotLease lease(dev, 0);
-    DeviceCtx &c = *lease.c;
-    DQ_TRY(init_ctx(c, dev));
-    hipStream_t st = stream ? (hipStream_t)stream : c.stream;
-    DQ_TRY(copy_many_offsets(d_a, count, st, a));
-    if (d_b) DQ_TRY(copy_many_offsets(d_b, count, st, b));
-    HIP_TRY(hipStreamSynchronize(st));
     return DQ_OK;
 }
 
@@ -392,43 +378,11 @@ int ms_many_enqueue(hipStream_t st, const RlzScratch &at, const MsSegs &sg, int6
 int parse_many_enqueue(hipStream_t st, const RlzScratch &at, const LzTexts &tx, int64_t positions, const uint8_t *d_bytes,
                        const int32_t *d_len, const int32_t *d_src, int32_t *d_phrases, int64_t cap, int64_t *d_poff, char *scratch)
 {
-    LzCounters *ctr = reinterpret_cast<LzCounters *>(scratch);
-    int32_t *exits = reinterpret_cast<int32_t *>(scratch + at.exits_at), *entry = reinterpret_cast<int32_t *>(scratch + at.entry_at);
-    uint32_t *count = reinterpret_cast<uint32_t *>(scratch + at.count_at), *bits = reinterpret_cast<uint32_t *>(scratch + at.bits_at);
-    const int64_t tiles = lz_tiles(positions);
-    const dim3 grid((unsigned)tiles), block(kBlock);
-    HIP_TRY(hipMemsetAsync(entry, 0xff, (size_t)tiles * sizeof(int32_t), st));
-    hipLaunchKernelGGL(lz_exit_many_kernel, grid, block, 0, st, d_len, tx, positions, exits);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(lz_walk_many_kernel, dim3((unsigned)((tx.count + kBlock - 1) / kBlock)), block, 0, st, (const int32_t *)exits, tx,
-                       positions, entry, ctr);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(lz_mark_many_kernel, grid, block, 0, st, d_len, tx, positions, (const int32_t *)entry, bits, count);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(lz_scan_kernel, dim3(1), block, 0, st, count, tiles, ctr);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(lz_emit_many_kernel, grid, block, 0, st, d_bytes, d_len, d_src, tx, positions, (const uint32_t *)bits,
-                       (const uint32_t *)count, d_phrases, cap, ctr);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(lz_offsets_kernel, dim3((unsigned)((tx.count + 1 + kBlock - 1) / kBlock)), block, 0, st, tx, positions,
-                       (const uint32_t *)bits, (const uint32_t *)count, (const LzCounters *)ctr, d_poff);
-    HIP_TRY(hipGetLastError());
+    DQ_TRY(lz_parse_many_enqueue(st, tx, positions, d_bytes, d_len, d_src, reinterpret_cast<int32_t *>(scratch + at.exits_at),
+                                 reinterpret_cast<int32_t *>(scratch + at.entry_at), reinterpret_cast<uint32_t *>(scratch + at.count_at),
+                                 reinterpret_cast<uint32_t *>(scratch + at.bits_at), d_phrases, cap, d_poff,
+                                 reinterpret_cast<LzCounters *>(scratch)));
     t_rlz_info.launches += kLzParseManyLaunches;
-    return DQ_OK;
-}
-
-inline int many_args(int32_t count, bool nulls)
-{
-    if (count < 0) return fail(DQ_ERR_BAD_ARGS, "negative count");
-    if (count > 0 && nulls) return fail(DQ_ERR_BAD_ARGS, "null buffer");
-    return DQ_OK;
-}
-
-inline int many_parse_args(int32_t count, int64_t cap, const int64_t *phrase_offsets)
-{
-    if (count < 0) return fail(DQ_ERR_BAD_ARGS, "negative count");
-    if (cap < 0) return fail(DQ_ERR_BAD_ARGS, "negative capacity");
-    if (!phrase_offsets) return fail(DQ_ERR_BAD_ARGS, "null phrase_offsets");
     return DQ_OK;
 }
 

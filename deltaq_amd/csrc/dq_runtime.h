@@ -710,6 +710,15 @@ int lz77_host(const uint8_t *text, int64_t n, const int32_t *sa, const int32_t *
               int32_t device);
 int lz77_dev(const void *d_text, int64_t n, const void *d_sa, const void *d_lcp, void *d_phrases, int64_t cap, int64_t *count,
              int32_t device, void *stream);
+// ... and of many texts in one call: the bodies of dq_lpf_hip_many_* and dq_lz77_hip_many_*
+int lpf_many_host(const int64_t *offsets, int32_t count, const int32_t *sas, const int32_t *lcps, int32_t *lpf, int32_t *src,
+                  int32_t device);
+int lpf_many_dev(const void *d_offsets, int32_t count, const void *d_sas, const void *d_lcps, void *d_lpf, void *d_src, int32_t device,
+                 void *stream);
+int lz77_many_host(const uint8_t *texts, const int64_t *offsets, int32_t count, const int32_t *sas, const int32_t *lcps,
+                   int32_t *phrases, int64_t cap, int64_t *phrase_offsets, int32_t device);
+int lz77_many_dev(const void *d_texts, const void *d_offsets, int32_t count, const void *d_sas, const void *d_lcps, void *d_phrases,
+                  int64_t cap, int64_t *phrase_offsets, int32_t device, void *stream);
 
 // Matching statistics of new against old from the SA and LCP of new + old, the relative LZ factorization and the parse
 // alone (dq_rlz_host.h, in dq_sufcheck.hip): the bodies of dq_mstat_hip_*, dq_rlz_hip_* and dq_lzparse_hip_*.  All of

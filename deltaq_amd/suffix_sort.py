@@ -909,6 +909,121 @@ class HipSuffixSort:
 
     lz77 = Lz77
 
+    # -- ... of many texts in one call: launches that depend on the total size alone, one wait (no counterpart) -------
+    def LpfMany(self, suffixes, lcps=None):
+        """``Lpf`` of many texts through the same launches and one wait: from lists of the texts' int32 suffix arrays and
+        LCP arrays (what ``SortMany`` and ``LcpMany`` return) a list of ``(lpf, src)``, each what
+        ``Lpf(suffixes[t], lcps[t])`` returns (``dq_lpf_hip_many_i32``).  The device form
+        ``LpfMany((offsets_tensor, sas_tensor, lcps_tensor))`` -- ``SortMany``'s device layout -- stays on the device on
+        the current torch stream (``dq_lpf_hip_many_dev_i32``) and returns two int32 tensors in that layout: text t's
+        entries start at ``offsets[t]``, and ``src`` counts from the text's own start.  ``_abi.last_lz77_info()`` tells
+        what happened.
+        """
+        if isinstance(suffixes, tuple) or _is_torch_tensor(suffixes) or _is_torch_tensor(lcps):
+            import torch
+
+            if not isinstance(suffixes, tuple) or len(suffixes) != 3 or lcps is not None or not all(_is_torch_tensor(a) for a in suffixes):
+                raise TypeError(self.MIXED_MANY_MESSAGE)
+            off, sa, lc = suffixes
+            sa, lc = self._lz_device_arrays(sa, lc, None)
+            if off.dtype != torch.int64 or off.dim() != 1 or not off.is_contiguous() or off.numel() < 1 or off.device != sa.device:
+                raise TypeError("offsets must be a contiguous 1-D int64 tensor of count + 1 entries on the arrays' device")
+            count = off.numel() - 1
+            lpf, src = torch.empty_like(sa), torch.empty_like(sa)
+            if count == 0 or sa.numel() == 0:
+                return lpf, src
+            dev, stream = _device_and_stream(sa)
+            _abi.check(self._lib.dq_lpf_hip_many_dev_i32(off.data_ptr(), count, sa.data_ptr(), lc.data_ptr(), lpf.data_ptr(),
+                                                         src.data_ptr(), dev, stream))
+            return lpf, src
+        off, flat_sa, flat_lcp = self._lz_many_host_arrays(suffixes, lcps, None)
+        count, total = off.size - 1, int(off[-1])
+        lpf, src = np.empty(max(total, 1), dtype=np.int32), np.empty(max(total, 1), dtype=np.int32)
+        _abi.check(self._lib.dq_lpf_hip_many_i32(off.ctypes.data, count, flat_sa.ctypes.data, flat_lcp.ctypes.data, lpf.ctypes.data,
+                                                 src.ctypes.data, self.device))
+        return [(lpf[off[t]:off[t + 1]], src[off[t]:off[t + 1]]) for t in range(count)]
+
+    lpf_many = LpfMany
+
+    def Lz77Many(self, texts, suffixes=None, lcps=None):
+        """``Lz77`` of many texts in ONE native call: a list of ``(z_t, 3)`` int32 arrays, each what ``Lz77(texts[t])``
+        returns and ``lz77_decode`` turns back into ``texts[t]`` (``dq_lz77_hip_many_i32``; the call has room for a
+        phrase per byte, which no factorization exceeds).  ``suffixes`` and ``lcps`` are lists of the texts' int32 suffix
+        arrays and LCP arrays; where either is left out, ``SortMany`` and ``LcpMany`` run first.  The device form
+        ``Lz77Many((texts_tensor, offsets_tensor), suffixes=sas_tensor, lcps=lcps_tensor)`` -- ``SortMany``'s device
+        layout -- stays on the device on the current torch stream (``dq_lz77_hip_many_dev_i32``) and returns
+        ``(phrases_tensor, phrase_offsets)``: the triples of all texts back to back (starts and sources counted from
+        each text's own start) and a host int64 array, text t's triples at ``[phrase_offsets[t], phrase_offsets[t + 1])``.
+        """
+        if isinstance(texts, tuple) or any(_is_torch_tensor(a) for a in (texts, suffixes, lcps)):
+            import torch
+
+            if (not isinstance(texts, tuple) or len(texts) != 2 or not all(_is_torch_tensor(a) for a in texts)
+                    or any(a is not None and not _is_torch_tensor(a) for a in (suffixes, lcps))):
+                raise TypeError(self.MIXED_MANY_MESSAGE)
+            flat, off = texts
+            self._check_many_device_layout(flat, off)
+            if flat.numel() > INT_MAX:
+                raise ValueError("Lz77Many has 32-bit indices: the texts together must be shorter than 2^31 bytes")
+            if suffixes is None or lcps is None:
+                suffixes = self.SortMany((flat, off))
+                lcps = self.LcpMany((flat, off), suffixes)
+            sa, lc = self._lz_device_arrays(suffixes, lcps, flat)
+            count, total = off.numel() - 1, flat.numel()
+            poff = np.zeros(count + 1, dtype=np.int64)
+            phrases = torch.empty((total, 3), dtype=torch.int32, device=flat.device)
+            if count == 0 or total == 0:
+                return phrases, poff
+            dev, stream = _device_and_stream(flat)
+            _abi.check(self._lib.dq_lz77_hip_many_dev_i32(flat.data_ptr(), off.data_ptr(), count, sa.data_ptr(), lc.data_ptr(),
+                                                          phrases.data_ptr(), total, poff.ctypes.data, dev, stream))
+            return phrases[:int(poff[-1])], poff
+        arrs = [_as_text(t) for t in texts]
+        if any(a.ndim != 1 for a in arrs):
+            raise TypeError("every text must be one-dimensional")
+        if sum(a.size for a in arrs) > INT_MAX:
+            raise ValueError("Lz77Many has 32-bit indices: the texts together must be shorter than 2^31 bytes")
+        if suffixes is None or lcps is None:
+            nonempty = any(a.size for a in arrs)
+            suffixes = self.SortMany(arrs) if nonempty else [np.zeros(0, np.int32) for _ in arrs]
+            lcps = self.LcpMany(arrs, suffixes) if nonempty else suffixes
+        off, flat_sa, flat_lcp = self._lz_many_host_arrays(suffixes, lcps, arrs)
+        count, total = len(arrs), int(off[-1])
+        flat = np.concatenate(arrs) if total else np.zeros(1, np.uint8)
+        poff = np.zeros(count + 1, dtype=np.int64)
+        phrases = np.empty((max(total, 1), 3), dtype=np.int32)
+        _abi.check(self._lib.dq_lz77_hip_many_i32(flat.ctypes.data, off.ctypes.data, count, flat_sa.ctypes.data, flat_lcp.ctypes.data,
+                                                  phrases.ctypes.data, total, poff.ctypes.data, self.device))
+        return [phrases[poff[t]:poff[t + 1]] for t in range(count)]
+
+    lz77_many = Lz77Many
+
+    def _lz_many_host_arrays(self, suffixes, lcps, texts):
+        """offsets and the flat suffix arrays / LCP arrays of a host many-texts call (a buffer of no entries has no
+        address: one entry stands in); ``texts``: the texts they must fit, or None."""
+        if lcps is None or any(_is_torch_tensor(a) for a in (suffixes, lcps)):
+            raise TypeError(self.MIXED_MANY_MESSAGE)
+        suffixes, lcps = list(suffixes), list(lcps)
+        if len(suffixes) != len(lcps) or (texts is not None and len(suffixes) != len(texts)):
+            raise ValueError("one suffix array and one LCP array per text")
+        for name, group in (("suffix", suffixes), ("LCP", lcps)):
+            if any(_is_torch_tensor(a) for a in group):
+                raise TypeError(self.MIXED_MANY_MESSAGE)
+            if any(not isinstance(a, np.ndarray) or a.dtype != np.int32 or a.ndim != 1 for a in group):
+                raise TypeError(f"every {name} array must be a 1-D numpy int32 array")
+        if any(a.size != b.size for a, b in zip(suffixes, lcps)) or (texts is not None and any(a.size != t.size for a, t in zip(suffixes, texts))):
+            raise ValueError(LENGTH_MISMATCH_MESSAGE)
+        count = len(suffixes)
+        off = np.zeros(count + 1, dtype=np.int64)
+        if count:
+            np.cumsum([a.size for a in suffixes], out=off[1:])
+        total = int(off[-1])
+        if total > INT_MAX:
+            raise ValueError("32-bit indices: the texts together must be shorter than 2^31 bytes")
+        flat_sa = np.concatenate(suffixes) if total else np.zeros(1, np.int32)
+        flat_lcp = np.concatenate(lcps) if total else np.zeros(1, np.int32)
+        return off, flat_sa, flat_lcp
+
     # -- a new file against an old one: matching statistics and the relative LZ factorization (no counterpart) --------
     def MatchStats(self, old, new, suffixes=None, lcp=None):
         """``(len, src)``: for every position j of ``new`` the length of the longest prefix of ``new[j:]`` that occurs

@@ -772,18 +772,60 @@ int32_t dq_lcp_last_info(int64_t *info, int32_t count);
  * host forms add their device copies of the arrays, the text and min(cap, n) triples.  No CPU fallback: DQ_ERR_OOM when
  * that does not fit.  The _dev_ forms take device pointers on `device`, enqueue on `stream` (NULL = the library's stream)
  * and return after it has drained.  One stream wait per call.
- * Out of scope: int64 forms, a many-texts form, and computing sa or lcp inside these calls (dq_sufsort_hip_*, dq_lcp_hip_*
- * do that).  No text above 2^20 + 1 bytes has been compared with a model.
+ * Out of scope: int64 forms, and computing sa or lcp inside these calls (dq_sufsort_hip_*, dq_lcp_hip_* do that).  No
+ * text above 2^20 + 1 bytes has been compared with a model.
  * dq_lz77_last_info: shape of the last of these calls on this thread, reset when one starts; `count` entries (7 are
  * defined, further ones read 0; a NULL array is DQ_ERR_BAD_ARGS): [0] phrases z, [1] literal phrases (both 0 in LPF
  * calls); [2] the longest lpf value (LPF calls) or the longest phrase (LZ77 calls); [3] ranks handed to the wave kernel;
- * [4] serial hops of the tile walker (0 in LPF calls); [5] kernel launches; [6] stream waits. */
+ * [4] serial hops of the tile walker (0 in LPF calls); [5] kernel launches; [6] stream waits.
+ *
+ * Many texts in one call (dq_lpf_hip_many_*, dq_lz77_hip_many_*).  The layout is dq_sufsort_hip_many_i32's: `count`
+ * texts back to back, text t at [offsets[t], offsets[t + 1]) with offsets[count + 1]; sas and lcps are what
+ * dq_sufsort_hip_many_* and dq_lcp_hip_many_* return for it (entries of sas count from the start of their own text).  lpf
+ * and src use the same layout, src[offsets[t] + i] is a position in text t itself, or -1.  Segment t of lpf and src, and
+ * text t's triples, are exactly what dq_lpf_hip_i32 / dq_lz77_hip_i32 give for text t alone; nothing outside the segments
+ * is written.  The triples (start, len, third) count start and a copy's source from the text's own start and are packed
+ * text after text: text t's are triples [phrase_offsets[t], phrase_offsets[t + 1]).  phrase_offsets[count + 1] is a HOST
+ * pointer in both forms and always receives the true prefix sums, whatever cap is; the first min(Z, cap) triples of all
+ * Z = phrase_offsets[count] are written and nothing beyond them; cap == 0 with phrases == NULL is the sizing call.
+ * Conventions as for dq_rlz_hip_many_*: all arguments, the offsets included, are judged before any device work; count ==
+ * 0, and in the host forms a call whose texts are all empty, return DQ_OK before a device is looked for, with
+ * phrase_offsets all zero; the device forms fetch d_offsets once (a wait that is not counted); one stream wait per call;
+ * a refusal leaves phrase_offsets untouched.
+ *   count < 0, a NULL buffer that is needed, negative cap, offsets[0] != 0, decreasing offsets     DQ_ERR_BAD_ARGS
+ *   the texts together above 2^31-1 bytes (both forms: the list of ranks and the parse's positions are 32-bit;
+ *   checkable from offsets alone)                                                                   DQ_ERR_TOO_LARGE
+ * Untrusted arrays: an entry of sas outside [0, size of its OWN text) -- one inside the call's total included -- makes
+ * the call return DQ_ERR_BAD_ARGS and is never an address; lcps values are clamped to [0, n_t]; the entry of lcps at a
+ * text's first rank is never used (poison there changes nothing).  In-range nonsense gives DQ_OK: every written src is
+ * in [-1, n_t) and every lpf in [0, n_t], no access leaves the buffers, every walk is bounded.  (A position that no
+ * rank names reads 0 / -1 in the host form; the device form leaves that entry of d_lpf / d_src as it was.)
+ * The kernels run over the flat ranks R = offsets[count] (deltaq_amd/csrc/dq_lz77.h): the entry of lcps at a text's first
+ * rank takes part as 0, so a neighbour found in a foreign text has nothing in common and counts as missing -- the text
+ * boundary is an exact barrier; the minima before and behind a tile are cut at text starts.  The launches are a function
+ * of R alone (lpf_many_launches / lz77_many_launches in deltaq_amd/csrc/dq_lz77_host.h: the levels of R + 3, and 6 more
+ * for the parse): a call of 1000 texts makes as many as a call of one text of the same total.  The record is
+ * dq_lz77_last_info's: totals over the call in [0], [1], [3], [4], the maximum in [2].  Device memory: what a one-text
+ * call over R bytes takes, and 12 bytes per rank (the call's own range-tested copy of sas and lcps, and the listed ranks'
+ * addresses), 16 bytes per 256 ranks, for an LZ77 call 8 bytes per text: 32.3 bytes per rank for an LPF call, 40.4 per
+ * rank and 8 per text for an LZ77 call; the host forms add their copies of the arrays, the offsets, the texts and
+ * min(cap, R) triples.  A host-form call that does not fit is DQ_ERR_OOM, it is not split.  The many forms are never
+ * chosen automatically. */
 int32_t dq_lpf_hip_i32(const int32_t *sa, const int32_t *lcp, int64_t n, int32_t *lpf, int32_t *src, int32_t device);
 int32_t dq_lpf_hip_dev_i32(const void *d_sa, const void *d_lcp, int64_t n, void *d_lpf, void *d_src, int32_t device, void *stream);
 int32_t dq_lz77_hip_i32(const uint8_t *text, int64_t n, const int32_t *sa, const int32_t *lcp,
                         int32_t *phrases, int64_t cap, int64_t *count, int32_t device);
 int32_t dq_lz77_hip_dev_i32(const void *d_text, int64_t n, const void *d_sa, const void *d_lcp,
                             void *d_phrases, int64_t cap, int64_t *count, int32_t device, void *stream);
+int32_t dq_lpf_hip_many_i32(const int64_t *offsets, int32_t count, const int32_t *sas, const int32_t *lcps,
+                            int32_t *lpf, int32_t *src, int32_t device);
+int32_t dq_lpf_hip_many_dev_i32(const void *d_offsets, int32_t count, const void *d_sas, const void *d_lcps,
+                                void *d_lpf, void *d_src, int32_t device, void *stream);
+int32_t dq_lz77_hip_many_i32(const uint8_t *texts, const int64_t *offsets, int32_t count, const int32_t *sas,
+                             const int32_t *lcps, int32_t *phrases, int64_t cap, int64_t *phrase_offsets, int32_t device);
+int32_t dq_lz77_hip_many_dev_i32(const void *d_texts, const void *d_offsets, int32_t count, const void *d_sas,
+                                 const void *d_lcps, void *d_phrases, int64_t cap, int64_t *phrase_offsets,
+                                 int32_t device, void *stream);
 int32_t dq_lz77_last_info(int64_t *info, int32_t count);
 
 /* ---- matching statistics of a new file against an old one, and the relative Lempel-Ziv factorization, on the device ----

@@ -69,6 +69,8 @@ PROTOTYPES = {                                               # export -> (restyp
     "dq_lpf_hip_dev_i32": (_i32, [_vp, _vp, _i64, _vp, _vp, _i32, _vp]),
     "dq_lz77_hip_dev_i32": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i32, _vp]),
     "dq_lz77_last_info": _INFO,
+    "dq_lpf_hip_many_dev_i32": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "dq_lz77_hip_many_dev_i32": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _i32, _vp]),
     "dq_mstat_hip_dev_i32": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _i32, _vp]),
     "dq_rlz_hip_dev_i32": (_i32, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _i32, _vp]),
     "dq_lzparse_hip_dev_i32": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i32, _vp]),
