@@ -187,6 +187,35 @@ public sealed class HipSuffixSort : ISuffixSort
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
     private static extern unsafe int dq_rlz_last_info(long* info, int count);
 
+    // the phrases back into bytes on the device: the verdict of a text lands in status (0 ok, -1 malformed, -2 slot too small), its size in outLen
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    private static extern unsafe int dq_lz77_decode_hip_i32(int* phrases, long z, byte* output, long cap, long* outLen, int* status, int device);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    private static extern unsafe int dq_rlz_decode_hip_i32(byte* oldData, long n, int* phrases, long z, byte* output, long cap, long* outLen, int* status, int device);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    private static extern unsafe int dq_lz77_decode_hip_many_i32(int* phrases, long* phraseOffsets, int count, byte* output, long* outOffsets, long* outLen, int* status, int device);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    private static extern unsafe int dq_rlz_decode_hip_many_i32(byte* olds, long* oldSpans, int* phrases, long* phraseOffsets, int count, byte* output, long* outOffsets, long* outLen, int* status, int device);
+
+    // (declared for hosts that keep their buffers on the device: device pointers, a hipStream_t or zero; the offset arrays, outLen and status are host memory)
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern unsafe int dq_lz77_decode_hip_dev_i32(IntPtr dPhrases, long z, IntPtr dOut, long cap, long* outLen, int* status, int device, IntPtr stream);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern unsafe int dq_rlz_decode_hip_dev_i32(IntPtr dOld, long n, IntPtr dPhrases, long z, IntPtr dOut, long cap, long* outLen, int* status, int device, IntPtr stream);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern unsafe int dq_lz77_decode_hip_many_dev_i32(IntPtr dPhrases, long* phraseOffsets, int count, IntPtr dOut, long* outOffsets, long* outLen, int* status, int device, IntPtr stream);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern unsafe int dq_rlz_decode_hip_many_dev_i32(IntPtr dOlds, long oldsBytes, long* oldSpans, IntPtr dPhrases, long* phraseOffsets, int count, IntPtr dOut, long* outOffsets, long* outLen, int* status, int device, IntPtr stream);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    private static extern unsafe int dq_lzdecode_last_info(long* info, int count);
+
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
     private static extern int dq_abi_version();
 
@@ -1583,6 +1612,191 @@ public sealed class HipSuffixSort : ISuffixSort
         }
 
         return text.ToArray();
+    }
+
+    private static long DecodedSize(ReadOnlySpan<int> phrases, int text)
+    {
+        if (phrases.Length % 3 != 0)
+        {
+            throw new ArgumentException("phrases are three ints each");
+        }
+
+        if (phrases.Length == 0)
+        {
+            return 0;
+        }
+
+        long size = (long)phrases[phrases.Length - 3] + Math.Max(1, phrases[phrases.Length - 2]);
+        if (size <= 0 || size > int.MaxValue)
+        {
+            throw new ArgumentException($"text {text}: malformed phrases (the last one ends at {size})");
+        }
+
+        return size;
+    }
+
+    private static void DecodeVerdict(int status, int text)
+    {
+        if (status != 0)
+        {
+            throw new ArgumentException(status == -1 ? $"text {text}: malformed phrases" : $"text {text}: the phrases decode to more than their last one says");
+        }
+    }
+
+    /// <summary>
+    /// <see cref="Lz77Decode"/> on the device (dq_lz77_decode_hip_i32): the text of a factorization <c>Lz77</c> returned.
+    /// The static <see cref="Lz77Decode"/> keeps its name and stays the host loop.  Phrases are untrusted: a malformed
+    /// list is refused with an <see cref="ArgumentException"/>, as the host loop refuses it.
+    /// </summary>
+    public unsafe byte[] Lz77DecodeDevice(ReadOnlySpan<int> phrases)
+    {
+        long size = DecodedSize(phrases, 0), outLen = 0;
+        var text = new byte[Math.Max(size, 1)];
+        int status = 0, rc;
+        fixed (int* pPhrases = phrases)
+        fixed (byte* pText = text)
+        {
+            rc = dq_lz77_decode_hip_i32(pPhrases, phrases.Length / 3, pText, size, &outLen, &status, _device);
+        }
+
+        LcpResult(rc, "dq_lz77_decode_hip_i32");
+        DecodeVerdict(status, 0);
+        return text.AsSpan(0, checked((int)outLen)).ToArray();
+    }
+
+    /// <summary>
+    /// <see cref="RlzDecode"/> on the device (dq_rlz_decode_hip_i32): the new file of a relative factorization against
+    /// <paramref name="old"/>.  A copy from outside old makes the list malformed.
+    /// </summary>
+    public unsafe byte[] RlzDecodeDevice(ReadOnlySpan<byte> old, ReadOnlySpan<int> phrases)
+    {
+        long size = DecodedSize(phrases, 0), outLen = 0;
+        var text = new byte[Math.Max(size, 1)];
+        int status = 0, rc;
+        fixed (byte* pOld = old)
+        fixed (int* pPhrases = phrases)
+        fixed (byte* pText = text)
+        {
+            rc = dq_rlz_decode_hip_i32(pOld, old.Length, pPhrases, phrases.Length / 3, pText, size, &outLen, &status, _device);
+        }
+
+        LcpResult(rc, "dq_rlz_decode_hip_i32");
+        DecodeVerdict(status, 0);
+        return text.AsSpan(0, checked((int)outLen)).ToArray();
+    }
+
+    /// <summary>
+    /// <see cref="Lz77DecodeDevice"/> of many texts in ONE native call (dq_lz77_decode_hip_many_i32): entry t is the text
+    /// of phrases[t], what <see cref="Lz77Many"/> returns for it.  The slots are sized off every text's last triple.
+    /// </summary>
+    public unsafe byte[][] Lz77DecodeMany(IReadOnlyList<ReadOnlyMemory<int>> phrases)
+    {
+        return DecodeMany(null, phrases);
+    }
+
+    /// <summary>
+    /// <see cref="RlzDecodeDevice"/> of many pairs in ONE native call (dq_rlz_decode_hip_many_i32): entry t is the new
+    /// file of phrases[t] against olds[t].  An old file that several texts name may be passed once per text: only its
+    /// span is uploaded twice, the C ABI's old_spans let a native host name one copy from every text.
+    /// </summary>
+    public unsafe byte[][] RlzDecodeMany(IReadOnlyList<ReadOnlyMemory<byte>> olds, IReadOnlyList<ReadOnlyMemory<int>> phrases)
+    {
+        if (olds.Count != phrases.Count)
+        {
+            throw new ArgumentException("one old file per phrase list");
+        }
+
+        return DecodeMany(olds, phrases);
+    }
+
+    private unsafe byte[][] DecodeMany(IReadOnlyList<ReadOnlyMemory<byte>>? olds, IReadOnlyList<ReadOnlyMemory<int>> phrases)
+    {
+        int count = phrases.Count;
+        var (tripleOffsets, flat) = Flatten(phrases, "DecodeMany");
+        var phraseOffsets = new long[count + 1];
+        var outOffsets = new long[count + 1];
+        for (int t = 0; t < count; t++)
+        {
+            phraseOffsets[t + 1] = tripleOffsets[t + 1] / 3;
+            outOffsets[t + 1] = outOffsets[t] + DecodedSize(phrases[t].Span, t);
+        }
+
+        if (outOffsets[count] > int.MaxValue)
+        {
+            throw new ArgumentException("the decoders have 32-bit positions: the texts together must be shorter than 2^31 bytes");
+        }
+
+        var output = new byte[Math.Max(outOffsets[count], 1)];
+        var outLen = new long[Math.Max(count, 1)];
+        var status = new int[Math.Max(count, 1)];
+        int rc;
+        string entry;
+        if (olds is null)
+        {
+            entry = "dq_lz77_decode_hip_many_i32";
+            fixed (int* pPhrases = flat)
+            fixed (long* pPhraseOffsets = phraseOffsets)
+            fixed (byte* pOut = output)
+            fixed (long* pOutOffsets = outOffsets)
+            fixed (long* pOutLen = outLen)
+            fixed (int* pStatus = status)
+            {
+                rc = dq_lz77_decode_hip_many_i32(pPhrases, pPhraseOffsets, count, pOut, pOutOffsets, pOutLen, pStatus, _device);
+            }
+        }
+        else
+        {
+            entry = "dq_rlz_decode_hip_many_i32";
+            var (oldOffsets, oldFlat) = Flatten(olds, "RlzDecodeMany");
+            var spans = new long[Math.Max(2 * count, 1)];
+            for (int t = 0; t < count; t++)
+            {
+                spans[2 * t] = oldOffsets[t];
+                spans[2 * t + 1] = oldOffsets[t + 1];
+            }
+
+            fixed (byte* pOlds = oldFlat)
+            fixed (long* pSpans = spans)
+            fixed (int* pPhrases = flat)
+            fixed (long* pPhraseOffsets = phraseOffsets)
+            fixed (byte* pOut = output)
+            fixed (long* pOutOffsets = outOffsets)
+            fixed (long* pOutLen = outLen)
+            fixed (int* pStatus = status)
+            {
+                rc = dq_rlz_decode_hip_many_i32(pOlds, pSpans, pPhrases, pPhraseOffsets, count, pOut, pOutOffsets, pOutLen, pStatus, _device);
+            }
+        }
+
+        LcpResult(rc, entry);
+        var result = new byte[count][];
+        for (int t = 0; t < count; t++)
+        {
+            DecodeVerdict(status[t], t);
+            result[t] = output.AsSpan(checked((int)outOffsets[t]), checked((int)outLen[t])).ToArray();
+        }
+
+        return result;
+    }
+
+    /// <summary>
+    /// Shape of the last device decode on this thread (dq_lzdecode_last_info): texts with status 0, texts refused,
+    /// positions whose byte was not known after the tile pass, global rounds that still found work (both 0 after the
+    /// relative decoder), kernel launches, stream waits.
+    /// </summary>
+    public static unsafe long[] LastLzDecodeInfo()
+    {
+        var info = new long[6];
+        fixed (long* p = info)
+        {
+            int rc = dq_lzdecode_last_info(p, info.Length);
+            if (rc != 0)
+            {
+                throw new InvalidOperationException($"dq_lzdecode_last_info failed ({rc})");
+            }
+        }
+
+        return info;
     }
 
     /// <summary>

@@ -67,6 +67,9 @@ EXPORTS = (
     "dq_lzparse_hip_i32", "dq_lzparse_hip_dev_i32", "dq_rlz_last_info",
     "dq_mstat_hip_many_i32", "dq_mstat_hip_many_dev_i32", "dq_rlz_hip_many_i32", "dq_rlz_hip_many_dev_i32",
     "dq_lzparse_hip_many_i32", "dq_lzparse_hip_many_dev_i32",
+    "dq_lz77_decode_hip_i32", "dq_lz77_decode_hip_dev_i32", "dq_rlz_decode_hip_i32", "dq_rlz_decode_hip_dev_i32",
+    "dq_lz77_decode_hip_many_i32", "dq_lz77_decode_hip_many_dev_i32", "dq_rlz_decode_hip_many_i32",
+    "dq_rlz_decode_hip_many_dev_i32", "dq_lzdecode_last_info",
     "dq_bsdiff_search_dev_i32", "dq_bsdiff_search_dev_i64", "dq_bsdiff_search_i32", "dq_bsdiff_search_i64",
     "dq_bsdiff_create", "dq_bsdiff_patch_bound", "dq_bsdiff_scan_i32", "dq_bspatch_apply",
     "dq_bspatch_new_size_many", "dq_bspatch_apply_many", "dq_bspatch_index_apply_many",
@@ -121,6 +124,10 @@ LZ77_RECORD = _n("phrases", "literals", "longest", "wave_ranks", "walker_hops", 
 
 # ... and the record of dq_rlz_last_info, struct RlzInfo of deltaq_amd/csrc/dq_rlz_info.h; tests/test_rlz_cpu.py checks it.
 RLZ_RECORD = _n("phrases", "literals", "longest", "matched", "walker_hops", "launches", "stream_waits")
+
+# ... and the record of dq_lzdecode_last_info, struct LzDecodeInfo of deltaq_amd/csrc/dq_lzdecode_info.h;
+# tests/test_lzdecode_cpu.py checks it.
+LZDECODE_RECORD = _n("texts_ok", "texts_refused", "linked", "jump_rounds", "launches", "stream_waits")
 
 
 class BackendMissingError(RuntimeError):
@@ -246,6 +253,24 @@ def load() -> ctypes.CDLL:
     L.dq_lzparse_hip_many_dev_i32.argtypes = [vp, vp, i32, vp, vp, vp, i64, vp, i32, vp]
     L.dq_rlz_last_info.restype = i32
     L.dq_rlz_last_info.argtypes = [ctypes.POINTER(i64), i32]
+    L.dq_lz77_decode_hip_i32.restype = i32
+    L.dq_lz77_decode_hip_i32.argtypes = [vp, i64, vp, i64, vp, vp, i32]
+    L.dq_lz77_decode_hip_dev_i32.restype = i32
+    L.dq_lz77_decode_hip_dev_i32.argtypes = [vp, i64, vp, i64, vp, vp, i32, vp]
+    L.dq_rlz_decode_hip_i32.restype = i32
+    L.dq_rlz_decode_hip_i32.argtypes = [vp, i64, vp, i64, vp, i64, vp, vp, i32]
+    L.dq_rlz_decode_hip_dev_i32.restype = i32
+    L.dq_rlz_decode_hip_dev_i32.argtypes = [vp, i64, vp, i64, vp, i64, vp, vp, i32, vp]
+    L.dq_lz77_decode_hip_many_i32.restype = i32
+    L.dq_lz77_decode_hip_many_i32.argtypes = [vp, vp, i32, vp, vp, vp, vp, i32]
+    L.dq_lz77_decode_hip_many_dev_i32.restype = i32
+    L.dq_lz77_decode_hip_many_dev_i32.argtypes = [vp, vp, i32, vp, vp, vp, vp, i32, vp]
+    L.dq_rlz_decode_hip_many_i32.restype = i32
+    L.dq_rlz_decode_hip_many_i32.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp, i32]
+    L.dq_rlz_decode_hip_many_dev_i32.restype = i32
+    L.dq_rlz_decode_hip_many_dev_i32.argtypes = [vp, i64, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp]
+    L.dq_lzdecode_last_info.restype = i32
+    L.dq_lzdecode_last_info.argtypes = [ctypes.POINTER(i64), i32]
     L.dq_sufsort_hip_batch_i32.restype = i32
     L.dq_sufsort_hip_batch_i32.argtypes = [i32, vp, vp, vp, i32, vp]
     L.dq_sufsort_hip_many_i32.restype = i32
@@ -470,6 +495,15 @@ def last_rlz_info() -> dict:
     v = (ctypes.c_int64 * len(RLZ_RECORD))()
     check(load().dq_rlz_last_info(v, len(RLZ_RECORD)))
     return {key: v[i] * scale for i, (key, scale) in enumerate(RLZ_RECORD)}
+
+
+def last_lzdecode_info() -> dict:
+    """Shape of the last dq_lz77_decode_hip_* / dq_rlz_decode_hip_* on this thread (dq_lzdecode_last_info): texts with
+    status 0, texts with status -1 or -2, positions whose byte was not known after the tile pass and global rounds that
+    still found work (both 0 in relative calls), kernel launches, stream waits."""
+    v = (ctypes.c_int64 * len(LZDECODE_RECORD))()
+    check(load().dq_lzdecode_last_info(v, len(LZDECODE_RECORD)))
+    return {key: v[i] * scale for i, (key, scale) in enumerate(LZDECODE_RECORD)}
 
 
 def last_batch_info() -> dict:

@@ -230,6 +230,20 @@ int last_info(const Record &record, int64_t *info, int32_t count, const char *wh
     return DQ_OK;
 }
 
+// an entry point of dq_lz77_decode_hip_* / dq_rlz_decode_hip_*: the decoders hold the verdicts, the sizes and the host
+// forms' staging on the host, and nothing may propagate through the C ABI
+template <typename Call>
+int32_t lzdecode_entry(Call call)
+{
+    EnvScope scope;
+    t_lzdecode_info = {};
+    try {
+        return call();
+    } catch (const std::bad_alloc &) {
+        return fail(DQ_ERR_OOM, "lz decode: host allocation failed");
+    }
+}
+
 }  // namespace
 }  // namespace dq
 
@@ -553,6 +567,68 @@ int32_t dq_lzparse_hip_many_dev_i32(const void *d_texts, const void *d_offsets, 
 }
 
 int32_t dq_rlz_last_info(int64_t *info, int32_t count) { return last_info(t_rlz_info, info, count, "null info array"); }
+
+int32_t dq_lz77_decode_hip_i32(const int32_t *phrases, int64_t z, uint8_t *out, int64_t cap, int64_t *out_len, int32_t *status,
+                               int32_t device)
+{
+    return lzdecode_entry([&] { return lzdecode_one(false, true, nullptr, 0, phrases, z, out, cap, out_len, status, device, nullptr); });
+}
+
+int32_t dq_lz77_decode_hip_dev_i32(const void *d_phrases, int64_t z, void *d_out, int64_t cap, int64_t *out_len, int32_t *status,
+                                   int32_t device, void *stream)
+{
+    return lzdecode_entry([&] { return lzdecode_one(false, false, nullptr, 0, d_phrases, z, d_out, cap, out_len, status, device, stream); });
+}
+
+int32_t dq_rlz_decode_hip_i32(const uint8_t *old_data, int64_t n, const int32_t *phrases, int64_t z, uint8_t *out, int64_t cap,
+                              int64_t *out_len, int32_t *status, int32_t device)
+{
+    return lzdecode_entry([&] { return lzdecode_one(true, true, old_data, n, phrases, z, out, cap, out_len, status, device, nullptr); });
+}
+
+int32_t dq_rlz_decode_hip_dev_i32(const void *d_old, int64_t n, const void *d_phrases, int64_t z, void *d_out, int64_t cap,
+                                  int64_t *out_len, int32_t *status, int32_t device, void *stream)
+{
+    return lzdecode_entry([&] { return lzdecode_one(true, false, d_old, n, d_phrases, z, d_out, cap, out_len, status, device, stream); });
+}
+
+int32_t dq_lz77_decode_hip_many_i32(const int32_t *phrases, const int64_t *phrase_offsets, int32_t count, uint8_t *out,
+                                    const int64_t *out_offsets, int64_t *out_len, int32_t *status, int32_t device)
+{
+    return lzdecode_entry([&] {
+        return lzdecode_many(false, true, nullptr, 0, nullptr, phrases, phrase_offsets, count, out, out_offsets, out_len, status, device, nullptr);
+    });
+}
+
+int32_t dq_lz77_decode_hip_many_dev_i32(const void *d_phrases, const int64_t *phrase_offsets, int32_t count, void *d_out,
+                                        const int64_t *out_offsets, int64_t *out_len, int32_t *status, int32_t device, void *stream)
+{
+    return lzdecode_entry([&] {
+        return lzdecode_many(false, false, nullptr, 0, nullptr, d_phrases, phrase_offsets, count, d_out, out_offsets, out_len, status, device,
+                             stream);
+    });
+}
+
+int32_t dq_rlz_decode_hip_many_i32(const uint8_t *olds, const int64_t *old_spans, const int32_t *phrases, const int64_t *phrase_offsets,
+                                   int32_t count, uint8_t *out, const int64_t *out_offsets, int64_t *out_len, int32_t *status,
+                                   int32_t device)
+{
+    return lzdecode_entry([&] {
+        return lzdecode_many(true, true, olds, 0, old_spans, phrases, phrase_offsets, count, out, out_offsets, out_len, status, device, nullptr);
+    });
+}
+
+int32_t dq_rlz_decode_hip_many_dev_i32(const void *d_olds, int64_t olds_bytes, const int64_t *old_spans, const void *d_phrases,
+                                       const int64_t *phrase_offsets, int32_t count, void *d_out, const int64_t *out_offsets,
+                                       int64_t *out_len, int32_t *status, int32_t device, void *stream)
+{
+    return lzdecode_entry([&] {
+        return lzdecode_many(true, false, d_olds, olds_bytes, old_spans, d_phrases, phrase_offsets, count, d_out, out_offsets, out_len, status,
+                             device, stream);
+    });
+}
+
+int32_t dq_lzdecode_last_info(int64_t *info, int32_t count) { return last_info(t_lzdecode_info, info, count, "null info array"); }
 
 int32_t dq_sufsort_hip_batch_i32(int32_t count, const uint8_t *const *texts, const int64_t *lens,
                                  int32_t *const *sas, int32_t ndev, const int32_t *devs)

@@ -41,6 +41,7 @@
 #include "dq_lcp_info.h"
 #include "dq_lz77_info.h"
 #include "dq_rlz_info.h"
+#include "dq_lzdecode_info.h"
 #include "dq_flags.h"
 #include "dq_work_lists.h"
 #include "dq_block_groups.h"
@@ -746,6 +747,16 @@ int lzparse_many_host(const uint8_t *texts, const int64_t *offsets, int32_t coun
                       int32_t *phrases, int64_t cap, int64_t *phrase_offsets, int32_t device);
 int lzparse_many_dev(const void *d_texts, const void *d_offsets, int32_t count, const void *d_len, const void *d_src, void *d_phrases,
                      int64_t cap, int64_t *phrase_offsets, int32_t device, void *stream);
+
+// The triples of dq_lz77_hip_* / dq_rlz_hip_* back into bytes (dq_lzdecode_host.h, in dq_sufcheck.hip): the bodies of
+// dq_lz77_decode_hip_* and dq_rlz_decode_hip_*, one text or many.  rlz: the relative decoder (old / olds are read);
+// host: the buffers are the host's (then olds is as large as the largest span end, and stream is not looked at).  All of
+// them fill t_lzdecode_info (dq_lzdecode_info.h); the entry point resets it.
+int lzdecode_one(bool rlz, bool host, const void *old, int64_t n, const void *phrases, int64_t z, void *out, int64_t cap, int64_t *out_len,
+                 int32_t *status, int32_t device, void *stream);
+int lzdecode_many(bool rlz, bool host, const void *olds, int64_t olds_bytes, const int64_t *old_spans, const void *phrases,
+                  const int64_t *phrase_offsets, int32_t count, void *out, const int64_t *out_offsets, int64_t *out_len, int32_t *status,
+                  int32_t device, void *stream);
 
 // match search + BSDIFF40 (dq_diff.hip)
 int match_search_dev_i32(const void *d_old, int64_t n, const void *d_sa, const void *d_new, int64_t m, const int64_t *d_scans,

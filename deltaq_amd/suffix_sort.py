@@ -21,6 +21,7 @@ from . import _abi
 
 LENGTH_MISMATCH_MESSAGE = "Text and suffix buffers should have the same length"  # LibDivSufSort.cs:31
 INT_MAX = 0x7FFFFFFF
+MIXED_LZ_MESSAGE = "text, suffixes, lcp and phrases must all be host buffers or all torch GPU tensors"   # (what Lz77 raises)
 
 # LDSSChecker.ResultCode (test/DeltaQ.SuffixSorting.LibDivSufSort.Tests/LDSSChecker.cs:11-18): what Check returns
 CHECK_DONE = _abi.DQ_SUFCHECK_DONE
@@ -1280,6 +1281,236 @@ class HipSuffixSort:
         return [phrases[poff[t]:poff[t + 1]] for t in range(count)]
 
     lzparse_many = LzParseMany
+
+    # -- the phrases back into bytes, on the device (no counterpart: lz77_decode / rlz_decode below are the host loops) ----
+    def Lz77Decode(self, phrases):
+        """The text of a factorization ``Lz77`` returned, decoded on the device: ``bytes`` from a host ``(z, 3)`` int32
+        array (``dq_lz77_decode_hip_i32``), a uint8 tensor from a torch GPU tensor, on the current torch stream
+        (``dq_lz77_decode_hip_dev_i32``).  Phrases are untrusted: a malformed list raises ``ValueError``, as
+        ``lz77_decode`` does.  ``_abi.last_lzdecode_info()`` tells what happened."""
+        return self._decode_one(None, phrases)
+
+    lz77_decode = Lz77Decode
+
+    def RlzDecode(self, old, phrases):
+        """The new file of a relative factorization ``Rlz(old, new)`` returned, decoded on the device
+        (``dq_rlz_decode_hip_i32`` / ``dq_rlz_decode_hip_dev_i32``): ``old`` and ``phrases`` both host buffers or both
+        torch GPU tensors.  A malformed list -- a copy from outside ``old`` included -- raises ``ValueError``."""
+        if old is None:
+            raise TypeError("RlzDecode needs the old file")
+        return self._decode_one(old, phrases)
+
+    rlz_decode = RlzDecode
+
+    def Lz77DecodeMany(self, phrases, phrase_offsets=None, sizes=None):
+        """``Lz77Decode`` of many texts in ONE native call.  ``phrases`` is what ``Lz77Many`` returns: a list of
+        ``(z_t, 3)`` int32 arrays (``phrase_offsets`` left out), or all triples back to back as one ``(Z, 3)`` array or
+        torch GPU tensor with the host int64 array ``phrase_offsets`` of count + 1 entries.  Host arrays give a list of
+        ``bytes`` (``dq_lz77_decode_hip_many_i32``); a GPU tensor stays on the device on the current torch stream
+        (``dq_lz77_decode_hip_many_dev_i32``) and gives ``(out_tensor, out_offsets)``: the texts back to back, text t at
+        ``[out_offsets[t], out_offsets[t + 1])``.  ``sizes``: the texts' decoded sizes where the caller knows them;
+        otherwise they are read off every text's last triple.  A malformed text raises ``ValueError`` naming it."""
+        return self._decode_many(None, None, phrases, phrase_offsets, sizes)
+
+    lz77_decode_many = Lz77DecodeMany
+
+    def RlzDecodeMany(self, olds_or_cats, spans, phrases, phrase_offsets=None, sizes=None):
+        """``RlzDecode`` of many pairs in ONE native call.  ``olds_or_cats`` is a list of old files (``spans`` None:
+        file t belongs to text t), or one buffer with ``spans``, a host ``(count, 2)`` int64 array of ``(begin, end)``
+        byte positions in it -- the old halves of ``RlzMany``'s cats where they stand, or one old file named by every
+        text.  ``phrases``, ``phrase_offsets``, ``sizes`` and the results as in ``Lz77DecodeMany``
+        (``dq_rlz_decode_hip_many_i32`` / ``dq_rlz_decode_hip_many_dev_i32``)."""
+        if olds_or_cats is None:
+            raise TypeError("RlzDecodeMany needs the old files")
+        return self._decode_many(olds_or_cats, spans, phrases, phrase_offsets, sizes)
+
+    rlz_decode_many = RlzDecodeMany
+
+    @staticmethod
+    def _decoded_size(last, what):
+        """start + max(1, len) of a text's last triple, refused where no well-formed text has it."""
+        size = int(last[0]) + max(1, int(last[1]))
+        if not 0 < size <= INT_MAX:
+            raise ValueError(f"{what}: malformed phrases (the last one ends at {size})")
+        return size
+
+    @staticmethod
+    def _host_phrases(phrases):
+        if not isinstance(phrases, np.ndarray) or phrases.dtype != np.int32 or phrases.ndim != 2 or phrases.shape[1] != 3:
+            raise TypeError("phrases must be a (z, 3) numpy int32 array")
+        return np.ascontiguousarray(phrases)
+
+    @staticmethod
+    def _device_phrases(phrases):
+        import torch
+
+        if (not _is_torch_tensor(phrases) or phrases.dtype != torch.int32 or phrases.dim() != 2 or phrases.shape[1] != 3
+                or not phrases.is_contiguous()):
+            raise TypeError("phrases must be a contiguous (z, 3) int32 tensor")
+        if not phrases.is_cuda:
+            raise TypeError("torch tensors must live on the GPU; pass host data as numpy")
+        return phrases
+
+    @staticmethod
+    def _device_bytes(old, like):
+        import torch
+
+        if old.dtype != torch.uint8 or old.dim() != 1 or not old.is_contiguous():
+            raise TypeError("a device old file must be a contiguous 1-D uint8 tensor")
+        if not old.is_cuda:
+            raise TypeError("torch tensors must live on the GPU; pass host data as bytes/numpy")
+        if old.device != like.device:
+            raise TypeError("old and phrases must be on the same device")
+        return old
+
+    def _decode_one(self, old, phrases):
+        out_len, status = ctypes.c_int64(0), ctypes.c_int32(0)
+        rlz = old is not None
+        if _is_torch_tensor(phrases) or _is_torch_tensor(old):
+            import torch
+
+            if not _is_torch_tensor(phrases) or (rlz and not _is_torch_tensor(old)):
+                raise TypeError(MIXED_LZ_MESSAGE)
+            P = self._device_phrases(phrases)
+            z = P.shape[0]
+            size = self._decoded_size(P[-1].tolist(), "text 0") if z else 0
+            out = torch.empty(size, dtype=torch.uint8, device=P.device)
+            dev, stream = _device_and_stream(P)
+            tail = (P.data_ptr() if z else None, z, out.data_ptr() if size else None, size, ctypes.byref(out_len),
+                    ctypes.byref(status), dev, stream)
+            if rlz:
+                O = self._device_bytes(old, P)
+                _abi.check(self._lib.dq_rlz_decode_hip_dev_i32(O.data_ptr() if O.numel() else None, O.numel(), *tail))
+            else:
+                _abi.check(self._lib.dq_lz77_decode_hip_dev_i32(*tail))
+            if status.value != 0:
+                raise ValueError("text 0: malformed phrases" if status.value == -1 else "text 0: the phrases decode to more than their last one says")
+            return out[:out_len.value]
+        P = self._host_phrases(phrases)
+        z = P.shape[0]
+        size = self._decoded_size(P[-1], "text 0") if z else 0
+        out = np.empty(max(size, 1), dtype=np.uint8)
+        tail = (P.ctypes.data if z else None, z, out.ctypes.data, size, ctypes.byref(out_len), ctypes.byref(status), self.device)
+        if rlz:
+            O = _as_text(old)
+            if O.ndim != 1:
+                raise TypeError("the old file must be one-dimensional")
+            _abi.check(self._lib.dq_rlz_decode_hip_i32(O.ctypes.data if O.size else None, O.size, *tail))
+        else:
+            _abi.check(self._lib.dq_lz77_decode_hip_i32(*tail))
+        if status.value != 0:
+            raise ValueError("text 0: malformed phrases" if status.value == -1 else "text 0: the phrases decode to more than their last one says")
+        return out[:out_len.value].tobytes()
+
+    def _decode_many(self, olds, spans, phrases, phrase_offsets, sizes):
+        rlz = olds is not None
+        device = _is_torch_tensor(phrases)
+        if isinstance(phrases, (list, tuple)):
+            if phrase_offsets is not None:
+                raise TypeError("a list of phrase arrays brings its own offsets: leave phrase_offsets out")
+            if any(_is_torch_tensor(p) for p in phrases):
+                raise TypeError(MIXED_LZ_MESSAGE)
+            parts = [self._host_phrases(p) for p in phrases]
+            poff = np.zeros(len(parts) + 1, dtype=np.int64)
+            if parts:
+                np.cumsum([p.shape[0] for p in parts], out=poff[1:])
+            P = np.concatenate(parts) if poff[-1] else np.zeros((0, 3), np.int32)
+        else:
+            if phrase_offsets is None or _is_torch_tensor(phrase_offsets):
+                raise TypeError("phrase_offsets must be a host int64 array of count + 1 entries")
+            poff = np.ascontiguousarray(phrase_offsets, dtype=np.int64)
+            if poff.ndim != 1 or poff.size < 1:
+                raise TypeError("phrase_offsets must be a host int64 array of count + 1 entries")
+            P = self._device_phrases(phrases) if device else self._host_phrases(phrases)
+            if poff[0] != 0 or (np.diff(poff) < 0).any() or poff[-1] != P.shape[0]:
+                raise ValueError("phrase_offsets must start at 0, never decrease and end at the number of triples")
+        count = poff.size - 1
+        # the old files: one buffer and a (begin, end) pair per text
+        O = S = None
+        if rlz:
+            if spans is None:
+                if _is_torch_tensor(olds) or any(_is_torch_tensor(o) for o in olds):
+                    raise TypeError("device old files come as one tensor with spans")
+                files = [_as_text(o) for o in olds]
+                if len(files) != count or any(f.ndim != 1 for f in files):
+                    raise ValueError("one one-dimensional old file per text")
+                if device:
+                    raise TypeError(MIXED_LZ_MESSAGE)
+                ends = np.cumsum([f.size for f in files], dtype=np.int64) if files else np.zeros(0, np.int64)
+                S = np.stack([ends - [f.size for f in files], ends], axis=1).astype(np.int64) if files else np.zeros((0, 2), np.int64)
+                O = np.concatenate(files) if files and ends[-1] else np.zeros(0, np.uint8)
+            else:
+                if _is_torch_tensor(spans):
+                    raise TypeError("spans must be a host (count, 2) int64 array")
+                S = np.ascontiguousarray(spans, dtype=np.int64)
+                if S.shape != (count, 2):
+                    raise ValueError("spans must hold one (begin, end) pair per text")
+                if _is_torch_tensor(olds) != device:
+                    raise TypeError(MIXED_LZ_MESSAGE)
+                O = self._device_bytes(olds, P) if device else _as_text(olds)
+                if not device and O.ndim != 1:
+                    raise TypeError("the old files must be one one-dimensional buffer")
+                total = O.numel() if device else O.size
+                if count and ((S[:, 0] < 0) | (S[:, 0] > S[:, 1]) | (S[:, 1] > total)).any():
+                    raise ValueError("a span lies outside the old files")
+        elif _is_torch_tensor(spans):
+            raise TypeError(MIXED_LZ_MESSAGE)
+        # the slots: the decoded sizes, from the caller or off every text's last triple
+        if sizes is None:
+            lens = np.zeros(count, dtype=np.int64)
+            full = np.flatnonzero(np.diff(poff) > 0)
+            if full.size:
+                at = poff[full + 1] - 1
+                if device:
+                    import torch
+
+                    lasts = P[torch.from_numpy(at).to(P.device)].cpu().numpy()
+                else:
+                    lasts = P[at]
+                for t, last in zip(full.tolist(), lasts):
+                    lens[t] = self._decoded_size(last, f"text {t}")
+        else:
+            lens = np.ascontiguousarray(sizes, dtype=np.int64)
+            if lens.shape != (count,) or (lens < 0).any():
+                raise ValueError("sizes must hold one size per text")
+        ooff = np.zeros(count + 1, dtype=np.int64)
+        np.cumsum(lens, out=ooff[1:])
+        total = int(ooff[-1])
+        if total > INT_MAX:
+            raise ValueError("the decoders have 32-bit positions: the texts together must be shorter than 2^31 bytes")
+        out_len, status = np.zeros(max(count, 1), dtype=np.int64), np.zeros(max(count, 1), dtype=np.int32)
+        z = P.shape[0]
+        if device:
+            import torch
+
+            out = torch.empty(total, dtype=torch.uint8, device=P.device)
+            dev, stream = _device_and_stream(P)
+            tail = (P.data_ptr() if z else None, poff.ctypes.data, count, out.data_ptr() if total else None, ooff.ctypes.data,
+                    out_len.ctypes.data, status.ctypes.data, dev, stream)
+            if rlz:
+                _abi.check(self._lib.dq_rlz_decode_hip_many_dev_i32(O.data_ptr() if O.numel() else None, O.numel(),
+                                                                    S.ctypes.data if count else None, *tail))
+            else:
+                _abi.check(self._lib.dq_lz77_decode_hip_many_dev_i32(*tail))
+        else:
+            out = np.empty(max(total, 1), dtype=np.uint8)
+            tail = (P.ctypes.data if z else None, poff.ctypes.data, count, out.ctypes.data, ooff.ctypes.data, out_len.ctypes.data,
+                    status.ctypes.data, self.device)
+            if rlz:
+                _abi.check(self._lib.dq_rlz_decode_hip_many_i32(O.ctypes.data if O.size else None, S.ctypes.data if count else None, *tail))
+            else:
+                _abi.check(self._lib.dq_lz77_decode_hip_many_i32(*tail))
+        bad = np.flatnonzero(status[:count])
+        if bad.size:
+            t = int(bad[0])
+            raise ValueError(f"text {t}: malformed phrases" if status[t] == -1 else
+                             f"text {t}: the phrases decode to {int(out_len[t])} bytes, more than its slot of {int(lens[t])}")
+        if sizes is not None and not np.array_equal(out_len[:count], lens):
+            t = int(np.flatnonzero(out_len[:count] != lens)[0])
+            raise ValueError(f"text {t}: the phrases decode to {int(out_len[t])} bytes, not {int(lens[t])}")
+        if device:
+            return out, ooff
+        return [out[ooff[t]:ooff[t + 1]].tobytes() for t in range(count)]
 
     def _is_many_device(self, olds, news, suffixes, lcps):
         """Whether a many-pairs call is the device form; mixing the two raises."""

@@ -955,6 +955,81 @@ int32_t dq_lzparse_hip_many_dev_i32(const void *d_texts, const void *d_offsets, 
                                     const void *d_src, void *d_phrases, int64_t cap, int64_t *phrase_offsets, int32_t device,
                                     void *stream);
 
+/* ---- the phrases back into bytes, on the device: one text, many texts, many (old, new) pairs per call ------------------
+ * The triples are exactly what dq_lz77_hip_* / dq_rlz_hip_* and their many forms write: (start, len, third) int32.  A
+ * literal has len == 0 and third is the byte; a copy has len > 0 and its source third is a position in the text's own
+ * output (dq_lz77_decode_*; it may overlap what it writes: third + len > start is normal) or in old (dq_rlz_decode_*).
+ * One text: z triples, a slot out[0 .. cap).  Many: text t's triples are [phrase_offsets[t], phrase_offsets[t + 1]) --
+ * the array dq_lz77_hip_many_* / dq_rlz_hip_many_* return --, its slot is out[out_offsets[t] .. out_offsets[t + 1]), and
+ * for the relative decoder its old file is olds[old_spans[2 t] .. old_spans[2 t + 1]): `count` pairs (begin, end) of
+ * byte positions in olds, so the old halves of dq_rlz_hip_many_*'s cats (begin = offsets[t] + m_t, end = offsets[t + 1])
+ * serve where they stand, and many new files may name one and the same old file.  phrase_offsets, out_offsets,
+ * old_spans, out_len and status are HOST pointers in every form: the library uploads what the kernels read, and nothing
+ * is fetched from the device before the work starts.  All positions are 32-bit: out_offsets[count] (cap), and
+ * phrase_offsets[count] (z), above 2^31-1 give DQ_ERR_TOO_LARGE, judged from the arguments alone.
+ * Verdicts.  Phrases are untrusted input.  A malformed text is its own verdict, never a failed call and never an address:
+ * status[t] is 0 (ok), -1 (malformed) or -2 (well-formed, but the decoded size exceeds the slot).  The decoded size is
+ * start + max(1, len) of the text's last triple, 0 for a text without triples; it always lands in out_len[t] -- also with
+ * status -2, so a caller can size and call again; after status -1 out_len[t] is 0.  A text is well-formed iff for every
+ * triple: the first one starts at 0; start[k + 1] == start[k] + max(1, len[k]) (in 64 bits); len >= 0; a literal's third
+ * lies in [0, 255]; an LZ77 copy has 0 <= third < start; an RLZ copy has 0 <= third and third + len <= end - begin; and
+ * the decoded size is at most 2^31-1.  The one-text forms return their verdict the same way, through *status and
+ * *out_len, and the call returns DQ_OK.
+ * What is written: a slot with status 0 holds the text in its first out_len[t] bytes; the rest of that slot, every byte
+ * between slots and every byte outside out stay untouched.  A slot with status -1 or -2 has unspecified contents inside
+ * the slot and nowhere else.
+ *   negative count, z, cap (n, olds_bytes); a NULL buffer that is needed (out_len, status and the host arrays always;
+ *   phrases where there is a triple; out where there is a triple and a slot byte; old where a span is not empty);
+ *   phrase_offsets[0] != 0 or out_offsets[0] != 0; decreasing offsets; an old_spans pair with begin < 0, begin > end
+ *   or end > the size of olds                                       DQ_ERR_BAD_ARGS
+ *   more than 2^31-1 slot bytes or triples                          DQ_ERR_TOO_LARGE
+ * -- all decided before a device is looked for, and out_len and status stay untouched.  The size of olds is n in the
+ * one-text forms, olds_bytes in the many device form and the largest end in the many host form.  count == 0, and a call
+ * whose texts all have no triples, return DQ_OK without a device, out_len and status all zero.
+ * Computed over the flat triples and the flat slot positions (deltaq_amd/csrc/dq_lzdecode.h): one thread per triple
+ * applies the rules to it and its successor into one verdict word per text; then per tile of 8192 slot positions every
+ * position of a text that is well-formed and fits finds its phrase by bisection.  The relative decoder gathers from old
+ * and is done.  The LZ77 decoder turns a position into a byte or into the position it copies from -- an overlapping
+ * copy folded by its period d = start - third, third + (i - start) mod d, so a run of any length is one hop --, chases the
+ * links inside the tile in LDS, and resolves the rest, which all point left of their tile, by pointer doubling in
+ * ceil(log2(tiles)) rounds over 4-byte words, updated in place; a last pass writes the bytes, 16 per lane.  The launches
+ * are a function of the total slot bytes S and the total triples Z alone (lzdecode_launches in
+ * deltaq_amd/csrc/dq_lzdecode_host.h): 2 for a relative call, 3 + ceil(log2(ceil(S / 8192))) for an LZ77 call, the check
+ * alone where S == 0; a call of 1000 texts makes as many as a call of one text of the same totals.
+ * Device memory, carved from the cached workspace of the slot the call leases: 4 bytes per slot byte for an LZ77 call,
+ * 8 bytes per text (verdict, size), 16 more per text for the offsets of a many call (32 with old_spans) and a line of
+ * counters; the host forms add their copies of the triples, of olds and of out.  No chunking and no CPU fallback:
+ * DQ_ERR_OOM where that does not fit.  The _dev_ forms take device pointers on `device`, enqueue on `stream` (NULL = the
+ * library's stream) and return after it has drained.  One stream wait per call.
+ * Out of scope: int64 forms, and a byte-level coder on the phrases.
+ * dq_lzdecode_last_info: shape of the last of these calls on this thread, reset when one starts; `count` entries (6 are
+ * defined, further ones read 0; a NULL array is DQ_ERR_BAD_ARGS): [0] texts with status 0; [1] texts with status -1 or
+ * -2; [2] positions whose byte was not known after the tile pass; [3] global rounds that still found work (both 0 in
+ * relative calls); [4] kernel launches; [5] stream waits. */
+int32_t dq_lz77_decode_hip_i32(const int32_t *phrases, int64_t z, uint8_t *out, int64_t cap,
+                               int64_t *out_len, int32_t *status, int32_t device);
+int32_t dq_lz77_decode_hip_dev_i32(const void *d_phrases, int64_t z, void *d_out, int64_t cap,
+                                   int64_t *out_len, int32_t *status, int32_t device, void *stream);
+int32_t dq_rlz_decode_hip_i32(const uint8_t *old_data, int64_t n, const int32_t *phrases, int64_t z,
+                              uint8_t *out, int64_t cap, int64_t *out_len, int32_t *status, int32_t device);
+int32_t dq_rlz_decode_hip_dev_i32(const void *d_old, int64_t n, const void *d_phrases, int64_t z,
+                                  void *d_out, int64_t cap, int64_t *out_len, int32_t *status,
+                                  int32_t device, void *stream);
+int32_t dq_lz77_decode_hip_many_i32(const int32_t *phrases, const int64_t *phrase_offsets, int32_t count,
+                                    uint8_t *out, const int64_t *out_offsets,
+                                    int64_t *out_len, int32_t *status, int32_t device);
+int32_t dq_lz77_decode_hip_many_dev_i32(const void *d_phrases, const int64_t *phrase_offsets, int32_t count,
+                                        void *d_out, const int64_t *out_offsets,
+                                        int64_t *out_len, int32_t *status, int32_t device, void *stream);
+int32_t dq_rlz_decode_hip_many_i32(const uint8_t *olds, const int64_t *old_spans, const int32_t *phrases,
+                                   const int64_t *phrase_offsets, int32_t count, uint8_t *out,
+                                   const int64_t *out_offsets, int64_t *out_len, int32_t *status, int32_t device);
+int32_t dq_rlz_decode_hip_many_dev_i32(const void *d_olds, int64_t olds_bytes, const int64_t *old_spans,
+                                       const void *d_phrases, const int64_t *phrase_offsets, int32_t count,
+                                       void *d_out, const int64_t *out_offsets, int64_t *out_len, int32_t *status,
+                                       int32_t device, void *stream);
+int32_t dq_lzdecode_last_info(int64_t *info, int32_t count);
+
 /* Device workspace (bytes) a sort of n bytes with index_bytes (4 or 8) wide indices needs,
  * excluding the caller's text and sa buffers: the device entry point's full layout (the reduced one at n = 2^32). */
 int64_t dq_sufsort_hip_workspace_bytes(int64_t n, int32_t index_bytes);

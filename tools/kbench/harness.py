@@ -78,6 +78,11 @@ PROTOTYPES = {                                               # export -> (restyp
     "dq_mstat_hip_many_dev_i32": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp]),
     "dq_rlz_hip_many_dev_i32": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _i32, _vp]),
     "dq_lzparse_hip_many_dev_i32": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _i32, _vp]),
+    "dq_lz77_decode_hip_dev_i32": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _i32, _vp]),
+    "dq_rlz_decode_hip_dev_i32": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _vp]),
+    "dq_lz77_decode_hip_many_dev_i32": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "dq_rlz_decode_hip_many_dev_i32": (_i32, [_vp, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "dq_lzdecode_last_info": _INFO,
 }
 
 
