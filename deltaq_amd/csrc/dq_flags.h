@@ -70,6 +70,7 @@ struct Flags {
     std::optional<int> slot_finish;         // DQ_SLOT_FINISH: 0 | 1, finish kernel of the slots route: bucket_sort_kernel's slot mode | slot_finish_kernel (dq_slot_finish.h; unset: 1)
     std::optional<int> tie_settle;          // DQ_TIE_SETTLE: 0 | 1, ties of the bucketed round 0: listed, then finished | settled from their bits in one kernel (unset: with the slots; 1: on every bucketed route)
     std::optional<int> status_zero;         // DQ_STATUS_ZERO: 0 | 1, look-back state of the first digit passes: zeroed before the key width is known | once the route is known, and only what it reads (unset: early_status_passes, dq_round0_plan.h)
+    std::optional<int> text_in_place;       // DQ_TEXT_IN_PLACE: 0 | 1, a 16-byte aligned device-resident text: always copied | read where the caller holds it until a kernel needs the padded copy, at any n (dq_text_view.h; unset: from slots_cut_min_n() on)
     std::optional<int> hist_loads;          // DQ_HIST_LOADS: 1 | 4, 16-byte loads a thread of text_hist_kernel keeps in flight (unset: 4)
     bool old_first_pass = false;            // DQ_OLD_FIRST_PASS: radix_rank_kernel instead of the XCD-local first pass
     bool no_fused_ties = false;             // DQ_NO_FUSED_TIES: the tie structure by a rebucket pass
@@ -188,6 +189,7 @@ inline Flags read_flags()
     f.slot_finish = num("DQ_SLOT_FINISH", 0, 1);
     f.tie_settle = num("DQ_TIE_SETTLE", 0, 1);
     f.status_zero = num("DQ_STATUS_ZERO", 0, 1);
+    f.text_in_place = num("DQ_TEXT_IN_PLACE", 0, 1);
     f.hist_loads = num("DQ_HIST_LOADS", 1, 4);
     f.old_first_pass = on("DQ_OLD_FIRST_PASS");
     f.no_fused_ties = on("DQ_NO_FUSED_TIES");

@@ -20,6 +20,7 @@
 #include "dq_coded_keys.h"
 #include "dq_radix.h"
 #include "dq_round0_plan.h"
+#include "dq_text_view.h"
 
 namespace dq {
 
@@ -718,14 +719,18 @@ __device__ __forceinline__ void sample_kgrams(const uint8_t *__restrict__ text, 
 // dq_round0_plan.h -- before it counts and stores any of them; one load per thread leaves 16 KiB in flight per CU.  A wave
 // takes a block of kLoads trips only while its last lane's last trip is in range, so on every trip the lanes of a wave
 // that are active are those of the one-load loop: the long-run ballot sees the same lanes either way.
+// tail_out (round 42): the text stays in the caller's buffer (copy_out is null); only its tail block (dq_text_view.h) is
+// written, for the kernels that read the text through a TextView.
 template <int kLoads>
 static __global__ __launch_bounds__(kBlock) void text_hist_kernel(const uint8_t *__restrict__ text, int64_t n,
                                                            unsigned long long *__restrict__ bytehist /*[256], zeroed*/,
                                                            unsigned long long *__restrict__ kgram_coll = nullptr,
                                                            uint8_t *__restrict__ copy_out = nullptr /* 16-byte aligned, or none */,
-                                                           unsigned long long *__restrict__ xcd_hist = nullptr /*[8][256], zeroed*/)
+                                                           unsigned long long *__restrict__ xcd_hist = nullptr /*[8][256], zeroed*/,
+                                                           uint8_t *__restrict__ tail_out = nullptr /* kTextTailBytes, n >= kTextViewMinN */)
 {
     static_assert(kBlock == kHistGroupThreads, "hist_chunk() counts in workgroups of kBlock threads");
+    static_assert(kTextTailBytes <= kBlock, "one thread per byte of the tail block");
     // 4 interleaved sub-histograms (hist[d][lane & 3]) spread equal bytes over 4 banks
     __shared__ uint32_t hist[kRadixSize * 4];
     if (kgram_coll && blockIdx.x == 0) {
@@ -791,6 +796,7 @@ static __global__ __launch_bounds__(kBlock) void text_hist_kernel(const uint8_t 
                 atomicAdd(&xcd_hist[b], ~0ull);
             }
         }
+        if (tail_out && tid < kTextTailBytes) tail_out[tid] = text_tail_byte(text, n, tid);
     }
     __syncthreads();
     const uint32_t c = hist[tid * 4] + hist[tid * 4 + 1] + hist[tid * 4 + 2] + hist[tid * 4 + 3];
@@ -803,12 +809,30 @@ static __global__ __launch_bounds__(kBlock) void text_hist_kernel(const uint8_t 
     if (kgram_coll && flat_chunks && lane_id() == 0) atomicAdd(&kgram_coll[9], flat_chunks);
 }
 
+// The padded copy of a text that text_hist_kernel left in the caller's buffer, made late (Round0::need_text): 16-byte
+// chunks grid-stride, the last n % 16 bytes by the first workgroup.  src and dst are 16-byte aligned; the zero pad behind
+// dst[n - 1] is the caller's.
+static __global__ __launch_bounds__(kBlock) void text_copy_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, int64_t n)
+{
+    const uint4 *s16 = reinterpret_cast<const uint4 *>(src);
+    uint4 *d16 = reinterpret_cast<uint4 *>(dst);
+    const int64_t chunks = n >> 4;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < chunks; i += (int64_t)gridDim.x * kBlock) d16[i] = s16[i];
+    if (blockIdx.x == 0)
+        for (int64_t i = (chunks << 4) + threadIdx.x; i < n; i += kBlock) dst[i] = src[i];
+}
+
 // digit_offset[p][d] for p < kb (one workgroup per digit place p)
 // sub_offset (bucketed round 0, dq_xcd_rank.h): the region of digit d of place 0 cut into 8 sub-regions, one per
 // eighth of the text: sub_offset[e][d] = digit_offset[0][d] + the suffixes of eighths < e whose digit 0 is d.
 // (xcd_hist counts the bytes at the POSITIONS of an eighth; its suffixes' digits sit kb - 1 positions further on.)
 // (the body of workgroup p: text_digit_offsets_kernel, and slot_setup_kernel of dq_slot_rank.h, which runs it beside the slot bases)
-__device__ __forceinline__ void text_digit_offsets_body(int p, const int64_t *__restrict__ bytehist, const uint8_t *__restrict__ text,
+// Text: a pointer to the padded text, or a TextView (dq_text_view.h); byte j < n only.
+__device__ __forceinline__ uint8_t text_byte(const uint8_t *text, int64_t j) { return text[j]; }
+__device__ __forceinline__ uint8_t text_byte(const TextView &text, int64_t j) { return *text.at(j); }
+
+template <typename Text>
+__device__ __forceinline__ void text_digit_offsets_body(int p, const int64_t *__restrict__ bytehist, const Text &text,
                                                         int64_t n, int kb, int64_t *__restrict__ digit_offset,
                                                         const int64_t *__restrict__ xcd_hist, int64_t *__restrict__ sub_offset)
 {
@@ -817,7 +841,7 @@ __device__ __forceinline__ void text_digit_offsets_body(int p, const int64_t *__
     const int64_t off = kb - 1 - p;                       // digit p of suffix i is T[i + off]
     const int64_t lead = off < n ? off : n;               // text positions < off are never a digit p
     int64_t c = bytehist[d];
-    for (int64_t j = 0; j < lead; ++j) c -= (text[j] == d);
+    for (int64_t j = 0; j < lead; ++j) c -= (text_byte(text, j) == d);
     if (d == 0) c += lead;                                // ... and `lead` suffixes read the zero pad
     int64_t total;
     const int64_t excl = block_excl_sum(c, tmp, &total);
@@ -832,8 +856,8 @@ __device__ __forceinline__ void text_digit_offsets_body(int p, const int64_t *__
             const int64_t s1 = std::min(s0 + E, n);
             // suffixes [s0, s1) have their digit at positions [s0 + off, s1 + off) (zero past the end)
             int64_t ce = xcd_hist[e * kRadixSize + d];
-            for (int64_t j = s0; j < std::min(s0 + off, s1); ++j) ce -= (text[j] == d);
-            for (int64_t j = std::max(s0 + off, s1); j < s1 + off; ++j) ce += j < n ? (text[j] == d) : (d == 0);
+            for (int64_t j = s0; j < std::min(s0 + off, s1); ++j) ce -= (text_byte(text, j) == d);
+            for (int64_t j = std::max(s0 + off, s1); j < s1 + off; ++j) ce += j < n ? (text_byte(text, j) == d) : (d == 0);
             run += ce;
         }
     }

@@ -70,9 +70,13 @@ struct Round0 {
     int64_t n;
     IdxT *d_sa;
     Launcher &L;
-    const uint8_t *text_src;            // the caller's device-resident text when w.text is still to be filled from it
+    const uint8_t *text_src;            // the caller's device-resident text (16-byte aligned) when w.text is still to be filled from it
     int period_hint;
     Round0Out<IdxT> &o;
+    // w.text does not hold this call's text: it is read in the caller's buffer through view() and w.text holds its tail
+    // block only (dq_text_view.h).  SuffixSorter's member: need_text() there and here makes the copy before anything else
+    // reads w.text.  Whatever an earlier sort left in w.text is never read: the flag is set per call, by prepare().
+    bool &text_missing;
 
     static constexpr int64_t wb = (int64_t)sizeof(IdxT);
     TextStats s;                        // what text_hist_kernel saw: from prepare() on
@@ -84,6 +88,23 @@ struct Round0 {
     IdxT *V[2] = {nullptr, nullptr};
 
     const uint64_t *text64() const { return reinterpret_cast<const uint64_t *>(w.text); }
+    // what slot_setup_kernel, xcd_text_rank_kernel and tie_settle_kernel read the text through
+    TextView view() const { return text_missing ? text_in_place(text_src, w.text, n) : text_copied(w.text, n); }
+    // the slots route behind the XCD-local first pass with the ties settled from their bits: every reader takes a view
+    bool settles(const Flags &F) const { return F.tie_settle.value_or(route.slots ? 1 : 0) != 0; }
+    bool view_route(const Flags &F) const { return route.slots && route.b.xcd_pass && settles(F); }
+
+    // the padded copy, if this call has not made it yet (the zero pad behind it is there since the entry point)
+    int need_text(const char *why)
+    {
+        if (!text_missing) return DQ_OK;
+        text_missing = false;
+        if (flags().trace) fprintf(stderr, "[dq] text: copied late, %s (n=%lld)\n", why, (long long)n);
+        LAUNCH(L, DQ_K_TEXT_HIST, n, 2 * n,
+               hipLaunchKernelGGL(text_copy_kernel, dim3((unsigned)std::min<int64_t>(((n >> 4) + kBlock - 1) / kBlock + 1, 4096)), dim3(kBlock), 0,
+                                  L.st, text_src, w.text, n));
+        return DQ_OK;
+    }
     int64_t tie_words() const { return (n + 63) / 64; }
 
     // the digit offsets the plain passes read (w.digit_offset): from the byte histogram of the text, or -- coded keys,
@@ -120,15 +141,20 @@ struct Round0 {
         unsigned long long *xcd_hist = n >= kRound0MinN ? reinterpret_cast<unsigned long long *>(w.bytehist + kXcdHistAt) : nullptr;
         if (xcd_hist) blocks = (blocks + kXcds - 1) / kXcds * kXcds;
         HIP_TRY(hipMemsetAsync(w.bytehist, 0, (size_t)(kXcdHistAt + (xcd_hist ? kXcds * kRadixSize : 0)) * 8, L.st));
+        text_missing = text_in_place_wanted(n, text_src != nullptr, kTextViewMinN, flags());
+        if (flags().trace)
+            fprintf(stderr, "[dq] text: %s (n=%lld)\n", text_missing ? "in place, the caller's buffer and a tail block" :
+                    text_src ? "copied by the histogram pass" : "copied in front of the sort", (long long)n);
         // (+1 workgroup: the k-gram sample, whose 8 counters sit right behind the byte histogram: one readback)
         LAUNCH(L, DQ_K_TEXT_HIST, n, n,
-               // (text_src: the caller's device buffer, not copied yet -- this pass reads it and fills w.text, see the kernel)
+               // (text_src: the caller's device buffer, not copied yet -- this pass reads it and fills w.text, see the kernel;
+               // text_missing: it writes the tail block only)
                // (DQ_HIST_LOADS=1: one 16-byte load in flight per thread, as before round 34)
                hipLaunchKernelGGL(flags().hist_loads.value_or(kHistLoads) < kHistLoads ? text_hist_kernel<1> : text_hist_kernel<kHistLoads>,
                                   dim3(blocks + 1), dim3(kBlock), 0, L.st,
                                   text_src ? text_src : (const uint8_t *)w.text, n, reinterpret_cast<unsigned long long *>(w.bytehist),
-                                  reinterpret_cast<unsigned long long *>(w.bytehist + 256), text_src ? w.text : (uint8_t *)nullptr,
-                                  xcd_hist));
+                                  reinterpret_cast<unsigned long long *>(w.bytehist + 256), text_src && !text_missing ? w.text : (uint8_t *)nullptr,
+                                  xcd_hist, text_missing ? w.text : (uint8_t *)nullptr));
         HIP_TRY(hipMemcpyAsync(c.pinned, w.bytehist, (256 + 10) * 8, hipMemcpyDeviceToHost, L.st));
         HIP_TRY(hipEventRecord(c.readback, L.st));
         // While the host waits for the histogram and picks the key width, the device zeroes what the passes need whatever
@@ -173,6 +199,7 @@ struct Round0 {
         // pass (whose 8 KB the launch above has zeroed), the first pass's where the plain first pass runs in front of the
         // slots, and on every other route what an early fill would have zeroed by now -- its bbytes <= 3 passes among them.
         route = plan_round0_route(s, F, k, coded, (int)wb, slot_span_words_of(w));
+        if (!view_route(F)) DQ_TRY(need_text("the route is not the slots route"));
         if (early > 0) DQ_TRY(prepare_status<IdxT>(L, w, n, k.kb, early));
         else DQ_TRY(prepare_status<IdxT>(L, w, n, route.slots ? (route.b.xcd_pass ? 0 : 1) : std::max(k.kb, kEarlyPasses)));
         if (hist_deferred) return DQ_OK;
@@ -231,7 +258,7 @@ struct Round0 {
             o.fin_cap = n;                                   // what the list may take: every member of every group fits
             LAUNCH(L, DQ_K_TIE_COLLECT, n, n / 8,
                    hipLaunchKernelGGL(tie_settle_kernel<IdxT>, dim3((unsigned)groups), dim3(kSettleThreads), 0, L.st,
-                                      reinterpret_cast<const uint64_t *>(ebits), tie_words(), n, d_sa, (const uint8_t *)w.text,
+                                      reinterpret_cast<const uint64_t *>(ebits), tie_words(), n, d_sa, view(),
                                       h_fin >= 0 ? h_fin : (int64_t)k.kb, act_rank, w.Va, o.fin_cap, tctr, listed));
             // [1] sticky flag, [3] list length, [6..7] counters
             DQ_TRY(read_totals<IdxT>(L, c, w, 64, "radix look-back timed out (device spin bound hit)"));
@@ -382,7 +409,7 @@ struct Round0 {
                 fprintf(stderr, "[dq] second pass into bucket slots: %d x %d slots of %lld words (n=%lld)\n", sp.first, sp.second,
                         (long long)b.X, (long long)n);
             hipLaunchKernelGGL(slot_setup_kernel, dim3(b.bbytes + kRadixSize + 1), dim3(kBlock), 0, st, (const int64_t *)w.bytehist,
-                               (const uint8_t *)w.text, n, b.bbytes, w.digit_offset, xcd_hist, sub_offset, b.X, slot_base);
+                               view(), n, b.bbytes, w.digit_offset, xcd_hist, sub_offset, b.X, slot_base);
         } else {
             hipLaunchKernelGGL(text_digit_offsets_kernel, dim3(b.bbytes), dim3(kBlock), 0, st, (const int64_t *)w.bytehist,
                                (const uint8_t *)w.text, n, b.bbytes, w.digit_offset, xcd_hist, sub_offset);
@@ -398,7 +425,7 @@ struct Round0 {
             if (sizeof(XcdRankCtl) > w.ctl_status_stride) return fail(DQ_ERR_HIP, "status buffer too small");
             LAUNCH(L, DQ_K_RADIX_RANK, n, n * (1 + 8),                 // persistent: one workgroup per CU
                    hipLaunchKernelGGL(xcd_text_rank_kernel, dim3((unsigned)std::min<int64_t>(c.ncu, (n + kXcdTileN - 1) / kXcdTileN)),
-                                      dim3(kXcdRankThreads), 0, st, reinterpret_cast<const uint32_t *>(w.text), K[first], n,
+                                      dim3(kXcdRankThreads), 0, st, view(), K[first], n,
                                       ib + lowbits, keybits, ib, (const int64_t *)w.xcd_offset,
                                       reinterpret_cast<XcdRankCtl *>(w.ctl_status)));
         } else {
@@ -408,10 +435,10 @@ struct Round0 {
         }
         if (slots) {
             // persistent; the profile category and the byte count stay the second digit pass's
-            const int groups = resident_groups(&c.slot_rank_groups, (const void *)slot_rank_kernel, kSlotRankThreads, c.dev);
+            const int groups = resident_groups(&c.slot_rank_groups, (const void *)slot_rank_kernel<false>, kSlotRankThreads, c.dev);
             LAUNCH(L, DQ_K_RADIX_RANK, n, n * 16,
-                   hipLaunchKernelGGL(slot_rank_kernel, dim3((unsigned)std::min<int64_t>(groups, (n + kSlotTileN - 1) / kSlotTileN)),
-                                      dim3(kSlotRankThreads), 0, st, (const uint64_t *)K[0], K[1], n, ib + lowbits + 8, ib + lowbits,
+                   hipLaunchKernelGGL(slot_rank_kernel<false>, dim3((unsigned)std::min<int64_t>(groups, (n + kSlotTileN - 1) / kSlotTileN)),
+                                      dim3(kSlotRankThreads), 0, st, (const uint64_t *)K[0], K[1], n, ib + lowbits + 8, ib + lowbits, ib,
                                       (const int64_t *)w.digit_offset, (const uint32_t *)slot_base, sctl, bflags));
         }
         for (int p = 1; p < b.bbytes && !slots; ++p) {       // pass p reads buffer p & 1 and writes the other
@@ -487,12 +514,14 @@ struct Round0 {
             // a bucket or a bin this path does not take (or a run of equal keys too long for the tie walk):
             // back to the plain digit passes, with the state they expect
             if (F.trace) fprintf(stderr, "[dq] bucketed round 0 gave up (n=%lld): plain digit passes\n", (long long)n);
+            DQ_TRY(need_text("the bucketed round 0 gave up"));
             DQ_TRY(prepare_status<IdxT>(L, w, n, kMaxPasses));
             HIP_TRY(hipMemsetAsync(w.Vb, 0, (size_t)(tie_words() + 1) * 8, st));
             HIP_TRY(hipMemsetAsync(w.totals, 0, 64, st));
             o.m = 0; o.fin_cap = 0; o.fin_left = 0;
             return digit_tables(kb, false);
         }
+        if (o.fin_left > 0) DQ_TRY(need_text("ties are left behind the settle"));
         o.fin_done = settle || o.m <= o.fin_cap;
         o.Kr[0] = Kfree; o.Kr[1] = Ks;
         if (settle) {

@@ -440,6 +440,18 @@ inline int early_status_passes(int64_t n, const Flags &F)
     return at > 0 && n >= at ? 0 : kEarlyPasses;
 }
 
+// A device-resident, 16-byte aligned text stays in the caller's buffer (dq_text_view.h) in the same regime: a random-like
+// text of that size takes the slots route, whose kernels read it through a view, and the padded copy is never made; a
+// text that takes another route pays one copy pass once the route is known.  min_view_n: kTextViewMinN.
+// DQ_TEXT_IN_PLACE = 0: never; 1: at any n >= min_view_n (tests).
+inline bool text_in_place_wanted(int64_t n, bool device_text_aligned, int64_t min_view_n, const Flags &F)
+{
+    if (!device_text_aligned || n < min_view_n) return false;
+    if (F.text_in_place) return *F.text_in_place != 0;
+    const int64_t at = slots_cut_min_n();
+    return at > 0 && n >= at;
+}
+
 // Packed words were chosen because few ties are expected: the last pass then records the tie structure itself (1 bit per
 // suffix + 2 words per tile and digit, in the idle Vb buffer) instead of writing the sorted words for a rebucket pass.
 inline bool fused_ties_wanted(int64_t n, KeyPlan k, const Flags &F)

@@ -13,6 +13,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "dq_text_view.h"
+
 #if defined(__HIPCC__)
 #define DQ_HD __host__ __device__
 #else
@@ -28,17 +30,22 @@ namespace dq {
 // first sorts first).  a + h <= n and b + h <= n.
 // (Byte-at-a-time, a pair that shares the whole window cost 2 x kMaxLen dependent loads: a 256 MiB slice of a
 // shared library with 38 M deep ties spent 12.7 ms in small_group_finish_kernel.)
-template <int kMaxLen>
-DQ_HD inline int suffix_window_compare(const uint8_t *text, int64_t n, int64_t h, int64_t a, int64_t b)
+// Text: a pointer to the padded text, or a TextView (dq_text_view.h), which places each suffix's window as a whole.
+DQ_HD inline const uint8_t *text_window(const uint8_t *text, int64_t p, int) { return text + p; }
+DQ_HD inline const uint8_t *text_window(const TextView &text, int64_t p, int len) { return text.window(p, len); }
+
+template <int kMaxLen, typename Text>
+DQ_HD inline int suffix_window_compare(const Text &text, int64_t n, int64_t h, int64_t a, int64_t b)
 {
     static_assert(kMaxLen % 8 == 0, "whole words");
     typedef uint64_t u64_any __attribute__((aligned(1), may_alias));
     const int64_t pa = a + h, pb = b + h;
+    const uint8_t *ta = text_window(text, pa, kMaxLen), *tb = text_window(text, pb, kMaxLen);
     uint64_t wa[kMaxLen / 8], wbv[kMaxLen / 8];
 #pragma unroll
     for (int k = 0; k < kMaxLen / 8; ++k) {
-        wa[k] = *reinterpret_cast<const u64_any *>(text + pa + 8 * k);
-        wbv[k] = *reinterpret_cast<const u64_any *>(text + pb + 8 * k);
+        wa[k] = *reinterpret_cast<const u64_any *>(ta + 8 * k);
+        wbv[k] = *reinterpret_cast<const u64_any *>(tb + 8 * k);
     }
     int d = kMaxLen;                                   // first differing byte
     bool a_less = false;

@@ -50,6 +50,27 @@ DQ_HD inline uint32_t sf_key(uint32_t unique) { return unique >> kBktArrBits; }
 DQ_HD inline uint32_t sf_arrival(uint32_t unique) { return (unique & ((1u << kBktArrBits) - 1)) - 1; }
 DQ_HD inline bool sf_same_bin(uint32_t a, uint32_t b, int shift) { return ((a ^ b) >> (shift + kBktArrBits)) == 0; }
 
+// ---- split slot words.  The top 16 key bits of a word in bucket b's slot are b itself: the slot says them.  Where the rest
+// fits 48 bits, slot_rank_kernel<true> writes, over the same slot numbering, two arrays instead of the 8-byte words:
+//   H[slot_base[b] + i]   uint32: the suffix in bits 0 .. ib - 1, above it the low key bits from bit 16 upward
+//   Lo[slot_base[b] + i]  uint16: the low 16 of the low key bits
+// H starts where the 8-byte slots start, Lo behind H's 4 * slot_base[65536] bytes rounded up to 16: 6/8 of the 8-byte
+// span, so whatever fits that span fits this one (slot_split_fits: from 8 words on) and no route decision changes.
+struct SlotHalves { uint32_t hi; uint16_t lo; };
+DQ_HD inline bool slot_split_applies(int ib, int lowbits) { return ib >= 1 && ib <= 31 && lowbits >= 1 && lowbits <= 16 + 32 - ib; }
+DQ_HD inline SlotHalves slot_split_pack(uint64_t word, int ib, int lowbits)
+{
+    const uint32_t key = (uint32_t)(word >> ib) & (uint32_t)((1ull << lowbits) - 1);
+    const uint32_t imask = (uint32_t)((1ull << ib) - 1);
+    return SlotHalves{((uint32_t)word & imask) | (uint32_t)((uint64_t)(key >> 16) << ib), (uint16_t)(key & 0xffffu)};
+}
+DQ_HD inline uint32_t slot_split_key(uint32_t hi, uint32_t lo, int ib) { return ((hi >> ib) << 16) | lo; }
+DQ_HD inline uint32_t slot_split_suf(uint32_t hi, int ib) { return hi & (uint32_t)((1ull << ib) - 1); }
+// where Lo starts, in bytes from H[0], for slots that end at word `end` (= slot_base[65536]); and whether both arrays
+// lie inside the end * 8 bytes of the 8-byte form
+DQ_HD inline uint64_t slot_split_lo_at(uint32_t end) { return ((uint64_t)end * 4 + 15) & ~(uint64_t)15; }
+DQ_HD inline bool slot_split_fits(uint32_t end) { return slot_split_lo_at(end) + (uint64_t)end * 2 <= (uint64_t)end * 8; }
+
 // The rank rule, one neighbour at a time: fin starts at the position, tie at 0.  A neighbour of another bin changes
 // nothing: to the left its key is smaller, to the right larger.
 DQ_HD inline void sf_left(uint32_t mine, uint32_t other, uint32_t &fin, uint32_t &tie)

@@ -25,6 +25,7 @@
 #pragma once
 #include "dq_bucket_sort.h"
 #include "dq_xcd_rank.h"
+#include "dq_slot_finish_plan.h"
 
 namespace dq {
 
@@ -63,8 +64,9 @@ static __global__ __launch_bounds__(kBlock) void slot_plan_kernel(const int64_t 
 }
 
 // The slots route's setup in one launch: the first `places` workgroups are text_digit_offsets_kernel's (dq_onesweep.h), the
-// 257 behind them slot_plan_kernel's.  Both read only the byte histograms (and the text's first bytes).
-static __global__ __launch_bounds__(kBlock) void slot_setup_kernel(const int64_t *__restrict__ bytehist, const uint8_t *__restrict__ text,
+// 257 behind them slot_plan_kernel's.  Both read only the byte histograms (and a few bytes of the text, through a view:
+// dq_text_view.h).
+static __global__ __launch_bounds__(kBlock) void slot_setup_kernel(const int64_t *__restrict__ bytehist, const TextView text,
                                                             int64_t n, int places, int64_t *__restrict__ digit_offset,
                                                             const int64_t *__restrict__ xcd_hist, int64_t *__restrict__ sub_offset,
                                                             int64_t X, uint32_t *__restrict__ slot_base /*[65537]*/)
@@ -123,10 +125,13 @@ constexpr int kSlotRankThreads = 1024;
 constexpr int kSlotRankItems = 12;
 constexpr int kSlotTileN = kSlotRankThreads * kSlotRankItems;
 
-// n < 2^31 (ib <= 31 on the bucketed path) and the slots end below 2^32 words (bucket_slots_fit): positions fit 32 bits
+// n < 2^31 (ib <= 31 on the bucketed path) and the slots end below 2^32 words (bucket_slots_fit): positions fit 32 bits.
+// kSplit: the run write stores split slot words (dq_slot_finish_plan.h) -- a dword to H and a short to Lo at the place
+// the 8-byte word would take, under the same predicate; everything in front of the run write is the same code.
+template <bool kSplit>
 static __global__ __launch_bounds__(kSlotRankThreads, 1) void slot_rank_kernel(
     const uint64_t *__restrict__ kin /* the first pass's output: regions by second byte */, uint64_t *__restrict__ wout, int64_t n,
-    int shift /* of the first byte, the digit of this pass */, int bshift /* of the bucket id */,
+    int shift /* of the first byte, the digit of this pass */, int bshift /* of the bucket id */, int ib /* suffix bits (kSplit) */,
     const int64_t *__restrict__ region /*[256] where the regions start*/, const uint32_t *__restrict__ slot_base /*[65537]*/,
     SlotRankCtl *__restrict__ ctl, BucketFlags *__restrict__ flags)
 {
@@ -281,11 +286,27 @@ static __global__ __launch_bounds__(kSlotRankThreads, 1) void slot_rank_kernel(
         for (int k = 0; k < kItems; ++k) key[k] = exch[k * kThreads + tid];
 
         // coalesced run writes; a word beyond its slot stays unwritten (the flag is up)
+        if constexpr (kSplit) {
+            uint32_t *__restrict__ H = reinterpret_cast<uint32_t *>(wout);
+            uint16_t *__restrict__ Lo = reinterpret_cast<uint16_t *>(reinterpret_cast<uint8_t *>(wout) + slot_split_lo_at(slot_base[kSlotBuckets]));
 #pragma unroll
-        for (int k = 0; k < kItems; ++k) {
-            const uint32_t q = (uint32_t)(k * kThreads + tid);
-            const uint32_t d = digit_of(key[k], shift);
-            if (q < valid && q < glim[d]) wout[gofs[d] + q] = key[k];
+            for (int k = 0; k < kItems; ++k) {
+                const uint32_t q = (uint32_t)(k * kThreads + tid);
+                const uint32_t d = digit_of(key[k], shift);
+                const SlotHalves h = slot_split_pack(key[k], ib, bshift - ib);
+                if (q < valid && q < glim[d]) {
+                    const uint32_t at = gofs[d] + q;
+                    H[at] = h.hi;
+                    Lo[at] = h.lo;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < kItems; ++k) {
+                const uint32_t q = (uint32_t)(k * kThreads + tid);
+                const uint32_t d = digit_of(key[k], shift);
+                if (q < valid && q < glim[d]) wout[gofs[d] + q] = key[k];
+            }
         }
         DQ_SLOT_PHASE(3);
         lo = next_lo;

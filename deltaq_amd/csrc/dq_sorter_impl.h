@@ -662,6 +662,7 @@ struct SuffixSorter {
     //      down and leave the list; *done: nothing is left.
     int64_t twin_half = 0;
     const uint8_t *text_src = nullptr;   // the caller's device-resident text when w.text is still to be filled from it
+    bool text_missing = false;           // round 0 left the text in the caller's buffer: w.text holds its tail block only (Round0::need_text)
     int period_hint = 0;                // (SortHints::run_period)
     int twin_pairs_step(bool *done)
     {
@@ -716,7 +717,8 @@ struct SuffixSorter {
         t_sort_info = {};
         HIP_TRY(hipMemsetAsync(w.totals, 0, 64, st));
         Round0Out<IdxT> r0;
-        int rc = Round0<IdxT>{c, st, w, n, d_sa, L, text_src, period_hint, r0}.run();
+        Round0<IdxT> round0{c, st, w, n, d_sa, L, text_src, period_hint, r0, text_missing};
+        int rc = round0.run();
         if (rc != DQ_OK) return rc;
         adopt(r0);
         t_sort_info.initial_active = m;
@@ -730,6 +732,12 @@ struct SuffixSorter {
         // the ISA exists and the list is keyed / laid out for a radix round -- or carries its ranks as 32-bit values
         // for the first LDS-class round (first_rank32: nothing else may read Kr[rcur] as ranks before that round)
         if (keys_ready || list_ungrouped || first_rank32) sparse = false;
+        // (every kernel from here on reads w.text; round 0 has made the copy wherever it left a list: nothing but a settle
+        // that finished every tie -- finish_sparse() then launches nothing -- goes on without it)
+        if (!(sparse && fin_done && fin_left == 0)) {
+            rc = round0.need_text("the doubling rounds read it");
+            if (rc != DQ_OK) return rc;
+        }
         if (sparse) rc = finish_sparse();
         else if (!r0.dense_built) rc = build_isa(Kr[rcur], Vr[rcur], m);
         if (rc != DQ_OK) return rc;

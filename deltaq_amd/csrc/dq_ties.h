@@ -203,11 +203,12 @@ constexpr int kSettleThreads = 256;
 constexpr int kSettleWords = 8;
 constexpr int kSettleQueue = 256;
 constexpr int kSettleMaxG = 8, kSettleLen = 32;
+static_assert(kSettleLen <= kTextTailLead, "a comparison's window is placed as a whole (TextView::window)");
 
 // the group SA[head, head + g), 3 <= g <= kSettleMaxG, ordered in place; false: a comparison stayed undecided (nothing
 // written) or an entry is no suffix of the text (*bad)
 template <typename IdxT>
-__device__ __forceinline__ bool settle_group(IdxT *SA, const uint8_t *__restrict__ text, int64_t n, int64_t h, int64_t head, int g, bool *bad)
+__device__ __forceinline__ bool settle_group(IdxT *SA, const TextView &text, int64_t n, int64_t h, int64_t head, int g, bool *bad)
 {
     // Place of a member = how many members sort before it: every pair is compared once, in rolled loops that read the
     // members from SA as they go (they are cached), so that this rare path costs the kernel one comparison's registers.
@@ -239,7 +240,7 @@ __device__ __forceinline__ bool settle_group(IdxT *SA, const uint8_t *__restrict
 
 template <typename IdxT>
 __global__ __launch_bounds__(kSettleThreads, 6) void tie_settle_kernel(
-    const uint64_t *__restrict__ ebits, int64_t nwords, int64_t n, IdxT *SA, const uint8_t *__restrict__ text, int64_t h,
+    const uint64_t *__restrict__ ebits, int64_t nwords, int64_t n, IdxT *SA, const TextView text /* dq_text_view.h */, int64_t h,
     uint64_t *__restrict__ list_rank, IdxT *__restrict__ list_suf, int64_t list_cap /* entries the list may take */,
     TieCounters *__restrict__ ctr /* count: tied suffixes seen */, unsigned long long *__restrict__ list_count /* zero on entry */)
 {

@@ -42,7 +42,7 @@ static_assert(kXcdRankThreads * kXcdRankItems == kXcdTileN, "the eighths are cut
 
 // n < 2^31 (ib <= 31 on the bucketed path): output positions fit 32 bits
 static __global__ __launch_bounds__(kXcdRankThreads, 1) void xcd_text_rank_kernel(
-    const uint32_t *__restrict__ t32 /* text, followed by >= 12 zero bytes */, uint64_t *__restrict__ kout, int64_t n,
+    const TextView text /* dq_text_view.h: the padded copy, or the caller's buffer and the tail block */, uint64_t *__restrict__ kout, int64_t n,
     int shift, int keybits, int ib, const int64_t *__restrict__ sub_offset /*[8][256]*/, XcdRankCtl *__restrict__ ctl)
 {
     constexpr int kThreads = kXcdRankThreads, kItems = kXcdRankItems, kTileN = kXcdTileN;
@@ -100,8 +100,11 @@ static __global__ __launch_bounds__(kXcdRankThreads, 1) void xcd_text_rank_kerne
         for (int j = 0; j < kItems / 4; ++j) {
             const int64_t e0 = base + (int64_t)(j * kThreads + tid) * 4;
             // (a group past the end is never read: only the last tile of the text is ragged; the 12 bytes of the
-            // last group within it reach into the zero pad behind the text)
-            if (e0 < n) { nw[j][0] = t32[e0 >> 2]; nw[j][1] = t32[(e0 >> 2) + 1]; nw[j][2] = t32[(e0 >> 2) + 2]; }
+            // last group within it reach into the zero pad behind the text: one 12-byte load from a multiple of 4)
+            if (e0 < n) {
+                const uint32_t *t32 = reinterpret_cast<const uint32_t *>(text.at(e0));
+                nw[j][0] = t32[0]; nw[j][1] = t32[1]; nw[j][2] = t32[2];
+            }
         }
     };
     load_text(tile);
