@@ -217,6 +217,25 @@ public sealed class HipSuffixSort : ISuffixSort
     private static extern unsafe int dq_lzdecode_last_info(long* info, int count);
 
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern long dq_lzpack_bound(long z, int count);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    private static extern unsafe int dq_lzpack_hip_many_i32(int* phrases, long* phraseOffsets, int count, int kind, byte* blobs, long cap, long* blobOffsets, int* status, int device);
+
+    // (declared for hosts that keep their buffers on the device: device pointers, a hipStream_t or zero)
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern unsafe int dq_lzpack_hip_many_dev_i32(IntPtr dPhrases, long* phraseOffsets, int count, int kind, IntPtr dBlobs, long cap, long* blobOffsets, int* status, int device, IntPtr stream);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    private static extern unsafe int dq_lzunpack_hip_many_i32(byte* blobs, long* blobOffsets, int count, int* phrases, long cap, long* phraseOffsets, long* outLen, int* kind, int* status, int device);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern unsafe int dq_lzunpack_hip_many_dev_i32(IntPtr dBlobs, long* blobOffsets, int count, IntPtr dPhrases, long cap, long* phraseOffsets, long* outLen, int* kind, int* status, int device, IntPtr stream);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    private static extern unsafe int dq_lzpack_last_info(long* info, int count);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
     private static extern int dq_abi_version();
 
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
@@ -1793,6 +1812,146 @@ public sealed class HipSuffixSort : ISuffixSort
             if (rc != 0)
             {
                 throw new InvalidOperationException($"dq_lzdecode_last_info failed ({rc})");
+            }
+        }
+
+        return info;
+    }
+
+    /// <summary>dq_lzpack_bound: bytes that hold the DQLZ blobs of any count texts of z triples together; -1 on negative arguments.</summary>
+    public static long LzPackBound(long z, int count) => dq_lzpack_bound(z, count);
+
+    /// <summary>
+    /// The phrase lists of many texts as DQLZ blobs in one native call (dq_lzpack_hip_many_i32; include/dq_sufsort.h has
+    /// the format).  Each list holds the (start, len, third) triples of one text, as Lz77 (kind 0) or Rlz (kind 1) return
+    /// them.  A malformed list throws, naming its text.
+    /// </summary>
+    public unsafe byte[][] LzPackMany(IReadOnlyList<int[]> phrases, int kind)
+    {
+        if (kind != 0 && kind != 1)
+        {
+            throw new ArgumentException("kind must be 0 (LZ77) or 1 (RLZ)");
+        }
+
+        int count = phrases.Count;
+        var offsets = new long[count + 1];
+        for (int t = 0; t < count; t++)
+        {
+            if (phrases[t].Length % 3 != 0)
+            {
+                throw new ArgumentException($"text {t}: a phrase list holds three values per phrase");
+            }
+
+            offsets[t + 1] = offsets[t] + phrases[t].Length / 3;
+        }
+
+        var flat = new int[Math.Max(1, offsets[count] * 3)];
+        for (int t = 0; t < count; t++)
+        {
+            phrases[t].CopyTo(flat, offsets[t] * 3);
+        }
+
+        long cap = dq_lzpack_bound(offsets[count], count);
+        var blobs = new byte[Math.Max(1, cap)];
+        var blobOffsets = new long[count + 1];
+        var status = new int[Math.Max(1, count)];
+        fixed (int* p = flat)
+        fixed (long* po = offsets)
+        fixed (byte* b = blobs)
+        fixed (long* bo = blobOffsets)
+        fixed (int* st = status)
+        {
+            int rc = dq_lzpack_hip_many_i32(p, po, count, kind, b, cap, bo, st, _device);
+            if (rc != 0)
+            {
+                throw new InvalidOperationException($"dq_lzpack_hip_many_i32 failed ({rc}): {Marshal.PtrToStringAnsi(dq_last_error()) ?? string.Empty}");
+            }
+        }
+
+        var result = new byte[count][];
+        for (int t = 0; t < count; t++)
+        {
+            if (status[t] != 0)
+            {
+                throw new ArgumentException($"text {t}: malformed phrases");
+            }
+
+            result[t] = new byte[blobOffsets[t + 1] - blobOffsets[t]];
+            Array.Copy(blobs, blobOffsets[t], result[t], 0, result[t].Length);
+        }
+
+        return result;
+    }
+
+    /// <summary>
+    /// DQLZ blobs back into phrase lists in one native call (dq_lzunpack_hip_many_i32): per blob the triples, the decoded
+    /// size and the kind of its header.  Blobs are untrusted: a malformed one throws, naming it.
+    /// </summary>
+    public unsafe (int[] Phrases, long Size, int Kind)[] LzUnpackMany(IReadOnlyList<byte[]> blobs)
+    {
+        int count = blobs.Count;
+        var offsets = new long[count + 1];
+        for (int t = 0; t < count; t++)
+        {
+            offsets[t + 1] = offsets[t] + blobs[t].Length;
+        }
+
+        var flat = new byte[Math.Max(1, offsets[count])];
+        for (int t = 0; t < count; t++)
+        {
+            blobs[t].CopyTo(flat, offsets[t]);
+        }
+
+        long cap = offsets[count];                      // a phrase costs a blob byte at least
+        var phrases = new int[Math.Max(1, cap * 3)];
+        var phraseOffsets = new long[count + 1];
+        var sizes = new long[Math.Max(1, count)];
+        var kinds = new int[Math.Max(1, count)];
+        var status = new int[Math.Max(1, count)];
+        fixed (byte* b = flat)
+        fixed (long* bo = offsets)
+        fixed (int* p = phrases)
+        fixed (long* po = phraseOffsets)
+        fixed (long* sz = sizes)
+        fixed (int* kd = kinds)
+        fixed (int* st = status)
+        {
+            int rc = dq_lzunpack_hip_many_i32(b, bo, count, p, cap, po, sz, kd, st, _device);
+            if (rc != 0)
+            {
+                throw new InvalidOperationException($"dq_lzunpack_hip_many_i32 failed ({rc}): {Marshal.PtrToStringAnsi(dq_last_error()) ?? string.Empty}");
+            }
+        }
+
+        var result = new (int[], long, int)[count];
+        for (int t = 0; t < count; t++)
+        {
+            if (status[t] != 0)
+            {
+                throw new ArgumentException($"blob {t}: malformed DQLZ blob");
+            }
+
+            var list = new int[(phraseOffsets[t + 1] - phraseOffsets[t]) * 3];
+            Array.Copy(phrases, phraseOffsets[t] * 3, list, 0, list.Length);
+            result[t] = (list, sizes[t], kinds[t]);
+        }
+
+        return result;
+    }
+
+    /// <summary>
+    /// Shape of the last pack or unpack call on this thread (dq_lzpack_last_info): texts with status 0, texts refused,
+    /// the tokens, control bytes and literal bytes of the former, kernel launches, stream waits.
+    /// </summary>
+    public static unsafe long[] LastLzPackInfo()
+    {
+        var info = new long[7];
+        fixed (long* p = info)
+        {
+            int rc = dq_lzpack_last_info(p, info.Length);
+            if (rc != 0)
+            {
+                throw new InvalidOperationException($"dq_lzpack_last_info failed ({rc})");
             }
         }
 

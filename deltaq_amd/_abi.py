@@ -70,6 +70,8 @@ EXPORTS = (
     "dq_lz77_decode_hip_i32", "dq_lz77_decode_hip_dev_i32", "dq_rlz_decode_hip_i32", "dq_rlz_decode_hip_dev_i32",
     "dq_lz77_decode_hip_many_i32", "dq_lz77_decode_hip_many_dev_i32", "dq_rlz_decode_hip_many_i32",
     "dq_rlz_decode_hip_many_dev_i32", "dq_lzdecode_last_info",
+    "dq_lzpack_bound", "dq_lzpack_hip_many_i32", "dq_lzpack_hip_many_dev_i32", "dq_lzunpack_hip_many_i32",
+    "dq_lzunpack_hip_many_dev_i32", "dq_lzpack_last_info",
     "dq_bsdiff_search_dev_i32", "dq_bsdiff_search_dev_i64", "dq_bsdiff_search_i32", "dq_bsdiff_search_i64",
     "dq_bsdiff_create", "dq_bsdiff_patch_bound", "dq_bsdiff_scan_i32", "dq_bspatch_apply",
     "dq_bspatch_new_size_many", "dq_bspatch_apply_many", "dq_bspatch_index_apply_many",
@@ -128,6 +130,10 @@ RLZ_RECORD = _n("phrases", "literals", "longest", "matched", "walker_hops", "lau
 # ... and the record of dq_lzdecode_last_info, struct LzDecodeInfo of deltaq_amd/csrc/dq_lzdecode_info.h;
 # tests/test_lzdecode_cpu.py checks it.
 LZDECODE_RECORD = _n("texts_ok", "texts_refused", "linked", "jump_rounds", "launches", "stream_waits")
+
+# ... and the record of dq_lzpack_last_info, struct LzPackInfo of deltaq_amd/csrc/dq_lzpack_info.h;
+# tests/test_lzpack_cpu.py checks it.
+LZPACK_RECORD = _n("texts_ok", "texts_refused", "tokens", "ctrl_bytes", "literal_bytes", "launches", "stream_waits")
 
 
 class BackendMissingError(RuntimeError):
@@ -271,6 +277,18 @@ def load() -> ctypes.CDLL:
     L.dq_rlz_decode_hip_many_dev_i32.argtypes = [vp, i64, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp]
     L.dq_lzdecode_last_info.restype = i32
     L.dq_lzdecode_last_info.argtypes = [ctypes.POINTER(i64), i32]
+    L.dq_lzpack_bound.restype = i64
+    L.dq_lzpack_bound.argtypes = [i64, i32]
+    L.dq_lzpack_hip_many_i32.restype = i32
+    L.dq_lzpack_hip_many_i32.argtypes = [vp, vp, i32, i32, vp, i64, vp, vp, i32]
+    L.dq_lzpack_hip_many_dev_i32.restype = i32
+    L.dq_lzpack_hip_many_dev_i32.argtypes = [vp, vp, i32, i32, vp, i64, vp, vp, i32, vp]
+    L.dq_lzunpack_hip_many_i32.restype = i32
+    L.dq_lzunpack_hip_many_i32.argtypes = [vp, vp, i32, vp, i64, vp, vp, vp, vp, i32]
+    L.dq_lzunpack_hip_many_dev_i32.restype = i32
+    L.dq_lzunpack_hip_many_dev_i32.argtypes = [vp, vp, i32, vp, i64, vp, vp, vp, vp, i32, vp]
+    L.dq_lzpack_last_info.restype = i32
+    L.dq_lzpack_last_info.argtypes = [ctypes.POINTER(i64), i32]
     L.dq_sufsort_hip_batch_i32.restype = i32
     L.dq_sufsort_hip_batch_i32.argtypes = [i32, vp, vp, vp, i32, vp]
     L.dq_sufsort_hip_many_i32.restype = i32
@@ -504,6 +522,15 @@ def last_lzdecode_info() -> dict:
     v = (ctypes.c_int64 * len(LZDECODE_RECORD))()
     check(load().dq_lzdecode_last_info(v, len(LZDECODE_RECORD)))
     return {key: v[i] * scale for i, (key, scale) in enumerate(LZDECODE_RECORD)}
+
+
+def last_lzpack_info() -> dict:
+    """Shape of the last dq_lzpack_hip_many_* / dq_lzunpack_hip_many_* on this thread (dq_lzpack_last_info): texts with
+    status 0 and with status -1, the tokens, control bytes and literal bytes of the former, kernel launches and stream
+    waits."""
+    v = (ctypes.c_int64 * len(LZPACK_RECORD))()
+    check(load().dq_lzpack_last_info(v, len(LZPACK_RECORD)))
+    return {key: v[i] * scale for i, (key, scale) in enumerate(LZPACK_RECORD)}
 
 
 def last_batch_info() -> dict:

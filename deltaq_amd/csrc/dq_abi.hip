@@ -244,6 +244,19 @@ int32_t lzdecode_entry(Call call)
     }
 }
 
+// an entry point of dq_lzpack_hip_many_* / dq_lzunpack_hip_many_*: as lzdecode_entry, with the packer's record
+template <typename Call>
+int32_t lzpack_entry(Call call)
+{
+    EnvScope scope;
+    t_lzpack_info = {};
+    try {
+        return call();
+    } catch (const std::bad_alloc &) {
+        return fail(DQ_ERR_OOM, "lz pack: host allocation failed");
+    }
+}
+
 }  // namespace
 }  // namespace dq
 
@@ -629,6 +642,39 @@ int32_t dq_rlz_decode_hip_many_dev_i32(const void *d_olds, int64_t olds_bytes, c
 }
 
 int32_t dq_lzdecode_last_info(int64_t *info, int32_t count) { return last_info(t_lzdecode_info, info, count, "null info array"); }
+
+int64_t dq_lzpack_bound(int64_t z, int32_t count) { return lzpack_bound(z, count); }
+
+int32_t dq_lzpack_hip_many_i32(const int32_t *phrases, const int64_t *phrase_offsets, int32_t count, int32_t kind, uint8_t *blobs,
+                               int64_t cap, int64_t *blob_offsets, int32_t *status, int32_t device)
+{
+    return lzpack_entry([&] { return lzpack_many(true, phrases, phrase_offsets, count, kind, blobs, cap, blob_offsets, status, device, nullptr); });
+}
+
+int32_t dq_lzpack_hip_many_dev_i32(const void *d_phrases, const int64_t *phrase_offsets, int32_t count, int32_t kind, void *d_blobs,
+                                   int64_t cap, int64_t *blob_offsets, int32_t *status, int32_t device, void *stream)
+{
+    return lzpack_entry([&] { return lzpack_many(false, d_phrases, phrase_offsets, count, kind, d_blobs, cap, blob_offsets, status, device, stream); });
+}
+
+int32_t dq_lzunpack_hip_many_i32(const uint8_t *blobs, const int64_t *blob_offsets, int32_t count, int32_t *phrases, int64_t cap,
+                                 int64_t *phrase_offsets, int64_t *out_len, int32_t *kind, int32_t *status, int32_t device)
+{
+    return lzpack_entry([&] {
+        return lzunpack_many(true, blobs, blob_offsets, count, phrases, cap, phrase_offsets, out_len, kind, status, device, nullptr);
+    });
+}
+
+int32_t dq_lzunpack_hip_many_dev_i32(const void *d_blobs, const int64_t *blob_offsets, int32_t count, void *d_phrases, int64_t cap,
+                                     int64_t *phrase_offsets, int64_t *out_len, int32_t *kind, int32_t *status, int32_t device,
+                                     void *stream)
+{
+    return lzpack_entry([&] {
+        return lzunpack_many(false, d_blobs, blob_offsets, count, d_phrases, cap, phrase_offsets, out_len, kind, status, device, stream);
+    });
+}
+
+int32_t dq_lzpack_last_info(int64_t *info, int32_t count) { return last_info(t_lzpack_info, info, count, "null info array"); }
 
 int32_t dq_sufsort_hip_batch_i32(int32_t count, const uint8_t *const *texts, const int64_t *lens,
                                  int32_t *const *sas, int32_t ndev, const int32_t *devs)

@@ -42,6 +42,7 @@
 #include "dq_lz77_info.h"
 #include "dq_rlz_info.h"
 #include "dq_lzdecode_info.h"
+#include "dq_lzpack_info.h"
 #include "dq_flags.h"
 #include "dq_work_lists.h"
 #include "dq_block_groups.h"
@@ -757,6 +758,15 @@ int lzdecode_one(bool rlz, bool host, const void *old, int64_t n, const void *ph
 int lzdecode_many(bool rlz, bool host, const void *olds, int64_t olds_bytes, const int64_t *old_spans, const void *phrases,
                   const int64_t *phrase_offsets, int32_t count, void *out, const int64_t *out_offsets, int64_t *out_len, int32_t *status,
                   int32_t device, void *stream);
+
+// Phrase triples into DQLZ byte streams and back (dq_lzpack_host.h, in dq_sufcheck.hip): the bodies of
+// dq_lzpack_hip_many_* and dq_lzunpack_hip_many_*.  host: the buffers are the host's (and stream is not looked at).  Both
+// fill t_lzpack_info (dq_lzpack_info.h); the entry point resets it.
+int64_t lzpack_bound(int64_t z, int32_t count);
+int lzpack_many(bool host, const void *phrases, const int64_t *phrase_offsets, int32_t count, int32_t kind, void *blobs, int64_t cap,
+                int64_t *blob_offsets, int32_t *status, int32_t device, void *stream);
+int lzunpack_many(bool host, const void *blobs, const int64_t *blob_offsets, int32_t count, void *phrases, int64_t cap,
+                  int64_t *phrase_offsets, int64_t *out_len, int32_t *kind, int32_t *status, int32_t device, void *stream);
 
 // match search + BSDIFF40 (dq_diff.hip)
 int match_search_dev_i32(const void *d_old, int64_t n, const void *d_sa, const void *d_new, int64_t m, const int64_t *d_scans,

@@ -1326,6 +1326,193 @@ class HipSuffixSort:
 
     rlz_decode_many = RlzDecodeMany
 
+    # -- the phrases as DQLZ byte streams, and the delta codec they make (include/dq_sufsort.h has the format) ------------
+    def LzPackMany(self, phrases, phrase_offsets=None, kind=0):
+        """The phrase lists of many texts as DQLZ blobs, in ONE native call.  ``phrases`` as in ``Lz77DecodeMany``: a
+        list of ``(z_t, 3)`` int32 arrays, or all triples as one array or torch GPU tensor with the host int64 array
+        ``phrase_offsets``.  ``kind``: 0 for what ``Lz77`` / ``Lz77Many`` return, 1 for ``Rlz`` / ``RlzMany``.  Host
+        arrays give a list of ``bytes`` (``dq_lzpack_hip_many_i32``); a GPU tensor stays on the device on the current
+        torch stream and gives ``(blobs_tensor, blob_offsets)``, blob t at ``[blob_offsets[t], blob_offsets[t + 1])``
+        (``dq_lzpack_hip_many_dev_i32``).  A malformed text raises ``ValueError`` naming it."""
+        if kind not in (0, 1):
+            raise ValueError("kind must be 0 (LZ77) or 1 (RLZ)")
+        P, poff, device = self._phrases_and_offsets(phrases, phrase_offsets)
+        count, z = poff.size - 1, P.shape[0]
+        boff, status = np.zeros(count + 1, dtype=np.int64), np.zeros(max(count, 1), dtype=np.int32)
+        cap = lzpack_bound(z, count)
+        if device:
+            import torch
+
+            out = torch.empty(cap, dtype=torch.uint8, device=P.device)
+            dev, stream = _device_and_stream(P)
+            _abi.check(self._lib.dq_lzpack_hip_many_dev_i32(P.data_ptr() if z else None, poff.ctypes.data, count, kind,
+                                                            out.data_ptr() if cap else None, cap, boff.ctypes.data,
+                                                            status.ctypes.data, dev, stream))
+        else:
+            out = np.empty(max(cap, 1), dtype=np.uint8)
+            _abi.check(self._lib.dq_lzpack_hip_many_i32(P.ctypes.data if z else None, poff.ctypes.data, count, kind, out.ctypes.data,
+                                                        cap, boff.ctypes.data, status.ctypes.data, self.device))
+        bad = np.flatnonzero(status[:count])
+        if bad.size:
+            raise ValueError(f"text {int(bad[0])}: malformed phrases")
+        if device:
+            return out[:int(boff[-1])], boff
+        return [out[boff[t]:boff[t + 1]].tobytes() for t in range(count)]
+
+    lzpack_many = LzPackMany
+
+    def LzPack(self, phrases, kind=0):
+        """One text through ``LzPackMany``: ``bytes`` from a host ``(z, 3)`` array, a uint8 tensor from a GPU tensor."""
+        if _is_torch_tensor(phrases):
+            return self.LzPackMany(phrases, np.array([0, phrases.shape[0]], dtype=np.int64), kind)[0]
+        return self.LzPackMany([phrases], None, kind)[0]
+
+    lzpack = LzPack
+
+    def LzUnpackMany(self, blobs, blob_offsets=None):
+        """DQLZ blobs back into phrase lists, in ONE native call: ``(phrases, phrase_offsets, sizes, kinds)`` -- the
+        triples of all blobs back to back as a ``(Z, 3)`` int32 array, the host int64 offsets of count + 1 entries,
+        and per blob the decoded size and the kind of its header.  ``blobs``: a list of ``bytes`` (``blob_offsets``
+        left out), or one uint8 buffer or torch GPU tensor with the host int64 array ``blob_offsets``; a GPU tensor
+        stays on the device on the current torch stream and gives the triples as a tensor
+        (``dq_lzunpack_hip_many_i32`` / ``dq_lzunpack_hip_many_dev_i32``).  Blobs are untrusted: a malformed one raises
+        ``ValueError`` naming it."""
+        device = _is_torch_tensor(blobs)
+        if isinstance(blobs, (list, tuple)):
+            if blob_offsets is not None:
+                raise TypeError("a list of blobs brings its own offsets: leave blob_offsets out")
+            if any(_is_torch_tensor(b) for b in blobs):
+                raise TypeError(MIXED_LZ_MESSAGE)
+            parts = [_as_text(b) for b in blobs]
+            if any(b.ndim != 1 for b in parts):
+                raise TypeError("every blob must be one-dimensional")
+            boff = np.zeros(len(parts) + 1, dtype=np.int64)
+            if parts:
+                np.cumsum([b.size for b in parts], out=boff[1:])
+            B = np.concatenate(parts) if boff[-1] else np.zeros(0, np.uint8)
+        else:
+            if blob_offsets is None or _is_torch_tensor(blob_offsets):
+                raise TypeError("blob_offsets must be a host int64 array of count + 1 entries")
+            boff = np.ascontiguousarray(blob_offsets, dtype=np.int64)
+            if boff.ndim != 1 or boff.size < 1:
+                raise TypeError("blob_offsets must be a host int64 array of count + 1 entries")
+            if device:
+                import torch
+
+                if blobs.dtype != torch.uint8 or blobs.dim() != 1 or not blobs.is_contiguous():
+                    raise TypeError("device blobs must be a contiguous 1-D uint8 tensor")
+                if not blobs.is_cuda:
+                    raise TypeError("torch tensors must live on the GPU; pass host data as bytes/numpy")
+                B = blobs
+            else:
+                B = _as_text(blobs)
+                if B.ndim != 1:
+                    raise TypeError("the blobs must be one one-dimensional buffer")
+            if boff[0] != 0 or (np.diff(boff) < 0).any() or boff[-1] != (B.numel() if device else B.size):
+                raise ValueError("blob_offsets must start at 0, never decrease and end at the number of bytes")
+        count, total = boff.size - 1, int(boff[-1])
+        if total > INT_MAX:
+            raise ValueError("the unpacker has 32-bit positions: the blobs together must be shorter than 2^31 bytes")
+        poff = np.zeros(count + 1, dtype=np.int64)
+        sizes, kinds = np.zeros(max(count, 1), dtype=np.int64), np.zeros(max(count, 1), dtype=np.int32)
+        status = np.zeros(max(count, 1), dtype=np.int32)
+        if device:
+            import torch
+
+            fn = self._lib.dq_lzunpack_hip_many_dev_i32
+            dev, stream = _device_and_stream(B)
+            head = (B.data_ptr() if total else None, boff.ctypes.data, count)
+            tail = (poff.ctypes.data, sizes.ctypes.data, kinds.ctypes.data, status.ctypes.data, dev, stream)
+            _abi.check(fn(*head, None, 0, *tail))
+            P = torch.empty((int(poff[-1]), 3), dtype=torch.int32, device=B.device)
+            if poff[-1]:
+                _abi.check(fn(*head, P.data_ptr(), int(poff[-1]), *tail))
+        else:
+            fn = self._lib.dq_lzunpack_hip_many_i32
+            head = (B.ctypes.data if total else None, boff.ctypes.data, count)
+            tail = (poff.ctypes.data, sizes.ctypes.data, kinds.ctypes.data, status.ctypes.data, self.device)
+            _abi.check(fn(*head, None, 0, *tail))
+            P = np.empty((int(poff[-1]), 3), dtype=np.int32)
+            if poff[-1]:
+                _abi.check(fn(*head, P.ctypes.data, int(poff[-1]), *tail))
+        bad = np.flatnonzero(status[:count])
+        if bad.size:
+            raise ValueError(f"blob {int(bad[0])}: malformed DQLZ blob")
+        return P, poff, sizes[:count], kinds[:count]
+
+    lzunpack_many = LzUnpackMany
+
+    def LzUnpack(self, blob):
+        """One blob through ``LzUnpackMany``: ``(phrases, size, kind)``."""
+        if _is_torch_tensor(blob):
+            P, _, sizes, kinds = self.LzUnpackMany(blob, np.array([0, blob.numel()], dtype=np.int64))
+        else:
+            P, _, sizes, kinds = self.LzUnpackMany([blob])
+        return P, int(sizes[0]), int(kinds[0])
+
+    lzunpack = LzUnpack
+
+    def DeltaCreateMany(self, olds, news):
+        """A DQLZ delta (kind 1) of every ``news[t]`` against ``olds[t]``: a list of ``bytes``, through ``RlzMany`` and
+        ``LzPackMany``.  ``DeltaApplyMany(olds, .)`` turns them back into the new files."""
+        return self.LzPackMany(self.RlzMany(olds, news), None, 1)
+
+    def DeltaCreate(self, old, new) -> bytes:
+        return self.DeltaCreateMany([old], [new])[0]
+
+    def DeltaApplyMany(self, olds, deltas):
+        """The new files of ``DeltaCreateMany``'s deltas, a list of ``bytes``, through ``LzUnpackMany`` and
+        ``RlzDecodeMany``.  A blob of the wrong kind, a malformed blob, or a copy from outside its old file raises
+        ``ValueError``."""
+        olds, deltas = list(olds), list(deltas)
+        if len(olds) != len(deltas):
+            raise ValueError("DeltaApplyMany takes one old file per delta")
+        P, poff, sizes, kinds = self.LzUnpackMany(deltas)
+        if (kinds != 1).any():
+            raise ValueError(f"blob {int(np.flatnonzero(kinds != 1)[0])}: not a relative (kind 1) blob")
+        return self.RlzDecodeMany(olds, None, P, poff, sizes)
+
+    def DeltaApply(self, old, delta) -> bytes:
+        return self.DeltaApplyMany([old], [delta])[0]
+
+    def Compress(self, text) -> bytes:
+        """The text as a DQLZ blob of kind 0, through ``Lz77Many`` and ``LzPackMany``."""
+        return self.LzPackMany(self.Lz77Many([text]), None, 0)[0]
+
+    def Decompress(self, blob) -> bytes:
+        """The text of ``Compress``'s blob, through ``LzUnpackMany`` and ``Lz77DecodeMany``; a blob of kind 1 or a
+        malformed one raises ``ValueError``."""
+        P, poff, sizes, kinds = self.LzUnpackMany([blob])
+        if (kinds != 0).any():
+            raise ValueError("blob 0: not an LZ77 (kind 0) blob")
+        return self.Lz77DecodeMany(P, poff, sizes)[0]
+
+    delta_create_many, delta_create, delta_apply_many, delta_apply = DeltaCreateMany, DeltaCreate, DeltaApplyMany, DeltaApply
+    compress, decompress = Compress, Decompress
+
+    def _phrases_and_offsets(self, phrases, phrase_offsets):
+        """``(P, poff, device)`` of the two forms ``Lz77DecodeMany`` takes its phrases in."""
+        device = _is_torch_tensor(phrases)
+        if isinstance(phrases, (list, tuple)):
+            if phrase_offsets is not None:
+                raise TypeError("a list of phrase arrays brings its own offsets: leave phrase_offsets out")
+            if any(_is_torch_tensor(p) for p in phrases):
+                raise TypeError(MIXED_LZ_MESSAGE)
+            parts = [self._host_phrases(p) for p in phrases]
+            poff = np.zeros(len(parts) + 1, dtype=np.int64)
+            if parts:
+                np.cumsum([p.shape[0] for p in parts], out=poff[1:])
+            return (np.concatenate(parts) if poff[-1] else np.zeros((0, 3), np.int32)), poff, False
+        if phrase_offsets is None or _is_torch_tensor(phrase_offsets):
+            raise TypeError("phrase_offsets must be a host int64 array of count + 1 entries")
+        poff = np.ascontiguousarray(phrase_offsets, dtype=np.int64)
+        if poff.ndim != 1 or poff.size < 1:
+            raise TypeError("phrase_offsets must be a host int64 array of count + 1 entries")
+        P = self._device_phrases(phrases) if device else self._host_phrases(phrases)
+        if poff[0] != 0 or (np.diff(poff) < 0).any() or poff[-1] != P.shape[0]:
+            raise ValueError("phrase_offsets must start at 0, never decrease and end at the number of triples")
+        return P, poff, device
+
     @staticmethod
     def _decoded_size(last, what):
         """start + max(1, len) of a text's last triple, refused where no well-formed text has it."""
@@ -1618,6 +1805,14 @@ class HipSuffixSort:
         if suffixes.numel() != lcp.numel() or (text is not None and suffixes.numel() != text.numel()):
             raise ValueError(LENGTH_MISMATCH_MESSAGE)
         return suffixes, lcp
+
+
+def lzpack_bound(z: int, count: int) -> int:
+    """Bytes that hold the DQLZ blobs of any ``count`` texts of ``z`` triples together (``dq_lzpack_bound``)."""
+    bound = _abi.load().dq_lzpack_bound(z, count)
+    if bound < 0:
+        raise ValueError("lzpack_bound: negative arguments or a bound beyond 64 bits")
+    return bound
 
 
 def lz77_decode(phrases) -> bytes:

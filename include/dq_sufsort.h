@@ -1001,7 +1001,7 @@ int32_t dq_lzparse_hip_many_dev_i32(const void *d_texts, const void *d_offsets, 
  * counters; the host forms add their copies of the triples, of olds and of out.  No chunking and no CPU fallback:
  * DQ_ERR_OOM where that does not fit.  The _dev_ forms take device pointers on `device`, enqueue on `stream` (NULL = the
  * library's stream) and return after it has drained.  One stream wait per call.
- * Out of scope: int64 forms, and a byte-level coder on the phrases.
+ * Out of scope: int64 forms.  The byte-level coder on the phrases is dq_lzpack_hip_many_* below.
  * dq_lzdecode_last_info: shape of the last of these calls on this thread, reset when one starts; `count` entries (6 are
  * defined, further ones read 0; a NULL array is DQ_ERR_BAD_ARGS): [0] texts with status 0; [1] texts with status -1 or
  * -2; [2] positions whose byte was not known after the tile pass; [3] global rounds that still found work (both 0 in
@@ -1029,6 +1029,81 @@ int32_t dq_rlz_decode_hip_many_dev_i32(const void *d_olds, int64_t olds_bytes, c
                                        void *d_out, const int64_t *out_offsets, int64_t *out_len, int32_t *status,
                                        int32_t device, void *stream);
 int32_t dq_lzdecode_last_info(int64_t *info, int32_t count);
+
+/* ---- the phrases as byte streams, on the device: DQLZ blobs of many texts per call ------------------------------------
+ * A blob holds the phrase list of one text in 32 + c + l bytes:
+ *   0..3 'D' 'Q' 'L' 'Z';  4 version = 1;  5 kind: 0 = LZ77 (a copy's source lies in the text's own output), 1 = RLZ (it
+ *   lies in old);  6..7 zero;  8..15 n, the decoded size, int64 LE, 0 <= n <= 2^31-1;  16..23 c, the control bytes, int64
+ *   LE;  24..31 l, the literal bytes, int64 LE;  then the control stream (c bytes) and the literal stream (l bytes: the
+ *   bytes of the literal phrases in phrase order).
+ * The control stream is a sequence of tokens, each exactly three LEB128 varints (7 bits a byte, low bits first, bit 7
+ * set on every byte but the last): lit_run, len, code.  Every copy phrase ends a token: lit_run counts the literal
+ * phrases since the previous copy (or the text's start), len >= 1 is the copy's length.  A final token (lit_run, 0, 0)
+ * always closes the stream with the trailing literals; an empty text is that token alone (c = 3, l = 0).
+ *   kind 0: code = start - third - 1, the distance less one; valid iff code <= start - 1.
+ *   kind 1: code = zigzag(third - expect), zigzag(v) = (v << 1) ^ (v >> 63) in 64 bits; expect = 0 for a text's first copy,
+ *           else third_prev + len_prev + lit_run of this token: where in old a copy stands that keeps step with new
+ *           across a substitution.  Valid iff 0 <= third and third + len <= 2^31-1; whether the copy ends inside old is
+ *           dq_rlz_decode_*'s verdict.
+ * A varint has at most 5 bytes (35 bits) and is in its shortest form (the last byte of a multi-byte varint is not 0);
+ * lit_run and len are at most 2^31-1.  Literal bytes never stand in the control stream: a control byte ends a varint iff
+ * it is below 0x80, and a varint's role is its index mod 3.
+ * A blob is well-formed iff: the header is as above; 32 + c + l is the blob's size; the last control byte is below 0x80;
+ * every varint is canonical and has at most 5 bytes; their number is a multiple of 3; exactly the last token has
+ * len == 0, and it has code == 0; the lit_runs sum to l; the lit_runs and lens sum to n (in 64 bits); the kind's rule
+ * holds for every copy.  Phrase lists that are well-formed in the sense of dq_lz77_decode_* (kind 1: with 2^31-1 for
+ * old's size) and well-formed blobs of a kind correspond one to one.
+ *   "abababb", kind 0: (0,0,'a') (1,0,'b') (2,4,0) (6,1,1)   control 02 04 01 00 01 04 00 00 00, literals "ab", n = 7
+ *   old "abab", new "babbc", kind 1: (0,3,1) (3,1,1) (4,0,'c')   control 00 03 02 00 01 05 01 00 00, literals "c", n = 5
+ * dq_lzpack_bound(z, count) = 47 * count + 16 * z bytes hold the blobs of any `count` texts of z triples together (a
+ * token is at most 15 bytes, a text has at most copies + 1 of them); -1 on negative arguments or overflow.
+ * Pack.  Text t's triples are [phrase_offsets[t], phrase_offsets[t + 1]); kind holds for the whole call.  status[t] is 0,
+ * or -1 where the triples are not well-formed (judged on the device; a triple never becomes an address), and such a text
+ * has a blob of 0 bytes.  blob_offsets[0 .. count] always receives the true prefix sums of the blob sizes; the blobs are
+ * written back to back into blobs iff blob_offsets[count] <= cap, otherwise nothing is written, and the call returns
+ * DQ_OK either way: cap == 0 with blobs == NULL is the sizing call.  Nothing outside blobs[0 .. blob_offsets[count]) is
+ * written.
+ * Unpack.  Blob t is blobs[blob_offsets[t] .. blob_offsets[t + 1]).  Blobs are untrusted: a malformed one is its own
+ * verdict, never a failed call and never an address.  status[t] is 0 or -1 (a blob shorter than 32 bytes among them).
+ * With status 0 out_len[t] = n and kind[t] is the header's kind; with -1 out_len[t] = 0, kind[t] = -1, and the blob has
+ * no phrases.  phrase_offsets[0 .. count] always receives the true prefix sums; the triples -- exactly the list that
+ * packs to the blob -- are written iff phrase_offsets[count] <= cap (triples), and nothing beyond them.  A status-0 blob
+ * of kind 0 is always accepted by dq_lz77_decode_* (status 0 or -2).
+ * Every offsets array, out_len, kind and status is a HOST pointer in both forms: the library uploads what the kernels
+ * read, and nothing is fetched from the device before the work starts.
+ *   negative count or cap; kind not 0 or 1; a NULL buffer that is needed (the host arrays always; phrases / blobs where
+ *   there is a triple / a blob byte; the output where cap > 0); offsets[0] != 0; decreasing offsets   DQ_ERR_BAD_ARGS
+ *   more than 2^31-1 triples (pack) or blob bytes (unpack) in the call                                  DQ_ERR_TOO_LARGE
+ * -- all decided before a device is looked for, and the output arrays stay untouched.  count == 0 returns DQ_OK without
+ * a device; so does an unpack call whose blobs are all empty (every status -1).
+ * Computed flat over the call (deltaq_amd/csrc/dq_lzpack.h): the packer over triples and tokens, the unpacker over blob
+ * bytes and varints; an item finds its text by bisection of the uploaded offsets.  All counting is prefix sums -- a sum
+ * per tile of 1024 items, ONE workgroup carrying the sums over the tiles, the tiles again with their carries; a text
+ * takes the difference to the sum at its own first item --, so nobody waits for anybody and the launches are constants
+ * (lzpack_launches, lzunpack_launches in deltaq_amd/csrc/dq_lzpack_host.h): 14 for a pack call, 15 for an unpack call,
+ * whatever the texts and however many.
+ * Device memory, carved from the cached workspace of the slot the call leases: about 70 bytes per triple and 90 per
+ * text for a pack call, 56 bytes per blob byte and 80 per blob for an unpack call; the host forms add their copies of
+ * the input and of min(cap, the bound) bytes of output.  No chunking and no CPU fallback: DQ_ERR_OOM where that does not
+ * fit.  The _dev_ forms take device pointers on `device`, enqueue on `stream` (NULL = the library's stream) and return
+ * after it has drained.  One stream wait per call.
+ * Out of scope: entropy coding of the two streams, int64 forms, chunking of host-form calls.
+ * dq_lzpack_last_info: shape of the last of these calls on this thread, reset when one starts; `count` entries (7 are
+ * defined, further ones read 0; a NULL array is DQ_ERR_BAD_ARGS): [0] texts with status 0; [1] texts with status -1;
+ * [2] tokens, [3] control bytes and [4] literal bytes of the texts with status 0; [5] kernel launches; [6] stream waits. */
+int64_t dq_lzpack_bound(int64_t z, int32_t count);
+int32_t dq_lzpack_hip_many_i32(const int32_t *phrases, const int64_t *phrase_offsets, int32_t count, int32_t kind,
+                               uint8_t *blobs, int64_t cap, int64_t *blob_offsets, int32_t *status, int32_t device);
+int32_t dq_lzpack_hip_many_dev_i32(const void *d_phrases, const int64_t *phrase_offsets, int32_t count, int32_t kind,
+                                   void *d_blobs, int64_t cap, int64_t *blob_offsets, int32_t *status,
+                                   int32_t device, void *stream);
+int32_t dq_lzunpack_hip_many_i32(const uint8_t *blobs, const int64_t *blob_offsets, int32_t count,
+                                 int32_t *phrases, int64_t cap, int64_t *phrase_offsets,
+                                 int64_t *out_len, int32_t *kind, int32_t *status, int32_t device);
+int32_t dq_lzunpack_hip_many_dev_i32(const void *d_blobs, const int64_t *blob_offsets, int32_t count,
+                                     void *d_phrases, int64_t cap, int64_t *phrase_offsets,
+                                     int64_t *out_len, int32_t *kind, int32_t *status, int32_t device, void *stream);
+int32_t dq_lzpack_last_info(int64_t *info, int32_t count);
 
 /* Device workspace (bytes) a sort of n bytes with index_bytes (4 or 8) wide indices needs,
  * excluding the caller's text and sa buffers: the device entry point's full layout (the reduced one at n = 2^32). */

@@ -83,6 +83,10 @@ PROTOTYPES = {                                               # export -> (restyp
     "dq_lz77_decode_hip_many_dev_i32": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp]),
     "dq_rlz_decode_hip_many_dev_i32": (_i32, [_vp, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp]),
     "dq_lzdecode_last_info": _INFO,
+    "dq_lzpack_bound": (_i64, [_i64, _i32]),
+    "dq_lzpack_hip_many_dev_i32": (_i32, [_vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _i32, _vp]),
+    "dq_lzunpack_hip_many_dev_i32": (_i32, [_vp, _vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "dq_lzpack_last_info": _INFO,
 }
 
 
