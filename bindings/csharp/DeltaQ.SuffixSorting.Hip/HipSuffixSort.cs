@@ -236,6 +236,16 @@ public sealed class HipSuffixSort : ISuffixSort
     private static extern unsafe int dq_lzpack_last_info(long* info, int count);
 
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    private static extern unsafe int dq_lzselect_hip_many_i32(int* len, int* src, long* offsets, int count, int kind, long* oldSizes, int minGain, int* outLen, int* outSrc, int device);
+
+    // (declared for hosts that keep their buffers on the device: device pointers, a hipStream_t or zero)
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern unsafe int dq_lzselect_hip_many_dev_i32(IntPtr dLen, IntPtr dSrc, long* offsets, int count, int kind, long* oldSizes, int minGain, IntPtr dOutLen, IntPtr dOutSrc, int device, IntPtr stream);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    private static extern unsafe int dq_lzselect_last_info(long* info, int count);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
     private static extern int dq_abi_version();
 
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
@@ -1952,6 +1962,100 @@ public sealed class HipSuffixSort : ISuffixSort
             if (rc != 0)
             {
                 throw new InvalidOperationException($"dq_lzpack_last_info failed ({rc})");
+            }
+        }
+
+        return info;
+    }
+
+    /// <summary>
+    /// The match arrays of many texts with every copy dropped that is not worth its DQLZ token, in one native call
+    /// (dq_lzselect_hip_many_i32; include/dq_sufsort.h has the rule): a position keeps (len, src) where the match is
+    /// valid and len - cost >= minGain, and becomes (0, -1), a literal to the parse, otherwise.  kind 0: what Lpf
+    /// returns; kind 1: what MatchStats returns, with oldSizes, the old files' sizes.  The arrays are untrusted.
+    /// </summary>
+    public unsafe (int[] Len, int[] Src)[] LzSelectMany(IReadOnlyList<int[]> len, IReadOnlyList<int[]> src, int kind = 0, IReadOnlyList<long>? oldSizes = null, int minGain = 1)
+    {
+        if (kind != 0 && kind != 1)
+        {
+            throw new ArgumentException("kind must be 0 (LZ77) or 1 (RLZ)");
+        }
+
+        int count = len.Count;
+        if (src.Count != count || (kind == 1 && (oldSizes == null || oldSizes.Count != count)))
+        {
+            throw new ArgumentException("LzSelectMany takes one len array and one src array per text, and for kind 1 one old size");
+        }
+
+        var offsets = new long[count + 1];
+        for (int t = 0; t < count; t++)
+        {
+            if (len[t].Length != src[t].Length)
+            {
+                throw new ArgumentException($"text {t}: len and src must have the same length");
+            }
+
+            offsets[t + 1] = offsets[t] + len[t].Length;
+        }
+
+        long total = offsets[count];
+        var flatLen = new int[Math.Max(1, total)];
+        var flatSrc = new int[Math.Max(1, total)];
+        for (int t = 0; t < count; t++)
+        {
+            len[t].CopyTo(flatLen, offsets[t]);
+            src[t].CopyTo(flatSrc, offsets[t]);
+        }
+
+        var olds = new long[Math.Max(1, count)];
+        for (int t = 0; kind == 1 && t < count; t++)
+        {
+            olds[t] = oldSizes![t];
+        }
+
+        var outLen = new int[Math.Max(1, total)];
+        var outSrc = new int[Math.Max(1, total)];
+        fixed (int* l = flatLen)
+        fixed (int* s = flatSrc)
+        fixed (long* o = offsets)
+        fixed (long* od = olds)
+        fixed (int* ol = outLen)
+        fixed (int* os = outSrc)
+        {
+            int rc = dq_lzselect_hip_many_i32(l, s, o, count, kind, kind == 1 ? od : null, minGain, ol, os, _device);
+            if (rc != 0)
+            {
+                throw new InvalidOperationException($"dq_lzselect_hip_many_i32 failed ({rc}): {Marshal.PtrToStringAnsi(dq_last_error()) ?? string.Empty}");
+            }
+        }
+
+        var result = new (int[], int[])[count];
+        for (int t = 0; t < count; t++)
+        {
+            var a = new int[len[t].Length];
+            var b = new int[len[t].Length];
+            Array.Copy(outLen, offsets[t], a, 0, a.Length);
+            Array.Copy(outSrc, offsets[t], b, 0, b.Length);
+            result[t] = (a, b);
+        }
+
+        return result;
+    }
+
+    /// <summary>
+    /// Shape of the last LzSelectMany on this thread (dq_lzselect_last_info): positions, positions with a valid match,
+    /// kept ones, invalid entries (len != 0 but not valid), the sum of len - cost over the kept ones, kernel launches,
+    /// stream waits.
+    /// </summary>
+    public static unsafe long[] LastLzSelectInfo()
+    {
+        var info = new long[7];
+        fixed (long* p = info)
+        {
+            int rc = dq_lzselect_last_info(p, info.Length);
+            if (rc != 0)
+            {
+                throw new InvalidOperationException($"dq_lzselect_last_info failed ({rc})");
             }
         }
 

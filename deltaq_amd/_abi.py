@@ -72,6 +72,7 @@ EXPORTS = (
     "dq_rlz_decode_hip_many_dev_i32", "dq_lzdecode_last_info",
     "dq_lzpack_bound", "dq_lzpack_hip_many_i32", "dq_lzpack_hip_many_dev_i32", "dq_lzunpack_hip_many_i32",
     "dq_lzunpack_hip_many_dev_i32", "dq_lzpack_last_info",
+    "dq_lzselect_hip_many_i32", "dq_lzselect_hip_many_dev_i32", "dq_lzselect_last_info",
     "dq_bsdiff_search_dev_i32", "dq_bsdiff_search_dev_i64", "dq_bsdiff_search_i32", "dq_bsdiff_search_i64",
     "dq_bsdiff_create", "dq_bsdiff_patch_bound", "dq_bsdiff_scan_i32", "dq_bspatch_apply",
     "dq_bspatch_new_size_many", "dq_bspatch_apply_many", "dq_bspatch_index_apply_many",
@@ -134,6 +135,10 @@ LZDECODE_RECORD = _n("texts_ok", "texts_refused", "linked", "jump_rounds", "laun
 # ... and the record of dq_lzpack_last_info, struct LzPackInfo of deltaq_amd/csrc/dq_lzpack_info.h;
 # tests/test_lzpack_cpu.py checks it.
 LZPACK_RECORD = _n("texts_ok", "texts_refused", "tokens", "ctrl_bytes", "literal_bytes", "launches", "stream_waits")
+
+# ... and the record of dq_lzselect_last_info, struct LzSelectInfo of deltaq_amd/csrc/dq_lzselect_info.h;
+# tests/test_lzselect_cpu.py checks it.
+LZSELECT_RECORD = _n("positions", "valid", "kept", "invalid", "gain", "launches", "stream_waits")
 
 
 class BackendMissingError(RuntimeError):
@@ -289,6 +294,12 @@ def load() -> ctypes.CDLL:
     L.dq_lzunpack_hip_many_dev_i32.argtypes = [vp, vp, i32, vp, i64, vp, vp, vp, vp, i32, vp]
     L.dq_lzpack_last_info.restype = i32
     L.dq_lzpack_last_info.argtypes = [ctypes.POINTER(i64), i32]
+    L.dq_lzselect_hip_many_i32.restype = i32
+    L.dq_lzselect_hip_many_i32.argtypes = [vp, vp, vp, i32, i32, vp, i32, vp, vp, i32]
+    L.dq_lzselect_hip_many_dev_i32.restype = i32
+    L.dq_lzselect_hip_many_dev_i32.argtypes = [vp, vp, vp, i32, i32, vp, i32, vp, vp, i32, vp]
+    L.dq_lzselect_last_info.restype = i32
+    L.dq_lzselect_last_info.argtypes = [ctypes.POINTER(i64), i32]
     L.dq_sufsort_hip_batch_i32.restype = i32
     L.dq_sufsort_hip_batch_i32.argtypes = [i32, vp, vp, vp, i32, vp]
     L.dq_sufsort_hip_many_i32.restype = i32
@@ -531,6 +542,15 @@ def last_lzpack_info() -> dict:
     v = (ctypes.c_int64 * len(LZPACK_RECORD))()
     check(load().dq_lzpack_last_info(v, len(LZPACK_RECORD)))
     return {key: v[i] * scale for i, (key, scale) in enumerate(LZPACK_RECORD)}
+
+
+def last_lzselect_info() -> dict:
+    """Shape of the last dq_lzselect_hip_many_* on this thread (dq_lzselect_last_info): positions, positions with a
+    valid match, kept ones, invalid entries (len != 0 but not valid), the sum of len - cost over the kept ones, kernel
+    launches and stream waits."""
+    v = (ctypes.c_int64 * len(LZSELECT_RECORD))()
+    check(load().dq_lzselect_last_info(v, len(LZSELECT_RECORD)))
+    return {key: v[i] * scale for i, (key, scale) in enumerate(LZSELECT_RECORD)}
 
 
 def last_batch_info() -> dict:

@@ -13,7 +13,9 @@ Five translation units, compiled side by side and linked into one library:
                                             (dq_lz77.h, dq_lz77_host.h), matching statistics and the relative
                                             LZ factorization (dq_rlz.h, dq_rlz_host.h), the decoders of both
                                             kinds of phrases (dq_lzdecode.h, dq_lzdecode_host.h), the DQLZ
-                                            packer and unpacker of phrases (dq_lzpack.h, dq_lzpack_host.h)
+                                            packer and unpacker of phrases (dq_lzpack.h, dq_lzpack_host.h), the
+                                            selection of copies in front of the parse (dq_lzselect.h,
+                                            dq_lzselect_host.h)
     dq_abi.hip                              the C ABI and the batch pipeline (host code only)
 Objects live in deltaq_amd/csrc/obj/ with the compiler's own dependency files, so an edit
 rebuilds only the units that include what changed.

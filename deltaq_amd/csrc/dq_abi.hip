@@ -676,6 +676,25 @@ int32_t dq_lzunpack_hip_many_dev_i32(const void *d_blobs, const int64_t *blob_of
 
 int32_t dq_lzpack_last_info(int64_t *info, int32_t count) { return last_info(t_lzpack_info, info, count, "null info array"); }
 
+int32_t dq_lzselect_hip_many_i32(const int32_t *len, const int32_t *src, const int64_t *offsets, int32_t count, int32_t kind,
+                                 const int64_t *old_sizes, int32_t min_gain, int32_t *out_len, int32_t *out_src, int32_t device)
+{
+    EnvScope scope;
+    t_lzselect_info = {};
+    return lzselect_many(true, len, src, offsets, count, kind, old_sizes, min_gain, out_len, out_src, device, nullptr);
+}
+
+int32_t dq_lzselect_hip_many_dev_i32(const void *d_len, const void *d_src, const int64_t *offsets, int32_t count, int32_t kind,
+                                     const int64_t *old_sizes, int32_t min_gain, void *d_out_len, void *d_out_src, int32_t device,
+                                     void *stream)
+{
+    EnvScope scope;
+    t_lzselect_info = {};
+    return lzselect_many(false, d_len, d_src, offsets, count, kind, old_sizes, min_gain, d_out_len, d_out_src, device, stream);
+}
+
+int32_t dq_lzselect_last_info(int64_t *info, int32_t count) { return last_info(t_lzselect_info, info, count, "null info array"); }
+
 int32_t dq_sufsort_hip_batch_i32(int32_t count, const uint8_t *const *texts, const int64_t *lens,
                                  int32_t *const *sas, int32_t ndev, const int32_t *devs)
 {

@@ -43,6 +43,7 @@
 #include "dq_rlz_info.h"
 #include "dq_lzdecode_info.h"
 #include "dq_lzpack_info.h"
+#include "dq_lzselect_info.h"
 #include "dq_flags.h"
 #include "dq_work_lists.h"
 #include "dq_block_groups.h"
@@ -767,6 +768,12 @@ int lzpack_many(bool host, const void *phrases, const int64_t *phrase_offsets, i
                 int64_t *blob_offsets, int32_t *status, int32_t device, void *stream);
 int lzunpack_many(bool host, const void *blobs, const int64_t *blob_offsets, int32_t count, void *phrases, int64_t cap,
                   int64_t *phrase_offsets, int64_t *out_len, int32_t *kind, int32_t *status, int32_t device, void *stream);
+
+// The copies worth their tokens (dq_lzselect_host.h, in dq_sufcheck.hip): the body of dq_lzselect_hip_many_*.  host: len,
+// src and the outputs are the host's (and stream is not looked at); offsets and old_sizes are the host's in both forms.
+// It fills t_lzselect_info (dq_lzselect_info.h); the entry point resets it.
+int lzselect_many(bool host, const void *len, const void *src, const int64_t *offsets, int32_t count, int32_t kind, const int64_t *old_sizes,
+                  int32_t min_gain, void *out_len, void *out_src, int32_t device, void *stream);
 
 // match search + BSDIFF40 (dq_diff.hip)
 int match_search_dev_i32(const void *d_old, int64_t n, const void *d_sa, const void *d_new, int64_t m, const int64_t *d_scans,

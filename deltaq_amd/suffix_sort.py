@@ -1452,13 +1452,128 @@ class HipSuffixSort:
 
     lzunpack = LzUnpack
 
-    def DeltaCreateMany(self, olds, news):
-        """A DQLZ delta (kind 1) of every ``news[t]`` against ``olds[t]``: a list of ``bytes``, through ``RlzMany`` and
-        ``LzPackMany``.  ``DeltaApplyMany(olds, .)`` turns them back into the new files."""
-        return self.LzPackMany(self.RlzMany(olds, news), None, 1)
+    # -- the copies worth their tokens, between the match arrays and the parse (include/dq_sufsort.h has the rule) -------
+    def LzSelectMany(self, length, src, offsets=None, kind=0, old_sizes=None, min_gain=1):
+        """The match arrays of many texts with every copy dropped that is not worth its DQLZ token, in ONE native call:
+        a position keeps ``(length, src)`` where the match is valid and ``length - cost >= min_gain``, and becomes
+        ``(0, -1)``, a literal to ``LzParseMany``, otherwise.  ``kind``: 0 for what ``LpfMany`` returns, 1 for
+        ``MatchStatsMany`` with ``old_sizes``, the old files' sizes (a host sequence, one per text).  Lists of host int32
+        arrays (``offsets`` left out) give a list of ``(length, src)`` (``dq_lzselect_hip_many_i32``); flat int32
+        arrays -- numpy, or torch GPU tensors -- with the host int64 array ``offsets`` of count + 1 entries give two
+        flat arrays of the same kind, a GPU tensor staying on the device on the current torch stream
+        (``dq_lzselect_hip_many_dev_i32``).  The arrays are untrusted.  ``_abi.last_lzselect_info()`` tells what
+        happened."""
+        if kind not in (0, 1):
+            raise ValueError("kind must be 0 (LZ77) or 1 (RLZ)")
+        if not isinstance(min_gain, (int, np.integer)) or not -(1 << 31) <= min_gain <= INT_MAX:
+            raise ValueError("min_gain must be an int32")
+        device = _is_torch_tensor(length) or _is_torch_tensor(src)
+        listed = isinstance(length, (list, tuple))
+        if listed:
+            if offsets is not None:
+                raise TypeError("a list of arrays brings its own offsets: leave offsets out")
+            lens, srs = list(length), list(src) if isinstance(src, (list, tuple)) else None
+            if srs is None or any(_is_torch_tensor(a) for a in (*lens, *srs)):
+                raise TypeError(MIXED_LZ_MESSAGE)
+            if len(lens) != len(srs):
+                raise ValueError("LzSelectMany takes one length array and one src array per text")
+            for name, group in (("length", lens), ("src", srs)):
+                if any(not isinstance(a, np.ndarray) or a.dtype != np.int32 or a.ndim != 1 for a in group):
+                    raise TypeError(f"every {name} array must be a 1-D numpy int32 array")
+            if any(a.size != b.size for a, b in zip(lens, srs)):
+                raise ValueError(LENGTH_MISMATCH_MESSAGE)
+            off = np.zeros(len(lens) + 1, dtype=np.int64)
+            if lens:
+                np.cumsum([a.size for a in lens], out=off[1:])
+            flat_len = np.concatenate(lens) if off[-1] else np.zeros(0, np.int32)
+            flat_src = np.concatenate(srs) if off[-1] else np.zeros(0, np.int32)
+        else:
+            if offsets is None or _is_torch_tensor(offsets):
+                raise TypeError("offsets must be a host int64 array of count + 1 entries")
+            off = np.ascontiguousarray(offsets, dtype=np.int64)
+            if off.ndim != 1 or off.size < 1:
+                raise TypeError("offsets must be a host int64 array of count + 1 entries")
+            if device:
+                import torch
 
-    def DeltaCreate(self, old, new) -> bytes:
-        return self.DeltaCreateMany([old], [new])[0]
+                if not (_is_torch_tensor(length) and _is_torch_tensor(src)):
+                    raise TypeError(MIXED_LZ_MESSAGE)
+                for name, a in (("length", length), ("src", src)):
+                    if a.dtype != torch.int32 or a.dim() != 1 or not a.is_contiguous():
+                        raise TypeError(f"device {name} must be a contiguous 1-D int32 tensor")
+                    if not a.is_cuda:
+                        raise TypeError("torch tensors must live on the GPU; pass host data as bytes/numpy")
+                if length.device != src.device:
+                    raise TypeError("length and src must live on one device")
+                flat_len, flat_src = length, src
+            else:
+                for name, a in (("length", length), ("src", src)):
+                    if not isinstance(a, np.ndarray) or a.dtype != np.int32 or a.ndim != 1:
+                        raise TypeError(f"{name} must be a 1-D numpy int32 array")
+                flat_len, flat_src = np.ascontiguousarray(length), np.ascontiguousarray(src)
+            sizes = (flat_len.numel(), flat_src.numel()) if device else (flat_len.size, flat_src.size)
+            if off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != sizes[0] or sizes[0] != sizes[1]:
+                raise ValueError("offsets must start at 0, never decrease and end at the number of positions of both arrays")
+        count, total = off.size - 1, int(off[-1])
+        if total > INT_MAX:
+            raise ValueError("LzSelectMany has 32-bit positions: the texts together must be shorter than 2^31 bytes")
+        olds = None
+        if kind == 1:
+            if old_sizes is None or _is_torch_tensor(old_sizes):
+                raise TypeError("kind 1 needs old_sizes, a host sequence of one size per text")
+            olds = np.ascontiguousarray(old_sizes, dtype=np.int64)
+            if olds.ndim != 1 or olds.size != count:
+                raise ValueError("kind 1 needs old_sizes, a host sequence of one size per text")
+            if olds.size and (olds.min() < 0 or olds.max() > INT_MAX):
+                raise ValueError("an old size outside [0, 2^31-1]")
+        if olds is not None and olds.size == 0:
+            olds = np.zeros(1, dtype=np.int64)                   # (a buffer of no entries has no address)
+        old_ptr = olds.ctypes.data if olds is not None else None
+        if device:
+            import torch
+
+            out_len, out_src = torch.empty_like(flat_len), torch.empty_like(flat_src)
+            dev, stream = _device_and_stream(flat_len)
+            _abi.check(self._lib.dq_lzselect_hip_many_dev_i32(flat_len.data_ptr() if total else None, flat_src.data_ptr() if total else None,
+                                                              off.ctypes.data, count, kind, old_ptr, int(min_gain),
+                                                              out_len.data_ptr() if total else None, out_src.data_ptr() if total else None,
+                                                              dev, stream))
+            return out_len, out_src
+        out_len, out_src = np.empty(total, dtype=np.int32), np.empty(total, dtype=np.int32)
+        _abi.check(self._lib.dq_lzselect_hip_many_i32(flat_len.ctypes.data if total else None, flat_src.ctypes.data if total else None,
+                                                      off.ctypes.data, count, kind, old_ptr, int(min_gain),
+                                                      out_len.ctypes.data if total else None, out_src.ctypes.data if total else None,
+                                                      self.device))
+        if not listed:
+            return out_len, out_src
+        return [(out_len[off[t]:off[t + 1]], out_src[off[t]:off[t + 1]]) for t in range(count)]
+
+    lzselect_many = LzSelectMany
+
+    def LzSelect(self, length, src, kind=0, old_size=None, min_gain=1):
+        """One text through ``LzSelectMany``: ``(length, src)`` as host arrays or as GPU tensors, like the arguments."""
+        olds = None if old_size is None else [old_size]
+        if _is_torch_tensor(length) or _is_torch_tensor(src):
+            n = length.numel() if _is_torch_tensor(length) else 0
+            return self.LzSelectMany(length, src, np.array([0, n], dtype=np.int64), kind, olds, min_gain)
+        return self.LzSelectMany([length], [src], None, kind, olds, min_gain)[0]
+
+    lzselect = LzSelect
+
+    def DeltaCreateMany(self, olds, news, select=False):
+        """A DQLZ delta (kind 1) of every ``news[t]`` against ``olds[t]``: a list of ``bytes``, through ``RlzMany`` and
+        ``LzPackMany``.  ``DeltaApplyMany(olds, .)`` turns them back into the new files.  ``select=True`` drops the
+        copies that are not worth their tokens: ``MatchStatsMany``, ``LzSelectMany`` (kind 1), ``LzParseMany``,
+        ``LzPackMany``; the blobs are ordinary ones."""
+        if not select:
+            return self.LzPackMany(self.RlzMany(olds, news), None, 1)
+        olds, news = [_as_text(o) for o in olds], [_as_text(w) for w in news]
+        stats = self.MatchStatsMany(olds, news)
+        chosen = self.LzSelectMany([a for a, _ in stats], [b for _, b in stats], None, 1, [o.size for o in olds])
+        return self.LzPackMany(self.LzParseMany(news, [a for a, _ in chosen], [b for _, b in chosen]), None, 1)
+
+    def DeltaCreate(self, old, new, select=False) -> bytes:
+        return self.DeltaCreateMany([old], [new], select)[0]
 
     def DeltaApplyMany(self, olds, deltas):
         """The new files of ``DeltaCreateMany``'s deltas, a list of ``bytes``, through ``LzUnpackMany`` and
@@ -1475,9 +1590,42 @@ class HipSuffixSort:
     def DeltaApply(self, old, delta) -> bytes:
         return self.DeltaApplyMany([old], [delta])[0]
 
-    def Compress(self, text) -> bytes:
-        """The text as a DQLZ blob of kind 0, through ``Lz77Many`` and ``LzPackMany``."""
+    def Compress(self, text, select=False) -> bytes:
+        """The text as a DQLZ blob of kind 0, through ``Lz77Many`` and ``LzPackMany``; ``select=True``: through
+        ``CompressMany``."""
+        if select:
+            return self.CompressMany([text], True)[0]
         return self.LzPackMany(self.Lz77Many([text]), None, 0)[0]
+
+    def CompressMany(self, texts, select=True):
+        """Many texts as DQLZ blobs of kind 0, a list of ``bytes``: ``SortMany``, ``LcpMany``, ``LpfMany``,
+        ``LzSelectMany`` (the copies worth their tokens), ``LzParseMany``, ``LzPackMany`` -- one native call each for
+        all texts.  With ``min_gain`` 1 a blob has at most ``35 + n + n // 128`` bytes.  ``select=False``: the greedy
+        parse, ``Lz77Many`` and ``LzPackMany``.  ``DecompressMany`` turns the blobs back into the texts."""
+        arrs = [_as_text(t) for t in texts]
+        if any(a.ndim != 1 for a in arrs):
+            raise TypeError("every text must be one-dimensional")
+        if not select:
+            return self.LzPackMany(self.Lz77Many(arrs), None, 0)
+        if sum(a.size for a in arrs) > INT_MAX:
+            raise ValueError("CompressMany has 32-bit indices: the texts together must be shorter than 2^31 bytes")
+        if any(a.size for a in arrs):
+            suffixes = self.SortMany(arrs)
+            matches = self.LpfMany(suffixes, self.LcpMany(arrs, suffixes))
+        else:
+            matches = [(np.zeros(0, np.int32), np.zeros(0, np.int32)) for _ in arrs]
+        chosen = self.LzSelectMany([a for a, _ in matches], [b for _, b in matches])
+        return self.LzPackMany(self.LzParseMany(arrs, [a for a, _ in chosen], [b for _, b in chosen]), None, 0)
+
+    def DecompressMany(self, blobs):
+        """The texts of ``CompressMany``'s blobs, a list of ``bytes``, through ``LzUnpackMany`` and ``Lz77DecodeMany``; a
+        blob of kind 1 or a malformed one raises ``ValueError``."""
+        P, poff, sizes, kinds = self.LzUnpackMany(list(blobs))
+        if (kinds != 0).any():
+            raise ValueError(f"blob {int(np.flatnonzero(kinds != 0)[0])}: not an LZ77 (kind 0) blob")
+        return self.Lz77DecodeMany(P, poff, sizes)
+
+    compress_many, decompress_many = CompressMany, DecompressMany
 
     def Decompress(self, blob) -> bytes:
         """The text of ``Compress``'s blob, through ``LzUnpackMany`` and ``Lz77DecodeMany``; a blob of kind 1 or a

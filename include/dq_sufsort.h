@@ -1105,6 +1105,60 @@ int32_t dq_lzunpack_hip_many_dev_i32(const void *d_blobs, const int64_t *blob_of
                                      int64_t *out_len, int32_t *kind, int32_t *status, int32_t device, void *stream);
 int32_t dq_lzpack_last_info(int64_t *info, int32_t count);
 
+/* ---- the copies worth their tokens: a selection between the match arrays and the parse ------------------------------
+ * The greedy parse makes a copy of every match of one byte and more, and a copy is a DQLZ token of three bytes at least:
+ * its blobs are often larger than their texts.  This stage stands between the match arrays -- lpf / src of dq_lpf_hip_*
+ * (kind 0), len / src of dq_mstat_hip_* (kind 1) -- and dq_lzparse_hip_*, which takes any finished (len, src) pair: a
+ * position keeps its match only where the match is worth its token.  tests/lzselect_model.py is the rule in Python.
+ * Layout: dq_lzparse_hip_many_*'s.  Text t's positions are [offsets[t], offsets[t + 1]) of len, src and the outputs;
+ * position i counts from the text's own start, n_t = offsets[t + 1] - offsets[t], L = len[i], s = src[i].
+ * vb(v) = the bytes of the LEB128 varint of v: 1 below 2^7, 2 below 2^14, 3 below 2^21, 4 below 2^28, else 5.
+ *   valid, kind 0:  1 <= L <= n_t - i  and  0 <= s < i
+ *   valid, kind 1:  1 <= L <= n_t - i,  0 <= s  and  s + L <= old_sizes[t]  (in 64 bits)
+ *   cost,  kind 0:  1 + vb(L) + vb(i - s - 1): the token's three varints, the lit_run at its minimum
+ *   cost,  kind 1:  1 + vb(L) + vb(2 * old_sizes[t]): a kind-1 code depends on the copy before it, which a position cannot
+ *                   know; this is the largest code a step inside old can take.  A stated choice, not a measured one: it
+ *                   is what turns the junk copies between two copies that keep pace into literals.
+ *   keep  iff  valid  and  L - cost >= min_gain:  out_len[i] = L, out_src[i] = s;  otherwise out_len[i] = 0, out_src[i] = -1.
+ * The output is safe for the parse and the decoders whatever the input held: the arrays are untrusted, and a value is
+ * compared, never used as an address.  min_gain is any int32: with INT32_MIN the stage only sanitises, and on true
+ * arrays parse(select(x)) is then exactly the greedy triples.
+ * The size bound.  For min_gain >= 1 and kind 0 the DQLZ blob of the parse of the selected arrays of a text of n bytes has
+ * at most 35 + n + floor(n / 128) bytes.  Proof: let the parse have copies of lengths L_1 .. L_k and R literals, n = sum
+ * L_j + R.  A kept copy has L - 1 - vb(L) - vb(code) >= 1, and the parse emits it with exactly that L (valid: it ends
+ * inside the text) and that code (start - third - 1), so vb(L_j) + vb(code_j) <= L_j - 2.  A lit_run varint has
+ * vb(run) <= 1 + floor(run / 128).  The tokens of the copies therefore take at most sum (L_j - 1) + floor(R / 128) bytes,
+ * the final token at most 3 + its share of floor(R / 128), the literals R, the header 32: at most
+ * 32 + 3 + (n - R) - k + R + floor(R / 128) <= 35 + n + floor(n / 128).  For kind 1 the same bound, with the new file's
+ * bytes for n, held on every model input tried; that is an observation, not a proof (a code may exceed the cost's).
+ * offsets[count + 1] and old_sizes[count] are HOST pointers in both forms, judged on the host and uploaded with the call;
+ * nothing is fetched first.  old_sizes is kind 1's alone: kind 0 ignores it, and it may be NULL.  A one-text call is
+ * count == 1.  out_len == len together with out_src == src is allowed (in place); any other overlap is undefined.
+ *   negative count; a NULL host array; a NULL buffer where there is a position; offsets[0] != 0; decreasing offsets;
+ *   kind not 0 or 1; kind 1 without old_sizes or with an entry outside [0, 2^31-1]                      DQ_ERR_BAD_ARGS
+ *   more than 2^31-1 positions                                                                          DQ_ERR_TOO_LARGE
+ * -- all decided before a device is looked for, and the outputs stay untouched.  count == 0, or a call without a
+ * position, returns DQ_OK without a device.
+ * ONE launch, flat over the call's positions (deltaq_amd/csrc/dq_lzselect.h): four positions a thread in tiles of 1024,
+ * 16-byte loads and stores where the four arrays are 16-byte aligned, scalar ones otherwise; a wave bisects the offsets
+ * once for its two ends, a thread only between them; a one-text call looks nothing up.  The counters reach device
+ * memory once per workgroup.  Scratch, from the cached workspace of the slot the call leases: the uploaded offsets and
+ * sizes and a 256-byte line of counters; the host form adds its copies of the two arrays (the kernel runs in place on
+ * them).  The _dev_ form takes device pointers on `device`, enqueues on `stream` (NULL = the library's stream) and
+ * returns after it has drained.  One stream wait per call.
+ * Out of scope: a lazy rule (a literal at i where i + 1 gains more), entropy coding, int64 forms.
+ * dq_lzselect_last_info: shape of the last of these calls on this thread, reset when one starts; `count` entries (7 are
+ * defined, further ones read 0; a NULL array is DQ_ERR_BAD_ARGS): [0] positions; [1] positions with a valid match;
+ * [2] kept; [3] invalid entries (len != 0 but not valid); [4] the sum of L - cost over the kept ones; [5] kernel
+ * launches; [6] stream waits. */
+int32_t dq_lzselect_hip_many_i32(const int32_t *len, const int32_t *src, const int64_t *offsets, int32_t count,
+                                 int32_t kind, const int64_t *old_sizes, int32_t min_gain,
+                                 int32_t *out_len, int32_t *out_src, int32_t device);
+int32_t dq_lzselect_hip_many_dev_i32(const void *d_len, const void *d_src, const int64_t *offsets, int32_t count,
+                                     int32_t kind, const int64_t *old_sizes, int32_t min_gain,
+                                     void *d_out_len, void *d_out_src, int32_t device, void *stream);
+int32_t dq_lzselect_last_info(int64_t *info, int32_t count);
+
 /* Device workspace (bytes) a sort of n bytes with index_bytes (4 or 8) wide indices needs,
  * excluding the caller's text and sa buffers: the device entry point's full layout (the reduced one at n = 2^32). */
 int64_t dq_sufsort_hip_workspace_bytes(int64_t n, int32_t index_bytes);

@@ -87,6 +87,8 @@ PROTOTYPES = {                                               # export -> (restyp
     "dq_lzpack_hip_many_dev_i32": (_i32, [_vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _i32, _vp]),
     "dq_lzunpack_hip_many_dev_i32": (_i32, [_vp, _vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _vp]),
     "dq_lzpack_last_info": _INFO,
+    "dq_lzselect_hip_many_dev_i32": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _vp]),
+    "dq_lzselect_last_info": _INFO,
 }
 
 
