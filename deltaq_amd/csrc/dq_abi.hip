@@ -244,6 +244,20 @@ int32_t lzdecode_entry(Call call)
     }
 }
 
+// an entry point of dq_lpf_hip_* / dq_lz77_hip_* (t_lz77_info) or dq_mstat_hip_* / dq_rlz_hip_* / dq_lzparse_hip_*
+// (t_rlz_info): the many forms hold the offsets, and the host forms phrase_offsets' staging, in vectors
+template <typename Info, typename Call>
+int32_t lz_entry(Info &record, const char *oom, Call call)
+{
+    EnvScope scope;
+    record = {};
+    try {
+        return call();
+    } catch (const std::bad_alloc &) {
+        return fail(DQ_ERR_OOM, oom);
+    }
+}
+
 // an entry point of dq_lzpack_hip_many_* / dq_lzunpack_hip_many_*: as lzdecode_entry, with the packer's record
 template <typename Call>
 int32_t lzpack_entry(Call call)
@@ -404,179 +418,157 @@ int32_t dq_lcp_last_info(int64_t *info, int32_t count) { return last_info(t_lcp_
 
 int32_t dq_lpf_hip_i32(const int32_t *sa, const int32_t *lcp, int64_t n, int32_t *lpf, int32_t *src, int32_t device)
 {
-    EnvScope scope;
-    t_lz77_info = {};
-    return lpf_host(sa, lcp, n, lpf, src, device);
+    return lz_entry(t_lz77_info, "lpf: host allocation failed", [&] { return lpf_one(true, sa, lcp, n, lpf, src, device, nullptr); });
 }
 
 int32_t dq_lpf_hip_dev_i32(const void *d_sa, const void *d_lcp, int64_t n, void *d_lpf, void *d_src, int32_t device, void *stream)
 {
-    EnvScope scope;
-    t_lz77_info = {};
-    return lpf_dev(d_sa, d_lcp, n, d_lpf, d_src, device, stream);
+    return lz_entry(t_lz77_info, "lpf: host allocation failed", [&] { return lpf_one(false, d_sa, d_lcp, n, d_lpf, d_src, device, stream); });
 }
 
 int32_t dq_lz77_hip_i32(const uint8_t *text, int64_t n, const int32_t *sa, const int32_t *lcp, int32_t *phrases, int64_t cap,
                         int64_t *count, int32_t device)
 {
-    EnvScope scope;
-    t_lz77_info = {};
-    return lz77_host(text, n, sa, lcp, phrases, cap, count, device);
+    return lz_entry(t_lz77_info, "lz77: host allocation failed", [&] {
+        return lz77_one(true, text, n, sa, lcp, phrases, cap, count, device, nullptr);
+    });
 }
 
 int32_t dq_lz77_hip_dev_i32(const void *d_text, int64_t n, const void *d_sa, const void *d_lcp, void *d_phrases, int64_t cap,
                             int64_t *count, int32_t device, void *stream)
 {
-    EnvScope scope;
-    t_lz77_info = {};
-    return lz77_dev(d_text, n, d_sa, d_lcp, d_phrases, cap, count, device, stream);
+    return lz_entry(t_lz77_info, "lz77: host allocation failed", [&] {
+        return lz77_one(false, d_text, n, d_sa, d_lcp, d_phrases, cap, count, device, stream);
+    });
 }
 
-// (the many forms hold the offsets, and the host forms phrase_offsets' staging, in vectors: nothing may propagate
-// through the C ABI)
 int32_t dq_lpf_hip_many_i32(const int64_t *offsets, int32_t count, const int32_t *sas, const int32_t *lcps, int32_t *lpf,
                             int32_t *src, int32_t device)
 {
-    EnvScope scope;
-    t_lz77_info = {};
-    return lpf_many_host(offsets, count, sas, lcps, lpf, src, device);
+    return lz_entry(t_lz77_info, "lpf many: host allocation failed", [&] {
+        return lpf_many(true, offsets, count, sas, lcps, lpf, src, device, nullptr);
+    });
 }
 
 int32_t dq_lpf_hip_many_dev_i32(const void *d_offsets, int32_t count, const void *d_sas, const void *d_lcps, void *d_lpf,
                                 void *d_src, int32_t device, void *stream)
 {
-    EnvScope scope;
-    t_lz77_info = {};
-    try {
-        return lpf_many_dev(d_offsets, count, d_sas, d_lcps, d_lpf, d_src, device, stream);
-    } catch (const std::bad_alloc &) {
-        return fail(DQ_ERR_OOM, "lpf many: host allocation failed");
-    }
+    return lz_entry(t_lz77_info, "lpf many: host allocation failed", [&] {
+        return lpf_many(false, d_offsets, count, d_sas, d_lcps, d_lpf, d_src, device, stream);
+    });
 }
 
 int32_t dq_lz77_hip_many_i32(const uint8_t *texts, const int64_t *offsets, int32_t count, const int32_t *sas,
                              const int32_t *lcps, int32_t *phrases, int64_t cap, int64_t *phrase_offsets, int32_t device)
 {
-    EnvScope scope;
-    t_lz77_info = {};
-    try {
-        return lz77_many_host(texts, offsets, count, sas, lcps, phrases, cap, phrase_offsets, device);
-    } catch (const std::bad_alloc &) {
-        return fail(DQ_ERR_OOM, "lz77 many: host allocation failed");
-    }
+    return lz_entry(t_lz77_info, "lz77 many: host allocation failed", [&] {
+        return lz77_many(true, texts, offsets, count, sas, lcps, phrases, cap, phrase_offsets, device, nullptr);
+    });
 }
 
 int32_t dq_lz77_hip_many_dev_i32(const void *d_texts, const void *d_offsets, int32_t count, const void *d_sas,
                                  const void *d_lcps, void *d_phrases, int64_t cap, int64_t *phrase_offsets,
                                  int32_t device, void *stream)
 {
-    EnvScope scope;
-    t_lz77_info = {};
-    try {
-        return lz77_many_dev(d_texts, d_offsets, count, d_sas, d_lcps, d_phrases, cap, phrase_offsets, device, stream);
-    } catch (const std::bad_alloc &) {
-        return fail(DQ_ERR_OOM, "lz77 many: host allocation failed");
-    }
+    return lz_entry(t_lz77_info, "lz77 many: host allocation failed", [&] {
+        return lz77_many(false, d_texts, d_offsets, count, d_sas, d_lcps, d_phrases, cap, phrase_offsets, device, stream);
+    });
 }
 
 int32_t dq_lz77_last_info(int64_t *info, int32_t count) { return last_info(t_lz77_info, info, count, "null info array"); }
 
 int32_t dq_mstat_hip_i32(const int32_t *sa, const int32_t *lcp, int64_t m, int64_t n, int32_t *len, int32_t *src, int32_t device)
 {
-    EnvScope scope;
-    t_rlz_info = {};
-    return mstat_host(sa, lcp, m, n, len, src, device);
+    return lz_entry(t_rlz_info, "mstat: host allocation failed", [&] { return mstat_one(true, sa, lcp, m, n, len, src, device, nullptr); });
 }
 
 int32_t dq_mstat_hip_dev_i32(const void *d_sa, const void *d_lcp, int64_t m, int64_t n, void *d_len, void *d_src, int32_t device,
                              void *stream)
 {
-    EnvScope scope;
-    t_rlz_info = {};
-    return mstat_dev(d_sa, d_lcp, m, n, d_len, d_src, device, stream);
+    return lz_entry(t_rlz_info, "mstat: host allocation failed", [&] { return mstat_one(false, d_sa, d_lcp, m, n, d_len, d_src, device, stream); });
 }
 
 int32_t dq_rlz_hip_i32(const uint8_t *new_data, int64_t m, int64_t n, const int32_t *sa, const int32_t *lcp, int32_t *phrases,
                        int64_t cap, int64_t *count, int32_t device)
 {
-    EnvScope scope;
-    t_rlz_info = {};
-    return rlz_host(new_data, m, n, sa, lcp, phrases, cap, count, device);
+    return lz_entry(t_rlz_info, "rlz: host allocation failed", [&] {
+        return rlz_one(true, new_data, m, n, sa, lcp, phrases, cap, count, device, nullptr);
+    });
 }
 
 int32_t dq_rlz_hip_dev_i32(const void *d_new, int64_t m, int64_t n, const void *d_sa, const void *d_lcp, void *d_phrases, int64_t cap,
                            int64_t *count, int32_t device, void *stream)
 {
-    EnvScope scope;
-    t_rlz_info = {};
-    return rlz_dev(d_new, m, n, d_sa, d_lcp, d_phrases, cap, count, device, stream);
+    return lz_entry(t_rlz_info, "rlz: host allocation failed", [&] {
+        return rlz_one(false, d_new, m, n, d_sa, d_lcp, d_phrases, cap, count, device, stream);
+    });
 }
 
 int32_t dq_lzparse_hip_i32(const uint8_t *text, int64_t n, const int32_t *len, const int32_t *src, int32_t *phrases, int64_t cap,
                            int64_t *count, int32_t device)
 {
-    EnvScope scope;
-    t_rlz_info = {};
-    return lzparse_host(text, n, len, src, phrases, cap, count, device);
+    return lz_entry(t_rlz_info, "lzparse: host allocation failed", [&] {
+        return lzparse_one(true, text, n, len, src, phrases, cap, count, device, nullptr);
+    });
 }
 
 int32_t dq_lzparse_hip_dev_i32(const void *d_text, int64_t n, const void *d_len, const void *d_src, void *d_phrases, int64_t cap,
                                int64_t *count, int32_t device, void *stream)
 {
-    EnvScope scope;
-    t_rlz_info = {};
-    return lzparse_dev(d_text, n, d_len, d_src, d_phrases, cap, count, device, stream);
+    return lz_entry(t_rlz_info, "lzparse: host allocation failed", [&] {
+        return lzparse_one(false, d_text, n, d_len, d_src, d_phrases, cap, count, device, stream);
+    });
 }
 
 int32_t dq_mstat_hip_many_i32(const int64_t *offsets, const int64_t *new_offsets, int32_t count, const int32_t *sas,
                               const int32_t *lcps, int32_t *len, int32_t *src, int32_t device)
 {
-    EnvScope scope;
-    t_rlz_info = {};
-    return mstat_many_host(offsets, new_offsets, count, sas, lcps, len, src, device);
+    return lz_entry(t_rlz_info, "mstat: host allocation failed", [&] {
+        return mstat_many(true, offsets, new_offsets, count, sas, lcps, len, src, device, nullptr);
+    });
 }
 
 int32_t dq_mstat_hip_many_dev_i32(const void *d_offsets, const void *d_new_offsets, int32_t count, const void *d_sas,
                                   const void *d_lcps, void *d_len, void *d_src, int32_t device, void *stream)
 {
-    EnvScope scope;
-    t_rlz_info = {};
-    return mstat_many_dev(d_offsets, d_new_offsets, count, d_sas, d_lcps, d_len, d_src, device, stream);
+    return lz_entry(t_rlz_info, "mstat: host allocation failed", [&] {
+        return mstat_many(false, d_offsets, d_new_offsets, count, d_sas, d_lcps, d_len, d_src, device, stream);
+    });
 }
 
 int32_t dq_rlz_hip_many_i32(const uint8_t *cats, const int64_t *offsets, const int64_t *new_offsets, int32_t count,
                             const int32_t *sas, const int32_t *lcps, int32_t *phrases, int64_t cap, int64_t *phrase_offsets,
                             int32_t device)
 {
-    EnvScope scope;
-    t_rlz_info = {};
-    return rlz_many_host(cats, offsets, new_offsets, count, sas, lcps, phrases, cap, phrase_offsets, device);
+    return lz_entry(t_rlz_info, "rlz: host allocation failed", [&] {
+        return rlz_many(true, cats, offsets, new_offsets, count, sas, lcps, phrases, cap, phrase_offsets, device, nullptr);
+    });
 }
 
 int32_t dq_rlz_hip_many_dev_i32(const void *d_cats, const void *d_offsets, const void *d_new_offsets, int32_t count,
                                 const void *d_sas, const void *d_lcps, void *d_phrases, int64_t cap, int64_t *phrase_offsets,
                                 int32_t device, void *stream)
 {
-    EnvScope scope;
-    t_rlz_info = {};
-    return rlz_many_dev(d_cats, d_offsets, d_new_offsets, count, d_sas, d_lcps, d_phrases, cap, phrase_offsets, device, stream);
+    return lz_entry(t_rlz_info, "rlz: host allocation failed", [&] {
+        return rlz_many(false, d_cats, d_offsets, d_new_offsets, count, d_sas, d_lcps, d_phrases, cap, phrase_offsets, device, stream);
+    });
 }
 
 int32_t dq_lzparse_hip_many_i32(const uint8_t *texts, const int64_t *offsets, int32_t count, const int32_t *len,
                                 const int32_t *src, int32_t *phrases, int64_t cap, int64_t *phrase_offsets, int32_t device)
 {
-    EnvScope scope;
-    t_rlz_info = {};
-    return lzparse_many_host(texts, offsets, count, len, src, phrases, cap, phrase_offsets, device);
+    return lz_entry(t_rlz_info, "lzparse: host allocation failed", [&] {
+        return lzparse_many(true, texts, offsets, count, len, src, phrases, cap, phrase_offsets, device, nullptr);
+    });
 }
 
 int32_t dq_lzparse_hip_many_dev_i32(const void *d_texts, const void *d_offsets, int32_t count, const void *d_len,
                                     const void *d_src, void *d_phrases, int64_t cap, int64_t *phrase_offsets, int32_t device,
                                     void *stream)
 {
-    EnvScope scope;
-    t_rlz_info = {};
-    return lzparse_many_dev(d_texts, d_offsets, count, d_len, d_src, d_phrases, cap, phrase_offsets, device, stream);
+    return lz_entry(t_rlz_info, "lzparse: host allocation failed", [&] {
+        return lzparse_many(false, d_texts, d_offsets, count, d_len, d_src, d_phrases, cap, phrase_offsets, device, stream);
+    });
 }
 
 int32_t dq_rlz_last_info(int64_t *info, int32_t count) { return last_info(t_rlz_info, info, count, "null info array"); }

@@ -698,29 +698,54 @@ __global__ __launch_bounds__(kBlock) void lpf_long_many_kernel(LpfLevels L, int6
 }
 
 // ---------------------------------------------------------------------------------------------- the parse
-// next[] of tile t0 .. into LDS: i + clamp(lpf[i], 1, n - i) for the positions of the text, n for the rest of the tile
-__device__ __forceinline__ void lz_load_next(const int32_t *__restrict__ lpf, int64_t n, int64_t t0, int32_t *s_next)
+// The tile kernels -- exit, mark, emit -- are one body each, templated on kMany as lpf_tile_body is; the walk is not (one
+// lane, or a lane per text).
+//
+// kMany: texts back to back, text t at positions [off[t], off[t + 1]) of lpf / src (dq_lz77_hip_many_*,
+// dq_lzparse_hip_many_*; the new files of dq_rlz_hip_many_*).  Every step is clamped to its own text's end, so every text
+// start is a phrase start and next[] over the concatenation is one increasing chain through all of them: the bodies are
+// the one-text bodies with the text's end in the clamp and its start taken off the triple.  The walk is one lane per text
+// from its own start to its own end (lz_walk_many_kernel); a tile's entry is the minimum over what the lanes report --
+// the chain from there passes every later text start of the tile.  lz_offsets_kernel turns the scanned tile counts and
+// the bitmap into the phrases before each text.  (LzTexts and lz_text_of: above, with the LPF array of many texts.)
+
+// next[] of tile t0 .. into LDS: i + clamp(lpf[i], 1, end - i) for the positions below n, n for the rest of the tile;
+// end is n, kMany: the end of i's text
+template <bool kMany>
+__device__ __forceinline__ void lz_load_next(const int32_t *__restrict__ lpf, const LzTexts &tx, int64_t n, int64_t t0, int32_t *s_next)
 {
+    int32_t lo = 0, hi = 0;                                                  // kMany: the texts of the tile's two ends
+    if constexpr (kMany) {
+        const int64_t last = t0 + kLzTile < n ? t0 + kLzTile - 1 : n - 1;   // (t0 < n: the tile holds a position)
+        lo = lz_text_of(tx.off, 0, tx.count - 1, t0);
+        hi = lz_text_of(tx.off, lo, tx.count - 1, last);
+    }
 #pragma unroll 4
     for (int k = 0; k < kLzPer; ++k) {
         const int at = k * kBlock + (int)threadIdx.x;
         const int64_t i = t0 + at;
         int64_t nx = n;
         if (i < n) {
+            int64_t end = n;
+            if constexpr (kMany) {
+                end = tx.off[lz_text_of(tx.off, lo, hi, i) + 1];
+                end = end > n ? n : (end <= i ? i + 1 : end);                // (the host checked the layout)
+            }
             const int64_t f = lpf[i];
-            nx = i + (f < 1 ? 1 : (f > n - i ? n - i : f));
+            nx = i + (f < 1 ? 1 : (f > end - i ? end - i : f));
         }
         s_next[at] = (int32_t)nx;
     }
 }
 
-__global__ __launch_bounds__(kBlock) void lz_exit_kernel(const int32_t *__restrict__ lpf, int64_t n, int32_t *__restrict__ exits)
+template <bool kMany>
+__device__ __forceinline__ void lz_exit_body(const int32_t *__restrict__ lpf, const LzTexts &tx, int64_t n, int32_t *__restrict__ exits)
 {
     __shared__ int32_t s_next[kLzTile];
     const int64_t t0 = (int64_t)blockIdx.x * kLzTile;
     const int64_t e64 = t0 + kLzTile < n ? t0 + kLzTile : n;
     const int32_t e = (int32_t)e64, b0 = (int32_t)t0;
-    lz_load_next(lpf, n, t0, s_next);
+    lz_load_next<kMany>(lpf, tx, n, t0, s_next);
     __syncthreads();
     // synchronous pointer jumping: after round k an entry is 2^k hops ahead or out of the tile; reads, barrier, writes
     for (int round = 0; round < kLzJumpRounds; ++round) {
@@ -745,6 +770,17 @@ __global__ __launch_bounds__(kBlock) void lz_exit_kernel(const int32_t *__restri
     }
 }
 
+__global__ __launch_bounds__(kBlock) void lz_exit_kernel(const int32_t *__restrict__ lpf, int64_t n, int32_t *__restrict__ exits)
+{
+    lz_exit_body<false>(lpf, LzTexts{}, n, exits);
+}
+
+__global__ __launch_bounds__(kBlock) void lz_exit_many_kernel(const int32_t *__restrict__ lpf, LzTexts tx, int64_t n,
+                                                              int32_t *__restrict__ exits)
+{
+    lz_exit_body<true>(lpf, tx, n, exits);
+}
+
 // One lane.  entry[] was filled with -1.  Every hop leaves its tile (forced, whatever exits[] holds), so there are at
 // most lz_tiles(n) hops.
 __global__ __launch_bounds__(kWave) void lz_walk_kernel(const int32_t *__restrict__ exits, int64_t n, int32_t *__restrict__ entry,
@@ -765,8 +801,33 @@ __global__ __launch_bounds__(kWave) void lz_walk_kernel(const int32_t *__restric
     ctr->hops = hops;
 }
 
-__global__ __launch_bounds__(kBlock) void lz_mark_kernel(const int32_t *__restrict__ lpf, int64_t n, const int32_t *__restrict__ entry,
-                                                         uint32_t *__restrict__ bits, uint32_t *__restrict__ tile_count)
+// One lane per text.  entry[] was filled with -1, which as an unsigned word is above every position: a tile's entry is
+// the least position a lane enters it at.  Every hop leaves its tile (forced) and no lane leaves its text, so a lane makes
+// at most one hop per tile its text touches; the hops of all lanes are summed.
+__global__ __launch_bounds__(kBlock) void lz_walk_many_kernel(const int32_t *__restrict__ exits, LzTexts tx, int64_t n,
+                                                              int32_t *__restrict__ entry, LzCounters *ctr)
+{
+    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    unsigned long long hops = 0;
+    if (t < tx.count) {
+        int64_t pos = tx.off[t], end = tx.off[t + 1];
+        end = end > n ? n : end;
+        while (pos >= 0 && pos < end) {
+            const int64_t tile = pos / kLzTile;
+            __hip_atomic_fetch_min(reinterpret_cast<uint32_t *>(entry) + tile, (uint32_t)pos, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const int64_t edge = (tile + 1) * kLzTile;
+            const int64_t nx = exits[pos];
+            pos = nx < edge ? edge : nx;
+            ++hops;
+        }
+    }
+    hops = wave_sum(hops);
+    if (lane_id() == 0 && hops) __hip_atomic_fetch_add(&ctr->hops, hops, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+template <bool kMany>
+__device__ __forceinline__ void lz_mark_body(const int32_t *__restrict__ lpf, const LzTexts &tx, int64_t n, const int32_t *__restrict__ entry,
+                                             uint32_t *__restrict__ bits, uint32_t *__restrict__ tile_count)
 {
     __shared__ int32_t s_next[kLzTile];
     __shared__ uint32_t s_bits[kBlock];
@@ -775,7 +836,7 @@ __global__ __launch_bounds__(kBlock) void lz_mark_kernel(const int32_t *__restri
     const int64_t first = entry[blockIdx.x];
     s_bits[threadIdx.x] = 0;
     const bool visited = first >= t0 && first < e;                           // (uniform) -1: the phrases jump over this tile
-    if (visited) lz_load_next(lpf, n, t0, s_next);
+    if (visited) lz_load_next<kMany>(lpf, tx, n, t0, s_next);
     __syncthreads();
     if (visited && threadIdx.x == 0) {
         uint32_t count = 0;
@@ -791,6 +852,19 @@ __global__ __launch_bounds__(kBlock) void lz_mark_kernel(const int32_t *__restri
     if (!visited && threadIdx.x == 0) tile_count[blockIdx.x] = 0;
     __syncthreads();
     bits[(int64_t)blockIdx.x * kBlock + threadIdx.x] = s_bits[threadIdx.x];
+}
+
+__global__ __launch_bounds__(kBlock) void lz_mark_kernel(const int32_t *__restrict__ lpf, int64_t n, const int32_t *__restrict__ entry,
+                                                         uint32_t *__restrict__ bits, uint32_t *__restrict__ tile_count)
+{
+    lz_mark_body<false>(lpf, LzTexts{}, n, entry, bits, tile_count);
+}
+
+__global__ __launch_bounds__(kBlock) void lz_mark_many_kernel(const int32_t *__restrict__ lpf, LzTexts tx, int64_t n,
+                                                              const int32_t *__restrict__ entry, uint32_t *__restrict__ bits,
+                                                              uint32_t *__restrict__ tile_count)
+{
+    lz_mark_body<true>(lpf, tx, n, entry, bits, tile_count);
 }
 
 // tile_count[t] -> the number of phrases that start before tile t, in place; the total is z.  One workgroup.
@@ -824,164 +898,13 @@ __global__ __launch_bounds__(kBlock) void lz_scan_kernel(uint32_t *__restrict__ 
 }
 
 // A thread owns the 32 positions of one bitmap word.  A copy is (i, len, src[i]), a literal (i, 0, T[i]); only the
-// triples below cap are written, all of them are counted.
-__global__ __launch_bounds__(kBlock) void lz_emit_kernel(const uint8_t *__restrict__ T, const int32_t *__restrict__ lpf,
-                                                         const int32_t *__restrict__ src, int64_t n, const uint32_t *__restrict__ bits,
-                                                         const uint32_t *__restrict__ tile_off, int32_t *__restrict__ phrases,
-                                                         int64_t cap, LzCounters *ctr)
-{
-    __shared__ uint32_t s_tmp[kWavesPerBlock];
-    uint32_t word = bits[(int64_t)blockIdx.x * kBlock + threadIdx.x];
-    const int64_t i0 = (int64_t)blockIdx.x * kLzTile + (int64_t)threadIdx.x * kLzPer;
-    uint32_t total;
-    int64_t at = (int64_t)tile_off[blockIdx.x] + block_excl_sum((uint32_t)__builtin_popcount(word), s_tmp, &total);
-    uint32_t literals = 0, longest = 0;
-    while (word) {
-        const int64_t i = i0 + __builtin_ctz(word);
-        word &= word - 1;
-        if (i < n) {                                                         // (a set bit is a position of the text)
-            const int64_t f = lpf[i];
-            const int32_t len = (int32_t)(f < 0 ? 0 : (f > n - i ? n - i : f));
-            const int32_t third = len ? src[i] : (int32_t)T[i];
-            literals += len == 0;
-            longest = (uint32_t)(len ? len : 1) > longest ? (uint32_t)(len ? len : 1) : longest;
-            if (at < cap) {
-                phrases[3 * at] = (int32_t)i;
-                phrases[3 * at + 1] = len;
-                phrases[3 * at + 2] = third;
-            }
-        }
-        ++at;
-    }
-    literals = wave_sum(literals);
-    longest = wave_max(longest);
-    if (lane_id() == 0) {
-        if (literals) __hip_atomic_fetch_add(&ctr->literals, literals, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        lz_raise(&ctr->longest_phrase, longest);
-    }
-}
-
-// ---------------------------------------------------------------------------------------------- the parse of many texts
-// Texts back to back, text t at positions [off[t], off[t + 1]) of lpf / src (dq_lzparse_hip_many_*; the new files of
-// dq_rlz_hip_many_*).  Every step is clamped to its own text's end, so every text start is a phrase start and next[]
-// over the concatenation is one increasing chain through all of them: the tile kernels are the one-text kernels with the
-// text's end in the clamp and its start taken off the triple.  The walk is one lane per text from its own start to its
-// own end (lz_walk_many_kernel); a tile's entry is the minimum over what the lanes report -- the chain from there passes
-// every later text start of the tile.  lz_offsets_kernel turns the scanned tile counts and the bitmap into the phrases
-// before each text.
-// (LzTexts and lz_text_of: above, with the LPF array of many texts)
-
-// next[] of tile t0 .. into LDS: i + clamp(lpf[i], 1, end of i's text - i); n for the rest of the tile
-__device__ __forceinline__ void lz_load_next_many(const int32_t *__restrict__ lpf, const LzTexts &tx, int64_t n, int64_t t0, int32_t *s_next)
-{
-    const int64_t last = t0 + kLzTile < n ? t0 + kLzTile - 1 : n - 1;       // (t0 < n: the tile holds a position)
-    const int32_t lo = lz_text_of(tx.off, 0, tx.count - 1, t0), hi = lz_text_of(tx.off, lo, tx.count - 1, last);
-#pragma unroll 4
-    for (int k = 0; k < kLzPer; ++k) {
-        const int at = k * kBlock + (int)threadIdx.x;
-        const int64_t i = t0 + at;
-        int64_t nx = n;
-        if (i < n) {
-            int64_t end = tx.off[lz_text_of(tx.off, lo, hi, i) + 1];
-            end = end > n ? n : (end <= i ? i + 1 : end);                    // (the host checked the layout)
-            const int64_t f = lpf[i];
-            nx = i + (f < 1 ? 1 : (f > end - i ? end - i : f));
-        }
-        s_next[at] = (int32_t)nx;
-    }
-}
-
-// lz_exit_kernel over the concatenation
-__global__ __launch_bounds__(kBlock) void lz_exit_many_kernel(const int32_t *__restrict__ lpf, LzTexts tx, int64_t n,
-                                                              int32_t *__restrict__ exits)
-{
-    __shared__ int32_t s_next[kLzTile];
-    const int64_t t0 = (int64_t)blockIdx.x * kLzTile;
-    const int64_t e64 = t0 + kLzTile < n ? t0 + kLzTile : n;
-    const int32_t e = (int32_t)e64, b0 = (int32_t)t0;
-    lz_load_next_many(lpf, tx, n, t0, s_next);
-    __syncthreads();
-    for (int round = 0; round < kLzJumpRounds; ++round) {
-        int32_t nv[kLzPer];
-        bool moved = false;
-#pragma unroll
-        for (int k = 0; k < kLzPer; ++k) {
-            const int32_t j = s_next[k * kBlock + (int)threadIdx.x];
-            const bool inside = j < e;                                       // (then b0 < j: next[] increases)
-            nv[k] = inside ? s_next[j - b0] : j;
-            moved = moved || inside;
-        }
-        if (!__syncthreads_or(moved)) break;                                 // (uniform; and every read is over)
-#pragma unroll
-        for (int k = 0; k < kLzPer; ++k) s_next[k * kBlock + (int)threadIdx.x] = nv[k];
-        __syncthreads();
-    }
-#pragma unroll 4
-    for (int k = 0; k < kLzPer; ++k) {
-        const int at = k * kBlock + (int)threadIdx.x;
-        if (t0 + at < n) exits[t0 + at] = s_next[at];
-    }
-}
-
-// One lane per text.  entry[] was filled with -1, which as an unsigned word is above every position: a tile's entry is
-// the least position a lane enters it at.  Every hop leaves its tile (forced) and no lane leaves its text, so a lane makes
-// at most one hop per tile its text touches; the hops of all lanes are summed.
-__global__ __launch_bounds__(kBlock) void lz_walk_many_kernel(const int32_t *__restrict__ exits, LzTexts tx, int64_t n,
-                                                              int32_t *__restrict__ entry, LzCounters *ctr)
-{
-    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    unsigned long long hops = 0;
-    if (t < tx.count) {
-        int64_t pos = tx.off[t], end = tx.off[t + 1];
-        end = end > n ? n : end;
-        while (pos >= 0 && pos < end) {
-            const int64_t tile = pos / kLzTile;
-            __hip_atomic_fetch_min(reinterpret_cast<uint32_t *>(entry) + tile, (uint32_t)pos, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const int64_t edge = (tile + 1) * kLzTile;
-            const int64_t nx = exits[pos];
-            pos = nx < edge ? edge : nx;
-            ++hops;
-        }
-    }
-    hops = wave_sum(hops);
-    if (lane_id() == 0 && hops) __hip_atomic_fetch_add(&ctr->hops, hops, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// lz_mark_kernel over the concatenation
-__global__ __launch_bounds__(kBlock) void lz_mark_many_kernel(const int32_t *__restrict__ lpf, LzTexts tx, int64_t n,
-                                                              const int32_t *__restrict__ entry, uint32_t *__restrict__ bits,
-                                                              uint32_t *__restrict__ tile_count)
-{
-    __shared__ int32_t s_next[kLzTile];
-    __shared__ uint32_t s_bits[kBlock];
-    const int64_t t0 = (int64_t)blockIdx.x * kLzTile;
-    const int64_t e = t0 + kLzTile < n ? t0 + kLzTile : n;
-    const int64_t first = entry[blockIdx.x];
-    s_bits[threadIdx.x] = 0;
-    const bool visited = first >= t0 && first < e;                           // (uniform) -1: the phrases jump over this tile
-    if (visited) lz_load_next_many(lpf, tx, n, t0, s_next);
-    __syncthreads();
-    if (visited && threadIdx.x == 0) {
-        uint32_t count = 0;
-        int64_t pos = first;
-        while (pos < e) {                                                    // next[] increases: at most kLzTile steps
-            const int at = (int)(pos - t0);
-            s_bits[at >> 5] |= 1u << (at & 31);
-            pos = s_next[at];
-            ++count;
-        }
-        tile_count[blockIdx.x] = count;
-    }
-    if (!visited && threadIdx.x == 0) tile_count[blockIdx.x] = 0;
-    __syncthreads();
-    bits[(int64_t)blockIdx.x * kBlock + threadIdx.x] = s_bits[threadIdx.x];
-}
-
-// lz_emit_kernel over the concatenation: a copy is (i - start of its text, len, src[i]), a literal (.., 0, its byte)
-__global__ __launch_bounds__(kBlock) void lz_emit_many_kernel(const uint8_t *__restrict__ T, const int32_t *__restrict__ lpf,
-                                                              const int32_t *__restrict__ src, LzTexts tx, int64_t n,
-                                                              const uint32_t *__restrict__ bits, const uint32_t *__restrict__ tile_off,
-                                                              int32_t *__restrict__ phrases, int64_t cap, LzCounters *ctr)
+// triples below cap are written, all of them are counted.  kMany: i counts from the start of its text, and the literal is
+// that text's byte.
+template <bool kMany>
+__device__ __forceinline__ void lz_emit_body(const uint8_t *__restrict__ T, const int32_t *__restrict__ lpf, const int32_t *__restrict__ src,
+                                             const LzTexts &tx, int64_t n, const uint32_t *__restrict__ bits,
+                                             const uint32_t *__restrict__ tile_off, int32_t *__restrict__ phrases, int64_t cap,
+                                             LzCounters *ctr)
 {
     __shared__ uint32_t s_tmp[kWavesPerBlock];
     uint32_t word = bits[(int64_t)blockIdx.x * kBlock + threadIdx.x];
@@ -990,20 +913,22 @@ __global__ __launch_bounds__(kBlock) void lz_emit_many_kernel(const uint8_t *__r
     int64_t at = (int64_t)tile_off[blockIdx.x] + block_excl_sum((uint32_t)__builtin_popcount(word), s_tmp, &total);
     uint32_t literals = 0, longest = 0;
     int32_t t = -1;
-    int64_t base = 0, end = 0;                                               // the text of the bit before: [base, end)
+    int64_t base = 0, end = kMany ? 0 : n;                                   // kMany: the text of the bit before, [base, end)
     while (word) {
         const int64_t i = i0 + __builtin_ctz(word);
         word &= word - 1;
         if (i < n) {                                                         // (a set bit is a position of a text)
-            if (i >= end) {
-                t = lz_text_of(tx.off, t < 0 ? 0 : t, tx.count - 1, i);
-                base = tx.off[t];
-                end = tx.off[t + 1];
-                end = end > n ? n : (end <= i ? i + 1 : end);
+            if constexpr (kMany) {
+                if (i >= end) {
+                    t = lz_text_of(tx.off, t < 0 ? 0 : t, tx.count - 1, i);
+                    base = tx.off[t];
+                    end = tx.off[t + 1];
+                    end = end > n ? n : (end <= i ? i + 1 : end);
+                }
             }
             const int64_t f = lpf[i];
             const int32_t len = (int32_t)(f < 0 ? 0 : (f > end - i ? end - i : f));
-            const int32_t third = len ? src[i] : (int32_t)T[tx.bytes[t] + (i - base)];
+            const int32_t third = len ? src[i] : (int32_t)T[kMany ? tx.bytes[t] + (i - base) : i];
             literals += len == 0;
             longest = (uint32_t)(len ? len : 1) > longest ? (uint32_t)(len ? len : 1) : longest;
             if (at < cap) {
@@ -1020,6 +945,22 @@ __global__ __launch_bounds__(kBlock) void lz_emit_many_kernel(const uint8_t *__r
         if (literals) __hip_atomic_fetch_add(&ctr->literals, literals, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         lz_raise(&ctr->longest_phrase, longest);
     }
+}
+
+__global__ __launch_bounds__(kBlock) void lz_emit_kernel(const uint8_t *__restrict__ T, const int32_t *__restrict__ lpf,
+                                                         const int32_t *__restrict__ src, int64_t n, const uint32_t *__restrict__ bits,
+                                                         const uint32_t *__restrict__ tile_off, int32_t *__restrict__ phrases,
+                                                         int64_t cap, LzCounters *ctr)
+{
+    lz_emit_body<false>(T, lpf, src, LzTexts{}, n, bits, tile_off, phrases, cap, ctr);
+}
+
+__global__ __launch_bounds__(kBlock) void lz_emit_many_kernel(const uint8_t *__restrict__ T, const int32_t *__restrict__ lpf,
+                                                              const int32_t *__restrict__ src, LzTexts tx, int64_t n,
+                                                              const uint32_t *__restrict__ bits, const uint32_t *__restrict__ tile_off,
+                                                              int32_t *__restrict__ phrases, int64_t cap, LzCounters *ctr)
+{
+    lz_emit_body<true>(T, lpf, src, tx, n, bits, tile_off, phrases, cap, ctr);
 }
 
 // One thread per entry of phrase_offsets[0 .. count]: the phrases that start before text t's first position -- the

@@ -184,11 +184,7 @@ int lzd_run(const LzdCall &q, bool host, const void *phrases, const void *olds, 
         if (host && q.S) HIP_TRY(hipMemcpyAsync(staged.get(), d_out, (size_t)q.S, hipMemcpyDeviceToHost, st));
         return DQ_OK;
     };
-    // the one wait of the call, made whatever `enqueued` says: nothing of the call stays in flight behind the return
-    const int enqueued = run();
-    const hipError_t e = hipStreamSynchronize(st);
-    if (enqueued != DQ_OK) return enqueued;
-    HIP_TRY(e);
+    DQ_TRY(wait_once(st, run()));
     t_lzdecode_info.stream_waits += 1;
     LzdCounters got;
     memcpy(&got, c.pinned, sizeof got);

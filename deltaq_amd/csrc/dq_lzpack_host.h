@@ -157,11 +157,7 @@ int lzpack_many(bool host, const void *phrases, const int64_t *poff, int32_t cou
         if (host && room) HIP_TRY(hipMemcpyAsync(staged.get(), q.blobs, (size_t)room, hipMemcpyDeviceToHost, st));
         return DQ_OK;
     };
-    // the one wait of the call, made whatever `enqueued` says: nothing of the call stays in flight behind the return
-    const int enqueued = run();
-    const hipError_t e = hipStreamSynchronize(st);
-    if (enqueued != DQ_OK) return enqueued;
-    HIP_TRY(e);
+    DQ_TRY(wait_once(st, run()));
     lzp_record(c.pinned, lzpack_launches(Z, count));
     for (size_t t = 0; t < n; ++t) {
         status[t] = verdict[t] ? -1 : 0;
@@ -256,10 +252,7 @@ int lzunpack_many(bool host, const void *blobs, const int64_t *boff, int32_t cou
         if (host && room) HIP_TRY(hipMemcpyAsync(staged.get(), q.out, (size_t)room * 12, hipMemcpyDeviceToHost, st));
         return DQ_OK;
     };
-    const int enqueued = run();
-    const hipError_t e = hipStreamSynchronize(st);
-    if (enqueued != DQ_OK) return enqueued;
-    HIP_TRY(e);
+    DQ_TRY(wait_once(st, run()));
     lzp_record(c.pinned, lzunpack_launches(B));
     for (size_t t = 0; t < n; ++t) {
         status[t] = verdict[t] ? -1 : 0;

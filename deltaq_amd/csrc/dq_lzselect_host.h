@@ -81,11 +81,7 @@ int lzselect_many(bool host, const void *len, const void *src, const int64_t *of
         }
         return DQ_OK;
     };
-    // the one wait of the call, made whatever `enqueued` says: nothing of the call stays in flight behind the return
-    const int enqueued = run();
-    const hipError_t e = hipStreamSynchronize(st);
-    if (enqueued != DQ_OK) return enqueued;
-    HIP_TRY(e);
+    DQ_TRY(wait_once(st, run()));
     LzsCounters got;
     memcpy(&got, c.pinned, sizeof got);
     t_lzselect_info.positions = N;

@@ -336,6 +336,16 @@ int carve_ws(DeviceCtx &c, Plan plan)
     return DQ_OK;
 }
 
+// The one wait of a call, made whatever its enqueues returned: nothing of the call stays in flight behind the return.
+// The enqueue's error comes first, then the wait's.
+inline int wait_once(hipStream_t st, int enqueued)
+{
+    const hipError_t e = hipStreamSynchronize(st);
+    if (enqueued != DQ_OK) return enqueued;
+    HIP_TRY(e);
+    return DQ_OK;
+}
+
 inline int bit_length(uint64_t x) { return x == 0 ? 1 : 64 - __builtin_clzll(x); }
 
 // ------------------------------------------------------------------ short texts: one launch
@@ -705,50 +715,33 @@ int lcp_many_host(const uint8_t *texts, const int64_t *offsets, int32_t count, c
 int lcp_many_dev(const void *d_texts, const void *d_offsets, int32_t count, const void *d_sas, void *d_lcps, int32_t device,
                  void *stream);
 
-// The LPF array and the LZ77 factorization from SA and LCP (dq_lz77_host.h, in dq_sufcheck.hip): the bodies of
-// dq_lpf_hip_* and dq_lz77_hip_*.  All of them fill t_lz77_info (dq_lz77_info.h); the entry point resets it.
-int lpf_host(const int32_t *sa, const int32_t *lcp, int64_t n, int32_t *lpf, int32_t *src, int32_t device);
-int lpf_dev(const void *d_sa, const void *d_lcp, int64_t n, void *d_lpf, void *d_src, int32_t device, void *stream);
-int lz77_host(const uint8_t *text, int64_t n, const int32_t *sa, const int32_t *lcp, int32_t *phrases, int64_t cap, int64_t *count,
-              int32_t device);
-int lz77_dev(const void *d_text, int64_t n, const void *d_sa, const void *d_lcp, void *d_phrases, int64_t cap, int64_t *count,
+// The LPF array and the LZ77 factorization from SA and LCP, of one text or of many in one call (dq_lz77_host.h, in
+// dq_sufcheck.hip): the bodies of dq_lpf_hip_* and dq_lz77_hip_*.  host: the buffers are the host's (the offsets too, and
+// stream is not looked at); otherwise device pointers.  All of them fill t_lz77_info (dq_lz77_info.h); the entry point
+// resets it.
+int lpf_one(bool host, const void *sa, const void *lcp, int64_t n, void *lpf, void *src, int32_t device, void *stream);
+int lz77_one(bool host, const void *text, int64_t n, const void *sa, const void *lcp, void *phrases, int64_t cap, int64_t *count,
              int32_t device, void *stream);
-// ... and of many texts in one call: the bodies of dq_lpf_hip_many_* and dq_lz77_hip_many_*
-int lpf_many_host(const int64_t *offsets, int32_t count, const int32_t *sas, const int32_t *lcps, int32_t *lpf, int32_t *src,
-                  int32_t device);
-int lpf_many_dev(const void *d_offsets, int32_t count, const void *d_sas, const void *d_lcps, void *d_lpf, void *d_src, int32_t device,
-                 void *stream);
-int lz77_many_host(const uint8_t *texts, const int64_t *offsets, int32_t count, const int32_t *sas, const int32_t *lcps,
-                   int32_t *phrases, int64_t cap, int64_t *phrase_offsets, int32_t device);
-int lz77_many_dev(const void *d_texts, const void *d_offsets, int32_t count, const void *d_sas, const void *d_lcps, void *d_phrases,
-                  int64_t cap, int64_t *phrase_offsets, int32_t device, void *stream);
+int lpf_many(bool host, const void *offsets, int32_t count, const void *sas, const void *lcps, void *lpf, void *src, int32_t device,
+             void *stream);
+int lz77_many(bool host, const void *texts, const void *offsets, int32_t count, const void *sas, const void *lcps, void *phrases,
+              int64_t cap, int64_t *phrase_offsets, int32_t device, void *stream);
 
 // Matching statistics of new against old from the SA and LCP of new + old, the relative LZ factorization and the parse
-// alone (dq_rlz_host.h, in dq_sufcheck.hip): the bodies of dq_mstat_hip_*, dq_rlz_hip_* and dq_lzparse_hip_*.  All of
-// them fill t_rlz_info (dq_rlz_info.h); the entry point resets it.
-int mstat_host(const int32_t *sa, const int32_t *lcp, int64_t m, int64_t n, int32_t *len, int32_t *src, int32_t device);
-int mstat_dev(const void *d_sa, const void *d_lcp, int64_t m, int64_t n, void *d_len, void *d_src, int32_t device, void *stream);
-int rlz_host(const uint8_t *new_data, int64_t m, int64_t n, const int32_t *sa, const int32_t *lcp, int32_t *phrases, int64_t cap,
-             int64_t *count, int32_t device);
-int rlz_dev(const void *d_new, int64_t m, int64_t n, const void *d_sa, const void *d_lcp, void *d_phrases, int64_t cap, int64_t *count,
-            int32_t device, void *stream);
-int lzparse_host(const uint8_t *text, int64_t n, const int32_t *len, const int32_t *src, int32_t *phrases, int64_t cap, int64_t *count,
-                 int32_t device);
-int lzparse_dev(const void *d_text, int64_t n, const void *d_len, const void *d_src, void *d_phrases, int64_t cap, int64_t *count,
+// alone, of one pair or of many in one call (dq_rlz_host.h, in dq_sufcheck.hip): the bodies of dq_mstat_hip_*,
+// dq_rlz_hip_* and dq_lzparse_hip_*.  host: as above.  All of them fill t_rlz_info (dq_rlz_info.h); the entry point
+// resets it.
+int mstat_one(bool host, const void *sa, const void *lcp, int64_t m, int64_t n, void *len, void *src, int32_t device, void *stream);
+int rlz_one(bool host, const void *new_data, int64_t m, int64_t n, const void *sa, const void *lcp, void *phrases, int64_t cap,
+            int64_t *count, int32_t device, void *stream);
+int lzparse_one(bool host, const void *text, int64_t n, const void *len, const void *src, void *phrases, int64_t cap, int64_t *count,
                 int32_t device, void *stream);
-// ... and of many pairs in one call: the bodies of dq_mstat_hip_many_*, dq_rlz_hip_many_* and dq_lzparse_hip_many_*
-int mstat_many_host(const int64_t *offsets, const int64_t *new_offsets, int32_t count, const int32_t *sas, const int32_t *lcps,
-                    int32_t *len, int32_t *src, int32_t device);
-int mstat_many_dev(const void *d_offsets, const void *d_new_offsets, int32_t count, const void *d_sas, const void *d_lcps, void *d_len,
-                   void *d_src, int32_t device, void *stream);
-int rlz_many_host(const uint8_t *cats, const int64_t *offsets, const int64_t *new_offsets, int32_t count, const int32_t *sas,
-                  const int32_t *lcps, int32_t *phrases, int64_t cap, int64_t *phrase_offsets, int32_t device);
-int rlz_many_dev(const void *d_cats, const void *d_offsets, const void *d_new_offsets, int32_t count, const void *d_sas,
-                 const void *d_lcps, void *d_phrases, int64_t cap, int64_t *phrase_offsets, int32_t device, void *stream);
-int lzparse_many_host(const uint8_t *texts, const int64_t *offsets, int32_t count, const int32_t *len, const int32_t *src,
-                      int32_t *phrases, int64_t cap, int64_t *phrase_offsets, int32_t device);
-int lzparse_many_dev(const void *d_texts, const void *d_offsets, int32_t count, const void *d_len, const void *d_src, void *d_phrases,
-                     int64_t cap, int64_t *phrase_offsets, int32_t device, void *stream);
+int mstat_many(bool host, const void *offsets, const void *new_offsets, int32_t count, const void *sas, const void *lcps, void *len,
+               void *src, int32_t device, void *stream);
+int rlz_many(bool host, const void *cats, const void *offsets, const void *new_offsets, int32_t count, const void *sas, const void *lcps,
+             void *phrases, int64_t cap, int64_t *phrase_offsets, int32_t device, void *stream);
+int lzparse_many(bool host, const void *texts, const void *offsets, int32_t count, const void *len, const void *src, void *phrases,
+                 int64_t cap, int64_t *phrase_offsets, int32_t device, void *stream);
 
 // The triples of dq_lz77_hip_* / dq_rlz_hip_* back into bytes (dq_lzdecode_host.h, in dq_sufcheck.hip): the bodies of
 // dq_lz77_decode_hip_* and dq_rlz_decode_hip_*, one text or many.  rlz: the relative decoder (old / olds are read);
