@@ -236,6 +236,25 @@ public sealed class HipSuffixSort : ISuffixSort
     private static extern unsafe int dq_lzpack_last_info(long* info, int count);
 
     [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern long dq_lzcode_bound(long bytes, int count);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    private static extern unsafe int dq_lzcode_hip_many(byte* blobs, long* blobOffsets, int count, byte* coded, long cap, long* codedOffsets, int* status, int device);
+
+    // (declared for hosts that keep their buffers on the device: device pointers, a hipStream_t or zero)
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern unsafe int dq_lzcode_hip_many_dev(IntPtr dBlobs, long* blobOffsets, int count, IntPtr dCoded, long cap, long* codedOffsets, int* status, int device, IntPtr stream);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    private static extern unsafe int dq_lzuncode_hip_many(byte* coded, long* codedOffsets, int count, byte* blobs, long* slotOffsets, long* outLen, int* status, int device);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    internal static extern unsafe int dq_lzuncode_hip_many_dev(IntPtr dCoded, long* codedOffsets, int count, IntPtr dBlobs, long* slotOffsets, long* outLen, int* status, int device, IntPtr stream);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
+    private static extern unsafe int dq_lzcode_last_info(long* info, int count);
+
+    [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)]
     private static extern unsafe int dq_lzselect_hip_many_i32(int* len, int* src, long* offsets, int count, int kind, long* oldSizes, int minGain, int* outLen, int* outSrc, int device);
 
     // (declared for hosts that keep their buffers on the device: device pointers, a hipStream_t or zero)
@@ -1962,6 +1981,161 @@ public sealed class HipSuffixSort : ISuffixSort
             if (rc != 0)
             {
                 throw new InvalidOperationException($"dq_lzpack_last_info failed ({rc})");
+            }
+        }
+
+        return info;
+    }
+
+    /// <summary>dq_lzcode_bound: bytes that hold the DQLE blobs of any count DQLZ blobs of `bytes` bytes together; -1 on negative arguments.</summary>
+    public static long LzCodeBound(long bytes, int count) => dq_lzcode_bound(bytes, count);
+
+    private static (byte[] Flat, long[] Offsets) Concatenate(IReadOnlyList<byte[]> parts, string what)
+    {
+        if (parts is null)
+        {
+            throw new ArgumentNullException(what);
+        }
+
+        var offsets = new long[parts.Count + 1];
+        for (int t = 0; t < parts.Count; ++t)
+        {
+            offsets[t + 1] = offsets[t] + (parts[t] ?? throw new ArgumentNullException(what)).Length;
+        }
+
+        var flat = new byte[Math.Max(offsets[parts.Count], 1)];
+        for (int t = 0; t < parts.Count; ++t)
+        {
+            parts[t].CopyTo(flat, offsets[t]);
+        }
+
+        return (flat, offsets);
+    }
+
+    /// <summary>
+    /// DQLZ blobs as entropy-coded DQLE blobs in one native call (dq_lzcode_hip_many; include/dq_sufsort.h has the
+    /// format).  A blob without the frame of DQLZ version 1 is refused by name.
+    /// </summary>
+    public unsafe byte[][] LzCodeMany(IReadOnlyList<byte[]> blobs)
+    {
+        var (flat, offsets) = Concatenate(blobs, nameof(blobs));
+        int count = blobs.Count;
+        if (count == 0)
+        {
+            return Array.Empty<byte[]>();
+        }
+
+        long cap = dq_lzcode_bound(offsets[count], count);
+        var coded = new byte[Math.Max(cap, 1)];
+        var codedOffsets = new long[count + 1];
+        var status = new int[count];
+        fixed (byte* b = flat)
+        fixed (long* bo = offsets)
+        fixed (byte* c = coded)
+        fixed (long* co = codedOffsets)
+        fixed (int* st = status)
+        {
+            int rc = dq_lzcode_hip_many(b, bo, count, c, cap, co, st, _device);
+            if (rc != 0)
+            {
+                throw new InvalidOperationException($"dq_lzcode_hip_many failed ({rc}): {Marshal.PtrToStringAnsi(dq_last_error()) ?? string.Empty}");
+            }
+        }
+
+        var result = new byte[count][];
+        for (int t = 0; t < count; ++t)
+        {
+            if (status[t] != 0)
+            {
+                throw new ArgumentException($"blob {t}: not framed as a DQLZ version 1 blob", nameof(blobs));
+            }
+
+            result[t] = new byte[codedOffsets[t + 1] - codedOffsets[t]];
+            Array.Copy(coded, codedOffsets[t], result[t], 0, result[t].Length);
+        }
+
+        return result;
+    }
+
+    /// <summary>
+    /// DQLE blobs back into their DQLZ blobs in one native call (dq_lzuncode_hip_many), the slots sized from the
+    /// headers.  Coded blobs are untrusted: a malformed one is refused by name.
+    /// </summary>
+    public unsafe byte[][] LzUncodeMany(IReadOnlyList<byte[]> coded)
+    {
+        var (flat, offsets) = Concatenate(coded, nameof(coded));
+        int count = coded.Count;
+        if (count == 0)
+        {
+            return Array.Empty<byte[]>();
+        }
+
+        var slotOffsets = new long[count + 1];
+        for (int t = 0; t < count; ++t)
+        {
+            long size = 0;
+            if (coded[t].Length >= 40)
+            {
+                long c = BitConverter.ToInt64(coded[t], 16), l = BitConverter.ToInt64(coded[t], 24);
+                if (c >= 0 && c <= int.MaxValue && l >= 0 && l <= int.MaxValue)
+                {
+                    size = 32 + c + l;
+                }
+            }
+
+            slotOffsets[t + 1] = slotOffsets[t] + size;
+        }
+
+        if (slotOffsets[count] > int.MaxValue)
+        {
+            throw new ArgumentException("the decoded blobs together must be shorter than 2^31 bytes", nameof(coded));
+        }
+
+        var blobs = new byte[Math.Max(slotOffsets[count], 1)];
+        var outLen = new long[count];
+        var status = new int[count];
+        fixed (byte* c = flat)
+        fixed (long* co = offsets)
+        fixed (byte* b = blobs)
+        fixed (long* so = slotOffsets)
+        fixed (long* ol = outLen)
+        fixed (int* st = status)
+        {
+            int rc = dq_lzuncode_hip_many(c, co, count, b, so, ol, st, _device);
+            if (rc != 0)
+            {
+                throw new InvalidOperationException($"dq_lzuncode_hip_many failed ({rc}): {Marshal.PtrToStringAnsi(dq_last_error()) ?? string.Empty}");
+            }
+        }
+
+        var result = new byte[count][];
+        for (int t = 0; t < count; ++t)
+        {
+            if (status[t] != 0)
+            {
+                throw new ArgumentException($"blob {t}: malformed DQLE blob", nameof(coded));
+            }
+
+            result[t] = new byte[outLen[t]];
+            Array.Copy(blobs, slotOffsets[t], result[t], 0, result[t].Length);
+        }
+
+        return result;
+    }
+
+    /// <summary>
+    /// Shape of the last code or uncode call on this thread (dq_lzcode_last_info): blobs with status 0, -1 and -2, the
+    /// stored, run and Huffman sections of the first, input bytes, output bytes, trees rebuilt, kernel launches, stream waits.
+    /// </summary>
+    public static unsafe long[] LastLzCodeInfo()
+    {
+        var info = new long[11];
+        fixed (long* p = info)
+        {
+            int rc = dq_lzcode_last_info(p, info.Length);
+            if (rc != 0)
+            {
+                throw new InvalidOperationException($"dq_lzcode_last_info failed ({rc})");
             }
         }
 

@@ -72,6 +72,8 @@ EXPORTS = (
     "dq_rlz_decode_hip_many_dev_i32", "dq_lzdecode_last_info",
     "dq_lzpack_bound", "dq_lzpack_hip_many_i32", "dq_lzpack_hip_many_dev_i32", "dq_lzunpack_hip_many_i32",
     "dq_lzunpack_hip_many_dev_i32", "dq_lzpack_last_info",
+    "dq_lzcode_bound", "dq_lzcode_hip_many", "dq_lzcode_hip_many_dev", "dq_lzuncode_hip_many", "dq_lzuncode_hip_many_dev",
+    "dq_lzcode_last_info",
     "dq_lzselect_hip_many_i32", "dq_lzselect_hip_many_dev_i32", "dq_lzselect_last_info",
     "dq_bsdiff_search_dev_i32", "dq_bsdiff_search_dev_i64", "dq_bsdiff_search_i32", "dq_bsdiff_search_i64",
     "dq_bsdiff_create", "dq_bsdiff_patch_bound", "dq_bsdiff_scan_i32", "dq_bspatch_apply",
@@ -135,6 +137,11 @@ LZDECODE_RECORD = _n("texts_ok", "texts_refused", "linked", "jump_rounds", "laun
 # ... and the record of dq_lzpack_last_info, struct LzPackInfo of deltaq_amd/csrc/dq_lzpack_info.h;
 # tests/test_lzpack_cpu.py checks it.
 LZPACK_RECORD = _n("texts_ok", "texts_refused", "tokens", "ctrl_bytes", "literal_bytes", "launches", "stream_waits")
+
+# ... and the record of dq_lzcode_last_info, struct LzCodeInfo of deltaq_amd/csrc/dq_lzcode_info.h;
+# tests/test_lzcode_cpu.py checks it.
+LZCODE_RECORD = _n("blobs_ok", "blobs_refused", "blobs_short", "stored_sections", "run_sections", "huffman_sections",
+                   "in_bytes", "out_bytes", "rebuilds", "launches", "stream_waits")
 
 # ... and the record of dq_lzselect_last_info, struct LzSelectInfo of deltaq_amd/csrc/dq_lzselect_info.h;
 # tests/test_lzselect_cpu.py checks it.
@@ -294,6 +301,18 @@ def load() -> ctypes.CDLL:
     L.dq_lzunpack_hip_many_dev_i32.argtypes = [vp, vp, i32, vp, i64, vp, vp, vp, vp, i32, vp]
     L.dq_lzpack_last_info.restype = i32
     L.dq_lzpack_last_info.argtypes = [ctypes.POINTER(i64), i32]
+    L.dq_lzcode_bound.restype = i64
+    L.dq_lzcode_bound.argtypes = [i64, i32]
+    L.dq_lzcode_hip_many.restype = i32
+    L.dq_lzcode_hip_many.argtypes = [vp, vp, i32, vp, i64, vp, vp, i32]
+    L.dq_lzcode_hip_many_dev.restype = i32
+    L.dq_lzcode_hip_many_dev.argtypes = [vp, vp, i32, vp, i64, vp, vp, i32, vp]
+    L.dq_lzuncode_hip_many.restype = i32
+    L.dq_lzuncode_hip_many.argtypes = [vp, vp, i32, vp, vp, vp, vp, i32]
+    L.dq_lzuncode_hip_many_dev.restype = i32
+    L.dq_lzuncode_hip_many_dev.argtypes = [vp, vp, i32, vp, vp, vp, vp, i32, vp]
+    L.dq_lzcode_last_info.restype = i32
+    L.dq_lzcode_last_info.argtypes = [ctypes.POINTER(i64), i32]
     L.dq_lzselect_hip_many_i32.restype = i32
     L.dq_lzselect_hip_many_i32.argtypes = [vp, vp, vp, i32, i32, vp, i32, vp, vp, i32]
     L.dq_lzselect_hip_many_dev_i32.restype = i32
@@ -533,6 +552,15 @@ def last_lzdecode_info() -> dict:
     v = (ctypes.c_int64 * len(LZDECODE_RECORD))()
     check(load().dq_lzdecode_last_info(v, len(LZDECODE_RECORD)))
     return {key: v[i] * scale for i, (key, scale) in enumerate(LZDECODE_RECORD)}
+
+
+def last_lzcode_info() -> dict:
+    """Shape of the last dq_lzcode_hip_many* / dq_lzuncode_hip_many* on this thread (dq_lzcode_last_info): blobs with
+    status 0, -1 and -2, the sections of the first by mode (stored, run, Huffman), input bytes, output bytes of the
+    blobs with status 0, trees rebuilt (encode), kernel launches and stream waits."""
+    v = (ctypes.c_int64 * len(LZCODE_RECORD))()
+    check(load().dq_lzcode_last_info(v, len(LZCODE_RECORD)))
+    return {key: v[i] * scale for i, (key, scale) in enumerate(LZCODE_RECORD)}
 
 
 def last_lzpack_info() -> dict:

@@ -15,7 +15,8 @@ Five translation units, compiled side by side and linked into one library:
                                             kinds of phrases (dq_lzdecode.h, dq_lzdecode_host.h), the DQLZ
                                             packer and unpacker of phrases (dq_lzpack.h, dq_lzpack_host.h), the
                                             selection of copies in front of the parse (dq_lzselect.h,
-                                            dq_lzselect_host.h)
+                                            dq_lzselect_host.h), the entropy-coded DQLE layer around the blobs
+                                            (dq_lzcode.h, dq_lzcode_plan.h, dq_lzcode_host.h)
     dq_abi.hip                              the C ABI and the batch pipeline (host code only)
 Objects live in deltaq_amd/csrc/obj/ with the compiler's own dependency files, so an edit
 rebuilds only the units that include what changed.

@@ -668,6 +668,42 @@ int32_t dq_lzunpack_hip_many_dev_i32(const void *d_blobs, const int64_t *blob_of
 
 int32_t dq_lzpack_last_info(int64_t *info, int32_t count) { return last_info(t_lzpack_info, info, count, "null info array"); }
 
+int64_t dq_lzcode_bound(int64_t bytes, int32_t count) { return lzcode_bound(bytes, count); }
+
+int32_t dq_lzcode_hip_many(const uint8_t *blobs, const int64_t *blob_offsets, int32_t count, uint8_t *coded, int64_t cap,
+                           int64_t *coded_offsets, int32_t *status, int32_t device)
+{
+    return lz_entry(t_lzcode_info, "lz code: host allocation failed", [&] {
+        return lzcode_many(true, blobs, blob_offsets, count, coded, cap, coded_offsets, status, device, nullptr);
+    });
+}
+
+int32_t dq_lzcode_hip_many_dev(const void *d_blobs, const int64_t *blob_offsets, int32_t count, void *d_coded, int64_t cap,
+                               int64_t *coded_offsets, int32_t *status, int32_t device, void *stream)
+{
+    return lz_entry(t_lzcode_info, "lz code: host allocation failed", [&] {
+        return lzcode_many(false, d_blobs, blob_offsets, count, d_coded, cap, coded_offsets, status, device, stream);
+    });
+}
+
+int32_t dq_lzuncode_hip_many(const uint8_t *coded, const int64_t *coded_offsets, int32_t count, uint8_t *blobs,
+                             const int64_t *slot_offsets, int64_t *out_len, int32_t *status, int32_t device)
+{
+    return lz_entry(t_lzcode_info, "lz uncode: host allocation failed", [&] {
+        return lzuncode_many(true, coded, coded_offsets, count, blobs, slot_offsets, out_len, status, device, nullptr);
+    });
+}
+
+int32_t dq_lzuncode_hip_many_dev(const void *d_coded, const int64_t *coded_offsets, int32_t count, void *d_blobs,
+                                 const int64_t *slot_offsets, int64_t *out_len, int32_t *status, int32_t device, void *stream)
+{
+    return lz_entry(t_lzcode_info, "lz uncode: host allocation failed", [&] {
+        return lzuncode_many(false, d_coded, coded_offsets, count, d_blobs, slot_offsets, out_len, status, device, stream);
+    });
+}
+
+int32_t dq_lzcode_last_info(int64_t *info, int32_t count) { return last_info(t_lzcode_info, info, count, "null info array"); }
+
 int32_t dq_lzselect_hip_many_i32(const int32_t *len, const int32_t *src, const int64_t *offsets, int32_t count, int32_t kind,
                                  const int64_t *old_sizes, int32_t min_gain, int32_t *out_len, int32_t *out_src, int32_t device)
 {

@@ -42,6 +42,7 @@
 // The host side: huff_group is the shared group frame (run_group, dq_runtime.h) around its areas (SymAreas, BitAreas: dq_block_groups.h), its
 // uploads and launch_huff, and the host form's validation and copy-out; bwt_group (dq_bwt_many.h) calls launch_huff too.
 #pragma once
+#include "dq_huff_lengths.h"
 
 namespace dq {
 
@@ -87,69 +88,10 @@ struct HuffLds {
 static_assert(sizeof(HuffLds) * 4 <= 160 * 1024, "four workgroups per CU by LDS");
 
 // libbz2's code lengths of table t from L.u.rfreq[t], by one wave: lane 0 builds the tree, all lanes read the depths
+// (dq_huff_lengths.h has the body, which the DQLE coder shares with another limit and wider weights)
 __device__ __forceinline__ void huff_build_lengths(HuffLds &L, int t, int alpha, int lane)
 {
-    uint64_t *heap = L.w.tree.heap[t];
-    int16_t *parent = L.w.tree.parent[t];
-    int32_t *f = L.u.rfreq[t];
-    for (int pass = 0; pass < 32; ++pass) {                     // (a halving a pass: 20 bits of frequency end it long before)
-        if (lane == 0) {
-            int n_nodes = alpha, n_heap = 0;
-            heap[0] = 0;
-            parent[0] = -2;
-            auto up = [&](int z, uint64_t e) {
-                while ((e >> 16) < (heap[z >> 1] >> 16)) { heap[z] = heap[z >> 1]; z >>= 1; }
-                heap[z] = e;
-            };
-            auto down = [&](int z) {
-                const uint64_t tmp = heap[z];
-                for (;;) {
-                    int y = z << 1;
-                    if (y > n_heap) break;
-                    uint64_t ey = heap[y];
-                    if (y < n_heap) {
-                        const uint64_t e1 = heap[y + 1];
-                        if ((e1 >> 16) < (ey >> 16)) { ++y; ey = e1; }
-                    }
-                    if ((tmp >> 16) < (ey >> 16)) break;
-                    heap[z] = ey;
-                    z = y;
-                }
-                heap[z] = tmp;
-            };
-            for (int i = 1; i <= alpha; ++i) {
-                parent[i] = -1;
-                const uint32_t fr = (uint32_t)f[i - 1];
-                up(++n_heap, ((uint64_t)((fr == 0 ? 1u : fr) << 8) << 16) | (uint32_t)i);
-            }
-            while (n_heap > 1) {
-                const uint64_t e1 = heap[1]; heap[1] = heap[n_heap--]; down(1);
-                const uint64_t e2 = heap[1]; heap[1] = heap[n_heap--]; down(1);
-                ++n_nodes;
-                parent[(int)(e1 & 0xffff)] = parent[(int)(e2 & 0xffff)] = (int16_t)n_nodes;
-                const uint32_t w1 = (uint32_t)(e1 >> 16), w2 = (uint32_t)(e2 >> 16);
-                const uint32_t wt = ((w1 & ~0xffu) + (w2 & ~0xffu)) | (1u + max(w1 & 0xffu, w2 & 0xffu));
-                parent[n_nodes] = -1;
-                up(++n_heap, ((uint64_t)wt << 16) | (uint32_t)n_nodes);
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-        bool too_long = false;
-        for (int i = 1 + lane; i <= alpha; i += kWave) {
-            int j = 0, k = i;
-            while (j < 2 * kHuffAlpha) {                        // (a tree: the bound only keeps a broken one from spinning)
-                const int p = parent[k];
-                if (p < 0) break;
-                k = p;
-                ++j;
-            }
-            L.len[t][i - 1] = (uint8_t)j;
-            too_long |= j > kHuffMaxLen;
-        }
-        if (__ballot(too_long) == 0) break;
-        for (int i = lane; i < alpha; i += kWave) f[i] = 1 + f[i] / 2;
-        __builtin_amdgcn_wave_barrier();
-    }
+    huff_lengths_body<uint32_t, kHuffMaxLen, 2 * kHuffAlpha>(L.w.tree.heap[t], L.w.tree.parent[t], L.u.rfreq[t], L.len[t], alpha, lane);
 }
 
 // syms / nsyms / in_use / off: dq_mtf_hip_many's results and the BLOCK offsets; crcs / origins: one word per block;

@@ -44,6 +44,8 @@
 #include "dq_lzdecode_info.h"
 #include "dq_lzpack_info.h"
 #include "dq_lzselect_info.h"
+#include "dq_lzcode_info.h"
+#include "dq_lzcode_plan.h"
 #include "dq_flags.h"
 #include "dq_work_lists.h"
 #include "dq_block_groups.h"
@@ -761,6 +763,14 @@ int lzpack_many(bool host, const void *phrases, const int64_t *phrase_offsets, i
                 int64_t *blob_offsets, int32_t *status, int32_t device, void *stream);
 int lzunpack_many(bool host, const void *blobs, const int64_t *blob_offsets, int32_t count, void *phrases, int64_t cap,
                   int64_t *phrase_offsets, int64_t *out_len, int32_t *kind, int32_t *status, int32_t device, void *stream);
+
+// DQLZ blobs into entropy-coded DQLE blobs and back (dq_lzcode_host.h, in dq_sufcheck.hip): the bodies of
+// dq_lzcode_hip_many* and dq_lzuncode_hip_many*; dq_lzcode_plan.h has the bound and what the host judges.  host: the
+// buffers are the host's (and stream is not looked at).  Both fill t_lzcode_info (dq_lzcode_info.h); the entry point resets it.
+int lzcode_many(bool host, const void *blobs, const int64_t *blob_offsets, int32_t count, void *coded, int64_t cap, int64_t *coded_offsets,
+                int32_t *status, int32_t device, void *stream);
+int lzuncode_many(bool host, const void *coded, const int64_t *coded_offsets, int32_t count, void *blobs, const int64_t *slot_offsets,
+                  int64_t *out_len, int32_t *status, int32_t device, void *stream);
 
 // The copies worth their tokens (dq_lzselect_host.h, in dq_sufcheck.hip): the body of dq_lzselect_hip_many_*.  host: len,
 // src and the outputs are the host's (and stream is not looked at); offsets and old_sizes are the host's in both forms.

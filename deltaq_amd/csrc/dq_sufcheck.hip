@@ -13,6 +13,7 @@
 #include "dq_rlz_host.h"        // dq_mstat_hip_*, dq_rlz_hip_*, dq_lzparse_hip_*: matching statistics and the relative parse (dq_rlz.h)
 #include "dq_lzdecode_host.h"   // dq_lz77_decode_hip_*, dq_rlz_decode_hip_*: the triples back into bytes (dq_lzdecode.h)
 #include "dq_lzpack_host.h"     // dq_lzpack_hip_many_*, dq_lzunpack_hip_many_*: the triples as DQLZ byte streams (dq_lzpack.h)
+#include "dq_lzcode_host.h"     // dq_lzcode_hip_many*, dq_lzuncode_hip_many*: DQLZ blobs entropy-coded as DQLE blobs (dq_lzcode.h)
 #include "dq_lzselect_host.h"   // dq_lzselect_hip_many_*: the copies worth their tokens, in front of the parse (dq_lzselect.h)
 
 namespace dq {

@@ -1452,6 +1452,143 @@ class HipSuffixSort:
 
     lzunpack = LzUnpack
 
+    # -- DQLZ blobs entropy-coded as DQLE blobs, the layer around them (include/dq_sufsort.h has the format) --------------
+    @staticmethod
+    def _blobs_and_offsets(blobs, offsets, what):
+        """(flat uint8 buffer, host int64 offsets, is_device) of a list of byte strings, or of one buffer / GPU tensor
+        with its offsets."""
+        device = _is_torch_tensor(blobs)
+        if isinstance(blobs, (list, tuple)):
+            if offsets is not None:
+                raise TypeError(f"a list of {what} brings its own offsets: leave the offsets out")
+            if any(_is_torch_tensor(b) for b in blobs):
+                raise TypeError(MIXED_LZ_MESSAGE)
+            parts = [_as_text(b) for b in blobs]
+            if any(b.ndim != 1 for b in parts):
+                raise TypeError(f"every one of the {what} must be one-dimensional")
+            off = np.zeros(len(parts) + 1, dtype=np.int64)
+            if parts:
+                np.cumsum([b.size for b in parts], out=off[1:])
+            return (np.concatenate(parts) if off[-1] else np.zeros(0, np.uint8)), off, False
+        if offsets is None or _is_torch_tensor(offsets):
+            raise TypeError("the offsets must be a host int64 array of count + 1 entries")
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        if off.ndim != 1 or off.size < 1:
+            raise TypeError("the offsets must be a host int64 array of count + 1 entries")
+        if device:
+            import torch
+
+            if blobs.dtype != torch.uint8 or blobs.dim() != 1 or not blobs.is_contiguous():
+                raise TypeError(f"device {what} must be a contiguous 1-D uint8 tensor")
+            if not blobs.is_cuda:
+                raise TypeError("torch tensors must live on the GPU; pass host data as bytes/numpy")
+            B = blobs
+        else:
+            B = _as_text(blobs)
+            if B.ndim != 1:
+                raise TypeError(f"the {what} must be one one-dimensional buffer")
+        if off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != (B.numel() if device else B.size):
+            raise ValueError("the offsets must start at 0, never decrease and end at the number of bytes")
+        return B, off, device
+
+    def LzCodeMany(self, blobs, blob_offsets=None):
+        """DQLZ blobs as entropy-coded DQLE blobs, in ONE native call.  ``blobs``: a list of ``bytes`` (``blob_offsets``
+        left out), which gives a list of ``bytes`` (``dq_lzcode_hip_many``); or one uint8 torch GPU tensor with the host
+        int64 array ``blob_offsets``, which stays on the device on the current torch stream and gives
+        ``(coded_tensor, coded_offsets)`` (``dq_lzcode_hip_many_dev``).  A blob without the frame of DQLZ version 1
+        raises ``ValueError`` naming it.  ``_abi.last_lzcode_info()`` tells what happened."""
+        B, boff, device = self._blobs_and_offsets(blobs, blob_offsets, "blobs")
+        count, total = boff.size - 1, int(boff[-1])
+        if total > INT_MAX:
+            raise ValueError("the coder has 32-bit positions: the blobs together must be shorter than 2^31 bytes")
+        coff, status = np.zeros(count + 1, dtype=np.int64), np.zeros(max(count, 1), dtype=np.int32)
+        cap = lzcode_bound(total, count)
+        if device:
+            import torch
+
+            out = torch.empty(cap, dtype=torch.uint8, device=B.device)
+            dev, stream = _device_and_stream(B)
+            _abi.check(self._lib.dq_lzcode_hip_many_dev(B.data_ptr() if total else None, boff.ctypes.data, count,
+                                                        out.data_ptr() if cap else None, cap, coff.ctypes.data,
+                                                        status.ctypes.data, dev, stream))
+        else:
+            out = np.empty(max(cap, 1), dtype=np.uint8)
+            _abi.check(self._lib.dq_lzcode_hip_many(B.ctypes.data if total else None, boff.ctypes.data, count, out.ctypes.data, cap,
+                                                    coff.ctypes.data, status.ctypes.data, self.device))
+        bad = np.flatnonzero(status[:count])
+        if bad.size:
+            raise ValueError(f"blob {int(bad[0])}: not framed as a DQLZ version 1 blob")
+        if device:
+            return out[:int(coff[-1])], coff
+        return [out[coff[t]:coff[t + 1]].tobytes() for t in range(count)]
+
+    lzcode_many = LzCodeMany
+
+    def LzUncodeMany(self, coded, coded_offsets=None):
+        """DQLE blobs back into their DQLZ blobs, in ONE decoding call: a list of ``bytes`` from a list of ``bytes``, its
+        slots sized from the headers (``dq_lzuncode_hip_many``); ``(blobs_tensor, blob_offsets)`` from a uint8 torch GPU
+        tensor with the host int64 array ``coded_offsets``, its slots sized by a call with empty slots
+        (``dq_lzuncode_hip_many_dev``).  Coded blobs are untrusted: a malformed one raises ``ValueError`` naming it."""
+        C, coff, device = self._blobs_and_offsets(coded, coded_offsets, "coded blobs")
+        count, total = coff.size - 1, int(coff[-1])
+        if total > INT_MAX:
+            raise ValueError("the decoder has 32-bit positions: the coded blobs together must be shorter than 2^31 bytes")
+        soff = np.zeros(count + 1, dtype=np.int64)
+        sizes, status = np.zeros(max(count, 1), dtype=np.int64), np.zeros(max(count, 1), dtype=np.int32)
+        if device:
+            import torch
+
+            fn = self._lib.dq_lzuncode_hip_many_dev
+            dev, stream = _device_and_stream(C)
+            head = (C.data_ptr() if total else None, coff.ctypes.data, count)
+            tail = (sizes.ctypes.data, status.ctypes.data, dev, stream)
+            _abi.check(fn(*head, None, soff.ctypes.data, *tail))                       # empty slots: the sizing call
+            self._raise_malformed_coded(status, count, (-1,))
+            np.cumsum(sizes[:count], out=soff[1:])
+            if soff[-1] > INT_MAX:
+                raise ValueError("the decoder has 32-bit positions: the decoded blobs together must be shorter than 2^31 bytes")
+            out = torch.empty(int(soff[-1]), dtype=torch.uint8, device=C.device)
+            _abi.check(fn(*head, out.data_ptr() if soff[-1] else None, soff.ctypes.data, *tail))
+            self._raise_malformed_coded(status, count, (-1, -2))
+            return out, soff
+        for t in range(count):                                                         # the headers' 32 + c + l, where sane
+            b = C[coff[t]:coff[t + 1]]
+            if b.size >= 40:
+                c, l = (int(v) for v in b[16:32].view("<i8"))
+                if 0 <= c <= INT_MAX and 0 <= l <= INT_MAX:
+                    soff[t + 1] = 32 + c + l
+        np.cumsum(soff, out=soff)
+        if soff[-1] > INT_MAX:
+            raise ValueError("the decoder has 32-bit positions: the decoded blobs together must be shorter than 2^31 bytes")
+        out = np.empty(max(int(soff[-1]), 1), dtype=np.uint8)
+        _abi.check(self._lib.dq_lzuncode_hip_many(C.ctypes.data if total else None, coff.ctypes.data, count, out.ctypes.data,
+                                                  soff.ctypes.data, sizes.ctypes.data, status.ctypes.data, self.device))
+        self._raise_malformed_coded(status, count, (-1, -2))
+        return [out[soff[t]:soff[t] + sizes[t]].tobytes() for t in range(count)]
+
+    lzuncode_many = LzUncodeMany
+
+    @staticmethod
+    def _raise_malformed_coded(status, count, which):
+        bad = np.flatnonzero(np.isin(status[:count], which))
+        if bad.size:
+            raise ValueError(f"blob {int(bad[0])}: malformed DQLE blob")
+
+    def _uncoded(self, blobs):
+        """The list with every blob that begins with b"DQLE" replaced by its DQLZ blob (one LzUncodeMany for all of them);
+        any other blob stays what it is."""
+        blobs = [bytes(b) if isinstance(b, (bytes, bytearray, memoryview)) else _as_text(b).tobytes() for b in blobs]
+        coded = [t for t, b in enumerate(blobs) if b[:4] == b"DQLE"]
+        if coded:
+            try:
+                plain = self.LzUncodeMany([blobs[t] for t in coded])
+            except ValueError as e:
+                k = int(str(e).split(":")[0].split()[1])
+                raise ValueError(f"blob {coded[k]}: malformed DQLE blob") from None
+            for t, b in zip(coded, plain):
+                blobs[t] = b
+        return blobs
+
     # -- the copies worth their tokens, between the match arrays and the parse (include/dq_sufsort.h has the rule) -------
     def LzSelectMany(self, length, src, offsets=None, kind=0, old_sizes=None, min_gain=1):
         """The match arrays of many texts with every copy dropped that is not worth its DQLZ token, in ONE native call:
@@ -1560,11 +1697,14 @@ class HipSuffixSort:
 
     lzselect = LzSelect
 
-    def DeltaCreateMany(self, olds, news, select=False):
+    def DeltaCreateMany(self, olds, news, select=False, entropy=False):
         """A DQLZ delta (kind 1) of every ``news[t]`` against ``olds[t]``: a list of ``bytes``, through ``RlzMany`` and
         ``LzPackMany``.  ``DeltaApplyMany(olds, .)`` turns them back into the new files.  ``select=True`` drops the
         copies that are not worth their tokens: ``MatchStatsMany``, ``LzSelectMany`` (kind 1), ``LzParseMany``,
-        ``LzPackMany``; the blobs are ordinary ones."""
+        ``LzPackMany``; the blobs are ordinary ones.  ``entropy=True`` sends the result through ``LzCodeMany``: DQLE
+        blobs, which ``DeltaApplyMany`` takes as well."""
+        if entropy:
+            return self.LzCodeMany(self.DeltaCreateMany(olds, news, select))
         if not select:
             return self.LzPackMany(self.RlzMany(olds, news), None, 1)
         olds, news = [_as_text(o) for o in olds], [_as_text(w) for w in news]
@@ -1572,8 +1712,8 @@ class HipSuffixSort:
         chosen = self.LzSelectMany([a for a, _ in stats], [b for _, b in stats], None, 1, [o.size for o in olds])
         return self.LzPackMany(self.LzParseMany(news, [a for a, _ in chosen], [b for _, b in chosen]), None, 1)
 
-    def DeltaCreate(self, old, new, select=False) -> bytes:
-        return self.DeltaCreateMany([old], [new], select)[0]
+    def DeltaCreate(self, old, new, select=False, entropy=False) -> bytes:
+        return self.DeltaCreateMany([old], [new], select, entropy)[0]
 
     def DeltaApplyMany(self, olds, deltas):
         """The new files of ``DeltaCreateMany``'s deltas, a list of ``bytes``, through ``LzUnpackMany`` and
@@ -1582,7 +1722,7 @@ class HipSuffixSort:
         olds, deltas = list(olds), list(deltas)
         if len(olds) != len(deltas):
             raise ValueError("DeltaApplyMany takes one old file per delta")
-        P, poff, sizes, kinds = self.LzUnpackMany(deltas)
+        P, poff, sizes, kinds = self.LzUnpackMany(self._uncoded(deltas))     # (DQLE blobs through LzUncodeMany first)
         if (kinds != 1).any():
             raise ValueError(f"blob {int(np.flatnonzero(kinds != 1)[0])}: not a relative (kind 1) blob")
         return self.RlzDecodeMany(olds, None, P, poff, sizes)
@@ -1590,18 +1730,23 @@ class HipSuffixSort:
     def DeltaApply(self, old, delta) -> bytes:
         return self.DeltaApplyMany([old], [delta])[0]
 
-    def Compress(self, text, select=False) -> bytes:
+    def Compress(self, text, select=False, entropy=False) -> bytes:
         """The text as a DQLZ blob of kind 0, through ``Lz77Many`` and ``LzPackMany``; ``select=True``: through
-        ``CompressMany``."""
+        ``CompressMany``; ``entropy=True``: that blob through ``LzCodeMany``, a DQLE blob."""
+        if entropy:
+            return self.LzCodeMany([self.Compress(text, select)])[0]
         if select:
             return self.CompressMany([text], True)[0]
         return self.LzPackMany(self.Lz77Many([text]), None, 0)[0]
 
-    def CompressMany(self, texts, select=True):
+    def CompressMany(self, texts, select=True, entropy=False):
         """Many texts as DQLZ blobs of kind 0, a list of ``bytes``: ``SortMany``, ``LcpMany``, ``LpfMany``,
         ``LzSelectMany`` (the copies worth their tokens), ``LzParseMany``, ``LzPackMany`` -- one native call each for
         all texts.  With ``min_gain`` 1 a blob has at most ``35 + n + n // 128`` bytes.  ``select=False``: the greedy
-        parse, ``Lz77Many`` and ``LzPackMany``.  ``DecompressMany`` turns the blobs back into the texts."""
+        parse, ``Lz77Many`` and ``LzPackMany``.  ``entropy=True`` sends the blobs through ``LzCodeMany``: DQLE blobs, each
+        at most 10 bytes longer than its DQLZ blob.  ``DecompressMany`` turns either kind back into the texts."""
+        if entropy:
+            return self.LzCodeMany(self.CompressMany(texts, select))
         arrs = [_as_text(t) for t in texts]
         if any(a.ndim != 1 for a in arrs):
             raise TypeError("every text must be one-dimensional")
@@ -1620,7 +1765,7 @@ class HipSuffixSort:
     def DecompressMany(self, blobs):
         """The texts of ``CompressMany``'s blobs, a list of ``bytes``, through ``LzUnpackMany`` and ``Lz77DecodeMany``; a
         blob of kind 1 or a malformed one raises ``ValueError``."""
-        P, poff, sizes, kinds = self.LzUnpackMany(list(blobs))
+        P, poff, sizes, kinds = self.LzUnpackMany(self._uncoded(blobs))      # (DQLE blobs through LzUncodeMany first)
         if (kinds != 0).any():
             raise ValueError(f"blob {int(np.flatnonzero(kinds != 0)[0])}: not an LZ77 (kind 0) blob")
         return self.Lz77DecodeMany(P, poff, sizes)
@@ -1630,7 +1775,7 @@ class HipSuffixSort:
     def Decompress(self, blob) -> bytes:
         """The text of ``Compress``'s blob, through ``LzUnpackMany`` and ``Lz77DecodeMany``; a blob of kind 1 or a
         malformed one raises ``ValueError``."""
-        P, poff, sizes, kinds = self.LzUnpackMany([blob])
+        P, poff, sizes, kinds = self.LzUnpackMany(self._uncoded([blob]))
         if (kinds != 0).any():
             raise ValueError("blob 0: not an LZ77 (kind 0) blob")
         return self.Lz77DecodeMany(P, poff, sizes)[0]
@@ -1960,6 +2105,14 @@ def lzpack_bound(z: int, count: int) -> int:
     bound = _abi.load().dq_lzpack_bound(z, count)
     if bound < 0:
         raise ValueError("lzpack_bound: negative arguments or a bound beyond 64 bits")
+    return bound
+
+
+def lzcode_bound(nbytes: int, count: int) -> int:
+    """Bytes that hold the DQLE blobs of any ``count`` DQLZ blobs of ``nbytes`` bytes together (``dq_lzcode_bound``)."""
+    bound = _abi.load().dq_lzcode_bound(nbytes, count)
+    if bound < 0:
+        raise ValueError("lzcode_bound: negative arguments or a bound beyond 64 bits")
     return bound
 
 

@@ -1087,7 +1087,8 @@ int32_t dq_lzdecode_last_info(int64_t *info, int32_t count);
  * the input and of min(cap, the bound) bytes of output.  No chunking and no CPU fallback: DQ_ERR_OOM where that does not
  * fit.  The _dev_ forms take device pointers on `device`, enqueue on `stream` (NULL = the library's stream) and return
  * after it has drained.  One stream wait per call.
- * Out of scope: entropy coding of the two streams, int64 forms, chunking of host-form calls.
+ * Out of scope: int64 forms, chunking of host-form calls.  Entropy coding of the two streams is the layer around the blobs,
+ * dq_lzcode_hip_many* below.
  * dq_lzpack_last_info: shape of the last of these calls on this thread, reset when one starts; `count` entries (7 are
  * defined, further ones read 0; a NULL array is DQ_ERR_BAD_ARGS): [0] texts with status 0; [1] texts with status -1;
  * [2] tokens, [3] control bytes and [4] literal bytes of the texts with status 0; [5] kernel launches; [6] stream waits. */
@@ -1104,6 +1105,89 @@ int32_t dq_lzunpack_hip_many_dev_i32(const void *d_blobs, const int64_t *blob_of
                                      void *d_phrases, int64_t cap, int64_t *phrase_offsets,
                                      int64_t *out_len, int32_t *kind, int32_t *status, int32_t device, void *stream);
 int32_t dq_lzpack_last_info(int64_t *info, int32_t count);
+
+/* ---- DQLZ blobs, entropy-coded: DQLE blobs of many DQLZ blobs per call ------------------------------------------------
+ * A layer AROUND DQLZ version 1 with a magic of its own: dq_lzpack_* / dq_lzunpack_* and DQLZ stay exactly as they are.
+ * The encoder takes finished DQLZ blobs and writes DQLE blobs, the decoder takes DQLE blobs and writes DQLZ blobs; whether
+ * a decoded blob is a well-formed phrase list remains dq_lzunpack_*'s verdict.  tests/lzcode_model.py is the format in
+ * Python.  DQLE version 1: a coded blob has 40 + cc + lc bytes:
+ *   0..3 'D' 'Q' 'L' 'E';  4 version = 1;  5..31 bytes 5..31 of the DQLZ header, verbatim (kind, two zero bytes, n, c, l);
+ *   32..39 cc, the bytes of the coded control section, int64 LE (lc is the rest of the blob);  then the control section
+ *   (cc bytes) and the literal section (lc bytes).
+ * A section codes a stream of m bytes, m = c or l of the header.  Its first byte is the mode:
+ *   mode 0, stored:  the m bytes follow; 1 + m bytes.
+ *   mode 2, run:     one byte follows, and the stream is that byte m times; 2 bytes; needs m >= 1.
+ *   mode 1, Huffman: needs m >= 1.  Behind the mode byte, in order: 32 bytes of in-use map (byte value s is used iff bit
+ *     s & 7 of map byte s >> 3 is set; alpha = the used values, alpha >= 2);  ceil(alpha / 2) bytes of code lengths of the
+ *     used values in increasing byte order, 4 bits each, the first in the high nibble, each 1..12, an unused last nibble 0;
+ *     k = ceil(m / 256) chunk entries, uint16 LE: the code bits of each chunk of 256 symbols (the last chunk has
+ *     m - 256 (k - 1) symbols);  ceil(B / 8) bytes of code bits, B = the sum of the entries: the chunks follow one another
+ *     without alignment, bits go most significant first within a byte, the pad bits of the last byte are 0.  Codes are
+ *     canonical: they ascend by (length, byte value), the first code is 0, a code is written most significant bit first.
+ * The encoder's lengths are libbz2's hbMakeCodeLengths on the used values' exact counts with a limit of 12: a weight is
+ * count << 8 with the depth in the low 8 bits (40 + 8 bits: a stream may have 2^31-1 bytes), ties are broken as the heap
+ * breaks them, and while a length exceeds 12 every count becomes 1 + count / 2 and the tree is rebuilt -- the rule of
+ * dq_huff_hip_many with another limit (one body on the device: deltaq_amd/csrc/dq_huff_lengths.h).  Such a code is
+ * complete: the sum of 2^(12 - len) is 4096.
+ * The encoder's choice, which fixes the bytes it writes: run iff m >= 2 and one value is used; otherwise Huffman iff
+ * alpha >= 2 and the Huffman section is strictly shorter than 1 + m; otherwise stored.  A coded blob therefore has at most
+ * 10 bytes more than its DQLZ blob: dq_lzcode_bound(bytes, count) = bytes + 10 * count; -1 on negative arguments or
+ * overflow.
+ *   "abracadabra" six times, 66 bytes: counts a 30, b 12, c 6, d 6, r 12, lengths 1 3 3 3 3; the section has 56 bytes:
+ *   01; the map with byte 12 = 1e and byte 14 = 04; the lengths 13 33 30; the entry 8a 00 (138 bits); 18 bytes of bits
+ *   beginning 4e ac 9c 9d.
+ *   The DQLE blob of "abababb" (above) has 40 + 10 + 3 bytes, both sections stored.
+ * A coded blob is well-formed iff: magic and version are as above; c and l lie in [0, 2^31-1]; 0 <= cc <= size - 40; every
+ * section has mode 0, 1 or 2 and exactly the size its mode and m give; and a Huffman section has alpha >= 2, every nibble
+ * in 1..12 and a zero pad nibble, a Kraft sum of exactly 4096, every chunk decoding its symbols in exactly its entry's
+ * bits, and zero pad bits.  This is local and checkable per chunk; it does NOT verify the encoder's choice, so several
+ * coded blobs may decode to one DQLZ blob.
+ * Encode.  Blob t is blobs[blob_offsets[t] .. blob_offsets[t + 1]).  The input needs only its frame: 'DQLZ', version 1,
+ * c, l >= 0 and 32 + c + l equal to the blob's size; otherwise status[t] = -1 and the coded blob has 0 bytes.
+ * coded_offsets[0 .. count] always receives the true prefix sums of the coded sizes; the coded blobs are written back to
+ * back iff coded_offsets[count] <= cap, otherwise nothing is written, and the call returns DQ_OK either way: cap == 0 with
+ * coded == NULL is the sizing call.  Nothing outside coded[0 .. coded_offsets[count]) is written.
+ * Decode.  Coded blob t is coded[coded_offsets[t] .. coded_offsets[t + 1]); its DQLZ blob goes to slot t,
+ * blobs[slot_offsets[t] .. slot_offsets[t + 1]) (the slot convention of dq_*_decode_hip_many_*).  status[t]: 0 ok, with
+ * out_len[t] = 32 + c + l bytes from the slot's start;  -1 malformed, out_len[t] = 0, the slot's contents unspecified;
+ * -2 the slot is too small: out_len[t] = 32 + c + l is the true size, nothing is decoded and nothing is written to the slot
+ * (decided from the header and the two mode bytes alone: a blob whose header or section sizes fail is -1 first, one whose
+ * Huffman body is wrong may be -2), so a call with empty slots is the cheap sizing call.  Coded blobs are untrusted: a
+ * malformed one is its own verdict, never a failed call and never an address, and no byte outside a blob's own slot is
+ * written.
+ * Every offsets array, out_len and status is a HOST pointer in both forms.
+ *   negative count or cap; a NULL buffer that is needed (the host arrays always; the input where it has a byte; the output
+ *   where cap > 0 / where the slots have a byte); offsets[0] != 0; decreasing offsets                  DQ_ERR_BAD_ARGS
+ *   more than 2^31-1 input bytes or slot bytes, or more than 2^30 blobs, in the call                    DQ_ERR_TOO_LARGE
+ * -- all decided before a device is looked for (deltaq_amd/csrc/dq_lzcode_plan.h), and the outputs stay untouched.
+ * count == 0 returns DQ_OK without a device; so does a decode call without a coded byte (every status -1).
+ * Computed flat over the call's 2 * count streams and their chunks (deltaq_amd/csrc/dq_lzcode.h); every count is a prefix
+ * sum of dq_lzpack's scan, so nobody waits for anybody and the launches are constants (lzcode_launches,
+ * lzuncode_launches): 11 for an encode call, 10 for a decode call, whatever the blobs and however many.  Device memory,
+ * carved from the cached workspace of the slot the call leases: about 3.5 KiB per blob and 1/16 byte per input byte for an
+ * encode call, 150 bytes per blob and half a byte per coded byte for a decode call; the host forms add their copies of the
+ * input and the output.  The decoder keeps no table in device memory: a work item builds its 8 KiB table in LDS.  The
+ * _dev forms take device pointers on `device`, enqueue on `stream` (NULL = the library's stream) and return after it has
+ * drained.  One stream wait per call.  No chunking and no CPU fallback: DQ_ERR_OOM where the scratch does not fit.
+ * Out of scope: a split of the control stream by varint role, an adaptive or order-1 model, several tables per stream,
+ * int64 forms, chunking of host-form calls, the framed bsdiff calls.
+ * dq_lzcode_last_info: shape of the last of these calls on this thread, reset when one starts; `count` entries (11 are
+ * defined, further ones read 0; a NULL array is DQ_ERR_BAD_ARGS): [0] blobs with status 0; [1] with status -1; [2] with
+ * status -2; [3] stored, [4] run and [5] Huffman sections of the blobs with status 0; [6] input bytes; [7] output bytes
+ * of the blobs with status 0; [8] trees rebuilt (encode); [9] kernel launches; [10] stream waits. */
+int64_t dq_lzcode_bound(int64_t bytes, int32_t count);
+int32_t dq_lzcode_hip_many(const uint8_t *blobs, const int64_t *blob_offsets, int32_t count,
+                           uint8_t *coded, int64_t cap, int64_t *coded_offsets, int32_t *status, int32_t device);
+int32_t dq_lzcode_hip_many_dev(const void *d_blobs, const int64_t *blob_offsets, int32_t count,
+                               void *d_coded, int64_t cap, int64_t *coded_offsets, int32_t *status,
+                               int32_t device, void *stream);
+int32_t dq_lzuncode_hip_many(const uint8_t *coded, const int64_t *coded_offsets, int32_t count,
+                             uint8_t *blobs, const int64_t *slot_offsets, int64_t *out_len, int32_t *status,
+                             int32_t device);
+int32_t dq_lzuncode_hip_many_dev(const void *d_coded, const int64_t *coded_offsets, int32_t count,
+                                 void *d_blobs, const int64_t *slot_offsets, int64_t *out_len, int32_t *status,
+                                 int32_t device, void *stream);
+int32_t dq_lzcode_last_info(int64_t *info, int32_t count);
 
 /* ---- the copies worth their tokens: a selection between the match arrays and the parse ------------------------------
  * The greedy parse makes a copy of every match of one byte and more, and a copy is a DQLZ token of three bytes at least:

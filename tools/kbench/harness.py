@@ -87,6 +87,10 @@ PROTOTYPES = {                                               # export -> (restyp
     "dq_lzpack_hip_many_dev_i32": (_i32, [_vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _i32, _vp]),
     "dq_lzunpack_hip_many_dev_i32": (_i32, [_vp, _vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _vp]),
     "dq_lzpack_last_info": _INFO,
+    "dq_lzcode_bound": (_i64, [_i64, _i32]),
+    "dq_lzcode_hip_many_dev": (_i32, [_vp, _vp, _i32, _vp, _i64, _vp, _vp, _i32, _vp]),
+    "dq_lzuncode_hip_many_dev": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "dq_lzcode_last_info": _INFO,
     "dq_lzselect_hip_many_dev_i32": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _vp]),
     "dq_lzselect_last_info": _INFO,
 }

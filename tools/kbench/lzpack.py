@@ -29,14 +29,11 @@ INFO = "dq_lzpack_last_info"
 KEYS = ("texts_ok", "texts_refused", "tokens", "ctrl_bytes", "literal_bytes", "launches", "stream_waits")
 
 
-def worker(name, lib_path, calls):
+def prepare(name, L, check):
+    """The set on the device, packed once and unpacked back (compared): the record so far and the three calls, and for
+    tools/kbench/lzcode.py, which codes the same blobs, the blobs and their offsets."""
     import numpy as np
     import torch
-    L = harness.load_library(lib_path)
-
-    def check(rc, what):
-        if rc != 0:
-            raise RuntimeError(f"{what} failed ({rc}): {L.dq_last_error()}")
 
     z = ctypes.c_int64(0)
     extra = {}
@@ -109,6 +106,17 @@ def worker(name, lib_path, calls):
     rec = {"texts": texts, "bytes": total, "phrases": cap, "blob_bytes": room, "blob_bytes_over_text_bytes": room / max(total, 1), **extra}
     rec["equals_the_input"] = True
     rec["last_call_info"] = info
+    return rec, pack, unpack, produce, made_by, dBlobs, boff
+
+
+def worker(name, lib_path, calls):
+    L = harness.load_library(lib_path)
+
+    def check(rc, what):
+        if rc != 0:
+            raise RuntimeError(f"{what} failed ({rc}): {L.dq_last_error()}")
+
+    rec, pack, unpack, produce, made_by, _, _ = prepare(name, L, check)
     rec["pack"] = harness.timed(pack, calls, 1)
     rec["unpack"] = harness.timed(unpack, calls, 1)
     rec["made_by"] = made_by
